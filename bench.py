@@ -19,7 +19,13 @@ N = 30 379 source; committed data fixtures, tests/golden/*.f32), distance transf
   value  = cube bounds evaluated by all ranks / wall time of the K timed steps (max over ranks).
 The headline batch is SIBLING-STRUCTURED (8 children per expansion, as the search produces them); SURVEY 8(d)'s literal
 microbench -- 65 536 unrelated cubes -- is `generic_path` / `roofline.frac_generic`, about half that rate.
-Also reported: `sustained` (the same step for >= 8 s: mean and slowest-window rate), `s2` (the HBM-bound configuration,
+
+A plain run does only what the headline needs: set-up, the untimed prewarm + W warm-up steps, the K timed steps, and the line
+(metric, value, unit, ms_per_step, ...).  `--dump-outputs DIR` then writes what the last timed step computed -- the upper and lower
+bounds of the batch and its best upper bound, float32 -- as DIR/ub.npy, DIR/lb.npy, DIR/best_ub.npy (rank r > 0: *_rank<r>.npy);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+Only with `--full` does the line also report: `value_repeats` (four more timed regions of K steps),
+`sustained` (the same step for >= 8 s: mean and slowest-window rate), `s2` (the HBM-bound configuration,
 N = M = 1 M, DT 512^3: three launches and its HBM roofline from the committed PMC traffic), ICP iterations/s (NN + sums + SVD update, host round trip included), an end-to-end
 registration of the same clouds (exact cube-bound count / wall time), the roofline of the dominant
 kernel (HIP events on the launch stream) and the CPU baseline timed on the host cores: the reference's own
@@ -265,8 +271,11 @@ def spawn_ranks(n, backend):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step = their wall time / this")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also run every other leg (repeats, sustained, ICP, roofline and probes, host-pointer "
+                                                           "path, end-to-end registrations, CPU baselines, S2, sharded legs); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (ub, lb, best_ub; float32 .npy) to DIR")
     ap.add_argument("--prewarm", type=int, default=30, help="untimed setup steps before the W warm-up steps (GPU clock ramp); reported as setup_prewarm_steps")
     ap.add_argument("--expansions", type=int, default=8192, help="BnB expansions (x8 cubes) per step per GPU")
     ap.add_argument("--sustain-s", type=float, default=8.0, help="length of the sustained leg, seconds (0 = skip); long enough for a 5-second SMI sampler to see the GPU busy")
@@ -295,6 +304,8 @@ def main():
     ap.add_argument("--deep-mse", type=float, default=3e-5, help="mse threshold of the deep strong-scaling leg (bunny; below the optimum's error: the search has to PROVE the optimum, 6.7 s on one GPU); 0 = skip")
     ap.add_argument("--e2e-repeats", type=int, default=5, help="registrations of the end-to-end leg (min / median / spread reported)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.prewarm < 0:
+        ap.error("--steps must be >= 1, --warmup and --prewarm >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly: be the launcher.  Nothing above or in spawn_ranks initialises the GPU; the ranks are children, not re-executions
@@ -399,9 +410,28 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     value = world * Bc * args.steps / elapsed
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the batch's bounds and its best upper bound (all-reduced over the ranks when N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if rank == 0 else "_rank%d" % rank
+        keep = slice(None)
+        if Bc > (1 << 22):           # 64 MB in all: a fixed, seeded sample of 4 M cubes of a larger batch
+            keep = np.sort(np.random.default_rng(0).choice(Bc, 1 << 22, replace=False))
+        for name, t, sel in (("ub", d_ub, keep), ("lb", d_lb, keep), ("best_ub", best2[(nstep[0] - 1) & 1], slice(None))):
+            np.save(os.path.join(args.dump_outputs, name + sfx + ".npy"), t.cpu().numpy()[sel].astype(np.float32))
+    out = None
+    if rank == 0:
+        out = {"metric": "bnb_cube_bounds_per_s", "value": round(value, 1), "unit": "cube-bounds/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "setup_prewarm_steps": args.prewarm, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+               "data": ("Stanford-bunny clouds named by the reference's bunny_goicp.toml (committed fixture)" if args.workload == "bunny" else "synthetic clouds (cuda-go-icp_amd/synth.py)") + " + synthetic cube batch",
+               "config": {"workload": "%s: N=%d source, M=%d target, DT %d^3, subsample 1.0" % (wname, N, M, V),
+                          "cubes_per_step_per_gpu": Bc, "lb_pass_fraction": n_lb / Bc, "rotations_per_step": 8,
+                          "dt_layout": "bricked4x4x4" if args.dt_layout else "linear", "exchange": "all_reduce(MIN) of the batch's best ub per step, running beside the next step's kernel, all complete inside the timed region" if world > 1 else "local min"}}
+    # ---- everything below is --full only ----
     # run-to-run spread: four more timed regions of the same K steps (reported beside `value`, never instead of it)
     repeats = []
-    for _ in range(4):
+    for _ in range(4 if args.full else 0):
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -421,7 +451,7 @@ def main():
     # for an SMI sampler to see the GPU busy).  The window count comes from the MAX-reduced timing above, so every rank runs
     # the same number of steps (the step holds a collective when N > 1).
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         wsteps = 100
         nwin = max(3, int(np.ceil(args.sustain_s / (wsteps * elapsed / args.steps))))
         rates = []
@@ -443,7 +473,7 @@ def main():
 
     # ---- ICP iterations/s: the loop does not shard, so N GPUs run N replicas side by side ----
     icp = None
-    if not args.no_icp:
+    if args.full and not args.no_icp:
         ms = C.c_float()
         Ri, ti = np.eye(3, dtype=np.float32).reshape(9).copy(), np.zeros(3, np.float32)
         err, it = C.c_float(), C.c_int32()
@@ -485,8 +515,7 @@ def main():
                                        "hbm_frac": None if tr is None else round(tr / (ms.value * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "pmc_reading": pj.get("reading")})
             icp["roofline_nn"].update(prov)
 
-    out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: HIP events on the launch stream, live ----
         ms = C.c_float()
         B.check(lib.goicp_time_bounds_device(h, d_rots.data_ptr(), d_cubes.data_ptr(), Bc, d_ub.data_ptr(), d_lb.data_ptr(), 10, C.byref(ms)))
@@ -665,24 +694,17 @@ def main():
             else:
                 cpu = {"value": port["port_value"], "unit": "cube-bounds/s", "cores": 1, "kind": "port", "sample": port["port_sample"]}
             cpu.update(port)
-        out = {"metric": "bnb_cube_bounds_per_s", "value": round(value, 1), "unit": "cube-bounds/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "setup_prewarm_steps": args.prewarm, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-               "data": ("Stanford-bunny clouds named by the reference's bunny_goicp.toml (committed fixture)" if args.workload == "bunny" else "synthetic clouds (cuda-go-icp_amd/synth.py)") + " + synthetic cube batch",
-               "config": {"workload": "%s: N=%d source, M=%d target, DT %d^3, subsample 1.0" % (wname, N, M, V),
-                          "cubes_per_step_per_gpu": Bc, "lb_pass_fraction": n_lb / Bc, "rotations_per_step": 8,
-                          "dt_layout": "bricked4x4x4" if args.dt_layout else "linear", "exchange": "all_reduce(MIN) of the batch's best ub per step, running beside the next step's kernel, all complete inside the timed region" if world > 1 else "local min"},
-               "value_repeats": {"n": len(repeats), "min": round(min(repeats), 1), "max": round(max(repeats), 1),
-                                 "spread_pct": round(100 * (max(repeats) - min(repeats)) / value, 2)},
-               "sustained": sustained,
-               "roofline": roofline, "generic_path": generic, "cpu_baseline": cpu, "icp": icp, "e2e": e2e, "e2e_deep": e2e_deep, "e2e_sharded": None}
+        out.update({"value_repeats": {"n": len(repeats), "min": round(min(repeats), 1), "max": round(max(repeats), 1),
+                                      "spread_pct": round(100 * (max(repeats) - min(repeats)) / value, 2)},
+                    "sustained": sustained,
+                    "roofline": roofline, "generic_path": generic, "cpu_baseline": cpu, "icp": icp, "e2e": e2e, "e2e_deep": e2e_deep, "e2e_sharded": None})
     reg.close()
     del d_rots, d_cubes, d_ub, d_lb
 
     # ---- the HBM-bound configuration (BASELINE configs[4] per GPU: N = M = 1 M, DT 512^3 = 537 MB, beyond the Infinity Cache):
     # a few launches of the same 65 536-cube batch, and the HBM roofline of that launch = fabric-side bytes (PMC, committed
     # profile of this same batch) / the launch time measured HERE / 8 TB/s
-    if rank == 0 and args.workload == "bunny" and args.s2_steps > 0:
+    if rank == 0 and args.full and args.workload == "bunny" and args.s2_steps > 0:
         try:
             out["s2"] = s2_leg(pkg, B, lib, args, dev, torch)
         except Exception as e:      # reported, never fatal for the headline line
@@ -699,7 +721,7 @@ def main():
     #            are measured, not quoted.
     sharded_res = None
     sharded_failed = False
-    if world > 1 and not args.no_sharded:
+    if world > 1 and args.full and not args.no_sharded:
         box = {}
 
         def sharded_leg():
@@ -835,7 +857,8 @@ def main():
             sharded_failed = bool(box.get('failed'))
 
     if rank == 0:
-        out["e2e_sharded"] = sharded_res
+        if args.full:
+            out["e2e_sharded"] = sharded_res
         def _clean(o):                      # NaN (a leg that was switched off) is not JSON: null instead
             if isinstance(o, float) and o != o:
                 return None

@@ -6,12 +6,15 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <queue>
 #include <random>
 #include <thread>
 #include <vector>
+
+#include <unistd.h>
 
 #include "comm.hpp"
 #include "config_io.hpp"
@@ -255,8 +258,13 @@ int main()
 	}
 	// ---- config / cloud IO ----
 	{
-		const char* toml = "/tmp/goicp_selftest.toml";
-		const char* txt = "/tmp/goicp_selftest.txt";
+		// a directory of this run's own: fixed names under /tmp collide with another user's (or run's) files
+		const char* tmpdir = std::getenv("TMPDIR");
+		std::string dir = std::string(tmpdir && *tmpdir ? tmpdir : "/tmp") + "/goicp_selftest_XXXXXX";
+		CHECK(mkdtemp(&dir[0]) != nullptr);
+		const std::string toml_s = dir + "/c.toml", txt_s = dir + "/c.txt", ply_s = dir + "/c.ply", missing_s = dir + "/does_not_exist.ply";
+		const char* toml = toml_s.c_str();
+		const char* txt = txt_s.c_str();
 		{ std::ofstream f(txt); f << "3\n0 0 0\n1 2 3\n-1 0.5 2\n"; }
 		{ std::ofstream f(toml); f << "[info]\ndescription = \"x\"\n[io]\ntarget = \"" << txt << "\"\nsource = \"" << txt << "\"\n[params]\nmode = 4\nmse_threshold = 1e-3\n[params.rotation]\nxmin = -90\nxmax = 90\n"; }
 		goicp_config c;
@@ -266,12 +274,14 @@ int main()
 		goicp::load_cloud(txt, 1.0f, 2.0f, 1, cloud);
 		CHECK(cloud.size() == 9 && cloud[3] == 2.f);
 		bool threw = false;
-		try { goicp::load_cloud("/tmp/does_not_exist.ply", 1.f, 1.f, 1, cloud); } catch (const goicp::IoError&) { threw = true; }
+		try { goicp::load_cloud(missing_s, 1.f, 1.f, 1, cloud); } catch (const goicp::IoError&) { threw = true; }
 		CHECK(threw);
-		goicp::write_viz_ply("/tmp/goicp_selftest.ply", cloud.data(), 3, cloud.data(), 3);
+		goicp::write_viz_ply(ply_s, cloud.data(), 3, cloud.data(), 3);
 		std::vector<float> back;
-		goicp::load_cloud("/tmp/goicp_selftest.ply", 1.f, 1.f, 1, back);
+		goicp::load_cloud(ply_s, 1.f, 1.f, 1, back);
 		CHECK(back.size() == 18);
+		for (const std::string& f : {toml_s, txt_s, ply_s}) std::remove(f.c_str());
+		rmdir(dir.c_str());
 	}
 	std::printf("host selftest: %s\n", g_fail ? "FAILED" : "ok");
 	return g_fail ? 1 : 0;

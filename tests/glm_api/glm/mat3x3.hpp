@@ -1,0 +1,2 @@
+// glm/mat3x3.hpp of the stand-in (glm.hpp holds the whole interface)
+#include "glm.hpp"

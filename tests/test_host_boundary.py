@@ -82,17 +82,40 @@ def test_config_parse_defaults_and_clamps(pkg, tmp_path):
     assert c.description == "Register data # not a comment"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/test"), reason="the reference checkout only exists in the build container")
-def test_reference_configs_parse(pkg):
-    """The reference's five configs (test/*.toml, e.g. test/skull_goicp.toml:16-41) go through goicp_config_load unchanged and
-    give the values of the committed expectation table (tests/golden/reference_configs.json, written from reading the files):
-    [io] paths, [params] mode / trim / subsample / mse_threshold / resize, [visualization], and the [params.rotation] /
-    [params.translation] / search_depth keys the reference declares but never parses (src/common.h:157-169)."""
+def _reference_style_toml(want):
+    """A config in the layout of the reference's test/*.toml (header comment, [info] with an authors array, quoted [io] paths and
+    [params] values with trailing comments, the optional [params.rotation] / [params.translation] tables, [visualization]),
+    holding the values of one entry of tests/golden/reference_configs.json."""
+    q = lambda s: '"%s"' % s
+    b = lambda v: "true" if v else "false"
+    lines = ["# Example configuration (reference layout)", "", "[info]", 'authors = ["A. Author",', '           "B. Author"]',
+             'version = "0.1"', "description = %s" % q(want["description"]), "", "[io]",
+             "target = %s    # target (reference) point cloud" % q(want["target"]), "source = %s     # source point cloud" % q(want["source"]),
+             "output = %s                      # output file: R, t, MSE" % q(want["output"]),
+             "visualization = %s                   # set to \"\" to skip" % q(want["visualization"]), "", "[params]",
+             "mode = %d                                  # 0..4" % want["mode"], "trim = %s" % b(want["trim"]),
+             "subsample = %r                             # subsample the source point cloud" % want["subsample"],
+             "mse_threshold = %r" % want["mse_threshold"], "resize = %r" % want["resize"]]
+    for key in ("rotation", "translation"):
+        if want[key + "_present"]:
+            r = want[key]
+            lines += ["", "[params.%s]" % key] + ["%s = %r" % (k, v) for k, v in zip(("xmin", "xmax", "ymin", "ymax", "zmin", "zmax"), r[:6])]
+            lines += ["search_depth = %d" % r[6]]
+    lines += ["", "[visualization]", "theta = %r" % want["theta"], "phi = %r" % want["phi"], "spin_after_finish = %s" % b(want["spin_after_finish"]), ""]
+    return "\n".join(lines)
+
+
+def test_reference_configs_parse(pkg, tmp_path):
+    """The reference's five configs (test/*.toml, e.g. test/skull_goicp.toml:16-41), restated in their layout from the committed
+    expectation table (tests/golden/reference_configs.json, written from reading the files), go through goicp_config_load and
+    give the table's values: [io] paths, [params] mode / trim / subsample / mse_threshold / resize, [visualization], and the
+    [params.rotation] / [params.translation] / search_depth keys the reference declares but never parses (src/common.h:157-169)."""
     import json
     table = json.load(open(os.path.join(GOLDEN, "reference_configs.json")))
-    assert sorted(table) == sorted(n for n in os.listdir("/root/reference/test") if n.endswith(".toml"))
+    assert sorted(table) == ["bunny_goicp.toml", "bunny_icp.toml", "face_goicp.toml", "skull_goicp.toml", "spanner_goicp.toml"]
     for name, want in table.items():
-        c = pkg.Config(os.path.join("/root/reference/test", name))
+        (tmp_path / name).write_text(_reference_style_toml(want))
+        c = pkg.Config(tmp_path / name)
         assert (c.mode, bool(c.trim), c.description) == (want["mode"], want["trim"], want["description"]), name
         for k in ("subsample", "mse_threshold", "resize"):
             assert getattr(c, k) == pytest.approx(want[k], rel=1e-6), (name, k)
@@ -197,7 +220,19 @@ def test_rodrigues_host_helper_matches_oracle(pkg, oracle_mod):
 # C++ shim (include/goicp_mi355.hpp): the reference's call sites compile against it
 # ----------------------------------------------------------------------------------------------
 SHIM_TU = os.path.join(ROOT, "tests", "shim_callsites.cpp")
-REF_GLM = "/root/reference/external/include"
+
+
+GLM_API = os.path.join(ROOT, "tests", "glm_api")     # stand-in for glm 0.9.6's vec3 / mat3 interface, used when no glm is found
+
+
+def _glm_include_flags():
+    """-I flags for glm: a real glm (GLM_INCLUDE_DIR, else the compiler's own search path) when `#include <glm/glm.hpp>`
+    compiles with it, else the stand-in under tests/glm_api."""
+    import subprocess
+    extra = ["-I", os.environ["GLM_INCLUDE_DIR"]] if os.environ.get("GLM_INCLUDE_DIR") else []
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-x", "c++"] + extra + ["-"], input="#include <glm/glm.hpp>\n",
+                       capture_output=True, text=True)
+    return extra if r.returncode == 0 else ["-I", GLM_API]
 
 
 def _syntax_only(extra):
@@ -212,14 +247,15 @@ def test_shim_compiles_without_glm():
     _syntax_only([])
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_GLM, "glm")), reason="the reference's vendored glm is only in the build container")
 def test_shim_compiles_against_reference_glm():
     """SURVEY 8(b): the call shapes of src/main.cpp:94,150 (FastGoICP construction from std::vector<glm::vec3>, worker
     thread on &FastGoICP::run), src/goicp_kernel.cu:161-177 (the viewer's locked read of optR/optT/curR/curT/finished/
     get_best_error with glm::mat3 / glm::vec3 on the other side), src/icp_kernel.h:9-13 / src/goicp_kernel.h:6-10 (the
-    step API) and src/fgoicp/registration.hpp:96-97, icp3d.hpp:30-35 (the operators) compile against the shim with the
-    reference's own vendored glm."""
-    _syntax_only(["-DSHIM_WITH_GLM", "-I", REF_GLM])
+    step API) and src/fgoicp/registration.hpp:96-97, icp3d.hpp:30-35 (the operators) compile against the shim with glm types
+    on the caller's side: the glm the reference vendors (0.9.6) when one is installed or named by GLM_INCLUDE_DIR, else the
+    stand-in tests/glm_api with that version's vec3 / mat3 interface.  Either way the shim takes its glm branch (Mat3 / Vec3 ARE
+    glm::mat3 / glm::vec3), so `prev_optR = f->optR` only compiles if that branch holds."""
+    _syntax_only(["-DSHIM_WITH_GLM"] + _glm_include_flags())
 
 
 def test_shim_matrix_layout_roundtrip(tmp_path):

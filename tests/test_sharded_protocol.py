@@ -238,7 +238,7 @@ def test_bench_plain_launch_two_ranks_gloo():
     n_gpus 2, the sharded legs present and error-free, the deep leg reaching the world-1 optimum with its work inflation reported."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--prewarm", "2",
-                        "--sustain-s", "0", "--s2-steps", "0", "--no-cpu", "--no-probe", "--e2e-repeats", "1", "--deep-mse", "1e-4"],
+                        "--full", "--sustain-s", "0", "--s2-steps", "0", "--no-cpu", "--no-probe", "--e2e-repeats", "1", "--deep-mse", "1e-4"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -268,7 +268,7 @@ def test_bench_single_gpu_line_contract():
     whose `achieved` is the line's own launch time turned into look-ups/s, the default registration (`e2e`) inside the tolerance against the reference's
     optimum, and the prove-the-optimum registration (`e2e_deep`, here at mse 1e-4) consistent with its own counters."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm", "2", "--sustain-s", "0", "--s2-steps", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm", "2", "--full", "--sustain-s", "0", "--s2-steps", "0",
                         "--no-cpu", "--e2e-repeats", "1", "--deep-mse", "1e-4"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -289,3 +289,33 @@ def test_bench_single_gpu_line_contract():
     d = j["e2e_deep"]
     assert d["sse"] > d["sse_threshold"] and d["rot_pops"] > 900 and abs(d["cube_bounds_per_s"] - d["cube_bounds"] / d["register_s"]) <= 0.01 * d["cube_bounds_per_s"]
     assert d["sse"] <= e["sse"] + 1e-6                                               # the deeper search cannot end worse
+
+
+def test_bench_rejects_zero_steps():
+    """`--steps` sets the number of timed steps and `ms_per_step` divides by it: 0 is refused before anything starts."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--warmup", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python3 bench.py` is the headline alone: ONE JSON line with the contract's keys and none of the --full legs, and
+    `--dump-outputs DIR` writes the last timed step's bounds (float32, one per cube) and their minimum, the step's best upper bound."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in j, k
+    for k in ("value_repeats", "sustained", "roofline", "cpu_baseline", "icp", "e2e", "e2e_deep", "s2", "e2e_sharded"):
+        assert k not in j, k
+    assert j["steps"] == 5 and j["metric"] == "bnb_cube_bounds_per_s" and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert abs(j["value"] - j["config"]["cubes_per_step_per_gpu"] * 5 / (j["ms_per_step"] * 5e-3)) <= 0.01 * j["value"]
+    ub, lb, best = (np.load(tmp_path / (n + ".npy")) for n in ("ub", "lb", "best_ub"))
+    Bc = j["config"]["cubes_per_step_per_gpu"]
+    assert ub.dtype == lb.dtype == best.dtype == np.float32 and ub.shape == lb.shape == (Bc,) and best.shape == (1,)
+    assert np.isfinite(ub).all() and np.isfinite(lb).all() and (ub >= 0).all() and (lb >= 0).all()
+    assert best[0] == ub.min()

@@ -42,7 +42,7 @@ if mode == "bounds":
     res["note"] = ("separate --pmc passes (FETCH_SIZE needs 3 of the 4 TCC slots). gfx950: FETCH_SIZE counts 64 B per 128-B request (MI355X_MICROARCH.md, HBM section), "
                    "so the corrected figure doubles it; TCC_MISS_sum x 128 B is the independent cross-check.  Fabric side of L2: Infinity-Cache hits included, an upper bound on HBM bytes.")
 else:
-    res = {"workload": workload, "commands": ["tools/pmc_collect.sh <out> icp_ --steps 1 --warmup 0 --prewarm 0 --sustain-s 0 --s2-steps 0 --no-cpu --no-e2e --no-probe",
+    res = {"workload": workload, "commands": ["tools/pmc_collect.sh <out> icp_ --full --steps 1 --warmup 0 --prewarm 0 --sustain-s 0 --s2-steps 0 --no-cpu --no-e2e --no-probe",
                                               "python tools/pmc_to_profile.py icp <out> '<workload>'"]}
     tot_corr = tot_miss = 0.0
     for k, e in raw.items():
