@@ -112,6 +112,7 @@ SYMBOLS = {
     "goicp_debug_queue_expand": (C.c_int, [C.c_void_p, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
     "goicp_debug_bounds_tile": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     "goicp_debug_cache_hits": (C.c_int, [_vp, _fp, _fp, C.POINTER(C.c_int64)]),
+    "goicp_debug_select": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "goicp_create": (C.c_int, [C.POINTER(CParams), _fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(_vp)]),
     "goicp_destroy": (C.c_int, [_vp]),
     "goicp_dt_info": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

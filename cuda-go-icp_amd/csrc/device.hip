@@ -2406,14 +2406,22 @@ static void launch_nn_store_k(const float4* src, int N, IcpState* st, const KdDe
 
 int icp_trim_blocks(int N) { return (N + kIcpThreads - 1) / kIcpThreads; }
 
+hipError_t launch_icp_select(const float* nn_d2, int N, int num, const IcpState* st, unsigned char* include, int kernel, hipStream_t stream)
+{
+	if (kernel == 0) kernel = N <= 1024 * kSelPer ? 1 : 2;
+	if (kernel == 1 && N > 1024 * kSelPer) return hipErrorInvalidValue;          // the register kernel holds kSelPer distances per thread
+	if (kernel == 1) hipLaunchKernelGGL(icp_select_kernel, dim3(1), dim3(1024), 0, stream, nn_d2, N, num, st, include);
+	else hipLaunchKernelGGL(icp_select_stream_kernel, dim3(1), dim3(1024), 0, stream, nn_d2, N, num, st, include);
+	return hipGetLastError();
+}
+
 hipError_t launch_icp_iteration_trim(const float4* src, int N, int num, IcpState* st, const KdDesc& kd, const DtDesc& dt,
                                      float* nn_d2, int* nn_slot, unsigned char* include, float* partials, hipStream_t stream)
 {
 	if (kd.K == 1) launch_nn_store_k<1>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
 	else if (kd.K == 2) launch_nn_store_k<2>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
 	else launch_nn_store_k<3>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
-	if (N <= 1024 * kSelPer) hipLaunchKernelGGL(icp_select_kernel, dim3(1), dim3(1024), 0, stream, nn_d2, N, num, st, include);
-	else hipLaunchKernelGGL(icp_select_stream_kernel, dim3(1), dim3(1024), 0, stream, nn_d2, N, num, st, include);
+	launch_icp_select(nn_d2, N, num, st, include, 0, stream);
 	const int nb = icp_trim_blocks(N);
 	hipLaunchKernelGGL(icp_accum_kernel, dim3(nb), dim3(kIcpThreads), 0, stream, src, N, st, kd, nn_d2, nn_slot, include, partials);
 	hipLaunchKernelGGL(icp_finalize_update, dim3(1), dim3(kFinThreads), 0, stream, partials, nb, st);
@@ -2479,8 +2487,9 @@ __global__ __launch_bounds__(1024) void reduce_min_kernel(const float* __restric
 {
 	__shared__ float sv[16];
 	__shared__ int si[16];
+	// a thread starts at (+inf, its first index): an all-+inf input then yields index 0, not the sentinel of a thread without values
 	float best = __builtin_inff();
-	int bi = 0x7fffffff;
+	int bi = (int)threadIdx.x * 4 < n ? (int)threadIdx.x * 4 : 0x7fffffff;
 	for (int i = threadIdx.x * 4; i < n; i += 4096) {
 		if (i + 3 < n) {
 			const float4 x = *reinterpret_cast<const float4*>(v + i);

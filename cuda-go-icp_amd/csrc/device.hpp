@@ -238,6 +238,9 @@ hipError_t launch_icp_iteration(const float4* src, int N, IcpState* d_state, con
                                 float* partials, int* ticket, float4* nn_cache, int* hit_counter, hipStream_t stream, unsigned long long* acc = nullptr);
 // trimmed iteration: only the `num` nearest correspondences enter the sums (IcpState.n must be num)
 int icp_trim_blocks(int N);
+// the trimmed iteration's selection of the num smallest nn_d2 (ties in point order) into include[]: kernel 0 = by size (the
+// iteration's choice), 1 = registers (N <= 32 768, else hipErrorInvalidValue without a launch), 2 = streaming
+hipError_t launch_icp_select(const float* nn_d2, int N, int num, const IcpState* st, unsigned char* include, int kernel, hipStream_t stream);
 hipError_t launch_icp_iteration_trim(const float4* src, int N, int num, IcpState* d_state, const KdDesc& kd, const DtDesc& dt,
                                      float* nn_d2, int* nn_slot, unsigned char* include, float* partials, hipStream_t stream);
 // In-place p <- R p + t, norm recomputed (ICP::kdTreeGPUStep's kernTransform, icp_kernel.cu:138-144)

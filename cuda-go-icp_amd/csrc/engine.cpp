@@ -1084,6 +1084,22 @@ void Engine::debug_queue_expand(const float R[9], int level, const float* parent
 	}
 }
 
+void Engine::debug_select(const float* d2, size_t n, int num, int kernel, unsigned char* include)
+{
+	if (n < 1 || n > 0x7fffffffu || num < 1 || (size_t)num > n || kernel < 0 || kernel > 2 || (kernel == 1 && n > 32768))
+		throw std::invalid_argument("goicp: debug_select: bad n / num / kernel");
+	DeviceGuard guard(dev_);
+	DevBuf<float> dd(n);
+	DevBuf<unsigned char> di(n);
+	DevBuf<IcpState> ds(1);
+	HIPCHK(hipMemcpyAsync(dd.p, d2, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemsetAsync(ds.p, 0, sizeof(IcpState), stream_));                 // converged = 0
+	HIPCHK(hipMemsetAsync(di.p, 0xff, n, stream_));                             // every flag is written by the kernel
+	HIPCHK(launch_icp_select(dd.p, (int)n, num, ds.p, di.p, kernel, stream_));
+	HIPCHK(hipMemcpyAsync(include, di.p, n, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+}
+
 long long Engine::debug_cache_hits(const float R[9], const float t[3])
 {
 	// two scoring passes at the same pose: the second one's queries should all hit the neighbour cache

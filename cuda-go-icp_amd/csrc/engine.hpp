@@ -133,6 +133,9 @@ public:
 	// measured ceiling of the gather path (4-byte loads into the resident DT): lookups/s; mode 0 coalesced, 1 divergent
 	double probe_gather(int mode, size_t window_bytes);
 	long long debug_cache_hits(const float R[9], const float t[3]);
+	// test: the trimmed ICP's selection of the num smallest of d2[0..n) on the device, as inclusion flags (kernel 0 = the iteration's
+	// choice by size, 1 = register kernel, n <= 32 768, 2 = streaming kernel)
+	void debug_select(const float* d2, size_t n, int num, int kernel, unsigned char* include);
 	// test: the n (<= 128) given translation nodes (parents4: corner xyz + width) expanded by ONE round of the device-resident queues -- an
 	// upper-bound search (coeff 0) and a lower-bound search (rotation level `level`) of the same rotation, twins of each other, both listing
 	// all n nodes: the round the outer search's lock-step batches run (selection by bnb_queue_kernel, evaluation by bounds_queue_kernel with

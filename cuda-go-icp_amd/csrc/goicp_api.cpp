@@ -225,6 +225,12 @@ int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, co
 	});
 }
 
+int goicp_debug_select(goicp_handle h, const float* d2, size_t n, int32_t num, int32_t kernel, uint8_t* include)
+{
+	REQUIRE(h && d2 && include && n >= 1 && n <= 0x7fffffffu && num >= 1 && (size_t)num <= n && kernel >= 0 && kernel <= 2 && !(kernel == 1 && n > 32768));
+	return guarded([&] { h->e->debug_select(d2, n, num, kernel, include); });
+}
+
 int goicp_debug_kabsch(const float H[9], float R[9])
 {
 	REQUIRE(H && R);

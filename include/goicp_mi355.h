@@ -452,6 +452,10 @@ int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, co
 /* diagnostics of the ICP pass's neighbour cache: two scoring passes at (R, t); *hits = queries of the second pass that
  * skipped the tree walk (-1 when the cache is off) */
 int goicp_debug_cache_hits(goicp_handle h, const float R[9], const float t[3], int64_t* hits);
+/* goicp_debug_select (test): the trimmed ICP iteration's selection of the num (1 <= num <= n) smallest of d2[0..n) -- ties go to the
+ * points that come first -- run on the device against a fresh (unconverged) loop state; include[i] = 1 for the selected points, else 0.
+ * kernel 0: the iteration's own choice by size; 1: the register kernel (n <= 32 768, else GOICP_ERR_INVALID); 2: the streaming kernel. */
+int goicp_debug_select(goicp_handle h, const float* d2, size_t n, int32_t num, int32_t kernel, uint8_t* include);
 
 #ifdef __cplusplus
 }

@@ -335,6 +335,20 @@ void orc_cube_bound_trim(const orc_dt* dt, const float* p, int N, const float* r
 	*lb_out = lb;
 }
 
+void orc_cube_terms(const orc_dt* dt, const float* p, int N, const float* rho,
+                    float tx, float ty, float tz, float w_child, float* m_out)
+{
+	/* the per-point clamped residuals of orc_cube_bound, same arithmetic; the caller sums them (w_child kept for the
+	 * signature's symmetry with orc_cube_bound: maxTransDis enters only the sums) */
+	(void)w_child;
+	for (int i = 0; i < N; i++) {
+		float m = orc_dt_distance(dt, (double)(p[3 * i] + tx), (double)(p[3 * i + 1] + ty), (double)(p[3 * i + 2] + tz));
+		if (rho) m -= rho[i];
+		if (m < 0) m = 0;
+		m_out[i] = m;
+	}
+}
+
 void orc_cube_bound(const orc_dt* dt, const float* p, int N, const float* rho,
                     float tx, float ty, float tz, float w_child, float* ub_out, float* lb_out)
 {

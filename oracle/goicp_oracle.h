@@ -56,6 +56,9 @@ void  orc_rotate(const float R[9], const float* data_xyz, int N, float* out_xyz)
 /* jly_goicp.cpp:262-315 for one child cube with centre (tx,ty,tz) and width w_child */
 void  orc_cube_bound(const orc_dt* dt, const float* prot_xyz, int N, const float* rho_or_null,
                      float tx, float ty, float tz, float w_child, float* ub, float* lb);
+/* the per-point clamped residuals m_i that orc_cube_bound sums (same arithmetic): test reference sums in float64 */
+void  orc_cube_terms(const orc_dt* dt, const float* prot_xyz, int N, const float* rho_or_null,
+                     float tx, float ty, float tz, float w_child, float* m_out);
 /* trimmed form (trimFraction > 0, jly_goicp.cpp:293-315): only the `inliers` smallest residuals are summed */
 void  orc_cube_bound_trim(const orc_dt* dt, const float* prot_xyz, int N, const float* rho_or_null,
                           float tx, float ty, float tz, float w_child, int inliers, float* ub, float* lb);

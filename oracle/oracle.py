@@ -53,6 +53,7 @@ def lib():
         L.orc_rotate.argtypes = [fp, fp, C.c_int, fp]
         L.orc_cube_bound.argtypes = [dp, fp, C.c_int, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp]
         L.orc_cube_bound_omp.argtypes = L.orc_cube_bound.argtypes
+        L.orc_cube_terms.argtypes = [dp, fp, C.c_int, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp]
         L.orc_cube_bound_trim.argtypes = [dp, fp, C.c_int, fp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp, fp]
         L.orc_inner_bnb_trim.argtypes = [dp, fp, C.c_int, fp, C.c_int, C.c_float, C.c_float, fp, fp,
                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -184,6 +185,29 @@ def cube_bound(dt, prot, rho, t, w_child, omp=False):
     fn(C.byref(dt.dt), pp, len(p), rp, np.float32(t[0]), np.float32(t[1]), np.float32(t[2]), np.float32(w_child),
        C.byref(ub), C.byref(lb))
     return np.float32(ub.value), np.float32(lb.value)
+
+
+def cube_terms(dt, prot, rho, t, w_child):
+    """The per-point clamped residuals m_i of cube_bound (float32, the oracle's arithmetic), in point order."""
+    p, pp = _f(prot)
+    rp = None
+    if rho is not None:
+        rho, rp = _f(rho)
+    m = np.empty(len(p), np.float32)
+    lib().orc_cube_terms(C.byref(dt.dt), pp, len(p), rp, np.float32(t[0]), np.float32(t[1]), np.float32(t[2]), np.float32(w_child),
+                         m.ctypes.data_as(C.POINTER(C.c_float)))
+    return m
+
+
+def cube_bound_f64(dt, prot, rho, t, w_child, inliers=None):
+    """Reference cube bound with float64 sums: ub = sum m^2, lb = sum max(m - maxTransDis, 0)^2 over the per-point residuals of
+    cube_terms (maxTransDis = float32(1.732050808 / 2 * w_child), the oracle's and the engine's constant); with `inliers`, over the `inliers` smallest m
+    only -- a multiset, the same whatever the order of tied values.  Returns (ub, lb) as Python floats."""
+    m = cube_terms(dt, prot, rho, t, w_child).astype(np.float64)
+    if inliers is not None and inliers < len(m):
+        m = np.partition(m, inliers - 1)[:inliers]
+    mtd = float(np.float32(1.732050808 / 2.0 * float(np.float32(w_child))))
+    return float(np.sum(m * m)), float(np.sum(np.maximum(m - mtd, 0.0) ** 2))
 
 
 def cube_bound_trim(dt, prot, rho, t, w_child, inliers):

@@ -321,3 +321,34 @@ def test_oracle_trim_fixture_is_current():
     live, fix = G.trimmed_bunny10(), golden("e2e_bunny10_trim_oracle")
     assert np.allclose(live["R"], fix["R"], atol=1e-6) and np.allclose(live["t"], fix["t"], atol=1e-6)
     assert abs(live["sse"] - fix["sse"]) <= 1e-5 * fix["sse"]
+
+
+@pytest.mark.parametrize("stride,tol", [(1, 2e-4), (10, 2e-5)])
+def test_cube_bound_f64_matches_oracle(oracle_mod, oracle_dt_bunny, stride, tol):
+    """oracle.cube_bound_f64 (the float64 reference of the GPU scale tests: the oracle's per-point residuals, orc_cube_terms, summed in
+    float64) against the oracle's own float sums, plain and trimmed, on bunny (N = 30 379) and bunny/10: equal up to float summation
+    error.  Measured worst over these 72 sums: 4.3e-5 (bunny), 4.0e-6 (bunny/10) -- the float sums in point order are the
+    ones that drift."""
+    data = cloud("data_bunny", stride)
+    _, rho = oracle_mod.rot_radii(data)
+    prot = oracle_mod.rotate(oracle_mod.rodrigues([0.3, -0.2, 0.9]), data)
+    rng = np.random.default_rng(5)
+    worst = 0.0
+    for i in range(24):
+        c = rng.uniform(-0.4, 0.4, 3).astype(np.float32)
+        w = np.float32(1.0 / (1 << int(rng.integers(1, 6))))
+        r = rho[(1, 5)[i % 2]] if i % 3 else None
+        m = oracle_mod.cube_terms(oracle_dt_bunny, prot, r, c, w)
+        assert m.shape == (len(data),) and (m >= 0).all()
+        for k in (None, int(len(data) * 0.9), 1):
+            fu, fl = oracle_mod.cube_bound_f64(oracle_dt_bunny, prot, r, c, w, inliers=k)
+            if k is None:
+                ou, ol = oracle_mod.cube_bound(oracle_dt_bunny, prot, r, c, w)
+            else:
+                ou, ol = oracle_mod.cube_bound_trim(oracle_dt_bunny, prot, r, c, w, k)
+            dev = max(abs(ou - fu) / max(fu, 1e-3), abs(ol - fl) / max(fl, 1e-3))
+            worst = max(worst, dev)
+            assert dev <= tol, (i, k, ou, fu, ol, fl)
+        # the k smallest: a multiset -- the first entry of the trimmed form is the smallest residual itself
+        assert oracle_mod.cube_bound_f64(oracle_dt_bunny, prot, r, c, w, inliers=1)[0] == float(m.min()) ** 2
+    print("cube_bound_f64 vs oracle float sums, stride %d: worst rel %.2e" % (stride, worst))

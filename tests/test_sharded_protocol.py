@@ -298,9 +298,12 @@ def test_bench_rejects_zero_steps():
 
 
 @pytest.mark.gpu
-def test_bench_plain_line_and_dumped_outputs(tmp_path):
+def test_bench_plain_line_and_dumped_outputs(tmp_path, oracle_mod, oracle_dt_bunny, bunny_model, bunny_data):
     """A plain `python3 bench.py` is the headline alone: ONE JSON line with the contract's keys and none of the --full legs, and
-    `--dump-outputs DIR` writes the last timed step's bounds (float32, one per cube) and their minimum, the step's best upper bound."""
+    `--dump-outputs DIR` writes the last timed step's bounds (float32, one per cube) and their minimum, the step's best upper bound.
+    The dumped bounds are those of the batch bench.make_batch(seed=1234) builds: bit-equal to the same batch evaluated in this
+    process, lb <= ub on every cube, and 256 seeded cubes (both passes, every parent and rotation level of the batch) within rel 2e-6
+    of the float64 reference (oracle.cube_bound_f64; measured worst on MI355X 1.7e-7)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path)],
                        env=env, capture_output=True, text=True, timeout=300)
@@ -319,3 +322,41 @@ def test_bench_plain_line_and_dumped_outputs(tmp_path):
     assert ub.dtype == lb.dtype == best.dtype == np.float32 and ub.shape == lb.shape == (Bc,) and best.shape == (1,)
     assert np.isfinite(ub).all() and np.isfinite(lb).all() and (ub >= 0).all() and (lb >= 0).all()
     assert best[0] == ub.min()
+    assert (lb <= ub).all()
+    # the batch rebuilt as bench.py builds it (engine defaults of the bench: DT 300^3, bricked layout, k-d source order)
+    import ctypes as C
+    import bench
+    pkg = load_pkg()
+    pkg.load_library()
+    reg = pkg.Registration(bunny_model, bunny_data, 1e-3, dt_size=300, dt_layout=1, morton_sort=2)
+    rots, recs, _ = bench.make_batch(pkg, reg, 8192, 8, seed=1234)
+    assert len(recs) == Bc
+    fp = C.POINTER(C.c_float)
+    ub2, lb2 = np.empty(Bc, np.float32), np.empty(Bc, np.float32)
+    pkg.binding.check(reg._lib.goicp_eval_bounds_batch(reg.handle, np.ascontiguousarray(rots, np.float32).ctypes.data_as(fp), len(rots),
+                                                       np.ascontiguousarray(recs).ctypes.data_as(C.POINTER(pkg.binding.CCube)), Bc,
+                                                       ub2.ctypes.data_as(fp), lb2.ctypes.data_as(fp)))
+    assert np.array_equal(ub, ub2) and np.array_equal(lb, lb2)
+    # 256 seeded cubes: one of every (pass, rotation level, child width) of the batch, the rest drawn at random
+    rng = np.random.default_rng(256)
+    key = recs["coeff"].astype(np.float64) * 1e3 + recs["delta"]
+    pick = [int(rng.choice(np.flatnonzero(key == k))) for k in np.unique(key)]
+    assert len(pick) == 6 + 6 * 6                # ub pass x 6 child widths + lb pass x 6 rotation levels x 6 child widths
+    pick += rng.choice(np.setdiff1d(np.arange(Bc), pick), 256 - len(pick), replace=False).tolist()
+    _, rho = oracle_mod.rot_radii(bunny_data)
+    level = {float(reg.rot_coeff(l)): l for l in range(3, 9)}
+    width = {float(reg._lib.goicp_trans_delta(1.0 / (1 << j))): 1.0 / (1 << j) for j in range(1, 7)}
+    prot, worst = {}, 0.0
+    for i in pick:
+        r = recs[i]
+        if int(r["rot"]) not in prot:
+            prot[int(r["rot"])] = oracle_mod.rotate(rots[int(r["rot"])], bunny_data)
+        lv = level[float(r["coeff"])] if r["coeff"] != 0 else None
+        assert lv is None or oracle_mod.rot_coeff(lv) == r["coeff"]
+        fu, fl = oracle_mod.cube_bound_f64(oracle_dt_bunny, prot[int(r["rot"])], None if lv is None else rho[lv], (r["tx"], r["ty"], r["tz"]),
+                                           width[float(r["delta"])])
+        d = max(abs(float(ub[i]) - fu) / max(fu, 1e-3), abs(float(lb[i]) - fl) / max(fl, 1e-3))
+        worst = max(worst, d)
+        assert d <= 2e-6, (i, ub[i], fu, lb[i], fl)
+    print("bench dump vs float64 reference (256 cubes): worst rel deviation %.2e" % worst)
+    reg.close()
