@@ -73,6 +73,12 @@ class CShardStats(C.Structure):
                [("wait_ms", C.c_double), ("step_ms", C.c_double), ("best_sse", C.c_float), ("failed_rank", C.c_int32)]
 
 
+class CIcpShardStats(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rank", "world", "block_begin", "block_end", "blocks", "sliced")] + \
+               [(n, C.c_int64) for n in ("queries", "runs", "passes", "collectives")] + \
+               [("sum_wait_ms", C.c_double), ("round_trip_ms", C.c_double)]
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -150,6 +156,10 @@ SYMBOLS = {
     "goicp_shard_options_default": (None, [C.POINTER(CShardOptions)]),
     "goicp_run_sharded_opt": (C.c_int, [C.POINTER(CShardEngineOps), C.POINTER(CCommOps), C.POINTER(CShardOptions), C.POINTER(CShardStats)]),
     "goicp_register_sharded_opt": (C.c_int, [_vp, C.POINTER(CCommOps), C.POINTER(CShardOptions), C.POINTER(CShardStats)]),
+    "goicp_comm_allreduce_sum_i64": (C.c_int, [C.POINTER(CCommOps), C.POINTER(C.c_int64), C.c_size_t]),
+    "goicp_icp_run_collective": (C.c_int, [_vp, C.POINTER(CCommOps), _fp, _fp, C.c_int32, C.c_float, _fp, C.POINTER(C.c_int32)]),
+    "goicp_icp_shard_stats_get": (C.c_int, [_vp, C.POINTER(CIcpShardStats)]),
+    "goicp_register_sharded_collective_icp": (C.c_int, [_vp, C.POINTER(CCommOps), C.POINTER(CShardOptions), C.POINTER(CShardStats)]),
     "goicp_comm_set_timeout_ms": (C.c_int, [C.POINTER(CCommOps), C.c_int32]),
     "goicp_thread_comm_create": (C.c_int, [C.c_int32, C.POINTER(CCommOps)]),
     "goicp_thread_comm_destroy": (C.c_int, [C.POINTER(CCommOps)]),

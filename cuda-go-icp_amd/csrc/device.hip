@@ -1642,12 +1642,17 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 // nn_cache (two float4 per source point: {q_ref.xyz, sqrt(best2_ref)}, {neighbour xyz, its original index}) != nullptr:
 // the exact skip test of rows_nearest<TWO>'s comment; entries never go stale (they are statements about the static
 // target cloud), an entry with sqrt(best2_ref) = 0 (fresh engine, tied neighbours) always walks.
-template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES = 2, bool STRIDED = false, bool ACC = false>
+// SLICE (ACC form only, goicp_icp_run_collective): the launch covers workgroups [b0, b0 + gridDim.x) of the world-1 grid -- the
+// global workgroup index blockIdx.x + b0 picks the queries and the replica, so every workgroup forms the same float row sums from the
+// same 16 queries as in a full pass, and the integer totals of the slices of all ranks add up to the world-1 totals bit for bit.
+template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES = 2, bool STRIDED = false, bool ACC = false, bool SLICE = false>
 __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kernel(const float4* __restrict__ src, int N,
                                                                   IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
                                                                   float* __restrict__ partials, int* __restrict__ ticket,
-                                                                  float4* __restrict__ nn_cache, int* __restrict__ hit_counter)
+                                                                  float4* __restrict__ nn_cache, int* __restrict__ hit_counter, int b0)
 {
+	static_assert(!SLICE || (ACC && !FUSED), "a slice of the pass exists in the fixed-point form only");
+	const int gb = SLICE ? (int)blockIdx.x + b0 : (int)blockIdx.x;   // workgroup index in the world-1 grid
 	__shared__ FinScratch sh;
 	float (*red)[kIcpAcc] = sh.red;                                   // [16 rows of the workgroup][16 sums]
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
@@ -1656,7 +1661,7 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kern
 	// quarter of the cloud apart (small clouds: the pass lasts as long as its slowest wavefront; far-from-surface queries
 	// come in neighbourhoods, so with neighbours in one wavefront all four rows walk long and in different stages, with
 	// strangers the one long walk of a wavefront runs alone: bunny 27.3 k -> 29.7 k iterations/s)
-	const int nw = (N + 3) >> 2, wv = blockIdx.x * (kIcpThreads / 64) + wave;
+	const int nw = (N + 3) >> 2, wv = gb * (kIcpThreads / 64) + wave;
 	const int i = STRIDED ? wv + row * nw : wv * 4 + row;
 	const bool valid = wv < nw && i < N;
 	const Box6x4 rootb = load_child_boxes4(kd.boxes[0], l);      // issued before the flag is tested: one round trip less
@@ -1740,7 +1745,7 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kern
 			// 1 899 of them) but 16 device-scope 64-bit integer adds of the sums in fixed point -- integer addition is
 			// associative, so the totals are exact and independent of the arrival order: still bit-reproducible
 			const long long v = __double2ll_rn((double)sum * (double)st->acc_scale);
-			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(blockIdx.x & (kIcpAccReplicas - 1)) * kIcpAcc + threadIdx.x;
+			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpAcc + threadIdx.x;
 			__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		} else {
 			partials[(size_t)blockIdx.x * kIcpAcc + threadIdx.x] = sum;
@@ -2251,6 +2256,58 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_finalize_update_acc(unsign
 	finalize_rows(sums, state, st, t);
 }
 
+// ---- the sharded ICP loop (goicp_icp_run_collective): slice pass -> export -> sum over the ranks on the host -> finalize from the sums ----
+// the 32 x 16 replicas of the fixed-point pass -> lane t & 15 holds the integer total of accumulator t & 15 (every lane of its column);
+// the replicas are zeroed on the way out.  Integer addition wraps, so the order of the adds does not matter.
+__device__ __forceinline__ long long acc_take_totals(unsigned long long* __restrict__ acc, int t)
+{
+	long long v[kIcpAccReplicas * kIcpAcc / kFinAccThreads];
+#pragma unroll
+	for (int j = 0; j < kIcpAccReplicas * kIcpAcc / kFinAccThreads; j++) v[j] = (long long)acc[kFinAccThreads * j + t];
+#pragma unroll
+	for (int j = 0; j < kIcpAccReplicas * kIcpAcc / kFinAccThreads; j++) acc[kFinAccThreads * j + t] = 0ull;
+	unsigned long long x = 0;
+#pragma unroll
+	for (int j = 0; j < kIcpAccReplicas * kIcpAcc / kFinAccThreads; j++) x += (unsigned long long)v[j];
+	x += (unsigned long long)__shfl_xor((long long)x, 16, 64);
+	x += (unsigned long long)__shfl_xor((long long)x, 32, 64);
+	return (long long)x;
+}
+// the loop state to LDS, one word per lane (the caller's barrier publishes it)
+__device__ __forceinline__ void icp_state_to_lds(const IcpState* __restrict__ state, IcpState& st, int t)
+{
+	if (t < (int)(sizeof(IcpState) / 4)) reinterpret_cast<unsigned*>(&st)[t] = reinterpret_cast<const unsigned*>(state)[t];
+}
+
+// ONE wavefront: this rank's 16 integer totals and the state's converged flag -> out[0..16] (a small device buffer the host reads back)
+__global__ __launch_bounds__(kFinAccThreads) void icp_acc_export_kernel(unsigned long long* __restrict__ acc, const IcpState* __restrict__ state,
+                                                                        long long* __restrict__ out)
+{
+	static_assert((kIcpAccReplicas * kIcpAcc) % kFinAccThreads == 0 && kFinAccThreads / kIcpAcc == 4, "four replicas per pass of the wavefront");
+	const int t = threadIdx.x;
+	const long long x = acc_take_totals(acc, t);      // a converged state added nothing: the replicas are zero, so are the totals
+	if (t < kIcpAcc) out[t] = x;
+	if (t == 0) out[kIcpAcc] = state->converged;
+	static_assert(sizeof(IcpState) % 4 == 0 && sizeof(IcpState) / 4 <= kFinAccThreads, "one state word per lane");
+	if (t < (int)(sizeof(IcpState) / 4)) reinterpret_cast<unsigned*>(out + kIcpAcc + 1)[t] = reinterpret_cast<const unsigned*>(state)[t];
+}
+
+// the second half of icp_finalize_update_acc: the 16 totals summed over the ranks -> (double)x * acc_inv -> finalize_rows
+__global__ __launch_bounds__(kFinAccThreads) void icp_finalize_from_sums_kernel(const long long* __restrict__ words, IcpState* __restrict__ state)
+{
+	__shared__ double sums[kIcpAcc];
+	__shared__ IcpState st;
+	static_assert(sizeof(IcpState) / 4 <= kFinAccThreads, "one state word per lane");
+	const int t = threadIdx.x;
+	icp_state_to_lds(state, st, t);
+	if (state->converged) return;                 // uniform
+	const long long x = t < kIcpAcc ? words[t] : 0;
+	__syncthreads();                              // the state words are in LDS
+	if (t < kIcpAcc) sums[t] = (double)x * (double)st.acc_inv;
+	__syncthreads();
+	finalize_rows(sums, state, st, t);
+}
+
 // test-only entry (goicp_debug_kabsch): the device SVD on a caller-supplied H, one lane
 __global__ void kabsch_debug_kernel(const float* __restrict__ H, float* __restrict__ R)
 {
@@ -2364,20 +2421,20 @@ int icp_blocks(int N)
 }
 
 // the fixed-point form (bricked DT, two launches per iteration): `acc` is the accumulator block; strangers per wavefront up to
-// kIcpStridedMaxN points, neighbours above
-template <int K>
+// kIcpStridedMaxN points, neighbours above.  SLICE: workgroups [b0, b0 + nb) of the world-1 grid only (launch_icp_pass_slice)
+template <int K, bool SLICE = false>
 static void launch_pass_acc(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, unsigned long long* acc, float4* nn_cache,
-                            int* hits, hipStream_t stream)
+                            int* hits, hipStream_t stream, int b0 = 0, int nb = -1)
 {
-	const dim3 grid(icp_blocks(N)), block(kIcpThreads);
+	const dim3 grid(nb < 0 ? icp_blocks(N) : nb), block(kIcpThreads);
 	float* a = reinterpret_cast<float*>(acc);
 	const bool strided = N <= kIcpStridedMaxN;
 	if (nn_cache) {
-		if (strided) hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, true, 2, true, true>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits);
-		else hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, true, 2, false, true>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits);
+		if (strided) hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, true, 2, true, true, SLICE>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits, b0);
+		else hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, true, 2, false, true, SLICE>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits, b0);
 	} else {
-		if (strided) hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, false, 4, true, true>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits);
-		else hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, false, 4, false, true>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits);
+		if (strided) hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, false, 4, true, true, SLICE>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits, b0);
+		else hipLaunchKernelGGL((icp_pass_kernel<K, 1, false, false, 4, false, true, SLICE>), grid, block, 0, stream, src, N, st, kd, dt, a, nullptr, nn_cache, hits, b0);
 	}
 }
 
@@ -2387,12 +2444,12 @@ static void launch_pass_k(const float4* src, int N, IcpState* st, const KdDesc& 
 {
 	const dim3 grid(icp_blocks(N)), block(kIcpThreads);
 	if (nn_cache) {
-		if (dt.layout) hipLaunchKernelGGL((icp_pass_kernel<K, 1, FUSED, true>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits);
-		else hipLaunchKernelGGL((icp_pass_kernel<K, 0, FUSED, true>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits);
+		if (dt.layout) hipLaunchKernelGGL((icp_pass_kernel<K, 1, FUSED, true>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits, 0);
+		else hipLaunchKernelGGL((icp_pass_kernel<K, 0, FUSED, true>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits, 0);
 	} else {
 		// four leaves per scan step (S2 845 -> 926 iterations/s, S1 21.9 k -> 23.0 k, bunny 27.0 k -> 27.1 k)
-		if (dt.layout) hipLaunchKernelGGL((icp_pass_kernel<K, 1, FUSED, false, FUSED ? 2 : 4>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits);
-		else hipLaunchKernelGGL((icp_pass_kernel<K, 0, FUSED, false, FUSED ? 2 : 4>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits);
+		if (dt.layout) hipLaunchKernelGGL((icp_pass_kernel<K, 1, FUSED, false, FUSED ? 2 : 4>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits, 0);
+		else hipLaunchKernelGGL((icp_pass_kernel<K, 0, FUSED, false, FUSED ? 2 : 4>), grid, block, 0, stream, src, N, st, kd, dt, partials, ticket, nn_cache, hits, 0);
 	}
 }
 
@@ -2425,6 +2482,40 @@ hipError_t launch_icp_iteration_trim(const float4* src, int N, int num, IcpState
 	const int nb = icp_trim_blocks(N);
 	hipLaunchKernelGGL(icp_accum_kernel, dim3(nb), dim3(kIcpThreads), 0, stream, src, N, st, kd, nn_d2, nn_slot, include, partials);
 	hipLaunchKernelGGL(icp_finalize_update, dim3(1), dim3(kFinThreads), 0, stream, partials, nb, st);
+	return hipGetLastError();
+}
+
+hipError_t launch_icp_pass_slice(const float4* src, int N, int b0, int b1, IcpState* st, const KdDesc& kd, const DtDesc& dt, unsigned long long* acc,
+                                 float4* nn_cache, int* hits, hipStream_t stream)
+{
+	if (!dt.layout || !acc || b0 < 0 || b1 > icp_blocks(N) || b0 > b1) return hipErrorInvalidValue;
+	if (b1 == b0) return hipSuccess;              // an empty range adds nothing: its totals are zero
+	if (kd.K == 1) launch_pass_acc<1, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
+	else if (kd.K == 2) launch_pass_acc<2, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
+	else launch_pass_acc<3, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
+	return hipGetLastError();
+}
+
+hipError_t launch_icp_acc_export(unsigned long long* acc, const IcpState* st, long long* out, hipStream_t stream)
+{
+	static_assert(kIcpExportWords * 8 >= (kIcpAcc + 1) * 8 + (int)sizeof(IcpState), "export buffer");
+	hipLaunchKernelGGL(icp_acc_export_kernel, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st, out);
+	return hipGetLastError();
+}
+
+long long icp_slice_queries(int N, int b0, int b1)
+{
+	const int waves = kIcpThreads / 64, nw = (N + 3) >> 2;
+	const bool strided = N <= kIcpStridedMaxN;
+	long long q = 0;
+	for (long long wv = (long long)b0 * waves; wv < (long long)b1 * waves && wv < nw; wv++)
+		for (int row = 0; row < 4; row++) q += (strided ? wv + (long long)row * nw : wv * 4 + row) < N;   // icp_pass_kernel's `valid`
+	return q;
+}
+
+hipError_t launch_icp_finalize_from_sums(const long long* sums16, IcpState* st, hipStream_t stream)
+{
+	hipLaunchKernelGGL(icp_finalize_from_sums_kernel, dim3(1), dim3(kFinAccThreads), 0, stream, sums16, st);
 	return hipGetLastError();
 }
 

@@ -236,6 +236,18 @@ size_t icp_partials_floats(int N);   // floats the `partials` buffer of launch_i
 // points sum there instead of writing a row of partial sums per workgroup; nullptr -> rows for every size
 hipError_t launch_icp_iteration(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt,
                                 float* partials, int* ticket, float4* nn_cache, int* hit_counter, hipStream_t stream, unsigned long long* acc = nullptr);
+// The sharded ICP loop (goicp_icp_run_collective), fixed-point form only (bricked DT, acc != nullptr).  One iteration on a rank:
+//   launch_icp_pass_slice    the pass over workgroups [b0, b1) of the world-1 grid (icp_blocks(N)) with the global N: every workgroup forms
+//                            the float row sums of the same 16 queries as at world 1; no finalize.  b0 == b1: nothing is launched
+//   launch_icp_acc_export    one wavefront: the replicas -> 16 int64 totals (replicas zeroed) + the state's converged flag -> out[0..16],
+//                            the loop state itself behind them (out + 17): ONE read-back per iteration
+//   launch_icp_finalize_from_sums  the totals summed over the ranks (16 int64) -> (double)x * acc_inv -> the update of icp_finalize_update_acc
+hipError_t launch_icp_pass_slice(const float4* src, int N, int b0, int b1, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, unsigned long long* acc,
+                                 float4* nn_cache, int* hit_counter, hipStream_t stream);
+hipError_t launch_icp_acc_export(unsigned long long* acc, const IcpState* d_state, long long* out, hipStream_t stream);   // out: kIcpExportWords
+hipError_t launch_icp_finalize_from_sums(const long long* sums16, IcpState* d_state, hipStream_t stream);
+constexpr int kIcpExportWords = 17 + (int)((sizeof(IcpState) + 7) / 8);   // launch_icp_acc_export: totals, converged flag, then the loop state
+long long icp_slice_queries(int N, int b0, int b1);                      // source points the workgroups [b0, b1) of a pass evaluate
 // trimmed iteration: only the `num` nearest correspondences enter the sums (IcpState.n must be num)
 int icp_trim_blocks(int N);
 // the trimmed iteration's selection of the num smallest nn_d2 (ties in point order) into include[]: kernel 0 = by size (the

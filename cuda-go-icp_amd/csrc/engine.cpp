@@ -11,6 +11,7 @@
 // over N points.  Any expansion order of a best-first BnB yields valid bounds; with trans_batch = 1
 // and wide_children = 0 the visit order is exactly the reference's.
 #include "engine.hpp"
+#include "comm.hpp"
 #include "trace.hpp"
 
 #include <algorithm>
@@ -559,6 +560,7 @@ void Engine::release()
 	hipFree(d_cubes_); hipFree(d_rots_); hipFree(d_ub_); hipFree(d_lb_); hipFree(d_scratch_);
 	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
 	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
+	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
 	hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
 	for (Stage& st : stage_) {
@@ -901,6 +903,163 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 	cnt_.icp_iters += st.passes;
 	cnt_.icp_runs++;
 	return st.err_new;
+}
+
+namespace {
+uint64_t fnv1a(uint64_t h, const void* p, size_t n)
+{
+	const unsigned char* b = static_cast<const unsigned char*>(p);
+	for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; }
+	return h;
+}
+// the goicp_status of the exception being handled (the C ABI's mapping, goicp_api.cpp guarded)
+int current_status()
+{
+	try { throw; }
+	catch (const StatusError& e) { return e.rc; }
+	catch (const std::invalid_argument&) { return GOICP_ERR_INVALID; }
+	catch (const std::bad_alloc&) { return GOICP_ERR_INTERNAL; }
+	catch (const std::runtime_error&) { return GOICP_ERR_DEVICE; }
+	catch (...) { return GOICP_ERR_INTERNAL; }
+}
+constexpr uint64_t kHealthyWord = ~(uint64_t)0;
+}  // namespace
+
+// The sharded ICP loop.  Rank r of G evaluates the workgroups [r B / G, (r+1) B / G) of the world-1 grid of the fixed-point
+// pass (B = icp_blocks(N), global N, block offset: every workgroup forms the float row sums of the same 16 queries as at world 1), exports its
+// 16 integer totals, and the ranks add them up (mod 2^64: associative, so the world-1 totals bit for bit); every rank then runs the same
+// finalize on the same totals and holds the same IcpState -- the same pose, error, iteration count and stop decision, with no collective to
+// agree on when to stop.  Per iteration: slice pass -> export -> read back (totals, converged flag, state) -> sum over the ranks -> upload ->
+// finalize.  Agreement and failure are collective: one MIN all-reduce of a check word over (R, t, max_iter, err_diff, N, acc_scale, mode)
+// first -- as h and ~h, so every rank sees whether all agree -- and a health word in every sum: a rank whose HIP call failed keeps
+// exchanging zeros, and all ranks leave in the same iteration.  Trimmed ICP (a global k-selection), the fused iteration and the linear DT
+// layout have no fixed-point pass: there every rank runs the full loop replicated (same state everywhere, no sums).
+int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3], int max_iter, float err_diff, float* err_out, int* iters_out)
+{
+	if (!comm || !comm->allreduce_min_u64 || !comm->bcast || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || max_iter < 0)
+		return GOICP_ERR_INVALID;
+	DeviceGuard guard(dev_);
+	TraceRange tr("goicp:icp_run_collective");
+	const int rank = comm->rank, world = comm->world;
+	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0;
+	IcpShardStats& ss = icp_shard_;
+	ss.rank = rank; ss.world = world; ss.sliced = sliced ? 1 : 0;
+	ss.blocks = icp_blocks((int)N_);
+	ss.block_begin = sliced ? (int)((long long)rank * ss.blocks / world) : 0;
+	ss.block_end = sliced ? (int)((long long)(rank + 1) * ss.blocks / world) : ss.blocks;
+	ss.runs++;
+	int local_rc = GOICP_OK;
+	auto local = [&](auto&& f) {
+		if (local_rc != GOICP_OK) return;
+		try { f(); } catch (...) { local_rc = current_status(); }
+	};
+	auto health = [&] { return local_rc == GOICP_OK ? kHealthyWord : ((uint64_t)((uint32_t)local_rc + 0x80000000u) << 32) | (uint32_t)rank; };
+	auto leave = [&](uint64_t hw) { return local_rc != GOICP_OK ? local_rc : (hw != kHealthyWord ? GOICP_ERR_PEER : GOICP_OK); };
+
+	// agreement: every rank must run the same loop on the same state
+	local([&] {
+		icp_state_init(R, t, err_diff, 1, 0);
+		if (sliced && !d_icp_x_) {
+			HIPCHK(hipMalloc(&d_icp_x_, sizeof(long long) * (kIcpExportWords + kIcpAcc)));
+			HIPCHK(hipHostMalloc(&h_icp_x_, sizeof(long long) * (kIcpExportWords + kIcpAcc)));
+		}
+	});
+	{
+		uint64_t h = 0xcbf29ce484222325ull;
+		const int32_t ints[4] = {max_iter, (int32_t)N_, sliced ? 1 : 0, world};
+		h = fnv1a(h, R, sizeof(float) * 9);
+		h = fnv1a(h, t, sizeof(float) * 3);
+		h = fnv1a(h, &err_diff, sizeof(err_diff));
+		h = fnv1a(h, ints, sizeof(ints));
+		h = fnv1a(h, &h_icp_state_->acc_scale, sizeof(float));
+		uint64_t w[3] = {h, ~h, health()};
+		const int rc = comm->allreduce_min_u64(comm->ctx, w, 3);
+		if (rc != GOICP_OK) return rc;
+		ss.collectives++;
+		if (w[2] != kHealthyWord) return leave(w[2]);
+		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff) or clouds");
+	}
+
+	const long long passes0 = cnt_.icp_iters;
+	if (!sliced) {
+		// fallback: the full loop on every rank, then one exchange of the health words so that every rank returns the same verdict
+		int it = 0;
+		float e = 0.f;
+		local([&] { e = icp_run(R, t, max_iter, err_diff, &it); });
+		uint64_t w = health();
+		const int rc = comm->allreduce_min_u64(comm->ctx, &w, 1);
+		if (rc != GOICP_OK) return rc;
+		ss.collectives++;
+		if (w != kHealthyWord) return leave(w);
+		ss.passes += cnt_.icp_iters - passes0;
+		ss.queries += (long long)N_ * (cnt_.icp_iters - passes0);
+		if (err_out) *err_out = e;
+		if (iters_out) *iters_out = it;
+		return GOICP_OK;
+	}
+
+	const long long per_pass = icp_slice_queries((int)N_, ss.block_begin, ss.block_end);
+	float4* cache = p_.icp_nn_cache == 1 ? d_nn_cache_ : nullptr;
+	int* hits = count_hits_ ? d_icp_ticket_ + 8 : nullptr;
+	long long* d_up = d_icp_x_ + kIcpExportWords;
+	long long* h_up = h_icp_x_ + kIcpExportWords;
+	constexpr int kWords = kIcpAcc + 2;          // 16 totals, converged flag, failed-rank count
+	for (int k = 0; k <= max_iter; k++) {
+		// k == max_iter: no pass, only the read-back of the final state (the totals are zero)
+		const double t0 = now_ms();
+		local([&] {
+			if (k < max_iter)
+				HIPCHK(launch_icp_pass_slice(d_src_, (int)N_, ss.block_begin, ss.block_end, d_icp_state_, kd_, dt_, d_icp_acc_, cache, hits, stream_));
+			HIPCHK(launch_icp_acc_export(d_icp_acc_, d_icp_state_, d_icp_x_, stream_));
+			HIPCHK(hipMemcpyAsync(h_icp_x_, d_icp_x_, sizeof(long long) * kIcpExportWords, hipMemcpyDeviceToHost, stream_));
+			HIPCHK(hipStreamSynchronize(stream_));
+		});
+		int64_t w[kWords] = {};
+		if (local_rc == GOICP_OK) {
+			std::memcpy(w, h_icp_x_, sizeof(int64_t) * kIcpAcc);
+			w[kIcpAcc] = h_icp_x_[kIcpAcc] != 0;
+		} else {
+			w[kIcpAcc + 1] = 1;
+		}
+		const double t1 = now_ms();
+		ss.round_trip_ms += t1 - t0;
+		const int rc = comm_allreduce_sum_i64(comm, w, kWords);
+		ss.sum_wait_ms += now_ms() - t1;
+		if (rc != GOICP_OK) return rc;
+		ss.collectives++;
+		if (w[kIcpAcc + 1] != 0) return local_rc != GOICP_OK ? local_rc : GOICP_ERR_PEER;
+		if (w[kIcpAcc] != 0 || k == max_iter) break;    // identical states: every rank stops here
+		const double t2 = now_ms();
+		local([&] {
+			std::memcpy(h_up, w, sizeof(int64_t) * kIcpAcc);
+			HIPCHK(hipMemcpyAsync(d_up, h_up, sizeof(int64_t) * kIcpAcc, hipMemcpyHostToDevice, stream_));
+			HIPCHK(launch_icp_finalize_from_sums(d_up, d_icp_state_, stream_));
+		});
+		ss.round_trip_ms += now_ms() - t2;
+	}
+	std::memcpy(h_icp_state_, h_icp_x_ + kIcpAcc + 1, sizeof(IcpState));
+	const IcpState& st = *h_icp_state_;
+	std::memcpy(R, st.R, sizeof(st.R));
+	std::memcpy(t, st.t, sizeof(st.t));
+	if (err_out) *err_out = st.err_new;
+	if (iters_out) *iters_out = st.iters;
+	cnt_.icp_iters += st.passes;
+	cnt_.icp_runs++;
+	ss.passes += st.passes;
+	ss.queries += per_pass * st.passes;
+	return GOICP_OK;
+}
+
+float Engine::refine_collective(float R[9], float t[3])
+{
+	const double t0 = now_ms();
+	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{icp_ms_, t0};
+	int it = 0;
+	float e = 0.f;
+	const int rc = icp_run_collective(icp_comm_, R, t, p_.icp_max_iter, icp_err_diff_, &e, &it);
+	if (rc != GOICP_OK) throw StatusError(rc, "collective ICP refinement failed (status " + std::to_string(rc) + ")");
+	unrefined_ = false;
+	return eval_sse(R, t);
 }
 
 float Engine::time_icp_pass(const float R[9], const float t[3], int iters, bool cached)
@@ -1652,7 +1811,13 @@ float Engine::icp_from(float R[9], float t[3])
 	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{icp_ms_, t0};
 	// GoICP::ICP (jly_goicp.cpp:93-132): ICP3D::Run, then re-score with the DT
 	int it = 0;
-	icp_run(R, t, p_.icp_max_iter, icp_err_diff_, &it);
+	if (icp_comm_) {
+		float ei = 0.f;
+		const int rc = icp_run_collective(icp_comm_, R, t, p_.icp_max_iter, icp_err_diff_, &ei, &it);
+		if (rc != GOICP_OK) throw StatusError(rc, "collective ICP failed (status " + std::to_string(rc) + ")");
+	} else {
+		icp_run(R, t, p_.icp_max_iter, icp_err_diff_, &it);
+	}
 	const float e = eval_sse(R, t);
 	if (p_.verbose > 1) std::fprintf(stderr, "[goicp] ICP run: %d iterations, %.2f ms, error %.6g (rot pops so far %lld, cube bounds %lld)\n", it, now_ms() - t0, e, cnt_.rot_pops, cnt_.cubes);
 	return e;
@@ -1663,6 +1828,7 @@ void Engine::offer_global_best(float sse, const float R[9], const float t[3])
 	DeviceGuard guard(dev_);
 	if (sse < opt_err_) {
 		adopt(sse, R, t);
+		unrefined_ = false;          // the collective protocol offers refined poses only
 		// drop queued nodes that can no longer win (jly_goicp.cpp:533-543)
 		std::priority_queue<Node> nq;
 		while (!queue_.empty()) {
@@ -1682,6 +1848,7 @@ void Engine::register_begin()
 	early_exit_ = converged_ = false;
 	rot_ramp_ = 8;
 	late_icp_.clear(); batches_done_ = 0;
+	unrefined_ = false;
 	last_round_work_ = 0; tile_sticky_ = false;      // every registration starts single-lane (determinism: the choice depends on this registration only)
 	{ const char* e = std::getenv("GOICP_ICP_DELAY_BATCHES"); icp_delay_ = e ? std::max(0, std::atoi(e)) : 0; }
 	icp_ms_ = 0; t_submit_ = t_wait_ = t_collect_ = 0;
@@ -1759,6 +1926,20 @@ bool Engine::handle_ub(Kid& k, const SearchOut& s)
 	if (!(s.best < opt_err_) || !s.improved) return false;
 	float t[3] = {s.best_node.x + s.best_node.w / 2, s.best_node.y + s.best_node.w / 2, s.best_node.z + s.best_node.w / 2};
 	adopt(s.best, k.R, t);
+	if (icp_comm_) {
+		// collective refinement (goicp_register_sharded_collective_icp): the upper bound is adopted as it is; the protocol refines the
+		// global winner on every rank after the next exchange (the deferral GOICP_ICP_DELAY_BATCHES models), so no pose is refined twice
+		unrefined_ = true;
+		publish(false);
+		if (opt_err_ < sse_thresh_) { early_exit_ = true; return true; }
+		std::priority_queue<Node> nq;
+		while (!queue_.empty()) {
+			Node n = queue_.top(); queue_.pop();
+			if (n.lb < opt_err_) nq.push(n); else break;
+		}
+		queue_.swap(nq);
+		return false;
+	}
 	float R[9], ti[3];
 	std::memcpy(R, k.R, sizeof(R)); std::memcpy(ti, t, sizeof(ti));
 	float e = icp_from(R, ti);

@@ -8,12 +8,30 @@
 #include <functional>
 #include <mutex>
 #include <queue>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "device.hpp"
 
+struct goicp_comm_ops;   // include/goicp_mi355.h
+
 namespace goicp {
+
+// a failure that already carries its goicp_status (a collective's GOICP_ERR_TIMEOUT / GOICP_ERR_PEER / GOICP_ERR_INVALID)
+struct StatusError : std::runtime_error {
+	int rc;
+	StatusError(int code, const std::string& msg) : std::runtime_error(msg), rc(code) {}
+};
+
+// goicp_icp_shard_stats: this engine's collective ICP runs (goicp_icp_run_collective), accumulated since it was created
+struct IcpShardStats {
+	int rank = 0, world = 1;
+	int block_begin = 0, block_end = 0, blocks = 0;   // this rank's workgroups [begin, end) of the world-1 grid of `blocks` (last run)
+	int sliced = 0;                                   // last run: 1 sliced passes, 0 replicated full passes (fallback)
+	long long queries = 0, runs = 0, passes = 0, collectives = 0;
+	double sum_wait_ms = 0, round_trip_ms = 0;
+};
 
 struct Params {
 	int dt_size = 300;            // jly_goicp.cpp:56
@@ -127,6 +145,17 @@ public:
 	float eval_sse(const float R[9], const float t[3]);
 	float inner_bnb(const float R[9], int level, float incumbent, float best_node[4], Counters* c);
 	float icp_run(float R[9], float t[3], int max_iter, float err_diff, int* iters);
+	// goicp_icp_run_collective: icp_run with the pass's workgroups split over the ranks of `comm` and the integer sums added up over
+	// them -- every rank ends with the world-1 state, bit for bit.  Returns a goicp_status (collective: every rank returns together)
+	int icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3], int max_iter, float err_diff, float* err, int* iters);
+	const IcpShardStats& icp_shard_stats() const { return icp_shard_; }
+	// goicp_register_sharded_collective_icp: while a communicator is set, the registration's refinements are collective -- the initial
+	// ICP inside register_begin runs collectively, and an improved upper bound is adopted UNREFINED (the protocol refines the
+	// global winner on every rank after the exchange, refine_collective)
+	void set_collective_icp(const goicp_comm_ops* comm) { icp_comm_ = comm; unrefined_ = false; }
+	bool pose_unrefined() const { return unrefined_; }
+	// collective ICP from R|t, then the DT re-score (replicated); the current best pose counts as refined from here on
+	float refine_collective(float R[9], float t[3]);
 	float time_icp_pass(const float R[9], const float t[3], int iters, bool cached = false);   // cached: every query hits the neighbour cache (steady state); else every query walks
 	void nn_query(const float* q_xyz, size_t n, int32_t* idx, float* d2);
 	void icp_step();   // one ICP iteration on the engine's current pose (ICP::kdTreeGPUStep)
@@ -320,6 +349,11 @@ private:
 	int* d_icp_ticket_ = nullptr;      // arrival ticket of the fused ICP iteration (zero between launches)
 	float* d_nn_d2_ = nullptr; int* d_nn_slot_ = nullptr; unsigned char* d_include_ = nullptr;   // trimmed ICP only
 	void icp_launch_one();
+	// the collective ICP loop: the exported totals + converged flag + loop state read back per iteration, the summed totals uploaded
+	long long* d_icp_x_ = nullptr; long long* h_icp_x_ = nullptr;
+	IcpShardStats icp_shard_;
+	const goicp_comm_ops* icp_comm_ = nullptr;
+	bool unrefined_ = false;           // collective registration: the best pose is an upper bound not yet refined by ICP
 	// nn query staging grows on demand
 	float rot_coeff_[20];
 

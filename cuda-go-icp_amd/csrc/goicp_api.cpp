@@ -32,6 +32,7 @@ template <class F> int guarded(F&& f)
 	try {
 		f();
 		return GOICP_OK;
+	} catch (const goicp::StatusError& e) { return fail(e.rc, e.what());
 	} catch (const goicp::ConfigError& e) { return fail(GOICP_ERR_CONFIG, e.what());
 	} catch (const goicp::IoError& e) { return fail(GOICP_ERR_IO, e.what());
 	} catch (const std::invalid_argument& e) { return fail(GOICP_ERR_INVALID, e.what());
@@ -343,6 +344,39 @@ int goicp_icp_run(goicp_handle h, float R[9], float t[3], int32_t max_iter, floa
 	});
 }
 
+int goicp_icp_run_collective(goicp_handle h, const goicp_comm_ops* comm, float R[9], float t[3], int32_t max_iter, float err_diff, float* err,
+                             int32_t* iters)
+{
+	REQUIRE(h && comm && comm->allreduce_min_u64 && comm->bcast && R && t && max_iter >= 0);
+	g_err.clear();
+	int rc = GOICP_ERR_INTERNAL;
+	const int g = guarded([&] {
+		int it = 0;
+		float e = 0.f;
+		rc = h->e->icp_run_collective(comm, R, t, max_iter, err_diff, &e, &it);
+		if (rc == GOICP_OK) {
+			if (err) *err = e;
+			if (iters) *iters = it;
+		}
+	});
+	if (g != GOICP_OK) return g;
+	if (rc == GOICP_ERR_TIMEOUT) g_err = "collective ICP: a collective missed the communicator's deadline (a rank is lost); exit non-zero";
+	else if (rc == GOICP_ERR_PEER) g_err = "collective ICP: another rank reported a failure";
+	else if (rc != GOICP_OK && g_err.empty()) g_err = "collective ICP failed";
+	return rc;
+}
+
+int goicp_icp_shard_stats_get(goicp_handle h, goicp_icp_shard_stats* out)
+{
+	REQUIRE(h && out);
+	const goicp::IcpShardStats& s = h->e->icp_shard_stats();
+	out->rank = s.rank; out->world = s.world;
+	out->block_begin = s.block_begin; out->block_end = s.block_end; out->blocks = s.blocks; out->sliced = s.sliced;
+	out->queries = s.queries; out->runs = s.runs; out->passes = s.passes; out->collectives = s.collectives;
+	out->sum_wait_ms = s.sum_wait_ms; out->round_trip_ms = s.round_trip_ms;
+	return GOICP_OK;
+}
+
 int goicp_time_icp_pass(goicp_handle h, const float R[9], const float t[3], int32_t iters, float* ms)
 {
 	REQUIRE(h && R && t && iters > 0 && ms);
@@ -465,6 +499,15 @@ int eo_qsize(void* c, int32_t* n) { return guarded([&] { *n = E(c)->queue_size()
 int eo_donate(void* c, int32_t max_nodes, float* nodes7, int32_t* n) { return guarded([&] { *n = E(c)->donate(max_nodes, nodes7); }); }
 int eo_receive(void* c, const float* nodes7, int32_t n) { return guarded([&] { E(c)->receive(nodes7, n); }); }
 int eo_end(void* c) { return guarded([&] { E(c)->register_end(); }); }
+int eo_unrefined(void* c, int32_t* flag) { return guarded([&] { *flag = E(c)->pose_unrefined() ? 1 : 0; }); }
+int eo_refine(void* c, const float pose[12], float* sse, float R[9], float t[3])
+{
+	return guarded([&] {
+		std::memcpy(R, pose, sizeof(float) * 9);
+		std::memcpy(t, pose + 9, sizeof(float) * 3);
+		*sse = E(c)->refine_collective(R, t);
+	});
+}
 }  // namespace
 
 void goicp_shard_options_default(goicp_shard_options* out)
@@ -508,6 +551,30 @@ int goicp_register_sharded_opt(goicp_handle h, const goicp_comm_ops* comm, const
 	return goicp_run_sharded_opt(&eo, comm, opt, stats);
 }
 
+int goicp_register_sharded_collective_icp(goicp_handle h, const goicp_comm_ops* comm, const goicp_shard_options* opt, goicp_shard_stats* stats)
+{
+	REQUIRE(h && comm && opt && comm->allreduce_min_u64 && comm->bcast && opt->rot_pops_per_step >= 1);
+	if (opt->stale_exchange) return fail(GOICP_ERR_INVALID, "goicp_register_sharded_collective_icp: stale_exchange would interleave the refinements' collectives with the exchange");
+	goicp_shard_engine_ops eo{};
+	eo.ctx = h; eo.sse_threshold = h->e->sse_threshold();
+	eo.begin = eo_begin; eo.step = eo_step; eo.pose = eo_pose; eo.offer = eo_offer; eo.queue_size = eo_qsize;
+	eo.donate = eo_donate; eo.receive = eo_receive; eo.end = eo_end;
+	const goicp::ShardIcpHooks hooks{eo_unrefined, eo_refine};
+	struct Scope {
+		goicp::Engine* e;
+		~Scope() { e->set_collective_icp(nullptr); }
+	} scope{h->e};
+	h->e->set_collective_icp(comm);
+	g_err.clear();
+	int rc = GOICP_ERR_INTERNAL;
+	const int g = guarded([&] { rc = goicp::run_sharded(&eo, comm, opt, stats, &hooks); });
+	if (g != GOICP_OK) return g;
+	if (rc == GOICP_ERR_TIMEOUT) g_err = "sharded registration: a collective missed the communicator's deadline (a rank is lost); exit non-zero";
+	else if (rc == GOICP_ERR_PEER) g_err = "sharded registration: rank " + std::to_string(stats ? stats->failed_rank : -1) + " reported a failure";
+	else if (rc != GOICP_OK && g_err.empty()) g_err = "sharded registration: a callback failed";
+	return rc;
+}
+
 int goicp_register_sharded(goicp_handle h, const goicp_comm_ops* comm, int32_t rot_pops_per_step, int32_t rebalance, goicp_shard_stats* stats)
 {
 	goicp_shard_options o;
@@ -521,6 +588,14 @@ int goicp_comm_set_timeout_ms(goicp_comm_ops* comm, int32_t timeout_ms)
 	REQUIRE(comm && comm->ctx && timeout_ms >= 1);
 	const int rc = goicp::comm_set_timeout_ms(comm, timeout_ms);
 	return rc == GOICP_OK ? rc : fail(rc, "goicp_comm_set_timeout_ms: not a communicator made by this library");
+}
+
+int goicp_comm_allreduce_sum_i64(const goicp_comm_ops* comm, int64_t* words, size_t n)
+{
+	REQUIRE(comm && comm->allreduce_min_u64 && comm->bcast && (words || n == 0));
+	const int rc = goicp::comm_allreduce_sum_i64(comm, words, n);
+	if (rc == GOICP_ERR_TIMEOUT) return fail(rc, "goicp_comm_allreduce_sum_i64: the communicator's deadline passed");
+	return rc == GOICP_OK ? rc : fail(rc, "goicp_comm_allreduce_sum_i64 failed");
 }
 
 int goicp_thread_comm_create(int32_t world, goicp_comm_ops* out)

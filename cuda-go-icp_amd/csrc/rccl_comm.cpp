@@ -1,7 +1,8 @@
 // RCCL communicator behind goicp_comm_ops: the exchanges of the sharded search (shard.cpp) as ncclAllReduce(MIN) /
-// ncclBroadcast over xGMI.  Payloads are 40-48 bytes (the donations 1.8 KB), so the collectives are latency-bound;
-// they run on a stream of their own -- never the engine's compute stream -- with one pinned staging block per
-// communicator (H2D, collective, D2H on that stream).  The host never blocks in hipStreamSynchronize: it polls
+// ncclBroadcast over xGMI, and the integer sums of the collective ICP loop as ncclAllReduce(SUM, int64).
+// Payloads are 40-48 bytes (the donations 1.8 KB, the sums 144), so the collectives are latency-bound; they run on a
+// stream of their own -- never the engine's compute stream -- with one pinned staging block per communicator (H2D,
+// collective, D2H on that stream).  The host never blocks in hipStreamSynchronize: it polls
 // hipStreamQuery against the communicator's deadline (default 60 s), so a rank that died or left the protocol turns
 // into GOICP_ERR_TIMEOUT on the others instead of a hang; a communicator that missed a deadline is marked broken and,
 // when the library owns it, torn down with ncclCommAbort.
@@ -84,6 +85,23 @@ int allreduce_min_u64(void* ctx, uint64_t* words, size_t n)
 	return GOICP_OK;
 }
 
+// the sum of the collective ICP loop (goicp_icp_run_collective): 16 totals + 2 control words per iteration, on the same staging path
+int allreduce_sum_i64(void* ctx, int64_t* words, size_t n)
+{
+	RcclComm* c = static_cast<RcclComm*>(ctx);
+	if (c->broken) return GOICP_ERR_TIMEOUT;
+	if (n * sizeof(int64_t) > c->cap) return GOICP_ERR_INVALID;
+	DevScope dev(c->device);
+	std::memcpy(c->h_buf, words, n * sizeof(int64_t));
+	auto fail = [&] { c->broken = true; (void)hipGetLastError(); return GOICP_ERR_DEVICE; };
+	if (hipMemcpyAsync(c->d_buf, c->h_buf, n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail();
+	if (ncclAllReduce(c->d_buf, c->d_buf, n, ncclInt64, ncclSum, c->comm, c->stream) != ncclSuccess) return fail();
+	if (hipMemcpyAsync(c->h_buf, c->d_buf, n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return fail();
+	if (const int rc = wait_stream(c)) return rc;
+	std::memcpy(words, c->h_buf, n * sizeof(int64_t));
+	return GOICP_OK;
+}
+
 int bcast(void* ctx, void* buf, size_t bytes, int32_t root)
 {
 	RcclComm* c = static_cast<RcclComm*>(ctx);
@@ -116,7 +134,7 @@ int finish(RcclComm* c, int32_t rank, int32_t world, goicp_comm_ops* out)
 	out->ctx = c; out->rank = rank; out->world = world;
 	out->allreduce_min_u64 = &allreduce_min_u64;
 	out->bcast = &bcast;
-	comm_register_library_kind(&allreduce_min_u64);
+	comm_register_library_kind(&allreduce_min_u64, &allreduce_sum_i64);
 	return GOICP_OK;
 }
 

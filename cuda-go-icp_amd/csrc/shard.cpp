@@ -29,6 +29,10 @@
 //     arrives one step late only delays pruning (the search stays a BnB with valid bounds), and every rank consumes
 //     the same sequence of exchange results at the same loop index, so stop decisions still agree; a final blocking
 //     exchange after the stop brings every rank to the global best.
+//   * collective refinement (goicp_register_sharded_collective_icp, ShardIcpHooks): a rank adopts an improved upper bound
+//     UNREFINED; the winner's broadcast carries that flag (13 floats), and when it is set every rank runs the collective ICP
+//     (goicp_icp_run_collective: the pass's workgroups split over the ranks, exact integer sums) from the broadcast pose right
+//     after the exchange, re-scores it and offers the result -- one refinement per global winner, none per local candidate;
 //   * a collective that fails (the communicator's deadline passed: GOICP_ERR_TIMEOUT) ends the run on this rank at once --
 //     the other ranks meet their own deadlines; the caller must then exit non-zero, never re-execute.
 #include "comm.hpp"
@@ -81,6 +85,7 @@ struct Snapshot {
 	float sse = std::numeric_limits<float>::infinity(), R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
 	bool finished = true, early_exit = false;
 	float frontier_lb = std::numeric_limits<float>::infinity();
+	bool unrefined = false;          // collective refinement: the best pose is an upper bound not yet refined
 };
 // what every rank reads out of it (identical on all ranks, except comm_rc)
 struct Exchanged {
@@ -89,13 +94,13 @@ struct Exchanged {
 	float gbest = 0.f, glb = 0.f;
 	int owner = 0;
 	bool any_early = false, any_active = false, any_idle = false, pose_moved = false;
-	float pose[12];
+	float pose[13];                  // R|t, and with the collective refinement the winner's unrefined flag
 	int collectives = 0, broadcasts = 0;
 };
 
 // One exchange: the packed all-reduce and, when the global best moved, the owner's pose.  `last_gbest` is the exchange
 // side's own state (the sequence of global bests is the same on every rank).
-Exchanged exchange(const goicp_comm_ops* comm, const Snapshot& s, float* last_gbest)
+Exchanged exchange(const goicp_comm_ops* comm, const Snapshot& s, float* last_gbest, bool with_flag = false)
 {
 	Exchanged x;
 	const float inf = std::numeric_limits<float>::infinity();
@@ -124,7 +129,8 @@ Exchanged exchange(const goicp_comm_ops* comm, const Snapshot& s, float* last_gb
 	if (x.gbest < *last_gbest) {
 		std::memcpy(x.pose, s.R, sizeof(s.R));
 		std::memcpy(x.pose + 9, s.t, sizeof(s.t));
-		x.comm_rc = comm->bcast(comm->ctx, x.pose, sizeof(x.pose), x.owner);
+		x.pose[12] = s.unrefined ? 1.f : 0.f;
+		x.comm_rc = comm->bcast(comm->ctx, x.pose, (with_flag ? 13 : 12) * sizeof(float), x.owner);
 		if (x.comm_rc != GOICP_OK) return x;
 		x.broadcasts = 1;
 		x.pose_moved = true;
@@ -182,9 +188,11 @@ private:
 
 }  // namespace
 
-int run_sharded(const goicp_shard_engine_ops* eng, const goicp_comm_ops* comm, const goicp_shard_options* opt, goicp_shard_stats* stats)
+int run_sharded(const goicp_shard_engine_ops* eng, const goicp_comm_ops* comm, const goicp_shard_options* opt, goicp_shard_stats* stats,
+                const ShardIcpHooks* icp)
 {
 	if (!eng || !comm || !opt || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || opt->rot_pops_per_step < 1) return GOICP_ERR_INVALID;
+	if (icp && (!icp->unrefined || !icp->refine || opt->stale_exchange)) return GOICP_ERR_INVALID;    // the helper thread would interleave collectives
 	const int rank = comm->rank, world = comm->world;
 	// step width: fixed, or the single-GPU driver's ramp (engine.cpp register_step: 8, 16, 32, 64 parents per batch) -- a rank
 	// then runs ONE batch per step and exchanges once per batch.  Every rank computes the same sequence.
@@ -216,6 +224,11 @@ int run_sharded(const goicp_shard_engine_ops* eng, const goicp_comm_ops* comm, c
 		st.step_ms += now_ms() - t0;
 		if (ramp_to) pops = std::min(ramp_to, pops * 2);
 		if (rc == GOICP_OK) rc = eng->pose(eng->ctx, &s.sse, s.R, s.t);
+		if (rc == GOICP_OK && icp) {
+			int32_t u = 0;
+			rc = icp->unrefined(eng->ctx, &u);
+			s.unrefined = u != 0;
+		}
 		if (rc != GOICP_OK) { local_rc = s.local_rc = rc; s.sse = inf; return s; }
 		st.steps++;
 		if (ss.finished) st.steps_idle++;
@@ -232,7 +245,16 @@ int run_sharded(const goicp_shard_engine_ops* eng, const goicp_comm_ops* comm, c
 			final_rc = local_rc != GOICP_OK ? local_rc : GOICP_ERR_PEER;
 			return true;
 		}
-		if (x.pose_moved && local_rc == GOICP_OK) {
+		if (x.pose_moved && icp && x.pose[12] != 0.f) {
+			// every rank is healthy here (a failure word would have ended the loop above): all refine the winner together
+			float e = inf, R[9], t[3];
+			int rc = icp->refine(eng->ctx, x.pose, &e, R, t);
+			if (rc == GOICP_OK) {
+				if (e < x.gbest) rc = eng->offer(eng->ctx, e, R, t);
+				else rc = eng->offer(eng->ctx, x.gbest, x.pose, x.pose + 9);        // ICP did not improve: the upper bound's pose stands
+			}
+			if (rc != GOICP_OK) local_rc = rc;                // every rank failed together inside the refinement, or tells it next time
+		} else if (x.pose_moved && local_rc == GOICP_OK) {
 			float cur = inf, R[9], t[3];
 			int rc = eng->pose(eng->ctx, &cur, R, t);
 			if (rc == GOICP_OK && cur > x.gbest) rc = eng->offer(eng->ctx, x.gbest, x.pose, x.pose + 9);
@@ -303,7 +325,7 @@ int run_sharded(const goicp_shard_engine_ops* eng, const goicp_comm_ops* comm, c
 		while (true) {
 			snap = do_step();
 			const double t0 = now_ms();
-			const Exchanged x = exchange(comm, snap, &last_gbest);
+			const Exchanged x = exchange(comm, snap, &last_gbest, icp != nullptr);
 			st.wait_ms += now_ms() - t0;
 			bool stop = false;
 			if (consume(x, &stop)) break;
@@ -369,7 +391,7 @@ struct ThreadGroup {
 	int arrived = 0, left = 0;
 	uint64_t generation = 0;
 	bool broken = false;             // a rank gave up waiting: every later (and every waiting) collective fails
-	std::vector<uint64_t> acc;       // MIN accumulator of the running all-reduce
+	std::vector<uint64_t> acc;       // MIN (or SUM) accumulator of the running all-reduce
 	std::vector<unsigned char> blob; // broadcast payload
 };
 struct ThreadComm {
@@ -411,6 +433,16 @@ int thread_allreduce(void* ctx, uint64_t* words, size_t n)
 	                  },
 	                  [&] { std::memcpy(words, c->g->acc.data(), n * sizeof(uint64_t)); });
 }
+int thread_allreduce_sum(void* ctx, int64_t* words, size_t n)
+{
+	ThreadComm* c = static_cast<ThreadComm*>(ctx);
+	return rendezvous(c,
+	                  [&] {
+		                  if (c->g->acc.empty()) c->g->acc.assign(words, words + n);
+		                  else for (size_t i = 0; i < n; i++) c->g->acc[i] += (uint64_t)words[i];      // mod 2^64
+	                  },
+	                  [&] { std::memcpy(words, c->g->acc.data(), n * sizeof(uint64_t)); });
+}
 int thread_bcast(void* ctx, void* buf, size_t bytes, int32_t root)
 {
 	ThreadComm* c = static_cast<ThreadComm*>(ctx);
@@ -424,20 +456,54 @@ int thread_bcast(void* ctx, void* buf, size_t bytes, int32_t root)
 int comm_default_timeout_ms() { return env_timeout_ms(); }
 
 namespace {
+struct Kind { CommAllreduceFn min; CommSumFn sum; };
 std::mutex g_kinds_m;
-std::vector<CommAllreduceFn> g_kinds;
+std::vector<Kind> g_kinds;
+// the kind a table belongs to, found by its all-reduce function (never by reading ctx); nullptr for a caller's own table
+const Kind* find_kind(const goicp_comm_ops* comm)
+{
+	if (!comm || !comm->allreduce_min_u64) return nullptr;
+	for (const Kind& k : g_kinds)
+		if (k.min == (CommAllreduceFn)comm->allreduce_min_u64) return &k;
+	return nullptr;
+}
 }  // namespace
 
-void comm_register_library_kind(CommAllreduceFn fn)
+void comm_register_library_kind(CommAllreduceFn fn, CommSumFn sum)
 {
 	std::lock_guard<std::mutex> lk(g_kinds_m);
-	if (std::find(g_kinds.begin(), g_kinds.end(), fn) == g_kinds.end()) g_kinds.push_back(fn);
+	for (const Kind& k : g_kinds)
+		if (k.min == fn) return;
+	g_kinds.push_back(Kind{fn, sum});
 }
 bool comm_is_library_kind(const goicp_comm_ops* comm)
 {
-	if (!comm || !comm->allreduce_min_u64) return false;
 	std::lock_guard<std::mutex> lk(g_kinds_m);
-	return std::find(g_kinds.begin(), g_kinds.end(), (CommAllreduceFn)comm->allreduce_min_u64) != g_kinds.end();
+	return find_kind(comm) != nullptr;
+}
+
+int comm_allreduce_sum_i64(const goicp_comm_ops* comm, int64_t* words, size_t n)
+{
+	if (!comm || !comm->allreduce_min_u64 || !comm->bcast || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || (n && !words))
+		return GOICP_ERR_INVALID;
+	CommSumFn sum = nullptr;
+	{
+		std::lock_guard<std::mutex> lk(g_kinds_m);
+		if (const Kind* k = find_kind(comm)) sum = k->sum;
+	}
+	if (sum) return sum(comm->ctx, words, n);
+	// any other table: every rank broadcasts its words in turn, every rank adds them up in rank order
+	std::vector<uint64_t> mine(words, words + n), buf(n), total(n, 0);
+	for (int r = 0; r < comm->world; r++) {
+		if (r == comm->rank) buf = mine;
+		if (n) {
+			const int rc = comm->bcast(comm->ctx, buf.data(), n * sizeof(uint64_t), r);
+			if (rc != GOICP_OK) return rc;
+		}
+		for (size_t i = 0; i < n; i++) total[i] += buf[i];
+	}
+	std::memcpy(words, total.data(), n * sizeof(uint64_t));
+	return GOICP_OK;
 }
 
 int comm_set_timeout_ms(goicp_comm_ops* comm, int ms)
@@ -455,7 +521,7 @@ int thread_comm_create(int world, goicp_comm_ops* out)
 	ThreadGroup* g = new (std::nothrow) ThreadGroup;
 	if (!g) return GOICP_ERR_INTERNAL;
 	g->world = world; g->refs = world;
-	comm_register_library_kind(&thread_allreduce);
+	comm_register_library_kind(&thread_allreduce, &thread_allreduce_sum);
 	for (int r = 0; r < world; r++) {
 		out[r].ctx = new ThreadComm{CommHeader{kCommMagic, env_timeout_ms()}, g, r};
 		out[r].rank = r; out[r].world = world;

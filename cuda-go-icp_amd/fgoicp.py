@@ -226,6 +226,24 @@ class Registration:
         B.check(self._lib.goicp_icp_step(self.handle))
         return self.poll()
 
+    def icp_run_collective(self, comm_ops, R=None, t=None, max_iter=10000, err_diff=1e-7, raise_on_error=True):
+        """goicp_icp_run_collective: ICP3D::Run with the source points sharded over the ranks of comm_ops (a binding.CCommOps); every rank
+        calls it with the same arguments and gets the world-1 result bit for bit.  -> (status, err, R (3,3), t, iters)"""
+        R = _f32(np.eye(3) if R is None else R, (9,)).copy()
+        t = _f32(np.zeros(3) if t is None else t, (3,)).copy()
+        err, it = C.c_float(), C.c_int32()
+        rc = self._lib.goicp_icp_run_collective(self.handle, C.byref(comm_ops), _fptr(R), _fptr(t), int(max_iter), float(err_diff),
+                                                C.byref(err), C.byref(it))
+        if raise_on_error:
+            B.check(rc)
+        return rc, np.float32(err.value), R.reshape(3, 3), t, it.value
+
+    def icp_shard_stats(self):
+        """goicp_icp_shard_stats_get as a dict: this engine's collective ICP runs since it was created."""
+        st = B.CIcpShardStats()
+        B.check(self._lib.goicp_icp_shard_stats_get(self.handle, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in B.CIcpShardStats._fields_}
+
     def poll(self):
         r = B.CResult()
         B.check(self._lib.goicp_poll(self.handle, C.byref(r)))

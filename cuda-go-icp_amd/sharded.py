@@ -10,6 +10,10 @@ builds the two callback tables the library takes from Python objects:
     Python at all), or the library's in-process thread communicator for N ranks in one process;
   * an engine table over any object with the stepped interface (the tests' CPU stand-in) -- a real engine is driven by
     goicp_register_sharded_opt directly.
+
+The ICP loop itself can be sharded too (goicp_icp_run_collective: each rank evaluates a slice of the pass's workgroups, the
+integer sums are added up over the ranks, every rank gets the world-1 result bit for bit): icp_run_thread_ranks here,
+Registration.icp_run_collective for one rank, and collective_icp=True on the registration drivers.
 """
 import numpy as np
 
@@ -112,17 +116,23 @@ def engine_ops(engine):
     return ops
 
 
-def run_sharded_library(engine_or_ops, comm_ops, rot_pops_per_step=8, rebalance=True, stale=False, raise_on_error=True, ramp_to=0):
+def run_sharded_library(engine_or_ops, comm_ops, rot_pops_per_step=8, rebalance=True, stale=False, raise_on_error=True, ramp_to=0,
+                        collective_icp=False):
     """Drive one rank through the library's protocol.  engine_or_ops: a fgoicp.FastGoICP (real engine) or a
-    CShardEngineOps table.  Returns the goicp_shard_stats as a dict (plus "status": the call's return code when
-    raise_on_error is False)."""
+    CShardEngineOps table.  collective_icp (real engines only): every refinement is a collective ICP over the ranks
+    (goicp_register_sharded_collective_icp).  Returns the goicp_shard_stats as a dict (plus "status": the call's return
+    code when raise_on_error is False)."""
     import ctypes as C
     from . import binding as B
     lib = B.load_library()
     st = B.CShardStats()
     opt = B.CShardOptions(int(rot_pops_per_step), int(bool(rebalance)), int(bool(stale)), int(ramp_to))
     if isinstance(engine_or_ops, B.CShardEngineOps):
+        if collective_icp:
+            raise TypeError("collective_icp needs real engines (fgoicp.FastGoICP)")
         rc = lib.goicp_run_sharded_opt(C.byref(engine_or_ops), C.byref(comm_ops), C.byref(opt), C.byref(st))
+    elif collective_icp:
+        rc = lib.goicp_register_sharded_collective_icp(engine_or_ops.registration.handle, C.byref(comm_ops), C.byref(opt), C.byref(st))
     else:
         rc = lib.goicp_register_sharded_opt(engine_or_ops.registration.handle, C.byref(comm_ops), C.byref(opt), C.byref(st))
     if raise_on_error:
@@ -132,7 +142,8 @@ def run_sharded_library(engine_or_ops, comm_ops, rot_pops_per_step=8, rebalance=
     return out
 
 
-def run_thread_ranks(engines, rot_pops_per_step=8, rebalance=True, stale=False, timeout_ms=None, raise_on_error=True, ramp_to=0):
+def run_thread_ranks(engines, rot_pops_per_step=8, rebalance=True, stale=False, timeout_ms=None, raise_on_error=True, ramp_to=0,
+                     collective_icp=False):
     """len(engines) ranks in ONE process: one host thread per rank over the library's in-process communicator
     (goicp_thread_comm_create) -- N engines on one GPU, or N CPU stand-ins.  engines: fgoicp.FastGoICP objects or
     CShardEngineOps tables.  Returns the per-rank stats (run_sharded_library's dicts)."""
@@ -148,7 +159,7 @@ def run_thread_ranks(engines, rot_pops_per_step=8, rebalance=True, stale=False, 
 
     def worker(r):
         try:
-            stats[r] = run_sharded_library(engines[r], comms[r], rot_pops_per_step, rebalance, stale, raise_on_error, ramp_to)
+            stats[r] = run_sharded_library(engines[r], comms[r], rot_pops_per_step, rebalance, stale, raise_on_error, ramp_to, collective_icp)
         except Exception as e:       # noqa: BLE001 -- reported to the caller below
             errs.append((r, e))
 
@@ -162,6 +173,48 @@ def run_thread_ranks(engines, rot_pops_per_step=8, rebalance=True, stale=False, 
     if errs:
         raise errs[0][1]
     return stats
+
+
+def _run_threads(world, work):
+    """work(r, comm_r) on one host thread per rank over `world` in-process communicators; -> the per-rank results."""
+    import threading
+    from . import binding as B
+    comms = thread_comms(world)
+    lib = B.load_library()
+    out, errs = [None] * world, []
+
+    def worker(r):
+        try:
+            out[r] = work(r, comms[r])
+        except Exception as e:       # noqa: BLE001 -- reported to the caller below
+            errs.append((r, e))
+
+    th = [threading.Thread(target=worker, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    for r in range(world):
+        lib.goicp_thread_comm_destroy(comms[r])
+    if errs:
+        raise errs[0][1]
+    return out
+
+
+def icp_run_thread_ranks(regs, R=None, t=None, max_iter=10000, err_diff=1e-7, timeout_ms=None, raise_on_error=True):
+    """goicp_icp_run_collective on len(regs) ranks in ONE process (fgoicp.Registration objects made from the same clouds and
+    parameters, one host thread each, the in-process communicator).  Returns every rank's (status, err, R, t, iters)."""
+    from . import binding as B
+    lib = B.load_library()
+
+    def work(r, comm):
+        if timeout_ms is not None:
+            B.check(lib.goicp_comm_set_timeout_ms(comm, int(timeout_ms)))
+        Rr = R[r] if isinstance(R, (list, tuple)) else R          # a list: one start pose per rank (the disagreement test)
+        tr = t[r] if isinstance(t, (list, tuple)) else t
+        return regs[r].icp_run_collective(comm, Rr, tr, max_iter, err_diff, raise_on_error=raise_on_error)
+
+    return _run_threads(len(regs), work)
 
 
 def thread_comms(world):

@@ -396,6 +396,43 @@ void goicp_shard_options_default(goicp_shard_options* out);   /* 8 parents in th
 int goicp_run_sharded_opt(const goicp_shard_engine_ops* engine, const goicp_comm_ops* comm, const goicp_shard_options* opt,
                           goicp_shard_stats* stats);
 int goicp_register_sharded_opt(goicp_handle h, const goicp_comm_ops* comm, const goicp_shard_options* opt, goicp_shard_stats* stats);
+/* element-wise SUM over the ranks of n signed 64-bit words, wrapping mod 2^64, in place; blocking, under the communicator's deadline
+ * (GOICP_ERR_TIMEOUT like the other collectives).  A communicator of this library sums natively (thread: a rendezvous; RCCL:
+ * ncclAllReduce(ncclInt64, ncclSum) on its own stream); any other table falls back to `world` broadcasts of the n words, added up on
+ * every rank -- the same totals everywhere. */
+int goicp_comm_allreduce_sum_i64(const goicp_comm_ops* comm, int64_t* words, size_t n);
+/* ICP3D<float>::Run (src/goicp/jly_icp3d.hpp:181-295) with the source points sharded over the ranks -- the semantics of goicp_icp_run,
+ * every rank ending with its world-1 result bit for bit (R, t, err, iters).  Every rank calls it with the same arguments and an engine
+ * made from the same clouds and parameters.  Rank r of G evaluates the workgroups [floor(r B / G), floor((r+1) B / G)) of the world-1
+ * grid of the fixed-point ICP pass (B workgroups of 16 queries: the same queries per workgroup as at world 1, so the same float row
+ * sums) and the ranks add up the 16 integer totals per iteration (goicp_comm_allreduce_sum_i64); every rank then runs the same update
+ * on the same totals, so all agree on the pose, the error and when to stop with no further collective.  One iteration: slice pass,
+ * export, read back, sum over the ranks, upload, update.  A rank whose range is empty takes part with zero totals.
+ * Agreement and failure are collective: the ranks first compare a check word over (R, t, max_iter, err_diff, N, fixed-point scale)
+ * -- ranks that disagree all return GOICP_ERR_INVALID, none hangs -- and every sum carries a health word: a rank whose HIP call
+ * failed keeps exchanging and all ranks leave in the same iteration with their own status or GOICP_ERR_PEER.
+ * Replicated fallback (every rank runs the full loop, no sums; goicp_icp_shard_stats.sliced = 0): trim_fraction > 0, icp_fused = 1,
+ * dt_layout = 0 -- none of these has the fixed-point pass.  The result is still identical on all ranks. */
+int goicp_icp_run_collective(goicp_handle h, const goicp_comm_ops* comm, float R[9], float t[3], int32_t max_iter, float err_diff,
+                             float* err, int32_t* iters);
+typedef struct goicp_icp_shard_stats {
+	int32_t rank, world;
+	int32_t block_begin, block_end;   /* this rank's workgroups [block_begin, block_end) of the world-1 pass grid (last run) */
+	int32_t blocks;                   /* workgroups of that grid */
+	int32_t sliced;                   /* last run: 1 sliced passes, 0 the replicated fallback */
+	int64_t queries;                  /* source points this rank evaluated, over all passes */
+	int64_t runs, passes, collectives;
+	double sum_wait_ms;               /* host time blocked in the sums (waiting for the slowest rank) */
+	double round_trip_ms;             /* host time of the per-iteration round trip: launch, read-back, upload */
+} goicp_icp_shard_stats;
+/* this engine's collective ICP runs, accumulated since goicp_create */
+int goicp_icp_shard_stats_get(goicp_handle h, goicp_icp_shard_stats* out);
+/* goicp_register_sharded_opt with every refinement collective: the initial ICP from the identity runs as goicp_icp_run_collective
+ * inside the protocol's begin, a rank adopts an improved upper bound without refining it, and when an exchange moves the global best
+ * to an unrefined pose every rank refines that pose with goicp_icp_run_collective, re-scores it with the DT and offers the result --
+ * one refinement per global winner instead of one per candidate on every rank.  stale_exchange = 1 is GOICP_ERR_INVALID (its helper
+ * thread would interleave collectives). */
+int goicp_register_sharded_collective_icp(goicp_handle h, const goicp_comm_ops* comm, const goicp_shard_options* opt, goicp_shard_stats* stats);
 /* deadline of every single collective of a communicator made by this library (thread or RCCL); default: the
  * environment's GOICP_COMM_TIMEOUT_MS, else 60 000 ms.  A collective that misses it returns GOICP_ERR_TIMEOUT and leaves
  * the communicator unusable (destroy it; an RCCL communicator the library owns is aborted with ncclCommAbort). */
