@@ -76,7 +76,7 @@ __device__ __forceinline__ float dt_fetch(const DtDesc& dt, int x, int y, int z)
 		e = __umul24(__umul24((unsigned)z, (unsigned)dt.V) + (unsigned)y, (unsigned)dt.V) + (unsigned)x;
 	} else {
 		const unsigned b = __umul24(__umul24((unsigned)z >> 2, (unsigned)dt.VB) + ((unsigned)y >> 2), (unsigned)dt.VB) + ((unsigned)x >> 2);
-		e = (b << 6) | ((((unsigned)z & 3u) << 4) | (((unsigned)y & 3u) << 2) | ((unsigned)x & 3u));
+		e = (b << 6) | (brick_z((unsigned)z) | brick_y((unsigned)y) | brick_x((unsigned)x));
 	}
 	if (LAYOUT == 2) return half_fetch(dt.grid, e);
 	return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(dt.grid) + (size_t)(e << 2));
@@ -145,10 +145,10 @@ __device__ __forceinline__ unsigned axis_offset(const DtDesc& dt, int i)
 	if ((unsigned)i >= (unsigned)dt.V) return kOutside;
 	const unsigned u = (unsigned)i;
 	if (LAYOUT == 0) return AXIS == 0 ? u : (AXIS == 1 ? __umul24(u, (unsigned)dt.V) : __umul24(u, (unsigned)(dt.V * dt.V)));
-	const unsigned hi = u >> 2, lo = u & 3u;
-	if (AXIS == 0) return (hi << 6) | lo;
-	if (AXIS == 1) return (__umul24(hi, (unsigned)dt.VB) << 6) | (lo << 2);
-	return (__umul24(hi, (unsigned)(dt.VB * dt.VB)) << 6) | (lo << 4);
+	const unsigned hi = u >> 2;
+	if (AXIS == 0) return (hi << 6) | brick_x(u);
+	if (AXIS == 1) return (__umul24(hi, (unsigned)dt.VB) << 6) | brick_y(u);
+	return (__umul24(hi, (unsigned)(dt.VB * dt.VB)) << 6) | brick_z(u);
 }
 
 // the 8 cube records of workgroup `group`: read from the batch, or derived from one expansion record with
@@ -254,11 +254,28 @@ __device__ __forceinline__ bool is_sibling_set(const CubeRec cr[kGroup])
 // sums are per pass -- each pass's sums see exactly the operations of a separate evaluation.
 // LAST_ZERO: coeff[NP - 1] is known to be 0 (the upper-bound pass, jly_goicp.cpp:284-285 with maxRotDis = 0): its residual is the looked-up
 // distance itself -- v - 0 and max(v, 0) are v bit for bit, the DT holds no negative value -- so the subtraction and the clamp are not issued.
+// Bricked grids, x siblings less than 4 voxels apart (the deep expansions): the two x lookups of a (y, z) pair often lie in one 16-B x row
+// of a brick, and one 16-B load then serves both (fewer cache-tag lookups than two dword gathers); the values are the same.
+
+// The float at byte offset `off` (bits 2-3) of a 16-B x row, picked with byte permutes: the selectors are per-lane VGPRs, where
+// v_cndmask would hold four lane masks in SGPRs across the four loads (the kernel then spills SGPRs).  row_sel(off) = the two selectors.
+struct RowSel { unsigned lo, hi; };
+__device__ __forceinline__ RowSel row_sel(unsigned off)
+{
+	return RowSel{0x03020100u + (off & 4u) * 0x01010101u, 0x03020100u + ((off >> 1) & 4u) * 0x01010101u};
+}
+__device__ __forceinline__ float row_pick(const float4& r, RowSel s)
+{
+	const unsigned lo = __builtin_amdgcn_perm(__float_as_uint(r.y), __float_as_uint(r.x), s.lo);
+	const unsigned hi = __builtin_amdgcn_perm(__float_as_uint(r.w), __float_as_uint(r.z), s.lo);
+	return __uint_as_float(__builtin_amdgcn_perm(hi, lo, s.hi));
+}
 template <int LAYOUT, int NP, bool LAST_ZERO>
 __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int p0, int p1, const DtDesc& dt, const Rot9& R0, const SiblingSet& ts, float delta,
                                             const float (&coeff)[NP], f2 (&ub2)[NP][4], f2 (&lb2)[NP][4])
 {
 	const f2 delta2 = f2{delta, delta}, ndelta2 = f2{-delta, -delta};
+	const bool merge_x = LAYOUT == 1 && (ts.tx1 - ts.tx0) * dt.scale_f < 4.f;      // uniform: one expansion per workgroup
 	// one bound for the six margins: on the unchecked branch below every index is inside the grid, i.e. |F| < V, and eps(F) = c1 + c2 |F| grows with
 	// |F|; a lane whose F lies outside takes the checked branch, which tests for itself (16 instead of 30 instructions for the test)
 	const float eps_grid = __fmaf_rn((float)(dt.V + 1), dt.c2, dt.c1);
@@ -295,16 +312,38 @@ __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int 
 				// BYTE offsets (the lean variant only runs on grids of at most 256 MB: they fit 32 bits)
 				if (LAYOUT == 0) { fx[k] = (unsigned)ix[k] << 2; fy[k] = __umul24((unsigned)iy[k], V) << 2; fz[k] = __umul24((unsigned)iz[k], V * V) << 2; }
 				else {
-					fx[k] = (((unsigned)ix[k] >> 2) << 8) | (((unsigned)ix[k] & 3u) << 2);
-					fy[k] = (__umul24((unsigned)iy[k] >> 2, (unsigned)dt.VB) << 8) | (((unsigned)iy[k] & 3u) << 4);
-					fz[k] = (__umul24((unsigned)iz[k] >> 2, (unsigned)(dt.VB * dt.VB)) << 8) | (((unsigned)iz[k] & 3u) << 6);
+					fx[k] = (((unsigned)ix[k] >> 2) << 8) | (brick_x((unsigned)ix[k]) << 2);
+					fy[k] = (__umul24((unsigned)iy[k] >> 2, (unsigned)dt.VB) << 8) | (brick_y((unsigned)iy[k]) << 2);
+					fz[k] = (__umul24((unsigned)iz[k] >> 2, (unsigned)(dt.VB * dt.VB)) << 8) | (brick_z((unsigned)iz[k]) << 2);
 				}
 			}
 			const char* gb = reinterpret_cast<const char*>(dt.grid);
+			unsigned yz[4];
+#pragma unroll
+			for (int k = 0; k < 4; k++) yz[k] = fy[k & 1] + fz[k >> 1];
+			f2 vv[4];
+			if (merge_x) {
+				// one 16-B load of the x row holding ix[0] per (y, z) pair; ix[1] comes from the same row unless it lies in the next one
+				// (fx[k] = brick << 8 | (ix[k] & 3) << 2: same row <=> equal above bit 3), and only those lanes make a second dword load
+				const bool split = (fx[0] ^ fx[1]) >= 16u;
+				const RowSel s0 = row_sel(fx[0]), s1 = row_sel(fx[1]);
+				float4 row[4];
+				float v1[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+				for (int k = 0; k < 4; k++) row[k] = *reinterpret_cast<const float4*>(gb + ((fx[0] & ~15u) + yz[k]));
+				if (split) {
+#pragma unroll
+					for (int k = 0; k < 4; k++) v1[k] = *reinterpret_cast<const float*>(gb + (fx[1] + yz[k]));
+				}
+#pragma unroll
+				for (int k = 0; k < 4; k++) vv[k] = f2{row_pick(row[k], s0), split ? v1[k] : row_pick(row[k], s1)};
+			} else {
+#pragma unroll
+				for (int k = 0; k < 4; k++) vv[k] = f2{*reinterpret_cast<const float*>(gb + (fx[0] + yz[k])), *reinterpret_cast<const float*>(gb + (fx[1] + yz[k]))};
+			}
 #pragma unroll
 			for (int k = 0; k < 4; k++) {
-				const unsigned yz = fy[k & 1] + fz[k >> 1];
-				const f2 v = f2{*reinterpret_cast<const float*>(gb + (fx[0] + yz)), *reinterpret_cast<const float*>(gb + (fx[1] + yz))};
+				const f2 v = vv[k];
 #pragma unroll
 				for (int q = 0; q < NP; q++) {
 					f2 vq = v, mm = v;
@@ -664,7 +703,7 @@ __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restri
 				const int b = idx >> 4, part = idx & 15;
 				const int t2 = (int)(((float)b + 0.5f) * rnbx), bx = b - t2 * nbx;
 				const int bz = (int)(((float)t2 + 0.5f) * rnby), by = t2 - bz * nby;
-				const int y = (by0 + by) * 4 + (part & 3) - y0, z = (bz0 + bz) * 4 + (part >> 2) - z0;
+				const int y = (by0 + by) * 4 + (part & 3) - y0, z = (bz0 + bz) * 4 + (part >> 2) - z0;       // piece = x row (brick_y | brick_z) >> 2
 				const size_t gb = ((size_t)(bz0 + bz) * dt.VB + (by0 + by)) * dt.VB + (bx0 + bx);
 				const float4 v = reinterpret_cast<const float4*>(dt.grid)[gb * 16 + part];
 				if ((unsigned)y < (unsigned)DY && (unsigned)z < (unsigned)DZ) *reinterpret_cast<float4*>(&tile[(z * DY + y) * DX + bx * 4]) = v;
@@ -1498,7 +1537,7 @@ __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt
 		const int iz = min(max((int)rintf((qz - dt.zmin_f) * dt.scale_f), 0), V1);
 		size_t off;
 		if (LAYOUT == 0) off = ((size_t)iz * dt.V + iy) * dt.V + ix;
-		else off = (((size_t)(iz >> 2) * dt.VB + (iy >> 2)) * dt.VB + (ix >> 2)) * 64 + (((iz & 3) << 4) | ((iy & 3) << 2) | (ix & 3));
+		else off = brick_index(ix, iy, iz, dt.VB);
 		const int slot = dt.nn_ids[off];
 		const float4 pt = kd.pts[slot];
 		const float d0 = qx - pt.x, d1 = qy - pt.y, d2 = qz - pt.z;
@@ -2706,8 +2745,7 @@ __global__ void dt_finish_kernel(const int32_t* w, DtDesc dt, float* out)
 		out[i] = v;
 	} else {
 		int x = (int)(i % V), y = (int)((i / V) % V), z = (int)(i / ((size_t)V * V));
-		size_t b = ((size_t)(z >> 2) * dt.VB + (y >> 2)) * dt.VB + (x >> 2);
-		out[b * 64 + (((z & 3) << 4) | ((y & 3) << 2) | (x & 3))] = v;
+		out[brick_index(x, y, z, dt.VB)] = v;
 	}
 }
 
@@ -2763,8 +2801,7 @@ __global__ void nnseed_finish_kernel(const int32_t* __restrict__ id, DtDesc dt, 
 	if (i >= n) return;
 	if (LAYOUT == 0) { out[i] = id[i]; return; }
 	const int x = (int)(i % V), y = (int)((i / V) % V), z = (int)(i / ((size_t)V * V));
-	const size_t b = ((size_t)(z >> 2) * dt.VB + (y >> 2)) * dt.VB + (x >> 2);
-	out[b * 64 + (((z & 3) << 4) | ((y & 3) << 2) | (x & 3))] = id[i];
+	out[brick_index(x, y, z, dt.VB)] = id[i];
 }
 hipError_t launch_nn_seed_build(const float4* pts, int nslots, const DtDesc& dt, int32_t* work_d, int32_t* work_id, int32_t* out, hipStream_t stream)
 {

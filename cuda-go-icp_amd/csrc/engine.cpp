@@ -764,10 +764,7 @@ void Engine::dt_download(float* out)
 	HIPCHK(hipMemcpy(tmp.data(), d_dt_, sizeof(float) * nb, hipMemcpyDeviceToHost));
 	for (size_t z = 0; z < V; z++)
 		for (size_t y = 0; y < V; y++)
-			for (size_t x = 0; x < V; x++) {
-				size_t b = ((z >> 2) * VB + (y >> 2)) * VB + (x >> 2);
-				out[(z * V + y) * V + x] = tmp[b * 64 + (((z & 3) << 4) | ((y & 3) << 2) | (x & 3))];
-			}
+			for (size_t x = 0; x < V; x++) out[(z * V + y) * V + x] = tmp[brick_index(x, y, z, VB)];
 }
 
 void Engine::nn_query(const float* q, size_t n, int32_t* idx, float* d2)

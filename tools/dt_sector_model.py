@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""CPU model of the vector-cache tag lookups the headline batch makes in the lean sibling path (device.hip lean_points).
+
+The cache looks up one tag per distinct 64-B sector that a group of lanes (a quad by default) touches in one load instruction.
+This tool rebuilds the bench batch (bench.make_batch, seed 1234: rotations, corners, widths), the source cloud in the engine's
+k-d order (engine.cpp, morton_sort 2) and the DT geometry (dt_expand 2, V 300), forms every voxel index the kernel forms (float
+index path; lanes outside the grid are left out) and counts, per layout:
+  * tags per DT gather instruction (8 dword gathers per point),
+  * tags per VMEM instruction, the float4 point load (16 tags per wavefront) included,
+  * with --merged: the same for 16-B x-row loads when the x siblings are less than 4 voxels apart (one row load per (y, z) pair,
+    a masked dword load for the lanes whose second x lies in the next row),
+  * the distinct sectors one lane's 8 sibling lookups hit, per child spacing.
+Layouts: 4x4x1 / 4x2x2 / 2x2x4 / 2x4x2 (64-B sector shape, x y z, inside 4x4x4 bricks of 256 B) or linear.
+
+  python3 tools/dt_sector_model.py [--layouts 4x4x1,4x2x2,...] [--lanes 4] [--every 16] [--merged] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def kd_order(src):
+    """engine.cpp's k-d order (morton_sort 2): longest-axis median splits, left part a multiple of 256/64/16/4/1, down to single points"""
+    perm = np.arange(len(src))
+    stack = [(0, len(src))]
+    while stack:
+        lo, hi = stack.pop()
+        n = hi - lo
+        if n <= 1:
+            continue
+        sub = perm[lo:hi]
+        pts = src[sub]
+        ax = int(np.argmax(pts.max(0) - pts.min(0)))          # first axis of the largest extent, as the engine's strict '>'
+        unit = 256 if n > 256 else 64 if n > 64 else 16 if n > 16 else 4 if n > 4 else 1
+        nl = ((n // 2 + unit // 2) // unit) * unit
+        if nl == 0:
+            nl = unit
+        if nl >= n:
+            nl = n - (n % unit if n % unit else unit)
+        order = np.lexsort((sub, pts[:, ax]))                 # (value, index): the engine's total order
+        perm[lo:hi] = sub[order]
+        stack.append((lo + nl, hi))
+        stack.append((lo, lo + nl))
+    return perm
+
+
+def dt_geometry(model, V=300, expand=2.0):
+    mn, mx = model.astype(np.float64).min(0), model.astype(np.float64).max(0)
+    c = (mn + mx) / 2
+    lo, hi = c - expand * (mx - c), c + expand * (mx - c)
+    side = (hi - lo).max()
+    return (c - side / 2).astype(np.float32), np.float32(V / side)
+
+
+def element_index(x, y, z, V, layout):
+    if layout == "linear":
+        return (z.astype(np.int64) * V + y) * V + x
+    sx, sy, sz = (int(t) for t in layout.split("x"))
+    VB = (V + 3) // 4
+    bx, by, bz = x & 3, y & 3, z & 3
+    inner = (bx % sx) + sx * ((by % sy) + sy * (bz % sz))
+    sector = (bx // sx) + (4 // sx) * ((by // sy) + (4 // sy) * (bz // sz))
+    return (((z >> 2).astype(np.int64) * VB + (y >> 2)) * VB + (x >> 2)) * 64 + sector * 16 + inner
+
+
+def tags(addr_bytes, valid, lanes):
+    """distinct 64-B sectors per aligned group of `lanes` lanes, summed: addr_bytes / valid of shape (N,), N a multiple of 64"""
+    s = np.where(valid, addr_bytes >> 6, -1).reshape(-1, lanes)
+    s = np.sort(s, 1)
+    distinct = (s[:, 1:] != s[:, :-1]) & (s[:, 1:] >= 0)
+    return int(distinct.sum() + (s[:, 0] >= 0).sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layouts", default="4x4x1,4x2x2,2x2x4,2x4x2,linear")
+    ap.add_argument("--lanes", type=int, default=4, help="lanes that share one tag lookup (4: a quad)")
+    ap.add_argument("--every", type=int, default=16, help="model every k-th expansion of the batch")
+    ap.add_argument("--merged", action="store_true", help="also model 16-B x-row loads for x siblings < 4 voxels apart")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+
+    from conftest import load_pkg, cloud
+    import bench
+    pkg = load_pkg()
+
+    class _Lib:                                              # make_batch's host calls: the geometry does not depend on them
+        @staticmethod
+        def goicp_trans_delta(w):
+            return float(np.float32(np.sqrt(3.0) / 2 * w))
+
+    class _Reg:
+        _lib = _Lib()
+
+        @staticmethod
+        def rot_coeff(level):
+            return np.float32(0)
+
+    rots, recs, _ = bench.make_batch(pkg, _Reg(), 8192, 8, seed=1234)
+    model, data = cloud("model_bunny"), cloud("data_bunny")
+    src = data[kd_order(data)].astype(np.float32)
+    N = len(src)
+    pad = (-N) % 64
+    V = 300
+    mn, scale = dt_geometry(model, V)
+    layouts = a.layouts.split(",")
+    res = {lay: {"gather_tags": 0, "gathers": 0, "merged_tags": 0, "merged_instr": 0} for lay in layouts}
+    spread = {}                                              # child spacing (voxels) -> [sum of distinct sectors per lane, lanes] per layout
+    waves = (N + pad) // 64
+    for e in range(0, 8192, a.every):
+        r = recs[8 * e:8 * e + 8]
+        R = rots[int(r["rot"][0])].reshape(3, 3).astype(np.float32)
+        rp = (src[:, 0:1] * R[:, 0] + src[:, 1:2] * R[:, 1]) + src[:, 2:3] * R[:, 2]
+        t = [(r["tx"][0], r["tx"][1]), (r["ty"][0], r["ty"][2]), (r["tz"][0], r["tz"][4])]
+        idx = [[((rp[:, k] + np.float32(t[k][j]) - mn[k]) * scale + np.float32(0.5)).astype(np.int32) for j in (0, 1)] for k in range(3)]
+        inside = np.ones(N, bool)
+        for k in range(3):
+            for j in (0, 1):
+                inside &= (idx[k][j] >= 0) & (idx[k][j] < V)
+        ix, iy, iz = ([np.pad(np.clip(v, 0, V - 1), (0, pad)) for v in idx[k]] for k in range(3))
+        ok = np.pad(inside, (0, pad))
+        spacing = float((np.float32(t[0][1]) - np.float32(t[0][0])) * scale)
+        for lay in layouts:
+            el = [[[element_index(ix[a_], iy[b], iz[c], V, lay) for c in (0, 1)] for b in (0, 1)] for a_ in (0, 1)]
+            d = res[lay]
+            sect = []
+            for c in range(8):
+                ad = el[c & 1][c >> 1 & 1][c >> 2 & 1] * 4
+                d["gather_tags"] += tags(ad, ok, a.lanes)
+                sect.append(ad >> 6)
+            d["gathers"] += 8 * waves
+            s = np.sort(np.stack(sect, 1)[:N][inside], 1)
+            sp = spread.setdefault("%.2f" % spacing, {})
+            acc = sp.setdefault(lay, [0, 0])
+            acc[0] += int(((s[:, 1:] != s[:, :-1]).sum(1) + 1).sum()); acc[1] += int(inside.sum())
+            if a.merged and lay != "linear":
+                if spacing < 4:
+                    for b in (0, 1):
+                        for c in (0, 1):
+                            row = (el[0][b][c] & ~3) * 4
+                            second = el[1][b][c] * 4
+                            split = ((ix[0] >> 2) != (ix[1] >> 2)) & ok
+                            d["merged_tags"] += tags(row, ok, a.lanes) + tags(second, split, a.lanes)
+                            d["merged_instr"] += waves * (1 + int(split.reshape(-1, 64).any(1).sum()) / waves)
+                else:
+                    for c in range(8):
+                        d["merged_tags"] += tags(el[c & 1][c >> 1 & 1][c >> 2 & 1] * 4, ok, a.lanes)
+                    d["merged_instr"] += 8 * waves
+    out = {"batch": "bench.make_batch(8192 expansions, 8 rotations, seed 1234), every %d-th expansion" % a.every, "N": N, "V": V,
+           "lanes_per_tag_group": a.lanes, "layouts": {}}
+    n_exp = len(range(0, 8192, a.every))
+    for lay, d in res.items():
+        g = d["gather_tags"] / d["gathers"]
+        o = {"tags_per_dt_gather": round(g, 2),
+             "tags_per_vmem_instr": round((d["gather_tags"] + 16 * waves * n_exp) / (d["gathers"] + waves * n_exp), 2),
+             "sectors_per_lane_by_child_spacing_voxels": {k: round(v[lay][0] / max(v[lay][1], 1), 2) for k, v in sorted(spread.items(), key=lambda kv: -float(kv[0]))}}
+        if a.merged and lay != "linear":
+            o["merged_tags_per_point"] = round(d["merged_tags"] / (waves * n_exp), 2)
+            o["unmerged_tags_per_point"] = round(d["gather_tags"] / (waves * n_exp), 2)
+            o["merged_vmem_instr_per_point"] = round(d["merged_instr"] / (waves * n_exp), 2)
+        out["layouts"][lay] = o
+    print(json.dumps(out, indent=1))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
