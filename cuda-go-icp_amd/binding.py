@@ -79,6 +79,10 @@ class CIcpShardStats(C.Structure):
                [("sum_wait_ms", C.c_double), ("round_trip_ms", C.c_double)]
 
 
+class CIcpOptions(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("normal_k", C.c_int32)]
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -140,6 +144,10 @@ SYMBOLS = {
     "goicp_time_icp_pass_cached": (C.c_int, [_vp, _fp, _fp, C.c_int32, _fp]),
     "goicp_nn_query": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp]),
     "goicp_icp_step": (C.c_int, [_vp]),
+    "goicp_icp_options_default": (None, [C.POINTER(CIcpOptions)]),
+    "goicp_set_icp_options": (C.c_int, [_vp, C.POINTER(CIcpOptions)]),
+    "goicp_knn_query": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
+    "goicp_target_normals": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),
     "goicp_poll": (C.c_int, [_vp, C.POINTER(CResult)]),

@@ -1,5 +1,6 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
+//                                [--point-to-plane] [--normal-k K]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -7,6 +8,8 @@
 //               (src/common.h:157-169) but never applies.  WITHOUT this flag the ranges ARE applied (the configs ship
 //               translation +-1.0: a root of width 2, 8x the volume of the CPU path's), so node counts and times on the
 //               reference's own .toml files are then not comparable with the strict-order goldens: use the flag for parity runs.
+//   --point-to-plane   every ICP of the run is point-to-plane (goicp_set_icp_options metric 1; --normal-k K neighbours per target
+//               normal, default 16).  Refused together with --ranks N > 1: the multi-GPU registration runs point-to-point ICP
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -33,8 +36,8 @@ static std::string resolve(const std::string& p, const std::string& toml)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]\n"); return 2; }
-	int iters = 50, verbose = 0, ranks = 1, reference_root = 0;
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K]\n"); return 2; }
+	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
 	for (int i = 2; i < argc; i++) {
@@ -44,6 +47,13 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--verbose")) verbose = 1;
 		else if (!std::strcmp(argv[i], "--ranks") && i + 1 < argc) ranks = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--reference-root")) reference_root = 1;
+		else if (!std::strcmp(argv[i], "--point-to-plane")) plane = 1;
+		else if (!std::strcmp(argv[i], "--normal-k") && i + 1 < argc) normal_k = std::atoi(argv[++i]);
+	}
+	if (plane && ranks > 1) {
+		// the multi-GPU registration runs point-to-point ICP only: refused before any device is touched
+		std::fprintf(stderr, "error: --point-to-plane cannot be combined with --ranks N > 1 (the multi-GPU registration runs point-to-point ICP)\n");
+		return 2;
 	}
 	try {
 		Config config(argv[1]);
@@ -83,6 +93,7 @@ int main(int argc, char** argv)
 		std::mutex mtx;
 		icp::FastGoICP engine(target, source, config.mse_threshold, mtx, &p);
 		goicp_handle h = engine.registration.handle();
+		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
 		goicp_result r;
 		if (config.mode <= 2) {
 			for (int i = 0; i < iters; i++) check(goicp_icp_step(h));

@@ -16,7 +16,10 @@
 //   icp_nn/select/accum  trimmed ICP: NN of every point, radix select of the num nearest, sums
 //   transform_kernel     rigid transform apply
 //   nn_query_kernel      1-NN operator for arbitrary queries
-//   dt_*                 exact Euclidean DT build (seed, three separable min-plus passes, sqrt/scale)
+//   knn_query_kernel     exact k-NN operator (k <= 32), ascending (d2, index)
+//   normal_build_kernel  target normals: k-NN, fp64 covariance, smallest eigenvector (opt-in point-to-plane ICP)
+//   icp_plane_pass_kernel / icp_plane_finalize   point-to-plane ICP iteration: the same walk, 28 fixed-point sums, 6x6 solve
+//   dt_*               exact Euclidean DT build (seed, three separable min-plus passes, sqrt/scale)
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <algorithm>
@@ -2678,6 +2681,499 @@ hipError_t launch_nn_query(const float* q, int n, const KdDesc& kd, const DtDesc
 	if (kd.K == 1) launch_nn_k<1>(q, n, kd, dt, idx, d2, stream);
 	else if (kd.K == 2) launch_nn_k<2>(q, n, kd, dt, idx, d2, stream);
 	else launch_nn_k<3>(q, n, kd, dt, idx, d2, stream);
+	return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Exact k nearest target points (k <= kKnnMax) over the same 64-ary box hierarchy, one 16-lane row per query.
+// The row keeps its sorted list in registers: lane l holds positions l (`ka`) and l + 16 (`kb`) as 64-bit keys
+// (distance bits << 32 | original index) -- distances are >= 0, so the keys order by (d2, index), the tie rule of the
+// 1-NN walk.  The walk is rows_nearest's: start from the nearest-point seed (a real candidate), visit child groups in
+// ascending box distance, prune against the k-th best distance, scan one leaf (16 slots, one per lane) per step; the
+// candidates of a scan that beat the k-th key are inserted one at a time (wave-uniform loop, row-local shuffles).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src)
+{
+	const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
+	return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long knn_key(float d2, int idx) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx; }
+// the row's key at position kn - 1, in every lane of the row
+__device__ __forceinline__ unsigned long long row_kth(unsigned long long ka, unsigned long long kb, int kn, int row)
+{
+	const int p = kn - 1;
+	return shfl_u64(p >= 16 ? kb : ka, row * 16 + (p & 15));
+}
+// insert the candidate keys `cand` of the row's lanes (~0: none) into the sorted list (ka, kb); candidates at or above the k-th key
+// are dropped.  Called by every lane of the wavefront (the loop count is wave-uniform).
+__device__ __forceinline__ void knn_insert(unsigned long long cand, unsigned long long& ka, unsigned long long& kb, int kn, int l, int row)
+{
+	while (true) {
+		const unsigned long long kth = row_kth(ka, kb, kn, row);
+		const bool pend = cand < kth;
+		const unsigned long long bal = __ballot(pend);
+		if (bal == 0ull) break;
+		const unsigned rb = (unsigned)(bal >> (16 * row)) & 0xffffu;
+		const int src = rb ? __ffs((int)rb) - 1 : 0;
+		unsigned long long c = shfl_u64(cand, row * 16 + src);
+		if (!rb) c = ~0ull;                        // this row has nothing pending: inserting the sentinel changes nothing
+		if (rb && l == src) cand = ~0ull;
+		const unsigned long long pa = shfl_u64(ka, row * 16 + (l > 0 ? l - 1 : 0));       // position l - 1
+		const unsigned long long qb = shfl_u64(kb, row * 16 + (l > 0 ? l - 1 : 0));
+		const unsigned long long a15 = shfl_u64(ka, row * 16 + 15);
+		const unsigned long long pb = l > 0 ? qb : a15;                                   // position l + 15
+		const unsigned long long na = ka < c ? ka : ((l == 0 || pa < c) ? c : pa);
+		const unsigned long long nb = kb < c ? kb : (pb < c ? c : pb);
+		ka = na; kb = nb;
+	}
+}
+
+template <int K, int LAYOUT>
+__device__ __forceinline__ void rows_knn(const KdDesc& kd, const DtDesc& dt, const Box6x4& rootb, int l, int row, float qx, float qy, float qz,
+                                         bool active, int kn, unsigned long long& ka, unsigned long long& kb)
+{
+	ka = ~0ull; kb = ~0ull;
+	if (!__any(active)) return;
+	unsigned key[K][4];
+	int node[K];
+	node[0] = 0;
+	boxes_keys4(rootb, qx, qy, qz, key[0]);
+#pragma unroll
+	for (int L = 1; L < K; L++) {
+		node[L] = 0;
+#pragma unroll
+		for (int j = 0; j < 4; j++) key[L][j] = 0xffffffffu;
+	}
+	Box6x4 fb = rootb;
+	if constexpr (K > 1) {
+		row_take(key[0], l, row, node[1]);
+		fb = load_child_boxes4(kd.boxes[1] + (size_t)node[1] * 384, l);
+	}
+	int seed_slot = -1;                            // the seed point enters the list here; its leaf slot is skipped by the scans
+	if (dt.nn_ids) {
+		const int V1 = dt.V - 1;
+		const int ix = min(max((int)rintf((qx - dt.xmin_f) * dt.scale_f), 0), V1);
+		const int iy = min(max((int)rintf((qy - dt.ymin_f) * dt.scale_f), 0), V1);
+		const int iz = min(max((int)rintf((qz - dt.zmin_f) * dt.scale_f), 0), V1);
+		size_t off;
+		if (LAYOUT == 0) off = ((size_t)iz * dt.V + iy) * dt.V + ix;
+		else off = brick_index(ix, iy, iz, dt.VB);
+		const int slot = dt.nn_ids[off];
+		const float4 pt = kd.pts[slot];
+		const float d0 = qx - pt.x, d1 = qy - pt.y, d2 = qz - pt.z;
+		float e = d0 * d0;                                                 // the leaf scan's accumulation order: the same bits
+		e += d1 * d1;
+		e += d2 * d2;
+		if (active && l == 0 && __float_as_int(pt.w) != INT_MAX) ka = knn_key(e, __float_as_int(pt.w));
+		seed_slot = slot;
+	}
+	int d = 0;
+	if constexpr (K > 1) {
+		boxes_keys4(fb, qx, qy, qz, key[1]);
+		d = 1;
+	}
+	bool done = !active;
+	while (__any(!done)) {
+		const unsigned bound = (unsigned)(row_kth(ka, kb, kn, row) >> 32);     // bits of the k-th best distance (+inf bits and above: list not full)
+		bool acted = done;
+		unsigned long long cand = ~0ull;
+#pragma unroll
+		for (int L = K - 1; L >= 0; L--) {
+			if (!acted && d == L) {
+				int c;
+				const unsigned m = row_take(key[L], l, row, c);
+				if ((m & ~3u) > bound) {
+					if (L == 0) { done = true; acted = true; }
+					else d = L - 1;
+				} else if (L == K - 1) {
+					const int s = (node[L] * 64 + c) * kLeafSlots + l;
+					const float4 pt = kd.pts[s];
+					const float d0 = qx - pt.x, d1 = qy - pt.y, d2 = qz - pt.z;
+					float e = d0 * d0;                                      // L2_Simple_Adaptor accumulation order
+					e += d1 * d1;
+					e += d2 * d2;
+					const int id = __float_as_int(pt.w);
+					if (s != seed_slot && id != INT_MAX) cand = knn_key(e, id);
+					acted = true;
+				} else {
+					const int NL = L + 1 < K ? L + 1 : L;
+					node[NL] = node[L] * 64 + c;
+					const Box6x4 cb = load_child_boxes4(kd.boxes[NL] + (size_t)node[NL] * 384, l);
+					boxes_keys4(cb, qx, qy, qz, key[NL]);
+					d = NL;
+					acted = true;
+				}
+			}
+		}
+		knn_insert(cand, ka, kb, kn, l, row);
+	}
+}
+
+template <int K, int LAYOUT>
+__global__ __launch_bounds__(kIcpThreads) void knn_query_kernel(const float* __restrict__ q, int n, int kn, KdDesc kd, DtDesc dt,
+                                                                int32_t* __restrict__ idx, float* __restrict__ d2)
+{
+	const int lane = threadIdx.x & 63, row = lane >> 4, l = lane & 15;
+	const int i = (blockIdx.x * (kIcpThreads / 64) + (threadIdx.x >> 6)) * 4 + row;
+	const bool valid = i < n;
+	const int iq = valid ? i : n - 1;
+	const float qx = q[3 * iq], qy = q[3 * iq + 1], qz = q[3 * iq + 2];
+	unsigned long long ka, kb;
+	rows_knn<K, LAYOUT>(kd, dt, load_child_boxes4(kd.boxes[0], l), l, row, qx, qy, qz, valid, kn, ka, kb);
+	if (!valid) return;
+	if (l < kn) { idx[(size_t)i * kn + l] = (int)(unsigned)ka; d2[(size_t)i * kn + l] = __uint_as_float((unsigned)(ka >> 32)); }
+	if (l + 16 < kn) { idx[(size_t)i * kn + l + 16] = (int)(unsigned)kb; d2[(size_t)i * kn + l + 16] = __uint_as_float((unsigned)(kb >> 32)); }
+}
+
+template <int K>
+static void launch_knn_k(const float* q, int n, int kn, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2, hipStream_t stream)
+{
+	const dim3 grid(icp_blocks(n)), block(kIcpThreads);
+	if (dt.layout) hipLaunchKernelGGL((knn_query_kernel<K, 1>), grid, block, 0, stream, q, n, kn, kd, dt, idx, d2);
+	else hipLaunchKernelGGL((knn_query_kernel<K, 0>), grid, block, 0, stream, q, n, kn, kd, dt, idx, d2);
+}
+
+hipError_t launch_knn_query(const float* q, int n, int k, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2, hipStream_t stream)
+{
+	if (k < 1 || k > kKnnMax || k > kd.M) return hipErrorInvalidValue;
+	if (n <= 0) return hipSuccess;
+	if (kd.K == 1) launch_knn_k<1>(q, n, k, kd, dt, idx, d2, stream);
+	else if (kd.K == 2) launch_knn_k<2>(q, n, k, kd, dt, idx, d2, stream);
+	else launch_knn_k<3>(q, n, k, kd, dt, idx, d2, stream);
+	return hipGetLastError();
+}
+
+// ---- target normals: one row per leaf slot -------------------------------------------------------------------------------
+// fp64 3x3 symmetric eigenproblem by cyclic Jacobi rotations: the rotation formula and the stop test of kabsch_rows' one-sided sweeps
+// (there on the columns of B, here on the symmetric matrix itself).  a = {a00, a01, a02, a11, a12, a22}; returns the eigenvector of the
+// smallest eigenvalue in v and the largest eigenvalue in lmax.
+__device__ __forceinline__ void sym3_smallest(const double a_in[6], double v[3], double& lmax)
+{
+	double A[3][3] = {{a_in[0], a_in[1], a_in[2]}, {a_in[1], a_in[3], a_in[4]}, {a_in[2], a_in[4], a_in[5]}};
+	double E[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};        // columns: eigenvectors
+	for (int sweep = 0; sweep < 32; sweep++) {
+		bool rotated = false;
+		for (int pq = 0; pq < 3; pq++) {
+			const int p = pq == 2 ? 1 : 0, qq = pq == 0 ? 1 : 2;
+			const double app = A[p][p], aqq = A[qq][qq], apq = A[p][qq];
+			if (apq == 0.0 || apq * apq <= 1e-24 * fabs(app * aqq)) continue;
+			rotated = true;
+			// the rotation that zeroes A[p][q]: tan = sign(da) * db / (|da| + sqrt(da^2 + db^2)), da = aqq - app, db = 2 apq
+			const double da = aqq - app, db = 2 * apq;
+			const double tn = (da >= 0 ? db : -db) / (fabs(da) + sqrt(da * da + db * db));
+			const double cs = rsqrt(1 + tn * tn), sn = cs * tn;
+			for (int k = 0; k < 3; k++) {                           // A <- A G (columns p, q)
+				const double akp = A[k][p], akq = A[k][qq];
+				A[k][p] = cs * akp - sn * akq; A[k][qq] = sn * akp + cs * akq;
+			}
+			for (int k = 0; k < 3; k++) {                           // A <- G^T A (rows p, q)
+				const double apk = A[p][k], aqk = A[qq][k];
+				A[p][k] = cs * apk - sn * aqk; A[qq][k] = sn * apk + cs * aqk;
+			}
+			for (int k = 0; k < 3; k++) {
+				const double ekp = E[k][p], ekq = E[k][qq];
+				E[k][p] = cs * ekp - sn * ekq; E[k][qq] = sn * ekp + cs * ekq;
+			}
+		}
+		if (!rotated) break;
+	}
+	int ks = 0;
+	if (A[1][1] < A[ks][ks]) ks = 1;
+	if (A[2][2] < A[ks][ks]) ks = 2;
+	lmax = fmax(A[0][0], fmax(A[1][1], A[2][2]));
+	v[0] = E[0][ks]; v[1] = E[1][ks]; v[2] = E[2][ks];
+}
+
+// row sum of a double over the 16 lanes of a row (fixed butterfly: the same bits in every lane)
+__device__ __forceinline__ double row_sum_f64(double x)
+{
+	x += __shfl_xor(x, 1, 64);
+	x += __shfl_xor(x, 2, 64);
+	x += __shfl_xor(x, 4, 64);
+	x += __shfl_xor(x, 8, 64);
+	return x;
+}
+
+template <int K, int LAYOUT>
+__global__ __launch_bounds__(kIcpThreads) void normal_build_kernel(const float* __restrict__ target, int nslots, int kn, float cx, float cy, float cz,
+                                                                   KdDesc kd, DtDesc dt, float4* __restrict__ normals)
+{
+	const int lane = threadIdx.x & 63, row = lane >> 4, l = lane & 15;
+	const int s = (blockIdx.x * (kIcpThreads / 64) + (threadIdx.x >> 6)) * 4 + row;     // leaf slot of this row
+	const float4 p = kd.pts[s < nslots ? s : nslots - 1];
+	const bool valid = s < nslots && __float_as_int(p.w) != INT_MAX;
+	unsigned long long ka, kb;
+	rows_knn<K, LAYOUT>(kd, dt, load_child_boxes4(kd.boxes[0], l), l, row, p.x, p.y, p.z, valid, kn, ka, kb);
+	// neighbours at positions l and l + 16 (< kn) of the row: their coordinates in fp64; mean, then the covariance about it
+	const bool ua = valid && l < kn, ub = valid && l + 16 < kn;
+	const int ia = ua ? (int)(unsigned)ka : 0, ib = ub ? (int)(unsigned)kb : 0;
+	double xa[3] = {0, 0, 0}, xb[3] = {0, 0, 0};
+	if (ua) { xa[0] = target[3 * (size_t)ia]; xa[1] = target[3 * (size_t)ia + 1]; xa[2] = target[3 * (size_t)ia + 2]; }
+	if (ub) { xb[0] = target[3 * (size_t)ib]; xb[1] = target[3 * (size_t)ib + 1]; xb[2] = target[3 * (size_t)ib + 2]; }
+	double mu[3];
+#pragma unroll
+	for (int k = 0; k < 3; k++) mu[k] = row_sum_f64(xa[k] + xb[k]) / (double)kn;
+	double cov[6];
+	{
+		const double a0 = ua ? xa[0] - mu[0] : 0.0, a1 = ua ? xa[1] - mu[1] : 0.0, a2 = ua ? xa[2] - mu[2] : 0.0;
+		const double b0 = ub ? xb[0] - mu[0] : 0.0, b1 = ub ? xb[1] - mu[1] : 0.0, b2 = ub ? xb[2] - mu[2] : 0.0;
+		cov[0] = row_sum_f64(a0 * a0 + b0 * b0);
+		cov[1] = row_sum_f64(a0 * a1 + b0 * b1);
+		cov[2] = row_sum_f64(a0 * a2 + b0 * b2);
+		cov[3] = row_sum_f64(a1 * a1 + b1 * b1);
+		cov[4] = row_sum_f64(a1 * a2 + b1 * b2);
+		cov[5] = row_sum_f64(a2 * a2 + b2 * b2);
+	}
+	if (!valid || l != 0) return;
+	double v[3], lmax;
+	sym3_smallest(cov, v, lmax);
+	float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+	if (lmax > 1e-30) {
+		const double nv = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+		n0 = (float)(v[0] / nv); n1 = (float)(v[1] / nv); n2 = (float)(v[2] / nv);
+		// sign: n . (p - centroid) >= 0 on the stored floats; a zero product -> the first nonzero component positive
+		const double dx = (double)p.x - (double)cx, dy = (double)p.y - (double)cy, dz = (double)p.z - (double)cz;
+		double dot = (double)n0 * dx;
+		dot += (double)n1 * dy;
+		dot += (double)n2 * dz;
+		const float first = n0 != 0.f ? n0 : (n1 != 0.f ? n1 : n2);
+		if (dot < 0.0 || (dot == 0.0 && first < 0.f)) { n0 = -n0; n1 = -n1; n2 = -n2; }
+	}
+	normals[__float_as_int(p.w)] = make_float4(n0, n1, n2, 0.f);      // by original index: the pass gathers by the neighbour's index
+}
+
+template <int K>
+static void launch_normals_k(const float* target, int nslots, int kn, const float c[3], const KdDesc& kd, const DtDesc& dt, float4* normals, hipStream_t stream)
+{
+	const dim3 grid(icp_blocks(nslots)), block(kIcpThreads);
+	if (dt.layout) hipLaunchKernelGGL((normal_build_kernel<K, 1>), grid, block, 0, stream, target, nslots, kn, c[0], c[1], c[2], kd, dt, normals);
+	else hipLaunchKernelGGL((normal_build_kernel<K, 0>), grid, block, 0, stream, target, nslots, kn, c[0], c[1], c[2], kd, dt, normals);
+}
+
+hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const float centroid[3], const KdDesc& kd, const DtDesc& dt, float4* normals,
+                               hipStream_t stream)
+{
+	if (k < 1 || k > kKnnMax || k > kd.M || nslots <= 0) return hipErrorInvalidValue;
+	if (kd.K == 1) launch_normals_k<1>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
+	else if (kd.K == 2) launch_normals_k<2>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
+	else launch_normals_k<3>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
+	return hipGetLastError();
+}
+
+// ---- point-to-plane ICP iteration ------------------------------------------------------------------------------------------
+// The pass: icp_pass_kernel's query assignment and walk (rows_nearest, four leaves per step, no neighbour cache), so the neighbour and
+// its distance are the same bits; the owner lane of a row then forms the row's 28 terms of the Gauss-Newton system linearised about
+// the pivot cq (the current transformed source centroid): a = q - cq, r = (q - m) . n, J = (a x n, n) -> the upper triangle of J J^T
+// (21), J r (6), d^2.  Float row sums in fixed order per workgroup, then 64-bit fixed-point adds into kIcpAccReplicas x kIcpPlaneStride
+// accumulators: integer addition is associative, so the totals do not depend on the arrival order, at any N.
+template <int K, int LAYOUT, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_kernel(const float4* __restrict__ src, int N,
+                                                                       const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+{
+	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
+	const int gb = (int)blockIdx.x;
+	const int nw = (N + 3) >> 2, wv = gb * (kIcpThreads / 64) + wave;
+	const int i = STRIDED ? wv + row * nw : wv * 4 + row;
+	const bool valid = wv < nw && i < N;
+	const Box6x4 rootb = load_child_boxes4(kd.boxes[0], l);
+	const int ic = valid ? i : N - 1;
+	const float4 p = src[ic];
+	if (st->converged) return;
+	const float qx = st->R[0] * p.x + st->R[1] * p.y + st->R[2] * p.z + st->t[0];
+	const float qy = st->R[3] * p.x + st->R[4] * p.y + st->R[5] * p.z + st->t[1];
+	const float qz = st->R[6] * p.x + st->R[7] * p.y + st->R[8] * p.z + st->t[2];
+	const RowNn r = rows_nearest<K, LAYOUT, false, 4>(kd, dt, rootb, l, row, qx, qy, qz, valid);
+	const int wrow = wave * 4 + row;
+	const bool owner = valid ? r.mine : l == 0;
+	if (owner) {
+		// the walk's registers are dead here; the terms go to LDS as they are formed (no array of 28 live values)
+		float* dst = red[wrow];
+		float J[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f, d2 = 0.f;
+		if (valid) {
+			const float4 nm = normals[r.idx];                         // one gather per correspondence (by original index: the walk's slot is dead)
+			const float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];
+			const float ex = qx - r.mx, ey = qy - r.my, ez = qz - r.mz;
+			res = ex * nm.x;
+			res += ey * nm.y;
+			res += ez * nm.z;
+			J[0] = ay * nm.z - az * nm.y;
+			J[1] = az * nm.x - ax * nm.z;
+			J[2] = ax * nm.y - ay * nm.x;
+			J[3] = nm.x; J[4] = nm.y; J[5] = nm.z;
+			d2 = r.best;
+		}
+		int k = 0;
+#pragma unroll
+		for (int a = 0; a < 6; a++)
+#pragma unroll
+			for (int b = a; b < 6; b++) dst[k++] = J[a] * J[b];
+#pragma unroll
+		for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
+		dst[27] = d2;
+	}
+	__syncthreads();
+	if (threadIdx.x < kIcpPlaneTerms) {
+		float sum = red[0][threadIdx.x];
+#pragma unroll
+		for (int x = 1; x < kIcpThreads / 16; x++) sum += red[x][threadIdx.x];
+		const long long v = __double2ll_rn((double)sum * (double)st->acc_scale);
+		unsigned long long* a = acc + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + threadIdx.x;
+		__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+// One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
+// Gauss-Newton step (A + mu I) x = -b by fp64 Cholesky, mu = 1e-12 trace(A); omega = x[0:3], tau = x[3:6]; dR = Rodrigues(omega);
+// R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is not positive definite (no usable normal) leaves
+// the pose unchanged: the next pass then scores the same error and the loop stops.
+__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+{
+	__shared__ double sums[kIcpPlaneStride];
+	__shared__ IcpState st;
+	static_assert(sizeof(IcpState) / 4 <= kFinAccThreads && kIcpPlaneStride * 2 == kFinAccThreads, "one state word per lane; two replicas per pass of the wavefront");
+	const int t = threadIdx.x;
+	icp_state_to_lds(state, st, t);
+	if (state->converged) return;                 // uniform; the pass added nothing
+	constexpr int kPer = kIcpAccReplicas * kIcpPlaneStride / kFinAccThreads;
+	unsigned long long v[kPer];
+#pragma unroll
+	for (int j = 0; j < kPer; j++) v[j] = acc[kFinAccThreads * j + t];
+#pragma unroll
+	for (int j = 0; j < kPer; j++) acc[kFinAccThreads * j + t] = 0ull;   // the next pass starts from zero
+	unsigned long long x = 0;
+#pragma unroll
+	for (int j = 0; j < kPer; j++) x += v[j];
+	x += (unsigned long long)__shfl_xor((long long)x, 32, 64);
+	__syncthreads();                              // the state words are in LDS
+	if (t < kIcpPlaneStride) sums[t] = (double)(long long)x * (double)st.acc_inv;
+	__syncthreads();
+	if (t != 0) return;
+	const float err_new = (float)sums[27];
+	const int passes = st.passes + 1;
+	if (st.frozen) { state->err_new = err_new; state->passes = passes; return; }
+	if (st.err > 0.f && st.err - err_new < st.err_diff_n) {                // jly_icp3d.hpp:255, as finalize_rows
+		state->err_new = err_new; state->passes = passes; state->converged = 1;
+		return;
+	}
+	// every loop below has constant bounds and is unrolled: the 6x6 system lives in registers (no scratch)
+	double A[6][6], b[6];
+	{
+		int k = 0;
+#pragma unroll
+		for (int a = 0; a < 6; a++)
+#pragma unroll
+			for (int c = a; c < 6; c++) { A[a][c] = sums[k]; A[c][a] = sums[k]; k++; }
+#pragma unroll
+		for (int a = 0; a < 6; a++) b[a] = sums[21 + a];
+	}
+	double tr = 0.0;
+#pragma unroll
+	for (int a = 0; a < 6; a++) tr += A[a][a];
+	const double mu = 1e-12 * tr;
+#pragma unroll
+	for (int a = 0; a < 6; a++) A[a][a] += mu;
+	// Cholesky A = L L^T in place (lower triangle), then L y = -b, L^T x = y
+	bool ok = tr > 0.0;
+#pragma unroll
+	for (int j = 0; j < 6; j++) {
+		double dj = A[j][j];
+#pragma unroll
+		for (int k = 0; k < j; k++) dj -= A[j][k] * A[j][k];
+		ok = ok && dj > 0.0;
+		const double ljj = ok ? sqrt(dj) : 1.0;
+		A[j][j] = ljj;
+#pragma unroll
+		for (int i2 = j + 1; i2 < 6; i2++) {
+			double s2 = A[i2][j];
+#pragma unroll
+			for (int k = 0; k < j; k++) s2 -= A[i2][k] * A[j][k];
+			A[i2][j] = s2 / ljj;
+		}
+	}
+	double xs[6], y[6];
+#pragma unroll
+	for (int i2 = 0; i2 < 6; i2++) {
+		double s2 = -b[i2];
+#pragma unroll
+		for (int k = 0; k < i2; k++) s2 -= A[i2][k] * y[k];
+		y[i2] = s2 / A[i2][i2];
+	}
+#pragma unroll
+	for (int i2 = 5; i2 >= 0; i2--) {
+		double s2 = y[i2];
+#pragma unroll
+		for (int k = i2 + 1; k < 6; k++) s2 -= A[k][i2] * xs[k];
+		xs[i2] = s2 / A[i2][i2];
+	}
+#pragma unroll
+	for (int a = 0; a < 6; a++) xs[a] = ok ? xs[a] : 0.0;
+	// dR = Rodrigues(omega) = I + sin(th)/th W + (1 - cos(th))/th^2 W^2, W = [omega]x
+	const double wx = xs[0], wy = xs[1], wz = xs[2];
+	const double th = sqrt(wx * wx + wy * wy + wz * wz);
+	double dR[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+	if (th > 0.0) {
+		const double s1 = sin(th) / th, c1 = (1.0 - cos(th)) / (th * th);
+		const double W[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
+#pragma unroll
+		for (int a = 0; a < 3; a++)
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				double w2 = 0.0;
+#pragma unroll
+				for (int k = 0; k < 3; k++) w2 += W[a][k] * W[k][c];
+				dR[a][c] += s1 * W[a][c] + c1 * w2;
+			}
+	}
+	float Rn[9], tn[3];
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			double s2 = 0.0;
+#pragma unroll
+			for (int k = 0; k < 3; k++) s2 += dR[a][k] * (double)st.R[3 * k + c];
+			Rn[3 * a + c] = (float)s2;
+		}
+		double s3 = 0.0;
+#pragma unroll
+		for (int k = 0; k < 3; k++) s3 += dR[a][k] * ((double)st.t[k] - (double)st.cq[k]);
+		tn[a] = (float)(s3 + (double)st.cq[a] + xs[3 + a]);
+	}
+#pragma unroll
+	for (int a = 0; a < 9; a++) state->R[a] = Rn[a];
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+		state->t[a] = tn[a];
+		state->cq[a] = Rn[3 * a] * st.src_centroid[0] + Rn[3 * a + 1] * st.src_centroid[1] + Rn[3 * a + 2] * st.src_centroid[2] + tn[a];
+	}
+	state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = st.iters + 1;
+}
+
+template <int K>
+static void launch_plane_k(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc,
+                           hipStream_t stream)
+{
+	const dim3 grid(icp_blocks(N)), block(kIcpThreads);
+	const bool strided = N <= kIcpStridedMaxN;       // the point-to-point pass's choice: strangers per wavefront for small clouds
+	if (dt.layout) {
+		if (strided) hipLaunchKernelGGL((icp_plane_pass_kernel<K, 1, true>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
+		else hipLaunchKernelGGL((icp_plane_pass_kernel<K, 1, false>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
+	} else {
+		if (strided) hipLaunchKernelGGL((icp_plane_pass_kernel<K, 0, true>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
+		else hipLaunchKernelGGL((icp_plane_pass_kernel<K, 0, false>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
+	}
+}
+
+hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
+                                      unsigned long long* acc, hipStream_t stream)
+{
+	if (!normals || !acc) return hipErrorInvalidValue;
+	if (kd.K == 1) launch_plane_k<1>(src, N, st, kd, dt, normals, acc, stream);
+	else if (kd.K == 2) launch_plane_k<2>(src, N, st, kd, dt, normals, acc, stream);
+	else launch_plane_k<3>(src, N, st, kd, dt, normals, acc, stream);
+	hipLaunchKernelGGL(icp_plane_finalize, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
 	return hipGetLastError();
 }
 

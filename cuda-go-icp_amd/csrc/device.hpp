@@ -285,6 +285,22 @@ hipError_t launch_transform(float4* src, int N, const Pose& pose, hipStream_t st
 hipError_t launch_nn_query(const float* q_xyz, int n, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2,
                            hipStream_t stream);
 
+// ---- point-to-plane ICP (opt-in, goicp_set_icp_options) ---------------------------------------------------------------------
+constexpr int kKnnMax = 32;        // most neighbours of the k-NN walk (two list entries per lane of a 16-lane row)
+constexpr int kIcpPlaneTerms = 28; // upper triangle of J J^T (21), J r (6), d^2
+constexpr int kIcpPlaneStride = 32; // accumulator words per replica (28 used)
+// exact k-NN of n queries (1 <= k <= min(kKnnMax, M), else hipErrorInvalidValue): idx / d2 are n x k, ascending (d2, original index)
+hipError_t launch_knn_query(const float* q_xyz, int n, int k, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2, hipStream_t stream);
+// target normals, one float4 per target point in original order (M; the leaf slots of kd.pts are walked): the k nearest target points (the point included),
+// fp64 covariance about their mean, eigenvector of the smallest eigenvalue, oriented away from `centroid`; degenerate -> 0.
+// target_xyz: the M target points in original order on the device
+hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const float centroid[3], const KdDesc& kd, const DtDesc& dt, float4* normals,
+                               hipStream_t stream);
+// one point-to-plane iteration (pass + one-wavefront finalize) on the device-resident state; acc: kIcpAccReplicas x kIcpPlaneStride
+// zeroed 64-bit words (kept zero between iterations by the finalize); the state's acc_scale / acc_inv scale the sums
+hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, const float4* normals,
+                                      unsigned long long* acc, hipStream_t stream);
+
 // min of n floats (+ first index attaining it, may be null): one workgroup; v must be 16-byte aligned
 hipError_t launch_reduce_min(const float* v, int n, float* out_min, int* out_idx, hipStream_t stream);
 

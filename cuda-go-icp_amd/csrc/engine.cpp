@@ -560,6 +560,7 @@ void Engine::release()
 	hipFree(d_cubes_); hipFree(d_rots_); hipFree(d_ub_); hipFree(d_lb_); hipFree(d_scratch_);
 	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
 	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
+	hipFree(d_icp_acc_plane_); d_icp_acc_plane_ = nullptr; hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
 	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
 	hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
@@ -783,6 +784,76 @@ void Engine::nn_query(const float* q, size_t n, int32_t* idx, float* d2)
 	HIPCHK(hipStreamSynchronize(stream_));
 }
 
+void Engine::knn_query(const float* q, size_t n, int k, int32_t* idx, float* d2)
+{
+	if (k < 1 || k > kKnnMax || (size_t)k > M_) throw std::invalid_argument("goicp_knn_query: k must be in [1, min(32, M)]");
+	if (n == 0) return;
+	if (n > (size_t)INT32_MAX / kKnnMax) throw std::invalid_argument("goicp_knn_query: too many queries");
+	DeviceGuard guard(dev_);
+	// one grow-only scratch block: queries | indices (n x k) | distances (n x k)
+	char* base = static_cast<char*>(scratch_bytes(sizeof(float) * 3 * n + (sizeof(int32_t) + sizeof(float)) * n * k));
+	float* dq = reinterpret_cast<float*>(base);
+	int32_t* di = reinterpret_cast<int32_t*>(base + sizeof(float) * 3 * n);
+	float* dd = reinterpret_cast<float*>(base + sizeof(float) * 3 * n + sizeof(int32_t) * n * k);
+	HIPCHK(hipMemcpyAsync(dq, q, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_knn_query(dq, (int)n, k, kd_, dt_, di, dd, stream_));
+	HIPCHK(hipMemcpyAsync(idx, di, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(d2, dd, sizeof(float) * n * k, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+}
+
+void Engine::ensure_normals(int k)
+{
+	if (normals_k_ == k && d_normals_) return;
+	if ((size_t)k > M_) throw std::invalid_argument("goicp_set_icp_options: normal_k exceeds the number of target points");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	if (!d_normals_) HIPCHK(hipMalloc(&d_normals_, sizeof(float4) * M_));
+	if (!d_icp_acc_plane_) {
+		HIPCHK(hipMalloc(&d_icp_acc_plane_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
+		HIPCHK(hipMemsetAsync(d_icp_acc_plane_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
+	}
+	HIPCHK(hipMemsetAsync(d_normals_, 0, sizeof(float4) * M_, stream_));
+	DevBuf<float> tgt(3 * M_);
+	HIPCHK(hipMemcpyAsync(tgt.p, h_target_.data(), sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_normal_build(tgt.p, (int)kd_slots_, k, model_centroid_, kd_, dt_, d_normals_, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	normals_k_ = k;
+	normal_build_ms_ = now_ms() - t0;
+	if (p_.verbose) std::fprintf(stderr, "[goicp] target normals (k = %d): %.2f ms\n", k, normal_build_ms_);
+}
+
+void Engine::set_icp_options(int metric, int normal_k)
+{
+	if (metric != 0 && metric != 1) throw std::invalid_argument("goicp_set_icp_options: metric must be 0 (point-to-point) or 1 (point-to-plane)");
+	if (normal_k < 3 || normal_k > kKnnMax) throw std::invalid_argument("goicp_set_icp_options: normal_k must be in [3, 32]");
+	if (metric == 1 && p_.trim_fraction > 0.f) throw std::invalid_argument("goicp_set_icp_options: point-to-plane ICP with trim_fraction > 0 is not supported");
+	if (registering_.load()) throw std::invalid_argument("goicp_set_icp_options: not while a registration runs");
+	if (metric == 1) {
+		ensure_normals(normal_k);
+		if (icp_metric_ != 1) {
+			// the first launch of the plane kernels (code object load) belongs here, not to the first refinement: one frozen pass
+			DeviceGuard guard(dev_);
+			const float I0[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z0[3] = {0, 0, 0};
+			icp_metric_ = 1;
+			icp_state_init(I0, Z0, 0.f, 0, 1);
+			icp_launch_one();
+			HIPCHK(hipStreamSynchronize(stream_));
+		}
+	}
+	icp_metric_ = metric;
+	normal_k_ = normal_k;
+}
+
+void Engine::target_normals(float* out)
+{
+	ensure_normals(normal_k_);
+	DeviceGuard guard(dev_);
+	std::vector<float4> n(M_);
+	HIPCHK(hipMemcpy(n.data(), d_normals_, sizeof(float4) * M_, hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < M_; i++) { out[3 * i] = n[i].x; out[3 * i + 1] = n[i].y; out[3 * i + 2] = n[i].z; }
+}
+
 void Engine::source_transformed(const float R[9], const float t[3], float* out)
 {
 	// rigid transform apply on the device (kernTransform, src/goicp_kernel.cu:16-22), then back to the
@@ -841,7 +912,9 @@ void Engine::icp_state_init(const float R[9], const float t[3], float err_diff, 
 
 void Engine::icp_launch_one()
 {
-	if (inliers_ < (int)N_)
+	if (icp_metric_ == 1)       // point-to-plane (set_icp_options refuses it together with trimming)
+		HIPCHK(launch_icp_iteration_plane(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_normals_, d_icp_acc_plane_, stream_));
+	else if (inliers_ < (int)N_)
 		HIPCHK(launch_icp_iteration_trim(d_src_, (int)N_, inliers_, d_icp_state_, kd_, dt_, d_nn_d2_, d_nn_slot_, d_include_, d_icp_partials_, stream_));
 	else
 		HIPCHK(launch_icp_iteration(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_icp_partials_, p_.icp_fused ? d_icp_ticket_ : nullptr,
@@ -938,7 +1011,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 	DeviceGuard guard(dev_);
 	TraceRange tr("goicp:icp_run_collective");
 	const int rank = comm->rank, world = comm->world;
-	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0;
+	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0 && icp_metric_ == 0;   // point-to-plane: replicated
 	IcpShardStats& ss = icp_shard_;
 	ss.rank = rank; ss.world = world; ss.sliced = sliced ? 1 : 0;
 	ss.blocks = icp_blocks((int)N_);
@@ -963,7 +1036,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 	});
 	{
 		uint64_t h = 0xcbf29ce484222325ull;
-		const int32_t ints[4] = {max_iter, (int32_t)N_, sliced ? 1 : 0, world};
+		const int32_t ints[5] = {max_iter, (int32_t)N_, sliced ? 1 : 0, world, icp_metric_};
 		h = fnv1a(h, R, sizeof(float) * 9);
 		h = fnv1a(h, t, sizeof(float) * 3);
 		h = fnv1a(h, &err_diff, sizeof(err_diff));
@@ -974,7 +1047,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 		if (rc != GOICP_OK) return rc;
 		ss.collectives++;
 		if (w[2] != kHealthyWord) return leave(w[2]);
-		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff) or clouds");
+		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric) or clouds");
 	}
 
 	const long long passes0 = cnt_.icp_iters;
@@ -1841,6 +1914,7 @@ void Engine::offer_global_best(float sse, const float R[9], const float t[3])
 void Engine::register_begin()
 {
 	DeviceGuard guard(dev_);
+	registering_.store(1);
 	cancel_.store(false);
 	early_exit_ = converged_ = false;
 	rot_ramp_ = 8;
@@ -2308,12 +2382,14 @@ void Engine::receive(const float* in, int n)
 void Engine::register_end()
 {
 	publish(true);
+	registering_.store(0);
 }
 
 void Engine::run()
 {
 	DeviceGuard guard(dev_);
 	TraceRange tr("goicp:register");
+	struct Idle { std::atomic<int>& r; ~Idle() { r.store(0); } } idle{registering_};   // also when the registration throws
 	double t0 = now_ms();
 	register_begin();
 	while (true) {

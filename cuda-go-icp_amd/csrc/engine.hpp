@@ -158,6 +158,13 @@ public:
 	float refine_collective(float R[9], float t[3]);
 	float time_icp_pass(const float R[9], const float t[3], int iters, bool cached = false);   // cached: every query hits the neighbour cache (steady state); else every query walks
 	void nn_query(const float* q_xyz, size_t n, int32_t* idx, float* d2);
+	// goicp_icp_options: the metric of every ICP this engine runs (0 point-to-point, 1 point-to-plane) and the neighbours per target
+	// normal; metric 1 builds the normals (once per normal_k).  Refused while a registration runs and together with trimming
+	void set_icp_options(int metric, int normal_k);
+	int icp_metric() const { return icp_metric_; }
+	void knn_query(const float* q_xyz, size_t n, int k, int32_t* idx, float* d2);
+	double normal_build_ms() const { return normal_build_ms_; }   // exact, ascending (d2, index), n x k
+	void target_normals(float* normals_xyz);                                         // M x 3, original target order (built on first use)
 	void icp_step();   // one ICP iteration on the engine's current pose (ICP::kdTreeGPUStep)
 	// measured ceiling of the gather path (4-byte loads into the resident DT): lookups/s; mode 0 coalesced, 1 divergent
 	double probe_gather(int mode, size_t window_bytes);
@@ -352,6 +359,13 @@ private:
 	// the collective ICP loop: the exported totals + converged flag + loop state read back per iteration, the summed totals uploaded
 	long long* d_icp_x_ = nullptr; long long* h_icp_x_ = nullptr;
 	IcpShardStats icp_shard_;
+	// point-to-plane ICP (opt-in): the metric, the normals (one float4 per target point, original order: the pass gathers by the neighbour's index) and its fixed-point accumulators
+	int icp_metric_ = 0, normal_k_ = 16, normals_k_ = 0;   // normals_k_: the normal_k the normals were built with (0: none yet)
+	float4* d_normals_ = nullptr;
+	double normal_build_ms_ = 0;
+	unsigned long long* d_icp_acc_plane_ = nullptr;        // kIcpAccReplicas x kIcpPlaneStride, zero between iterations
+	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
+	void ensure_normals(int k);
 	const goicp_comm_ops* icp_comm_ = nullptr;
 	bool unrefined_ = false;           // collective registration: the best pose is an upper bound not yet refined by ICP
 	// nn query staging grows on demand

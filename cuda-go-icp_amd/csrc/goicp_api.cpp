@@ -395,6 +395,31 @@ int goicp_nn_query(goicp_handle h, const float* q, size_t n, int32_t* index, flo
 	return guarded([&] { h->e->nn_query(q, n, index, dist_sq); });
 }
 
+void goicp_icp_options_default(goicp_icp_options* out)
+{
+	if (!out) return;
+	out->metric = 0;
+	out->normal_k = 16;
+}
+
+int goicp_set_icp_options(goicp_handle h, const goicp_icp_options* opt)
+{
+	REQUIRE(h && opt);
+	return guarded([&] { h->e->set_icp_options(opt->metric, opt->normal_k); });
+}
+
+int goicp_knn_query(goicp_handle h, const float* q, size_t n, int32_t k, int32_t* index, float* dist_sq)
+{
+	REQUIRE(h && (n == 0 || (q && index && dist_sq)));
+	return guarded([&] { h->e->knn_query(q, n, k, index, dist_sq); });
+}
+
+int goicp_target_normals(goicp_handle h, float* normals_xyz)
+{
+	REQUIRE(h && normals_xyz);
+	return guarded([&] { h->e->target_normals(normals_xyz); });
+}
+
 int goicp_icp_step(goicp_handle h)
 {
 	REQUIRE(h);

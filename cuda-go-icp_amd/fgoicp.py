@@ -126,7 +126,9 @@ class TransNode:
 class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
-    def __init__(self, pct, pcs, mse_threshold=1e-3, **params):
+    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, **params):
+        """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
+        engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -146,6 +148,37 @@ class Registration:
         thr, inl = C.c_float(), C.c_int32()
         B.check(self._lib.goicp_thresholds(h, C.byref(thr), C.byref(inl)))
         self.sse_threshold, self.inliers = np.float32(thr.value), inl.value     # as the engine uses them (trimming included)
+        if icp_metric is not None or normal_k is not None:
+            try:
+                self.set_icp_options(0 if icp_metric is None else icp_metric, 16 if normal_k is None else normal_k)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- ICP metric (goicp_icp_options) ----
+    @staticmethod
+    def icp_options_default():
+        o = B.CIcpOptions()
+        B.load_library().goicp_icp_options_default(C.byref(o))
+        return o
+
+    def set_icp_options(self, metric=0, normal_k=16):
+        """goicp_set_icp_options: 0 point-to-point (default), 1 point-to-plane; builds the target normals for metric 1."""
+        o = B.CIcpOptions(int(metric), int(normal_k))
+        B.check(self._lib.goicp_set_icp_options(self.handle, C.byref(o)))
+
+    def knn_query(self, q, k):
+        """exact k nearest target points -> (index (n, k) int32, dist_sq (n, k) float32), ascending (dist_sq, index)"""
+        q = _f32(q, (-1, 3))
+        idx, d2 = np.empty((len(q), int(k)), np.int32), np.empty((len(q), int(k)), np.float32)
+        B.check(self._lib.goicp_knn_query(self.handle, _fptr(q), len(q), int(k), idx.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2)))
+        return idx, d2
+
+    def target_normals(self):
+        """(M, 3) float32 target normals in the target's order (built on first use)"""
+        n = np.empty((self.nt, 3), np.float32)
+        B.check(self._lib.goicp_target_normals(self.handle, _fptr(n)))
+        return n
 
     def close(self):
         if getattr(self, "handle", None):
@@ -254,8 +287,10 @@ class IterativeClosestPoint3D:
     """IterativeClosestPoint3D(reg, pct, pcs, max_iter, threshold, R, t).run() -> (sse, R, t).
     `threshold` is the reference CPU path's err_diff (mean squared error decrease per point)."""
 
-    def __init__(self, reg, max_iter=10000, convergence_threshold=1e-7, R=None, t=None):
+    def __init__(self, reg, max_iter=10000, convergence_threshold=1e-7, R=None, t=None, icp_metric=None, normal_k=None):
         self.reg, self.max_iter, self.thr = reg, int(max_iter), float(convergence_threshold)
+        if icp_metric is not None or normal_k is not None:      # the options of reg's handle (every ICP it runs)
+            reg.set_icp_options(0 if icp_metric is None else icp_metric, 16 if normal_k is None else normal_k)
         self.R = _f32(np.eye(3) if R is None else R, (9,)).copy()
         self.t = _f32(np.zeros(3) if t is None else t, (3,)).copy()
         self.iters = 0
@@ -272,8 +307,8 @@ class FastGoICP:
     """icp::FastGoICP(pct, pcs, mse_threshold, mtx): run() blocks (use a worker thread), the result
     fields are a consistent snapshot (the reference published them unlocked)."""
 
-    def __init__(self, pct, pcs, mse_threshold, mtx=None, **params):
-        self.registration = Registration(pct, pcs, mse_threshold, **params)
+    def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, **params):
+        self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, **params)
         self.mtx = mtx or threading.Lock()
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine

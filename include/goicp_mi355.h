@@ -285,6 +285,28 @@ int goicp_time_icp_pass_cached(goicp_handle h, const float R[9], const float t[3
  * exact 1-NN of n query points in the target; ties -> lowest target index. */
 int goicp_nn_query(goicp_handle h, const float* query_xyz, size_t n, int32_t* index, float* dist_sq);
 
+/* ---- point-to-plane ICP (opt-in; new, the reference has point-to-point only) ---------------------------------------------
+ * The options apply to every ICP the handle runs: goicp_icp_run, goicp_icp_step, goicp_time_icp_pass (it times the pass of the chosen
+ * metric), the ICP inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded*.  With metric 1 every iteration
+ * is one damped Gauss-Newton step on sum_i ((q_i - m_i) . n_i)^2, linearised about the transformed source centroid: m_i = the exact
+ * nearest target point of q_i (the same neighbour search as point-to-point), n_i = its normal.  err keeps its meaning: the sum of
+ * squared NN distances of the last pass; the stop rule is ICP3D::Run's.  Refused (GOICP_ERR_INVALID): metric 1 with trim_fraction > 0,
+ * metric outside {0, 1}, normal_k outside [3, 32], any change while a registration runs.  goicp_icp_run_collective runs metric 1
+ * replicated on every rank (the metric joins its check word); goicp_register_multi_gpu stays point-to-point. */
+typedef struct goicp_icp_options {
+	int32_t metric;     /* 0 point-to-point = ICP3D<float>::Run (default), 1 point-to-plane */
+	int32_t normal_k;   /* neighbours per target normal (the point itself included), 3..32, default 16 */
+} goicp_icp_options;
+void goicp_icp_options_default(goicp_icp_options* out);
+/* builds the target normals when metric == 1 (once per normal_k): k-NN, fp64 covariance, eigenvector of the smallest eigenvalue,
+ * oriented so that n . (p - target centroid) >= 0 (a zero product: first nonzero component positive); degenerate neighbourhoods get 0 */
+int goicp_set_icp_options(goicp_handle h, const goicp_icp_options* opt);
+/* exact k nearest target points of n queries, ascending (dist_sq, index); 1 <= k <= min(32, M) else GOICP_ERR_INVALID.
+ * index / dist_sq: n x k.  k = 1 gives goicp_nn_query's result bit for bit. */
+int goicp_knn_query(goicp_handle h, const float* query_xyz, size_t n, int32_t k, int32_t* index, float* dist_sq);
+/* the target normals (M x 3, original target order) with the handle's normal_k; built on first use if needed */
+int goicp_target_normals(goicp_handle h, float* normals_xyz);
+
 /* ICP::kdTreeGPUStep / ICP::naiveGPUStep (src/icp_kernel.h:9-13, icp_kernel.cu:176-279): ONE ICP
  * iteration from the engine's current step pose (identity after create); the accumulated pose is
  * visible through goicp_poll().curR/curT. */

@@ -203,6 +203,12 @@ public:
 	// the same with an explicit rotation level (rot_level < 0 <=> fix_rot)
 	BoundsResult_t compute_sse_error(const Mat3& R, int rot_level, const std::vector<TransNode>& tnodes) const { return bounds(R, rot_level, tnodes); }
 	goicp_handle handle() const { return h_; }
+	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
+	void set_icp_options(int metric, int normal_k = 16)
+	{
+		goicp_icp_options o{metric, normal_k};
+		check(goicp_set_icp_options(h_, &o));
+	}
 
 private:
 	BoundsResult_t bounds(const Mat3& R, int rot_level, const std::vector<TransNode>& tnodes) const
