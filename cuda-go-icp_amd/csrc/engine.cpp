@@ -155,18 +155,11 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
 	HIPCHK(hipEventCreate(&ev0_));
 	HIPCHK(hipEventCreate(&ev1_));
-	HIPCHK(hipStreamCreateWithFlags(&stream2_, hipStreamNonBlocking));
-	lane_stream_[0] = stream_; lane_stream_[1] = stream2_;
+	// lane 1's stream is made here, not in a timed registration (a stream costs ~2 ms to create); lanes 2.. make theirs on first use
+	lane_stream_[0] = stream_;
+	HIPCHK(hipStreamCreateWithFlags(&lane_stream_[1], hipStreamNonBlocking));
 	HIPCHK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-	{ const char* e = std::getenv("GOICP_TILE_CONCURRENT"); if (e) tile_concurrent_ = std::atoi(e) != 0; }     // A/B only (tools/tile_deep.py)
 	lanes_ = p_.lanes; lane_min_searches_ = std::max(2, p_.lane_min_searches);
-	{ const char* e = std::getenv("GOICP_LANES"); if (e) lanes_ = std::atoi(e); }                                  // tuning only (tools/lanes_probe.py)
-	{ const char* e = std::getenv("GOICP_LANE_MIN"); if (e) lane_min_searches_ = std::max(2, std::atoi(e)); }
-	{ const char* e = std::getenv("GOICP_LANE_MIN_WORK"); if (e) lane_min_work_ = std::atof(e); }
-	{ const char* e = std::getenv("GOICP_SOFT_OVERFLOW"); if (e) soft_overflow_ = std::atoi(e) != 0; }      // A/B only
-	{ const char* e = std::getenv("GOICP_TILE_STICKY_SHARE"); if (e) tile_sticky_share_ = std::atof(e); }
-	{ const char* e = std::getenv("GOICP_AUTO_LANES"); if (e) auto_lanes_ = std::min(kMaxLanes, std::max(2, std::atoi(e))); }
 
 	h_target_.assign(target, target + 3 * M);
 	if (!(p_.trim_fraction >= 0.f) || p_.trim_fraction >= 1.f) throw std::invalid_argument("goicp: trim_fraction must be in [0,1)");
@@ -454,7 +447,6 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 	HIPCHK(hipMemsetAsync(d_icp_acc_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpAcc, stream_));
 	for (size_t i = 0; i < N_; i++) src_radius_ = std::max(src_radius_, h_src_sorted_[4 * i + 3]);
 	for (size_t i = 0; i < 3 * M_; i++) target_abs_max_ = std::max(target_abs_max_, std::fabs(target[i]));
-	if (const char* e = std::getenv("GOICP_ICP_CACHE_REL")) { const float v = (float)std::atof(e); if (v > 0.f) icp_cache_rel_ = v; }     // tuning only
 	if (p_.icp_nn_cache) {
 		HIPCHK(hipMalloc(&d_nn_cache_, sizeof(float4) * 2 * N_));
 		HIPCHK(hipMemsetAsync(d_nn_cache_, 0, sizeof(float4) * 2 * N_, stream_));      // sqrt(best2_ref) = 0: the first pass walks
@@ -572,12 +564,10 @@ void Engine::release()
 	}
 	if (ev0_) hipEventDestroy(ev0_);
 	if (ev1_) hipEventDestroy(ev1_);
-	if (stream2_) { hipStreamSynchronize(stream2_); hipStreamDestroy(stream2_); }
-	for (int k = 2; k < kMaxLanes; k++) if (lane_stream_[k]) { hipStreamSynchronize(lane_stream_[k]); hipStreamDestroy(lane_stream_[k]); }
+	for (int k = 1; k < kMaxLanes; k++) if (lane_stream_[k]) { hipStreamSynchronize(lane_stream_[k]); hipStreamDestroy(lane_stream_[k]); }
 	for (int k = 0; k < kMaxLanes; k++) lane_stream_[k] = nullptr;
 	if (ev_fork_) hipEventDestroy(ev_fork_);
-	if (ev_join_) hipEventDestroy(ev_join_);
-	stream2_ = nullptr; ev_fork_ = ev_join_ = nullptr;
+	ev_fork_ = nullptr;
 	if (stream_) hipStreamDestroy(stream_);
 	d_src_ = nullptr; d_dt_ = nullptr; d_overshoot_ = nullptr; d_kd_pts_ = nullptr;
 	for (int l = 0; l < kMaxLevels; l++) d_kd_boxes_[l] = nullptr;
@@ -958,8 +948,8 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 		if (fin->converged || cancel_.load()) break;
 		// icp_nn_cache = 2: the exact walk-skipping cache pays once the cloud has nearly stopped moving (the tail of a run: a cached neighbour stays
 		// provably nearest for many iterations) and loses while it still moves (every miss is a slower 2-nearest walk) -- so it is switched on, for
-		// the chunks queued from here on, when the error fell by less than icp_cache_rel_ over the last chunk.  Exact either way: bit-identical states
-		if (p_.icp_nn_cache == 2 && d_nn_cache_ && !icp_cache_active_ && prev_err > 0.f && fin->err > 0.f && (prev_err - fin->err) < icp_cache_rel_ * fin->err)
+		// the chunks queued from here on, when the error fell by less than kIcpCacheRel over the last chunk.  Exact either way: bit-identical states
+		if (p_.icp_nn_cache == 2 && d_nn_cache_ && !icp_cache_active_ && prev_err > 0.f && fin->err > 0.f && (prev_err - fin->err) < kIcpCacheRel * fin->err)
 			icp_cache_active_ = true;
 		prev_err = fin->err;
 		have = next;
@@ -1387,11 +1377,12 @@ void Engine::ensure_stage(int k, size_t B)
 void Engine::free_lane(QLane& L)
 {
 	hipFree(L.d_search); hipHostFree(L.h_search); hipFree(L.d_nodes);
-	for (int k = 0; k < 2; k++) { hipFree(L.d_parents[k]); hipFree(L.d_psearch[k]); hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); if (L.ev_ctl[k]) hipEventDestroy(L.ev_ctl[k]); }
+	for (int k = 0; k < 2; k++) { hipFree(L.d_parents[k]); hipFree(L.d_psearch[k]); hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); }
+	if (L.ev_ctl) hipEventDestroy(L.ev_ctl);
 	hipFree(L.sort.keys); hipFree(L.sort.order); hipFree(L.sort.hist); hipFree(const_cast<float4*>(L.sort.cen));
 	hipFree(L.d_ub); hipFree(L.d_lb); hipFree(L.d_scratch); hipFree(L.d_ctl); hipHostFree(L.h_ctl);
 	hipFree(L.tile.ub); hipFree(L.tile.lb); hipFree(L.tile.scratch);
-	L = QLane{};          // the stream is the engine's (stream_ / stream2_), not the lane's to destroy
+	L = QLane{};          // the stream is the engine's (lane_stream_), not the lane's to destroy
 }
 
 void Engine::ensure_queues(size_t nsearch) { ensure_lane(0, nsearch); }
@@ -1433,8 +1424,7 @@ void Engine::ensure_lane(int li, size_t nsearch)
 	// 256 expansions (tools/sort_threshold_probe.py chunks / chunks2, registration in ms): bunny (30 k) 2 048 | 2 560 | 3 072 | 4 096 points =
 	// 32.8 | 31.8-32.4 | 32.5 | 34.3, bunny mse 1e-4 271 | 266 | 267 | 270, synthetic 40 k at mse 3e-5 -- | 770 | 765 | 720 (3 584: 744), every second
 	// bunny point (15 k) 1 280 .. 4 096: 26.3-27.4, flat: ten chunks is 3 072 / 4 096 / 1 536 points there
-	int kSortChunkPts = (int)(((N_ + 9) / 10 + 255) / 256 * 256);
-	if (const char* e = std::getenv("GOICP_SORT_CHUNK_PTS")) { const int v = std::atoi(e); if (v >= 256) kSortChunkPts = v; }     // tuning only
+	const int kSortChunkPts = (int)(((N_ + 9) / 10 + 255) / 256 * 256);
 	const int sort_chunks = (int)((N_ + kSortChunkPts - 1) / kSortChunkPts);
 	if (p_.sort_items && bounds_uses_lean(bounds_dt()) && inliers_ >= (int)N_ && N_ >= 12288 && N_ <= 65536 && sort_chunks >= 4 && sort_chunks <= 16) {
 		float4* cen = nullptr;
@@ -1445,10 +1435,11 @@ void Engine::ensure_lane(int li, size_t nsearch)
 		HIPCHK(hipMalloc(&L.sort.order, sizeof(unsigned) * max_groups * sort_chunks));
 		HIPCHK(hipMalloc(&L.sort.hist, qsort_hist_bytes()));
 		HIPCHK(hipMemsetAsync(L.sort.hist, 0, qsort_hist_bytes(), L.stream));     // kept zero between uses by the kernels themselves
-		L.sort.chunk_pts = kSortChunkPts; L.sort.chunks = sort_chunks; L.sort.min_groups = 256;
-		if (const char* e = std::getenv("GOICP_SORT_MIN_GROUPS")) { const int v = std::atoi(e); if (v > 0) L.sort.min_groups = v; }     // tuning only (tools/tune_e2e.py); the default is the measured optimum                    // rounds from this many expansions.  Round 3 (512 | 1024 | 2048 | 4096): 35.0 | 34.5 | 33.6 | 37.3 ms.  Re-swept in round 4 with the
+		// sorted rounds from kSortMinGroups expansions.  Round 3 (512 | 1024 | 2048 | 4096): 35.0 | 34.5 | 33.6 | 37.3 ms.  Re-swept in round 4 with the
 		// twin lists and the 4 096-point chunks in place (tools/sort_threshold_probe.py, median of 7): 1 | 128 | 512 | 1024 | 2048 | 4096 | off = 33.8 | 33.3 | 33.5 | 33.6 | 34.4 | 36.6 | 36.3 ms;
 		// mse 1e-4 / 3e-5 (0.27 / 6.8 s) flat between 128, 256 and 2048 -- so round 1 of a large batch (230 roots x two passes) is sorted too
+		constexpr int kSortMinGroups = 256;
+		L.sort.chunk_pts = kSortChunkPts; L.sort.chunks = sort_chunks; L.sort.min_groups = kSortMinGroups;
 		L.sort.shift = qsort_shift(dt_.V);           // 16-voxel cells (32-voxel cells: 35.1 ms)
 	}
 	HIPCHK(hipMalloc(&L.d_scratch, sizeof(float) * bounds_queue_scratch_floats((int)max_groups, L.sort.order ? L.sort.chunks : 0)));
@@ -1464,9 +1455,9 @@ void Engine::ensure_lane(int li, size_t nsearch)
 	}
 	if (!L.d_ctl) {
 		HIPCHK(hipMalloc(&L.d_ctl, sizeof(QCtl)));
-		HIPCHK(hipHostMalloc(&L.h_ctl, sizeof(QCtl) * 2));
-		std::memset(L.h_ctl, 0, sizeof(QCtl) * 2);
-		for (int k = 0; k < 2; k++) HIPCHK(hipEventCreateWithFlags(&L.ev_ctl[k], hipEventDisableTiming));
+		HIPCHK(hipHostMalloc(&L.h_ctl, sizeof(QCtl)));
+		std::memset(L.h_ctl, 0, sizeof(QCtl));
+		HIPCHK(hipEventCreateWithFlags(&L.ev_ctl, hipEventDisableTiming));
 	}
 	L.cap = cap;
 }
@@ -1491,9 +1482,9 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 	// rounds of 416 M point-expansions (bunny, mse 3e-5) 6.74 -> 5.71 -> 5.71 s, 183 M (synthetic 40 k, mse 3e-5) 721 -> 669 -> 649 ms, 90 M (bunny,
 	// mse 1e-4) 269 -> 264 -> 262 ms, 39 M (3 k points, mse 3e-5) 1.10 -> 1.22 -> 1.02 s (its heavy batches only), 20 M (the default bunny
 	// registration) 33.7 -> 34.2 -> 33.1 ms (never cut).  So lanes = 0 (auto) cuts a batch when the PREVIOUS batch's mean round was at least
-	// lane_min_work_ point-expansions (swept 16 / 32 / 64 / 128 / 256 M: 64 M) -- a count, not a time: the choice is deterministic
-	const bool lanes_wanted = lanes_ >= 2 || (lanes_ == 0 && last_round_work_ >= lane_min_work_);
-	int nl = (lanes_wanted && S >= (size_t)lane_min_searches_ && stream2_) ? std::min(kMaxLanes, lanes_ >= 2 ? lanes_ : auto_lanes_) : 1;
+	// kLaneMinWork point-expansions (swept 16 / 32 / 64 / 128 / 256 M: 64 M) -- a count, not a time: the choice is deterministic
+	const bool lanes_wanted = lanes_ >= 2 || (lanes_ == 0 && last_round_work_ >= kLaneMinWork);
+	int nl = (lanes_wanted && S >= (size_t)lane_min_searches_) ? std::min(kMaxLanes, lanes_ >= 2 ? lanes_ : kAutoLanes) : 1;
 	struct Run {
 		QLane* L = nullptr;
 		std::vector<int> idx;                 // lane slot -> index into `searches`
@@ -1541,7 +1532,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 		HIPCHK(hipMemcpyAsync(L.d_search, L.h_search, sizeof(QSearch) * Sl, hipMemcpyHostToDevice, L.stream));
 		r.qp = queue_params();
 		r.qp.list_cap = L.list_cap; r.qp.seg_cap = L.seg_cap;
-		r.qp.soft_overflow = soft_overflow_ ? 1 : 0;
+		r.qp.soft_overflow = 1;
 		r.qp.K = K;
 		r.qp.kmax = std::min(kQueueMaxPop, L.list_cap / (int)std::max<size_t>(Sl, 1));   // >= kQueueRoundPop: Sl <= the slots the lists were sized for
 		HIPCHK(launch_bnb_init(L.d_search, L.d_nodes, (int)Sl, r.qp, L.d_ctl, L.stream));
@@ -1580,19 +1571,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 				// 33.1-33.6 -> 32.8 ms, skull 6.4 -> 6.3, the rest within the spread.  (From a SIDE stream the copy lost: its blit kernel cannot
 				// start while the persistent bound kernels hold every CU -- bunny 33.9 ms, synthetic 40 k mse 3e-5 610 -> 642 ms.)
 				HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, L.stream));
-				HIPCHK(hipEventRecord(L.ev_ctl[0], L.stream));
-			}
-			// The round's two lists are independent (own records, own bounds, own partial sums), so the tile list's evaluation CAN be forked onto a
-			// second stream right behind the queue kernel and run beside the direct list's.  Built and measured (EXPERIMENTS R4.8): slower -- bunny
-			// mse 3e-5 6.73 -> 7.40 s, bunny/10 1.09 -> 1.14 s, identical results -- the VALU-bound tile kernel (32 KB of LDS per workgroup) and the
-			// gather kernel (122 VGPRs) take each other's occupancy; opt-in for A/B only (single-lane batches)
-			const bool fork_tiles = qp.tile_on && tile_concurrent_ && nl == 1;
-			if (fork_tiles) {
-				HIPCHK(hipEventRecord(ev_fork_, L.stream));
-				HIPCHK(hipStreamWaitEvent(stream2_, ev_fork_, 0));
-				HIPCHK(launch_bounds_tile_queue(d_src_, (int)N_, dt_, d_rots_, L.tile, L.d_ctl, parity, stream2_));
-				HIPCHK(hipEventRecord(ev_join_, stream2_));
-				tile_rounds_++;
+				HIPCHK(hipEventRecord(L.ev_ctl, L.stream));
 			}
 			const bool sorted = r.sort_round && std::min<long long>(r.round_cap, max_groups) >= L.sort.min_groups;
 			if (sorted) HIPCHK(launch_queue_sort(L.d_parents[parity], d_rots_, &L.d_ctl->n_groups[parity], max_groups, L.sort, bounds_dt(), L.stream));
@@ -1600,8 +1579,9 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 			                           inliers_, L.d_scratch, L.d_ub, L.d_lb, L.stream, r.twins ? L.d_search : nullptr, r.twins ? L.d_psearch[parity] : nullptr, sorted ? &L.sort : nullptr));
 			if (r.round_cap < (1ll << 40)) r.round_cap *= 8;
 			r.rounds_done++;
-			if (fork_tiles) HIPCHK(hipStreamWaitEvent(L.stream, ev_join_, 0));
-			else if (qp.tile_on) { HIPCHK(launch_bounds_tile_queue(d_src_, (int)N_, dt_, d_rots_, L.tile, L.d_ctl, parity, L.stream)); tile_rounds_++; }
+			// the tile list's evaluation behind the direct list's, on the lane's own stream: forking it onto a second stream to run beside it was
+			// measured slower (EXPERIMENTS R4.8: the tile and gather kernels take each other's occupancy)
+			if (qp.tile_on) { HIPCHK(launch_bounds_tile_queue(d_src_, (int)N_, dt_, d_rots_, L.tile, L.d_ctl, parity, L.stream)); tile_rounds_++; }
 			r.last = parity;
 			r.parity ^= 1;
 			cnt_.bounds_launches++;
@@ -1641,9 +1621,9 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 			Run& r = run[li];
 			if (r.done) continue;
 			const double t1 = now_ms();
-			HIPCHK(hipEventSynchronize(r.L->ev_ctl[0]));
+			HIPCHK(hipEventSynchronize(r.L->ev_ctl));
 			t_wait_ += now_ms() - t1;
-			const QCtl& c = r.L->h_ctl[0];
+			const QCtl& c = *r.L->h_ctl;
 			if (c.overflow) overflow = true;
 			if (c.overflow || overflow || (c.n_groups[r.last] == 0 && c.n_tile_groups[r.last] == 0) || cancel_.load()) { r.done = true; live--; continue; }
 			adapt(r, c);
@@ -1679,7 +1659,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 			tile_total += run[li].L->h_ctl->tile_total;
 			for (size_t i = 0; i < run[li].idx.size(); i++) all += run[li].L->h_search[i].cubes;
 		}
-		tile_sticky_ = tile_total > 0 && (double)tile_total * kGroup >= tile_sticky_share_ * (double)all;
+		tile_sticky_ = tile_total > 0 && (double)tile_total * kGroup >= kTileStickyShare * (double)all;
 	}
 	for (int li = 0; li < nl; li++) {
 		const QLane& L = *run[li].L;
@@ -1899,16 +1879,20 @@ void Engine::offer_global_best(float sse, const float R[9], const float t[3])
 	if (sse < opt_err_) {
 		adopt(sse, R, t);
 		unrefined_ = false;          // the collective protocol offers refined poses only
-		// drop queued nodes that can no longer win (jly_goicp.cpp:533-543)
-		std::priority_queue<Node> nq;
-		while (!queue_.empty()) {
-			Node n = queue_.top(); queue_.pop();
-			if (n.lb < opt_err_) nq.push(n); else break;
-		}
-		queue_.swap(nq);
+		prune_queue();
 		if (opt_err_ < sse_thresh_) early_exit_ = true;
 		publish(false);
 	}
+}
+
+void Engine::prune_queue()
+{
+	std::priority_queue<Node> nq;
+	while (!queue_.empty()) {
+		Node n = queue_.top(); queue_.pop();
+		if (n.lb < opt_err_) nq.push(n); else break;
+	}
+	queue_.swap(nq);
 }
 
 void Engine::register_begin()
@@ -1918,10 +1902,8 @@ void Engine::register_begin()
 	cancel_.store(false);
 	early_exit_ = converged_ = false;
 	rot_ramp_ = 8;
-	late_icp_.clear(); batches_done_ = 0;
 	unrefined_ = false;
 	last_round_work_ = 0; tile_sticky_ = false;      // every registration starts single-lane (determinism: the choice depends on this registration only)
-	{ const char* e = std::getenv("GOICP_ICP_DELAY_BATCHES"); icp_delay_ = e ? std::max(0, std::atoi(e)) : 0; }
 	icp_ms_ = 0; t_submit_ = t_wait_ = t_collect_ = 0;
 	std::memset(level_hist_, 0, sizeof(level_hist_));
 	cnt_ = Counters{};
@@ -1999,55 +1981,22 @@ bool Engine::handle_ub(Kid& k, const SearchOut& s)
 	adopt(s.best, k.R, t);
 	if (icp_comm_) {
 		// collective refinement (goicp_register_sharded_collective_icp): the upper bound is adopted as it is; the protocol refines the
-		// global winner on every rank after the next exchange (the deferral GOICP_ICP_DELAY_BATCHES models), so no pose is refined twice
+		// global winner on every rank after the next exchange, so no pose is refined twice
 		unrefined_ = true;
 		publish(false);
 		if (opt_err_ < sse_thresh_) { early_exit_ = true; return true; }
-		std::priority_queue<Node> nq;
-		while (!queue_.empty()) {
-			Node n = queue_.top(); queue_.pop();
-			if (n.lb < opt_err_) nq.push(n); else break;
-		}
-		queue_.swap(nq);
+		prune_queue();
 		return false;
 	}
 	float R[9], ti[3];
 	std::memcpy(R, k.R, sizeof(R)); std::memcpy(ti, t, sizeof(ti));
 	float e = icp_from(R, ti);
-	if (icp_delay_ > 0) {
-		LateIcp li; li.e = e; std::memcpy(li.R, R, sizeof(R)); std::memcpy(li.t, ti, sizeof(ti)); li.due = batches_done_ + icp_delay_;
-		late_icp_.push_back(li);
-		publish(false);
-		return false;
-	}
 	if (e < opt_err_) adopt(e, R, ti);
 	if (p_.verbose) std::fprintf(stderr, "[goicp] rank %d  error* %.6g (ub %.6g, level %d)\n", rank_, opt_err_, s.best, k.node.l);
 	publish(false);
 	if (opt_err_ < sse_thresh_) { early_exit_ = true; return true; }   // :527
-	std::priority_queue<Node> nq;                                       // :533-543
-	while (!queue_.empty()) {
-		Node n = queue_.top(); queue_.pop();
-		if (n.lb < opt_err_) nq.push(n); else break;
-	}
-	queue_.swap(nq);
+	prune_queue();                                                      // :533-543
 	return false;
-}
-
-void Engine::fold_late_icp(bool all)
-{
-	for (size_t i = 0; i < late_icp_.size();) {
-		if (!all && late_icp_[i].due > batches_done_) { i++; continue; }
-		const LateIcp li = late_icp_[i];
-		late_icp_.erase(late_icp_.begin() + (long)i);
-		if (li.e < opt_err_) {
-			adopt(li.e, li.R, li.t);
-			if (opt_err_ < sse_thresh_) early_exit_ = true;
-			std::priority_queue<Node> nq;
-			while (!queue_.empty()) { Node n = queue_.top(); queue_.pop(); if (n.lb < opt_err_) nq.push(n); else break; }
-			queue_.swap(nq);
-			publish(false);
-		}
-	}
 }
 
 // :551-562: the lower-bound search is in
@@ -2293,10 +2242,8 @@ StepStatus Engine::register_step(int max_rot_pops)
 		publish(false);
 	} else
 	while (true) {
-		if (!late_icp_.empty()) fold_late_icp(early_exit_ || converged_ || queue_.empty());      // nothing left to run beside: wait for every refinement
 		if (early_exit_ || cancel_.load() || pops >= max_rot_pops) break;
-		if (converged_ || queue_.empty()) { if (late_icp_.empty()) break; continue; }
-		batches_done_++;
+		if (converged_ || queue_.empty()) break;
 		// Rotation parents expanded together: ramps 8, 16, 32 ... rot_batch.  Easy registrations end in
 		// the first rounds and pay for little speculation; long searches run with few, large launches
 		// (full bunny: 310 launches / 63 ms at a fixed 8, 52 launches / 55 ms at 64).
@@ -2334,7 +2281,6 @@ StepStatus Engine::register_step(int max_rot_pops)
 		process_parents(parents);
 		publish(false);
 	}
-	if (!late_icp_.empty() && (early_exit_ || converged_ || queue_.empty())) fold_late_icp(true);
 	StepStatus st{};
 	st.early_exit = early_exit_ ? 1 : 0;
 	st.finished = (early_exit_ || converged_ || (queue_.empty() && flights_.empty()) || cancel_.load()) ? 1 : 0;

@@ -94,7 +94,7 @@ struct Counters {
 	long long bounds_launches = 0;
 	long long queue_fallbacks = 0;
 	long long tile_expansions = 0;   // BnB expansions evaluated from LDS-staged DT tiles (8 cube bounds each; counted in `cubes` too)
-	long long lane_batches = 0;      // batches of inner searches that ran as two lanes
+	long long lane_batches = 0;      // batches of inner searches cut into two or more lanes
 };
 
 // what the viewer polls (fgoicp.hpp:34,67-69; goicp_kernel.cu:161-177)
@@ -226,7 +226,6 @@ private:
 	void run_inner_host(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots, bool fallback = false);
 	bool run_inner_device(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);   // false: a round's lists overflowed, nothing was changed; redo_: searches whose own queue did
 	std::vector<InnerSearch*> redo_;
-	bool soft_overflow_ = true;       // env GOICP_SOFT_OVERFLOW = 0 (A/B only): a slab overflow sends the whole batch back, as before round 4
 	void ensure_queues(size_t nsearch);
 	void process_parents(const std::vector<Node>& parents);
 	struct Kid { Node node; float R[9]; float parent_lb; };                       // a rotation child and its Rodrigues matrix
@@ -279,11 +278,7 @@ private:
 
 	hipStream_t stream_ = nullptr;
 	hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-	// A/B only (env GOICP_TILE_CONCURRENT = 1): the tile list's evaluation BESIDE the direct list's (two independent kernels of the same round) on a
-	// second stream, forked after the queue kernel and joined before the next one.  Measured slower (EXPERIMENTS R4.8): default off
-	hipStream_t stream2_ = nullptr;
-	hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
-	int tile_concurrent_ = 0;
+	hipEvent_t ev_fork_ = nullptr;        // the other lanes of a batch start behind the engine's stream (run_inner_device)
 	float4* d_src_ = nullptr;         // N  (x,y,z,|p|), k-d order (Params::morton_sort)
 	std::vector<int32_t> src_perm_;   // sorted position -> original index
 	std::vector<float> h_src_sorted_; // N*4
@@ -327,22 +322,23 @@ private:
 		int seg_cap = 0;                                    // segments the tile list holds (list_cap / 64 + search slots)
 		int* d_psearch[2] = {nullptr, nullptr};             // per listed expansion: the search that listed it (twin test of the bound evaluation)
 		float* d_ub = nullptr; float* d_lb = nullptr; float* d_scratch = nullptr;
-		QCtl* d_ctl = nullptr; QCtl* h_ctl = nullptr;       // h_ctl: two pinned snapshots (one per chunk of rounds in flight)
-		hipEvent_t ev_ctl[2] = {nullptr, nullptr};
+		QCtl* d_ctl = nullptr; QCtl* h_ctl = nullptr;       // h_ctl: the pinned snapshot of the last read-back
+		hipEvent_t ev_ctl = nullptr;                        // recorded behind that read-back
 		QTile tile{};                                       // the tile list's buffers (null when lds_tiles == 0 or the DT is not bricked fp32)
 		int tile_hint_seen = 0;                             // QCtl::tile_hint at the last read-back
 	} ql_[kMaxLanes];
-	hipStream_t lane_stream_[kMaxLanes] = {};               // lane 0: stream_, lane 1: stream2_, further lanes: their own
+	hipStream_t lane_stream_[kMaxLanes] = {};               // lane 0: stream_, lane 1: created with the engine, further lanes: on first use
 	void free_lane(QLane& L);
 	void ensure_lane(int li, size_t nsearch);
-	double last_round_work_ = 0, lane_min_work_ = 64e6;    // point-expansions (expansions x source points) of the previous batch's mean round / the auto mode's bar
-	int auto_lanes_ = 3;                                    // lanes the auto mode cuts a batch into (env GOICP_AUTO_LANES; measured 2 / 3 / 4 at the end of round 4: bunny mse 3e-5
+	double last_round_work_ = 0;                            // point-expansions (expansions x source points) of the previous batch's mean round
+	static constexpr double kLaneMinWork = 64e6;            // the auto mode's bar on last_round_work_ (run_inner_device)
+	static constexpr int kAutoLanes = 3;                    // lanes the auto mode cuts a batch into (measured 2 / 3 / 4 at the end of round 4: bunny mse 3e-5
 	                                                        // 5.06 / 5.02 / 5.48 s, synthetic 40 k mse 3e-5 621 / 621 / 681 ms, 3 k points mse 3e-5 1 033 / 1 016 / 1 100 ms, bunny mse 1e-4 259 / 261 / 268 ms)
-	int lanes_ = 0, lane_min_searches_ = 64;                // Params::lanes / lane_min_searches (env GOICP_LANES / GOICP_LANE_MIN override, tuning only)
+	int lanes_ = 0, lane_min_searches_ = 64;                // Params::lanes / lane_min_searches
 	bool tiles_usable() const;
 	long long sel_hist_[4][4] = {};       // verbose: QCtl::sel_hist summed over the registration
-	double tile_sticky_share_ = 0.5;      // ... when at least this share of the previous batch's cube bounds came from tiles (env GOICP_TILE_STICKY_SHARE, tuning only)
 	bool tile_sticky_ = false;            // lds_tiles == 2: the previous batch evaluated expansions from tiles -> this batch launches the tile list in every round
+	static constexpr double kTileStickyShare = 0.5;   // ... when at least this share of the previous batch's cube bounds came from tiles
 	long long tile_rounds_ = 0;           // rounds whose tile evaluation was launched
 	long long queue_rounds_ = 0, queue_fallbacks_ = 0;
 	// icp staging
@@ -350,8 +346,8 @@ private:
 	unsigned long long* d_icp_acc_ = nullptr;   // fixed-point sums of the small-cloud ICP pass (kIcpAccReplicas x 16, zero between iterations)
 	float src_radius_ = 0.f, target_abs_max_ = 0.f;   // extents that bound the pass's terms (IcpState::acc_scale)
 	float4* d_nn_cache_ = nullptr;     // per source point: {q_ref, sqrt(best2_ref)}, {neighbour, index} (exact walk-skipping, device.hip)
-	bool icp_cache_active_ = false;    // icp_nn_cache = 2: switched on inside a run once the error's decrease per chunk falls under icp_cache_rel_ (the tail of a run)
-	float icp_cache_rel_ = 0.02f;
+	bool icp_cache_active_ = false;    // icp_nn_cache = 2: switched on inside a run once the error's decrease per chunk falls under kIcpCacheRel (the tail of a run)
+	static constexpr float kIcpCacheRel = 0.02f;
 	bool count_hits_ = false;
 	int* d_icp_ticket_ = nullptr;      // arrival ticket of the fused ICP iteration (zero between launches)
 	float* d_nn_d2_ = nullptr; int* d_nn_slot_ = nullptr; unsigned char* d_include_ = nullptr;   // trimmed ICP only
@@ -377,13 +373,7 @@ private:
 	float optR_[9], optT_[3], curR_[9], curT_[3];
 	bool early_exit_ = false, converged_ = false;
 	int rot_ramp_ = 8;
-	// experiment knob (env GOICP_ICP_DELAY_BATCHES = k, tools/icp_delay_probe.py): a refinement's result is folded in k rotation batches after
-	// the upper bound that triggered it -- what an ICP overlapped with the next batches would do to the search, without the concurrency
-	struct LateIcp { float e, R[9], t[3]; long long due; };
-	std::vector<LateIcp> late_icp_;
-	int icp_delay_ = 0;
-	long long batches_done_ = 0;
-	void fold_late_icp(bool all);
+	void prune_queue();               // drop queued nodes that can no longer win (jly_goicp.cpp:533-543)
 	Counters cnt_;
 	std::atomic<bool> cancel_{false};
 	std::mutex mtx_;

@@ -266,7 +266,7 @@ typedef struct goicp_counters {
 	int64_t queue_fallbacks;     /* batches of inner searches in which a device queue outgrew its slab: the searches concerned (only they, since round 4)
 	                              * were re-run through the host queues */
 	int64_t tile_expansions;     /* BnB expansions (8 cube bounds each, counted in `cubes` too) evaluated from LDS-staged DT tiles */
-	int64_t lane_batches;        /* batches of inner searches that ran as two lanes (goicp_params::lanes) */
+	int64_t lane_batches;        /* batches of inner searches cut into two or more lanes (goicp_params::lanes) */
 } goicp_counters;
 int goicp_inner_bnb(goicp_handle h, const float R[9], int32_t level, float incumbent, float* value,
                     float best_node[4], goicp_counters* counters);

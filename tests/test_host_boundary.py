@@ -285,6 +285,17 @@ int main() {
     assert r.returncode == 0 and "ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_environment_reads_are_the_allowed_ones():
+    """The engine's behaviour comes from goicp_params alone: the library reads no tuning or A/B switch from the environment.
+    The only reads are the roctx switch (trace.hpp), the communicator's time-out (shard.cpp) and TMPDIR (host_selftest.cpp)."""
+    import glob
+    csrc = os.path.join(ROOT, "cuda-go-icp_amd", "csrc")
+    names = set()
+    for path in sorted(glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.hpp")) + glob.glob(os.path.join(csrc, "*.hip"))):
+        names |= set(re.findall(r'getenv\s*\(\s*"([^"]*)"', open(path).read()))
+    assert names == {"GOICP_ROCTX", "GOICP_COMM_TIMEOUT_MS", "TMPDIR"}, sorted(names)
+
+
 # ----------------------------------------------------------------------------------------------
 # sanitizer builds (SURVEY 5): CPU only
 # ----------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Exploration on the GPU box (not a test): registrations of the test workloads under the driver options
 (`flowsweep`: lock-step / continuous flow x round width on six workloads -- the tables of DESIGN section 4 --, `spanner`, `s2`,
-`bunny`, `ksweep`, `ramp`, `flow`, `create`).  usage: python3 tools/tune_r2.py <mode>"""
+`bunny`, `ksweep`, `flow`, `create`).  usage: python3 tools/tune_r2.py <mode>"""
 import sys, time, os
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -70,17 +70,6 @@ elif which == "flow":
             print("bunny flow=%d K=%d run %.4fs sse %.4f rot_pops %d trans_pops %d cubes %d launches %d icp %d" % (
                 fl, K, time.time() - t1, eng.get_best_error(), c.rot_pops, c.trans_pops, c.cubes, c.bounds_launches, c.icp_iters), flush=True)
             eng.registration.close()
-elif which == "ramp":
-    for ramp in (4, 8, 16, 32, 64):
-        for rb in (32, 64, 128, 256):
-            os.environ["GOICP_RAMP"] = str(ramp)
-            best = None
-            for rep in range(3):
-                eng = pkg.FastGoICP(cloud("model_bunny"), cloud("data_bunny"), 1e-3, rot_batch=rb)
-                t1 = time.time(); eng.run(); dt = time.time() - t1; c = eng.counters
-                best = min(best, dt) if best else dt
-                eng.registration.close()
-            print("ramp=%d rot_batch=%d: best %.4fs rot_pops %d cubes %d launches %d icp %d" % (ramp, rb, best, c.rot_pops, c.cubes, c.bounds_launches, c.icp_iters), flush=True)
 elif which == "bunny":
     for dq in (1, 0, 1, 0):
         eng = pkg.FastGoICP(cloud("model_bunny"), cloud("data_bunny"), 1e-3, verbose=1, device_queues=dq)
