@@ -140,6 +140,7 @@ SYMBOLS = {
     "goicp_eval_sse": (C.c_int, [_vp, _fp, _fp, _fp]),
     "goicp_inner_bnb": (C.c_int, [_vp, _fp, C.c_int32, C.c_float, _fp, _fp, C.POINTER(CCounters)]),
     "goicp_icp_run": (C.c_int, [_vp, _fp, _fp, C.c_int32, C.c_float, _fp, C.POINTER(C.c_int32)]),
+    "goicp_icp_run_batch": (C.c_int, [_vp, C.c_size_t, _fp, _fp, C.c_int32, C.c_float, _fp, C.POINTER(C.c_int32)]),
     "goicp_time_icp_pass": (C.c_int, [_vp, _fp, _fp, C.c_int32, _fp]),
     "goicp_time_icp_pass_cached": (C.c_int, [_vp, _fp, _fp, C.c_int32, _fp]),
     "goicp_nn_query": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp]),

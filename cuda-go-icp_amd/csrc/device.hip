@@ -1687,11 +1687,11 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 // SLICE (ACC form only, goicp_icp_run_collective): the launch covers workgroups [b0, b0 + gridDim.x) of the world-1 grid -- the
 // global workgroup index blockIdx.x + b0 picks the queries and the replica, so every workgroup forms the same float row sums from the
 // same 16 queries as in a full pass, and the integer totals of the slices of all ranks add up to the world-1 totals bit for bit.
-template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES = 2, bool STRIDED = false, bool ACC = false, bool SLICE = false>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kernel(const float4* __restrict__ src, int N,
-                                                                  IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                  float* __restrict__ partials, int* __restrict__ ticket,
-                                                                  float4* __restrict__ nn_cache, int* __restrict__ hit_counter, int b0)
+// The body is shared with icp_pass_batch_kernel (goicp_icp_run_batch), which runs the ACC form on one pose slot per blockIdx.y.  Its pointers carry no
+// __restrict__ of their own: they come from the kernels' restrict parameters, which keeps icp_pass_kernel's code what it was before the split.
+template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES, bool STRIDED, bool ACC, bool SLICE>
+__device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, float* partials, int* ticket,
+                                              float4* nn_cache, int* hit_counter, int b0)
 {
 	static_assert(!SLICE || (ACC && !FUSED), "a slice of the pass exists in the fixed-point form only");
 	const int gb = SLICE ? (int)blockIdx.x + b0 : (int)blockIdx.x;   // workgroup index in the world-1 grid
@@ -1812,6 +1812,30 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kern
 		finalize_reduce<kIcpThreads>(partials, (int)gridDim.x, sh);
 		if (threadIdx.x < 64) finalize_rows(sh.sums, st, *st, (int)threadIdx.x);
 	}
+}
+
+template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES = 2, bool STRIDED = false, bool ACC = false, bool SLICE = false>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kernel(const float4* __restrict__ src, int N,
+                                                                  IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                  float* __restrict__ partials, int* __restrict__ ticket,
+                                                                  float4* __restrict__ nn_cache, int* __restrict__ hit_counter, int b0)
+{
+	icp_pass_body<K, LAYOUT, FUSED, CACHE, LEAVES, STRIDED, ACC, SLICE>(src, N, st, kd, dt, partials, ticket, nn_cache, hit_counter, b0);
+}
+
+// The batched pass (goicp_icp_run_batch): grid (icp_blocks(N), active poses); blockIdx.y picks a pose slot from the device list
+// `active`, slot s owns states[s] and the accumulator block acc + s * kIcpBatchAccWords (16 x 32 words used).  Every workgroup runs the body of the
+// default single-pose pass (fixed point, four leaves per step, no neighbour cache: every query walks) on that slot: the same 16 queries,
+// the same float row sums, the same acc_scale, the same replica -- and integer addition is associative, so the slot's totals are the
+// single-pose totals bit for bit, whatever else the grid holds.
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_batch_kernel(const float4* __restrict__ src, int N,
+                                                                        IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                        unsigned long long* __restrict__ acc, const int* __restrict__ active)
+{
+	const int s = active[blockIdx.y];
+	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false>(src, N, states + s, kd, dt,
+	                                                          reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0);
 }
 
 // ---- trimmed ICP (trim_fraction > 0; jly_icp3d.hpp:236-252): NN for every point, exact selection of
@@ -2274,7 +2298,7 @@ __global__ __launch_bounds__(kFinThreads) void icp_finalize_update(const float* 
 // two shuffles, no cross-wavefront stage -- and a single wavefront finds a free SIMD at once where sixteen had to wait for a whole compute
 // unit (tools/overlap_probe.py: beside a bound-evaluation stream the old form waited ~400 us per iteration).  Integer sums: the same totals.
 constexpr int kFinAccThreads = 64;
-__global__ __launch_bounds__(kFinAccThreads) void icp_finalize_update_acc(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+__device__ __forceinline__ void finalize_acc_body(unsigned long long* acc, IcpState* state)
 {
 	__shared__ double sums[kIcpAcc];
 	__shared__ IcpState st;
@@ -2296,6 +2320,17 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_finalize_update_acc(unsign
 	if (t < kIcpAcc) sums[t] = (double)x * (double)st.acc_inv;
 	__syncthreads();
 	finalize_rows(sums, state, st, t);
+}
+__global__ __launch_bounds__(kFinAccThreads) void icp_finalize_update_acc(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+{
+	finalize_acc_body(acc, state);
+}
+// goicp_icp_run_batch: one wavefront per active pose (blockIdx.x indexes the list), the unchanged finalize on that pose's slot
+__global__ __launch_bounds__(kFinAccThreads) void icp_finalize_batch_acc(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
+                                                                         const int* __restrict__ active)
+{
+	const int s = active[blockIdx.x];
+	finalize_acc_body(acc + (size_t)s * kIcpBatchAccWords, states + s);
 }
 
 // ---- the sharded ICP loop (goicp_icp_run_collective): slice pass -> export -> sum over the ranks on the host -> finalize from the sums ----
@@ -2967,9 +3002,8 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 // (21), J r (6), d^2.  Float row sums in fixed order per workgroup, then 64-bit fixed-point adds into kIcpAccReplicas x kIcpPlaneStride
 // accumulators: integer addition is associative, so the totals do not depend on the arrival order, at any N.
 template <int K, int LAYOUT, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_kernel(const float4* __restrict__ src, int N,
-                                                                       const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+__device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, const IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
+                                                    unsigned long long* acc)
 {
 	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
@@ -3024,11 +3058,31 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pas
 	}
 }
 
+template <int K, int LAYOUT, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_kernel(const float4* __restrict__ src, int N,
+                                                                       const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+{
+	icp_plane_pass_body<K, LAYOUT, STRIDED>(src, N, st, kd, dt, normals, acc);
+}
+
+// goicp_icp_run_batch, point-to-plane: icp_pass_batch_kernel's slot scheme (blockIdx.y -> active[] -> states[s], accumulator block
+// acc + s * kIcpBatchAccWords) around the unchanged plane pass body
+template <int K, int LAYOUT, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_batch_kernel(const float4* __restrict__ src, int N,
+                                                                             const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                             const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
+                                                                             const int* __restrict__ active)
+{
+	const int s = active[blockIdx.y];
+	icp_plane_pass_body<K, LAYOUT, STRIDED>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
+}
+
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
 // Gauss-Newton step (A + mu I) x = -b by fp64 Cholesky, mu = 1e-12 trace(A); omega = x[0:3], tau = x[3:6]; dR = Rodrigues(omega);
 // R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is not positive definite (no usable normal) leaves
 // the pose unchanged: the next pass then scores the same error and the loop stops.
-__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+__device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc, IcpState* state)
 {
 	__shared__ double sums[kIcpPlaneStride];
 	__shared__ IcpState st;
@@ -3150,6 +3204,17 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned lo
 	}
 	state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = st.iters + 1;
 }
+__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+{
+	icp_plane_finalize_body(acc, state);
+}
+// goicp_icp_run_batch: one wavefront per active pose, the unchanged plane finalize on that pose's slot
+__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
+                                                                           const int* __restrict__ active)
+{
+	const int s = active[blockIdx.x];
+	icp_plane_finalize_body(acc + (size_t)s * kIcpBatchAccWords, states + s);
+}
 
 template <int K>
 static void launch_plane_k(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc,
@@ -3174,6 +3239,39 @@ hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* st, co
 	else if (kd.K == 2) launch_plane_k<2>(src, N, st, kd, dt, normals, acc, stream);
 	else launch_plane_k<3>(src, N, st, kd, dt, normals, acc, stream);
 	hipLaunchKernelGGL(icp_plane_finalize, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
+	return hipGetLastError();
+}
+
+// ---- batched multi-start ICP (goicp_icp_run_batch): one pass over every active pose, then one finalize wavefront per active pose ----
+template <int K>
+static void launch_batch_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                           int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	const dim3 grid(icp_blocks(N), n_active), block(kIcpThreads);
+	const bool strided = N <= kIcpStridedMaxN;       // the single-pose passes' choice
+	if (metric == 0) {
+		if (strided) hipLaunchKernelGGL((icp_pass_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
+		else hipLaunchKernelGGL((icp_pass_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
+	} else if (dt.layout) {
+		if (strided) hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 1, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+		else hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 1, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+	} else {
+		if (strided) hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 0, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+		else hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 0, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+	}
+}
+
+hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                      int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || (metric != 0 && metric != 1) || (metric == 0 && !dt.layout) ||
+	    (metric == 1 && !normals))
+		return hipErrorInvalidValue;
+	if (kd.K == 1) launch_batch_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	else if (kd.K == 2) launch_batch_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	else launch_batch_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	if (metric == 0) hipLaunchKernelGGL(icp_finalize_batch_acc, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	else hipLaunchKernelGGL(icp_plane_finalize_batch, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
 	return hipGetLastError();
 }
 

@@ -301,6 +301,16 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, const float4* normals,
                                       unsigned long long* acc, hipStream_t stream);
 
+// ---- batched multi-start ICP (goicp_icp_run_batch) --------------------------------------------------------------------------------
+// One iteration of up to kIcpBatchMax independent loops over the same clouds: states[s] is pose slot s's loop state, acc + s * kIcpBatchAccWords
+// its accumulator block (zeroed 64-bit words, kept zero between iterations by the finalize), active[0 .. n_active) the slots this iteration
+// visits (device memory).  metric 0: the default fixed-point pass (bricked DT only), metric 1: the point-to-plane pass (normals required).
+// Pose s's state evolves bit for bit as under launch_icp_iteration(..., acc) / launch_icp_iteration_plane on its own.
+constexpr int kIcpBatchMax = 1024;
+constexpr int kIcpBatchAccWords = kIcpAccReplicas * kIcpPlaneStride;   // accumulator words per slot (either metric)
+hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                      int metric, const float4* normals, unsigned long long* acc, hipStream_t stream);
+
 // min of n floats (+ first index attaining it, may be null): one workgroup; v must be 16-byte aligned
 hipError_t launch_reduce_min(const float* v, int n, float* out_min, int* out_idx, hipStream_t stream);
 

@@ -556,6 +556,7 @@ void Engine::release()
 	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
 	hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
+	free_icp_batch();
 	for (Stage& st : stage_) {
 		hipFree(st.d_parents); hipFree(st.d_ub);
 		hipHostFree(st.h_parents); hipHostFree(st.h_ub);
@@ -871,8 +872,13 @@ void Engine::source_transformed(const float R[9], const float t[3], float* out)
 // ------------------------------------------------------------------------------------------------
 void Engine::icp_state_init(const float R[9], const float t[3], float err_diff, int carry_means, int frozen)
 {
-	IcpState& st = *h_icp_state_;
 	icp_cache_active_ = false;          // icp_nn_cache = 2: every run starts with plain walks
+	icp_state_fill(*h_icp_state_, R, t, err_diff, carry_means, frozen);
+	HIPCHK(hipMemcpyAsync(d_icp_state_, h_icp_state_, sizeof(IcpState), hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], float err_diff, int carry_means, int frozen) const
+{
 	std::memset(&st, 0, sizeof(st));
 	std::memcpy(st.R, R, sizeof(st.R));
 	std::memcpy(st.t, t, sizeof(st.t));
@@ -897,7 +903,6 @@ void Engine::icp_state_init(const float R[9], const float t[3], float err_diff, 
 		st.acc_scale = std::ldexp(1.0f, e);
 		st.acc_inv = std::ldexp(1.0f, -e);
 	}
-	HIPCHK(hipMemcpyAsync(d_icp_state_, h_icp_state_, sizeof(IcpState), hipMemcpyHostToDevice, stream_));
 }
 
 void Engine::icp_launch_one()
@@ -963,6 +968,99 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 	cnt_.icp_iters += st.passes;
 	cnt_.icp_runs++;
 	return st.err_new;
+}
+
+void Engine::ensure_icp_batch(size_t K)
+{
+	if (K <= batch_cap_) return;
+	free_icp_batch();
+	const size_t cap = std::max<size_t>(K, 16);
+	HIPCHK(hipMalloc(&d_batch_states_, sizeof(IcpState) * cap));
+	HIPCHK(hipHostMalloc(&h_batch_states_, sizeof(IcpState) * 3 * cap));
+	HIPCHK(hipMalloc(&d_batch_acc_, sizeof(unsigned long long) * kIcpBatchAccWords * cap));
+	HIPCHK(hipMemsetAsync(d_batch_acc_, 0, sizeof(unsigned long long) * kIcpBatchAccWords * cap, stream_));
+	HIPCHK(hipMalloc(&d_batch_active_, sizeof(int) * 2 * cap));
+	HIPCHK(hipHostMalloc(&h_batch_active_, sizeof(int) * 2 * cap));
+	batch_cap_ = cap;
+}
+
+void Engine::free_icp_batch()
+{
+	hipFree(d_batch_states_); hipHostFree(h_batch_states_); hipFree(d_batch_acc_); hipFree(d_batch_active_); hipHostFree(h_batch_active_);
+	d_batch_states_ = nullptr; h_batch_states_ = nullptr; d_batch_acc_ = nullptr; d_batch_active_ = nullptr; h_batch_active_ = nullptr;
+	batch_cap_ = 0;
+}
+
+// K icp_run loops in one device loop.  Every iteration is one batched pass over the active poses (grid: icp_blocks(N) x active) and one
+// finalize wavefront per active pose; pose s has its own IcpState and accumulator block, so its arithmetic is that of icp_run's default
+// fixed-point iteration (or of the point-to-plane iteration) bit for bit.  Chunks of icp_chunk iterations are queued one chunk ahead, as in
+// icp_run; after each chunk the K states come back, and the next chunk's active list keeps only the poses not yet seen converged (a pose
+// that converges inside a chunk already queued turns the rest of it into no-ops, as in icp_run), so the grid shrinks as poses converge.
+void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err_diff, float* err, int32_t* iters)
+{
+	if (K == 0 || K > (size_t)kIcpBatchMax) throw std::invalid_argument("goicp_icp_run_batch: K must be in [1, 1024]");
+	if (!R || !t || max_iter < 0) throw std::invalid_argument("goicp_icp_run_batch: R and t must be non-null and max_iter >= 0");
+	if (p_.trim_fraction > 0.f || inliers_ < (int)N_)
+		throw std::invalid_argument("goicp_icp_run_batch: trim_fraction > 0 is not supported (a per-pose global selection)");
+	if (icp_metric_ == 0 && (dt_.layout == 0 || p_.icp_fused))
+		throw std::invalid_argument("goicp_icp_run_batch: point-to-point needs the fixed-point pass of goicp_icp_run (dt_layout = 1, icp_fused = 0)");
+	if (registering_.load()) throw std::invalid_argument("goicp_icp_run_batch: not while a registration runs");
+	DeviceGuard guard(dev_);
+	if (icp_metric_ == 1) ensure_normals(normal_k_);
+	ensure_icp_batch(K);
+	IcpState* up = h_batch_states_;
+	for (size_t k = 0; k < K; k++) icp_state_fill(up[k], R + 9 * k, t + 3 * k, err_diff, 1, 0);
+	HIPCHK(hipMemcpyAsync(d_batch_states_, up, sizeof(IcpState) * K, hipMemcpyHostToDevice, stream_));
+	const int chunk = std::max(1, p_.icp_chunk);
+	int queued = 0, n_active = (int)K;
+	std::vector<int> act(K);
+	for (size_t k = 0; k < K; k++) act[k] = (int)k;
+	IcpState* slots[2] = {h_batch_states_ + batch_cap_, h_batch_states_ + 2 * batch_cap_};
+	hipEvent_t evs[2] = {ev0_, ev1_};
+	auto submit = [&](int slot) -> bool {
+		if (queued >= max_iter || n_active == 0) return false;
+		const int k = std::min(chunk, max_iter - queued);
+		// this slot's pinned list was last read by the chunk two submissions back, which the host has already waited for
+		int* h_act = h_batch_active_ + slot * batch_cap_;
+		int* d_act = d_batch_active_ + slot * batch_cap_;
+		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
+		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
+		for (int i = 0; i < k; i++)
+			HIPCHK(launch_icp_iteration_batch(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
+		queued += k;
+		HIPCHK(hipMemcpyAsync(slots[slot], d_batch_states_, sizeof(IcpState) * K, hipMemcpyDeviceToHost, stream_));
+		HIPCHK(hipEventRecord(evs[slot], stream_));
+		return true;
+	};
+	int cur = 0;
+	bool have = submit(0);
+	const IcpState* fin = up;              // max_iter = 0: the states as uploaded
+	while (have) {
+		const bool next = submit(cur ^ 1);     // one chunk ahead, over the poses not yet seen converged
+		HIPCHK(hipEventSynchronize(evs[cur]));
+		fin = slots[cur];
+		if (cancel_.load()) break;
+		n_active = 0;
+		for (size_t k = 0; k < K; k++)
+			if (!fin[k].converged) act[n_active++] = (int)k;
+		if (n_active == 0) break;
+		have = next;
+		cur ^= 1;
+	}
+	// a chunk still queued holds only no-ops for the poses seen converged (and, after a cancel, finishes its iterations): the states
+	// read back are final once it has drained, and the pinned lists are free again for the next call
+	HIPCHK(hipStreamSynchronize(stream_));
+	long long passes = 0;
+	for (size_t k = 0; k < K; k++) {
+		const IcpState& st = fin[k];
+		std::memcpy(R + 9 * k, st.R, sizeof(st.R));
+		std::memcpy(t + 3 * k, st.t, sizeof(st.t));
+		if (err) err[k] = st.err_new;
+		if (iters) iters[k] = st.iters;
+		passes += st.passes;
+	}
+	cnt_.icp_iters += passes;
+	cnt_.icp_runs += (long long)K;
 }
 
 namespace {

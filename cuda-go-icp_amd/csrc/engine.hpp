@@ -145,6 +145,10 @@ public:
 	float eval_sse(const float R[9], const float t[3]);
 	float inner_bnb(const float R[9], int level, float incumbent, float best_node[4], Counters* c);
 	float icp_run(float R[9], float t[3], int max_iter, float err_diff, int* iters);
+	// goicp_icp_run_batch: K independent icp_run loops, one start pose each (R: K x 9, t: K x 3 in/out; err, iters: K, may be null), in one
+	// device loop over the active poses; pose k ends bit for bit as icp_run from R + 9k, t + 3k.  The single-pose ICP state, the icp_step
+	// pose, the poll snapshot and the neighbour cache are left alone
+	void icp_run_batch(size_t K, float* R, float* t, int max_iter, float err_diff, float* err, int32_t* iters);
 	// goicp_icp_run_collective: icp_run with the pass's workgroups split over the ranks of `comm` and the integer sums added up over
 	// them -- every rank ends with the world-1 state, bit for bit.  Returns a goicp_status (collective: every rank returns together)
 	int icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3], int max_iter, float err_diff, float* err, int* iters);
@@ -249,6 +253,7 @@ private:
 	float icp_from(float R[9], float t[3]);
 	void publish(bool finished);
 	void icp_state_init(const float R[9], const float t[3], float err_diff, int carry_means, int frozen);
+	void icp_state_fill(IcpState& st, const float R[9], const float t[3], float err_diff, int carry_means, int frozen) const;   // host half of icp_state_init
 	void icp_state_fetch();
 
 	// HIP's current device is per host thread: every public entry point re-establishes the engine's device
@@ -361,6 +366,14 @@ private:
 	double normal_build_ms_ = 0;
 	unsigned long long* d_icp_acc_plane_ = nullptr;        // kIcpAccReplicas x kIcpPlaneStride, zero between iterations
 	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
+	// goicp_icp_run_batch (allocated on first use, grown on demand): cap pose slots of loop state and accumulators (kIcpBatchAccWords each,
+	// zero between iterations), the pinned mirror of the states (one upload slot + two fetch slots), two active lists (device + pinned)
+	IcpState* d_batch_states_ = nullptr; IcpState* h_batch_states_ = nullptr;
+	unsigned long long* d_batch_acc_ = nullptr;
+	int* d_batch_active_ = nullptr; int* h_batch_active_ = nullptr;
+	size_t batch_cap_ = 0;
+	void ensure_icp_batch(size_t K);
+	void free_icp_batch();
 	void ensure_normals(int k);
 	const goicp_comm_ops* icp_comm_ = nullptr;
 	bool unrefined_ = false;           // collective registration: the best pose is an upper bound not yet refined by ICP

@@ -344,6 +344,12 @@ int goicp_icp_run(goicp_handle h, float R[9], float t[3], int32_t max_iter, floa
 	});
 }
 
+int goicp_icp_run_batch(goicp_handle h, size_t K, float* R, float* t, int32_t max_iter, float err_diff, float* err, int32_t* iters)
+{
+	REQUIRE(h && R && t && max_iter >= 0 && K >= 1 && K <= (size_t)goicp::kIcpBatchMax);
+	return guarded([&] { h->e->icp_run_batch(K, R, t, max_iter, err_diff, err, iters); });
+}
+
 int goicp_icp_run_collective(goicp_handle h, const goicp_comm_ops* comm, float R[9], float t[3], int32_t max_iter, float err_diff, float* err,
                              int32_t* iters)
 {

@@ -259,6 +259,19 @@ class Registration:
         B.check(self._lib.goicp_icp_step(self.handle))
         return self.poll()
 
+    def icp_run_batch(self, R, t, max_iter=10000, err_diff=1e-7):
+        """goicp_icp_run_batch: K independent ICP runs (this handle's ICP options), one per start pose, refined together on the device.
+        R (K,3,3) or (K,9), t (K,3) -> (R (K,3,3), t (K,3), err (K,), iters (K,)); pose k is bit for bit the single run from R[k], t[k]."""
+        R, t = np.asarray(R), np.asarray(t)
+        if R.ndim not in (2, 3) or R.shape[1:] not in ((3, 3), (9,)) or t.ndim != 2 or t.shape[1] != 3 or len(R) != len(t) or len(R) == 0:
+            raise ValueError("icp_run_batch: R must be (K,3,3) or (K,9) and t (K,3) with the same K >= 1, got %s and %s" % (R.shape, t.shape))
+        K = len(R)
+        R, t = _f32(R, (K, 9)).copy(), _f32(t, (K, 3)).copy()
+        err, it = np.empty(K, np.float32), np.empty(K, np.int32)
+        B.check(self._lib.goicp_icp_run_batch(self.handle, K, _fptr(R), _fptr(t), int(max_iter), float(err_diff), _fptr(err),
+                                              it.ctypes.data_as(C.POINTER(C.c_int32))))
+        return R.reshape(K, 3, 3), t, err, it
+
     def icp_run_collective(self, comm_ops, R=None, t=None, max_iter=10000, err_diff=1e-7, raise_on_error=True):
         """goicp_icp_run_collective: ICP3D::Run with the source points sharded over the ranks of comm_ops (a binding.CCommOps); every rank
         calls it with the same arguments and gets the world-1 result bit for bit.  -> (status, err, R (3,3), t, iters)"""

@@ -275,6 +275,16 @@ int goicp_inner_bnb(goicp_handle h, const float R[9], int32_t level, float incum
  * (src/goicp/jly_icp3d.hpp:181-295).  R,t in/out; err = sum of squared NN distances of the last pass. */
 int goicp_icp_run(goicp_handle h, float R[9], float t[3], int32_t max_iter, float err_diff,
                   float* err, int32_t* iters);
+/* K independent ICP3D<float>::Run loops on one handle, one start pose each, refined together in one device loop (multi-start ICP: the
+ * candidates of a coarse search, the symmetric poses of an object, detector or RANSAC hypotheses).  R: K x 9, t: K x 3, row-major, in/out.
+ * err (K, may be NULL): sum of squared NN distances of each pose's last pass.  iters (K, may be NULL): each pose's iteration count.
+ * Pose k's result is bit-identical to goicp_icp_run(h, R + 9k, t + 3k, max_iter, err_diff, ...) on the same handle, under the handle's ICP
+ * options (goicp_set_icp_options: metric 0 and 1).  goicp_cancel stops it as it stops goicp_icp_run; the counters add icp_runs += K and
+ * icp_iters += the passes of all poses.  The handle's single-pose ICP state, the goicp_icp_step pose, the goicp_poll snapshot and the
+ * neighbour cache are left alone.  GOICP_ERR_INVALID: K == 0 or K > 1024, a NULL h, R or t, max_iter < 0, trim_fraction > 0, metric 0
+ * without goicp_icp_run's fixed-point pass (dt_layout = 0 or icp_fused = 1), a registration running on the handle. */
+int goicp_icp_run_batch(goicp_handle h, size_t K, float* R, float* t, int32_t max_iter, float err_diff,
+                        float* err, int32_t* iters);
 /* average duration (ms) of one ICP correspondence pass (NN + sums) at the given pose */
 int goicp_time_icp_pass(goicp_handle h, const float R[9], const float t[3], int32_t iters, float* ms_per_pass);
 /* the same with the neighbour cache in play at a repeated pose: every query hits (the steady-state floor of a pass);

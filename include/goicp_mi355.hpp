@@ -245,6 +245,23 @@ public:
 		curR = R_; curT = t_;
 		return Result_t{err, R_, t_};
 	}
+	// multi-start form (goicp_icp_run_batch): refines every pose of R / t (same length, at most 1024) in place with this object's
+	// max_iter and threshold; pose k ends as run() from R[k], t[k] would leave it.  Returns each pose's error; iters (optional) its iterations
+	std::vector<float> run_batch(std::vector<Mat3>& R, std::vector<Vec3>& t, std::vector<int32_t>* iters = nullptr) const
+	{
+		if (R.size() != t.size()) throw std::invalid_argument("IterativeClosestPoint3D::run_batch: R and t differ in length");
+		const size_t K = R.size();
+		std::vector<float> rows(9 * K), tt(3 * K), err(K);
+		std::vector<int32_t> it(K);
+		for (size_t k = 0; k < K; k++) {
+			to_rows(R[k], &rows[9 * k]);
+			for (int i = 0; i < 3; i++) tt[3 * k + i] = t[k][i];
+		}
+		check(goicp_icp_run_batch(reg_.handle(), K, rows.data(), tt.data(), (int32_t)max_iter_, thr_, err.data(), it.data()));
+		for (size_t k = 0; k < K; k++) { R[k] = from_rows(&rows[9 * k]); t[k] = from_xyz(&tt[3 * k]); }
+		if (iters) *iters = it;
+		return err;
+	}
 
 private:
 	const Registration& reg_;
