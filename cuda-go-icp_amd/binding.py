@@ -83,6 +83,10 @@ class CIcpOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("normal_k", C.c_int32)]
 
 
+class CIcpGate(C.Structure):
+    _fields_ = [("max_corr_dist", C.c_float), ("min_inliers", C.c_int32), ("capped_walk", C.c_int32)]
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -149,6 +153,10 @@ SYMBOLS = {
     "goicp_set_icp_options": (C.c_int, [_vp, C.POINTER(CIcpOptions)]),
     "goicp_knn_query": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_target_normals": (C.c_int, [_vp, _fp]),
+    "goicp_icp_gate_default": (None, [C.POINTER(CIcpGate)]),
+    "goicp_set_icp_gate": (C.c_int, [_vp, C.POINTER(CIcpGate)]),
+    "goicp_icp_inliers": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int32)]),
+    "goicp_eval_correspondences": (C.c_int, [_vp, _fp, _fp, C.c_float, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),
     "goicp_poll": (C.c_int, [_vp, C.POINTER(CResult)]),

@@ -1,6 +1,6 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
-//                                [--point-to-plane] [--normal-k K]
+//                                [--point-to-plane] [--normal-k K] [--max-corr-dist D]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -10,6 +10,9 @@
 //               reference's own .toml files are then not comparable with the strict-order goldens: use the flag for parity runs.
 //   --point-to-plane   every ICP of the run is point-to-plane (goicp_set_icp_options metric 1; --normal-k K neighbours per target
 //               normal, default 16).  Refused together with --ranks N > 1: the multi-GPU registration runs point-to-point ICP
+//   --max-corr-dist D   every ICP of the run uses only correspondences within distance D (goicp_set_icp_gate; cloud units after
+//               `resize`); output.toml then gets an [icp_gate] table with D and the inlier count of the final pose.  D must be a finite
+//               number > 0, and the flag is refused together with --ranks N > 1 and --trim-fraction F > 0 -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -36,10 +39,12 @@ static std::string resolve(const std::string& p, const std::string& toml)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
+	const char* gate_arg = nullptr;
+	float gate = 0.f;
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -49,6 +54,20 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--reference-root")) reference_root = 1;
 		else if (!std::strcmp(argv[i], "--point-to-plane")) plane = 1;
 		else if (!std::strcmp(argv[i], "--normal-k") && i + 1 < argc) normal_k = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--max-corr-dist")) gate_arg = i + 1 < argc ? argv[++i] : "";
+	}
+	if (gate_arg) {
+		// a bad gate is refused before any device is touched
+		char* end = nullptr;
+		gate = std::strtof(gate_arg, &end);
+		if (end == gate_arg || *end != '\0' || !(gate > 0.f) || !(gate <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: --max-corr-dist needs a finite distance > 0, got '%s'\n", gate_arg);
+			return 2;
+		}
+		if (ranks > 1 || trim_fraction > 0.f) {
+			std::fprintf(stderr, "error: --max-corr-dist cannot be combined with --ranks N > 1 (the multi-GPU registration is ungated) or --trim-fraction F > 0\n");
+			return 2;
+		}
 	}
 	if (plane && ranks > 1) {
 		// the multi-GPU registration runs point-to-point ICP only: refused before any device is touched
@@ -94,6 +113,7 @@ int main(int argc, char** argv)
 		icp::FastGoICP engine(target, source, config.mse_threshold, mtx, &p);
 		goicp_handle h = engine.registration.handle();
 		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
+		if (gate > 0.f) engine.registration.set_icp_gate(gate);
 		goicp_result r;
 		if (config.mode <= 2) {
 			for (int i = 0; i < iters; i++) check(goicp_icp_step(h));
@@ -115,6 +135,17 @@ int main(int argc, char** argv)
 		for (int i = 0; i < 3; i++) std::printf("%12.7f %12.7f %12.7f\n", R[3 * i], R[3 * i + 1], R[3 * i + 2]);
 		std::printf("Optimal Translation Vector:\n%12.7f\n%12.7f\n%12.7f\n", t[0], t[1], t[2]);
 		if (!config.io.output.empty()) engine.write_output(config.io.output);
+		if (gate > 0.f) {
+			int32_t n_in = 0;
+			check(goicp_eval_correspondences(h, R, t, gate, nullptr, nullptr, &n_in, nullptr));
+			std::printf("Inliers within %.7g: %d of %zu\n", gate, (int)n_in, source.size());
+			if (!config.io.output.empty()) {
+				FILE* f = std::fopen(config.io.output.c_str(), "a");
+				if (!f) throw std::runtime_error("cannot append to " + config.io.output);
+				std::fprintf(f, "\n[icp_gate]\nmax_corr_dist = %.9g\ninliers = %d\n", gate, (int)n_in);
+				std::fclose(f);
+			}
+		}
 		if (!config.io.visualization.empty()) engine.write_visualization(config.io.visualization);
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());

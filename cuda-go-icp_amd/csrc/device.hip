@@ -1500,12 +1500,19 @@ __device__ __forceinline__ unsigned row_take(unsigned key[4], int l, int row, in
 // source point: on a later pass at position q' the cached point m is still THE nearest neighbour whenever
 // |q' - m| + |q' - q_ref| < sqrt(best2_ref) -- every other point is at least sqrt(best2_ref) - |q' - q_ref| away -- so the
 // walk is skipped exactly, not approximately.
+//
+// CAP (the gated ICP pass): the pruning bound starts at min(seed distance, cap) -- a box whose key lies above cap's bits is never entered,
+// and a query whose seed lies beyond the cap and that has no box within it ends at its first step.  The cap is non-strict, so every
+// target point with d^2 <= cap is still found, with the same neighbour and tie rule (a point AT the cap beats the empty candidate
+// INT_MAX); a query with nothing inside the cap returns best = cap with NO lane `mine`: its neighbour is unspecified and the caller
+// must not use it.  cap = +inf is the uncapped walk.
 struct RowNn { float best; int idx; bool mine; float mx, my, mz; int slot; float best2; };
 
-template <int K, int LAYOUT, bool TWO = false, int LEAVES = 2>
+template <int K, int LAYOUT, bool TWO = false, int LEAVES = 2, bool CAP = false>
 __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt, const Box6x4& rootb, int l, int row,
-                                              float qx, float qy, float qz, bool active)
+                                              float qx, float qy, float qz, bool active, float cap = 0.f)
 {
+	static_assert(!CAP || !TWO, "the capped walk has no second-best form");
 	// no row of this wavefront needs a walk (every query hit the neighbour cache): nothing to fetch, nothing to compute
 	if (!__any(active)) return RowNn{INFINITY, INT_MAX, false, 0.f, 0.f, 0.f, 0, INFINITY};
 	unsigned key[K][4];
@@ -1550,6 +1557,9 @@ __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt
 		r.best = e; r.idx = __float_as_int(pt.w); r.mine = l == 0; r.mx = pt.x; r.my = pt.y; r.mz = pt.z; r.slot = slot;
 	} else
 		r.best = nn_upper_bound<LAYOUT>(dt, qx, qy, qz);
+	if constexpr (CAP) {
+		if (r.best > cap) { r.best = cap; r.idx = INT_MAX; r.mine = false; }
+	}
 	unsigned bbits = __float_as_uint(r.best);
 	unsigned b2bits = 0x7f800000u;                // +inf: nothing but the neighbour seen yet
 	int d = 0;
@@ -1676,6 +1686,7 @@ __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt
 constexpr int kFinThreads = 1024;                  // the stand-alone finalize: 256 row streams x four float4 columns
 struct FinScratch { double wsum[kFinThreads / 64][kIcpAcc]; double sums[kIcpAcc]; float red[kIcpThreads / 16][kIcpAcc]; int last; IcpState st; };   // red: one row of sums per 16-lane row
 template <int T> __device__ __forceinline__ void finalize_reduce(const float* __restrict__ partials, int nblocks, FinScratch& sh);
+template <bool GATE = false>
 __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, IcpState* __restrict__ state, const IcpState& rd, int lane);
 
 // FUSED: the workgroup that arrives last (one ticket per launch; agent-scope release before the ticket, acquire
@@ -1689,11 +1700,15 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 // same 16 queries as in a full pass, and the integer totals of the slices of all ranks add up to the world-1 totals bit for bit.
 // The body is shared with icp_pass_batch_kernel (goicp_icp_run_batch), which runs the ACC form on one pose slot per blockIdx.y.  Its pointers carry no
 // __restrict__ of their own: they come from the kernels' restrict parameters, which keeps icp_pass_kernel's code what it was before the split.
-template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES, bool STRIDED, bool ACC, bool SLICE>
+// GATE (goicp_set_icp_gate; ACC form only): the owning lane zeroes its terms when d^2 > IcpState::g2 and contributes 1 to a count otherwise; the
+// accumulator block then has the plane pass's stride (kIcpPlaneStride words per replica), the count a plain integer in word 16.  `capped`: the walk
+// prunes at g2 (rows_nearest<CAP>); an outlier's row may then have no owning lane at all.
+template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES, bool STRIDED, bool ACC, bool SLICE, bool GATE = false>
 __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, float* partials, int* ticket,
-                                              float4* nn_cache, int* hit_counter, int b0)
+                                              float4* nn_cache, int* hit_counter, int b0, int capped = 0)
 {
 	static_assert(!SLICE || (ACC && !FUSED), "a slice of the pass exists in the fixed-point form only");
+	static_assert(!GATE || (ACC && !FUSED && !CACHE && !SLICE), "the gated pass exists in the fixed-point form only; every query walks");
 	const int gb = SLICE ? (int)blockIdx.x + b0 : (int)blockIdx.x;   // workgroup index in the world-1 grid
 	__shared__ FinScratch sh;
 	float (*red)[kIcpAcc] = sh.red;                                   // [16 rows of the workgroup][16 sums]
@@ -1736,13 +1751,17 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 			nn_cache[2 * (size_t)i] = make_float4(qx, qy, qz, __fsqrt_rn(r.best2) * 0.99999f);
 			nn_cache[2 * (size_t)i + 1] = make_float4(r.mx, r.my, r.mz, __int_as_float(r.idx));
 		}
+	} else if constexpr (GATE) {
+		r = rows_nearest<K, LAYOUT, false, LEAVES, true>(kd, dt, rootb, l, row, qx, qy, qz, valid, capped ? st->g2 : INFINITY);
 	} else {
 		r = rows_nearest<K, LAYOUT, false, LEAVES>(kd, dt, rootb, l, row, qx, qy, qz, valid);
 	}
 	float acc[kIcpAcc];
 #pragma unroll
 	for (int k = 0; k < kIcpAcc; k++) acc[k] = 0.f;
-	if (valid && r.mine) {                                       // exactly one lane of the row
+	bool inlier = valid && r.mine;                               // exactly one lane of the row (GATE: at most one)
+	if constexpr (GATE) inlier = inlier && r.best <= st->g2;
+	if (inlier) {
 		const float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];   // pivots keep the covariance sums well conditioned
 		const float bx = r.mx - st->cm[0], by = r.my - st->cm[1], bz = r.mz - st->cm[2];
 		acc[0] = ax; acc[1] = ay; acc[2] = az;
@@ -1756,18 +1775,34 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 	// row: that lane stores its 16 terms to LDS (four 16-byte stores), rows without a query store zeros, and 16 threads add
 	// the workgroup's 16 rows in fixed order.  (The previous form ran 16 DPP row sums + 32 cross-row shuffles per wavefront:
 	// 160 of the ~1 180 VALU instructions of a wavefront, on a kernel the counters show to be VALU-issue-limited.)
+	__shared__ int gate_cnt[GATE ? kIcpThreads / 16 : 1];        // GATE: one inlier flag per row
 	{
 		const int wrow = wave * 4 + row;
-		const bool owner = valid ? r.mine : l == 0;
+		bool owner = valid ? r.mine : l == 0;
+		if constexpr (GATE) {
+			// a capped walk that found nothing inside the gate leaves the row without an owning lane: its lane 0 stores the zeros
+			const unsigned mine_row = (unsigned)(__ballot(valid && r.mine) >> (16 * row)) & 0xffffu;
+			owner = mine_row ? (valid && r.mine) : l == 0;
+		}
 		if (owner) {
 			float4* dst = reinterpret_cast<float4*>(red[wrow]);
 			dst[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
 			dst[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
 			dst[2] = make_float4(acc[8], acc[9], acc[10], acc[11]);
 			dst[3] = make_float4(acc[12], acc[13], acc[14], acc[15]);
+			if constexpr (GATE) gate_cnt[wrow] = inlier ? 1 : 0;
 		}
 	}
 	__syncthreads();
+	if constexpr (GATE) {
+		if (threadIdx.x == kIcpAcc) {                             // the workgroup's inlier count: a plain integer, word 16 of the replica
+			int c = 0;
+#pragma unroll
+			for (int x = 0; x < kIcpThreads / 16; x++) c += gate_cnt[x];
+			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + kIcpAcc;
+			__hip_atomic_fetch_add(a, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
 	if (threadIdx.x < kIcpAcc) {
 		float sum = red[0][threadIdx.x];
 #pragma unroll
@@ -1787,7 +1822,7 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 			// 1 899 of them) but 16 device-scope 64-bit integer adds of the sums in fixed point -- integer addition is
 			// associative, so the totals are exact and independent of the arrival order: still bit-reproducible
 			const long long v = __double2ll_rn((double)sum * (double)st->acc_scale);
-			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpAcc + threadIdx.x;
+			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * (GATE ? kIcpPlaneStride : kIcpAcc) + threadIdx.x;
 			__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		} else {
 			partials[(size_t)blockIdx.x * kIcpAcc + threadIdx.x] = sum;
@@ -1836,6 +1871,24 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_batc
 	const int s = active[blockIdx.y];
 	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false>(src, N, states + s, kd, dt,
 	                                                          reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0);
+}
+
+// The gated pass (goicp_set_icp_gate), single pose and batch: the default fixed-point pass in its GATE form, on the 32-word replica stride.
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_gate_kernel(const float4* __restrict__ src, int N,
+                                                                       IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                       unsigned long long* __restrict__ acc, int capped)
+{
+	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, true>(src, N, st, kd, dt, reinterpret_cast<float*>(acc), nullptr, nullptr, nullptr, 0, capped);
+}
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_gate_batch_kernel(const float4* __restrict__ src, int N,
+                                                                             IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                             unsigned long long* __restrict__ acc, const int* __restrict__ active, int capped)
+{
+	const int s = active[blockIdx.y];
+	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, true>(src, N, states + s, kd, dt,
+	                                                                reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0, capped);
 }
 
 // ---- trimmed ICP (trim_fraction > 0; jly_icp3d.hpp:236-252): NN for every point, exact selection of
@@ -2199,25 +2252,48 @@ __device__ __forceinline__ void kabsch_rows(double b0, double b1, double b2, int
 	}
 }
 
+// The gated loop's decision after a pass (goicp_set_icp_gate): the inlier count, the truncated cost C = err + (N - n_in) * g2 -- the
+// objective sum min(d^2, g2) that gated ICP descends, so the loop does not stop while the inlier set still grows -- and whether to stop:
+// too few inliers, or the reference's one-sided test (jly_icp3d.hpp:255) on C.  With n_in = N the term is 0 * g2 = 0: the ungated test, bit for bit.
+struct GateStep { int n_in; float cost; bool stop; };
+__device__ __forceinline__ GateStep gate_step(const IcpState& rd, float err_new, double count)
+{
+	GateStep g;
+	g.n_in = (int)count;
+	g.cost = err_new + (float)((int)rd.n - g.n_in) * rd.g2;
+	g.stop = g.n_in < rd.min_inliers || (rd.cost > 0.f && rd.cost - g.cost < rd.err_diff_n);
+	return g;
+}
+
 // called by every lane of ONE wavefront (lanes >= 3 shadow lane 2 and write nothing)
 // state: where the new pose is written; rd: where the old one is read -- the stand-alone finalize hands in a copy its threads
 // fetched into LDS beside the partial rows (one round trip instead of a chain of four behind the branches below)
+// GATE: sums[16] is the pass's inlier count; it takes n's place in the update, and the stop rule is gate_step's
+template <bool GATE>
 __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, IcpState* __restrict__ state, const IcpState& rd, int lane)
 {
 	const int a = lane < 3 ? lane : 2;
 	const bool writer = lane < 3;
 	const float err_new = (float)sums[15];
 	const int passes = rd.passes + 1;
+	GateStep gs{0, 0.f, false};
+	if constexpr (GATE) gs = gate_step(rd, err_new, sums[kIcpAcc]);
 	if (rd.frozen) {                                                     // timing / scoring only
-		if (lane == 0) { state->err_new = err_new; state->passes = passes; }
+		if (lane == 0) {
+			state->err_new = err_new; state->passes = passes;
+			if constexpr (GATE) state->n_in = gs.n_in;
+		}
 		return;
 	}
 	const float err = rd.err;
-	if (err > 0.f && err - err_new < rd.err_diff_n) {                    // jly_icp3d.hpp:255
-		if (lane == 0) { state->err_new = err_new; state->passes = passes; state->converged = 1; }
+	if (GATE ? gs.stop : (err > 0.f && err - err_new < rd.err_diff_n)) {   // jly_icp3d.hpp:255
+		if (lane == 0) {
+			state->err_new = err_new; state->passes = passes; state->converged = 1;
+			if constexpr (GATE) state->n_in = gs.n_in;
+		}
 		return;
 	}
-	const double nn = (double)rd.n;
+	const double nn = GATE ? (double)gs.n_in : (double)rd.n;
 	const float cq = rd.cq[a], cm = rd.cm[a];
 	const bool carry = rd.carry_means != 0;
 	const double sum_q = sums[a] + nn * (double)cq;
@@ -2263,7 +2339,10 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 		state->R[3 * a] = Rn[0]; state->R[3 * a + 1] = Rn[1]; state->R[3 * a + 2] = Rn[2];
 		state->t[a] = tn; state->cq[a] = cq_new; state->mu_d[a] = mu_d; state->mu_m[a] = mu_m;
 	}
-	if (lane == 0) { state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = iters; }
+	if (lane == 0) {
+		state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = iters;
+		if constexpr (GATE) { state->n_in = gs.n_in; state->cost = gs.cost; }
+	}
 }
 
 // Large clouds (1 M queries = 62 500 partial rows): a single workgroup reading them all is an 85 us tail on a 1.1 ms pass.
@@ -3001,9 +3080,11 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 // the pivot cq (the current transformed source centroid): a = q - cq, r = (q - m) . n, J = (a x n, n) -> the upper triangle of J J^T
 // (21), J r (6), d^2.  Float row sums in fixed order per workgroup, then 64-bit fixed-point adds into kIcpAccReplicas x kIcpPlaneStride
 // accumulators: integer addition is associative, so the totals do not depend on the arrival order, at any N.
-template <int K, int LAYOUT, bool STRIDED>
+// GATE (goicp_set_icp_gate): the owner zeroes its terms when d^2 > IcpState::g2 and otherwise adds 1 to word 28, the inlier count -- an exact
+// float sum of at most 16 ones per workgroup, added unscaled as a plain integer; `capped`: the walk prunes at g2 (rows_nearest<CAP>)
+template <int K, int LAYOUT, bool STRIDED, bool GATE = false>
 __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, const IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                                                    unsigned long long* acc)
+                                                    unsigned long long* acc, int capped = 0)
 {
 	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
@@ -3018,14 +3099,23 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 	const float qx = st->R[0] * p.x + st->R[1] * p.y + st->R[2] * p.z + st->t[0];
 	const float qy = st->R[3] * p.x + st->R[4] * p.y + st->R[5] * p.z + st->t[1];
 	const float qz = st->R[6] * p.x + st->R[7] * p.y + st->R[8] * p.z + st->t[2];
-	const RowNn r = rows_nearest<K, LAYOUT, false, 4>(kd, dt, rootb, l, row, qx, qy, qz, valid);
+	RowNn r;
+	if constexpr (GATE) r = rows_nearest<K, LAYOUT, false, 4, true>(kd, dt, rootb, l, row, qx, qy, qz, valid, capped ? st->g2 : INFINITY);
+	else r = rows_nearest<K, LAYOUT, false, 4>(kd, dt, rootb, l, row, qx, qy, qz, valid);
 	const int wrow = wave * 4 + row;
-	const bool owner = valid ? r.mine : l == 0;
+	bool owner = valid ? r.mine : l == 0;
+	bool inlier = valid;
+	if constexpr (GATE) {
+		// a capped walk that found nothing inside the gate leaves the row without an owning lane: its lane 0 stores the zeros
+		const unsigned mine_row = (unsigned)(__ballot(valid && r.mine) >> (16 * row)) & 0xffffu;
+		owner = mine_row ? (valid && r.mine) : l == 0;
+		inlier = valid && r.mine && r.best <= st->g2;
+	}
 	if (owner) {
 		// the walk's registers are dead here; the terms go to LDS as they are formed (no array of 28 live values)
 		float* dst = red[wrow];
 		float J[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f, d2 = 0.f;
-		if (valid) {
+		if (inlier) {
 			const float4 nm = normals[r.idx];                         // one gather per correspondence (by original index: the walk's slot is dead)
 			const float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];
 			const float ex = qx - r.mx, ey = qy - r.my, ez = qz - r.mz;
@@ -3046,13 +3136,14 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 #pragma unroll
 		for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
 		dst[27] = d2;
+		if constexpr (GATE) dst[kIcpPlaneTerms] = inlier ? 1.f : 0.f;
 	}
 	__syncthreads();
-	if (threadIdx.x < kIcpPlaneTerms) {
+	if (threadIdx.x < kIcpPlaneTerms + (GATE ? 1 : 0)) {
 		float sum = red[0][threadIdx.x];
 #pragma unroll
 		for (int x = 1; x < kIcpThreads / 16; x++) sum += red[x][threadIdx.x];
-		const long long v = __double2ll_rn((double)sum * (double)st->acc_scale);
+		const long long v = GATE && threadIdx.x == kIcpPlaneTerms ? (long long)sum : __double2ll_rn((double)sum * (double)st->acc_scale);
 		unsigned long long* a = acc + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + threadIdx.x;
 		__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
@@ -3078,12 +3169,35 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pas
 	icp_plane_pass_body<K, LAYOUT, STRIDED>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
 }
 
+// the gated plane pass (goicp_set_icp_gate), single pose and batch (bricked DT only)
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_gate_kernel(const float4* __restrict__ src, int N,
+                                                                             const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                             const float4* __restrict__ normals, unsigned long long* __restrict__ acc, int capped)
+{
+	icp_plane_pass_body<K, 1, STRIDED, true>(src, N, st, kd, dt, normals, acc, capped);
+}
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_gate_batch_kernel(const float4* __restrict__ src, int N,
+                                                                                   const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                                   const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
+                                                                                   const int* __restrict__ active, int capped)
+{
+	const int s = active[blockIdx.y];
+	icp_plane_pass_body<K, 1, STRIDED, true>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords, capped);
+}
+
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
 // Gauss-Newton step (A + mu I) x = -b by fp64 Cholesky, mu = 1e-12 trace(A); omega = x[0:3], tau = x[3:6]; dR = Rodrigues(omega);
 // R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is not positive definite (no usable normal) leaves
 // the pose unchanged: the next pass then scores the same error and the loop stops.
+// GATE: word 28 is the inlier count (unscaled); the stop rule is gate_step's, the Cholesky system is the one over the inliers as it stands.
+// PLANE = false: the same wavefront as the gated POINT-TO-POINT finalize -- the gated pass of either metric adds to kIcpPlaneStride-word
+// replicas -- 16 scaled totals and the count in word 16, then finalize_rows<GATE>
+template <bool GATE = false, bool PLANE = true>
 __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc, IcpState* state)
 {
+	static_assert(PLANE || GATE, "the ungated point-to-point finalize is finalize_acc_body");
 	__shared__ double sums[kIcpPlaneStride];
 	__shared__ IcpState st;
 	static_assert(sizeof(IcpState) / 4 <= kFinAccThreads && kIcpPlaneStride * 2 == kFinAccThreads, "one state word per lane; two replicas per pass of the wavefront");
@@ -3101,14 +3215,25 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 	for (int j = 0; j < kPer; j++) x += v[j];
 	x += (unsigned long long)__shfl_xor((long long)x, 32, 64);
 	__syncthreads();                              // the state words are in LDS
-	if (t < kIcpPlaneStride) sums[t] = (double)(long long)x * (double)st.acc_inv;
+	if (t < kIcpPlaneStride) sums[t] = GATE && t == (PLANE ? kIcpPlaneTerms : kIcpAcc) ? (double)(long long)x : (double)(long long)x * (double)st.acc_inv;
 	__syncthreads();
+	if constexpr (!PLANE) {
+		finalize_rows<true>(sums, state, st, t);
+		return;
+	}
 	if (t != 0) return;
 	const float err_new = (float)sums[27];
 	const int passes = st.passes + 1;
-	if (st.frozen) { state->err_new = err_new; state->passes = passes; return; }
-	if (st.err > 0.f && st.err - err_new < st.err_diff_n) {                // jly_icp3d.hpp:255, as finalize_rows
+	GateStep gs{0, 0.f, false};
+	if constexpr (GATE) gs = gate_step(st, err_new, sums[kIcpPlaneTerms]);
+	if (st.frozen) {
+		state->err_new = err_new; state->passes = passes;
+		if constexpr (GATE) state->n_in = gs.n_in;
+		return;
+	}
+	if (GATE ? gs.stop : (st.err > 0.f && st.err - err_new < st.err_diff_n)) {   // jly_icp3d.hpp:255, as finalize_rows
 		state->err_new = err_new; state->passes = passes; state->converged = 1;
+		if constexpr (GATE) state->n_in = gs.n_in;
 		return;
 	}
 	// every loop below has constant bounds and is unrolled: the 6x6 system lives in registers (no scratch)
@@ -3203,10 +3328,24 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 		state->cq[a] = Rn[3 * a] * st.src_centroid[0] + Rn[3 * a + 1] * st.src_centroid[1] + Rn[3 * a + 2] * st.src_centroid[2] + tn[a];
 	}
 	state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = st.iters + 1;
+	if constexpr (GATE) { state->n_in = gs.n_in; state->cost = gs.cost; }
 }
 __global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
 {
 	icp_plane_finalize_body(acc, state);
+}
+// the gated finalizes (goicp_set_icp_gate): PLANE = false point-to-point, true point-to-plane; single pose, and one wavefront per active pose
+template <bool PLANE>
+__global__ __launch_bounds__(kFinAccThreads) void icp_gate_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+{
+	icp_plane_finalize_body<true, PLANE>(acc, state);
+}
+template <bool PLANE>
+__global__ __launch_bounds__(kFinAccThreads) void icp_gate_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
+                                                                          const int* __restrict__ active)
+{
+	const int s = active[blockIdx.x];
+	icp_plane_finalize_body<true, PLANE>(acc + (size_t)s * kIcpBatchAccWords, states + s);
 }
 // goicp_icp_run_batch: one wavefront per active pose, the unchanged plane finalize on that pose's slot
 __global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
@@ -3272,6 +3411,96 @@ hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states
 	else launch_batch_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
 	if (metric == 0) hipLaunchKernelGGL(icp_finalize_batch_acc, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
 	else hipLaunchKernelGGL(icp_plane_finalize_batch, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	return hipGetLastError();
+}
+
+// ---- distance-gated ICP (goicp_set_icp_gate): the gated pass + the gated finalize of the metric, single pose and batch ----
+template <int K>
+static void launch_gate_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt, int metric,
+                          const float4* normals, unsigned long long* acc, int capped, hipStream_t stream)
+{
+	const dim3 block(kIcpThreads);
+	const bool strided = N <= kIcpStridedMaxN;       // the ungated passes' choice
+	if (!active) {
+		const dim3 grid(icp_blocks(N));
+		if (metric == 0) {
+			if (strided) hipLaunchKernelGGL((icp_pass_gate_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, capped);
+			else hipLaunchKernelGGL((icp_pass_gate_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, capped);
+		} else {
+			if (strided) hipLaunchKernelGGL((icp_plane_pass_gate_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, capped);
+			else hipLaunchKernelGGL((icp_plane_pass_gate_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, capped);
+		}
+	} else {
+		const dim3 grid(icp_blocks(N), n_active);
+		if (metric == 0) {
+			if (strided) hipLaunchKernelGGL((icp_pass_gate_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active, capped);
+			else hipLaunchKernelGGL((icp_pass_gate_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active, capped);
+		} else {
+			if (strided) hipLaunchKernelGGL((icp_plane_pass_gate_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active, capped);
+			else hipLaunchKernelGGL((icp_plane_pass_gate_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active, capped);
+		}
+	}
+}
+
+hipError_t launch_icp_iteration_gate(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
+                                     unsigned long long* acc, int capped, hipStream_t stream)
+{
+	if (!st || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals)) return hipErrorInvalidValue;
+	if (kd.K == 1) launch_gate_k<1>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
+	else if (kd.K == 2) launch_gate_k<2>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
+	else launch_gate_k<3>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
+	if (metric == 0) hipLaunchKernelGGL(icp_gate_finalize<false>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
+	else hipLaunchKernelGGL(icp_gate_finalize<true>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
+	return hipGetLastError();
+}
+
+hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                           int metric, const float4* normals, unsigned long long* acc, int capped, hipStream_t stream)
+{
+	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals))
+		return hipErrorInvalidValue;
+	if (kd.K == 1) launch_gate_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
+	else if (kd.K == 2) launch_gate_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
+	else launch_gate_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
+	if (metric == 0) hipLaunchKernelGGL(icp_gate_finalize_batch<false>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	else hipLaunchKernelGGL(icp_gate_finalize_batch<true>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	return hipGetLastError();
+}
+
+// goicp_eval_correspondences: icp_nn_kernel's walk at a pose handed in by value; a neighbour beyond the gate is reported as -1
+template <int K, int LAYOUT>
+__global__ __launch_bounds__(kIcpThreads) void eval_corr_kernel(const float4* __restrict__ src, int N, Pose pose, float g2, KdDesc kd, DtDesc dt,
+                                                                int32_t* __restrict__ idx, float* __restrict__ d2)
+{
+	const int lane = threadIdx.x & 63, row = lane >> 4, l = lane & 15;
+	const int i = (blockIdx.x * (kIcpThreads / 64) + (threadIdx.x >> 6)) * 4 + row;
+	const bool valid = i < N;
+	const Box6x4 rootb = load_child_boxes4(kd.boxes[0], l);
+	const float4 p = src[valid ? i : N - 1];
+	// jly_icp3d.hpp:222-224, left-to-right float sums: the pass's own expression, so d2 holds the pass's bits
+	const float qx = pose.R[0] * p.x + pose.R[1] * p.y + pose.R[2] * p.z + pose.t[0];
+	const float qy = pose.R[3] * p.x + pose.R[4] * p.y + pose.R[5] * p.z + pose.t[1];
+	const float qz = pose.R[6] * p.x + pose.R[7] * p.y + pose.R[8] * p.z + pose.t[2];
+	const RowNn r = rows_nearest<K, LAYOUT, false, 4>(kd, dt, rootb, l, row, qx, qy, qz, valid);
+	if (valid && r.mine) { idx[i] = r.best <= g2 ? r.idx : -1; d2[i] = r.best; }
+}
+
+template <int K>
+static void launch_eval_corr_k(const float4* src, int N, const Pose& pose, float g2, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2, hipStream_t stream)
+{
+	const dim3 grid(icp_blocks(N)), block(kIcpThreads);
+	if (dt.layout) hipLaunchKernelGGL((eval_corr_kernel<K, 1>), grid, block, 0, stream, src, N, pose, g2, kd, dt, idx, d2);
+	else hipLaunchKernelGGL((eval_corr_kernel<K, 0>), grid, block, 0, stream, src, N, pose, g2, kd, dt, idx, d2);
+}
+
+hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pose, float g2, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2,
+                                       hipStream_t stream)
+{
+	if (N <= 0) return hipSuccess;
+	if (!idx || !d2) return hipErrorInvalidValue;
+	if (kd.K == 1) launch_eval_corr_k<1>(src, N, pose, g2, kd, dt, idx, d2, stream);
+	else if (kd.K == 2) launch_eval_corr_k<2>(src, N, pose, g2, kd, dt, idx, d2, stream);
+	else launch_eval_corr_k<3>(src, N, pose, g2, kd, dt, idx, d2, stream);
 	return hipGetLastError();
 }
 

@@ -246,6 +246,11 @@ struct IcpState {
 	int32_t frozen;              // 1: passes only score, the pose is not updated
 	float acc_scale, acc_inv;    // small clouds: the pass adds its sums as 64-bit fixed point, value * acc_scale (a power of two chosen from the
 	                             // clouds' extent so that N terms cannot overflow), into kIcpAccReplicas x 16 accumulators
+	// distance-gated ICP (goicp_set_icp_gate; all zero and never read without a gate)
+	float g2;                    // squared maximum correspondence distance: a correspondence is an inlier iff d^2 <= g2
+	int32_t min_inliers;         // fewer inliers in a pass: the pose stays and the loop stops
+	int32_t n_in;                // inliers of the last pass
+	float cost;                  // truncated cost err + (n - n_in) * g2 of the previous pass: what the stop rule compares (-1: none yet)
 };
 constexpr int kIcpAccReplicas = 32;   // workgroup b adds to replica b % 32: ~60 adds per address and pass (a device-scope atomic takes ~12 ns)
 constexpr int kIcpStridedMaxN = 40000;   // up to this many source points: strangers per wavefront + fixed-point sums (device.hip icp_pass_kernel)
@@ -300,6 +305,23 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 // zeroed 64-bit words (kept zero between iterations by the finalize); the state's acc_scale / acc_inv scale the sums
 hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, const float4* normals,
                                       unsigned long long* acc, hipStream_t stream);
+
+// ---- distance-gated ICP (opt-in, goicp_set_icp_gate) ------------------------------------------------------------------------------
+// One gated iteration of either metric (0 point-to-point, 1 point-to-plane; bricked DT only): the metric's pass in its GATE form -- the
+// owning lane of a query contributes its terms and 1 to a count iff d^2 <= IcpState::g2 -- and the metric's one-wavefront finalize with
+// the count in place of n and the truncated-cost stop rule.  Fixed-point sums at every N.  acc: kIcpAccReplicas x kIcpPlaneStride zeroed
+// 64-bit words for BOTH metrics (kept zero by the finalize); the count is a plain integer in word kIcpGateCountWord[metric] of a replica.
+// capped: the walk's pruning bound starts at min(seed distance, g2) -- exact for every inlier, no neighbour for an outlier.
+constexpr int kIcpGateCountWord[2] = {16, 28};
+hipError_t launch_icp_iteration_gate(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
+                                     unsigned long long* acc, int capped, hipStream_t stream);
+// goicp_icp_run_batch under a gate: launch_icp_iteration_batch's slot scheme around the gated pass and finalize
+hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                           int metric, const float4* normals, unsigned long long* acc, int capped, hipStream_t stream);
+// goicp_eval_correspondences: the pass's transform (jly_icp3d.hpp:222-224 order) and walk for every source point, one launch;
+// idx[i] = original index of the neighbour of source slot i (-1 when d2[i] > g2), d2[i] = the walk's distance bits
+hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pose, float g2, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2,
+                                       hipStream_t stream);
 
 // ---- batched multi-start ICP (goicp_icp_run_batch) --------------------------------------------------------------------------------
 // One iteration of up to kIcpBatchMax independent loops over the same clouds: states[s] is pose slot s's loop state, acc + s * kIcpBatchAccWords

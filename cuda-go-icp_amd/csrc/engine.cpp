@@ -552,6 +552,7 @@ void Engine::release()
 	hipFree(d_cubes_); hipFree(d_rots_); hipFree(d_ub_); hipFree(d_lb_); hipFree(d_scratch_);
 	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
 	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
+	hipFree(d_icp_acc_gate_); d_icp_acc_gate_ = nullptr;
 	hipFree(d_icp_acc_plane_); d_icp_acc_plane_ = nullptr; hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
 	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
@@ -820,6 +821,8 @@ void Engine::set_icp_options(int metric, int normal_k)
 	if (normal_k < 3 || normal_k > kKnnMax) throw std::invalid_argument("goicp_set_icp_options: normal_k must be in [3, 32]");
 	if (metric == 1 && p_.trim_fraction > 0.f) throw std::invalid_argument("goicp_set_icp_options: point-to-plane ICP with trim_fraction > 0 is not supported");
 	if (registering_.load()) throw std::invalid_argument("goicp_set_icp_options: not while a registration runs");
+	if (metric == 1 && icp_gated() && gate_min_inliers_ != 0 && gate_min_inliers_ < 6)
+		throw std::invalid_argument("goicp_set_icp_options: the handle's gate has min_inliers below point-to-plane's floor of 6");
 	if (metric == 1) {
 		ensure_normals(normal_k);
 		if (icp_metric_ != 1) {
@@ -834,6 +837,62 @@ void Engine::set_icp_options(int metric, int normal_k)
 	}
 	icp_metric_ = metric;
 	normal_k_ = normal_k;
+}
+
+void Engine::set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk)
+{
+	if (!(max_corr_dist >= 0.f) || !std::isfinite(max_corr_dist)) throw std::invalid_argument("goicp_set_icp_gate: max_corr_dist must be finite and >= 0 (0 = off)");
+	if (min_inliers < 0 || (min_inliers != 0 && min_inliers < gate_floor()))
+		throw std::invalid_argument("goicp_set_icp_gate: min_inliers must be 0 (the metric's default) or at least 3 (point-to-point) / 6 (point-to-plane)");
+	if (capped_walk != 0 && capped_walk != 1) throw std::invalid_argument("goicp_set_icp_gate: capped_walk must be 0 or 1");
+	if (registering_.load()) throw std::invalid_argument("goicp_set_icp_gate: not while a registration runs");
+	if (max_corr_dist > 0.f) {
+		if (p_.trim_fraction > 0.f || inliers_ < (int)N_) throw std::invalid_argument("goicp_set_icp_gate: a gate together with trim_fraction > 0 is not supported");
+		if (dt_.layout == 0 || p_.icp_fused)
+			throw std::invalid_argument("goicp_set_icp_gate: the gated pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
+		if (!d_icp_acc_gate_) {
+			DeviceGuard guard(dev_);
+			HIPCHK(hipMalloc(&d_icp_acc_gate_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
+			HIPCHK(hipMemsetAsync(d_icp_acc_gate_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
+		}
+	}
+	gate_dist_ = max_corr_dist;
+	gate_min_inliers_ = min_inliers;
+	gate_capped_ = capped_walk;
+}
+
+void Engine::icp_inliers(size_t K, int32_t* out) const
+{
+	if (!out || K == 0 || K != last_inliers_.size()) throw std::invalid_argument("goicp_icp_inliers: K must be the pose count of the last goicp_icp_run (1) or goicp_icp_run_batch");
+	std::memcpy(out, last_inliers_.data(), sizeof(int32_t) * K);
+}
+
+void Engine::eval_correspondences(const float R[9], const float t[3], float max_corr_dist, int32_t* index, float* dist_sq, int32_t* inliers, float* sse)
+{
+	if (!(max_corr_dist >= 0.f) || !std::isfinite(max_corr_dist)) throw std::invalid_argument("goicp_eval_correspondences: max_corr_dist must be finite and >= 0 (0 = no gate)");
+	DeviceGuard guard(dev_);
+	const float g2 = max_corr_dist > 0.f ? max_corr_dist * max_corr_dist : INFINITY;
+	char* base = static_cast<char*>(scratch_bytes((sizeof(int32_t) + sizeof(float)) * N_));
+	int32_t* di = reinterpret_cast<int32_t*>(base);
+	float* dd = reinterpret_cast<float*>(base + sizeof(int32_t) * N_);
+	Pose pose;
+	std::memcpy(pose.R, R, sizeof(pose.R));
+	std::memcpy(pose.t, t, sizeof(pose.t));
+	HIPCHK(launch_eval_correspondences(d_src_, (int)N_, pose, g2, kd_, dt_, di, dd, stream_));
+	std::vector<int32_t> hi(N_), oi(N_);
+	std::vector<float> hd(N_), od(N_);
+	HIPCHK(hipMemcpyAsync(hi.data(), di, sizeof(int32_t) * N_, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(hd.data(), dd, sizeof(float) * N_, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	for (size_t i = 0; i < N_; i++) { oi[(size_t)src_perm_[i]] = hi[i]; od[(size_t)src_perm_[i]] = hd[i]; }   // back to the caller's point order
+	int32_t n_in = 0;
+	double sum = 0.0;
+	for (size_t i = 0; i < N_; i++)
+		if (od[i] <= g2) { n_in++; sum += (double)od[i]; }
+	if (index) std::memcpy(index, oi.data(), sizeof(int32_t) * N_);
+	if (dist_sq) std::memcpy(dist_sq, od.data(), sizeof(float) * N_);
+	if (inliers) *inliers = n_in;
+	if (sse) *sse = (float)sum;
 }
 
 void Engine::target_normals(float* out)
@@ -892,6 +951,11 @@ void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], fl
 	st.n = (float)inliers_;                        // means over the num correspondences used (the reference divides by n, App. B-12)
 	st.carry_means = carry_means;
 	st.frozen = frozen;
+	if (icp_gated()) {
+		st.g2 = gate_dist_ * gate_dist_;               // formed once, in float: the pass compares the walk's d^2 with these bits
+		st.min_inliers = gate_min_inliers_ ? gate_min_inliers_ : gate_floor();
+		st.cost = -1.f;
+	}
 	{
 		// fixed-point scale of the small-cloud pass: every term is a coordinate difference, a product of two, or a squared
 		// distance between a moved source point and the target, all below L^2 with L the sum of the extents; N of them must
@@ -907,7 +971,9 @@ void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], fl
 
 void Engine::icp_launch_one()
 {
-	if (icp_metric_ == 1)       // point-to-plane (set_icp_options refuses it together with trimming)
+	if (icp_gated())            // either metric (set_icp_gate refuses it together with trimming, the linear DT and the fused iteration)
+		HIPCHK(launch_icp_iteration_gate(d_src_, (int)N_, d_icp_state_, kd_, dt_, icp_metric_, d_normals_, d_icp_acc_gate_, gate_capped_, stream_));
+	else if (icp_metric_ == 1)       // point-to-plane (set_icp_options refuses it together with trimming)
 		HIPCHK(launch_icp_iteration_plane(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_normals_, d_icp_acc_plane_, stream_));
 	else if (inliers_ < (int)N_)
 		HIPCHK(launch_icp_iteration_trim(d_src_, (int)N_, inliers_, d_icp_state_, kd_, dt_, d_nn_d2_, d_nn_slot_, d_include_, d_icp_partials_, stream_));
@@ -967,6 +1033,7 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 	if (iters_out) *iters_out = st.iters;
 	cnt_.icp_iters += st.passes;
 	cnt_.icp_runs++;
+	last_inliers_.assign(1, icp_gated() ? st.n_in : (int32_t)inliers_);
 	return st.err_new;
 }
 
@@ -1026,7 +1093,10 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
 		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
 		for (int i = 0; i < k; i++)
-			HIPCHK(launch_icp_iteration_batch(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
+			if (icp_gated())
+				HIPCHK(launch_icp_iteration_batch_gate(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, gate_capped_, stream_));
+			else
+				HIPCHK(launch_icp_iteration_batch(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
 		queued += k;
 		HIPCHK(hipMemcpyAsync(slots[slot], d_batch_states_, sizeof(IcpState) * K, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipEventRecord(evs[slot], stream_));
@@ -1051,8 +1121,10 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 	// read back are final once it has drained, and the pinned lists are free again for the next call
 	HIPCHK(hipStreamSynchronize(stream_));
 	long long passes = 0;
+	last_inliers_.resize(K);
 	for (size_t k = 0; k < K; k++) {
 		const IcpState& st = fin[k];
+		last_inliers_[k] = icp_gated() ? st.n_in : (int32_t)inliers_;
 		std::memcpy(R + 9 * k, st.R, sizeof(st.R));
 		std::memcpy(t + 3 * k, st.t, sizeof(st.t));
 		if (err) err[k] = st.err_new;
@@ -1099,7 +1171,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 	DeviceGuard guard(dev_);
 	TraceRange tr("goicp:icp_run_collective");
 	const int rank = comm->rank, world = comm->world;
-	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0 && icp_metric_ == 0;   // point-to-plane: replicated
+	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0 && icp_metric_ == 0 && !icp_gated();   // point-to-plane, a gate: replicated
 	IcpShardStats& ss = icp_shard_;
 	ss.rank = rank; ss.world = world; ss.sliced = sliced ? 1 : 0;
 	ss.blocks = icp_blocks((int)N_);
@@ -1130,6 +1202,11 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 		h = fnv1a(h, &err_diff, sizeof(err_diff));
 		h = fnv1a(h, ints, sizeof(ints));
 		h = fnv1a(h, &h_icp_state_->acc_scale, sizeof(float));
+		if (icp_gated()) {                             // the gate joins the check word (an ungated handle hashes what it always did)
+			const int32_t gi[2] = {gate_min_inliers_ ? gate_min_inliers_ : gate_floor(), gate_capped_};
+			h = fnv1a(h, &gate_dist_, sizeof(float));
+			h = fnv1a(h, gi, sizeof(gi));
+		}
 		uint64_t w[3] = {h, ~h, health()};
 		const int rc = comm->allreduce_min_u64(comm->ctx, w, 3);
 		if (rc != GOICP_OK) return rc;

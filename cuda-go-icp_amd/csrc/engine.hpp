@@ -166,6 +166,17 @@ public:
 	// normal; metric 1 builds the normals (once per normal_k).  Refused while a registration runs and together with trimming
 	void set_icp_options(int metric, int normal_k);
 	int icp_metric() const { return icp_metric_; }
+	// goicp_icp_gate: a maximum correspondence distance for every ICP this engine runs (0 = off).  A correspondence is an inlier iff the walk's
+	// d^2 <= max_corr_dist^2; sums, update and stop rule run over the inliers (device.hip gate_step).  min_inliers 0 = the metric's floor (3 / 6).
+	// Refused: a negative or non-finite distance, min_inliers below the floor, a gate with trimming, with dt_layout 0 or with icp_fused, while
+	// a registration runs
+	void set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk);
+	bool icp_gated() const { return gate_dist_ > 0.f; }
+	// inlier counts of the last icp_run (K = 1) or icp_run_batch (its K); any other K is refused
+	void icp_inliers(size_t K, int32_t* out) const;
+	// goicp_eval_correspondences: per source point (original order) the neighbour's index (-1 beyond the gate) and d^2 at R|t, the inlier count
+	// and the inliers' sum of d^2 (double sum in source order, rounded once); max_corr_dist 0 = no gate; any output may be null
+	void eval_correspondences(const float R[9], const float t[3], float max_corr_dist, int32_t* index, float* dist_sq, int32_t* inliers, float* sse);
 	void knn_query(const float* q_xyz, size_t n, int k, int32_t* idx, float* d2);
 	double normal_build_ms() const { return normal_build_ms_; }   // exact, ascending (d2, index), n x k
 	void target_normals(float* normals_xyz);                                         // M x 3, original target order (built on first use)
@@ -365,6 +376,11 @@ private:
 	float4* d_normals_ = nullptr;
 	double normal_build_ms_ = 0;
 	unsigned long long* d_icp_acc_plane_ = nullptr;        // kIcpAccReplicas x kIcpPlaneStride, zero between iterations
+	// distance-gated ICP (opt-in): the gate, and the accumulators of its single-pose pass (kIcpAccReplicas x kIcpPlaneStride for either metric)
+	float gate_dist_ = 0.f; int gate_min_inliers_ = 0, gate_capped_ = 1;
+	unsigned long long* d_icp_acc_gate_ = nullptr;
+	std::vector<int32_t> last_inliers_;                    // icp_inliers: the last run's counts
+	int gate_floor() const { return icp_metric_ == 1 ? 6 : 3; }
 	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
 	// goicp_icp_run_batch (allocated on first use, grown on demand): cap pose slots of loop state and accumulators (kIcpBatchAccWords each,
 	// zero between iterations), the pinned mirror of the states (one upload slot + two fetch slots), two active lists (device + pinned)

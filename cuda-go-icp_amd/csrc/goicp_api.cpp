@@ -414,6 +414,39 @@ int goicp_set_icp_options(goicp_handle h, const goicp_icp_options* opt)
 	return guarded([&] { h->e->set_icp_options(opt->metric, opt->normal_k); });
 }
 
+void goicp_icp_gate_default(goicp_icp_gate* out)
+{
+	if (!out) return;
+	out->max_corr_dist = 0.f;
+	out->min_inliers = 0;
+	out->capped_walk = 1;
+}
+
+int goicp_set_icp_gate(goicp_handle h, const goicp_icp_gate* gate)
+{
+	REQUIRE(gate);
+	// what the struct alone decides is refused before the handle is looked at
+	REQUIRE(gate->max_corr_dist >= 0.f && gate->max_corr_dist <= 3.402823466e+38f);
+	REQUIRE(gate->min_inliers == 0 || gate->min_inliers >= 3);
+	REQUIRE(gate->capped_walk == 0 || gate->capped_walk == 1);
+	REQUIRE(h);
+	return guarded([&] { h->e->set_icp_gate(gate->max_corr_dist, gate->min_inliers, gate->capped_walk); });
+}
+
+int goicp_icp_inliers(goicp_handle h, size_t K, int32_t* inliers)
+{
+	REQUIRE(h && inliers && K >= 1);
+	return guarded([&] { h->e->icp_inliers(K, inliers); });
+}
+
+int goicp_eval_correspondences(goicp_handle h, const float R[9], const float t[3], float max_corr_dist, int32_t* index, float* dist_sq, int32_t* inliers,
+                               float* sse_inliers)
+{
+	REQUIRE(max_corr_dist >= 0.f && max_corr_dist <= 3.402823466e+38f);
+	REQUIRE(h && R && t);
+	return guarded([&] { h->e->eval_correspondences(R, t, max_corr_dist, index, dist_sq, inliers, sse_inliers); });
+}
+
 int goicp_knn_query(goicp_handle h, const float* q, size_t n, int32_t k, int32_t* index, float* dist_sq)
 {
 	REQUIRE(h && (n == 0 || (q && index && dist_sq)));

@@ -126,9 +126,10 @@ class TransNode:
 class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
-    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, **params):
+    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, **params):
         """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
-        engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched."""
+        engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched.
+        max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -154,6 +155,39 @@ class Registration:
             except Exception:
                 self.close()
                 raise
+        if max_corr_dist is not None:
+            try:
+                self.set_icp_gate(max_corr_dist)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- distance gate (goicp_icp_gate) ----
+    @staticmethod
+    def icp_gate_default():
+        g = B.CIcpGate()
+        B.load_library().goicp_icp_gate_default(C.byref(g))
+        return g
+
+    def set_icp_gate(self, max_corr_dist=0.0, min_inliers=0, capped_walk=1):
+        """goicp_set_icp_gate: a correspondence takes part in an ICP iteration iff its squared distance is <= max_corr_dist^2 (0 = off)."""
+        g = B.CIcpGate(float(max_corr_dist), int(min_inliers), int(capped_walk))
+        B.check(self._lib.goicp_set_icp_gate(self.handle, C.byref(g)))
+
+    def icp_inliers(self, K=1):
+        """inlier counts (K,) of the last icp run (K = 1) or icp_run_batch (its K)"""
+        n = np.empty(int(K), np.int32)
+        B.check(self._lib.goicp_icp_inliers(self.handle, int(K), n.ctypes.data_as(C.POINTER(C.c_int32))))
+        return n
+
+    def eval_correspondences(self, R, t, max_corr_dist=0.0):
+        """goicp_eval_correspondences at R|t -> (index (N,) int32, -1 beyond the gate; dist_sq (N,) float32; inliers; sse of the inliers)"""
+        R, t = _f32(R, (9,)), _f32(t, (3,))
+        idx, d2 = np.empty(self.ns, np.int32), np.empty(self.ns, np.float32)
+        n, sse = C.c_int32(), C.c_float()
+        B.check(self._lib.goicp_eval_correspondences(self.handle, _fptr(R), _fptr(t), float(max_corr_dist), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     _fptr(d2), C.byref(n), C.byref(sse)))
+        return idx, d2, n.value, np.float32(sse.value)
 
     # ---- ICP metric (goicp_icp_options) ----
     @staticmethod
@@ -300,8 +334,10 @@ class IterativeClosestPoint3D:
     """IterativeClosestPoint3D(reg, pct, pcs, max_iter, threshold, R, t).run() -> (sse, R, t).
     `threshold` is the reference CPU path's err_diff (mean squared error decrease per point)."""
 
-    def __init__(self, reg, max_iter=10000, convergence_threshold=1e-7, R=None, t=None, icp_metric=None, normal_k=None):
+    def __init__(self, reg, max_iter=10000, convergence_threshold=1e-7, R=None, t=None, icp_metric=None, normal_k=None, max_corr_dist=None):
         self.reg, self.max_iter, self.thr = reg, int(max_iter), float(convergence_threshold)
+        if max_corr_dist is not None:                           # the gate of reg's handle (every ICP it runs)
+            reg.set_icp_gate(max_corr_dist)
         if icp_metric is not None or normal_k is not None:      # the options of reg's handle (every ICP it runs)
             reg.set_icp_options(0 if icp_metric is None else icp_metric, 16 if normal_k is None else normal_k)
         self.R = _f32(np.eye(3) if R is None else R, (9,)).copy()
@@ -320,8 +356,8 @@ class FastGoICP:
     """icp::FastGoICP(pct, pcs, mse_threshold, mtx): run() blocks (use a worker thread), the result
     fields are a consistent snapshot (the reference published them unlocked)."""
 
-    def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, **params):
-        self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, **params)
+    def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, max_corr_dist=None, **params):
+        self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, max_corr_dist=max_corr_dist, **params)
         self.mtx = mtx or threading.Lock()
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine

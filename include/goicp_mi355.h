@@ -317,6 +317,38 @@ int goicp_knn_query(goicp_handle h, const float* query_xyz, size_t n, int32_t k,
 /* the target normals (M x 3, original target order) with the handle's normal_k; built on first use if needed */
 int goicp_target_normals(goicp_handle h, float* normals_xyz);
 
+/* ---- distance-gated ICP (opt-in; new: a maximum correspondence distance, the outlier rule of PCL / Open3D) ----------------------
+ * The gate applies to every ICP the handle runs, both metrics: goicp_icp_run, goicp_icp_run_batch, goicp_icp_step, goicp_time_icp_pass, the
+ * ICP inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded* (the DT re-score of a refined pose still scores
+ * all N points, so the search's guarantee is untouched).  g = max_corr_dist, in cloud units as handed to goicp_create; g2 = g * g in float.
+ *   - a correspondence is an inlier iff d^2 <= g2, d^2 being the float goicp_nn_query returns for the transformed point (ties and
+ *     neighbours are goicp_nn_query's): the inlier set of a pass depends on the pose only;
+ *   - all sums of an iteration run over the inliers, n_in of them; the update is the ungated one with n_in in place of n;
+ *   - err = the inliers' sum of d^2 of the last pass; goicp_icp_inliers = its n_in;
+ *   - stop rule: ICP3D::Run's one-sided test on the truncated cost C = err + (N - n_in) * g2 (= sum of min(d^2, g2)):
+ *     stop iff C_prev > 0 && C_prev - C_new < err_diff * N;
+ *   - n_in < min_inliers: the pose stays and the loop stops, status GOICP_OK;
+ *   - while no pass rejects a point, R, t, err and iters are those of the ungated run, bit for bit.
+ * Refused (GOICP_ERR_INVALID): a negative, NaN or infinite distance, min_inliers below the metric's floor (3 point-to-point, 6
+ * point-to-plane; 0 = that floor), capped_walk outside {0, 1}, a gate together with trim_fraction > 0, with dt_layout = 0 or with
+ * icp_fused = 1 (the gated pass is fixed-point only), any change while a registration runs.  icp_nn_cache is ignored under a gate (every
+ * query walks).  goicp_icp_run_collective: the gate joins the check word and the loop runs replicated on every rank;
+ * goicp_register_multi_gpu stays ungated. */
+typedef struct goicp_icp_gate {
+	float max_corr_dist;   /* 0 = off (default) */
+	int32_t min_inliers;   /* 0 = the metric's default */
+	int32_t capped_walk;   /* 1 (default): the neighbour walk prunes at g2 -- same inliers, same sums; 0: the full walk */
+} goicp_icp_gate;
+void goicp_icp_gate_default(goicp_icp_gate* out);
+int goicp_set_icp_gate(goicp_handle h, const goicp_icp_gate* gate);
+/* inlier counts of the last goicp_icp_run (K = 1) or goicp_icp_run_batch (its K); without a gate every count is N.  Any other K: GOICP_ERR_INVALID */
+int goicp_icp_inliers(goicp_handle h, size_t K, int32_t* inliers);
+/* the correspondences of the source cloud at R|t, one launch: per source point (original order) the neighbour's target index (-1 when
+ * d^2 > max_corr_dist^2) and d^2 -- the bits an ICP pass at this pose sees (same transform expression, same walk) -- plus the inlier count
+ * and the inliers' sum of d^2 (summed in double in source order, rounded once).  max_corr_dist = 0: no gate.  Any output may be NULL. */
+int goicp_eval_correspondences(goicp_handle h, const float R[9], const float t[3], float max_corr_dist,
+                               int32_t* index, float* dist_sq, int32_t* inliers, float* sse_inliers);
+
 /* ICP::kdTreeGPUStep / ICP::naiveGPUStep (src/icp_kernel.h:9-13, icp_kernel.cu:176-279): ONE ICP
  * iteration from the engine's current step pose (identity after create); the accumulated pose is
  * visible through goicp_poll().curR/curT. */

@@ -180,6 +180,7 @@ public:
 		if (params) p = *params; else goicp_params_default(&p);
 		p.mse_threshold = mse_threshold;
 		check(goicp_create(&p, reinterpret_cast<const float*>(pct.data()), nt, reinterpret_cast<const float*>(pcs.data()), ns, &h_));
+		ns_ = ns;
 	}
 	~Registration() { goicp_destroy(h_); }
 	Registration(const Registration&) = delete;
@@ -209,6 +210,28 @@ public:
 		goicp_icp_options o{metric, normal_k};
 		check(goicp_set_icp_options(h_, &o));
 	}
+	// a maximum correspondence distance for every ICP this registration runs (goicp_set_icp_gate); 0 switches it off
+	void set_icp_gate(float max_corr_dist, int min_inliers = 0, int capped_walk = 1)
+	{
+		goicp_icp_gate g{max_corr_dist, min_inliers, capped_walk};
+		check(goicp_set_icp_gate(h_, &g));
+	}
+	// goicp_eval_correspondences at R|t: neighbour index per source point (-1 beyond the gate) and squared distance; returns the inlier count
+	int eval_correspondences(Mat3 R, Vec3 t, float max_corr_dist, std::vector<int32_t>* index = nullptr, std::vector<float>* dist_sq = nullptr,
+	                         float* sse_inliers = nullptr) const
+	{
+		float rows[9], tt[3] = {t[0], t[1], t[2]};
+		to_rows(R, rows);
+		int32_t n = 0;
+		std::vector<int32_t> idx;
+		std::vector<float> d2;
+		if (index) idx.resize(ns_);
+		if (dist_sq) d2.resize(ns_);
+		check(goicp_eval_correspondences(h_, rows, tt, max_corr_dist, index ? idx.data() : nullptr, dist_sq ? d2.data() : nullptr, &n, sse_inliers));
+		if (index) *index = idx;
+		if (dist_sq) *dist_sq = d2;
+		return (int)n;
+	}
 
 private:
 	BoundsResult_t bounds(const Mat3& R, int rot_level, const std::vector<TransNode>& tnodes) const
@@ -224,6 +247,7 @@ private:
 		return {lb, ub};
 	}
 	goicp_handle h_ = nullptr;
+	size_t ns_ = 0;
 };
 
 class IterativeClosestPoint3D {
