@@ -87,6 +87,10 @@ class CIcpGate(C.Structure):
     _fields_ = [("max_corr_dist", C.c_float), ("min_inliers", C.c_int32), ("capped_walk", C.c_int32)]
 
 
+class CIcpRobust(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("scale", C.c_float)]
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -157,6 +161,9 @@ SYMBOLS = {
     "goicp_set_icp_gate": (C.c_int, [_vp, C.POINTER(CIcpGate)]),
     "goicp_icp_inliers": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int32)]),
     "goicp_eval_correspondences": (C.c_int, [_vp, _fp, _fp, C.c_float, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), _fp]),
+    "goicp_icp_robust_default": (None, [C.POINTER(CIcpRobust)]),
+    "goicp_set_icp_robust": (C.c_int, [_vp, C.POINTER(CIcpRobust)]),
+    "goicp_icp_robust_stats": (C.c_int, [_vp, C.c_size_t, _fp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),
     "goicp_poll": (C.c_int, [_vp, C.POINTER(CResult)]),

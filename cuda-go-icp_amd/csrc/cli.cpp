@@ -1,6 +1,6 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
-//                                [--point-to-plane] [--normal-k K] [--max-corr-dist D]
+//                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -13,6 +13,9 @@
 //   --max-corr-dist D   every ICP of the run uses only correspondences within distance D (goicp_set_icp_gate; cloud units after
 //               `resize`); output.toml then gets an [icp_gate] table with D and the inlier count of the final pose.  D must be a finite
 //               number > 0, and the flag is refused together with --ranks N > 1 and --trim-fraction F > 0 -- before any device is touched
+//   --robust-kernel {huber,cauchy,gm,tukey} --robust-scale C   every ICP of the run weights its correspondences by that M-estimator with
+//               scale C (goicp_set_icp_robust; cloud units after `resize`).  C must be a finite number > 0, both flags are needed, and they are
+//               refused together with --ranks N > 1, --trim-fraction F > 0 and --max-corr-dist -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -39,12 +42,15 @@ static std::string resolve(const std::string& p, const std::string& toml)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
 	const char* gate_arg = nullptr;
 	float gate = 0.f;
+	const char *rk_arg = nullptr, *rc_arg = nullptr;
+	int robust_kernel = 0;
+	float robust_scale = 0.f;
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -55,6 +61,28 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--point-to-plane")) plane = 1;
 		else if (!std::strcmp(argv[i], "--normal-k") && i + 1 < argc) normal_k = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--max-corr-dist")) gate_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--robust-kernel")) rk_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--robust-scale")) rc_arg = i + 1 < argc ? argv[++i] : "";
+	}
+	if (rk_arg || rc_arg) {
+		// a bad robust kernel is refused before any device is touched
+		static const char* const names[4] = {"huber", "cauchy", "gm", "tukey"};
+		for (int k = 0; rk_arg && k < 4; k++)
+			if (!std::strcmp(rk_arg, names[k])) robust_kernel = k + 1;
+		if (!robust_kernel) {
+			std::fprintf(stderr, "error: --robust-kernel needs one of huber, cauchy, gm, tukey (and --robust-scale needs --robust-kernel), got '%s'\n", rk_arg ? rk_arg : "");
+			return 2;
+		}
+		char* end = nullptr;
+		robust_scale = rc_arg ? std::strtof(rc_arg, &end) : 0.f;
+		if (!rc_arg || end == rc_arg || *end != '\0' || !(robust_scale > 0.f) || !(robust_scale <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: --robust-kernel needs --robust-scale with a finite scale > 0, got '%s'\n", rc_arg ? rc_arg : "");
+			return 2;
+		}
+		if (ranks > 1 || trim_fraction > 0.f || gate_arg) {
+			std::fprintf(stderr, "error: --robust-kernel cannot be combined with --ranks N > 1 (the multi-GPU registration is plain), --trim-fraction F > 0 or --max-corr-dist\n");
+			return 2;
+		}
 	}
 	if (gate_arg) {
 		// a bad gate is refused before any device is touched
@@ -114,6 +142,7 @@ int main(int argc, char** argv)
 		goicp_handle h = engine.registration.handle();
 		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
 		if (gate > 0.f) engine.registration.set_icp_gate(gate);
+		if (robust_kernel) engine.registration.set_icp_robust(robust_kernel, robust_scale);
 		goicp_result r;
 		if (config.mode <= 2) {
 			for (int i = 0; i < iters; i++) check(goicp_icp_step(h));

@@ -1686,8 +1686,43 @@ __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt
 constexpr int kFinThreads = 1024;                  // the stand-alone finalize: 256 row streams x four float4 columns
 struct FinScratch { double wsum[kFinThreads / 64][kIcpAcc]; double sums[kIcpAcc]; float red[kIcpThreads / 16][kIcpAcc]; int last; IcpState st; };   // red: one row of sums per 16-lane row
 template <int T> __device__ __forceinline__ void finalize_reduce(const float* __restrict__ partials, int nblocks, FinScratch& sh);
-template <bool GATE = false>
+template <bool GATE = false, bool ROBUST = false>
 __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, IcpState* __restrict__ state, const IcpState& rd, int lane);
+
+// Robust-kernel ICP (goicp_set_icp_robust): the weight w of a correspondence from its residual r (metric 0: the distance d = sqrtf(d^2); metric 1:
+// |(q - m) . n|) and its term rho of the robust cost C from the distance d, with u = r / c, v = d / c.  Float, on the owning lane, operation by
+// operation as written (-ffp-contract=off; `/` and __fsqrt_rn are the correctly rounded ones), so that a twin can restate them:
+//   1 Huber          w = 1 if r <= c else c / r         rho = d^2 if d <= c else 2 c d - c^2
+//   2 Cauchy         w = 1 / (1 + u^2)                  rho = c^2 log1pf(v^2)
+//   3 Geman-McClure  w = 1 / (1 + u^2)^2                rho = d^2 / (1 + v^2)
+//   4 Tukey          w = (1 - u^2)^2 if r <= c else 0   rho = c^2/3 v^2 (3 - 3 v^2 + v^4) [= c^2/3 (1 - (1 - v^2)^3), without the cancellation] if d <= c else c^2/3
+// rho <= d^2 for every kernel; the min() holds that against rounding (and against an overflowing v^2), so C <= sum d^2 and the pass's fixed-point
+// scale serves.  rho is only read by the stop test.  A Huber term inside the scale is w = 1.0f, rho = the walk's d^2 bits: the plain pass, bit for bit.
+struct RobustTerms { float w, rho; };
+__device__ __forceinline__ RobustTerms robust_terms(int rk, float c, float r, float d, float d2)
+{
+	RobustTerms o;
+	const float u = r / c, u2 = u * u;
+	const float v = d / c, v2 = v * v;
+	const float c2 = c * c;
+	if (rk == 1) {
+		o.w = r <= c ? 1.f : c / r;
+		o.rho = d <= c ? d2 : 2.f * c * d - c2;
+	} else if (rk == 2) {
+		o.w = 1.f / (1.f + u2);
+		o.rho = c2 * log1pf(v2);
+	} else if (rk == 3) {
+		const float s1 = 1.f + u2;
+		o.w = 1.f / (s1 * s1);
+		o.rho = d2 / (1.f + v2);
+	} else {
+		const float a1 = 1.f - u2;
+		o.w = r <= c ? a1 * a1 : 0.f;
+		o.rho = d <= c ? (c2 / 3.f) * (v2 * (3.f - 3.f * v2 + v2 * v2)) : c2 / 3.f;
+	}
+	o.rho = fminf(o.rho, d2);
+	return o;
+}
 
 // FUSED: the workgroup that arrives last (one ticket per launch; agent-scope release before the ticket, acquire
 // after it -- cdna_hip_programming.md Guideline 16, counter form) also runs the finalize, so an ICP iteration is ONE
@@ -1703,12 +1738,16 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 // GATE (goicp_set_icp_gate; ACC form only): the owning lane zeroes its terms when d^2 > IcpState::g2 and contributes 1 to a count otherwise; the
 // accumulator block then has the plane pass's stride (kIcpPlaneStride words per replica), the count a plain integer in word 16.  `capped`: the walk
 // prunes at g2 (rows_nearest<CAP>); an outlier's row may then have no owning lane at all.
-template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES, bool STRIDED, bool ACC, bool SLICE, bool GATE = false>
+// ROBUST (goicp_set_icp_robust; ACC form only, the plain walk): the owning lane multiplies its 15 Kabsch terms by robust_terms' weight -- d^2 stays
+// unweighted: err is over all N points -- and hands w and rho to two more column sums; the block has the plane pass's stride, W = sum w in word 16
+// (scaled by kIcpRobustWScale), C = sum rho in word 17 (scaled as the terms).
+template <int K, int LAYOUT, bool FUSED, bool CACHE, int LEAVES, bool STRIDED, bool ACC, bool SLICE, bool GATE = false, bool ROBUST = false>
 __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, float* partials, int* ticket,
                                               float4* nn_cache, int* hit_counter, int b0, int capped = 0)
 {
 	static_assert(!SLICE || (ACC && !FUSED), "a slice of the pass exists in the fixed-point form only");
 	static_assert(!GATE || (ACC && !FUSED && !CACHE && !SLICE), "the gated pass exists in the fixed-point form only; every query walks");
+	static_assert(!ROBUST || (ACC && !FUSED && !CACHE && !SLICE && !GATE), "the robust pass exists in the fixed-point form only; every query walks; no gate");
 	const int gb = SLICE ? (int)blockIdx.x + b0 : (int)blockIdx.x;   // workgroup index in the world-1 grid
 	__shared__ FinScratch sh;
 	float (*red)[kIcpAcc] = sh.red;                                   // [16 rows of the workgroup][16 sums]
@@ -1760,6 +1799,7 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 #pragma unroll
 	for (int k = 0; k < kIcpAcc; k++) acc[k] = 0.f;
 	bool inlier = valid && r.mine;                               // exactly one lane of the row (GATE: at most one)
+	[[maybe_unused]] RobustTerms rob{0.f, 0.f};                  // ROBUST: a row without a query adds no weight and no cost
 	if constexpr (GATE) inlier = inlier && r.best <= st->g2;
 	if (inlier) {
 		const float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];   // pivots keep the covariance sums well conditioned
@@ -1770,12 +1810,19 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 		acc[9] = ay * bx; acc[10] = ay * by; acc[11] = ay * bz;
 		acc[12] = az * bx; acc[13] = az * by; acc[14] = az * bz;
 		acc[15] = r.best;
+		if constexpr (ROBUST) {
+			const float d = __fsqrt_rn(r.best);
+			rob = robust_terms(st->rk, st->rc, d, d, r.best);
+#pragma unroll
+			for (int k = 0; k < 15; k++) acc[k] *= rob.w;
+		}
 	}
 	// Exactly one lane of a row holds its correspondence (the others hold zeros), so there is nothing to reduce inside a
 	// row: that lane stores its 16 terms to LDS (four 16-byte stores), rows without a query store zeros, and 16 threads add
 	// the workgroup's 16 rows in fixed order.  (The previous form ran 16 DPP row sums + 32 cross-row shuffles per wavefront:
 	// 160 of the ~1 180 VALU instructions of a wavefront, on a kernel the counters show to be VALU-issue-limited.)
 	__shared__ int gate_cnt[GATE ? kIcpThreads / 16 : 1];        // GATE: one inlier flag per row
+	__shared__ float rob_red[ROBUST ? kIcpThreads / 16 : 1][2];  // ROBUST: w and rho per row
 	{
 		const int wrow = wave * 4 + row;
 		bool owner = valid ? r.mine : l == 0;
@@ -1791,9 +1838,21 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 			dst[2] = make_float4(acc[8], acc[9], acc[10], acc[11]);
 			dst[3] = make_float4(acc[12], acc[13], acc[14], acc[15]);
 			if constexpr (GATE) gate_cnt[wrow] = inlier ? 1 : 0;
+			if constexpr (ROBUST) *reinterpret_cast<float2*>(rob_red[wrow]) = make_float2(rob.w, rob.rho);
 		}
 	}
 	__syncthreads();
+	if constexpr (ROBUST) {
+		if (threadIdx.x >= kIcpAcc && threadIdx.x < kIcpAcc + 2) {   // W and C: float column sums in fixed order, as the 16 terms
+			const int col = threadIdx.x - kIcpAcc;
+			float sum = rob_red[0][col];
+#pragma unroll
+			for (int x = 1; x < kIcpThreads / 16; x++) sum += rob_red[x][col];
+			const long long v = __double2ll_rn((double)sum * (col == 0 ? kIcpRobustWScale : (double)st->acc_scale));
+			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + threadIdx.x;
+			__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
 	if constexpr (GATE) {
 		if (threadIdx.x == kIcpAcc) {                             // the workgroup's inlier count: a plain integer, word 16 of the replica
 			int c = 0;
@@ -1822,7 +1881,7 @@ __device__ __forceinline__ void icp_pass_body(const float4* src, int N, IcpState
 			// 1 899 of them) but 16 device-scope 64-bit integer adds of the sums in fixed point -- integer addition is
 			// associative, so the totals are exact and independent of the arrival order: still bit-reproducible
 			const long long v = __double2ll_rn((double)sum * (double)st->acc_scale);
-			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * (GATE ? kIcpPlaneStride : kIcpAcc) + threadIdx.x;
+			unsigned long long* a = reinterpret_cast<unsigned long long*>(partials) + (size_t)(gb & (kIcpAccReplicas - 1)) * (GATE || ROBUST ? kIcpPlaneStride : kIcpAcc) + threadIdx.x;
 			__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		} else {
 			partials[(size_t)blockIdx.x * kIcpAcc + threadIdx.x] = sum;
@@ -1889,6 +1948,24 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_gate
 	const int s = active[blockIdx.y];
 	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, true>(src, N, states + s, kd, dt,
 	                                                                reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0, capped);
+}
+
+// The robust pass (goicp_set_icp_robust), single pose and batch: the default fixed-point pass in its ROBUST form, on the 32-word replica stride.
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_robust_kernel(const float4* __restrict__ src, int N,
+                                                                         IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                         unsigned long long* __restrict__ acc)
+{
+	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, false, true>(src, N, st, kd, dt, reinterpret_cast<float*>(acc), nullptr, nullptr, nullptr, 0);
+}
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_robust_batch_kernel(const float4* __restrict__ src, int N,
+                                                                               IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                               unsigned long long* __restrict__ acc, const int* __restrict__ active)
+{
+	const int s = active[blockIdx.y];
+	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, false, true>(src, N, states + s, kd, dt,
+	                                                                       reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0);
 }
 
 // ---- trimmed ICP (trim_fraction > 0; jly_icp3d.hpp:236-252): NN for every point, exact selection of
@@ -2265,11 +2342,25 @@ __device__ __forceinline__ GateStep gate_step(const IcpState& rd, float err_new,
 	return g;
 }
 
+// The robust loop's decision after a pass (goicp_set_icp_robust): W = sum w, the robust cost C = sum rho, and whether to stop: W below the metric's
+// floor (IcpState::min_inliers), or the reference's one-sided test (jly_icp3d.hpp:255) on C.  While every weight is 1.0f, W is exactly N and C is the
+// pass's err from the same integer total: the plain test, bit for bit.
+struct RobustStep { double W; float cost; bool stop; };
+__device__ __forceinline__ RobustStep robust_step(const IcpState& rd, double W, double C)
+{
+	RobustStep s;
+	s.W = W;
+	s.cost = (float)C;
+	s.stop = W < (double)rd.min_inliers || (rd.cost > 0.f && rd.cost - s.cost < rd.err_diff_n);
+	return s;
+}
+
 // called by every lane of ONE wavefront (lanes >= 3 shadow lane 2 and write nothing)
 // state: where the new pose is written; rd: where the old one is read -- the stand-alone finalize hands in a copy its threads
 // fetched into LDS beside the partial rows (one round trip instead of a chain of four behind the branches below)
 // GATE: sums[16] is the pass's inlier count; it takes n's place in the update, and the stop rule is gate_step's
-template <bool GATE>
+// ROBUST: sums[16] is W, sums[17] is C; W takes n's place (the terms arrive weighted), and the stop rule is robust_step's
+template <bool GATE, bool ROBUST>
 __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, IcpState* __restrict__ state, const IcpState& rd, int lane)
 {
 	const int a = lane < 3 ? lane : 2;
@@ -2278,22 +2369,26 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 	const int passes = rd.passes + 1;
 	GateStep gs{0, 0.f, false};
 	if constexpr (GATE) gs = gate_step(rd, err_new, sums[kIcpAcc]);
+	RobustStep rs{0.0, 0.f, false};
+	if constexpr (ROBUST) rs = robust_step(rd, sums[kIcpAcc], sums[kIcpAcc + 1]);
 	if (rd.frozen) {                                                     // timing / scoring only
 		if (lane == 0) {
 			state->err_new = err_new; state->passes = passes;
 			if constexpr (GATE) state->n_in = gs.n_in;
+			if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; }
 		}
 		return;
 	}
 	const float err = rd.err;
-	if (GATE ? gs.stop : (err > 0.f && err - err_new < rd.err_diff_n)) {   // jly_icp3d.hpp:255
+	if (GATE ? gs.stop : ROBUST ? rs.stop : (err > 0.f && err - err_new < rd.err_diff_n)) {   // jly_icp3d.hpp:255
 		if (lane == 0) {
 			state->err_new = err_new; state->passes = passes; state->converged = 1;
 			if constexpr (GATE) state->n_in = gs.n_in;
+			if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; }
 		}
 		return;
 	}
-	const double nn = GATE ? (double)gs.n_in : (double)rd.n;
+	const double nn = GATE ? (double)gs.n_in : ROBUST ? rs.W : (double)rd.n;
 	const float cq = rd.cq[a], cm = rd.cm[a];
 	const bool carry = rd.carry_means != 0;
 	const double sum_q = sums[a] + nn * (double)cq;
@@ -2342,6 +2437,7 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 	if (lane == 0) {
 		state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = iters;
 		if constexpr (GATE) { state->n_in = gs.n_in; state->cost = gs.cost; }
+		if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; state->cost = rs.cost; }
 	}
 }
 
@@ -3082,10 +3178,14 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 // accumulators: integer addition is associative, so the totals do not depend on the arrival order, at any N.
 // GATE (goicp_set_icp_gate): the owner zeroes its terms when d^2 > IcpState::g2 and otherwise adds 1 to word 28, the inlier count -- an exact
 // float sum of at most 16 ones per workgroup, added unscaled as a plain integer; `capped`: the walk prunes at g2 (rows_nearest<CAP>)
-template <int K, int LAYOUT, bool STRIDED, bool GATE = false>
+// ROBUST (goicp_set_icp_robust; the plain walk): the 27 terms of J J^T and J r are multiplied by robust_terms' weight of |r| (d^2 stays unweighted),
+// each term times its row's weight in the column sums;
+// w goes to word 28 (scaled by kIcpRobustWScale), rho -- of the distance d, the quantity the plain plane loop's stop test reads -- to word 29
+template <int K, int LAYOUT, bool STRIDED, bool GATE = false, bool ROBUST = false>
 __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, const IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
                                                     unsigned long long* acc, int capped = 0)
 {
+	static_assert(!ROBUST || !GATE, "a robust kernel and a gate exclude each other");
 	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
 	const int gb = (int)blockIdx.x;
@@ -3137,13 +3237,23 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 		for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
 		dst[27] = d2;
 		if constexpr (GATE) dst[kIcpPlaneTerms] = inlier ? 1.f : 0.f;
+		if constexpr (ROBUST) {
+			// the 27 terms go to LDS unweighted and the row's weight beside them: the column sums below multiply (J and the walk's registers are
+			// dead by now, so the weight costs no register of the walk's budget)
+			RobustTerms rob{0.f, 0.f};                                // a row without a query adds no weight and no cost
+			if (inlier) rob = robust_terms(st->rk, st->rc, fabsf(res), __fsqrt_rn(d2), d2);
+			dst[kIcpPlaneTerms] = rob.w; dst[kIcpPlaneTerms + 1] = rob.rho;
+		}
 	}
 	__syncthreads();
-	if (threadIdx.x < kIcpPlaneTerms + (GATE ? 1 : 0)) {
-		float sum = red[0][threadIdx.x];
+	if (threadIdx.x < kIcpPlaneTerms + (GATE ? 1 : ROBUST ? 2 : 0)) {
+		// ROBUST: each of the 27 terms times its row's weight, in float, before the sum (d^2, w and rho as they are)
+		const bool weighted = ROBUST && threadIdx.x < kIcpPlaneTerms - 1;
+		float sum = weighted ? red[0][threadIdx.x] * red[0][kIcpPlaneTerms] : red[0][threadIdx.x];
 #pragma unroll
-		for (int x = 1; x < kIcpThreads / 16; x++) sum += red[x][threadIdx.x];
-		const long long v = GATE && threadIdx.x == kIcpPlaneTerms ? (long long)sum : __double2ll_rn((double)sum * (double)st->acc_scale);
+		for (int x = 1; x < kIcpThreads / 16; x++) sum += weighted ? red[x][threadIdx.x] * red[x][kIcpPlaneTerms] : red[x][threadIdx.x];
+		const long long v = GATE && threadIdx.x == kIcpPlaneTerms ? (long long)sum
+		                  : __double2ll_rn((double)sum * (ROBUST && threadIdx.x == kIcpPlaneTerms ? kIcpRobustWScale : (double)st->acc_scale));
 		unsigned long long* a = acc + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + threadIdx.x;
 		__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
@@ -3187,6 +3297,24 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pas
 	icp_plane_pass_body<K, 1, STRIDED, true>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords, capped);
 }
 
+// the robust plane pass (goicp_set_icp_robust), single pose and batch (bricked DT only)
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_robust_kernel(const float4* __restrict__ src, int N,
+                                                                               const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
+                                                                               const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+{
+	icp_plane_pass_body<K, 1, STRIDED, false, true>(src, N, st, kd, dt, normals, acc);
+}
+template <int K, bool STRIDED>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_robust_batch_kernel(const float4* __restrict__ src, int N,
+                                                                                     const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                                     const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
+                                                                                     const int* __restrict__ active)
+{
+	const int s = active[blockIdx.y];
+	icp_plane_pass_body<K, 1, STRIDED, false, true>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
+}
+
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
 // Gauss-Newton step (A + mu I) x = -b by fp64 Cholesky, mu = 1e-12 trace(A); omega = x[0:3], tau = x[3:6]; dR = Rodrigues(omega);
 // R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is not positive definite (no usable normal) leaves
@@ -3194,10 +3322,14 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pas
 // GATE: word 28 is the inlier count (unscaled); the stop rule is gate_step's, the Cholesky system is the one over the inliers as it stands.
 // PLANE = false: the same wavefront as the gated POINT-TO-POINT finalize -- the gated pass of either metric adds to kIcpPlaneStride-word
 // replicas -- 16 scaled totals and the count in word 16, then finalize_rows<GATE>
-template <bool GATE = false, bool PLANE = true>
+// ROBUST: words 28 / 29 (PLANE = false: 16 / 17) are W (scaled by kIcpRobustWScale) and C; the stop rule is robust_step's, the Cholesky system is the
+// weighted one as it stands; PLANE = false: finalize_rows<false, true>
+template <bool GATE = false, bool PLANE = true, bool ROBUST = false>
 __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc, IcpState* state)
 {
-	static_assert(PLANE || GATE, "the ungated point-to-point finalize is finalize_acc_body");
+	static_assert(PLANE || GATE || ROBUST, "the plain point-to-point finalize is finalize_acc_body");
+	static_assert(!GATE || !ROBUST, "a robust kernel and a gate exclude each other");
+	constexpr int kCountWord = PLANE ? kIcpPlaneTerms : kIcpAcc;
 	__shared__ double sums[kIcpPlaneStride];
 	__shared__ IcpState st;
 	static_assert(sizeof(IcpState) / 4 <= kFinAccThreads && kIcpPlaneStride * 2 == kFinAccThreads, "one state word per lane; two replicas per pass of the wavefront");
@@ -3215,10 +3347,12 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 	for (int j = 0; j < kPer; j++) x += v[j];
 	x += (unsigned long long)__shfl_xor((long long)x, 32, 64);
 	__syncthreads();                              // the state words are in LDS
-	if (t < kIcpPlaneStride) sums[t] = GATE && t == (PLANE ? kIcpPlaneTerms : kIcpAcc) ? (double)(long long)x : (double)(long long)x * (double)st.acc_inv;
+	if (t < kIcpPlaneStride)
+		sums[t] = GATE && t == kCountWord ? (double)(long long)x
+		        : (double)(long long)x * (ROBUST && t == kCountWord ? 1.0 / kIcpRobustWScale : (double)st.acc_inv);
 	__syncthreads();
 	if constexpr (!PLANE) {
-		finalize_rows<true>(sums, state, st, t);
+		finalize_rows<GATE, ROBUST>(sums, state, st, t);
 		return;
 	}
 	if (t != 0) return;
@@ -3226,14 +3360,18 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 	const int passes = st.passes + 1;
 	GateStep gs{0, 0.f, false};
 	if constexpr (GATE) gs = gate_step(st, err_new, sums[kIcpPlaneTerms]);
+	RobustStep rs{0.0, 0.f, false};
+	if constexpr (ROBUST) rs = robust_step(st, sums[kIcpPlaneTerms], sums[kIcpPlaneTerms + 1]);
 	if (st.frozen) {
 		state->err_new = err_new; state->passes = passes;
 		if constexpr (GATE) state->n_in = gs.n_in;
+		if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; }
 		return;
 	}
-	if (GATE ? gs.stop : (st.err > 0.f && st.err - err_new < st.err_diff_n)) {   // jly_icp3d.hpp:255, as finalize_rows
+	if (GATE ? gs.stop : ROBUST ? rs.stop : (st.err > 0.f && st.err - err_new < st.err_diff_n)) {   // jly_icp3d.hpp:255, as finalize_rows
 		state->err_new = err_new; state->passes = passes; state->converged = 1;
 		if constexpr (GATE) state->n_in = gs.n_in;
+		if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; }
 		return;
 	}
 	// every loop below has constant bounds and is unrolled: the 6x6 system lives in registers (no scratch)
@@ -3329,6 +3467,7 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 	}
 	state->err = err_new; state->err_new = err_new; state->passes = passes; state->iters = st.iters + 1;
 	if constexpr (GATE) { state->n_in = gs.n_in; state->cost = gs.cost; }
+	if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; state->cost = rs.cost; }
 }
 __global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
 {
@@ -3346,6 +3485,19 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_gate_finalize_batch(unsign
 {
 	const int s = active[blockIdx.x];
 	icp_plane_finalize_body<true, PLANE>(acc + (size_t)s * kIcpBatchAccWords, states + s);
+}
+// the robust finalizes (goicp_set_icp_robust): PLANE = false point-to-point, true point-to-plane; single pose, and one wavefront per active pose
+template <bool PLANE>
+__global__ __launch_bounds__(kFinAccThreads) void icp_robust_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+{
+	icp_plane_finalize_body<false, PLANE, true>(acc, state);
+}
+template <bool PLANE>
+__global__ __launch_bounds__(kFinAccThreads) void icp_robust_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
+                                                                            const int* __restrict__ active)
+{
+	const int s = active[blockIdx.x];
+	icp_plane_finalize_body<false, PLANE, true>(acc + (size_t)s * kIcpBatchAccWords, states + s);
 }
 // goicp_icp_run_batch: one wavefront per active pose, the unchanged plane finalize on that pose's slot
 __global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
@@ -3464,6 +3616,59 @@ hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* s
 	else launch_gate_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
 	if (metric == 0) hipLaunchKernelGGL(icp_gate_finalize_batch<false>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
 	else hipLaunchKernelGGL(icp_gate_finalize_batch<true>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	return hipGetLastError();
+}
+
+// ---- robust-kernel ICP (goicp_set_icp_robust): the robust pass + the robust finalize of the metric, single pose and batch ----
+template <int K>
+static void launch_robust_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt, int metric,
+                            const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	const dim3 block(kIcpThreads);
+	const bool strided = N <= kIcpStridedMaxN;       // the plain passes' choice
+	if (!active) {
+		const dim3 grid(icp_blocks(N));
+		if (metric == 0) {
+			if (strided) hipLaunchKernelGGL((icp_pass_robust_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc);
+			else hipLaunchKernelGGL((icp_pass_robust_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc);
+		} else {
+			if (strided) hipLaunchKernelGGL((icp_plane_pass_robust_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc);
+			else hipLaunchKernelGGL((icp_plane_pass_robust_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc);
+		}
+	} else {
+		const dim3 grid(icp_blocks(N), n_active);
+		if (metric == 0) {
+			if (strided) hipLaunchKernelGGL((icp_pass_robust_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
+			else hipLaunchKernelGGL((icp_pass_robust_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
+		} else {
+			if (strided) hipLaunchKernelGGL((icp_plane_pass_robust_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+			else hipLaunchKernelGGL((icp_plane_pass_robust_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
+		}
+	}
+}
+
+hipError_t launch_icp_iteration_robust(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
+                                       unsigned long long* acc, hipStream_t stream)
+{
+	if (!st || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals)) return hipErrorInvalidValue;
+	if (kd.K == 1) launch_robust_k<1>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
+	else if (kd.K == 2) launch_robust_k<2>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
+	else launch_robust_k<3>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
+	if (metric == 0) hipLaunchKernelGGL(icp_robust_finalize<false>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
+	else hipLaunchKernelGGL(icp_robust_finalize<true>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
+	return hipGetLastError();
+}
+
+hipError_t launch_icp_iteration_batch_robust(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                             int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals))
+		return hipErrorInvalidValue;
+	if (kd.K == 1) launch_robust_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	else if (kd.K == 2) launch_robust_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	else launch_robust_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
+	if (metric == 0) hipLaunchKernelGGL(icp_robust_finalize_batch<false>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	else hipLaunchKernelGGL(icp_robust_finalize_batch<true>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
 	return hipGetLastError();
 }
 

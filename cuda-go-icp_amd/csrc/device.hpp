@@ -251,6 +251,12 @@ struct IcpState {
 	int32_t min_inliers;         // fewer inliers in a pass: the pose stays and the loop stops
 	int32_t n_in;                // inliers of the last pass
 	float cost;                  // truncated cost err + (n - n_in) * g2 of the previous pass: what the stop rule compares (-1: none yet)
+	// robust-kernel ICP (goicp_set_icp_robust; all zero and never read without a kernel).  `cost` above is then the robust cost
+	// C = sum rho of the previous pass, and `min_inliers` the weight floor (3 / 6)
+	int32_t rk;                  // kernel: 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey
+	float rc;                    // scale c > 0
+	float w_sum;                 // W = sum of the weights of the last pass
+	float cost_new;              // C of the last pass
 };
 constexpr int kIcpAccReplicas = 32;   // workgroup b adds to replica b % 32: ~60 adds per address and pass (a device-scope atomic takes ~12 ns)
 constexpr int kIcpStridedMaxN = 40000;   // up to this many source points: strangers per wavefront + fixed-point sums (device.hip icp_pass_kernel)
@@ -322,6 +328,21 @@ hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* s
 // idx[i] = original index of the neighbour of source slot i (-1 when d2[i] > g2), d2[i] = the walk's distance bits
 hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pose, float g2, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2,
                                        hipStream_t stream);
+
+// ---- robust-kernel ICP (opt-in, goicp_set_icp_robust) -----------------------------------------------------------------------------
+// One IRLS iteration of either metric (bricked DT only): the metric's pass in its ROBUST form -- the owning lane of a query forms the
+// weight w of IcpState::rk / rc from its residual in float (robust_terms) and multiplies every term of the update by it; d^2 stays
+// unweighted -- and the metric's one-wavefront finalize with W = sum w in place of n and the stop rule on C = sum rho.  Fixed-point sums at
+// every N.  acc: kIcpAccReplicas x kIcpPlaneStride zeroed 64-bit words for BOTH metrics (kept zero by the finalize); W (scaled by
+// kIcpRobustWScale) is word kIcpGateCountWord[metric] of a replica, C (scaled by the pass's acc_scale) the word after it.
+// kIcpRobustWScale: w <= 1, so a workgroup's float row sum is <= 16 and the total over N <= 2^23 points <= 2^23; times 2^36 that is
+// 2^59 < 2^63.  A sum of weights that are all 1.0f is an integer and stays exact: W == N.
+constexpr double kIcpRobustWScale = 68719476736.0;   // 2^36
+hipError_t launch_icp_iteration_robust(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
+                                       unsigned long long* acc, hipStream_t stream);
+// goicp_icp_run_batch under a kernel: launch_icp_iteration_batch's slot scheme around the robust pass and finalize
+hipError_t launch_icp_iteration_batch_robust(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
+                                             int metric, const float4* normals, unsigned long long* acc, hipStream_t stream);
 
 // ---- batched multi-start ICP (goicp_icp_run_batch) --------------------------------------------------------------------------------
 // One iteration of up to kIcpBatchMax independent loops over the same clouds: states[s] is pose slot s's loop state, acc + s * kIcpBatchAccWords

@@ -847,6 +847,7 @@ void Engine::set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk)
 	if (capped_walk != 0 && capped_walk != 1) throw std::invalid_argument("goicp_set_icp_gate: capped_walk must be 0 or 1");
 	if (registering_.load()) throw std::invalid_argument("goicp_set_icp_gate: not while a registration runs");
 	if (max_corr_dist > 0.f) {
+		if (icp_robust()) throw std::invalid_argument("goicp_set_icp_gate: a gate together with a robust kernel is not supported (goicp_set_icp_robust kernel 0 first)");
 		if (p_.trim_fraction > 0.f || inliers_ < (int)N_) throw std::invalid_argument("goicp_set_icp_gate: a gate together with trim_fraction > 0 is not supported");
 		if (dt_.layout == 0 || p_.icp_fused)
 			throw std::invalid_argument("goicp_set_icp_gate: the gated pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
@@ -859,6 +860,34 @@ void Engine::set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk)
 	gate_dist_ = max_corr_dist;
 	gate_min_inliers_ = min_inliers;
 	gate_capped_ = capped_walk;
+}
+
+void Engine::set_icp_robust(int kernel, float scale)
+{
+	if (kernel < 0 || kernel > 4) throw std::invalid_argument("goicp_set_icp_robust: kernel must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 Tukey");
+	if (kernel != 0 && (!(scale > 0.f) || !std::isfinite(scale))) throw std::invalid_argument("goicp_set_icp_robust: scale must be finite and > 0");
+	if (registering_.load()) throw std::invalid_argument("goicp_set_icp_robust: not while a registration runs");
+	if (kernel != 0) {
+		if (p_.trim_fraction > 0.f || inliers_ < (int)N_) throw std::invalid_argument("goicp_set_icp_robust: a robust kernel together with trim_fraction > 0 is not supported");
+		if (icp_gated()) throw std::invalid_argument("goicp_set_icp_robust: a robust kernel together with a gate is not supported (goicp_set_icp_gate max_corr_dist 0 first)");
+		if (dt_.layout == 0 || p_.icp_fused)
+			throw std::invalid_argument("goicp_set_icp_robust: the robust pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
+		if (!d_icp_acc_gate_) {          // the gated pass's block: same size, and a gate and a kernel exclude each other
+			DeviceGuard guard(dev_);
+			HIPCHK(hipMalloc(&d_icp_acc_gate_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
+			HIPCHK(hipMemsetAsync(d_icp_acc_gate_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
+		}
+	}
+	robust_kernel_ = kernel;
+	robust_scale_ = kernel ? scale : 0.f;
+}
+
+void Engine::icp_robust_stats(size_t K, float* cost, float* weight_sum) const
+{
+	if (K == 0 || K != last_robust_cost_.size())
+		throw std::invalid_argument("goicp_icp_robust_stats: K must be the pose count of the last goicp_icp_run (1) or goicp_icp_run_batch");
+	if (cost) std::memcpy(cost, last_robust_cost_.data(), sizeof(float) * K);
+	if (weight_sum) std::memcpy(weight_sum, last_robust_w_.data(), sizeof(float) * K);
 }
 
 void Engine::icp_inliers(size_t K, int32_t* out) const
@@ -956,6 +985,12 @@ void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], fl
 		st.min_inliers = gate_min_inliers_ ? gate_min_inliers_ : gate_floor();
 		st.cost = -1.f;
 	}
+	if (icp_robust()) {
+		st.rk = robust_kernel_;
+		st.rc = robust_scale_;
+		st.min_inliers = gate_floor();                 // the weight floor: W below it leaves the pose and stops the loop
+		st.cost = -1.f;
+	}
 	{
 		// fixed-point scale of the small-cloud pass: every term is a coordinate difference, a product of two, or a squared
 		// distance between a moved source point and the target, all below L^2 with L the sum of the extents; N of them must
@@ -971,7 +1006,9 @@ void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], fl
 
 void Engine::icp_launch_one()
 {
-	if (icp_gated())            // either metric (set_icp_gate refuses it together with trimming, the linear DT and the fused iteration)
+	if (icp_robust())           // either metric (set_icp_robust refuses it together with a gate, trimming, the linear DT and the fused iteration)
+		HIPCHK(launch_icp_iteration_robust(d_src_, (int)N_, d_icp_state_, kd_, dt_, icp_metric_, d_normals_, d_icp_acc_gate_, stream_));
+	else if (icp_gated())       // either metric (set_icp_gate refuses it together with trimming, the linear DT and the fused iteration)
 		HIPCHK(launch_icp_iteration_gate(d_src_, (int)N_, d_icp_state_, kd_, dt_, icp_metric_, d_normals_, d_icp_acc_gate_, gate_capped_, stream_));
 	else if (icp_metric_ == 1)       // point-to-plane (set_icp_options refuses it together with trimming)
 		HIPCHK(launch_icp_iteration_plane(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_normals_, d_icp_acc_plane_, stream_));
@@ -1034,6 +1071,9 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 	cnt_.icp_iters += st.passes;
 	cnt_.icp_runs++;
 	last_inliers_.assign(1, icp_gated() ? st.n_in : (int32_t)inliers_);
+	// without a kernel every weight is 1: C is the pass's err, W is N
+	last_robust_cost_.assign(1, icp_robust() ? st.cost_new : st.err_new);
+	last_robust_w_.assign(1, icp_robust() ? st.w_sum : (float)inliers_);
 	return st.err_new;
 }
 
@@ -1093,7 +1133,9 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
 		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
 		for (int i = 0; i < k; i++)
-			if (icp_gated())
+			if (icp_robust())
+				HIPCHK(launch_icp_iteration_batch_robust(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
+			else if (icp_gated())
 				HIPCHK(launch_icp_iteration_batch_gate(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, gate_capped_, stream_));
 			else
 				HIPCHK(launch_icp_iteration_batch(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
@@ -1122,9 +1164,13 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 	HIPCHK(hipStreamSynchronize(stream_));
 	long long passes = 0;
 	last_inliers_.resize(K);
+	last_robust_cost_.resize(K);
+	last_robust_w_.resize(K);
 	for (size_t k = 0; k < K; k++) {
 		const IcpState& st = fin[k];
 		last_inliers_[k] = icp_gated() ? st.n_in : (int32_t)inliers_;
+		last_robust_cost_[k] = icp_robust() ? st.cost_new : st.err_new;
+		last_robust_w_[k] = icp_robust() ? st.w_sum : (float)inliers_;
 		std::memcpy(R + 9 * k, st.R, sizeof(st.R));
 		std::memcpy(t + 3 * k, st.t, sizeof(st.t));
 		if (err) err[k] = st.err_new;
@@ -1171,7 +1217,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 	DeviceGuard guard(dev_);
 	TraceRange tr("goicp:icp_run_collective");
 	const int rank = comm->rank, world = comm->world;
-	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0 && icp_metric_ == 0 && !icp_gated();   // point-to-plane, a gate: replicated
+	const bool sliced = inliers_ >= (int)N_ && !p_.icp_fused && dt_.layout != 0 && icp_metric_ == 0 && !icp_gated() && !icp_robust();   // point-to-plane, a gate, a robust kernel: replicated
 	IcpShardStats& ss = icp_shard_;
 	ss.rank = rank; ss.world = world; ss.sliced = sliced ? 1 : 0;
 	ss.blocks = icp_blocks((int)N_);
@@ -1207,12 +1253,16 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 			h = fnv1a(h, &gate_dist_, sizeof(float));
 			h = fnv1a(h, gi, sizeof(gi));
 		}
+		if (icp_robust()) {                            // so do the robust kernel and its scale
+			h = fnv1a(h, &robust_kernel_, sizeof(robust_kernel_));
+			h = fnv1a(h, &robust_scale_, sizeof(float));
+		}
 		uint64_t w[3] = {h, ~h, health()};
 		const int rc = comm->allreduce_min_u64(comm->ctx, w, 3);
 		if (rc != GOICP_OK) return rc;
 		ss.collectives++;
 		if (w[2] != kHealthyWord) return leave(w[2]);
-		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric) or clouds");
+		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric, gate, robust kernel or scale) or clouds");
 	}
 
 	const long long passes0 = cnt_.icp_iters;

@@ -172,6 +172,14 @@ public:
 	// a registration runs
 	void set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk);
 	bool icp_gated() const { return gate_dist_ > 0.f; }
+	// goicp_icp_robust: an M-estimator for every ICP this engine runs (kernel 0 = off; 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey; scale c > 0).
+	// Every term of the update is multiplied by the weight w of the correspondence's residual, W = sum w takes n's place, and the stop rule
+	// reads the robust cost C = sum rho (device.hip robust_terms / robust_step).  Refused: a kernel outside 0..4, a scale that is not finite
+	// and > 0, a kernel with trimming, with a gate, with dt_layout 0 or with icp_fused, while a registration runs
+	void set_icp_robust(int kernel, float scale);
+	bool icp_robust() const { return robust_kernel_ != 0; }
+	// C and W of the last pass of the last icp_run (K = 1) or icp_run_batch (its K); any other K is refused; either output may be null
+	void icp_robust_stats(size_t K, float* cost, float* weight_sum) const;
 	// inlier counts of the last icp_run (K = 1) or icp_run_batch (its K); any other K is refused
 	void icp_inliers(size_t K, int32_t* out) const;
 	// goicp_eval_correspondences: per source point (original order) the neighbour's index (-1 beyond the gate) and d^2 at R|t, the inlier count
@@ -381,6 +389,9 @@ private:
 	unsigned long long* d_icp_acc_gate_ = nullptr;
 	std::vector<int32_t> last_inliers_;                    // icp_inliers: the last run's counts
 	int gate_floor() const { return icp_metric_ == 1 ? 6 : 3; }
+	// robust-kernel ICP (opt-in): kernel and scale; its single-pose pass adds into d_icp_acc_gate_ (a gate and a kernel exclude each other)
+	int32_t robust_kernel_ = 0; float robust_scale_ = 0.f;
+	std::vector<float> last_robust_cost_, last_robust_w_;  // icp_robust_stats: the last run's C and W
 	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
 	// goicp_icp_run_batch (allocated on first use, grown on demand): cap pose slots of loop state and accumulators (kIcpBatchAccWords each,
 	// zero between iterations), the pinned mirror of the states (one upload slot + two fetch slots), two active lists (device + pinned)

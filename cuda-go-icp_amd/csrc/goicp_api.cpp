@@ -433,6 +433,25 @@ int goicp_set_icp_gate(goicp_handle h, const goicp_icp_gate* gate)
 	return guarded([&] { h->e->set_icp_gate(gate->max_corr_dist, gate->min_inliers, gate->capped_walk); });
 }
 
+void goicp_icp_robust_default(goicp_icp_robust* out)
+{
+	if (!out) return;
+	out->kernel = 0;
+	out->scale = 0.f;
+}
+
+int goicp_set_icp_robust(goicp_handle h, const goicp_icp_robust* r)
+{
+	REQUIRE(r && h);
+	return guarded([&] { h->e->set_icp_robust(r->kernel, r->scale); });
+}
+
+int goicp_icp_robust_stats(goicp_handle h, size_t K, float* cost, float* weight_sum)
+{
+	REQUIRE(h && K >= 1);
+	return guarded([&] { h->e->icp_robust_stats(K, cost, weight_sum); });
+}
+
 int goicp_icp_inliers(goicp_handle h, size_t K, int32_t* inliers)
 {
 	REQUIRE(h && inliers && K >= 1);

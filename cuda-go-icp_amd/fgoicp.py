@@ -126,10 +126,12 @@ class TransNode:
 class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
-    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, **params):
+    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, robust_kernel=0, robust_scale=0.0, **params):
         """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
         engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched.
-        max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance."""
+        max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance.
+        robust_kernel / robust_scale: goicp_set_icp_robust after creation -- 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey (or their names)
+        weight every correspondence of every ICP of this engine by its residual; 0 keeps the plain loop."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -161,6 +163,35 @@ class Registration:
             except Exception:
                 self.close()
                 raise
+
+        if robust_kernel:
+            try:
+                self.set_icp_robust(robust_kernel, robust_scale)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- robust kernel (goicp_icp_robust) ----
+    ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "gm": 3, "geman-mcclure": 3, "tukey": 4}
+
+    @staticmethod
+    def icp_robust_default():
+        r = B.CIcpRobust()
+        B.load_library().goicp_icp_robust_default(C.byref(r))
+        return r
+
+    def set_icp_robust(self, kernel=0, scale=0.0):
+        """goicp_set_icp_robust: kernel 0 off, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey (or "huber", "cauchy", "gm", "tukey"); scale c > 0."""
+        if isinstance(kernel, str):
+            kernel = self.ROBUST_KERNELS[kernel.lower()]
+        r = B.CIcpRobust(int(kernel), float(scale))
+        B.check(self._lib.goicp_set_icp_robust(self.handle, C.byref(r)))
+
+    def icp_robust_stats(self, K=1):
+        """(cost (K,), weight_sum (K,)) of the last pass of the last icp run (K = 1) or icp_run_batch (its K)"""
+        c, w = np.empty(int(K), np.float32), np.empty(int(K), np.float32)
+        B.check(self._lib.goicp_icp_robust_stats(self.handle, int(K), _fptr(c), _fptr(w)))
+        return c, w
 
     # ---- distance gate (goicp_icp_gate) ----
     @staticmethod

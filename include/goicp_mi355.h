@@ -349,6 +349,38 @@ int goicp_icp_inliers(goicp_handle h, size_t K, int32_t* inliers);
 int goicp_eval_correspondences(goicp_handle h, const float R[9], const float t[3], float max_corr_dist,
                                int32_t* index, float* dist_sq, int32_t* inliers, float* sse_inliers);
 
+/* ---- robust-kernel ICP (opt-in; new: M-estimator weights, the RobustKernel of Open3D / the loss functions of Ceres) ---------------
+ * Iteratively re-weighted least squares: every correspondence is weighted smoothly by its residual.  The kernel applies to every ICP the
+ * handle runs, both metrics, exactly where the gate does: goicp_icp_run, goicp_icp_run_batch, goicp_icp_step, goicp_time_icp_pass, the ICP
+ * inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded* (the DT re-score of a refined pose is unchanged, so
+ * the search's guarantee is untouched).  c = scale, in cloud units as handed to goicp_create; d = sqrtf(d^2), d^2 being the float
+ * goicp_nn_query returns for the transformed point; the residual is r = d (metric 0) or r = |(q - m) . n| (metric 1); u = r / c, v = d / c.
+ *   kernel             weight w(r)                        cost term rho
+ *   1 Huber            1 if r <= c, else c / r            d^2 if d <= c, else 2 c d - c^2
+ *   2 Cauchy           1 / (1 + u^2)                      c^2 log1p(v^2)
+ *   3 Geman-McClure    1 / (1 + u^2)^2                    d^2 / (1 + v^2)
+ *   4 Tukey            (1 - u^2)^2 if r <= c, else 0      c^2/3 (1 - (1 - v^2)^3) if d <= c, else c^2/3
+ *   - every term an iteration sums (metric 0: the 15 Kabsch terms; metric 1: the 27 terms of J J^T and J r) is multiplied by w in float;
+ *     the update is the plain one with W = sum w in place of n (carried means included; metric 1: the same damped system, weighted);
+ *   - err keeps its meaning: the sum of d^2 over ALL N points of the last pass;
+ *   - stop rule: ICP3D::Run's one-sided test on the robust cost C = sum rho: stop iff C_prev > 0 && C_prev - C_new < err_diff * N.  rho is
+ *     taken of the distance d for both metrics -- for metric 0 that is rho(r); for metric 1 it is the robust form of the sum of d^2 that the
+ *     plain point-to-plane loop tests;
+ *   - W < 3 (metric 0) / 6 (metric 1): the pose stays and the loop stops, status GOICP_OK -- a redescending kernel with a scale far below
+ *     the residuals ends like this; goicp_icp_robust_stats shows it;
+ *   - while every weight of every pass is exactly 1 (a Huber scale above every residual), R, t, err and iters are those of the plain run,
+ *     bit for bit.
+ * Refused (GOICP_ERR_INVALID): a kernel outside 0..4, a scale that is <= 0, NaN or infinite with kernel != 0, a kernel together with
+ * trim_fraction > 0, with a gate (in either order of setting), with dt_layout = 0 or with icp_fused = 1 (the robust pass is fixed-point
+ * only), any change while a registration runs.  icp_nn_cache is ignored under a kernel (every query walks).  goicp_icp_run_collective:
+ * kernel and scale join the check word and the loop runs replicated on every rank; goicp_register_multi_gpu stays plain. */
+typedef struct goicp_icp_robust { int32_t kernel; float scale; } goicp_icp_robust;   /* kernel 0 = off (default) */
+void goicp_icp_robust_default(goicp_icp_robust* out);
+int goicp_set_icp_robust(goicp_handle h, const goicp_icp_robust* r);
+/* of the last goicp_icp_run (K = 1) or goicp_icp_run_batch (its K): robust cost C and weight sum W of each pose's last pass (without a
+ * kernel: err and N).  Either output may be NULL.  Any other K: GOICP_ERR_INVALID */
+int goicp_icp_robust_stats(goicp_handle h, size_t K, float* cost, float* weight_sum);
+
 /* ICP::kdTreeGPUStep / ICP::naiveGPUStep (src/icp_kernel.h:9-13, icp_kernel.cu:176-279): ONE ICP
  * iteration from the engine's current step pose (identity after create); the accumulated pose is
  * visible through goicp_poll().curR/curT. */

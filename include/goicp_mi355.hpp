@@ -216,6 +216,12 @@ public:
 		goicp_icp_gate g{max_corr_dist, min_inliers, capped_walk};
 		check(goicp_set_icp_gate(h_, &g));
 	}
+	// a robust kernel for every ICP this registration runs (goicp_set_icp_robust): 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey; 0 switches it off
+	void set_icp_robust(int kernel, float scale = 0.f)
+	{
+		goicp_icp_robust r{kernel, scale};
+		check(goicp_set_icp_robust(h_, &r));
+	}
 	// goicp_eval_correspondences at R|t: neighbour index per source point (-1 beyond the gate) and squared distance; returns the inlier count
 	int eval_correspondences(Mat3 R, Vec3 t, float max_corr_dist, std::vector<int32_t>* index = nullptr, std::vector<float>* dist_sq = nullptr,
 	                         float* sse_inliers = nullptr) const
