@@ -164,6 +164,8 @@ SYMBOLS = {
     "goicp_icp_robust_default": (None, [C.POINTER(CIcpRobust)]),
     "goicp_set_icp_robust": (C.c_int, [_vp, C.POINTER(CIcpRobust)]),
     "goicp_icp_robust_stats": (C.c_int, [_vp, C.c_size_t, _fp, _fp]),
+    "goicp_set_search_truncation": (C.c_int, [_vp, C.c_float]),
+    "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),
     "goicp_poll": (C.c_int, [_vp, C.POINTER(CResult)]),

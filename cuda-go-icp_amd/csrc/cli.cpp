@@ -1,6 +1,7 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
+//                                [--trunc-dist D]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -16,6 +17,11 @@
 //   --robust-kernel {huber,cauchy,gm,tukey} --robust-scale C   every ICP of the run weights its correspondences by that M-estimator with
 //               scale C (goicp_set_icp_robust; cloud units after `resize`).  C must be a finite number > 0, both flags are needed, and they are
 //               refused together with --ranks N > 1, --trim-fraction F > 0 and --max-corr-dist -- before any device is touched
+//   --trunc-dist D   the SEARCH minimises the truncated cost sum min(DT(R p + t), D)^2 instead of the plain sum of squares
+//               (goicp_set_search_truncation; cloud units after `resize`): bounds, pose scores and the reported best error are all truncated,
+//               and output.toml gets a [search] table with trunc_dist.  Goes with --max-corr-dist, --point-to-plane and --robust-kernel (they
+//               only change the refinement).  D must be a finite number > 0, and the flag is refused together with --ranks N > 1 and
+//               --trim-fraction F > 0 -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -42,13 +48,15 @@ static std::string resolve(const std::string& p, const std::string& toml)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
 	const char* gate_arg = nullptr;
 	float gate = 0.f;
 	const char *rk_arg = nullptr, *rc_arg = nullptr;
+	const char* trunc_arg = nullptr;
+	float trunc = 0.f;
 	int robust_kernel = 0;
 	float robust_scale = 0.f;
 	for (int i = 2; i < argc; i++) {
@@ -63,6 +71,7 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--max-corr-dist")) gate_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-kernel")) rk_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-scale")) rc_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--trunc-dist")) trunc_arg = i + 1 < argc ? argv[++i] : "";
 	}
 	if (rk_arg || rc_arg) {
 		// a bad robust kernel is refused before any device is touched
@@ -94,6 +103,19 @@ int main(int argc, char** argv)
 		}
 		if (ranks > 1 || trim_fraction > 0.f) {
 			std::fprintf(stderr, "error: --max-corr-dist cannot be combined with --ranks N > 1 (the multi-GPU registration is ungated) or --trim-fraction F > 0\n");
+			return 2;
+		}
+	}
+	if (trunc_arg) {
+		// a bad truncation distance is refused before any device is touched
+		char* end = nullptr;
+		trunc = std::strtof(trunc_arg, &end);
+		if (end == trunc_arg || *end != '\0' || !(trunc > 0.f) || !(trunc <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: --trunc-dist needs a finite distance > 0, got '%s'\n", trunc_arg);
+			return 2;
+		}
+		if (ranks > 1 || trim_fraction > 0.f) {
+			std::fprintf(stderr, "error: --trunc-dist cannot be combined with --ranks N > 1 (the multi-GPU registration searches the plain objective) or --trim-fraction F > 0\n");
 			return 2;
 		}
 	}
@@ -143,6 +165,7 @@ int main(int argc, char** argv)
 		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
 		if (gate > 0.f) engine.registration.set_icp_gate(gate);
 		if (robust_kernel) engine.registration.set_icp_robust(robust_kernel, robust_scale);
+		if (trunc > 0.f) engine.registration.set_search_truncation(trunc);
 		goicp_result r;
 		if (config.mode <= 2) {
 			for (int i = 0; i < iters; i++) check(goicp_icp_step(h));
@@ -174,6 +197,12 @@ int main(int argc, char** argv)
 				std::fprintf(f, "\n[icp_gate]\nmax_corr_dist = %.9g\ninliers = %d\n", gate, (int)n_in);
 				std::fclose(f);
 			}
+		}
+		if (trunc > 0.f && !config.io.output.empty()) {
+			FILE* f = std::fopen(config.io.output.c_str(), "a");
+			if (!f) throw std::runtime_error("cannot append to " + config.io.output);
+			std::fprintf(f, "\n[search]\ntrunc_dist = %.9g\n", trunc);
+			std::fclose(f);
 		}
 		if (!config.io.visualization.empty()) engine.write_visualization(config.io.visualization);
 	} catch (const std::exception& e) {

@@ -260,6 +260,18 @@ __device__ __forceinline__ bool is_sibling_set(const CubeRec cr[kGroup])
 // Bricked grids, x siblings less than 4 voxels apart (the deep expansions): the two x lookups of a (y, z) pair often lie in one 16-B x row
 // of a brick, and one 16-B load then serves both (fewer cache-tag lookups than two dword gathers); the values are the same.
 
+// Truncated search objective (opt-in, goicp_set_search_truncation; DtDesc::trunc = g > 0): every term of a bound is clamped at g AFTER its
+// subtractions -- upper-bound term min(m, g)^2, lower-bound term min(max(m - delta, 0), g)^2 with m = max(DT - coeff |p|, 0) as ever.  Valid:
+// rho_g(e) = min(e, g)^2 does not decrease in e >= 0, and max(m - delta, 0) is a lower bound of the residual of every pose of the cube, so
+// rho_g of it is a lower bound of rho_g of that residual.  A grid clamped at g beforehand would give max(min(DT, g) - a, 0) instead: valid as
+// well, but never larger and strictly smaller wherever DT > g and a > 0 (DT = 2 g, a = g: 0 against g) -- it forgets by how much a far point
+// clears g, which is exactly what lets a cube full of outliers keep its floor n_out g^2 under a large radius.  So the clamp is on the term.
+// min(max(x, 0), g) is ONE instruction, the median of (x, 0, g) for g >= 0, and takes the place of the untruncated form's max(x, 0): the
+// truncated kernels issue no more vector instructions per term than the plain ones, except where the plain form had no clamp to replace
+// (the pass without a rotation radius: one median per upper-bound term more).  g = +huge leaves every bit as it was.
+__device__ __forceinline__ float trunc_clamp(float x, float g) { return __builtin_amdgcn_fmed3f(x, 0.f, g); }
+__device__ __forceinline__ f2 trunc_clamp2(f2 x, float g) { return f2{trunc_clamp(x.x, g), trunc_clamp(x.y, g)}; }
+
 // The float at byte offset `off` (bits 2-3) of a 16-B x row, picked with byte permutes: the selectors are per-lane VGPRs, where
 // v_cndmask would hold four lane masks in SGPRs across the four loads (the kernel then spills SGPRs).  row_sel(off) = the two selectors.
 struct RowSel { unsigned lo, hi; };
@@ -273,7 +285,7 @@ __device__ __forceinline__ float row_pick(const float4& r, RowSel s)
 	const unsigned hi = __builtin_amdgcn_perm(__float_as_uint(r.w), __float_as_uint(r.z), s.lo);
 	return __uint_as_float(__builtin_amdgcn_perm(hi, lo, s.hi));
 }
-template <int LAYOUT, int NP, bool LAST_ZERO>
+template <int LAYOUT, int NP, bool LAST_ZERO, bool TRUNC = false>
 __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int p0, int p1, const DtDesc& dt, const Rot9& R0, const SiblingSet& ts, float delta,
                                             const float (&coeff)[NP], f2 (&ub2)[NP][4], f2 (&lb2)[NP][4])
 {
@@ -350,6 +362,13 @@ __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int 
 #pragma unroll
 				for (int q = 0; q < NP; q++) {
 					f2 vq = v, mm = v;
+					if constexpr (TRUNC) {
+						if (!(LAST_ZERO && q == NP - 1)) vq = v - f2{rho[q], rho[q]};
+						mm = trunc_clamp2(vq, dt.trunc);                   // the pass without a radius too: vq = v >= 0 there, the median is min(v, g)
+						ub2[q][k] = ub2[q][k] + mm * mm;
+						const f2 dis = trunc_clamp2(vq + ndelta2, dt.trunc);
+						lb2[q][k] = lb2[q][k] + dis * dis;
+					} else {
 					if (!(LAST_ZERO && q == NP - 1)) {
 						vq = v - f2{rho[q], rho[q]};
 						mm = __builtin_elementwise_max(vq, f2{0.f, 0.f});
@@ -358,6 +377,7 @@ __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int 
 					// max(mm - delta, 0) == max(vq - delta, 0) bit for bit (delta >= 0: vq < 0 gives 0 either way, vq >= 0 is mm; x + (-d) is x - d)
 					const f2 dis = __builtin_elementwise_max(vq + ndelta2, f2{0.f, 0.f});
 					lb2[q][k] = lb2[q][k] + dis * dis;
+					}
 				}
 			}
 		} else {
@@ -368,9 +388,15 @@ __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int 
 #pragma unroll
 				for (int k = 0; k < 4; k++) {
 					const f2 mm = f2{m[2 * k], m[2 * k + 1]};
+					if constexpr (TRUNC) {
+						const f2 mu = trunc_clamp2(mm, dt.trunc), dis = trunc_clamp2(mm - delta2, dt.trunc);
+						ub2[q][k] = ub2[q][k] + mu * mu;
+						lb2[q][k] = lb2[q][k] + dis * dis;
+					} else {
 					ub2[q][k] = ub2[q][k] + mm * mm;
 					const f2 dis = __builtin_elementwise_max(mm - delta2, f2{0.f, 0.f});
 					lb2[q][k] = lb2[q][k] + dis * dis;
+					}
 				}
 			}
 		}
@@ -411,7 +437,7 @@ constexpr int kSortBins = 1 << 15;                // Morton cells, 5 bits per ax
 __device__ __forceinline__ bool qsort_on(const QSort& qs, int ngroups) { return qs.order != nullptr && ngroups >= qs.min_groups; }
 
 // work item `work` of `total` = groups*chunks: one (cube group, point chunk) pair
-template <int LAYOUT, bool LEAN>
+template <int LAYOUT, bool LEAN, bool TRUNC = false>
 __device__ __forceinline__ void bounds_work(
     int work, int total, const float4* __restrict__ src, int N, const DtDesc& dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int chunks, int chunk_pts,
@@ -493,7 +519,7 @@ __device__ __forceinline__ void bounds_work(
 #pragma unroll
 					for (int k = 0; k < 4; k++) { ub2[q][k] = f2{0.f, 0.f}; lb2[q][k] = f2{0.f, 0.f}; }
 				const float co[2] = {coeff, 0.f};
-				lean_points<LAYOUT, 2, true>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);
+				lean_points<LAYOUT, 2, true, TRUNC>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);
 #pragma unroll
 				for (int k = 0; k < 4; k++) { ub[2 * k] = ub2[1][k].x; ub[2 * k + 1] = ub2[1][k].y; lb[2 * k] = lb2[1][k].x; lb[2 * k + 1] = lb2[1][k].y; }
 				bounds_item_store(ub, lb, twin, chunk, chunks, B, scratch, ub_out, lb_out, red);
@@ -505,8 +531,8 @@ __device__ __forceinline__ void bounds_work(
 #pragma unroll
 				for (int k = 0; k < 4; k++) { ub2[0][k] = f2{0.f, 0.f}; lb2[0][k] = f2{0.f, 0.f}; }
 				const float co[1] = {coeff};
-				if (coeff == 0.f) lean_points<LAYOUT, 1, true>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);       // block-uniform: one expansion per workgroup
-				else lean_points<LAYOUT, 1, false>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);
+				if (coeff == 0.f) lean_points<LAYOUT, 1, true, TRUNC>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);       // block-uniform: one expansion per workgroup
+				else lean_points<LAYOUT, 1, false, TRUNC>(src, p0, p1, dt, R0, ts, delta, co, ub2, lb2);
 #pragma unroll
 				for (int k = 0; k < 4; k++) { ub[2 * k] = ub2[0][k].x; ub[2 * k + 1] = ub2[0][k].y; lb[2 * k] = lb2[0][k].x; lb[2 * k + 1] = lb2[0][k].y; }
 			}
@@ -518,9 +544,15 @@ __device__ __forceinline__ void bounds_work(
 			sibling_residuals<LAYOUT>(dt, R0, ts, p, coeff * p.w, m);
 #pragma unroll
 			for (int c = 0; c < kGroup; c++) {
+				if constexpr (TRUNC) {
+					const float mu = trunc_clamp(m[c], dt.trunc), dis = trunc_clamp(m[c] - delta, dt.trunc);
+					ub[c] += mu * mu;
+					lb[c] += dis * dis;
+				} else {
 				ub[c] += m[c] * m[c];
 				const float dis = fmaxf(m[c] - delta, 0.f);
 				lb[c] += dis * dis;
+				}
 			}
 		}
 	} else
@@ -541,9 +573,15 @@ __device__ __forceinline__ void bounds_work(
 			float m = dt_distance<LAYOUT>(dt, rx + cr[c].tx, ry + cr[c].ty, rz + cr[c].tz);
 			m = m - cr[c].coeff * p.w;          // rotation uncertainty radius (jly_goicp.cpp:284-285, :159)
 			if (m < 0.f) m = 0.f;
+			if constexpr (TRUNC) {
+				const float mu = trunc_clamp(m, dt.trunc), dis = trunc_clamp(m - cr[c].delta, dt.trunc);
+				ub[c] += mu * mu;
+				lb[c] += dis * dis;
+			} else {
 			ub[c] += m * m;                      // :302-306
 			const float dis = fmaxf(m - cr[c].delta, 0.f);   // :312-314 (adding 0 when dis <= 0 is the same sum)
 			lb[c] += dis * dis;
+			}
 		}
 	}
 
@@ -598,7 +636,7 @@ __device__ __forceinline__ int add3(int a, int b, int c)
 	return r;
 }
 
-template <bool QUEUED>
+template <bool QUEUED, bool TRUNC = false>
 __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
                                                           const ParentRec* __restrict__ parents, const TileSeg* __restrict__ segs, int nseg_host, int chunks_host,
                                                           int chunk_pts_host, const int* __restrict__ d_nseg, int* __restrict__ d_chunks,
@@ -759,6 +797,13 @@ __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restri
 					for (int k = 0; k < 4; k++) {                         // pair k: children 2k (x0) and 2k + 1 (x1) of y[(k & 1)], z[(k >> 1)]
 						f2 v = f2{*reinterpret_cast<const float*>(tb + add3(ax[0], ay[k & 1], az[k >> 1])), *reinterpret_cast<const float*>(tb + add3(ax[1], ay[k & 1], az[k >> 1]))};
 						f2 m = v;
+						if constexpr (TRUNC) {
+							if constexpr (!UB_PASS) v = v - rho2;
+							m = trunc_clamp2(v, dt.trunc);                        // (the upper-bound pass too: v >= 0 there, the median is min(v, g))
+							ub2[k] = ub2[k] + m * m;
+							const f2 dis = trunc_clamp2(v + ndelta2, dt.trunc);
+							lb2[k] = lb2[k] + dis * dis;
+						} else {
 						if constexpr (!UB_PASS) {
 							v = v - rho2;
 							m = __builtin_elementwise_max(v, f2{0.f, 0.f});
@@ -768,6 +813,7 @@ __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restri
 						// subtraction no longer waits for the clamp (a packed subtract of the packed difference)
 						const f2 dis = __builtin_elementwise_max(v + ndelta2, f2{0.f, 0.f});      // x + (-d) is x - d bit for bit
 						lb2[k] = lb2[k] + dis * dis;
+						}
 					}
 				}
 				};
@@ -783,9 +829,15 @@ __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restri
 #pragma unroll
 					for (int k = 0; k < 4; k++) {
 						const f2 m2 = f2{m[2 * k], m[2 * k + 1]};
+						if constexpr (TRUNC) {
+							const f2 mu = trunc_clamp2(m2, dt.trunc), dis = trunc_clamp2(m2 - delta2, dt.trunc);
+							ub2[k] = ub2[k] + mu * mu;
+							lb2[k] = lb2[k] + dis * dis;
+						} else {
 						ub2[k] = ub2[k] + m2 * m2;
 						const f2 dis = __builtin_elementwise_max(m2 - delta2, f2{0.f, 0.f});
 						lb2[k] = lb2[k] + dis * dis;
+						}
 					}
 				}
 			}
@@ -824,8 +876,8 @@ hipError_t launch_bounds_tile(const float4* src, int N, const DtDesc& dt, const 
 	if (dt.layout != 1 || n < 1 || n > 64 || nseg < 1 || chunks < 1) return hipErrorInvalidValue;
 	int cp = (N + chunks - 1) / chunks;
 	cp = (cp + kTilePatch - 1) / kTilePatch * kTilePatch;
-	hipLaunchKernelGGL(bounds_tile_kernel<false>, dim3(nseg * chunks), dim3(256), 0, stream, src, N, dt, rots, parents, static_cast<const TileSeg*>(segs), nseg, chunks, cp,
-	                   static_cast<const int*>(nullptr), static_cast<int*>(nullptr), scratch, ub, lb, stats);
+	hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_tile_kernel<false, true> : bounds_tile_kernel<false>), dim3(nseg * chunks), dim3(256), 0, stream, src, N, dt, rots, parents,
+	                   static_cast<const TileSeg*>(segs), nseg, chunks, cp, static_cast<const int*>(nullptr), static_cast<int*>(nullptr), scratch, ub, lb, stats);
 	if (chunks > 1) {
 		const int groups = nseg * n, t = groups * 2 * kGroup;
 		hipLaunchKernelGGL(bounds_finalize, dim3((t + 255) / 256), dim3(256), 0, stream, scratch, groups * kGroup, groups, chunks, ub, lb);
@@ -845,7 +897,7 @@ size_t bounds_tile_queue_scratch_floats(int max_groups)
 hipError_t launch_bounds_tile_queue(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const QTile& tile, QCtl* ctl, int parity, hipStream_t stream)
 {
 	if (dt.layout != 1 || N <= 0) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(bounds_tile_kernel<true>, dim3(kTileQueueGrid), dim3(256), 0, stream, src, N, dt, rots, tile.parents[parity], tile.segs[parity], 0, 1, 0,
+	hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_tile_kernel<true, true> : bounds_tile_kernel<true>), dim3(kTileQueueGrid), dim3(256), 0, stream, src, N, dt, rots, tile.parents[parity], tile.segs[parity], 0, 1, 0,
 	                   &ctl->n_tile_segs[parity], &ctl->tile_chunks, tile.scratch, tile.ub, tile.lb, static_cast<unsigned*>(nullptr));
 	return hipGetLastError();
 }
@@ -941,14 +993,14 @@ hipError_t launch_bounds_grouped(const float4* src, int N, const DtDesc& dt, con
 	return hipGetLastError();
 }
 
-template <int LAYOUT, bool LEAN = false>
+template <int LAYOUT, bool LEAN = false, bool TRUNC = false>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int chunks, int chunk_pts,
     float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out)
 {
 	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
-	bounds_work<LAYOUT, LEAN>(blockIdx.x, gridDim.x, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
+	bounds_work<LAYOUT, LEAN, TRUNC>(blockIdx.x, gridDim.x, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
 }
 
 // The same evaluation for a batch whose size only the DEVICE knows (the device-resident BnB queues, bnbqueue.hip):
@@ -961,7 +1013,7 @@ __host__ __device__ inline void bounds_shape(int B, int N, int* groups, int* chu
 // So the fixed grid draws its items dynamically: eight counters, one per XCD slot (blocks b and b+8 share an XCD), each
 // handing out the items whose index is congruent to that slot -- the XCD-aware tiling of bounds_work is kept, and the
 // fetch of the next item overlaps the evaluation of the current one.
-template <int LAYOUT, bool LEAN = false>
+template <int LAYOUT, bool LEAN = false, bool TRUNC = false>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_queue_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots, const ParentRec* __restrict__ parents,
     const int* __restrict__ d_groups, int* __restrict__ work8, int* __restrict__ d_chunks, float* __restrict__ scratch, float* __restrict__ ub_out,
@@ -989,7 +1041,7 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_queue_kernel(
 	int item = next_item[0], buf = 0;
 	while (item * stride + slot < total) {
 		if (threadIdx.x == 0) next_item[buf ^ 1] = atomicAdd(ctr, 1);   // in flight while this item is evaluated
-		bounds_work<LAYOUT, LEAN>(item * stride + slot, total, src, N, dt, rots, nullptr, parents, ngroups * kGroup, groups, chunks, chunk_pts, scratch, ub_out,
+		bounds_work<LAYOUT, LEAN, TRUNC>(item * stride + slot, total, src, N, dt, rots, nullptr, parents, ngroups * kGroup, groups, chunks, chunk_pts, scratch, ub_out,
 		                    lb_out, red, sorted ? qs.order : nullptr, twin);
 		__syncthreads();                                                 // `red` is reused by the next item; next_item is published
 		buf ^= 1;
@@ -1212,6 +1264,13 @@ hipError_t launch_bounds_queue(const float4* src, int N, const DtDesc& dt, const
 		return hipGetLastError();
 	}
 	const dim3 grid(2048), block(kBoundsThreads);                        // 8 workgroups per CU, a multiple of 8 (XCD slots)
+	if (dt.trunc > 0.f) {                                                // the truncated objective (DtDesc::trunc): the same four choices
+		if (dt.layout == 0) hipLaunchKernelGGL((bounds_queue_kernel<0, false, true>), grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
+		else if (dt.layout == 1 && bounds_lean(dt)) hipLaunchKernelGGL((bounds_queue_kernel<1, true, true>), grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
+		else if (dt.layout == 1) hipLaunchKernelGGL((bounds_queue_kernel<1, false, true>), grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
+		else hipLaunchKernelGGL((bounds_queue_kernel<2, false, true>), grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
+		return hipGetLastError();
+	}
 	if (dt.layout == 0) hipLaunchKernelGGL(bounds_queue_kernel<0>, grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
 	else if (dt.layout == 1 && bounds_lean(dt)) hipLaunchKernelGGL((bounds_queue_kernel<1, true>), grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
 	else if (dt.layout == 1) hipLaunchKernelGGL(bounds_queue_kernel<1>, grid, block, 0, stream, src, N, dt, rots, parents, d_groups, d_work8, d_chunks, scratch, ub, lb, searches, parent_search, qs);
@@ -1332,6 +1391,16 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 	int groups, chunks, chunk_pts;
 	bounds_shape(B, N, &groups, &chunks, &chunk_pts);
 	dim3 grid(groups * chunks), block(kBoundsThreads);
+	if (dt.trunc > 0.f) {                                                // the truncated objective (DtDesc::trunc): the same four choices
+		if (dt.layout == 0)
+			hipLaunchKernelGGL((bounds_kernel<0, false, true>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
+		else if (dt.layout == 1 && bounds_lean(dt))
+			hipLaunchKernelGGL((bounds_kernel<1, true, true>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
+		else if (dt.layout == 1)
+			hipLaunchKernelGGL((bounds_kernel<1, false, true>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
+		else
+			hipLaunchKernelGGL((bounds_kernel<2, false, true>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
+	} else
 	if (dt.layout == 0)
 		hipLaunchKernelGGL(bounds_kernel<0>, grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
 	else if (dt.layout == 1 && bounds_lean(dt))

@@ -53,6 +53,10 @@ struct DtDesc {
 	int V;          // voxels per side
 	int VB;         // bricks per side = ceil(V/4)         (layout 1)
 	int layout;
+	// truncation distance g of the search objective (goicp_set_search_truncation; 0 = off).  > 0: the bound launches (launch_bounds*, launch_bounds_queue,
+	// launch_bounds_tile*) pick their TRUNC instantiations, which clamp every term at g (device.hip trunc_clamp); nothing else reads it.  It sits in
+	// what was the padding in front of `scale`: the struct, and with it the argument block of every kernel, keeps its size and offsets
+	float trunc;
 	double scale;   // voxels per unit                      (jly_3ddt.cpp:923)
 	double xmin, ymin, zmin;
 	// float images of the geometry + the error model of the float index fast path (device.hip voxel_fast)
@@ -65,6 +69,7 @@ struct DtDesc {
 	// falls into the voxel, i.e. an upper bound that is almost always the answer itself (launch_nn_seed_build)
 	const int32_t* nn_ids;
 };
+static_assert(sizeof(DtDesc) == 104 && offsetof(DtDesc, trunc) == 20 && offsetof(DtDesc, scale) == 24, "DtDesc layout");
 
 // One translation sub-cube to bound (the inner body of GoICP::InnerBnB, jly_goicp.cpp:262-315).
 struct CubeRec {

@@ -882,6 +882,16 @@ void Engine::set_icp_robust(int kernel, float scale)
 	robust_scale_ = kernel ? scale : 0.f;
 }
 
+void Engine::set_search_truncation(float g)
+{
+	if (!(g >= 0.f) || !std::isfinite(g)) throw std::invalid_argument("goicp_set_search_truncation: max_dist must be finite and >= 0 (0 = off)");
+	if (registering_.load()) throw std::invalid_argument("goicp_set_search_truncation: not while a registration runs");
+	if (g > 0.f && (p_.trim_fraction > 0.f || inliers_ < (int)N_))
+		throw std::invalid_argument("goicp_set_search_truncation: truncation together with trim_fraction > 0 is not supported");
+	dt_.trunc = g;                    // read by the bound launches only (device.hpp DtDesc::trunc)
+	if (d_dt16_) dt16_.trunc = g;
+}
+
 void Engine::icp_robust_stats(size_t K, float* cost, float* weight_sum) const
 {
 	if (K == 0 || K != last_robust_cost_.size())

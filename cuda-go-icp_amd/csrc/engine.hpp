@@ -177,6 +177,14 @@ public:
 	// reads the robust cost C = sum rho (device.hip robust_terms / robust_step).  Refused: a kernel outside 0..4, a scale that is not finite
 	// and > 0, a kernel with trimming, with a gate, with dt_layout 0 or with icp_fused, while a registration runs
 	void set_icp_robust(int kernel, float scale);
+	// goicp_set_search_truncation: the objective of the SEARCH (0 = off, the plain L2 objective).  g > 0: every term of every cube bound and
+	// of every pose score is clamped at g -- E_g(R, t) = sum min(DT(R p + t), g)^2, upper-bound term min(m, g)^2, lower-bound term
+	// min(max(m - delta, 0), g)^2 (device.hip trunc_clamp).  g rides in DtDesc::trunc of both grids, so every launch that takes bounds_dt() or
+	// dt_ -- eval_bounds_dev(_grouped), the device-queue and tile rounds, run_inner_host, inner_bnb, the debug entries, eval_sse and with it the
+	// re-scores of icp_from and register_begin -- evaluates the truncated form; SSEThresh, pruning, early exit and adopt-on-improvement are
+	// untouched.  Refused: a negative or non-finite distance, truncation with trimming, while a registration runs
+	void set_search_truncation(float g);
+	float search_truncation() const { return dt_.trunc; }
 	bool icp_robust() const { return robust_kernel_ != 0; }
 	// C and W of the last pass of the last icp_run (K = 1) or icp_run_batch (its K); any other K is refused; either output may be null
 	void icp_robust_stats(size_t K, float* cost, float* weight_sum) const;

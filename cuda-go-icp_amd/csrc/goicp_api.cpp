@@ -446,6 +446,20 @@ int goicp_set_icp_robust(goicp_handle h, const goicp_icp_robust* r)
 	return guarded([&] { h->e->set_icp_robust(r->kernel, r->scale); });
 }
 
+int goicp_set_search_truncation(goicp_handle h, float max_dist)
+{
+	// what the distance alone decides is refused before the handle is looked at
+	REQUIRE(max_dist >= 0.f && max_dist <= 3.402823466e+38f);
+	REQUIRE(h);
+	return guarded([&] { h->e->set_search_truncation(max_dist); });
+}
+
+int goicp_search_truncation(goicp_handle h, float* max_dist)
+{
+	REQUIRE(h && max_dist);
+	return guarded([&] { *max_dist = h->e->search_truncation(); });
+}
+
 int goicp_icp_robust_stats(goicp_handle h, size_t K, float* cost, float* weight_sum)
 {
 	REQUIRE(h && K >= 1);

@@ -126,12 +126,15 @@ class TransNode:
 class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
-    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, robust_kernel=0, robust_scale=0.0, **params):
+    def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, robust_kernel=0, robust_scale=0.0, trunc_dist=None,
+                 **params):
         """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
         engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched.
         max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance.
         robust_kernel / robust_scale: goicp_set_icp_robust after creation -- 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey (or their names)
-        weight every correspondence of every ICP of this engine by its residual; 0 keeps the plain loop."""
+        weight every correspondence of every ICP of this engine by its residual; 0 keeps the plain loop.
+        trunc_dist: goicp_set_search_truncation after creation -- the search (bounds, pose scores, best_sse) minimises
+        sum min(DT(R p + t), trunc_dist)^2 instead of the plain sum of squares; None or 0 keeps the plain objective."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -170,6 +173,23 @@ class Registration:
             except Exception:
                 self.close()
                 raise
+
+        if trunc_dist:
+            try:
+                self.set_search_truncation(trunc_dist)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- truncated search objective (goicp_set_search_truncation) ----
+    def set_search_truncation(self, max_dist=0.0):
+        """goicp_set_search_truncation: every term of the search's bounds and scores is clamped at max_dist (0 = off, the plain objective)."""
+        B.check(self._lib.goicp_set_search_truncation(self.handle, float(max_dist)))
+
+    def search_truncation(self):
+        g = C.c_float()
+        B.check(self._lib.goicp_search_truncation(self.handle, C.byref(g)))
+        return g.value
 
     # ---- robust kernel (goicp_icp_robust) ----
     ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "gm": 3, "geman-mcclure": 3, "tukey": 4}
@@ -387,8 +407,9 @@ class FastGoICP:
     """icp::FastGoICP(pct, pcs, mse_threshold, mtx): run() blocks (use a worker thread), the result
     fields are a consistent snapshot (the reference published them unlocked)."""
 
-    def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, max_corr_dist=None, **params):
-        self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, max_corr_dist=max_corr_dist, **params)
+    def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, max_corr_dist=None, trunc_dist=None, **params):
+        self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, max_corr_dist=max_corr_dist,
+                                         trunc_dist=trunc_dist, **params)
         self.mtx = mtx or threading.Lock()
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine

@@ -381,6 +381,30 @@ int goicp_set_icp_robust(goicp_handle h, const goicp_icp_robust* r);
  * kernel: err and N).  Either output may be NULL.  Any other K: GOICP_ERR_INVALID */
 int goicp_icp_robust_stats(goicp_handle h, size_t K, float* cost, float* weight_sum);
 
+/* ---- truncated-cost search (opt-in; new: an outlier-robust objective for the GLOBAL part) -------------------------------------------
+ * The gate, the robust kernels and point-to-plane change the refinement only; the search itself -- cube bounds, inner and outer BnB, the
+ * DT re-score that decides whether a refined pose is adopted -- minimises the plain sum of squares over all N source points.  With
+ * max_dist = g > 0 (cloud units as handed to goicp_create, like the gate) the handle's search minimises the TRUNCATED cost instead, the one
+ * gated ICP descends:
+ *     E_g(R, t) = sum_i min(DT(R p_i + t), g)^2.
+ * With m = max(DT(R p + t_c) - coeff |p|, 0) the per-point clamped residual of a cube as ever (same float expression, bit for bit):
+ *     upper-bound term  min(m, g)^2               lower-bound term  min(max(m - delta, 0), g)^2
+ * -- the clamp comes AFTER the subtractions.  The bounds are valid because min(e, g)^2 does not decrease in e >= 0: a lower bound of a
+ * residual, clamped, is a lower bound of the clamped residual.  Everything else stays: SSEThresh = mse_threshold * N, pruning, early
+ * exit, a refined pose is adopted only when its (now truncated) score improves -- so the guarantee holds whatever ICP flavour refines.
+ * What changes meaning on such a handle: goicp_eval_bounds* and goicp_time_bounds_device return the truncated bounds, goicp_eval_sse
+ * returns E_g, goicp_inner_bnb searches E_g, best_sse of goicp_poll (and of the result files) is E_g of the best pose, and 0 <= lb <= ub
+ * <= N g^2 always.  g = +huge reproduces the plain handle's bits.
+ * The threshold: n_out outliers contribute a floor of about n_out g^2 that mse_threshold * N does not know about.  A threshold ABOVE
+ * that floor exits early on sloppy poses; a threshold BELOW the optimum's cost never triggers the early exit and makes the engine prove
+ * the optimum of E_g (to within SSEThresh).  Choose it with the floor in mind.
+ * Refused (GOICP_ERR_INVALID): a negative, NaN or infinite distance, truncation together with trim_fraction > 0 (the trimmed bounds have
+ * no truncated form), any change while a registration runs.  max_dist = 0 switches truncation off again (the plain bits return).
+ * goicp_register_sharded*: works when EVERY rank's handle carries the same max_dist -- as with the other per-handle options that is the
+ * caller's duty, the protocol does not check it; goicp_register_multi_gpu creates its own engines and stays untruncated. */
+int goicp_set_search_truncation(goicp_handle h, float max_dist);
+int goicp_search_truncation(goicp_handle h, float* max_dist);
+
 /* ICP::kdTreeGPUStep / ICP::naiveGPUStep (src/icp_kernel.h:9-13, icp_kernel.cu:176-279): ONE ICP
  * iteration from the engine's current step pose (identity after create); the accumulated pose is
  * visible through goicp_poll().curR/curT. */

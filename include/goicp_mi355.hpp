@@ -222,6 +222,14 @@ public:
 		goicp_icp_robust r{kernel, scale};
 		check(goicp_set_icp_robust(h_, &r));
 	}
+	// the objective of the SEARCH (goicp_set_search_truncation): bounds, pose scores and best_sse become sum min(DT(R p + t), max_dist)^2; 0 switches it off
+	void set_search_truncation(float max_dist) { check(goicp_set_search_truncation(h_, max_dist)); }
+	float search_truncation() const
+	{
+		float g = 0.f;
+		check(goicp_search_truncation(h_, &g));
+		return g;
+	}
 	// goicp_eval_correspondences at R|t: neighbour index per source point (-1 beyond the gate) and squared distance; returns the inlier count
 	int eval_correspondences(Mat3 R, Vec3 t, float max_corr_dist, std::vector<int32_t>* index = nullptr, std::vector<float>* dist_sq = nullptr,
 	                         float* sse_inliers = nullptr) const
