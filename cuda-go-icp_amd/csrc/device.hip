@@ -2396,6 +2396,15 @@ __device__ __forceinline__ void kabsch_rows(double b0, double b1, double b2, int
 		t += v2 * (ks == 2 ? det : 1.0) * lane_get(u2, j);
 		r[j] = (float)t;
 	}
+	// H = 0 has no singular direction at all, and U above is the zero matrix: the rotation of the reference's SVD there is the identity
+	// (U = V = I), the step a pure translation.  It is what a single correspondence gives, exactly: the pass centres on the pivot cq =
+	// R * centroid + t, which for one point is the moved point itself (the same float expression), so every term of H is an exact 0.
+	// Uniform: the norms are wave-wide sums.  An H with two vanishing singular values (collinear correspondences) still leaves two columns
+	// of U zero and the result singular: degenerate geometry beyond this case is not handled here.
+	if (n0 == 0.0 && n1 == 0.0 && n2 == 0.0) {                              // exact zeros only: a NaN in H still propagates
+#pragma unroll
+		for (int j = 0; j < 3; j++) r[j] = row == j ? 1.f : 0.f;
+	}
 }
 
 // The gated loop's decision after a pass (goicp_set_icp_gate): the inlier count, the truncated cost C = err + (N - n_in) * g2 -- the
