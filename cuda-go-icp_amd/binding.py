@@ -91,6 +91,16 @@ class CIcpRobust(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("scale", C.c_float)]
 
 
+class CPoseInfoOptions(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
+
+
+class CPoseInfo(C.Structure):
+    _fields_ = [("information", C.c_double * 36), ("gradient", C.c_double * 6), ("covariance", C.c_double * 36), ("eigenvalues", C.c_double * 6),
+                ("eigenvectors", C.c_double * 36), ("pivot", C.c_double * 3), ("weight_sum", C.c_double), ("cost", C.c_double), ("sse", C.c_double),
+                ("sigma2", C.c_double), ("inliers", C.c_int64), ("rank", C.c_int32), ("metric", C.c_int32), ("dof_nonpositive", C.c_int32)]
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -164,6 +174,11 @@ SYMBOLS = {
     "goicp_icp_robust_default": (None, [C.POINTER(CIcpRobust)]),
     "goicp_set_icp_robust": (C.c_int, [_vp, C.POINTER(CIcpRobust)]),
     "goicp_icp_robust_stats": (C.c_int, [_vp, C.c_size_t, _fp, _fp]),
+    "goicp_pose_info_options_default": (None, [C.POINTER(CPoseInfoOptions)]),
+    "goicp_pose_information": (C.c_int, [_vp, _fp, _fp, C.POINTER(CPoseInfoOptions), C.POINTER(CPoseInfo)]),
+    "goicp_pose_information_batch": (C.c_int, [_vp, C.c_size_t, _fp, _fp, C.POINTER(CPoseInfoOptions), C.POINTER(CPoseInfo)]),
+    "goicp_result_information": (C.c_int, [_vp, C.POINTER(CPoseInfoOptions), C.POINTER(CPoseInfo)]),
+    "goicp_information_decompose": (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "goicp_set_search_truncation": (C.c_int, [_vp, C.c_float]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),

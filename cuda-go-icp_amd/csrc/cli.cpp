@@ -1,7 +1,7 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
-//                                [--trunc-dist D]
+//                                [--trunc-dist D] [--information [--information-rank-tol X]]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -22,9 +22,14 @@
 //               and output.toml gets a [search] table with trunc_dist.  Goes with --max-corr-dist, --point-to-plane and --robust-kernel (they
 //               only change the refinement).  D must be a finite number > 0, and the flag is refused together with --ranks N > 1 and
 //               --trim-fraction F > 0 -- before any device is touched
+//   --information   after the run, the information matrix and covariance of the final pose (goicp_pose_information: the handle's metric and
+//               weights, pivot = the transformed source centroid): one line with rank and sigma, and output.toml gets an [information] table
+//               (rank, sigma2, inliers, weight_sum, eigenvalues, information and covariance as arrays of rows).  --information-rank-tol X sets
+//               rank_tol (in [0, 1)).  Refused together with --ranks N > 1 -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,7 +53,7 @@ static std::string resolve(const std::string& p, const std::string& toml)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
@@ -59,6 +64,9 @@ int main(int argc, char** argv)
 	float trunc = 0.f;
 	int robust_kernel = 0;
 	float robust_scale = 0.f;
+	int information = 0;
+	const char* rank_tol_arg = nullptr;
+	double rank_tol = -1.0;
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -72,6 +80,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--robust-kernel")) rk_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-scale")) rc_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--trunc-dist")) trunc_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--information")) information = 1;
+		else if (!std::strcmp(argv[i], "--information-rank-tol")) rank_tol_arg = i + 1 < argc ? argv[++i] : "";
 	}
 	if (rk_arg || rc_arg) {
 		// a bad robust kernel is refused before any device is touched
@@ -116,6 +126,25 @@ int main(int argc, char** argv)
 		}
 		if (ranks > 1 || trim_fraction > 0.f) {
 			std::fprintf(stderr, "error: --trunc-dist cannot be combined with --ranks N > 1 (the multi-GPU registration searches the plain objective) or --trim-fraction F > 0\n");
+			return 2;
+		}
+	}
+	if (information || rank_tol_arg) {
+		// refused before any device is touched
+		if (!information) {
+			std::fprintf(stderr, "error: --information-rank-tol needs --information\n");
+			return 2;
+		}
+		if (rank_tol_arg) {
+			char* end = nullptr;
+			rank_tol = std::strtod(rank_tol_arg, &end);
+			if (end == rank_tol_arg || *end != '\0' || !(rank_tol >= 0.0 && rank_tol < 1.0)) {
+				std::fprintf(stderr, "error: --information-rank-tol needs a number in [0, 1), got '%s'\n", rank_tol_arg);
+				return 2;
+			}
+		}
+		if (ranks > 1) {
+			std::fprintf(stderr, "error: --information cannot be combined with --ranks N > 1 (the multi-GPU registration has no information pass)\n");
 			return 2;
 		}
 	}
@@ -203,6 +232,32 @@ int main(int argc, char** argv)
 			if (!f) throw std::runtime_error("cannot append to " + config.io.output);
 			std::fprintf(f, "\n[search]\ntrunc_dist = %.9g\n", trunc);
 			std::fclose(f);
+		}
+		if (information) {
+			goicp_pose_info_options io;
+			goicp_pose_info_options_default(&io);
+			if (rank_tol >= 0.0) io.rank_tol = rank_tol;
+			const goicp_pose_info I = engine.registration.pose_information(R, t, &io);
+			std::printf("Information: rank %d of 6, sigma %.7g (metric %d, %lld inliers)\n", (int)I.rank, std::sqrt(I.sigma2), (int)I.metric, (long long)I.inliers);
+			if (!config.io.output.empty()) {
+				FILE* f = std::fopen(config.io.output.c_str(), "a");
+				if (!f) throw std::runtime_error("cannot append to " + config.io.output);
+				std::fprintf(f, "\n[information]\nmetric = %d\nrank = %d\nrank_tol = %.17g\nsigma2 = %.17g\ninliers = %lld\nweight_sum = %.17g\n", (int)I.metric, (int)I.rank,
+				             io.rank_tol, I.sigma2, (long long)I.inliers, I.weight_sum);
+				std::fprintf(f, "eigenvalues = [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g]\n", I.eigenvalues[0], I.eigenvalues[1], I.eigenvalues[2], I.eigenvalues[3],
+				             I.eigenvalues[4], I.eigenvalues[5]);
+				const double* mats[2] = {I.information, I.covariance};
+				const char* names[2] = {"information", "covariance"};
+				for (int m = 0; m < 2; m++) {
+					std::fprintf(f, "%s = [\n", names[m]);
+					for (int i = 0; i < 6; i++) {
+						const double* row = mats[m] + 6 * i;
+						std::fprintf(f, "  [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g],\n", row[0], row[1], row[2], row[3], row[4], row[5]);
+					}
+					std::fprintf(f, "]\n");
+				}
+				std::fclose(f);
+			}
 		}
 		if (!config.io.visualization.empty()) engine.write_visualization(config.io.visualization);
 	} catch (const std::exception& e) {

@@ -3787,6 +3787,161 @@ hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pos
 	return hipGetLastError();
 }
 
+// ---- pose information (goicp_pose_information) ---------------------------------------------------------------------------
+// The Gauss-Newton normal matrix and gradient of either metric at a pose handed in by value, about a pivot c: a = q - c, e = q - m.
+// The pass is the plane pass's: query assignment, the uncapped walk (rows_nearest, four leaves per step: sse needs every point's d^2, an
+// outlier's too, so the gate never caps this walk), the owner lane of a row forms the row's terms and stores them to LDS, float column
+// sums over the workgroup's 16 rows in fixed order, 64-bit fixed-point adds into replica (workgroup & 31) of a kIcpPlaneStride block.
+// The weight w: 1; [d^2 <= g2] under a gate (g2 = +inf without one); robust_terms' weight under a kernel (rk != 0).
+//   METRIC 0 (19 words): W | sum w a (3) | sum w a a^T, upper triangle (6) | sum w a x e (3) | sum w e (3) | sum w d^2 | sum d^2 | n_in;
+//            the owner multiplies by w itself: (w a) a^T, w (a x e), w e, w d^2
+//   METRIC 1 (31 words): sum w j j^T, upper triangle (21) | sum w j r (6) | sum w r^2 | sum d^2 | W | n_in, j = (a x n, n), r = e . n;
+//            the 28 weighted terms go to LDS unweighted and the column sums multiply by the row's w, as the robust plane pass does
+// W is scaled by kIcpRobustWScale, n_in (rows with w > 0) is a plain integer, every other word by PoseInfoArgs::scale.
+template <int K, int METRIC>
+__device__ __forceinline__ void pose_info_body(const float4* src, int N, const PoseInfoArgs& pa, int strided, const KdDesc& kd, const DtDesc& dt,
+                                               const float4* normals, unsigned long long* acc)
+{
+	constexpr int kWords = kPoseInfoWords[METRIC];
+	constexpr int kWordW = METRIC ? 29 : 0, kWordN = METRIC ? 30 : 18;
+	static_assert(kWords <= kIcpPlaneStride, "the words of a replica");
+	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = lane >> 4, l = lane & 15;
+	const int gb = (int)blockIdx.x;
+	const int nw = (N + 3) >> 2, wv = gb * (kIcpThreads / 64) + wave;
+	const int i = strided ? wv + row * nw : wv * 4 + row;
+	const bool valid = wv < nw && i < N;
+	const Box6x4 rootb = load_child_boxes4(kd.boxes[0], l);
+	const float4 p = src[valid ? i : N - 1];
+	// jly_icp3d.hpp:222-224, left-to-right float sums: the pass's own expression
+	const float qx = pa.R[0] * p.x + pa.R[1] * p.y + pa.R[2] * p.z + pa.t[0];
+	const float qy = pa.R[3] * p.x + pa.R[4] * p.y + pa.R[5] * p.z + pa.t[1];
+	const float qz = pa.R[6] * p.x + pa.R[7] * p.y + pa.R[8] * p.z + pa.t[2];
+	const RowNn r = rows_nearest<K, 1, false, 4>(kd, dt, rootb, l, row, qx, qy, qz, valid);
+	const int wrow = wave * 4 + row;
+	if (valid ? r.mine : l == 0) {
+		float* dst = red[wrow];
+		if (!valid) {
+#pragma unroll
+			for (int k = 0; k < kWords; k++) dst[k] = 0.f;       // a row without a query: no terms, no weight, no count
+		} else {
+			const float d2 = r.best;
+			const float ax = qx - pa.c[0], ay = qy - pa.c[1], az = qz - pa.c[2];
+			const float ex = qx - r.mx, ey = qy - r.my, ez = qz - r.mz;
+			if constexpr (METRIC == 0) {
+				float w = d2 <= pa.g2 ? 1.f : 0.f;
+				if (pa.rk) { const float d = __fsqrt_rn(d2); w = robust_terms(pa.rk, pa.rc, d, d, d2).w; }
+				const float wax = w * ax, way = w * ay, waz = w * az;
+				dst[0] = w;
+				dst[1] = wax; dst[2] = way; dst[3] = waz;
+				dst[4] = wax * ax; dst[5] = wax * ay; dst[6] = wax * az;
+				dst[7] = way * ay; dst[8] = way * az; dst[9] = waz * az;
+				dst[10] = w * (ay * ez - az * ey);
+				dst[11] = w * (az * ex - ax * ez);
+				dst[12] = w * (ax * ey - ay * ex);
+				dst[13] = w * ex; dst[14] = w * ey; dst[15] = w * ez;
+				dst[16] = w * d2;
+				dst[17] = d2;
+				dst[kWordN] = w > 0.f ? 1.f : 0.f;
+			} else {
+				const float4 nm = normals[r.idx];                     // by original index, as the plane pass gathers it
+				float res = ex * nm.x;
+				res += ey * nm.y;
+				res += ez * nm.z;
+				float J[6];
+				J[0] = ay * nm.z - az * nm.y;
+				J[1] = az * nm.x - ax * nm.z;
+				J[2] = ax * nm.y - ay * nm.x;
+				J[3] = nm.x; J[4] = nm.y; J[5] = nm.z;
+				int k = 0;
+#pragma unroll
+				for (int a = 0; a < 6; a++)
+#pragma unroll
+					for (int b = a; b < 6; b++) dst[k++] = J[a] * J[b];
+#pragma unroll
+				for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
+				dst[27] = res * res;
+				dst[28] = d2;
+				float w = d2 <= pa.g2 ? 1.f : 0.f;
+				if (pa.rk) w = robust_terms(pa.rk, pa.rc, fabsf(res), __fsqrt_rn(d2), d2).w;
+				dst[kWordW] = w;
+				dst[kWordN] = w > 0.f ? 1.f : 0.f;
+			}
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < kWords) {
+		const bool weighted = METRIC == 1 && threadIdx.x < 28;
+		float sum = weighted ? red[0][threadIdx.x] * red[0][kWordW] : red[0][threadIdx.x];
+#pragma unroll
+		for (int x = 1; x < kIcpThreads / 16; x++) sum += weighted ? red[x][threadIdx.x] * red[x][kWordW] : red[x][threadIdx.x];
+		const long long v = threadIdx.x == kWordN ? (long long)sum
+		                  : __double2ll_rn((double)sum * (threadIdx.x == kWordW ? kIcpRobustWScale : (double)pa.scale));
+		unsigned long long* a = acc + (size_t)(gb & (kIcpAccReplicas - 1)) * kIcpPlaneStride + threadIdx.x;
+		__hip_atomic_fetch_add(a, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+template <int K, int METRIC>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void pose_info_kernel(const float4* __restrict__ src, int N, PoseInfoArgs pa, int strided,
+                                                                  KdDesc kd, DtDesc dt, const float4* __restrict__ normals,
+                                                                  unsigned long long* __restrict__ acc)
+{
+	pose_info_body<K, METRIC>(src, N, pa, strided, kd, dt, normals, acc);
+}
+
+// goicp_pose_information_batch: blockIdx.y is the pose slot -- its argument block args[slot], its accumulator block acc + slot * kIcpBatchAccWords.
+// The body, the queries of a workgroup, the replica and the scale are the single call's, so a slot's integer totals are the single call's bit for bit.
+template <int K, int METRIC>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void pose_info_batch_kernel(const float4* __restrict__ src, int N,
+                                                                        const PoseInfoArgs* __restrict__ args, int strided, KdDesc kd, DtDesc dt,
+                                                                        const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+{
+	const int s = (int)blockIdx.y;
+	pose_info_body<K, METRIC>(src, N, args[s], strided, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
+}
+
+template <int K>
+static void launch_pose_info_k(const float4* src, int N, const PoseInfoArgs* h_args, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd,
+                               const DtDesc& dt, const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	const dim3 block(kIcpThreads);
+	const int strided = N <= kIcpStridedMaxN ? 1 : 0;        // the ICP passes' choice
+	if (h_args) {
+		const dim3 grid(icp_blocks(N));
+		if (metric == 0) hipLaunchKernelGGL((pose_info_kernel<K, 0>), grid, block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc);
+		else hipLaunchKernelGGL((pose_info_kernel<K, 1>), grid, block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc);
+	} else {
+		const dim3 grid(icp_blocks(N), n_poses);
+		if (metric == 0) hipLaunchKernelGGL((pose_info_batch_kernel<K, 0>), grid, block, 0, stream, src, N, d_args, strided, kd, dt, normals, acc);
+		else hipLaunchKernelGGL((pose_info_batch_kernel<K, 1>), grid, block, 0, stream, src, N, d_args, strided, kd, dt, normals, acc);
+	}
+}
+
+static hipError_t launch_pose_info_any(const float4* src, int N, const PoseInfoArgs* h_args, const PoseInfoArgs* d_args, int n_poses, int metric,
+                                       const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	if (N <= 0 || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals) || n_poses < 1 || n_poses > kIcpBatchMax)
+		return hipErrorInvalidValue;
+	if (kd.K == 1) launch_pose_info_k<1>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+	else if (kd.K == 2) launch_pose_info_k<2>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+	else launch_pose_info_k<3>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+	return hipGetLastError();
+}
+
+hipError_t launch_pose_info(const float4* src, int N, const PoseInfoArgs& args, int metric, const KdDesc& kd, const DtDesc& dt, const float4* normals,
+                            unsigned long long* acc, hipStream_t stream)
+{
+	return launch_pose_info_any(src, N, &args, nullptr, 1, metric, kd, dt, normals, acc, stream);
+}
+
+hipError_t launch_pose_info_batch(const float4* src, int N, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd, const DtDesc& dt,
+                                  const float4* normals, unsigned long long* acc, hipStream_t stream)
+{
+	if (!d_args) return hipErrorInvalidValue;
+	return launch_pose_info_any(src, N, nullptr, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Exact Euclidean distance transform of the seed grid (replaces DT3D::Build's 8-pass propagation,
 // jly_3ddt.cpp:710-742; same bbox/expand/cubify/int(x+0.5) seeding, jly_3ddt.cpp:889-965).

@@ -359,6 +359,28 @@ constexpr int kIcpBatchAccWords = kIcpAccReplicas * kIcpPlaneStride;   // accumu
 hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
                                       int metric, const float4* normals, unsigned long long* acc, hipStream_t stream);
 
+// ---- pose information (goicp_pose_information) -------------------------------------------------------------------------
+// One pass at a pose handed in by value: the sums of the Gauss-Newton normal matrix and gradient about the pivot c, of either metric, under the
+// weights of a plain (g2 = +inf, rk = 0), gated (g2 finite) or robust (rk != 0, rc) handle.  Bricked DT only.  acc: kIcpAccReplicas x
+// kIcpPlaneStride zeroed 64-bit words (the caller zeroes them and adds up the replicas); the first kPoseInfoWords[metric] words of a replica
+// are used -- their order: device.hip pose_info_body.  scale: the power of two every word but W (kIcpRobustWScale) and the count is scaled by.
+struct PoseInfoArgs {
+	float R[9], t[3];
+	float c[3];         // pivot
+	float g2;           // squared gate, +inf = none
+	int32_t rk;         // robust kernel, 0 = none
+	float rc;           // its scale
+	float scale;        // fixed-point scale of the sums
+	int32_t pad;
+};
+static_assert(sizeof(PoseInfoArgs) == 80, "PoseInfoArgs layout");
+constexpr int kPoseInfoWords[2] = {19, 31};
+hipError_t launch_pose_info(const float4* src, int N, const PoseInfoArgs& args, int metric, const KdDesc& kd, const DtDesc& dt, const float4* normals,
+                            unsigned long long* acc, hipStream_t stream);
+// n_poses <= kIcpBatchMax argument blocks in device memory, slot s adding into acc + s * kIcpBatchAccWords: each slot the single call bit for bit
+hipError_t launch_pose_info_batch(const float4* src, int N, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd, const DtDesc& dt,
+                                  const float4* normals, unsigned long long* acc, hipStream_t stream);
+
 // min of n floats (+ first index attaining it, may be null): one workgroup; v must be 16-byte aligned
 hipError_t launch_reduce_min(const float* v, int n, float* out_min, int* out_idx, hipStream_t stream);
 

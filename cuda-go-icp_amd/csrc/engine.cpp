@@ -553,6 +553,7 @@ void Engine::release()
 	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
 	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
 	hipFree(d_icp_acc_gate_); d_icp_acc_gate_ = nullptr;
+	hipFree(d_info_acc_); d_info_acc_ = nullptr; hipFree(d_info_args_); d_info_args_ = nullptr; info_cap_ = 0;
 	hipFree(d_icp_acc_plane_); d_icp_acc_plane_ = nullptr; hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
 	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
@@ -961,6 +962,213 @@ void Engine::source_transformed(const float R[9], const float t[3], float* out)
 		float* o = out + 3 * (size_t)src_perm_[i];
 		o[0] = h[4 * i]; o[1] = h[4 * i + 1]; o[2] = h[4 * i + 2];
 	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pose information (goicp_pose_information): one pass of sums on the device, the finishing step in fp64 on the host
+// ------------------------------------------------------------------------------------------------
+// Eigen-decomposition of a symmetric 6x6 by cyclic Jacobi (fp64), eigenvalues ascending, eigenvectors as rows; rank = the eigenvalues above
+// rank_tol * lambda_max (strictly: one exactly at the threshold is dropped); pinv over the retained ones.  A diagonal input is returned as it is.
+void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank)
+{
+	if (!(rank_tol >= 0.0 && rank_tol < 1.0)) throw std::invalid_argument("goicp_information_decompose: rank_tol must be in [0, 1)");
+	double a[6][6], v[6][6];
+	for (int i = 0; i < 6; i++)
+		for (int j = 0; j < 6; j++) {
+			if (!std::isfinite(info[6 * i + j])) throw std::invalid_argument("goicp_information_decompose: the matrix has a non-finite entry");
+			a[i][j] = 0.5 * (info[6 * i + j] + info[6 * j + i]);
+			v[i][j] = i == j ? 1.0 : 0.0;
+		}
+	for (int sweep = 0; sweep < 64; sweep++) {
+		double off = 0.0;
+		for (int i = 0; i < 6; i++)
+			for (int j = i + 1; j < 6; j++) off += a[i][j] * a[i][j];
+		if (off == 0.0) break;
+		for (int p = 0; p < 5; p++)
+			for (int q = p + 1; q < 6; q++) {
+				if (a[p][q] == 0.0) continue;
+				// the rotation that zeroes a[p][q] (Golub & Van Loan, symmetric Schur decomposition)
+				const double tau = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+				const double t = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+				const double c = 1.0 / std::sqrt(1.0 + t * t), sn = t * c;
+				for (int k = 0; k < 6; k++) {
+					const double akp = a[k][p], akq = a[k][q];
+					a[k][p] = c * akp - sn * akq;
+					a[k][q] = sn * akp + c * akq;
+				}
+				for (int k = 0; k < 6; k++) {
+					const double apk = a[p][k], aqk = a[q][k];
+					a[p][k] = c * apk - sn * aqk;
+					a[q][k] = sn * apk + c * aqk;
+				}
+				a[p][q] = a[q][p] = 0.0;
+				for (int k = 0; k < 6; k++) {
+					const double vkp = v[k][p], vkq = v[k][q];
+					v[k][p] = c * vkp - sn * vkq;
+					v[k][q] = sn * vkp + c * vkq;
+				}
+			}
+	}
+	int order[6] = {0, 1, 2, 3, 4, 5};
+	std::stable_sort(order, order + 6, [&](int x, int y) { return a[x][x] < a[y][y]; });
+	double lam[6], vr[6][6];
+	for (int i = 0; i < 6; i++) {
+		lam[i] = a[order[i]][order[i]];
+		for (int k = 0; k < 6; k++) vr[i][k] = v[k][order[i]];
+	}
+	const double thr = rank_tol * lam[5];
+	int rk = 0;
+	double pi[36] = {0};
+	for (int i = 0; i < 6; i++) {
+		if (!(lam[i] > thr) || !(lam[i] > 0.0)) continue;
+		rk++;
+		for (int x = 0; x < 6; x++)
+			for (int y = 0; y < 6; y++) pi[6 * x + y] += vr[i][x] * vr[i][y] / lam[i];
+	}
+	if (eig) std::memcpy(eig, lam, sizeof(lam));
+	if (vec) std::memcpy(vec, vr, sizeof(vr));
+	if (pinv) std::memcpy(pinv, pi, sizeof(pi));
+	if (rank) *rank = rk;
+}
+
+void Engine::ensure_pose_info(size_t K)
+{
+	if (K <= info_cap_) return;
+	hipFree(d_info_acc_); hipFree(d_info_args_);
+	d_info_acc_ = nullptr; d_info_args_ = nullptr; info_cap_ = 0;
+	HIPCHK(hipMalloc(&d_info_acc_, sizeof(unsigned long long) * kIcpBatchAccWords * K));
+	HIPCHK(hipMalloc(&d_info_args_, sizeof(PoseInfoArgs) * K));
+	info_cap_ = K;
+}
+
+void Engine::pose_information(size_t K, const float* R, const float* t, const goicp_pose_info_options* opt, goicp_pose_info* out, bool batch)
+{
+	const char* fn = batch ? "goicp_pose_information_batch" : "goicp_pose_information";
+	auto refuse = [&](const char* why) { throw std::invalid_argument(std::string(fn) + ": " + why); };
+	goicp_pose_info_options o;
+	o.metric = -1; o.use_pivot = 0; o.pivot[0] = o.pivot[1] = o.pivot[2] = 0.0; o.rank_tol = kPoseInfoRankTol;
+	if (opt) o = *opt;
+	if (K == 0 || K > (size_t)kIcpBatchMax) refuse("K must be in [1, 1024]");
+	if (!R || !t || !out) refuse("R, t and out must be non-null");
+	if (o.metric < -1 || o.metric > 1) refuse("metric must be -1 (the handle's), 0 (point-to-point) or 1 (point-to-plane)");
+	if (!(o.rank_tol >= 0.0 && o.rank_tol < 1.0)) refuse("rank_tol must be in [0, 1)");
+	for (size_t i = 0; i < 9 * K; i++)
+		if (!std::isfinite(R[i])) refuse("R has a non-finite entry");
+	for (size_t i = 0; i < 3 * K; i++)
+		if (!std::isfinite(t[i])) refuse("t has a non-finite entry");
+	if (o.use_pivot)
+		for (int i = 0; i < 3; i++)
+			if (!std::isfinite(o.pivot[i]) || std::fabs(o.pivot[i]) > 3.0e38) refuse("the pivot has a non-finite entry");
+	if (p_.trim_fraction > 0.f || inliers_ < (int)N_) refuse("trim_fraction > 0 is not supported");
+	if (dt_.layout == 0 || p_.icp_fused) refuse("the information pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
+	if (registering_.load()) refuse("not while a registration runs");
+	const int metric = o.metric < 0 ? icp_metric_ : o.metric;
+	DeviceGuard guard(dev_);
+	if (metric == 1) ensure_normals(normal_k_);
+	if (src_crad_ < 0.0) {
+		// largest distance of a source point from the source centroid: with the default pivot |a| <= |R| * this
+		double m = 0.0;
+		for (size_t i = 0; i < N_; i++) {
+			const double dx = (double)h_src_sorted_[4 * i] - src_centroid_[0], dy = (double)h_src_sorted_[4 * i + 1] - src_centroid_[1],
+			             dz = (double)h_src_sorted_[4 * i + 2] - src_centroid_[2];
+			m = std::max(m, std::sqrt(dx * dx + dy * dy + dz * dz));
+		}
+		src_crad_ = m;
+	}
+	std::vector<PoseInfoArgs> args(K);
+	for (size_t k = 0; k < K; k++) {
+		PoseInfoArgs& a = args[k];
+		const float* Rk = R + 9 * k;
+		const float* tk = t + 3 * k;
+		std::memcpy(a.R, Rk, sizeof(a.R));
+		std::memcpy(a.t, tk, sizeof(a.t));
+		float c0[3];
+		double rho = 0.0, tl = 0.0, off = 0.0;
+		for (int i = 0; i < 9; i++) rho += (double)Rk[i] * Rk[i];
+		rho = std::sqrt(rho);                          // Frobenius norm: bounds |R x| / |x|
+		for (int i = 0; i < 3; i++) {
+			c0[i] = Rk[3 * i] * src_centroid_[0] + Rk[3 * i + 1] * src_centroid_[1] + Rk[3 * i + 2] * src_centroid_[2] + tk[i];   // icp_state_fill's cq
+			a.c[i] = o.use_pivot ? (float)o.pivot[i] : c0[i];
+			tl += (double)tk[i] * tk[i];
+			off += ((double)a.c[i] - c0[i]) * ((double)a.c[i] - c0[i]);
+		}
+		a.g2 = icp_gated() ? gate_dist_ * gate_dist_ : INFINITY;   // icp_state_fill's float product
+		a.rk = robust_kernel_;
+		a.rc = robust_scale_;
+		a.pad = 0;
+		// fixed-point scale: |a| <= Ba, |e| <= E, |n| <= 1, so every term is below T^2 with T = 2 (max(Ba, E) + 1), and N of them must fit 2^62
+		const double Ba = rho * src_crad_ + std::sqrt(off);
+		const double E = rho * (double)src_radius_ + std::sqrt(tl) + std::sqrt(3.0) * (double)target_abs_max_;
+		const double T = 2.0 * (std::max(Ba, E) + 1.0);
+		const double need = std::log2(4.6e18 / ((double)N_ * T * T));
+		if (!std::isfinite(need) || need < -60.0) refuse("the pivot (or the pose) is so far from the clouds that the fixed-point sums would overflow");
+		const int e = std::min(60, (int)std::floor(need));
+		a.scale = std::ldexp(1.0f, e);
+	}
+	ensure_pose_info(K);
+	const size_t words = (size_t)kIcpBatchAccWords * K;
+	HIPCHK(hipMemsetAsync(d_info_acc_, 0, sizeof(unsigned long long) * words, stream_));
+	if (batch) {
+		HIPCHK(hipMemcpyAsync(d_info_args_, args.data(), sizeof(PoseInfoArgs) * K, hipMemcpyHostToDevice, stream_));
+		HIPCHK(launch_pose_info_batch(d_src_, (int)N_, d_info_args_, (int)K, metric, kd_, dt_, d_normals_, d_info_acc_, stream_));
+	} else {
+		HIPCHK(launch_pose_info(d_src_, (int)N_, args[0], metric, kd_, dt_, d_normals_, d_info_acc_, stream_));
+	}
+	std::vector<long long> acc(words);
+	HIPCHK(hipMemcpyAsync(acc.data(), d_info_acc_, sizeof(long long) * words, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	const int nwords = kPoseInfoWords[metric];
+	for (size_t k = 0; k < K; k++) {
+		long long tot[kIcpPlaneStride] = {0};
+		for (int r = 0; r < kIcpAccReplicas; r++)
+			for (int w = 0; w < nwords; w++) tot[w] += acc[k * kIcpBatchAccWords + (size_t)r * kIcpPlaneStride + w];   // integers: exact in any order
+		const double inv = 1.0 / (double)args[k].scale;      // a power of two
+		goicp_pose_info& I = out[k];
+		std::memset(&I, 0, sizeof(I));
+		double* A = I.information;
+		if (metric == 0) {
+			const double W = (double)tot[0] / kIcpRobustWScale;
+			const double sa[3] = {tot[1] * inv, tot[2] * inv, tot[3] * inv};
+			const double xx = tot[4] * inv, xy = tot[5] * inv, xz = tot[6] * inv, yy = tot[7] * inv, yz = tot[8] * inv, zz = tot[9] * inv;
+			// A_ww = sum w (|a|^2 I - a a^T), A_wt = sum w [a]x, A_tt = W I
+			const double ww[3][3] = {{yy + zz, -xy, -xz}, {-xy, xx + zz, -yz}, {-xz, -yz, xx + yy}};
+			const double wt[3][3] = {{0.0, -sa[2], sa[1]}, {sa[2], 0.0, -sa[0]}, {-sa[1], sa[0], 0.0}};
+			for (int i = 0; i < 3; i++)
+				for (int j = 0; j < 3; j++) {
+					A[6 * i + j] = ww[i][j];
+					A[6 * i + 3 + j] = wt[i][j];
+					A[6 * (3 + j) + i] = wt[i][j];
+					A[6 * (3 + i) + 3 + j] = i == j ? W : 0.0;
+				}
+			for (int i = 0; i < 6; i++) I.gradient[i] = tot[10 + i] * inv;
+			I.weight_sum = W; I.cost = tot[16] * inv; I.sse = tot[17] * inv; I.inliers = tot[18];
+		} else {
+			int w = 0;
+			for (int i = 0; i < 6; i++)
+				for (int j = i; j < 6; j++) { A[6 * i + j] = A[6 * j + i] = tot[w] * inv; w++; }
+			for (int i = 0; i < 6; i++) I.gradient[i] = tot[21 + i] * inv;
+			I.cost = tot[27] * inv; I.sse = tot[28] * inv; I.weight_sum = (double)tot[29] / kIcpRobustWScale; I.inliers = tot[30];
+		}
+		for (int i = 0; i < 3; i++) I.pivot[i] = (double)args[k].c[i];
+		I.metric = metric;
+		double pinv[36];
+		information_decompose(A, o.rank_tol, I.eigenvalues, I.eigenvectors, pinv, &I.rank);
+		const double dof = (metric == 0 ? 3.0 : 1.0) * I.weight_sum - 6.0;
+		if (dof > 0.0) {
+			I.sigma2 = I.cost / dof;
+			for (int i = 0; i < 36; i++) I.covariance[i] = I.sigma2 * pinv[i];
+		} else {
+			I.dof_nonpositive = 1;         // sigma2 and the covariance stay zero
+		}
+	}
+}
+
+void Engine::result_information(const goicp_pose_info_options* opt, goicp_pose_info* out)
+{
+	if (registering_.load()) throw std::invalid_argument("goicp_result_information: not while a registration runs");
+	const Result r = poll();
+	if (!r.finished) throw std::invalid_argument("goicp_result_information: the handle has no finished registration");
+	pose_information(1, r.optR, r.optT, opt, out, false);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -15,6 +15,8 @@
 #include "device.hpp"
 
 struct goicp_comm_ops;   // include/goicp_mi355.h
+struct goicp_pose_info_options;
+struct goicp_pose_info;
 
 namespace goicp {
 
@@ -193,6 +195,14 @@ public:
 	// goicp_eval_correspondences: per source point (original order) the neighbour's index (-1 beyond the gate) and d^2 at R|t, the inlier count
 	// and the inliers' sum of d^2 (double sum in source order, rounded once); max_corr_dist 0 = no gate; any output may be null
 	void eval_correspondences(const float R[9], const float t[3], float max_corr_dist, int32_t* index, float* dist_sq, int32_t* inliers, float* sse);
+	// goicp_pose_information(_batch): the Gauss-Newton normal matrix and gradient of either metric at K given poses under the handle's weights
+	// (plain, gate, robust kernel), about the caller's pivot or the transformed source centroid, and the fp64 finishing step per pose
+	// (DESIGN 15).  batch: the blockIdx.y form (slot k is the single call at pose k bit for bit).  Touches no ICP or search state.
+	// Refused: trimming, dt_layout 0, icp_fused, a metric outside {-1, 0, 1}, non-finite R / t / pivot, a pivot that would overflow the
+	// fixed-point sums, rank_tol outside [0, 1), K outside 1..1024, while a registration runs
+	void pose_information(size_t K, const float* R, const float* t, const goicp_pose_info_options* opt, goicp_pose_info* out, bool batch);
+	void result_information(const goicp_pose_info_options* opt, goicp_pose_info* out);   // at optR | optT of the last finished registration
+	static constexpr double kPoseInfoRankTol = 1e-6;
 	void knn_query(const float* q_xyz, size_t n, int k, int32_t* idx, float* d2);
 	double normal_build_ms() const { return normal_build_ms_; }   // exact, ascending (d2, index), n x k
 	void target_normals(float* normals_xyz);                                         // M x 3, original target order (built on first use)
@@ -410,6 +420,11 @@ private:
 	void ensure_icp_batch(size_t K);
 	void free_icp_batch();
 	void ensure_normals(int k);
+	// pose information (allocated on first use, grown on demand): info_cap_ accumulator blocks (kIcpBatchAccWords each) and argument blocks
+	unsigned long long* d_info_acc_ = nullptr; PoseInfoArgs* d_info_args_ = nullptr;
+	size_t info_cap_ = 0;
+	double src_crad_ = -1.0;           // largest distance of a source point from the source centroid (first use)
+	void ensure_pose_info(size_t K);
 	const goicp_comm_ops* icp_comm_ = nullptr;
 	bool unrefined_ = false;           // collective registration: the best pose is an upper bound not yet refined by ICP
 	// nn query staging grows on demand
@@ -442,6 +457,8 @@ void build_kdtree(const float* xyz, int M, int leaf_max, KdHost* out);
 // fn(0..ntasks-1) on up to `threads` host threads (tasks claimed from a counter; the first exception is rethrown)
 void parallel_tasks(int threads, int ntasks, const std::function<void(int)>& fn);
 void rodrigues(float ax, float ay, float az, float R[9]);   // jly_goicp.cpp:449-467
+// goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
+void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)
 
 }  // namespace goicp

@@ -492,6 +492,39 @@ int goicp_target_normals(goicp_handle h, float* normals_xyz)
 	return guarded([&] { h->e->target_normals(normals_xyz); });
 }
 
+void goicp_pose_info_options_default(goicp_pose_info_options* out)
+{
+	if (!out) return;
+	out->metric = -1;
+	out->use_pivot = 0;
+	out->pivot[0] = out->pivot[1] = out->pivot[2] = 0.0;
+	out->rank_tol = goicp::Engine::kPoseInfoRankTol;
+}
+
+int goicp_pose_information(goicp_handle h, const float R[9], const float t[3], const goicp_pose_info_options* opt, goicp_pose_info* out)
+{
+	REQUIRE(h && R && t && out);
+	return guarded([&] { h->e->pose_information(1, R, t, opt, out, false); });
+}
+
+int goicp_pose_information_batch(goicp_handle h, size_t K, const float* R, const float* t, const goicp_pose_info_options* opt, goicp_pose_info* out)
+{
+	REQUIRE(h);                 // K and the pointers are refused by name below
+	return guarded([&] { h->e->pose_information(K, R, t, opt, out, true); });
+}
+
+int goicp_result_information(goicp_handle h, const goicp_pose_info_options* opt, goicp_pose_info* out)
+{
+	REQUIRE(h && out);
+	return guarded([&] { h->e->result_information(opt, out); });
+}
+
+int goicp_information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank)
+{
+	REQUIRE(info);
+	return guarded([&] { goicp::information_decompose(info, rank_tol, eig, vec, pinv, rank); });
+}
+
 int goicp_icp_step(goicp_handle h)
 {
 	REQUIRE(h);

@@ -29,6 +29,38 @@ def _f32(a, shape=None):
     return a
 
 
+def _pose_info_options(metric=None, pivot=None, rank_tol=None):
+    o = B.CPoseInfoOptions()
+    B.load_library().goicp_pose_info_options_default(C.byref(o))
+    if metric is not None:
+        o.metric = int(metric)
+    if pivot is not None:
+        pv = np.asarray(pivot, np.float64).reshape(3)
+        o.use_pivot = 1
+        o.pivot[:] = [float(x) for x in pv]
+    if rank_tol is not None:
+        o.rank_tol = float(rank_tol)
+    return o
+
+
+def _pose_info_dict(i):
+    """goicp_pose_info -> dict of numpy arrays and scalars (the struct's field names)"""
+    return {"information": np.array(i.information, np.float64).reshape(6, 6), "gradient": np.array(i.gradient, np.float64),
+            "covariance": np.array(i.covariance, np.float64).reshape(6, 6), "eigenvalues": np.array(i.eigenvalues, np.float64),
+            "eigenvectors": np.array(i.eigenvectors, np.float64).reshape(6, 6), "pivot": np.array(i.pivot, np.float64),
+            "weight_sum": float(i.weight_sum), "cost": float(i.cost), "sse": float(i.sse), "sigma2": float(i.sigma2),
+            "inliers": int(i.inliers), "rank": int(i.rank), "metric": int(i.metric), "dof_nonpositive": int(i.dof_nonpositive)}
+
+
+def information_decompose(A, rank_tol=1e-6):
+    """goicp_information_decompose (host only): symmetric 6x6 -> (eigenvalues ascending (6,), eigenvectors as rows (6, 6), pinv (6, 6), rank)"""
+    A = np.ascontiguousarray(A, np.float64).reshape(36)
+    eig, vec, pinv, rank = np.empty(6), np.empty(36), np.empty(36), C.c_int32()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    B.check(B.load_library().goicp_information_decompose(dp(A), float(rank_tol), dp(eig), dp(vec), dp(pinv), C.byref(rank)))
+    return eig, vec.reshape(6, 6), pinv.reshape(6, 6), rank.value
+
+
 class Config:
     """Config(toml_filepath): same keys, defaults and clamps as the reference; raises on parse error."""
 
@@ -240,6 +272,29 @@ class Registration:
                                                      _fptr(d2), C.byref(n), C.byref(sse)))
         return idx, d2, n.value, np.float32(sse.value)
 
+    # ---- pose information (goicp_pose_information) ----
+    def pose_information(self, R, t, metric=None, pivot=None, rank_tol=None):
+        """goicp_pose_information at R|t -> dict: information (6, 6), gradient, covariance, eigenvalues, eigenvectors (rows), pivot, weight_sum,
+        cost, sse, sigma2, inliers, rank, metric, dof_nonpositive.  metric None = the handle's; pivot None = the transformed source centroid."""
+        R, t = _f32(R, (9,)), _f32(t, (3,))
+        o, out = _pose_info_options(metric, pivot, rank_tol), B.CPoseInfo()
+        B.check(self._lib.goicp_pose_information(self.handle, _fptr(R), _fptr(t), C.byref(o), C.byref(out)))
+        return _pose_info_dict(out)
+
+    def pose_information_batch(self, R, t, metric=None, pivot=None, rank_tol=None):
+        """goicp_pose_information_batch: R (K, 3, 3), t (K, 3) -> list of K dicts, entry k the single call at pose k bit for bit"""
+        R, t = _f32(R, (-1, 9)), _f32(t, (-1, 3))
+        K = len(R)
+        o, out = _pose_info_options(metric, pivot, rank_tol), (B.CPoseInfo * max(K, 1))()
+        B.check(self._lib.goicp_pose_information_batch(self.handle, K, _fptr(R), _fptr(t), C.byref(o), out))
+        return [_pose_info_dict(out[k]) for k in range(K)]
+
+    def result_information(self, metric=None, pivot=None, rank_tol=None):
+        """goicp_result_information: the same at optR | optT of the last finished registration"""
+        o, out = _pose_info_options(metric, pivot, rank_tol), B.CPoseInfo()
+        B.check(self._lib.goicp_result_information(self.handle, C.byref(o), C.byref(out)))
+        return _pose_info_dict(out)
+
     # ---- ICP metric (goicp_icp_options) ----
     @staticmethod
     def icp_options_default():
@@ -432,6 +487,10 @@ class FastGoICP:
     curT = property(lambda s: np.array(s._snap().curT, np.float32))
     finished = property(lambda s: bool(s._snap().finished))
     counters = property(lambda s: s._snap().counters)
+
+    def information(self, metric=None, pivot=None, rank_tol=None):
+        """information matrix, covariance and rank at the registration's result (Registration.result_information)"""
+        return self.registration.result_information(metric, pivot, rank_tol)
 
     def write_output(self, path):
         B.check(self.registration._lib.goicp_result_write_toml(self.registration.handle, str(path).encode()))

@@ -405,6 +405,56 @@ int goicp_icp_robust_stats(goicp_handle h, size_t K, float* cost, float* weight_
 int goicp_set_search_truncation(goicp_handle h, float max_dist);
 int goicp_search_truncation(goicp_handle h, float* max_dist);
 
+/* ---- pose information (opt-in; new: how well the data determines a pose -- the information matrix of Open3D's
+ * get_information_matrix_from_point_clouds, the covariance estimators of PCL) -----------------------------------------------------
+ * At a GIVEN pose R|t the Gauss-Newton normal matrix A and gradient b of the handle's ICP objective, for either metric, and their
+ * finishing step.  q_i = R p_i + t (the pass's float expression: goicp_transform_source's bits), m_i its exact nearest target point and
+ * d_i^2 the walk's bits (goicp_eval_correspondences'), n_i the normal of m_i (metric 1; built on first use).  Weight w_i: 1 on a plain
+ * handle, [d_i^2 <= g2] under the handle's gate, the handle's robust kernel weight (same float arithmetic as the robust pass) under a
+ * kernel.  Pivot c: the caller's, by default R src_centroid + t.  With a_i = q_i - c the perturbation is q' = Exp(omega)(q - c) + c + tau,
+ * x = (omega, tau):
+ *   metric 0: e = q - m, J = [ -[a]x | I ]:  A = sum w J^T J, b = sum w J^T e = (sum w a x e, sum w e), cost = sum w d^2, dim = 3
+ *   metric 1: j = (a x n, n), r = e . n:     A = sum w j j^T, b = sum w j r,                           cost = sum w r^2, dim = 1
+ * sse = sum d^2 over ALL N points, weight_sum W = sum w, inliers = the points with w > 0.  The sums are float per workgroup, then exact
+ * 64-bit fixed point: the result does not depend on the order workgroups arrive in.  Finishing step, fp64 on the host: eigenvalues
+ * (ascending) and eigenvectors (rows) of A by cyclic Jacobi; rank = the eigenvalues > rank_tol * lambda_max; dof = dim W - 6;
+ * sigma2 = cost / dof and covariance = sigma2 * pinv A over the retained eigenvalues when dof > 0; else sigma2 = 0, covariance = 0 and
+ * dof_nonpositive = 1 (status still GOICP_OK).  This is the Gauss-Newton / Cramer-Rao covariance for FIXED correspondences with i.i.d.
+ * residuals; it ignores correspondence uncertainty (it is not Censi's estimator).
+ * Refused (GOICP_ERR_INVALID): trim_fraction > 0, dt_layout = 0 or icp_fused = 1 (the pass is fixed-point only, as the gate), a metric
+ * outside {-1, 0, 1}, a non-finite R, t or pivot, a pivot so far away that the fixed-point sums would overflow, rank_tol outside [0, 1),
+ * K outside 1..1024, any call while a registration runs.  A handle that never calls these launches what it launched before. */
+typedef struct goicp_pose_info_options {
+	int32_t metric;      /* -1 = the handle's (default), 0 point-to-point, 1 point-to-plane */
+	int32_t use_pivot;   /* 0 (default): the transformed source centroid; 1: pivot[] */
+	double pivot[3];
+	double rank_tol;     /* default 1e-6: the terms are float, 2^-24 per rounding, so an eigenvalue below ~16 roundings of the largest is
+	                        indistinguishable from zero */
+} goicp_pose_info_options;
+void goicp_pose_info_options_default(goicp_pose_info_options* out);
+typedef struct goicp_pose_info {
+	double information[36];   /* A, row-major, omega then tau */
+	double gradient[6];       /* b */
+	double covariance[36];
+	double eigenvalues[6];    /* ascending */
+	double eigenvectors[36];  /* row i belongs to eigenvalues[i] */
+	double pivot[3];          /* the pivot used (as the float the pass subtracted) */
+	double weight_sum, cost, sse, sigma2;
+	int64_t inliers;
+	int32_t rank, metric, dof_nonpositive;
+} goicp_pose_info;
+/* opt = NULL: the defaults */
+int goicp_pose_information(goicp_handle h, const float R[9], const float t[3], const goicp_pose_info_options* opt, goicp_pose_info* out);
+/* K poses (R: K x 9, t: K x 3) in one launch, out[K]; slot k is the single call at pose k bit for bit */
+int goicp_pose_information_batch(goicp_handle h, size_t K, const float* R, const float* t, const goicp_pose_info_options* opt,
+                                 goicp_pose_info* out);
+/* the same at optR | optT of the handle's last finished registration; GOICP_ERR_INVALID when there is none */
+int goicp_result_information(goicp_handle h, const goicp_pose_info_options* opt, goicp_pose_info* out);
+/* the finishing step on its own (host only, no handle, no GPU): info is symmetrised as (A + A^T) / 2; eig ascending, vec rows, pinv over
+ * the eigenvalues > rank_tol * lambda_max (an eigenvalue exactly AT the threshold is dropped).  Any output may be NULL.
+ * GOICP_ERR_INVALID: a non-finite entry, rank_tol outside [0, 1) */
+int goicp_information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
+
 /* ICP::kdTreeGPUStep / ICP::naiveGPUStep (src/icp_kernel.h:9-13, icp_kernel.cu:176-279): ONE ICP
  * iteration from the engine's current step pose (identity after create); the accumulated pose is
  * visible through goicp_poll().curR/curT. */

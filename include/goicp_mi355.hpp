@@ -224,6 +224,14 @@ public:
 	}
 	// the objective of the SEARCH (goicp_set_search_truncation): bounds, pose scores and best_sse become sum min(DT(R p + t), max_dist)^2; 0 switches it off
 	void set_search_truncation(float max_dist) { check(goicp_set_search_truncation(h_, max_dist)); }
+	// goicp_pose_information at R | t: information matrix, gradient, covariance, eigen-decomposition and rank (the struct is the C ABI's plain
+	// goicp_pose_info); opt = nullptr: the handle's metric, the transformed source centroid as pivot, the default rank_tol
+	goicp_pose_info pose_information(const float R[9], const float t[3], const goicp_pose_info_options* opt = nullptr)
+	{
+		goicp_pose_info out;
+		check(goicp_pose_information(h_, R, t, opt, &out));
+		return out;
+	}
 	float search_truncation() const
 	{
 		float g = 0.f;
@@ -340,6 +348,13 @@ public:
 		check(goicp_poll(registration.handle(), &r));
 		std::lock_guard<std::mutex> lk(mtx);
 		take(r);
+	}
+	// goicp_result_information: the same at optR | optT of the last finished registration
+	goicp_pose_info information(const goicp_pose_info_options* opt = nullptr)
+	{
+		goicp_pose_info out;
+		check(goicp_result_information(registration.handle(), opt, &out));
+		return out;
 	}
 	void write_output(const std::string& path) { check(goicp_result_write_toml(registration.handle(), path.c_str())); }
 	void write_visualization(const std::string& path) { check(goicp_result_write_ply(registration.handle(), path.c_str())); }
