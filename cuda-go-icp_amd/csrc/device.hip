@@ -1802,7 +1802,7 @@ __device__ __forceinline__ RobustTerms robust_terms(int rk, float c, float r, fl
 // SLICE (ACC form only, goicp_icp_run_collective): the launch covers workgroups [b0, b0 + gridDim.x) of the world-1 grid -- the
 // global workgroup index blockIdx.x + b0 picks the queries and the replica, so every workgroup forms the same float row sums from the
 // same 16 queries as in a full pass, and the integer totals of the slices of all ranks add up to the world-1 totals bit for bit.
-// The body is shared with icp_pass_batch_kernel (goicp_icp_run_batch), which runs the ACC form on one pose slot per blockIdx.y.  Its pointers carry no
+// The body is shared with icp_opt_pass_kernel (the opt-in iterations), which in a batch runs the ACC form on one pose slot per blockIdx.y.  Its pointers carry no
 // __restrict__ of their own: they come from the kernels' restrict parameters, which keeps icp_pass_kernel's code what it was before the split.
 // GATE (goicp_set_icp_gate; ACC form only): the owning lane zeroes its terms when d^2 > IcpState::g2 and contributes 1 to a count otherwise; the
 // accumulator block then has the plane pass's stride (kIcpPlaneStride words per replica), the count a plain integer in word 16.  `capped`: the walk
@@ -1984,57 +1984,6 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_kern
                                                                   float4* __restrict__ nn_cache, int* __restrict__ hit_counter, int b0)
 {
 	icp_pass_body<K, LAYOUT, FUSED, CACHE, LEAVES, STRIDED, ACC, SLICE>(src, N, st, kd, dt, partials, ticket, nn_cache, hit_counter, b0);
-}
-
-// The batched pass (goicp_icp_run_batch): grid (icp_blocks(N), active poses); blockIdx.y picks a pose slot from the device list
-// `active`, slot s owns states[s] and the accumulator block acc + s * kIcpBatchAccWords (16 x 32 words used).  Every workgroup runs the body of the
-// default single-pose pass (fixed point, four leaves per step, no neighbour cache: every query walks) on that slot: the same 16 queries,
-// the same float row sums, the same acc_scale, the same replica -- and integer addition is associative, so the slot's totals are the
-// single-pose totals bit for bit, whatever else the grid holds.
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_batch_kernel(const float4* __restrict__ src, int N,
-                                                                        IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                        unsigned long long* __restrict__ acc, const int* __restrict__ active)
-{
-	const int s = active[blockIdx.y];
-	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false>(src, N, states + s, kd, dt,
-	                                                          reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0);
-}
-
-// The gated pass (goicp_set_icp_gate), single pose and batch: the default fixed-point pass in its GATE form, on the 32-word replica stride.
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_gate_kernel(const float4* __restrict__ src, int N,
-                                                                       IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                       unsigned long long* __restrict__ acc, int capped)
-{
-	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, true>(src, N, st, kd, dt, reinterpret_cast<float*>(acc), nullptr, nullptr, nullptr, 0, capped);
-}
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_gate_batch_kernel(const float4* __restrict__ src, int N,
-                                                                             IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                             unsigned long long* __restrict__ acc, const int* __restrict__ active, int capped)
-{
-	const int s = active[blockIdx.y];
-	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, true>(src, N, states + s, kd, dt,
-	                                                                reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0, capped);
-}
-
-// The robust pass (goicp_set_icp_robust), single pose and batch: the default fixed-point pass in its ROBUST form, on the 32-word replica stride.
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_robust_kernel(const float4* __restrict__ src, int N,
-                                                                         IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                         unsigned long long* __restrict__ acc)
-{
-	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, false, true>(src, N, st, kd, dt, reinterpret_cast<float*>(acc), nullptr, nullptr, nullptr, 0);
-}
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_pass_robust_batch_kernel(const float4* __restrict__ src, int N,
-                                                                               IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                               unsigned long long* __restrict__ acc, const int* __restrict__ active)
-{
-	const int s = active[blockIdx.y];
-	icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, false, true>(src, N, states + s, kd, dt,
-	                                                                       reinterpret_cast<float*>(acc + (size_t)s * kIcpBatchAccWords), nullptr, nullptr, nullptr, 0);
 }
 
 // ---- trimmed ICP (trim_fraction > 0; jly_icp3d.hpp:236-252): NN for every point, exact selection of
@@ -2578,13 +2527,6 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_finalize_update_acc(unsign
 {
 	finalize_acc_body(acc, state);
 }
-// goicp_icp_run_batch: one wavefront per active pose (blockIdx.x indexes the list), the unchanged finalize on that pose's slot
-__global__ __launch_bounds__(kFinAccThreads) void icp_finalize_batch_acc(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
-                                                                         const int* __restrict__ active)
-{
-	const int s = active[blockIdx.x];
-	finalize_acc_body(acc + (size_t)s * kIcpBatchAccWords, states + s);
-}
 
 // ---- the sharded ICP loop (goicp_icp_run_collective): slice pass -> export -> sum over the ranks on the host -> finalize from the sums ----
 // the 32 x 16 replicas of the fixed-point pass -> lane t & 15 holds the integer total of accumulator t & 15 (every lane of its column);
@@ -2738,6 +2680,18 @@ hipError_t launch_probe_gather(const DtDesc& dt, int mode, unsigned window, int 
 	return hipGetLastError();
 }
 
+// A run-time value as a template argument: f(std::integral_constant<int, V>) for the first listed V equal to v, for the last one otherwise.
+//   with_k(kd.K, [&](auto K) { launch_x<K()>(...); });
+template <int V0, int... Vs, class F>
+static void with_value(int v, F&& f)
+{
+	if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+	else if (v == V0) f(std::integral_constant<int, V0>{});
+	else with_value<Vs...>(v, f);
+}
+template <class F> static void with_k(int K, F&& f) { with_value<1, 2, 3>(K, f); }        // KdDesc::K, the box levels: 1, 2, else 3
+template <class F> static void with_flag(bool b, F&& f) { with_value<1, 0>(b, f); }
+
 size_t icp_partials_floats(int N)     // the pass's rows + the rows of the intermediate level (large clouds)
 {
 	const size_t nb = (size_t)icp_blocks(N);
@@ -2805,9 +2759,7 @@ hipError_t launch_icp_select(const float* nn_d2, int N, int num, const IcpState*
 hipError_t launch_icp_iteration_trim(const float4* src, int N, int num, IcpState* st, const KdDesc& kd, const DtDesc& dt,
                                      float* nn_d2, int* nn_slot, unsigned char* include, float* partials, hipStream_t stream)
 {
-	if (kd.K == 1) launch_nn_store_k<1>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
-	else if (kd.K == 2) launch_nn_store_k<2>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
-	else launch_nn_store_k<3>(src, N, st, kd, dt, nn_d2, nn_slot, stream);
+	with_k(kd.K, [&](auto K) { launch_nn_store_k<K()>(src, N, st, kd, dt, nn_d2, nn_slot, stream); });
 	launch_icp_select(nn_d2, N, num, st, include, 0, stream);
 	const int nb = icp_trim_blocks(N);
 	hipLaunchKernelGGL(icp_accum_kernel, dim3(nb), dim3(kIcpThreads), 0, stream, src, N, st, kd, nn_d2, nn_slot, include, partials);
@@ -2820,9 +2772,7 @@ hipError_t launch_icp_pass_slice(const float4* src, int N, int b0, int b1, IcpSt
 {
 	if (!dt.layout || !acc || b0 < 0 || b1 > icp_blocks(N) || b0 > b1) return hipErrorInvalidValue;
 	if (b1 == b0) return hipSuccess;              // an empty range adds nothing: its totals are zero
-	if (kd.K == 1) launch_pass_acc<1, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
-	else if (kd.K == 2) launch_pass_acc<2, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
-	else launch_pass_acc<3, true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0);
+	with_k(kd.K, [&](auto K) { launch_pass_acc<K(), true>(src, N, st, kd, dt, acc, nn_cache, hits, stream, b0, b1 - b0); });
 	return hipGetLastError();
 }
 
@@ -2855,21 +2805,15 @@ hipError_t launch_icp_iteration(const float4* src, int N, IcpState* st, const Kd
 {
 	if (!ticket && acc && dt.layout) {
 		// the default form: fixed-point sums, no rows of partial sums
-		if (kd.K == 1) launch_pass_acc<1>(src, N, st, kd, dt, acc, nn_cache, hits, stream);
-		else if (kd.K == 2) launch_pass_acc<2>(src, N, st, kd, dt, acc, nn_cache, hits, stream);
-		else launch_pass_acc<3>(src, N, st, kd, dt, acc, nn_cache, hits, stream);
+		with_k(kd.K, [&](auto K) { launch_pass_acc<K()>(src, N, st, kd, dt, acc, nn_cache, hits, stream); });
 		hipLaunchKernelGGL(icp_finalize_update_acc, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
 		return hipGetLastError();
 	}
 	if (ticket) {
-		if (kd.K == 1) launch_pass_k<1, true>(src, N, st, kd, dt, partials, ticket, nn_cache, hits, stream);
-		else if (kd.K == 2) launch_pass_k<2, true>(src, N, st, kd, dt, partials, ticket, nn_cache, hits, stream);
-		else launch_pass_k<3, true>(src, N, st, kd, dt, partials, ticket, nn_cache, hits, stream);
+		with_k(kd.K, [&](auto K) { launch_pass_k<K(), true>(src, N, st, kd, dt, partials, ticket, nn_cache, hits, stream); });
 		return hipGetLastError();
 	}
-	if (kd.K == 1) launch_pass_k<1, false>(src, N, st, kd, dt, partials, nullptr, nn_cache, hits, stream);
-	else if (kd.K == 2) launch_pass_k<2, false>(src, N, st, kd, dt, partials, nullptr, nn_cache, hits, stream);
-	else launch_pass_k<3, false>(src, N, st, kd, dt, partials, nullptr, nn_cache, hits, stream);
+	with_k(kd.K, [&](auto K) { launch_pass_k<K(), false>(src, N, st, kd, dt, partials, nullptr, nn_cache, hits, stream); });
 	const int nb = icp_blocks(N);
 	if (nb > 4 * kPreRows) {
 		// two-level sum: the reduced rows live behind the pass's own rows in the same buffer (icp_partials_floats sizes it)
@@ -2966,9 +2910,7 @@ static void launch_nn_k(const float* q, int n, const KdDesc& kd, const DtDesc& d
 hipError_t launch_nn_query(const float* q, int n, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2, hipStream_t stream)
 {
 	if (n <= 0) return hipSuccess;
-	if (kd.K == 1) launch_nn_k<1>(q, n, kd, dt, idx, d2, stream);
-	else if (kd.K == 2) launch_nn_k<2>(q, n, kd, dt, idx, d2, stream);
-	else launch_nn_k<3>(q, n, kd, dt, idx, d2, stream);
+	with_k(kd.K, [&](auto K) { launch_nn_k<K()>(q, n, kd, dt, idx, d2, stream); });
 	return hipGetLastError();
 }
 
@@ -3125,9 +3067,7 @@ hipError_t launch_knn_query(const float* q, int n, int k, const KdDesc& kd, cons
 {
 	if (k < 1 || k > kKnnMax || k > kd.M) return hipErrorInvalidValue;
 	if (n <= 0) return hipSuccess;
-	if (kd.K == 1) launch_knn_k<1>(q, n, k, kd, dt, idx, d2, stream);
-	else if (kd.K == 2) launch_knn_k<2>(q, n, k, kd, dt, idx, d2, stream);
-	else launch_knn_k<3>(q, n, k, kd, dt, idx, d2, stream);
+	with_k(kd.K, [&](auto K) { launch_knn_k<K()>(q, n, k, kd, dt, idx, d2, stream); });
 	return hipGetLastError();
 }
 
@@ -3242,9 +3182,7 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
                                hipStream_t stream)
 {
 	if (k < 1 || k > kKnnMax || k > kd.M || nslots <= 0) return hipErrorInvalidValue;
-	if (kd.K == 1) launch_normals_k<1>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
-	else if (kd.K == 2) launch_normals_k<2>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
-	else launch_normals_k<3>(target_xyz, nslots, k, centroid, kd, dt, normals, stream);
+	with_k(kd.K, [&](auto K) { launch_normals_k<K()>(target_xyz, nslots, k, centroid, kd, dt, normals, stream); });
 	return hipGetLastError();
 }
 
@@ -3337,60 +3275,30 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 	}
 }
 
-template <int K, int LAYOUT, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_kernel(const float4* __restrict__ src, int N,
-                                                                       const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+// The pass of every opt-in iteration (launch_icp_iteration_opt): METRIC 0 is the default fixed-point pass (four leaves per step, no neighbour cache:
+// every query walks) in its plain, GATE or ROBUST form, METRIC 1 the plane pass; LAYOUT is the DT's (METRIC 1, plain mode; 1 everywhere else).
+// BATCH (goicp_icp_run_batch): grid (icp_blocks(N), active poses); blockIdx.y picks a pose slot from the device list `active`, slot s owns states[s]
+// and the accumulator block acc + s * kIcpBatchAccWords.  Every workgroup runs the single-pose body on that slot: the same 16 queries, the same float
+// row sums, the same acc_scale, the same replica -- and integer addition is associative, so the slot's totals are the single-pose totals bit for bit,
+// whatever else the grid holds.  `normals` is read by METRIC 1 only, `active` by BATCH only, `capped` by the gated mode only.
+template <int K, int LAYOUT, bool STRIDED, int METRIC, int MODE, bool BATCH>
+__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_kernel(const float4* __restrict__ src, int N,
+                                                                      IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
+                                                                      const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
+                                                                      const int* __restrict__ active, int capped)
 {
-	icp_plane_pass_body<K, LAYOUT, STRIDED>(src, N, st, kd, dt, normals, acc);
-}
-
-// goicp_icp_run_batch, point-to-plane: icp_pass_batch_kernel's slot scheme (blockIdx.y -> active[] -> states[s], accumulator block
-// acc + s * kIcpBatchAccWords) around the unchanged plane pass body
-template <int K, int LAYOUT, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_batch_kernel(const float4* __restrict__ src, int N,
-                                                                             const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                             const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
-                                                                             const int* __restrict__ active)
-{
-	const int s = active[blockIdx.y];
-	icp_plane_pass_body<K, LAYOUT, STRIDED>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
-}
-
-// the gated plane pass (goicp_set_icp_gate), single pose and batch (bricked DT only)
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_gate_kernel(const float4* __restrict__ src, int N,
-                                                                             const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                             const float4* __restrict__ normals, unsigned long long* __restrict__ acc, int capped)
-{
-	icp_plane_pass_body<K, 1, STRIDED, true>(src, N, st, kd, dt, normals, acc, capped);
-}
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_gate_batch_kernel(const float4* __restrict__ src, int N,
-                                                                                   const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                                   const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
-                                                                                   const int* __restrict__ active, int capped)
-{
-	const int s = active[blockIdx.y];
-	icp_plane_pass_body<K, 1, STRIDED, true>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords, capped);
-}
-
-// the robust plane pass (goicp_set_icp_robust), single pose and batch (bricked DT only)
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_robust_kernel(const float4* __restrict__ src, int N,
-                                                                               const IcpState* __restrict__ st, KdDesc kd, DtDesc dt,
-                                                                               const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
-{
-	icp_plane_pass_body<K, 1, STRIDED, false, true>(src, N, st, kd, dt, normals, acc);
-}
-template <int K, bool STRIDED>
-__global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_plane_pass_robust_batch_kernel(const float4* __restrict__ src, int N,
-                                                                                     const IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
-                                                                                     const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
-                                                                                     const int* __restrict__ active)
-{
-	const int s = active[blockIdx.y];
-	icp_plane_pass_body<K, 1, STRIDED, false, true>(src, N, states + s, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
+	constexpr bool GATE = MODE == kIcpModeGate, ROBUST = MODE == kIcpModeRobust;
+	IcpState* st = states;
+	unsigned long long* a = acc;
+	if constexpr (BATCH) {
+		const int s = active[blockIdx.y];
+		st = states + s;
+		a = acc + (size_t)s * kIcpBatchAccWords;
+	}
+	if constexpr (METRIC == 0)
+		icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, GATE, ROBUST>(src, N, st, kd, dt, reinterpret_cast<float*>(a), nullptr, nullptr, nullptr, 0, capped);
+	else
+		icp_plane_pass_body<K, LAYOUT, STRIDED, GATE, ROBUST>(src, N, st, kd, dt, normals, a, capped);
 }
 
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
@@ -3547,206 +3455,51 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 	if constexpr (GATE) { state->n_in = gs.n_in; state->cost = gs.cost; }
 	if constexpr (ROBUST) { state->w_sum = (float)rs.W; state->cost_new = rs.cost; state->cost = rs.cost; }
 }
-__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
+// The finalize of every opt-in iteration: one wavefront; BATCH: one per active pose (blockIdx.x indexes the list), on that pose's slot.  Plain
+// point-to-point is the default finalize's body, everything else icp_plane_finalize_body<GATE, PLANE, ROBUST>.
+template <int METRIC, int MODE, bool BATCH>
+__global__ __launch_bounds__(kFinAccThreads) void icp_opt_finalize_kernel(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
+                                                                        const int* __restrict__ active)
 {
-	icp_plane_finalize_body(acc, state);
-}
-// the gated finalizes (goicp_set_icp_gate): PLANE = false point-to-point, true point-to-plane; single pose, and one wavefront per active pose
-template <bool PLANE>
-__global__ __launch_bounds__(kFinAccThreads) void icp_gate_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
-{
-	icp_plane_finalize_body<true, PLANE>(acc, state);
-}
-template <bool PLANE>
-__global__ __launch_bounds__(kFinAccThreads) void icp_gate_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
-                                                                          const int* __restrict__ active)
-{
-	const int s = active[blockIdx.x];
-	icp_plane_finalize_body<true, PLANE>(acc + (size_t)s * kIcpBatchAccWords, states + s);
-}
-// the robust finalizes (goicp_set_icp_robust): PLANE = false point-to-point, true point-to-plane; single pose, and one wavefront per active pose
-template <bool PLANE>
-__global__ __launch_bounds__(kFinAccThreads) void icp_robust_finalize(unsigned long long* __restrict__ acc, IcpState* __restrict__ state)
-{
-	icp_plane_finalize_body<false, PLANE, true>(acc, state);
-}
-template <bool PLANE>
-__global__ __launch_bounds__(kFinAccThreads) void icp_robust_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
-                                                                            const int* __restrict__ active)
-{
-	const int s = active[blockIdx.x];
-	icp_plane_finalize_body<false, PLANE, true>(acc + (size_t)s * kIcpBatchAccWords, states + s);
-}
-// goicp_icp_run_batch: one wavefront per active pose, the unchanged plane finalize on that pose's slot
-__global__ __launch_bounds__(kFinAccThreads) void icp_plane_finalize_batch(unsigned long long* __restrict__ acc, IcpState* __restrict__ states,
-                                                                           const int* __restrict__ active)
-{
-	const int s = active[blockIdx.x];
-	icp_plane_finalize_body(acc + (size_t)s * kIcpBatchAccWords, states + s);
-}
-
-template <int K>
-static void launch_plane_k(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc,
-                           hipStream_t stream)
-{
-	const dim3 grid(icp_blocks(N)), block(kIcpThreads);
-	const bool strided = N <= kIcpStridedMaxN;       // the point-to-point pass's choice: strangers per wavefront for small clouds
-	if (dt.layout) {
-		if (strided) hipLaunchKernelGGL((icp_plane_pass_kernel<K, 1, true>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
-		else hipLaunchKernelGGL((icp_plane_pass_kernel<K, 1, false>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
-	} else {
-		if (strided) hipLaunchKernelGGL((icp_plane_pass_kernel<K, 0, true>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
-		else hipLaunchKernelGGL((icp_plane_pass_kernel<K, 0, false>), grid, block, 0, stream, src, N, st, kd, dt, normals, acc);
+	IcpState* st = states;
+	unsigned long long* a = acc;
+	if constexpr (BATCH) {
+		const int s = active[blockIdx.x];
+		st = states + s;
+		a = acc + (size_t)s * kIcpBatchAccWords;
 	}
+	if constexpr (METRIC == 0 && MODE == kIcpModePlain) finalize_acc_body(a, st);
+	else icp_plane_finalize_body<MODE == kIcpModeGate, METRIC == 1, MODE == kIcpModeRobust>(a, st);
 }
 
-hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                                      unsigned long long* acc, hipStream_t stream)
+// ---- the opt-in iterations (point-to-plane, gate, robust kernel; single pose and goicp_icp_run_batch): one pass, then the finalize ----
+hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream)
 {
-	if (!normals || !acc) return hipErrorInvalidValue;
-	if (kd.K == 1) launch_plane_k<1>(src, N, st, kd, dt, normals, acc, stream);
-	else if (kd.K == 2) launch_plane_k<2>(src, N, st, kd, dt, normals, acc, stream);
-	else launch_plane_k<3>(src, N, st, kd, dt, normals, acc, stream);
-	hipLaunchKernelGGL(icp_plane_finalize, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
-	return hipGetLastError();
-}
-
-// ---- batched multi-start ICP (goicp_icp_run_batch): one pass over every active pose, then one finalize wavefront per active pose ----
-template <int K>
-static void launch_batch_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                           int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
-{
-	const dim3 grid(icp_blocks(N), n_active), block(kIcpThreads);
-	const bool strided = N <= kIcpStridedMaxN;       // the single-pose passes' choice
-	if (metric == 0) {
-		if (strided) hipLaunchKernelGGL((icp_pass_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
-		else hipLaunchKernelGGL((icp_pass_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
-	} else if (dt.layout) {
-		if (strided) hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 1, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-		else hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 1, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-	} else {
-		if (strided) hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 0, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-		else hipLaunchKernelGGL((icp_plane_pass_batch_kernel<K, 0, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-	}
-}
-
-hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                      int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
-{
-	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || (metric != 0 && metric != 1) || (metric == 0 && !dt.layout) ||
-	    (metric == 1 && !normals))
+	const bool batch = a.active != nullptr;
+	if (!a.states || !a.acc || (a.metric != 0 && a.metric != 1) || (a.metric == 1 && !a.normals) || a.mode < kIcpModePlain || a.mode > kIcpModeRobust)
 		return hipErrorInvalidValue;
-	if (kd.K == 1) launch_batch_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	else if (kd.K == 2) launch_batch_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	else launch_batch_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	if (metric == 0) hipLaunchKernelGGL(icp_finalize_batch_acc, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
-	else hipLaunchKernelGGL(icp_plane_finalize_batch, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
-	return hipGetLastError();
-}
-
-// ---- distance-gated ICP (goicp_set_icp_gate): the gated pass + the gated finalize of the metric, single pose and batch ----
-template <int K>
-static void launch_gate_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt, int metric,
-                          const float4* normals, unsigned long long* acc, int capped, hipStream_t stream)
-{
-	const dim3 block(kIcpThreads);
-	const bool strided = N <= kIcpStridedMaxN;       // the ungated passes' choice
-	if (!active) {
-		const dim3 grid(icp_blocks(N));
-		if (metric == 0) {
-			if (strided) hipLaunchKernelGGL((icp_pass_gate_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, capped);
-			else hipLaunchKernelGGL((icp_pass_gate_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, capped);
-		} else {
-			if (strided) hipLaunchKernelGGL((icp_plane_pass_gate_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, capped);
-			else hipLaunchKernelGGL((icp_plane_pass_gate_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, capped);
-		}
-	} else {
-		const dim3 grid(icp_blocks(N), n_active);
-		if (metric == 0) {
-			if (strided) hipLaunchKernelGGL((icp_pass_gate_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active, capped);
-			else hipLaunchKernelGGL((icp_pass_gate_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active, capped);
-		} else {
-			if (strided) hipLaunchKernelGGL((icp_plane_pass_gate_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active, capped);
-			else hipLaunchKernelGGL((icp_plane_pass_gate_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active, capped);
-		}
-	}
-}
-
-hipError_t launch_icp_iteration_gate(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
-                                     unsigned long long* acc, int capped, hipStream_t stream)
-{
-	if (!st || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals)) return hipErrorInvalidValue;
-	if (kd.K == 1) launch_gate_k<1>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
-	else if (kd.K == 2) launch_gate_k<2>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
-	else launch_gate_k<3>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, capped, stream);
-	if (metric == 0) hipLaunchKernelGGL(icp_gate_finalize<false>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
-	else hipLaunchKernelGGL(icp_gate_finalize<true>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
-	return hipGetLastError();
-}
-
-hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                           int metric, const float4* normals, unsigned long long* acc, int capped, hipStream_t stream)
-{
-	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals))
-		return hipErrorInvalidValue;
-	if (kd.K == 1) launch_gate_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
-	else if (kd.K == 2) launch_gate_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
-	else launch_gate_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, capped, stream);
-	if (metric == 0) hipLaunchKernelGGL(icp_gate_finalize_batch<false>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
-	else hipLaunchKernelGGL(icp_gate_finalize_batch<true>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
-	return hipGetLastError();
-}
-
-// ---- robust-kernel ICP (goicp_set_icp_robust): the robust pass + the robust finalize of the metric, single pose and batch ----
-template <int K>
-static void launch_robust_k(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt, int metric,
-                            const float4* normals, unsigned long long* acc, hipStream_t stream)
-{
-	const dim3 block(kIcpThreads);
-	const bool strided = N <= kIcpStridedMaxN;       // the plain passes' choice
-	if (!active) {
-		const dim3 grid(icp_blocks(N));
-		if (metric == 0) {
-			if (strided) hipLaunchKernelGGL((icp_pass_robust_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc);
-			else hipLaunchKernelGGL((icp_pass_robust_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc);
-		} else {
-			if (strided) hipLaunchKernelGGL((icp_plane_pass_robust_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc);
-			else hipLaunchKernelGGL((icp_plane_pass_robust_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc);
-		}
-	} else {
-		const dim3 grid(icp_blocks(N), n_active);
-		if (metric == 0) {
-			if (strided) hipLaunchKernelGGL((icp_pass_robust_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
-			else hipLaunchKernelGGL((icp_pass_robust_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, acc, active);
-		} else {
-			if (strided) hipLaunchKernelGGL((icp_plane_pass_robust_batch_kernel<K, true>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-			else hipLaunchKernelGGL((icp_plane_pass_robust_batch_kernel<K, false>), grid, block, 0, stream, src, N, states, kd, dt, normals, acc, active);
-		}
-	}
-}
-
-hipError_t launch_icp_iteration_robust(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
-                                       unsigned long long* acc, hipStream_t stream)
-{
-	if (!st || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals)) return hipErrorInvalidValue;
-	if (kd.K == 1) launch_robust_k<1>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
-	else if (kd.K == 2) launch_robust_k<2>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
-	else launch_robust_k<3>(src, N, st, nullptr, 1, kd, dt, metric, normals, acc, stream);
-	if (metric == 0) hipLaunchKernelGGL(icp_robust_finalize<false>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
-	else hipLaunchKernelGGL(icp_robust_finalize<true>, dim3(1), dim3(kFinAccThreads), 0, stream, acc, st);
-	return hipGetLastError();
-}
-
-hipError_t launch_icp_iteration_batch_robust(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                             int metric, const float4* normals, unsigned long long* acc, hipStream_t stream)
-{
-	if (!states || !active || !acc || n_active < 1 || n_active > kIcpBatchMax || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals))
-		return hipErrorInvalidValue;
-	if (kd.K == 1) launch_robust_k<1>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	else if (kd.K == 2) launch_robust_k<2>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	else launch_robust_k<3>(src, N, states, active, n_active, kd, dt, metric, normals, acc, stream);
-	if (metric == 0) hipLaunchKernelGGL(icp_robust_finalize_batch<false>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
-	else hipLaunchKernelGGL(icp_robust_finalize_batch<true>, dim3(n_active), dim3(kFinAccThreads), 0, stream, acc, states, active);
+	if (!dt.layout && (a.metric == 0 || a.mode != kIcpModePlain)) return hipErrorInvalidValue;   // the linear DT: the plain plane pass only
+	if (a.n_active < 1 || a.n_active > kIcpBatchMax || (!batch && a.n_active != 1)) return hipErrorInvalidValue;
+	if (!batch && a.metric == 0 && a.mode == kIcpModePlain) return hipErrorInvalidValue;         // launch_icp_iteration's
+	const dim3 pass_grid(icp_blocks(a.N), a.n_active), fin_grid(a.n_active);
+	with_k(kd.K, [&](auto K) {
+		with_flag(a.N <= kIcpStridedMaxN, [&](auto S) {       // the default pass's choice: strangers per wavefront for small clouds
+			auto go = [&](auto L, auto M, auto MODE, auto B) {
+				hipLaunchKernelGGL((icp_opt_pass_kernel<K(), L(), S(), M(), MODE(), B()>), pass_grid, dim3(kIcpThreads), 0, stream, a.src, a.N, a.states, kd, dt,
+				                   a.normals, a.acc, a.active, a.capped);
+				hipLaunchKernelGGL((icp_opt_finalize_kernel<M(), MODE(), B()>), fin_grid, dim3(kFinAccThreads), 0, stream, a.acc, a.states, a.active);
+			};
+			constexpr std::integral_constant<int, 0> c0{};
+			constexpr std::integral_constant<int, 1> c1{};
+			// the instantiations: the linear DT with the plain plane pass only; plain point-to-point in a batch only
+			if (a.mode != kIcpModePlain)
+				with_flag(a.metric, [&](auto M) { with_value<kIcpModeGate, kIcpModeRobust>(a.mode, [&](auto MODE) { with_flag(batch, [&](auto B) { go(c1, M, MODE, B); }); }); });
+			else if (a.metric == 1)
+				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c1, c0, B); }); });
+			else
+				go(c1, c0, c0, c1);
+		});
+	});
 	return hipGetLastError();
 }
 
@@ -3781,9 +3534,7 @@ hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pos
 {
 	if (N <= 0) return hipSuccess;
 	if (!idx || !d2) return hipErrorInvalidValue;
-	if (kd.K == 1) launch_eval_corr_k<1>(src, N, pose, g2, kd, dt, idx, d2, stream);
-	else if (kd.K == 2) launch_eval_corr_k<2>(src, N, pose, g2, kd, dt, idx, d2, stream);
-	else launch_eval_corr_k<3>(src, N, pose, g2, kd, dt, idx, d2, stream);
+	with_k(kd.K, [&](auto K) { launch_eval_corr_k<K()>(src, N, pose, g2, kd, dt, idx, d2, stream); });
 	return hipGetLastError();
 }
 
@@ -3923,9 +3674,7 @@ static hipError_t launch_pose_info_any(const float4* src, int N, const PoseInfoA
 {
 	if (N <= 0 || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals) || n_poses < 1 || n_poses > kIcpBatchMax)
 		return hipErrorInvalidValue;
-	if (kd.K == 1) launch_pose_info_k<1>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
-	else if (kd.K == 2) launch_pose_info_k<2>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
-	else launch_pose_info_k<3>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+	with_k(kd.K, [&](auto K) { launch_pose_info_k<K()>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream); });
 	return hipGetLastError();
 }
 

@@ -312,52 +312,56 @@ hipError_t launch_knn_query(const float* q_xyz, int n, int k, const KdDesc& kd, 
 // target_xyz: the M target points in original order on the device
 hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const float centroid[3], const KdDesc& kd, const DtDesc& dt, float4* normals,
                                hipStream_t stream);
-// one point-to-plane iteration (pass + one-wavefront finalize) on the device-resident state; acc: kIcpAccReplicas x kIcpPlaneStride
-// zeroed 64-bit words (kept zero between iterations by the finalize); the state's acc_scale / acc_inv scale the sums
-hipError_t launch_icp_iteration_plane(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                                      unsigned long long* acc, hipStream_t stream);
 
 // ---- distance-gated ICP (opt-in, goicp_set_icp_gate) ------------------------------------------------------------------------------
-// One gated iteration of either metric (0 point-to-point, 1 point-to-plane; bricked DT only): the metric's pass in its GATE form -- the
-// owning lane of a query contributes its terms and 1 to a count iff d^2 <= IcpState::g2 -- and the metric's one-wavefront finalize with
-// the count in place of n and the truncated-cost stop rule.  Fixed-point sums at every N.  acc: kIcpAccReplicas x kIcpPlaneStride zeroed
-// 64-bit words for BOTH metrics (kept zero by the finalize); the count is a plain integer in word kIcpGateCountWord[metric] of a replica.
-// capped: the walk's pruning bound starts at min(seed distance, g2) -- exact for every inlier, no neighbour for an outlier.
+// A gated iteration of either metric (0 point-to-point, 1 point-to-plane; bricked DT only; launch_icp_iteration_opt, kIcpModeGate): the
+// metric's pass in its GATE form -- the owning lane of a query contributes its terms and 1 to a count iff d^2 <= IcpState::g2 -- and the
+// metric's one-wavefront finalize with the count in place of n and the truncated-cost stop rule.  Fixed-point sums at every N.
 constexpr int kIcpGateCountWord[2] = {16, 28};
-hipError_t launch_icp_iteration_gate(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
-                                     unsigned long long* acc, int capped, hipStream_t stream);
-// goicp_icp_run_batch under a gate: launch_icp_iteration_batch's slot scheme around the gated pass and finalize
-hipError_t launch_icp_iteration_batch_gate(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                           int metric, const float4* normals, unsigned long long* acc, int capped, hipStream_t stream);
 // goicp_eval_correspondences: the pass's transform (jly_icp3d.hpp:222-224 order) and walk for every source point, one launch;
 // idx[i] = original index of the neighbour of source slot i (-1 when d2[i] > g2), d2[i] = the walk's distance bits
 hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pose, float g2, const KdDesc& kd, const DtDesc& dt, int32_t* idx, float* d2,
                                        hipStream_t stream);
 
 // ---- robust-kernel ICP (opt-in, goicp_set_icp_robust) -----------------------------------------------------------------------------
-// One IRLS iteration of either metric (bricked DT only): the metric's pass in its ROBUST form -- the owning lane of a query forms the
-// weight w of IcpState::rk / rc from its residual in float (robust_terms) and multiplies every term of the update by it; d^2 stays
-// unweighted -- and the metric's one-wavefront finalize with W = sum w in place of n and the stop rule on C = sum rho.  Fixed-point sums at
-// every N.  acc: kIcpAccReplicas x kIcpPlaneStride zeroed 64-bit words for BOTH metrics (kept zero by the finalize); W (scaled by
-// kIcpRobustWScale) is word kIcpGateCountWord[metric] of a replica, C (scaled by the pass's acc_scale) the word after it.
+// An IRLS iteration of either metric (bricked DT only; launch_icp_iteration_opt, kIcpModeRobust): the metric's pass in its ROBUST form -- the
+// owning lane of a query forms the weight w of IcpState::rk / rc from its residual in float (robust_terms) and multiplies every term of the
+// update by it; d^2 stays unweighted -- and the metric's one-wavefront finalize with W = sum w in place of n and the stop rule on C = sum rho.
+// Fixed-point sums at every N.
 // kIcpRobustWScale: w <= 1, so a workgroup's float row sum is <= 16 and the total over N <= 2^23 points <= 2^23; times 2^36 that is
 // 2^59 < 2^63.  A sum of weights that are all 1.0f is an integer and stays exact: W == N.
 constexpr double kIcpRobustWScale = 68719476736.0;   // 2^36
-hipError_t launch_icp_iteration_robust(const float4* src, int N, IcpState* d_state, const KdDesc& kd, const DtDesc& dt, int metric, const float4* normals,
-                                       unsigned long long* acc, hipStream_t stream);
-// goicp_icp_run_batch under a kernel: launch_icp_iteration_batch's slot scheme around the robust pass and finalize
-hipError_t launch_icp_iteration_batch_robust(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                             int metric, const float4* normals, unsigned long long* acc, hipStream_t stream);
 
-// ---- batched multi-start ICP (goicp_icp_run_batch) --------------------------------------------------------------------------------
-// One iteration of up to kIcpBatchMax independent loops over the same clouds: states[s] is pose slot s's loop state, acc + s * kIcpBatchAccWords
-// its accumulator block (zeroed 64-bit words, kept zero between iterations by the finalize), active[0 .. n_active) the slots this iteration
-// visits (device memory).  metric 0: the default fixed-point pass (bricked DT only), metric 1: the point-to-plane pass (normals required).
-// Pose s's state evolves bit for bit as under launch_icp_iteration(..., acc) / launch_icp_iteration_plane on its own.
+// ---- the opt-in ICP iterations: point-to-plane, gate, robust kernel; single pose and batched multi-start (goicp_icp_run_batch) ----
+// One iteration (the pass + the one-wavefront finalize) of every cell of (metric, mode, single pose | batch) but the default one -- plain
+// point-to-point on a single pose is launch_icp_iteration's.  The linear DT (dt.layout 0) has the plain point-to-plane iteration only.
+// Single pose (active == nullptr, n_active == 1): `states` is the device-resident loop state, `acc` kIcpAccReplicas x kIcpPlaneStride zeroed 64-bit
+// words (kept zero between iterations by the finalize); the state's acc_scale / acc_inv scale the sums.
+// Batch: up to kIcpBatchMax independent loops over the same clouds: states[s] is pose slot s's loop state, acc + s * kIcpBatchAccWords its
+// accumulator block (as the single pose's), active[0 .. n_active) the slots this iteration visits (device memory).  Pose s's state evolves bit
+// for bit as under the single-pose iteration (launch_icp_iteration(..., acc) for plain point-to-point) on its own.
+// The accumulator block, every cell: the replica stride is kIcpPlaneStride words for BOTH metrics but in plain point-to-point (a batch only),
+// whose replicas are the default pass's 16 words.  Words 0 .. 15 (metric 0) / 0 .. 27 (metric 1) of a replica are the pass's terms.
+//   kIcpModeGate    the inlier count, a plain integer, in word kIcpGateCountWord[metric] = 16 / 28
+//   kIcpModeRobust  W (scaled by kIcpRobustWScale) in word kIcpGateCountWord[metric] = 16 / 28, C (scaled by the pass's acc_scale) in the word
+//                   after it, 17 / 29
+// Anything else -- a null states or acc, a metric other than 0 / 1, metric 1 without normals, metric 0 or a mode on the linear DT, n_active outside
+// [1, kIcpBatchMax] or != 1 without a list, the default cell -- is hipErrorInvalidValue without a launch.
+enum IcpMode : int { kIcpModePlain = 0, kIcpModeGate = 1, kIcpModeRobust = 2 };
 constexpr int kIcpBatchMax = 1024;
 constexpr int kIcpBatchAccWords = kIcpAccReplicas * kIcpPlaneStride;   // accumulator words per slot (either metric)
-hipError_t launch_icp_iteration_batch(const float4* src, int N, IcpState* states, const int* active, int n_active, const KdDesc& kd, const DtDesc& dt,
-                                      int metric, const float4* normals, unsigned long long* acc, hipStream_t stream);
+struct IcpOptArgs {
+	const float4* src; int N;
+	IcpState* states;             // the loop state; batch: kIcpBatchMax slots at most
+	const int* active;            // nullptr: single pose
+	int n_active;                 // 1 for a single pose
+	int metric;                   // 0 point-to-point, 1 point-to-plane
+	int mode;                     // IcpMode
+	const float4* normals;        // metric 1: one per target point (launch_normal_build)
+	unsigned long long* acc;
+	int capped;                   // kIcpModeGate: the walk's pruning bound starts at min(seed distance, g2) -- exact for every inlier, no neighbour for an outlier
+};
+hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream);
 
 // ---- pose information (goicp_pose_information) -------------------------------------------------------------------------
 // One pass at a pose handed in by value: the sums of the Gauss-Newton normal matrix and gradient about the pivot c, of either metric, under the

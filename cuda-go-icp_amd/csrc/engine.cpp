@@ -552,9 +552,9 @@ void Engine::release()
 	hipFree(d_cubes_); hipFree(d_rots_); hipFree(d_ub_); hipFree(d_lb_); hipFree(d_scratch_);
 	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
 	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
-	hipFree(d_icp_acc_gate_); d_icp_acc_gate_ = nullptr;
+	hipFree(d_icp_acc_opt_); d_icp_acc_opt_ = nullptr;
 	hipFree(d_info_acc_); d_info_acc_ = nullptr; hipFree(d_info_args_); d_info_args_ = nullptr; info_cap_ = 0;
-	hipFree(d_icp_acc_plane_); d_icp_acc_plane_ = nullptr; hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
+	hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
 	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
 	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
 	hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
@@ -795,6 +795,16 @@ void Engine::knn_query(const float* q, size_t n, int k, int32_t* idx, float* d2)
 	HIPCHK(hipStreamSynchronize(stream_));
 }
 
+// the accumulator block of the single-pose opt-in iterations (launch_icp_iteration_opt): one for every metric and mode -- each finalize leaves
+// it zeroed, and only one of them runs at a time on the engine's stream
+void Engine::ensure_icp_acc_opt()
+{
+	if (d_icp_acc_opt_) return;
+	DeviceGuard guard(dev_);
+	HIPCHK(hipMalloc(&d_icp_acc_opt_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
+	HIPCHK(hipMemsetAsync(d_icp_acc_opt_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
+}
+
 void Engine::ensure_normals(int k)
 {
 	if (normals_k_ == k && d_normals_) return;
@@ -802,10 +812,7 @@ void Engine::ensure_normals(int k)
 	DeviceGuard guard(dev_);
 	const double t0 = now_ms();
 	if (!d_normals_) HIPCHK(hipMalloc(&d_normals_, sizeof(float4) * M_));
-	if (!d_icp_acc_plane_) {
-		HIPCHK(hipMalloc(&d_icp_acc_plane_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
-		HIPCHK(hipMemsetAsync(d_icp_acc_plane_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
-	}
+	ensure_icp_acc_opt();
 	HIPCHK(hipMemsetAsync(d_normals_, 0, sizeof(float4) * M_, stream_));
 	DevBuf<float> tgt(3 * M_);
 	HIPCHK(hipMemcpyAsync(tgt.p, h_target_.data(), sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
@@ -852,11 +859,7 @@ void Engine::set_icp_gate(float max_corr_dist, int min_inliers, int capped_walk)
 		if (p_.trim_fraction > 0.f || inliers_ < (int)N_) throw std::invalid_argument("goicp_set_icp_gate: a gate together with trim_fraction > 0 is not supported");
 		if (dt_.layout == 0 || p_.icp_fused)
 			throw std::invalid_argument("goicp_set_icp_gate: the gated pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
-		if (!d_icp_acc_gate_) {
-			DeviceGuard guard(dev_);
-			HIPCHK(hipMalloc(&d_icp_acc_gate_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
-			HIPCHK(hipMemsetAsync(d_icp_acc_gate_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
-		}
+		ensure_icp_acc_opt();
 	}
 	gate_dist_ = max_corr_dist;
 	gate_min_inliers_ = min_inliers;
@@ -873,11 +876,7 @@ void Engine::set_icp_robust(int kernel, float scale)
 		if (icp_gated()) throw std::invalid_argument("goicp_set_icp_robust: a robust kernel together with a gate is not supported (goicp_set_icp_gate max_corr_dist 0 first)");
 		if (dt_.layout == 0 || p_.icp_fused)
 			throw std::invalid_argument("goicp_set_icp_robust: the robust pass is fixed-point only (needs dt_layout = 1 and icp_fused = 0)");
-		if (!d_icp_acc_gate_) {          // the gated pass's block: same size, and a gate and a kernel exclude each other
-			DeviceGuard guard(dev_);
-			HIPCHK(hipMalloc(&d_icp_acc_gate_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
-			HIPCHK(hipMemsetAsync(d_icp_acc_gate_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
-		}
+		ensure_icp_acc_opt();
 	}
 	robust_kernel_ = kernel;
 	robust_scale_ = kernel ? scale : 0.f;
@@ -1224,17 +1223,29 @@ void Engine::icp_state_fill(IcpState& st, const float R[9], const float t[3], fl
 
 void Engine::icp_launch_one()
 {
-	if (icp_robust())           // either metric (set_icp_robust refuses it together with a gate, trimming, the linear DT and the fused iteration)
-		HIPCHK(launch_icp_iteration_robust(d_src_, (int)N_, d_icp_state_, kd_, dt_, icp_metric_, d_normals_, d_icp_acc_gate_, stream_));
-	else if (icp_gated())       // either metric (set_icp_gate refuses it together with trimming, the linear DT and the fused iteration)
-		HIPCHK(launch_icp_iteration_gate(d_src_, (int)N_, d_icp_state_, kd_, dt_, icp_metric_, d_normals_, d_icp_acc_gate_, gate_capped_, stream_));
-	else if (icp_metric_ == 1)       // point-to-plane (set_icp_options refuses it together with trimming)
-		HIPCHK(launch_icp_iteration_plane(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_normals_, d_icp_acc_plane_, stream_));
+	// a kernel or a gate, either metric (set_icp_robust / set_icp_gate refuse each other, trimming, the linear DT and the fused iteration), or
+	// point-to-plane (set_icp_options refuses it together with trimming)
+	if (icp_mode() != kIcpModePlain || icp_metric_ == 1)
+		HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_icp_state_, nullptr, 1, icp_metric_, icp_mode(), d_normals_, d_icp_acc_opt_, gate_capped_}, kd_, dt_, stream_));
 	else if (inliers_ < (int)N_)
 		HIPCHK(launch_icp_iteration_trim(d_src_, (int)N_, inliers_, d_icp_state_, kd_, dt_, d_nn_d2_, d_nn_slot_, d_include_, d_icp_partials_, stream_));
 	else
 		HIPCHK(launch_icp_iteration(d_src_, (int)N_, d_icp_state_, kd_, dt_, d_icp_partials_, p_.icp_fused ? d_icp_ticket_ : nullptr,
 		                            (p_.icp_nn_cache == 1 || icp_cache_active_) ? d_nn_cache_ : nullptr, count_hits_ ? d_icp_ticket_ + 8 : nullptr, stream_, d_icp_acc_));
+}
+
+// what icp_inliers and icp_robust_stats report, from the final states of a run's K poses
+void Engine::icp_last_stats(const IcpState* fin, size_t K)
+{
+	last_inliers_.resize(K);
+	last_robust_cost_.resize(K);
+	last_robust_w_.resize(K);
+	for (size_t k = 0; k < K; k++) {
+		last_inliers_[k] = icp_gated() ? fin[k].n_in : (int32_t)inliers_;
+		// without a kernel every weight is 1: C is the pass's err, W is N
+		last_robust_cost_[k] = icp_robust() ? fin[k].cost_new : fin[k].err_new;
+		last_robust_w_[k] = icp_robust() ? fin[k].w_sum : (float)inliers_;
+	}
 }
 
 void Engine::icp_state_fetch()
@@ -1288,10 +1299,7 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 	if (iters_out) *iters_out = st.iters;
 	cnt_.icp_iters += st.passes;
 	cnt_.icp_runs++;
-	last_inliers_.assign(1, icp_gated() ? st.n_in : (int32_t)inliers_);
-	// without a kernel every weight is 1: C is the pass's err, W is N
-	last_robust_cost_.assign(1, icp_robust() ? st.cost_new : st.err_new);
-	last_robust_w_.assign(1, icp_robust() ? st.w_sum : (float)inliers_);
+	icp_last_stats(&st, 1);
 	return st.err_new;
 }
 
@@ -1351,12 +1359,7 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
 		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
 		for (int i = 0; i < k; i++)
-			if (icp_robust())
-				HIPCHK(launch_icp_iteration_batch_robust(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
-			else if (icp_gated())
-				HIPCHK(launch_icp_iteration_batch_gate(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, gate_capped_, stream_));
-			else
-				HIPCHK(launch_icp_iteration_batch(d_src_, (int)N_, d_batch_states_, d_act, n_active, kd_, dt_, icp_metric_, d_normals_, d_batch_acc_, stream_));
+			HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_batch_states_, d_act, n_active, icp_metric_, icp_mode(), d_normals_, d_batch_acc_, gate_capped_}, kd_, dt_, stream_));
 		queued += k;
 		HIPCHK(hipMemcpyAsync(slots[slot], d_batch_states_, sizeof(IcpState) * K, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipEventRecord(evs[slot], stream_));
@@ -1381,14 +1384,9 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 	// read back are final once it has drained, and the pinned lists are free again for the next call
 	HIPCHK(hipStreamSynchronize(stream_));
 	long long passes = 0;
-	last_inliers_.resize(K);
-	last_robust_cost_.resize(K);
-	last_robust_w_.resize(K);
+	icp_last_stats(fin, K);
 	for (size_t k = 0; k < K; k++) {
 		const IcpState& st = fin[k];
-		last_inliers_[k] = icp_gated() ? st.n_in : (int32_t)inliers_;
-		last_robust_cost_[k] = icp_robust() ? st.cost_new : st.err_new;
-		last_robust_w_[k] = icp_robust() ? st.w_sum : (float)inliers_;
 		std::memcpy(R + 9 * k, st.R, sizeof(st.R));
 		std::memcpy(t + 3 * k, st.t, sizeof(st.t));
 		if (err) err[k] = st.err_new;

@@ -394,20 +394,24 @@ private:
 	int* d_icp_ticket_ = nullptr;      // arrival ticket of the fused ICP iteration (zero between launches)
 	float* d_nn_d2_ = nullptr; int* d_nn_slot_ = nullptr; unsigned char* d_include_ = nullptr;   // trimmed ICP only
 	void icp_launch_one();
+	int icp_mode() const { return icp_robust() ? kIcpModeRobust : icp_gated() ? kIcpModeGate : kIcpModePlain; }   // launch_icp_iteration_opt's
+	void icp_last_stats(const IcpState* fin, size_t K);
 	// the collective ICP loop: the exported totals + converged flag + loop state read back per iteration, the summed totals uploaded
 	long long* d_icp_x_ = nullptr; long long* h_icp_x_ = nullptr;
 	IcpShardStats icp_shard_;
-	// point-to-plane ICP (opt-in): the metric, the normals (one float4 per target point, original order: the pass gathers by the neighbour's index) and its fixed-point accumulators
+	// point-to-plane ICP (opt-in): the metric, the normals (one float4 per target point, original order: the pass gathers by the neighbour's index)
 	int icp_metric_ = 0, normal_k_ = 16, normals_k_ = 0;   // normals_k_: the normal_k the normals were built with (0: none yet)
 	float4* d_normals_ = nullptr;
 	double normal_build_ms_ = 0;
-	unsigned long long* d_icp_acc_plane_ = nullptr;        // kIcpAccReplicas x kIcpPlaneStride, zero between iterations
-	// distance-gated ICP (opt-in): the gate, and the accumulators of its single-pose pass (kIcpAccReplicas x kIcpPlaneStride for either metric)
+	// the fixed-point accumulators of every single-pose opt-in iteration (point-to-plane, gate, kernel; one runs at a time):
+	// kIcpAccReplicas x kIcpPlaneStride, zero between iterations
+	unsigned long long* d_icp_acc_opt_ = nullptr;
+	void ensure_icp_acc_opt();
+	// distance-gated ICP (opt-in): the gate
 	float gate_dist_ = 0.f; int gate_min_inliers_ = 0, gate_capped_ = 1;
-	unsigned long long* d_icp_acc_gate_ = nullptr;
 	std::vector<int32_t> last_inliers_;                    // icp_inliers: the last run's counts
 	int gate_floor() const { return icp_metric_ == 1 ? 6 : 3; }
-	// robust-kernel ICP (opt-in): kernel and scale; its single-pose pass adds into d_icp_acc_gate_ (a gate and a kernel exclude each other)
+	// robust-kernel ICP (opt-in): kernel and scale (a gate and a kernel exclude each other)
 	int32_t robust_kernel_ = 0; float robust_scale_ = 0.f;
 	std::vector<float> last_robust_cost_, last_robust_w_;  // icp_robust_stats: the last run's C and W
 	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
