@@ -180,6 +180,9 @@ SYMBOLS = {
     "goicp_result_information": (C.c_int, [_vp, C.POINTER(CPoseInfoOptions), C.POINTER(CPoseInfo)]),
     "goicp_information_decompose": (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "goicp_set_search_truncation": (C.c_int, [_vp, C.c_float]),
+    "goicp_set_source": (C.c_int, [_vp, _fp, C.c_size_t]),
+    "goicp_source_order_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
+    "goicp_debug_source_order": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

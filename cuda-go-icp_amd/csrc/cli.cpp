@@ -1,7 +1,7 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
-//                                [--trunc-dist D] [--information [--information-rank-tol X]]
+//                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -26,6 +26,12 @@
 //               weights, pivot = the transformed source centroid): one line with rank and sigma, and output.toml gets an [information] table
 //               (rank, sigma2, inliers, weight_sum, eigenvalues, information and covariance as arrays of rows).  --information-rank-tol X sets
 //               rank_tol (in [0, 1)).  Refused together with --ranks N > 1 -- before any device is touched
+//   --source-list FILE   a stream of scans against one model: FILE names one cloud per line (blank lines and lines starting with # are
+//               skipped; relative paths are tried as given, then beside FILE).  After the config's own source, each listed cloud is loaded
+//               with the config's subsample, resize and the seed, swapped into the SAME engine (goicp_set_source: the target's distance
+//               transform, k-d hierarchy and every option set above are kept) and registered; one line per cloud with the swap's
+//               milliseconds, and io.output / io.visualization are written with .1, .2, ... before the extension.  Refused together with
+//               --ranks N > 1 and when FILE cannot be read or names no cloud -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -33,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <chrono>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -51,9 +58,18 @@ static std::string resolve(const std::string& p, const std::string& toml)
 	return s == std::string::npos ? p : toml.substr(0, s + 1) + p;
 }
 
+// path.ext -> path.k.ext (no extension: path.k)
+static std::string numbered(const std::string& p, int k)
+{
+	const size_t slash = p.find_last_of("/\\"), dot = p.find_last_of('.');
+	const std::string tag = "." + std::to_string(k);
+	if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return p + tag;
+	return p.substr(0, dot) + tag + p.substr(dot);
+}
+
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
@@ -67,6 +83,8 @@ int main(int argc, char** argv)
 	int information = 0;
 	const char* rank_tol_arg = nullptr;
 	double rank_tol = -1.0;
+	const char* list_arg = nullptr;
+	std::vector<std::string> source_list;
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -82,6 +100,33 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--trunc-dist")) trunc_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--information")) information = 1;
 		else if (!std::strcmp(argv[i], "--information-rank-tol")) rank_tol_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--source-list")) list_arg = i + 1 < argc ? argv[++i] : "";
+	}
+	if (list_arg) {
+		// refused before any device is touched
+		if (ranks > 1) {
+			std::fprintf(stderr, "error: --source-list cannot be combined with --ranks N > 1 (the multi-GPU registration creates its own engines)\n");
+			return 2;
+		}
+		FILE* f = *list_arg ? std::fopen(list_arg, "r") : nullptr;
+		if (!f) {
+			std::fprintf(stderr, "error: --source-list needs a readable file with one cloud path per line, got '%s'\n", list_arg);
+			return 2;
+		}
+		char line[4096];
+		while (std::fgets(line, sizeof(line), f)) {
+			std::string s(line);
+			while (!s.empty() && (s.back() == '\n' || s.back() == '\r' || s.back() == ' ' || s.back() == '\t')) s.pop_back();
+			size_t b = 0;
+			while (b < s.size() && (s[b] == ' ' || s[b] == '\t')) b++;
+			s = s.substr(b);
+			if (!s.empty() && s[0] != '#') source_list.push_back(resolve(s, list_arg));
+		}
+		std::fclose(f);
+		if (source_list.empty()) {
+			std::fprintf(stderr, "error: --source-list: '%s' names no cloud\n", list_arg);
+			return 2;
+		}
 	}
 	if (rk_arg || rc_arg) {
 		// a bad robust kernel is refused before any device is touched
@@ -260,6 +305,24 @@ int main(int argc, char** argv)
 			}
 		}
 		if (!config.io.visualization.empty()) engine.write_visualization(config.io.visualization);
+		for (size_t k = 0; k < source_list.size(); k++) {
+			// the next scan on the same engine: only the source stage of creation is redone
+			std::vector<P3> next;
+			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
+			const auto t0 = std::chrono::steady_clock::now();
+			engine.set_source(next);
+			const double swap_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+			if (config.mode <= 2) {
+				for (int i = 0; i < iters; i++) check(goicp_icp_step(h));
+			} else {
+				engine.run();
+			}
+			check(goicp_poll(h, &r));
+			std::printf("source %zu (%s): %zu points, swap %.3f ms, register %.1f ms, Best Error: %.7g, rotation nodes %lld\n", k + 1, source_list[k].c_str(), next.size(),
+			            swap_ms, r.register_ms, r.best_sse, (long long)r.counters.rot_pops);
+			if (!config.io.output.empty()) engine.write_output(numbered(config.io.output, (int)k + 1));
+			if (!config.io.visualization.empty()) engine.write_visualization(numbered(config.io.visualization, (int)k + 1));
+		}
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "error: %s\n", e.what());
 		return 1;

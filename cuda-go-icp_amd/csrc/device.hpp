@@ -396,6 +396,26 @@ hipError_t launch_probe_gather(const DtDesc& dt, int mode, unsigned window, int 
 // ---- device-side build of the box hierarchy (kdbuild.hip): Morton sort + bottom-up boxes ----------
 hipError_t launch_kd_build(const float* d_xyz, int M, int K, const float mn[3], float ext, float* const boxes[kMaxLevels],
                            float4* pts, hipStream_t stream);
+// ---- source order on the device (kdbuild.hip): the permutation Params::morton_sort defines (goicp_source_order_host is its host twin) ----
+// size of the left part when the k-d order splits a run of n points: half, rounded to a multiple of 256 / 64 / 16 / 4 points (the largest
+// unit smaller than the run); n <= 1: n (nothing to split).  A function of n alone -- the host recursion and the device levels share it
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int source_order_left(int n)
+{
+	if (n <= 1) return n;
+	const int unit = n > 256 ? 256 : (n > 64 ? 64 : (n > 16 ? 16 : (n > 4 ? 4 : 1)));
+	int nl = ((n / 2 + unit / 2) / unit) * unit;
+	if (nl == 0) nl = unit;
+	if (nl >= n) nl = n - (n % unit ? n % unit : unit);
+	return nl;
+}
+// d_xyz: the n points on the device; mode 0 input order, 1 Morton curve (mn / ext: the cloud's per-axis minimum and largest extent as the
+// host forms them), 2 k-d order; d_perm[sorted position] = original index.  Returns after the stream has drained
+hipError_t launch_source_order(const float* d_xyz, int n, int mode, const float mn[3], float ext, int32_t* d_perm, hipStream_t stream);
+// d_src[i] = (x, y, z, |p|) of point d_perm[i]
+hipError_t launch_source_gather(const float* d_xyz, const int32_t* d_perm, int n, float4* d_src, hipStream_t stream);
 
 // ---- distance transform build (DT3D::Build, jly_3ddt.cpp:889-979; exact EDT) -------------------
 // work: V^3 int32 (linear).  out: V^3 floats in dt.layout (may alias work only for layout 0).

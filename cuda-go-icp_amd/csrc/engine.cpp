@@ -43,16 +43,6 @@ double now_ms()
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-uint32_t part1by2(uint32_t x)
-{
-	x &= 0x3ff;
-	x = (x ^ (x << 16)) & 0xff0000ff;
-	x = (x ^ (x << 8)) & 0x0300f00f;
-	x = (x ^ (x << 4)) & 0x030c30c3;
-	x = (x ^ (x << 2)) & 0x09249249;
-	return x;
-}
-
 // device allocation that frees itself on every exit path (temporaries of init / operators)
 template <class T> struct DevBuf {
 	T* p = nullptr;
@@ -163,9 +153,6 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 
 	h_target_.assign(target, target + 3 * M);
 	if (!(p_.trim_fraction >= 0.f) || p_.trim_fraction >= 1.f) throw std::invalid_argument("goicp: trim_fraction must be in [0,1)");
-	inliers_ = (int)((float)N_ * (1 - p_.trim_fraction));    // jly_goicp.cpp:201
-	if (inliers_ < 1) inliers_ = 1;
-	sse_thresh_ = p_.mse_threshold * (float)inliers_;         // jly_goicp.cpp:208
 	icp_err_diff_ = p_.mse_threshold / 10000;        // jly_goicp.cpp:186
 
 	// ---- search domain: the CPU path's roots (jly_goicp.cpp:44-53) unless the configured ranges narrow it ----
@@ -217,98 +204,7 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 
 	lap("validation + device setup");
 	// ---- source cloud: (x,y,z,|p|), ordered for gather locality (morton_sort: 0 input order, 1 Morton curve, 2 k-d order) ----
-	{
-		std::vector<int32_t> perm(N_);
-		for (size_t i = 0; i < N_; i++) perm[i] = (int32_t)i;
-		if (p_.morton_sort == 1) {
-			float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-			for (size_t i = 0; i < N_; i++)
-				for (int k = 0; k < 3; k++) {
-					mn[k] = std::min(mn[k], source[3 * i + k]);
-					mx[k] = std::max(mx[k], source[3 * i + k]);
-				}
-			float ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-30f});
-			std::vector<uint32_t> code(N_);
-			for (size_t i = 0; i < N_; i++) {
-				uint32_t c = 0;
-				for (int k = 0; k < 3; k++) {
-					float f = (source[3 * i + k] - mn[k]) / ext;
-					uint32_t q = (uint32_t)std::min(1023.f, std::max(0.f, f * 1024.f));
-					c |= part1by2(q) << k;
-				}
-				code[i] = c;
-			}
-			std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return code[a] < code[b]; });
-		} else if (p_.morton_sort >= 2) {
-			// k-d order: split the longest axis of the subset's bounding box at the median, rounded so that
-			// the left part holds a multiple of 256 / 64 / 16 / 4 points (the largest that is smaller than the
-			// subset), down to single points.  Every aligned run of 64 points (one wavefront's gathers) is
-			// then a compact box-shaped surface patch, every aligned 4 and 16 lanes a sub-patch of it, and
-			// every aligned 256 (one workgroup iteration) a subtree: fewer distinct DT cache lines per gather
-			// instruction than a space-filling curve gives.  65 536-cube launch on the bunny: Morton 2.28 ms,
-			// Hilbert 2.13 ms, 64-point clusters 1.94 ms (principal-axis splits 2.01 ms), clusters ordered
-			// down to 4 points 1.85 ms, down to single points 1.84 ms.
-			// one split; returns the size of the left part (0 = nothing to split)
-			auto split = [&](size_t lo, size_t hi) -> size_t {
-				const size_t n = hi - lo;
-				if (n <= 1) return 0;
-				float bmn[3] = {INFINITY, INFINITY, INFINITY}, bmx[3] = {-INFINITY, -INFINITY, -INFINITY};
-				for (size_t i = lo; i < hi; i++)
-					for (int k = 0; k < 3; k++) {
-						bmn[k] = std::min(bmn[k], source[3 * perm[i] + k]);
-						bmx[k] = std::max(bmx[k], source[3 * perm[i] + k]);
-					}
-				int ax = 0;
-				for (int k = 1; k < 3; k++) if (bmx[k] - bmn[k] > bmx[ax] - bmn[ax]) ax = k;
-				const size_t unit = n > 256 ? 256 : (n > 64 ? 64 : (n > 16 ? 16 : (n > 4 ? 4 : 1)));
-				size_t nl = ((n / 2 + unit / 2) / unit) * unit;
-				if (nl == 0) nl = unit;
-				if (nl >= n) nl = n - (n % unit ? n % unit : unit);
-				std::nth_element(perm.begin() + lo, perm.begin() + lo + nl, perm.begin() + hi, [&](int32_t a, int32_t b) {
-					const float fa = source[3 * a + ax], fb = source[3 * b + ax];
-					return fa < fb || (fa == fb && a < b);                    // total order: the permutation is reproducible
-				});
-				return nl;
-			};
-			auto order_range = [&](size_t lo0, size_t hi0) {
-				std::vector<std::pair<size_t, size_t>> stack{{lo0, hi0}};
-				while (!stack.empty()) {
-					auto [lo, hi] = stack.back(); stack.pop_back();
-					const size_t nl = split(lo, hi);
-					if (!nl) continue;
-					stack.push_back({lo + nl, hi});
-					stack.push_back({lo, lo + nl});
-				}
-			};
-			// the top of the tree level by level (its 1, 2, 4, 8 splits side by side), the (<= 16) ranges below in parallel
-			std::vector<std::pair<size_t, size_t>> ranges{{0, N_}};
-			while (N_ >= (1u << 13) && ranges.size() < 16) {
-				std::vector<size_t> nls(ranges.size());
-				parallel_tasks(16, (int)ranges.size(), [&](int t) { nls[t] = split(ranges[t].first, ranges[t].second); });
-				std::vector<std::pair<size_t, size_t>> next;
-				for (size_t t = 0; t < ranges.size(); t++) {
-					const auto [lo, hi] = ranges[t];
-					if (nls[t]) { next.push_back({lo, lo + nls[t]}); next.push_back({lo + nls[t], hi}); } else next.push_back({lo, hi});
-				}
-				if (next.size() == ranges.size()) break;
-				ranges.swap(next);
-			}
-			parallel_tasks(16, (int)ranges.size(), [&](int t) { order_range(ranges[t].first, ranges[t].second); });
-		}
-		src_perm_ = perm;
-		h_src_sorted_.resize(4 * N_);
-		double cs[3] = {0, 0, 0};
-		for (size_t i = 0; i < N_; i++) {
-			const float* s = source + 3 * (size_t)perm[i];
-			float x = s[0], y = s[1], z = s[2];
-			h_src_sorted_[4 * i] = x; h_src_sorted_[4 * i + 1] = y; h_src_sorted_[4 * i + 2] = z;
-			h_src_sorted_[4 * i + 3] = std::sqrt(x * x + y * y + z * z);   // normData, jly_goicp.cpp:145
-			cs[0] += x; cs[1] += y; cs[2] += z;
-		}
-		for (int k = 0; k < 3; k++) src_centroid_[k] = (float)(cs[k] / (double)N_);
-		HIPCHK(hipMalloc(&d_src_, sizeof(float4) * N_));
-		HIPCHK(hipMemcpy(d_src_, h_src_sorted_.data(), sizeof(float4) * N_, hipMemcpyHostToDevice));
-	}
+	load_source(source, N, false);
 
 	lap("source order + upload");
 	// ---- distance transform geometry (jly_3ddt.cpp:891-923), double ----
@@ -436,21 +332,10 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		dt_.nn_ids = d_nn_ids_;
 		lap("nearest-point table");
 	}
-	HIPCHK(hipMalloc(&d_icp_partials_, sizeof(float) * std::max(icp_partials_floats((int)N_), (size_t)icp_trim_blocks((int)N_) * kIcpAcc)));
-	if (inliers_ < (int)N_) {
-		HIPCHK(hipMalloc(&d_nn_d2_, sizeof(float) * N_));
-		HIPCHK(hipMalloc(&d_nn_slot_, sizeof(int) * N_));
-		HIPCHK(hipMalloc(&d_include_, N_));
-	}
 	HIPCHK(hipMalloc(&d_icp_state_, sizeof(IcpState)));
 	HIPCHK(hipMalloc(&d_icp_acc_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpAcc));
 	HIPCHK(hipMemsetAsync(d_icp_acc_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpAcc, stream_));
-	for (size_t i = 0; i < N_; i++) src_radius_ = std::max(src_radius_, h_src_sorted_[4 * i + 3]);
 	for (size_t i = 0; i < 3 * M_; i++) target_abs_max_ = std::max(target_abs_max_, std::fabs(target[i]));
-	if (p_.icp_nn_cache) {
-		HIPCHK(hipMalloc(&d_nn_cache_, sizeof(float4) * 2 * N_));
-		HIPCHK(hipMemsetAsync(d_nn_cache_, 0, sizeof(float4) * 2 * N_, stream_));      // sqrt(best2_ref) = 0: the first pass walks
-	}
 	HIPCHK(hipMalloc(&d_icp_ticket_, 64));
 	HIPCHK(hipMemset(d_icp_ticket_, 0, 64));
 	HIPCHK(hipHostMalloc(&h_icp_state_, sizeof(IcpState) * 3));      // [0] the state as uploaded / as last fetched, [1], [2] icp_run's two fetch slots
@@ -535,6 +420,153 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 	lap("staging buffers");
 }
 
+void Engine::check_source(const float* source, size_t N)
+{
+	if (!source || N == 0) throw std::invalid_argument("goicp: empty source cloud");
+	if (N > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp: cloud too large");
+	for (size_t i = 0; i < 3 * N; i++) if (!std::isfinite(source[i])) throw std::invalid_argument("goicp: non-finite coordinate in the source cloud");
+}
+
+void Engine::load_source(const float* source, size_t N, bool device_order)
+{
+	N_ = N;
+	inliers_ = (int)((float)N_ * (1 - p_.trim_fraction));    // jly_goicp.cpp:201
+	if (inliers_ < 1) inliers_ = 1;
+	sse_thresh_ = p_.mse_threshold * (float)inliers_;         // jly_goicp.cpp:208
+	if (N_ > cap_src_) {
+		hipFree(d_src_);
+		d_src_ = nullptr; cap_src_ = 0;
+		HIPCHK(hipMalloc(&d_src_, sizeof(float4) * N_));
+		cap_src_ = N_;
+	}
+	std::vector<int32_t> perm(N_);
+	const bool on_device = device_order && p_.morton_sort >= 1;
+	if (on_device) {
+		// the order on the device (launch_source_order), the gather with |p| straight into d_src_; the permutation comes back for the
+		// host mirror, whose sums below keep init's order of additions
+		const int mode = p_.morton_sort == 1 ? 1 : 2;
+		float mn[3] = {0, 0, 0}, ext = 1.f;
+		if (mode == 1) source_morton_frame(source, N_, mn, &ext);
+		DevBuf<float> d_xyz(3 * N_);
+		DevBuf<int32_t> d_perm(N_);
+		HIPCHK(hipMemcpyAsync(d_xyz.p, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+		HIPCHK(hipEventRecord(ev0_, stream_));
+		HIPCHK(launch_source_order(d_xyz.p, (int)N_, mode, mn, ext, d_perm.p, stream_));
+		HIPCHK(hipEventRecord(ev1_, stream_));
+		HIPCHK(launch_source_gather(d_xyz.p, d_perm.p, (int)N_, d_src_, stream_));
+		HIPCHK(hipMemcpyAsync(perm.data(), d_perm.p, sizeof(int32_t) * N_, hipMemcpyDeviceToHost, stream_));
+		HIPCHK(hipStreamSynchronize(stream_));
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		source_order_ms_ = ms;
+	} else {
+		source_order_host(source, N_, p_.morton_sort, perm.data());
+	}
+	src_perm_ = perm;
+	h_src_sorted_.resize(4 * N_);
+	double cs[3] = {0, 0, 0};
+	for (size_t i = 0; i < N_; i++) {
+		const float* s = source + 3 * (size_t)perm[i];
+		float x = s[0], y = s[1], z = s[2];
+		h_src_sorted_[4 * i] = x; h_src_sorted_[4 * i + 1] = y; h_src_sorted_[4 * i + 2] = z;
+		h_src_sorted_[4 * i + 3] = std::sqrt(x * x + y * y + z * z);   // normData, jly_goicp.cpp:145
+		cs[0] += x; cs[1] += y; cs[2] += z;
+	}
+	for (int k = 0; k < 3; k++) src_centroid_[k] = (float)(cs[k] / (double)N_);
+	if (!on_device) HIPCHK(hipMemcpy(d_src_, h_src_sorted_.data(), sizeof(float4) * N_, hipMemcpyHostToDevice));
+	src_radius_ = 0.f;
+	for (size_t i = 0; i < N_; i++) src_radius_ = std::max(src_radius_, h_src_sorted_[4 * i + 3]);
+	src_crad_ = -1.0;
+	// ---- the N-sized buffers (grow-only: a smaller cloud uses the front of what is there, every kernel is bounded by N) ----
+	const size_t partials = std::max(icp_partials_floats((int)N_), (size_t)icp_trim_blocks((int)N_) * kIcpAcc);
+	if (partials > cap_partials_) {
+		hipFree(d_icp_partials_);
+		d_icp_partials_ = nullptr; cap_partials_ = 0;
+		HIPCHK(hipMalloc(&d_icp_partials_, sizeof(float) * partials));
+		cap_partials_ = partials;
+	}
+	if (inliers_ < (int)N_ && N_ > cap_trim_) {
+		hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
+		d_nn_d2_ = nullptr; d_nn_slot_ = nullptr; d_include_ = nullptr; cap_trim_ = 0;
+		HIPCHK(hipMalloc(&d_nn_d2_, sizeof(float) * N_));
+		HIPCHK(hipMalloc(&d_nn_slot_, sizeof(int) * N_));
+		HIPCHK(hipMalloc(&d_include_, N_));
+		cap_trim_ = N_;
+	}
+	if (p_.icp_nn_cache) {
+		if (N_ > cap_cache_) {
+			hipFree(d_nn_cache_);
+			d_nn_cache_ = nullptr; cap_cache_ = 0;
+			HIPCHK(hipMalloc(&d_nn_cache_, sizeof(float4) * 2 * N_));
+			cap_cache_ = N_;
+		}
+		HIPCHK(hipMemsetAsync(d_nn_cache_, 0, sizeof(float4) * 2 * N_, stream_));      // sqrt(best2_ref) = 0: the first pass walks
+	}
+}
+
+void Engine::set_source(const float* source, size_t N)
+{
+	// everything that can refuse comes first: a refused call leaves the engine as it was
+	check_source(source, N);
+	if (registering_.load()) throw std::invalid_argument("goicp_set_source: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	TraceRange tr("goicp:set_source");
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	load_source(source, N, true);
+	for (QLane& L : ql_) if (L.cap) lane_source_buffers(L);
+	ensure_batch(4096, 64);                          // the bounds scratch depends on N
+	// ---- the search and ICP state of a fresh engine; params, options, normals, callback, shard and the shard statistics stay ----
+	cancel_.store(false);
+	early_exit_ = converged_ = false;
+	rot_ramp_ = 8;
+	unrefined_ = false;
+	last_round_work_ = 0; tile_sticky_ = false;
+	icp_cache_active_ = false;
+	while (!queue_.empty()) queue_.pop();
+	if (flow_mode() && ql_[0].cap) flow_reset();
+	cnt_ = Counters{};
+	queue_rounds_ = 0; queue_fallbacks_ = 0; tile_rounds_ = 0;
+	std::memset(sel_hist_, 0, sizeof(sel_hist_));
+	std::memset(level_hist_, 0, sizeof(level_hist_));
+	last_inliers_.clear(); last_robust_cost_.clear(); last_robust_w_.clear();   // no ICP has run on this cloud
+	opt_err_ = 1e10f;
+	register_ms_ = bnb_ms_ = icp_ms_ = 0;
+	const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+	std::memcpy(optR_, I, sizeof(I)); std::memcpy(curR_, I, sizeof(I)); std::memcpy(stepR_, I, sizeof(I));
+	std::memset(optT_, 0, sizeof(optT_)); std::memset(curT_, 0, sizeof(curT_)); std::memset(stepT_, 0, sizeof(stepT_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	{
+		// the snapshot of a fresh engine (init publishes before a callback can be set: none is called here either)
+		std::lock_guard<std::mutex> lk(mtx_);
+		std::memcpy(snap_.optR, optR_, sizeof(optR_)); std::memcpy(snap_.optT, optT_, sizeof(optT_));
+		std::memcpy(snap_.curR, curR_, sizeof(curR_)); std::memcpy(snap_.curT, curT_, sizeof(curT_));
+		snap_.best_sse = opt_err_;
+		snap_.finished = 0;
+		snap_.counters = cnt_;
+		snap_.dt_build_ms = dt_build_ms_;
+		snap_.register_ms = register_ms_;
+	}
+	if (p_.verbose) std::fprintf(stderr, "[goicp] set_source: %zu points, %.2f ms (device order %.3f ms)\n", N_, now_ms() - t0, source_order_ms_);
+}
+
+void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)
+{
+	if (!perm) throw std::invalid_argument("goicp_debug_source_order: perm must be non-null");
+	if (mode < 0 || mode > 2) throw std::invalid_argument("goicp_debug_source_order: mode must be 0, 1 or 2");
+	check_source(xyz, n);
+	if (registering_.load()) throw std::invalid_argument("goicp_debug_source_order: not while a registration runs");
+	DeviceGuard guard(dev_);
+	float mn[3] = {0, 0, 0}, ext = 1.f;
+	if (mode == 1) source_morton_frame(xyz, n, mn, &ext);
+	DevBuf<float> d_xyz(3 * n);
+	DevBuf<int32_t> d_perm(n);
+	HIPCHK(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_source_order(d_xyz.p, (int)n, mode, mn, ext, d_perm.p, stream_));
+	HIPCHK(hipMemcpyAsync(perm, d_perm.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+}
+
 Engine::~Engine() { release(); }
 
 void Engine::release()
@@ -573,6 +605,7 @@ void Engine::release()
 	ev_fork_ = nullptr;
 	if (stream_) hipStreamDestroy(stream_);
 	d_src_ = nullptr; d_dt_ = nullptr; d_overshoot_ = nullptr; d_kd_pts_ = nullptr;
+	cap_src_ = cap_trim_ = cap_cache_ = cap_partials_ = 0;
 	for (int l = 0; l < kMaxLevels; l++) d_kd_boxes_[l] = nullptr;
 	d_cubes_ = nullptr; d_rots_ = nullptr; d_ub_ = d_lb_ = d_scratch_ = nullptr;
 	h_cubes_ = nullptr; h_rots_ = nullptr; h_ub_ = h_lb_ = nullptr;
@@ -1826,6 +1859,57 @@ void Engine::free_lane(QLane& L)
 	L = QLane{};          // the stream is the engine's (lane_stream_), not the lane's to destroy
 }
 
+// What a lane derives from the source cloud (ensure_lane; again after set_source): the sorted-round setup with the chunk centroids, the
+// round's scratch (sized by the sort's chunks) and the tile list, which exists only while tiles_usable()
+void Engine::lane_source_buffers(QLane& L)
+{
+	const size_t max_groups = (size_t)L.list_cap;
+	HIPCHK(hipStreamSynchronize(L.stream));
+	hipFree(L.sort.keys); hipFree(L.sort.order); hipFree(L.sort.hist); hipFree(const_cast<float4*>(L.sort.cen)); L.sort = QSort{};
+	hipFree(L.d_scratch); L.d_scratch = nullptr;
+	if (!tiles_usable() && L.tile.ub) {
+		for (int k = 0; k < 2; k++) { hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); }
+		hipFree(L.tile.ub); hipFree(L.tile.lb); hipFree(L.tile.scratch); L.tile = QTile{};
+	}
+	// footprint-ordered items for the large rounds (lean grids, untrimmed, clouds of 4..16 chunks of 4 096 points).  Measured, registration in ms,
+	// chunk 2 048 | 3 072 | 4 096 | 6 144 | search order: bunny 34.4 | 33.1 | 33.8 | 34.1 | 36.8 (run-to-run +-0.6); bunny mse 1e-4 280 | 277 | 280 | 276 | 295;
+	// synthetic 40 k mse 3e-5 798 | 758 | 714 | 725 | 921; spanner 150 k mse 2e-5 223 | 212 | 206 | 201 | 195 -- above ~64 k points the unsorted
+	// launch's large chunks win, so the feature stops there
+	// round 4: the cloud is cut into TEN chunks (rounded up to 256 points) rather than into chunks of 4 096 points -- re-swept with the threshold at
+	// 256 expansions (tools/sort_threshold_probe.py chunks / chunks2, registration in ms): bunny (30 k) 2 048 | 2 560 | 3 072 | 4 096 points =
+	// 32.8 | 31.8-32.4 | 32.5 | 34.3, bunny mse 1e-4 271 | 266 | 267 | 270, synthetic 40 k at mse 3e-5 -- | 770 | 765 | 720 (3 584: 744), every second
+	// bunny point (15 k) 1 280 .. 4 096: 26.3-27.4, flat: ten chunks is 3 072 / 4 096 / 1 536 points there
+	const int kSortChunkPts = (int)(((N_ + 9) / 10 + 255) / 256 * 256);
+	const int sort_chunks = (int)((N_ + kSortChunkPts - 1) / kSortChunkPts);
+	if (p_.sort_items && bounds_uses_lean(bounds_dt()) && inliers_ >= (int)N_ && N_ >= 12288 && N_ <= 65536 && sort_chunks >= 4 && sort_chunks <= 16) {
+		float4* cen = nullptr;
+		HIPCHK(hipMalloc(&cen, sizeof(float4) * sort_chunks));
+		HIPCHK(launch_chunk_centroids(d_src_, (int)N_, kSortChunkPts, cen, L.stream));
+		L.sort.cen = cen;
+		HIPCHK(hipMalloc(&L.sort.keys, sizeof(unsigned) * max_groups * sort_chunks));
+		HIPCHK(hipMalloc(&L.sort.order, sizeof(unsigned) * max_groups * sort_chunks));
+		HIPCHK(hipMalloc(&L.sort.hist, qsort_hist_bytes()));
+		HIPCHK(hipMemsetAsync(L.sort.hist, 0, qsort_hist_bytes(), L.stream));     // kept zero between uses by the kernels themselves
+		// sorted rounds from kSortMinGroups expansions.  Round 3 (512 | 1024 | 2048 | 4096): 35.0 | 34.5 | 33.6 | 37.3 ms.  Re-swept in round 4 with the
+		// twin lists and the 4 096-point chunks in place (tools/sort_threshold_probe.py, median of 7): 1 | 128 | 512 | 1024 | 2048 | 4096 | off = 33.8 | 33.3 | 33.5 | 33.6 | 34.4 | 36.6 | 36.3 ms;
+		// mse 1e-4 / 3e-5 (0.27 / 6.8 s) flat between 128, 256 and 2048 -- so round 1 of a large batch (230 roots x two passes) is sorted too
+		constexpr int kSortMinGroups = 256;
+		L.sort.chunk_pts = kSortChunkPts; L.sort.chunks = sort_chunks; L.sort.min_groups = kSortMinGroups;
+		L.sort.shift = qsort_shift(dt_.V);           // 16-voxel cells (32-voxel cells: 35.1 ms)
+	}
+	HIPCHK(hipMalloc(&L.d_scratch, sizeof(float) * bounds_queue_scratch_floats((int)max_groups, L.sort.order ? L.sort.chunks : 0)));
+	if (tiles_usable() && !L.tile.ub) {
+		// the second expansion list of a round (LDS-staged DT tiles): same capacity as the direct list
+		for (int k = 0; k < 2; k++) {
+			HIPCHK(hipMalloc(&L.tile.parents[k], sizeof(ParentRec) * max_groups));
+			HIPCHK(hipMalloc(&L.tile.segs[k], sizeof(TileSeg) * L.seg_cap));
+		}
+		HIPCHK(hipMalloc(&L.tile.ub, sizeof(float) * max_groups * kGroup));
+		HIPCHK(hipMalloc(&L.tile.lb, sizeof(float) * max_groups * kGroup));
+		HIPCHK(hipMalloc(&L.tile.scratch, sizeof(float) * bounds_tile_queue_scratch_floats(L.seg_cap)));
+	}
+}
+
 void Engine::ensure_queues(size_t nsearch) { ensure_lane(0, nsearch); }
 
 void Engine::ensure_lane(int li, size_t nsearch)
@@ -1857,43 +1941,7 @@ void Engine::ensure_lane(int li, size_t nsearch)
 	for (int k = 0; k < 2; k++) HIPCHK(hipMalloc(&L.d_psearch[k], sizeof(int) * max_groups));
 	HIPCHK(hipMalloc(&L.d_ub, sizeof(float) * max_groups * kGroup));
 	HIPCHK(hipMalloc(&L.d_lb, sizeof(float) * max_groups * kGroup));
-	// footprint-ordered items for the large rounds (lean grids, untrimmed, clouds of 4..16 chunks of 4 096 points).  Measured, registration in ms,
-	// chunk 2 048 | 3 072 | 4 096 | 6 144 | search order: bunny 34.4 | 33.1 | 33.8 | 34.1 | 36.8 (run-to-run +-0.6); bunny mse 1e-4 280 | 277 | 280 | 276 | 295;
-	// synthetic 40 k mse 3e-5 798 | 758 | 714 | 725 | 921; spanner 150 k mse 2e-5 223 | 212 | 206 | 201 | 195 -- above ~64 k points the unsorted
-	// launch's large chunks win, so the feature stops there
-	// round 4: the cloud is cut into TEN chunks (rounded up to 256 points) rather than into chunks of 4 096 points -- re-swept with the threshold at
-	// 256 expansions (tools/sort_threshold_probe.py chunks / chunks2, registration in ms): bunny (30 k) 2 048 | 2 560 | 3 072 | 4 096 points =
-	// 32.8 | 31.8-32.4 | 32.5 | 34.3, bunny mse 1e-4 271 | 266 | 267 | 270, synthetic 40 k at mse 3e-5 -- | 770 | 765 | 720 (3 584: 744), every second
-	// bunny point (15 k) 1 280 .. 4 096: 26.3-27.4, flat: ten chunks is 3 072 / 4 096 / 1 536 points there
-	const int kSortChunkPts = (int)(((N_ + 9) / 10 + 255) / 256 * 256);
-	const int sort_chunks = (int)((N_ + kSortChunkPts - 1) / kSortChunkPts);
-	if (p_.sort_items && bounds_uses_lean(bounds_dt()) && inliers_ >= (int)N_ && N_ >= 12288 && N_ <= 65536 && sort_chunks >= 4 && sort_chunks <= 16) {
-		float4* cen = nullptr;
-		HIPCHK(hipMalloc(&cen, sizeof(float4) * sort_chunks));
-		HIPCHK(launch_chunk_centroids(d_src_, (int)N_, kSortChunkPts, cen, L.stream));
-		L.sort.cen = cen;
-		HIPCHK(hipMalloc(&L.sort.keys, sizeof(unsigned) * max_groups * sort_chunks));
-		HIPCHK(hipMalloc(&L.sort.order, sizeof(unsigned) * max_groups * sort_chunks));
-		HIPCHK(hipMalloc(&L.sort.hist, qsort_hist_bytes()));
-		HIPCHK(hipMemsetAsync(L.sort.hist, 0, qsort_hist_bytes(), L.stream));     // kept zero between uses by the kernels themselves
-		// sorted rounds from kSortMinGroups expansions.  Round 3 (512 | 1024 | 2048 | 4096): 35.0 | 34.5 | 33.6 | 37.3 ms.  Re-swept in round 4 with the
-		// twin lists and the 4 096-point chunks in place (tools/sort_threshold_probe.py, median of 7): 1 | 128 | 512 | 1024 | 2048 | 4096 | off = 33.8 | 33.3 | 33.5 | 33.6 | 34.4 | 36.6 | 36.3 ms;
-		// mse 1e-4 / 3e-5 (0.27 / 6.8 s) flat between 128, 256 and 2048 -- so round 1 of a large batch (230 roots x two passes) is sorted too
-		constexpr int kSortMinGroups = 256;
-		L.sort.chunk_pts = kSortChunkPts; L.sort.chunks = sort_chunks; L.sort.min_groups = kSortMinGroups;
-		L.sort.shift = qsort_shift(dt_.V);           // 16-voxel cells (32-voxel cells: 35.1 ms)
-	}
-	HIPCHK(hipMalloc(&L.d_scratch, sizeof(float) * bounds_queue_scratch_floats((int)max_groups, L.sort.order ? L.sort.chunks : 0)));
-	if (tiles_usable()) {
-		// the second expansion list of a round (LDS-staged DT tiles): same capacity as the direct list
-		for (int k = 0; k < 2; k++) {
-			HIPCHK(hipMalloc(&L.tile.parents[k], sizeof(ParentRec) * max_groups));
-			HIPCHK(hipMalloc(&L.tile.segs[k], sizeof(TileSeg) * L.seg_cap));
-		}
-		HIPCHK(hipMalloc(&L.tile.ub, sizeof(float) * max_groups * kGroup));
-		HIPCHK(hipMalloc(&L.tile.lb, sizeof(float) * max_groups * kGroup));
-		HIPCHK(hipMalloc(&L.tile.scratch, sizeof(float) * bounds_tile_queue_scratch_floats(L.seg_cap)));
-	}
+	lane_source_buffers(L);
 	if (!L.d_ctl) {
 		HIPCHK(hipMalloc(&L.d_ctl, sizeof(QCtl)));
 		HIPCHK(hipHostMalloc(&L.h_ctl, sizeof(QCtl)));

@@ -256,10 +256,23 @@ public:
 	hipStream_t stream() const { return stream_; }
 	const float4* d_source() const { return d_src_; }
 	void source_transformed(const float R[9], const float t[3], float* out_xyz);  // original order
+	// goicp_set_source: a new source cloud under the same target -- everything derived from the target is kept (distance transform, k-d
+	// hierarchy, nearest-point table, normals, streams, queues, warm-ups), the params and the per-handle options persist, the search / ICP
+	// state is the one of a fresh engine.  The order is computed on the device (kdbuild.hip).  Refused while a registration runs
+	void set_source(const float* source_xyz, size_t N);
+	// goicp_debug_source_order (test): the device ordering alone, of any cloud
+	void debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm);
+	double last_source_order_ms() const { return source_order_ms_; }   // the device ordering of the last set_source (HIP events)
 
 private:
 	struct InnerSearch;
 	void init(const float* target_xyz, size_t M, const float* source_xyz, size_t N);
+	static void check_source(const float* source_xyz, size_t N);
+	// the source stage of init and all of set_source's device work: order (host, or device when device_order) -> gather with |p| ->
+	// centroid -> upload -> the N-sized buffers (grow-only)
+	void load_source(const float* source_xyz, size_t N, bool device_order);
+	size_t cap_src_ = 0, cap_trim_ = 0, cap_cache_ = 0, cap_partials_ = 0;   // points / floats the N-sized device buffers hold
+	double source_order_ms_ = 0;
 	void release();
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(int k, size_t B);
@@ -371,6 +384,7 @@ private:
 	} ql_[kMaxLanes];
 	hipStream_t lane_stream_[kMaxLanes] = {};               // lane 0: stream_, lane 1: created with the engine, further lanes: on first use
 	void free_lane(QLane& L);
+	void lane_source_buffers(QLane& L);   // what a lane derives from the source: the sorted-round setup, the scratch sized by it, the tile list
 	void ensure_lane(int li, size_t nsearch);
 	double last_round_work_ = 0;                            // point-expansions (expansions x source points) of the previous batch's mean round
 	static constexpr double kLaneMinWork = 64e6;            // the auto mode's bar on last_round_work_ (run_inner_device)
@@ -461,6 +475,10 @@ void build_kdtree(const float* xyz, int M, int leaf_max, KdHost* out);
 // fn(0..ntasks-1) on up to `threads` host threads (tasks claimed from a counter; the first exception is rethrown)
 void parallel_tasks(int threads, int ntasks, const std::function<void(int)>& fn);
 void rodrigues(float ax, float ay, float az, float R[9]);   // jly_goicp.cpp:449-467
+// goicp_source_order_host: the source order of Params::morton_sort on the host (kdtree.cpp); perm[sorted position] = original index
+void source_order_host(const float* xyz, size_t n, int mode, int32_t* perm);
+// per-axis minimum and largest extent (at least 1e-30) of a cloud, as the Morton order quantises it
+void source_morton_frame(const float* xyz, size_t n, float mn[3], float* ext);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

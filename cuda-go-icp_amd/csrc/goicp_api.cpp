@@ -2,6 +2,7 @@
 // around goicp::Engine and the config / cloud IO helpers.
 #include "../../include/goicp_mi355.h"
 
+#include <climits>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -167,6 +168,25 @@ int goicp_destroy(goicp_handle h)
 {
 	if (!h) return GOICP_OK;
 	return guarded([&] { delete h->e; delete h; });
+}
+
+int goicp_set_source(goicp_handle h, const float* source_xyz, size_t n_source)
+{
+	REQUIRE(h && source_xyz && n_source > 0);
+	return guarded([&] { h->e->set_source(source_xyz, n_source); });
+}
+
+int goicp_source_order_host(const float* xyz, size_t n, int32_t mode, int32_t* perm)
+{
+	REQUIRE(xyz && perm && n > 0 && mode >= 0 && mode <= 2);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::source_order_host(xyz, n, mode, perm); });
+}
+
+int goicp_debug_source_order(goicp_handle h, const float* xyz, size_t n, int32_t mode, int32_t* perm)
+{
+	REQUIRE(h && xyz && perm && n > 0);
+	return guarded([&] { h->e->debug_source_order(xyz, n, mode, perm); });
 }
 
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)

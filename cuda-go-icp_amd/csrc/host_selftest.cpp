@@ -252,6 +252,16 @@ int main()
 		std::atomic<int> hits{0};
 		goicp::parallel_tasks(8, 100, [&](int) { hits++; });
 		CHECK(hits == 100);
+		// the source order (threaded top from 8 192 points on): a permutation in every mode, at sizes around the thresholds
+		for (int n : {1, 2, 5, 257, 8191, 8192, 20000})
+			for (int mode = 0; mode <= 2; mode++) {
+				std::vector<int32_t> perm((size_t)n, -1);
+				goicp::source_order_host(pts.data(), (size_t)n, mode, perm.data());
+				std::vector<char> seen((size_t)n, 0);
+				bool ok = true;
+				for (int32_t v : perm) { ok = ok && v >= 0 && v < n && !seen[(size_t)v]; if (ok) seen[(size_t)v] = 1; }
+				CHECK(ok);
+			}
 		float R[9];
 		goicp::rodrigues(0.3f, -0.2f, 0.9f, R);
 		CHECK(std::fabs(R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]) - 1.f) < 1e-5f);

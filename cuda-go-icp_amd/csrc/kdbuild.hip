@@ -6,8 +6,13 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+#include <algorithm>
 #include <climits>
 #include <cmath>
+#include <vector>
 
 #include "device.hpp"
 
@@ -103,6 +108,222 @@ hipError_t launch_kd_build(const float* d_xyz, int M, int K, const float mn[3], 
 	}
 	e = hipStreamSynchronize(stream);            // the temporaries are in use until here
 	return e != hipSuccess ? e : hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Source order on the device (Params::morton_sort; host twin: source_order_host, kdtree.cpp).
+//
+// Mode 2, the k-d order.  The host recursion splits a run at the source_order_left(n)-th element of the order (coordinate on the longest
+// axis of the run's bounding box, index) and recurses down to single points.  The size of the left part depends on the run's length only,
+// the comparator is a total order and the recursion ends at single points, so the permutation is unique -- and every level of the
+// recursion can be done for all runs at once:
+//   * the point ids are sorted once per axis by (key(coordinate), id) -- a stable radix sort of ascending ids;
+//   * invariant: inside every run, each of the three lists holds the run's points in that axis' order.  So the run's bounding box is the
+//     first and the last element of each list, and the left part is the first nl entries of the longest axis' list;
+//   * a level flags the ids of the left parts, then stable-partitions all three lists inside every run (rank = exclusive scan of the
+//     flags minus its value at the run's start), which keeps the invariant for both halves; the chosen axis' list comes out unchanged;
+//   * the run bounds live per position in device arrays and are rewritten by the level's own kernel; the number of levels is a function
+//     of N alone (the host counts it), so the loop has no round trip at all.
+// After the last level every run is a single point and any list is the permutation.
+// ------------------------------------------------------------------------------------------------
+// order-preserving key of a float; -0 ties with +0 as in the host's fa == fb
+__device__ __forceinline__ unsigned so_key(float f)
+{
+	unsigned b = __float_as_uint(f);
+	if (b == 0x80000000u) b = 0u;
+	return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ void so_axis_keys_kernel(const float* __restrict__ xyz, int n, int axis, unsigned* __restrict__ keys, int* __restrict__ ids)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	keys[i] = so_key(xyz[3 * (size_t)i + axis]);
+	ids[i] = i;
+}
+
+// the host's 30-bit code: (s - mn) / ext, * 1024.f, clamp, cast -- IEEE division, nothing fused (the file is built with -ffp-contract=off)
+__global__ void so_morton_kernel(const float* __restrict__ xyz, int n, float mnx, float mny, float mnz, float ext,
+                                 unsigned* __restrict__ keys, int* __restrict__ ids)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float fx = __fdiv_rn(xyz[3 * (size_t)i] - mnx, ext), fy = __fdiv_rn(xyz[3 * (size_t)i + 1] - mny, ext), fz = __fdiv_rn(xyz[3 * (size_t)i + 2] - mnz, ext);
+	const unsigned qx = (unsigned)fminf(1023.f, fmaxf(0.f, fx * 1024.f));
+	const unsigned qy = (unsigned)fminf(1023.f, fmaxf(0.f, fy * 1024.f));
+	const unsigned qz = (unsigned)fminf(1023.f, fmaxf(0.f, fz * 1024.f));
+	keys[i] = spread10(qx) | (spread10(qy) << 1) | (spread10(qz) << 2);
+	ids[i] = i;
+}
+
+__global__ void so_iota_kernel(int* __restrict__ v, int n)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) v[i] = i;
+}
+
+__global__ void so_root_kernel(int* __restrict__ lo, int* __restrict__ hi, int n)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) { lo[i] = 0; hi[i] = n; }
+}
+
+// one thread per POSITION i: its run [lo, hi), the run's longest axis (the host's float expression, first axis wins a tie), the flag of the
+// id at position i of that axis' list (1 = left part), and the bounds of the half position i belongs to from the next level on
+__global__ void so_flag_kernel(const float* __restrict__ xyz, const int* __restrict__ lists, int n, const int* __restrict__ lo, const int* __restrict__ hi,
+                               int* __restrict__ lo2, int* __restrict__ hi2, unsigned char* __restrict__ flag)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int a = lo[i], b = hi[i], len = b - a;
+	if (len <= 1) {
+		flag[lists[i]] = 1;
+		lo2[i] = a; hi2[i] = b;
+		return;
+	}
+	float ext[3];
+	for (int k = 0; k < 3; k++) {
+		const int* L = lists + (size_t)k * n;
+		ext[k] = xyz[3 * (size_t)L[b - 1] + k] - xyz[3 * (size_t)L[a] + k];
+	}
+	int ax = 0;
+	for (int k = 1; k < 3; k++) if (ext[k] > ext[ax]) ax = k;
+	const int nl = source_order_left(len);
+	const bool left = i - a < nl;
+	flag[lists[(size_t)ax * n + i]] = left ? 1 : 0;
+	lo2[i] = left ? a : a + nl;
+	hi2[i] = left ? a + nl : b;
+}
+
+struct SoFlagOf {
+	const int* lists;
+	const unsigned char* flag;
+	__device__ int operator()(int j) const { return (int)flag[lists[j]]; }
+};
+
+// one thread per list entry j = k n + i: the stable partition of list k inside the run of position i.  scan = exclusive scan of the
+// flags over all 3 n entries; its value at the run's start is subtracted, so the lists may share one scan
+__global__ void so_partition_kernel(const int* __restrict__ lists, int* __restrict__ lists2, int n, const int* __restrict__ lo, const int* __restrict__ hi,
+                                    const unsigned char* __restrict__ flag, const int* __restrict__ scan)
+{
+	const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= 3LL * n) return;
+	const int k = (int)(j / n), i = (int)(j - (long long)k * n);
+	const int a = lo[i], len = hi[i] - a;
+	const int nl = source_order_left(len);
+	const int id = lists[j];
+	const int r = scan[j] - scan[(size_t)k * n + a];          // flagged entries of this run before position i
+	const int pos = flag[id] ? a + r : a + nl + (i - a - r);
+	if (pos >= a && pos < a + len) lists2[(size_t)k * n + pos] = id;
+}
+
+__global__ void so_gather_kernel(const float* __restrict__ xyz, const int* __restrict__ perm, int n, float4* __restrict__ out)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t id = (size_t)perm[i];
+	const float x = xyz[3 * id], y = xyz[3 * id + 1], z = xyz[3 * id + 2];
+	out[i] = make_float4(x, y, z, sqrtf(x * x + y * y + z * z));   // normData, jly_goicp.cpp:145
+}
+
+// levels of the k-d order's recursion for n points: the lengths at a level are few distinct values, all functions of n
+static int source_order_levels(int n)
+{
+	std::vector<int> cur{n};
+	int levels = 0;
+	while (cur.back() > 1) {
+		std::vector<int> next;
+		for (int v : cur) {
+			const int nl = source_order_left(v);
+			next.push_back(nl);
+			if (v > 1) next.push_back(v - nl);
+		}
+		std::sort(next.begin(), next.end());
+		next.erase(std::unique(next.begin(), next.end()), next.end());
+		cur.swap(next);
+		levels++;
+	}
+	return levels;
+}
+
+hipError_t launch_source_order(const float* d_xyz, int n, int mode, const float mn[3], float ext, int32_t* d_perm, hipStream_t stream)
+{
+	if (n <= 0) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define SO_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	if (mode <= 0) {
+		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, d_perm, n);
+		SO_TRY(hipGetLastError());
+		return hipStreamSynchronize(stream);
+	}
+	unsigned *keys = nullptr, *keys2 = nullptr;
+	int *ids = nullptr, *lists = nullptr, *lists2 = nullptr, *scan = nullptr, *seg = nullptr;
+	unsigned char* flag = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		unsigned*& a; unsigned*& b; int*& c; int*& d; int*& f; int*& g; int*& h; unsigned char*& i; void*& t;
+		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(i); hipFree(t); }
+	} cleanup{keys, keys2, ids, lists, lists2, scan, seg, flag, tmp};
+	const size_t N = (size_t)n;
+	SO_TRY(hipMalloc(&keys, sizeof(unsigned) * N));
+	SO_TRY(hipMalloc(&keys2, sizeof(unsigned) * N));
+	SO_TRY(hipMalloc(&ids, sizeof(int) * N));
+	size_t sort_bytes = 0, scan_bytes = 0;
+	if (mode == 1) {
+		hipLaunchKernelGGL(so_morton_kernel, grd, blk, 0, stream, d_xyz, n, mn[0], mn[1], mn[2], ext, keys, ids);
+		SO_TRY(hipGetLastError());
+		SO_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
+		SO_TRY(hipMalloc(&tmp, sort_bytes ? sort_bytes : 16));
+		SO_TRY(rocprim::radix_sort_pairs(tmp, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
+		return hipStreamSynchronize(stream);         // the temporaries are in use until here
+	}
+	const int levels = source_order_levels(n);
+	SO_TRY(hipMalloc(&lists, sizeof(int) * 3 * N));
+	if (levels > 0) {
+		SO_TRY(hipMalloc(&lists2, sizeof(int) * 3 * N));
+		SO_TRY(hipMalloc(&scan, sizeof(int) * 3 * N));
+		SO_TRY(hipMalloc(&seg, sizeof(int) * 4 * N));
+		SO_TRY(hipMalloc(&flag, N));
+	}
+	auto flags_of = [&](const int* l) { return rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), SoFlagOf{l, flag}); };
+	SO_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, lists, N, 0, 32, stream));
+	if (levels > 0) SO_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
+	const size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
+	SO_TRY(hipMalloc(&tmp, tmp_bytes));
+	for (int k = 0; k < 3; k++) {
+		hipLaunchKernelGGL(so_axis_keys_kernel, grd, blk, 0, stream, d_xyz, n, k, keys, ids);
+		SO_TRY(hipGetLastError());
+		size_t bytes = sort_bytes;
+		SO_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, lists + (size_t)k * N, N, 0, 32, stream));
+	}
+	if (levels > 0) {
+		int *lo = seg, *hi = seg + N, *lo2 = seg + 2 * N, *hi2 = seg + 3 * N;
+		hipLaunchKernelGGL(so_root_kernel, grd, blk, 0, stream, lo, hi, n);
+		SO_TRY(hipGetLastError());
+		const dim3 grd3((unsigned)((3 * N + 255) / 256));
+		for (int l = 0; l < levels; l++) {
+			hipLaunchKernelGGL(so_flag_kernel, grd, blk, 0, stream, d_xyz, lists, n, lo, hi, lo2, hi2, flag);
+			SO_TRY(hipGetLastError());
+			size_t bytes = scan_bytes;
+			SO_TRY(rocprim::exclusive_scan(tmp, bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
+			hipLaunchKernelGGL(so_partition_kernel, grd3, blk, 0, stream, lists, lists2, n, lo, hi, flag, scan);
+			SO_TRY(hipGetLastError());
+			std::swap(lists, lists2);
+			std::swap(lo, lo2);
+			std::swap(hi, hi2);
+		}
+	}
+	SO_TRY(hipMemcpyAsync(d_perm, lists, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+#undef SO_TRY
+	return hipStreamSynchronize(stream);             // the temporaries are in use until here
+}
+
+hipError_t launch_source_gather(const float* d_xyz, const int32_t* d_perm, int n, float4* d_src, hipStream_t stream)
+{
+	hipLaunchKernelGGL(so_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_xyz, d_perm, n, d_src);
+	return hipGetLastError();
 }
 
 }  // namespace goicp

@@ -153,4 +153,108 @@ void rodrigues(float ax, float ay, float az, float R[9])
 	R[6] = xz - ys;           R[7] = yz + xs;           R[8] = c + uz * uz * omc;
 }
 
+namespace {
+
+uint32_t part1by2(uint32_t x)
+{
+	x &= 0x3ff;
+	x = (x ^ (x << 16)) & 0xff0000ff;
+	x = (x ^ (x << 8)) & 0x0300f00f;
+	x = (x ^ (x << 4)) & 0x030c30c3;
+	x = (x ^ (x << 2)) & 0x09249249;
+	return x;
+}
+
+}  // namespace
+
+void source_morton_frame(const float* source, size_t N, float mn[3], float* ext)
+{
+	float mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+	mn[0] = mn[1] = mn[2] = INFINITY;
+	for (size_t i = 0; i < N; i++)
+		for (int k = 0; k < 3; k++) {
+			mn[k] = std::min(mn[k], source[3 * i + k]);
+			mx[k] = std::max(mx[k], source[3 * i + k]);
+		}
+	*ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-30f});
+}
+
+// The source order of Params::morton_sort (0 input order, 1 Morton curve, 2 k-d order): perm[sorted position] = original index
+void source_order_host(const float* source, size_t N_, int mode, int32_t* perm_out)
+{
+	std::vector<int32_t> perm(N_);
+	for (size_t i = 0; i < N_; i++) perm[i] = (int32_t)i;
+	if (mode == 1) {
+		float mn[3], ext;
+		source_morton_frame(source, N_, mn, &ext);
+		std::vector<uint32_t> code(N_);
+		for (size_t i = 0; i < N_; i++) {
+			uint32_t c = 0;
+			for (int k = 0; k < 3; k++) {
+				float f = (source[3 * i + k] - mn[k]) / ext;
+				uint32_t q = (uint32_t)std::min(1023.f, std::max(0.f, f * 1024.f));
+				c |= part1by2(q) << k;
+			}
+			code[i] = c;
+		}
+		std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return code[a] < code[b]; });
+	} else if (mode >= 2) {
+		// k-d order: split the longest axis of the subset's bounding box at the median, rounded so that
+		// the left part holds a multiple of 256 / 64 / 16 / 4 points (the largest that is smaller than the
+		// subset), down to single points.  Every aligned run of 64 points (one wavefront's gathers) is
+		// then a compact box-shaped surface patch, every aligned 4 and 16 lanes a sub-patch of it, and
+		// every aligned 256 (one workgroup iteration) a subtree: fewer distinct DT cache lines per gather
+		// instruction than a space-filling curve gives.  65 536-cube launch on the bunny: Morton 2.28 ms,
+		// Hilbert 2.13 ms, 64-point clusters 1.94 ms (principal-axis splits 2.01 ms), clusters ordered
+		// down to 4 points 1.85 ms, down to single points 1.84 ms.
+		// The result is unique whatever nth_element does inside a half: the size of the left part depends on the
+		// run's length only (source_order_left), the comparator is a total order, and the recursion ends at single
+		// points -- which is what lets the device build the same permutation level by level (kdbuild.hip)
+		// one split; returns the size of the left part (0 = nothing to split)
+		auto split = [&](size_t lo, size_t hi) -> size_t {
+			const size_t n = hi - lo;
+			if (n <= 1) return 0;
+			float bmn[3] = {INFINITY, INFINITY, INFINITY}, bmx[3] = {-INFINITY, -INFINITY, -INFINITY};
+			for (size_t i = lo; i < hi; i++)
+				for (int k = 0; k < 3; k++) {
+					bmn[k] = std::min(bmn[k], source[3 * perm[i] + k]);
+					bmx[k] = std::max(bmx[k], source[3 * perm[i] + k]);
+				}
+			int ax = 0;
+			for (int k = 1; k < 3; k++) if (bmx[k] - bmn[k] > bmx[ax] - bmn[ax]) ax = k;
+			const size_t nl = (size_t)source_order_left((int)n);
+			std::nth_element(perm.begin() + lo, perm.begin() + lo + nl, perm.begin() + hi, [&](int32_t a, int32_t b) {
+				const float fa = source[3 * a + ax], fb = source[3 * b + ax];
+				return fa < fb || (fa == fb && a < b);                    // total order: the permutation is reproducible
+			});
+			return nl;
+		};
+		auto order_range = [&](size_t lo0, size_t hi0) {
+			std::vector<std::pair<size_t, size_t>> stack{{lo0, hi0}};
+			while (!stack.empty()) {
+				auto [lo, hi] = stack.back(); stack.pop_back();
+				const size_t nl = split(lo, hi);
+				if (!nl) continue;
+				stack.push_back({lo + nl, hi});
+				stack.push_back({lo, lo + nl});
+			}
+		};
+		// the top of the tree level by level (its 1, 2, 4, 8 splits side by side), the (<= 16) ranges below in parallel
+		std::vector<std::pair<size_t, size_t>> ranges{{0, N_}};
+		while (N_ >= (1u << 13) && ranges.size() < 16) {
+			std::vector<size_t> nls(ranges.size());
+			parallel_tasks(16, (int)ranges.size(), [&](int t) { nls[t] = split(ranges[t].first, ranges[t].second); });
+			std::vector<std::pair<size_t, size_t>> next;
+			for (size_t t = 0; t < ranges.size(); t++) {
+				const auto [lo, hi] = ranges[t];
+				if (nls[t]) { next.push_back({lo, lo + nls[t]}); next.push_back({lo + nls[t], hi}); } else next.push_back({lo, hi});
+			}
+			if (next.size() == ranges.size()) break;
+			ranges.swap(next);
+		}
+		parallel_tasks(16, (int)ranges.size(), [&](int t) { order_range(ranges[t].first, ranges[t].second); });
+	}
+	std::memcpy(perm_out, perm.data(), sizeof(int32_t) * N_);
+}
+
 }  // namespace goicp

@@ -61,6 +61,15 @@ def information_decompose(A, rank_tol=1e-6):
     return eig, vec.reshape(6, 6), pinv.reshape(6, 6), rank.value
 
 
+def source_order(xyz, mode=2):
+    """goicp_source_order_host (host only): the permutation the engine orders a source cloud by (goicp_params.morton_sort = mode: 0 input
+    order, 1 Morton curve, 2 k-d order); perm[sorted position] = original index.  The device ordering of goicp_set_source equals it."""
+    xyz = _f32(xyz, (-1, 3))
+    perm = np.empty(len(xyz), np.int32)
+    B.check(B.load_library().goicp_source_order_host(_fptr(xyz), len(xyz), int(mode), perm.ctypes.data_as(C.POINTER(C.c_int32))))
+    return perm
+
+
 class Config:
     """Config(toml_filepath): same keys, defaults and clamps as the reference; raises on parse error."""
 
@@ -212,6 +221,24 @@ class Registration:
             except Exception:
                 self.close()
                 raise
+
+    # ---- source swap (goicp_set_source) ----
+    def set_source(self, pcs):
+        """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
+        options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit."""
+        pcs = _f32(pcs, (-1, 3))
+        B.check(self._lib.goicp_set_source(self.handle, _fptr(pcs), len(pcs)))
+        self.pcs, self.ns = pcs, len(pcs)
+        thr, inl = C.c_float(), C.c_int32()
+        B.check(self._lib.goicp_thresholds(self.handle, C.byref(thr), C.byref(inl)))
+        self.sse_threshold, self.inliers = np.float32(thr.value), inl.value
+
+    def debug_source_order(self, xyz, mode=2):
+        """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""
+        xyz = _f32(xyz, (-1, 3))
+        perm = np.empty(len(xyz), np.int32)
+        B.check(self._lib.goicp_debug_source_order(self.handle, _fptr(xyz), len(xyz), int(mode), perm.ctypes.data_as(C.POINTER(C.c_int32))))
+        return perm
 
     # ---- truncated search objective (goicp_set_search_truncation) ----
     def set_search_truncation(self, max_dist=0.0):
@@ -468,6 +495,11 @@ class FastGoICP:
         self.mtx = mtx or threading.Lock()
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
+
+    def set_source(self, pcs):
+        """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
+        self.registration.set_source(pcs)
+        self.sse_threshold = self.registration.sse_threshold
 
     def run(self):
         B.check(self.registration._lib.goicp_register(self.registration.handle))

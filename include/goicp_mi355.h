@@ -200,6 +200,30 @@ void goicp_params_from_config(const goicp_config* c, goicp_params* p);
 int goicp_create(const goicp_params* params, const float* target_xyz, size_t n_target,
                  const float* source_xyz, size_t n_source, goicp_handle* out);
 int goicp_destroy(goicp_handle h);
+/*
+ * goicp_set_source: a new source cloud on a live handle (PCL's setInputSource under a fixed target).  Everything derived from the target
+ * is kept -- the distance transform and its fp16 copy, the k-d hierarchy, the nearest-point table, the built target normals, the streams,
+ * the device queues and the warm-ups -- and only the source stage of goicp_create is redone: the order of goicp_params::morton_sort
+ * (computed on the device for modes 1 and 2), the gather with |p|, the centroid and the buffers sized by n_source (n_source may grow or
+ * shrink).  Afterwards the handle answers every entry point bit for bit as a fresh handle created with the same params and target, the
+ * new source, and the same per-handle options applied; only the wall-clock fields of goicp_poll may differ.
+ *   persists: the params, goicp_set_icp_options / _gate / _robust, goicp_set_search_truncation, the progress callback (not called by the
+ *             swap), goicp_set_shard, goicp_icp_shard_stats (accumulated since create);
+ *   resets:   the goicp_icp_step pose, the goicp_poll snapshot (identity poses, best_sse 1e10, finished 0, counters 0), the neighbour cache,
+ *             and the last run's goicp_icp_inliers / goicp_icp_robust_stats (refused until an ICP has run on the new cloud), so
+ *             goicp_result_information is refused until a registration has finished on it.
+ * GOICP_ERR_INVALID, the handle untouched: NULL arguments, n_source == 0, a non-finite coordinate, n_source above goicp_create's limit,
+ * any call while a registration runs (between goicp_register_begin and goicp_register_end included).  After any other error (a HIP
+ * failure in the middle of a swap) the handle is good for goicp_destroy only.  Sharded use: every rank swaps to the same cloud.
+ */
+int goicp_set_source(goicp_handle h, const float* source_xyz, size_t n_source);
+/*
+ * goicp_source_order_host (host only, no handle, no GPU): the source order of goicp_params::morton_sort = mode (0 input order, 1 30-bit
+ * Morton curve over the cloud's bounding cube, 2 k-d order: recursive split of the longest bounding-box axis at the median rounded to
+ * 256 / 64 / 16 / 4 points, down to single points; ties by index, -0 == +0).  perm[sorted position] = original index, n entries.
+ * GOICP_ERR_INVALID: NULL arguments, n == 0 or above goicp_create's limit, a mode outside 0..2.
+ */
+int goicp_source_order_host(const float* xyz, size_t n, int32_t mode, int32_t* perm);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);
@@ -663,6 +687,9 @@ int goicp_debug_cache_hits(goicp_handle h, const float R[9], const float t[3], i
  * points that come first -- run on the device against a fresh (unconverged) loop state; include[i] = 1 for the selected points, else 0.
  * kernel 0: the iteration's own choice by size; 1: the register kernel (n <= 32 768, else GOICP_ERR_INVALID); 2: the streaming kernel. */
 int goicp_debug_select(goicp_handle h, const float* d2, size_t n, int32_t num, int32_t kernel, uint8_t* include);
+/* goicp_debug_source_order (test): the DEVICE ordering goicp_set_source uses, alone, of any finite cloud (the handle lends its device and
+ * stream; its state is untouched); equals goicp_source_order_host element for element */
+int goicp_debug_source_order(goicp_handle h, const float* xyz, size_t n, int32_t mode, int32_t* perm);
 
 #ifdef __cplusplus
 }

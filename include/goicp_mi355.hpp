@@ -204,6 +204,15 @@ public:
 	// the same with an explicit rotation level (rot_level < 0 <=> fix_rot)
 	BoundsResult_t compute_sse_error(const Mat3& R, int rot_level, const std::vector<TransNode>& tnodes) const { return bounds(R, rot_level, tnodes); }
 	goicp_handle handle() const { return h_; }
+	// a new source cloud under the same target (goicp_set_source): everything built from the target, the params and the options set on this
+	// registration stay; afterwards it answers as one constructed with (pct, pcs) and the same options would
+	template <class Point3>
+	void set_source(const std::vector<Point3>& pcs, size_t ns)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		check(goicp_set_source(h_, reinterpret_cast<const float*>(pcs.data()), ns));
+		ns_ = ns;
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
@@ -338,6 +347,13 @@ public:
 	void run()
 	{
 		check(goicp_register(registration.handle()));
+		sync();
+	}
+	// Registration::set_source, then the public members are the fresh handle's (identity poses, not finished)
+	template <class Point3>
+	void set_source(const std::vector<Point3>& pcs)
+	{
+		registration.set_source(pcs, pcs.size());
 		sync();
 	}
 	void cancel() { goicp_cancel(registration.handle()); }
