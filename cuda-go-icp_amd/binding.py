@@ -183,6 +183,9 @@ SYMBOLS = {
     "goicp_set_source": (C.c_int, [_vp, _fp, C.c_size_t]),
     "goicp_source_order_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "goicp_debug_source_order": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
+    "goicp_voxel_downsample_host": (C.c_int, [_fp, C.c_size_t, C.c_float, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "goicp_voxel_downsample": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "goicp_set_source_voxel": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, C.POINTER(C.c_size_t)]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

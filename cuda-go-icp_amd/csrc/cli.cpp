@@ -1,7 +1,7 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
-//                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE]
+//                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -32,6 +32,11 @@
 //               transform, k-d hierarchy and every option set above are kept) and registered; one line per cloud with the swap's
 //               milliseconds, and io.output / io.visualization are written with .1, .2, ... before the extension.  Refused together with
 //               --ranks N > 1 and when FILE cannot be read or names no cloud -- before any device is touched
+//   --voxel V   the source -- and every cloud of --source-list -- is reduced to one centroid per occupied cell of a grid of pitch V (cloud
+//               units after `resize`) before it is registered.  The config's own source is reduced on the host (goicp_voxel_downsample_host:
+//               no engine exists yet), every listed cloud on the device as part of its swap (goicp_set_source_voxel: the same bits).
+//               --target-voxel V reduces the target the same way, on the host, before the engine is created.  V must be a finite number > 0
+//               -- refused before any device is touched; the .toml surface is the reference's and stays as it is
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -69,7 +74,7 @@ static std::string numbered(const std::string& p, int k)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
@@ -85,6 +90,8 @@ int main(int argc, char** argv)
 	double rank_tol = -1.0;
 	const char* list_arg = nullptr;
 	std::vector<std::string> source_list;
+	const char *voxel_arg = nullptr, *tvoxel_arg = nullptr;
+	float voxel = 0.f, target_voxel = 0.f;
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -101,6 +108,20 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--information")) information = 1;
 		else if (!std::strcmp(argv[i], "--information-rank-tol")) rank_tol_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--source-list")) list_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--voxel")) voxel_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--target-voxel")) tvoxel_arg = i + 1 < argc ? argv[++i] : "";
+	}
+	for (int k = 0; k < 2; k++) {
+		// a bad voxel is refused before any device is touched
+		const char* arg = k ? tvoxel_arg : voxel_arg;
+		if (!arg) continue;
+		char* end = nullptr;
+		const float v = std::strtof(arg, &end);
+		if (end == arg || *end != '\0' || !(v > 0.f) || !(v <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: %s needs a finite voxel size > 0, got '%s'\n", k ? "--target-voxel" : "--voxel", arg);
+			return 2;
+		}
+		(k ? target_voxel : voxel) = v;
 	}
 	if (list_arg) {
 		// refused before any device is touched
@@ -203,6 +224,18 @@ int main(int argc, char** argv)
 		std::vector<P3> source, target;
 		load_cloud(resolve(config.io.source, argv[1]), config.subsample, config.resize, source, seed);
 		load_cloud(resolve(config.io.target, argv[1]), config.subsample, config.resize, target, seed);
+		for (int k = 0; k < 2; k++) {
+			// the host function: no engine exists yet
+			std::vector<P3>& cloud = k ? target : source;
+			const float v = k ? target_voxel : voxel;
+			if (!(v > 0.f) || cloud.empty()) continue;
+			std::vector<P3> reduced(cloud.size());
+			size_t m = 0;
+			check(goicp_voxel_downsample_host(&cloud[0].x, cloud.size(), v, &reduced[0].x, nullptr, &m));
+			reduced.resize(m);
+			std::printf("%s voxel %g: %zu of %zu points kept\n", k ? "target" : "source", v, m, cloud.size());
+			cloud.swap(reduced);
+		}
 		std::printf("mode %d: source %zu points, target %zu points, mse_threshold %g\n", config.mode, source.size(),
 		            target.size(), config.mse_threshold);
 		goicp_params p;
@@ -310,7 +343,8 @@ int main(int argc, char** argv)
 			std::vector<P3> next;
 			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
 			const auto t0 = std::chrono::steady_clock::now();
-			engine.set_source(next);
+			size_t kept = next.size();
+			if (voxel > 0.f) kept = engine.set_source(next, voxel); else engine.set_source(next);
 			const double swap_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 			if (config.mode <= 2) {
 				for (int i = 0; i < iters; i++) check(goicp_icp_step(h));
@@ -318,7 +352,7 @@ int main(int argc, char** argv)
 				engine.run();
 			}
 			check(goicp_poll(h, &r));
-			std::printf("source %zu (%s): %zu points, swap %.3f ms, register %.1f ms, Best Error: %.7g, rotation nodes %lld\n", k + 1, source_list[k].c_str(), next.size(),
+			std::printf("source %zu (%s): %zu points, swap %.3f ms, register %.1f ms, Best Error: %.7g, rotation nodes %lld\n", k + 1, source_list[k].c_str(), kept,
 			            swap_ms, r.register_ms, r.best_sse, (long long)r.counters.rot_pops);
 			if (!config.io.output.empty()) engine.write_output(numbered(config.io.output, (int)k + 1));
 			if (!config.io.visualization.empty()) engine.write_visualization(numbered(config.io.visualization, (int)k + 1));

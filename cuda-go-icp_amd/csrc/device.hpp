@@ -416,6 +416,19 @@ inline int source_order_left(int n)
 hipError_t launch_source_order(const float* d_xyz, int n, int mode, const float mn[3], float ext, int32_t* d_perm, hipStream_t stream);
 // d_src[i] = (x, y, z, |p|) of point d_perm[i]
 hipError_t launch_source_gather(const float* d_xyz, const int32_t* d_perm, int n, float4* d_src, hipStream_t stream);
+// ---- voxel-grid downsampling on the device (kdbuild.hip; goicp_voxel_downsample_host is its host twin) ----
+// what the host derives from the cloud while it checks it (voxel_frame, kdtree.cpp): the per-axis minimum, the largest offset E from it, the
+// shift s of the exact fixed-point terms llrint(ldexp(d, s)), and the number of key bits in use (cell x | y << 21 | z << 42)
+struct VoxelFrame {
+	float mn[3], E, voxel;
+	int s, key_bits;
+};
+// d_xyz: the n points on the device.  d_out: room for 3 n floats, the first 3 m are written (one centroid per occupied cell, ascending key);
+// d_count (may be null): room for n ints, the first m are written.  ev_begin / ev_end (may be null) are recorded around the device work
+// proper: the kernels, the read-back of m and the two m-sized allocations, not the n-sized allocations and the frees.  Returns after the
+// stream has drained
+hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& f, float* d_out, int32_t* d_count, int* m, hipStream_t stream,
+                                   hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 
 // ---- distance transform build (DT3D::Build, jly_3ddt.cpp:889-979; exact EDT) -------------------
 // work: V^3 int32 (linear).  out: V^3 floats in dt.layout (may alias work only for layout 0).

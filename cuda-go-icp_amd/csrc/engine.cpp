@@ -427,7 +427,7 @@ void Engine::check_source(const float* source, size_t N)
 	for (size_t i = 0; i < 3 * N; i++) if (!std::isfinite(source[i])) throw std::invalid_argument("goicp: non-finite coordinate in the source cloud");
 }
 
-void Engine::load_source(const float* source, size_t N, bool device_order)
+void Engine::load_source(const float* source, size_t N, bool device_order, const float* d_xyz_ready)
 {
 	N_ = N;
 	inliers_ = (int)((float)N_ * (1 - p_.trim_fraction));    // jly_goicp.cpp:201
@@ -447,13 +447,14 @@ void Engine::load_source(const float* source, size_t N, bool device_order)
 		const int mode = p_.morton_sort == 1 ? 1 : 2;
 		float mn[3] = {0, 0, 0}, ext = 1.f;
 		if (mode == 1) source_morton_frame(source, N_, mn, &ext);
-		DevBuf<float> d_xyz(3 * N_);
+		DevBuf<float> d_up(d_xyz_ready ? 0 : 3 * N_);
 		DevBuf<int32_t> d_perm(N_);
-		HIPCHK(hipMemcpyAsync(d_xyz.p, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+		if (!d_xyz_ready) HIPCHK(hipMemcpyAsync(d_up.p, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+		const float* d_xyz = d_xyz_ready ? d_xyz_ready : d_up.p;
 		HIPCHK(hipEventRecord(ev0_, stream_));
-		HIPCHK(launch_source_order(d_xyz.p, (int)N_, mode, mn, ext, d_perm.p, stream_));
+		HIPCHK(launch_source_order(d_xyz, (int)N_, mode, mn, ext, d_perm.p, stream_));
 		HIPCHK(hipEventRecord(ev1_, stream_));
-		HIPCHK(launch_source_gather(d_xyz.p, d_perm.p, (int)N_, d_src_, stream_));
+		HIPCHK(launch_source_gather(d_xyz, d_perm.p, (int)N_, d_src_, stream_));
 		HIPCHK(hipMemcpyAsync(perm.data(), d_perm.p, sizeof(int32_t) * N_, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipStreamSynchronize(stream_));
 		float ms = 0.f;
@@ -514,6 +515,12 @@ void Engine::set_source(const float* source, size_t N)
 	TraceRange tr("goicp:set_source");
 	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
 	load_source(source, N, true);
+	finish_source_swap();
+	if (p_.verbose) std::fprintf(stderr, "[goicp] set_source: %zu points, %.2f ms (device order %.3f ms)\n", N_, now_ms() - t0, source_order_ms_);
+}
+
+void Engine::finish_source_swap()
+{
 	for (QLane& L : ql_) if (L.cap) lane_source_buffers(L);
 	ensure_batch(4096, 64);                          // the bounds scratch depends on N
 	// ---- the search and ICP state of a fresh engine; params, options, normals, callback, shard and the shard statistics stay ----
@@ -547,7 +554,54 @@ void Engine::set_source(const float* source, size_t N)
 		snap_.dt_build_ms = dt_build_ms_;
 		snap_.register_ms = register_ms_;
 	}
-	if (p_.verbose) std::fprintf(stderr, "[goicp] set_source: %zu points, %.2f ms (device order %.3f ms)\n", N_, now_ms() - t0, source_order_ms_);
+}
+
+void Engine::voxel_downsample(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m_out)
+{
+	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_voxel_downsample: out_xyz and m must be non-null");
+	VoxelFrame f;
+	voxel_frame(xyz, n, voxel, &f);
+	if (registering_.load()) throw std::invalid_argument("goicp_voxel_downsample: not while a registration runs");
+	DeviceGuard guard(dev_);
+	DevBuf<float> d_xyz(3 * n), d_out(3 * n);
+	DevBuf<int32_t> d_cnt(out_count ? n : 0);
+	int m = 0;
+	HIPCHK(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_voxel_downsample(d_xyz.p, (int)n, f, d_out.p, out_count ? d_cnt.p : nullptr, &m, stream_));
+	HIPCHK(hipMemcpyAsync(out_xyz, d_out.p, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_cnt.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	*m_out = (size_t)m;
+	if (p_.verbose) std::fprintf(stderr, "[goicp] voxel_downsample: %zu -> %d points\n", n, m);
+}
+
+void Engine::set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept)
+{
+	// everything that can refuse comes first: a refused call leaves the engine as it was
+	VoxelFrame f;
+	voxel_frame(xyz, n, voxel, &f);
+	if (registering_.load()) throw std::invalid_argument("goicp_set_source_voxel: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	TraceRange tr("goicp:set_source_voxel");
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	// the raw cloud goes up once; the reduced cloud stays on the device for the ordering stage, and comes back for the host mirror
+	DevBuf<float> d_raw(3 * n), d_red(3 * n);
+	int m = 0;
+	HIPCHK(hipMemcpyAsync(d_raw.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_voxel_downsample(d_raw.p, (int)n, f, d_red.p, nullptr, &m, stream_, ev0_, ev1_));
+	std::vector<float> red(3 * (size_t)m);
+	HIPCHK(hipMemcpyAsync(red.data(), d_red.p, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	float ms = 0.f;
+	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+	voxel_ms_ = ms;
+	load_source(red.data(), (size_t)m, true, d_red.p);
+	finish_source_swap();
+	if (n_kept) *n_kept = (size_t)m;
+	if (p_.verbose)
+		std::fprintf(stderr, "[goicp] set_source_voxel: %zu -> %zu points, %.2f ms (device reduction %.3f ms, device order %.3f ms)\n", n, N_, now_ms() - t0,
+		             voxel_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
 }
 
 void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)

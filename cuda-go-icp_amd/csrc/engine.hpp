@@ -263,6 +263,12 @@ public:
 	// goicp_debug_source_order (test): the device ordering alone, of any cloud
 	void debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm);
 	double last_source_order_ms() const { return source_order_ms_; }   // the device ordering of the last set_source (HIP events)
+	// goicp_voxel_downsample: the voxel-grid reduction on the device (kdbuild.hip launch_voxel_downsample); the engine lends its device and
+	// stream and nothing else: no member is written.  Refused while a registration runs
+	void voxel_downsample(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
+	// goicp_set_source_voxel: the raw cloud goes up once, is reduced and ordered on the device; only the reduced cloud and the permutation
+	// come back.  Afterwards the engine is the one set_source(voxel_downsample_host's output) leaves
+	void set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept);
 
 private:
 	struct InnerSearch;
@@ -270,9 +276,11 @@ private:
 	static void check_source(const float* source_xyz, size_t N);
 	// the source stage of init and all of set_source's device work: order (host, or device when device_order) -> gather with |p| ->
 	// centroid -> upload -> the N-sized buffers (grow-only)
-	void load_source(const float* source_xyz, size_t N, bool device_order);
+	// d_xyz_ready: the same cloud already on the device (3 N floats; set_source_voxel), which the device order then reads instead of an upload
+	void load_source(const float* source_xyz, size_t N, bool device_order, const float* d_xyz_ready = nullptr);
+	void finish_source_swap();                       // set_source / set_source_voxel after load_source: the search and ICP state of a fresh engine
 	size_t cap_src_ = 0, cap_trim_ = 0, cap_cache_ = 0, cap_partials_ = 0;   // points / floats the N-sized device buffers hold
-	double source_order_ms_ = 0;
+	double source_order_ms_ = 0, voxel_ms_ = 0;
 	void release();
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(int k, size_t B);
@@ -479,6 +487,11 @@ void rodrigues(float ax, float ay, float az, float R[9]);   // jly_goicp.cpp:449
 void source_order_host(const float* xyz, size_t n, int mode, int32_t* perm);
 // per-axis minimum and largest extent (at least 1e-30) of a cloud, as the Morton order quantises it
 void source_morton_frame(const float* xyz, size_t n, float mn[3], float* ext);
+// voxel-grid downsampling (kdtree.cpp).  voxel_frame checks the cloud and the voxel (std::invalid_argument: empty or too large a
+// cloud, a non-finite coordinate, a voxel that is not positive and finite, extent / voxel >= 2^21) and fills what both paths share;
+// voxel_downsample_host is goicp_voxel_downsample_host: out_xyz holds 3 n floats, out_count (may be null) n ints
+void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f);
+void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

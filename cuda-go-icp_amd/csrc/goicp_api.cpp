@@ -189,6 +189,25 @@ int goicp_debug_source_order(goicp_handle h, const float* xyz, size_t n, int32_t
 	return guarded([&] { h->e->debug_source_order(xyz, n, mode, perm); });
 }
 
+int goicp_voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m)
+{
+	REQUIRE(xyz && out_xyz && m && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::voxel_downsample_host(xyz, n, voxel, out_xyz, out_count, m); });
+}
+
+int goicp_voxel_downsample(goicp_handle h, const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m)
+{
+	REQUIRE(h && xyz && out_xyz && m && n > 0);
+	return guarded([&] { h->e->voxel_downsample(xyz, n, voxel, out_xyz, out_count, m); });
+}
+
+int goicp_set_source_voxel(goicp_handle h, const float* xyz, size_t n, float voxel, size_t* n_kept)
+{
+	REQUIRE(h && xyz && n > 0);
+	return guarded([&] { h->e->set_source_voxel(xyz, n, voxel, n_kept); });
+}
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

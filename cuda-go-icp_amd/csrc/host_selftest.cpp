@@ -262,6 +262,41 @@ int main()
 				for (int32_t v : perm) { ok = ok && v >= 0 && v < n && !seen[(size_t)v]; if (ok) seen[(size_t)v] = 1; }
 				CHECK(ok);
 			}
+		// voxel-grid downsampling on the host: the counts sum to n, every centroid lies inside the cloud's box, a voxel wider than the cloud
+		// gives one cell and a tiny one leaves every point alone; each refusal throws and writes nothing
+		for (int n : {1, 2, 65, 257, 20000})
+			for (float v : {1e-5f, 0.05f, 0.7f, 8.f}) {
+				std::vector<float> out(3 * (size_t)n, -9.f);
+				std::vector<int32_t> cnt((size_t)n, -9);
+				size_t m = 0;
+				goicp::voxel_downsample_host(pts.data(), (size_t)n, v, out.data(), cnt.data(), &m);
+				CHECK(m >= 1 && m <= (size_t)n);
+				long long total = 0;
+				bool inside = true;
+				for (size_t c = 0; c < m; c++) {
+					total += cnt[c];
+					for (int k = 0; k < 3; k++) inside = inside && out[3 * c + k] >= -1.f && out[3 * c + k] <= 1.f;
+				}
+				CHECK(total == n && inside);
+				CHECK(v < 8.f || m == 1);
+				CHECK(v > 1e-5f || m == (size_t)n);
+				CHECK(m == (size_t)n || (out[3 * m] == -9.f && cnt[m] == -9));
+			}
+		{
+			std::vector<float> out(30, -9.f);
+			size_t m = 77;
+			float bad[6] = {0.f, 0.f, 0.f, 1.f, NAN, 0.f};
+			int refused = 0;
+			for (int what = 0; what < 5; what++)
+				try {
+					if (what == 0) goicp::voxel_downsample_host(pts.data(), 10, 0.f, out.data(), nullptr, &m);
+					if (what == 1) goicp::voxel_downsample_host(pts.data(), 10, NAN, out.data(), nullptr, &m);
+					if (what == 2) goicp::voxel_downsample_host(pts.data(), 10, INFINITY, out.data(), nullptr, &m);
+					if (what == 3) goicp::voxel_downsample_host(bad, 2, 0.5f, out.data(), nullptr, &m);
+					if (what == 4) goicp::voxel_downsample_host(pts.data(), 10, 1e-9f, out.data(), nullptr, &m);   // more than 21 bits per axis
+				} catch (const std::invalid_argument&) { refused++; }
+			CHECK(refused == 5 && m == 77 && out[0] == -9.f);
+		}
 		float R[9];
 		goicp::rodrigues(0.3f, -0.2f, 0.9f, R);
 		CHECK(std::fabs(R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]) - 1.f) < 1e-5f);

@@ -326,4 +326,160 @@ hipError_t launch_source_gather(const float* d_xyz, const int32_t* d_perm, int n
 	return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Voxel-grid downsampling on the device (host twin: voxel_downsample_host, kdtree.cpp): one centroid per occupied cell, cells in
+// ascending key order.  rocPRIM's are the radix sort of (key, id) and the inclusive scan of the head flags (the cell index of every sorted
+// position); ours are the key kernel, the segmented sum and the finishing kernel.  The sums are exact 64-bit integers -- the term of a
+// coordinate is llrint(ldexp(d, s)), VoxelFrame::s chosen so that n terms stay below 2^62 -- so the order of addition cannot matter and the
+// pieces of a cell that spans several waves may arrive by atomicAdd in any order.
+// ------------------------------------------------------------------------------------------------
+// the cell of an offset d >= 0 from the frame's minimum: IEEE division, as the host's (int)floorf(d / v)
+__device__ __forceinline__ unsigned long long vx_cell(float d, float v) { return (unsigned long long)(int)floorf(__fdiv_rn(d, v)); }
+
+__global__ void vx_key_kernel(const float* __restrict__ xyz, int n, float mnx, float mny, float mnz, float v, unsigned long long* __restrict__ keys,
+                              int* __restrict__ ids)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float dx = xyz[3 * (size_t)i] - mnx, dy = xyz[3 * (size_t)i + 1] - mny, dz = xyz[3 * (size_t)i + 2] - mnz;
+	keys[i] = vx_cell(dx, v) | (vx_cell(dy, v) << 21) | (vx_cell(dz, v) << 42);
+	ids[i] = i;
+}
+
+struct VxHeadOf {
+	const unsigned long long* keys;
+	__device__ int operator()(int i) const { return (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0; }
+};
+
+__device__ __forceinline__ long long vx_shfl_up(long long v, int off)
+{
+	const int lo = __shfl_up((int)(unsigned)((unsigned long long)v & 0xffffffffull), off, 64);
+	const int hi = __shfl_up((int)(unsigned)((unsigned long long)v >> 32), off, 64);
+	return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
+}
+
+// One thread per SORTED position i (blocks of 256 = 4 waves of 64 consecutive positions).  cell1[i] = 1 + the cell index of position i (the
+// inclusive scan of the head flags).  Inside a wave, a segmented inclusive scan over the head flags: a lane adds the value 2^k lanes below
+// while that lane is still inside its own segment.  The last lane of every segment piece holds the piece's sums.  A segment that opens and
+// closes inside the wave is stored plainly (nobody else writes its cell); a piece of a segment cut by a wave edge -- at most the first and
+// the last piece of a wave -- is added to the zeroed accumulators with 64-bit atomicAdd.  acc: 4 words per cell (three sums, the count);
+// first_id[cell]: the id of the cell's first sorted point (the one a singleton cell returns)
+__global__ void __launch_bounds__(256) vx_segsum_kernel(const float* __restrict__ xyz, const int* __restrict__ ids, const int* __restrict__ cell1, int n,
+                                                        float mnx, float mny, float mnz, int s, unsigned long long* __restrict__ acc,
+                                                        int* __restrict__ first_id)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	const int lane = threadIdx.x & 63;
+	const bool valid = i < n;
+	long long t0 = 0, t1 = 0, t2 = 0;
+	int cnt = 0, c1 = 0;
+	bool head = true;                                          // a lane past the end closes the segment below it
+	if (valid) {
+		const int id = ids[i];
+		c1 = cell1[i];
+		head = i == 0 || cell1[i - 1] != c1;
+		const float dx = xyz[3 * (size_t)id] - mnx, dy = xyz[3 * (size_t)id + 1] - mny, dz = xyz[3 * (size_t)id + 2] - mnz;
+		t0 = llrint(ldexp((double)dx, s)); t1 = llrint(ldexp((double)dy, s)); t2 = llrint(ldexp((double)dz, s));
+		cnt = 1;
+		if (head) first_id[c1 - 1] = id;
+	}
+	const unsigned long long heads = __ballot(head);
+	const unsigned long long below = heads & (~0ull >> (63 - lane));        // the heads at or below this lane
+	const int start = below ? 63 - __clzll(below) : 0;          // first lane of this lane's piece
+	const int reach = lane - start;
+	for (int off = 1; off < 64; off <<= 1) {
+		const long long u0 = vx_shfl_up(t0, off), u1 = vx_shfl_up(t1, off), u2 = vx_shfl_up(t2, off);
+		const int uc = __shfl_up(cnt, off, 64);
+		if (off <= reach) { t0 += u0; t1 += u1; t2 += u2; cnt += uc; }
+	}
+	if (!valid) return;
+	const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+	if (!tail) return;
+	const bool opened = below != 0ull;                          // the segment's head is in this wave
+	const bool closed = lane < 63 || i == n - 1 || cell1[i + 1] != c1;
+	unsigned long long* a = acc + 4 * (size_t)(c1 - 1);
+	if (opened && closed) {
+		a[0] = (unsigned long long)t0; a[1] = (unsigned long long)t1; a[2] = (unsigned long long)t2; a[3] = (unsigned long long)cnt;
+	} else {
+		atomicAdd(a, (unsigned long long)t0); atomicAdd(a + 1, (unsigned long long)t1); atomicAdd(a + 2, (unsigned long long)t2);
+		atomicAdd(a + 3, (unsigned long long)cnt);
+	}
+}
+
+// one thread per cell: a singleton returns its point's own bits, any other cell (float)(mn + ldexp(S / count, -s)) in fp64
+__global__ void vx_finish_kernel(const float* __restrict__ xyz, const unsigned long long* __restrict__ acc, const int* __restrict__ first_id, int m,
+                                 float mnx, float mny, float mnz, int s, float* __restrict__ out, int32_t* __restrict__ count)
+{
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= m) return;
+	const unsigned long long* a = acc + 4 * (size_t)c;
+	const long long cnt = (long long)a[3];
+	float x, y, z;
+	if (cnt == 1) {
+		const size_t id = (size_t)first_id[c];
+		x = xyz[3 * id]; y = xyz[3 * id + 1]; z = xyz[3 * id + 2];
+	} else {
+		x = (float)((double)mnx + ldexp((double)(long long)a[0] / (double)cnt, -s));
+		y = (float)((double)mny + ldexp((double)(long long)a[1] / (double)cnt, -s));
+		z = (float)((double)mnz + ldexp((double)(long long)a[2] / (double)cnt, -s));
+	}
+	out[3 * (size_t)c] = x; out[3 * (size_t)c + 1] = y; out[3 * (size_t)c + 2] = z;
+	if (count) count[c] = (int32_t)cnt;
+}
+
+hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& f, float* d_out, int32_t* d_count, int* m_out, hipStream_t stream,
+                                   hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n <= 0 || !m_out) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define VX_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	unsigned long long *keys = nullptr, *keys2 = nullptr, *acc = nullptr;
+	int *ids = nullptr, *ids2 = nullptr, *cell1 = nullptr, *first_id = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		unsigned long long*& a; unsigned long long*& b; unsigned long long*& c; int*& d; int*& f; int*& g; int*& h; void*& t;
+		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(t); }
+	} cleanup{keys, keys2, acc, ids, ids2, cell1, first_id, tmp};
+	const size_t N = (size_t)n;
+	VX_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
+	VX_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
+	VX_TRY(hipMalloc(&ids, sizeof(int) * N));
+	VX_TRY(hipMalloc(&ids2, sizeof(int) * N));
+	VX_TRY(hipMalloc(&cell1, sizeof(int) * N));
+	// the used key bits only; the sort is stable and the ids start ascending, so the ids of a cell ascend
+	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+	auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), VxHeadOf{keys2});
+	size_t sort_bytes = 0, scan_bytes = 0;
+	VX_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	VX_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, heads, cell1, N, rocprim::plus<int>(), stream));
+	const size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
+	VX_TRY(hipMalloc(&tmp, tmp_bytes));
+	// ev_begin .. ev_end: the kernels, the 4-byte read-back of m and the two m-sized allocations; the n-sized allocations above and the
+	// frees at the end are outside
+	if (ev_begin) VX_TRY(hipEventRecord(ev_begin, stream));
+	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
+	VX_TRY(hipGetLastError());
+	size_t bytes = sort_bytes;
+	VX_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	bytes = scan_bytes;
+	VX_TRY(rocprim::inclusive_scan(tmp, bytes, heads, cell1, N, rocprim::plus<int>(), stream));
+	int m = 0;                                                  // the last index + 1
+	VX_TRY(hipMemcpyAsync(&m, cell1 + (N - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
+	VX_TRY(hipStreamSynchronize(stream));
+	if (m < 1 || m > n) return hipErrorUnknown;
+	VX_TRY(hipMalloc(&acc, sizeof(unsigned long long) * 4 * (size_t)m));
+	VX_TRY(hipMalloc(&first_id, sizeof(int) * (size_t)m));
+	VX_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4 * (size_t)m, stream));
+	hipLaunchKernelGGL(vx_segsum_kernel, grd, blk, 0, stream, d_xyz, ids2, cell1, n, f.mn[0], f.mn[1], f.mn[2], f.s, acc, first_id);
+	VX_TRY(hipGetLastError());
+	hipLaunchKernelGGL(vx_finish_kernel, dim3((m + 255) / 256), blk, 0, stream, d_xyz, acc, first_id, m, f.mn[0], f.mn[1], f.mn[2], f.s, d_out, d_count);
+	VX_TRY(hipGetLastError());
+	if (ev_end) VX_TRY(hipEventRecord(ev_end, stream));
+	*m_out = m;
+#undef VX_TRY
+	return hipStreamSynchronize(stream);                       // the temporaries are in use until here
+}
+
 }  // namespace goicp

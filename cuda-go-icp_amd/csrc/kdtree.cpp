@@ -257,4 +257,66 @@ void source_order_host(const float* source, size_t N_, int mode, int32_t* perm_o
 	std::memcpy(perm_out, perm.data(), sizeof(int32_t) * N_);
 }
 
+// ---- voxel-grid downsampling: the frame both paths share, and the host path ----
+void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f)
+{
+	if (!xyz || n == 0) throw std::invalid_argument("goicp voxel: empty cloud");
+	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp voxel: cloud too large");
+	if (!(voxel > 0.f) || !std::isfinite(voxel)) throw std::invalid_argument("goicp voxel: the voxel size must be positive and finite");
+	float mn[3] = {INFINITY, INFINITY, INFINITY};
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) {
+			const float x = xyz[3 * i + k];
+			if (!std::isfinite(x)) throw std::invalid_argument("goicp voxel: non-finite coordinate in the cloud");
+			mn[k] = std::min(mn[k], x);
+		}
+	float E = 0.f;
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) E = std::max(E, xyz[3 * i + k] - mn[k]);
+	if (!(E / voxel < 2097152.f)) throw std::invalid_argument("goicp voxel: the grid needs more than 21 bits per axis (extent / voxel >= 2^21)");
+	for (int k = 0; k < 3; k++) f->mn[k] = mn[k];
+	f->E = E;
+	f->voxel = voxel;
+	f->s = 0;
+	if (E > 0.f) {
+		int e = 0, b = 0;
+		std::frexp(E, &e);                             // E < 2^e
+		for (size_t v = n; v; v >>= 1) b++;            // n < 2^b
+		f->s = 62 - e - b;                             // every term < 2^(62-b), fewer than 2^b of them: the sums stay below 2^62
+	}
+	int cbits = 0;
+	for (int c = (int)std::floor(E / voxel); c; c >>= 1) cbits++;
+	f->key_bits = 42 + std::max(cbits, 1);
+}
+
+void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m_out)
+{
+	VoxelFrame f;
+	voxel_frame(xyz, n, voxel, &f);
+	std::vector<std::pair<uint64_t, int32_t>> ki(n);
+	for (size_t i = 0; i < n; i++) {
+		uint64_t key = 0;
+		for (int k = 0; k < 3; k++) key |= (uint64_t)(int)std::floor((xyz[3 * i + k] - f.mn[k]) / voxel) << (21 * k);
+		ki[i] = {key, (int32_t)i};
+	}
+	std::sort(ki.begin(), ki.end());                   // (key, id): the ids of a cell ascend, as after a stable sort
+	size_t m = 0;
+	for (size_t a = 0; a < n;) {
+		size_t b = a;
+		long long S[3] = {0, 0, 0};
+		for (; b < n && ki[b].first == ki[a].first; b++) {
+			const float* p = xyz + 3 * (size_t)ki[b].second;
+			for (int k = 0; k < 3; k++) S[k] += std::llrint(std::ldexp((double)(p[k] - f.mn[k]), f.s));
+		}
+		const size_t cnt = b - a;
+		const float* p = xyz + 3 * (size_t)ki[a].second;
+		for (int k = 0; k < 3; k++)
+			out_xyz[3 * m + k] = cnt == 1 ? p[k] : (float)((double)f.mn[k] + std::ldexp((double)S[k] / (double)cnt, -f.s));
+		if (out_count) out_count[m] = (int32_t)cnt;
+		m++;
+		a = b;
+	}
+	*m_out = m;
+}
+
 }  // namespace goicp

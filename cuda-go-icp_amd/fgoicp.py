@@ -70,6 +70,19 @@ def source_order(xyz, mode=2):
     return perm
 
 
+def _voxel_call(fn, xyz, voxel):
+    xyz = _f32(xyz, (-1, 3))
+    out, cnt, m = np.empty((len(xyz), 3), np.float32), np.empty(len(xyz), np.int32), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), len(xyz), float(voxel), _fptr(out), cnt.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(m)))
+    return out[:m.value].copy(), cnt[:m.value].copy()
+
+
+def voxel_downsample(xyz, voxel):
+    """goicp_voxel_downsample_host (host only): one centroid per occupied cell of a grid of pitch `voxel`, cells in ascending key order ->
+    (cloud (m, 3) float32, counts (m,) int32).  Registration.voxel_downsample and set_source(voxel=) give the same bits on the device."""
+    return _voxel_call(B.load_library().goicp_voxel_downsample_host, xyz, voxel)
+
+
 class Config:
     """Config(toml_filepath): same keys, defaults and clamps as the reference; raises on parse error."""
 
@@ -223,15 +236,40 @@ class Registration:
                 raise
 
     # ---- source swap (goicp_set_source) ----
-    def set_source(self, pcs):
+    @property
+    def pcs(self):
+        """the source cloud in the handle's "original order"; after set_source(voxel=) the reduced cloud, formed on first use (the host
+        function's output is the device's, bit for bit, so a scan stream that never asks never pays for a host reduction)"""
+        if self._pcs is None:
+            self._pcs = voxel_downsample(*self._pcs_raw)[0]
+            self._pcs_raw = None
+        return self._pcs
+
+    @pcs.setter
+    def pcs(self, value):
+        self._pcs, self._pcs_raw = value, None
+
+    def set_source(self, pcs, voxel=None):
         """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
-        options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit."""
+        options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit.
+        voxel: goicp_set_source_voxel -- the cloud is reduced to one centroid per voxel on the device first, and the handle answers as after
+        set_source(voxel_downsample(pcs, voxel)[0]); self.ns is the number of points kept, self.pcs the reduced cloud."""
         pcs = _f32(pcs, (-1, 3))
-        B.check(self._lib.goicp_set_source(self.handle, _fptr(pcs), len(pcs)))
-        self.pcs, self.ns = pcs, len(pcs)
+        if voxel is None:
+            B.check(self._lib.goicp_set_source(self.handle, _fptr(pcs), len(pcs)))
+            self.pcs, self.ns = pcs, len(pcs)
+        else:
+            kept = C.c_size_t(0)
+            B.check(self._lib.goicp_set_source_voxel(self.handle, _fptr(pcs), len(pcs), float(voxel), C.byref(kept)))
+            self._pcs, self._pcs_raw, self.ns = None, (pcs, float(voxel)), kept.value
         thr, inl = C.c_float(), C.c_int32()
         B.check(self._lib.goicp_thresholds(self.handle, C.byref(thr), C.byref(inl)))
         self.sse_threshold, self.inliers = np.float32(thr.value), inl.value
+
+    def voxel_downsample(self, xyz, voxel):
+        """goicp_voxel_downsample: the module-level voxel_downsample on the device (the handle lends its device and stream, its state is
+        untouched) -> (cloud (m, 3) float32, counts (m,) int32), the same bits"""
+        return _voxel_call(lambda *a: self._lib.goicp_voxel_downsample(self.handle, *a), xyz, voxel)
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""
@@ -496,9 +534,9 @@ class FastGoICP:
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
 
-    def set_source(self, pcs):
+    def set_source(self, pcs, voxel=None):
         """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
-        self.registration.set_source(pcs)
+        self.registration.set_source(pcs, voxel)
         self.sse_threshold = self.registration.sse_threshold
 
     def run(self):

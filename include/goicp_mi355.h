@@ -224,6 +224,30 @@ int goicp_set_source(goicp_handle h, const float* source_xyz, size_t n_source);
  * GOICP_ERR_INVALID: NULL arguments, n == 0 or above goicp_create's limit, a mode outside 0..2.
  */
 int goicp_source_order_host(const float* xyz, size_t n, int32_t mode, int32_t* perm);
+/*
+ * Voxel-grid downsampling (PCL's VoxelGrid, Open3D's voxel_down_sample): one centroid per occupied cell of a grid of pitch `voxel`.
+ * All three functions produce the same bits.  Float arithmetic is IEEE single precision, nothing fused:
+ *   frame   mn_k = min_i x_ik, d_ik = x_ik - mn_k, E = max_ik d_ik;
+ *   cell    c_ik = (int)floorf(d_ik / voxel); key = c_x | c_y << 21 | c_z << 42 (refused when E / voxel >= 2^21);
+ *   sums    exact integers: the term of a coordinate is llrint(ldexp((double)d, s)), s = 62 - e - b with E < 2^e (frexp) and b the bit length
+ *           of n (s = 0 when E == 0), so every per-cell sum S_k stays below 2^62 and the order of addition cannot matter;
+ *   output  the m occupied cells in ascending key order; a cell of one point returns that point's own bits, any other cell
+ *           (float)((double)mn_k + ldexp((double)S_k / (double)count, -s)).  Each centroid is within 2^-23 (E + max|x|) of the cell's fp64
+ *           centroid.
+ * out_xyz holds n x 3 floats (the first m x 3 are written), out_count (may be NULL) n ints (points per cell), *m the number of cells.
+ * goicp_voxel_downsample_host runs on the host alone (no handle, no GPU).  goicp_voxel_downsample runs the reduction on the device: the
+ * handle lends its device and stream, its state is untouched.
+ * goicp_set_source_voxel reduces on the device and swaps: the raw cloud is uploaded once, only the reduced cloud and the permutation come
+ * back.  Afterwards the handle answers every entry point bit for bit as after goicp_set_source(h, D, m) with D the output of
+ * goicp_voxel_downsample_host -- D's order is the "original order" of goicp_transform_source and goicp_eval_correspondences -- and
+ * everything goicp_set_source keeps and resets carries over.  *n_kept (may be NULL) = m.  Sharded use: every rank calls it with the same
+ * cloud and voxel.
+ * GOICP_ERR_INVALID, the handle untouched: NULL arguments, n == 0 or above goicp_create's limit, a non-finite coordinate, a voxel that is
+ * <= 0, NaN or infinite, E / voxel >= 2^21, and for the two handle forms any call while a registration runs.
+ */
+int goicp_voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
+int goicp_voxel_downsample(goicp_handle h, const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
+int goicp_set_source_voxel(goicp_handle h, const float* xyz, size_t n, float voxel, size_t* n_kept);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

@@ -213,6 +213,17 @@ public:
 		check(goicp_set_source(h_, reinterpret_cast<const float*>(pcs.data()), ns));
 		ns_ = ns;
 	}
+	// the same behind a voxel grid (goicp_set_source_voxel): the cloud is reduced to one centroid per occupied cell of pitch `voxel` on the
+	// device, then swapped in; returns the number of points kept, which is the registration's source size from here on
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, size_t ns, float voxel)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		size_t kept = 0;
+		check(goicp_set_source_voxel(h_, reinterpret_cast<const float*>(pcs.data()), ns, voxel, &kept));
+		ns_ = kept;
+		return kept;
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
@@ -355,6 +366,14 @@ public:
 	{
 		registration.set_source(pcs, pcs.size());
 		sync();
+	}
+	// ... behind a voxel grid of pitch `voxel`; returns the number of points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, float voxel)
+	{
+		const size_t kept = registration.set_source(pcs, pcs.size(), voxel);
+		sync();
+		return kept;
 	}
 	void cancel() { goicp_cancel(registration.handle()); }
 	float get_best_error() const { return best_sse; }       // fgoicp.hpp:34; read under `mtx` like the other members
