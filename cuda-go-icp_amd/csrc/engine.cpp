@@ -32,27 +32,10 @@ constexpr double kPI = 3.1415926536;
 constexpr double kSQRT3 = 1.732050808;
 constexpr int kMaxRotLevel = 20;
 
-void hip_check(hipError_t e, const char* what)
-{
-	if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x) hip_check((x), #x)
-
 double now_ms()
 {
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-// device allocation that frees itself on every exit path (temporaries of init / operators)
-template <class T> struct DevBuf {
-	T* p = nullptr;
-	DevBuf() = default;
-	explicit DevBuf(size_t n) { HIPCHK(hipMalloc(&p, sizeof(T) * (n ? n : 1))); }
-	~DevBuf() { hipFree(p); }
-	DevBuf(const DevBuf&) = delete;
-	DevBuf& operator=(const DevBuf&) = delete;
-	T* release() { T* q = p; p = nullptr; return q; }
-};
 
 }  // namespace
 
@@ -68,15 +51,11 @@ Engine::DeviceGuard::~DeviceGuard()
 
 void* Engine::scratch_bytes(size_t bytes)
 {
-	if (bytes > cap_opscratch_) {
+	if (bytes > d_opscratch_.size()) {
 		HIPCHK(hipStreamSynchronize(stream_));
-		hipFree(d_opscratch_);
-		d_opscratch_ = nullptr; cap_opscratch_ = 0;
-		const size_t cap = std::max(bytes, (size_t)1 << 16);
-		HIPCHK(hipMalloc(&d_opscratch_, cap));
-		cap_opscratch_ = cap;
+		d_opscratch_.alloc(std::max(bytes, (size_t)1 << 16));
 	}
-	return d_opscratch_;
+	return d_opscratch_.get();
 }
 
 struct Engine::InnerSearch {
@@ -99,15 +78,12 @@ float Engine::rot_coeff(int level) const
 	return rot_coeff_[level < kMaxRotLevel ? level : kMaxRotLevel - 1];
 }
 
-Engine::Engine(const Params& p, const float* target, size_t M, const float* source, size_t N)
-    : p_(p), M_(M), N_(N)
+// init runs in a DELEGATING constructor: the object counts as constructed once the private constructor returns, so when init throws,
+// ~Engine runs before the members go -- a half-built engine is released on its own device like a whole one
+Engine::Engine(const Params& p, size_t M, size_t N) : p_(p), M_(M), N_(N) {}
+Engine::Engine(const Params& p, const float* target, size_t M, const float* source, size_t N) : Engine(p, M, N)
 {
-	try {
-		init(target, M, source, N);
-	} catch (...) {
-		release();      // a half-built engine must not leak device memory
-		throw;
-	}
+	init(target, M, source, N);
 }
 
 void Engine::init(const float* target, size_t M, const float* source, size_t N)
@@ -140,15 +116,15 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 	if (p_.stream_priority > 0) {
 		int least = 0, greatest = 0;
 		HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-		HIPCHK(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, greatest));
+		stream_.create(greatest);
 	} else
-		HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-	HIPCHK(hipEventCreate(&ev0_));
-	HIPCHK(hipEventCreate(&ev1_));
+		stream_.create();
+	ev0_.create();
+	ev1_.create();
 	// lane 1's stream is made here, not in a timed registration (a stream costs ~2 ms to create); lanes 2.. make theirs on first use
 	lane_stream_[0] = stream_;
-	HIPCHK(hipStreamCreateWithFlags(&lane_stream_[1], hipStreamNonBlocking));
-	HIPCHK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
+	make_lane_stream(1);
+	ev_fork_.create(hipEventDisableTiming);
 	lanes_ = p_.lanes; lane_min_searches_ = std::max(2, p_.lane_min_searches);
 
 	h_target_.assign(target, target + 3 * M);
@@ -247,33 +223,32 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		double t0 = now_ms();
 		const size_t V = dt_.V, nlin = V * V * V;
 		const size_t nout = dt_.layout ? (size_t)dt_.VB * dt_.VB * dt_.VB * 64 : nlin;
-		DevBuf<float> model_buf(3 * M_);
-		DevBuf<int32_t> work_buf(nlin);
-		float* d_model = model_buf.p;
-		int32_t* d_work = work_buf.p;
-		HIPCHK(hipMemcpyAsync(d_model, target, sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
+		Buf<float> model_buf(3 * M_);
+		Buf<int32_t> work_buf;
+		float* d_model = model_buf;
+		d_dt_.alloc(nout);
 		if (dt_.layout) {
-			HIPCHK(hipMalloc(&d_dt_, sizeof(float) * nout));
+			work_buf.alloc(nlin);
 			HIPCHK(hipMemsetAsync(d_dt_, 0, sizeof(float) * nout, stream_));
-		} else {
-			d_dt_ = reinterpret_cast<float*>(work_buf.release());   // the linear grid is built in place: the engine owns it from here
 		}
+		int32_t* d_work = dt_.layout ? work_buf.get() : reinterpret_cast<int32_t*>(d_dt_.get());   // the linear grid is built in place
+		HIPCHK(hipMemcpyAsync(d_model, target, sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
 		dt_.grid = d_dt_;
 		{   // table of the out-of-grid extension term, same float sqrt + double divide as the kernel's fallback
 			const int n = 16384;
 			std::vector<double> tab(n);
 			for (int i = 0; i < n; i++) tab[i] = (double)std::sqrt((float)i) / dt_.scale;
-			HIPCHK(hipMalloc(&d_overshoot_, sizeof(double) * n));
+			d_overshoot_.alloc(n);
 			HIPCHK(hipMemcpyAsync(d_overshoot_, tab.data(), sizeof(double) * n, hipMemcpyHostToDevice, stream_));
 			HIPCHK(hipStreamSynchronize(stream_));
 			dt_.overshoot = d_overshoot_; dt_.n_overshoot = n;
 		}
 		HIPCHK(launch_dt_build(d_model, (int)M_, dt_, d_work, d_dt_, stream_));
 		if (p_.bounds_fp16 && dt_.layout == 1) {
-			HIPCHK(hipMalloc(&d_dt16_, sizeof(unsigned short) * nout));
+			d_dt16_.alloc(nout);
 			HIPCHK(launch_dt_to_half(d_dt_, d_dt16_, nout, stream_));
 			dt16_ = dt_;
-			dt16_.grid = static_cast<const float*>(d_dt16_);
+			dt16_.grid = reinterpret_cast<const float*>(d_dt16_.get());
 			dt16_.layout = 2;
 		}
 		HIPCHK(hipStreamSynchronize(stream_));
@@ -289,10 +264,10 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 			KdHost kh;
 			build_kdtree(target, (int)M_, kLeafSlots, &kh);
 			for (int l = 0; l < kh.K; l++) {
-				HIPCHK(hipMalloc(&d_kd_boxes_[l], sizeof(float) * kh.boxes[l].size()));
+				d_kd_boxes_[l].alloc(kh.boxes[l].size());
 				HIPCHK(hipMemcpy(d_kd_boxes_[l], kh.boxes[l].data(), sizeof(float) * kh.boxes[l].size(), hipMemcpyHostToDevice));
 			}
-			HIPCHK(hipMalloc(&d_kd_pts_, sizeof(float4) * kh.pts.size()));
+			d_kd_pts_.alloc(kh.pts.size());
 			HIPCHK(hipMemcpy(d_kd_pts_, kh.pts.data(), sizeof(float4) * kh.pts.size(), hipMemcpyHostToDevice));
 			kd_.K = kh.K;
 			kd_slots_ = kh.pts.size();
@@ -301,16 +276,18 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 			int K = 1;
 			while (K < kMaxLevels && (long long)kLeafSlots * (1LL << (6 * K)) < (long long)M_) K++;
 			if ((long long)kLeafSlots * (1LL << (6 * K)) < (long long)M_) throw std::invalid_argument("goicp: target cloud too large for the k-d tree");
-			DevBuf<float> model_buf(3 * M_);
-			float* d_model = model_buf.p;
+			Buf<float> model_buf(3 * M_);
+			float* d_model = model_buf;
 			HIPCHK(hipMemcpyAsync(d_model, target, sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
-			for (int l = 0; l < K; l++) HIPCHK(hipMalloc(&d_kd_boxes_[l], sizeof(float) * 384 * ((size_t)1 << (6 * l))));
-			HIPCHK(hipMalloc(&d_kd_pts_, sizeof(float4) * kLeafSlots * ((size_t)1 << (6 * K))));
+			for (int l = 0; l < K; l++) d_kd_boxes_[l].alloc(384 * ((size_t)1 << (6 * l)));
+			d_kd_pts_.alloc(kLeafSlots * ((size_t)1 << (6 * K)));
 			float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
 			for (size_t i = 0; i < M_; i++)
 				for (int k = 0; k < 3; k++) { mn[k] = std::min(mn[k], target[3 * i + k]); mx[k] = std::max(mx[k], target[3 * i + k]); }
 			const float ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]});
-			HIPCHK(launch_kd_build(d_model, (int)M_, K, mn, ext, d_kd_boxes_, d_kd_pts_, stream_));
+			float* boxes[kMaxLevels];
+			for (int l = 0; l < kMaxLevels; l++) boxes[l] = d_kd_boxes_[l];
+			HIPCHK(launch_kd_build(d_model, (int)M_, K, mn, ext, boxes, d_kd_pts_, stream_));
 			kd_.K = K;
 			kd_slots_ = (size_t)kLeafSlots * ((size_t)1 << (6 * K));
 		}
@@ -324,21 +301,21 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		const size_t V = dt_.V, nlin = V * V * V;
 		const size_t nout = dt_.layout ? (size_t)dt_.VB * dt_.VB * dt_.VB * 64 : nlin;
 		const int nslots = (int)kd_slots_;                  // the slots that exist (the root group of the hierarchy is sparse: 16 x 2^D, not 16 x 64^K)
-		DevBuf<int32_t> wd(nlin), wi(nlin);
-		HIPCHK(hipMalloc(&d_nn_ids_, sizeof(int32_t) * nout));
+		Buf<int32_t> wd(nlin), wi(nlin);
+		d_nn_ids_.alloc(nout);
 		HIPCHK(hipMemsetAsync(d_nn_ids_, 0, sizeof(int32_t) * nout, stream_));          // brick padding beyond V: slot 0, never addressed
-		HIPCHK(launch_nn_seed_build(d_kd_pts_, nslots, dt_, wd.p, wi.p, d_nn_ids_, stream_));
+		HIPCHK(launch_nn_seed_build(d_kd_pts_, nslots, dt_, wd, wi, d_nn_ids_, stream_));
 		HIPCHK(hipStreamSynchronize(stream_));
 		dt_.nn_ids = d_nn_ids_;
 		lap("nearest-point table");
 	}
-	HIPCHK(hipMalloc(&d_icp_state_, sizeof(IcpState)));
-	HIPCHK(hipMalloc(&d_icp_acc_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpAcc));
+	d_icp_state_.alloc(1);
+	d_icp_acc_.alloc((size_t)kIcpAccReplicas * kIcpAcc);
 	HIPCHK(hipMemsetAsync(d_icp_acc_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpAcc, stream_));
 	for (size_t i = 0; i < 3 * M_; i++) target_abs_max_ = std::max(target_abs_max_, std::fabs(target[i]));
-	HIPCHK(hipMalloc(&d_icp_ticket_, 64));
+	d_icp_ticket_.alloc(64 / sizeof(int));
 	HIPCHK(hipMemset(d_icp_ticket_, 0, 64));
-	HIPCHK(hipHostMalloc(&h_icp_state_, sizeof(IcpState) * 3));      // [0] the state as uploaded / as last fetched, [1], [2] icp_run's two fetch slots
+	h_icp_state_.alloc(3);      // [0] the state as uploaded / as last fetched, [1], [2] icp_run's two fetch slots
 	ensure_batch(4096, 64);
 	if (p_.device_queues && p_.trans_batch > 1 && p_.wide_children) {
 		// the device-resident inner-BnB queues, sized for a full round of the outer search, and their pinned mirror touched
@@ -346,8 +323,8 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		ensure_queues(flow_mode() ? kFlowSearches : 1);
 		if (flow_mode()) {
 			ensure_batch(1, kFlowSearches / 2);
-			HIPCHK(hipHostMalloc(&h_qinit_, sizeof(QInit) * kFlowSearches));
-			HIPCHK(hipMalloc(&d_qinit_, sizeof(QInit) * kFlowSearches));
+			h_qinit_.alloc(kFlowSearches);
+			d_qinit_.alloc(kFlowSearches);
 			std::memset(h_qinit_, 0, sizeof(QInit) * kFlowSearches);
 		}
 		std::memset(ql_[0].h_search, 0, sizeof(QSearch) * ql_[0].cap);
@@ -433,12 +410,7 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 	inliers_ = (int)((float)N_ * (1 - p_.trim_fraction));    // jly_goicp.cpp:201
 	if (inliers_ < 1) inliers_ = 1;
 	sse_thresh_ = p_.mse_threshold * (float)inliers_;         // jly_goicp.cpp:208
-	if (N_ > cap_src_) {
-		hipFree(d_src_);
-		d_src_ = nullptr; cap_src_ = 0;
-		HIPCHK(hipMalloc(&d_src_, sizeof(float4) * N_));
-		cap_src_ = N_;
-	}
+	d_src_.reserve(N_);
 	std::vector<int32_t> perm(N_);
 	const bool on_device = device_order && p_.morton_sort >= 1;
 	if (on_device) {
@@ -447,15 +419,15 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 		const int mode = p_.morton_sort == 1 ? 1 : 2;
 		float mn[3] = {0, 0, 0}, ext = 1.f;
 		if (mode == 1) source_morton_frame(source, N_, mn, &ext);
-		DevBuf<float> d_up(d_xyz_ready ? 0 : 3 * N_);
-		DevBuf<int32_t> d_perm(N_);
-		if (!d_xyz_ready) HIPCHK(hipMemcpyAsync(d_up.p, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
-		const float* d_xyz = d_xyz_ready ? d_xyz_ready : d_up.p;
+		Buf<float> d_up(d_xyz_ready ? 0 : 3 * N_);
+		Buf<int32_t> d_perm(N_);
+		if (!d_xyz_ready) HIPCHK(hipMemcpyAsync(d_up, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+		const float* d_xyz = d_xyz_ready ? d_xyz_ready : d_up.get();
 		HIPCHK(hipEventRecord(ev0_, stream_));
-		HIPCHK(launch_source_order(d_xyz, (int)N_, mode, mn, ext, d_perm.p, stream_));
+		HIPCHK(launch_source_order(d_xyz, (int)N_, mode, mn, ext, d_perm, stream_));
 		HIPCHK(hipEventRecord(ev1_, stream_));
-		HIPCHK(launch_source_gather(d_xyz, d_perm.p, (int)N_, d_src_, stream_));
-		HIPCHK(hipMemcpyAsync(perm.data(), d_perm.p, sizeof(int32_t) * N_, hipMemcpyDeviceToHost, stream_));
+		HIPCHK(launch_source_gather(d_xyz, d_perm, (int)N_, d_src_, stream_));
+		HIPCHK(hipMemcpyAsync(perm.data(), d_perm, sizeof(int32_t) * N_, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipStreamSynchronize(stream_));
 		float ms = 0.f;
 		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
@@ -480,27 +452,10 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 	src_crad_ = -1.0;
 	// ---- the N-sized buffers (grow-only: a smaller cloud uses the front of what is there, every kernel is bounded by N) ----
 	const size_t partials = std::max(icp_partials_floats((int)N_), (size_t)icp_trim_blocks((int)N_) * kIcpAcc);
-	if (partials > cap_partials_) {
-		hipFree(d_icp_partials_);
-		d_icp_partials_ = nullptr; cap_partials_ = 0;
-		HIPCHK(hipMalloc(&d_icp_partials_, sizeof(float) * partials));
-		cap_partials_ = partials;
-	}
-	if (inliers_ < (int)N_ && N_ > cap_trim_) {
-		hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
-		d_nn_d2_ = nullptr; d_nn_slot_ = nullptr; d_include_ = nullptr; cap_trim_ = 0;
-		HIPCHK(hipMalloc(&d_nn_d2_, sizeof(float) * N_));
-		HIPCHK(hipMalloc(&d_nn_slot_, sizeof(int) * N_));
-		HIPCHK(hipMalloc(&d_include_, N_));
-		cap_trim_ = N_;
-	}
+	d_icp_partials_.reserve(partials);
+	if (inliers_ < (int)N_) { d_nn_d2_.reserve(N_); d_nn_slot_.reserve(N_); d_include_.reserve(N_); }
 	if (p_.icp_nn_cache) {
-		if (N_ > cap_cache_) {
-			hipFree(d_nn_cache_);
-			d_nn_cache_ = nullptr; cap_cache_ = 0;
-			HIPCHK(hipMalloc(&d_nn_cache_, sizeof(float4) * 2 * N_));
-			cap_cache_ = N_;
-		}
+		d_nn_cache_.reserve(2 * N_);
 		HIPCHK(hipMemsetAsync(d_nn_cache_, 0, sizeof(float4) * 2 * N_, stream_));      // sqrt(best2_ref) = 0: the first pass walks
 	}
 }
@@ -563,13 +518,13 @@ void Engine::voxel_downsample(const float* xyz, size_t n, float voxel, float* ou
 	voxel_frame(xyz, n, voxel, &f);
 	if (registering_.load()) throw std::invalid_argument("goicp_voxel_downsample: not while a registration runs");
 	DeviceGuard guard(dev_);
-	DevBuf<float> d_xyz(3 * n), d_out(3 * n);
-	DevBuf<int32_t> d_cnt(out_count ? n : 0);
+	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<int32_t> d_cnt(out_count ? n : 0);
 	int m = 0;
-	HIPCHK(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	HIPCHK(launch_voxel_downsample(d_xyz.p, (int)n, f, d_out.p, out_count ? d_cnt.p : nullptr, &m, stream_));
-	HIPCHK(hipMemcpyAsync(out_xyz, d_out.p, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-	if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_cnt.p, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_voxel_downsample(d_xyz, (int)n, f, d_out, out_count ? d_cnt.get() : nullptr, &m, stream_));
+	HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_cnt, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 	*m_out = (size_t)m;
 	if (p_.verbose) std::fprintf(stderr, "[goicp] voxel_downsample: %zu -> %d points\n", n, m);
@@ -586,17 +541,17 @@ void Engine::set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n
 	TraceRange tr("goicp:set_source_voxel");
 	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
 	// the raw cloud goes up once; the reduced cloud stays on the device for the ordering stage, and comes back for the host mirror
-	DevBuf<float> d_raw(3 * n), d_red(3 * n);
+	Buf<float> d_raw(3 * n), d_red(3 * n);
 	int m = 0;
-	HIPCHK(hipMemcpyAsync(d_raw.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	HIPCHK(launch_voxel_downsample(d_raw.p, (int)n, f, d_red.p, nullptr, &m, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_voxel_downsample(d_raw, (int)n, f, d_red, nullptr, &m, stream_, ev0_, ev1_));
 	std::vector<float> red(3 * (size_t)m);
-	HIPCHK(hipMemcpyAsync(red.data(), d_red.p, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(red.data(), d_red, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 	float ms = 0.f;
 	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
 	voxel_ms_ = ms;
-	load_source(red.data(), (size_t)m, true, d_red.p);
+	load_source(red.data(), (size_t)m, true, d_red);
 	finish_source_swap();
 	if (n_kept) *n_kept = (size_t)m;
 	if (p_.verbose)
@@ -613,60 +568,30 @@ void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* p
 	DeviceGuard guard(dev_);
 	float mn[3] = {0, 0, 0}, ext = 1.f;
 	if (mode == 1) source_morton_frame(xyz, n, mn, &ext);
-	DevBuf<float> d_xyz(3 * n);
-	DevBuf<int32_t> d_perm(n);
-	HIPCHK(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	HIPCHK(launch_source_order(d_xyz.p, (int)n, mode, mn, ext, d_perm.p, stream_));
-	HIPCHK(hipMemcpyAsync(perm, d_perm.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+	Buf<float> d_xyz(3 * n);
+	Buf<int32_t> d_perm(n);
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_source_order(d_xyz, (int)n, mode, mn, ext, d_perm, stream_));
+	HIPCHK(hipMemcpyAsync(perm, d_perm, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 }
 
-Engine::~Engine() { release(); }
-
-void Engine::release()
+// The members release themselves; what is left here is the order: the engine's device current, nothing in flight on its streams, then the
+// members in reverse order of declaration (engine.hpp: buffers and events, the streams, and last restore_device_, which puts the
+// caller's device back).  Also the path of an init that threw (see the constructor)
+Engine::~Engine()
 {
+	if (!stream_) return;      // init threw before anything was created
 	int prev = -1;
-	if (stream_ && hipGetDevice(&prev) == hipSuccess && prev != dev_) hipSetDevice(dev_); else prev = -1;
-	if (stream_) hipStreamSynchronize(stream_);
-	hipFree(d_opscratch_); d_opscratch_ = nullptr; cap_opscratch_ = 0;
-	for (QLane& L : ql_) free_lane(L);
-	hipFree(d_qinit_); hipHostFree(h_qinit_); d_qinit_ = nullptr; h_qinit_ = nullptr;
-	hipFree(d_src_); hipFree(d_dt_); hipFree(d_overshoot_); hipFree(d_dt16_); d_dt16_ = nullptr;
-	hipFree(d_nn_ids_); d_nn_ids_ = nullptr;
-	for (int l = 0; l < kMaxLevels; l++) hipFree(d_kd_boxes_[l]);
-	hipFree(d_kd_pts_);
-	hipFree(d_cubes_); hipFree(d_rots_); hipFree(d_ub_); hipFree(d_lb_); hipFree(d_scratch_);
-	hipHostFree(h_cubes_); hipHostFree(h_rots_); hipHostFree(h_ub_); hipHostFree(h_lb_);
-	hipFree(d_icp_acc_); d_icp_acc_ = nullptr;
-	hipFree(d_icp_acc_opt_); d_icp_acc_opt_ = nullptr;
-	hipFree(d_info_acc_); d_info_acc_ = nullptr; hipFree(d_info_args_); d_info_args_ = nullptr; info_cap_ = 0;
-	hipFree(d_normals_); d_normals_ = nullptr; normals_k_ = 0;
-	hipFree(d_icp_x_); d_icp_x_ = nullptr; hipHostFree(h_icp_x_); h_icp_x_ = nullptr;
-	hipFree(d_icp_partials_); hipFree(d_icp_state_); hipHostFree(h_icp_state_); hipFree(d_icp_ticket_); d_icp_ticket_ = nullptr; hipFree(d_nn_cache_); d_nn_cache_ = nullptr;
-	hipFree(d_nn_d2_); hipFree(d_nn_slot_); hipFree(d_include_);
-	free_icp_batch();
-	for (Stage& st : stage_) {
-		hipFree(st.d_parents); hipFree(st.d_ub);
-		hipHostFree(st.h_parents); hipHostFree(st.h_ub);
-		if (st.ev) hipEventDestroy(st.ev);
-		st = Stage{};
-	}
-	if (ev0_) hipEventDestroy(ev0_);
-	if (ev1_) hipEventDestroy(ev1_);
-	for (int k = 1; k < kMaxLanes; k++) if (lane_stream_[k]) { hipStreamSynchronize(lane_stream_[k]); hipStreamDestroy(lane_stream_[k]); }
-	for (int k = 0; k < kMaxLanes; k++) lane_stream_[k] = nullptr;
-	if (ev_fork_) hipEventDestroy(ev_fork_);
-	ev_fork_ = nullptr;
-	if (stream_) hipStreamDestroy(stream_);
-	d_src_ = nullptr; d_dt_ = nullptr; d_overshoot_ = nullptr; d_kd_pts_ = nullptr;
-	cap_src_ = cap_trim_ = cap_cache_ = cap_partials_ = 0;
-	for (int l = 0; l < kMaxLevels; l++) d_kd_boxes_[l] = nullptr;
-	d_cubes_ = nullptr; d_rots_ = nullptr; d_ub_ = d_lb_ = d_scratch_ = nullptr;
-	h_cubes_ = nullptr; h_rots_ = nullptr; h_ub_ = h_lb_ = nullptr;
-	d_icp_partials_ = nullptr; d_icp_state_ = nullptr; h_icp_state_ = nullptr;
-	d_nn_d2_ = nullptr; d_nn_slot_ = nullptr; d_include_ = nullptr;
-	ev0_ = ev1_ = nullptr; stream_ = nullptr;
-	if (prev >= 0) hipSetDevice(prev);
+	if (hipGetDevice(&prev) == hipSuccess && prev != dev_) { hipSetDevice(dev_); restore_device_.prev = prev; }
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) hipStreamSynchronize(lane_stream_[k]);   // lane 0 is the engine's stream
+}
+Engine::RestoreDevice::~RestoreDevice() { if (prev >= 0) hipSetDevice(prev); }
+
+void Engine::make_lane_stream(int li)
+{
+	lane_own_[li].create();
+	lane_stream_[li] = lane_own_[li];
 }
 
 void Engine::ensure_batch(size_t B, size_t K)
@@ -674,36 +599,25 @@ void Engine::ensure_batch(size_t B, size_t K)
 	if (B > cap_cubes_) {
 		size_t cap = std::max<size_t>(B, cap_cubes_ * 2);
 		hipStreamSynchronize(stream_);
-		hipFree(d_cubes_); hipFree(d_ub_); hipFree(d_lb_);
-		hipHostFree(h_cubes_); hipHostFree(h_ub_); hipHostFree(h_lb_);
-		d_cubes_ = nullptr; d_ub_ = d_lb_ = nullptr; h_cubes_ = nullptr; h_ub_ = h_lb_ = nullptr; cap_cubes_ = 0;   // a throwing hipMalloc must not leave freed pointers behind
-		HIPCHK(hipMalloc(&d_cubes_, sizeof(CubeRec) * cap));
-		HIPCHK(hipMalloc(&d_ub_, sizeof(float) * cap));
-		HIPCHK(hipMalloc(&d_lb_, sizeof(float) * cap));
-		HIPCHK(hipHostMalloc(&h_cubes_, sizeof(CubeRec) * cap));
-		HIPCHK(hipHostMalloc(&h_ub_, sizeof(float) * cap));
-		HIPCHK(hipHostMalloc(&h_lb_, sizeof(float) * cap));
+		cap_cubes_ = 0;       // stays 0 when one of the six throws: the next call allocates all of them again
+		d_cubes_.alloc(cap); d_ub_.alloc(cap); d_lb_.alloc(cap);
+		h_cubes_.alloc(cap); h_ub_.alloc(cap); h_lb_.alloc(cap);
 		cap_cubes_ = cap;
 	}
 	if (K > cap_rots_) {
 		size_t cap = std::max<size_t>(K, cap_rots_ * 2);
 		hipStreamSynchronize(stream_);
-		hipFree(d_rots_); hipHostFree(h_rots_);
-		d_rots_ = nullptr; h_rots_ = nullptr; cap_rots_ = 0;
-		HIPCHK(hipMalloc(&d_rots_, sizeof(Rot9) * cap));
-		HIPCHK(hipHostMalloc(&h_rots_, sizeof(Rot9) * cap));
+		cap_rots_ = 0;
+		d_rots_.alloc(cap); h_rots_.alloc(cap);
 		cap_rots_ = cap;
 	}
 	size_t need = bounds_scratch_floats((int)std::max<size_t>(B, 1), (int)N_, nullptr, nullptr);
 	// the scratch need is not monotone in B (fewer cubes -> more point chunks): size for the worst case
 	size_t worst = (size_t)2 * kGroup * (8 * ((cap_cubes_ + kGroup - 1) / kGroup) + 4096);   // groups x (<= 8 + 2048/groups) chunks
 	need = std::max(need, worst);
-	if (need > cap_scratch_) {
+	if (need > d_scratch_.size()) {
 		hipStreamSynchronize(stream_);
-		hipFree(d_scratch_);
-		d_scratch_ = nullptr; cap_scratch_ = 0;
-		HIPCHK(hipMalloc(&d_scratch_, sizeof(float) * need));
-		cap_scratch_ = need;
+		d_scratch_.alloc(need);
 	}
 }
 
@@ -714,14 +628,11 @@ void Engine::eval_bounds_dev(const Rot9* d_rots, const CubeRec* d_cubes, int B, 
 {
 	DeviceGuard guard(dev_);
 	size_t need = bounds_scratch_floats(B, (int)N_, nullptr, nullptr);
-	if (need > cap_scratch_) {
+	if (need > d_scratch_.size()) {
 		// only the two streams that can still be using the old scratch, not the whole device
 		HIPCHK(hipStreamSynchronize(stream_));
 		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
-		hipFree(d_scratch_);
-		d_scratch_ = nullptr; cap_scratch_ = 0;
-		HIPCHK(hipMalloc(&d_scratch_, sizeof(float) * need));
-		cap_scratch_ = need;
+		d_scratch_.alloc(need);
 	}
 	if (inliers_ < (int)N_)
 		HIPCHK(launch_bounds_trim(d_src_, (int)N_, dt_, d_rots, d_cubes, d_parents, B, inliers_, d_ub, d_lb, s ? s : stream_));
@@ -742,13 +653,10 @@ void Engine::eval_bounds_dev_grouped(const Rot9* d_rots, int nrots, const CubeRe
 	if (inliers_ < (int)N_) { eval_bounds_dev(d_rots, d_cubes, B, d_ub, d_lb, s); return; }     // the trimmed kernel owns whole cubes: nothing to group
 	if (nrots < 1 || nrots > 16) throw std::invalid_argument("goicp: grouped bounds take 1..16 rotations");
 	const size_t need = bounds_scratch_floats(B, (int)N_, nullptr, nullptr);
-	if (need > cap_scratch_) {
+	if (need > d_scratch_.size()) {
 		HIPCHK(hipStreamSynchronize(stream_));
 		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
-		hipFree(d_scratch_);
-		d_scratch_ = nullptr; cap_scratch_ = 0;
-		HIPCHK(hipMalloc(&d_scratch_, sizeof(float) * need));
-		cap_scratch_ = need;
+		d_scratch_.alloc(need);
 	}
 	void* gs = scratch_bytes(bounds_grouped_scratch_bytes(B, nrots));
 	HIPCHK(launch_bounds_grouped(d_src_, (int)N_, bounds_dt(), d_rots, nrots, d_cubes, B, gs, d_scratch_, d_ub, d_lb, s ? s : stream_));
@@ -888,7 +796,7 @@ void Engine::ensure_icp_acc_opt()
 {
 	if (d_icp_acc_opt_) return;
 	DeviceGuard guard(dev_);
-	HIPCHK(hipMalloc(&d_icp_acc_opt_, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride));
+	d_icp_acc_opt_.alloc((size_t)kIcpAccReplicas * kIcpPlaneStride);
 	HIPCHK(hipMemsetAsync(d_icp_acc_opt_, 0, sizeof(unsigned long long) * kIcpAccReplicas * kIcpPlaneStride, stream_));
 }
 
@@ -898,12 +806,12 @@ void Engine::ensure_normals(int k)
 	if ((size_t)k > M_) throw std::invalid_argument("goicp_set_icp_options: normal_k exceeds the number of target points");
 	DeviceGuard guard(dev_);
 	const double t0 = now_ms();
-	if (!d_normals_) HIPCHK(hipMalloc(&d_normals_, sizeof(float4) * M_));
+	if (!d_normals_) d_normals_.alloc(M_);
 	ensure_icp_acc_opt();
 	HIPCHK(hipMemsetAsync(d_normals_, 0, sizeof(float4) * M_, stream_));
-	DevBuf<float> tgt(3 * M_);
-	HIPCHK(hipMemcpyAsync(tgt.p, h_target_.data(), sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
-	HIPCHK(launch_normal_build(tgt.p, (int)kd_slots_, k, model_centroid_, kd_, dt_, d_normals_, stream_));
+	Buf<float> tgt(3 * M_);
+	HIPCHK(hipMemcpyAsync(tgt, h_target_.data(), sizeof(float) * 3 * M_, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_normal_build(tgt, (int)kd_slots_, k, model_centroid_, kd_, dt_, d_normals_, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 	normals_k_ = k;
 	normal_build_ms_ = now_ms() - t0;
@@ -1119,12 +1027,10 @@ void information_decompose(const double info[36], double rank_tol, double eig[6]
 
 void Engine::ensure_pose_info(size_t K)
 {
-	if (K <= info_cap_) return;
-	hipFree(d_info_acc_); hipFree(d_info_args_);
-	d_info_acc_ = nullptr; d_info_args_ = nullptr; info_cap_ = 0;
-	HIPCHK(hipMalloc(&d_info_acc_, sizeof(unsigned long long) * kIcpBatchAccWords * K));
-	HIPCHK(hipMalloc(&d_info_args_, sizeof(PoseInfoArgs) * K));
-	info_cap_ = K;
+	if (K <= d_info_args_.size()) return;      // the second of the two: it holds K only when both do
+	d_info_args_.reset();
+	d_info_acc_.alloc((size_t)kIcpBatchAccWords * K);
+	d_info_args_.alloc(K);
 }
 
 void Engine::pose_information(size_t K, const float* R, const float* t, const goicp_pose_info_options* opt, goicp_pose_info* out, bool batch)
@@ -1393,22 +1299,15 @@ float Engine::icp_run(float R[9], float t[3], int max_iter, float err_diff, int*
 void Engine::ensure_icp_batch(size_t K)
 {
 	if (K <= batch_cap_) return;
-	free_icp_batch();
-	const size_t cap = std::max<size_t>(K, 16);
-	HIPCHK(hipMalloc(&d_batch_states_, sizeof(IcpState) * cap));
-	HIPCHK(hipHostMalloc(&h_batch_states_, sizeof(IcpState) * 3 * cap));
-	HIPCHK(hipMalloc(&d_batch_acc_, sizeof(unsigned long long) * kIcpBatchAccWords * cap));
-	HIPCHK(hipMemsetAsync(d_batch_acc_, 0, sizeof(unsigned long long) * kIcpBatchAccWords * cap, stream_));
-	HIPCHK(hipMalloc(&d_batch_active_, sizeof(int) * 2 * cap));
-	HIPCHK(hipHostMalloc(&h_batch_active_, sizeof(int) * 2 * cap));
-	batch_cap_ = cap;
-}
-
-void Engine::free_icp_batch()
-{
-	hipFree(d_batch_states_); hipHostFree(h_batch_states_); hipFree(d_batch_acc_); hipFree(d_batch_active_); hipHostFree(h_batch_active_);
-	d_batch_states_ = nullptr; h_batch_states_ = nullptr; d_batch_acc_ = nullptr; d_batch_active_ = nullptr; h_batch_active_ = nullptr;
 	batch_cap_ = 0;
+	const size_t cap = std::max<size_t>(K, 16);
+	d_batch_states_.alloc(cap);
+	h_batch_states_.alloc(3 * cap);
+	d_batch_acc_.alloc((size_t)kIcpBatchAccWords * cap);
+	HIPCHK(hipMemsetAsync(d_batch_acc_, 0, sizeof(unsigned long long) * kIcpBatchAccWords * cap, stream_));
+	d_batch_active_.alloc(2 * cap);
+	h_batch_active_.alloc(2 * cap);
+	batch_cap_ = cap;
 }
 
 // K icp_run loops in one device loop.  Every iteration is one batched pass over the active poses (grid: icp_blocks(N) x active) and one
@@ -1538,9 +1437,9 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 	// agreement: every rank must run the same loop on the same state
 	local([&] {
 		icp_state_init(R, t, err_diff, 1, 0);
-		if (sliced && !d_icp_x_) {
-			HIPCHK(hipMalloc(&d_icp_x_, sizeof(long long) * (kIcpExportWords + kIcpAcc)));
-			HIPCHK(hipHostMalloc(&h_icp_x_, sizeof(long long) * (kIcpExportWords + kIcpAcc)));
+		if (sliced && !h_icp_x_) {
+			d_icp_x_.alloc(kIcpExportWords + kIcpAcc);
+			h_icp_x_.alloc(kIcpExportWords + kIcpAcc);
 		}
 	});
 	{
@@ -1700,11 +1599,11 @@ double Engine::probe_gather(int mode, size_t window_bytes)
 
 void debug_kabsch(const float H[9], float R[9])
 {
-	DevBuf<float> buf(18);
-	HIPCHK(hipMemcpy(buf.p, H, sizeof(float) * 9, hipMemcpyHostToDevice));
-	HIPCHK(launch_kabsch_debug(buf.p, buf.p + 9, nullptr));
+	Buf<float> buf(18);
+	HIPCHK(hipMemcpy(buf.get(), H, sizeof(float) * 9, hipMemcpyHostToDevice));
+	HIPCHK(launch_kabsch_debug(buf.get(), buf.get() + 9, nullptr));
 	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(R, buf.p + 9, sizeof(float) * 9, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(R, buf.get() + 9, sizeof(float) * 9, hipMemcpyDeviceToHost));
 }
 
 void Engine::debug_bounds_tile(const float* rots9, const float* parents4, int nseg, int n, int level, int chunks, float* ub_tile, float* lb_tile,
@@ -1726,21 +1625,21 @@ void Engine::debug_bounds_tile(const float* rots9, const float* parents4, int ns
 	}
 	int g2 = 0, c2 = 0;
 	const size_t sc_direct = bounds_scratch_floats((int)B, (int)N_, &g2, &c2), sc_tile = G * (size_t)chunks * 2 * kGroup;
-	DevBuf<ParentRec> d_par(G);
-	DevBuf<Seg> d_seg((size_t)nseg);
-	DevBuf<Rot9> d_rot((size_t)nseg);
-	DevBuf<float> d_out(4 * B), d_sc(std::max(sc_direct, sc_tile) + 64);
-	DevBuf<unsigned> d_stats(2);
-	HIPCHK(hipMemcpyAsync(d_par.p, par.data(), sizeof(ParentRec) * G, hipMemcpyHostToDevice, stream_));
-	HIPCHK(hipMemcpyAsync(d_seg.p, segs.data(), sizeof(Seg) * (size_t)nseg, hipMemcpyHostToDevice, stream_));
-	HIPCHK(hipMemcpyAsync(d_rot.p, rots9, sizeof(Rot9) * (size_t)nseg, hipMemcpyHostToDevice, stream_));
-	HIPCHK(hipMemsetAsync(d_stats.p, 0, sizeof(unsigned) * 2, stream_));
-	float* t_ub = d_out.p; float* t_lb = d_out.p + B; float* r_ub = d_out.p + 2 * B; float* r_lb = d_out.p + 3 * B;
+	Buf<ParentRec> d_par(G);
+	Buf<Seg> d_seg((size_t)nseg);
+	Buf<Rot9> d_rot((size_t)nseg);
+	Buf<float> d_out(4 * B), d_sc(std::max(sc_direct, sc_tile) + 64);
+	Buf<unsigned> d_stats(2);
+	HIPCHK(hipMemcpyAsync(d_par.get(), par.data(), sizeof(ParentRec) * G, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(d_seg.get(), segs.data(), sizeof(Seg) * (size_t)nseg, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(d_rot.get(), rots9, sizeof(Rot9) * (size_t)nseg, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemsetAsync(d_stats.get(), 0, sizeof(unsigned) * 2, stream_));
+	float* t_ub = d_out.get(); float* t_lb = d_out.get() + B; float* r_ub = d_out.get() + 2 * B; float* r_lb = d_out.get() + 3 * B;
 	const int reps = 5;
 	for (int pass = 0; pass < 2; pass++) {              // pass 0 warms up (and counts the sub-patches), pass 1 is timed
 		HIPCHK(hipEventRecord(ev0_, stream_));
 		for (int r = 0; r < (pass ? reps : 1); r++)
-			HIPCHK(launch_bounds_tile(d_src_, (int)N_, dt_, d_rot.p, d_par.p, d_seg.p, nseg, n, chunks, d_sc.p, t_ub, t_lb, pass ? nullptr : d_stats.p, stream_));
+			HIPCHK(launch_bounds_tile(d_src_, (int)N_, dt_, d_rot.get(), d_par.get(), d_seg.get(), nseg, n, chunks, d_sc.get(), t_ub, t_lb, pass ? nullptr : d_stats.get(), stream_));
 		HIPCHK(hipEventRecord(ev1_, stream_));
 		HIPCHK(hipEventSynchronize(ev1_));
 		if (pass) { HIPCHK(hipEventElapsedTime(&ms[0], ev0_, ev1_)); ms[0] /= reps; }
@@ -1748,7 +1647,7 @@ void Engine::debug_bounds_tile(const float* rots9, const float* parents4, int ns
 	for (int pass = 0; pass < 2; pass++) {
 		HIPCHK(hipEventRecord(ev0_, stream_));
 		for (int r = 0; r < (pass ? reps : 1); r++)
-			HIPCHK(launch_bounds(d_src_, (int)N_, dt_, d_rot.p, nullptr, d_par.p, (int)B, d_sc.p, r_ub, r_lb, stream_));
+			HIPCHK(launch_bounds(d_src_, (int)N_, dt_, d_rot.get(), nullptr, d_par.get(), (int)B, d_sc.get(), r_ub, r_lb, stream_));
 		HIPCHK(hipEventRecord(ev1_, stream_));
 		HIPCHK(hipEventSynchronize(ev1_));
 		if (pass) { HIPCHK(hipEventElapsedTime(&ms[1], ev0_, ev1_)); ms[1] /= reps; }
@@ -1757,7 +1656,7 @@ void Engine::debug_bounds_tile(const float* rots9, const float* parents4, int ns
 	HIPCHK(hipMemcpy(lb_tile, t_lb, sizeof(float) * B, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(ub_direct, r_ub, sizeof(float) * B, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(lb_direct, r_lb, sizeof(float) * B, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(stats, d_stats.p, sizeof(unsigned) * 2, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(stats, d_stats.get(), sizeof(unsigned) * 2, hipMemcpyDeviceToHost));
 }
 
 void Engine::debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2])
@@ -1836,14 +1735,14 @@ void Engine::debug_select(const float* d2, size_t n, int num, int kernel, unsign
 	if (n < 1 || n > 0x7fffffffu || num < 1 || (size_t)num > n || kernel < 0 || kernel > 2 || (kernel == 1 && n > 32768))
 		throw std::invalid_argument("goicp: debug_select: bad n / num / kernel");
 	DeviceGuard guard(dev_);
-	DevBuf<float> dd(n);
-	DevBuf<unsigned char> di(n);
-	DevBuf<IcpState> ds(1);
-	HIPCHK(hipMemcpyAsync(dd.p, d2, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
-	HIPCHK(hipMemsetAsync(ds.p, 0, sizeof(IcpState), stream_));                 // converged = 0
-	HIPCHK(hipMemsetAsync(di.p, 0xff, n, stream_));                             // every flag is written by the kernel
-	HIPCHK(launch_icp_select(dd.p, (int)n, num, ds.p, di.p, kernel, stream_));
-	HIPCHK(hipMemcpyAsync(include, di.p, n, hipMemcpyDeviceToHost, stream_));
+	Buf<float> dd(n);
+	Buf<unsigned char> di(n);
+	Buf<IcpState> ds(1);
+	HIPCHK(hipMemcpyAsync(dd.get(), d2, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemsetAsync(ds.get(), 0, sizeof(IcpState), stream_));                 // converged = 0
+	HIPCHK(hipMemsetAsync(di.get(), 0xff, n, stream_));                             // every flag is written by the kernel
+	HIPCHK(launch_icp_select(dd.get(), (int)n, num, ds.get(), di.get(), kernel, stream_));
+	HIPCHK(hipMemcpyAsync(include, di.get(), n, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -1889,28 +1788,27 @@ void Engine::icp_step()
 void Engine::ensure_stage(int k, size_t B)
 {
 	Stage& st = stage_[k];
-	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+	if (!st.ev) st.ev.create(hipEventDisableTiming);
 	if (B <= st.cap) return;
 	const size_t cap = std::max<size_t>(B, st.cap * 2);
-	hipFree(st.d_parents); hipFree(st.d_ub);
-	hipHostFree(st.h_parents); hipHostFree(st.h_ub);
-	st.d_parents = nullptr; st.d_ub = nullptr; st.h_parents = nullptr; st.h_ub = nullptr; st.cap = 0;
-	HIPCHK(hipMalloc(&st.d_parents, sizeof(ParentRec) * (cap / 8 + 1)));
-	HIPCHK(hipMalloc(&st.d_ub, sizeof(float) * 2 * cap));                 // ub[B] | lb[B]: one copy back per round
-	HIPCHK(hipHostMalloc(&st.h_parents, sizeof(ParentRec) * (cap / 8 + 1)));
-	HIPCHK(hipHostMalloc(&st.h_ub, sizeof(float) * 2 * cap));
+	st.cap = 0;
+	st.d_parents.alloc(cap / 8 + 1);
+	st.d_ub.alloc(2 * cap);                 // ub[B] | lb[B]: one copy back per round
+	st.h_parents.alloc(cap / 8 + 1);
+	st.h_ub.alloc(2 * cap);
 	st.cap = cap;
 }
 
-void Engine::free_lane(QLane& L)
+void Engine::QLane::drop_sort()
 {
-	hipFree(L.d_search); hipHostFree(L.h_search); hipFree(L.d_nodes);
-	for (int k = 0; k < 2; k++) { hipFree(L.d_parents[k]); hipFree(L.d_psearch[k]); hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); }
-	if (L.ev_ctl) hipEventDestroy(L.ev_ctl);
-	hipFree(L.sort.keys); hipFree(L.sort.order); hipFree(L.sort.hist); hipFree(const_cast<float4*>(L.sort.cen));
-	hipFree(L.d_ub); hipFree(L.d_lb); hipFree(L.d_scratch); hipFree(L.d_ctl); hipHostFree(L.h_ctl);
-	hipFree(L.tile.ub); hipFree(L.tile.lb); hipFree(L.tile.scratch);
-	L = QLane{};          // the stream is the engine's (lane_stream_), not the lane's to destroy
+	sort_keys.reset(); sort_order.reset(); sort_hist.reset(); sort_cen.reset();
+	sort = QSort{};
+}
+void Engine::QLane::drop_tile()
+{
+	for (int k = 0; k < 2; k++) { tile_parents[k].reset(); tile_segs[k].reset(); }
+	tile_ub.reset(); tile_lb.reset(); tile_scratch.reset();
+	tile = QTile{};
 }
 
 // What a lane derives from the source cloud (ensure_lane; again after set_source): the sorted-round setup with the chunk centroids, the
@@ -1919,12 +1817,9 @@ void Engine::lane_source_buffers(QLane& L)
 {
 	const size_t max_groups = (size_t)L.list_cap;
 	HIPCHK(hipStreamSynchronize(L.stream));
-	hipFree(L.sort.keys); hipFree(L.sort.order); hipFree(L.sort.hist); hipFree(const_cast<float4*>(L.sort.cen)); L.sort = QSort{};
-	hipFree(L.d_scratch); L.d_scratch = nullptr;
-	if (!tiles_usable() && L.tile.ub) {
-		for (int k = 0; k < 2; k++) { hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); }
-		hipFree(L.tile.ub); hipFree(L.tile.lb); hipFree(L.tile.scratch); L.tile = QTile{};
-	}
+	L.drop_sort();
+	L.d_scratch.reset();
+	if (!tiles_usable() && L.tile.ub) L.drop_tile();
 	// footprint-ordered items for the large rounds (lean grids, untrimmed, clouds of 4..16 chunks of 4 096 points).  Measured, registration in ms,
 	// chunk 2 048 | 3 072 | 4 096 | 6 144 | search order: bunny 34.4 | 33.1 | 33.8 | 34.1 | 36.8 (run-to-run +-0.6); bunny mse 1e-4 280 | 277 | 280 | 276 | 295;
 	// synthetic 40 k mse 3e-5 798 | 758 | 714 | 725 | 921; spanner 150 k mse 2e-5 223 | 212 | 206 | 201 | 195 -- above ~64 k points the unsorted
@@ -1936,13 +1831,12 @@ void Engine::lane_source_buffers(QLane& L)
 	const int kSortChunkPts = (int)(((N_ + 9) / 10 + 255) / 256 * 256);
 	const int sort_chunks = (int)((N_ + kSortChunkPts - 1) / kSortChunkPts);
 	if (p_.sort_items && bounds_uses_lean(bounds_dt()) && inliers_ >= (int)N_ && N_ >= 12288 && N_ <= 65536 && sort_chunks >= 4 && sort_chunks <= 16) {
-		float4* cen = nullptr;
-		HIPCHK(hipMalloc(&cen, sizeof(float4) * sort_chunks));
-		HIPCHK(launch_chunk_centroids(d_src_, (int)N_, kSortChunkPts, cen, L.stream));
-		L.sort.cen = cen;
-		HIPCHK(hipMalloc(&L.sort.keys, sizeof(unsigned) * max_groups * sort_chunks));
-		HIPCHK(hipMalloc(&L.sort.order, sizeof(unsigned) * max_groups * sort_chunks));
-		HIPCHK(hipMalloc(&L.sort.hist, qsort_hist_bytes()));
+		L.sort_cen.alloc(sort_chunks);
+		HIPCHK(launch_chunk_centroids(d_src_, (int)N_, kSortChunkPts, L.sort_cen, L.stream));
+		L.sort_keys.alloc(max_groups * sort_chunks);
+		L.sort_order.alloc(max_groups * sort_chunks);
+		L.sort_hist.alloc(qsort_hist_bytes() / sizeof(unsigned));
+		L.sort.cen = L.sort_cen; L.sort.keys = L.sort_keys; L.sort.order = L.sort_order; L.sort.hist = L.sort_hist;
 		HIPCHK(hipMemsetAsync(L.sort.hist, 0, qsort_hist_bytes(), L.stream));     // kept zero between uses by the kernels themselves
 		// sorted rounds from kSortMinGroups expansions.  Round 3 (512 | 1024 | 2048 | 4096): 35.0 | 34.5 | 33.6 | 37.3 ms.  Re-swept in round 4 with the
 		// twin lists and the 4 096-point chunks in place (tools/sort_threshold_probe.py, median of 7): 1 | 128 | 512 | 1024 | 2048 | 4096 | off = 33.8 | 33.3 | 33.5 | 33.6 | 34.4 | 36.6 | 36.3 ms;
@@ -1951,16 +1845,17 @@ void Engine::lane_source_buffers(QLane& L)
 		L.sort.chunk_pts = kSortChunkPts; L.sort.chunks = sort_chunks; L.sort.min_groups = kSortMinGroups;
 		L.sort.shift = qsort_shift(dt_.V);           // 16-voxel cells (32-voxel cells: 35.1 ms)
 	}
-	HIPCHK(hipMalloc(&L.d_scratch, sizeof(float) * bounds_queue_scratch_floats((int)max_groups, L.sort.order ? L.sort.chunks : 0)));
+	L.d_scratch.alloc(bounds_queue_scratch_floats((int)max_groups, L.sort.order ? L.sort.chunks : 0));
 	if (tiles_usable() && !L.tile.ub) {
 		// the second expansion list of a round (LDS-staged DT tiles): same capacity as the direct list
 		for (int k = 0; k < 2; k++) {
-			HIPCHK(hipMalloc(&L.tile.parents[k], sizeof(ParentRec) * max_groups));
-			HIPCHK(hipMalloc(&L.tile.segs[k], sizeof(TileSeg) * L.seg_cap));
+			L.tile_parents[k].alloc(max_groups);
+			L.tile_segs[k].alloc(L.seg_cap);
 		}
-		HIPCHK(hipMalloc(&L.tile.ub, sizeof(float) * max_groups * kGroup));
-		HIPCHK(hipMalloc(&L.tile.lb, sizeof(float) * max_groups * kGroup));
-		HIPCHK(hipMalloc(&L.tile.scratch, sizeof(float) * bounds_tile_queue_scratch_floats(L.seg_cap)));
+		L.tile_ub.alloc(max_groups * kGroup);
+		L.tile_lb.alloc(max_groups * kGroup);
+		L.tile_scratch.alloc(bounds_tile_queue_scratch_floats(L.seg_cap));
+		L.tile = QTile{{L.tile_parents[0], L.tile_parents[1]}, {L.tile_segs[0], L.tile_segs[1]}, L.tile_ub, L.tile_lb, L.tile_scratch};
 	}
 }
 
@@ -1969,7 +1864,7 @@ void Engine::ensure_queues(size_t nsearch) { ensure_lane(0, nsearch); }
 void Engine::ensure_lane(int li, size_t nsearch)
 {
 	QLane& L = ql_[li];
-	if (!lane_stream_[li]) HIPCHK(hipStreamCreateWithFlags(&lane_stream_[li], hipStreamNonBlocking));     // lanes 2.. : on first use (a stream costs ~2 ms to create)
+	if (!lane_stream_[li]) make_lane_stream(li);     // lanes 2.. : on first use (a stream costs ~2 ms to create)
 	L.stream = lane_stream_[li];
 	if (nsearch <= L.cap) return;
 	// first use: room for a full round of the outer search (rot_batch parents x 8 children x {ub, lb} pass) -- growing in
@@ -1977,30 +1872,26 @@ void Engine::ensure_lane(int li, size_t nsearch)
 	size_t cap = std::max<size_t>(L.cap, p_.wide_children ? (size_t)16 * (size_t)std::max(1, p_.rot_batch) : 16);
 	while (cap < nsearch) cap *= 2;
 	HIPCHK(hipStreamSynchronize(L.stream));
-	hipFree(L.d_search); hipHostFree(L.h_search); hipFree(L.d_nodes); hipFree(L.d_parents[0]); hipFree(L.d_parents[1]); hipFree(L.d_psearch[0]); hipFree(L.d_psearch[1]);
-	hipFree(L.sort.keys); hipFree(L.sort.order); hipFree(L.sort.hist); hipFree(const_cast<float4*>(L.sort.cen)); L.sort = QSort{};
-	hipFree(L.d_ub); hipFree(L.d_lb); hipFree(L.d_scratch);
-	for (int k = 0; k < 2; k++) { hipFree(L.tile.parents[k]); hipFree(L.tile.segs[k]); }
-	hipFree(L.tile.ub); hipFree(L.tile.lb); hipFree(L.tile.scratch); L.tile = QTile{};
-	L.d_search = nullptr; L.h_search = nullptr; L.d_nodes = nullptr; L.d_parents[0] = L.d_parents[1] = nullptr; L.d_psearch[0] = L.d_psearch[1] = nullptr;
-	L.d_ub = L.d_lb = L.d_scratch = nullptr; L.cap = 0;
+	L.cap = 0;
+	L.drop_sort();      // sized by the lists: lane_source_buffers makes them again
+	L.drop_tile();
 	const size_t max_groups = cap * kQueueRoundPop;          // what the round's lists hold; QParams::kmax keeps (searches running) x (their steps) inside
 	L.list_cap = (int)max_groups;
 	// segments (<= 64 expansions of one search) of the tile list: every search contributes floor(n / 64) full ones and at most one partial
 	L.seg_cap = (int)(max_groups / 64 + cap);
-	HIPCHK(hipMalloc(&L.d_search, sizeof(QSearch) * cap));
-	HIPCHK(hipHostMalloc(&L.h_search, sizeof(QSearch) * cap));
-	HIPCHK(hipMalloc(&L.d_nodes, sizeof(QNode) * cap * kQueueCap));          // 196 KB per search; HBM is not the scarce resource here
-	for (int k = 0; k < 2; k++) HIPCHK(hipMalloc(&L.d_parents[k], sizeof(ParentRec) * max_groups));
-	for (int k = 0; k < 2; k++) HIPCHK(hipMalloc(&L.d_psearch[k], sizeof(int) * max_groups));
-	HIPCHK(hipMalloc(&L.d_ub, sizeof(float) * max_groups * kGroup));
-	HIPCHK(hipMalloc(&L.d_lb, sizeof(float) * max_groups * kGroup));
+	L.d_search.alloc(cap);
+	L.h_search.alloc(cap);
+	L.d_nodes.alloc(cap * kQueueCap);          // 196 KB per search; HBM is not the scarce resource here
+	for (int k = 0; k < 2; k++) L.d_parents[k].alloc(max_groups);
+	for (int k = 0; k < 2; k++) L.d_psearch[k].alloc(max_groups);
+	L.d_ub.alloc(max_groups * kGroup);
+	L.d_lb.alloc(max_groups * kGroup);
 	lane_source_buffers(L);
 	if (!L.d_ctl) {
-		HIPCHK(hipMalloc(&L.d_ctl, sizeof(QCtl)));
-		HIPCHK(hipHostMalloc(&L.h_ctl, sizeof(QCtl)));
+		L.d_ctl.alloc(1);
+		L.h_ctl.alloc(1);
 		std::memset(L.h_ctl, 0, sizeof(QCtl));
-		HIPCHK(hipEventCreateWithFlags(&L.ev_ctl, hipEventDisableTiming));
+		L.ev_ctl.create(hipEventDisableTiming);
 	}
 	L.cap = cap;
 }
@@ -2045,7 +1936,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 	if (nl > 1) {            // the other lanes start behind the rotation upload (and everything else queued on the engine's stream)
 		HIPCHK(hipEventRecord(ev_fork_, stream_));
 		for (int li = 1; li < nl; li++) {
-			if (!lane_stream_[li]) HIPCHK(hipStreamCreateWithFlags(&lane_stream_[li], hipStreamNonBlocking));     // lanes 2.. : on first use (a stream costs ~2 ms to create)
+			if (!lane_stream_[li]) make_lane_stream(li);     // lanes 2.. : on first use (a stream costs ~2 ms to create)
 			HIPCHK(hipStreamWaitEvent(lane_stream_[li], ev_fork_, 0));
 		}
 	}
@@ -2674,8 +2565,8 @@ int Engine::flow_step(int max_rot_pops)
 	const QParams qp = queue_params();
 	ensure_batch(1, kFlowSearches / 2);
 	if (!h_qinit_) {
-		HIPCHK(hipHostMalloc(&h_qinit_, sizeof(QInit) * kFlowSearches));
-		HIPCHK(hipMalloc(&d_qinit_, sizeof(QInit) * kFlowSearches));
+		h_qinit_.alloc(kFlowSearches);
+		d_qinit_.alloc(kFlowSearches);
 	}
 	int pops = 0;
 	auto unhandled = [&] { size_t n = 0; for (const Flight& f : flights_) n += f.handled ? 0 : 1; return n; };

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "hipbuf.hpp"
 
 struct goicp_comm_ops;   // include/goicp_mi355.h
 struct goicp_pose_info_options;
@@ -254,7 +255,7 @@ public:
 	int inliers() const { return inliers_; }
 	float rot_coeff(int level) const;
 	hipStream_t stream() const { return stream_; }
-	const float4* d_source() const { return d_src_; }
+	const float4* d_source() const { return d_src_.get(); }
 	void source_transformed(const float R[9], const float t[3], float* out_xyz);  // original order
 	// goicp_set_source: a new source cloud under the same target -- everything derived from the target is kept (distance transform, k-d
 	// hierarchy, nearest-point table, normals, streams, queues, warm-ups), the params and the per-handle options persist, the search / ICP
@@ -271,6 +272,7 @@ public:
 	void set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept);
 
 private:
+	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
 	struct InnerSearch;
 	void init(const float* target_xyz, size_t M, const float* source_xyz, size_t N);
 	static void check_source(const float* source_xyz, size_t N);
@@ -279,9 +281,7 @@ private:
 	// d_xyz_ready: the same cloud already on the device (3 N floats; set_source_voxel), which the device order then reads instead of an upload
 	void load_source(const float* source_xyz, size_t N, bool device_order, const float* d_xyz_ready = nullptr);
 	void finish_source_swap();                       // set_source / set_source_voxel after load_source: the search and ICP state of a fresh engine
-	size_t cap_src_ = 0, cap_trim_ = 0, cap_cache_ = 0, cap_partials_ = 0;   // points / floats the N-sized device buffers hold
 	double source_order_ms_ = 0, voxel_ms_ = 0;
-	void release();
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(int k, size_t B);
 	void run_inner(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);
@@ -306,7 +306,6 @@ private:
 	std::vector<Flight> flights_;
 	std::vector<int> free_search_, free_rot_;
 	int q_hi_ = 0, q_parity_ = 0, flow_active_ = 0;
-	QInit* h_qinit_ = nullptr; QInit* d_qinit_ = nullptr;
 	void adopt(float err, const float R[9], const float t[3]);
 	float icp_from(float R[9], float t[3]);
 	void publish(bool finished);
@@ -333,65 +332,74 @@ private:
 	bool rot_boxed_ = false, trans_boxed_ = false;
 	float rot_lo_[3], rot_hi_[3], trans_lo_[3], trans_hi_[3];
 	std::function<void(const Result&)> progress_cb_;
-	void* d_opscratch_ = nullptr; size_t cap_opscratch_ = 0;
 	size_t M_ = 0, N_ = 0;
 	float sse_thresh_ = 0.f, icp_err_diff_ = 0.f;
 	int inliers_ = 0;             // inlierNum = (int)(Nd * (1 - trimFraction)), jly_goicp.cpp:201
 	int rank_ = 0, world_ = 1;
 
-	hipStream_t stream_ = nullptr;
-	hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-	hipEvent_t ev_fork_ = nullptr;        // the other lanes of a batch start behind the engine's stream (run_inner_device)
-	float4* d_src_ = nullptr;         // N  (x,y,z,|p|), k-d order (Params::morton_sort)
+	// ---- what the engine owns on the device.  Members go in reverse order of declaration: the caller's device is restored after everything
+	// else is gone (~Engine made the engine's device current), and the streams outlive the buffers and events used on them ----
+	struct RestoreDevice { int prev = -1; ~RestoreDevice(); } restore_device_;
+	static constexpr int kMaxLanes = 4;
+	Stream stream_;
+	Stream lane_own_[kMaxLanes];                            // [0] stays empty: lane 0 runs on stream_
+	hipStream_t lane_stream_[kMaxLanes] = {};               // lane 0: stream_, lane 1: created with the engine, further lanes: on first use
+	void make_lane_stream(int li);
+	Event ev0_, ev1_;
+	Event ev_fork_;                   // the other lanes of a batch start behind the engine's stream (run_inner_device)
+	Buf<unsigned char> d_opscratch_;  // scratch_bytes
+	PinnedBuf<QInit> h_qinit_; Buf<QInit> d_qinit_;
+	Buf<float4> d_src_;               // N  (x,y,z,|p|), k-d order (Params::morton_sort); grow-only, as every N-sized buffer below
 	std::vector<int32_t> src_perm_;   // sorted position -> original index
 	std::vector<float> h_src_sorted_; // N*4
 	std::vector<float> h_target_;     // M*3 (kept for viz.ply)
 	float src_centroid_[3] = {0, 0, 0}, model_centroid_[3] = {0, 0, 0};
 	DtDesc dt_{};
-	float* d_dt_ = nullptr;
+	Buf<float> d_dt_;
 	DtDesc dt16_{};                   // Params::bounds_fp16: the same grid in half precision (layout 2)
-	void* d_dt16_ = nullptr;
+	Buf<unsigned short> d_dt16_;
 	size_t kd_slots_ = 0;                 // float4 slots behind KdDesc::pts
-	int32_t* d_nn_ids_ = nullptr;         // nearest-target-point table of the ICP neighbour search (DtDesc::nn_ids)
+	Buf<int32_t> d_nn_ids_;               // nearest-target-point table of the ICP neighbour search (DtDesc::nn_ids)
 	bool score_exact_ = false;        // set while eval_sse scores a pose: always the fp32 grid
 	const DtDesc& bounds_dt() const { return (d_dt16_ && !score_exact_ && inliers_ >= (int)N_) ? dt16_ : dt_; }
-	double* d_overshoot_ = nullptr;
+	Buf<double> d_overshoot_;
 	// k-d tree
 	KdDesc kd_{};
-	float* d_kd_boxes_[kMaxLevels] = {nullptr, nullptr, nullptr}; float4* d_kd_pts_ = nullptr;
+	Buf<float> d_kd_boxes_[kMaxLevels]; Buf<float4> d_kd_pts_;
 	// bounds staging
-	size_t cap_cubes_ = 0, cap_rots_ = 0, cap_scratch_ = 0;
-	CubeRec* d_cubes_ = nullptr; CubeRec* h_cubes_ = nullptr;
-	Rot9* d_rots_ = nullptr; Rot9* h_rots_ = nullptr;
-	float* d_ub_ = nullptr; float* d_lb_ = nullptr; float* h_ub_ = nullptr; float* h_lb_ = nullptr;
-	float* d_scratch_ = nullptr;
+	size_t cap_cubes_ = 0, cap_rots_ = 0;   // what the six cube buffers / the two rotation buffers hold (0 while one of them is missing)
+	Buf<CubeRec> d_cubes_; PinnedBuf<CubeRec> h_cubes_;
+	Buf<Rot9> d_rots_; PinnedBuf<Rot9> h_rots_;
+	Buf<float> d_ub_, d_lb_; PinnedBuf<float> h_ub_, h_lb_;
+	Buf<float> d_scratch_;
 	struct Stage {   // per-group staging of the pipelined inner-BnB rounds
-		ParentRec* d_parents = nullptr; ParentRec* h_parents = nullptr;   // one record per expansion; the kernels derive the 8 children
-		float* d_ub = nullptr; float* h_ub = nullptr;   // ub[B] followed by lb[B]
-		size_t cap = 0, B = 0; hipEvent_t ev = nullptr;
+		Buf<ParentRec> d_parents; PinnedBuf<ParentRec> h_parents;   // one record per expansion; the kernels derive the 8 children
+		Buf<float> d_ub; PinnedBuf<float> h_ub;   // ub[B] followed by lb[B]
+		size_t cap = 0, B = 0; Event ev;          // cap: cube bounds the four buffers hold
 	} stage_[2];
 	// device-resident inner-BnB queues (bnbqueue.hip).  A LANE is one self-contained set of them -- search slots, node slabs, the
 	// round's two expansion lists with their bounds and partial sums, the sort buffers, the control block with its pinned snapshots --
 	// driven on its own stream.  Lane 0 always exists; lane 1 is created for batches cut in two (Params::lanes, run_inner_device)
-	static constexpr int kMaxLanes = 4;
 	struct QLane {
-		hipStream_t stream = nullptr;
+		hipStream_t stream = nullptr;                       // lane_stream_[li]: not the lane's to destroy
 		size_t cap = 0;                                     // search slots
-		QSearch* d_search = nullptr; QSearch* h_search = nullptr;
-		QNode* d_nodes = nullptr;
-		ParentRec* d_parents[2] = {nullptr, nullptr};
+		Buf<QSearch> d_search; PinnedBuf<QSearch> h_search;
+		Buf<QNode> d_nodes;
+		Buf<ParentRec> d_parents[2];
 		QSort sort{};                                       // footprint-ordered items of large rounds (device.hip); order == nullptr: off
+		Buf<unsigned> sort_keys, sort_order, sort_hist; Buf<float4> sort_cen;   // ... what `sort` points into
 		int list_cap = 0;                                   // expansions the round's lists (parents, bounds, partial sums) hold
 		int seg_cap = 0;                                    // segments the tile list holds (list_cap / 64 + search slots)
-		int* d_psearch[2] = {nullptr, nullptr};             // per listed expansion: the search that listed it (twin test of the bound evaluation)
-		float* d_ub = nullptr; float* d_lb = nullptr; float* d_scratch = nullptr;
-		QCtl* d_ctl = nullptr; QCtl* h_ctl = nullptr;       // h_ctl: the pinned snapshot of the last read-back
-		hipEvent_t ev_ctl = nullptr;                        // recorded behind that read-back
+		Buf<int> d_psearch[2];                              // per listed expansion: the search that listed it (twin test of the bound evaluation)
+		Buf<float> d_ub, d_lb, d_scratch;
+		Buf<QCtl> d_ctl; PinnedBuf<QCtl> h_ctl;             // h_ctl: the pinned snapshot of the last read-back
+		Event ev_ctl;                                       // recorded behind that read-back
 		QTile tile{};                                       // the tile list's buffers (null when lds_tiles == 0 or the DT is not bricked fp32)
+		Buf<ParentRec> tile_parents[2]; Buf<TileSeg> tile_segs[2]; Buf<float> tile_ub, tile_lb, tile_scratch;   // ... what `tile` points into
 		int tile_hint_seen = 0;                             // QCtl::tile_hint at the last read-back
+		void drop_sort();                                   // the sort's / the tile list's buffers go and the descriptor reads "off"
+		void drop_tile();
 	} ql_[kMaxLanes];
-	hipStream_t lane_stream_[kMaxLanes] = {};               // lane 0: stream_, lane 1: created with the engine, further lanes: on first use
-	void free_lane(QLane& L);
 	void lane_source_buffers(QLane& L);   // what a lane derives from the source: the sorted-round setup, the scratch sized by it, the tile list
 	void ensure_lane(int li, size_t nsearch);
 	double last_round_work_ = 0;                            // point-expansions (expansions x source points) of the previous batch's mean round
@@ -406,28 +414,28 @@ private:
 	long long tile_rounds_ = 0;           // rounds whose tile evaluation was launched
 	long long queue_rounds_ = 0, queue_fallbacks_ = 0;
 	// icp staging
-	float* d_icp_partials_ = nullptr; IcpState* d_icp_state_ = nullptr; IcpState* h_icp_state_ = nullptr;
-	unsigned long long* d_icp_acc_ = nullptr;   // fixed-point sums of the small-cloud ICP pass (kIcpAccReplicas x 16, zero between iterations)
+	Buf<float> d_icp_partials_; Buf<IcpState> d_icp_state_; PinnedBuf<IcpState> h_icp_state_;
+	Buf<unsigned long long> d_icp_acc_;         // fixed-point sums of the small-cloud ICP pass (kIcpAccReplicas x 16, zero between iterations)
 	float src_radius_ = 0.f, target_abs_max_ = 0.f;   // extents that bound the pass's terms (IcpState::acc_scale)
-	float4* d_nn_cache_ = nullptr;     // per source point: {q_ref, sqrt(best2_ref)}, {neighbour, index} (exact walk-skipping, device.hip)
+	Buf<float4> d_nn_cache_;           // per source point: {q_ref, sqrt(best2_ref)}, {neighbour, index} (exact walk-skipping, device.hip)
 	bool icp_cache_active_ = false;    // icp_nn_cache = 2: switched on inside a run once the error's decrease per chunk falls under kIcpCacheRel (the tail of a run)
 	static constexpr float kIcpCacheRel = 0.02f;
 	bool count_hits_ = false;
-	int* d_icp_ticket_ = nullptr;      // arrival ticket of the fused ICP iteration (zero between launches)
-	float* d_nn_d2_ = nullptr; int* d_nn_slot_ = nullptr; unsigned char* d_include_ = nullptr;   // trimmed ICP only
+	Buf<int> d_icp_ticket_;            // arrival ticket of the fused ICP iteration (zero between launches)
+	Buf<float> d_nn_d2_; Buf<int> d_nn_slot_; Buf<unsigned char> d_include_;   // trimmed ICP only
 	void icp_launch_one();
 	int icp_mode() const { return icp_robust() ? kIcpModeRobust : icp_gated() ? kIcpModeGate : kIcpModePlain; }   // launch_icp_iteration_opt's
 	void icp_last_stats(const IcpState* fin, size_t K);
 	// the collective ICP loop: the exported totals + converged flag + loop state read back per iteration, the summed totals uploaded
-	long long* d_icp_x_ = nullptr; long long* h_icp_x_ = nullptr;
+	Buf<long long> d_icp_x_; PinnedBuf<long long> h_icp_x_;
 	IcpShardStats icp_shard_;
 	// point-to-plane ICP (opt-in): the metric, the normals (one float4 per target point, original order: the pass gathers by the neighbour's index)
 	int icp_metric_ = 0, normal_k_ = 16, normals_k_ = 0;   // normals_k_: the normal_k the normals were built with (0: none yet)
-	float4* d_normals_ = nullptr;
+	Buf<float4> d_normals_;
 	double normal_build_ms_ = 0;
 	// the fixed-point accumulators of every single-pose opt-in iteration (point-to-plane, gate, kernel; one runs at a time):
 	// kIcpAccReplicas x kIcpPlaneStride, zero between iterations
-	unsigned long long* d_icp_acc_opt_ = nullptr;
+	Buf<unsigned long long> d_icp_acc_opt_;
 	void ensure_icp_acc_opt();
 	// distance-gated ICP (opt-in): the gate
 	float gate_dist_ = 0.f; int gate_min_inliers_ = 0, gate_capped_ = 1;
@@ -439,16 +447,14 @@ private:
 	std::atomic<int> registering_{0};                      // register_begin .. register_end: the options may not change
 	// goicp_icp_run_batch (allocated on first use, grown on demand): cap pose slots of loop state and accumulators (kIcpBatchAccWords each,
 	// zero between iterations), the pinned mirror of the states (one upload slot + two fetch slots), two active lists (device + pinned)
-	IcpState* d_batch_states_ = nullptr; IcpState* h_batch_states_ = nullptr;
-	unsigned long long* d_batch_acc_ = nullptr;
-	int* d_batch_active_ = nullptr; int* h_batch_active_ = nullptr;
-	size_t batch_cap_ = 0;
+	Buf<IcpState> d_batch_states_; PinnedBuf<IcpState> h_batch_states_;
+	Buf<unsigned long long> d_batch_acc_;
+	Buf<int> d_batch_active_; PinnedBuf<int> h_batch_active_;
+	size_t batch_cap_ = 0;             // pose slots all five hold (0 while one of them is missing)
 	void ensure_icp_batch(size_t K);
-	void free_icp_batch();
 	void ensure_normals(int k);
-	// pose information (allocated on first use, grown on demand): info_cap_ accumulator blocks (kIcpBatchAccWords each) and argument blocks
-	unsigned long long* d_info_acc_ = nullptr; PoseInfoArgs* d_info_args_ = nullptr;
-	size_t info_cap_ = 0;
+	// pose information (allocated on first use, grown on demand): one accumulator block (kIcpBatchAccWords) and one argument block per pose
+	Buf<unsigned long long> d_info_acc_; Buf<PoseInfoArgs> d_info_args_;
 	double src_crad_ = -1.0;           // largest distance of a source point from the source centroid (first use)
 	void ensure_pose_info(size_t K);
 	const goicp_comm_ops* icp_comm_ = nullptr;

@@ -204,10 +204,90 @@ void run_missing_rank()
 	for (int r = 0; r < world; r++) goicp::thread_comm_destroy(&comm[(size_t)r]);
 }
 
+// ---- the owner type of hipbuf.hpp over a counting host policy (the HIP policies are never instantiated here: no HIP library is linked) ----
+struct CountingMem {
+	static int live;
+	static bool fail_next;
+	static void* alloc(size_t bytes)
+	{
+		if (fail_next) { fail_next = false; throw std::runtime_error("counting policy: allocation refused"); }
+		live++;
+		return std::malloc(bytes);
+	}
+	static void free(void* p) { live--; std::free(p); }
+};
+int CountingMem::live = 0;
+bool CountingMem::fail_next = false;
+using CBuf = goicp::Buf<int, CountingMem>;
+struct Owners { CBuf a, b[2]; goicp::Buf<double, CountingMem> c; size_t cap = 0; };   // stand-in for the engine's QLane / Stage
+
+template <class F> bool refused(F&& f)
+{
+	try { f(); } catch (const std::runtime_error&) { return true; }
+	return false;
+}
+
+void run_buf()
+{
+	int& live = CountingMem::live;
+	{
+		CBuf x;
+		CHECK(!x && x.get() == nullptr && x.size() == 0 && live == 0);
+		x.alloc(8);
+		CHECK(x && x.size() == 8 && live == 1);
+		for (int i = 0; i < 8; i++) x[i] = i;                       // all 8 elements are there (ASan checks the bound)
+		const int* p8 = x.get();
+		CHECK(!x.reserve(8) && !x.reserve(3) && x.get() == p8 && x.size() == 8 && live == 1);   // no-op: same pointer
+		CHECK(x.reserve(9) && x.size() == 9 && live == 1);          // growth: the old block is gone, one is live
+		x[8] = 8;
+		x.alloc(2);                                                 // alloc is exact, also downwards
+		CHECK(x.size() == 2 && live == 1);
+		CBuf y(std::move(x));
+		CHECK(!x && x.size() == 0 && y.size() == 2 && live == 1);
+		CBuf z(5);
+		CHECK(live == 2);
+		z = std::move(y);                                           // over a live buffer: z's 5 are released
+		CHECK(!y && z.size() == 2 && live == 1);
+		z = std::move(z);
+		CHECK(z && z.size() == 2 && live == 1);
+		z.reset();
+		CHECK(!z && z.size() == 0 && live == 0);
+		z.reset();
+		CHECK(live == 0);
+		CBuf e(0);                                                  // zero elements: a real pointer, size 0
+		CHECK(e && e.size() == 0 && live == 1);
+		CHECK(!e.reserve(0) && e.reserve(1) && live == 1);
+		// a refused allocation over a live buffer leaves the object empty, and usable
+		CBuf f(4);
+		CountingMem::fail_next = true;
+		CHECK(refused([&] { f.alloc(6); }) && !f && f.get() == nullptr && f.size() == 0 && live == 1);
+		f.alloc(3);
+		CHECK(f.size() == 3 && live == 2);
+		CountingMem::fail_next = true;
+		CHECK(refused([&] { f.reserve(7); }) && !f && f.size() == 0 && live == 1);
+		CHECK(f.reserve(7) && f.size() == 7 && live == 2);
+		CountingMem::fail_next = true;
+		CHECK(refused([] { CBuf g(3); }) && live == 2);
+	}
+	CHECK(live == 0);                                               // scope exit
+	{
+		Owners o;
+		o.a.alloc(3); o.b[0].alloc(4); o.b[1].alloc(5); o.c.alloc(6); o.cap = 6;
+		CHECK(live == 4);
+		o = Owners{};
+		CHECK(live == 0 && !o.a && !o.b[0] && !o.b[1] && !o.c && o.c.size() == 0 && o.cap == 0);
+		o.b[1].alloc(2);
+		Owners q(std::move(o));
+		CHECK(live == 1 && !o.b[1] && q.b[1].size() == 2);
+	}
+	CHECK(live == 0);
+}
+
 }  // namespace
 
 int main()
 {
+	run_buf();
 	// ---- sharding protocol + thread communicator, 1 / 2 / 4 / 7 ranks ----
 	long long don = 0;
 	const float single = run_world(1, 1, nullptr);

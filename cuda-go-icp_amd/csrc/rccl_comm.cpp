@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "comm.hpp"
+#include "hipbuf.hpp"
 
 namespace goicp {
 
@@ -29,10 +30,9 @@ struct RcclComm {
 	ncclComm_t comm = nullptr;
 	bool owns = false;
 	int device = 0;
-	hipStream_t stream = nullptr;
-	void* d_buf = nullptr;
-	void* h_buf = nullptr;
-	size_t cap = 0;
+	Stream stream;                         // released with the struct, on `device` (finish, rccl_comm_destroy)
+	Buf<unsigned char> d_buf;              // kStageBytes each
+	PinnedBuf<unsigned char> h_buf;
 	std::string err;
 };
 
@@ -71,7 +71,7 @@ int allreduce_min_u64(void* ctx, uint64_t* words, size_t n)
 {
 	RcclComm* c = static_cast<RcclComm*>(ctx);
 	if (c->broken) return GOICP_ERR_TIMEOUT;
-	if (n * sizeof(uint64_t) > c->cap) return GOICP_ERR_INVALID;
+	if (n * sizeof(uint64_t) > kStageBytes) return GOICP_ERR_INVALID;
 	DevScope dev(c->device);
 	std::memcpy(c->h_buf, words, n * sizeof(uint64_t));
 	// any failure to enqueue leaves the stream in an unknown state: the communicator is broken from here on (destroy then aborts
@@ -90,7 +90,7 @@ int allreduce_sum_i64(void* ctx, int64_t* words, size_t n)
 {
 	RcclComm* c = static_cast<RcclComm*>(ctx);
 	if (c->broken) return GOICP_ERR_TIMEOUT;
-	if (n * sizeof(int64_t) > c->cap) return GOICP_ERR_INVALID;
+	if (n * sizeof(int64_t) > kStageBytes) return GOICP_ERR_INVALID;
 	DevScope dev(c->device);
 	std::memcpy(c->h_buf, words, n * sizeof(int64_t));
 	auto fail = [&] { c->broken = true; (void)hipGetLastError(); return GOICP_ERR_DEVICE; };
@@ -106,7 +106,7 @@ int bcast(void* ctx, void* buf, size_t bytes, int32_t root)
 {
 	RcclComm* c = static_cast<RcclComm*>(ctx);
 	if (c->broken) return GOICP_ERR_TIMEOUT;
-	if (bytes > c->cap) return GOICP_ERR_INVALID;
+	if (bytes > kStageBytes) return GOICP_ERR_INVALID;
 	DevScope dev(c->device);
 	std::memcpy(c->h_buf, buf, bytes);
 	auto fail = [&] { c->broken = true; (void)hipGetLastError(); return GOICP_ERR_DEVICE; };
@@ -121,15 +121,16 @@ int bcast(void* ctx, void* buf, size_t bytes, int32_t root)
 int finish(RcclComm* c, int32_t rank, int32_t world, goicp_comm_ops* out)
 {
 	DevScope dev(c->device);
-	if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_buf, kStageBytes) != hipSuccess ||
-	    hipHostMalloc(&c->h_buf, kStageBytes) != hipSuccess) {
-		if (c->stream) hipStreamDestroy(c->stream);
-		hipFree(c->d_buf); hipHostFree(c->h_buf);
-		if (c->owns && c->comm) ncclCommDestroy(c->comm);
+	try {
+		c->stream.create();
+		c->d_buf.alloc(kStageBytes);
+		c->h_buf.alloc(kStageBytes);
+	} catch (const std::runtime_error&) {
+		const ncclComm_t owned = c->owns ? c->comm : nullptr;
 		delete c;
+		if (owned) ncclCommDestroy(owned);
 		return GOICP_ERR_DEVICE;
 	}
-	c->cap = kStageBytes;
 	c->hdr.timeout_ms = comm_default_timeout_ms();
 	out->ctx = c; out->rank = rank; out->world = world;
 	out->allreduce_min_u64 = &allreduce_min_u64;
@@ -175,25 +176,20 @@ int rccl_comm_destroy(goicp_comm_ops* comm)
 {
 	if (!comm || !comm->ctx) return GOICP_OK;
 	RcclComm* c = static_cast<RcclComm*>(comm->ctx);
-	{
-		DevScope dev(c->device);
-		if (c->broken) {
-			// a collective is stuck on the stream: abort the communicator first (its kernels then leave), never wait on it;
-			// a wrapped communicator stays the caller's to abort, its stream and staging blocks are left alone (leaked)
-			if (c->owns && c->comm) {
-				ncclCommAbort(c->comm);
-				hipStreamDestroy(c->stream);
-				hipFree(c->d_buf); hipHostFree(c->h_buf);
-			}
-		} else {
-			hipStreamSynchronize(c->stream);
-			hipStreamDestroy(c->stream);
-			hipFree(c->d_buf); hipHostFree(c->h_buf);
-			if (c->owns && c->comm) ncclCommDestroy(c->comm);
-		}
-	}
-	delete c;
 	comm->ctx = nullptr;
+	DevScope dev(c->device);
+	const ncclComm_t owned = c->owns ? c->comm : nullptr;
+	if (c->broken) {
+		// a collective is stuck on the stream: abort the communicator first (its kernels then leave), never wait on it;
+		// a wrapped communicator stays the caller's to abort: its stream and staging blocks are left alone -- `c` is leaked whole
+		if (!owned) return GOICP_OK;
+		ncclCommAbort(owned);
+		delete c;
+	} else {
+		hipStreamSynchronize(c->stream);
+		delete c;
+		if (owned) ncclCommDestroy(owned);
+	}
 	return GOICP_OK;
 }
 
