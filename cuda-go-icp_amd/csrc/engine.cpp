@@ -37,6 +37,13 @@ double now_ms()
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// adds the milliseconds its scope took to `acc`
+struct ScopedMs {
+	double& acc;
+	double t0 = now_ms();
+	~ScopedMs() { acc += now_ms() - t0; }
+};
+
 }  // namespace
 
 Engine::DeviceGuard::DeviceGuard(int dev) : want(dev)
@@ -70,7 +77,19 @@ struct Engine::InnerSearch {
 	long long pops = 0, cubes = 0;
 	float min_ub = std::numeric_limits<float>::infinity();   // smallest upper bound of any cube evaluated
 	int stale = 0;                // rounds since the incumbent last improved (host fallback: round widening)
+	void finish(const SearchOut& o) { best = o.best; improved = o.improved; best_node = o.best_node; pops = o.pops; cubes = o.cubes; min_ub = o.min_ub; done = true; }
 };
+
+Engine::SearchOut Engine::SearchOut::of(const InnerSearch& s) { return SearchOut{s.best, s.improved, s.best_node, s.pops, s.cubes, s.min_ub}; }
+Engine::SearchOut Engine::SearchOut::of(const QSearch& q) { return SearchOut{q.best, q.improved != 0, Node{q.bx, q.by, q.bz, q.bw, 0.f, 0.f, 0}, q.pops, q.cubes, q.min_ub}; }
+
+Engine::InnerSearch Engine::fresh_search(int rot_slot, float coeff, float incumbent) const
+{
+	InnerSearch s;
+	s.rot_slot = rot_slot; s.coeff = coeff; s.best = incumbent;
+	s.pq.push(trans_root_);
+	return s;
+}
 
 float Engine::rot_coeff(int level) const
 {
@@ -320,7 +339,7 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 	if (p_.device_queues && p_.trans_batch > 1 && p_.wide_children) {
 		// the device-resident inner-BnB queues, sized for a full round of the outer search, and their pinned mirror touched
 		// once (the first use of a fresh pinned block costs milliseconds -- measured 8 ms inside the first registration)
-		ensure_queues(flow_mode() ? kFlowSearches : 1);
+		ensure_lane(0, flow_mode() ? kFlowSearches : 1);
 		if (flow_mode()) {
 			ensure_batch(1, kFlowSearches / 2);
 			h_qinit_.alloc(kFlowSearches);
@@ -361,12 +380,9 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 			HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9) * (kFlowSearches / 2), hipMemcpyHostToDevice, stream_));
 			HIPCHK(hipMemcpyAsync(d_qinit_, h_qinit_, sizeof(QInit) * kFlowSearches, hipMemcpyHostToDevice, stream_));
 			HIPCHK(launch_bnb_init_list(ql_[0].d_search, ql_[0].d_nodes, d_qinit_, 1, qp, stream_));
-			for (int r = 0; r < 3; r++) {
-				HIPCHK(launch_bnb_queue(ql_[0].d_search, ql_[0].d_nodes, kFlowSearches, qp, ql_[0].d_parents[q_parity_ ^ 1], ql_[0].d_parents[q_parity_], ql_[0].d_ub, ql_[0].d_lb, ql_[0].d_scratch, ql_[0].d_ctl, q_parity_, stream_));
-				HIPCHK(launch_bounds_queue(d_src_, (int)N_, bounds_dt(), d_rots_, ql_[0].d_parents[q_parity_], &ql_[0].d_ctl->n_groups[q_parity_], &ql_[0].d_ctl->work[q_parity_][0], &ql_[0].d_ctl->chunks,
-				                           kFlowSearches * qp.K, inliers_, ql_[0].d_scratch, ql_[0].d_ub, ql_[0].d_lb, stream_));
-				q_parity_ ^= 1;
-			}
+			RoundOpts warm_round;
+			warm_round.count = false;
+			for (int r = 0; r < 3; r++, q_parity_ ^= 1) queue_round(ql_[0], kFlowSearches, qp, q_parity_, kFlowSearches * qp.K, warm_round);
 			HIPCHK(hipMemcpyAsync(ql_[0].h_ctl, ql_[0].d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
 			HIPCHK(hipMemcpyAsync(ql_[0].h_search, ql_[0].d_search, sizeof(QSearch) * kFlowSearches, hipMemcpyDeviceToHost, stream_));
 			HIPCHK(hipStreamSynchronize(stream_));
@@ -621,19 +637,30 @@ void Engine::ensure_batch(size_t B, size_t K)
 	}
 }
 
+void Engine::upload_rots(const std::vector<Rot9>& rots)
+{
+	ensure_batch(1, rots.size());
+	std::memcpy(h_rots_, rots.data(), sizeof(Rot9) * rots.size());
+	HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9) * rots.size(), hipMemcpyHostToDevice, stream_));
+}
+
 // ------------------------------------------------------------------------------------------------
 // operators
 // ------------------------------------------------------------------------------------------------
+void Engine::ensure_bounds_scratch(int B, hipStream_t s)
+{
+	const size_t need = bounds_scratch_floats(B, (int)N_, nullptr, nullptr);
+	if (need <= d_scratch_.size()) return;
+	// only the two streams that can still be using the old scratch, not the whole device
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
+	d_scratch_.alloc(need);
+}
+
 void Engine::eval_bounds_dev(const Rot9* d_rots, const CubeRec* d_cubes, int B, float* d_ub, float* d_lb, hipStream_t s, const ParentRec* d_parents)
 {
 	DeviceGuard guard(dev_);
-	size_t need = bounds_scratch_floats(B, (int)N_, nullptr, nullptr);
-	if (need > d_scratch_.size()) {
-		// only the two streams that can still be using the old scratch, not the whole device
-		HIPCHK(hipStreamSynchronize(stream_));
-		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
-		d_scratch_.alloc(need);
-	}
+	ensure_bounds_scratch(B, s);
 	if (inliers_ < (int)N_)
 		HIPCHK(launch_bounds_trim(d_src_, (int)N_, dt_, d_rots, d_cubes, d_parents, B, inliers_, d_ub, d_lb, s ? s : stream_));
 	else
@@ -652,12 +679,7 @@ void Engine::eval_bounds_dev_grouped(const Rot9* d_rots, int nrots, const CubeRe
 	DeviceGuard guard(dev_);
 	if (inliers_ < (int)N_) { eval_bounds_dev(d_rots, d_cubes, B, d_ub, d_lb, s); return; }     // the trimmed kernel owns whole cubes: nothing to group
 	if (nrots < 1 || nrots > 16) throw std::invalid_argument("goicp: grouped bounds take 1..16 rotations");
-	const size_t need = bounds_scratch_floats(B, (int)N_, nullptr, nullptr);
-	if (need > d_scratch_.size()) {
-		HIPCHK(hipStreamSynchronize(stream_));
-		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
-		d_scratch_.alloc(need);
-	}
+	ensure_bounds_scratch(B, s);
 	void* gs = scratch_bytes(bounds_grouped_scratch_bytes(B, nrots));
 	HIPCHK(launch_bounds_grouped(d_src_, (int)N_, bounds_dt(), d_rots, nrots, d_cubes, B, gs, d_scratch_, d_ub, d_lb, s ? s : stream_));
 	cnt_.bounds_launches++;
@@ -1539,8 +1561,7 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 
 float Engine::refine_collective(float R[9], float t[3])
 {
-	const double t0 = now_ms();
-	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{icp_ms_, t0};
+	ScopedMs acc{icp_ms_};
 	int it = 0;
 	float e = 0.f;
 	const int rc = icp_run_collective(icp_comm_, R, t, p_.icp_max_iter, icp_err_diff_, &e, &it);
@@ -1665,51 +1686,51 @@ void Engine::debug_queue_expand(const float R[9], int level, const float* parent
 	if (n < 1 || n > kQueueRoundPop) throw std::invalid_argument("goicp: debug_queue_expand takes 1..128 nodes");
 	if (!(p_.device_queues && p_.trans_batch > 1 && p_.wide_children)) throw std::invalid_argument("goicp: debug_queue_expand needs the device-queue configuration");
 	if (inliers_ < (int)N_) throw std::invalid_argument("goicp: debug_queue_expand: untrimmed engines only");
-	ensure_queues(2);
-	ensure_batch(1, 1);
-	std::memcpy(h_rots_[0].r, R, sizeof(float) * 9);
-	HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9), hipMemcpyHostToDevice, stream_));
-	const bool twins = p_.twin_fusion && ql_[0].d_psearch[0] != nullptr;
+	ensure_lane(0, 2);
+	QLane& L = ql_[0];
+	std::vector<Rot9> rot(1);
+	std::memcpy(rot[0].r, R, sizeof(float) * 9);
+	upload_rots(rot);
+	const bool twins = p_.twin_fusion && L.d_psearch[0] != nullptr;
 	// two searches whose queues hold exactly the given nodes (lower bound 0: all of them pass the stop rule against a huge incumbent and,
 	// n <= K, all are selected; the list keeps the queue order)
 	std::vector<QNode> nodes((size_t)n);
 	for (int i = 0; i < n; i++) nodes[(size_t)i] = QNode{parents4[4 * i], parents4[4 * i + 1], parents4[4 * i + 2], parents4[4 * i + 3], 0.f, 0.f};
 	for (int s = 0; s < 2; s++) {
-		QSearch& q = ql_[0].h_search[s];
+		QSearch& q = L.h_search[s];
 		std::memset(&q, 0, sizeof(q));
 		q.best = 1e30f; q.coeff = s ? rot_coeff(level) : 0.f; q.rot = 0; q.count = n; q.min_ub = INFINITY; q.twin = twins ? (s ^ 1) : -1;
-		HIPCHK(hipMemcpyAsync(ql_[0].d_nodes + (size_t)s * kQueueCap, nodes.data(), sizeof(QNode) * (size_t)n, hipMemcpyHostToDevice, stream_));
+		HIPCHK(hipMemcpyAsync(L.d_nodes + (size_t)s * kQueueCap, nodes.data(), sizeof(QNode) * (size_t)n, hipMemcpyHostToDevice, stream_));
 	}
-	HIPCHK(hipMemcpyAsync(ql_[0].d_search, ql_[0].h_search, sizeof(QSearch) * 2, hipMemcpyHostToDevice, stream_));
-	std::memset(ql_[0].h_ctl, 0, sizeof(QCtl));
-	ql_[0].h_ctl->tile_chunks = 1;
-	HIPCHK(hipMemcpyAsync(ql_[0].d_ctl, ql_[0].h_ctl, sizeof(QCtl), hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(L.d_search, L.h_search, sizeof(QSearch) * 2, hipMemcpyHostToDevice, stream_));
+	std::memset(L.h_ctl, 0, sizeof(QCtl));
+	L.h_ctl->tile_chunks = 1;
+	HIPCHK(hipMemcpyAsync(L.d_ctl, L.h_ctl, sizeof(QCtl), hipMemcpyHostToDevice, stream_));
 	QParams qp = queue_params();
 	qp.K = std::max(n, 1); qp.kmax = kQueueRoundPop; qp.tile_on = 0; qp.stale_widen = 0; qp.stale_compact = 0;
 	const int parity = 0, max_groups = 2 * n;
-	HIPCHK(launch_bnb_queue(ql_[0].d_search, ql_[0].d_nodes, 2, qp, ql_[0].d_parents[parity ^ 1], ql_[0].d_parents[parity], ql_[0].d_ub, ql_[0].d_lb, ql_[0].d_scratch, ql_[0].d_ctl, parity, stream_, nullptr,
-	                        twins ? ql_[0].d_psearch[parity] : nullptr));
-	HIPCHK(launch_bounds_queue(d_src_, (int)N_, bounds_dt(), d_rots_, ql_[0].d_parents[parity], &ql_[0].d_ctl->n_groups[parity], &ql_[0].d_ctl->work[parity][0], &ql_[0].d_ctl->chunks, max_groups,
-	                           inliers_, ql_[0].d_scratch, ql_[0].d_ub, ql_[0].d_lb, stream_, twins ? ql_[0].d_search : nullptr, twins ? ql_[0].d_psearch[parity] : nullptr, nullptr));
-	HIPCHK(hipMemcpyAsync(ql_[0].h_ctl, ql_[0].d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipMemcpyAsync(ql_[0].h_search, ql_[0].d_search, sizeof(QSearch) * 2, hipMemcpyDeviceToHost, stream_));
+	RoundOpts round;
+	round.twins = twins; round.count = false;
+	queue_round(L, 2, qp, parity, max_groups, round);
+	HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(L.h_search, L.d_search, sizeof(QSearch) * 2, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
-	if (ql_[0].h_ctl->overflow || ql_[0].h_ctl->n_groups[parity] != 2 * n || ql_[0].h_search[0].n_parents != n || ql_[0].h_search[1].n_parents != n)
+	if (L.h_ctl->overflow || L.h_ctl->n_groups[parity] != 2 * n || L.h_search[0].n_parents != n || L.h_search[1].n_parents != n)
 		throw std::logic_error("goicp: debug_queue_expand: the round did not list every node");
-	const int chunks = ql_[0].h_ctl->chunks;
+	const int chunks = L.h_ctl->chunks;
 	info[0] = chunks; info[1] = twins ? 1 : 0;
 	std::vector<ParentRec> listed((size_t)2 * n);
-	HIPCHK(hipMemcpy(listed.data(), ql_[0].d_parents[parity], sizeof(ParentRec) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(listed.data(), L.d_parents[parity], sizeof(ParentRec) * 2 * (size_t)n, hipMemcpyDeviceToHost));
 	std::vector<float> ub((size_t)16 * n), lb((size_t)16 * n), part;
 	if (chunks > 1) {
 		part.resize((size_t)2 * n * chunks * 2 * kGroup);
-		HIPCHK(hipMemcpy(part.data(), ql_[0].d_scratch, sizeof(float) * part.size(), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(part.data(), L.d_scratch, sizeof(float) * part.size(), hipMemcpyDeviceToHost));
 	} else {
-		HIPCHK(hipMemcpy(ub.data(), ql_[0].d_ub, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(lb.data(), ql_[0].d_lb, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(ub.data(), L.d_ub, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(lb.data(), L.d_lb, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
 	}
 	for (int s = 0; s < 2; s++) {
-		const int off = ql_[0].h_search[s].parent_off;
+		const int off = L.h_search[s].parent_off;
 		float* ou = s ? ub1 : ub0; float* ol = s ? lb1 : lb0;
 		for (int e = 0; e < n; e++) {
 			const ParentRec& pr = listed[(size_t)off + e];
@@ -1785,9 +1806,9 @@ void Engine::icp_step()
 // ------------------------------------------------------------------------------------------------
 // inner (translation) BnB, batched across searches
 // ------------------------------------------------------------------------------------------------
-void Engine::ensure_stage(int k, size_t B)
+void Engine::ensure_stage(size_t B)
 {
-	Stage& st = stage_[k];
+	Stage& st = stage_;
 	if (!st.ev) st.ev.create(hipEventDisableTiming);
 	if (B <= st.cap) return;
 	const size_t cap = std::max<size_t>(B, st.cap * 2);
@@ -1859,8 +1880,6 @@ void Engine::lane_source_buffers(QLane& L)
 	}
 }
 
-void Engine::ensure_queues(size_t nsearch) { ensure_lane(0, nsearch); }
-
 void Engine::ensure_lane(int li, size_t nsearch)
 {
 	QLane& L = ql_[li];
@@ -1896,6 +1915,37 @@ void Engine::ensure_lane(int li, size_t nsearch)
 	L.cap = cap;
 }
 
+// One round of a lane's device queues, queued on the lane's own stream: the queue kernel (digest the previous round's bounds, select the
+// next expansions), then the bound evaluation of what it listed -- the direct list, and the tile list when qp.tile_on.  o.count = false:
+// a round that belongs to no search (engine creation, debug_queue_expand) and moves no counter
+void Engine::queue_round(QLane& L, int nsearch, const QParams& qp, int parity, int max_groups, const RoundOpts& o)
+{
+	int* const psearch = o.twins ? L.d_psearch[parity].get() : nullptr;
+	HIPCHK(launch_bnb_queue(L.d_search, L.d_nodes, nsearch, qp, L.d_parents[parity ^ 1], L.d_parents[parity], L.d_ub, L.d_lb, L.d_scratch, L.d_ctl, parity, L.stream,
+	                        o.tiles ? &L.tile : nullptr, psearch, o.deep));
+	if (o.read_ctl) {
+		// Everything the host looks at after a chunk -- what the last round listed, how many searches are running, overflow, the tile
+		// hint -- is written by THIS kernel; the bound evaluations behind it only fill in the bounds the next queue kernel digests.  So the
+		// control block is read back here, ahead of the round's bound evaluation, and the host decides and queues the next chunk
+		// while those bounds are being evaluated: the same information at the same point of the search as a read-back after the chunk
+		// (identical decisions, identical counts) for a 4 us copy in the stream instead of ~45 us of idle GPU per chunk.  Measured: bunny
+		// 33.1-33.6 -> 32.8 ms, skull 6.4 -> 6.3, the rest within the spread.  (From a SIDE stream the copy lost: its blit kernel cannot
+		// start while the persistent bound kernels hold every CU -- bunny 33.9 ms, synthetic 40 k mse 3e-5 610 -> 642 ms.)
+		HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, L.stream));
+		HIPCHK(hipEventRecord(L.ev_ctl, L.stream));
+	}
+	if (o.sorted) HIPCHK(launch_queue_sort(L.d_parents[parity], d_rots_, &L.d_ctl->n_groups[parity], max_groups, L.sort, bounds_dt(), L.stream));
+	HIPCHK(launch_bounds_queue(d_src_, (int)N_, bounds_dt(), d_rots_, L.d_parents[parity], &L.d_ctl->n_groups[parity], &L.d_ctl->work[parity][0], &L.d_ctl->chunks, max_groups,
+	                           inliers_, L.d_scratch, L.d_ub, L.d_lb, L.stream, o.twins ? L.d_search.get() : nullptr, psearch, o.sorted ? &L.sort : nullptr));
+	// the tile list's evaluation behind the direct list's, on the lane's own stream: forking it onto a second stream to run beside it was
+	// measured slower (EXPERIMENTS R4.8: the tile and gather kernels take each other's occupancy)
+	if (qp.tile_on) HIPCHK(launch_bounds_tile_queue(d_src_, (int)N_, dt_, d_rots_, L.tile, L.d_ctl, parity, L.stream));
+	if (!o.count) return;
+	cnt_.bounds_launches++;
+	queue_rounds_++;
+	if (qp.tile_on) tile_rounds_++;
+}
+
 // The inner searches with their queues on the device: a round = bnb_queue_kernel (digest the previous round's
 // bounds, select the next expansions) + the bound evaluation of the listed expansions; the host queues rounds and
 // looks at one word every few rounds.  Same bounds, same stop and prune rules as run_inner_host.
@@ -1904,9 +1954,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 	TraceRange tr("goicp:inner_bnb_rounds");
 	const size_t S = searches.size(), nrot = rots.size();
 	const int K = std::min(std::max(1, p_.trans_batch), kQueueRoundPop);
-	ensure_batch(1, nrot);
-	std::memcpy(h_rots_, rots.data(), sizeof(Rot9) * nrot);
-	HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9) * nrot, hipMemcpyHostToDevice, stream_));
+	upload_rots(rots);
 	// Lanes: the searches of a batch are independent of each other (own queue, own incumbent; only the two passes of one rotation child --
 	// twins, same rotation slot -- share loads), so a large batch is cut into lanes by rotation slot and each lane runs its own lock-step rounds
 	// on its own stream with its own lists and control block.  Same bounds, same stop and prune rules per search; what changes is that one
@@ -1987,41 +2035,22 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 	const bool deep_batch = tile_sticky_;
 	// One chunk of rounds of a lane: queue kernel + (sort) + bound evaluation(s) per round; the control block is read back behind the LAST round's queue kernel.
 	auto submit = [&](Run& r) {
-		const double t0 = now_ms();
+		ScopedMs t{t_submit_};
 		QLane& L = *r.L;
 		const size_t Sl = r.idx.size();
 		QParams& qp = r.qp;
 		const int max_groups = (int)std::min<size_t>(Sl * (size_t)std::min(qp.kmax, 4 * qp.K), (size_t)L.list_cap);   // most the round can list (the kernel widens a stale search's step up to x4)
+		RoundOpts o;
+		o.tiles = r.tiles; o.twins = r.twins; o.deep = deep_batch;
 		for (int k = 0; k < r.chunk; k++) {
-			const int parity = r.parity;
-			HIPCHK(launch_bnb_queue(L.d_search, L.d_nodes, (int)Sl, qp, L.d_parents[parity ^ 1], L.d_parents[parity], L.d_ub, L.d_lb, L.d_scratch, L.d_ctl, parity, L.stream, r.tiles ? &L.tile : nullptr,
-			                        r.twins ? L.d_psearch[parity] : nullptr, deep_batch));
-			if (k == r.chunk - 1) {
-				// Everything the host looks at after a chunk -- what the last round listed, how many searches are running, overflow, the tile
-				// hint -- is written by THIS kernel; the bound evaluations behind it only fill in the bounds the next queue kernel digests.  So the
-				// control block is read back here, ahead of the last round's bound evaluation, and the host decides and queues the next chunk
-				// while those bounds are being evaluated: the same information at the same point of the search as a read-back after the chunk
-				// (identical decisions, identical counts) for a 4 us copy in the stream instead of ~45 us of idle GPU per chunk.  Measured: bunny
-				// 33.1-33.6 -> 32.8 ms, skull 6.4 -> 6.3, the rest within the spread.  (From a SIDE stream the copy lost: its blit kernel cannot
-				// start while the persistent bound kernels hold every CU -- bunny 33.9 ms, synthetic 40 k mse 3e-5 610 -> 642 ms.)
-				HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, L.stream));
-				HIPCHK(hipEventRecord(L.ev_ctl, L.stream));
-			}
-			const bool sorted = r.sort_round && std::min<long long>(r.round_cap, max_groups) >= L.sort.min_groups;
-			if (sorted) HIPCHK(launch_queue_sort(L.d_parents[parity], d_rots_, &L.d_ctl->n_groups[parity], max_groups, L.sort, bounds_dt(), L.stream));
-			HIPCHK(launch_bounds_queue(d_src_, (int)N_, bounds_dt(), d_rots_, L.d_parents[parity], &L.d_ctl->n_groups[parity], &L.d_ctl->work[parity][0], &L.d_ctl->chunks, max_groups,
-			                           inliers_, L.d_scratch, L.d_ub, L.d_lb, L.stream, r.twins ? L.d_search : nullptr, r.twins ? L.d_psearch[parity] : nullptr, sorted ? &L.sort : nullptr));
+			o.read_ctl = k == r.chunk - 1;
+			o.sorted = r.sort_round && std::min<long long>(r.round_cap, max_groups) >= L.sort.min_groups;
+			queue_round(L, (int)Sl, qp, r.parity, max_groups, o);
 			if (r.round_cap < (1ll << 40)) r.round_cap *= 8;
 			r.rounds_done++;
-			// the tile list's evaluation behind the direct list's, on the lane's own stream: forking it onto a second stream to run beside it was
-			// measured slower (EXPERIMENTS R4.8: the tile and gather kernels take each other's occupancy)
-			if (qp.tile_on) { HIPCHK(launch_bounds_tile_queue(d_src_, (int)N_, dt_, d_rots_, L.tile, L.d_ctl, parity, L.stream)); tile_rounds_++; }
-			r.last = parity;
+			r.last = r.parity;
 			r.parity ^= 1;
-			cnt_.bounds_launches++;
-			queue_rounds_++;
 		}
-		t_submit_ += now_ms() - t0;
 	};
 	// fold a chunk's read-back into the parameters of the chunks still to be queued
 	auto adapt = [&](Run& r, const QCtl& c) {
@@ -2054,9 +2083,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 		for (int li = 0; li < nl; li++) {
 			Run& r = run[li];
 			if (r.done) continue;
-			const double t1 = now_ms();
-			HIPCHK(hipEventSynchronize(r.L->ev_ctl));
-			t_wait_ += now_ms() - t1;
+			{ ScopedMs t{t_wait_}; HIPCHK(hipEventSynchronize(r.L->ev_ctl)); }
 			const QCtl& c = *r.L->h_ctl;
 			if (c.overflow) overflow = true;
 			if (c.overflow || overflow || (c.n_groups[r.last] == 0 && c.n_tile_groups[r.last] == 0) || cancel_.load()) { r.done = true; live--; continue; }
@@ -2080,21 +2107,15 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 	for (int li = 0; li < nl; li++) if (run[li].L->h_ctl->overflow) overflow = true;
 	if (overflow) { queue_fallbacks_++; cnt_.queue_fallbacks++; return false; }
 	if (nl > 1) cnt_.lane_batches++;
-	{
-		long long cubes = 0;
-		for (int li = 0; li < nl; li++) for (size_t i = 0; i < run[li].idx.size(); i++) cubes += run[li].L->h_search[i].cubes;
-		int rounds = 1;
-		for (int li = 0; li < nl; li++) rounds = std::max(rounds, run[li].rounds_done);
-		last_round_work_ = (double)cubes / kGroup / rounds * (double)N_;
+	long long cubes = 0, tile_total = 0;
+	int rounds = 1;
+	for (int li = 0; li < nl; li++) {
+		tile_total += run[li].L->h_ctl->tile_total;
+		rounds = std::max(rounds, run[li].rounds_done);
+		for (size_t i = 0; i < run[li].idx.size(); i++) cubes += run[li].L->h_search[i].cubes;
 	}
-	{
-		long long tile_total = 0, all = 0;
-		for (int li = 0; li < nl; li++) {
-			tile_total += run[li].L->h_ctl->tile_total;
-			for (size_t i = 0; i < run[li].idx.size(); i++) all += run[li].L->h_search[i].cubes;
-		}
-		tile_sticky_ = tile_total > 0 && (double)tile_total * kGroup >= kTileStickyShare * (double)all;
-	}
+	last_round_work_ = (double)cubes / kGroup / rounds * (double)N_;
+	tile_sticky_ = tile_total > 0 && (double)tile_total * kGroup >= kTileStickyShare * (double)cubes;
 	for (int li = 0; li < nl; li++) {
 		const QLane& L = *run[li].L;
 		cnt_.tile_expansions += L.h_ctl->tile_total;
@@ -2103,9 +2124,7 @@ bool Engine::run_inner_device(std::vector<InnerSearch*>& searches, const std::ve
 			const QSearch& q = L.h_search[i];
 			InnerSearch& s = *searches[(size_t)run[li].idx[i]];
 			if (q.done == 2) { redo_.push_back(&s); continue; }          // its queue outgrew the slab: untouched here, re-run by run_inner through the host queues
-			s.best = q.best; s.improved = q.improved != 0; s.done = true;
-			s.best_node = Node{q.bx, q.by, q.bz, q.bw, 0.f, 0.f, 0};
-			s.pops = q.pops; s.cubes = q.cubes; s.min_ub = q.min_ub;
+			s.finish(SearchOut::of(q));
 		}
 	}
 	t_collect_ += now_ms() - t2;
@@ -2118,10 +2137,9 @@ void Engine::run_inner(std::vector<InnerSearch*>& searches, const std::vector<Ro
 	for (auto* s : searches)
 		if (s->rot_slot < 0 || (size_t)s->rot_slot >= rots.size()) throw std::logic_error("goicp: rotation slot out of range");
 	if (p_.device_queues && p_.trans_batch > 1) {
-		const double t_begin = now_ms();
 		redo_.clear();
-		const bool ok = run_inner_device(searches, rots);
-		bnb_ms_ += now_ms() - t_begin;
+		bool ok;
+		{ ScopedMs t{bnb_ms_}; ok = run_inner_device(searches, rots); }
 		if (ok && redo_.empty()) return;
 		if (ok) {
 			// searches whose queue outgrew its slab (they have not been touched): through the host queues, alone
@@ -2147,25 +2165,20 @@ void Engine::run_inner(std::vector<InnerSearch*>& searches, const std::vector<Ro
 void Engine::run_inner_host(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots, bool fallback)
 {
 	DeviceGuard guard(dev_);
-	const double t_begin = now_ms();
-	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{bnb_ms_, t_begin};
+	ScopedMs acc{bnb_ms_};
 	const int K0 = std::max(1, p_.trans_batch);
 	const bool widen = fallback && p_.adaptive_k && p_.stale_widen && K0 > 1;
-	const size_t nrot = rots.size();
-	ensure_batch(1, nrot);
-	std::memcpy(h_rots_, rots.data(), sizeof(Rot9) * nrot);
-	HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9) * nrot, hipMemcpyHostToDevice, stream_));
+	upload_rots(rots);
+	Stage& st = stage_;
 
 	// One group per round.  (Measured on MI355X: splitting the searches into two alternating groups so
 	// that the host digests one group's results while the GPU evaluates the other's did not pay --
 	// 0.087 s vs 0.083 s on the full bunny: the rounds are bound by the small launches themselves, not by
-	// host work.  The two-stage plumbing is kept for a device-resident queue.)
-	std::vector<InnerSearch*> grp[2];
-	grp[0] = searches;
-
-	auto submit = [&](int k) -> bool {
+	// host work.)
+	auto submit = [&]() -> bool {
+		ScopedMs t{t_submit_};
 		size_t B = 0;
-		for (auto* s : grp[k]) {
+		for (auto* s : searches) {
 			s->parents.clear();
 			if (s->done) continue;
 			const int K = !widen ? K0 : (s->stale >= 3 ? 16 * K0 : (s->stale >= 1 ? 4 * K0 : K0));
@@ -2183,10 +2196,9 @@ void Engine::run_inner_host(std::vector<InnerSearch*>& searches, const std::vect
 			B += 8 * s->parents.size();
 		}
 		if (B == 0) return false;
-		ensure_stage(k, B);
-		Stage& st = stage_[k];
+		ensure_stage(B);
 		size_t o = 0;
-		for (auto* s : grp[k])
+		for (auto* s : searches)
 			for (const Node& par : s->parents) {
 				// the kernels expand the 8 children themselves (load_group in device.hip; jly_goicp.cpp:262-273)
 				ParentRec& r = st.h_parents[o++];
@@ -2200,17 +2212,14 @@ void Engine::run_inner_host(std::vector<InnerSearch*>& searches, const std::vect
 		HIPCHK(hipEventRecord(st.ev, stream_));
 		return true;
 	};
-	auto collect = [&](int k) {
-		Stage& st = stage_[k];
-		HIPCHK(hipEventSynchronize(st.ev));
+	auto collect = [&] {
+		ScopedMs t{t_collect_};
 		size_t o = 0;
-		for (auto* s : grp[k]) {
+		for (auto* s : searches) {
 			const float best_before = s->best;
-			for (const Node& par : s->parents) {
-				Node c{};
-				c.w = par.w / 2;
+			for (const Node& par : s->parents)
 				for (int j = 0; j < 8; j++, o++) {
-					c.x = par.x + (j & 1) * c.w; c.y = par.y + (j >> 1 & 1) * c.w; c.z = par.z + (j >> 2 & 1) * c.w;
+					Node c = child_cube(par, j);
 					const float ub = st.h_ub[o], lb = st.h_ub[st.B + o];
 					s->cubes++;
 					if (trans_boxed_ && !in_box(c, trans_lo_, trans_hi_)) continue;   // outside the configured translation range
@@ -2221,19 +2230,14 @@ void Engine::run_inner_host(std::vector<InnerSearch*>& searches, const std::vect
 					c.ub = ub; c.lb = lb;
 					s->pq.push(c);
 				}
-			}
 			if (!s->parents.empty()) s->stale = s->best < best_before ? 0 : s->stale + 1;
 		}
 	};
-	auto timed = [&](double& acc, auto&& fn) { const double t0 = now_ms(); auto r = fn(); acc += now_ms() - t0; return r; };
-	bool fly[2] = {timed(t_submit_, [&] { return submit(0); }), !grp[1].empty() && submit(1)};
-	while (fly[0] || fly[1])
-		for (int k = 0; k < 2; k++)
-			if (fly[k]) {
-				timed(t_wait_, [&] { HIPCHK(hipEventSynchronize(stage_[k].ev)); return 0; });
-				timed(t_collect_, [&] { collect(k); return 0; });
-				fly[k] = !cancel_.load() && timed(t_submit_, [&] { return submit(k); });
-			}
+	while (submit()) {
+		{ ScopedMs t{t_wait_}; HIPCHK(hipEventSynchronize(st.ev)); }
+		collect();
+		if (cancel_.load()) break;
+	}
 	HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -2242,11 +2246,7 @@ float Engine::inner_bnb(const float R[9], int level, float incumbent, float best
 	DeviceGuard guard(dev_);
 	std::vector<Rot9> rots(1);
 	std::memcpy(rots[0].r, R, sizeof(float) * 9);
-	InnerSearch s;
-	s.rot_slot = 0;
-	s.coeff = rot_coeff(level);
-	s.best = incumbent;
-	s.pq.push(trans_root_);   // jly_goicp.cpp:50-53
+	InnerSearch s = fresh_search(0, rot_coeff(level), incumbent);
 	std::vector<InnerSearch*> v{&s};
 	run_inner(v, rots);
 	if (best_node && s.improved) { best_node[0] = s.best_node.x; best_node[1] = s.best_node.y; best_node[2] = s.best_node.z; best_node[3] = s.best_node.w; }
@@ -2291,8 +2291,7 @@ void Engine::adopt(float err, const float R[9], const float t[3])
 float Engine::icp_from(float R[9], float t[3])
 {
 	TraceRange tr("goicp:icp_run+rescore");
-	const double t0 = now_ms();
-	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{icp_ms_, t0};
+	ScopedMs acc{icp_ms_};
 	// GoICP::ICP (jly_goicp.cpp:93-132): ICP3D::Run, then re-score with the DT
 	int it = 0;
 	if (icp_comm_) {
@@ -2303,7 +2302,7 @@ float Engine::icp_from(float R[9], float t[3])
 		icp_run(R, t, p_.icp_max_iter, icp_err_diff_, &it);
 	}
 	const float e = eval_sse(R, t);
-	if (p_.verbose > 1) std::fprintf(stderr, "[goicp] ICP run: %d iterations, %.2f ms, error %.6g (rot pops so far %lld, cube bounds %lld)\n", it, now_ms() - t0, e, cnt_.rot_pops, cnt_.cubes);
+	if (p_.verbose > 1) std::fprintf(stderr, "[goicp] ICP run: %d iterations, %.2f ms, error %.6g (rot pops so far %lld, cube bounds %lld)\n", it, now_ms() - acc.t0, e, cnt_.rot_pops, cnt_.cubes);
 	return e;
 }
 
@@ -2342,7 +2341,7 @@ void Engine::register_begin()
 	std::memset(level_hist_, 0, sizeof(level_hist_));
 	cnt_ = Counters{};
 	while (!queue_.empty()) queue_.pop();
-	if (flow_mode()) { ensure_queues(kFlowSearches); flow_reset(); }
+	if (flow_mode()) { ensure_lane(0, kFlowSearches); flow_reset(); }
 	const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 	const float Z[3] = {0, 0, 0};
 	// initial error (jly_goicp.cpp:357-372) and initial ICP (:375-391)
@@ -2364,11 +2363,10 @@ void Engine::register_begin()
 		// parents' bounds are 0, so nothing is lost
 		int k = 0;
 		for (int a = 0; a < 8; a++) {
-			Node c1 = root; c1.w = root.w / 2; c1.l = 1;
-			c1.x = root.x + (a & 1) * c1.w; c1.y = root.y + (a >> 1 & 1) * c1.w; c1.z = root.z + (a >> 2 & 1) * c1.w;
+			const Node c1 = child_cube(root, a);
 			for (int b = 0; b < 8; b++, k++) {
-				Node c2 = c1; c2.w = c1.w / 2; c2.l = 2;
-				c2.x = c1.x + (b & 1) * c2.w; c2.y = c1.y + (b >> 1 & 1) * c2.w; c2.z = c1.z + (b >> 2 & 1) * c2.w;
+				Node c2 = child_cube(c1, b);
+				c2.l = 2;
 				if (rot_boxed_ && !in_box(c2, rot_lo_, rot_hi_)) continue;
 				if (k % world_ == rank_) queue_.push(c2);
 			}
@@ -2381,11 +2379,9 @@ void Engine::register_begin()
 void Engine::make_kids(const std::vector<Node>& parents, std::vector<Kid>& kids)
 {
 	for (const Node& parent : parents) {
-		Node c{};
-		c.w = parent.w / 2;          // jly_goicp.cpp:427-428
-		c.l = parent.l + 1;
 		for (int j = 0; j < 8; j++) {
-			c.x = parent.x + (j & 1) * c.w; c.y = parent.y + (j >> 1 & 1) * c.w; c.z = parent.z + (j >> 2 & 1) * c.w;
+			Node c = child_cube(parent, j);          // jly_goicp.cpp:427-428
+			c.l = parent.l + 1;
 			float v1 = c.x + c.w / 2, v2 = c.y + c.w / 2, v3 = c.z + c.w / 2;
 			// pi-ball cull (:443): float sqrt, double subtraction and comparison
 			if ((double)std::sqrt(v1 * v1 + v2 * v2 + v3 * v3) - kSQRT3 * (double)c.w / 2 > kPI) continue;
@@ -2451,14 +2447,6 @@ void Engine::process_parents(const std::vector<Node>& parents)
 	if (kids.empty()) return;
 	std::vector<Rot9> rots(kids.size());
 	for (size_t i = 0; i < kids.size(); i++) std::memcpy(rots[i].r, kids[i].R, sizeof(float) * 9);
-	const Node troot = trans_root_;
-	auto fresh = [&](size_t slot, float coeff) {
-		InnerSearch s;
-		s.rot_slot = (int)slot; s.coeff = coeff; s.best = opt_err_;
-		s.pq.push(troot);
-		return s;
-	};
-	auto out = [](const InnerSearch& s) { return SearchOut{s.best, s.improved, s.best_node, s.pops, s.cubes, s.min_ub}; };
 
 	if (p_.wide_children) {
 		// every child's upper-bound AND lower-bound search in lock-step: one launch per round covers
@@ -2466,7 +2454,7 @@ void Engine::process_parents(const std::vector<Node>& parents)
 		// start (the reference lets earlier children tighten it: fewer nodes, same bounds).
 		std::vector<InnerSearch> ubs, lbs;
 		ubs.reserve(kids.size()); lbs.reserve(kids.size());
-		for (size_t i = 0; i < kids.size(); i++) { ubs.push_back(fresh(i, 0.f)); lbs.push_back(fresh(i, rot_coeff(kids[i].node.l))); }
+		for (size_t i = 0; i < kids.size(); i++) { ubs.push_back(fresh_search((int)i, 0.f, opt_err_)); lbs.push_back(fresh_search((int)i, rot_coeff(kids[i].node.l), opt_err_)); }
 		std::vector<InnerSearch*> ptr;
 		// a child's two searches side by side: they share the rotation, expand the same root and a third of the same
 		// depth-1 nodes in the same rounds, and the bound kernel walks the expansions in search order -- the second of the
@@ -2474,19 +2462,19 @@ void Engine::process_parents(const std::vector<Node>& parents)
 		for (size_t i = 0; i < kids.size(); i++) { ptr.push_back(&ubs[i]); ptr.push_back(&lbs[i]); }
 		run_inner(ptr, rots);
 		for (size_t i = 0; i < kids.size(); i++) {
-			if (handle_ub(kids[i], out(ubs[i]))) return;
-			handle_lb(kids[i], out(lbs[i]));
+			if (handle_ub(kids[i], SearchOut::of(ubs[i]))) return;
+			handle_lb(kids[i], SearchOut::of(lbs[i]));
 		}
 	} else {
 		for (size_t i = 0; i < kids.size(); i++) {
-			InnerSearch u = fresh(i, 0.f);
+			InnerSearch u = fresh_search((int)i, 0.f, opt_err_);
 			std::vector<InnerSearch*> p1{&u};
 			run_inner(p1, rots);
-			if (handle_ub(kids[i], out(u))) return;
-			InnerSearch l = fresh(i, rot_coeff(kids[i].node.l));
+			if (handle_ub(kids[i], SearchOut::of(u))) return;
+			InnerSearch l = fresh_search((int)i, rot_coeff(kids[i].node.l), opt_err_);
 			std::vector<InnerSearch*> p2{&l};
 			run_inner(p2, rots);
-			handle_lb(kids[i], out(l));
+			handle_lb(kids[i], SearchOut::of(l));
 			if (cancel_.load()) return;
 		}
 	}
@@ -2547,22 +2535,20 @@ void Engine::flow_fallback()
 	for (Flight& f : todo) {
 		std::vector<Rot9> rots(1);
 		std::memcpy(rots[0].r, f.kid.R, sizeof(float) * 9);
-		InnerSearch u, l;
-		u.rot_slot = l.rot_slot = 0; u.coeff = 0.f; l.coeff = rot_coeff(f.kid.node.l); u.best = l.best = f.incumbent;
-		u.pq.push(trans_root_); l.pq.push(trans_root_);
+		InnerSearch u = fresh_search(0, 0.f, f.incumbent), l = fresh_search(0, rot_coeff(f.kid.node.l), f.incumbent);
 		std::vector<InnerSearch*> ptr{&u, &l};
 		run_inner_host(ptr, rots, true);
-		if (handle_ub(f.kid, SearchOut{u.best, u.improved, u.best_node, u.pops, u.cubes, u.min_ub})) return;
-		handle_lb(f.kid, SearchOut{l.best, l.improved, l.best_node, l.pops, l.cubes, l.min_ub});
+		if (handle_ub(f.kid, SearchOut::of(u))) return;
+		handle_lb(f.kid, SearchOut::of(l));
 	}
 }
 
 int Engine::flow_step(int max_rot_pops)
 {
 	TraceRange tr("goicp:flow_step");
-	const double t_begin = now_ms();
-	struct Acc { double& a; double t0; ~Acc() { a += now_ms() - t0; } } acc{bnb_ms_, t_begin};
+	ScopedMs acc{bnb_ms_};
 	const QParams qp = queue_params();
+	QLane& L = ql_[0];                // the flow's one lane; its stream is stream_ (ensure_lane)
 	ensure_batch(1, kFlowSearches / 2);
 	if (!h_qinit_) {
 		h_qinit_.alloc(kFlowSearches);
@@ -2577,18 +2563,7 @@ int Engine::flow_step(int max_rot_pops)
 		const int P = std::max(1, std::min(std::min(p_.rot_batch, rot_ramp_), kFlowSearches / 16));
 		if (!converged_ && !queue_.empty() && pops < max_rot_pops && flow_active_ <= (flights_.empty() ? kFlowSearches : p_.flow) &&
 		    free_search_.size() >= (size_t)16 * P && free_rot_.size() >= (size_t)8 * P) {
-			std::vector<Node> parents;
-			while ((int)parents.size() < P && !queue_.empty() && pops < max_rot_pops) {
-				const Node parent = queue_.top();
-				if ((opt_err_ - parent.lb) <= sse_thresh_) {      // jly_goicp.cpp:416 -- only final once nothing is in flight
-					if (parents.empty() && unhandled() == 0) { queue_.pop(); cnt_.rot_pops++; pops++; converged_ = true; }
-					break;
-				}
-				queue_.pop();
-				cnt_.rot_pops++;
-				pops++;
-				parents.push_back(parent);
-			}
+			const std::vector<Node> parents = pop_parents(P, max_rot_pops, pops, unhandled() == 0);   // the stop rule is only final once nothing is in flight
 			if (!parents.empty()) {
 				rot_ramp_ = std::min(rot_ramp_ * 2, 1 << 20);
 				std::vector<Kid> kids;
@@ -2609,7 +2584,7 @@ int Engine::flow_step(int max_rot_pops)
 				if (n) {
 					HIPCHK(hipMemcpyAsync(d_rots_, h_rots_, sizeof(Rot9) * (kFlowSearches / 2), hipMemcpyHostToDevice, stream_));
 					HIPCHK(hipMemcpyAsync(d_qinit_, h_qinit_, sizeof(QInit) * n, hipMemcpyHostToDevice, stream_));
-					HIPCHK(launch_bnb_init_list(ql_[0].d_search, ql_[0].d_nodes, d_qinit_, n, qp, stream_));
+					HIPCHK(launch_bnb_init_list(L.d_search, L.d_nodes, d_qinit_, n, qp, stream_));
 					flow_active_ += n;
 				}
 			}
@@ -2621,39 +2596,28 @@ int Engine::flow_step(int max_rot_pops)
 		if (p_.adaptive_k && qp.K >= 32) qr.K = flow_active_ <= 16 ? kQueueRoundPop : (flow_active_ <= 64 ? std::min(kQueueRoundPop, 2 * qp.K) : qp.K);
 		// most the round can list: the queue kernel widens a stale search's step up to x4 (stale_widen), as in run_inner_device --
 		// sizing the evaluation's grid by q_hi_ * K left the expansions listed beyond it unevaluated in trimmed runs (one workgroup each)
-		const int max_groups = (int)std::min<size_t>((size_t)q_hi_ * (size_t)std::min(qr.kmax, 4 * qr.K), (size_t)ql_[0].list_cap);
-		for (int r = 0; r < 3; r++) {
-			HIPCHK(launch_bnb_queue(ql_[0].d_search, ql_[0].d_nodes, q_hi_, qr, ql_[0].d_parents[q_parity_ ^ 1], ql_[0].d_parents[q_parity_], ql_[0].d_ub, ql_[0].d_lb, ql_[0].d_scratch, ql_[0].d_ctl, q_parity_, stream_));
-			HIPCHK(launch_bounds_queue(d_src_, (int)N_, bounds_dt(), d_rots_, ql_[0].d_parents[q_parity_], &ql_[0].d_ctl->n_groups[q_parity_], &ql_[0].d_ctl->work[q_parity_][0], &ql_[0].d_ctl->chunks,
-			                           max_groups, inliers_, ql_[0].d_scratch, ql_[0].d_ub, ql_[0].d_lb, stream_));
-			q_parity_ ^= 1;
-			cnt_.bounds_launches++;
-			queue_rounds_++;
-		}
-		HIPCHK(hipMemcpyAsync(ql_[0].h_ctl, ql_[0].d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
-		HIPCHK(hipMemcpyAsync(ql_[0].h_search, ql_[0].d_search, sizeof(QSearch) * (size_t)q_hi_, hipMemcpyDeviceToHost, stream_));
+		const int max_groups = (int)std::min<size_t>((size_t)q_hi_ * (size_t)std::min(qr.kmax, 4 * qr.K), (size_t)L.list_cap);
+		for (int r = 0; r < 3; r++, q_parity_ ^= 1) queue_round(L, q_hi_, qr, q_parity_, max_groups, RoundOpts{});
+		HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
+		HIPCHK(hipMemcpyAsync(L.h_search, L.d_search, sizeof(QSearch) * (size_t)q_hi_, hipMemcpyDeviceToHost, stream_));
 		t_submit_ += now_ms() - t0;
-		const double t1 = now_ms();
-		HIPCHK(hipStreamSynchronize(stream_));
-		t_wait_ += now_ms() - t1;
-		if (ql_[0].h_ctl->overflow) { flow_fallback(); continue; }
+		{ ScopedMs t{t_wait_}; HIPCHK(hipStreamSynchronize(stream_)); }
+		if (L.h_ctl->overflow) { flow_fallback(); continue; }
 		// ---- harvest: every child whose two searches have stopped, in admission order ----
 		const double t2 = now_ms();
 		int active = 0;
 		bool stop = false;
 		for (Flight& f : flights_) {
 			if (f.handled) continue;
-			const QSearch& u = ql_[0].h_search[f.s_ub];
-			const QSearch& l = ql_[0].h_search[f.s_lb];
+			const QSearch& u = L.h_search[f.s_ub];
+			const QSearch& l = L.h_search[f.s_lb];
 			// a search that has stopped has no pending children: done is only set in the selection phase, after the digest
 			if (!u.done || !l.done) { active += (u.done ? 0 : 1) + (l.done ? 0 : 1); continue; }
 			f.handled = true;
 			free_search_.push_back(f.s_ub); free_search_.push_back(f.s_lb); free_rot_.push_back(f.rot_slot);
 			if (stop) continue;                                                  // early exit taken: the rest is abandoned
-			const SearchOut su{u.best, u.improved != 0, Node{u.bx, u.by, u.bz, u.bw, 0.f, 0.f, 0}, u.pops, u.cubes, u.min_ub};
-			const SearchOut sl{l.best, l.improved != 0, Node{l.bx, l.by, l.bz, l.bw, 0.f, 0.f, 0}, l.pops, l.cubes, l.min_ub};
-			if (handle_ub(f.kid, su)) { stop = true; continue; }
-			handle_lb(f.kid, sl);
+			if (handle_ub(f.kid, SearchOut::of(u))) { stop = true; continue; }
+			handle_lb(f.kid, SearchOut::of(l));
 		}
 		t_collect_ += now_ms() - t2;
 		flow_active_ = active;
@@ -2663,6 +2627,24 @@ int Engine::flow_step(int max_rot_pops)
 		if (pops >= max_rot_pops && flights_.empty()) break;
 	}
 	return pops;
+}
+
+std::vector<Node> Engine::pop_parents(int P, int max_rot_pops, int& pops, bool may_converge)
+{
+	std::vector<Node> parents;
+	while ((int)parents.size() < P && !queue_.empty() && pops < max_rot_pops) {
+		const Node parent = queue_.top();
+		if ((opt_err_ - parent.lb) <= sse_thresh_) {      // jly_goicp.cpp:416
+			// single rank: global convergence.  sharded: this rank's frontier can no longer improve
+			if (parents.empty() && may_converge) { queue_.pop(); cnt_.rot_pops++; pops++; converged_ = true; }
+			break;
+		}
+		queue_.pop();
+		cnt_.rot_pops++;
+		pops++;
+		parents.push_back(parent);
+	}
+	return parents;
 }
 
 StepStatus Engine::register_step(int max_rot_pops)
@@ -2683,19 +2665,7 @@ StepStatus Engine::register_step(int max_rot_pops)
 		// (full bunny: 310 launches / 63 ms at a fixed 8, 52 launches / 55 ms at 64).
 		const int P = p_.wide_children ? std::max(1, std::min(p_.rot_batch, rot_ramp_)) : 1;
 		rot_ramp_ = std::min(rot_ramp_ * 2, 1 << 20);
-		std::vector<Node> parents;
-		while ((int)parents.size() < P && !queue_.empty() && pops < max_rot_pops) {
-			Node parent = queue_.top();
-			if ((opt_err_ - parent.lb) <= sse_thresh_) {      // jly_goicp.cpp:416
-				// single rank: global convergence.  sharded: this rank's frontier can no longer improve
-				if (parents.empty()) { queue_.pop(); cnt_.rot_pops++; pops++; converged_ = true; }
-				break;
-			}
-			queue_.pop();
-			cnt_.rot_pops++;
-			pops++;
-			parents.push_back(parent);
-		}
+		std::vector<Node> parents = pop_parents(P, max_rot_pops, pops, true);
 		if (parents.empty()) break;
 		// ub_share: part of a batch goes to the queued cubes with the smallest upper bound seen inside them, whatever their lower
 		// bound -- the early exit (jly_goicp.cpp:527) needs a pose below SSEThresh, and that is found by refining a promising

@@ -210,7 +210,7 @@ public:
 	void icp_step();   // one ICP iteration on the engine's current pose (ICP::kdTreeGPUStep)
 	// measured ceiling of the gather path (4-byte loads into the resident DT): lookups/s; mode 0 coalesced, 1 divergent
 	double probe_gather(int mode, size_t window_bytes);
-	long long debug_cache_hits(const float R[9], const float t[3]);
+	long long debug_cache_hits(const float R[9], const float t[3]);   // queries of a repeated pass that skipped the tree walk (-1: cache off)
 	// test: the trimmed ICP's selection of the num smallest of d2[0..n) on the device, as inclusion flags (kernel 0 = the iteration's
 	// choice by size, 1 = register kernel, n <= 32 768, 2 = streaming kernel)
 	void debug_select(const float* d2, size_t n, int num, int kernel, unsigned char* include);
@@ -224,7 +224,7 @@ public:
 	// measurement / test: the 8 children of nseg x n expansions (segment i: rotation i, parents4[(i*n + e)*4 ..] = corner xyz + width) through
 	// the LDS-tile kernel and through the direct kernel; out arrays hold 8*nseg*n floats each; ms[0] tile, ms[1] direct (per launch)
 	void debug_bounds_tile(const float* rots9, const float* parents4, int nseg, int n, int level, int chunks, float* ub_tile, float* lb_tile,
-	                       float* ub_direct, float* lb_direct, float ms[2], unsigned stats[2]);   // queries of a repeated pass that skipped the tree walk (-1: cache off)
+	                       float* ub_direct, float* lb_direct, float ms[2], unsigned stats[2]);
 
 	// ---- registration ----
 	void run();                                  // FastGoICP::run / GoICP::Register
@@ -283,15 +283,31 @@ private:
 	void finish_source_swap();                       // set_source / set_source_voxel after load_source: the search and ICP state of a fresh engine
 	double source_order_ms_ = 0, voxel_ms_ = 0;
 	void ensure_batch(size_t B, size_t K);
-	void ensure_stage(int k, size_t B);
+	void ensure_stage(size_t B);
+	void ensure_bounds_scratch(int B, hipStream_t s);   // d_scratch_ holds a launch of B cube bounds; growing waits for stream_ and s only
+	void upload_rots(const std::vector<Rot9>& rots);    // the batch's rotation table -> d_rots_, on stream_
 	void run_inner(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);
 	void run_inner_host(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots, bool fallback = false);
 	bool run_inner_device(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);   // false: a round's lists overflowed, nothing was changed; redo_: searches whose own queue did
 	std::vector<InnerSearch*> redo_;
-	void ensure_queues(size_t nsearch);
 	void process_parents(const std::vector<Node>& parents);
 	struct Kid { Node node; float R[9]; float parent_lb; };                       // a rotation child and its Rodrigues matrix
-	struct SearchOut { float best; bool improved; Node best_node; long long pops, cubes; float min_ub; };   // what an inner search returns (min_ub: smallest upper bound of any cube it evaluated)
+	struct SearchOut {   // what an inner search returns (min_ub: smallest upper bound of any cube it evaluated)
+		float best; bool improved; Node best_node; long long pops, cubes; float min_ub;
+		static SearchOut of(const InnerSearch& s);   // from the host's record of a search
+		static SearchOut of(const QSearch& q);       // from the device queues' record
+	};
+	InnerSearch fresh_search(int rot_slot, float coeff, float incumbent) const;   // a search about to start: the translation root queued (jly_goicp.cpp:50-53)
+	// octant j of a cube: the same float expressions wherever a cube is split (jly_goicp.cpp:262-273, :427-441)
+	static Node child_cube(const Node& parent, int j)
+	{
+		Node c{};
+		c.w = parent.w / 2;
+		c.x = parent.x + (j & 1) * c.w; c.y = parent.y + (j >> 1 & 1) * c.w; c.z = parent.z + (j >> 2 & 1) * c.w;
+		return c;
+	}
+	// up to P rotation parents off the queue, by the stop rule of jly_goicp.cpp:416; may_converge: a first parent inside SSEThresh ends the search
+	std::vector<Node> pop_parents(int P, int max_rot_pops, int& pops, bool may_converge);
 	void make_kids(const std::vector<Node>& parents, std::vector<Kid>& kids);
 	bool handle_ub(Kid& k, const SearchOut& s);
 	void handle_lb(Kid& k, const SearchOut& s);
@@ -372,11 +388,11 @@ private:
 	Buf<Rot9> d_rots_; PinnedBuf<Rot9> h_rots_;
 	Buf<float> d_ub_, d_lb_; PinnedBuf<float> h_ub_, h_lb_;
 	Buf<float> d_scratch_;
-	struct Stage {   // per-group staging of the pipelined inner-BnB rounds
+	struct Stage {   // staging of a round of the host-queue inner BnB (run_inner_host)
 		Buf<ParentRec> d_parents; PinnedBuf<ParentRec> h_parents;   // one record per expansion; the kernels derive the 8 children
 		Buf<float> d_ub; PinnedBuf<float> h_ub;   // ub[B] followed by lb[B]
 		size_t cap = 0, B = 0; Event ev;          // cap: cube bounds the four buffers hold
-	} stage_[2];
+	} stage_;
 	// device-resident inner-BnB queues (bnbqueue.hip).  A LANE is one self-contained set of them -- search slots, node slabs, the
 	// round's two expansion lists with their bounds and partial sums, the sort buffers, the control block with its pinned snapshots --
 	// driven on its own stream.  Lane 0 always exists; lane 1 is created for batches cut in two (Params::lanes, run_inner_device)
@@ -402,6 +418,10 @@ private:
 	} ql_[kMaxLanes];
 	void lane_source_buffers(QLane& L);   // what a lane derives from the source: the sorted-round setup, the scratch sized by it, the tile list
 	void ensure_lane(int li, size_t nsearch);
+	// one round of a lane (engine.cpp queue_round).  tiles / twins: the tile list / the twin lists are in use; deep: the 64-VGPR build of the queue kernel
+	// (the launcher's default); sorted: footprint-ordered items; read_ctl: QCtl is read back behind the round's selection (ev_ctl); count: the round counters move
+	struct RoundOpts { bool tiles = false, twins = false, deep = true, sorted = false, read_ctl = false, count = true; };
+	void queue_round(QLane& L, int nsearch, const QParams& qp, int parity, int max_groups, const RoundOpts& o);
 	double last_round_work_ = 0;                            // point-expansions (expansions x source points) of the previous batch's mean round
 	static constexpr double kLaneMinWork = 64e6;            // the auto mode's bar on last_round_work_ (run_inner_device)
 	static constexpr int kAutoLanes = 3;                    // lanes the auto mode cuts a batch into (measured 2 / 3 / 4 at the end of round 4: bunny mse 3e-5
