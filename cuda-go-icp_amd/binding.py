@@ -91,6 +91,10 @@ class CIcpRobust(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("scale", C.c_float)]
 
 
+class CSourceFilter(C.Structure):
+    _fields_ = [("voxel", C.c_float), ("radius", C.c_float), ("min_neighbors", C.c_int32)]
+
+
 class CPoseInfoOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
 
@@ -186,6 +190,12 @@ SYMBOLS = {
     "goicp_voxel_downsample_host": (C.c_int, [_fp, C.c_size_t, C.c_float, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     "goicp_voxel_downsample": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
     "goicp_set_source_voxel": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, C.POINTER(C.c_size_t)]),
+    "goicp_radius_outlier_removal_host": (C.c_int, [_fp, C.c_size_t, C.c_float, C.c_int32, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_size_t)]),
+    "goicp_radius_outlier_removal": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, C.c_int32, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_size_t)]),
+    "goicp_source_filter_default": (None, [C.POINTER(CSourceFilter)]),
+    "goicp_set_source_filtered": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourceFilter), C.POINTER(C.c_size_t)]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

@@ -2,6 +2,7 @@
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
 //                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
+//                                [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -37,6 +38,13 @@
 //               no engine exists yet), every listed cloud on the device as part of its swap (goicp_set_source_voxel: the same bits).
 //               --target-voxel V reduces the target the same way, on the host, before the engine is created.  V must be a finite number > 0
 //               -- refused before any device is touched; the .toml surface is the reference's and stays as it is
+//   --outlier-radius R --outlier-min-neighbors K   (both or neither) radius outlier removal, after --voxel: a point of the source -- and
+//               of every cloud of --source-list -- with fewer than K other points within R (cloud units after `resize`) is dropped before
+//               the cloud is registered.  The config's own source is filtered on the host (goicp_radius_outlier_removal_host), every listed
+//               cloud on the device as part of its swap (goicp_set_source_filtered: the same bits); each prints "kept m of n".
+//               --target-outlier-radius R --target-outlier-min-neighbors K filter the target the same way, on the host, after
+//               --target-voxel and before the engine is created.  R must be finite, > 0 and R * R a normal float, K an integer >= 1 --
+//               refused before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -74,7 +82,7 @@ static std::string numbered(const std::string& p, int k)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
@@ -92,6 +100,9 @@ int main(int argc, char** argv)
 	std::vector<std::string> source_list;
 	const char *voxel_arg = nullptr, *tvoxel_arg = nullptr;
 	float voxel = 0.f, target_voxel = 0.f;
+	const char *orad_arg[2] = {nullptr, nullptr}, *omin_arg[2] = {nullptr, nullptr};   // [0] the source's, [1] the target's
+	float outlier_radius[2] = {0.f, 0.f};
+	int outlier_min[2] = {0, 0};
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -110,6 +121,10 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--source-list")) list_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--voxel")) voxel_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-voxel")) tvoxel_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--outlier-radius")) orad_arg[0] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--outlier-min-neighbors")) omin_arg[0] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--target-outlier-radius")) orad_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--target-outlier-min-neighbors")) omin_arg[1] = i + 1 < argc ? argv[++i] : "";
 	}
 	for (int k = 0; k < 2; k++) {
 		// a bad voxel is refused before any device is touched
@@ -122,6 +137,29 @@ int main(int argc, char** argv)
 			return 2;
 		}
 		(k ? target_voxel : voxel) = v;
+	}
+	for (int k = 0; k < 2; k++) {
+		// a bad outlier filter is refused before any device is touched
+		const char* pre = k ? "--target-outlier" : "--outlier";
+		if (!orad_arg[k] && !omin_arg[k]) continue;
+		if (!orad_arg[k] || !omin_arg[k]) {
+			std::fprintf(stderr, "error: %s-radius and %s-min-neighbors go together\n", pre, pre);
+			return 2;
+		}
+		char* end = nullptr;
+		const float r = std::strtof(orad_arg[k], &end);
+		const float r2 = r * r;
+		if (end == orad_arg[k] || *end != '\0' || !(r > 0.f) || !(r2 >= 1.17549435e-38f) || !(r2 <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: %s-radius needs a finite radius > 0 whose square is a normal float, got '%s'\n", pre, orad_arg[k]);
+			return 2;
+		}
+		const long kk = std::strtol(omin_arg[k], &end, 10);
+		if (end == omin_arg[k] || *end != '\0' || kk < 1 || kk > 2147483647L) {
+			std::fprintf(stderr, "error: %s-min-neighbors needs an integer >= 1, got '%s'\n", pre, omin_arg[k]);
+			return 2;
+		}
+		outlier_radius[k] = r;
+		outlier_min[k] = (int)kk;
 	}
 	if (list_arg) {
 		// refused before any device is touched
@@ -236,6 +274,19 @@ int main(int argc, char** argv)
 			std::printf("%s voxel %g: %zu of %zu points kept\n", k ? "target" : "source", v, m, cloud.size());
 			cloud.swap(reduced);
 		}
+		for (int k = 0; k < 2; k++) {
+			// after the voxel grid; the host function again
+			std::vector<P3>& cloud = k ? target : source;
+			if (!(outlier_radius[k] > 0.f) || cloud.empty()) continue;
+			std::vector<P3> kept(cloud.size());
+			size_t m = 0;
+			check(goicp_radius_outlier_removal_host(&cloud[0].x, cloud.size(), outlier_radius[k], outlier_min[k], &kept[0].x, nullptr, nullptr, &m));
+			kept.resize(m);
+			std::printf("%s outlier radius %g min neighbors %d: kept %zu of %zu points\n", k ? "target" : "source", outlier_radius[k], outlier_min[k], m,
+			            cloud.size());
+			if (m == 0) throw std::runtime_error(std::string(k ? "target" : "source") + ": the outlier filter keeps no point");
+			cloud.swap(kept);
+		}
 		std::printf("mode %d: source %zu points, target %zu points, mse_threshold %g\n", config.mode, source.size(),
 		            target.size(), config.mse_threshold);
 		goicp_params p;
@@ -344,7 +395,13 @@ int main(int argc, char** argv)
 			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
 			const auto t0 = std::chrono::steady_clock::now();
 			size_t kept = next.size();
-			if (voxel > 0.f) kept = engine.set_source(next, voxel); else engine.set_source(next);
+			if (outlier_radius[0] > 0.f) {
+				goicp_source_filter f;
+				goicp_source_filter_default(&f);
+				f.voxel = voxel; f.radius = outlier_radius[0]; f.min_neighbors = outlier_min[0];
+				kept = engine.set_source(next, f);
+				std::printf("source %zu outlier radius %g min neighbors %d: kept %zu of %zu points\n", k + 1, f.radius, f.min_neighbors, kept, next.size());
+			} else if (voxel > 0.f) kept = engine.set_source(next, voxel); else engine.set_source(next);
 			const double swap_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 			if (config.mode <= 2) {
 				for (int i = 0; i < iters; i++) check(goicp_icp_step(h));

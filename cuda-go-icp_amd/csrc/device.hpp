@@ -429,6 +429,16 @@ struct VoxelFrame {
 // stream has drained
 hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& f, float* d_out, int32_t* d_count, int* m, hipStream_t stream,
                                    hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ---- radius outlier removal on the device (kdbuild.hip; goicp_radius_outlier_removal_host is its host twin) ----
+// f: the frame of the grid of pitch f.voxel = r * 1.03125f (radius_frame, kdtree.cpp); r2 = r * r in float.  d_out: room for 3 n floats,
+// the first 3 m are written (the kept points, input order, own bits); d_index (may be null): room for n ints, the first m are written (the
+// kept points' indices, ascending); d_count (may be null): n ints, min(#neighbours, min_neighbors) of every point.  *m may be 0.
+// ev_begin / ev_end (may be null) are recorded around the kernels and the read-back of m.  Returns after the stream has drained
+hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, float* d_out, int32_t* d_index,
+                                         int32_t* d_count, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// per-axis minimum and maximum of n points on the device (one rocPRIM reduction, 24 bytes come back): the frame of a cloud that a device
+// stage produced and the host has not seen.  Returns after the stream has drained
+hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream);
 
 // ---- distance transform build (DT3D::Build, jly_3ddt.cpp:889-979; exact EDT) -------------------
 // work: V^3 int32 (linear).  out: V^3 floats in dt.layout (may alias work only for layout 0).

@@ -575,6 +575,89 @@ void Engine::set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n
 		             voxel_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
 }
 
+void Engine::radius_outlier_removal(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
+                                    int32_t* out_count, size_t* m_out)
+{
+	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_radius_outlier_removal: out_xyz and m must be non-null");
+	VoxelFrame f;
+	radius_frame(xyz, n, radius, min_neighbors, &f);
+	if (registering_.load()) throw std::invalid_argument("goicp_radius_outlier_removal: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<int32_t> d_idx(out_index ? n : 0), d_cnt(out_count ? n : 0);
+	int m = 0;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_radius_outlier_removal(d_xyz, (int)n, f, radius * radius, min_neighbors, d_out, out_index ? d_idx.get() : nullptr,
+	                                     out_count ? d_cnt.get() : nullptr, &m, stream_));
+	if (m > 0) HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_index && m > 0) HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_cnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	*m_out = (size_t)m;
+	if (p_.verbose) std::fprintf(stderr, "[goicp] radius_outlier_removal: %zu -> %d points\n", n, m);
+}
+
+void Engine::set_source_filtered(const float* xyz, size_t n, float voxel, float radius, int32_t min_neighbors, size_t* n_kept)
+{
+	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_filtered: voxel must be 0 (no stage) or a voxel size > 0");
+	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_filtered: radius must be 0 (no stage) or a radius > 0");
+	if (!(radius > 0.f)) {
+		// no radius stage: the two existing swaps, bit for bit
+		if (voxel > 0.f) {
+			set_source_voxel(xyz, n, voxel, n_kept);
+		} else {
+			set_source(xyz, n);
+			if (n_kept) *n_kept = n;
+		}
+		return;
+	}
+	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows
+	VoxelFrame fv, fr;
+	if (voxel > 0.f) {
+		voxel_frame(xyz, n, voxel, &fv);
+		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
+	} else {
+		radius_frame(xyz, n, radius, min_neighbors, &fr);
+	}
+	if (registering_.load()) throw std::invalid_argument("goicp_set_source_filtered: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	TraceRange tr("goicp:set_source_filtered");
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
+	Buf<float> d_raw(3 * n), d_red(voxel > 0.f ? 3 * n : 0);
+	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	const float* d_in = d_raw;
+	int n_in = (int)n;
+	float ms = 0.f;
+	if (voxel > 0.f) {
+		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		voxel_ms_ = ms;
+		d_in = d_red;
+		// the frame of the reduced cloud, as radius_frame would find it on the host: 24 bytes come back, not the cloud
+		float mn[3], mx[3];
+		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+		radius_frame_of_box(mn, mx, (size_t)n_in, radius, min_neighbors, &fr);
+	}
+	Buf<float> d_kept(3 * (size_t)n_in);
+	int m = 0;
+	HIPCHK(launch_radius_outlier_removal(d_in, n_in, fr, radius * radius, min_neighbors, d_kept, nullptr, nullptr, &m, stream_, ev0_, ev1_));
+	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+	outlier_ms_ = ms;
+	if (m < 1) throw std::invalid_argument("goicp_set_source_filtered: the filter keeps no point");
+	std::vector<float> kept(3 * (size_t)m);
+	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	load_source(kept.data(), (size_t)m, true, d_kept);
+	finish_source_swap();
+	if (n_kept) *n_kept = (size_t)m;
+	if (p_.verbose)
+		std::fprintf(stderr, "[goicp] set_source_filtered: %zu -> %d -> %zu points, %.2f ms (device voxel %.3f ms, device outlier %.3f ms, device order %.3f ms)\n", n,
+		             n_in, N_, now_ms() - t0, voxel > 0.f ? voxel_ms_ : 0.0, outlier_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
+}
+
 void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)
 {
 	if (!perm) throw std::invalid_argument("goicp_debug_source_order: perm must be non-null");

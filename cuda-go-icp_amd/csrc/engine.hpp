@@ -270,6 +270,13 @@ public:
 	// goicp_set_source_voxel: the raw cloud goes up once, is reduced and ordered on the device; only the reduced cloud and the permutation
 	// come back.  Afterwards the engine is the one set_source(voxel_downsample_host's output) leaves
 	void set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept);
+	// goicp_radius_outlier_removal: the radius filter on the device (kdbuild.hip launch_radius_outlier_removal); as voxel_downsample, the
+	// engine lends its device and stream and nothing else
+	void radius_outlier_removal(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index, int32_t* out_count,
+	                            size_t* m);
+	// goicp_set_source_filtered: voxel grid (voxel > 0), then radius filter (radius > 0), then the swap; the raw cloud goes up once, the
+	// stages are chained on the device, only the final cloud and the permutation come back.  A filter that keeps nothing is refused
+	void set_source_filtered(const float* xyz, size_t n, float voxel, float radius, int32_t min_neighbors, size_t* n_kept);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -281,7 +288,7 @@ private:
 	// d_xyz_ready: the same cloud already on the device (3 N floats; set_source_voxel), which the device order then reads instead of an upload
 	void load_source(const float* source_xyz, size_t N, bool device_order, const float* d_xyz_ready = nullptr);
 	void finish_source_swap();                       // set_source / set_source_voxel after load_source: the search and ICP state of a fresh engine
-	double source_order_ms_ = 0, voxel_ms_ = 0;
+	double source_order_ms_ = 0, voxel_ms_ = 0, outlier_ms_ = 0;
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(size_t B);
 	void ensure_bounds_scratch(int B, hipStream_t s);   // d_scratch_ holds a launch of B cube bounds; growing waits for stream_ and s only
@@ -518,6 +525,15 @@ void source_morton_frame(const float* xyz, size_t n, float mn[3], float* ext);
 // voxel_downsample_host is goicp_voxel_downsample_host: out_xyz holds 3 n floats, out_count (may be null) n ints
 void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f);
 void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
+// radius outlier removal (kdtree.cpp).  radius_frame checks the cloud, the radius and min_neighbors (std::invalid_argument: what
+// voxel_frame refuses, a radius that is not positive and finite or whose square is no normal float, min_neighbors < 1, extent / radius >=
+// 2^16) and fills the frame of the grid of pitch radius * 1.03125f; radius_frame_of_box is the same from the per-axis bounds of a cloud the
+// host has not seen.  radius_outlier_removal_host is goicp_radius_outlier_removal_host: out_xyz holds 3 n floats, out_index (may be null) n
+// ints, out_count (may be null) n ints
+void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
+void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
+void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
+                                 int32_t* out_count, size_t* m);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

@@ -208,6 +208,35 @@ int goicp_set_source_voxel(goicp_handle h, const float* xyz, size_t n, float vox
 	return guarded([&] { h->e->set_source_voxel(xyz, n, voxel, n_kept); });
 }
 
+int goicp_radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
+                                      int32_t* out_count, size_t* m)
+{
+	REQUIRE(xyz && out_xyz && m && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::radius_outlier_removal_host(xyz, n, radius, min_neighbors, out_xyz, out_index, out_count, m); });
+}
+
+int goicp_radius_outlier_removal(goicp_handle h, const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
+                                 int32_t* out_count, size_t* m)
+{
+	REQUIRE(h && xyz && out_xyz && m && n > 0);
+	return guarded([&] { h->e->radius_outlier_removal(xyz, n, radius, min_neighbors, out_xyz, out_index, out_count, m); });
+}
+
+void goicp_source_filter_default(goicp_source_filter* out)
+{
+	if (!out) return;
+	out->voxel = 0.f;
+	out->radius = 0.f;
+	out->min_neighbors = 0;
+}
+
+int goicp_set_source_filtered(goicp_handle h, const float* xyz, size_t n, const goicp_source_filter* f, size_t* n_kept)
+{
+	REQUIRE(h && xyz && f && n > 0);
+	return guarded([&] { h->e->set_source_filtered(xyz, n, f->voxel, f->radius, f->min_neighbors, n_kept); });
+}
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

@@ -377,6 +377,65 @@ int main()
 				} catch (const std::invalid_argument&) { refused++; }
 			CHECK(refused == 5 && m == 77 && out[0] == -9.f);
 		}
+		// radius outlier removal on the host against all pairs (the header's expression): kept points, indices and saturated counts; the
+		// 70 000-point case runs the threaded path; each refusal throws and writes nothing
+		for (int n : {1, 2, 65, 257, 3000})
+			for (float r : {4e-5f, 0.05f, 0.3f, 8.f})
+				for (int k : {1, 3, n}) {
+					std::vector<float> out(3 * (size_t)n + 3, -9.f);
+					std::vector<int32_t> idx((size_t)n + 1, -9), cnt((size_t)n, -9);
+					size_t m = 77;
+					goicp::radius_outlier_removal_host(pts.data(), (size_t)n, r, k, out.data(), idx.data(), cnt.data(), &m);
+					const float r2 = r * r;
+					size_t w = 0;
+					bool ok = m <= (size_t)n;
+					for (int i = 0; i < n && ok; i++) {
+						int c = 0;
+						for (int j = 0; j < n; j++) {
+							if (j == i) continue;
+							const float dx = pts[3 * i] - pts[3 * j], dy = pts[3 * i + 1] - pts[3 * j + 1], dz = pts[3 * i + 2] - pts[3 * j + 2];
+							const float d2 = dx * dx + dy * dy + dz * dz;
+							if (d2 <= r2 && c < k) c++;
+						}
+						ok = ok && cnt[(size_t)i] == c;
+						if (c == k) {
+							ok = ok && w < m && idx[w] == i && !std::memcmp(&out[3 * w], &pts[3 * (size_t)i], 12);
+							w++;
+						}
+					}
+					CHECK(ok && w == m && out[3 * m] == -9.f && idx[m] == -9);
+				}
+		{
+			const size_t n = 70000;
+			std::vector<float> big(3 * n), out(3 * n);
+			for (size_t i = 0; i < 3 * n; i++) big[i] = pts[i % pts.size()] + (i < pts.size() ? 0.f : 2.5f * (float)(i / pts.size()));
+			std::vector<int32_t> cnt(n), cnt1(n);
+			size_t m = 0, m1 = 0;
+			goicp::radius_outlier_removal_host(big.data(), n, 0.05f, 2, out.data(), nullptr, cnt.data(), &m);
+			goicp::radius_outlier_removal_host(big.data(), 60000, 0.05f, 2, out.data(), nullptr, cnt1.data(), &m1);   // below the threading threshold
+			bool same = m > 0 && m < n;
+			for (size_t i = 0; i < 60000; i++) same = same && cnt[i] == cnt1[i];      // the copies are 2.5 apart: no neighbours across them
+			CHECK(same);
+		}
+		{
+			std::vector<float> out(30, -9.f);
+			std::vector<int32_t> idx(10, -9);
+			size_t m = 77;
+			float bad[6] = {0.f, 0.f, 0.f, 1.f, NAN, 0.f};
+			int refused = 0;
+			for (int what = 0; what < 8; what++)
+				try {
+					if (what == 0) goicp::radius_outlier_removal_host(pts.data(), 10, 0.f, 2, out.data(), idx.data(), nullptr, &m);
+					if (what == 1) goicp::radius_outlier_removal_host(pts.data(), 10, NAN, 2, out.data(), idx.data(), nullptr, &m);
+					if (what == 2) goicp::radius_outlier_removal_host(pts.data(), 10, INFINITY, 2, out.data(), idx.data(), nullptr, &m);
+					if (what == 3) goicp::radius_outlier_removal_host(bad, 2, 0.5f, 2, out.data(), idx.data(), nullptr, &m);
+					if (what == 4) goicp::radius_outlier_removal_host(pts.data(), 10, 1e-6f, 2, out.data(), idx.data(), nullptr, &m);   // more than 16 bits per axis
+					if (what == 5) goicp::radius_outlier_removal_host(pts.data(), 10, 1e-25f, 2, out.data(), idx.data(), nullptr, &m);  // r * r is no normal float
+					if (what == 6) goicp::radius_outlier_removal_host(pts.data(), 10, 1e25f, 2, out.data(), idx.data(), nullptr, &m);
+					if (what == 7) goicp::radius_outlier_removal_host(pts.data(), 10, 0.5f, 0, out.data(), idx.data(), nullptr, &m);
+				} catch (const std::invalid_argument&) { refused++; }
+			CHECK(refused == 8 && m == 77 && out[0] == -9.f && idx[0] == -9);
+		}
 		float R[9];
 		goicp::rodrigues(0.3f, -0.2f, 0.9f, R);
 		CHECK(std::fabs(R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]) - 1.f) < 1e-5f);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -480,6 +481,207 @@ hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& 
 	*m_out = m;
 #undef VX_TRY
 	return hipStreamSynchronize(stream);                       // the temporaries are in use until here
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radius outlier removal on the device (host twin: radius_outlier_removal_host, kdtree.cpp).  A grid of pitch 1.03125 r only
+// selects candidates -- any pair within r lies in cells that differ by at most one per axis -- and what counts is the float expression of
+// the header, so every candidate set that covers the 27 cells gives the same bits.  rocPRIM's are the radix sort of (key, id) and the scan
+// of the keep flags; ours are the key kernel (the voxel operator's), the gather into sorted 16-byte records, the count kernel and the
+// compaction.
+// ------------------------------------------------------------------------------------------------
+struct __align__(16) RorPt { float x, y, z; int id; };
+constexpr int kRorBlock = 256;                                 // the span of sorted points a workgroup owns, and the LDS tile (4 KB)
+
+__global__ void ror_gather_kernel(const float* __restrict__ xyz, const int* __restrict__ ids, int n, RorPt* __restrict__ pts)
+{
+	const int s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= n) return;
+	const int id = ids[s];
+	pts[s] = RorPt{xyz[3 * (size_t)id], xyz[3 * (size_t)id + 1], xyz[3 * (size_t)id + 2], id};
+}
+
+// the first sorted position whose key is >= k (upper = false) or > k (upper = true); a negative k is below every key
+__device__ __forceinline__ int ror_bound(const unsigned long long* __restrict__ keys, int n, long long k, bool upper)
+{
+	if (k < 0) return 0;
+	int lo = 0, hi = n;
+	while (lo < hi) {
+		const int mid = lo + ((hi - lo) >> 1);
+		const unsigned long long v = keys[mid];
+		if (upper ? v <= (unsigned long long)k : v < (unsigned long long)k) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+
+// A workgroup owns kRorBlock consecutive SORTED points, keys Ka..Kb.  The cells around a point with key K are the 9 runs
+// [K + D - 1, K + D + 1], D = dy 2^21 + dz 2^42, so all runs of the span lie in the 9 intervals [Ka + D - 1, Kb + D + 1].  Lanes 0..8 find
+// them by binary search, lane 0 makes them disjoint (D ascends, so both ends ascend: each interval starts no earlier than the one before
+// it ends).  A key of the intervals that is no neighbour cell -- a field that wrapped below zero, the cells between two rows -- is only a
+// candidate that fails the distance test or the cull.  The intervals pass through LDS in tiles of kRorBlock records; each lane tests its
+// own point against every record of a tile, skips its own id and stops counting at min_neighbors.  A wave skips a tile none of whose
+// unsaturated lanes has a run that meets the tile's key range, and the workgroup leaves once every lane is saturated: a dense cell costs a
+// lane min_neighbors hits, not the cell.  No workgroup waits on another.
+__global__ void __launch_bounds__(kRorBlock) ror_count_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, float r2,
+                                                              int min_neighbors, int32_t* __restrict__ count, int* __restrict__ flag)
+{
+	__shared__ RorPt tile[kRorBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kRorBlock, last = min(first + kRorBlock, n) - 1;
+	const int s = first + tid;
+	const bool valid = s < n;
+	if (tid < 9) {
+		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
+		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
+		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
+	}
+	__syncthreads();
+	if (tid == 0)
+		for (int o = 1; o < 9; o++) {
+			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
+			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
+		}
+	__syncthreads();
+	RorPt P{0.f, 0.f, 0.f, -1};
+	long long K = 0;
+	if (valid) { P = pts[s]; K = (long long)keys[s]; }
+	int cnt = valid ? 0 : min_neighbors;                         // a lane past the end counts as saturated
+	for (int o = 0; o < 9; o++) {
+		const int lo = iv_lo[o], hi = iv_hi[o];
+		for (int t0 = lo; t0 < hi; t0 += kRorBlock) {
+			if (__syncthreads_and(cnt >= min_neighbors)) goto done;   // also: the previous tile has been read by everybody
+			const int len = min(kRorBlock, hi - t0);
+			if (tid < len) tile[tid] = pts[t0 + tid];
+			__syncthreads();
+			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
+			bool need = false;
+			if (cnt < min_neighbors)
+				for (int q = 0; q < 9; q++) {
+					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
+					need = need || (c - 1 <= tb && c + 1 >= ta);
+				}
+			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
+			for (int j = 0; j < len; j++) {
+				const RorPt Q = tile[j];
+				const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+				const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+				if (d2 <= r2 && Q.id != P.id && cnt < min_neighbors) cnt++;
+			}
+		}
+	}
+done:
+	if (valid) {
+		count[P.id] = cnt;
+		flag[P.id] = cnt == min_neighbors ? 1 : 0;
+	}
+}
+
+// scan: the exclusive scan of the flags in input order (n + 1 entries, the last one is m)
+__global__ void ror_compact_kernel(const float* __restrict__ xyz, const int* __restrict__ flag, const int* __restrict__ scan, int n,
+                                   float* __restrict__ out, int32_t* __restrict__ index)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || !flag[i]) return;
+	const size_t d = (size_t)scan[i];
+	out[3 * d] = xyz[3 * (size_t)i]; out[3 * d + 1] = xyz[3 * (size_t)i + 1]; out[3 * d + 2] = xyz[3 * (size_t)i + 2];
+	if (index) index[d] = i;
+}
+
+hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, float* d_out, int32_t* d_index,
+                                         int32_t* d_count, int* m_out, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n <= 0 || !m_out || min_neighbors < 1) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define ROR_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	unsigned long long *keys = nullptr, *keys2 = nullptr;
+	int *ids = nullptr, *ids2 = nullptr, *flag = nullptr, *scan = nullptr, *cnt = nullptr;
+	RorPt* pts = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		unsigned long long*& a; unsigned long long*& b; int*& c; int*& d; int*& f; int*& g; int*& h; RorPt*& p; void*& t;
+		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(p); hipFree(t); }
+	} cleanup{keys, keys2, ids, ids2, flag, scan, cnt, pts, tmp};
+	const size_t N = (size_t)n;
+	ROR_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
+	ROR_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
+	ROR_TRY(hipMalloc(&ids, sizeof(int) * N));
+	ROR_TRY(hipMalloc(&ids2, sizeof(int) * N));
+	ROR_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
+	ROR_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
+	ROR_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
+	if (!d_count) ROR_TRY(hipMalloc(&cnt, sizeof(int) * N));
+	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+	size_t sort_bytes = 0, scan_bytes = 0;
+	ROR_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	ROR_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	ROR_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	// ev_begin .. ev_end: the kernels and the 4-byte read-back of m; the allocations above and the frees at the end are outside
+	if (ev_begin) ROR_TRY(hipEventRecord(ev_begin, stream));
+	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
+	ROR_TRY(hipGetLastError());
+	size_t bytes = sort_bytes;
+	ROR_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+	ROR_TRY(hipGetLastError());
+	ROR_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
+	hipLaunchKernelGGL(ror_count_kernel, dim3((n + kRorBlock - 1) / kRorBlock), dim3(kRorBlock), 0, stream, pts, keys2, n, r2, min_neighbors,
+	                   d_count ? d_count : cnt, flag);
+	ROR_TRY(hipGetLastError());
+	bytes = scan_bytes;
+	ROR_TRY(rocprim::exclusive_scan(tmp, bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	hipLaunchKernelGGL(ror_compact_kernel, grd, blk, 0, stream, d_xyz, flag, scan, n, d_out, d_index);
+	ROR_TRY(hipGetLastError());
+	int m = -1;
+	ROR_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+	if (ev_end) ROR_TRY(hipEventRecord(ev_end, stream));
+	ROR_TRY(hipStreamSynchronize(stream));                     // the temporaries are in use until here
+#undef ROR_TRY
+	if (m < 0 || m > n) return hipErrorUnknown;
+	*m_out = m;
+	return hipSuccess;
+}
+
+// the per-axis minimum and maximum of a cloud on the device: what voxel_frame derives on the host, for a cloud that never leaves the device
+struct MinMax3 { float mn[3], mx[3]; };
+struct MinMaxOf {
+	const float* xyz;
+	__device__ MinMax3 operator()(int i) const
+	{
+		const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+		return MinMax3{{x, y, z}, {x, y, z}};
+	}
+};
+struct MinMaxJoin {
+	__device__ MinMax3 operator()(const MinMax3& a, const MinMax3& b) const
+	{
+		MinMax3 r;
+		for (int k = 0; k < 3; k++) { r.mn[k] = fminf(a.mn[k], b.mn[k]); r.mx[k] = fmaxf(a.mx[k], b.mx[k]); }
+		return r;
+	}
+};
+
+hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream)
+{
+	if (n <= 0) return hipErrorInvalidValue;
+	hipError_t e;
+	MinMax3* d_res = nullptr;
+	void* tmp = nullptr;
+	struct Cleanup { MinMax3*& r; void*& t; ~Cleanup() { hipFree(r); hipFree(t); } } cleanup{d_res, tmp};
+	auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), MinMaxOf{d_xyz});
+	const MinMax3 init{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
+	size_t bytes = 0;
+	if ((e = rocprim::reduce(nullptr, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream)) != hipSuccess) return e;
+	if ((e = hipMalloc(&tmp, std::max<size_t>(bytes, 16))) != hipSuccess) return e;
+	if ((e = hipMalloc(&d_res, sizeof(MinMax3))) != hipSuccess) return e;
+	if ((e = rocprim::reduce(tmp, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream)) != hipSuccess) return e;
+	MinMax3 res;
+	if ((e = hipMemcpyAsync(&res, d_res, sizeof(MinMax3), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+	if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+	for (int k = 0; k < 3; k++) { mn[k] = res.mn[k]; mx[k] = res.mx[k]; }
+	return hipSuccess;
 }
 
 }  // namespace goicp

@@ -258,21 +258,10 @@ void source_order_host(const float* source, size_t N_, int mode, int32_t* perm_o
 }
 
 // ---- voxel-grid downsampling: the frame both paths share, and the host path ----
-void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f)
+// what follows the scan of the cloud: the limits on E and the derived fields.  radius > 0: the radius filter's grid, with its 2^16 rule
+static void fill_frame(const float mn[3], float E, size_t n, float voxel, float radius, VoxelFrame* f)
 {
-	if (!xyz || n == 0) throw std::invalid_argument("goicp voxel: empty cloud");
-	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp voxel: cloud too large");
-	if (!(voxel > 0.f) || !std::isfinite(voxel)) throw std::invalid_argument("goicp voxel: the voxel size must be positive and finite");
-	float mn[3] = {INFINITY, INFINITY, INFINITY};
-	for (size_t i = 0; i < n; i++)
-		for (int k = 0; k < 3; k++) {
-			const float x = xyz[3 * i + k];
-			if (!std::isfinite(x)) throw std::invalid_argument("goicp voxel: non-finite coordinate in the cloud");
-			mn[k] = std::min(mn[k], x);
-		}
-	float E = 0.f;
-	for (size_t i = 0; i < n; i++)
-		for (int k = 0; k < 3; k++) E = std::max(E, xyz[3 * i + k] - mn[k]);
+	if (radius > 0.f && !(E / radius < 65536.f)) throw std::invalid_argument("goicp outlier: the grid needs more than 16 bits per axis (extent / radius >= 2^16)");
 	if (!(E / voxel < 2097152.f)) throw std::invalid_argument("goicp voxel: the grid needs more than 21 bits per axis (extent / voxel >= 2^21)");
 	for (int k = 0; k < 3; k++) f->mn[k] = mn[k];
 	f->E = E;
@@ -287,6 +276,48 @@ void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f)
 	int cbits = 0;
 	for (int c = (int)std::floor(E / voxel); c; c >>= 1) cbits++;
 	f->key_bits = 42 + std::max(cbits, 1);
+}
+
+// radius > 0: the frame of the radius filter's grid (pitch `voxel` = radius * 1.03125f), which adds the 2^16 rule
+static void grid_frame(const float* xyz, size_t n, float voxel, float radius, VoxelFrame* f)
+{
+	if (!xyz || n == 0) throw std::invalid_argument("goicp voxel: empty cloud");
+	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp voxel: cloud too large");
+	if (!(voxel > 0.f) || !std::isfinite(voxel)) throw std::invalid_argument("goicp voxel: the voxel size must be positive and finite");
+	float mn[3] = {INFINITY, INFINITY, INFINITY};
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) {
+			const float x = xyz[3 * i + k];
+			if (!std::isfinite(x)) throw std::invalid_argument("goicp voxel: non-finite coordinate in the cloud");
+			mn[k] = std::min(mn[k], x);
+		}
+	float E = 0.f;
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) E = std::max(E, xyz[3 * i + k] - mn[k]);
+	fill_frame(mn, E, n, voxel, radius, f);
+}
+
+void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f) { grid_frame(xyz, n, voxel, 0.f, f); }
+
+void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
+{
+	if (!xyz || n == 0) throw std::invalid_argument("goicp outlier: empty cloud");
+	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp outlier: cloud too large");
+	if (!(radius > 0.f) || !std::isfinite(radius)) throw std::invalid_argument("goicp outlier: the radius must be positive and finite");
+	const float r2 = radius * radius;
+	if (!std::isnormal(r2)) throw std::invalid_argument("goicp outlier: radius * radius must be a normal float");
+	if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+	grid_frame(xyz, n, radius * 1.03125f, radius, f);
+}
+
+void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
+{
+	if (!(radius > 0.f) || !std::isfinite(radius)) throw std::invalid_argument("goicp outlier: the radius must be positive and finite");
+	if (!std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: radius * radius must be a normal float");
+	if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+	float E = 0.f;
+	for (int k = 0; k < 3; k++) E = std::max(E, mx[k] - mn[k]);   // rounding is monotone: the largest offset is the one of an axis' maximum
+	fill_frame(mn, E, n, radius * 1.03125f, radius, f);
 }
 
 void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m_out)
@@ -315,6 +346,65 @@ void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_x
 		if (out_count) out_count[m] = (int32_t)cnt;
 		m++;
 		a = b;
+	}
+	*m_out = m;
+}
+
+// ---- radius outlier removal: the host path.  The points are sorted by the key of their cell (pitch 1.03125 r); the 27 cells
+// around a point are 9 runs of up to three consecutive keys, each one lower and one upper binary search; a point leaves its loop once it
+// has min_neighbors.  The grid only selects candidates: what counts is the float expression of the header ----
+void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
+                                 int32_t* out_count, size_t* m_out)
+{
+	VoxelFrame f;
+	radius_frame(xyz, n, radius, min_neighbors, &f);
+	const float r2 = radius * radius;
+	std::vector<std::pair<uint64_t, int32_t>> ki(n);
+	for (size_t i = 0; i < n; i++) {
+		uint64_t key = 0;
+		for (int k = 0; k < 3; k++) key |= (uint64_t)(int)std::floor((xyz[3 * i + k] - f.mn[k]) / f.voxel) << (21 * k);
+		ki[i] = {key, (int32_t)i};
+	}
+	std::sort(ki.begin(), ki.end());
+	struct Pt { float x, y, z; int32_t id; };
+	std::vector<uint64_t> keys(n);
+	std::vector<Pt> pts(n);
+	for (size_t s = 0; s < n; s++) {
+		const float* p = xyz + 3 * (size_t)ki[s].second;
+		keys[s] = ki[s].first;
+		pts[s] = {p[0], p[1], p[2], ki[s].second};
+	}
+	std::vector<std::pair<uint64_t, int32_t>>().swap(ki);
+	std::vector<int32_t> count(n);
+	const size_t chunk = 4096, chunks = (n + chunk - 1) / chunk;
+	parallel_tasks(n >= 65536 ? 8 : 1, (int)chunks, [&](int t) {
+		for (size_t s = (size_t)t * chunk; s < std::min(n, ((size_t)t + 1) * chunk); s++) {
+			const Pt P = pts[s];
+			const int64_t cx = (int64_t)(keys[s] & 0x1fffffu), cy = (int64_t)((keys[s] >> 21) & 0x1fffffu), cz = (int64_t)(keys[s] >> 42);
+			int32_t cnt = 0;
+			for (int64_t z = std::max<int64_t>(cz - 1, 0); z <= cz + 1 && cnt < min_neighbors; z++)       // clamped at the low faces; past the
+				for (int64_t y = std::max<int64_t>(cy - 1, 0); y <= cy + 1 && cnt < min_neighbors; y++) {   // high ones there are no keys
+					const uint64_t base = ((uint64_t)z << 42) | ((uint64_t)y << 21);
+					const size_t a = std::lower_bound(keys.begin(), keys.end(), base | (uint64_t)std::max<int64_t>(cx - 1, 0)) - keys.begin();
+					const size_t b = std::upper_bound(keys.begin() + a, keys.end(), base | (uint64_t)(cx + 1)) - keys.begin();
+					for (size_t j = a; j < b && cnt < min_neighbors; j++) {
+						const Pt& Q = pts[j];
+						if (Q.id == P.id) continue;
+						const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+						const float d2 = dx * dx + dy * dy + dz * dz;
+						if (d2 <= r2) cnt++;
+					}
+				}
+			count[(size_t)P.id] = cnt;
+		}
+	});
+	size_t m = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (out_count) out_count[i] = count[i];
+		if (count[i] != min_neighbors) continue;
+		for (int k = 0; k < 3; k++) out_xyz[3 * m + k] = xyz[3 * i + k];
+		if (out_index) out_index[m] = (int32_t)i;
+		m++;
 	}
 	*m_out = m;
 }

@@ -83,6 +83,30 @@ def voxel_downsample(xyz, voxel):
     return _voxel_call(B.load_library().goicp_voxel_downsample_host, xyz, voxel)
 
 
+def _outlier_call(fn, xyz, radius, min_neighbors):
+    xyz = _f32(xyz, (-1, 3))
+    n, ip = len(xyz), C.POINTER(C.c_int32)
+    out, idx, cnt, m = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.int32), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), n, float(radius), int(min_neighbors), _fptr(out), idx.ctypes.data_as(ip), cnt.ctypes.data_as(ip), C.byref(m)))
+    return out[:m.value].copy(), idx[:m.value].copy(), cnt
+
+
+def radius_outlier_removal(xyz, radius, min_neighbors):
+    """goicp_radius_outlier_removal_host (host only): the points with at least `min_neighbors` other points within `radius`, in input order
+    -> (cloud (m, 3) float32, their indices (m,) int32, min(neighbours, min_neighbors) of every input point (n,) int32).
+    Registration.radius_outlier_removal and set_source(radius=, min_neighbors=) give the same bits on the device."""
+    return _outlier_call(B.load_library().goicp_radius_outlier_removal_host, xyz, radius, min_neighbors)
+
+
+def _filter_host(pcs, voxel, radius, min_neighbors):
+    """the composition of the host functions that goicp_set_source_filtered equals"""
+    if voxel:
+        pcs = voxel_downsample(pcs, voxel)[0]
+    if radius:
+        pcs = radius_outlier_removal(pcs, radius, min_neighbors)[0]
+    return pcs
+
+
 class Config:
     """Config(toml_filepath): same keys, defaults and clamps as the reference; raises on parse error."""
 
@@ -241,7 +265,7 @@ class Registration:
         """the source cloud in the handle's "original order"; after set_source(voxel=) the reduced cloud, formed on first use (the host
         function's output is the device's, bit for bit, so a scan stream that never asks never pays for a host reduction)"""
         if self._pcs is None:
-            self._pcs = voxel_downsample(*self._pcs_raw)[0]
+            self._pcs = _filter_host(*self._pcs_raw)
             self._pcs_raw = None
         return self._pcs
 
@@ -249,19 +273,31 @@ class Registration:
     def pcs(self, value):
         self._pcs, self._pcs_raw = value, None
 
-    def set_source(self, pcs, voxel=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None):
         """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
         options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit.
         voxel: goicp_set_source_voxel -- the cloud is reduced to one centroid per voxel on the device first, and the handle answers as after
-        set_source(voxel_downsample(pcs, voxel)[0]); self.ns is the number of points kept, self.pcs the reduced cloud."""
+        set_source(voxel_downsample(pcs, voxel)[0]); self.ns is the number of points kept, self.pcs the reduced cloud.
+        radius, min_neighbors (both or neither): goicp_set_source_filtered -- after the voxel grid, if any, the points with fewer than
+        min_neighbors others within radius are dropped on the device, and the handle answers as after set_source of
+        radius_outlier_removal(..., radius, min_neighbors)[0]."""
         pcs = _f32(pcs, (-1, 3))
-        if voxel is None:
+        if (radius is None) != (min_neighbors is None):
+            raise ValueError("set_source: radius and min_neighbors go together")
+        if voxel is None and radius is None:
             B.check(self._lib.goicp_set_source(self.handle, _fptr(pcs), len(pcs)))
             self.pcs, self.ns = pcs, len(pcs)
-        else:
+        elif radius is None:
             kept = C.c_size_t(0)
             B.check(self._lib.goicp_set_source_voxel(self.handle, _fptr(pcs), len(pcs), float(voxel), C.byref(kept)))
-            self._pcs, self._pcs_raw, self.ns = None, (pcs, float(voxel)), kept.value
+            self._pcs, self._pcs_raw, self.ns = None, (pcs, float(voxel), None, None), kept.value
+        else:
+            if not float(radius) > 0 or (voxel is not None and not float(voxel) > 0):
+                raise ValueError("set_source: a stage that is named needs a size > 0")
+            kept = C.c_size_t(0)
+            f = B.CSourceFilter(float(voxel or 0.0), float(radius), int(min_neighbors))
+            B.check(self._lib.goicp_set_source_filtered(self.handle, _fptr(pcs), len(pcs), C.byref(f), C.byref(kept)))
+            self._pcs, self._pcs_raw, self.ns = None, (pcs, None if voxel is None else float(voxel), float(radius), int(min_neighbors)), kept.value
         thr, inl = C.c_float(), C.c_int32()
         B.check(self._lib.goicp_thresholds(self.handle, C.byref(thr), C.byref(inl)))
         self.sse_threshold, self.inliers = np.float32(thr.value), inl.value
@@ -270,6 +306,11 @@ class Registration:
         """goicp_voxel_downsample: the module-level voxel_downsample on the device (the handle lends its device and stream, its state is
         untouched) -> (cloud (m, 3) float32, counts (m,) int32), the same bits"""
         return _voxel_call(lambda *a: self._lib.goicp_voxel_downsample(self.handle, *a), xyz, voxel)
+
+    def radius_outlier_removal(self, xyz, radius, min_neighbors):
+        """goicp_radius_outlier_removal: the module-level radius_outlier_removal on the device (the handle lends its device and stream, its
+        state is untouched) -> (cloud (m, 3) float32, indices (m,) int32, counts (n,) int32), the same bits"""
+        return _outlier_call(lambda *a: self._lib.goicp_radius_outlier_removal(self.handle, *a), xyz, radius, min_neighbors)
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""
@@ -534,9 +575,9 @@ class FastGoICP:
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
 
-    def set_source(self, pcs, voxel=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None):
         """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
-        self.registration.set_source(pcs, voxel)
+        self.registration.set_source(pcs, voxel, radius, min_neighbors)
         self.sse_threshold = self.registration.sse_threshold
 
     def run(self):

@@ -248,6 +248,42 @@ int goicp_source_order_host(const float* xyz, size_t n, int32_t mode, int32_t* p
 int goicp_voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
 int goicp_voxel_downsample(goicp_handle h, const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
 int goicp_set_source_voxel(goicp_handle h, const float* xyz, size_t n, float voxel, size_t* n_kept);
+/*
+ * Radius outlier removal (PCL's RadiusOutlierRemoval, Open3D's remove_radius_outlier): a point is kept when at least min_neighbors other
+ * points lie within `radius` of it.  The host function, the device function and the filtered swap produce the same bits.  Float
+ * arithmetic is IEEE single precision, nothing fused:
+ *   r2      = radius * radius;
+ *   pair    for points i != j: dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j, d2 = dx*dx + dy*dy + dz*dz evaluated left to right
+ *           (symmetric in i and j); j is a neighbour of i iff j != i && d2 <= r2.  A duplicate of a point is its neighbour, a point is
+ *           never its own;
+ *   count   count_i = min(number of neighbours of i, min_neighbors): the count saturates, so every implementation may stop early;
+ *   keep    point i is kept iff count_i == min_neighbors;
+ *   output  the m kept points in input order with their own bits, their original indices (ascending), and count_i of all n points.
+ * The definition names no grid: the implementations search a grid of pitch radius * 1.03125f built on the voxel operator's frame, which
+ * only selects candidates (DESIGN 18 proves that it misses no pair).
+ * out_xyz holds n x 3 floats (the first m x 3 are written), out_index (may be NULL) n ints (the first m are written), out_count (may be
+ * NULL) n ints (all written), *m the number of points kept; m == 0 is a valid result.
+ * goicp_radius_outlier_removal_host runs on the host alone (no handle, no GPU).  goicp_radius_outlier_removal runs on the device: the
+ * handle lends its device and stream, its state is untouched.
+ * GOICP_ERR_INVALID, nothing written: NULL arguments, n == 0 or above goicp_create's limit, a non-finite coordinate, a radius that is
+ * <= 0, NaN or infinite or whose radius * radius is not a normal float, min_neighbors < 1, E / radius >= 2^16 (E the frame's largest
+ * offset, as in the voxel operator), and for the handle form any call while a registration runs.
+ */
+int goicp_radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index, int32_t* out_count, size_t* m);
+int goicp_radius_outlier_removal(goicp_handle h, const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index, int32_t* out_count, size_t* m);
+/*
+ * The filtered swap: the voxel grid when voxel > 0, then the radius filter on the reduced cloud when radius > 0, then the swap.  The raw
+ * cloud is uploaded once and the stages are chained on the device; only the final cloud and the permutation (and the 24 bytes of the
+ * reduced cloud's bounding box) come back.  Afterwards the handle answers every entry point bit for bit as after goicp_set_source(h, D, m)
+ * with D the composition of goicp_voxel_downsample_host and goicp_radius_outlier_removal_host -- D's order is the "original order" of
+ * goicp_transform_source and goicp_eval_correspondences -- and everything goicp_set_source keeps and resets carries over.  With both
+ * stages off it is goicp_set_source, with only `voxel` set goicp_set_source_voxel.  *n_kept (may be NULL) = m.
+ * GOICP_ERR_INVALID, the handle untouched: a filter that keeps no point, radius > 0 with min_neighbors < 1, a negative or NaN voxel or
+ * radius, everything the stages and goicp_set_source refuse, and any call while a registration runs.
+ */
+typedef struct goicp_source_filter { float voxel; float radius; int32_t min_neighbors; } goicp_source_filter;
+void goicp_source_filter_default(goicp_source_filter* out);   /* all 0 = no stage */
+int goicp_set_source_filtered(goicp_handle h, const float* xyz, size_t n, const goicp_source_filter* f, size_t* n_kept);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

@@ -224,6 +224,17 @@ public:
 		ns_ = kept;
 		return kept;
 	}
+	// the same behind the whole filter chain (goicp_set_source_filtered): the voxel grid when f.voxel > 0, then radius outlier removal when
+	// f.radius > 0 (points with fewer than f.min_neighbors others within f.radius are dropped), all on the device; returns the points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, size_t ns, const goicp_source_filter& f)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		size_t kept = 0;
+		check(goicp_set_source_filtered(h_, reinterpret_cast<const float*>(pcs.data()), ns, &f, &kept));
+		ns_ = kept;
+		return kept;
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
@@ -372,6 +383,14 @@ public:
 	size_t set_source(const std::vector<Point3>& pcs, float voxel)
 	{
 		const size_t kept = registration.set_source(pcs, pcs.size(), voxel);
+		sync();
+		return kept;
+	}
+	// ... behind the filter chain `f` (voxel grid, then radius outlier removal); returns the number of points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_filter& f)
+	{
+		const size_t kept = registration.set_source(pcs, pcs.size(), f);
 		sync();
 		return kept;
 	}
