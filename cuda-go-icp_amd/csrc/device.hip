@@ -403,6 +403,117 @@ __device__ __forceinline__ void lean_points(const float4* __restrict__ src, int 
 	}
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pair form of the lean loop: TWO expansions of one rotation over one point chunk (launch_bounds, bounds_order = 2).  The point load, R p
+// and |p| are shared; everything else is per member and is lean_points<.., 1, ..>'s own expression, in its order, on its thread: the six
+// indices, the exactness test, the inside test, the gathers (merged x rows per member), the packed sums -- so every bound keeps its bits.
+// Both members' gathers are issued before either is consumed.  The loop has no checked form: a member some lane of which leaves the grid
+// is given up and evaluated again by the plain path (bounds_work), which decides per wavefront and point exactly as it always did.
+// ------------------------------------------------------------------------------------------------
+struct LeanIdx { int ix[2], iy[2], iz[2]; };
+__device__ __forceinline__ bool lean_index(const DtDesc& dt, float rx, float ry, float rz, const SiblingSet& ts, float eps_grid, LeanIdx& o)
+{
+	const float qx[2] = {rx + ts.tx0, rx + ts.tx1}, qy[2] = {ry + ts.ty0, ry + ts.ty1}, qz[2] = {rz + ts.tz0, rz + ts.tz1};
+	float F[6] = {__fmaf_rn(qx[0] - dt.xmin_f, dt.scale_f, 0.5f), __fmaf_rn(qx[1] - dt.xmin_f, dt.scale_f, 0.5f),
+	              __fmaf_rn(qy[0] - dt.ymin_f, dt.scale_f, 0.5f), __fmaf_rn(qy[1] - dt.ymin_f, dt.scale_f, 0.5f),
+	              __fmaf_rn(qz[0] - dt.zmin_f, dt.scale_f, 0.5f), __fmaf_rn(qz[1] - dt.zmin_f, dt.scale_f, 0.5f)};
+	float worst = INFINITY;
+#pragma unroll
+	for (int k = 0; k < 6; k++) worst = fminf(worst, fabsf(F[k] - rintf(F[k])));
+	o.ix[0] = (int)F[0]; o.ix[1] = (int)F[1]; o.iy[0] = (int)F[2]; o.iy[1] = (int)F[3]; o.iz[0] = (int)F[4]; o.iz[1] = (int)F[5];
+	if (worst <= eps_grid) {
+#pragma unroll
+		for (int k = 0; k < 2; k++) {
+			o.ix[k] = voxel_exact(qx[k], dt.xmin, dt.scale);
+			o.iy[k] = voxel_exact(qy[k], dt.ymin, dt.scale);
+			o.iz[k] = voxel_exact(qz[k], dt.zmin, dt.scale);
+		}
+	}
+	const unsigned V = (unsigned)dt.V;
+	return (unsigned)o.ix[0] < V && (unsigned)o.ix[1] < V && (unsigned)o.iy[0] < V && (unsigned)o.iy[1] < V && (unsigned)o.iz[0] < V && (unsigned)o.iz[1] < V;
+}
+// the eight looked-up values of a member whose indices all lie inside the bricked grid, as four x-sibling pairs (lean_points' gathers)
+__device__ __forceinline__ void lean_gather(const DtDesc& dt, const LeanIdx& I, bool merge_x, f2 (&vv)[4])
+{
+	unsigned fx[2], fy[2], fz[2];
+#pragma unroll
+	for (int k = 0; k < 2; k++) {
+		fx[k] = (((unsigned)I.ix[k] >> 2) << 8) | (brick_x((unsigned)I.ix[k]) << 2);
+		fy[k] = (__umul24((unsigned)I.iy[k] >> 2, (unsigned)dt.VB) << 8) | (brick_y((unsigned)I.iy[k]) << 2);
+		fz[k] = (__umul24((unsigned)I.iz[k] >> 2, (unsigned)(dt.VB * dt.VB)) << 8) | (brick_z((unsigned)I.iz[k]) << 2);
+	}
+	const char* gb = reinterpret_cast<const char*>(dt.grid);
+	unsigned yz[4];
+#pragma unroll
+	for (int k = 0; k < 4; k++) yz[k] = fy[k & 1] + fz[k >> 1];
+	if (merge_x) {
+		const bool split = (fx[0] ^ fx[1]) >= 16u;
+		const RowSel s0 = row_sel(fx[0]), s1 = row_sel(fx[1]);
+		float4 row[4];
+		float v1[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+		for (int k = 0; k < 4; k++) row[k] = *reinterpret_cast<const float4*>(gb + ((fx[0] & ~15u) + yz[k]));
+		if (split) {
+#pragma unroll
+			for (int k = 0; k < 4; k++) v1[k] = *reinterpret_cast<const float*>(gb + (fx[1] + yz[k]));
+		}
+#pragma unroll
+		for (int k = 0; k < 4; k++) vv[k] = f2{row_pick(row[k], s0), split ? v1[k] : row_pick(row[k], s1)};
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++) vv[k] = f2{*reinterpret_cast<const float*>(gb + (fx[0] + yz[k])), *reinterpret_cast<const float*>(gb + (fx[1] + yz[k]))};
+	}
+}
+template <bool LAST_ZERO, bool TRUNC>
+__device__ __forceinline__ void lean_accum(const f2 (&vv)[4], float rho, f2 ndelta2, float g, f2 (&ub2)[4], f2 (&lb2)[4])
+{
+#pragma unroll
+	for (int k = 0; k < 4; k++) {
+		const f2 v = vv[k];
+		f2 vq = v, mm = v;
+		if constexpr (TRUNC) {
+			if (!LAST_ZERO) vq = v - f2{rho, rho};
+			mm = trunc_clamp2(vq, g);
+			ub2[k] = ub2[k] + mm * mm;
+			const f2 dis = trunc_clamp2(vq + ndelta2, g);
+			lb2[k] = lb2[k] + dis * dis;
+		} else {
+			if (!LAST_ZERO) {
+				vq = v - f2{rho, rho};
+				mm = __builtin_elementwise_max(vq, f2{0.f, 0.f});
+			}
+			ub2[k] = ub2[k] + mm * mm;
+			const f2 dis = __builtin_elementwise_max(vq + ndelta2, f2{0.f, 0.f});
+			lb2[k] = lb2[k] + dis * dis;
+		}
+	}
+}
+struct PairMember { SiblingSet ts; float delta, coeff; };
+// okA / okB (wavefront-uniform): cleared when some lane of the wavefront left the grid under that member; the member's sums are then
+// unfinished and the caller evaluates it again on the plain path, which owns the checked form
+template <bool LZ_A, bool LZ_B, bool TRUNC>
+__device__ __forceinline__ void lean_points_pair(const float4* __restrict__ src, int p0, int p1, const DtDesc& dt, const Rot9& R0, const PairMember& A, const PairMember& Bm,
+                                                 f2 (&ubA)[4], f2 (&lbA)[4], f2 (&ubB)[4], f2 (&lbB)[4], bool& okA, bool& okB)
+{
+	const f2 ndA2 = f2{-A.delta, -A.delta}, ndB2 = f2{-Bm.delta, -Bm.delta};
+	const bool mxA = (A.ts.tx1 - A.ts.tx0) * dt.scale_f < 4.f, mxB = (Bm.ts.tx1 - Bm.ts.tx0) * dt.scale_f < 4.f;      // uniform
+	const float eps_grid = __fmaf_rn((float)(dt.V + 1), dt.c2, dt.c1);
+	for (int i = p0 + (int)threadIdx.x; i < p1; i += kBoundsThreads) {
+		const float4 p = src[i];
+		const float rx = R0.r[0] * p.x + R0.r[1] * p.y + R0.r[2] * p.z;
+		const float ry = R0.r[3] * p.x + R0.r[4] * p.y + R0.r[5] * p.z;
+		const float rz = R0.r[6] * p.x + R0.r[7] * p.y + R0.r[8] * p.z;
+		LeanIdx IA, IB;
+		okA = okA && __all(lean_index(dt, rx, ry, rz, A.ts, eps_grid, IA));
+		okB = okB && __all(lean_index(dt, rx, ry, rz, Bm.ts, eps_grid, IB));
+		f2 va[4], vb[4];
+		if (okA) lean_gather(dt, IA, mxA, va);
+		if (okB) lean_gather(dt, IB, mxB, vb);
+		if (okA) lean_accum<LZ_A, TRUNC>(va, A.coeff * p.w, ndA2, dt.trunc, ubA, lbA);
+		if (okB) lean_accum<LZ_B, TRUNC>(vb, Bm.coeff * p.w, ndB2, dt.trunc, ubB, lbB);
+	}
+}
+
 // the sums of one (expansion, chunk) work item: wave64 reduce, then the 4 wavefronts through LDS, then the item's row of the scratch block (or,
 // unsplit, the bounds themselves)
 __device__ __forceinline__ void bounds_item_store(const float (&ub)[kGroup], const float (&lb)[kGroup], int group, int chunk, int chunks, int B,
@@ -1003,6 +1114,258 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_kernel(
 	bounds_work<LAYOUT, LEAN, TRUNC>(blockIdx.x, gridDim.x, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Footprint order of a PLAIN bound launch (launch_bounds with a BoundsOrder; the engine passes one for cube batches handed in on the
+// device).  Such a batch carries no rotation count and arrives in any translation order, so the pre-pass keys its G = ceil(B / 8) groups by
+// the RUN of equal rotation they arrive in (a rotation that recurs later starts a new run) and, inside a run, by the Morton cell of the
+// parent cube's centre in DT voxels: 5 bits per axis over the run's own extent, cells no smaller than cell_vox.  One workgroup per run:
+// every workgroup finds the run starts for itself (a scan over the rotation of each group), then counting-sorts its run in LDS and writes
+// its slice of order[] and, two neighbours of the order at a time, of the pair list (a leftover stays single).  More runs than max_runs
+// (unrelated cubes): ctl[1] = 0, the launch walks the groups as they came.  The order inside a cell is whatever the atomics give: no bound
+// depends on it, every group writes its own rows.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int group_rot(const CubeRec* __restrict__ cubes, int g) { return cubes[(size_t)g * kGroup].rot; }
+__device__ __forceinline__ void group_centre(const CubeRec* __restrict__ cubes, int g, int B, float (&c)[3])
+{
+	const int i0 = g * kGroup, i1 = min(i0 + kGroup - 1, B - 1);
+	const CubeRec a = cubes[i0], b = cubes[i1];                       // children 0 and 7 of an expansion: their mean is the parent's centre
+	c[0] = 0.5f * (a.tx + b.tx); c[1] = 0.5f * (a.ty + b.ty); c[2] = 0.5f * (a.tz + b.tz);
+}
+// bounds_work's item mapping and its inverse: the new kernels pick (group, chunk) themselves and hand bounds_work the index that maps to it,
+// so that bounds_work -- and with it every kernel that was there before -- stays as it was
+__device__ __forceinline__ void bounds_item_of(int work, int total, int groups, int chunks, int& group, int& chunk)
+{
+	if ((chunks & 7) == 0) {
+		const int cpx = chunks >> 3, xcd = work & 7, slot = work >> 3;
+		group = slot / cpx;
+		chunk = xcd * cpx + (slot - group * cpx);
+	} else {
+		const int swz = xcd_remap(work, total);
+		chunk = swz / groups; group = swz - chunk * groups;
+	}
+}
+__device__ __forceinline__ int bounds_work_of(int group, int chunk, int groups, int chunks)
+{
+	if ((chunks & 7) == 0) {
+		const int cpx = chunks >> 3, xcd = chunk / cpx;
+		return ((group * cpx + (chunk - xcd * cpx)) << 3) | xcd;
+	}
+	const int nb = groups * chunks, q = nb >> 3, r = nb & 7, swz = chunk * groups + group;
+	int xcd, off;
+	if (swz < r * (q + 1)) { xcd = swz / (q + 1); off = swz - xcd * (q + 1); }
+	else { const int t = swz - r * (q + 1); xcd = r + t / q; off = t - (xcd - r) * q; }
+	return (off << 3) | xcd;
+}
+__global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __restrict__ cubes, int B, int G, DtDesc dt, BoundsOrder bo)
+{
+	constexpr int per = kSortBins / 1024;            // 32 consecutive bins per thread, padded against the bank conflict (task_scan_kernel)
+	__shared__ unsigned lds[kSortBins + kSortBins / per];
+	__shared__ unsigned wtot[16];
+	__shared__ int run_start[kBoundsOrderMaxRuns + 2];
+	__shared__ float ext[16][6];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	// the runs of equal rotation, in arrival order
+	const int seg = (G + 1023) / 1024, g0 = min(tid * seg, G), g1 = min(g0 + seg, G);
+	unsigned local = 0;
+	{
+		int prev = g0 < g1 ? group_rot(cubes, g0 > 0 ? g0 - 1 : 0) : 0;
+		for (int g = g0; g < g1; g++) { const int r = group_rot(cubes, g); local += (unsigned)(r != prev); prev = r; }
+	}
+	unsigned incl = local;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+	if (lane == 63) wtot[wave] = incl;
+	__syncthreads();
+	unsigned before = 0, total = 0;
+	for (int w = 0; w < 16; w++) { if (w < wave) before += wtot[w]; total += wtot[w]; }
+	const int runs = (int)total + 1;
+	if (runs > bo.max_runs) {
+		if (blockIdx.x == 0 && tid == 0) { bo.ctl[0] = 0; bo.ctl[1] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1; }
+		return;
+	}
+	if (tid == 0) { run_start[0] = 0; run_start[runs] = G; }
+	{
+		int id = (int)(before + incl - local);
+		int prev = g0 < g1 ? group_rot(cubes, g0 > 0 ? g0 - 1 : 0) : 0;
+		for (int g = g0; g < g1; g++) { const int r = group_rot(cubes, g); if (r != prev) run_start[++id] = g; prev = r; }
+	}
+	__syncthreads();
+	const int run = blockIdx.x;
+	if (run >= runs) return;
+	const int s0 = run_start[run], n = run_start[run + 1] - s0;
+	int item0 = 0, items = 0;
+	for (int q = 0; q < runs; q++) { if (q == run) item0 = items; items += (run_start[q + 1] - run_start[q] + 1) >> 1; }
+	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; if (bo.host_note) *bo.host_note = (long long)G << 1; }
+	// the extent of the run's centres
+	float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+	for (int j = tid; j < n; j += 1024) {
+		float c[3];
+		group_centre(cubes, s0 + j, B, c);
+#pragma unroll
+		for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], c[k]); hi[k] = fmaxf(hi[k], c[k]); }
+	}
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
+		if (lane == 0) { ext[wave][k] = lo[k]; ext[wave][3 + k] = hi[k]; }
+	}
+	for (int i = tid; i < kSortBins + kSortBins / per; i += 1024) lds[i] = 0u;
+	__syncthreads();
+	float span = 0.f;
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		for (int w = 0; w < 16; w++) { lo[k] = fminf(lo[k], ext[w][k]); hi[k] = fmaxf(hi[k], ext[w][3 + k]); }
+		span = fmaxf(span, hi[k] - lo[k]);
+	}
+	const float cell = fmaxf(fmaxf(bo.cell_vox, 1.f), span * dt.scale_f * (1.f / 31.5f));   // voxels; 32 cells cover the span
+	const float to_cell = dt.scale_f / cell;
+	for (int j = tid; j < n; j += 1024) {
+		float c[3];
+		group_centre(cubes, s0 + j, B, c);
+		unsigned key = 0;
+#pragma unroll
+		for (int k = 0; k < 3; k++) {
+			const unsigned v = (unsigned)min(max((int)((c[k] - lo[k]) * to_cell), 0), 31);
+#pragma unroll
+			for (int b = 0; b < 5; b++) key |= ((v >> b) & 1u) << (3 * b + k);
+		}
+		bo.keys[s0 + j] = key;
+		atomicAdd(&lds[key + key / per], 1u);
+	}
+	__syncthreads();
+	// exclusive scan of the 32 768 counters
+	const int b0 = tid * (per + 1);
+	local = 0;
+#pragma unroll
+	for (int k = 0; k < per; k++) local += lds[b0 + k];
+	incl = local;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+	__syncthreads();                                  // wtot is read above by every thread
+	if (lane == 63) wtot[wave] = incl;
+	__syncthreads();
+	before = 0;
+	for (int w = 0; w < wave; w++) before += wtot[w];
+	unsigned runsum = before + incl - local;
+#pragma unroll
+	for (int k = 0; k < per; k++) { const unsigned c = lds[b0 + k]; lds[b0 + k] = runsum; runsum += c; }
+	__syncthreads();
+	for (int j = tid; j < n; j += 1024) {
+		const unsigned key = bo.keys[s0 + j];             // this thread's own store
+		bo.order[s0 + atomicAdd(&lds[key + key / per], 1u)] = (unsigned)(s0 + j);
+	}
+	__threadfence();
+	__syncthreads();
+	for (int j = 2 * tid; j < n; j += 2048) {
+		const int it = item0 + (j >> 1);
+		bo.pairs[2 * it] = (int)__hip_atomic_load(&bo.order[s0 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		bo.pairs[2 * it + 1] = j + 1 < n ? (int)__hip_atomic_load(&bo.order[s0 + j + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+	}
+}
+
+// the plain launch walking order[] (bounds_order = 1): bounds_kernel<1, true> with the slot -> group table.  gate: 0 = leave at once when the
+// pre-pass built an order (the launch after bounds_pair_kernel for batches it left alone), 1 = walk order[] when there is one
+template <bool TRUNC>
+__global__ __launch_bounds__(kBoundsThreads) void bounds_ordered_kernel(
+    const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
+    const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int chunks, int chunk_pts,
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const unsigned* __restrict__ order, const int* __restrict__ ctl, int gate)
+{
+	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
+	int work = blockIdx.x;
+	if (ctl[1]) {
+		if (!gate) return;
+		int group, chunk;
+		bounds_item_of(work, gridDim.x, groups, chunks, group, chunk);
+		work = bounds_work_of((int)order[group], chunk, groups, chunks);
+	}
+	bounds_work<1, true, TRUNC>(work, gridDim.x, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
+}
+
+// one member of a pair item: is the group a sibling set, and then its two translations per axis, its delta and coefficient
+__device__ __forceinline__ bool pair_member(const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int group, int B, PairMember& m, int& rot)
+{
+	CubeRec cr[kGroup];
+	load_group(cubes, parents, group, B, cr);
+	bool sib = group * kGroup + kGroup <= B;
+#pragma unroll
+	for (int c = 0; c < kGroup; c++)
+		sib = sib && cr[c].rot == cr[0].rot && cr[c].tx == cr[c & 1].tx && cr[c].ty == cr[c & 2].ty && cr[c].tz == cr[c & 4].tz &&
+		      cr[c].delta == cr[0].delta && cr[c].coeff == cr[0].coeff;
+	m.ts = SiblingSet{cr[0].tx, cr[1].tx, cr[0].ty, cr[2].ty, cr[0].tz, cr[4].tz};
+	m.delta = cr[0].delta; m.coeff = cr[0].coeff; rot = cr[0].rot;
+	return sib;
+}
+// the pair launch (bounds_order = 2): grid = max_items * chunks, an item = the two groups pairs[] names over one chunk, mapped to the XCDs as bounds_work maps (group, chunk).  Two sibling sets of one rotation are evaluated together
+// (lean_points_pair); anything else -- a generic group, a partial last group, a foreign rotation, a single -- group by group on the plain path.
+template <bool TRUNC>
+__global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
+    const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
+    const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, const int* __restrict__ ctl)
+{
+	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
+	const int work = blockIdx.x, total = gridDim.x;
+	int chunk, item;
+	if ((chunks & 7) == 0) {
+		const int cpx = chunks >> 3, xcd = work & 7, slot = work >> 3;
+		item = slot / cpx;
+		chunk = xcd * cpx + (slot - item * cpx);
+	} else {
+		const int swz = xcd_remap(work, total);
+		chunk = swz / max_items; item = swz - chunk * max_items;
+	}
+	if (item >= ctl[0]) return;                          // ctl[0] = 0: the pre-pass left the batch alone, the gated plain launch that follows evaluates it
+	int ga = pairs[2 * item], gb = pairs[2 * item + 1];
+	if (gb >= 0) {
+		PairMember A, Bm;
+		int ra, rb;
+		const bool sa = pair_member(cubes, parents, ga, B, A, ra), sb = pair_member(cubes, parents, gb, B, Bm, rb);
+		if (sa && sb && ra == rb) {
+			if (A.coeff != 0.f && Bm.coeff == 0.f) {       // at most one member without a rotation radius: make it the first (LZ_A)
+				const PairMember t = A; A = Bm; Bm = t;
+				const int g = ga; ga = gb; gb = g;
+			}
+			const Rot9 R0 = rots[ra];
+			const int p0 = chunk * chunk_pts;
+			const int p1 = p0 + chunk_pts < N ? p0 + chunk_pts : N;
+			f2 ubA[4], lbA[4], ubB[4], lbB[4];
+#pragma unroll
+			for (int k = 0; k < 4; k++) { ubA[k] = f2{0.f, 0.f}; lbA[k] = f2{0.f, 0.f}; ubB[k] = f2{0.f, 0.f}; lbB[k] = f2{0.f, 0.f}; }
+			bool okA = true, okB = true;
+			if (A.coeff == 0.f && Bm.coeff == 0.f) lean_points_pair<true, true, TRUNC>(src, p0, p1, dt, R0, A, Bm, ubA, lbA, ubB, lbB, okA, okB);
+			else if (A.coeff == 0.f) lean_points_pair<true, false, TRUNC>(src, p0, p1, dt, R0, A, Bm, ubA, lbA, ubB, lbB, okA, okB);
+			else lean_points_pair<false, false, TRUNC>(src, p0, p1, dt, R0, A, Bm, ubA, lbA, ubB, lbB, okA, okB);
+			// some wavefront gave a member up: its sums are void in all four (the barrier hands back a predicate, so one per member)
+			const int bad = (__syncthreads_or(okA ? 0 : 1) ? 1 : 0) | (__syncthreads_or(okB ? 0 : 1) ? 2 : 0);
+			float ub[kGroup], lb[kGroup];
+			if (!(bad & 1)) {
+#pragma unroll
+				for (int k = 0; k < 4; k++) { ub[2 * k] = ubA[k].x; ub[2 * k + 1] = ubA[k].y; lb[2 * k] = lbA[k].x; lb[2 * k + 1] = lbA[k].y; }
+				bounds_item_store(ub, lb, ga, chunk, chunks, B, scratch, ub_out, lb_out, red);
+				__syncthreads();                              // `red` is reused
+			}
+			if (!(bad & 2)) {
+#pragma unroll
+				for (int k = 0; k < 4; k++) { ub[2 * k] = ubB[k].x; ub[2 * k + 1] = ubB[k].y; lb[2 * k] = lbB[k].x; lb[2 * k + 1] = lbB[k].y; }
+				bounds_item_store(ub, lb, gb, chunk, chunks, B, scratch, ub_out, lb_out, red);
+				__syncthreads();
+			}
+			if (bad == 0) return;
+			if (!(bad & 1)) ga = gb;                          // what is left for the plain path: the member given up, or both
+			if (bad != 3) gb = -1;
+		}
+	}
+#pragma unroll 1
+	for (int m = 0; m < 2; m++) {
+		const int g = m ? gb : ga;
+		if (g < 0) break;
+		if (m) __syncthreads();
+		bounds_work<1, true, TRUNC>(bounds_work_of(g, chunk, groups, chunks), groups * chunks, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
+	}
+}
+
 // The same evaluation for a batch whose size only the DEVICE knows (the device-resident BnB queues, bnbqueue.hip):
 // *d_groups expansions of 8 children each; a fixed grid walks the (group, chunk) work items, the split of the cloud
 // into chunks follows from the count exactly as on the host (bounds_shape).  ub_out / lb_out: [8 * groups] each.
@@ -1385,12 +1748,26 @@ hipError_t launch_queue_sort(const ParentRec* parents, const Rot9* rots, const i
 }
 
 hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const CubeRec* cubes, const ParentRec* parents,
-                         int B, float* scratch, float* ub, float* lb, hipStream_t stream)
+                         int B, float* scratch, float* ub, float* lb, hipStream_t stream, const BoundsOrder* bo)
 {
 	if (B <= 0 || N <= 0) return hipSuccess;
 	int groups, chunks, chunk_pts;
 	bounds_shape(B, N, &groups, &chunks, &chunk_pts);
 	dim3 grid(groups * chunks), block(kBoundsThreads);
+	if (bo && bo->mode > 0 && cubes && !parents && dt.layout == 1 && bounds_lean(dt) && groups >= bo->min_groups && bo->max_runs >= 1 && bo->max_runs <= kBoundsOrderMaxRuns) {
+		hipLaunchKernelGGL(bounds_order_kernel, dim3(bo->max_runs), dim3(1024), 0, stream, cubes, B, groups, dt, *bo);
+		if (bo->mode == 1) {
+			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_ordered_kernel<true> : bounds_ordered_kernel<false>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups,
+			                   chunks, chunk_pts, scratch, ub, lb, bo->order, bo->ctl, 1);
+		} else {
+			const int max_items = (int)bounds_order_items(groups, bo->max_runs);
+			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_pair_kernel<true> : bounds_pair_kernel<false>), dim3(max_items * chunks), block, 0, stream, src, N, dt, rots, cubes, parents,
+			                   B, groups, max_items, chunks, chunk_pts, scratch, ub, lb, bo->pairs, bo->ctl);
+			// more runs than the cap (unrelated cubes): the pair launch left at once and this one is the plain launch; otherwise it leaves at once
+			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_ordered_kernel<true> : bounds_ordered_kernel<false>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups,
+			                   chunks, chunk_pts, scratch, ub, lb, bo->order, bo->ctl, 0);
+		}
+	} else
 	if (dt.trunc > 0.f) {                                                // the truncated objective (DtDesc::trunc): the same four choices
 		if (dt.layout == 0)
 			hipLaunchKernelGGL((bounds_kernel<0, false, true>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);

@@ -118,8 +118,22 @@ constexpr int kIcpAcc = 16;        // sum(q-cq)[3] sum(m-cm)[3] sum((q-cq)(m-cm)
 // scratch must hold groups*chunks*2*kGroup floats.  ub/lb: [B].
 size_t bounds_scratch_floats(int B, int N, int* groups_out, int* chunks_out);
 // `parents` != nullptr: B/8 expansions, `cubes` ignored
+// `bo` given (lean bricked grids, at least bo->min_groups groups): a device pre-pass orders the groups by where their gathers land and the
+// launch walks them in that order (mode 1), two neighbours of the order at a time (mode 2); every group writes its own rows: same bits
+struct BoundsOrder {
+	int mode;                    // 1 order, 2 order + pairs
+	int min_groups, max_runs;    // fewer groups, or more runs of equal rotation: the launch is the unordered one
+	float cell_vox;              // smallest Morton cell of the order, in DT voxels
+	unsigned* keys;              // [groups]
+	unsigned* order;             // [groups]
+	int* pairs;                  // [2 * bounds_order_items(groups, max_runs)]: the two groups of an item, -1 = none
+	int* ctl;                    // [0] items of the pair list, [1] 1 = order and pairs are valid (0: too many runs)
+	long long* host_note;        // pinned host memory: the pre-pass leaves (groups << 1 | left alone) there, a hint for the caller's next launch
+};
+constexpr int kBoundsOrderMaxRuns = 64;
+inline size_t bounds_order_items(int groups, int max_runs) { return (size_t)(groups + 1) / 2 + (size_t)max_runs; }
 hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const CubeRec* cubes, const ParentRec* parents,
-                         int B, float* scratch, float* ub, float* lb, hipStream_t stream);
+                         int B, float* scratch, float* ub, float* lb, hipStream_t stream, const BoundsOrder* bo = nullptr);
 
 // an UNRELATED cube batch, evaluated grouped by (rotation, pass, translation cell) and written back in the caller's order (same bits)
 size_t bounds_grouped_scratch_bytes(int B, int nrots);

@@ -740,6 +740,33 @@ void Engine::ensure_bounds_scratch(int B, hipStream_t s)
 	d_scratch_.alloc(need);
 }
 
+const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
+{
+	const int groups = (B + kGroup - 1) / kGroup;
+	if (p_.bounds_order <= 0 || groups < p_.bounds_order_min_groups || !bounds_uses_lean(bounds_dt())) return nullptr;
+	if (!h_border_note_) { h_border_note_.alloc(1); *h_border_note_.get() = -1; }
+	if (p_.bounds_order_reprobe > 0) {
+		// unrelated cubes come in streams of equal size: once a pre-pass has left such a batch alone, the next ones take the plain launch untouched
+		const long long note = *static_cast<volatile long long*>(h_border_note_.get());
+		if (note == (((long long)groups << 1) | 1) && ++border_skipped_ < p_.bounds_order_reprobe) return nullptr;
+		border_skipped_ = 0;
+	}
+	const int max_runs = std::min(std::max(p_.bounds_order_max_runs, 1), kBoundsOrderMaxRuns);
+	const size_t items = bounds_order_items(groups, max_runs), need = 2 * (size_t)groups + 2 * items + 2;
+	if (need > d_border_.size()) {
+		HIPCHK(hipStreamSynchronize(stream_));
+		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
+		d_border_.alloc(need + need / 2);
+	}
+	// carved for this launch: a stream runs its launches in order, and the buffer only ever grows after the streams were waited for
+	border_.mode = p_.bounds_order >= 2 ? 2 : 1;
+	border_.min_groups = p_.bounds_order_min_groups; border_.max_runs = max_runs; border_.cell_vox = p_.bounds_order_cell;
+	border_.keys = d_border_.get(); border_.order = border_.keys + groups;
+	border_.pairs = reinterpret_cast<int*>(border_.order + groups); border_.ctl = border_.pairs + 2 * items;
+	border_.host_note = h_border_note_.get();
+	return &border_;
+}
+
 void Engine::eval_bounds_dev(const Rot9* d_rots, const CubeRec* d_cubes, int B, float* d_ub, float* d_lb, hipStream_t s, const ParentRec* d_parents)
 {
 	DeviceGuard guard(dev_);
@@ -747,8 +774,23 @@ void Engine::eval_bounds_dev(const Rot9* d_rots, const CubeRec* d_cubes, int B, 
 	if (inliers_ < (int)N_)
 		HIPCHK(launch_bounds_trim(d_src_, (int)N_, dt_, d_rots, d_cubes, d_parents, B, inliers_, d_ub, d_lb, s ? s : stream_));
 	else
-		HIPCHK(launch_bounds(d_src_, (int)N_, bounds_dt(), d_rots, d_cubes, d_parents, B, d_scratch_, d_ub, d_lb, s ? s : stream_));
+	{
+		const BoundsOrder* bo = d_cubes && !d_parents ? ensure_bounds_order(B, s) : nullptr;     // cube batches only: the search's own rounds come ordered (launch_queue_sort)
+		HIPCHK(launch_bounds(d_src_, (int)N_, bounds_dt(), d_rots, d_cubes, d_parents, B, d_scratch_, d_ub, d_lb, s ? s : stream_, bo));
+		border_form_ = bo ? bo->mode : 0; border_stream_ = s ? s : stream_;
+	}
 	cnt_.bounds_launches++;
+}
+
+void Engine::debug_bounds_order(int info[3])
+{
+	DeviceGuard guard(dev_);
+	info[0] = border_form_; info[1] = info[2] = 0;
+	if (!border_form_) return;
+	int ctl[2] = {0, 0};
+	HIPCHK(hipStreamSynchronize(border_stream_));
+	HIPCHK(hipMemcpy(ctl, border_.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+	info[1] = ctl[1]; info[2] = ctl[0];
 }
 
 void Engine::reduce_min_dev(const float* d_v, int n, float* d_min, int* d_idx, hipStream_t s)

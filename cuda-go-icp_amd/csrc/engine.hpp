@@ -66,6 +66,14 @@ struct Params {
 	float ub_share = 0.f;         // opt-in, widened search: on top of a batch's parents by smallest lower bound, this fraction more are drawn by the smallest upper
 	                              // bound seen inside them (needs ub_tiebreak = 1 for the key).  Measured slower everywhere: default 0
 	int sort_items = 1;           // rounds of >= 2 048 expansions walk their (expansion, chunk) items in the order of where their gathers land (device.hip, launch_queue_sort)
+	int bounds_order = 2;         // tuning only.  Cube batches handed in on the device (eval_bounds_dev, lean bricked grid): 0 the groups are walked as they came; 1 a device pre-pass
+	                              // orders them by run of equal rotation and Morton cell of the parent cube's centre (device.hip, bounds_order_kernel); 2 and two
+	                              // neighbours of that order are evaluated together (lean_points_pair).  Same bits in every form
+	int bounds_order_min_groups = 1024;   // tuning only: batches of fewer expansions keep the plain launch (the pre-pass is a launch of its own)
+	int bounds_order_max_runs = 16;       // tuning only: batches with more runs of equal rotation (unrelated cubes) are walked as they came; at most 64
+	float bounds_order_cell = 4.f;        // tuning only: smallest Morton cell of the order, in DT voxels
+	int bounds_order_reprobe = 64;        // tuning only: after the pre-pass left a batch alone, batches of the same size skip the pre-pass (the parent's launch) and every
+	                                      // this-many-th of them runs it again; 0: every batch runs it
 	int twin_fusion = 1;          // the same translation node listed by both searches of a rotation child in a round is gathered once (device.hip lean_points<.., 2>)
 	int lds_tiles = 2;            // LDS-staged DT tiles for inner searches whose selected nodes lie within a few voxels of each other (deep rounds): 0 off, 1 the
 	                              // tile evaluation is launched every round, 2 only while the previous rounds had searches that qualify (default)
@@ -220,6 +228,7 @@ public:
 	// twin fusion when the engine has it on).  out[pass][8 n]: the children's bounds of pass 0 (upper-bound search) and pass 1
 	// (lower-bound search), in the order of parents4.  info[0] = point chunks the evaluation split the cloud into, info[1] = 1 when the
 	// twin lists were in use.
+	void debug_bounds_order(int info[3]);   // test: form of the last eval_bounds_dev launch, and what its pre-pass decided (device.hip BoundsOrder::ctl)
 	void debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2]);
 	// measurement / test: the 8 children of nseg x n expansions (segment i: rotation i, parents4[(i*n + e)*4 ..] = corner xyz + width) through
 	// the LDS-tile kernel and through the direct kernel; out arrays hold 8*nseg*n floats each; ms[0] tile, ms[1] direct (per launch)
@@ -291,6 +300,13 @@ private:
 	double source_order_ms_ = 0, voxel_ms_ = 0, outlier_ms_ = 0;
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(size_t B);
+	const BoundsOrder* ensure_bounds_order(int B, hipStream_t s);   // the order / pair buffers for a launch of B cube bounds (nullptr: the plain launch); grows like the scratch
+	Buf<unsigned> d_border_;
+	PinnedBuf<long long> h_border_note_;  // what the last pre-pass found (BoundsOrder::host_note): read without a wait, a hint only -- every form gives the same bits
+	int border_skipped_ = 0;
+	int border_form_ = 0;                // the form of the last eval_bounds_dev launch, and the stream it went to (debug_bounds_order)
+	hipStream_t border_stream_ = nullptr;
+	BoundsOrder border_{};
 	void ensure_bounds_scratch(int B, hipStream_t s);   // d_scratch_ holds a launch of B cube bounds; growing waits for stream_ and s only
 	void upload_rots(const std::vector<Rot9>& rots);    // the batch's rotation table -> d_rots_, on stream_
 	void run_inner(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);

@@ -187,6 +187,15 @@ typedef struct goicp_params {
 	                          * lane_min_searches.  Same searches, same bounds, same result per search; measured (tools/lanes_probe.py): prove-the-optimum
 	                          * bunny 6.74 -> 5.7 s, synthetic 40 k 721 -> 649 ms, default (early-exit) registrations never qualify and are unchanged */
 	int32_t lane_min_searches; /* default 64 */
+	int32_t bounds_order;    /* tuning only.  goicp_eval_bounds_device on a bricked fp32 grid that fits the Infinity Cache: 0 the groups of eight cubes are walked as they
+	                          * came; 1 a device pre-pass orders them by run of equal rotation (in arrival order) and, inside a run, by the Morton cell of the
+	                          * parent cube's centre, so that the workgroups in flight gather from neighbouring distance-transform lines; 2 and two
+	                          * neighbours of that order are evaluated by one workgroup, sharing the point load and the rotation.  Every cube's bounds are the same bits in all forms */
+	int32_t bounds_order_min_groups; /* tuning only: batches of fewer groups keep the plain launch */
+	int32_t bounds_order_max_runs;   /* tuning only: batches with more runs of equal rotation are walked as they came (at most 64) */
+	float bounds_order_cell;         /* tuning only: smallest Morton cell of the order, in distance-transform voxels (<= 0: the default) */
+	int32_t bounds_order_reprobe;    /* tuning only (default 64): once the pre-pass has left a batch alone, batches of the same size take the plain launch without a
+	                                  * pre-pass, and every this-many-th of them runs it again; 0: every batch runs the pre-pass */
 } goicp_params;
 
 void goicp_params_default(goicp_params* p);
@@ -740,6 +749,12 @@ int goicp_debug_bounds_tile(goicp_handle h, const float* rots9, const float* par
  */
 int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, const float* parents4, int32_t n, float* ub_ubpass, float* lb_ubpass,
                              float* ub_lbpass, float* lb_lbpass, int32_t info[2]);
+/* goicp_debug_bounds_order (test): how the last goicp_eval_bounds_device / goicp_time_bounds_device launch of this handle walked its batch.
+ * info[0] = the form launched (goicp_params::bounds_order: 0 the plain launch -- switch off, fewer groups than bounds_order_min_groups, not
+ * a bricked fp32 grid in the Infinity Cache --, 1 ordered, 2 ordered + pairs); for forms 1 and 2, read back after the launch has finished:
+ * info[1] = 1 when the device pre-pass built an order, 0 when it left the batch alone (more runs of equal rotation than
+ * bounds_order_max_runs); info[2] = the work items of the pair list (pairs and singles; 0 when left alone) */
+int goicp_debug_bounds_order(goicp_handle h, int32_t info[3]);
 /* diagnostics of the ICP pass's neighbour cache: two scoring passes at (R, t); *hits = queries of the second pass that
  * skipped the tree walk (-1 when the cache is off) */
 int goicp_debug_cache_hits(goicp_handle h, const float R[9], const float t[3], int64_t* hits);

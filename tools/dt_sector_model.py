@@ -13,6 +13,15 @@ index path; lanes outside the grid are left out) and counts, per layout:
 Layouts: 4x4x1 / 4x2x2 / 2x2x4 / 2x4x2 (64-B sector shape, x y z, inside 4x4x4 bricks of 256 B) or linear.
 
   python3 tools/dt_sector_model.py [--layouts 4x4x1,4x2x2,...] [--lanes 4] [--every 16] [--merged] [--json out.json]
+
+--lines: the 128-B LINES (two sectors of a brick) instead of the tags -- what the L1 asks the L2 for.  Distinct lines per wavefront iteration
+(64 points x 8 children), per workgroup iteration (256 points: the sum over its four wavefronts and their union) and per (expansion, chunk)
+item; then, for windows of consecutive expansions of one rotation run, union / sum of their line sets over the same points -- 5 expansions
+over 256 points, 20 over 1 024, a PAIR over 64 and over 256 -- in the order the batch arrives in and in the order of bounds_order_kernel
+(device.hip: Morton cell of the parent cube's centre, 5 bits per axis over the run's extent, cells of at least --cell voxels), and the median
+distance in voxels between the centres of consecutive expansions.
+
+  python3 tools/dt_sector_model.py --lines [--cell 4] [--every 16] [--json out.json]
 """
 import argparse
 import json
@@ -78,6 +87,85 @@ def tags(addr_bytes, valid, lanes):
     return int(distinct.sum() + (s[:, 0] >= 0).sum())
 
 
+def run_order(centres_vox, cell):
+    """bounds_order_kernel's order of one rotation run (ties in arrival order)"""
+    lo = centres_vox.min(0)
+    span = float((centres_vox.max(0) - lo).max())
+    c = max(cell, 1.0, span / 31.5)
+    q = np.clip(((centres_vox - lo) / c).astype(np.int64), 0, 31)
+    key = np.zeros(len(q), np.int64)
+    for b in range(5):
+        for k in range(3):
+            key |= ((q[:, k] >> b) & 1) << (3 * b + k)
+    return np.argsort(key, kind="stable")
+
+
+def lines_mode(a, rots, recs, src, mn, scale, V):
+    N = len(src)
+    chunk_pts = -(-(-(-N // 8)) // 256) * 256                 # bounds_shape: eight chunks, a multiple of 256 points
+    n_exp, per_run = len(recs) // 8, len(recs) // 8 // len(rots)
+
+    def line_ids(e, pts):
+        r = recs[8 * e:8 * e + 8]
+        R = rots[int(r["rot"][0])].reshape(3, 3).astype(np.float32)
+        p = src[pts]
+        rp = (p[:, 0:1] * R[:, 0] + p[:, 1:2] * R[:, 1]) + p[:, 2:3] * R[:, 2]
+        t = [(r["tx"][0], r["tx"][1]), (r["ty"][0], r["ty"][2]), (r["tz"][0], r["tz"][4])]
+        idx = [[((rp[:, k] + np.float32(t[k][j]) - mn[k]) * scale + np.float32(0.5)).astype(np.int32) for j in (0, 1)] for k in range(3)]
+        ok = np.ones(len(p), bool)
+        for k in range(3):
+            for j in (0, 1):
+                ok &= (idx[k][j] >= 0) & (idx[k][j] < V)
+        out = np.full((len(p), 8), -1, np.int64)
+        for c in range(8):
+            el = element_index(np.clip(idx[0][c & 1], 0, V - 1), np.clip(idx[1][c >> 1 & 1], 0, V - 1), np.clip(idx[2][c >> 2 & 1], 0, V - 1), V, "4x4x1")
+            out[:, c] = np.where(ok, el >> 5, -1)                   # 32 floats per 128-B line
+        return out
+
+    def distinct(x):
+        u = np.unique(x)
+        return len(u) - int(u[0] < 0) if len(u) else 0
+
+    centres = np.stack([(recs[f][0::8] + recs[f][7::8]) * np.float32(0.5) for f in ("tx", "ty", "tz")], 1).astype(np.float64) * float(scale)
+    orders = {"as_given": [np.arange(per_run) for _ in rots], "ordered": [run_order(centres[r * per_run:(r + 1) * per_run], a.cell) for r in range(len(rots))]}
+    out = {"batch": "bench.make_batch(%d expansions, %d rotations, seed 1234); windows every %d expansions" % (n_exp, len(rots), a.every), "N": N, "V": V,
+           "chunk_pts": chunk_pts, "cell_voxels": a.cell}
+    # per wavefront / workgroup iteration / item, every k-th expansion, chunk 0 .. 7 in turn
+    wave, wg_sum, wg_union, item, n_w, n_g, n_i = 0, 0, 0, 0, 0, 0, 0
+    for j, e in enumerate(range(0, n_exp, a.every)):
+        ch = j % 8
+        pts = np.arange(ch * chunk_pts, min((ch + 1) * chunk_pts, N))
+        L = line_ids(e, pts)
+        item += distinct(L); n_i += 1
+        for g0 in range(0, len(pts), 256):
+            ws = [distinct(L[w0:w0 + 64]) for w0 in range(g0, min(g0 + 256, len(pts)), 64)]
+            wave += sum(ws); n_w += len(ws)
+            wg_sum += sum(ws); wg_union += distinct(L[g0:g0 + 256]); n_g += 1
+    out["lines_per_wave_iteration"] = round(wave / n_w, 1)
+    out["lines_per_workgroup_iteration"] = {"sum_of_wavefronts": round(wg_sum / n_g, 1), "union": round(wg_union / n_g, 1),
+                                            "per_wave_if_shared": round(wg_union / n_w, 1)}
+    out["lines_per_item"] = round(item / n_i, 1)
+    for name, ords in orders.items():
+        res = {}
+        dist = []
+        for r, o in enumerate(ords):
+            c = centres[r * per_run:(r + 1) * per_run][o]
+            dist.append(np.linalg.norm(np.diff(c, axis=0), axis=1))
+        res["median_voxels_between_consecutive"] = round(float(np.median(np.concatenate(dist))), 1)
+        for label, k, npts in (("5_expansions_256_points", 5, 256), ("20_expansions_1024_points", 20, 1024), ("pair_64_points", 2, 64), ("pair_256_points", 2, 256)):
+            un = sm = 0
+            for r, o in enumerate(ords):
+                for w, s0 in enumerate(range(0, per_run - k + 1, max(a.every * 4, k))):
+                    p0 = ((r * 7 + w * 3) % 8) * chunk_pts + 256 * (w % 4)
+                    pts = np.arange(p0, min(p0 + npts, N))
+                    sets = [line_ids(r * per_run + int(o[s0 + i]), pts) for i in range(k)]
+                    sm += sum(distinct(x) for x in sets)
+                    un += distinct(np.concatenate(sets))
+            res[label + "_union_over_sum"] = round(un / max(sm, 1), 3)
+        out[name] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layouts", default="4x4x1,4x2x2,2x2x4,2x4x2,linear")
@@ -85,6 +173,8 @@ def main():
     ap.add_argument("--every", type=int, default=16, help="model every k-th expansion of the batch")
     ap.add_argument("--merged", action="store_true", help="also model 16-B x-row loads for x siblings < 4 voxels apart")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--lines", action="store_true", help="model 128-B lines and their sharing between consecutive expansions (see above)")
+    ap.add_argument("--cell", type=float, default=4.0, help="--lines: smallest Morton cell of the order, voxels")
     a = ap.parse_args()
 
     from conftest import load_pkg, cloud
@@ -110,6 +200,13 @@ def main():
     pad = (-N) % 64
     V = 300
     mn, scale = dt_geometry(model, V)
+    if a.lines:
+        out = lines_mode(a, rots, recs, src, mn, scale, V)
+        print(json.dumps(out, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     layouts = a.layouts.split(",")
     res = {lay: {"gather_tags": 0, "gathers": 0, "merged_tags": 0, "merged_instr": 0} for lay in layouts}
     spread = {}                                              # child spacing (voxels) -> [sum of distinct sectors per lane, lanes] per layout

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn the raw per-dispatch counter averages of tools/pmc_collect.sh into the summary committed under profiles/.
-usage: pmc_to_profile.py bounds <pmc outdir> <workload text> > profiles/rNN_pmc_bounds_<w>.json
+usage: pmc_to_profile.py bounds <pmc outdir> <workload text> [kernel substring, default bounds_kernel] > profiles/rNN_pmc_bounds_<w>.json
        pmc_to_profile.py icp    <pmc outdir> <workload text> > profiles/rNN_pmc_icp.json
 Corrections as /opt/skills/guides/MI355X_MICROARCH.md prescribes (HBM / rocprofv3 section): separate --pmc passes; FETCH_SIZE and
 WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE counts 64 B per 128-byte request, so fabric-side read bytes = 2 x FETCH_SIZE x 1024."""
@@ -11,7 +11,7 @@ import sys
 
 mode, out, workload = sys.argv[1], sys.argv[2], sys.argv[3]
 here = os.path.dirname(os.path.abspath(__file__))
-want = "bounds_kernel" if mode == "bounds" else "icp_"
+want = sys.argv[4] if len(sys.argv) > 4 else "bounds_kernel" if mode == "bounds" else "icp_"
 raw = json.loads(subprocess.check_output([sys.executable, os.path.join(here, "pmc_summary.py"), out, want, "--largest"]))
 
 
@@ -21,7 +21,7 @@ def traffic(e):
 
 
 if mode == "bounds":
-    k = [n for n in raw if "bounds_kernel" in n][0]
+    k = [n for n in raw if want in n][0]
     e = raw[k]
     rawb, corr = traffic(e)
     hit, miss = e.get("TCC_HIT_sum", 0.0), e.get("TCC_MISS_sum", 0.0)
