@@ -50,7 +50,9 @@ struct Params {
 	int morton_sort = 2;          // source order on the device: 0 input order, 1 Morton curve, 2 k-d order (locality of the DT gathers)
 	int icp_chunk = 16;           // ICP iterations queued per host round trip
 	int kd_gpu_build = -1;        // box hierarchy built on the device (Morton sort, looser boxes): 1 yes, 0 / -1 host median splits (threaded)
-	int bounds_fp16 = 0;          // 1: BnB cube bounds read a half-precision copy of the bricked DT (rounded toward zero: lower bounds stay valid, upper bounds low by <= 2^-10 relative); ICP, the DT re-score and trimmed bounds keep the fp32 grid.  Not bit-parity: opt-in
+	int bounds_fp16 = 0;          // 1: BnB cube bounds read a half-precision copy of the bricked DT (rounded toward zero: lower bounds stay valid; each LOOKED-UP VALUE is low by < 2^-10 relative where its half is normal, i.e. from 2^-14 up to 65504 -- below, by < 2^-24 absolute; above,
+	                              // it is 65504 -- and a bound's own deviation is larger: the radius subtracted from the value, v - rho, amplifies it); ICP, the DT re-score and trimmed bounds keep the fp32 grid.  No effect with
+	                              // dt_layout = 0: the copy is made of the bricked grid only, a linear-layout engine keeps fp32 bounds.  Not bit-parity: opt-in
 	int icp_nn_cache = 0;         // 1: an ICP pass skips (exactly) the tree walk of every query whose cached neighbour is provably still the nearest (measured slower on real trajectories, EXPERIMENTS 3.6: opt-in);
 	                              // 2: the same, switched on inside a run only once the error falls by < 2 % per 16 iterations (the tail; measured +0..3 %, EXPERIMENTS R4.11: opt-in);
 	                              // 0: every query walks every pass; bit-identical states in every mode

@@ -121,8 +121,12 @@ typedef struct goicp_params {
 	int32_t icp_fused;       /* 1: one launch per ICP iteration, the last workgroup to arrive runs the update;
 	                          * 0: correspondence pass + update as two launches (same arithmetic, bit-identical states) */
 	int32_t bounds_fp16;     /* 1: the BnB cube bounds read a half-precision copy of the bricked DT (one 128-byte line per 4x4x4 brick
-	                          * instead of two), rounded toward zero so that lower bounds stay valid; upper bounds come out low by
-	                          * <= 2^-10 relative.  ICP, the DT re-score of a pose and trimmed bounds keep the fp32 grid.  NOT the
+	                          * instead of two), rounded toward zero so that lower bounds stay valid.  Each LOOKED-UP VALUE comes out
+	                          * low by < 2^-10 relative where its half is normal (2^-14 .. 65504 in cloud units; below that by
+	                          * < 2^-24 absolute, above it the value is 65504); a bound deviates by more than that, because the
+	                          * rotation radius subtracted from the value (v - rho) amplifies the relative error of what is left.
+	                          * ICP, the DT re-score of a pose and trimmed bounds keep the fp32 grid.  No effect with dt_layout = 0:
+	                          * the copy is made of the bricked grid only, and a linear-layout engine evaluates fp32 bounds.  NOT the
 	                          * bit-parity path: opt-in, default 0 */
 	int32_t icp_nn_cache;    /* opt-in (default 0; measured slower on real ICP trajectories).  1: the ICP pass keeps, per source point, its last neighbour m, the position q_ref it was found at
 	                          * and a lower bound s on the distance from q_ref to every OTHER target point (a 2-nearest walk); at a later
