@@ -1119,9 +1119,9 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_kernel(
 // device).  Such a batch carries no rotation count and arrives in any translation order, so the pre-pass keys its G = ceil(B / 8) groups by
 // the RUN of equal rotation they arrive in (a rotation that recurs later starts a new run) and, inside a run, by the Morton cell of the
 // parent cube's centre in DT voxels: 5 bits per axis over the run's own extent, cells no smaller than cell_vox.  One workgroup per run:
-// every workgroup finds the run starts for itself (a scan over the rotation of each group), then counting-sorts its run in LDS and writes
-// its slice of order[] and, two neighbours of the order at a time, of the pair list (a leftover stays single).  More runs than max_runs
-// (unrelated cubes): ctl[1] = 0, the launch walks the groups as they came.  The order inside a cell is whatever the atomics give: no bound
+// every workgroup finds the run starts for itself (each group's rotation against its predecessor's), then counting-sorts its run in LDS and
+// writes its slice of order[] and, two neighbours of the order at a time, of the pair list (a leftover stays single).  More runs than max_runs
+// (unrelated cubes): ctl = (0, 0), the launch walks the groups as they came.  The order inside a cell is whatever the atomics give: no bound
 // depends on it, every group writes its own rows.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int group_rot(const CubeRec* __restrict__ cubes, int g) { return cubes[(size_t)g * kGroup].rot; }
@@ -1156,38 +1156,66 @@ __device__ __forceinline__ int bounds_work_of(int group, int chunk, int groups, 
 	else { const int t = swz - r * (q + 1); xcd = r + t / q; off = t - (xcd - r) * q; }
 	return (off << 3) | xcd;
 }
+// the 15-bit Morton cell of a centre: 5 bits per axis, cells of 1 / to_cell from the run's low corner
+__device__ __forceinline__ unsigned order_key(const float (&c)[3], const float (&lo)[3], float to_cell)
+{
+	unsigned key = 0;
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		const unsigned v = (unsigned)min(max((int)((c[k] - lo[k]) * to_cell), 0), 31);
+#pragma unroll
+		for (int b = 0; b < 5; b++) key |= ((v >> b) & 1u) << (3 * b + k);
+	}
+	return key;
+}
+// No step of the pre-pass waits on a chain of loads.  Run starts: thread t compares the rotation of groups t, t + 1024, ... with their
+// predecessors' (independent loads, all in flight together); the at most 63 boundaries take a slot of an LDS list and are ranked there.  A
+// thread keeps the centres and keys of its first kOrderHeld groups of the run in registers from the extent to the scatter (a longer run
+// loads the rest again in each phase), and the scatter writes order[] and the pair list straight from the slot the counting sort hands out.
+constexpr int kOrderHeld = 4;                        // runs of up to 4 096 groups; eight spill at the 128 VGPRs of a 1 024-thread workgroup
 __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __restrict__ cubes, int B, int G, DtDesc dt, BoundsOrder bo)
 {
 	constexpr int per = kSortBins / 1024;            // 32 consecutive bins per thread, padded against the bank conflict (task_scan_kernel)
-	__shared__ unsigned lds[kSortBins + kSortBins / per];
+	constexpr int words = kSortBins + kSortBins / per;
+	__shared__ __attribute__((aligned(16))) unsigned lds[words];
 	__shared__ unsigned wtot[16];
 	__shared__ int run_start[kBoundsOrderMaxRuns + 2];
+	__shared__ int bound[kBoundsOrderMaxRuns];
+	__shared__ int nbound;
 	__shared__ float ext[16][6];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	// the runs of equal rotation, in arrival order
-	const int seg = (G + 1023) / 1024, g0 = min(tid * seg, G), g1 = min(g0 + seg, G);
-	unsigned local = 0;
-	{
-		int prev = g0 < g1 ? group_rot(cubes, g0 > 0 ? g0 - 1 : 0) : 0;
-		for (int g = g0; g < g1; g++) { const int r = group_rot(cubes, g); local += (unsigned)(r != prev); prev = r; }
-	}
-	unsigned incl = local;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-	if (lane == 63) wtot[wave] = incl;
+	static_assert(words % 4 == 0, "the counters are cleared four at a time");
+	for (int i = tid; i < words / 4; i += 1024) reinterpret_cast<uint4*>(lds)[i] = make_uint4(0u, 0u, 0u, 0u);
+	if (tid == 0) nbound = 0;
 	__syncthreads();
-	unsigned before = 0, total = 0;
-	for (int w = 0; w < 16; w++) { if (w < wave) before += wtot[w]; total += wtot[w]; }
-	const int runs = (int)total + 1;
+	// the runs of equal rotation, in arrival order
+	for (int base = 0; base < G; base += 8 * 1024) {
+		int r[8], p[8];
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			const int g = min(base + k * 1024 + tid, G - 1);
+			r[k] = group_rot(cubes, g);
+			p[k] = lane == 0 ? group_rot(cubes, g > 0 ? g - 1 : 0) : 0;   // a group's record is a cache line of its own: the other lanes take the predecessor from their neighbour
+		}
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			const int g = base + k * 1024 + tid, up = __shfl_up(r[k], 1, 64);
+			if (lane) p[k] = up;
+			if (g < G && r[k] != p[k]) { const int slot = atomicAdd(&nbound, 1); if (slot < kBoundsOrderMaxRuns) bound[slot] = g; }
+		}
+	}
+	__syncthreads();
+	const int nb = nbound, runs = nb + 1;
 	if (runs > bo.max_runs) {
 		if (blockIdx.x == 0 && tid == 0) { bo.ctl[0] = 0; bo.ctl[1] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1; }
 		return;
 	}
 	if (tid == 0) { run_start[0] = 0; run_start[runs] = G; }
-	{
-		int id = (int)(before + incl - local);
-		int prev = g0 < g1 ? group_rot(cubes, g0 > 0 ? g0 - 1 : 0) : 0;
-		for (int g = g0; g < g1; g++) { const int r = group_rot(cubes, g); if (r != prev) run_start[++id] = g; prev = r; }
+	if (tid < nb) {                                      // nb < max_runs <= kBoundsOrderMaxRuns: every boundary has its slot
+		const int b = bound[tid];
+		int rank = 1;
+		for (int q = 0; q < nb; q++) rank += (int)(bound[q] < b);
+		run_start[rank] = b;
 	}
 	__syncthreads();
 	const int run = blockIdx.x;
@@ -1196,9 +1224,17 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	int item0 = 0, items = 0;
 	for (int q = 0; q < runs; q++) { if (q == run) item0 = items; items += (run_start[q + 1] - run_start[q] + 1) >> 1; }
 	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; if (bo.host_note) *bo.host_note = (long long)G << 1; }
-	// the extent of the run's centres
+	// the extent of the run's centres (a thread without a k-th group holds the run's last one again: it changes neither the extent nor, below, a counter)
+	float held[kOrderHeld][3];
 	float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-	for (int j = tid; j < n; j += 1024) {
+#pragma unroll
+	for (int h = 0; h < kOrderHeld; h++) group_centre(cubes, s0 + min(tid + h * 1024, n - 1), B, held[h]);
+#pragma unroll
+	for (int h = 0; h < kOrderHeld; h++) {
+#pragma unroll
+		for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], held[h][k]); hi[k] = fmaxf(hi[k], held[h][k]); }
+	}
+	for (int j = tid + kOrderHeld * 1024; j < n; j += 1024) {
 		float c[3];
 		group_centre(cubes, s0 + j, B, c);
 #pragma unroll
@@ -1210,7 +1246,6 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 		for (int o = 32; o > 0; o >>= 1) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
 		if (lane == 0) { ext[wave][k] = lo[k]; ext[wave][3 + k] = hi[k]; }
 	}
-	for (int i = tid; i < kSortBins + kSortBins / per; i += 1024) lds[i] = 0u;
 	__syncthreads();
 	float span = 0.f;
 #pragma unroll
@@ -1220,52 +1255,55 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	}
 	const float cell = fmaxf(fmaxf(bo.cell_vox, 1.f), span * dt.scale_f * (1.f / 31.5f));   // voxels; 32 cells cover the span
 	const float to_cell = dt.scale_f / cell;
-	for (int j = tid; j < n; j += 1024) {
+	unsigned key[kOrderHeld];
+#pragma unroll
+	for (int h = 0; h < kOrderHeld; h++) {
+		key[h] = order_key(held[h], lo, to_cell);
+		if (tid + h * 1024 < n) atomicAdd(&lds[key[h] + key[h] / per], 1u);
+	}
+	for (int j = tid + kOrderHeld * 1024; j < n; j += 1024) {
 		float c[3];
 		group_centre(cubes, s0 + j, B, c);
-		unsigned key = 0;
-#pragma unroll
-		for (int k = 0; k < 3; k++) {
-			const unsigned v = (unsigned)min(max((int)((c[k] - lo[k]) * to_cell), 0), 31);
-#pragma unroll
-			for (int b = 0; b < 5; b++) key |= ((v >> b) & 1u) << (3 * b + k);
-		}
-		bo.keys[s0 + j] = key;
-		atomicAdd(&lds[key + key / per], 1u);
+		const unsigned kj = order_key(c, lo, to_cell);
+		atomicAdd(&lds[kj + kj / per], 1u);
 	}
 	__syncthreads();
 	// exclusive scan of the 32 768 counters
 	const int b0 = tid * (per + 1);
-	local = 0;
+	unsigned local = 0;
 #pragma unroll
 	for (int k = 0; k < per; k++) local += lds[b0 + k];
-	incl = local;
+	unsigned incl = local;
 #pragma unroll
 	for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-	__syncthreads();                                  // wtot is read above by every thread
 	if (lane == 63) wtot[wave] = incl;
 	__syncthreads();
-	before = 0;
+	unsigned before = 0;
 	for (int w = 0; w < wave; w++) before += wtot[w];
 	unsigned runsum = before + incl - local;
 #pragma unroll
 	for (int k = 0; k < per; k++) { const unsigned c = lds[b0 + k]; lds[b0 + k] = runsum; runsum += c; }
 	__syncthreads();
-	for (int j = tid; j < n; j += 1024) {
-		const unsigned key = bo.keys[s0 + j];             // this thread's own store
-		bo.order[s0 + atomicAdd(&lds[key + key / per], 1u)] = (unsigned)(s0 + j);
-	}
-	__threadfence();
-	__syncthreads();
-	for (int j = 2 * tid; j < n; j += 2048) {
-		const int it = item0 + (j >> 1);
-		bo.pairs[2 * it] = (int)__hip_atomic_load(&bo.order[s0 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		bo.pairs[2 * it + 1] = j + 1 < n ? (int)__hip_atomic_load(&bo.order[s0 + j + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+	// slot `pos` of the run's order: order[] and the pos-th member of the run's pair list; a leftover's partner is -1
+	auto place = [&](unsigned kj, int j) {
+		const int pos = (int)atomicAdd(&lds[kj + kj / per], 1u), it = item0 + (pos >> 1);
+		bo.order[s0 + pos] = (unsigned)(s0 + j);
+		bo.pairs[2 * it + (pos & 1)] = s0 + j;
+		if (pos == n - 1 && !(pos & 1)) bo.pairs[2 * it + 1] = -1;
+	};
+#pragma unroll
+	for (int h = 0; h < kOrderHeld; h++)
+		if (tid + h * 1024 < n) place(key[h], tid + h * 1024);
+	for (int j = tid + kOrderHeld * 1024; j < n; j += 1024) {
+		float c[3];
+		group_centre(cubes, s0 + j, B, c);
+		place(order_key(c, lo, to_cell), j);
 	}
 }
 
-// the plain launch walking order[] (bounds_order = 1): bounds_kernel<1, true> with the slot -> group table.  gate: 0 = leave at once when the
-// pre-pass built an order (the launch after bounds_pair_kernel for batches it left alone), 1 = walk order[] when there is one
+// the plain launch walking order[] when the pre-pass built one (bounds_order = 1): bounds_kernel<1, true> with the slot -> group table.
+// gate is 1 in the one launch there is; 0 (leave at once when there is an order) served a second launch after bounds_pair_kernel, which
+// evaluates the batches the pre-pass leaves alone itself now.  The argument stays: without it the compiler spills 38 SGPRs here, not 24.
 template <bool TRUNC>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_ordered_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
@@ -1299,6 +1337,8 @@ __device__ __forceinline__ bool pair_member(const CubeRec* __restrict__ cubes, c
 }
 // the pair launch (bounds_order = 2): grid = max_items * chunks, an item = the two groups pairs[] names over one chunk, mapped to the XCDs as bounds_work maps (group, chunk).  Two sibling sets of one rotation are evaluated together
 // (lean_points_pair); anything else -- a generic group, a partial last group, a foreign rotation, a single -- group by group on the plain path.
+// A batch the pre-pass left alone (ctl[1] = 0) is evaluated here too, two groups per item in arrival order on the plain path: the grid of
+// bounds_order_items(groups, max_runs) >= (groups + 1) / 2 items covers it, and no second launch is needed.
 template <bool TRUNC>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
@@ -1316,9 +1356,17 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
 		const int swz = xcd_remap(work, total);
 		chunk = swz / max_items; item = swz - chunk * max_items;
 	}
-	if (item >= ctl[0]) return;                          // ctl[0] = 0: the pre-pass left the batch alone, the gated plain launch that follows evaluates it
-	int ga = pairs[2 * item], gb = pairs[2 * item + 1];
-	if (gb >= 0) {
+	const bool listed = ctl[1] != 0;
+	int ga, gb;
+	if (listed) {
+		if (item >= ctl[0]) return;
+		ga = pairs[2 * item]; gb = pairs[2 * item + 1];
+	} else {                                             // the pre-pass left the batch alone: groups 2 item and 2 item + 1 as they came, each on the plain path
+		ga = 2 * item;
+		if (ga >= groups) return;
+		gb = ga + 1 < groups ? ga + 1 : -1;
+	}
+	if (listed && gb >= 0) {
 		PairMember A, Bm;
 		int ra, rb;
 		const bool sa = pair_member(cubes, parents, ga, B, A, ra), sb = pair_member(cubes, parents, gb, B, Bm, rb);
@@ -1763,9 +1811,6 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 			const int max_items = (int)bounds_order_items(groups, bo->max_runs);
 			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_pair_kernel<true> : bounds_pair_kernel<false>), dim3(max_items * chunks), block, 0, stream, src, N, dt, rots, cubes, parents,
 			                   B, groups, max_items, chunks, chunk_pts, scratch, ub, lb, bo->pairs, bo->ctl);
-			// more runs than the cap (unrelated cubes): the pair launch left at once and this one is the plain launch; otherwise it leaves at once
-			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_ordered_kernel<true> : bounds_ordered_kernel<false>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups,
-			                   chunks, chunk_pts, scratch, ub, lb, bo->order, bo->ctl, 0);
 		}
 	} else
 	if (dt.trunc > 0.f) {                                                // the truncated objective (DtDesc::trunc): the same four choices
@@ -3224,7 +3269,26 @@ hipError_t launch_transform(float4* src, int N, const Pose& pose, hipStream_t st
 
 // min over n floats and the first index that attains it (what a search does with the upper bounds of a batch: the incumbent
 // is the smallest ub, first child on ties -- bnb_queue_kernel's digest; exposed so that a caller driving goicp_eval_bounds_device
-// itself, like bench.py's step, reduces with the library's own code).  One workgroup: 65 536 values are 64 per thread.
+// itself, like bench.py's step, reduces with the library's own code).  One workgroup: 65 536 values are 64 per thread, two sweeps of eight
+// quads, and a thread issues all the loads of a sweep before it compares any of them (one wait for the memory per sweep, not one per quad).
+// the whole sweeps of Q quads per thread that fit between base and n; a thread's indices rise from quad to quad and sweep to sweep, so `<` keeps the first of equal values
+template <int Q>
+__device__ __forceinline__ void min_sweeps(const float* __restrict__ v, int n, int& base, float& best, int& bi)
+{
+	for (; n - base >= Q * 4096; base += Q * 4096) {
+		float4 x[Q];
+#pragma unroll
+		for (int k = 0; k < Q; k++) x[k] = *reinterpret_cast<const float4*>(v + base + k * 4096 + (int)threadIdx.x * 4);
+#pragma unroll
+		for (int k = 0; k < Q; k++) {
+			const int i = base + k * 4096 + (int)threadIdx.x * 4;
+			if (x[k].x < best) { best = x[k].x; bi = i; }
+			if (x[k].y < best) { best = x[k].y; bi = i + 1; }
+			if (x[k].z < best) { best = x[k].z; bi = i + 2; }
+			if (x[k].w < best) { best = x[k].w; bi = i + 3; }
+		}
+	}
+}
 __global__ __launch_bounds__(1024) void reduce_min_kernel(const float* __restrict__ v, int n, float* __restrict__ out_min, int* __restrict__ out_idx)
 {
 	__shared__ float sv[16];
@@ -3232,7 +3296,11 @@ __global__ __launch_bounds__(1024) void reduce_min_kernel(const float* __restric
 	// a thread starts at (+inf, its first index): an all-+inf input then yields index 0, not the sentinel of a thread without values
 	float best = __builtin_inff();
 	int bi = (int)threadIdx.x * 4 < n ? (int)threadIdx.x * 4 : 0x7fffffff;
-	for (int i = threadIdx.x * 4; i < n; i += 4096) {
+	int base = 0;
+	min_sweeps<8>(v, n, base, best, bi);
+	min_sweeps<2>(v, n, base, best, bi);
+	// fewer than 8 192 values are left: at most two quads of a thread, and the ragged end value by value
+	for (int i = base + (int)threadIdx.x * 4; i < n; i += 4096) {
 		if (i + 3 < n) {
 			const float4 x = *reinterpret_cast<const float4*>(v + i);
 			if (x.x < best) { best = x.x; bi = i; }

@@ -22,6 +22,12 @@ over 256 points, 20 over 1 024, a PAIR over 64 and over 256 -- in the order the 
 distance in voxels between the centres of consecutive expansions.
 
   python3 tools/dt_sector_model.py --lines [--cell 4] [--every 16] [--json out.json]
+
+--lines --keys: the same windows for other keys of the order (KEY_VARIANTS below: a cell floor of 2 voxels, 10 bits per axis over quarter-voxel
+cells, the expansion's depth between a coarse and a fine Morton cell, the depth first), and the share of the order's pairs (2 i, 2 i + 1)
+whose members have the same depth.
+
+  python3 tools/dt_sector_model.py --lines --keys [--json profiles/r07_order_keys_model.json]
 """
 import argparse
 import json
@@ -100,6 +106,39 @@ def run_order(centres_vox, cell):
     return np.argsort(key, kind="stable")
 
 
+def morton(q, bits):
+    key = np.zeros(len(q), np.int64)
+    for b in range(bits):
+        for k in range(3):
+            key |= ((q[:, k] >> b) & 1) << (3 * b + k)
+    return key
+
+
+def fine_key(centres_vox, cell):
+    """bounds_order_kernel's key"""
+    lo = centres_vox.min(0)
+    c = max(cell, 1.0, float((centres_vox.max(0) - lo).max()) / 31.5)
+    return morton(np.clip(((centres_vox - lo) / c).astype(np.int64), 0, 31), 5)
+
+
+def key_variant(name, centres_vox, depth, cell):
+    """the order of one rotation run under another key (ties in arrival order)"""
+    lo = centres_vox.min(0)
+    if name == "cell_floor_2":
+        return np.argsort(fine_key(centres_vox, 2.0), kind="stable")
+    if name == "bits10_quarter_voxel_cells":
+        return np.argsort(morton(np.clip(((centres_vox - lo) / 0.25).astype(np.int64), 0, 1023), 10), kind="stable")
+    if name == "coarse16_depth_fine":
+        coarse = morton(np.clip(((centres_vox - lo) / 16.0).astype(np.int64), 0, 31), 5)
+        return np.lexsort((np.arange(len(depth)), fine_key(centres_vox, cell), depth, coarse))
+    if name == "depth_fine":
+        return np.lexsort((np.arange(len(depth)), fine_key(centres_vox, cell), depth))
+    raise ValueError(name)
+
+
+KEY_VARIANTS = ("cell_floor_2", "bits10_quarter_voxel_cells", "coarse16_depth_fine", "depth_fine")
+
+
 def lines_mode(a, rots, recs, src, mn, scale, V):
     N = len(src)
     chunk_pts = -(-(-(-N // 8)) // 256) * 256                 # bounds_shape: eight chunks, a multiple of 256 points
@@ -128,6 +167,11 @@ def lines_mode(a, rots, recs, src, mn, scale, V):
 
     centres = np.stack([(recs[f][0::8] + recs[f][7::8]) * np.float32(0.5) for f in ("tx", "ty", "tz")], 1).astype(np.float64) * float(scale)
     orders = {"as_given": [np.arange(per_run) for _ in rots], "ordered": [run_order(centres[r * per_run:(r + 1) * per_run], a.cell) for r in range(len(rots))]}
+    width = (recs["tx"][1::8] - recs["tx"][0::8]).astype(np.float64)
+    depth = np.unique(-width, return_inverse=True)[1]            # 0 = the widest parent cube of the batch
+    if a.keys:
+        for name in KEY_VARIANTS:
+            orders[name] = [key_variant(name, centres[r * per_run:(r + 1) * per_run], depth[r * per_run:(r + 1) * per_run], a.cell) for r in range(len(rots))]
     out = {"batch": "bench.make_batch(%d expansions, %d rotations, seed 1234); windows every %d expansions" % (n_exp, len(rots), a.every), "N": N, "V": V,
            "chunk_pts": chunk_pts, "cell_voxels": a.cell}
     # per wavefront / workgroup iteration / item, every k-th expansion, chunk 0 .. 7 in turn
@@ -152,6 +196,8 @@ def lines_mode(a, rots, recs, src, mn, scale, V):
             c = centres[r * per_run:(r + 1) * per_run][o]
             dist.append(np.linalg.norm(np.diff(c, axis=0), axis=1))
         res["median_voxels_between_consecutive"] = round(float(np.median(np.concatenate(dist))), 1)
+        same = [depth[r * per_run:(r + 1) * per_run][o][0:per_run - 1:2] == depth[r * per_run:(r + 1) * per_run][o][1:per_run:2] for r, o in enumerate(ords)]
+        res["pairs_of_equal_depth"] = round(float(np.mean(np.concatenate(same))), 3)
         for label, k, npts in (("5_expansions_256_points", 5, 256), ("20_expansions_1024_points", 20, 1024), ("pair_64_points", 2, 64), ("pair_256_points", 2, 256)):
             un = sm = 0
             for r, o in enumerate(ords):
@@ -175,6 +221,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--lines", action="store_true", help="model 128-B lines and their sharing between consecutive expansions (see above)")
     ap.add_argument("--cell", type=float, default=4.0, help="--lines: smallest Morton cell of the order, voxels")
+    ap.add_argument("--keys", action="store_true", help="--lines: also model the other keys of the order (KEY_VARIANTS)")
     a = ap.parse_args()
 
     from conftest import load_pkg, cloud
