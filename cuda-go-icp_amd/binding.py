@@ -96,6 +96,10 @@ class CSourceFilter(C.Structure):
     _fields_ = [("voxel", C.c_float), ("radius", C.c_float), ("min_neighbors", C.c_int32)]
 
 
+class CSourcePipeline(C.Structure):
+    _fields_ = [("voxel", C.c_float), ("stat_neighbors", C.c_int32), ("stat_std_ratio", C.c_float), ("radius", C.c_float), ("min_neighbors", C.c_int32)]
+
+
 class CPoseInfoOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
 
@@ -198,6 +202,12 @@ SYMBOLS = {
                                               C.POINTER(C.c_size_t)]),
     "goicp_source_filter_default": (None, [C.POINTER(CSourceFilter)]),
     "goicp_set_source_filtered": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourceFilter), C.POINTER(C.c_size_t)]),
+    "goicp_statistical_outlier_removal_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.c_float, _fp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_double),
+                                                        C.POINTER(C.c_size_t)]),
+    "goicp_statistical_outlier_removal": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.c_float, _fp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_size_t)]),
+    "goicp_source_pipeline_default": (None, [C.POINTER(CSourcePipeline)]),
+    "goicp_set_source_pipeline": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(C.c_size_t)]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

@@ -3,6 +3,7 @@
 //                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
 //                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
 //                                [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]
+//                                [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -45,6 +46,12 @@
 //               --target-outlier-radius R --target-outlier-min-neighbors K filter the target the same way, on the host, after
 //               --target-voxel and before the engine is created.  R must be finite, > 0 and R * R a normal float, K an integer >= 1 --
 //               refused before any device is touched
+//   --stat-neighbors K --stat-std-ratio A   (both or neither) statistical outlier removal, after --voxel and before --outlier-radius: a
+//               point of the source -- and of every cloud of --source-list -- whose mean distance to its K nearest neighbours lies more than
+//               A sample deviations above the cloud's mean of it is dropped.  The config's own source is filtered on the host
+//               (goicp_statistical_outlier_removal_host), every listed cloud on the device as part of its swap (goicp_set_source_pipeline:
+//               the same bits); each prints "kept m of n".  --target-stat-neighbors K --target-stat-std-ratio A filter the target the same
+//               way, on the host.  K must be an integer in 1..64, A a finite number >= 0 -- refused before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -82,7 +89,7 @@ static std::string numbered(const std::string& p, int k)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
@@ -103,6 +110,9 @@ int main(int argc, char** argv)
 	const char *orad_arg[2] = {nullptr, nullptr}, *omin_arg[2] = {nullptr, nullptr};   // [0] the source's, [1] the target's
 	float outlier_radius[2] = {0.f, 0.f};
 	int outlier_min[2] = {0, 0};
+	const char *sk_arg[2] = {nullptr, nullptr}, *sa_arg[2] = {nullptr, nullptr};       // statistical filter: [0] the source's, [1] the target's
+	int stat_k[2] = {0, 0};
+	float stat_ratio[2] = {0.f, 0.f};
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -125,6 +135,10 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--outlier-min-neighbors")) omin_arg[0] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-outlier-radius")) orad_arg[1] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-outlier-min-neighbors")) omin_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--stat-neighbors")) sk_arg[0] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--stat-std-ratio")) sa_arg[0] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--target-stat-neighbors")) sk_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--target-stat-std-ratio")) sa_arg[1] = i + 1 < argc ? argv[++i] : "";
 	}
 	for (int k = 0; k < 2; k++) {
 		// a bad voxel is refused before any device is touched
@@ -160,6 +174,28 @@ int main(int argc, char** argv)
 		}
 		outlier_radius[k] = r;
 		outlier_min[k] = (int)kk;
+	}
+	for (int k = 0; k < 2; k++) {
+		// a bad statistical filter is refused before any device is touched
+		const char* pre = k ? "--target-stat" : "--stat";
+		if (!sk_arg[k] && !sa_arg[k]) continue;
+		if (!sk_arg[k] || !sa_arg[k]) {
+			std::fprintf(stderr, "error: %s-neighbors and %s-std-ratio go together\n", pre, pre);
+			return 2;
+		}
+		char* end = nullptr;
+		const long kk = std::strtol(sk_arg[k], &end, 10);
+		if (end == sk_arg[k] || *end != '\0' || kk < 1 || kk > GOICP_STAT_MAX_NEIGHBORS) {
+			std::fprintf(stderr, "error: %s-neighbors needs an integer in 1..%d, got '%s'\n", pre, GOICP_STAT_MAX_NEIGHBORS, sk_arg[k]);
+			return 2;
+		}
+		const float a = std::strtof(sa_arg[k], &end);
+		if (end == sa_arg[k] || *end != '\0' || !(a >= 0.f) || !(a <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: %s-std-ratio needs a finite number >= 0, got '%s'\n", pre, sa_arg[k]);
+			return 2;
+		}
+		stat_k[k] = (int)kk;
+		stat_ratio[k] = a;
 	}
 	if (list_arg) {
 		// refused before any device is touched
@@ -275,7 +311,18 @@ int main(int argc, char** argv)
 			cloud.swap(reduced);
 		}
 		for (int k = 0; k < 2; k++) {
-			// after the voxel grid; the host function again
+			// after the voxel grid, before the radius filter; the host function again
+			std::vector<P3>& cloud = k ? target : source;
+			if (stat_k[k] < 1 || cloud.empty()) continue;
+			std::vector<P3> kept(cloud.size());
+			size_t m = 0;
+			check(goicp_statistical_outlier_removal_host(&cloud[0].x, cloud.size(), stat_k[k], stat_ratio[k], &kept[0].x, nullptr, nullptr, nullptr, &m));
+			kept.resize(m);
+			std::printf("%s stat neighbors %d std ratio %g: kept %zu of %zu points\n", k ? "target" : "source", stat_k[k], stat_ratio[k], m, cloud.size());
+			cloud.swap(kept);
+		}
+		for (int k = 0; k < 2; k++) {
+			// after the voxel grid and the statistical filter; the host function again
 			std::vector<P3>& cloud = k ? target : source;
 			if (!(outlier_radius[k] > 0.f) || cloud.empty()) continue;
 			std::vector<P3> kept(cloud.size());
@@ -395,7 +442,14 @@ int main(int argc, char** argv)
 			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
 			const auto t0 = std::chrono::steady_clock::now();
 			size_t kept = next.size();
-			if (outlier_radius[0] > 0.f) {
+			if (stat_k[0] > 0) {
+				goicp_source_pipeline sp;
+				goicp_source_pipeline_default(&sp);
+				sp.voxel = voxel; sp.stat_neighbors = stat_k[0]; sp.stat_std_ratio = stat_ratio[0];
+				sp.radius = outlier_radius[0]; sp.min_neighbors = outlier_min[0];
+				kept = engine.set_source(next, sp);
+				std::printf("source %zu stat neighbors %d std ratio %g: kept %zu of %zu points\n", k + 1, sp.stat_neighbors, sp.stat_std_ratio, kept, next.size());
+			} else if (outlier_radius[0] > 0.f) {
 				goicp_source_filter f;
 				goicp_source_filter_default(&f);
 				f.voxel = voxel; f.radius = outlier_radius[0]; f.min_neighbors = outlier_min[0];

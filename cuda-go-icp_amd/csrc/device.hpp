@@ -450,6 +450,20 @@ hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& 
 // ev_begin / ev_end (may be null) are recorded around the kernels and the read-back of m.  Returns after the stream has drained
 hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, float* d_out, int32_t* d_index,
                                          int32_t* d_count, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ---- statistical outlier removal on the device (kdbuild.hip; goicp_statistical_outlier_removal_host is its host twin) ----
+constexpr int kStatMaxLevels = 48;
+// what a run did: the grid levels that ran, the points each resolved, and the points left to the top level (all points as candidates)
+struct StatReport {
+	int levels_run = 0, resolved[kStatMaxLevels] = {}, top = 0;
+};
+// frames[L] / r2[L], L < levels <= kStatMaxLevels: the frame of the grid of pitch r_L * 1.03125f and r_L * r_L in float, r_L = r0 * 2^L
+// (stat_levels and radius_frame_of_box, kdtree.cpp); levels == 0: the top level alone.  k = neighbors in 1..64, k <= n - 1.  d_out: room for
+// 3 n floats, the first 3 m are written; d_index (may be null): n ints, the first m are written; d_mean (may be null): n floats, u_i of every
+// point; *threshold (may be null): the reported threshold.  *m >= 1.  ev_begin / ev_end (may be null) are recorded around the kernels and
+// the read-backs (one int per level, m and the threshold at the end).  Returns after the stream has drained
+hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, float std_ratio,
+                                       float* d_out, int32_t* d_index, float* d_mean, double* threshold, int* m, StatReport* report, hipStream_t stream,
+                                       hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // per-axis minimum and maximum of n points on the device (one rocPRIM reduction, 24 bytes come back): the frame of a cloud that a device
 // stage produced and the host has not seen.  Returns after the stream has drained
 hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream);

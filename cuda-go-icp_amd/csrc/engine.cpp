@@ -658,6 +658,165 @@ void Engine::set_source_filtered(const float* xyz, size_t n, float voxel, float 
 		             n_in, N_, now_ms() - t0, voxel > 0.f ? voxel_ms_ : 0.0, outlier_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
 }
 
+namespace {
+
+// the level plan of a cloud with these bounds: the frames and squared radii launch_stat_outlier_removal searches by
+struct StatPlan {
+	std::vector<VoxelFrame> frames;
+	std::vector<float> r2;
+	// sample: stat_sample_size(n) points, every (n / that)-th of the cloud
+	StatPlan(const float mn[3], const float mx[3], size_t n, int32_t k, const std::vector<float>& sample)
+	{
+		float r = 0.f;
+		int levels = 0;
+		stat_levels(mn, mx, n, k, sample.data(), sample.size() / 3, &r, &levels);
+		levels = std::min(levels, kStatMaxLevels);
+		frames.resize((size_t)levels);
+		r2.resize((size_t)levels);
+		for (int L = 0; L < levels; L++, r *= 2.f) {
+			radius_frame_of_box(mn, mx, n, r, 1, &frames[(size_t)L]);
+			r2[(size_t)L] = r * r;
+		}
+	}
+};
+
+std::vector<float> stat_sample_host(const float* xyz, size_t n)
+{
+	const size_t ns = stat_sample_size(n), stride = n / ns;
+	std::vector<float> s(3 * ns);
+	for (size_t i = 0; i < ns; i++) std::memcpy(&s[3 * i], xyz + 3 * i * stride, 3 * sizeof(float));
+	return s;
+}
+
+void stat_report_line(const char* what, size_t n, int m, const StatReport& rep)
+{
+	std::fprintf(stderr, "[goicp] %s: %zu -> %d points, levels %d, resolved", what, n, m, rep.levels_run + (rep.top > 0 ? 1 : 0));
+	for (int L = 0; L < rep.levels_run; L++) std::fprintf(stderr, " %d", rep.resolved[L]);
+	std::fprintf(stderr, ", top %d\n", rep.top);
+}
+
+}  // namespace
+
+void Engine::statistical_outlier_removal(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+                                         float* out_mean_dist, double* threshold, size_t* m_out)
+{
+	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_statistical_outlier_removal: out_xyz and m must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	stat_check_params(n, neighbors, std_ratio);
+	if (registering_.load()) throw std::invalid_argument("goicp_statistical_outlier_removal: not while a registration runs");
+	const StatPlan plan(mn, mx, n, neighbors, stat_sample_host(xyz, n));
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz(3 * n), d_out(3 * n), d_mean(out_mean_dist ? n : 0);
+	Buf<int32_t> d_idx(out_index ? n : 0);
+	int m = 0;
+	double thr = 0.0;
+	StatReport rep;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_stat_outlier_removal(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), neighbors, std_ratio, d_out,
+	                                   out_index ? d_idx.get() : nullptr, out_mean_dist ? d_mean.get() : nullptr, &thr, &m, &rep, stream_));
+	HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_index) HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_mean_dist) HIPCHK(hipMemcpyAsync(out_mean_dist, d_mean, sizeof(float) * n, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (threshold) *threshold = thr;
+	*m_out = (size_t)m;
+	if (p_.verbose) stat_report_line("statistical_outlier_removal", n, m, rep);
+}
+
+void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
+                                 size_t* n_kept)
+{
+	if (stat_neighbors < 0) throw std::invalid_argument("goicp_set_source_pipeline: stat_neighbors must be 0 (no stage) or in 1..64");
+	if (stat_neighbors == 0) {
+		// no statistical stage: the filtered swap, bit for bit
+		set_source_filtered(xyz, n, voxel, radius, min_neighbors, n_kept);
+		return;
+	}
+	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_pipeline: voxel must be 0 (no stage) or a voxel size > 0");
+	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_pipeline: radius must be 0 (no stage) or a radius > 0");
+	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows
+	VoxelFrame fv;
+	float mn[3], mx[3];
+	if (voxel > 0.f) {
+		voxel_frame(xyz, n, voxel, &fv);
+		stat_check_params(65, stat_neighbors, stat_std_ratio);   // the range of k and the ratio; k against the reduced cloud's size below
+	} else {
+		stat_check_cloud(xyz, n, mn, mx);
+		stat_check_params(n, stat_neighbors, stat_std_ratio);
+	}
+	if (radius > 0.f) {
+		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
+	}
+	if (registering_.load()) throw std::invalid_argument("goicp_set_source_pipeline: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	TraceRange tr("goicp:set_source_pipeline");
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
+	Buf<float> d_raw(3 * n), d_red(voxel > 0.f ? 3 * n : 0);
+	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	const float* d_in = d_raw;
+	int n_in = (int)n;
+	float voxel_ms = 0.f, stat_ms = 0.f, outlier_ms = 0.f;
+	if (voxel > 0.f) {
+		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&voxel_ms, ev0_, ev1_));
+		d_in = d_red;
+		stat_check_params((size_t)n_in, stat_neighbors, stat_std_ratio);
+		// the bounds of the reduced cloud, as stat_check_cloud would find them on the host: 24 bytes come back, not the cloud
+		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+	}
+	const int n_voxel = n_in;
+	Buf<float> d_stat(3 * (size_t)n_in);
+	int m = 0;
+	StatReport rep;
+	{
+		// the sample that steers the first radius: from the host's cloud, or 48 KB of the reduced cloud
+		std::vector<float> sample;
+		if (voxel > 0.f) {
+			const size_t ns = stat_sample_size((size_t)n_in), stride = (size_t)n_in / ns;
+			sample.resize(3 * ns);
+			HIPCHK(hipMemcpy2DAsync(sample.data(), 3 * sizeof(float), d_in, 3 * sizeof(float) * stride, 3 * sizeof(float), ns, hipMemcpyDeviceToHost, stream_));
+			HIPCHK(hipStreamSynchronize(stream_));
+		} else {
+			sample = stat_sample_host(xyz, n);
+		}
+		const StatPlan plan(mn, mx, (size_t)n_in, stat_neighbors, sample);
+		HIPCHK(launch_stat_outlier_removal(d_in, n_in, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), stat_neighbors, stat_std_ratio, d_stat,
+		                                   nullptr, nullptr, nullptr, &m, &rep, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&stat_ms, ev0_, ev1_));
+	}
+	const int n_stat = m;
+	Buf<float> d_kept(radius > 0.f ? 3 * (size_t)m : 0);
+	const float* d_final = d_stat;
+	if (radius > 0.f) {
+		VoxelFrame fr;
+		HIPCHK(launch_cloud_minmax(d_stat, m, mn, mx, stream_));
+		radius_frame_of_box(mn, mx, (size_t)m, radius, min_neighbors, &fr);
+		int kept = 0;
+		HIPCHK(launch_radius_outlier_removal(d_stat, m, fr, radius * radius, min_neighbors, d_kept, nullptr, nullptr, &kept, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&outlier_ms, ev0_, ev1_));
+		m = kept;
+		d_final = d_kept;
+	}
+	if (m < 1) throw std::invalid_argument("goicp_set_source_pipeline: the chain keeps no point");
+	std::vector<float> kept(3 * (size_t)m);
+	HIPCHK(hipMemcpyAsync(kept.data(), d_final, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (voxel > 0.f) voxel_ms_ = voxel_ms;
+	if (radius > 0.f) outlier_ms_ = outlier_ms;
+	load_source(kept.data(), (size_t)m, true, d_final);
+	finish_source_swap();
+	if (n_kept) *n_kept = (size_t)m;
+	if (p_.verbose) {
+		stat_report_line("set_source_pipeline statistical stage", (size_t)n_voxel, n_stat, rep);
+		std::fprintf(stderr, "[goicp] set_source_pipeline: %zu -> %d -> %d -> %zu points, %.2f ms (device voxel %.3f ms, device statistical %.3f ms, device outlier %.3f ms, device order %.3f ms)\n",
+		             n, n_voxel, n_stat, N_, now_ms() - t0, voxel_ms, stat_ms, outlier_ms, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
+	}
+}
+
 void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)
 {
 	if (!perm) throw std::invalid_argument("goicp_debug_source_order: perm must be non-null");

@@ -288,6 +288,14 @@ public:
 	// goicp_set_source_filtered: voxel grid (voxel > 0), then radius filter (radius > 0), then the swap; the raw cloud goes up once, the
 	// stages are chained on the device, only the final cloud and the permutation come back.  A filter that keeps nothing is refused
 	void set_source_filtered(const float* xyz, size_t n, float voxel, float radius, int32_t min_neighbors, size_t* n_kept);
+	// goicp_statistical_outlier_removal: the statistical filter on the device (kdbuild.hip launch_stat_outlier_removal); as voxel_downsample,
+	// the engine lends its device and stream and nothing else
+	void statistical_outlier_removal(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+	                                 float* out_mean_dist, double* threshold, size_t* m);
+	// goicp_set_source_pipeline: voxel grid (voxel > 0), statistical filter (stat_neighbors > 0), radius filter (radius > 0), then the swap,
+	// chained on the device behind one upload.  With the statistical stage off it is set_source_filtered
+	void set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
+	                         size_t* n_kept);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -552,6 +560,17 @@ void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbor
 void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
                                  int32_t* out_count, size_t* m);
+// statistical outlier removal (kdtree.cpp).  stat_check_params refuses neighbors outside 1..64 or above n - 1 and a std_ratio that
+// is negative, NaN or infinite; stat_check_cloud what voxel_frame refuses of a cloud, and returns its per-axis bounds.  stat_levels is the
+// plan both paths search by: r0 (0 = no grid level, the top level alone) and the number of grid levels at radii r0 * 2^L, fixed in advance
+// from the extent, n, k and a sample of the cloud (ns = stat_sample_size(n) points, every (n / ns)-th; may be null), which only steers the
+// amount of work.  statistical_outlier_removal_host is goicp_statistical_outlier_removal_host
+void stat_check_params(size_t n, int32_t neighbors, float std_ratio);
+void stat_check_cloud(const float* xyz, size_t n, float mn[3], float mx[3]);
+size_t stat_sample_size(size_t n);
+void stat_levels(const float mn[3], const float mx[3], size_t n, int32_t neighbors, const float* sample, size_t ns, float* r0, int* levels);
+void statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+                                      float* out_mean_dist, double* threshold, size_t* m);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

@@ -240,6 +240,37 @@ int goicp_set_source_filtered(goicp_handle h, const float* xyz, size_t n, const 
 	return guarded([&] { h->e->set_source_filtered(xyz, n, f->voxel, f->radius, f->min_neighbors, n_kept); });
 }
 
+int goicp_statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+                                           float* out_mean_dist, double* threshold, size_t* m)
+{
+	REQUIRE(xyz && out_xyz && m && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::statistical_outlier_removal_host(xyz, n, neighbors, std_ratio, out_xyz, out_index, out_mean_dist, threshold, m); });
+}
+
+int goicp_statistical_outlier_removal(goicp_handle h, const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+                                      float* out_mean_dist, double* threshold, size_t* m)
+{
+	REQUIRE(h && xyz && out_xyz && m && n > 0);
+	return guarded([&] { h->e->statistical_outlier_removal(xyz, n, neighbors, std_ratio, out_xyz, out_index, out_mean_dist, threshold, m); });
+}
+
+void goicp_source_pipeline_default(goicp_source_pipeline* out)
+{
+	if (!out) return;
+	out->voxel = 0.f;
+	out->stat_neighbors = 0;
+	out->stat_std_ratio = 0.f;
+	out->radius = 0.f;
+	out->min_neighbors = 0;
+}
+
+int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, size_t* n_kept)
+{
+	REQUIRE(h && xyz && p && n > 0);
+	return guarded([&] { h->e->set_source_pipeline(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, n_kept); });
+}
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

@@ -644,6 +644,344 @@ hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelF
 	return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Statistical outlier removal on the device (host twin: statistical_outlier_removal_host, kdtree.cpp).  The k smallest d2 of every
+// point are found on grids of doubling radius r_L = r0 2^L (pitch 1.03125 r_L, the radius filter's grid and its proof): a point whose k-th
+// smallest d2 over its 27 cells is <= r_L * r_L has seen every point that close, so those k are its k smallest of the whole
+// cloud; the others go to a compacted list for the next level, and what the last level leaves scans all points.  Level 0 serves every point
+// (stat_knn_block_kernel, the count kernel's shape), the later levels few scattered ones (stat_knn_wave_kernel, a wave per point).  The
+// number of levels is fixed by the host; the length of the list comes back between levels (4 bytes) so that an empty one ends the chain.
+// The statistics stay on the device: the maximum over float bits, exact 64-bit integer sums, one thread that finishes in fp64.
+// ------------------------------------------------------------------------------------------------
+constexpr int kStatBlock = 256;
+
+__device__ __forceinline__ float stat_d2(float px, float py, float pz, const RorPt& Q)
+{
+	const float dx = px - Q.x, dy = py - Q.y, dz = pz - Q.z;
+	return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// the correctly rounded float square root: sqrtf, which the build keeps IEEE (the compiler's default for HIP; so_gather_kernel's |p| relies
+// on the same).  __fsqrt_rn is the hardware's approximate instruction in this toolchain and differs from the host in the last bit
+__device__ __forceinline__ float stat_sqrt(float v) { return sqrtf(v); }
+
+// The count kernel's shape: a workgroup owns kStatBlock consecutive SORTED points, finds the 9 candidate intervals of its span once, makes
+// them disjoint (no candidate is offered twice) and passes them through LDS in tiles; a wave skips a tile that meets none of its lanes'
+// runs, and a lane takes only tiles that meet its own.  Each lane keeps its k smallest d2 ascending in LDS at stride kStatBlock (lane t owns
+// column t: no two lanes of a wave share a bank column), KT >= k rows of 1 KB.  A candidate is inserted only when strictly below the lane's
+// k-th value, so ties and a cell of identical points cost nothing.  A lane whose k-th value is <= r2 writes u; any other appends its id to
+// the open list.  No workgroup waits on another
+template <int KT>
+__global__ void __launch_bounds__(kStatBlock) stat_knn_block_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, int k,
+                                                                    float r2, float* __restrict__ u, int* __restrict__ open_list, int* __restrict__ open_count)
+{
+	__shared__ RorPt tile[kStatBlock];
+	__shared__ float best[KT * kStatBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kStatBlock, last = min(first + kStatBlock, n) - 1;
+	const int s = first + tid;
+	const bool valid = s < n;
+	if (tid < 9) {
+		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
+		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
+		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
+	}
+	for (int j = 0; j < k; j++) best[j * kStatBlock + tid] = INFINITY;
+	__syncthreads();
+	if (tid == 0)
+		for (int o = 1; o < 9; o++) {
+			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
+			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
+		}
+	__syncthreads();
+	RorPt P{0.f, 0.f, 0.f, -1};
+	long long K = 0;
+	if (valid) { P = pts[s]; K = (long long)keys[s]; }
+	float kth = INFINITY;
+	for (int o = 0; o < 9; o++) {
+		const int lo = iv_lo[o], hi = iv_hi[o];
+		for (int t0 = lo; t0 < hi; t0 += kStatBlock) {
+			__syncthreads();                                     // the previous tile has been read by everybody
+			const int len = min(kStatBlock, hi - t0);
+			if (tid < len) tile[tid] = pts[t0 + tid];
+			__syncthreads();
+			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
+			bool need = false;
+			if (valid)
+				for (int q = 0; q < 9; q++) {
+					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
+					need = need || (c - 1 <= tb && c + 1 >= ta);
+				}
+			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
+			if (!need) continue;
+			for (int j = 0; j < len; j++) {
+				const RorPt Q = tile[j];
+				const float d2 = stat_d2(P.x, P.y, P.z, Q);
+				if (d2 < kth && Q.id != P.id) {
+					int p = k - 1;
+					while (p > 0) {
+						const float b = best[(p - 1) * kStatBlock + tid];
+						if (!(b > d2)) break;
+						best[p * kStatBlock + tid] = b;
+						p--;
+					}
+					best[p * kStatBlock + tid] = d2;
+					kth = best[(k - 1) * kStatBlock + tid];
+				}
+			}
+		}
+	}
+	if (!valid) return;
+	if (kth <= r2) {
+		double sum = 0.0;
+		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(best[j * kStatBlock + tid]));
+		u[P.id] = (float)__ddiv_rn(sum, (double)k);
+	} else {
+		open_list[atomicAdd(open_count, 1)] = P.id;
+	}
+}
+
+// A wave per listed point.  Lanes 0..8 find the point's own 9 runs [K + D - 1, K + D + 1] (disjoint key ranges: no candidate is offered
+// twice); all = 1 is the top level, the one run [0, n).  The lanes read 64 candidates at a time; lane j holds the j-th smallest d2 seen so
+// far in a register, and a candidate strictly below the k-th value is inserted by one shuffle: a lane keeps its value if it is <= v, takes
+// v if its lower neighbour's value is <= v, and its lower neighbour's value otherwise.  The loops run over the runs' lengths, which the
+// host's number of levels bounds; no wave waits on another
+__global__ void __launch_bounds__(256) stat_knn_wave_kernel(const float* __restrict__ xyz, const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys,
+                                                            int n, const int* __restrict__ list, int count, int k, float r2, int all, float mnx, float mny,
+                                                            float mnz, float pitch, float* __restrict__ u, int* __restrict__ open_list,
+                                                            int* __restrict__ open_count)
+{
+	const int w = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+	if (w >= count) return;                                      // wave-uniform
+	const int id = list[w];
+	const float px = xyz[3 * (size_t)id], py = xyz[3 * (size_t)id + 1], pz = xyz[3 * (size_t)id + 2];
+	int my_lo = 0, my_hi = 0;
+	if (all) {
+		if (lane == 0) my_hi = n;
+	} else if (lane < 9) {
+		const long long K = (long long)(vx_cell(px - mnx, pitch) | (vx_cell(py - mny, pitch) << 21) | (vx_cell(pz - mnz, pitch) << 42));
+		const long long c = K + (long long)(lane % 3 - 1) * (1ll << 21) + (long long)(lane / 3 - 1) * (1ll << 42);
+		my_lo = ror_bound(keys, n, c - 1, false);
+		my_hi = max(my_lo, ror_bound(keys, n, c + 1, true));
+	}
+	float mine = INFINITY, kth = INFINITY;
+	const int runs = all ? 1 : 9;
+	for (int o = 0; o < runs; o++) {
+		const int lo = __shfl(my_lo, o, 64), hi = __shfl(my_hi, o, 64);
+		for (int base = lo; base < hi; base += 64) {
+			const int j = base + lane;
+			float d2 = INFINITY;
+			if (j < hi) {
+				const RorPt Q = pts[j];
+				if (Q.id != id) d2 = stat_d2(px, py, pz, Q);
+			}
+			unsigned long long hot = __ballot(d2 < kth);
+			while (hot) {
+				const int src = __ffsll((long long)hot) - 1;
+				hot &= hot - 1;
+				const float v = __shfl(d2, src, 64);
+				if (v < kth) {                                       // wave-uniform
+					const float below = __shfl_up(mine, 1, 64);
+					mine = (mine <= v) ? mine : ((lane == 0 || below <= v) ? v : below);
+					kth = __shfl(mine, k - 1, 64);
+				}
+			}
+		}
+	}
+	if (all || kth <= r2) {
+		double sum = 0.0;
+		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(__shfl(mine, j, 64)));
+		if (lane == 0) u[id] = (float)__ddiv_rn(sum, (double)k);
+	} else if (lane == 0) {
+		open_list[atomicAdd(open_count, 1)] = id;
+	}
+}
+
+// what the finishing thread leaves for the flags and the host
+struct StatFinish { double Tq, threshold; int e, all; };
+
+__device__ __forceinline__ unsigned long long stat_xor64(unsigned long long v, int off)
+{
+	const int lo = __shfl_xor((int)(unsigned)(v & 0xffffffffull), off, 64);
+	const int hi = __shfl_xor((int)(unsigned)(v >> 32), off, 64);
+	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+}
+
+// U over the bits of u: non-negative floats order as unsigned integers
+__global__ void __launch_bounds__(256) stat_max_kernel(const float* __restrict__ u, int n, unsigned* __restrict__ umax)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	unsigned b = i < n ? __float_as_uint(u[i]) : 0u;
+	for (int off = 32; off; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
+	if ((threadIdx.x & 63) == 0 && b) atomicMax(umax, b);
+}
+
+__device__ __forceinline__ unsigned long long stat_q(float u, int e) { return (unsigned long long)(long long)floor(ldexp((double)u, 31 - e)); }
+
+// sums[0..2] = S1, A, B: exact integers, so the order in which the waves arrive cannot matter
+__global__ void __launch_bounds__(256) stat_sums_kernel(const float* __restrict__ u, int n, const unsigned* __restrict__ umax, unsigned long long* __restrict__ sums)
+{
+	const unsigned ub = *umax;
+	if (!ub) return;
+	int e = 0;
+	frexpf(__uint_as_float(ub), &e);
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long q = i < n ? stat_q(u[i], e) : 0ull;
+	unsigned long long s1 = q, a = (q * q) >> 32, b = (q * q) & 0xffffffffull;
+	for (int off = 32; off; off >>= 1) { s1 += stat_xor64(s1, off); a += stat_xor64(a, off); b += stat_xor64(b, off); }
+	if ((threadIdx.x & 63) == 0) { atomicAdd(sums, s1); atomicAdd(sums + 1, a); atomicAdd(sums + 2, b); }
+}
+
+// one thread: the finish of the header in fp64, each operation rounded once
+__global__ void stat_finish_kernel(const unsigned* __restrict__ umax, const unsigned long long* __restrict__ sums, int n, float alpha, StatFinish* __restrict__ fin)
+{
+	if (blockIdx.x || threadIdx.x) return;
+	StatFinish r{0.0, 0.0, 0, 1};
+	const unsigned ub = *umax;
+	if (ub) {
+		frexpf(__uint_as_float(ub), &r.e);
+		const double S1 = (double)(long long)sums[0], A = (double)(long long)sums[1], B = (double)(long long)sums[2];
+		const double nd = (double)n;
+		const double mean = __ddiv_rn(S1, nd);
+		const double S2 = __dadd_rn(ldexp(A, 32), B);
+		double var = __ddiv_rn(__dsub_rn(S2, __dmul_rn(S1, mean)), __dsub_rn(nd, 1.0));
+		if (!(var > 0.0)) var = 0.0;
+		r.Tq = __dadd_rn(mean, __dmul_rn((double)alpha, __dsqrt_rn(var)));
+		r.threshold = ldexp(r.Tq, r.e - 31);
+		r.all = 0;
+	}
+	*fin = r;
+}
+
+__global__ void stat_flag_kernel(const float* __restrict__ u, int n, const StatFinish* __restrict__ fin, int* __restrict__ flag)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	flag[i] = (fin->all || (double)(long long)stat_q(u[i], fin->e) <= fin->Tq) ? 1 : 0;
+}
+
+hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, float std_ratio,
+                                       float* d_out, int32_t* d_index, float* d_mean, double* threshold, int* m_out, StatReport* report, hipStream_t stream,
+                                       hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n < 2 || !m_out || k < 1 || k > 64 || k > n - 1 || levels < 0 || levels > kStatMaxLevels || (levels > 0 && (!frames || !r2))) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define ST_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	unsigned long long *keys = nullptr, *keys2 = nullptr, *sums = nullptr;
+	int *ids = nullptr, *ids2 = nullptr, *flag = nullptr, *scan = nullptr, *listA = nullptr, *listB = nullptr, *counts = nullptr;
+	float* mean = nullptr;
+	RorPt* pts = nullptr;
+	StatFinish* fin = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		void* const* p[14];
+		~Cleanup() { for (void* const* q : p) hipFree(*q); }
+	} cleanup{{(void**)&keys, (void**)&keys2, (void**)&sums, (void**)&ids, (void**)&ids2, (void**)&flag, (void**)&scan, (void**)&listA, (void**)&listB,
+	           (void**)&counts, (void**)&mean, (void**)&pts, (void**)&fin, &tmp}};
+	const size_t N = (size_t)n;
+	ST_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
+	ST_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
+	ST_TRY(hipMalloc(&sums, sizeof(unsigned long long) * 4));        // S1, A, B and the bits of U
+	ST_TRY(hipMalloc(&ids, sizeof(int) * N));
+	ST_TRY(hipMalloc(&ids2, sizeof(int) * N));
+	ST_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
+	ST_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
+	ST_TRY(hipMalloc(&listA, sizeof(int) * N));
+	ST_TRY(hipMalloc(&listB, sizeof(int) * N));
+	ST_TRY(hipMalloc(&counts, sizeof(int) * (kStatMaxLevels + 1)));
+	ST_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
+	ST_TRY(hipMalloc(&fin, sizeof(StatFinish)));
+	if (!d_mean) ST_TRY(hipMalloc(&mean, sizeof(float) * N));
+	float* u = d_mean ? d_mean : mean;
+	unsigned* umax = (unsigned*)(sums + 3);
+	size_t sort_bytes = 0, scan_bytes = 0;
+	for (int L = 0; L < levels; L++) {
+		size_t bytes = 0;
+		ST_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys2, ids, ids2, N, 0, (unsigned)std::min(std::max(frames[L].key_bits, 1), 63), stream));
+		sort_bytes = std::max(sort_bytes, bytes);
+	}
+	ST_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	ST_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	StatReport rep;
+	// ev_begin .. ev_end: the kernels and the read-backs; the allocations above and the frees at the end are outside
+	if (ev_begin) ST_TRY(hipEventRecord(ev_begin, stream));
+	ST_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
+	ST_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 4, stream));
+	int open = n;                                              // the points no level has resolved yet
+	int *cur = listA, *nxt = listB;
+	for (int L = 0; L < levels && open > 0; L++) {
+		const VoxelFrame& f = frames[L];
+		const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+		hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
+		ST_TRY(hipGetLastError());
+		size_t bytes = sort_bytes;
+		ST_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+		ST_TRY(hipGetLastError());
+		if (L == 0) {
+			const dim3 g0((n + kStatBlock - 1) / kStatBlock), b0(kStatBlock);
+			if (k <= 16) hipLaunchKernelGGL(stat_knn_block_kernel<16>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
+			else if (k <= 32) hipLaunchKernelGGL(stat_knn_block_kernel<32>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
+			else hipLaunchKernelGGL(stat_knn_block_kernel<64>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
+		} else {
+			hipLaunchKernelGGL(stat_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, r2[L], 0,
+			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, u, nxt, counts + L);
+		}
+		ST_TRY(hipGetLastError());
+		int left = -1;
+		ST_TRY(hipMemcpyAsync(&left, counts + L, sizeof(int), hipMemcpyDeviceToHost, stream));
+		ST_TRY(hipStreamSynchronize(stream));
+		if (left < 0 || left > open) return hipErrorUnknown;
+		rep.resolved[L] = open - left;
+		rep.levels_run = L + 1;
+		open = left;
+		std::swap(cur, nxt);
+	}
+	if (open > 0) {
+		// the top level: every point is a candidate, in any order
+		if (rep.levels_run == 0) {
+			hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, ids2, n);
+			ST_TRY(hipGetLastError());
+			hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, cur, n);
+			ST_TRY(hipGetLastError());
+			hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+			ST_TRY(hipGetLastError());
+		}
+		hipLaunchKernelGGL(stat_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, 0.f, 1, 0.f, 0.f,
+		                   0.f, 1.f, u, nxt, counts + kStatMaxLevels);
+		ST_TRY(hipGetLastError());
+		rep.top = open;
+	}
+	hipLaunchKernelGGL(stat_max_kernel, grd, blk, 0, stream, u, n, umax);
+	ST_TRY(hipGetLastError());
+	hipLaunchKernelGGL(stat_sums_kernel, grd, blk, 0, stream, u, n, umax, sums);
+	ST_TRY(hipGetLastError());
+	hipLaunchKernelGGL(stat_finish_kernel, dim3(1), dim3(64), 0, stream, umax, sums, n, std_ratio, fin);
+	ST_TRY(hipGetLastError());
+	hipLaunchKernelGGL(stat_flag_kernel, grd, blk, 0, stream, u, n, fin, flag);
+	ST_TRY(hipGetLastError());
+	ST_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
+	size_t bytes = scan_bytes;
+	ST_TRY(rocprim::exclusive_scan(tmp, bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	hipLaunchKernelGGL(ror_compact_kernel, grd, blk, 0, stream, d_xyz, flag, scan, n, d_out, d_index);
+	ST_TRY(hipGetLastError());
+	int m = -1;
+	StatFinish h_fin{0.0, 0.0, 0, 0};
+	ST_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+	ST_TRY(hipMemcpyAsync(&h_fin, fin, sizeof(StatFinish), hipMemcpyDeviceToHost, stream));
+	if (ev_end) ST_TRY(hipEventRecord(ev_end, stream));
+	ST_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
+#undef ST_TRY
+	if (m < 1 || m > n) return hipErrorUnknown;
+	*m_out = m;
+	if (threshold) *threshold = h_fin.threshold;
+	if (report) *report = rep;
+	return hipSuccess;
+}
+
 // the per-axis minimum and maximum of a cloud on the device: what voxel_frame derives on the host, for a cloud that never leaves the device
 struct MinMax3 { float mn[3], mx[3]; };
 struct MinMaxOf {

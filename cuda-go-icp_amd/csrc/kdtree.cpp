@@ -409,4 +409,221 @@ void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32
 	*m_out = m;
 }
 
+// ---- statistical outlier removal: what both paths share, and the host path ----
+void stat_check_params(size_t n, int32_t neighbors, float std_ratio)
+{
+	if (neighbors < 1 || neighbors > 64) throw std::invalid_argument("goicp stat outlier: neighbors must be in 1..64");
+	if (n == 0 || (size_t)neighbors > n - 1) throw std::invalid_argument("goicp stat outlier: neighbors must be at most n - 1");
+	if (!std::isfinite(std_ratio) || std_ratio < 0.f) throw std::invalid_argument("goicp stat outlier: std_ratio must be finite and >= 0");
+}
+
+void stat_check_cloud(const float* xyz, size_t n, float mn[3], float mx[3])
+{
+	if (!xyz || n == 0) throw std::invalid_argument("goicp stat outlier: empty cloud");
+	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp stat outlier: cloud too large");
+	for (int k = 0; k < 3; k++) { mn[k] = INFINITY; mx[k] = -INFINITY; }
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) {
+			const float x = xyz[3 * i + k];
+			if (!std::isfinite(x)) throw std::invalid_argument("goicp stat outlier: non-finite coordinate in the cloud");
+			mn[k] = std::min(mn[k], x);
+			mx[k] = std::max(mx[k], x);
+		}
+}
+
+// The first radius only decides how much work the levels do, never a bit of the result, so it is an estimate from a sample: the median
+// distance r_s from a sample point to its 8th nearest in the sample (ns points, every (n / ns)-th of the cloud), scaled to the radius that
+// holds 2 k points of the whole cloud as if the cloud were locally three-dimensional, r_s cbrt(2 k ns / (8 n)) -- a surface scan then gets
+// a few times more candidates than it needs, never fewer.  The median does not move with a few far points, which is what the extent E
+// would do; without a usable sample (none given, or r_s == 0) the fallback is E cbrt(k / n), a cloud that fills its bounding cube
+static float stat_r0_estimate(const float* sample, size_t ns, size_t n, int32_t neighbors)
+{
+	if (!sample || ns < 16) return 0.f;
+	const size_t m = std::min<size_t>(8, ns - 1), step = std::max<size_t>(1, ns / 256);
+	std::vector<float> d2(ns), rs;
+	for (size_t i = 0; i < ns; i += step) {
+		for (size_t j = 0; j < ns; j++) {
+			const float dx = sample[3 * i] - sample[3 * j], dy = sample[3 * i + 1] - sample[3 * j + 1], dz = sample[3 * i + 2] - sample[3 * j + 2];
+			d2[j] = dx * dx + dy * dy + dz * dz;
+		}
+		d2[i] = INFINITY;
+		std::nth_element(d2.begin(), d2.begin() + (m - 1), d2.end());
+		rs.push_back(std::sqrt(d2[m - 1]));
+	}
+	std::nth_element(rs.begin(), rs.begin() + rs.size() / 2, rs.end());
+	const float r_s = rs[rs.size() / 2];
+	if (!(r_s > 0.f) || !std::isfinite(r_s)) return 0.f;
+	return r_s * std::cbrt(2.f * (float)neighbors * (float)ns / ((float)m * (float)n));
+}
+
+size_t stat_sample_size(size_t n) { return std::min<size_t>(n, 4096); }
+
+// Clamped to [E 2^-15, E]; no grid level (r0 = 0) when E == 0 or r0 * r0 is no normal float.  The level radii double up to the first
+// two that reach 2 E (where one cell holds the cloud) or until their square overflows; what is left after them goes to the top level
+void stat_levels(const float mn[3], const float mx[3], size_t n, int32_t neighbors, const float* sample, size_t ns, float* r0_out, int* levels_out)
+{
+	*r0_out = 0.f;
+	*levels_out = 0;
+	float E = 0.f;
+	for (int k = 0; k < 3; k++) E = std::max(E, mx[k] - mn[k]);
+	if (!(E > 0.f) || !std::isfinite(E)) return;
+	float r0 = stat_r0_estimate(sample, ns, n, neighbors);
+	if (!(r0 > 0.f) || !std::isfinite(r0)) r0 = E * std::cbrt((float)neighbors / (float)n);
+	r0 = std::min(r0, E);
+	if (!(E / r0 < 32768.f)) r0 = E * (1.f / 32768.f);
+	if (!std::isnormal(r0 * r0) || !(E / r0 < 65536.f)) return;
+	int cap = 2;
+	for (float r = r0; r < E && cap < 40; r *= 2.f) cap++;
+	int levels = 0;
+	for (float r = r0; levels < cap && std::isnormal(r * r) && std::isfinite(r * 1.03125f); r *= 2.f) levels++;
+	*r0_out = r0;
+	*levels_out = levels;
+}
+
+namespace {
+
+// the k smallest d2 of a point, kept as a max-heap of at most k values
+struct StatHeap {
+	float h[64];
+	int size = 0, k;
+	explicit StatHeap(int k_) : k(k_) {}
+	void offer(float d2)
+	{
+		if (size < k) { h[size++] = d2; std::push_heap(h, h + size); }
+		else if (d2 < h[0]) { std::pop_heap(h, h + k); h[k - 1] = d2; std::push_heap(h, h + k); }
+	}
+	bool within(float r2) const { return size == k && h[0] <= r2; }
+	float mean()
+	{
+		std::sort(h, h + k);
+		double s = 0.0;
+		for (int j = 0; j < k; j++) s += (double)std::sqrt(h[j]);
+		return (float)(s / (double)k);
+	}
+};
+
+inline float stat_d2(const float* p, const float* q)
+{
+	const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+	return dx * dx + dy * dy + dz * dz;
+}
+
+}  // namespace
+
+void statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
+                                      float* out_mean_dist, double* threshold, size_t* m_out)
+{
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	stat_check_params(n, neighbors, std_ratio);
+	const int k = neighbors;
+	float r0 = 0.f;
+	int levels = 0;
+	{
+		// every (n / ns)-th point of the cloud
+		const size_t ns = stat_sample_size(n), stride = n / ns;
+		std::vector<float> sample(3 * ns);
+		for (size_t i = 0; i < ns; i++) std::memcpy(&sample[3 * i], xyz + 3 * i * stride, 3 * sizeof(float));
+		stat_levels(mn, mx, n, k, sample.data(), ns, &r0, &levels);
+	}
+	std::vector<float> u(n);
+	std::vector<int32_t> list(n), next;
+	std::iota(list.begin(), list.end(), 0);
+	const int threads = n >= 65536 ? 8 : 1;
+	const size_t chunk = 4096;
+	struct Pt { float x, y, z; int32_t id; };
+	std::vector<uint64_t> keys;
+	std::vector<Pt> pts;
+	std::vector<std::pair<uint64_t, int32_t>> ki;
+	std::vector<unsigned char> open;
+	float r = r0;
+	for (int L = 0; L < levels && !list.empty(); L++, r *= 2.f) {
+		VoxelFrame f;
+		radius_frame_of_box(mn, mx, n, r, 1, &f);
+		const float r2 = r * r;
+		auto key_of = [&](const float* p) {
+			uint64_t key = 0;
+			for (int a = 0; a < 3; a++) key |= (uint64_t)(int)std::floor((p[a] - f.mn[a]) / f.voxel) << (21 * a);
+			return key;
+		};
+		ki.resize(n);
+		for (size_t i = 0; i < n; i++) ki[i] = {key_of(xyz + 3 * i), (int32_t)i};
+		std::sort(ki.begin(), ki.end());
+		keys.resize(n); pts.resize(n);
+		for (size_t s = 0; s < n; s++) {
+			const float* p = xyz + 3 * (size_t)ki[s].second;
+			keys[s] = ki[s].first;
+			pts[s] = {p[0], p[1], p[2], ki[s].second};
+		}
+		open.assign(list.size(), 0);
+		parallel_tasks(threads, (int)((list.size() + chunk - 1) / chunk), [&](int t) {
+			for (size_t e = (size_t)t * chunk; e < std::min(list.size(), ((size_t)t + 1) * chunk); e++) {
+				const int32_t id = list[e];
+				const float* P = xyz + 3 * (size_t)id;
+				const uint64_t K = key_of(P);
+				const int64_t cx = (int64_t)(K & 0x1fffffu), cy = (int64_t)((K >> 21) & 0x1fffffu), cz = (int64_t)(K >> 42);
+				StatHeap H(k);
+				for (int64_t z = std::max<int64_t>(cz - 1, 0); z <= cz + 1; z++)
+					for (int64_t y = std::max<int64_t>(cy - 1, 0); y <= cy + 1; y++) {
+						const uint64_t base = ((uint64_t)z << 42) | ((uint64_t)y << 21);
+						const size_t a = std::lower_bound(keys.begin(), keys.end(), base | (uint64_t)std::max<int64_t>(cx - 1, 0)) - keys.begin();
+						const size_t b = std::upper_bound(keys.begin() + a, keys.end(), base | (uint64_t)(cx + 1)) - keys.begin();
+						for (size_t j = a; j < b; j++)
+							if (pts[j].id != id) H.offer(stat_d2(P, &pts[j].x));
+					}
+				if (H.within(r2)) u[(size_t)id] = H.mean(); else open[e] = 1;
+			}
+		});
+		next.clear();
+		for (size_t e = 0; e < list.size(); e++) if (open[e]) next.push_back(list[e]);
+		list.swap(next);
+	}
+	// the top level: every point is a candidate
+	if (!list.empty())
+		parallel_tasks(threads, (int)((list.size() + 255) / 256), [&](int t) {
+			for (size_t e = (size_t)t * 256; e < std::min(list.size(), ((size_t)t + 1) * 256); e++) {
+				const int32_t id = list[e];
+				const float* P = xyz + 3 * (size_t)id;
+				StatHeap H(k);
+				for (size_t j = 0; j < n; j++)
+					if ((int32_t)j != id) H.offer(stat_d2(P, xyz + 3 * j));
+				u[(size_t)id] = H.mean();
+			}
+		});
+	// the fixed-point image and the finish
+	float U = 0.f;
+	for (size_t i = 0; i < n; i++) U = std::max(U, u[i]);
+	int e = 0;
+	double Tq = 0.0, thr = 0.0;
+	if (U > 0.f) {
+		std::frexp(U, &e);
+		int64_t S1 = 0, A = 0, B = 0;
+		for (size_t i = 0; i < n; i++) {
+			const uint64_t q = (uint64_t)(int64_t)std::floor(std::ldexp((double)u[i], 31 - e));
+			S1 += (int64_t)q;
+			A += (int64_t)((q * q) >> 32);
+			B += (int64_t)((q * q) & 0xffffffffull);
+		}
+		const double nd = (double)n;
+		const double mean = (double)S1 / nd;
+		const double S2 = std::ldexp((double)A, 32) + (double)B;
+		const double prod = (double)S1 * mean;
+		double var = (S2 - prod) / (nd - 1.0);
+		if (!(var > 0.0)) var = 0.0;
+		const double dev = (double)std_ratio * std::sqrt(var);
+		Tq = mean + dev;
+		thr = std::ldexp(Tq, e - 31);
+	}
+	size_t m = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (out_mean_dist) out_mean_dist[i] = u[i];
+		if (U > 0.f && !((double)(int64_t)std::floor(std::ldexp((double)u[i], 31 - e)) <= Tq)) continue;
+		for (int a = 0; a < 3; a++) out_xyz[3 * m + a] = xyz[3 * i + a];
+		if (out_index) out_index[m] = (int32_t)i;
+		m++;
+	}
+	if (threshold) *threshold = thr;
+	*m_out = m;
+}
+
 }  // namespace goicp

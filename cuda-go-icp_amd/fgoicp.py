@@ -98,10 +98,28 @@ def radius_outlier_removal(xyz, radius, min_neighbors):
     return _outlier_call(B.load_library().goicp_radius_outlier_removal_host, xyz, radius, min_neighbors)
 
 
-def _filter_host(pcs, voxel, radius, min_neighbors):
-    """the composition of the host functions that goicp_set_source_filtered equals"""
+def _stat_call(fn, xyz, neighbors, std_ratio):
+    xyz = _f32(xyz, (-1, 3))
+    n = len(xyz)
+    out, idx, mean, thr, m = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.float32), C.c_double(0.0), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), n, int(neighbors), float(std_ratio), _fptr(out), idx.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(mean), C.byref(thr), C.byref(m)))
+    return out[:m.value].copy(), idx[:m.value].copy(), mean, thr.value
+
+
+def statistical_outlier_removal(xyz, neighbors, std_ratio):
+    """goicp_statistical_outlier_removal_host (host only): the points whose mean distance to their `neighbors` nearest neighbours is at most
+    the cloud's mean of it plus `std_ratio` sample deviations, in input order -> (cloud (m, 3) float32, their indices (m,) int32, the mean
+    distance of every input point (n,) float32, the threshold as a float).  Registration.statistical_outlier_removal and
+    set_source(stat_neighbors=, std_ratio=) give the same bits on the device."""
+    return _stat_call(B.load_library().goicp_statistical_outlier_removal_host, xyz, neighbors, std_ratio)
+
+
+def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None):
+    """the composition of the host functions that goicp_set_source_filtered and goicp_set_source_pipeline equal"""
     if voxel:
         pcs = voxel_downsample(pcs, voxel)[0]
+    if stat_neighbors:
+        pcs = statistical_outlier_removal(pcs, stat_neighbors, std_ratio)[0]
     if radius:
         pcs = radius_outlier_removal(pcs, radius, min_neighbors)[0]
     return pcs
@@ -273,18 +291,32 @@ class Registration:
     def pcs(self, value):
         self._pcs, self._pcs_raw = value, None
 
-    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None):
         """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
         options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit.
         voxel: goicp_set_source_voxel -- the cloud is reduced to one centroid per voxel on the device first, and the handle answers as after
         set_source(voxel_downsample(pcs, voxel)[0]); self.ns is the number of points kept, self.pcs the reduced cloud.
         radius, min_neighbors (both or neither): goicp_set_source_filtered -- after the voxel grid, if any, the points with fewer than
         min_neighbors others within radius are dropped on the device, and the handle answers as after set_source of
-        radius_outlier_removal(..., radius, min_neighbors)[0]."""
+        radius_outlier_removal(..., radius, min_neighbors)[0].
+        stat_neighbors, std_ratio (both or neither): goicp_set_source_pipeline -- between the voxel grid and the radius filter, if any, the
+        statistical filter drops the points whose mean distance to their stat_neighbors nearest neighbours is above the mean plus std_ratio
+        deviations, and the handle answers as after set_source of the composed host functions' output."""
         pcs = _f32(pcs, (-1, 3))
         if (radius is None) != (min_neighbors is None):
             raise ValueError("set_source: radius and min_neighbors go together")
-        if voxel is None and radius is None:
+        if (stat_neighbors is None) != (std_ratio is None):
+            raise ValueError("set_source: stat_neighbors and std_ratio go together")
+        if stat_neighbors is not None:
+            if not int(stat_neighbors) > 0 or (voxel is not None and not float(voxel) > 0) or (radius is not None and not float(radius) > 0):
+                raise ValueError("set_source: a stage that is named needs a size > 0")
+            kept = C.c_size_t(0)
+            p = B.CSourcePipeline(float(voxel or 0.0), int(stat_neighbors), float(std_ratio), float(radius or 0.0), int(min_neighbors or 0))
+            B.check(self._lib.goicp_set_source_pipeline(self.handle, _fptr(pcs), len(pcs), C.byref(p), C.byref(kept)))
+            self._pcs, self.ns = None, kept.value
+            self._pcs_raw = (pcs, None if voxel is None else float(voxel), None if radius is None else float(radius),
+                             None if min_neighbors is None else int(min_neighbors), int(stat_neighbors), float(std_ratio))
+        elif voxel is None and radius is None:
             B.check(self._lib.goicp_set_source(self.handle, _fptr(pcs), len(pcs)))
             self.pcs, self.ns = pcs, len(pcs)
         elif radius is None:
@@ -311,6 +343,11 @@ class Registration:
         """goicp_radius_outlier_removal: the module-level radius_outlier_removal on the device (the handle lends its device and stream, its
         state is untouched) -> (cloud (m, 3) float32, indices (m,) int32, counts (n,) int32), the same bits"""
         return _outlier_call(lambda *a: self._lib.goicp_radius_outlier_removal(self.handle, *a), xyz, radius, min_neighbors)
+
+    def statistical_outlier_removal(self, xyz, neighbors, std_ratio):
+        """goicp_statistical_outlier_removal: the module-level statistical_outlier_removal on the device (the handle lends its device and
+        stream, its state is untouched) -> (cloud (m, 3) float32, indices (m,) int32, mean distances (n,) float32, threshold), the same bits"""
+        return _stat_call(lambda *a: self._lib.goicp_statistical_outlier_removal(self.handle, *a), xyz, neighbors, std_ratio)
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""
@@ -575,9 +612,9 @@ class FastGoICP:
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
 
-    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None):
         """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
-        self.registration.set_source(pcs, voxel, radius, min_neighbors)
+        self.registration.set_source(pcs, voxel, radius, min_neighbors, stat_neighbors, std_ratio)
         self.sse_threshold = self.registration.sse_threshold
 
     def run(self):

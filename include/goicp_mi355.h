@@ -297,6 +297,52 @@ int goicp_radius_outlier_removal(goicp_handle h, const float* xyz, size_t n, flo
 typedef struct goicp_source_filter { float voxel; float radius; int32_t min_neighbors; } goicp_source_filter;
 void goicp_source_filter_default(goicp_source_filter* out);   /* all 0 = no stage */
 int goicp_set_source_filtered(goicp_handle h, const float* xyz, size_t n, const goicp_source_filter* f, size_t* n_kept);
+/*
+ * Statistical outlier removal (PCL's StatisticalOutlierRemoval with setMeanK / setStddevMulThresh, Open3D's remove_statistical_outlier
+ * with nb_neighbors / std_ratio): a point is dropped when its mean distance to its k = `neighbors` nearest neighbours lies more than
+ * alpha = `std_ratio` standard deviations above the cloud's mean of that quantity.  The host function, the device function and the chained
+ * swap produce the same bits.  Arithmetic is IEEE, nothing fused:
+ *   pair    for points i != j, in float: dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j, d2 = dx*dx + dy*dy + dz*dz evaluated left to right
+ *           (the radius filter's expression, symmetric in i and j).  A duplicate of a point is its neighbour at distance 0, a point is
+ *           never its own neighbour;
+ *   nearest the n - 1 values d2(i, .) sorted ascending, the first k of them as a multiset (ties share a value: which tied point is taken
+ *           cannot show).  s_i = sum of (double)sqrtf(d2) over them, added in ascending order, sqrtf correctly rounded;
+ *           u_i = (float)(s_i / (double)k);
+ *   image   U = max u_i.  U == 0: every point is kept and the threshold is 0.  Otherwise frexp(U) gives e with U < 2^e,
+ *           q_i = (int64)floor(ldexp((double)u_i, 31 - e)), 0 <= q_i < 2^31, and the exact integer sums S1 = sum q_i,
+ *           A = sum (q_i * q_i >> 32), B = sum (q_i * q_i & 0xffffffff): below 2^60 each, so the order of addition cannot matter;
+ *   finish  in fp64, each operation rounded once: nd = (double)n, mean = (double)S1 / nd, S2 = ldexp((double)A, 32) + (double)B,
+ *           var = (S2 - (double)S1 * mean) / (nd - 1), set to 0 unless var > 0, Tq = mean + (double)alpha * sqrt(var) -- PCL's
+ *           (sum m^2 - (sum m)^2 / n) / (n - 1), Open3D's sample deviation;
+ *   keep    point i is kept iff (double)q_i <= Tq.  The point with the smallest q always passes, so m >= 1.  The reported threshold is
+ *           ldexp(Tq, e - 31); the quantisation step is below U * 2^-30;
+ *   output  the m kept points in input order with their own bits, their original indices (ascending), u_i of all n points, the threshold.
+ * The definition names no grid and nothing about the cloud's extent is refused: the implementations search grids of doubling pitch that
+ * only select candidates.  A cloud whose d2 all underflow to 0 has u = 0 and keeps everything.
+ * out_xyz holds n x 3 floats (the first m x 3 are written), out_index (may be NULL) n ints (the first m are written), out_mean_dist (may
+ * be NULL) n floats (all written), *threshold (may be NULL) the threshold, *m the number of points kept.
+ * goicp_statistical_outlier_removal_host runs on the host alone (no handle, no GPU).  goicp_statistical_outlier_removal runs on the
+ * device: the handle lends its device and stream, its state is untouched.
+ * GOICP_ERR_INVALID, nothing written: NULL arguments, n == 0 or above goicp_create's limit, a non-finite coordinate, neighbors outside
+ * 1..GOICP_STAT_MAX_NEIGHBORS or above n - 1, a std_ratio that is negative, NaN or infinite, and for the handle form any call while a
+ * registration runs.
+ */
+#define GOICP_STAT_MAX_NEIGHBORS 64
+int goicp_statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index, float* out_mean_dist, double* threshold, size_t* m);
+int goicp_statistical_outlier_removal(goicp_handle h, const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index, float* out_mean_dist, double* threshold, size_t* m);
+/*
+ * The three-stage swap: the voxel grid when voxel > 0, then the statistical filter when stat_neighbors > 0, then the radius filter when
+ * radius > 0, then the swap.  The raw cloud is uploaded once, every stage reads the previous stage's device buffer, and only the final
+ * cloud and the permutation (and the 24 bytes of an intermediate cloud's bounding box) come back.  Afterwards the handle answers every
+ * entry point bit for bit as after goicp_set_source(h, D, m) with D the composition of the host functions.  With the statistical stage
+ * off it runs goicp_set_source_filtered.  *n_kept (may be NULL) = m.
+ * GOICP_ERR_INVALID, the handle untouched: everything the stages and goicp_set_source_filtered refuse, a negative stat_neighbors,
+ * stat_neighbors above the size of the cloud that reaches the stage minus one, a chain that keeps no point, and any call while a
+ * registration runs.
+ */
+typedef struct goicp_source_pipeline { float voxel; int32_t stat_neighbors; float stat_std_ratio; float radius; int32_t min_neighbors; } goicp_source_pipeline;
+void goicp_source_pipeline_default(goicp_source_pipeline* out);   /* all 0 = no stage */
+int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, size_t* n_kept);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

@@ -235,6 +235,18 @@ public:
 		ns_ = kept;
 		return kept;
 	}
+	// the same behind the three-stage chain (goicp_set_source_pipeline): the voxel grid when p.voxel > 0, then statistical outlier removal
+	// when p.stat_neighbors > 0 (mean distance to the nearest neighbours above the mean plus p.stat_std_ratio deviations), then radius
+	// outlier removal when p.radius > 0, all on the device; returns the points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, size_t ns, const goicp_source_pipeline& p)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		size_t kept = 0;
+		check(goicp_set_source_pipeline(h_, reinterpret_cast<const float*>(pcs.data()), ns, &p, &kept));
+		ns_ = kept;
+		return kept;
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
@@ -391,6 +403,14 @@ public:
 	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_filter& f)
 	{
 		const size_t kept = registration.set_source(pcs, pcs.size(), f);
+		sync();
+		return kept;
+	}
+	// ... behind the three-stage chain `p` (voxel grid, statistical outlier removal, radius outlier removal); returns the number of points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_pipeline& p)
+	{
+		const size_t kept = registration.set_source(pcs, pcs.size(), p);
 		sync();
 		return kept;
 	}
