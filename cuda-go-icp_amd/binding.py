@@ -208,6 +208,10 @@ SYMBOLS = {
                                                    C.POINTER(C.c_size_t)]),
     "goicp_source_pipeline_default": (None, [C.POINTER(CSourcePipeline)]),
     "goicp_set_source_pipeline": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(C.c_size_t)]),
+    "goicp_knn_self_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
+    "goicp_knn_self": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
+    "goicp_estimate_normals_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
+    "goicp_estimate_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

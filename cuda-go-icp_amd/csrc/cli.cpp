@@ -52,6 +52,11 @@
 //               (goicp_statistical_outlier_removal_host), every listed cloud on the device as part of its swap (goicp_set_source_pipeline:
 //               the same bits); each prints "kept m of n".  --target-stat-neighbors K --target-stat-std-ratio A filter the target the same
 //               way, on the host.  K must be an integer in 1..64, A a finite number >= 0 -- refused before any device is touched
+//   --estimate-normals IN OUT.ply [--normal-k K] [--viewpoint X,Y,Z]   a mode of its own that takes no config and registers nothing: per-point
+//               normals and surface variation of the cloud IN from its K-point neighbourhoods (K counts the point itself, 3..32, default 16;
+//               goicp_estimate_normals on the device when there is one, goicp_estimate_normals_host otherwise: the same bits), flipped
+//               towards the viewpoint when one is given.  OUT.ply is an ASCII PLY with x y z nx ny nz curvature.  Refused together with
+//               --ranks -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -87,8 +92,102 @@ static std::string numbered(const std::string& p, int k)
 	return p.substr(0, dot) + tag + p.substr(dot);
 }
 
+// goicp_cli --estimate-normals IN OUT.ply [--normal-k K] [--viewpoint X,Y,Z] [--verbose]: no config, no registration.  `at` is the
+// position of --estimate-normals in argv
+static int estimate_normals_mode(int argc, char** argv, int at)
+{
+	const char *in = at + 1 < argc ? argv[at + 1] : nullptr, *out = at + 2 < argc ? argv[at + 2] : nullptr;
+	const char *k_arg = nullptr, *vp_arg = nullptr;
+	int verbose = 0;
+	// refused before any device is touched
+	for (int i = 1; i < argc; i++) {
+		if (i >= at && i <= at + 2) continue;
+		if (!std::strcmp(argv[i], "--ranks")) {
+			std::fprintf(stderr, "error: --estimate-normals cannot be combined with --ranks (it runs on one device and registers nothing)\n");
+			return 2;
+		}
+		if (!std::strcmp(argv[i], "--normal-k")) k_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--viewpoint")) vp_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--verbose")) verbose = 1;
+		else {
+			std::fprintf(stderr, "error: --estimate-normals takes --normal-k K, --viewpoint X,Y,Z and --verbose, got '%s'\n", argv[i]);
+			return 2;
+		}
+	}
+	if (!in || !out || !*in || !*out || !std::strncmp(in, "--", 2) || !std::strncmp(out, "--", 2)) {
+		std::fprintf(stderr, "error: --estimate-normals needs IN and OUT.ply\n");
+		return 2;
+	}
+	long k = 16;
+	if (k_arg) {
+		char* end = nullptr;
+		k = std::strtol(k_arg, &end, 10);
+		if (end == k_arg || *end != '\0' || k < 3 || k > GOICP_KNN_SELF_MAX) {
+			std::fprintf(stderr, "error: --estimate-normals needs --normal-k in 3..%d, got '%s'\n", GOICP_KNN_SELF_MAX, k_arg);
+			return 2;
+		}
+	}
+	float vp[3] = {0.f, 0.f, 0.f};
+	if (vp_arg) {
+		const char* s = vp_arg;
+		bool ok = true;
+		for (int a = 0; a < 3 && ok; a++) {
+			char* end = nullptr;
+			vp[a] = std::strtof(s, &end);
+			ok = end != s && std::isfinite(vp[a]) && *end == (a < 2 ? ',' : '\0');
+			s = end + 1;
+		}
+		if (!ok) {
+			std::fprintf(stderr, "error: --viewpoint needs three finite numbers X,Y,Z, got '%s'\n", vp_arg);
+			return 2;
+		}
+	}
+	try {
+		std::vector<P3> cloud;
+		load_cloud(in, 1.f, 1.f, cloud, 0);
+		const size_t n = cloud.size();
+		std::vector<float> normals(3 * n), variation(n);
+		// a handle only lends its device: eight corners of a cube are its clouds
+		std::vector<P3> corners;
+		for (int c = 0; c < 8; c++) corners.push_back(P3{c & 1 ? 0.5f : -0.5f, c & 2 ? 0.5f : -0.5f, c & 4 ? 0.5f : -0.5f});
+		goicp_params params;
+		goicp_params_default(&params);
+		params.dt_size = 32;
+		params.verbose = verbose;
+		goicp_handle h = nullptr;
+		const auto t0 = std::chrono::steady_clock::now();
+		const int rc = goicp_create(&params, &corners[0].x, 8, &corners[0].x, 8, &h);
+		if (rc != GOICP_OK && rc != GOICP_ERR_NO_DEVICE) check(rc);
+		const auto t1 = std::chrono::steady_clock::now();
+		const int st = h ? goicp_estimate_normals(h, &cloud[0].x, n, (int32_t)k, vp_arg ? vp : nullptr, normals.data(), variation.data(), nullptr)
+		                 : goicp_estimate_normals_host(n ? &cloud[0].x : nullptr, n, (int32_t)k, vp_arg ? vp : nullptr, normals.data(), variation.data(), nullptr);
+		const auto t2 = std::chrono::steady_clock::now();
+		const std::string why = st != GOICP_OK ? goicp_last_error() : "";
+		const bool on_device = h != nullptr;
+		if (h) goicp_destroy(h);
+		if (st != GOICP_OK) throw std::runtime_error(why);
+		FILE* f = std::fopen(out, "w");
+		if (!f) throw std::runtime_error(std::string("cannot write ") + out);
+		std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+		                "property float nz\nproperty float curvature\nend_header\n", n);
+		for (size_t i = 0; i < n; i++)
+			std::fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", cloud[i].x, cloud[i].y, cloud[i].z, normals[3 * i], normals[3 * i + 1], normals[3 * i + 2],
+			             variation[i]);
+		if (std::fclose(f) != 0) throw std::runtime_error(std::string("cannot write ") + out);
+		std::printf("estimate normals: %zu points, k %ld, %s, %.2f ms%s -> %s\n", n, k, on_device ? "on the device" : "on the host (no device)",
+		            std::chrono::duration<double, std::milli>(t2 - t1).count(),
+		            on_device ? (" (handle " + std::to_string(std::chrono::duration<double, std::milli>(t1 - t0).count()) + " ms)").c_str() : "", out);
+		return 0;
+	} catch (const std::exception& e) {
+		std::fprintf(stderr, "error: %s\n", e.what());
+		return 1;
+	}
+}
+
 int main(int argc, char** argv)
 {
+	for (int i = 1; i < argc; i++)
+		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
 	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here

@@ -2,6 +2,7 @@
 // device.hip, compiled by hipcc for gfx950).  Host C++ (engine.cpp, goicp_api.cpp) only sees this.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -464,6 +465,128 @@ struct StatReport {
 hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, float std_ratio,
                                        float* d_out, int32_t* d_index, float* d_mean, double* threshold, int* m, StatReport* report, hipStream_t stream,
                                        hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ---- exact self k-NN and normal estimation on the device (kdbuild.hip; goicp_knn_self_host / goicp_estimate_normals_host are
+// the host twins) ----
+constexpr int kKnnSelfMax = 32;
+// frames / r2 / levels as launch_stat_outlier_removal takes them.  k in 1..kKnnSelfMax, k <= n - 1.  d_index: n x k ints, row i = the k
+// nearest other points of point i ascending by the key (bits of d2) << 32 | index; d_dist_sq (may be null): n x k floats, their d2;
+// d_order (may be null): n ints, the points in the order of the first grid level (input order when no level ran).  ev_begin / ev_end (may
+// be null) are recorded around the kernels and the read-backs (one int per level).  Returns after the stream has drained
+hipError_t launch_self_knn(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, int32_t* d_index, float* d_dist_sq,
+                           int* d_order, StatReport* report, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// k in 3..kKnnSelfMax counts the point itself, k - 1 <= n - 1.  d_index: n x (k - 1) ints, the neighbours used (launch_self_knn's rows at
+// k - 1); vp: the viewpoint on the host, or null; d_normals: n x 3 floats; d_variation (may be null): n floats
+hipError_t launch_estimate_normals(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, const float* vp,
+                                   float* d_normals, float* d_variation, int32_t* d_index, StatReport* report, hipStream_t stream,
+                                   hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+
+// The PCA of one neighbourhood as include/goicp_mi355.h defines it, one text for the host path (kdtree.cpp) and normal_pca_kernel: fp64,
+// every operation rounded once (the device takes the _rn intrinsics, the host is built with -ffp-contract=off), + - * / sqrt only.
+#if defined(__HIPCC__)
+#define GOICP_HD __host__ __device__
+#else
+#define GOICP_HD
+#endif
+namespace pca {
+#if defined(__HIP_DEVICE_COMPILE__)
+GOICP_HD inline double add(double a, double b) { return __dadd_rn(a, b); }
+GOICP_HD inline double sub(double a, double b) { return __dsub_rn(a, b); }
+GOICP_HD inline double mul(double a, double b) { return __dmul_rn(a, b); }
+GOICP_HD inline double div(double a, double b) { return __ddiv_rn(a, b); }
+GOICP_HD inline double root(double a) { return __dsqrt_rn(a); }
+#else
+GOICP_HD inline double add(double a, double b) { return a + b; }
+GOICP_HD inline double sub(double a, double b) { return a - b; }
+GOICP_HD inline double mul(double a, double b) { return a * b; }
+GOICP_HD inline double div(double a, double b) { return a / b; }
+GOICP_HD inline double root(double a) { return std::sqrt(a); }
+#endif
+GOICP_HD inline double mag(double a) { return a < 0.0 ? -a : a; }
+constexpr int kMaxSweeps = 32;
+
+// one Jacobi rotation of the pair (P, Q); false: the pair was skipped
+template <int P, int Q> GOICP_HD inline bool rotate(double A[3][3], double V[3][3])
+{
+	const double app = A[P][P], aqq = A[Q][Q], apq = A[P][Q];
+	if (apq == 0.0 || mul(apq, apq) <= mul(1e-24, mag(mul(app, aqq)))) return false;
+	const double da = sub(aqq, app), db = add(apq, apq);
+	const double tn = div(da >= 0.0 ? db : -db, add(mag(da), root(add(mul(da, da), mul(db, db)))));
+	const double cs = div(1.0, root(add(1.0, mul(tn, tn)))), sn = mul(cs, tn);
+	for (int k = 0; k < 3; k++) {                                // A <- A G (columns P, Q)
+		const double akp = A[k][P], akq = A[k][Q];
+		A[k][P] = sub(mul(cs, akp), mul(sn, akq)); A[k][Q] = add(mul(sn, akp), mul(cs, akq));
+	}
+	for (int k = 0; k < 3; k++) {                                // A <- G^T A (rows P, Q)
+		const double apk = A[P][k], aqk = A[Q][k];
+		A[P][k] = sub(mul(cs, apk), mul(sn, aqk)); A[Q][k] = add(mul(sn, apk), mul(cs, aqk));
+	}
+	for (int k = 0; k < 3; k++) {                                // V <- V G
+		const double vkp = V[k][P], vkq = V[k][Q];
+		V[k][P] = sub(mul(cs, vkp), mul(sn, vkq)); V[k][Q] = add(mul(sn, vkp), mul(cs, vkq));
+	}
+	return true;
+}
+}  // namespace pca
+
+// xyz: the cloud; i: the point; row: its kk = k - 1 nearest others in key order; (vpx, vpy, vpz): the viewpoint when has_vp -> the normal and the
+// surface variation
+GOICP_HD inline void normal_pca_point(const float* xyz, int i, const int32_t* row, int kk, bool has_vp, float vpx, float vpy, float vpz, float out_n[3],
+                                      float* out_var)
+{
+	using namespace pca;
+	const double xi = (double)xyz[3 * (size_t)i], yi = (double)xyz[3 * (size_t)i + 1], zi = (double)xyz[3 * (size_t)i + 2];
+	const double kd = (double)(kk + 1);
+	// the mean of the offsets e_j; the point's own offset (0, 0, 0) comes first
+	double sx = 0.0, sy = 0.0, sz = 0.0;
+	for (int j = 0; j < kk; j++) {
+		const float* q = xyz + 3 * (size_t)row[j];
+		sx = add(sx, sub((double)q[0], xi)); sy = add(sy, sub((double)q[1], yi)); sz = add(sz, sub((double)q[2], zi));
+	}
+	const double mx = div(sx, kd), my = div(sy, kd), mz = div(sz, kd);
+	double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
+	for (int j = -1; j < kk; j++) {
+		double dx = sub(0.0, mx), dy = sub(0.0, my), dz = sub(0.0, mz);
+		if (j >= 0) {
+			const float* q = xyz + 3 * (size_t)row[j];
+			dx = sub(sub((double)q[0], xi), mx); dy = sub(sub((double)q[1], yi), my); dz = sub(sub((double)q[2], zi), mz);
+		}
+		c00 = add(c00, mul(dx, dx)); c01 = add(c01, mul(dx, dy)); c02 = add(c02, mul(dx, dz));
+		c11 = add(c11, mul(dy, dy)); c12 = add(c12, mul(dy, dz)); c22 = add(c22, mul(dz, dz));
+	}
+	double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
+	double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+	for (int sweep = 0; sweep < kMaxSweeps; sweep++) {
+		const bool r01 = rotate<0, 1>(A, V), r02 = rotate<0, 2>(A, V), r12 = rotate<1, 2>(A, V);
+		if (!(r01 || r02 || r12)) break;
+	}
+	const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+	// the column of the smallest l, the lowest index on equal values (selects on values: an index into V would put it into scratch)
+	const bool s1 = l1 < l0;
+	const double l01 = s1 ? l1 : l0;
+	const bool s2 = l2 < l01;
+	const double v0 = s2 ? V[0][2] : (s1 ? V[0][1] : V[0][0]), v1 = s2 ? V[1][2] : (s1 ? V[1][1] : V[1][0]), v2 = s2 ? V[2][2] : (s1 ? V[2][1] : V[2][0]);
+	// ascending: a <= b <= c
+	double a = l0, b = l1, c = l2, t;
+	if (b < a) { t = a; a = b; b = t; }
+	if (c < b) { t = b; b = c; c = t; }
+	if (b < a) { t = a; a = b; b = t; }
+	if (!(c > 0.0)) {                                            // every neighbour coincides with the point
+		out_n[0] = out_n[1] = out_n[2] = 0.f;
+		*out_var = 0.f;
+		return;
+	}
+	*out_var = (float)div(a > 0.0 ? a : 0.0, add(add(a, b), c));
+	const double len = root(add(add(mul(v0, v0), mul(v1, v1)), mul(v2, v2)));
+	const float n0 = (float)div(v0, len), n1 = (float)div(v1, len), n2 = (float)div(v2, len);
+	double d = 0.0;
+	if (has_vp) d = add(add(mul((double)n0, sub((double)vpx, xi)), mul((double)n1, sub((double)vpy, yi))), mul((double)n2, sub((double)vpz, zi)));
+	const float lead = n0 != 0.f ? n0 : (n1 != 0.f ? n1 : n2);
+	const bool flip = d != 0.0 ? d < 0.0 : lead < 0.f;
+	out_n[0] = n0 == 0.f ? 0.f : (flip ? -n0 : n0);
+	out_n[1] = n1 == 0.f ? 0.f : (flip ? -n1 : n1);
+	out_n[2] = n2 == 0.f ? 0.f : (flip ? -n2 : n2);
+}
+
 // per-axis minimum and maximum of n points on the device (one rocPRIM reduction, 24 bytes come back): the frame of a cloud that a device
 // stage produced and the host has not seen.  Returns after the stream has drained
 hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream);

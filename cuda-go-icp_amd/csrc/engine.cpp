@@ -724,6 +724,61 @@ void Engine::statistical_outlier_removal(const float* xyz, size_t n, int32_t nei
 	if (p_.verbose) stat_report_line("statistical_outlier_removal", n, m, rep);
 }
 
+void Engine::knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
+{
+	if (!out_index) throw std::invalid_argument("goicp_knn_self: out_index must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	knn_self_check_params(n, k);
+	if (registering_.load()) throw std::invalid_argument("goicp_knn_self: not while a registration runs");
+	const StatPlan plan(mn, mx, n, k, stat_sample_host(xyz, n));
+	DeviceGuard guard(dev_);
+	const size_t rows = n * (size_t)k;
+	Buf<float> d_xyz(3 * n), d_d2(out_dist_sq ? rows : 0);
+	Buf<int32_t> d_idx(rows);
+	StatReport rep;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_self_knn(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, d_idx, out_dist_sq ? d_d2.get() : nullptr, nullptr,
+	                       &rep, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, stream_));
+	if (out_dist_sq) HIPCHK(hipMemcpyAsync(out_dist_sq, d_d2, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		stat_report_line("knn_self", n, (int)n, rep);
+		std::fprintf(stderr, "[goicp] knn_self: k %d, device %.3f ms\n", k, ms);
+	}
+}
+
+void Engine::estimate_normals(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index)
+{
+	if (!out_normals) throw std::invalid_argument("goicp_estimate_normals: out_normals must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	normals_check_params(n, k, vp);
+	if (registering_.load()) throw std::invalid_argument("goicp_estimate_normals: not while a registration runs");
+	const StatPlan plan(mn, mx, n, k - 1, stat_sample_host(xyz, n));
+	DeviceGuard guard(dev_);
+	const size_t rows = n * (size_t)(k - 1);
+	Buf<float> d_xyz(3 * n), d_nrm(3 * n), d_var(out_variation ? n : 0);
+	Buf<int32_t> d_idx(rows);
+	StatReport rep;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_estimate_normals(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, vp, d_nrm,
+	                               out_variation ? d_var.get() : nullptr, d_idx, &rep, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_normals, d_nrm, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, stream_));
+	if (out_variation) HIPCHK(hipMemcpyAsync(out_variation, d_var, sizeof(float) * n, hipMemcpyDeviceToHost, stream_));
+	if (out_index) HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		stat_report_line("estimate_normals", n, (int)n, rep);
+		std::fprintf(stderr, "[goicp] estimate_normals: k %d, device %.3f ms\n", k, ms);
+	}
+}
+
 void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
                                  size_t* n_kept)
 {

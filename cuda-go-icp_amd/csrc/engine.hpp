@@ -296,6 +296,10 @@ public:
 	// chained on the device behind one upload.  With the statistical stage off it is set_source_filtered
 	void set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
 	                         size_t* n_kept);
+	// goicp_knn_self / goicp_estimate_normals: the exact self k-NN and the normals of any cloud on the device (kdbuild.hip launch_self_knn /
+	// launch_estimate_normals); as statistical_outlier_removal, the engine lends its device and stream and nothing else
+	void knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
+	void estimate_normals(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -571,6 +575,13 @@ size_t stat_sample_size(size_t n);
 void stat_levels(const float mn[3], const float mx[3], size_t n, int32_t neighbors, const float* sample, size_t ns, float* r0, int* levels);
 void statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
                                       float* out_mean_dist, double* threshold, size_t* m);
+// exact self k-NN and normal estimation (kdtree.cpp).  knn_self_check_params refuses k outside 1..32 or above n - 1,
+// normals_check_params k outside 3..32, k - 1 above n - 1 and a non-finite viewpoint; the cloud is checked by stat_check_cloud.
+// knn_self_host / estimate_normals_host are goicp_knn_self_host / goicp_estimate_normals_host
+void knn_self_check_params(size_t n, int32_t k);
+void normals_check_params(size_t n, int32_t k, const float* vp);
+void knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
+void estimate_normals_host(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

@@ -271,6 +271,33 @@ int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const 
 	return guarded([&] { h->e->set_source_pipeline(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, n_kept); });
 }
 
+int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
+{
+	REQUIRE(xyz && out_index && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::knn_self_host(xyz, n, k, out_index, out_dist_sq); });
+}
+
+int goicp_knn_self(goicp_handle h, const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
+{
+	REQUIRE(h && xyz && out_index && n > 0);
+	return guarded([&] { h->e->knn_self(xyz, n, k, out_index, out_dist_sq); });
+}
+
+int goicp_estimate_normals_host(const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index)
+{
+	REQUIRE(xyz && out_normals && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::estimate_normals_host(xyz, n, k, vp, out_normals, out_variation, out_index); });
+}
+
+int goicp_estimate_normals(goicp_handle h, const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation,
+                           int32_t* out_index)
+{
+	REQUIRE(h && xyz && out_normals && n > 0);
+	return guarded([&] { h->e->estimate_normals(xyz, n, k, vp, out_normals, out_variation, out_index); });
+}
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

@@ -982,6 +982,297 @@ hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFra
 	return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Exact self k-NN and normal estimation on the device (host twins: knn_self_host, estimate_normals_host, kdtree.cpp).  The
+// statistical filter's search with the neighbours kept, not only their distances: every candidate is the 64-bit key
+// (bits of d2) << 32 | index, a total order, so the k smallest keys are the rows the header defines, ties at the k-th place included.  A
+// point is resolved at level L when the d2 of its k-th key is <= r_L * r_L: every point that close lies in its 27 cells, so
+// no unseen point has a smaller key.  Level 0 serves every point (self_knn_block_kernel), the later levels and the top level the listed
+// ones (self_knn_wave_kernel); normal_pca_kernel turns the rows into normals, one thread per point.
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned long long kKnnNoKey = ~0ull;                // above every key: the d2 of a key is finite
+
+__device__ __forceinline__ unsigned long long knn_key(float d2, int id) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(unsigned)id; }
+// the d2 of a key; of kKnnNoKey a NaN, which is <= no radius
+__device__ __forceinline__ float knn_key_d2(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+
+// stat_knn_block_kernel's shape with keys in the columns: lane t owns column t of `best` (8-byte words at stride kStatBlock: the 32 lanes
+// of a half wave read 64 consecutive dwords, one bank each), KT >= k rows of 2 KB.  A candidate is inserted only when its key is strictly
+// below the lane's k-th key, held in registers; keys are unique, so a cell of identical points costs one comparison per candidate once the
+// column holds the k smallest indices.  A lane whose k-th d2 is <= r2 writes row P.id; any other appends its id to the open list.  No
+// workgroup waits on another
+template <int KT>
+__global__ void __launch_bounds__(kStatBlock) self_knn_block_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, int k,
+                                                                    float r2, int32_t* __restrict__ out_index, float* __restrict__ out_d2,
+                                                                    int* __restrict__ open_list, int* __restrict__ open_count)
+{
+	__shared__ RorPt tile[kStatBlock];
+	__shared__ unsigned long long best[KT * kStatBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kStatBlock, last = min(first + kStatBlock, n) - 1;
+	const int s = first + tid;
+	const bool valid = s < n;
+	if (tid < 9) {
+		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
+		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
+		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
+	}
+	for (int j = 0; j < k; j++) best[j * kStatBlock + tid] = kKnnNoKey;
+	__syncthreads();
+	if (tid == 0)
+		for (int o = 1; o < 9; o++) {
+			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
+			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
+		}
+	__syncthreads();
+	RorPt P{0.f, 0.f, 0.f, -1};
+	long long K = 0;
+	if (valid) { P = pts[s]; K = (long long)keys[s]; }
+	unsigned long long kth = kKnnNoKey;
+	for (int o = 0; o < 9; o++) {
+		const int lo = iv_lo[o], hi = iv_hi[o];
+		for (int t0 = lo; t0 < hi; t0 += kStatBlock) {
+			__syncthreads();                                     // the previous tile has been read by everybody
+			const int len = min(kStatBlock, hi - t0);
+			if (tid < len) tile[tid] = pts[t0 + tid];
+			__syncthreads();
+			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
+			bool need = false;
+			if (valid)
+				for (int q = 0; q < 9; q++) {
+					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
+					need = need || (c - 1 <= tb && c + 1 >= ta);
+				}
+			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
+			if (!need) continue;
+			for (int j = 0; j < len; j++) {
+				const RorPt Q = tile[j];
+				const unsigned long long ck = knn_key(stat_d2(P.x, P.y, P.z, Q), Q.id);
+				if (ck < kth && Q.id != P.id) {
+					int p = k - 1;
+					while (p > 0) {
+						const unsigned long long b = best[(p - 1) * kStatBlock + tid];
+						if (!(b > ck)) break;
+						best[p * kStatBlock + tid] = b;
+						p--;
+					}
+					best[p * kStatBlock + tid] = ck;
+					kth = best[(k - 1) * kStatBlock + tid];
+				}
+			}
+		}
+	}
+	if (!valid) return;
+	if (knn_key_d2(kth) <= r2) {
+		const size_t row = (size_t)P.id * (size_t)k;
+		for (int j = 0; j < k; j++) {
+			const unsigned long long key = best[j * kStatBlock + tid];
+			out_index[row + j] = (int32_t)(unsigned)(key & 0xffffffffull);
+			if (out_d2) out_d2[row + j] = knn_key_d2(key);
+		}
+	} else {
+		open_list[atomicAdd(open_count, 1)] = P.id;
+	}
+}
+
+__device__ __forceinline__ unsigned long long knn_shfl64(unsigned long long v, int src)
+{
+	const int lo = __shfl((int)(unsigned)(v & 0xffffffffull), src, 64);
+	const int hi = __shfl((int)(unsigned)(v >> 32), src, 64);
+	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+}
+
+__device__ __forceinline__ unsigned long long knn_shfl_up64(unsigned long long v)
+{
+	const int lo = __shfl_up((int)(unsigned)(v & 0xffffffffull), 1, 64);
+	const int hi = __shfl_up((int)(unsigned)(v >> 32), 1, 64);
+	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+}
+
+// stat_knn_wave_kernel with keys: a wave per listed point, lane j holds the j-th smallest key seen so far (a 64-bit shuffle is two 32-bit
+// ones), a candidate strictly below the k-th key is inserted by one shuffle up -- a lane keeps its key if it is below the candidate, takes
+// the candidate if its lower neighbour's key is below it, and its lower neighbour's key otherwise.  Lanes 0..k-1 write the row.  all = 1 is
+// the top level, the one run [0, n).  The loops run over the runs' lengths; no wave waits on another
+__global__ void __launch_bounds__(256) self_knn_wave_kernel(const float* __restrict__ xyz, const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys,
+                                                            int n, const int* __restrict__ list, int count, int k, float r2, int all, float mnx, float mny,
+                                                            float mnz, float pitch, int32_t* __restrict__ out_index, float* __restrict__ out_d2,
+                                                            int* __restrict__ open_list, int* __restrict__ open_count)
+{
+	const int w = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+	if (w >= count) return;                                      // wave-uniform
+	const int id = list[w];
+	const float px = xyz[3 * (size_t)id], py = xyz[3 * (size_t)id + 1], pz = xyz[3 * (size_t)id + 2];
+	int my_lo = 0, my_hi = 0;
+	if (all) {
+		if (lane == 0) my_hi = n;
+	} else if (lane < 9) {
+		const long long K = (long long)(vx_cell(px - mnx, pitch) | (vx_cell(py - mny, pitch) << 21) | (vx_cell(pz - mnz, pitch) << 42));
+		const long long c = K + (long long)(lane % 3 - 1) * (1ll << 21) + (long long)(lane / 3 - 1) * (1ll << 42);
+		my_lo = ror_bound(keys, n, c - 1, false);
+		my_hi = max(my_lo, ror_bound(keys, n, c + 1, true));
+	}
+	unsigned long long mine = kKnnNoKey, kth = kKnnNoKey;
+	const int runs = all ? 1 : 9;
+	for (int o = 0; o < runs; o++) {
+		const int lo = __shfl(my_lo, o, 64), hi = __shfl(my_hi, o, 64);
+		for (int base = lo; base < hi; base += 64) {
+			const int j = base + lane;
+			unsigned long long ck = kKnnNoKey;
+			if (j < hi) {
+				const RorPt Q = pts[j];
+				if (Q.id != id) ck = knn_key(stat_d2(px, py, pz, Q), Q.id);
+			}
+			unsigned long long hot = __ballot(ck < kth);
+			while (hot) {
+				const int src = __ffsll((long long)hot) - 1;
+				hot &= hot - 1;
+				const unsigned long long v = knn_shfl64(ck, src);
+				if (v < kth) {                                       // wave-uniform
+					const unsigned long long below = knn_shfl_up64(mine);
+					mine = (mine < v) ? mine : ((lane == 0 || below < v) ? v : below);
+					kth = knn_shfl64(mine, k - 1);
+				}
+			}
+		}
+	}
+	if (all || knn_key_d2(kth) <= r2) {
+		if (lane < k) {
+			const size_t at = (size_t)id * (size_t)k + (size_t)lane;
+			out_index[at] = (int32_t)(unsigned)(mine & 0xffffffffull);
+			if (out_d2) out_d2[at] = knn_key_d2(mine);
+		}
+	} else if (lane == 0) {
+		open_list[atomicAdd(open_count, 1)] = id;
+	}
+}
+
+// One thread per point, taken in the order of the first grid level so that the threads of a wave gather from neighbouring memory.  The
+// arithmetic is normal_pca_point's (device.hpp), the host's text
+__global__ void __launch_bounds__(256) normal_pca_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ rows, const int* __restrict__ order, int n,
+                                                         int kk, int has_vp, float vpx, float vpy, float vpz, float* __restrict__ normals,
+                                                         float* __restrict__ variation)
+{
+	const int s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= n) return;
+	const int i = order[s];
+	float nrm[3], var;
+	normal_pca_point(xyz, i, rows + (size_t)i * (size_t)kk, kk, has_vp != 0, vpx, vpy, vpz, nrm, &var);
+	normals[3 * (size_t)i] = nrm[0]; normals[3 * (size_t)i + 1] = nrm[1]; normals[3 * (size_t)i + 2] = nrm[2];
+	if (variation) variation[i] = var;
+}
+
+hipError_t launch_self_knn(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, int32_t* d_index, float* d_dist_sq,
+                           int* d_order, StatReport* report, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n < 2 || !d_index || k < 1 || k > kKnnSelfMax || k > n - 1 || levels < 0 || levels > kStatMaxLevels || (levels > 0 && (!frames || !r2))) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define KS_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	unsigned long long *keys = nullptr, *keys2 = nullptr;
+	int *ids = nullptr, *ids2 = nullptr, *listA = nullptr, *listB = nullptr, *counts = nullptr;
+	RorPt* pts = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		void* const* p[9];
+		~Cleanup() { for (void* const* q : p) hipFree(*q); }
+	} cleanup{{(void**)&keys, (void**)&keys2, (void**)&ids, (void**)&ids2, (void**)&listA, (void**)&listB, (void**)&counts, (void**)&pts, &tmp}};
+	const size_t N = (size_t)n;
+	KS_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
+	KS_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
+	KS_TRY(hipMalloc(&ids, sizeof(int) * N));
+	KS_TRY(hipMalloc(&ids2, sizeof(int) * N));
+	KS_TRY(hipMalloc(&listA, sizeof(int) * N));
+	KS_TRY(hipMalloc(&listB, sizeof(int) * N));
+	KS_TRY(hipMalloc(&counts, sizeof(int) * (kStatMaxLevels + 1)));
+	KS_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
+	size_t sort_bytes = 0;
+	for (int L = 0; L < levels; L++) {
+		size_t bytes = 0;
+		KS_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys2, ids, ids2, N, 0, (unsigned)std::min(std::max(frames[L].key_bits, 1), 63), stream));
+		sort_bytes = std::max(sort_bytes, bytes);
+	}
+	KS_TRY(hipMalloc(&tmp, std::max<size_t>(sort_bytes, 16)));
+	StatReport rep;
+	// ev_begin .. ev_end: the kernels and the read-backs; the allocations above and the frees at the end are outside
+	if (ev_begin) KS_TRY(hipEventRecord(ev_begin, stream));
+	KS_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
+	int open = n;                                              // the points no level has resolved yet
+	int *cur = listA, *nxt = listB;
+	for (int L = 0; L < levels && open > 0; L++) {
+		const VoxelFrame& f = frames[L];
+		const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+		hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
+		KS_TRY(hipGetLastError());
+		size_t bytes = sort_bytes;
+		KS_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+		KS_TRY(hipGetLastError());
+		if (L == 0) {
+			if (d_order) KS_TRY(hipMemcpyAsync(d_order, ids2, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+			const dim3 g0((n + kStatBlock - 1) / kStatBlock), b0(kStatBlock);
+			if (k <= 16) hipLaunchKernelGGL(self_knn_block_kernel<16>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], d_index, d_dist_sq, nxt, counts);
+			else hipLaunchKernelGGL(self_knn_block_kernel<32>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], d_index, d_dist_sq, nxt, counts);
+		} else {
+			hipLaunchKernelGGL(self_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, r2[L], 0,
+			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, d_index, d_dist_sq, nxt, counts + L);
+		}
+		KS_TRY(hipGetLastError());
+		int left = -1;
+		KS_TRY(hipMemcpyAsync(&left, counts + L, sizeof(int), hipMemcpyDeviceToHost, stream));
+		KS_TRY(hipStreamSynchronize(stream));
+		if (left < 0 || left > open) return hipErrorUnknown;
+		rep.resolved[L] = open - left;
+		rep.levels_run = L + 1;
+		open = left;
+		std::swap(cur, nxt);
+	}
+	if (rep.levels_run == 0) {
+		// no grid level: input order, for the top level's records and list and for the caller
+		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, ids2, n);
+		KS_TRY(hipGetLastError());
+		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, cur, n);
+		KS_TRY(hipGetLastError());
+		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+		KS_TRY(hipGetLastError());
+		if (d_order) KS_TRY(hipMemcpyAsync(d_order, ids2, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+	}
+	if (open > 0) {
+		// the top level: every point is a candidate, in any order
+		hipLaunchKernelGGL(self_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, 0.f, 1, 0.f, 0.f,
+		                   0.f, 1.f, d_index, d_dist_sq, nxt, counts + kStatMaxLevels);
+		KS_TRY(hipGetLastError());
+		rep.top = open;
+	}
+	if (ev_end) KS_TRY(hipEventRecord(ev_end, stream));
+	KS_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
+#undef KS_TRY
+	if (report) *report = rep;
+	return hipSuccess;
+}
+
+hipError_t launch_estimate_normals(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, const float* vp,
+                                   float* d_normals, float* d_variation, int32_t* d_index, StatReport* report, hipStream_t stream, hipEvent_t ev_begin,
+                                   hipEvent_t ev_end)
+{
+	if (n < 3 || !d_normals || !d_index || k < 3 || k > kKnnSelfMax || k - 1 > n - 1) return hipErrorInvalidValue;
+	int* order = nullptr;
+	struct Cleanup {
+		int*& p;
+		~Cleanup() { hipFree(p); }
+	} cleanup{order};
+	hipError_t e;
+	if ((e = hipMalloc(&order, sizeof(int) * (size_t)n)) != hipSuccess) return e;
+	// ev_begin is recorded by the search, ev_end after the PCA
+	if ((e = launch_self_knn(d_xyz, n, frames, r2, levels, k - 1, d_index, nullptr, order, report, stream, ev_begin, nullptr)) != hipSuccess) return e;
+	hipLaunchKernelGGL(normal_pca_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_xyz, d_index, order, n, k - 1, vp ? 1 : 0, vp ? vp[0] : 0.f,
+	                   vp ? vp[1] : 0.f, vp ? vp[2] : 0.f, d_normals, d_variation);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	if (ev_end && (e = hipEventRecord(ev_end, stream)) != hipSuccess) return e;
+	return hipStreamSynchronize(stream);                       // `order` is in use until here
+}
+
 // the per-axis minimum and maximum of a cloud on the device: what voxel_frame derives on the host, for a cloud that never leaves the device
 struct MinMax3 { float mn[3], mx[3]; };
 struct MinMaxOf {

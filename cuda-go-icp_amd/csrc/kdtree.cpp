@@ -626,4 +626,161 @@ void statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighb
 	*m_out = m;
 }
 
+// ---- exact self k-NN and normal estimation: what both paths share, and the host path ----
+void knn_self_check_params(size_t n, int32_t k)
+{
+	if (k < 1 || k > kKnnSelfMax) throw std::invalid_argument("goicp knn self: k must be in 1..32");
+	if (n == 0 || (size_t)k > n - 1) throw std::invalid_argument("goicp knn self: k must be at most n - 1");
+}
+
+void normals_check_params(size_t n, int32_t k, const float* vp)
+{
+	if (k < 3 || k > kKnnSelfMax) throw std::invalid_argument("goicp estimate normals: k must be in 3..32 (it counts the point itself)");
+	if (n == 0 || (size_t)(k - 1) > n - 1) throw std::invalid_argument("goicp estimate normals: k - 1 must be at most n - 1");
+	if (vp && !(std::isfinite(vp[0]) && std::isfinite(vp[1]) && std::isfinite(vp[2]))) throw std::invalid_argument("goicp estimate normals: non-finite viewpoint");
+}
+
+namespace {
+
+// the k smallest keys (bits of d2) << 32 | index of a point, kept as a max-heap of at most k keys
+struct KeyHeap {
+	uint64_t h[kKnnSelfMax];
+	int size = 0, k;
+	explicit KeyHeap(int k_) : k(k_) {}
+	void offer(float d2, int32_t j)
+	{
+		uint32_t bits;
+		std::memcpy(&bits, &d2, sizeof bits);
+		const uint64_t key = ((uint64_t)bits << 32) | (uint32_t)j;
+		if (size < k) { h[size++] = key; std::push_heap(h, h + size); }
+		else if (key < h[0]) { std::pop_heap(h, h + k); h[k - 1] = key; std::push_heap(h, h + k); }
+	}
+	static float d2_of(uint64_t key)
+	{
+		const uint32_t bits = (uint32_t)(key >> 32);
+		float d2;
+		std::memcpy(&d2, &bits, sizeof d2);
+		return d2;
+	}
+	bool within(float r2) const { return size == k && d2_of(h[0]) <= r2; }
+	// ascending by key; index (k ints) and dist_sq (k floats, may be null) are the point's own words
+	void write(int32_t* index, float* dist_sq)
+	{
+		std::sort(h, h + k);
+		for (int j = 0; j < k; j++) {
+			index[j] = (int32_t)(uint32_t)(h[j] & 0xffffffffull);
+			if (dist_sq) dist_sq[j] = d2_of(h[j]);
+		}
+	}
+};
+
+// the rows of every point: the level loop of statistical_outlier_removal_host with keys in the heap.  A point is resolved at level L when
+// it holds k keys and the d2 of its k-th key is <= r2_L (DESIGN 20 has the proof that the ties at the k-th place are then decided)
+void knn_self_rows(const float* xyz, size_t n, int k, const float mn[3], const float mx[3], int32_t* out_index, float* out_dist_sq)
+{
+	float r0 = 0.f;
+	int levels = 0;
+	{
+		const size_t ns = stat_sample_size(n), stride = n / ns;
+		std::vector<float> sample(3 * ns);
+		for (size_t i = 0; i < ns; i++) std::memcpy(&sample[3 * i], xyz + 3 * i * stride, 3 * sizeof(float));
+		stat_levels(mn, mx, n, k, sample.data(), ns, &r0, &levels);
+	}
+	std::vector<int32_t> list(n), next;
+	std::iota(list.begin(), list.end(), 0);
+	const int threads = n >= 65536 ? 8 : 1;
+	const size_t chunk = 4096;
+	struct Pt { float x, y, z; int32_t id; };
+	std::vector<uint64_t> keys;
+	std::vector<Pt> pts;
+	std::vector<std::pair<uint64_t, int32_t>> ki;
+	std::vector<unsigned char> open;
+	float r = r0;
+	for (int L = 0; L < levels && !list.empty(); L++, r *= 2.f) {
+		VoxelFrame f;
+		radius_frame_of_box(mn, mx, n, r, 1, &f);
+		const float r2 = r * r;
+		auto key_of = [&](const float* p) {
+			uint64_t key = 0;
+			for (int a = 0; a < 3; a++) key |= (uint64_t)(int)std::floor((p[a] - f.mn[a]) / f.voxel) << (21 * a);
+			return key;
+		};
+		ki.resize(n);
+		for (size_t i = 0; i < n; i++) ki[i] = {key_of(xyz + 3 * i), (int32_t)i};
+		std::sort(ki.begin(), ki.end());
+		keys.resize(n); pts.resize(n);
+		for (size_t s = 0; s < n; s++) {
+			const float* p = xyz + 3 * (size_t)ki[s].second;
+			keys[s] = ki[s].first;
+			pts[s] = {p[0], p[1], p[2], ki[s].second};
+		}
+		open.assign(list.size(), 0);
+		parallel_tasks(threads, (int)((list.size() + chunk - 1) / chunk), [&](int t) {
+			for (size_t e = (size_t)t * chunk; e < std::min(list.size(), ((size_t)t + 1) * chunk); e++) {
+				const int32_t id = list[e];
+				const float* P = xyz + 3 * (size_t)id;
+				const uint64_t K = key_of(P);
+				const int64_t cx = (int64_t)(K & 0x1fffffu), cy = (int64_t)((K >> 21) & 0x1fffffu), cz = (int64_t)(K >> 42);
+				KeyHeap H(k);
+				for (int64_t z = std::max<int64_t>(cz - 1, 0); z <= cz + 1; z++)
+					for (int64_t y = std::max<int64_t>(cy - 1, 0); y <= cy + 1; y++) {
+						const uint64_t base = ((uint64_t)z << 42) | ((uint64_t)y << 21);
+						const size_t a = std::lower_bound(keys.begin(), keys.end(), base | (uint64_t)std::max<int64_t>(cx - 1, 0)) - keys.begin();
+						const size_t b = std::upper_bound(keys.begin() + a, keys.end(), base | (uint64_t)(cx + 1)) - keys.begin();
+						for (size_t j = a; j < b; j++)
+							if (pts[j].id != id) H.offer(stat_d2(P, &pts[j].x), pts[j].id);
+					}
+				if (H.within(r2)) H.write(out_index + (size_t)id * k, out_dist_sq ? out_dist_sq + (size_t)id * k : nullptr); else open[e] = 1;
+			}
+		});
+		next.clear();
+		for (size_t e = 0; e < list.size(); e++) if (open[e]) next.push_back(list[e]);
+		list.swap(next);
+	}
+	// the top level: every point is a candidate
+	if (!list.empty())
+		parallel_tasks(threads, (int)((list.size() + 255) / 256), [&](int t) {
+			for (size_t e = (size_t)t * 256; e < std::min(list.size(), ((size_t)t + 1) * 256); e++) {
+				const int32_t id = list[e];
+				const float* P = xyz + 3 * (size_t)id;
+				KeyHeap H(k);
+				for (size_t j = 0; j < n; j++)
+					if ((int32_t)j != id) H.offer(stat_d2(P, xyz + 3 * j), (int32_t)j);
+				H.write(out_index + (size_t)id * k, out_dist_sq ? out_dist_sq + (size_t)id * k : nullptr);
+			}
+		});
+}
+
+}  // namespace
+
+void knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
+{
+	if (!out_index) throw std::invalid_argument("goicp_knn_self_host: out_index must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	knn_self_check_params(n, k);
+	knn_self_rows(xyz, n, k, mn, mx, out_index, out_dist_sq);
+}
+
+void estimate_normals_host(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index)
+{
+	if (!out_normals) throw std::invalid_argument("goicp_estimate_normals_host: out_normals must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	normals_check_params(n, k, vp);
+	const int kk = k - 1;
+	std::vector<int32_t> rows_own;
+	if (!out_index) rows_own.resize(n * (size_t)kk);
+	int32_t* rows = out_index ? out_index : rows_own.data();
+	knn_self_rows(xyz, n, kk, mn, mx, rows, nullptr);
+	const size_t chunk = 4096;
+	parallel_tasks(n >= 65536 ? 8 : 1, (int)((n + chunk - 1) / chunk), [&](int t) {
+		for (size_t i = (size_t)t * chunk; i < std::min(n, ((size_t)t + 1) * chunk); i++) {
+			float var;
+			normal_pca_point(xyz, (int)i, rows + i * (size_t)kk, kk, vp != nullptr, vp ? vp[0] : 0.f, vp ? vp[1] : 0.f, vp ? vp[2] : 0.f, out_normals + 3 * i, &var);
+			if (out_variation) out_variation[i] = var;
+		}
+	});
+}
+
 }  // namespace goicp

@@ -114,6 +114,36 @@ def statistical_outlier_removal(xyz, neighbors, std_ratio):
     return _stat_call(B.load_library().goicp_statistical_outlier_removal_host, xyz, neighbors, std_ratio)
 
 
+def _knn_self_call(fn, xyz, k):
+    xyz = _f32(xyz, (-1, 3))
+    n, k = len(xyz), int(k)
+    idx, d2 = np.empty((n, max(k, 0)), np.int32), np.empty((n, max(k, 0)), np.float32)
+    B.check(fn(_fptr(xyz), n, k, idx.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2)))
+    return idx, d2
+
+
+def knn_self(xyz, k):
+    """goicp_knn_self_host (host only): the k nearest OTHER points of every point of the cloud, exact, ascending by (d2, index) ->
+    (indices (n, k) int32, squared distances (n, k) float32).  Registration.knn_self gives the same bits on the device."""
+    return _knn_self_call(B.load_library().goicp_knn_self_host, xyz, k)
+
+
+def _normals_call(fn, xyz, k, viewpoint):
+    xyz = _f32(xyz, (-1, 3))
+    n, k = len(xyz), int(k)
+    vp = None if viewpoint is None else _f32(viewpoint, (3,))
+    nrm, var, idx = np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty((n, max(k - 1, 0)), np.int32)
+    B.check(fn(_fptr(xyz), n, k, None if vp is None else _fptr(vp), _fptr(nrm), _fptr(var), idx.ctypes.data_as(C.POINTER(C.c_int32))))
+    return nrm, var, idx
+
+
+def estimate_normals(xyz, k, viewpoint=None):
+    """goicp_estimate_normals_host (host only): per-point normals and surface variation from the k-point neighbourhood (the point itself and
+    its k - 1 nearest others), flipped towards `viewpoint` when one is given -> (normals (n, 3) float32, variation (n,) float32, the
+    neighbours used (n, k - 1) int32).  Registration.estimate_normals gives the same bits on the device."""
+    return _normals_call(B.load_library().goicp_estimate_normals_host, xyz, k, viewpoint)
+
+
 def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None):
     """the composition of the host functions that goicp_set_source_filtered and goicp_set_source_pipeline equal"""
     if voxel:
@@ -348,6 +378,15 @@ class Registration:
         """goicp_statistical_outlier_removal: the module-level statistical_outlier_removal on the device (the handle lends its device and
         stream, its state is untouched) -> (cloud (m, 3) float32, indices (m,) int32, mean distances (n,) float32, threshold), the same bits"""
         return _stat_call(lambda *a: self._lib.goicp_statistical_outlier_removal(self.handle, *a), xyz, neighbors, std_ratio)
+
+    def knn_self(self, xyz, k):
+        """goicp_knn_self: the module-level knn_self on the device (the handle lends its device and stream, its state is untouched)"""
+        return _knn_self_call(lambda *a: self._lib.goicp_knn_self(self.handle, *a), xyz, k)
+
+    def estimate_normals(self, xyz, k, viewpoint=None):
+        """goicp_estimate_normals: the module-level estimate_normals on the device (the handle lends its device and stream, its state is
+        untouched)"""
+        return _normals_call(lambda *a: self._lib.goicp_estimate_normals(self.handle, *a), xyz, k, viewpoint)
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""

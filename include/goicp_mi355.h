@@ -343,6 +343,56 @@ int goicp_statistical_outlier_removal(goicp_handle h, const float* xyz, size_t n
 typedef struct goicp_source_pipeline { float voxel; int32_t stat_neighbors; float stat_std_ratio; float radius; int32_t min_neighbors; } goicp_source_pipeline;
 void goicp_source_pipeline_default(goicp_source_pipeline* out);   /* all 0 = no stage */
 int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, size_t* n_kept);
+/*
+ * Exact self k-NN and normal estimation for any cloud (PCL's NormalEstimation with setKSearch and setViewPoint, Open3D's estimate_normals
+ * with KDTreeSearchParamKNN plus orient_normals_towards_camera_location).  Each operator has a host function, a device function and a
+ * numpy twin that produce the same bits.  Arithmetic is IEEE, nothing fused.
+ *
+ * Self k-NN: for every point i of the n points, its k nearest OTHER points.
+ *   pair    the statistical filter's float expression: dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j, d2 = dx*dx + dy*dy + dz*dz evaluated
+ *           left to right.  A duplicate of a point is its neighbour at distance 0, a point is never its own neighbour;
+ *   order   by the 64-bit key ((uint64)bits of d2 << 32) | j, ascending: d2 >= 0, so this is (d2, index) order, a total order -- ties at the
+ *           k-th place go to the smaller index (goicp_knn_query's rule; unlike the statistical filter's multiset, which tied point is
+ *           taken shows here);
+ *   output  out_index: n x k int32, row i = the k smallest keys' indices, ascending by key; out_dist_sq (may be NULL): n x k floats, their d2.
+ * The definition names no grid and nothing about the cloud's extent is refused: the implementations search grids of doubling pitch that
+ * only select candidates.
+ * GOICP_ERR_INVALID, nothing written: NULL arguments, n == 0 or above goicp_create's limit, a non-finite coordinate, k outside
+ * 1..GOICP_KNN_SELF_MAX or above n - 1, and for the handle form any call while a registration runs.
+ *
+ * Normals: k in 3..GOICP_KNN_SELF_MAX counts the point itself (as goicp_icp_options.normal_k does), k - 1 <= n - 1; vp (may be NULL) is a
+ * viewpoint.  The neighbourhood of i is i itself followed by its k - 1 nearest others in key order (the self k-NN at k - 1).  Everything
+ * below is fp64, each operation rounded once, and uses only + - * / sqrt (and negation, comparisons, |.|):
+ *   offsets e_j = (double)x_j - (double)x_i per component; e_0 = (0, 0, 0) is the point's own.  Offsets from the point keep every error
+ *           relative to the neighbourhood's size, not to |x|;
+ *   mean    m = (sum of e_j) / (double)k, the sum added sequentially in neighbourhood order from 0;
+ *   cov     d_j = e_j - m; the six entries C_ab = sum over j of d_ja * d_jb, each product rounded, added sequentially in the same order
+ *           from 0;
+ *   eigen   cyclic Jacobi on the full 3 x 3 matrix A = C with V = I, the pairs (p, q) = (0,1), (0,2), (1,2) per sweep.  A pair is skipped
+ *           when apq == 0 or apq*apq <= 1e-24 * |app*aqq| (apq = A[p][q]).  Otherwise da = aqq - app, db = apq + apq,
+ *           tn = (da >= 0 ? db : -db) / (|da| + sqrt(da*da + db*db)), cs = 1 / sqrt(1 + tn*tn), sn = cs * tn, and for r = 0, 1, 2 in turn:
+ *           columns (A[r][p], A[r][q]) <- (cs*A[r][p] - sn*A[r][q], sn*A[r][p] + cs*A[r][q]), then rows
+ *           (A[p][r], A[q][r]) <- (cs*A[p][r] - sn*A[q][r], sn*A[p][r] + cs*A[q][r]), then the columns of V as those of A.  The
+ *           iteration stops after a sweep that skipped all three pairs, or after 32 sweeps;
+ *   normal  l_c = A[c][c].  The column of V with the smallest l_c, the lowest c on equal values: v.  len = sqrt((v0*v0 + v1*v1) + v2*v2),
+ *           n_c = (float)(v_c / len);
+ *   flat    with a <= b <= c the three l sorted: c <= 0 (every neighbour coincides with the point) gives normal (0, 0, 0), variation 0;
+ *   variation  (float)((a > 0 ? a : 0) / ((a + b) + c)): PCL's curvature, in [0, 1/3];
+ *   sign    on the float normal.  With a viewpoint, d = ((double)n_0 * ((double)vp_0 - (double)x_i0) + (double)n_1 * (...)) + (double)n_2 * (...);
+ *           d < 0 negates the normal.  With no viewpoint or d == 0, the normal is negated when its first non-zero component is negative.
+ *           A zero component is written as +0;
+ *   output  out_normals: n x 3 floats in input order; out_variation (may be NULL): n floats; out_index (may be NULL): n x (k - 1) int32,
+ *           the neighbours used.
+ * GOICP_ERR_INVALID, nothing written: what the self k-NN refuses of the cloud, k outside 3..GOICP_KNN_SELF_MAX, k - 1 > n - 1, a
+ * non-finite viewpoint, and for the handle form any call while a registration runs.
+ * The _host forms run on the host alone (no handle, no GPU).  The handle forms run on the device: the handle lends its device and stream,
+ * its state is untouched.
+ */
+#define GOICP_KNN_SELF_MAX 32
+int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
+int goicp_knn_self(goicp_handle h, const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
+int goicp_estimate_normals_host(const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
+int goicp_estimate_normals(goicp_handle h, const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

@@ -247,6 +247,28 @@ public:
 		ns_ = kept;
 		return kept;
 	}
+	// the exact k nearest other points of every point of any cloud, on the device (goicp_knn_self): index gets n x k entries, row i ascending
+	// by (squared distance, index); dist_sq (may be null) their squared distances.  The registration lends its device, its state is untouched
+	template <class Point3>
+	void knn_self(const std::vector<Point3>& cloud, size_t n, int k, std::vector<int32_t>& index, std::vector<float>* dist_sq = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		index.resize(k > 0 ? n * (size_t)k : 0);
+		if (dist_sq) dist_sq->resize(index.size());
+		check(goicp_knn_self(h_, reinterpret_cast<const float*>(cloud.data()), n, (int32_t)k, index.data(), dist_sq ? dist_sq->data() : nullptr));
+	}
+	// per-point normals of any cloud, on the device (goicp_estimate_normals): the k-point neighbourhood counts the point itself; viewpoint (may
+	// be null) flips every normal towards it; variation (may be null) gets the surface variation (PCL's curvature) of every point
+	template <class Point3>
+	void estimate_normals(const std::vector<Point3>& cloud, size_t n, int k, const float* viewpoint, std::vector<Point3>& normals,
+	                      std::vector<float>* variation = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		normals.resize(n);
+		if (variation) variation->resize(n);
+		check(goicp_estimate_normals(h_, reinterpret_cast<const float*>(cloud.data()), n, (int32_t)k, viewpoint, reinterpret_cast<float*>(normals.data()),
+		                             variation ? variation->data() : nullptr, nullptr));
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
