@@ -10,7 +10,7 @@ missing.
 from . import binding  # noqa: F401
 from .binding import GoicpError, build_library, library_path, load_library  # noqa: F401
 from .fgoicp import (Config, FastGoICP, IterativeClosestPoint3D, Registration, RotNode, TransNode,  # noqa: F401
-                     estimate_normals, knn_self, load_cloud, radius_outlier_removal, source_order, statistical_outlier_removal,
+                     cluster, cluster_filter, estimate_normals, knn_self, load_cloud, radius_outlier_removal, source_order, statistical_outlier_removal,
                      voxel_downsample)
 
 

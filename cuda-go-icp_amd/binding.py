@@ -100,6 +100,10 @@ class CSourcePipeline(C.Structure):
     _fields_ = [("voxel", C.c_float), ("stat_neighbors", C.c_int32), ("stat_std_ratio", C.c_float), ("radius", C.c_float), ("min_neighbors", C.c_int32)]
 
 
+class CClusterSelect(C.Structure):
+    _fields_ = [("radius", C.c_float), ("min_neighbors", C.c_int32), ("min_size", C.c_int32), ("max_clusters", C.c_int32)]
+
+
 class CPoseInfoOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
 
@@ -208,6 +212,14 @@ SYMBOLS = {
                                                    C.POINTER(C.c_size_t)]),
     "goicp_source_pipeline_default": (None, [C.POINTER(CSourcePipeline)]),
     "goicp_set_source_pipeline": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(C.c_size_t)]),
+    "goicp_cluster_host": (C.c_int, [_fp, C.c_size_t, C.c_float, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "goicp_cluster": (C.c_int, [_vp, _fp, C.c_size_t, C.c_float, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "goicp_cluster_select_default": (None, [C.POINTER(CClusterSelect)]),
+    "goicp_cluster_filter_host": (C.c_int, [_fp, C.c_size_t, C.POINTER(CClusterSelect), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_size_t)]),
+    "goicp_cluster_filter": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CClusterSelect), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_size_t)]),
+    "goicp_set_source_clustered": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(CClusterSelect), C.POINTER(C.c_size_t)]),
     "goicp_knn_self_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_knn_self": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_estimate_normals_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),

@@ -52,6 +52,14 @@
 //               (goicp_statistical_outlier_removal_host), every listed cloud on the device as part of its swap (goicp_set_source_pipeline:
 //               the same bits); each prints "kept m of n".  --target-stat-neighbors K --target-stat-std-ratio A filter the target the same
 //               way, on the host.  K must be an integer in 1..64, A a finite number >= 0 -- refused before any device is touched
+//   --cluster-radius R [--cluster-min-neighbors K] [--cluster-min-size S] [--cluster-keep C]   Euclidean / DBSCAN clustering, after the other
+//               filters: the points of the source -- and of every cloud of --source-list -- are grouped into the connected components of
+//               the core points under distance R (a point is core with at least K other points within R; K = 0, the default, makes every
+//               point core), and only the C largest clusters (default 1; 0 = all) with at least S members (default 0) stay.  The config's
+//               own source is filtered on the host (goicp_cluster_filter_host), every listed cloud on the device as part of its swap
+//               (goicp_set_source_clustered: the same bits); each prints "kept m of n".  The --target-cluster-* forms filter the target the
+//               same way, on the host, before the engine is created.  R must be finite, > 0 and R * R a normal float, K, S and C integers
+//               >= 0, and the three need --cluster-radius -- refused before any device is touched
 //   --estimate-normals IN OUT.ply [--normal-k K] [--viewpoint X,Y,Z]   a mode of its own that takes no config and registers nothing: per-point
 //               normals and surface variation of the cloud IN from its K-point neighbourhoods (K counts the point itself, 3..32, default 16;
 //               goicp_estimate_normals on the device when there is one, goicp_estimate_normals_host otherwise: the same bits), flipped
@@ -212,6 +220,9 @@ int main(int argc, char** argv)
 	const char *sk_arg[2] = {nullptr, nullptr}, *sa_arg[2] = {nullptr, nullptr};       // statistical filter: [0] the source's, [1] the target's
 	int stat_k[2] = {0, 0};
 	float stat_ratio[2] = {0.f, 0.f};
+	const char* cl_arg[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // radius, min-neighbors, min-size, keep
+	goicp_cluster_select cluster[2];                                                                        // [0] the source's, [1] the target's
+	for (int k = 0; k < 2; k++) goicp_cluster_select_default(&cluster[k]);
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -238,6 +249,12 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--stat-std-ratio")) sa_arg[0] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-neighbors")) sk_arg[1] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-std-ratio")) sa_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else {
+			static const char* const cl_names[2][4] = {{"--cluster-radius", "--cluster-min-neighbors", "--cluster-min-size", "--cluster-keep"},
+			                                           {"--target-cluster-radius", "--target-cluster-min-neighbors", "--target-cluster-min-size", "--target-cluster-keep"}};
+			for (int q = 0; q < 8; q++)
+				if (!std::strcmp(argv[i], cl_names[q / 4][q % 4])) { cl_arg[q / 4][q % 4] = i + 1 < argc ? argv[++i] : ""; break; }
+		}
 	}
 	for (int k = 0; k < 2; k++) {
 		// a bad voxel is refused before any device is touched
@@ -295,6 +312,34 @@ int main(int argc, char** argv)
 		}
 		stat_k[k] = (int)kk;
 		stat_ratio[k] = a;
+	}
+	for (int k = 0; k < 2; k++) {
+		// a bad cluster selection is refused before any device is touched
+		const char* pre = k ? "--target-cluster" : "--cluster";
+		if (!cl_arg[k][0] && !cl_arg[k][1] && !cl_arg[k][2] && !cl_arg[k][3]) continue;
+		if (!cl_arg[k][0]) {
+			std::fprintf(stderr, "error: %s-min-neighbors, %s-min-size and %s-keep need %s-radius\n", pre, pre, pre, pre);
+			return 2;
+		}
+		char* end = nullptr;
+		const float r = std::strtof(cl_arg[k][0], &end);
+		const float r2 = r * r;
+		if (end == cl_arg[k][0] || *end != '\0' || !(r > 0.f) || !(r2 >= 1.17549435e-38f) || !(r2 <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: %s-radius needs a finite radius > 0 whose square is a normal float, got '%s'\n", pre, cl_arg[k][0]);
+			return 2;
+		}
+		static const char* const what[4] = {"radius", "min-neighbors", "min-size", "keep"};
+		long v[4] = {0, 0, 0, 1};                                   // the defaults: every point is core, any size, the largest cluster
+		for (int a = 1; a < 4; a++) {
+			if (!cl_arg[k][a]) continue;
+			v[a] = std::strtol(cl_arg[k][a], &end, 10);
+			if (end == cl_arg[k][a] || *end != '\0' || v[a] < 0 || v[a] > 2147483647L) {
+				std::fprintf(stderr, "error: %s-%s needs an integer >= 0, got '%s'\n", pre, what[a], cl_arg[k][a]);
+				return 2;
+			}
+		}
+		cluster[k].radius = r;
+		cluster[k].min_neighbors = (int32_t)v[1]; cluster[k].min_size = (int32_t)v[2]; cluster[k].max_clusters = (int32_t)v[3];
 	}
 	if (list_arg) {
 		// refused before any device is touched
@@ -433,6 +478,19 @@ int main(int argc, char** argv)
 			if (m == 0) throw std::runtime_error(std::string(k ? "target" : "source") + ": the outlier filter keeps no point");
 			cloud.swap(kept);
 		}
+		for (int k = 0; k < 2; k++) {
+			// after every other filter; the host function again
+			std::vector<P3>& cloud = k ? target : source;
+			if (!(cluster[k].radius > 0.f) || cloud.empty()) continue;
+			std::vector<P3> kept(cloud.size());
+			size_t m = 0;
+			check(goicp_cluster_filter_host(&cloud[0].x, cloud.size(), &cluster[k], &kept[0].x, nullptr, nullptr, &m));
+			kept.resize(m);
+			std::printf("%s cluster radius %g min neighbors %d min size %d keep %d: kept %zu of %zu points\n", k ? "target" : "source", cluster[k].radius,
+			            (int)cluster[k].min_neighbors, (int)cluster[k].min_size, (int)cluster[k].max_clusters, m, cloud.size());
+			if (m == 0) throw std::runtime_error(std::string(k ? "target" : "source") + ": the cluster selection keeps no point");
+			cloud.swap(kept);
+		}
 		std::printf("mode %d: source %zu points, target %zu points, mse_threshold %g\n", config.mode, source.size(),
 		            target.size(), config.mse_threshold);
 		goicp_params p;
@@ -541,7 +599,15 @@ int main(int argc, char** argv)
 			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
 			const auto t0 = std::chrono::steady_clock::now();
 			size_t kept = next.size();
-			if (stat_k[0] > 0) {
+			if (cluster[0].radius > 0.f) {
+				goicp_source_pipeline sp;
+				goicp_source_pipeline_default(&sp);
+				sp.voxel = voxel; sp.stat_neighbors = stat_k[0]; sp.stat_std_ratio = stat_ratio[0];
+				sp.radius = outlier_radius[0]; sp.min_neighbors = outlier_min[0];
+				kept = engine.set_source(next, &sp, cluster[0]);
+				std::printf("source %zu cluster radius %g min neighbors %d min size %d keep %d: kept %zu of %zu points\n", k + 1, cluster[0].radius,
+				            (int)cluster[0].min_neighbors, (int)cluster[0].min_size, (int)cluster[0].max_clusters, kept, next.size());
+			} else if (stat_k[0] > 0) {
 				goicp_source_pipeline sp;
 				goicp_source_pipeline_default(&sp);
 				sp.voxel = voxel; sp.stat_neighbors = stat_k[0]; sp.stat_std_ratio = stat_ratio[0];

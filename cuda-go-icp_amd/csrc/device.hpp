@@ -451,6 +451,16 @@ hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& 
 // ev_begin / ev_end (may be null) are recorded around the kernels and the read-back of m.  Returns after the stream has drained
 hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, float* d_out, int32_t* d_index,
                                          int32_t* d_count, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// ---- Euclidean / DBSCAN clustering on the device (kdbuild.hip; goicp_cluster_host is its host twin) ----
+// f: the radius filter's frame (cluster_frame, kdtree.cpp); r2 = r * r in float; min_neighbors >= 0 (0: every point is core).  d_label: n
+// ints, the cluster of every point, -1 for noise; d_sizes: room for n ints, the first *c are the clusters' sizes (the rest is zero); *c may
+// be 0.  ev_begin / ev_end (may be null) are recorded around the kernels and the read-back of c.  Returns after the stream has drained
+hipError_t launch_cluster(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, int32_t* d_label, int32_t* d_sizes, int* c,
+                          hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+// the points whose cluster l has d_keep[l] != 0 (c ints on the device), in input order: d_out room for 3 n floats, d_index and d_out_label
+// (each may be null) room for n ints, the first *m written; *m may be 0.  Returns after the stream has drained
+hipError_t launch_cluster_compact(const float* d_xyz, int n, const int32_t* d_label, const int32_t* d_keep, float* d_out, int32_t* d_index,
+                                  int32_t* d_out_label, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 // ---- statistical outlier removal on the device (kdbuild.hip; goicp_statistical_outlier_removal_host is its host twin) ----
 constexpr int kStatMaxLevels = 48;
 // what a run did: the grid levels that ran, the points each resolved, and the points left to the top level (all points as candidates)

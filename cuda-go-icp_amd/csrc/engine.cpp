@@ -872,6 +872,194 @@ void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_
 	}
 }
 
+void Engine::cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters)
+{
+	if (!out_label || !n_clusters) throw std::invalid_argument("goicp_cluster: out_label and n_clusters must be non-null");
+	VoxelFrame f;
+	cluster_frame(xyz, n, radius, min_neighbors, &f);
+	if (registering_.load()) throw std::invalid_argument("goicp_cluster: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz(3 * n);
+	Buf<int32_t> d_label(n), d_sizes(n);
+	int c = 0;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_cluster(d_xyz, (int)n, f, radius * radius, min_neighbors, d_label, d_sizes, &c, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_label, d_label, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+	if (out_sizes && c > 0) HIPCHK(hipMemcpyAsync(out_sizes, d_sizes, sizeof(int32_t) * (size_t)c, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	*n_clusters = (size_t)c;
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		std::fprintf(stderr, "[goicp] cluster: %zu points, %d clusters, device %.3f ms\n", n, c, ms);
+	}
+}
+
+namespace {
+
+// the cluster selection of a cloud on the device: launch_cluster, the c sizes to the host, cluster_select there, the c keep flags back and
+// the compaction.  d_out: room for 3 n floats; d_index / d_out_label may be null.  ms (may be null): the device time of both launchers
+void cluster_filter_device(const float* d_in, int n, const VoxelFrame& f, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters,
+                           float* d_out, int32_t* d_index, int32_t* d_out_label, int* m, int* c_out, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                           float* ms)
+{
+	Buf<int32_t> d_label((size_t)n), d_sizes((size_t)n);
+	int c = 0;
+	float ms0 = 0.f, ms1 = 0.f;
+	HIPCHK(launch_cluster(d_in, n, f, radius * radius, min_neighbors, d_label, d_sizes, &c, stream, ev0, ev1));
+	HIPCHK(hipEventElapsedTime(&ms0, ev0, ev1));
+	*m = 0;
+	if (c_out) *c_out = c;
+	if (c > 0) {
+		std::vector<int32_t> sizes((size_t)c), keep;
+		HIPCHK(hipMemcpyAsync(sizes.data(), d_sizes, sizeof(int32_t) * (size_t)c, hipMemcpyDeviceToHost, stream));
+		HIPCHK(hipStreamSynchronize(stream));
+		cluster_select(sizes.data(), (size_t)c, min_size, max_clusters, &keep);
+		// the keep flags take the sizes' place
+		HIPCHK(hipMemcpyAsync(d_sizes, keep.data(), sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, stream));
+		HIPCHK(launch_cluster_compact(d_in, n, d_label, d_sizes, d_out, d_index, d_out_label, m, stream, ev0, ev1));
+		HIPCHK(hipEventElapsedTime(&ms1, ev0, ev1));
+	}
+	if (ms) *ms = ms0 + ms1;
+}
+
+}  // namespace
+
+void Engine::cluster_filter(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
+                            int32_t* out_index, int32_t* out_label, size_t* m_out)
+{
+	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_cluster_filter: out_xyz and m must be non-null");
+	cluster_check_select(min_size, max_clusters);
+	VoxelFrame f;
+	cluster_frame(xyz, n, radius, min_neighbors, &f);
+	if (registering_.load()) throw std::invalid_argument("goicp_cluster_filter: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<int32_t> d_idx(out_index ? n : 0), d_lab(out_label ? n : 0);
+	int m = 0, c = 0;
+	float ms = 0.f;
+	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	cluster_filter_device(d_xyz, (int)n, f, radius, min_neighbors, min_size, max_clusters, d_out, out_index ? d_idx.get() : nullptr,
+	                      out_label ? d_lab.get() : nullptr, &m, &c, stream_, ev0_, ev1_, &ms);
+	if (m > 0) HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_index && m > 0) HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_label && m > 0) HIPCHK(hipMemcpyAsync(out_label, d_lab, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	*m_out = (size_t)m;
+	if (p_.verbose) std::fprintf(stderr, "[goicp] cluster_filter: %zu -> %d points of %d clusters, device %.3f ms\n", n, m, c, ms);
+}
+
+void Engine::set_source_clustered(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
+                                  float cluster_radius, int32_t cluster_min_neighbors, int32_t cluster_min_size, int32_t cluster_max_clusters, size_t* n_kept)
+{
+	if (std::isnan(cluster_radius) || cluster_radius < 0.f) throw std::invalid_argument("goicp_set_source_clustered: the cluster radius must be 0 (no stage) or a radius > 0");
+	if (cluster_min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
+	cluster_check_select(cluster_min_size, cluster_max_clusters);
+	if (!(cluster_radius > 0.f)) {
+		// no cluster stage: the three-stage swap, bit for bit
+		set_source_pipeline(xyz, n, voxel, stat_neighbors, stat_std_ratio, radius, min_neighbors, n_kept);
+		return;
+	}
+	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_clustered: voxel must be 0 (no stage) or a voxel size > 0");
+	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_clustered: radius must be 0 (no stage) or a radius > 0");
+	if (stat_neighbors < 0) throw std::invalid_argument("goicp_set_source_clustered: stat_neighbors must be 0 (no stage) or in 1..64");
+	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows.  The
+	// first stage that runs checks the raw cloud; what a later stage can only refuse of its own input is refused when that input exists,
+	// still before the swap
+	const bool has_voxel = voxel > 0.f, has_stat = stat_neighbors > 0, has_radius = radius > 0.f;
+	VoxelFrame fv, fr, fc;
+	float mn[3], mx[3];
+	if (has_voxel) voxel_frame(xyz, n, voxel, &fv);
+	else if (has_stat) stat_check_cloud(xyz, n, mn, mx);
+	else if (has_radius) radius_frame(xyz, n, radius, min_neighbors, &fr);
+	else cluster_frame(xyz, n, cluster_radius, cluster_min_neighbors, &fc);
+	if (has_stat) stat_check_params(has_voxel ? 65 : n, stat_neighbors, stat_std_ratio);
+	if (has_radius) {
+		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
+	}
+	if (!std::isfinite(cluster_radius) || !std::isnormal(cluster_radius * cluster_radius))
+		throw std::invalid_argument("goicp cluster: the radius must be finite and radius * radius a normal float");
+	if (registering_.load()) throw std::invalid_argument("goicp_set_source_clustered: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const double t0 = now_ms();
+	TraceRange tr("goicp:set_source_clustered");
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
+	Buf<float> d_raw(3 * n), d_red(has_voxel ? 3 * n : 0);
+	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	const float* d_in = d_raw;
+	int n_in = (int)n;
+	bool first = true;                                          // d_in is still the raw cloud, whose frame the host has
+	float voxel_ms = 0.f, stat_ms = 0.f, outlier_ms = 0.f, cluster_ms = 0.f;
+	if (has_voxel) {
+		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&voxel_ms, ev0_, ev1_));
+		d_in = d_red;
+		first = false;
+	}
+	const int n_voxel = n_in;
+	Buf<float> d_stat(has_stat ? 3 * (size_t)n_in : 0);
+	if (has_stat) {
+		std::vector<float> sample;
+		if (!first) {
+			stat_check_params((size_t)n_in, stat_neighbors, stat_std_ratio);
+			HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+			const size_t ns = stat_sample_size((size_t)n_in), stride = (size_t)n_in / ns;
+			sample.resize(3 * ns);
+			HIPCHK(hipMemcpy2DAsync(sample.data(), 3 * sizeof(float), d_in, 3 * sizeof(float) * stride, 3 * sizeof(float), ns, hipMemcpyDeviceToHost, stream_));
+			HIPCHK(hipStreamSynchronize(stream_));
+		} else {
+			sample = stat_sample_host(xyz, n);
+		}
+		const StatPlan plan(mn, mx, (size_t)n_in, stat_neighbors, sample);
+		StatReport rep;
+		int m = 0;
+		HIPCHK(launch_stat_outlier_removal(d_in, n_in, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), stat_neighbors, stat_std_ratio, d_stat,
+		                                   nullptr, nullptr, nullptr, &m, &rep, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&stat_ms, ev0_, ev1_));
+		d_in = d_stat;
+		n_in = m;
+		first = false;
+	}
+	const int n_stat = n_in;
+	Buf<float> d_rad(has_radius ? 3 * (size_t)n_in : 0);
+	if (has_radius) {
+		if (!first) {
+			HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+			radius_frame_of_box(mn, mx, (size_t)n_in, radius, min_neighbors, &fr);
+		}
+		int m = 0;
+		HIPCHK(launch_radius_outlier_removal(d_in, n_in, fr, radius * radius, min_neighbors, d_rad, nullptr, nullptr, &m, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&outlier_ms, ev0_, ev1_));
+		if (m < 1) throw std::invalid_argument("goicp_set_source_clustered: the chain keeps no point");
+		d_in = d_rad;
+		n_in = m;
+		first = false;
+	}
+	const int n_radius = n_in;
+	if (!first) {
+		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+		cluster_frame_of_box(mn, mx, (size_t)n_in, cluster_radius, cluster_min_neighbors, &fc);
+	}
+	Buf<float> d_kept(3 * (size_t)n_in);
+	int m = 0, c = 0;
+	cluster_filter_device(d_in, n_in, fc, cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_max_clusters, d_kept, nullptr, nullptr, &m, &c,
+	                      stream_, ev0_, ev1_, &cluster_ms);
+	if (m < 1) throw std::invalid_argument("goicp_set_source_clustered: the selection keeps no point");
+	std::vector<float> kept(3 * (size_t)m);
+	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (has_voxel) voxel_ms_ = voxel_ms;
+	if (has_radius) outlier_ms_ = outlier_ms;
+	load_source(kept.data(), (size_t)m, true, d_kept);
+	finish_source_swap();
+	if (n_kept) *n_kept = (size_t)m;
+	if (p_.verbose)
+		std::fprintf(stderr, "[goicp] set_source_clustered: %zu -> %d -> %d -> %d -> %zu points of %d clusters, %.2f ms (device voxel %.3f ms, device statistical %.3f ms, device outlier %.3f ms, device cluster %.3f ms, device order %.3f ms)\n",
+		             n, n_voxel, n_stat, n_radius, N_, c, now_ms() - t0, voxel_ms, stat_ms, outlier_ms, cluster_ms, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
+}
+
 void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)
 {
 	if (!perm) throw std::invalid_argument("goicp_debug_source_order: perm must be non-null");

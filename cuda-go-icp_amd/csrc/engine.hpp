@@ -300,6 +300,15 @@ public:
 	// launch_estimate_normals); as statistical_outlier_removal, the engine lends its device and stream and nothing else
 	void knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
 	void estimate_normals(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index);
+	// goicp_cluster / goicp_cluster_filter: Euclidean / DBSCAN clustering and the cluster selection on the device (kdbuild.hip launch_cluster /
+	// launch_cluster_compact; the selection itself runs on the host over the c sizes); the engine lends its device and stream and nothing else
+	void cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
+	void cluster_filter(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
+	                    int32_t* out_index, int32_t* out_label, size_t* m);
+	// goicp_set_source_clustered: set_source_pipeline's stages, then the cluster selection (cluster_radius > 0), then the swap, chained on the
+	// device behind one upload.  With the cluster stage off it is set_source_pipeline.  A selection that keeps nothing is refused
+	void set_source_clustered(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
+	                          float cluster_radius, int32_t cluster_min_neighbors, int32_t cluster_min_size, int32_t cluster_max_clusters, size_t* n_kept);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -564,6 +573,17 @@ void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbor
 void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
                                  int32_t* out_count, size_t* m);
+// Euclidean / DBSCAN clustering (kdtree.cpp).  cluster_frame / cluster_frame_of_box are radius_frame / radius_frame_of_box with
+// min_neighbors == 0 legal and a negative one refused; cluster_check_select refuses a negative min_size or max_clusters; cluster_select is
+// the selection over the c sizes that both paths share (keep[l] = 1 or 0).  cluster_host / cluster_filter_host are goicp_cluster_host /
+// goicp_cluster_filter_host
+void cluster_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
+void cluster_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
+void cluster_check_select(int32_t min_size, int32_t max_clusters);
+void cluster_select(const int32_t* sizes, size_t c, int32_t min_size, int32_t max_clusters, std::vector<int32_t>* keep);
+void cluster_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
+void cluster_filter_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
+                         int32_t* out_index, int32_t* out_label, size_t* m);
 // statistical outlier removal (kdtree.cpp).  stat_check_params refuses neighbors outside 1..64 or above n - 1 and a std_ratio that
 // is negative, NaN or infinite; stat_check_cloud what voxel_frame refuses of a cloud, and returns its per-axis bounds.  stat_levels is the
 // plan both paths search by: r0 (0 = no grid level, the top level alone) and the number of grid levels at radii r0 * 2^L, fixed in advance

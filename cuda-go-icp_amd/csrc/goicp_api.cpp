@@ -271,6 +271,54 @@ int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const 
 	return guarded([&] { h->e->set_source_pipeline(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, n_kept); });
 }
 
+int goicp_cluster_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters)
+{
+	REQUIRE(xyz && out_label && n_clusters && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::cluster_host(xyz, n, radius, min_neighbors, out_label, out_sizes, n_clusters); });
+}
+
+int goicp_cluster(goicp_handle h, const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters)
+{
+	REQUIRE(h && xyz && out_label && n_clusters && n > 0);
+	return guarded([&] { h->e->cluster(xyz, n, radius, min_neighbors, out_label, out_sizes, n_clusters); });
+}
+
+void goicp_cluster_select_default(goicp_cluster_select* out)
+{
+	if (!out) return;
+	out->radius = 0.f;
+	out->min_neighbors = 0;
+	out->min_size = 0;
+	out->max_clusters = 0;
+}
+
+int goicp_cluster_filter_host(const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label, size_t* m)
+{
+	REQUIRE(xyz && s && out_xyz && m && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::cluster_filter_host(xyz, n, s->radius, s->min_neighbors, s->min_size, s->max_clusters, out_xyz, out_index, out_label, m); });
+}
+
+int goicp_cluster_filter(goicp_handle h, const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label,
+                         size_t* m)
+{
+	REQUIRE(h && xyz && s && out_xyz && m && n > 0);
+	return guarded([&] { h->e->cluster_filter(xyz, n, s->radius, s->min_neighbors, s->min_size, s->max_clusters, out_xyz, out_index, out_label, m); });
+}
+
+int goicp_set_source_clustered(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_cluster_select* s, size_t* n_kept)
+{
+	REQUIRE(h && xyz && s && n > 0);
+	goicp_source_pipeline none;
+	goicp_source_pipeline_default(&none);
+	if (!p) p = &none;
+	return guarded([&] {
+		h->e->set_source_clustered(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, s->radius, s->min_neighbors, s->min_size,
+		                           s->max_clusters, n_kept);
+	});
+}
+
 int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
 {
 	REQUIRE(xyz && out_index && n > 0);

@@ -645,6 +645,333 @@ hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelF
 }
 
 // ------------------------------------------------------------------------------------------------
+// Euclidean / DBSCAN clustering on the device (host twin: cluster_host, kdtree.cpp).  The radius filter's keys, sort, records and
+// count kernel give the core flag; new are the component kernel (a single-pass lock-free union-find over the core pairs), the flatten
+// kernel, the border kernel and the relabelling.  parent[] is indexed by input index and only ever holds parent[v] <= v: a hook puts the
+// larger root under the smaller one and path halving replaces a parent by an ancestor, which is smaller still.  So every tree's root is
+// its smallest index, and once every core pair within r has been united the root of a component is its smallest core index, whatever
+// the order in which the workgroups ran.
+// ------------------------------------------------------------------------------------------------
+constexpr int kClBlock = 256;                                  // the count kernel's span and tile
+
+__global__ void cl_init_kernel(int* __restrict__ parent, int* __restrict__ core, int n, int all_core)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	parent[i] = i;
+	if (all_core) core[i] = 1;
+}
+
+// a parent word as the L2 holds it.  A stale value would do no harm either: a former parent of v stays an ancestor of v for good
+__device__ __forceinline__ int cl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The root of x's tree as far as this thread can see, with path halving.  Terminates: parent[v] <= v holds for every word at every moment
+// and a non-root's parent is strictly smaller, so x strictly decreases from one iteration to the next, whatever other threads write
+// meanwhile: at most x iterations.  atomicMin keeps every word monotone (g is an ancestor of x, and so is whatever the word holds)
+__device__ __forceinline__ int cl_find(int* parent, int x)
+{
+	for (;;) {
+		const int p = cl_load(parent + x);
+		if (p == x) return x;
+		const int g = cl_load(parent + p);
+		if (g != p) atomicMin(parent + x, g);
+		x = g;
+	}
+}
+
+// Unite the trees of a and b: the larger root is hooked under the smaller by a compare-and-swap that succeeds only while the larger is
+// still a root.  b < a cannot lie in a's tree when a is a root (its descendants are larger), so no hook closes a cycle.  Terminates: a
+// failed swap returns the word's value old < a (somebody else hooked a), and the next round starts from old and from b' <= b < a, so
+// max(a, b) strictly decreases from one round to the next: at most max(a, b) rounds.  Nothing here waits for another thread
+__device__ __forceinline__ void cl_unite(int* parent, int a, int b)
+{
+	for (;;) {
+		a = cl_find(parent, a);
+		b = cl_find(parent, b);
+		if (a == b) return;
+		if (a < b) { const int t = a; a = b; b = t; }
+		const int old = atomicCAS(parent + a, a, b);
+		if (old == a) return;
+		a = old;
+	}
+}
+
+// what the component and the border kernel share with ror_count_kernel: the 9 disjoint candidate intervals of the workgroup's span
+__device__ __forceinline__ void cl_intervals(const unsigned long long* __restrict__ keys, int n, int first, int last, int* iv_lo, int* iv_hi)
+{
+	const int tid = threadIdx.x;
+	if (tid < 9) {
+		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
+		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
+		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
+	}
+	__syncthreads();
+	if (tid == 0)
+		for (int o = 1; o < 9; o++) {
+			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
+			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
+		}
+	__syncthreads();
+}
+
+__device__ __forceinline__ bool cl_tile_meets(long long K, long long ta, long long tb)
+{
+	bool need = false;
+	for (int q = 0; q < 9; q++) {
+		const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
+		need = need || (c - 1 <= tb && c + 1 >= ta);
+	}
+	return need;
+}
+
+// The count kernel's shape: a workgroup owns kClBlock consecutive SORTED points and passes their candidate intervals through LDS in
+// tiles, each record with its core flag.  A core lane unites its point with every core candidate within r that has a smaller index (each
+// pair once).  The tile loops run over the intervals' lengths; the loops inside cl_unite are bounded as written there.  No workgroup waits
+// on another: a workgroup that runs alone finishes
+__global__ void __launch_bounds__(kClBlock) cl_union_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, float r2,
+                                                            const int* __restrict__ core, int* parent)
+{
+	__shared__ RorPt tile[kClBlock];
+	__shared__ int tile_core[kClBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kClBlock, last = min(first + kClBlock, n) - 1;
+	const int s = first + tid;
+	RorPt P{0.f, 0.f, 0.f, -1};
+	long long K = 0;
+	bool mine = false;
+	if (s < n) { P = pts[s]; K = (long long)keys[s]; mine = core[P.id] != 0; }
+	if (!__syncthreads_or(mine)) return;                         // no core point in the span
+	cl_intervals(keys, n, first, last, iv_lo, iv_hi);
+	for (int o = 0; o < 9; o++) {
+		const int lo = iv_lo[o], hi = iv_hi[o];
+		for (int t0 = lo; t0 < hi; t0 += kClBlock) {
+			__syncthreads();                                     // the previous tile has been read by everybody
+			const int len = min(kClBlock, hi - t0);
+			if (tid < len) {
+				const RorPt Q = pts[t0 + tid];
+				tile[tid] = Q;
+				tile_core[tid] = core[Q.id];
+			}
+			__syncthreads();
+			const bool need = mine && cl_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
+			if (!need) continue;                                 // the next barrier is at the loop's head, which every lane reaches
+			for (int j = 0; j < len; j++) {
+				const RorPt Q = tile[j];
+				if (!tile_core[j] || Q.id >= P.id) continue;
+				const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+				const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+				if (d2 <= r2) cl_unite(parent, P.id, Q.id);
+			}
+		}
+	}
+}
+
+// after the component kernel has finished: root[i] = the root of core point i, -1 for any other point.  The walk moves to a strictly
+// smaller index each step (parent[v] < v for a non-root) and nothing is written to parent any more
+__global__ void cl_flatten_kernel(const int* __restrict__ parent, const int* __restrict__ core, int n, int* __restrict__ root)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	int x = -1;
+	if (core[i]) {
+		x = i;
+		for (int p = parent[x]; p != x; p = parent[x]) x = p;
+	}
+	root[i] = x;
+}
+
+// The same tile shape for the points that are not core: the smallest key (bits of d2) << 32 | index over the core candidates within r, then
+// that neighbour's root.  root[] is read at core indices and written at the others only
+__global__ void __launch_bounds__(kClBlock) cl_border_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, float r2,
+                                                             const int* __restrict__ core, int* root)
+{
+	__shared__ RorPt tile[kClBlock];
+	__shared__ int tile_core[kClBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kClBlock, last = min(first + kClBlock, n) - 1;
+	const int s = first + tid;
+	RorPt P{0.f, 0.f, 0.f, -1};
+	long long K = 0;
+	bool mine = false;
+	if (s < n) { P = pts[s]; K = (long long)keys[s]; mine = core[P.id] == 0; }
+	if (!__syncthreads_or(mine)) return;                         // every point of the span is core
+	cl_intervals(keys, n, first, last, iv_lo, iv_hi);
+	unsigned long long best = ~0ull;
+	for (int o = 0; o < 9; o++) {
+		const int lo = iv_lo[o], hi = iv_hi[o];
+		for (int t0 = lo; t0 < hi; t0 += kClBlock) {
+			__syncthreads();                                     // the previous tile has been read by everybody
+			const int len = min(kClBlock, hi - t0);
+			if (tid < len) {
+				const RorPt Q = pts[t0 + tid];
+				tile[tid] = Q;
+				tile_core[tid] = core[Q.id];
+			}
+			__syncthreads();
+			const bool need = mine && cl_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
+			if (!need) continue;                                 // the next barrier is at the loop's head, which every lane reaches
+			for (int j = 0; j < len; j++) {
+				const RorPt Q = tile[j];
+				if (!tile_core[j]) continue;                      // a core point is not P, which is none
+				const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+				const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+				const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(unsigned)Q.id;
+				if (d2 <= r2 && key < best) best = key;
+			}
+		}
+	}
+	if (mine && best != ~0ull) root[P.id] = root[(int)(unsigned)(best & 0xffffffffull)];
+}
+
+__global__ void cl_rootflag_kernel(const int* __restrict__ root, int n, int* __restrict__ isroot)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) isroot[i] = root[i] == i ? 1 : 0;
+}
+
+// scan: the exclusive scan of the root flags, so scan[r] is the dense label of root r; sizes is zeroed and counts by integer atomicAdd
+__global__ void cl_label_kernel(const int* __restrict__ root, const int* __restrict__ scan, int n, int32_t* __restrict__ label, int32_t* __restrict__ sizes)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int r = root[i];
+	const int l = r < 0 ? -1 : scan[r];
+	label[i] = l;
+	if (l >= 0) atomicAdd(sizes + l, 1);
+}
+
+__global__ void cl_keepflag_kernel(const int32_t* __restrict__ label, const int32_t* __restrict__ keep, int n, int* __restrict__ flag)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const int l = label[i];
+	flag[i] = (l >= 0 && keep[l]) ? 1 : 0;
+}
+
+__global__ void cl_compact_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ label, const int* __restrict__ flag, const int* __restrict__ scan,
+                                  int n, float* __restrict__ out, int32_t* __restrict__ index, int32_t* __restrict__ out_label)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || !flag[i]) return;
+	const size_t d = (size_t)scan[i];
+	out[3 * d] = xyz[3 * (size_t)i]; out[3 * d + 1] = xyz[3 * (size_t)i + 1]; out[3 * d + 2] = xyz[3 * (size_t)i + 2];
+	if (index) index[d] = i;
+	if (out_label) out_label[d] = label[i];
+}
+
+hipError_t launch_cluster(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, int32_t* d_label, int32_t* d_sizes, int* c_out,
+                          hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n <= 0 || !c_out || !d_label || !d_sizes || min_neighbors < 0) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256), tgrd((n + kClBlock - 1) / kClBlock), tblk(kClBlock);
+	hipError_t e;
+#define CL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	unsigned long long *keys = nullptr, *keys2 = nullptr;
+	int *ids = nullptr, *ids2 = nullptr, *core = nullptr, *parent = nullptr, *root = nullptr, *isroot = nullptr, *scan = nullptr;
+	RorPt* pts = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		unsigned long long*& a; unsigned long long*& b; int*& c; int*& d; int*& f; int*& g; int*& h; int*& i; int*& j; RorPt*& p; void*& t;
+		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(i); hipFree(j); hipFree(p); hipFree(t); }
+	} cleanup{keys, keys2, ids, ids2, core, parent, root, isroot, scan, pts, tmp};
+	const size_t N = (size_t)n;
+	CL_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
+	CL_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
+	CL_TRY(hipMalloc(&ids, sizeof(int) * N));
+	CL_TRY(hipMalloc(&ids2, sizeof(int) * N));
+	CL_TRY(hipMalloc(&core, sizeof(int) * N));
+	CL_TRY(hipMalloc(&parent, sizeof(int) * N));
+	CL_TRY(hipMalloc(&root, sizeof(int) * N));
+	CL_TRY(hipMalloc(&isroot, sizeof(int) * (N + 1)));
+	CL_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
+	CL_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
+	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+	size_t sort_bytes = 0, scan_bytes = 0;
+	CL_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	CL_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	CL_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	// ev_begin .. ev_end: the kernels and the 4-byte read-back of c; the allocations above and the frees at the end are outside
+	if (ev_begin) CL_TRY(hipEventRecord(ev_begin, stream));
+	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
+	CL_TRY(hipGetLastError());
+	size_t bytes = sort_bytes;
+	CL_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
+	hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
+	CL_TRY(hipGetLastError());
+	hipLaunchKernelGGL(cl_init_kernel, grd, blk, 0, stream, parent, core, n, min_neighbors == 0 ? 1 : 0);
+	CL_TRY(hipGetLastError());
+	if (min_neighbors > 0) {
+		// the radius filter's saturating count: core[i] = (count_i == min_neighbors); the counts themselves go to root, which is rewritten below
+		hipLaunchKernelGGL(ror_count_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, min_neighbors, root, core);
+		CL_TRY(hipGetLastError());
+	}
+	hipLaunchKernelGGL(cl_union_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, core, parent);
+	CL_TRY(hipGetLastError());
+	hipLaunchKernelGGL(cl_flatten_kernel, grd, blk, 0, stream, parent, core, n, root);
+	CL_TRY(hipGetLastError());
+	if (min_neighbors > 0) {
+		hipLaunchKernelGGL(cl_border_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, core, root);
+		CL_TRY(hipGetLastError());
+	}
+	hipLaunchKernelGGL(cl_rootflag_kernel, grd, blk, 0, stream, root, n, isroot);
+	CL_TRY(hipGetLastError());
+	CL_TRY(hipMemsetAsync(isroot + N, 0, sizeof(int), stream));
+	bytes = scan_bytes;
+	CL_TRY(rocprim::exclusive_scan(tmp, bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	CL_TRY(hipMemsetAsync(d_sizes, 0, sizeof(int32_t) * N, stream));
+	hipLaunchKernelGGL(cl_label_kernel, grd, blk, 0, stream, root, scan, n, d_label, d_sizes);
+	CL_TRY(hipGetLastError());
+	int c = -1;
+	CL_TRY(hipMemcpyAsync(&c, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+	if (ev_end) CL_TRY(hipEventRecord(ev_end, stream));
+	CL_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
+#undef CL_TRY
+	if (c < 0 || c > n) return hipErrorUnknown;
+	*c_out = c;
+	return hipSuccess;
+}
+
+hipError_t launch_cluster_compact(const float* d_xyz, int n, const int32_t* d_label, const int32_t* d_keep, float* d_out, int32_t* d_index,
+                                  int32_t* d_out_label, int* m_out, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n <= 0 || !m_out || !d_label || !d_keep || !d_out) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	hipError_t e;
+#define CL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+	int *flag = nullptr, *scan = nullptr;
+	void* tmp = nullptr;
+	// every exit path frees the temporaries
+	struct Cleanup {
+		int*& a; int*& b; void*& t;
+		~Cleanup() { hipFree(a); hipFree(b); hipFree(t); }
+	} cleanup{flag, scan, tmp};
+	const size_t N = (size_t)n;
+	CL_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
+	CL_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
+	size_t scan_bytes = 0;
+	CL_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	CL_TRY(hipMalloc(&tmp, std::max<size_t>(scan_bytes, 16)));
+	if (ev_begin) CL_TRY(hipEventRecord(ev_begin, stream));
+	hipLaunchKernelGGL(cl_keepflag_kernel, grd, blk, 0, stream, d_label, d_keep, n, flag);
+	CL_TRY(hipGetLastError());
+	CL_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
+	CL_TRY(rocprim::exclusive_scan(tmp, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	hipLaunchKernelGGL(cl_compact_kernel, grd, blk, 0, stream, d_xyz, d_label, flag, scan, n, d_out, d_index, d_out_label);
+	CL_TRY(hipGetLastError());
+	int m = -1;
+	CL_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+	if (ev_end) CL_TRY(hipEventRecord(ev_end, stream));
+	CL_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
+#undef CL_TRY
+	if (m < 0 || m > n) return hipErrorUnknown;
+	*m_out = m;
+	return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Statistical outlier removal on the device (host twin: statistical_outlier_removal_host, kdtree.cpp).  The k smallest d2 of every
 // point are found on grids of doubling radius r_L = r0 2^L (pitch 1.03125 r_L, the radius filter's grid and its proof): a point whose k-th
 // smallest d2 over its 27 cells is <= r_L * r_L has seen every point that close, so those k are its k smallest of the whole

@@ -409,6 +409,162 @@ void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32
 	*m_out = m;
 }
 
+// ---- Euclidean / DBSCAN clustering: what both paths share, and the host path ----
+// the radius filter's frame and refusals, except that min_neighbors == 0 (every point is core) is legal
+void cluster_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
+{
+	if (min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
+	radius_frame(xyz, n, radius, std::max(min_neighbors, 1), f);
+}
+
+void cluster_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
+{
+	if (min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
+	radius_frame_of_box(mn, mx, n, radius, std::max(min_neighbors, 1), f);
+}
+
+void cluster_check_select(int32_t min_size, int32_t max_clusters)
+{
+	if (min_size < 0) throw std::invalid_argument("goicp cluster: min_size must not be negative");
+	if (max_clusters < 0) throw std::invalid_argument("goicp cluster: max_clusters must not be negative");
+}
+
+// keep[l] = 1 for the clusters the selection keeps: ranked by size descending, ties to the smaller label, the first max_clusters (0 = all) of
+// those with size >= max(min_size, 1)
+void cluster_select(const int32_t* sizes, size_t c, int32_t min_size, int32_t max_clusters, std::vector<int32_t>* keep)
+{
+	keep->assign(c, 0);
+	std::vector<uint64_t> rank(c);
+	for (size_t l = 0; l < c; l++) rank[l] = ((uint64_t)(uint32_t)(INT32_MAX - sizes[l]) << 32) | (uint64_t)l;
+	std::sort(rank.begin(), rank.end());
+	const size_t limit = max_clusters > 0 ? std::min<size_t>((size_t)max_clusters, c) : c;
+	for (size_t k = 0; k < limit; k++) {
+		const size_t l = (size_t)(rank[k] & 0xffffffffu);
+		if (sizes[l] >= std::max(min_size, 1)) (*keep)[l] = 1;
+	}
+}
+
+// The radius filter's sorted cells and 27-cell candidate runs.  Pass 1 is its saturating count (the core flag), pass 2 a sequential
+// union-find over the core pairs (the larger root goes under the smaller, so a component's root is its smallest core index), pass 3 the
+// border points' smallest key over their core neighbours, then the relabelling in ascending root order
+void cluster_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* c_out)
+{
+	VoxelFrame f;
+	cluster_frame(xyz, n, radius, min_neighbors, &f);
+	const float r2 = radius * radius;
+	std::vector<std::pair<uint64_t, int32_t>> ki(n);
+	for (size_t i = 0; i < n; i++) {
+		uint64_t key = 0;
+		for (int k = 0; k < 3; k++) key |= (uint64_t)(int)std::floor((xyz[3 * i + k] - f.mn[k]) / f.voxel) << (21 * k);
+		ki[i] = {key, (int32_t)i};
+	}
+	std::sort(ki.begin(), ki.end());
+	struct Pt { float x, y, z; int32_t id; };
+	std::vector<uint64_t> keys(n);
+	std::vector<Pt> pts(n);
+	for (size_t s = 0; s < n; s++) {
+		const float* p = xyz + 3 * (size_t)ki[s].second;
+		keys[s] = ki[s].first;
+		pts[s] = {p[0], p[1], p[2], ki[s].second};
+	}
+	std::vector<std::pair<uint64_t, int32_t>>().swap(ki);
+	// fn(Q, d2) for every other point Q of the 27 cells around sorted position s that lies within r; fn returns false to stop
+	auto neighbours = [&](size_t s, auto&& fn) {
+		const Pt P = pts[s];
+		const int64_t cx = (int64_t)(keys[s] & 0x1fffffu), cy = (int64_t)((keys[s] >> 21) & 0x1fffffu), cz = (int64_t)(keys[s] >> 42);
+		for (int64_t z = std::max<int64_t>(cz - 1, 0); z <= cz + 1; z++)
+			for (int64_t y = std::max<int64_t>(cy - 1, 0); y <= cy + 1; y++) {
+				const uint64_t base = ((uint64_t)z << 42) | ((uint64_t)y << 21);
+				const size_t a = std::lower_bound(keys.begin(), keys.end(), base | (uint64_t)std::max<int64_t>(cx - 1, 0)) - keys.begin();
+				const size_t b = std::upper_bound(keys.begin() + a, keys.end(), base | (uint64_t)(cx + 1)) - keys.begin();
+				for (size_t j = a; j < b; j++) {
+					const Pt& Q = pts[j];
+					if (Q.id == P.id) continue;
+					const float dx = P.x - Q.x, dy = P.y - Q.y, dz = P.z - Q.z;
+					const float d2 = dx * dx + dy * dy + dz * dz;
+					if (d2 <= r2 && !fn(Q, d2)) return;
+				}
+			}
+	};
+	std::vector<char> core(n, 1);
+	if (min_neighbors > 0) {
+		const size_t chunk = 4096, chunks = (n + chunk - 1) / chunk;
+		parallel_tasks(n >= 65536 ? 8 : 1, (int)chunks, [&](int t) {
+			for (size_t s = (size_t)t * chunk; s < std::min(n, ((size_t)t + 1) * chunk); s++) {
+				int32_t cnt = 0;
+				neighbours(s, [&](const Pt&, float) { return ++cnt < min_neighbors; });
+				core[(size_t)pts[s].id] = cnt == min_neighbors;
+			}
+		});
+	}
+	std::vector<int32_t> parent(n);
+	for (size_t i = 0; i < n; i++) parent[i] = (int32_t)i;
+	auto find = [&](int32_t x) {
+		while (parent[(size_t)x] != x) {
+			parent[(size_t)x] = parent[(size_t)parent[(size_t)x]];   // path halving
+			x = parent[(size_t)x];
+		}
+		return x;
+	};
+	for (size_t s = 0; s < n; s++) {
+		const int32_t i = pts[s].id;
+		if (!core[(size_t)i]) continue;
+		neighbours(s, [&](const Pt& Q, float) {
+			if (Q.id < i && core[(size_t)Q.id]) {
+				const int32_t a = find(i), b = find(Q.id);
+				if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b);
+			}
+			return true;
+		});
+	}
+	// root[i]: the smallest core index of i's cluster, -1 for noise
+	std::vector<int32_t> root(n, -1);
+	for (size_t i = 0; i < n; i++) if (core[i]) root[i] = find((int32_t)i);
+	for (size_t s = 0; s < n; s++) {
+		const int32_t i = pts[s].id;
+		if (core[(size_t)i]) continue;
+		uint64_t best = UINT64_MAX;
+		neighbours(s, [&](const Pt& Q, float d2) {
+			if (core[(size_t)Q.id]) {
+				uint32_t bits;
+				std::memcpy(&bits, &d2, sizeof(bits));
+				best = std::min(best, ((uint64_t)bits << 32) | (uint64_t)(uint32_t)Q.id);
+			}
+			return true;
+		});
+		if (best != UINT64_MAX) root[(size_t)i] = root[(size_t)(best & 0xffffffffu)];
+	}
+	std::vector<int32_t> dense(n, -1);
+	size_t c = 0;
+	for (size_t i = 0; i < n; i++) if (root[i] == (int32_t)i) dense[i] = (int32_t)c++;
+	if (out_sizes) for (size_t l = 0; l < c; l++) out_sizes[l] = 0;
+	for (size_t i = 0; i < n; i++) {
+		const int32_t l = root[i] < 0 ? -1 : dense[(size_t)root[i]];
+		out_label[i] = l;
+		if (out_sizes && l >= 0) out_sizes[(size_t)l]++;
+	}
+	*c_out = c;
+}
+
+void cluster_filter_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
+                         int32_t* out_index, int32_t* out_label, size_t* m_out)
+{
+	cluster_check_select(min_size, max_clusters);
+	std::vector<int32_t> label(n), sizes(n), keep;
+	size_t c = 0;
+	cluster_host(xyz, n, radius, min_neighbors, label.data(), sizes.data(), &c);
+	cluster_select(sizes.data(), c, min_size, max_clusters, &keep);
+	size_t m = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (label[i] < 0 || !keep[(size_t)label[i]]) continue;
+		for (int k = 0; k < 3; k++) out_xyz[3 * m + k] = xyz[3 * i + k];
+		if (out_index) out_index[m] = (int32_t)i;
+		if (out_label) out_label[m] = label[i];
+		m++;
+	}
+	*m_out = m;
+}
+
 // ---- statistical outlier removal: what both paths share, and the host path ----
 void stat_check_params(size_t n, int32_t neighbors, float std_ratio)
 {

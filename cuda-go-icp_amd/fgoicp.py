@@ -144,14 +144,47 @@ def estimate_normals(xyz, k, viewpoint=None):
     return _normals_call(B.load_library().goicp_estimate_normals_host, xyz, k, viewpoint)
 
 
-def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None):
-    """the composition of the host functions that goicp_set_source_filtered and goicp_set_source_pipeline equal"""
+def _cluster_call(fn, xyz, radius, min_neighbors):
+    xyz = _f32(xyz, (-1, 3))
+    n, ip = len(xyz), C.POINTER(C.c_int32)
+    label, sizes, c = np.empty(n, np.int32), np.empty(n, np.int32), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), n, float(radius), int(min_neighbors), label.ctypes.data_as(ip), sizes.ctypes.data_as(ip), C.byref(c)))
+    return label, sizes[:c.value].copy()
+
+
+def cluster(xyz, radius, min_neighbors=0):
+    """goicp_cluster_host (host only): connected components of the core points under `radius` (min_neighbors = 0: every point is core,
+    Euclidean clustering; >= 1: DBSCAN with min_points = min_neighbors + 1), border points joined to their nearest core neighbour ->
+    (labels (n,) int32, -1 = noise, sizes (c,) int32).  Registration.cluster gives the same bits on the device."""
+    return _cluster_call(B.load_library().goicp_cluster_host, xyz, radius, min_neighbors)
+
+
+def _cluster_filter_call(fn, xyz, radius, min_neighbors, min_size, keep):
+    xyz = _f32(xyz, (-1, 3))
+    n, ip = len(xyz), C.POINTER(C.c_int32)
+    out, idx, lab, m = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.int32), C.c_size_t(0)
+    s = B.CClusterSelect(float(radius), int(min_neighbors), int(min_size), int(keep))
+    B.check(fn(_fptr(xyz), n, C.byref(s), _fptr(out), idx.ctypes.data_as(ip), lab.ctypes.data_as(ip), C.byref(m)))
+    return out[:m.value].copy(), idx[:m.value].copy(), lab[:m.value].copy()
+
+
+def cluster_filter(xyz, radius, min_neighbors=0, min_size=0, keep=0):
+    """goicp_cluster_filter_host (host only): the points of the `keep` largest clusters (0 = all) with at least `min_size` members, in input
+    order -> (cloud (m, 3) float32, their indices (m,) int32, their labels (m,) int32).  Registration.cluster_filter and
+    set_source(cluster_radius=, ...) give the same bits on the device."""
+    return _cluster_filter_call(B.load_library().goicp_cluster_filter_host, xyz, radius, min_neighbors, min_size, keep)
+
+
+def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None, cluster=None):
+    """the composition of the host functions that goicp_set_source_filtered, goicp_set_source_pipeline and goicp_set_source_clustered equal"""
     if voxel:
         pcs = voxel_downsample(pcs, voxel)[0]
     if stat_neighbors:
         pcs = statistical_outlier_removal(pcs, stat_neighbors, std_ratio)[0]
     if radius:
         pcs = radius_outlier_removal(pcs, radius, min_neighbors)[0]
+    if cluster:
+        pcs = cluster_filter(pcs, *cluster)[0]
     return pcs
 
 
@@ -321,7 +354,8 @@ class Registration:
     def pcs(self, value):
         self._pcs, self._pcs_raw = value, None
 
-    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None, cluster_radius=None,
+                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0):
         """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
         options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit.
         voxel: goicp_set_source_voxel -- the cloud is reduced to one centroid per voxel on the device first, and the handle answers as after
@@ -331,13 +365,29 @@ class Registration:
         radius_outlier_removal(..., radius, min_neighbors)[0].
         stat_neighbors, std_ratio (both or neither): goicp_set_source_pipeline -- between the voxel grid and the radius filter, if any, the
         statistical filter drops the points whose mean distance to their stat_neighbors nearest neighbours is above the mean plus std_ratio
-        deviations, and the handle answers as after set_source of the composed host functions' output."""
+        deviations, and the handle answers as after set_source of the composed host functions' output.
+        cluster_radius (with cluster_min_neighbors, cluster_min_size, cluster_keep): goicp_set_source_clustered -- after the other stages, if
+        any, only the points of the cluster_keep largest clusters (0 = all) with at least cluster_min_size members stay, and the handle
+        answers as after set_source of cluster_filter(..., cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_keep)[0]."""
         pcs = _f32(pcs, (-1, 3))
         if (radius is None) != (min_neighbors is None):
             raise ValueError("set_source: radius and min_neighbors go together")
         if (stat_neighbors is None) != (std_ratio is None):
             raise ValueError("set_source: stat_neighbors and std_ratio go together")
-        if stat_neighbors is not None:
+        if cluster_radius is not None:
+            if not float(cluster_radius) > 0 or (voxel is not None and not float(voxel) > 0) or (radius is not None and not float(radius) > 0) \
+                    or (stat_neighbors is not None and not int(stat_neighbors) > 0):
+                raise ValueError("set_source: a stage that is named needs a size > 0")
+            kept = C.c_size_t(0)
+            p = B.CSourcePipeline(float(voxel or 0.0), int(stat_neighbors or 0), float(std_ratio or 0.0), float(radius or 0.0), int(min_neighbors or 0))
+            cs = B.CClusterSelect(float(cluster_radius), int(cluster_min_neighbors), int(cluster_min_size), int(cluster_keep))
+            B.check(self._lib.goicp_set_source_clustered(self.handle, _fptr(pcs), len(pcs), C.byref(p), C.byref(cs), C.byref(kept)))
+            self._pcs, self.ns = None, kept.value
+            self._pcs_raw = (pcs, None if voxel is None else float(voxel), None if radius is None else float(radius),
+                             None if min_neighbors is None else int(min_neighbors), None if stat_neighbors is None else int(stat_neighbors),
+                             None if std_ratio is None else float(std_ratio),
+                             (float(cluster_radius), int(cluster_min_neighbors), int(cluster_min_size), int(cluster_keep)))
+        elif stat_neighbors is not None:
             if not int(stat_neighbors) > 0 or (voxel is not None and not float(voxel) > 0) or (radius is not None and not float(radius) > 0):
                 raise ValueError("set_source: a stage that is named needs a size > 0")
             kept = C.c_size_t(0)
@@ -378,6 +428,16 @@ class Registration:
         """goicp_statistical_outlier_removal: the module-level statistical_outlier_removal on the device (the handle lends its device and
         stream, its state is untouched) -> (cloud (m, 3) float32, indices (m,) int32, mean distances (n,) float32, threshold), the same bits"""
         return _stat_call(lambda *a: self._lib.goicp_statistical_outlier_removal(self.handle, *a), xyz, neighbors, std_ratio)
+
+    def cluster(self, xyz, radius, min_neighbors=0):
+        """goicp_cluster: the module-level cluster on the device (the handle lends its device and stream, its state is untouched) ->
+        (labels (n,) int32, sizes (c,) int32), the same bits"""
+        return _cluster_call(lambda *a: self._lib.goicp_cluster(self.handle, *a), xyz, radius, min_neighbors)
+
+    def cluster_filter(self, xyz, radius, min_neighbors=0, min_size=0, keep=0):
+        """goicp_cluster_filter: the module-level cluster_filter on the device (the handle lends its device and stream, its state is
+        untouched) -> (cloud (m, 3) float32, indices (m,) int32, labels (m,) int32), the same bits"""
+        return _cluster_filter_call(lambda *a: self._lib.goicp_cluster_filter(self.handle, *a), xyz, radius, min_neighbors, min_size, keep)
 
     def knn_self(self, xyz, k):
         """goicp_knn_self: the module-level knn_self on the device (the handle lends its device and stream, its state is untouched)"""
@@ -651,9 +711,11 @@ class FastGoICP:
         self.mse_threshold = float(mse_threshold)
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
 
-    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None):
+    def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None, cluster_radius=None,
+                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0):
         """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
-        self.registration.set_source(pcs, voxel, radius, min_neighbors, stat_neighbors, std_ratio)
+        self.registration.set_source(pcs, voxel, radius, min_neighbors, stat_neighbors, std_ratio, cluster_radius, cluster_min_neighbors,
+                                     cluster_min_size, cluster_keep)
         self.sse_threshold = self.registration.sse_threshold
 
     def run(self):

@@ -393,6 +393,46 @@ int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_inde
 int goicp_knn_self(goicp_handle h, const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
 int goicp_estimate_normals_host(const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
 int goicp_estimate_normals(goicp_handle h, const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
+/*
+ * Euclidean / DBSCAN clustering (PCL's EuclideanClusterExtraction, Open3D's cluster_dbscan): connected components under a distance, and
+ * the filter "keep the largest clusters" built on it.  The host functions, the device functions and the clustered swap produce the same
+ * bits.  The only float expression is the radius filter's pair; everything else is integers:
+ *   r2      = radius * radius;
+ *   pair    for points i != j: dx = x_i - x_j, dy = y_i - y_j, dz = z_i - z_j, d2 = dx*dx + dy*dy + dz*dz evaluated left to right; j is a
+ *           neighbour of i iff j != i && d2 <= r2.  A duplicate of a point is its neighbour, a point is never its own;
+ *   core    point i is core iff min(number of neighbours of i, min_neighbors) == min_neighbors (the radius filter's saturating count).
+ *           min_neighbors == 0 makes every point core: PCL's Euclidean clustering.  min_neighbors >= 1 is DBSCAN with
+ *           min_points = min_neighbors + 1;
+ *   cluster a connected component of the core points under the neighbour relation;
+ *   border  a point that is not core but has a core neighbour joins the cluster of the core neighbour j with the smallest 64-bit key
+ *           ((uint64)bits of d2 << 32) | j.  A border point never connects two clusters;
+ *   noise   every other point: label -1;
+ *   labels  the c clusters are numbered 0..c-1 in ascending order of their smallest core member's index; sizes[l] counts the core and the
+ *           border members of cluster l;
+ *   select  (the filter) the clusters ranked by size descending, ties to the smaller label; of those with size >= max(min_size, 1) the
+ *           first max_clusters are kept (max_clusters == 0: all of them).  The output is the m points of the kept clusters in input
+ *           order with their own bits, their original indices (ascending) and their labels.
+ * The definition names no grid: the implementations search the radius filter's grid.
+ * goicp_cluster: out_label holds n ints (all written), out_sizes (may be NULL) n ints (the first c are written), *n_clusters = c; c == 0
+ * (all noise) is a valid result.  goicp_cluster_filter: out_xyz holds n x 3 floats (the first m x 3 are written), out_index and out_label
+ * (each may be NULL) n ints (the first m are written), *m the number of points kept; m == 0 is a valid result.
+ * The _host forms run on the host alone (no handle, no GPU).  The handle forms run on the device: the handle lends its device and stream,
+ * its state is untouched.
+ * goicp_set_source_clustered chains the stages of goicp_set_source_pipeline (p; NULL = none of them), then the cluster selection when
+ * s->radius > 0, then the swap, on the device behind one upload.  Afterwards the handle answers every entry point bit for bit as after
+ * goicp_set_source(h, D, m) with D the composition of the host functions.  With s->radius == 0 it is goicp_set_source_pipeline.
+ * *n_kept (may be NULL) = m.
+ * GOICP_ERR_INVALID, nothing written or the handle untouched: what goicp_radius_outlier_removal refuses except min_neighbors == 0, a
+ * negative min_neighbors, min_size or max_clusters, for the swap everything goicp_set_source_pipeline refuses, a negative or NaN
+ * s->radius and a selection that keeps no point, and for the handle forms any call while a registration runs.
+ */
+int goicp_cluster_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
+int goicp_cluster(goicp_handle h, const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
+typedef struct goicp_cluster_select { float radius; int32_t min_neighbors; int32_t min_size; int32_t max_clusters; } goicp_cluster_select;
+void goicp_cluster_select_default(goicp_cluster_select* out);   /* all 0 = no stage */
+int goicp_cluster_filter_host(const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label, size_t* m);
+int goicp_cluster_filter(goicp_handle h, const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label, size_t* m);
+int goicp_set_source_clustered(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_cluster_select* s, size_t* n_kept);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

@@ -247,6 +247,48 @@ public:
 		ns_ = kept;
 		return kept;
 	}
+	// the same behind the pipeline's stages and the cluster selection (goicp_set_source_clustered): after p's stages (p may be null), only the
+	// points of the s.max_clusters largest clusters (0 = all) with at least s.min_size members stay; returns the points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, size_t ns, const goicp_source_pipeline* p, const goicp_cluster_select& s)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		size_t kept = 0;
+		check(goicp_set_source_clustered(h_, reinterpret_cast<const float*>(pcs.data()), ns, p, &s, &kept));
+		ns_ = kept;
+		return kept;
+	}
+	// Euclidean / DBSCAN clustering of any cloud, on the device (goicp_cluster): label gets n entries (-1 = noise), sizes the c clusters'
+	// sizes; returns c.  The registration lends its device, its state is untouched
+	template <class Point3>
+	size_t cluster(const std::vector<Point3>& cloud, size_t n, float radius, int min_neighbors, std::vector<int32_t>& label, std::vector<int32_t>* sizes = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		label.resize(n);
+		if (sizes) sizes->resize(n);
+		size_t c = 0;
+		check(goicp_cluster(h_, reinterpret_cast<const float*>(cloud.data()), n, radius, (int32_t)min_neighbors, label.data(), sizes ? sizes->data() : nullptr, &c));
+		if (sizes) sizes->resize(c);
+		return c;
+	}
+	// the points of the selected clusters of any cloud, on the device (goicp_cluster_filter), in input order: kept gets the m points, index
+	// and label (each may be null) their original indices and cluster labels; returns m
+	template <class Point3>
+	size_t cluster_filter(const std::vector<Point3>& cloud, size_t n, const goicp_cluster_select& s, std::vector<Point3>& kept,
+	                      std::vector<int32_t>* index = nullptr, std::vector<int32_t>* label = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		kept.resize(n);
+		if (index) index->resize(n);
+		if (label) label->resize(n);
+		size_t m = 0;
+		check(goicp_cluster_filter(h_, reinterpret_cast<const float*>(cloud.data()), n, &s, reinterpret_cast<float*>(kept.data()), index ? index->data() : nullptr,
+		                           label ? label->data() : nullptr, &m));
+		kept.resize(m);
+		if (index) index->resize(m);
+		if (label) label->resize(m);
+		return m;
+	}
 	// the exact k nearest other points of every point of any cloud, on the device (goicp_knn_self): index gets n x k entries, row i ascending
 	// by (squared distance, index); dist_sq (may be null) their squared distances.  The registration lends its device, its state is untouched
 	template <class Point3>
@@ -433,6 +475,14 @@ public:
 	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_pipeline& p)
 	{
 		const size_t kept = registration.set_source(pcs, pcs.size(), p);
+		sync();
+		return kept;
+	}
+	// ... behind the chain `p` (may be null) and the cluster selection `s` (keep the largest clusters); returns the number of points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_pipeline* p, const goicp_cluster_select& s)
+	{
+		const size_t kept = registration.set_source(pcs, pcs.size(), p, s);
 		sync();
 		return kept;
 	}
