@@ -154,6 +154,7 @@ SYMBOLS = {
     "goicp_debug_bounds_tile": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     "goicp_debug_cache_hits": (C.c_int, [_vp, _fp, _fp, C.POINTER(C.c_int64)]),
     "goicp_debug_bounds_order": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "goicp_debug_bounds_twins": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "goicp_debug_select": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "goicp_create": (C.c_int, [C.POINTER(CParams), _fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(_vp)]),
     "goicp_destroy": (C.c_int, [_vp]),

@@ -515,9 +515,10 @@ __device__ __forceinline__ void lean_points_pair(const float4* __restrict__ src,
 }
 
 // the sums of one (expansion, chunk) work item: wave64 reduce, then the 4 wavefronts through LDS, then the item's row of the scratch block (or,
-// unsplit, the bounds themselves)
+// unsplit, the bounds themselves).  also >= 0: a second group whose expansion is the same bit for bit (bounds_pair_kernel) gets the same sums
 __device__ __forceinline__ void bounds_item_store(const float (&ub)[kGroup], const float (&lb)[kGroup], int group, int chunk, int chunks, int B,
-                                                  float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, float (*red)[2 * kGroup])
+                                                  float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, float (*red)[2 * kGroup],
+                                                  int also = -1)
 {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c0 = group * kGroup;
 #pragma unroll
@@ -533,8 +534,10 @@ __device__ __forceinline__ void bounds_item_store(const float (&ub)[kGroup], con
 		if (chunks == 1) {
 			int c = threadIdx.x & (kGroup - 1);
 			if (c0 + c < B) (threadIdx.x < kGroup ? ub_out : lb_out)[c0 + c] = s;
+			if (also >= 0 && also * kGroup + c < B) (threadIdx.x < kGroup ? ub_out : lb_out)[also * kGroup + c] = s;
 		} else {
 			scratch[((size_t)group * chunks + chunk) * (2 * kGroup) + threadIdx.x] = s;
+			if (also >= 0) scratch[((size_t)also * chunks + chunk) * (2 * kGroup) + threadIdx.x] = s;
 		}
 	}
 }
@@ -1207,7 +1210,7 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	__syncthreads();
 	const int nb = nbound, runs = nb + 1;
 	if (runs > bo.max_runs) {
-		if (blockIdx.x == 0 && tid == 0) { bo.ctl[0] = 0; bo.ctl[1] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1; }
+		if (blockIdx.x == 0 && tid == 0) { bo.ctl[0] = 0; bo.ctl[1] = 0; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1; }
 		return;
 	}
 	if (tid == 0) { run_start[0] = 0; run_start[runs] = G; }
@@ -1223,7 +1226,7 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	const int s0 = run_start[run], n = run_start[run + 1] - s0;
 	int item0 = 0, items = 0;
 	for (int q = 0; q < runs; q++) { if (q == run) item0 = items; items += (run_start[q + 1] - run_start[q] + 1) >> 1; }
-	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; if (bo.host_note) *bo.host_note = (long long)G << 1; }
+	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = (long long)G << 1; }
 	// the extent of the run's centres (a thread without a k-th group holds the run's last one again: it changes neither the extent nor, below, a counter)
 	float held[kOrderHeld][3];
 	float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -1335,15 +1338,28 @@ __device__ __forceinline__ bool pair_member(const CubeRec* __restrict__ cubes, c
 	m.delta = cr[0].delta; m.coeff = cr[0].coeff; rot = cr[0].rot;
 	return sib;
 }
+// do two members look up the same voxels under every point?  raw bits: -0 against +0 is no match and keeps the pair form
+__device__ __forceinline__ bool same_box(const PairMember& a, const PairMember& b)
+{
+	const unsigned d = (__float_as_uint(a.ts.tx0) ^ __float_as_uint(b.ts.tx0)) | (__float_as_uint(a.ts.tx1) ^ __float_as_uint(b.ts.tx1)) |
+	                   (__float_as_uint(a.ts.ty0) ^ __float_as_uint(b.ts.ty0)) | (__float_as_uint(a.ts.ty1) ^ __float_as_uint(b.ts.ty1)) |
+	                   (__float_as_uint(a.ts.tz0) ^ __float_as_uint(b.ts.tz0)) | (__float_as_uint(a.ts.tz1) ^ __float_as_uint(b.ts.tz1)) |
+	                   (__float_as_uint(a.delta) ^ __float_as_uint(b.delta));
+	return d == 0u;
+}
 // the pair launch (bounds_order = 2): grid = max_items * chunks, an item = the two groups pairs[] names over one chunk, mapped to the XCDs as bounds_work maps (group, chunk).  Two sibling sets of one rotation are evaluated together
 // (lean_points_pair); anything else -- a generic group, a partial last group, a foreign rotation, a single -- group by group on the plain path.
+// COINCIDENT members -- the six translations and delta equal as raw bits: the root expansion of every inner search, the node both searches of a
+// rotation child list; the pre-pass puts them in one cell, hence next to each other -- have the same addresses: such an item runs
+// lean_points<1, 2, ..> once (the loop of the queue twins), or, with equal coefficients too, lean_points<1, 1, ..> once for both groups' rows.
+// Thread 0 of the item's chunk-0 workgroup counts the form in ctl[2] / ctl[3] (goicp_debug_bounds_twins).
 // A batch the pre-pass left alone (ctl[1] = 0) is evaluated here too, two groups per item in arrival order on the plain path: the grid of
 // bounds_order_items(groups, max_runs) >= (groups + 1) / 2 items covers it, and no second launch is needed.
 template <bool TRUNC>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
-    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, const int* __restrict__ ctl)
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl)
 {
 	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
 	const int work = blockIdx.x, total = gridDim.x;
@@ -1371,13 +1387,52 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
 		int ra, rb;
 		const bool sa = pair_member(cubes, parents, ga, B, A, ra), sb = pair_member(cubes, parents, gb, B, Bm, rb);
 		if (sa && sb && ra == rb) {
+			const Rot9 R0 = rots[ra];
+			const int p0 = chunk * chunk_pts;
+			const int p1 = p0 + chunk_pts < N ? p0 + chunk_pts : N;
+			if (same_box(A, Bm)) {
+				// coincident members: one index set, one exactness test and one set of gathers per point serve both (lean_points, which has
+				// its own checked branch: nothing is given up here); a pass of the NP = 2 loop is a separate evaluation operation for operation
+				const bool same = __float_as_uint(A.coeff) == __float_as_uint(Bm.coeff) || (A.coeff == 0.f && Bm.coeff == 0.f);
+				if (chunk == 0 && threadIdx.x == 0) atomicAdd(ctl + (same ? 3 : 2), 1);
+				float ub[kGroup], lb[kGroup];
+				if (same) {                                       // the same expansion twice: evaluated once, stored to both groups' rows
+					f2 ub2[1][4], lb2[1][4];
+#pragma unroll
+					for (int k = 0; k < 4; k++) { ub2[0][k] = f2{0.f, 0.f}; lb2[0][k] = f2{0.f, 0.f}; }
+					const float co[1] = {A.coeff};
+					if (A.coeff == 0.f) lean_points<1, 1, true, TRUNC>(src, p0, p1, dt, R0, A.ts, A.delta, co, ub2, lb2);
+					else lean_points<1, 1, false, TRUNC>(src, p0, p1, dt, R0, A.ts, A.delta, co, ub2, lb2);
+#pragma unroll
+					for (int k = 0; k < 4; k++) { ub[2 * k] = ub2[0][k].x; ub[2 * k + 1] = ub2[0][k].y; lb[2 * k] = lb2[0][k].x; lb[2 * k + 1] = lb2[0][k].y; }
+					bounds_item_store(ub, lb, ga, chunk, chunks, B, scratch, ub_out, lb_out, red, gb);
+					return;
+				}
+				if (A.coeff == 0.f) {                             // the member without a rotation radius goes last (LAST_ZERO)
+					const float c = A.coeff; A.coeff = Bm.coeff; Bm.coeff = c;
+					const int g = ga; ga = gb; gb = g;
+				}
+				f2 ub2[2][4], lb2[2][4];
+#pragma unroll
+				for (int q = 0; q < 2; q++)
+#pragma unroll
+					for (int k = 0; k < 4; k++) { ub2[q][k] = f2{0.f, 0.f}; lb2[q][k] = f2{0.f, 0.f}; }
+				const float co[2] = {A.coeff, Bm.coeff};
+				if (Bm.coeff == 0.f) lean_points<1, 2, true, TRUNC>(src, p0, p1, dt, R0, A.ts, A.delta, co, ub2, lb2);
+				else lean_points<1, 2, false, TRUNC>(src, p0, p1, dt, R0, A.ts, A.delta, co, ub2, lb2);
+#pragma unroll
+				for (int k = 0; k < 4; k++) { ub[2 * k] = ub2[1][k].x; ub[2 * k + 1] = ub2[1][k].y; lb[2 * k] = lb2[1][k].x; lb[2 * k + 1] = lb2[1][k].y; }
+				bounds_item_store(ub, lb, gb, chunk, chunks, B, scratch, ub_out, lb_out, red);
+				__syncthreads();                                  // `red` is reused
+#pragma unroll
+				for (int k = 0; k < 4; k++) { ub[2 * k] = ub2[0][k].x; ub[2 * k + 1] = ub2[0][k].y; lb[2 * k] = lb2[0][k].x; lb[2 * k + 1] = lb2[0][k].y; }
+				bounds_item_store(ub, lb, ga, chunk, chunks, B, scratch, ub_out, lb_out, red);
+				return;
+			}
 			if (A.coeff != 0.f && Bm.coeff == 0.f) {       // at most one member without a rotation radius: make it the first (LZ_A)
 				const PairMember t = A; A = Bm; Bm = t;
 				const int g = ga; ga = gb; gb = g;
 			}
-			const Rot9 R0 = rots[ra];
-			const int p0 = chunk * chunk_pts;
-			const int p1 = p0 + chunk_pts < N ? p0 + chunk_pts : N;
 			f2 ubA[4], lbA[4], ubB[4], lbB[4];
 #pragma unroll
 			for (int k = 0; k < 4; k++) { ubA[k] = f2{0.f, 0.f}; lbA[k] = f2{0.f, 0.f}; ubB[k] = f2{0.f, 0.f}; lbB[k] = f2{0.f, 0.f}; }

@@ -128,7 +128,8 @@ struct BoundsOrder {
 	unsigned* keys;              // [groups]
 	unsigned* order;             // [groups]
 	int* pairs;                  // [2 * bounds_order_items(groups, max_runs)]: the two groups of an item, -1 = none
-	int* ctl;                    // [0] items of the pair list, [1] 1 = order and pairs are valid (0: too many runs)
+	int* ctl;                    // [0] items of the pair list, [1] 1 = order and pairs are valid (0: too many runs); [2], [3] items the pair launch
+	                             // evaluated in twin form / in identical form (coincident members, bounds_pair_kernel): zeroed by the pre-pass
 	long long* host_note;        // pinned host memory: the pre-pass leaves (groups << 1 | left alone) there, a hint for the caller's next launch
 };
 constexpr int kBoundsOrderMaxRuns = 64;

@@ -1154,7 +1154,7 @@ const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
 		border_skipped_ = 0;
 	}
 	const int max_runs = std::min(std::max(p_.bounds_order_max_runs, 1), kBoundsOrderMaxRuns);
-	const size_t items = bounds_order_items(groups, max_runs), need = 2 * (size_t)groups + 2 * items + 2;
+	const size_t items = bounds_order_items(groups, max_runs), need = 2 * (size_t)groups + 2 * items + 4;
 	if (need > d_border_.size()) {
 		HIPCHK(hipStreamSynchronize(stream_));
 		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
@@ -1193,6 +1193,15 @@ void Engine::debug_bounds_order(int info[3])
 	HIPCHK(hipStreamSynchronize(border_stream_));
 	HIPCHK(hipMemcpy(ctl, border_.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
 	info[1] = ctl[1]; info[2] = ctl[0];
+}
+
+void Engine::debug_bounds_twins(int info[2])
+{
+	DeviceGuard guard(dev_);
+	info[0] = info[1] = 0;
+	if (border_form_ != 2) return;
+	HIPCHK(hipStreamSynchronize(border_stream_));
+	HIPCHK(hipMemcpy(info, border_.ctl + 2, 2 * sizeof(int), hipMemcpyDeviceToHost));
 }
 
 void Engine::reduce_min_dev(const float* d_v, int n, float* d_min, int* d_idx, hipStream_t s)

@@ -231,6 +231,7 @@ public:
 	// (lower-bound search), in the order of parents4.  info[0] = point chunks the evaluation split the cloud into, info[1] = 1 when the
 	// twin lists were in use.
 	void debug_bounds_order(int info[3]);   // test: form of the last eval_bounds_dev launch, and what its pre-pass decided (device.hip BoundsOrder::ctl)
+	void debug_bounds_twins(int info[2]);   // test: items of that launch evaluated in twin form and in identical form (BoundsOrder::ctl[2], [3])
 	void debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2]);
 	// measurement / test: the 8 children of nseg x n expansions (segment i: rotation i, parents4[(i*n + e)*4 ..] = corner xyz + width) through
 	// the LDS-tile kernel and through the direct kernel; out arrays hold 8*nseg*n floats each; ms[0] tile, ms[1] direct (per launch)

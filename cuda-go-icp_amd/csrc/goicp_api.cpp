@@ -413,6 +413,16 @@ int goicp_debug_bounds_order(goicp_handle h, int32_t info[3])
 	});
 }
 
+int goicp_debug_bounds_twins(goicp_handle h, int32_t info[2])
+{
+	REQUIRE(h && info);
+	return guarded([&] {
+		int inf[2] = {0, 0};
+		h->e->debug_bounds_twins(inf);
+		info[0] = inf[0]; info[1] = inf[1];
+	});
+}
+
 int goicp_debug_select(goicp_handle h, const float* d2, size_t n, int32_t num, int32_t kernel, uint8_t* include)
 {
 	REQUIRE(h && d2 && include && n >= 1 && n <= 0x7fffffffu && num >= 1 && (size_t)num <= n && kernel >= 0 && kernel <= 2 && !(kernel == 1 && n > 32768));

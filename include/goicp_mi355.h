@@ -895,6 +895,11 @@ int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, co
  * info[1] = 1 when the device pre-pass built an order, 0 when it left the batch alone (more runs of equal rotation than
  * bounds_order_max_runs); info[2] = the work items of the pair list (pairs and singles; 0 when left alone) */
 int goicp_debug_bounds_order(goicp_handle h, int32_t info[3]);
+/* goicp_debug_bounds_twins (test): what the pair launch (form 2) of the same last call did with coincident members -- two sibling sets of
+ * one item whose six translations and delta are equal bit for bit.  info[0] = items evaluated in twin form (one index set and one gather
+ * per point, a sum per coefficient), info[1] = items whose coefficients were equal as well (evaluated once, stored to both).  Both 0 for the
+ * other forms and for a batch the pre-pass left alone. */
+int goicp_debug_bounds_twins(goicp_handle h, int32_t info[2]);
 /* diagnostics of the ICP pass's neighbour cache: two scoring passes at (R, t); *hits = queries of the second pass that
  * skipped the tree walk (-1 when the cache is off) */
 int goicp_debug_cache_hits(goicp_handle h, const float R[9], const float t[3], int64_t* hits);

@@ -28,6 +28,13 @@ cells, the expansion's depth between a coarse and a fine Morton cell, the depth 
 whose members have the same depth.
 
   python3 tools/dt_sector_model.py --lines --keys [--json profiles/r07_order_keys_model.json]
+
+--twins: the COINCIDENT items of the pair launch (bounds_pair_kernel: both members of an item with the same six translations and delta,
+bit for bit) when the order inside a Morton cell is random, for the bench batch and for a batch shaped like the two inner searches of a
+rotation child (search_shaped_batch): items any order could give at most (floor(family / 2) per family of equal expansions in a run), the
+items --trials random tie orders capture (mean, min, max), and how many two-member families share their cell with anything else.
+
+  python3 tools/dt_sector_model.py --twins [--trials 200] [--json profiles/r08_twin_tie_order_model.json]
 """
 import argparse
 import json
@@ -139,6 +146,80 @@ def key_variant(name, centres_vox, depth, cell):
 KEY_VARIANTS = ("cell_floor_2", "bits10_quarter_voxel_cells", "coarse16_depth_fine", "depth_fine")
 
 
+def search_shaped_batch(n_runs, seed, ub_nodes=7, lb_nodes=16):
+    """A cube batch shaped like the two inner searches of a rotation child (no recorded batch exists: the shape follows the counts of
+    EXPERIMENTS 3.6, bunny: 18 287 / 40 470 expansions of the upper-bound / lower-bound searches over 2 601 roots, the roots and 1.25 depth-1
+    nodes per root common to both).  Per run: both searches expand the root; the upper-bound search then descends (a child of its deepest
+    node three times in four, else of any node it expanded), the lower-bound search spreads (a child of a random expanded node, shallow
+    ones first).  Records as bench.make_batch writes them; the coefficient only tells the passes apart."""
+    rng = np.random.default_rng(seed)
+    j = np.arange(8)
+    off = np.stack([j & 1, (j >> 1) & 1, (j >> 2) & 1], 1).astype(np.float32)
+    recs = []
+    for run in range(n_runs):
+        for coeff, count, deep in ((np.float32(0), ub_nodes, True), (np.float32(0.1), lb_nodes, False)):
+            done = [((-0.5, -0.5, -0.5), 1.0)]                 # (corner, width) of the expanded nodes: the root first
+            seen = {done[0]}
+            while len(done) < count:
+                if deep:
+                    parent = min(done, key=lambda n: n[1]) if rng.random() < 0.75 else done[int(rng.integers(len(done)))]
+                else:
+                    w_ = np.array([n[1] for n in done])
+                    parent = done[int(rng.choice(len(done), p=w_ / w_.sum()))]
+                c = int(rng.integers(8))
+                hw = parent[1] / 2
+                node = (tuple(float(parent[0][k] + ((c >> k) & 1) * hw) for k in range(3)), hw)
+                if node in seen or hw < 1.0 / 64:
+                    continue
+                seen.add(node)
+                done.append(node)
+            for corner, width in done:
+                w = np.float32(width) / np.float32(2)
+                r = np.zeros(8, dtype=[("tx", "<f4"), ("ty", "<f4"), ("tz", "<f4"), ("delta", "<f4"), ("coeff", "<f4"), ("rot", "<i4")])
+                cx = np.asarray(corner, np.float32)[None, :] + off * w + w / np.float32(2)
+                r["tx"], r["ty"], r["tz"] = cx[:, 0], cx[:, 1], cx[:, 2]
+                r["delta"], r["coeff"], r["rot"] = np.float32(np.sqrt(3.0) / 2 * w), coeff, run
+                recs.append(r)
+    recs = np.concatenate(recs)
+    # arrival order inside a run is the caller's: shuffled, so that no tie is decided by the generator
+    g = len(recs) // 8
+    perm = np.lexsort((rng.random(g), recs["rot"][0::8]))
+    return recs.reshape(g, 8)[perm].reshape(-1)
+
+
+def twins_mode(recs, scale, cell, trials, seed):
+    """bounds_pair_kernel's coincident items under a RANDOM order inside every Morton cell (the pre-pass's LDS atomics give no other promise):
+    groups of a run with the same six translations and delta, bit for bit, form a family; floor(size / 2) items per family is the most any
+    order can give; a trial shuffles every cell, pairs neighbours (2 i, 2 i + 1) of the run's order and counts the pairs inside one family"""
+    rng = np.random.default_rng(seed)
+    g = len(recs) // 8
+    first = recs.reshape(g, 8)
+    box = np.stack([first["tx"][:, 0], first["tx"][:, 1], first["ty"][:, 0], first["ty"][:, 2], first["tz"][:, 0], first["tz"][:, 4], first["delta"][:, 0]], 1).astype(np.float32)
+    centres = np.stack([(first[a][:, 0] + first[a][:, 7]) * np.float32(0.5) for a in ("tx", "ty", "tz")], 1) * scale
+    rot = first["rot"][:, 0]
+    starts = np.flatnonzero(np.concatenate([[True], rot[1:] != rot[:-1]]))
+    bounds = np.concatenate([starts, [g]])
+    eligible, two_member, shared, caught = 0, 0, 0, np.zeros(trials, np.int64)
+    for s, e in zip(bounds[:-1], bounds[1:]):
+        key = fine_key(centres[s:e], cell)
+        _, fam = np.unique(box[s:e].view(np.uint32), axis=0, return_inverse=True)
+        fam = fam.ravel()
+        size = np.bincount(fam)
+        eligible += int((size // 2).sum())
+        for f in np.flatnonzero(size == 2):
+            two_member += 1
+            members = np.flatnonzero(fam == f)
+            shared += int((key == key[members[0]]).sum() > 2)
+        for t in range(trials):
+            order = np.lexsort((rng.random(e - s), key))
+            a, b = order[0:len(order) - 1:2], order[1::2]
+            caught[t] += int((fam[a] == fam[b]).sum())
+    return {"groups": int(g), "runs": int(len(starts)), "items": int(((bounds[1:] - bounds[:-1] + 1) // 2).sum()), "twin_eligible_items": eligible,
+            "two_member_families": two_member, "two_member_families_sharing_their_cell": shared, "trials": trials,
+            "captured_mean": round(float(caught.mean()), 1), "captured_min": int(caught.min()), "captured_max": int(caught.max()),
+            "captured_share_mean": round(float(caught.mean()) / max(eligible, 1), 4), "captured_share_min": round(float(caught.min()) / max(eligible, 1), 4)}
+
+
 def lines_mode(a, rots, recs, src, mn, scale, V):
     N = len(src)
     chunk_pts = -(-(-(-N // 8)) // 256) * 256                 # bounds_shape: eight chunks, a multiple of 256 points
@@ -222,6 +303,8 @@ def main():
     ap.add_argument("--lines", action="store_true", help="model 128-B lines and their sharing between consecutive expansions (see above)")
     ap.add_argument("--cell", type=float, default=4.0, help="--lines: smallest Morton cell of the order, voxels")
     ap.add_argument("--keys", action="store_true", help="--lines: also model the other keys of the order (KEY_VARIANTS)")
+    ap.add_argument("--twins", action="store_true", help="model the coincident items of the pair launch under a random order inside every cell (see above)")
+    ap.add_argument("--trials", type=int, default=200, help="--twins: random tie orders per batch")
     a = ap.parse_args()
 
     from conftest import load_pkg, cloud
@@ -247,6 +330,15 @@ def main():
     pad = (-N) % 64
     V = 300
     mn, scale = dt_geometry(model, V)
+    if a.twins:
+        out = {"cell_vox": a.cell, "voxels_per_unit": round(float(scale), 2),
+               "bench_batch": dict(batch="bench.make_batch(8192 expansions, 8 rotations, seed 1234)", **twins_mode(recs, scale, a.cell, a.trials, 0)),
+               "search_shaped_batch": dict(batch="search_shaped_batch(64 runs, seed 1): 7 + 16 expansions per run", **twins_mode(search_shaped_batch(64, 1), scale, a.cell, a.trials, 0))}
+        print(json.dumps(out, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.lines:
         out = lines_mode(a, rots, recs, src, mn, scale, V)
         print(json.dumps(out, indent=1))
