@@ -151,6 +151,8 @@ SYMBOLS = {
     "goicp_probe_gather": (C.c_int, [_vp, C.c_int32, C.c_size_t, C.POINTER(C.c_double)]),
     "goicp_debug_kabsch": (C.c_int, [_fp, _fp]),
     "goicp_debug_queue_expand": (C.c_int, [C.c_void_p, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
+    "goicp_debug_queue_expand_tiles": (C.c_int, [C.c_void_p, _fp, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), C.c_int32, _fp,
+                                                 C.POINTER(C.c_int32), _fp, _fp]),
     "goicp_debug_bounds_tile": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     "goicp_debug_cache_hits": (C.c_int, [_vp, _fp, _fp, C.POINTER(C.c_int64)]),
     "goicp_debug_bounds_order": (C.c_int, [_vp, C.POINTER(C.c_int32)]),

@@ -1003,6 +1003,7 @@ hipError_t launch_bounds_tile(const float4* src, int N, const DtDesc& dt, const 
 static inline bool bounds_lean(const DtDesc& dt) { return (size_t)dt.V * dt.V * dt.V * sizeof(float) <= ((size_t)256 << 20); }
 bool bounds_uses_lean(const DtDesc& dt) { return dt.layout == 1 && bounds_lean(dt); }
 constexpr int kTileQueueGrid = 256 * (160 * 1024 / (kTileFloats * 4 + 2048));   // as many workgroups per CU as their LDS allows (32 KB tiles: four)
+int bounds_tile_queue_grid() { return kTileQueueGrid; }
 size_t bounds_tile_queue_scratch_floats(int max_groups)
 {
 	// groups x chunks x 16 with chunks <= ceil(grid / segments) and groups <= 64 segments: at most 64 (grid + segments) rows

@@ -232,6 +232,7 @@ hipError_t launch_bnb_queue(QSearch* searches, QNode* q, int nsearch, const QPar
 // bounds of the tile list of round `parity` (segment count known to the device only); fixed grid
 hipError_t launch_bounds_tile_queue(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const QTile& tile, QCtl* ctl, int parity, hipStream_t stream);
 size_t bounds_tile_queue_scratch_floats(int max_groups);
+int bounds_tile_queue_grid();         // workgroups of that launch (its items walk the grid in a stride loop)
 // bounds of the 8 children of the *d_groups expansions in `parents` (count known to the device only); max_groups sizes the grids
 // (d_chunks: QCtl::chunks -- the evaluation leaves chunk partials in `scratch` when it splits the cloud, and says so there)
 hipError_t launch_bounds_queue(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const ParentRec* parents, const int* d_groups,

@@ -2216,6 +2216,81 @@ void Engine::debug_bounds_tile(const float* rots9, const float* parents4, int ns
 	HIPCHK(hipMemcpy(stats, d_stats.get(), sizeof(unsigned) * 2, hipMemcpyDeviceToHost));
 }
 
+// What the two queue-round test entries share.  Set-up: the rotation, two searches (0: the upper-bound pass, coeff 0; 1: the lower-bound pass of
+// rotation level `level`) whose queues hold exactly the first cnt[s] of the given nodes (lower bound 0: all of them pass the stop rule against a
+// huge incumbent and, cnt <= K, all are selected; the list keeps the queue order), and a zeroed control block.  -> the twin lists are in use
+bool Engine::debug_queue_setup(QLane& L, const float R[9], int level, const float* parents4, const int cnt[2])
+{
+	std::vector<Rot9> rot(1);
+	std::memcpy(rot[0].r, R, sizeof(float) * 9);
+	upload_rots(rot);
+	const bool twins = p_.twin_fusion && L.d_psearch[0] != nullptr;
+	const int n = std::max(cnt[0], cnt[1]);
+	std::vector<QNode> nodes((size_t)n);
+	for (int i = 0; i < n; i++) nodes[(size_t)i] = QNode{parents4[4 * i], parents4[4 * i + 1], parents4[4 * i + 2], parents4[4 * i + 3], 0.f, 0.f};
+	for (int s = 0; s < 2; s++) {
+		QSearch& q = L.h_search[s];
+		std::memset(&q, 0, sizeof(q));
+		q.best = 1e30f; q.coeff = s ? rot_coeff(level) : 0.f; q.rot = 0; q.count = cnt[s]; q.min_ub = INFINITY; q.twin = twins ? (s ^ 1) : -1;
+		HIPCHK(hipMemcpyAsync(L.d_nodes + (size_t)s * kQueueCap, nodes.data(), sizeof(QNode) * (size_t)cnt[s], hipMemcpyHostToDevice, stream_));
+	}
+	HIPCHK(hipMemcpyAsync(L.d_search, L.h_search, sizeof(QSearch) * 2, hipMemcpyHostToDevice, stream_));
+	std::memset(L.h_ctl, 0, sizeof(QCtl));
+	L.h_ctl->tile_chunks = 1;
+	HIPCHK(hipMemcpyAsync(L.d_ctl, L.h_ctl, sizeof(QCtl), hipMemcpyHostToDevice, stream_));
+	return twins;
+}
+
+// the control block and the searches after the round
+void Engine::debug_queue_fetch(QLane& L)
+{
+	HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(L.h_search, L.d_search, sizeof(QSearch) * 2, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+}
+
+// Read-back: the children's bounds of both searches from the list they were evaluated in (`total` expansions; L.h_search[s].parent_off places
+// search s), in the order of parents4.  chunks > 1: the chunk partials of d_scratch are added here in chunk order -- in float, as the next
+// round's digest does (exact_sum false), or in double and rounded once, so that what comes back is the evaluation's error and not this sum's
+void Engine::debug_queue_gather(QLane& L, const ParentRec* d_list, int total, int chunks, const float* d_scratch, const float* d_ub, const float* d_lb, bool exact_sum,
+                                const float* parents4, const int cnt[2], float* const out[4])
+{
+	std::vector<ParentRec> listed((size_t)total);
+	HIPCHK(hipMemcpy(listed.data(), d_list, sizeof(ParentRec) * (size_t)total, hipMemcpyDeviceToHost));
+	std::vector<float> ub((size_t)kGroup * total), lb((size_t)kGroup * total), part;
+	if (chunks > 1) {
+		part.resize((size_t)total * chunks * 2 * kGroup);
+		HIPCHK(hipMemcpy(part.data(), d_scratch, sizeof(float) * part.size(), hipMemcpyDeviceToHost));
+	} else {
+		HIPCHK(hipMemcpy(ub.data(), d_ub, sizeof(float) * ub.size(), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(lb.data(), d_lb, sizeof(float) * lb.size(), hipMemcpyDeviceToHost));
+	}
+	for (int s = 0; s < 2; s++) {
+		const int off = L.h_search[s].parent_off;
+		if (off < 0 || off + cnt[s] > total) throw std::logic_error("goicp: debug queue round: a search's expansions lie outside the list");
+		float* ou = out[2 * s]; float* ol = out[2 * s + 1];
+		for (int e = 0; e < cnt[s]; e++) {
+			const ParentRec& pr = listed[(size_t)off + e];
+			if (pr.x != parents4[4 * e] || pr.y != parents4[4 * e + 1] || pr.z != parents4[4 * e + 2] || pr.w != parents4[4 * e + 3])
+				throw std::logic_error("goicp: debug queue round: the list is not in queue order");
+			for (int c = 0; c < kGroup; c++) {
+				if (chunks > 1) {
+					const float* sp = part.data() + (size_t)(off + e) * chunks * (2 * kGroup);
+					if (exact_sum) {
+						double a = 0.0, b = 0.0;
+						for (int j = 0; j < chunks; j++) { a += (double)sp[(size_t)j * 2 * kGroup + c]; b += (double)sp[(size_t)j * 2 * kGroup + kGroup + c]; }
+						ou[8 * e + c] = (float)a; ol[8 * e + c] = (float)b;
+					} else {
+						float a = 0.f, b = 0.f;
+						for (int j = 0; j < chunks; j++) { a += sp[(size_t)j * 2 * kGroup + c]; b += sp[(size_t)j * 2 * kGroup + kGroup + c]; }
+						ou[8 * e + c] = a; ol[8 * e + c] = b;
+					}
+				} else { ou[8 * e + c] = ub[(size_t)8 * (off + e) + c]; ol[8 * e + c] = lb[(size_t)8 * (off + e) + c]; }
+			}
+		}
+	}
+}
+
 void Engine::debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2])
 {
 	DeviceGuard guard(dev_);
@@ -2224,66 +2299,87 @@ void Engine::debug_queue_expand(const float R[9], int level, const float* parent
 	if (inliers_ < (int)N_) throw std::invalid_argument("goicp: debug_queue_expand: untrimmed engines only");
 	ensure_lane(0, 2);
 	QLane& L = ql_[0];
-	std::vector<Rot9> rot(1);
-	std::memcpy(rot[0].r, R, sizeof(float) * 9);
-	upload_rots(rot);
-	const bool twins = p_.twin_fusion && L.d_psearch[0] != nullptr;
-	// two searches whose queues hold exactly the given nodes (lower bound 0: all of them pass the stop rule against a huge incumbent and,
-	// n <= K, all are selected; the list keeps the queue order)
-	std::vector<QNode> nodes((size_t)n);
-	for (int i = 0; i < n; i++) nodes[(size_t)i] = QNode{parents4[4 * i], parents4[4 * i + 1], parents4[4 * i + 2], parents4[4 * i + 3], 0.f, 0.f};
-	for (int s = 0; s < 2; s++) {
-		QSearch& q = L.h_search[s];
-		std::memset(&q, 0, sizeof(q));
-		q.best = 1e30f; q.coeff = s ? rot_coeff(level) : 0.f; q.rot = 0; q.count = n; q.min_ub = INFINITY; q.twin = twins ? (s ^ 1) : -1;
-		HIPCHK(hipMemcpyAsync(L.d_nodes + (size_t)s * kQueueCap, nodes.data(), sizeof(QNode) * (size_t)n, hipMemcpyHostToDevice, stream_));
-	}
-	HIPCHK(hipMemcpyAsync(L.d_search, L.h_search, sizeof(QSearch) * 2, hipMemcpyHostToDevice, stream_));
-	std::memset(L.h_ctl, 0, sizeof(QCtl));
-	L.h_ctl->tile_chunks = 1;
-	HIPCHK(hipMemcpyAsync(L.d_ctl, L.h_ctl, sizeof(QCtl), hipMemcpyHostToDevice, stream_));
+	const int cnt[2] = {n, n};
+	const bool twins = debug_queue_setup(L, R, level, parents4, cnt);
 	QParams qp = queue_params();
 	qp.K = std::max(n, 1); qp.kmax = kQueueRoundPop; qp.tile_on = 0; qp.stale_widen = 0; qp.stale_compact = 0;
 	const int parity = 0, max_groups = 2 * n;
 	RoundOpts round;
 	round.twins = twins; round.count = false;
 	queue_round(L, 2, qp, parity, max_groups, round);
-	HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipMemcpyAsync(L.h_search, L.d_search, sizeof(QSearch) * 2, hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipStreamSynchronize(stream_));
+	debug_queue_fetch(L);
 	if (L.h_ctl->overflow || L.h_ctl->n_groups[parity] != 2 * n || L.h_search[0].n_parents != n || L.h_search[1].n_parents != n)
 		throw std::logic_error("goicp: debug_queue_expand: the round did not list every node");
 	const int chunks = L.h_ctl->chunks;
 	info[0] = chunks; info[1] = twins ? 1 : 0;
-	std::vector<ParentRec> listed((size_t)2 * n);
-	HIPCHK(hipMemcpy(listed.data(), L.d_parents[parity], sizeof(ParentRec) * 2 * (size_t)n, hipMemcpyDeviceToHost));
-	std::vector<float> ub((size_t)16 * n), lb((size_t)16 * n), part;
-	if (chunks > 1) {
-		part.resize((size_t)2 * n * chunks * 2 * kGroup);
-		HIPCHK(hipMemcpy(part.data(), L.d_scratch, sizeof(float) * part.size(), hipMemcpyDeviceToHost));
-	} else {
-		HIPCHK(hipMemcpy(ub.data(), L.d_ub, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(lb.data(), L.d_lb, sizeof(float) * 16 * (size_t)n, hipMemcpyDeviceToHost));
-	}
+	float* const out[4] = {ub0, lb0, ub1, lb1};
+	debug_queue_gather(L, L.d_parents[parity], 2 * n, chunks, L.d_scratch, L.d_ub, L.d_lb, false, parents4, cnt, out);
+}
+
+void Engine::debug_queue_expand_tiles(const float R[9], int level, const float* parents4, int n, int n_ub, float* ub0, float* lb0, float* ub1, float* lb1, int info[4],
+                                      const QueueDigest* dg)
+{
+	DeviceGuard guard(dev_);
+	if (n < 1 || n > kQueueRoundPop || n_ub < 1 || n_ub > n) throw std::invalid_argument("goicp: debug_queue_expand_tiles takes 1..128 nodes, 1..n of them in the upper-bound search");
+	if (!(p_.device_queues && p_.trans_batch > 1 && p_.wide_children)) throw std::invalid_argument("goicp: debug_queue_expand_tiles needs the device-queue configuration");
+	if (!tiles_usable()) throw std::invalid_argument("goicp: debug_queue_expand_tiles needs the tile list (lds_tiles, the bricked fp32 grid, no trimming)");
+	ensure_lane(0, 2);
+	QLane& L = ql_[0];
+	if (!L.tile.ub) throw std::logic_error("goicp: debug_queue_expand_tiles: the lane has no tile list");
+	const int cnt[2] = {n_ub, n};
+	const bool twins = debug_queue_setup(L, R, level, parents4, cnt);
+	QParams qp = queue_params();
+	qp.K = n; qp.kmax = kQueueRoundPop; qp.stale_widen = 0; qp.stale_compact = 0;
+	qp.tile_on = 1; qp.tile_min = 1; qp.tile_spread = 1e30f;              // any selection qualifies, however far apart its nodes lie
+	const int parity = 0, total = n_ub + n;
+	// every row the evaluation does not write reads back as NaN: an item that never stored its sums cannot pass for one that did
+	HIPCHK(hipMemsetAsync(L.tile.scratch, 0xff, sizeof(float) * bounds_tile_queue_scratch_floats(L.seg_cap), stream_));
+	HIPCHK(hipMemsetAsync(L.tile.ub, 0xff, sizeof(float) * (size_t)L.list_cap * kGroup, stream_));
+	HIPCHK(hipMemsetAsync(L.tile.lb, 0xff, sizeof(float) * (size_t)L.list_cap * kGroup, stream_));
+	RoundOpts round;
+	round.tiles = true; round.twins = twins; round.count = false;
+	queue_round(L, 2, qp, parity, 2 * n, round);
+	debug_queue_fetch(L);
+	const QCtl& c = *L.h_ctl;
+	if (c.overflow || c.n_groups[parity] != 0 || c.n_tile_groups[parity] != total || L.h_search[0].n_parents != n_ub || L.h_search[1].n_parents != n ||
+	    L.h_search[0].tile != 1 || L.h_search[1].tile != 1)
+		throw std::logic_error("goicp: debug_queue_expand_tiles: the round did not list every node in the tile list");
+	const int chunks = c.tile_chunks, nsegs = c.n_tile_segs[parity];
+	if (chunks < 1 || nsegs != (n_ub + 63) / 64 + (n + 63) / 64) throw std::logic_error("goicp: debug_queue_expand_tiles: unexpected tile shape");
+	info[0] = chunks; info[1] = nsegs; info[2] = bounds_tile_queue_grid(); info[3] = twins ? 1 : 0;
+	float* const out[4] = {ub0, lb0, ub1, lb1};
+	// (the chunk partials are added in double: up to 342 of them in a test, which a float sum's own rounding would blur)
+	debug_queue_gather(L, L.tile.parents[parity], total, chunks, L.tile.scratch, L.tile.ub, L.tile.lb, true, parents4, cnt, out);
+	if (!dg) return;
+	// the next round's queue kernel alone: it digests the tile list's bounds (S->tile: tile.parents[0], tile.ub / lb or tile.scratch with
+	// ctl->tile_chunks) and selects one node per search
+	QParams q2 = qp;
+	q2.K = 1; q2.tile_on = 0;
+	HIPCHK(launch_bnb_queue(L.d_search, L.d_nodes, 2, q2, L.d_parents[0], L.d_parents[1], L.d_ub, L.d_lb, L.d_scratch, L.d_ctl, 1, stream_, &L.tile,
+	                        twins ? L.d_psearch[1].get() : nullptr, true));
+	HIPCHK(hipMemcpyAsync(L.h_ctl, L.d_ctl, sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(L.h_search, L.d_search, sizeof(QSearch) * 2, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (L.h_ctl->overflow) throw std::logic_error("goicp: debug_queue_expand_tiles: the digest overflowed");
 	for (int s = 0; s < 2; s++) {
-		const int off = L.h_search[s].parent_off;
-		float* ou = s ? ub1 : ub0; float* ol = s ? lb1 : lb0;
-		for (int e = 0; e < n; e++) {
-			const ParentRec& pr = listed[(size_t)off + e];
-			if (pr.x != parents4[4 * e] || pr.y != parents4[4 * e + 1] || pr.z != parents4[4 * e + 2] || pr.w != parents4[4 * e + 3])
-				throw std::logic_error("goicp: debug_queue_expand: the list is not in queue order");
-			for (int c = 0; c < kGroup; c++) {
-				if (chunks > 1) {
-					// the chunk partials, added in chunk order as the next round's digest does (bnbqueue.hip)
-					float a = 0.f, b = 0.f;
-					for (int j = 0; j < chunks; j++) {
-						const float* sp = part.data() + ((size_t)(off + e) * chunks + j) * (2 * kGroup);
-						a += sp[c]; b += sp[kGroup + c];
-					}
-					ou[8 * e + c] = a; ol[8 * e + c] = b;
-				} else { ou[8 * e + c] = ub[(size_t)8 * (off + e) + c]; ol[8 * e + c] = lb[(size_t)8 * (off + e) + c]; }
-			}
+		const QSearch& S = L.h_search[s];
+		// (a search that stopped on the stop rule lists nothing and keeps the flags of its last selection)
+		if (S.count < 0 || S.count > 8 * cnt[s] || S.n_parents < 0 || S.n_parents > 1 || (S.n_parents == 1 && S.tile != 0) || (S.n_parents == 0 && S.done != 1))
+			throw std::logic_error("goicp: debug_queue_expand_tiles: unexpected queue after the digest");
+		dg->counts[2 * s] = S.count; dg->counts[2 * s + 1] = S.n_parents;
+		if (S.count > 0) {
+			static_assert(sizeof(QNode) == 6 * sizeof(float), "a queue node is six floats");
+			HIPCHK(hipMemcpy(dg->nodes + (size_t)s * 8 * n * 6, L.d_nodes + (size_t)s * kQueueCap, sizeof(QNode) * (size_t)S.count, hipMemcpyDeviceToHost));
 		}
+		float* li = dg->listed + 4 * s;
+		li[0] = li[1] = li[2] = li[3] = 0.f;
+		if (S.n_parents == 1) {
+			ParentRec pr;
+			HIPCHK(hipMemcpy(&pr, L.d_parents[1].get() + S.parent_off, sizeof(ParentRec), hipMemcpyDeviceToHost));
+			li[0] = pr.x; li[1] = pr.y; li[2] = pr.z; li[3] = pr.w;
+		}
+		float* so = dg->search + 8 * s;
+		so[0] = S.best; so[1] = S.min_ub; so[2] = (float)S.improved; so[3] = S.bx; so[4] = S.by; so[5] = S.bz; so[6] = S.bw; so[7] = (float)S.done;
 	}
 }
 

@@ -233,6 +233,19 @@ public:
 	void debug_bounds_order(int info[3]);   // test: form of the last eval_bounds_dev launch, and what its pre-pass decided (device.hip BoundsOrder::ctl)
 	void debug_bounds_twins(int info[2]);   // test: items of that launch evaluated in twin form and in identical form (BoundsOrder::ctl[2], [3])
 	void debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2]);
+	// test: the same round with the TILE list on (tile_min 1, no spread limit): both searches list their nodes there and nothing in the direct
+	// list; the upper-bound search queues only the first n_ub nodes (out arrays: 8 n_ub and 8 n floats).  info = {tile chunks the device chose,
+	// tile segments, workgroups of the tile launch, twin lists in use}.  The tile buffers are filled with NaN before the round: a row the
+	// evaluation never wrote cannot pass for one it did.  dg (may be null): the queue kernel is launched once more (K = 1) and
+	// digests the round from the tile buffers -- what it pushed, what it listed next and the searches' incumbents come back in *dg.
+	struct QueueDigest {
+		float* nodes;      // [2][8 n][6]: the queue of search s after the digest and the next selection (corner, width, ub, lb per node)
+		int* counts;       // [2][2]: nodes in that queue, nodes the selection took out of it
+		float* listed;     // [2][4]: the node taken (corner, width), when one was
+		float* search;     // [2][8]: best, min_ub, improved, bx, by, bz, bw, done
+	};
+	void debug_queue_expand_tiles(const float R[9], int level, const float* parents4, int n, int n_ub, float* ub0, float* lb0, float* ub1, float* lb1, int info[4],
+	                              const QueueDigest* dg);
 	// measurement / test: the 8 children of nseg x n expansions (segment i: rotation i, parents4[(i*n + e)*4 ..] = corner xyz + width) through
 	// the LDS-tile kernel and through the direct kernel; out arrays hold 8*nseg*n floats each; ms[0] tile, ms[1] direct (per launch)
 	void debug_bounds_tile(const float* rots9, const float* parents4, int nseg, int n, int level, int chunks, float* ub_tile, float* lb_tile,
@@ -475,6 +488,11 @@ private:
 	                                                        // 5.06 / 5.02 / 5.48 s, synthetic 40 k mse 3e-5 621 / 621 / 681 ms, 3 k points mse 3e-5 1 033 / 1 016 / 1 100 ms, bunny mse 1e-4 259 / 261 / 268 ms)
 	int lanes_ = 0, lane_min_searches_ = 64;                // Params::lanes / lane_min_searches
 	bool tiles_usable() const;
+	// shared by debug_queue_expand and debug_queue_expand_tiles (engine.cpp)
+	bool debug_queue_setup(QLane& L, const float R[9], int level, const float* parents4, const int cnt[2]);
+	void debug_queue_fetch(QLane& L);
+	void debug_queue_gather(QLane& L, const ParentRec* d_list, int total, int chunks, const float* d_scratch, const float* d_ub, const float* d_lb, bool exact_sum,
+	                        const float* parents4, const int cnt[2], float* const out[4]);
 	long long sel_hist_[4][4] = {};       // verbose: QCtl::sel_hist summed over the registration
 	bool tile_sticky_ = false;            // lds_tiles == 2: the previous batch evaluated expansions from tiles -> this batch launches the tile list in every round
 	static constexpr double kTileStickyShare = 0.5;   // ... when at least this share of the previous batch's cube bounds came from tiles

@@ -403,6 +403,21 @@ int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, co
 	});
 }
 
+int goicp_debug_queue_expand_tiles(goicp_handle h, const float R[9], int32_t level, const float* parents4, int32_t n, int32_t n_ub, float* ub_ubpass,
+                                   float* lb_ubpass, float* ub_lbpass, float* lb_lbpass, int32_t info[4], int32_t digest, float* queue_nodes,
+                                   int32_t* queue_counts, float* listed4, float* search8)
+{
+	REQUIRE(h && R && parents4 && ub_ubpass && lb_ubpass && ub_lbpass && lb_lbpass && info && n >= 1 && n_ub >= 1 && n_ub <= n);
+	REQUIRE(!digest || (queue_nodes && queue_counts && listed4 && search8));
+	return guarded([&] {
+		int inf[4] = {0, 0, 0, 0}, counts[4] = {0, 0, 0, 0};
+		const goicp::Engine::QueueDigest dg{queue_nodes, counts, listed4, search8};
+		h->e->debug_queue_expand_tiles(R, level, parents4, n, n_ub, ub_ubpass, lb_ubpass, ub_lbpass, lb_lbpass, inf, digest ? &dg : nullptr);
+		for (int k = 0; k < 4; k++) info[k] = inf[k];
+		if (digest) for (int k = 0; k < 4; k++) queue_counts[k] = counts[k];
+	});
+}
+
 int goicp_debug_bounds_order(goicp_handle h, int32_t info[3])
 {
 	REQUIRE(h && info);

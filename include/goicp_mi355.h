@@ -889,6 +889,20 @@ int goicp_debug_bounds_tile(goicp_handle h, const float* rots9, const float* par
  */
 int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, const float* parents4, int32_t n, float* ub_ubpass, float* lb_ubpass,
                              float* ub_lbpass, float* lb_lbpass, int32_t info[2]);
+/*
+ * goicp_debug_queue_expand_tiles (test): goicp_debug_queue_expand with the round's TILE list on -- tile_min 1 and no spread limit, so both
+ * searches list every node there and nothing in the direct list (GOICP_ERR_INTERNAL otherwise) -- evaluated by the queued LDS-tile kernel
+ * (segment count and cloud split chosen on the device).  The upper-bound search queues only the first n_ub (1 <= n_ub <= n) nodes:
+ * ub_ubpass / lb_ubpass hold 8 n_ub floats, ub_lbpass / lb_lbpass 8 n; with more than one point chunk the chunk partials are added on the
+ * host in chunk order, in double (rounded once).  info = {point chunks, segments, workgroups of the tile launch, twin lists in use}.  GOICP_ERR_INVALID on a handle
+ * without the tile list (lds_tiles 0, dt_layout 0, bounds_fp16, trimmed).
+ * digest != 0: the queue kernel is launched once more (K = 1) and digests that round from the tile buffers.  queue_nodes[s][8 n][6] = the
+ * queue of search s afterwards (corner xyz, width, ub, lb per node), queue_counts[s] = {nodes in it, nodes the new selection took out (0 / 1)},
+ * listed4[s] = that node (corner xyz, width), search8[s] = {best, min_ub, improved, bx, by, bz, bw, done}; s = 0 upper-, 1 lower-bound search.
+ */
+int goicp_debug_queue_expand_tiles(goicp_handle h, const float R[9], int32_t level, const float* parents4, int32_t n, int32_t n_ub, float* ub_ubpass,
+                                   float* lb_ubpass, float* ub_lbpass, float* lb_lbpass, int32_t info[4], int32_t digest, float* queue_nodes,
+                                   int32_t* queue_counts, float* listed4, float* search8);
 /* goicp_debug_bounds_order (test): how the last goicp_eval_bounds_device / goicp_time_bounds_device launch of this handle walked its batch.
  * info[0] = the form launched (goicp_params::bounds_order: 0 the plain launch -- switch off, fewer groups than bounds_order_min_groups, not
  * a bricked fp32 grid in the Infinity Cache --, 1 ordered, 2 ordered + pairs); for forms 1 and 2, read back after the launch has finished:
