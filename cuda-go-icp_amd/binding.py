@@ -184,6 +184,10 @@ SYMBOLS = {
     "goicp_set_icp_options": (C.c_int, [_vp, C.POINTER(CIcpOptions)]),
     "goicp_knn_query": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_target_normals": (C.c_int, [_vp, _fp]),
+    "goicp_set_icp_symmetric": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "goicp_get_icp_symmetric": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "goicp_source_normals": (C.c_int, [_vp, _fp]),
+    "goicp_set_source_normals": (C.c_int, [_vp, _fp, C.c_size_t]),
     "goicp_icp_gate_default": (None, [C.POINTER(CIcpGate)]),
     "goicp_set_icp_gate": (C.c_int, [_vp, C.POINTER(CIcpGate)]),
     "goicp_icp_inliers": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int32)]),

@@ -1,6 +1,6 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
-//                                [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
+//                                [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
 //                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
 //                                [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]
 //                                [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]
@@ -13,6 +13,9 @@
 //               reference's own .toml files are then not comparable with the strict-order goldens: use the flag for parity runs.
 //   --point-to-plane   every ICP of the run is point-to-plane (goicp_set_icp_options metric 1; --normal-k K neighbours per target
 //               normal, default 16).  Refused together with --ranks N > 1: the multi-GPU registration runs point-to-point ICP
+//   --symmetric   implies --point-to-plane; every ICP of the run takes the symmetric point-to-plane form over the normals of both clouds
+//               (goicp_set_icp_symmetric; --source-normal-k K neighbours per source normal, 3..32, default 16).  Refused together with
+//               --ranks N > 1 and --trim-fraction F > 0, and with K out of range -- before any device is touched
 //   --max-corr-dist D   every ICP of the run uses only correspondences within distance D (goicp_set_icp_gate; cloud units after
 //               `resize`); output.toml then gets an [icp_gate] table with D and the inlier count of the final pose.  D must be a finite
 //               number > 0, and the flag is refused together with --ranks N > 1 and --trim-fraction F > 0 -- before any device is touched
@@ -196,8 +199,9 @@ int main(int argc, char** argv)
 {
 	for (int i = 1; i < argc; i++)
 		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]\n"); return 2; }
-	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16;
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]\n"); return 2; }
+	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16;
+	const char* snk_arg = nullptr;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
 	const char* gate_arg = nullptr;
@@ -232,6 +236,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--reference-root")) reference_root = 1;
 		else if (!std::strcmp(argv[i], "--point-to-plane")) plane = 1;
 		else if (!std::strcmp(argv[i], "--normal-k") && i + 1 < argc) normal_k = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--symmetric")) symmetric = plane = 1;
+		else if (!std::strcmp(argv[i], "--source-normal-k")) snk_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--max-corr-dist")) gate_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-kernel")) rk_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-scale")) rc_arg = i + 1 < argc ? argv[++i] : "";
@@ -432,6 +438,23 @@ int main(int argc, char** argv)
 			return 2;
 		}
 	}
+	if (snk_arg) {
+		char* end = nullptr;
+		const long k = std::strtol(snk_arg, &end, 10);
+		if (end == snk_arg || *end != '\0' || k < 3 || k > GOICP_KNN_SELF_MAX) {
+			std::fprintf(stderr, "error: --source-normal-k needs an integer in 3..%d, got '%s'\n", GOICP_KNN_SELF_MAX, snk_arg);
+			return 2;
+		}
+		if (!symmetric) {
+			std::fprintf(stderr, "error: --source-normal-k goes with --symmetric\n");
+			return 2;
+		}
+		source_normal_k = (int)k;
+	}
+	if (symmetric && (ranks > 1 || trim_fraction > 0.f)) {
+		std::fprintf(stderr, "error: --symmetric cannot be combined with --ranks N > 1 (the multi-GPU registration runs point-to-point ICP) or --trim-fraction F > 0\n");
+		return 2;
+	}
 	if (plane && ranks > 1) {
 		// the multi-GPU registration runs point-to-point ICP only: refused before any device is touched
 		std::fprintf(stderr, "error: --point-to-plane cannot be combined with --ranks N > 1 (the multi-GPU registration runs point-to-point ICP)\n");
@@ -525,6 +548,7 @@ int main(int argc, char** argv)
 		icp::FastGoICP engine(target, source, config.mse_threshold, mtx, &p);
 		goicp_handle h = engine.registration.handle();
 		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
+		if (symmetric) engine.registration.set_icp_symmetric(true, source_normal_k);
 		if (gate > 0.f) engine.registration.set_icp_gate(gate);
 		if (robust_kernel) engine.registration.set_icp_robust(robust_kernel, robust_scale);
 		if (trunc > 0.f) engine.registration.set_search_truncation(trunc);
@@ -549,6 +573,15 @@ int main(int argc, char** argv)
 		for (int i = 0; i < 3; i++) std::printf("%12.7f %12.7f %12.7f\n", R[3 * i], R[3 * i + 1], R[3 * i + 2]);
 		std::printf("Optimal Translation Vector:\n%12.7f\n%12.7f\n%12.7f\n", t[0], t[1], t[2]);
 		if (!config.io.output.empty()) engine.write_output(config.io.output);
+		if (symmetric) {
+			std::printf("ICP metric: symmetric point-to-plane (normal_k %d, source_normal_k %d)\n", normal_k, source_normal_k);
+			if (!config.io.output.empty()) {
+				FILE* f = std::fopen(config.io.output.c_str(), "a");
+				if (!f) throw std::runtime_error("cannot append to " + config.io.output);
+				std::fprintf(f, "\n[icp_symmetric]\nenabled = true\nsource_normal_k = %d\n", source_normal_k);
+				std::fclose(f);
+			}
+		}
 		if (gate > 0.f) {
 			int32_t n_in = 0;
 			check(goicp_eval_correspondences(h, R, t, gate, nullptr, nullptr, &n_in, nullptr));
@@ -571,7 +604,8 @@ int main(int argc, char** argv)
 			goicp_pose_info_options_default(&io);
 			if (rank_tol >= 0.0) io.rank_tol = rank_tol;
 			const goicp_pose_info I = engine.registration.pose_information(R, t, &io);
-			std::printf("Information: rank %d of 6, sigma %.7g (metric %d, %lld inliers)\n", (int)I.rank, std::sqrt(I.sigma2), (int)I.metric, (long long)I.inliers);
+			std::printf("Information: rank %d of 6, sigma %.7g (metric %d%s, %lld inliers)\n", (int)I.rank, std::sqrt(I.sigma2), (int)I.metric,
+			            symmetric && I.metric == 1 ? " symmetric" : "", (long long)I.inliers);
 			if (!config.io.output.empty()) {
 				FILE* f = std::fopen(config.io.output.c_str(), "a");
 				if (!f) throw std::runtime_error("cannot append to " + config.io.output);

@@ -3698,9 +3698,29 @@ hipError_t launch_normal_build(const float* target_xyz, int nslots, int k, const
 // ROBUST (goicp_set_icp_robust; the plain walk): the 27 terms of J J^T and J r are multiplied by robust_terms' weight of |r| (d^2 stays unweighted),
 // each term times its row's weight in the column sums;
 // w goes to word 28 (scaled by kIcpRobustWScale), rho -- of the distance d, the quantity the plain plane loop's stop test reads -- to word 29
-template <int K, int LAYOUT, bool STRIDED, bool GATE = false, bool ROBUST = false>
+// SYM (goicp_set_icp_symmetric; include/goicp_mi355.h "symmetric point-to-plane"): the owner also loads the source normal of its query
+// (src_normals, parallel to src), rotates it by R, turns it to the target normal's side, and takes n = (s + nm) / 2 and the midpoint
+// c = a - e / 2 in the place of nm and a: r = e . n, J = (c x n, n).  |n| <= 1 and c lies between a and m - cq, so the 28 terms keep the plane
+// pass's bound; everything after J and r is the plane pass's text
+// -> (n, h): h = 0.5f, or 0 where the source normal is exactly zero -- the correspondence is then plain point-to-plane, n = nm and c = a - h e = a
+__device__ __forceinline__ float4 symmetric_normal(const float* R, const float4& ns, const float4& nm)
+{
+	float sx = R[0] * ns.x + R[1] * ns.y + R[2] * ns.z;          // q's row expression without t
+	float sy = R[3] * ns.x + R[4] * ns.y + R[5] * ns.z;
+	float sz = R[6] * ns.x + R[7] * ns.y + R[8] * ns.z;
+	float dot = sx * nm.x;
+	dot += sy * nm.y;
+	dot += sz * nm.z;
+	if (dot < 0.f) { sx = -sx; sy = -sy; sz = -sz; }                  // the same side as the target's normal
+	const bool s0 = sx == 0.f && sy == 0.f && sz == 0.f, m0 = nm.x == 0.f && nm.y == 0.f && nm.z == 0.f;
+	if (s0) return make_float4(nm.x, nm.y, nm.z, 0.f);                // no source normal: plain point-to-plane (both zero: n = 0)
+	if (m0) return make_float4(sx, sy, sz, 0.5f);
+	return make_float4(0.5f * (sx + nm.x), 0.5f * (sy + nm.y), 0.5f * (sz + nm.z), 0.5f);
+}
+
+template <int K, int LAYOUT, bool STRIDED, bool GATE = false, bool ROBUST = false, bool SYM = false>
 __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, const IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                                                    unsigned long long* acc, int capped = 0)
+                                                    unsigned long long* acc, int capped = 0, const float4* src_normals = nullptr)
 {
 	static_assert(!ROBUST || !GATE, "a robust kernel and a gate exclude each other");
 	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
@@ -3733,9 +3753,15 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 		float* dst = red[wrow];
 		float J[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f, d2 = 0.f;
 		if (inlier) {
-			const float4 nm = normals[r.idx];                         // one gather per correspondence (by original index: the walk's slot is dead)
-			const float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];
+			float4 nm = normals[r.idx];                               // one gather per correspondence (by original index: the walk's slot is dead)
+			float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];
 			const float ex = qx - r.mx, ey = qy - r.my, ez = qz - r.mz;
+			if constexpr (SYM) {
+				const float4 ns = src_normals[ic];                    // the query's own normal: one coalesced load (an inlier's ic is its i)
+				const float4 n = symmetric_normal(st->R, ns, nm);
+				nm.x = n.x; nm.y = n.y; nm.z = n.z;
+				ax -= n.w * ex; ay -= n.w * ey; az -= n.w * ez;           // c: the midpoint of the correspondence relative to the pivot
+			}
 			res = ex * nm.x;
 			res += ey * nm.y;
 			res += ez * nm.z;
@@ -3781,12 +3807,14 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 // BATCH (goicp_icp_run_batch): grid (icp_blocks(N), active poses); blockIdx.y picks a pose slot from the device list `active`, slot s owns states[s]
 // and the accumulator block acc + s * kIcpBatchAccWords.  Every workgroup runs the single-pose body on that slot: the same 16 queries, the same float
 // row sums, the same acc_scale, the same replica -- and integer addition is associative, so the slot's totals are the single-pose totals bit for bit,
-// whatever else the grid holds.  `normals` is read by METRIC 1 only, `active` by BATCH only, `capped` by the gated mode only.
+// whatever else the grid holds.  `normals` is read by METRIC 1 and 2 only, `active` by BATCH only, `capped` by the gated mode only.
+// METRIC 2 is internal: metric 1 on a handle with goicp_set_icp_symmetric on; `src_normals` (parallel to src) is read by it alone.
 template <int K, int LAYOUT, bool STRIDED, int METRIC, int MODE, bool BATCH>
 __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_kernel(const float4* __restrict__ src, int N,
                                                                       IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
-                                                                      const int* __restrict__ active, int capped)
+                                                                      const int* __restrict__ active, int capped,
+                                                                      const float4* __restrict__ src_normals)
 {
 	constexpr bool GATE = MODE == kIcpModeGate, ROBUST = MODE == kIcpModeRobust;
 	IcpState* st = states;
@@ -3799,7 +3827,7 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_
 	if constexpr (METRIC == 0)
 		icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, GATE, ROBUST>(src, N, st, kd, dt, reinterpret_cast<float*>(a), nullptr, nullptr, nullptr, 0, capped);
 	else
-		icp_plane_pass_body<K, LAYOUT, STRIDED, GATE, ROBUST>(src, N, st, kd, dt, normals, a, capped);
+		icp_plane_pass_body<K, LAYOUT, STRIDED, GATE, ROBUST, METRIC == 2>(src, N, st, kd, dt, normals, a, capped, src_normals);
 }
 
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
@@ -3970,14 +3998,15 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_opt_finalize_kernel(unsign
 		a = acc + (size_t)s * kIcpBatchAccWords;
 	}
 	if constexpr (METRIC == 0 && MODE == kIcpModePlain) finalize_acc_body(a, st);
-	else icp_plane_finalize_body<MODE == kIcpModeGate, METRIC == 1, MODE == kIcpModeRobust>(a, st);
+	else icp_plane_finalize_body<MODE == kIcpModeGate, METRIC != 0, MODE == kIcpModeRobust>(a, st);
 }
 
 // ---- the opt-in iterations (point-to-plane, gate, robust kernel; single pose and goicp_icp_run_batch): one pass, then the finalize ----
 hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream)
 {
 	const bool batch = a.active != nullptr;
-	if (!a.states || !a.acc || (a.metric != 0 && a.metric != 1) || (a.metric == 1 && !a.normals) || a.mode < kIcpModePlain || a.mode > kIcpModeRobust)
+	if (!a.states || !a.acc || a.metric < 0 || a.metric > 2 || (a.metric != 0 && !a.normals) || (a.metric == 2 && !a.src_normals) || a.mode < kIcpModePlain ||
+	    a.mode > kIcpModeRobust)
 		return hipErrorInvalidValue;
 	if (!dt.layout && (a.metric == 0 || a.mode != kIcpModePlain)) return hipErrorInvalidValue;   // the linear DT: the plain plane pass only
 	if (a.n_active < 1 || a.n_active > kIcpBatchMax || (!batch && a.n_active != 1)) return hipErrorInvalidValue;
@@ -3987,16 +4016,19 @@ hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const
 		with_flag(a.N <= kIcpStridedMaxN, [&](auto S) {       // the default pass's choice: strangers per wavefront for small clouds
 			auto go = [&](auto L, auto M, auto MODE, auto B) {
 				hipLaunchKernelGGL((icp_opt_pass_kernel<K(), L(), S(), M(), MODE(), B()>), pass_grid, dim3(kIcpThreads), 0, stream, a.src, a.N, a.states, kd, dt,
-				                   a.normals, a.acc, a.active, a.capped);
+				                   a.normals, a.acc, a.active, a.capped, a.src_normals);
 				hipLaunchKernelGGL((icp_opt_finalize_kernel<M(), MODE(), B()>), fin_grid, dim3(kFinAccThreads), 0, stream, a.acc, a.states, a.active);
 			};
 			constexpr std::integral_constant<int, 0> c0{};
 			constexpr std::integral_constant<int, 1> c1{};
+			constexpr std::integral_constant<int, 2> c2{};
 			// the instantiations: the linear DT with the plain plane pass only; plain point-to-point in a batch only
 			if (a.mode != kIcpModePlain)
-				with_flag(a.metric, [&](auto M) { with_value<kIcpModeGate, kIcpModeRobust>(a.mode, [&](auto MODE) { with_flag(batch, [&](auto B) { go(c1, M, MODE, B); }); }); });
+				with_value<2, 1, 0>(a.metric, [&](auto M) { with_value<kIcpModeGate, kIcpModeRobust>(a.mode, [&](auto MODE) { with_flag(batch, [&](auto B) { go(c1, M, MODE, B); }); }); });
 			else if (a.metric == 1)
 				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c1, c0, B); }); });
+			else if (a.metric == 2)
+				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c2, c0, B); }); });
 			else
 				go(c1, c0, c0, c1);
 		});
@@ -4050,9 +4082,43 @@ hipError_t launch_eval_correspondences(const float4* src, int N, const Pose& pos
 //   METRIC 1 (31 words): sum w j j^T, upper triangle (21) | sum w j r (6) | sum w r^2 | sum d^2 | W | n_in, j = (a x n, n), r = e . n;
 //            the 28 weighted terms go to LDS unweighted and the column sums multiply by the row's w, as the robust plane pass does
 // W is scaled by kIcpRobustWScale, n_in (rows with w > 0) is a plain integer, every other word by PoseInfoArgs::scale.
+//   METRIC 2 (internal; the symmetric form of metric 1): metric 1's words with n = symmetric_normal and j = (c x n, n), c = a - e / 2,
+//            in two phases -- the owner stores the row's raw inputs, pose_info_symmetric_row forms the words behind a barrier
+// METRIC 2, second phase: one lane per row turns the row's raw inputs (a, e, nm, d^2, the query's index; the last word: the row has a query)
+// into metric 1's 31 words
+__device__ __forceinline__ void pose_info_symmetric_row(float* dst, const PoseInfoArgs& pa, const float4* src_normals)
+{
+	if (dst[kIcpPlaneStride - 1] == 0.f) return;
+	float ax = dst[0], ay = dst[1], az = dst[2];
+	const float ex = dst[3], ey = dst[4], ez = dst[5], d2 = dst[9];
+	const float4 nm = make_float4(dst[6], dst[7], dst[8], 0.f);
+	const float4 n = symmetric_normal(pa.R, src_normals[__float_as_int(dst[10])], nm);
+	ax -= n.w * ex; ay -= n.w * ey; az -= n.w * ez;           // c: the midpoint of the correspondence relative to the pivot
+	float res = ex * n.x;
+	res += ey * n.y;
+	res += ez * n.z;
+	float J[6];
+	J[0] = ay * n.z - az * n.y;
+	J[1] = az * n.x - ax * n.z;
+	J[2] = ax * n.y - ay * n.x;
+	J[3] = n.x; J[4] = n.y; J[5] = n.z;
+	int k = 0;
+#pragma unroll
+	for (int a = 0; a < 6; a++)
+#pragma unroll
+		for (int b = a; b < 6; b++) dst[k++] = J[a] * J[b];
+#pragma unroll
+	for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
+	dst[27] = res * res;
+	dst[28] = d2;
+	float w = d2 <= pa.g2 ? 1.f : 0.f;
+	if (pa.rk) w = robust_terms(pa.rk, pa.rc, fabsf(res), __fsqrt_rn(d2), d2).w;
+	dst[29] = w;
+	dst[30] = w > 0.f ? 1.f : 0.f;
+}
 template <int K, int METRIC>
 __device__ __forceinline__ void pose_info_body(const float4* src, int N, const PoseInfoArgs& pa, int strided, const KdDesc& kd, const DtDesc& dt,
-                                               const float4* normals, unsigned long long* acc)
+                                               const float4* normals, unsigned long long* acc, const float4* src_normals = nullptr)
 {
 	constexpr int kWords = kPoseInfoWords[METRIC];
 	constexpr int kWordW = METRIC ? 29 : 0, kWordN = METRIC ? 30 : 18;
@@ -4076,6 +4142,7 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 		if (!valid) {
 #pragma unroll
 			for (int k = 0; k < kWords; k++) dst[k] = 0.f;       // a row without a query: no terms, no weight, no count
+			if constexpr (METRIC == 2) dst[kIcpPlaneStride - 1] = 0.f;
 		} else {
 			const float d2 = r.best;
 			const float ax = qx - pa.c[0], ay = qy - pa.c[1], az = qz - pa.c[2];
@@ -4096,6 +4163,19 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 				dst[17] = d2;
 				dst[kWordN] = w > 0.f ? 1.f : 0.f;
 			} else {
+				if constexpr (METRIC == 2) {
+					// the row's raw inputs go to LDS; sixteen lanes form the symmetric terms from them after the barrier below, so the walk keeps
+					// metric 1's registers (its K = 3 form is at the 64-VGPR bound).  The query's index again (a valid row's i is below N), from
+					// the lane and wave numbers as the hardware gives them
+					const float4 nm = normals[r.idx];
+					const int wave2 = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6, row2 = (int)__lane_id() >> 4;
+					const int wv2 = gb * (kIcpThreads / 64) + wave2;
+					dst[0] = ax; dst[1] = ay; dst[2] = az; dst[3] = ex; dst[4] = ey; dst[5] = ez;
+					dst[6] = nm.x; dst[7] = nm.y; dst[8] = nm.z; dst[9] = d2;
+					dst[10] = __int_as_float(strided ? wv2 + row2 * nw : wv2 * 4 + row2);
+					static_assert(kWords < kIcpPlaneStride, "the row's spare word");
+					dst[kIcpPlaneStride - 1] = 1.f;
+				} else {
 				const float4 nm = normals[r.idx];                     // by original index, as the plane pass gathers it
 				float res = ex * nm.x;
 				res += ey * nm.y;
@@ -4118,12 +4198,17 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 				if (pa.rk) w = robust_terms(pa.rk, pa.rc, fabsf(res), __fsqrt_rn(d2), d2).w;
 				dst[kWordW] = w;
 				dst[kWordN] = w > 0.f ? 1.f : 0.f;
+				}
 			}
 		}
 	}
 	__syncthreads();
+	if constexpr (METRIC == 2) {
+		if (threadIdx.x < kIcpThreads / 16) pose_info_symmetric_row(red[threadIdx.x], pa, src_normals);
+		__syncthreads();
+	}
 	if (threadIdx.x < kWords) {
-		const bool weighted = METRIC == 1 && threadIdx.x < 28;
+		const bool weighted = METRIC != 0 && threadIdx.x < 28;
 		float sum = weighted ? red[0][threadIdx.x] * red[0][kWordW] : red[0][threadIdx.x];
 #pragma unroll
 		for (int x = 1; x < kIcpThreads / 16; x++) sum += weighted ? red[x][threadIdx.x] * red[x][kWordW] : red[x][threadIdx.x];
@@ -4137,9 +4222,9 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 template <int K, int METRIC>
 __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void pose_info_kernel(const float4* __restrict__ src, int N, PoseInfoArgs pa, int strided,
                                                                   KdDesc kd, DtDesc dt, const float4* __restrict__ normals,
-                                                                  unsigned long long* __restrict__ acc)
+                                                                  unsigned long long* __restrict__ acc, const float4* __restrict__ src_normals)
 {
-	pose_info_body<K, METRIC>(src, N, pa, strided, kd, dt, normals, acc);
+	pose_info_body<K, METRIC>(src, N, pa, strided, kd, dt, normals, acc, src_normals);
 }
 
 // goicp_pose_information_batch: blockIdx.y is the pose slot -- its argument block args[slot], its accumulator block acc + slot * kIcpBatchAccWords.
@@ -4147,49 +4232,70 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void pose_info_ker
 template <int K, int METRIC>
 __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void pose_info_batch_kernel(const float4* __restrict__ src, int N,
                                                                         const PoseInfoArgs* __restrict__ args, int strided, KdDesc kd, DtDesc dt,
-                                                                        const float4* __restrict__ normals, unsigned long long* __restrict__ acc)
+                                                                        const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
+                                                                        const float4* __restrict__ src_normals)
 {
 	const int s = (int)blockIdx.y;
-	pose_info_body<K, METRIC>(src, N, args[s], strided, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords);
+	pose_info_body<K, METRIC>(src, N, args[s], strided, kd, dt, normals, acc + (size_t)s * kIcpBatchAccWords, src_normals);
 }
 
 template <int K>
 static void launch_pose_info_k(const float4* src, int N, const PoseInfoArgs* h_args, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd,
-                               const DtDesc& dt, const float4* normals, unsigned long long* acc, hipStream_t stream)
+                               const DtDesc& dt, const float4* normals, unsigned long long* acc, const float4* src_normals, hipStream_t stream)
 {
 	const dim3 block(kIcpThreads);
 	const int strided = N <= kIcpStridedMaxN ? 1 : 0;        // the ICP passes' choice
-	if (h_args) {
-		const dim3 grid(icp_blocks(N));
-		if (metric == 0) hipLaunchKernelGGL((pose_info_kernel<K, 0>), grid, block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc);
-		else hipLaunchKernelGGL((pose_info_kernel<K, 1>), grid, block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc);
-	} else {
-		const dim3 grid(icp_blocks(N), n_poses);
-		if (metric == 0) hipLaunchKernelGGL((pose_info_batch_kernel<K, 0>), grid, block, 0, stream, src, N, d_args, strided, kd, dt, normals, acc);
-		else hipLaunchKernelGGL((pose_info_batch_kernel<K, 1>), grid, block, 0, stream, src, N, d_args, strided, kd, dt, normals, acc);
-	}
+	with_value<2, 1, 0>(metric, [&](auto M) {
+		if (h_args)
+			hipLaunchKernelGGL((pose_info_kernel<K, M()>), dim3(icp_blocks(N)), block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc, src_normals);
+		else
+			hipLaunchKernelGGL((pose_info_batch_kernel<K, M()>), dim3(icp_blocks(N), n_poses), block, 0, stream, src, N, d_args, strided, kd, dt, normals, acc,
+			                   src_normals);
+	});
 }
 
 static hipError_t launch_pose_info_any(const float4* src, int N, const PoseInfoArgs* h_args, const PoseInfoArgs* d_args, int n_poses, int metric,
-                                       const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc, hipStream_t stream)
+                                       const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc, const float4* src_normals,
+                                       hipStream_t stream)
 {
-	if (N <= 0 || !acc || !dt.layout || (metric != 0 && metric != 1) || (metric == 1 && !normals) || n_poses < 1 || n_poses > kIcpBatchMax)
+	if (N <= 0 || !acc || !dt.layout || metric < 0 || metric > 2 || (metric != 0 && !normals) || (metric == 2 && !src_normals) || n_poses < 1 ||
+	    n_poses > kIcpBatchMax)
 		return hipErrorInvalidValue;
-	with_k(kd.K, [&](auto K) { launch_pose_info_k<K()>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, stream); });
+	with_k(kd.K, [&](auto K) { launch_pose_info_k<K()>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, src_normals, stream); });
 	return hipGetLastError();
 }
 
 hipError_t launch_pose_info(const float4* src, int N, const PoseInfoArgs& args, int metric, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                            unsigned long long* acc, hipStream_t stream)
+                            unsigned long long* acc, hipStream_t stream, const float4* src_normals)
 {
-	return launch_pose_info_any(src, N, &args, nullptr, 1, metric, kd, dt, normals, acc, stream);
+	return launch_pose_info_any(src, N, &args, nullptr, 1, metric, kd, dt, normals, acc, src_normals, stream);
 }
 
 hipError_t launch_pose_info_batch(const float4* src, int N, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd, const DtDesc& dt,
-                                  const float4* normals, unsigned long long* acc, hipStream_t stream)
+                                  const float4* normals, unsigned long long* acc, hipStream_t stream, const float4* src_normals)
 {
 	if (!d_args) return hipErrorInvalidValue;
-	return launch_pose_info_any(src, N, nullptr, d_args, n_poses, metric, kd, dt, normals, acc, stream);
+	return launch_pose_info_any(src, N, nullptr, d_args, n_poses, metric, kd, dt, normals, acc, src_normals, stream);
+}
+
+// ---- source normals into the order of the source (goicp_set_icp_symmetric) ---------------------------------------------------------------
+// out[i] = (normal of point perm[i], 0): the float4 array parallel to src that the symmetric pass loads by query.  nrm: 3 n floats in the
+// caller's point order (launch_estimate_normals' output, or the caller's own normals); perm: launch_source_order's permutation
+__global__ __launch_bounds__(256) void source_normals_gather_kernel(const float* __restrict__ nrm, const int32_t* __restrict__ perm, int n,
+                                                                    float4* __restrict__ out)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const size_t o = 3 * (size_t)perm[i];
+	out[i] = make_float4(nrm[o], nrm[o + 1], nrm[o + 2], 0.f);
+}
+
+hipError_t launch_source_normals_gather(const float* d_normals_xyz, const int32_t* d_perm, int n, float4* d_out, hipStream_t stream)
+{
+	if (n <= 0) return hipSuccess;
+	if (!d_normals_xyz || !d_perm || !d_out) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(source_normals_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_normals_xyz, d_perm, n, d_out);
+	return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -362,7 +362,8 @@ constexpr double kIcpRobustWScale = 68719476736.0;   // 2^36
 //   kIcpModeGate    the inlier count, a plain integer, in word kIcpGateCountWord[metric] = 16 / 28
 //   kIcpModeRobust  W (scaled by kIcpRobustWScale) in word kIcpGateCountWord[metric] = 16 / 28, C (scaled by the pass's acc_scale) in the word
 //                   after it, 17 / 29
-// Anything else -- a null states or acc, a metric other than 0 / 1, metric 1 without normals, metric 0 or a mode on the linear DT, n_active outside
+// metric 2 is internal: metric 1 in its symmetric form (goicp_set_icp_symmetric), metric 1's words and modes, src_normals beside normals.
+// Anything else -- a null states or acc, a metric outside 0..2, metric 1 / 2 without normals, metric 2 without src_normals, metric 0 or a mode on the linear DT, n_active outside
 // [1, kIcpBatchMax] or != 1 without a list, the default cell -- is hipErrorInvalidValue without a launch.
 enum IcpMode : int { kIcpModePlain = 0, kIcpModeGate = 1, kIcpModeRobust = 2 };
 constexpr int kIcpBatchMax = 1024;
@@ -372,11 +373,12 @@ struct IcpOptArgs {
 	IcpState* states;             // the loop state; batch: kIcpBatchMax slots at most
 	const int* active;            // nullptr: single pose
 	int n_active;                 // 1 for a single pose
-	int metric;                   // 0 point-to-point, 1 point-to-plane
+	int metric;                   // 0 point-to-point, 1 point-to-plane, 2 symmetric point-to-plane
 	int mode;                     // IcpMode
 	const float4* normals;        // metric 1: one per target point (launch_normal_build)
 	unsigned long long* acc;
 	int capped;                   // kIcpModeGate: the walk's pruning bound starts at min(seed distance, g2) -- exact for every inlier, no neighbour for an outlier
+	const float4* src_normals = nullptr;   // metric 2: one per source point, parallel to src (launch_source_normals_gather)
 };
 hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream);
 
@@ -395,12 +397,14 @@ struct PoseInfoArgs {
 	int32_t pad;
 };
 static_assert(sizeof(PoseInfoArgs) == 80, "PoseInfoArgs layout");
-constexpr int kPoseInfoWords[2] = {19, 31};
+constexpr int kPoseInfoWords[3] = {19, 31, 31};   // [2]: the symmetric form of metric 1 (src_normals beside normals), metric 1's layout
 hipError_t launch_pose_info(const float4* src, int N, const PoseInfoArgs& args, int metric, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                            unsigned long long* acc, hipStream_t stream);
+                            unsigned long long* acc, hipStream_t stream, const float4* src_normals = nullptr);
 // n_poses <= kIcpBatchMax argument blocks in device memory, slot s adding into acc + s * kIcpBatchAccWords: each slot the single call bit for bit
 hipError_t launch_pose_info_batch(const float4* src, int N, const PoseInfoArgs* d_args, int n_poses, int metric, const KdDesc& kd, const DtDesc& dt,
-                                  const float4* normals, unsigned long long* acc, hipStream_t stream);
+                                  const float4* normals, unsigned long long* acc, hipStream_t stream, const float4* src_normals = nullptr);
+// d_out[i] = (normal of point d_perm[i], 0): normals in the caller's point order (3 n floats) into the source's order
+hipError_t launch_source_normals_gather(const float* d_normals_xyz, const int32_t* d_perm, int n, float4* d_out, hipStream_t stream);
 
 // min of n floats (+ first index attaining it, may be null): one workgroup; v must be 16-byte aligned
 hipError_t launch_reduce_min(const float* v, int n, float* out_min, int* out_idx, hipStream_t stream);

@@ -429,16 +429,19 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 	d_src_.reserve(N_);
 	std::vector<int32_t> perm(N_);
 	const bool on_device = device_order && p_.morton_sort >= 1;
+	Buf<float> d_up;          // what a device-ordered swap leaves on the device: the source normals below read both
+	Buf<int32_t> d_perm;
+	const float* d_xyz = nullptr;
 	if (on_device) {
 		// the order on the device (launch_source_order), the gather with |p| straight into d_src_; the permutation comes back for the
 		// host mirror, whose sums below keep init's order of additions
 		const int mode = p_.morton_sort == 1 ? 1 : 2;
 		float mn[3] = {0, 0, 0}, ext = 1.f;
 		if (mode == 1) source_morton_frame(source, N_, mn, &ext);
-		Buf<float> d_up(d_xyz_ready ? 0 : 3 * N_);
-		Buf<int32_t> d_perm(N_);
+		d_up.alloc(d_xyz_ready ? 0 : 3 * N_);
+		d_perm.alloc(N_);
 		if (!d_xyz_ready) HIPCHK(hipMemcpyAsync(d_up, source, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
-		const float* d_xyz = d_xyz_ready ? d_xyz_ready : d_up.get();
+		d_xyz = d_xyz_ready ? d_xyz_ready : d_up.get();
 		HIPCHK(hipEventRecord(ev0_, stream_));
 		HIPCHK(launch_source_order(d_xyz, (int)N_, mode, mn, ext, d_perm, stream_));
 		HIPCHK(hipEventRecord(ev1_, stream_));
@@ -474,6 +477,17 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 		d_nn_cache_.reserve(2 * N_);
 		HIPCHK(hipMemsetAsync(d_nn_cache_, 0, sizeof(float4) * 2 * N_, stream_));      // sqrt(best2_ref) = 0: the first pass walks
 	}
+	// the source normals, estimated or the caller's, belong to the cloud that just left; with the symmetric metric active the new cloud's are
+	// part of the source stage (the first ICP after a swap is not charged for them), otherwise they are built on first use
+	src_normals_k_ = 0;
+	src_normals_user_ = false;
+	if (symmetric_active()) build_source_normals(source, d_xyz, on_device ? d_perm.get() : nullptr);
+}
+
+void Engine::check_swap_size(size_t n, const char* fn) const
+{
+	if (icp_symmetric_ && n < (size_t)source_normal_k_)
+		throw std::invalid_argument(std::string(fn) + ": the cloud has fewer points than the handle's source_normal_k (goicp_set_icp_symmetric)");
 }
 
 void Engine::set_source(const float* source, size_t N)
@@ -481,6 +495,7 @@ void Engine::set_source(const float* source, size_t N)
 	// everything that can refuse comes first: a refused call leaves the engine as it was
 	check_source(source, N);
 	if (registering_.load()) throw std::invalid_argument("goicp_set_source: not while a registration runs");
+	check_swap_size(N, "goicp_set_source");
 	DeviceGuard guard(dev_);
 	const double t0 = now_ms();
 	TraceRange tr("goicp:set_source");
@@ -566,6 +581,7 @@ void Engine::set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n
 	HIPCHK(hipStreamSynchronize(stream_));
 	float ms = 0.f;
 	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+	check_swap_size((size_t)m, "goicp_set_source_voxel");
 	voxel_ms_ = ms;
 	load_source(red.data(), (size_t)m, true, d_red);
 	finish_source_swap();
@@ -647,6 +663,7 @@ void Engine::set_source_filtered(const float* xyz, size_t n, float voxel, float 
 	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
 	outlier_ms_ = ms;
 	if (m < 1) throw std::invalid_argument("goicp_set_source_filtered: the filter keeps no point");
+	check_swap_size((size_t)m, "goicp_set_source_filtered");
 	std::vector<float> kept(3 * (size_t)m);
 	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
@@ -779,6 +796,116 @@ void Engine::estimate_normals(const float* xyz, size_t n, int32_t k, const float
 	}
 }
 
+// ---- symmetric point-to-plane ICP: the source normals ----
+void Engine::build_source_normals(const float* h_xyz, const float* d_xyz, const int32_t* d_perm)
+{
+	const int k = source_normal_k_;
+	float mn[3], mx[3];
+	stat_check_cloud(h_xyz, N_, mn, mx);
+	normals_check_params(N_, k, nullptr);
+	const double t0 = now_ms();
+	const StatPlan plan(mn, mx, N_, k - 1, stat_sample_host(h_xyz, N_));
+	Buf<float> d_up(d_xyz ? 0 : 3 * N_), d_nrm(3 * N_);
+	Buf<int32_t> d_idx(N_ * (size_t)(k - 1)), d_pu(d_perm ? 0 : N_);
+	StatReport rep;
+	if (!d_xyz) {
+		HIPCHK(hipMemcpyAsync(d_up, h_xyz, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+		d_xyz = d_up.get();
+	}
+	if (!d_perm) {
+		HIPCHK(hipMemcpyAsync(d_pu, src_perm_.data(), sizeof(int32_t) * N_, hipMemcpyHostToDevice, stream_));
+		d_perm = d_pu.get();
+	}
+	HIPCHK(launch_estimate_normals(d_xyz, (int)N_, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, nullptr, d_nrm, nullptr, d_idx, &rep, stream_));
+	d_src_normals_.reserve(N_);
+	HIPCHK(launch_source_normals_gather(d_nrm, d_perm, (int)N_, d_src_normals_, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	src_normals_k_ = k;
+	src_normals_user_ = false;
+	source_normal_build_ms_ = now_ms() - t0;
+	if (p_.verbose) std::fprintf(stderr, "[goicp] source normals (k = %d, %zu points): %.2f ms\n", k, N_, source_normal_build_ms_);
+}
+
+void Engine::ensure_source_normals()
+{
+	if (src_normals_user_ || (src_normals_k_ == source_normal_k_ && d_src_normals_)) return;
+	DeviceGuard guard(dev_);
+	// the cloud as the handle holds it, back in the caller's point order
+	std::vector<float> xyz(3 * N_);
+	for (size_t i = 0; i < N_; i++) std::memcpy(&xyz[3 * (size_t)src_perm_[i]], &h_src_sorted_[4 * i], 3 * sizeof(float));
+	build_source_normals(xyz.data(), nullptr, nullptr);
+}
+
+void Engine::check_symmetric_query(const char* fn) const
+{
+	if (registering_.load()) throw std::invalid_argument(std::string(fn) + ": not while a registration runs");
+}
+
+void Engine::set_icp_symmetric(int enabled, int source_normal_k)
+{
+	if (enabled != 0 && enabled != 1) throw std::invalid_argument("goicp_set_icp_symmetric: enabled must be 0 or 1");
+	if (source_normal_k < 3 || source_normal_k > kKnnMax) throw std::invalid_argument("goicp_set_icp_symmetric: source_normal_k must be in [3, 32]");
+	if ((size_t)source_normal_k > N_) throw std::invalid_argument("goicp_set_icp_symmetric: source_normal_k exceeds the number of source points");
+	if (enabled && p_.trim_fraction > 0.f) throw std::invalid_argument("goicp_set_icp_symmetric: symmetric ICP with trim_fraction > 0 is not supported");
+	check_symmetric_query("goicp_set_icp_symmetric");
+	if (enabled && icp_gated() && gate_min_inliers_ != 0 && gate_min_inliers_ < 6)
+		throw std::invalid_argument("goicp_set_icp_symmetric: the handle's gate has min_inliers below point-to-plane's floor of 6");
+	const bool was = symmetric_active();
+	icp_symmetric_ = enabled != 0;
+	source_normal_k_ = source_normal_k;
+	if (symmetric_active()) {
+		DeviceGuard guard(dev_);
+		ensure_source_normals();
+		if (!was) {
+			// the first launch of the symmetric kernels (code object load) belongs here, not to the first refinement: one frozen pass
+			const float I0[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z0[3] = {0, 0, 0};
+			icp_state_init(I0, Z0, 0.f, 0, 1);
+			icp_launch_one();
+			HIPCHK(hipStreamSynchronize(stream_));
+		}
+	}
+}
+
+void Engine::source_normals(float* out)
+{
+	if (!out) throw std::invalid_argument("goicp_source_normals: out must be non-null");
+	check_symmetric_query("goicp_source_normals");
+	if (!src_normals_user_ && (size_t)source_normal_k_ > N_)
+		throw std::invalid_argument("goicp_source_normals: source_normal_k exceeds the number of source points");
+	DeviceGuard guard(dev_);
+	ensure_source_normals();
+	std::vector<float4> n(N_);
+	HIPCHK(hipMemcpy(n.data(), d_src_normals_, sizeof(float4) * N_, hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < N_; i++) {
+		float* o = out + 3 * (size_t)src_perm_[i];         // back to the caller's point order
+		o[0] = n[i].x; o[1] = n[i].y; o[2] = n[i].z;
+	}
+}
+
+void Engine::set_source_normals(const float* normals, size_t n)
+{
+	if (!normals) throw std::invalid_argument("goicp_set_source_normals: normals must be non-null");
+	if (n != N_) throw std::invalid_argument("goicp_set_source_normals: n must be the handle's source count");
+	for (size_t i = 0; i < n; i++) {
+		const float* v = normals + 3 * i;
+		if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2])) throw std::invalid_argument("goicp_set_source_normals: non-finite normal");
+		if (v[0] == 0.f && v[1] == 0.f && v[2] == 0.f) continue;
+		const double len = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+		if (std::fabs(len - 1.0) > 1e-3) throw std::invalid_argument("goicp_set_source_normals: a normal must be zero or of unit length (within 1e-3)");
+	}
+	check_symmetric_query("goicp_set_source_normals");
+	DeviceGuard guard(dev_);
+	Buf<float> d_nrm(3 * N_);
+	Buf<int32_t> d_perm(N_);
+	HIPCHK(hipMemcpyAsync(d_nrm, normals, sizeof(float) * 3 * N_, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(d_perm, src_perm_.data(), sizeof(int32_t) * N_, hipMemcpyHostToDevice, stream_));
+	d_src_normals_.reserve(N_);
+	HIPCHK(launch_source_normals_gather(d_nrm, d_perm, (int)N_, d_src_normals_, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	src_normals_user_ = true;
+	src_normals_k_ = 0;
+}
+
 void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
                                  size_t* n_kept)
 {
@@ -857,6 +984,7 @@ void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_
 		d_final = d_kept;
 	}
 	if (m < 1) throw std::invalid_argument("goicp_set_source_pipeline: the chain keeps no point");
+	check_swap_size((size_t)m, "goicp_set_source_pipeline");
 	std::vector<float> kept(3 * (size_t)m);
 	HIPCHK(hipMemcpyAsync(kept.data(), d_final, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
@@ -1047,6 +1175,7 @@ void Engine::set_source_clustered(const float* xyz, size_t n, float voxel, int32
 	cluster_filter_device(d_in, n_in, fc, cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_max_clusters, d_kept, nullptr, nullptr, &m, &c,
 	                      stream_, ev0_, ev1_, &cluster_ms);
 	if (m < 1) throw std::invalid_argument("goicp_set_source_clustered: the selection keeps no point");
+	check_swap_size((size_t)m, "goicp_set_source_clustered");
 	std::vector<float> kept(3 * (size_t)m);
 	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
@@ -1615,6 +1744,8 @@ void Engine::pose_information(size_t K, const float* R, const float* t, const go
 	const int metric = o.metric < 0 ? icp_metric_ : o.metric;
 	DeviceGuard guard(dev_);
 	if (metric == 1) ensure_normals(normal_k_);
+	const int kmetric = metric == 1 && icp_symmetric_ ? 2 : metric;     // the symmetric form wherever metric 1 is evaluated on a flagged handle
+	if (kmetric == 2) ensure_source_normals();
 	if (src_crad_ < 0.0) {
 		// largest distance of a source point from the source centroid: with the default pivot |a| <= |R| * this
 		double m = 0.0;
@@ -1660,9 +1791,9 @@ void Engine::pose_information(size_t K, const float* R, const float* t, const go
 	HIPCHK(hipMemsetAsync(d_info_acc_, 0, sizeof(unsigned long long) * words, stream_));
 	if (batch) {
 		HIPCHK(hipMemcpyAsync(d_info_args_, args.data(), sizeof(PoseInfoArgs) * K, hipMemcpyHostToDevice, stream_));
-		HIPCHK(launch_pose_info_batch(d_src_, (int)N_, d_info_args_, (int)K, metric, kd_, dt_, d_normals_, d_info_acc_, stream_));
+		HIPCHK(launch_pose_info_batch(d_src_, (int)N_, d_info_args_, (int)K, kmetric, kd_, dt_, d_normals_, d_info_acc_, stream_, d_src_normals_));
 	} else {
-		HIPCHK(launch_pose_info(d_src_, (int)N_, args[0], metric, kd_, dt_, d_normals_, d_info_acc_, stream_));
+		HIPCHK(launch_pose_info(d_src_, (int)N_, args[0], kmetric, kd_, dt_, d_normals_, d_info_acc_, stream_, d_src_normals_));
 	}
 	std::vector<long long> acc(words);
 	HIPCHK(hipMemcpyAsync(acc.data(), d_info_acc_, sizeof(long long) * words, hipMemcpyDeviceToHost, stream_));
@@ -1729,6 +1860,7 @@ void Engine::result_information(const goicp_pose_info_options* opt, goicp_pose_i
 void Engine::icp_state_init(const float R[9], const float t[3], float err_diff, int carry_means, int frozen)
 {
 	icp_cache_active_ = false;          // icp_nn_cache = 2: every run starts with plain walks
+	if (symmetric_active()) ensure_source_normals();   // built with the flag, the metric or the swap: a no-op but after set_icp_options(1) on a flagged handle
 	icp_state_fill(*h_icp_state_, R, t, err_diff, carry_means, frozen);
 	HIPCHK(hipMemcpyAsync(d_icp_state_, h_icp_state_, sizeof(IcpState), hipMemcpyHostToDevice, stream_));
 }
@@ -1777,7 +1909,7 @@ void Engine::icp_launch_one()
 	// a kernel or a gate, either metric (set_icp_robust / set_icp_gate refuse each other, trimming, the linear DT and the fused iteration), or
 	// point-to-plane (set_icp_options refuses it together with trimming)
 	if (icp_mode() != kIcpModePlain || icp_metric_ == 1)
-		HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_icp_state_, nullptr, 1, icp_metric_, icp_mode(), d_normals_, d_icp_acc_opt_, gate_capped_}, kd_, dt_, stream_));
+		HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_icp_state_, nullptr, 1, icp_kernel_metric(), icp_mode(), d_normals_, d_icp_acc_opt_, gate_capped_, d_src_normals_}, kd_, dt_, stream_));
 	else if (inliers_ < (int)N_)
 		HIPCHK(launch_icp_iteration_trim(d_src_, (int)N_, inliers_, d_icp_state_, kd_, dt_, d_nn_d2_, d_nn_slot_, d_include_, d_icp_partials_, stream_));
 	else
@@ -1884,6 +2016,7 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 	if (registering_.load()) throw std::invalid_argument("goicp_icp_run_batch: not while a registration runs");
 	DeviceGuard guard(dev_);
 	if (icp_metric_ == 1) ensure_normals(normal_k_);
+	if (symmetric_active()) ensure_source_normals();
 	ensure_icp_batch(K);
 	IcpState* up = h_batch_states_;
 	for (size_t k = 0; k < K; k++) icp_state_fill(up[k], R + 9 * k, t + 3 * k, err_diff, 1, 0);
@@ -1903,7 +2036,7 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
 		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
 		for (int i = 0; i < k; i++)
-			HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_batch_states_, d_act, n_active, icp_metric_, icp_mode(), d_normals_, d_batch_acc_, gate_capped_}, kd_, dt_, stream_));
+			HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_batch_states_, d_act, n_active, icp_kernel_metric(), icp_mode(), d_normals_, d_batch_acc_, gate_capped_, d_src_normals_}, kd_, dt_, stream_));
 		queued += k;
 		HIPCHK(hipMemcpyAsync(slots[slot], d_batch_states_, sizeof(IcpState) * K, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipEventRecord(evs[slot], stream_));
@@ -2017,12 +2150,16 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 			h = fnv1a(h, &robust_kernel_, sizeof(robust_kernel_));
 			h = fnv1a(h, &robust_scale_, sizeof(float));
 		}
+		if (icp_symmetric_) {                          // and the symmetric flag with its source_normal_k
+			const int32_t si[2] = {1, source_normal_k_};
+			h = fnv1a(h, si, sizeof(si));
+		}
 		uint64_t w[3] = {h, ~h, health()};
 		const int rc = comm->allreduce_min_u64(comm->ctx, w, 3);
 		if (rc != GOICP_OK) return rc;
 		ss.collectives++;
 		if (w[2] != kHealthyWord) return leave(w[2]);
-		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric, gate, robust kernel or scale) or clouds");
+		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric, symmetric flag, gate, robust kernel or scale) or clouds");
 	}
 
 	const long long passes0 = cnt_.icp_iters;

@@ -179,6 +179,18 @@ public:
 	// normal; metric 1 builds the normals (once per normal_k).  Refused while a registration runs and together with trimming
 	void set_icp_options(int metric, int normal_k);
 	int icp_metric() const { return icp_metric_; }
+	// goicp_set_icp_symmetric: a modifier of metric 1 -- the symmetric point-to-plane objective over the normals of both clouds (include/goicp_mi355.h).
+	// Stored and inert under metric 0.  source_normal_k: the neighbours per estimated source normal.  Refused: source_normal_k outside 3..32 or
+	// above the source's size, enabled together with trimming or with a gate whose min_inliers is below 6, while a registration runs
+	void set_icp_symmetric(int enabled, int source_normal_k);
+	bool icp_symmetric() const { return icp_symmetric_; }
+	int source_normal_k() const { return source_normal_k_; }
+	bool user_source_normals() const { return src_normals_user_; }
+	void check_symmetric_query(const char* fn) const;            // what every entry point of the feature refuses: a running registration
+	void source_normals(float* normals_xyz);                     // N x 3, original source order (built on first use)
+	// the caller's own normals (original source order; each exactly zero or of length within 1e-3 of 1), in the place of the estimated ones
+	// until the next source swap
+	void set_source_normals(const float* normals_xyz, size_t n);
 	// goicp_icp_gate: a maximum correspondence distance for every ICP this engine runs (0 = off).  A correspondence is an inlier iff the walk's
 	// d^2 <= max_corr_dist^2; sums, update and stop rule run over the inliers (device.hip gate_step).  min_inliers 0 = the metric's floor (3 / 6).
 	// Refused: a negative or non-finite distance, min_inliers below the floor, a gate with trimming, with dt_layout 0 or with icp_fused, while
@@ -216,6 +228,7 @@ public:
 	static constexpr double kPoseInfoRankTol = 1e-6;
 	void knn_query(const float* q_xyz, size_t n, int k, int32_t* idx, float* d2);
 	double normal_build_ms() const { return normal_build_ms_; }   // exact, ascending (d2, index), n x k
+	double source_normal_build_ms() const { return source_normal_build_ms_; }
 	void target_normals(float* normals_xyz);                                         // M x 3, original target order (built on first use)
 	void icp_step();   // one ICP iteration on the engine's current pose (ICP::kdTreeGPUStep)
 	// measured ceiling of the gather path (4-byte loads into the resident DT): lookups/s; mode 0 coalesced, 1 divergent
@@ -538,6 +551,18 @@ private:
 	size_t batch_cap_ = 0;             // pose slots all five hold (0 while one of them is missing)
 	void ensure_icp_batch(size_t K);
 	void ensure_normals(int k);
+	// symmetric point-to-plane ICP (opt-in): the flag, the source normals (one float4 per source point, parallel to d_src_: the pass loads by query)
+	bool icp_symmetric_ = false, src_normals_user_ = false;
+	int source_normal_k_ = 16, src_normals_k_ = 0;        // src_normals_k_: the k the estimated normals were built with (0: none yet)
+	Buf<float4> d_src_normals_;                           // N, the source's order; grow-only
+	double source_normal_build_ms_ = 0;
+	bool symmetric_active() const { return icp_symmetric_ && icp_metric_ == 1; }
+	int icp_kernel_metric() const { return symmetric_active() ? 2 : icp_metric_; }   // launch_icp_iteration_opt's
+	void ensure_source_normals();
+	// launch_estimate_normals on the source in the caller's point order, then the gather into the source's order.  d_xyz / d_perm: the cloud and
+	// the permutation where they are on the device already (a swap), else both are uploaded
+	void build_source_normals(const float* h_xyz, const float* d_xyz, const int32_t* d_perm);
+	void check_swap_size(size_t n, const char* fn) const;   // a swap to fewer than source_normal_k points is refused while the flag is on
 	// pose information (allocated on first use, grown on demand): one accumulator block (kIcpBatchAccWords) and one argument block per pose
 	Buf<unsigned long long> d_info_acc_; Buf<PoseInfoArgs> d_info_args_;
 	double src_crad_ = -1.0;           // largest distance of a source point from the source centroid (first use)

@@ -704,6 +704,35 @@ int goicp_target_normals(goicp_handle h, float* normals_xyz)
 	return guarded([&] { h->e->target_normals(normals_xyz); });
 }
 
+int goicp_set_icp_symmetric(goicp_handle h, int32_t enabled, int32_t source_normal_k)
+{
+	REQUIRE(h);
+	return guarded([&] { h->e->set_icp_symmetric(enabled, source_normal_k); });
+}
+
+int goicp_get_icp_symmetric(goicp_handle h, int32_t* enabled, int32_t* source_normal_k, int32_t* user_normals)
+{
+	REQUIRE(h && enabled && source_normal_k && user_normals);
+	return guarded([&] {
+		h->e->check_symmetric_query("goicp_get_icp_symmetric");
+		*enabled = h->e->icp_symmetric() ? 1 : 0;
+		*source_normal_k = h->e->source_normal_k();
+		*user_normals = h->e->user_source_normals() ? 1 : 0;
+	});
+}
+
+int goicp_source_normals(goicp_handle h, float* normals_xyz)
+{
+	REQUIRE(h && normals_xyz);
+	return guarded([&] { h->e->source_normals(normals_xyz); });
+}
+
+int goicp_set_source_normals(goicp_handle h, const float* normals_xyz, size_t n)
+{
+	REQUIRE(h && normals_xyz);
+	return guarded([&] { h->e->set_source_normals(normals_xyz, n); });
+}
+
 void goicp_pose_info_options_default(goicp_pose_info_options* out)
 {
 	if (!out) return;

@@ -286,14 +286,16 @@ class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
     def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, robust_kernel=0, robust_scale=0.0, trunc_dist=None,
-                 **params):
+                 icp_symmetric=False, source_normal_k=16, **params):
         """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
         engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched.
         max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance.
         robust_kernel / robust_scale: goicp_set_icp_robust after creation -- 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 Tukey (or their names)
         weight every correspondence of every ICP of this engine by its residual; 0 keeps the plain loop.
         trunc_dist: goicp_set_search_truncation after creation -- the search (bounds, pose scores, best_sse) minimises
-        sum min(DT(R p + t), trunc_dist)^2 instead of the plain sum of squares; None or 0 keeps the plain objective."""
+        sum min(DT(R p + t), trunc_dist)^2 instead of the plain sum of squares; None or 0 keeps the plain objective.
+        icp_symmetric / source_normal_k: goicp_set_icp_symmetric after creation -- wherever this engine evaluates metric 1 it takes the
+        symmetric point-to-plane form over the normals of both clouds (source normals from source_normal_k neighbours); inert under metric 0."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -336,6 +338,13 @@ class Registration:
         if trunc_dist:
             try:
                 self.set_search_truncation(trunc_dist)
+            except Exception:
+                self.close()
+                raise
+
+        if icp_symmetric:
+            try:
+                self.set_icp_symmetric(True, source_normal_k)
             except Exception:
                 self.close()
                 raise
@@ -561,6 +570,28 @@ class Registration:
         n = np.empty((self.nt, 3), np.float32)
         B.check(self._lib.goicp_target_normals(self.handle, _fptr(n)))
         return n
+
+    # ---- symmetric point-to-plane ICP (goicp_set_icp_symmetric) ----
+    def set_icp_symmetric(self, enabled=True, source_normal_k=16):
+        """goicp_set_icp_symmetric: metric 1 in its symmetric form over the normals of both clouds; stored and inert under metric 0."""
+        B.check(self._lib.goicp_set_icp_symmetric(self.handle, int(bool(enabled)), int(source_normal_k)))
+
+    def icp_symmetric(self):
+        """goicp_get_icp_symmetric -> (enabled, source_normal_k, user_normals)"""
+        e, k, u = C.c_int32(), C.c_int32(), C.c_int32()
+        B.check(self._lib.goicp_get_icp_symmetric(self.handle, C.byref(e), C.byref(k), C.byref(u)))
+        return bool(e.value), k.value, bool(u.value)
+
+    def source_normals(self):
+        """(N, 3) float32 source normals in the source's original order: the estimated ones (built on first use) or the caller's"""
+        n = np.empty((self.ns, 3), np.float32)
+        B.check(self._lib.goicp_source_normals(self.handle, _fptr(n)))
+        return n
+
+    def set_source_normals(self, normals):
+        """goicp_set_source_normals: the caller's normals (N x 3, original source order, each zero or of unit length) until the next swap"""
+        normals = _f32(normals, (-1, 3))
+        B.check(self._lib.goicp_set_source_normals(self.handle, _fptr(normals), len(normals)))
 
     def close(self):
         if getattr(self, "handle", None):

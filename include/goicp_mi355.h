@@ -550,6 +550,42 @@ int goicp_knn_query(goicp_handle h, const float* query_xyz, size_t n, int32_t k,
 /* the target normals (M x 3, original target order) with the handle's normal_k; built on first use if needed */
 int goicp_target_normals(goicp_handle h, float* normals_xyz);
 
+/* ---- symmetric point-to-plane ICP (opt-in; a per-handle modifier of metric 1, not a metric value of its own) ---------------------
+ * The objective of Rusinkiewicz, "A Symmetric Objective Function for ICP" (SIGGRAPH 2019; PCL's
+ * TransformationEstimationSymmetricPointToPlaneLLS) in the incremental form of the point-to-plane iteration above: it reads the normals of
+ * BOTH clouds and is exact for pairs of points on any locally quadratic surface, not only on planes.  The flag takes effect wherever
+ * metric 1 is evaluated on the handle -- goicp_icp_run, _step, _run_batch, goicp_time_icp_pass, the refinements of goicp_register (every
+ * driver) and of goicp_register_sharded*, goicp_pose_information[_batch] with metric -1 or 1 -- and is stored and inert under metric 0; a
+ * handle that never sets it runs none of this.  For a correspondence with q = R p + t (the engine's float expression), m the nearest
+ * target point (the unchanged walk: same index, same d^2 bits), nm = the target normal of m and ns = the source normal of p, in float,
+ * left to right, without contraction:
+ *   s   = R ns                       by the row expression of q without t;
+ *   dot = s.x nm.x + s.y nm.y + s.z nm.z;  dot < 0: s = -s   ("enforce same direction": the objective does not depend on either
+ *                                          cloud's orientation convention);
+ *   n   = 0.5f * (s + nm);           s exactly zero: n = nm; nm exactly zero: n = s; both: n = 0 (the correspondence adds only d^2);
+ *                                    |n| <= 1;
+ *   e = q - m,  a = q - cq,  c = a - 0.5f * e    (the midpoint of the correspondence relative to the pivot cq); s exactly zero:
+ *                                    c = a, so the correspondence is plain point-to-plane, bit for bit;
+ *   r = e . n,  J = (c x n, n).
+ * Everything after J and r is point-to-plane's: the 21 + 6 + 1 sums, the 64-bit fixed-point replicas, the damped Cholesky step, the pose
+ * and pivot update, ICP3D::Run's stop rule on sum d^2, the gate's inlier word, the robust weight of |r| with rho of d.
+ * Source normals: estimated on the device on first use (or as part of a source swap while the flag is on and metric 1 is active) --
+ * goicp_estimate_normals of the handle's source cloud (the N points it registers) with k = source_normal_k and no viewpoint -- or the
+ * caller's own (goicp_set_source_normals).  Every source swap (goicp_set_source, _voxel, _filtered, _pipeline, _clustered) drops both; a
+ * swap to fewer than source_normal_k points is refused while the flag is on, before anything on the handle changes.
+ * All four calls refuse with GOICP_ERR_INVALID, and change nothing: a NULL argument, source_normal_k outside 3..32 or above the source's
+ * size, enabled together with trim_fraction > 0 or with a gate whose min_inliers is below 6, any call while a registration runs.
+ * goicp_icp_run_collective runs the symmetric form replicated on every rank (the flag and source_normal_k join its check word);
+ * goicp_register_multi_gpu stays point-to-point. */
+int goicp_set_icp_symmetric(goicp_handle h, int32_t enabled, int32_t source_normal_k);
+int goicp_get_icp_symmetric(goicp_handle h, int32_t* enabled, int32_t* source_normal_k, int32_t* user_normals);
+/* the source normals (N x 3, original source order) the symmetric form reads: the estimated ones (built on first use) or the caller's */
+int goicp_source_normals(goicp_handle h, float* normals_xyz);
+/* the caller's own normals (e.g. a sensor's), original source order; they take the estimated ones' place until the next source swap.
+ * n must be the handle's source count; every value finite; each normal exactly zero or of length within 1e-3 of 1 (checked in fp64),
+ * stored as given */
+int goicp_set_source_normals(goicp_handle h, const float* normals_xyz, size_t n);
+
 /* ---- distance-gated ICP (opt-in; new: a maximum correspondence distance, the outlier rule of PCL / Open3D) ----------------------
  * The gate applies to every ICP the handle runs, both metrics: goicp_icp_run, goicp_icp_run_batch, goicp_icp_step, goicp_time_icp_pass, the
  * ICP inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded* (the DT re-score of a refined pose still scores

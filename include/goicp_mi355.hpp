@@ -317,6 +317,30 @@ public:
 		goicp_icp_options o{metric, normal_k};
 		check(goicp_set_icp_options(h_, &o));
 	}
+	// metric 1 in its symmetric form over the normals of both clouds (goicp_set_icp_symmetric); stored and inert under metric 0
+	void set_icp_symmetric(bool enabled, int source_normal_k = 16) { check(goicp_set_icp_symmetric(h_, enabled ? 1 : 0, (int32_t)source_normal_k)); }
+	struct IcpSymmetric { bool enabled; int source_normal_k; bool user_normals; };
+	IcpSymmetric icp_symmetric() const
+	{
+		int32_t e = 0, k = 0, u = 0;
+		check(goicp_get_icp_symmetric(h_, &e, &k, &u));
+		return IcpSymmetric{e != 0, (int)k, u != 0};
+	}
+	// the source normals the symmetric form reads (original source order): the estimated ones, built on first use, or the caller's
+	template <class Point3>
+	void source_normals(std::vector<Point3>& normals) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		normals.resize(ns_);
+		check(goicp_source_normals(h_, reinterpret_cast<float*>(normals.data())));
+	}
+	// the caller's own normals (each zero or of unit length) until the next source swap (goicp_set_source_normals)
+	template <class Point3>
+	void set_source_normals(const std::vector<Point3>& normals)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		check(goicp_set_source_normals(h_, reinterpret_cast<const float*>(normals.data()), normals.size()));
+	}
 	// a maximum correspondence distance for every ICP this registration runs (goicp_set_icp_gate); 0 switches it off
 	void set_icp_gate(float max_corr_dist, int min_inliers = 0, int capped_walk = 1)
 	{
