@@ -44,6 +44,14 @@ struct ScopedMs {
 	~ScopedMs() { acc += now_ms() - t0; }
 };
 
+// a cloud of the host's on the device: the copy is queued on the stream
+Buf<float> upload_cloud(const float* xyz, size_t n, hipStream_t stream)
+{
+	Buf<float> d(3 * n);
+	HIPCHK(hipMemcpyAsync(d, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream));
+	return d;
+}
+
 }  // namespace
 
 Engine::DeviceGuard::DeviceGuard(int dev) : want(dev)
@@ -490,19 +498,24 @@ void Engine::check_swap_size(size_t n, const char* fn) const
 		throw std::invalid_argument(std::string(fn) + ": the cloud has fewer points than the handle's source_normal_k (goicp_set_icp_symmetric)");
 }
 
-void Engine::set_source(const float* source, size_t N)
+void Engine::sync_lane_streams()
+{
+	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+}
+
+void Engine::set_source(const float* source, size_t N, const char* fn)
 {
 	// everything that can refuse comes first: a refused call leaves the engine as it was
 	check_source(source, N);
-	if (registering_.load()) throw std::invalid_argument("goicp_set_source: not while a registration runs");
-	check_swap_size(N, "goicp_set_source");
+	if (registering_.load()) throw std::invalid_argument(std::string(fn) + ": not while a registration runs");
+	check_swap_size(N, fn);
 	DeviceGuard guard(dev_);
 	const double t0 = now_ms();
-	TraceRange tr("goicp:set_source");
-	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	TraceRange tr(fn);
+	sync_lane_streams();
 	load_source(source, N, true);
 	finish_source_swap();
-	if (p_.verbose) std::fprintf(stderr, "[goicp] set_source: %zu points, %.2f ms (device order %.3f ms)\n", N_, now_ms() - t0, source_order_ms_);
+	if (p_.verbose) std::fprintf(stderr, "[goicp] %s: %zu points, %.2f ms (device order %.3f ms)\n", fn + 6, N_, now_ms() - t0, source_order_ms_);
 }
 
 void Engine::finish_source_swap()
@@ -549,46 +562,15 @@ void Engine::voxel_downsample(const float* xyz, size_t n, float voxel, float* ou
 	voxel_frame(xyz, n, voxel, &f);
 	if (registering_.load()) throw std::invalid_argument("goicp_voxel_downsample: not while a registration runs");
 	DeviceGuard guard(dev_);
-	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_out(3 * n);
 	Buf<int32_t> d_cnt(out_count ? n : 0);
 	int m = 0;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_voxel_downsample(d_xyz, (int)n, f, d_out, out_count ? d_cnt.get() : nullptr, &m, stream_));
 	HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_cnt, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
 	*m_out = (size_t)m;
 	if (p_.verbose) std::fprintf(stderr, "[goicp] voxel_downsample: %zu -> %d points\n", n, m);
-}
-
-void Engine::set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept)
-{
-	// everything that can refuse comes first: a refused call leaves the engine as it was
-	VoxelFrame f;
-	voxel_frame(xyz, n, voxel, &f);
-	if (registering_.load()) throw std::invalid_argument("goicp_set_source_voxel: not while a registration runs");
-	DeviceGuard guard(dev_);
-	const double t0 = now_ms();
-	TraceRange tr("goicp:set_source_voxel");
-	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
-	// the raw cloud goes up once; the reduced cloud stays on the device for the ordering stage, and comes back for the host mirror
-	Buf<float> d_raw(3 * n), d_red(3 * n);
-	int m = 0;
-	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	HIPCHK(launch_voxel_downsample(d_raw, (int)n, f, d_red, nullptr, &m, stream_, ev0_, ev1_));
-	std::vector<float> red(3 * (size_t)m);
-	HIPCHK(hipMemcpyAsync(red.data(), d_red, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipStreamSynchronize(stream_));
-	float ms = 0.f;
-	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
-	check_swap_size((size_t)m, "goicp_set_source_voxel");
-	voxel_ms_ = ms;
-	load_source(red.data(), (size_t)m, true, d_red);
-	finish_source_swap();
-	if (n_kept) *n_kept = (size_t)m;
-	if (p_.verbose)
-		std::fprintf(stderr, "[goicp] set_source_voxel: %zu -> %zu points, %.2f ms (device reduction %.3f ms, device order %.3f ms)\n", n, N_, now_ms() - t0,
-		             voxel_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
 }
 
 void Engine::radius_outlier_removal(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
@@ -599,10 +581,9 @@ void Engine::radius_outlier_removal(const float* xyz, size_t n, float radius, in
 	radius_frame(xyz, n, radius, min_neighbors, &f);
 	if (registering_.load()) throw std::invalid_argument("goicp_radius_outlier_removal: not while a registration runs");
 	DeviceGuard guard(dev_);
-	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_out(3 * n);
 	Buf<int32_t> d_idx(out_index ? n : 0), d_cnt(out_count ? n : 0);
 	int m = 0;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_radius_outlier_removal(d_xyz, (int)n, f, radius * radius, min_neighbors, d_out, out_index ? d_idx.get() : nullptr,
 	                                     out_count ? d_cnt.get() : nullptr, &m, stream_));
 	if (m > 0) HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
@@ -613,69 +594,15 @@ void Engine::radius_outlier_removal(const float* xyz, size_t n, float radius, in
 	if (p_.verbose) std::fprintf(stderr, "[goicp] radius_outlier_removal: %zu -> %d points\n", n, m);
 }
 
-void Engine::set_source_filtered(const float* xyz, size_t n, float voxel, float radius, int32_t min_neighbors, size_t* n_kept)
-{
-	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_filtered: voxel must be 0 (no stage) or a voxel size > 0");
-	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_filtered: radius must be 0 (no stage) or a radius > 0");
-	if (!(radius > 0.f)) {
-		// no radius stage: the two existing swaps, bit for bit
-		if (voxel > 0.f) {
-			set_source_voxel(xyz, n, voxel, n_kept);
-		} else {
-			set_source(xyz, n);
-			if (n_kept) *n_kept = n;
-		}
-		return;
-	}
-	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows
-	VoxelFrame fv, fr;
-	if (voxel > 0.f) {
-		voxel_frame(xyz, n, voxel, &fv);
-		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
-		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
-	} else {
-		radius_frame(xyz, n, radius, min_neighbors, &fr);
-	}
-	if (registering_.load()) throw std::invalid_argument("goicp_set_source_filtered: not while a registration runs");
-	DeviceGuard guard(dev_);
-	const double t0 = now_ms();
-	TraceRange tr("goicp:set_source_filtered");
-	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
-	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
-	Buf<float> d_raw(3 * n), d_red(voxel > 0.f ? 3 * n : 0);
-	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	const float* d_in = d_raw;
-	int n_in = (int)n;
-	float ms = 0.f;
-	if (voxel > 0.f) {
-		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
-		voxel_ms_ = ms;
-		d_in = d_red;
-		// the frame of the reduced cloud, as radius_frame would find it on the host: 24 bytes come back, not the cloud
-		float mn[3], mx[3];
-		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
-		radius_frame_of_box(mn, mx, (size_t)n_in, radius, min_neighbors, &fr);
-	}
-	Buf<float> d_kept(3 * (size_t)n_in);
-	int m = 0;
-	HIPCHK(launch_radius_outlier_removal(d_in, n_in, fr, radius * radius, min_neighbors, d_kept, nullptr, nullptr, &m, stream_, ev0_, ev1_));
-	HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
-	outlier_ms_ = ms;
-	if (m < 1) throw std::invalid_argument("goicp_set_source_filtered: the filter keeps no point");
-	check_swap_size((size_t)m, "goicp_set_source_filtered");
-	std::vector<float> kept(3 * (size_t)m);
-	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipStreamSynchronize(stream_));
-	load_source(kept.data(), (size_t)m, true, d_kept);
-	finish_source_swap();
-	if (n_kept) *n_kept = (size_t)m;
-	if (p_.verbose)
-		std::fprintf(stderr, "[goicp] set_source_filtered: %zu -> %d -> %zu points, %.2f ms (device voxel %.3f ms, device outlier %.3f ms, device order %.3f ms)\n", n,
-		             n_in, N_, now_ms() - t0, voxel > 0.f ? voxel_ms_ : 0.0, outlier_ms_, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
-}
-
 namespace {
+
+std::vector<float> stat_sample_host(const float* xyz, size_t n)
+{
+	const size_t ns = stat_sample_size(n), stride = n / ns;
+	std::vector<float> s(3 * ns);
+	for (size_t i = 0; i < ns; i++) std::memcpy(&s[3 * i], xyz + 3 * i * stride, 3 * sizeof(float));
+	return s;
+}
 
 // the level plan of a cloud with these bounds: the frames and squared radii launch_stat_outlier_removal searches by
 struct StatPlan {
@@ -695,15 +622,14 @@ struct StatPlan {
 			r2[(size_t)L] = r * r;
 		}
 	}
+	// of a cloud the host holds, which stat_check_cloud checks on the way
+	static StatPlan of_host_cloud(const float* xyz, size_t n, int32_t k)
+	{
+		float mn[3], mx[3];
+		stat_check_cloud(xyz, n, mn, mx);
+		return StatPlan(mn, mx, n, k, stat_sample_host(xyz, n));
+	}
 };
-
-std::vector<float> stat_sample_host(const float* xyz, size_t n)
-{
-	const size_t ns = stat_sample_size(n), stride = n / ns;
-	std::vector<float> s(3 * ns);
-	for (size_t i = 0; i < ns; i++) std::memcpy(&s[3 * i], xyz + 3 * i * stride, 3 * sizeof(float));
-	return s;
-}
 
 void stat_report_line(const char* what, size_t n, int m, const StatReport& rep)
 {
@@ -718,18 +644,15 @@ void Engine::statistical_outlier_removal(const float* xyz, size_t n, int32_t nei
                                          float* out_mean_dist, double* threshold, size_t* m_out)
 {
 	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_statistical_outlier_removal: out_xyz and m must be non-null");
-	float mn[3], mx[3];
-	stat_check_cloud(xyz, n, mn, mx);
 	stat_check_params(n, neighbors, std_ratio);
+	const StatPlan plan = StatPlan::of_host_cloud(xyz, n, neighbors);
 	if (registering_.load()) throw std::invalid_argument("goicp_statistical_outlier_removal: not while a registration runs");
-	const StatPlan plan(mn, mx, n, neighbors, stat_sample_host(xyz, n));
 	DeviceGuard guard(dev_);
-	Buf<float> d_xyz(3 * n), d_out(3 * n), d_mean(out_mean_dist ? n : 0);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_out(3 * n), d_mean(out_mean_dist ? n : 0);
 	Buf<int32_t> d_idx(out_index ? n : 0);
 	int m = 0;
 	double thr = 0.0;
 	StatReport rep;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_stat_outlier_removal(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), neighbors, std_ratio, d_out,
 	                                   out_index ? d_idx.get() : nullptr, out_mean_dist ? d_mean.get() : nullptr, &thr, &m, &rep, stream_));
 	HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
@@ -744,17 +667,14 @@ void Engine::statistical_outlier_removal(const float* xyz, size_t n, int32_t nei
 void Engine::knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
 {
 	if (!out_index) throw std::invalid_argument("goicp_knn_self: out_index must be non-null");
-	float mn[3], mx[3];
-	stat_check_cloud(xyz, n, mn, mx);
 	knn_self_check_params(n, k);
+	const StatPlan plan = StatPlan::of_host_cloud(xyz, n, k);
 	if (registering_.load()) throw std::invalid_argument("goicp_knn_self: not while a registration runs");
-	const StatPlan plan(mn, mx, n, k, stat_sample_host(xyz, n));
 	DeviceGuard guard(dev_);
 	const size_t rows = n * (size_t)k;
-	Buf<float> d_xyz(3 * n), d_d2(out_dist_sq ? rows : 0);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_d2(out_dist_sq ? rows : 0);
 	Buf<int32_t> d_idx(rows);
 	StatReport rep;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_self_knn(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, d_idx, out_dist_sq ? d_d2.get() : nullptr, nullptr,
 	                       &rep, stream_, ev0_, ev1_));
 	HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, stream_));
@@ -771,17 +691,14 @@ void Engine::knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index,
 void Engine::estimate_normals(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index)
 {
 	if (!out_normals) throw std::invalid_argument("goicp_estimate_normals: out_normals must be non-null");
-	float mn[3], mx[3];
-	stat_check_cloud(xyz, n, mn, mx);
 	normals_check_params(n, k, vp);
+	const StatPlan plan = StatPlan::of_host_cloud(xyz, n, k - 1);
 	if (registering_.load()) throw std::invalid_argument("goicp_estimate_normals: not while a registration runs");
-	const StatPlan plan(mn, mx, n, k - 1, stat_sample_host(xyz, n));
 	DeviceGuard guard(dev_);
 	const size_t rows = n * (size_t)(k - 1);
-	Buf<float> d_xyz(3 * n), d_nrm(3 * n), d_var(out_variation ? n : 0);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_nrm(3 * n), d_var(out_variation ? n : 0);
 	Buf<int32_t> d_idx(rows);
 	StatReport rep;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_estimate_normals(d_xyz, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, vp, d_nrm,
 	                               out_variation ? d_var.get() : nullptr, d_idx, &rep, stream_, ev0_, ev1_));
 	HIPCHK(hipMemcpyAsync(out_normals, d_nrm, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, stream_));
@@ -800,11 +717,9 @@ void Engine::estimate_normals(const float* xyz, size_t n, int32_t k, const float
 void Engine::build_source_normals(const float* h_xyz, const float* d_xyz, const int32_t* d_perm)
 {
 	const int k = source_normal_k_;
-	float mn[3], mx[3];
-	stat_check_cloud(h_xyz, N_, mn, mx);
 	normals_check_params(N_, k, nullptr);
 	const double t0 = now_ms();
-	const StatPlan plan(mn, mx, N_, k - 1, stat_sample_host(h_xyz, N_));
+	const StatPlan plan = StatPlan::of_host_cloud(h_xyz, N_, k - 1);
 	Buf<float> d_up(d_xyz ? 0 : 3 * N_), d_nrm(3 * N_);
 	Buf<int32_t> d_idx(N_ * (size_t)(k - 1)), d_pu(d_perm ? 0 : N_);
 	StatReport rep;
@@ -906,100 +821,6 @@ void Engine::set_source_normals(const float* normals, size_t n)
 	src_normals_k_ = 0;
 }
 
-void Engine::set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
-                                 size_t* n_kept)
-{
-	if (stat_neighbors < 0) throw std::invalid_argument("goicp_set_source_pipeline: stat_neighbors must be 0 (no stage) or in 1..64");
-	if (stat_neighbors == 0) {
-		// no statistical stage: the filtered swap, bit for bit
-		set_source_filtered(xyz, n, voxel, radius, min_neighbors, n_kept);
-		return;
-	}
-	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_pipeline: voxel must be 0 (no stage) or a voxel size > 0");
-	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_pipeline: radius must be 0 (no stage) or a radius > 0");
-	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows
-	VoxelFrame fv;
-	float mn[3], mx[3];
-	if (voxel > 0.f) {
-		voxel_frame(xyz, n, voxel, &fv);
-		stat_check_params(65, stat_neighbors, stat_std_ratio);   // the range of k and the ratio; k against the reduced cloud's size below
-	} else {
-		stat_check_cloud(xyz, n, mn, mx);
-		stat_check_params(n, stat_neighbors, stat_std_ratio);
-	}
-	if (radius > 0.f) {
-		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
-		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
-	}
-	if (registering_.load()) throw std::invalid_argument("goicp_set_source_pipeline: not while a registration runs");
-	DeviceGuard guard(dev_);
-	const double t0 = now_ms();
-	TraceRange tr("goicp:set_source_pipeline");
-	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
-	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
-	Buf<float> d_raw(3 * n), d_red(voxel > 0.f ? 3 * n : 0);
-	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
-	const float* d_in = d_raw;
-	int n_in = (int)n;
-	float voxel_ms = 0.f, stat_ms = 0.f, outlier_ms = 0.f;
-	if (voxel > 0.f) {
-		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&voxel_ms, ev0_, ev1_));
-		d_in = d_red;
-		stat_check_params((size_t)n_in, stat_neighbors, stat_std_ratio);
-		// the bounds of the reduced cloud, as stat_check_cloud would find them on the host: 24 bytes come back, not the cloud
-		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
-	}
-	const int n_voxel = n_in;
-	Buf<float> d_stat(3 * (size_t)n_in);
-	int m = 0;
-	StatReport rep;
-	{
-		// the sample that steers the first radius: from the host's cloud, or 48 KB of the reduced cloud
-		std::vector<float> sample;
-		if (voxel > 0.f) {
-			const size_t ns = stat_sample_size((size_t)n_in), stride = (size_t)n_in / ns;
-			sample.resize(3 * ns);
-			HIPCHK(hipMemcpy2DAsync(sample.data(), 3 * sizeof(float), d_in, 3 * sizeof(float) * stride, 3 * sizeof(float), ns, hipMemcpyDeviceToHost, stream_));
-			HIPCHK(hipStreamSynchronize(stream_));
-		} else {
-			sample = stat_sample_host(xyz, n);
-		}
-		const StatPlan plan(mn, mx, (size_t)n_in, stat_neighbors, sample);
-		HIPCHK(launch_stat_outlier_removal(d_in, n_in, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), stat_neighbors, stat_std_ratio, d_stat,
-		                                   nullptr, nullptr, nullptr, &m, &rep, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&stat_ms, ev0_, ev1_));
-	}
-	const int n_stat = m;
-	Buf<float> d_kept(radius > 0.f ? 3 * (size_t)m : 0);
-	const float* d_final = d_stat;
-	if (radius > 0.f) {
-		VoxelFrame fr;
-		HIPCHK(launch_cloud_minmax(d_stat, m, mn, mx, stream_));
-		radius_frame_of_box(mn, mx, (size_t)m, radius, min_neighbors, &fr);
-		int kept = 0;
-		HIPCHK(launch_radius_outlier_removal(d_stat, m, fr, radius * radius, min_neighbors, d_kept, nullptr, nullptr, &kept, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&outlier_ms, ev0_, ev1_));
-		m = kept;
-		d_final = d_kept;
-	}
-	if (m < 1) throw std::invalid_argument("goicp_set_source_pipeline: the chain keeps no point");
-	check_swap_size((size_t)m, "goicp_set_source_pipeline");
-	std::vector<float> kept(3 * (size_t)m);
-	HIPCHK(hipMemcpyAsync(kept.data(), d_final, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-	HIPCHK(hipStreamSynchronize(stream_));
-	if (voxel > 0.f) voxel_ms_ = voxel_ms;
-	if (radius > 0.f) outlier_ms_ = outlier_ms;
-	load_source(kept.data(), (size_t)m, true, d_final);
-	finish_source_swap();
-	if (n_kept) *n_kept = (size_t)m;
-	if (p_.verbose) {
-		stat_report_line("set_source_pipeline statistical stage", (size_t)n_voxel, n_stat, rep);
-		std::fprintf(stderr, "[goicp] set_source_pipeline: %zu -> %d -> %d -> %zu points, %.2f ms (device voxel %.3f ms, device statistical %.3f ms, device outlier %.3f ms, device order %.3f ms)\n",
-		             n, n_voxel, n_stat, N_, now_ms() - t0, voxel_ms, stat_ms, outlier_ms, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
-	}
-}
-
 void Engine::cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters)
 {
 	if (!out_label || !n_clusters) throw std::invalid_argument("goicp_cluster: out_label and n_clusters must be non-null");
@@ -1007,10 +828,9 @@ void Engine::cluster(const float* xyz, size_t n, float radius, int32_t min_neigh
 	cluster_frame(xyz, n, radius, min_neighbors, &f);
 	if (registering_.load()) throw std::invalid_argument("goicp_cluster: not while a registration runs");
 	DeviceGuard guard(dev_);
-	Buf<float> d_xyz(3 * n);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_);
 	Buf<int32_t> d_label(n), d_sizes(n);
 	int c = 0;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_cluster(d_xyz, (int)n, f, radius * radius, min_neighbors, d_label, d_sizes, &c, stream_, ev0_, ev1_));
 	HIPCHK(hipMemcpyAsync(out_label, d_label, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
 	if (out_sizes && c > 0) HIPCHK(hipMemcpyAsync(out_sizes, d_sizes, sizeof(int32_t) * (size_t)c, hipMemcpyDeviceToHost, stream_));
@@ -1062,11 +882,10 @@ void Engine::cluster_filter(const float* xyz, size_t n, float radius, int32_t mi
 	cluster_frame(xyz, n, radius, min_neighbors, &f);
 	if (registering_.load()) throw std::invalid_argument("goicp_cluster_filter: not while a registration runs");
 	DeviceGuard guard(dev_);
-	Buf<float> d_xyz(3 * n), d_out(3 * n);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_out(3 * n);
 	Buf<int32_t> d_idx(out_index ? n : 0), d_lab(out_label ? n : 0);
 	int m = 0, c = 0;
 	float ms = 0.f;
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	cluster_filter_device(d_xyz, (int)n, f, radius, min_neighbors, min_size, max_clusters, d_out, out_index ? d_idx.get() : nullptr,
 	                      out_label ? d_lab.get() : nullptr, &m, &c, stream_, ev0_, ev1_, &ms);
 	if (m > 0) HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
@@ -1077,116 +896,122 @@ void Engine::cluster_filter(const float* xyz, size_t n, float radius, int32_t mi
 	if (p_.verbose) std::fprintf(stderr, "[goicp] cluster_filter: %zu -> %d points of %d clusters, device %.3f ms\n", n, m, c, ms);
 }
 
-void Engine::set_source_clustered(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
-                                  float cluster_radius, int32_t cluster_min_neighbors, int32_t cluster_min_size, int32_t cluster_max_clusters, size_t* n_kept)
+void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const SourceStages& st, size_t* n_kept)
 {
-	if (std::isnan(cluster_radius) || cluster_radius < 0.f) throw std::invalid_argument("goicp_set_source_clustered: the cluster radius must be 0 (no stage) or a radius > 0");
-	if (cluster_min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
-	cluster_check_select(cluster_min_size, cluster_max_clusters);
-	if (!(cluster_radius > 0.f)) {
-		// no cluster stage: the three-stage swap, bit for bit
-		set_source_pipeline(xyz, n, voxel, stat_neighbors, stat_std_ratio, radius, min_neighbors, n_kept);
+	const std::string who(fn);
+	if (std::isnan(st.voxel) || st.voxel < 0.f) throw std::invalid_argument(who + ": voxel must be 0 (no stage) or a voxel size > 0");
+	if (st.stat_neighbors < 0) throw std::invalid_argument(who + ": stat_neighbors must be 0 (no stage) or in 1..64");
+	if (std::isnan(st.radius) || st.radius < 0.f) throw std::invalid_argument(who + ": radius must be 0 (no stage) or a radius > 0");
+	if (std::isnan(st.cluster_radius) || st.cluster_radius < 0.f) throw std::invalid_argument(who + ": the cluster radius must be 0 (no stage) or a radius > 0");
+	// the counts of the cluster stage are refused with that stage off too; every other parameter of a stage that is off is not looked at
+	if (st.cluster_min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
+	cluster_check_select(st.cluster_min_size, st.cluster_max_clusters);
+	const bool has_voxel = st.voxel > 0.f, has_stat = st.stat_neighbors > 0, has_radius = st.radius > 0.f, has_cluster = st.cluster_radius > 0.f;
+	if (!has_voxel && !has_stat && !has_radius && !has_cluster) {
+		set_source(xyz, n, fn);
+		if (n_kept) *n_kept = n;
 		return;
 	}
-	if (std::isnan(voxel) || voxel < 0.f) throw std::invalid_argument("goicp_set_source_clustered: voxel must be 0 (no stage) or a voxel size > 0");
-	if (std::isnan(radius) || radius < 0.f) throw std::invalid_argument("goicp_set_source_clustered: radius must be 0 (no stage) or a radius > 0");
-	if (stat_neighbors < 0) throw std::invalid_argument("goicp_set_source_clustered: stat_neighbors must be 0 (no stage) or in 1..64");
 	// everything that can refuse comes first: a refused call leaves the engine as it was.  The stages write no member the ABI shows.  The
-	// first stage that runs checks the raw cloud; what a later stage can only refuse of its own input is refused when that input exists,
-	// still before the swap
-	const bool has_voxel = voxel > 0.f, has_stat = stat_neighbors > 0, has_radius = radius > 0.f;
-	VoxelFrame fv, fr, fc;
+	// first stage that runs checks the raw cloud and takes its frame (the statistical stage: its bounds) from the host's walk over it; of
+	// the later stages the parameters are checked here, and what only their input can show when that input exists, still before the swap
+	VoxelFrame f;
 	float mn[3], mx[3];
-	if (has_voxel) voxel_frame(xyz, n, voxel, &fv);
+	if (has_voxel) voxel_frame(xyz, n, st.voxel, &f);
 	else if (has_stat) stat_check_cloud(xyz, n, mn, mx);
-	else if (has_radius) radius_frame(xyz, n, radius, min_neighbors, &fr);
-	else cluster_frame(xyz, n, cluster_radius, cluster_min_neighbors, &fc);
-	if (has_stat) stat_check_params(has_voxel ? 65 : n, stat_neighbors, stat_std_ratio);
-	if (has_radius) {
-		if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
-		if (!std::isfinite(radius) || !std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: the radius must be finite and radius * radius a normal float");
-	}
-	if (!std::isfinite(cluster_radius) || !std::isnormal(cluster_radius * cluster_radius))
-		throw std::invalid_argument("goicp cluster: the radius must be finite and radius * radius a normal float");
-	if (registering_.load()) throw std::invalid_argument("goicp_set_source_clustered: not while a registration runs");
+	else if (has_radius) radius_frame(xyz, n, st.radius, st.min_neighbors, &f);
+	else cluster_frame(xyz, n, st.cluster_radius, st.cluster_min_neighbors, &f);
+	if (has_stat) stat_check_params(has_voxel ? 65 : n, st.stat_neighbors, st.stat_std_ratio);   // behind the grid: the range of k and the ratio alone
+	if (has_radius) radius_check_params(st.radius, st.min_neighbors);
+	if (has_cluster) radius_check_params(st.cluster_radius, std::max(st.cluster_min_neighbors, 1));
+	if (registering_.load()) throw std::invalid_argument(who + ": not while a registration runs");
 	DeviceGuard guard(dev_);
 	const double t0 = now_ms();
-	TraceRange tr("goicp:set_source_clustered");
-	for (int k = 0; k < kMaxLanes; k++) if (lane_stream_[k]) HIPCHK(hipStreamSynchronize(lane_stream_[k]));   // lane 0 is the engine's stream
+	TraceRange tr(fn);
+	sync_lane_streams();
 	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
-	Buf<float> d_raw(3 * n), d_red(has_voxel ? 3 * n : 0);
-	HIPCHK(hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
+	const Buf<float> d_raw = upload_cloud(xyz, n, stream_);
+	Buf<float> d_voxel, d_stat, d_radius, d_cluster;
 	const float* d_in = d_raw;
-	int n_in = (int)n;
-	bool first = true;                                          // d_in is still the raw cloud, whose frame the host has
-	float voxel_ms = 0.f, stat_ms = 0.f, outlier_ms = 0.f, cluster_ms = 0.f;
-	if (has_voxel) {
-		HIPCHK(launch_voxel_downsample(d_raw, (int)n, fv, d_red, nullptr, &n_in, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&voxel_ms, ev0_, ev1_));
-		d_in = d_red;
+	int n_in = (int)n, m = 0, n_clusters = 0;
+	bool first = true;                                          // d_in is still the raw cloud, which the host has seen
+	float ms = 0.f;
+	std::string counts = std::to_string(n), times;              // of the verbose line
+	// a stage has run: its output is the input of what follows
+	auto ran = [&](const char* stage, const Buf<float>& d_out) {
+		if (m < 1) throw std::invalid_argument(who + ": the chain keeps no point");
+		d_in = d_out;
+		n_in = m;
 		first = false;
+		if (!p_.verbose) return;
+		char t[64];
+		std::snprintf(t, sizeof(t), "device %s %.3f ms, ", stage, ms);
+		counts += " -> " + std::to_string(m);
+		times += t;
+	};
+	// the bounds of an input the host has not seen, as its walk would find them: 24 bytes come back, not the cloud
+	auto bounds = [&] { HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_)); };
+	if (has_voxel) {
+		d_voxel.alloc(3 * n);
+		HIPCHK(launch_voxel_downsample(d_in, n_in, f, d_voxel, nullptr, &m, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		ran("voxel", d_voxel);
 	}
-	const int n_voxel = n_in;
-	Buf<float> d_stat(has_stat ? 3 * (size_t)n_in : 0);
 	if (has_stat) {
+		// the sample that steers the first radius: from the host's cloud, or 48 KB of the one on the device
 		std::vector<float> sample;
-		if (!first) {
-			stat_check_params((size_t)n_in, stat_neighbors, stat_std_ratio);
-			HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
+		if (first) {
+			sample = stat_sample_host(xyz, n);
+		} else {
+			stat_check_params((size_t)n_in, st.stat_neighbors, st.stat_std_ratio);
+			bounds();
 			const size_t ns = stat_sample_size((size_t)n_in), stride = (size_t)n_in / ns;
 			sample.resize(3 * ns);
 			HIPCHK(hipMemcpy2DAsync(sample.data(), 3 * sizeof(float), d_in, 3 * sizeof(float) * stride, 3 * sizeof(float), ns, hipMemcpyDeviceToHost, stream_));
 			HIPCHK(hipStreamSynchronize(stream_));
-		} else {
-			sample = stat_sample_host(xyz, n);
 		}
-		const StatPlan plan(mn, mx, (size_t)n_in, stat_neighbors, sample);
+		const StatPlan plan(mn, mx, (size_t)n_in, st.stat_neighbors, sample);
 		StatReport rep;
-		int m = 0;
-		HIPCHK(launch_stat_outlier_removal(d_in, n_in, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), stat_neighbors, stat_std_ratio, d_stat,
+		d_stat.alloc(3 * (size_t)n_in);
+		HIPCHK(launch_stat_outlier_removal(d_in, n_in, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), st.stat_neighbors, st.stat_std_ratio, d_stat,
 		                                   nullptr, nullptr, nullptr, &m, &rep, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&stat_ms, ev0_, ev1_));
-		d_in = d_stat;
-		n_in = m;
-		first = false;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		if (p_.verbose) stat_report_line((who.substr(6) + " statistical stage").c_str(), (size_t)n_in, m, rep);
+		ran("statistical", d_stat);
 	}
-	const int n_stat = n_in;
-	Buf<float> d_rad(has_radius ? 3 * (size_t)n_in : 0);
 	if (has_radius) {
 		if (!first) {
-			HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
-			radius_frame_of_box(mn, mx, (size_t)n_in, radius, min_neighbors, &fr);
+			bounds();
+			radius_frame_of_box(mn, mx, (size_t)n_in, st.radius, st.min_neighbors, &f);
 		}
-		int m = 0;
-		HIPCHK(launch_radius_outlier_removal(d_in, n_in, fr, radius * radius, min_neighbors, d_rad, nullptr, nullptr, &m, stream_, ev0_, ev1_));
-		HIPCHK(hipEventElapsedTime(&outlier_ms, ev0_, ev1_));
-		if (m < 1) throw std::invalid_argument("goicp_set_source_clustered: the chain keeps no point");
-		d_in = d_rad;
-		n_in = m;
-		first = false;
+		d_radius.alloc(3 * (size_t)n_in);
+		HIPCHK(launch_radius_outlier_removal(d_in, n_in, f, st.radius * st.radius, st.min_neighbors, d_radius, nullptr, nullptr, &m, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		ran("outlier", d_radius);
 	}
-	const int n_radius = n_in;
-	if (!first) {
-		HIPCHK(launch_cloud_minmax(d_in, n_in, mn, mx, stream_));
-		cluster_frame_of_box(mn, mx, (size_t)n_in, cluster_radius, cluster_min_neighbors, &fc);
+	if (has_cluster) {
+		if (!first) {
+			bounds();
+			cluster_frame_of_box(mn, mx, (size_t)n_in, st.cluster_radius, st.cluster_min_neighbors, &f);
+		}
+		d_cluster.alloc(3 * (size_t)n_in);
+		cluster_filter_device(d_in, n_in, f, st.cluster_radius, st.cluster_min_neighbors, st.cluster_min_size, st.cluster_max_clusters, d_cluster, nullptr, nullptr,
+		                      &m, &n_clusters, stream_, ev0_, ev1_, &ms);
+		ran("cluster", d_cluster);
 	}
-	Buf<float> d_kept(3 * (size_t)n_in);
-	int m = 0, c = 0;
-	cluster_filter_device(d_in, n_in, fc, cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_max_clusters, d_kept, nullptr, nullptr, &m, &c,
-	                      stream_, ev0_, ev1_, &cluster_ms);
-	if (m < 1) throw std::invalid_argument("goicp_set_source_clustered: the selection keeps no point");
-	check_swap_size((size_t)m, "goicp_set_source_clustered");
-	std::vector<float> kept(3 * (size_t)m);
-	HIPCHK(hipMemcpyAsync(kept.data(), d_kept, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	check_swap_size((size_t)n_in, fn);
+	std::vector<float> kept(3 * (size_t)n_in);
+	HIPCHK(hipMemcpyAsync(kept.data(), d_in, sizeof(float) * 3 * (size_t)n_in, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));
-	if (has_voxel) voxel_ms_ = voxel_ms;
-	if (has_radius) outlier_ms_ = outlier_ms;
-	load_source(kept.data(), (size_t)m, true, d_kept);
+	load_source(kept.data(), (size_t)n_in, true, d_in);
 	finish_source_swap();
-	if (n_kept) *n_kept = (size_t)m;
-	if (p_.verbose)
-		std::fprintf(stderr, "[goicp] set_source_clustered: %zu -> %d -> %d -> %d -> %zu points of %d clusters, %.2f ms (device voxel %.3f ms, device statistical %.3f ms, device outlier %.3f ms, device cluster %.3f ms, device order %.3f ms)\n",
-		             n, n_voxel, n_stat, n_radius, N_, c, now_ms() - t0, voxel_ms, stat_ms, outlier_ms, cluster_ms, p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
+	if (n_kept) *n_kept = N_;
+	if (p_.verbose) {
+		if (has_cluster) counts += " points of " + std::to_string(n_clusters) + " clusters";
+		else counts += " points";
+		std::fprintf(stderr, "[goicp] %s: %s, %.2f ms (%sdevice order %.3f ms)\n", fn + 6, counts.c_str(), now_ms() - t0, times.c_str(),
+		             p_.morton_sort >= 1 ? source_order_ms_ : 0.0);
+	}
 }
 
 void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm)
@@ -1198,9 +1023,8 @@ void Engine::debug_source_order(const float* xyz, size_t n, int mode, int32_t* p
 	DeviceGuard guard(dev_);
 	float mn[3] = {0, 0, 0}, ext = 1.f;
 	if (mode == 1) source_morton_frame(xyz, n, mn, &ext);
-	Buf<float> d_xyz(3 * n);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_);
 	Buf<int32_t> d_perm(n);
-	HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, stream_));
 	HIPCHK(launch_source_order(d_xyz, (int)n, mode, mn, ext, d_perm, stream_));
 	HIPCHK(hipMemcpyAsync(perm, d_perm, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
 	HIPCHK(hipStreamSynchronize(stream_));

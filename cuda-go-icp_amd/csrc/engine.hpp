@@ -297,32 +297,40 @@ public:
 	void source_transformed(const float R[9], const float t[3], float* out_xyz);  // original order
 	// goicp_set_source: a new source cloud under the same target -- everything derived from the target is kept (distance transform, k-d
 	// hierarchy, nearest-point table, normals, streams, queues, warm-ups), the params and the per-handle options persist, the search / ICP
-	// state is the one of a fresh engine.  The order is computed on the device (kdbuild.hip).  Refused while a registration runs
-	void set_source(const float* source_xyz, size_t N);
+	// state is the one of a fresh engine.  The order is computed on the device (kdbuild.hip).  Refused while a registration runs.  fn: the C
+	// entry point the caller used, which the refusals, the trace range and the verbose line name
+	void set_source(const float* source_xyz, size_t N, const char* fn = "goicp_set_source");
+	// goicp_set_source_voxel / _filtered / _pipeline / _clustered: one chain, of which each entry point can switch on its share of the stages
+	// voxel grid -> statistical filter -> radius filter -> cluster selection (a stage whose size is 0 is off; with none on it is
+	// set_source).  The raw cloud goes up once, each stage reads the one before it on the device, only the final cloud and the permutation
+	// come back; afterwards the engine is the one set_source(the composition of the host functions) leaves.  What the arguments and the raw
+	// cloud show is refused before any device work (the first stage that runs checks the raw cloud on the host and takes its frame from
+	// it); what only an intermediate cloud shows (k above its size, the 2^16 rule of a later grid, a stage that keeps no point) when that
+	// cloud exists, still before load_source: a refused call leaves the engine as it was
+	struct SourceStages {
+		float voxel = 0.f;
+		int32_t stat_neighbors = 0;
+		float stat_std_ratio = 0.f;
+		float radius = 0.f;
+		int32_t min_neighbors = 0;
+		float cluster_radius = 0.f;
+		int32_t cluster_min_neighbors = 0, cluster_min_size = 0, cluster_max_clusters = 0;
+	};
+	void set_source_staged(const char* fn, const float* xyz, size_t n, const SourceStages& st, size_t* n_kept);
 	// goicp_debug_source_order (test): the device ordering alone, of any cloud
 	void debug_source_order(const float* xyz, size_t n, int mode, int32_t* perm);
 	double last_source_order_ms() const { return source_order_ms_; }   // the device ordering of the last set_source (HIP events)
 	// goicp_voxel_downsample: the voxel-grid reduction on the device (kdbuild.hip launch_voxel_downsample); the engine lends its device and
 	// stream and nothing else: no member is written.  Refused while a registration runs
 	void voxel_downsample(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
-	// goicp_set_source_voxel: the raw cloud goes up once, is reduced and ordered on the device; only the reduced cloud and the permutation
-	// come back.  Afterwards the engine is the one set_source(voxel_downsample_host's output) leaves
-	void set_source_voxel(const float* xyz, size_t n, float voxel, size_t* n_kept);
 	// goicp_radius_outlier_removal: the radius filter on the device (kdbuild.hip launch_radius_outlier_removal); as voxel_downsample, the
 	// engine lends its device and stream and nothing else
 	void radius_outlier_removal(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index, int32_t* out_count,
 	                            size_t* m);
-	// goicp_set_source_filtered: voxel grid (voxel > 0), then radius filter (radius > 0), then the swap; the raw cloud goes up once, the
-	// stages are chained on the device, only the final cloud and the permutation come back.  A filter that keeps nothing is refused
-	void set_source_filtered(const float* xyz, size_t n, float voxel, float radius, int32_t min_neighbors, size_t* n_kept);
 	// goicp_statistical_outlier_removal: the statistical filter on the device (kdbuild.hip launch_stat_outlier_removal); as voxel_downsample,
 	// the engine lends its device and stream and nothing else
 	void statistical_outlier_removal(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
 	                                 float* out_mean_dist, double* threshold, size_t* m);
-	// goicp_set_source_pipeline: voxel grid (voxel > 0), statistical filter (stat_neighbors > 0), radius filter (radius > 0), then the swap,
-	// chained on the device behind one upload.  With the statistical stage off it is set_source_filtered
-	void set_source_pipeline(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
-	                         size_t* n_kept);
 	// goicp_knn_self / goicp_estimate_normals: the exact self k-NN and the normals of any cloud on the device (kdbuild.hip launch_self_knn /
 	// launch_estimate_normals); as statistical_outlier_removal, the engine lends its device and stream and nothing else
 	void knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
@@ -332,10 +340,6 @@ public:
 	void cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
 	void cluster_filter(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
 	                    int32_t* out_index, int32_t* out_label, size_t* m);
-	// goicp_set_source_clustered: set_source_pipeline's stages, then the cluster selection (cluster_radius > 0), then the swap, chained on the
-	// device behind one upload.  With the cluster stage off it is set_source_pipeline.  A selection that keeps nothing is refused
-	void set_source_clustered(const float* xyz, size_t n, float voxel, int32_t stat_neighbors, float stat_std_ratio, float radius, int32_t min_neighbors,
-	                          float cluster_radius, int32_t cluster_min_neighbors, int32_t cluster_min_size, int32_t cluster_max_clusters, size_t* n_kept);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -344,10 +348,11 @@ private:
 	static void check_source(const float* source_xyz, size_t N);
 	// the source stage of init and all of set_source's device work: order (host, or device when device_order) -> gather with |p| ->
 	// centroid -> upload -> the N-sized buffers (grow-only)
-	// d_xyz_ready: the same cloud already on the device (3 N floats; set_source_voxel), which the device order then reads instead of an upload
+	// d_xyz_ready: the same cloud already on the device (3 N floats; set_source_staged), which the device order then reads instead of an upload
 	void load_source(const float* source_xyz, size_t N, bool device_order, const float* d_xyz_ready = nullptr);
-	void finish_source_swap();                       // set_source / set_source_voxel after load_source: the search and ICP state of a fresh engine
-	double source_order_ms_ = 0, voxel_ms_ = 0, outlier_ms_ = 0;
+	void finish_source_swap();                       // set_source / set_source_staged after load_source: the search and ICP state of a fresh engine
+	void sync_lane_streams();                        // a swap waits for what the lanes still have in flight before it touches the source buffers
+	double source_order_ms_ = 0;
 	void ensure_batch(size_t B, size_t K);
 	void ensure_stage(size_t B);
 	const BoundsOrder* ensure_bounds_order(int B, hipStream_t s);   // the order / pair buffers for a launch of B cube bounds (nullptr: the plain launch); grows like the scratch
@@ -608,11 +613,12 @@ void source_morton_frame(const float* xyz, size_t n, float mn[3], float* ext);
 // voxel_downsample_host is goicp_voxel_downsample_host: out_xyz holds 3 n floats, out_count (may be null) n ints
 void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f);
 void voxel_downsample_host(const float* xyz, size_t n, float voxel, float* out_xyz, int32_t* out_count, size_t* m);
-// radius outlier removal (kdtree.cpp).  radius_frame checks the cloud, the radius and min_neighbors (std::invalid_argument: what
-// voxel_frame refuses, a radius that is not positive and finite or whose square is no normal float, min_neighbors < 1, extent / radius >=
-// 2^16) and fills the frame of the grid of pitch radius * 1.03125f; radius_frame_of_box is the same from the per-axis bounds of a cloud the
-// host has not seen.  radius_outlier_removal_host is goicp_radius_outlier_removal_host: out_xyz holds 3 n floats, out_index (may be null) n
-// ints, out_count (may be null) n ints
+// radius outlier removal (kdtree.cpp).  radius_check_params refuses what needs no cloud (std::invalid_argument: a radius that is
+// not positive and finite or whose square is no normal float, min_neighbors < 1); radius_frame checks those and the cloud (what voxel_frame
+// refuses, extent / radius >= 2^16) and fills the frame of the grid of pitch radius * 1.03125f; radius_frame_of_box is the same from the
+// per-axis bounds of a cloud the host has not seen.  radius_outlier_removal_host is goicp_radius_outlier_removal_host: out_xyz holds 3 n
+// floats, out_index (may be null) n ints, out_count (may be null) n ints
+void radius_check_params(float radius, int32_t min_neighbors);
 void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,

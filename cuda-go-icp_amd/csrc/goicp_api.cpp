@@ -207,8 +207,10 @@ int goicp_voxel_downsample(goicp_handle h, const float* xyz, size_t n, float vox
 
 int goicp_set_source_voxel(goicp_handle h, const float* xyz, size_t n, float voxel, size_t* n_kept)
 {
-	REQUIRE(h && xyz && n > 0);
-	return guarded([&] { h->e->set_source_voxel(xyz, n, voxel, n_kept); });
+	REQUIRE(h && xyz && n > 0 && voxel != 0.f);          // this entry point has no "no stage": a voxel of 0 is as bad as a negative one
+	goicp::Engine::SourceStages st;
+	st.voxel = voxel;
+	return guarded([&] { h->e->set_source_staged("goicp_set_source_voxel", xyz, n, st, n_kept); });
 }
 
 int goicp_radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, float* out_xyz, int32_t* out_index,
@@ -237,7 +239,11 @@ void goicp_source_filter_default(goicp_source_filter* out)
 int goicp_set_source_filtered(goicp_handle h, const float* xyz, size_t n, const goicp_source_filter* f, size_t* n_kept)
 {
 	REQUIRE(h && xyz && f && n > 0);
-	return guarded([&] { h->e->set_source_filtered(xyz, n, f->voxel, f->radius, f->min_neighbors, n_kept); });
+	goicp::Engine::SourceStages st;
+	st.voxel = f->voxel;
+	st.radius = f->radius;
+	st.min_neighbors = f->min_neighbors;
+	return guarded([&] { h->e->set_source_staged("goicp_set_source_filtered", xyz, n, st, n_kept); });
 }
 
 int goicp_statistical_outlier_removal_host(const float* xyz, size_t n, int32_t neighbors, float std_ratio, float* out_xyz, int32_t* out_index,
@@ -265,10 +271,22 @@ void goicp_source_pipeline_default(goicp_source_pipeline* out)
 	out->min_neighbors = 0;
 }
 
+// the first three stages of the chain, as the C struct names them
+static goicp::Engine::SourceStages stages_of(const goicp_source_pipeline& p)
+{
+	goicp::Engine::SourceStages st;
+	st.voxel = p.voxel;
+	st.stat_neighbors = p.stat_neighbors;
+	st.stat_std_ratio = p.stat_std_ratio;
+	st.radius = p.radius;
+	st.min_neighbors = p.min_neighbors;
+	return st;
+}
+
 int goicp_set_source_pipeline(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, size_t* n_kept)
 {
 	REQUIRE(h && xyz && p && n > 0);
-	return guarded([&] { h->e->set_source_pipeline(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, n_kept); });
+	return guarded([&] { h->e->set_source_staged("goicp_set_source_pipeline", xyz, n, stages_of(*p), n_kept); });
 }
 
 int goicp_cluster_host(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters)
@@ -310,13 +328,13 @@ int goicp_cluster_filter(goicp_handle h, const float* xyz, size_t n, const goicp
 int goicp_set_source_clustered(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_cluster_select* s, size_t* n_kept)
 {
 	REQUIRE(h && xyz && s && n > 0);
-	goicp_source_pipeline none;
-	goicp_source_pipeline_default(&none);
-	if (!p) p = &none;
-	return guarded([&] {
-		h->e->set_source_clustered(xyz, n, p->voxel, p->stat_neighbors, p->stat_std_ratio, p->radius, p->min_neighbors, s->radius, s->min_neighbors, s->min_size,
-		                           s->max_clusters, n_kept);
-	});
+	goicp::Engine::SourceStages st;
+	if (p) st = stages_of(*p);
+	st.cluster_radius = s->radius;
+	st.cluster_min_neighbors = s->min_neighbors;
+	st.cluster_min_size = s->min_size;
+	st.cluster_max_clusters = s->max_clusters;
+	return guarded([&] { h->e->set_source_staged("goicp_set_source_clustered", xyz, n, st, n_kept); });
 }
 
 int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)

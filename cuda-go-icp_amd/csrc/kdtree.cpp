@@ -299,22 +299,24 @@ static void grid_frame(const float* xyz, size_t n, float voxel, float radius, Vo
 
 void voxel_frame(const float* xyz, size_t n, float voxel, VoxelFrame* f) { grid_frame(xyz, n, voxel, 0.f, f); }
 
+void radius_check_params(float radius, int32_t min_neighbors)
+{
+	if (!(radius > 0.f) || !std::isfinite(radius)) throw std::invalid_argument("goicp outlier: the radius must be positive and finite");
+	if (!std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: radius * radius must be a normal float");
+	if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+}
+
 void radius_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
 {
 	if (!xyz || n == 0) throw std::invalid_argument("goicp outlier: empty cloud");
 	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp outlier: cloud too large");
-	if (!(radius > 0.f) || !std::isfinite(radius)) throw std::invalid_argument("goicp outlier: the radius must be positive and finite");
-	const float r2 = radius * radius;
-	if (!std::isnormal(r2)) throw std::invalid_argument("goicp outlier: radius * radius must be a normal float");
-	if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+	radius_check_params(radius, min_neighbors);
 	grid_frame(xyz, n, radius * 1.03125f, radius, f);
 }
 
 void radius_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f)
 {
-	if (!(radius > 0.f) || !std::isfinite(radius)) throw std::invalid_argument("goicp outlier: the radius must be positive and finite");
-	if (!std::isnormal(radius * radius)) throw std::invalid_argument("goicp outlier: radius * radius must be a normal float");
-	if (min_neighbors < 1) throw std::invalid_argument("goicp outlier: min_neighbors must be at least 1");
+	radius_check_params(radius, min_neighbors);
 	float E = 0.f;
 	for (int k = 0; k < 3; k++) E = std::max(E, mx[k] - mn[k]);   // rounding is monotone: the largest offset is the one of an axis' maximum
 	fill_frame(mn, E, n, radius * 1.03125f, radius, f);

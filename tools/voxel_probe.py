@@ -3,7 +3,7 @@ gains from a reduced source.
 
 Per case -- bunny (30 k source points), spanner (150 k / 150 k), the synthetic 1 M / 1 M cloud of bench.py's s2 workload -- with the voxel
 bisected (on the host function) so that about 1/8 of the source points remain:
-  (a) device_reduction_ms   the device reduction alone (HIP events around launch_voxel_downsample: the "device reduction" figure of the
+  (a) device_reduction_ms   the device reduction alone (HIP events around launch_voxel_downsample: the "device voxel" figure of the
                             verbose line of goicp_set_source_voxel)
   (b) host_ms               goicp_voxel_downsample_host on the same cloud, wall time on the same machine
   (c) set_source_voxel_ms   goicp_set_source_voxel(S, voxel) wall time, next to set_source_raw_ms: goicp_set_source(S) of the raw cloud, both on
@@ -79,7 +79,7 @@ def run_case(pkg, name, T, S, kw, reps, limit):
             assert lib.goicp_set_source_voxel(v.handle, S.ctypes.data_as(fp), len(S), voxel, C.byref(kept)) == 0, lib.goicp_last_error()
             vox.append((time.perf_counter() - t0) * 1e3)
         assert kept.value == m
-        g = re.search(r"set_source_voxel: \d+ -> \d+ points, [0-9.]+ ms \(device reduction ([0-9.]+) ms", err.text)
+        g = re.search(r"set_source_voxel: \d+ -> \d+ points, [0-9.]+ ms \(device voxel ([0-9.]+) ms", err.text)
         dev.append(float(g.group(1)))
         with Stderr():
             v.set_source(S0)
