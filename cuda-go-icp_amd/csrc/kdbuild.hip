@@ -19,6 +19,55 @@
 
 namespace goicp {
 
+// The device temporaries of one launcher.  get() allocates and keeps the pointer; the destructor frees what was allocated on every exit
+// path -- not what the launcher's locals name by then, so swapping two of them (lists / lists2, cur / nxt) is harmless.  Nothing here
+// throws: the launchers return hipError_t
+class Temps {
+public:
+	Temps() = default;
+	Temps(const Temps&) = delete;
+	Temps& operator=(const Temps&) = delete;
+	~Temps() { for (int i = 0; i < count_; i++) hipFree(owned_[i]); }
+	hipError_t get_bytes(void*& p, size_t bytes)
+	{
+		if (count_ == kMax) return hipErrorOutOfMemory;
+		const hipError_t e = hipMalloc(&p, bytes);
+		if (e == hipSuccess) owned_[count_++] = p;
+		return e;
+	}
+	template <class T> hipError_t get(T*& p, size_t n)
+	{
+		void* v = nullptr;
+		const hipError_t e = get_bytes(v, sizeof(T) * n);
+		p = static_cast<T*>(v);
+		return e;
+	}
+
+private:
+	static constexpr int kMax = 16;                              // the statistical filter's 14 are the most
+	void* owned_[kMax];
+	int count_ = 0;
+};
+#define KD_TRY(x) do { const hipError_t kd_try_e = (x); if (kd_try_e != hipSuccess) return kd_try_e; } while (0)
+
+// the end of a launcher's device work: ev_end (may be null), then the stream drains -- the launcher's temporaries are in use until then
+static hipError_t end_and_drain(hipEvent_t ev_end, hipStream_t stream)
+{
+	if (ev_end) KD_TRY(hipEventRecord(ev_end, stream));
+	return hipStreamSynchronize(stream);
+}
+
+// a 64-bit shuffle is two 32-bit ones
+template <class F> __device__ __forceinline__ unsigned long long shfl64_halves(unsigned long long v, F f)
+{
+	const int lo = f((int)(unsigned)(v & 0xffffffffull));
+	const int hi = f((int)(unsigned)(v >> 32));
+	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+}
+__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src) { return shfl64_halves(v, [=](int w) { return __shfl(w, src, 64); }); }
+__device__ __forceinline__ unsigned long long shfl_up64(unsigned long long v, int off) { return shfl64_halves(v, [=](int w) { return __shfl_up(w, off, 64); }); }
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int off) { return shfl64_halves(v, [=](int w) { return __shfl_xor(w, off, 64); }); }
+
 __device__ __forceinline__ unsigned spread10(unsigned x)
 {
 	x &= 0x3ffu;
@@ -87,28 +136,23 @@ hipError_t launch_kd_build(const float* d_xyz, int M, int K, const float mn[3], 
 	int *vals = nullptr, *vals2 = nullptr;
 	void* tmp = nullptr;
 	size_t tmp_bytes = 0;
-	hipError_t e;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		unsigned*& a; unsigned*& b; int*& c; int*& d; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(t); }
-	} cleanup{keys, keys2, vals, vals2, tmp};
-	if ((e = hipMalloc(&keys, sizeof(unsigned) * M)) != hipSuccess) return e;
-	if ((e = hipMalloc(&keys2, sizeof(unsigned) * M)) != hipSuccess) return e;
-	if ((e = hipMalloc(&vals, sizeof(int) * M)) != hipSuccess) return e;
-	if ((e = hipMalloc(&vals2, sizeof(int) * M)) != hipSuccess) return e;
+	Temps t;
+	KD_TRY(t.get(keys, M));
+	KD_TRY(t.get(keys2, M));
+	KD_TRY(t.get(vals, M));
+	KD_TRY(t.get(vals2, M));
 	hipLaunchKernelGGL(kd_morton_kernel, dim3((M + 255) / 256), dim3(256), 0, stream, d_xyz, M, mn[0], mn[1], mn[2],
 	                   ext > 0.f ? 1.f / ext : 0.f, keys, vals);
-	if ((e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, (size_t)M, 0, 30, stream)) != hipSuccess) return e;
-	if ((e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16)) != hipSuccess) return e;
-	if ((e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys2, vals, vals2, (size_t)M, 0, 30, stream)) != hipSuccess) return e;
+	KD_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, (size_t)M, 0, 30, stream));
+	KD_TRY(t.get_bytes(tmp, tmp_bytes ? tmp_bytes : 16));
+	KD_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys2, vals, vals2, (size_t)M, 0, 30, stream));
 	hipLaunchKernelGGL(kd_leaves_kernel, dim3((L + 255) / 256), dim3(256), 0, stream, d_xyz, vals2, M, L, pts, boxes[K - 1]);
 	for (int l = K - 2; l >= 0; l--) {
 		const int upper_children = 1 << (6 * (l + 1));
 		hipLaunchKernelGGL(kd_level_kernel, dim3((upper_children + 255) / 256), dim3(256), 0, stream, boxes[l + 1], boxes[l], upper_children);
 	}
-	e = hipStreamSynchronize(stream);            // the temporaries are in use until here
-	return e != hipSuccess ? e : hipGetLastError();
+	KD_TRY(hipStreamSynchronize(stream));        // the temporaries are in use until here
+	return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -251,73 +295,66 @@ hipError_t launch_source_order(const float* d_xyz, int n, int mode, const float 
 {
 	if (n <= 0) return hipErrorInvalidValue;
 	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define SO_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
 	if (mode <= 0) {
 		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, d_perm, n);
-		SO_TRY(hipGetLastError());
+		KD_TRY(hipGetLastError());
 		return hipStreamSynchronize(stream);
 	}
 	unsigned *keys = nullptr, *keys2 = nullptr;
 	int *ids = nullptr, *lists = nullptr, *lists2 = nullptr, *scan = nullptr, *seg = nullptr;
 	unsigned char* flag = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		unsigned*& a; unsigned*& b; int*& c; int*& d; int*& f; int*& g; int*& h; unsigned char*& i; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(i); hipFree(t); }
-	} cleanup{keys, keys2, ids, lists, lists2, scan, seg, flag, tmp};
+	Temps t;
 	const size_t N = (size_t)n;
-	SO_TRY(hipMalloc(&keys, sizeof(unsigned) * N));
-	SO_TRY(hipMalloc(&keys2, sizeof(unsigned) * N));
-	SO_TRY(hipMalloc(&ids, sizeof(int) * N));
+	KD_TRY(t.get(keys, N));
+	KD_TRY(t.get(keys2, N));
+	KD_TRY(t.get(ids, N));
 	size_t sort_bytes = 0, scan_bytes = 0;
 	if (mode == 1) {
 		hipLaunchKernelGGL(so_morton_kernel, grd, blk, 0, stream, d_xyz, n, mn[0], mn[1], mn[2], ext, keys, ids);
-		SO_TRY(hipGetLastError());
-		SO_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
-		SO_TRY(hipMalloc(&tmp, sort_bytes ? sort_bytes : 16));
-		SO_TRY(rocprim::radix_sort_pairs(tmp, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
+		KD_TRY(hipGetLastError());
+		KD_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
+		KD_TRY(t.get_bytes(tmp, sort_bytes ? sort_bytes : 16));
+		KD_TRY(rocprim::radix_sort_pairs(tmp, sort_bytes, keys, keys2, ids, d_perm, N, 0, 30, stream));
 		return hipStreamSynchronize(stream);         // the temporaries are in use until here
 	}
 	const int levels = source_order_levels(n);
-	SO_TRY(hipMalloc(&lists, sizeof(int) * 3 * N));
+	KD_TRY(t.get(lists, 3 * N));
 	if (levels > 0) {
-		SO_TRY(hipMalloc(&lists2, sizeof(int) * 3 * N));
-		SO_TRY(hipMalloc(&scan, sizeof(int) * 3 * N));
-		SO_TRY(hipMalloc(&seg, sizeof(int) * 4 * N));
-		SO_TRY(hipMalloc(&flag, N));
+		KD_TRY(t.get(lists2, 3 * N));
+		KD_TRY(t.get(scan, 3 * N));
+		KD_TRY(t.get(seg, 4 * N));
+		KD_TRY(t.get(flag, N));
 	}
 	auto flags_of = [&](const int* l) { return rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), SoFlagOf{l, flag}); };
-	SO_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, lists, N, 0, 32, stream));
-	if (levels > 0) SO_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
+	KD_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, lists, N, 0, 32, stream));
+	if (levels > 0) KD_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
 	const size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
-	SO_TRY(hipMalloc(&tmp, tmp_bytes));
+	KD_TRY(t.get_bytes(tmp, tmp_bytes));
 	for (int k = 0; k < 3; k++) {
 		hipLaunchKernelGGL(so_axis_keys_kernel, grd, blk, 0, stream, d_xyz, n, k, keys, ids);
-		SO_TRY(hipGetLastError());
+		KD_TRY(hipGetLastError());
 		size_t bytes = sort_bytes;
-		SO_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, lists + (size_t)k * N, N, 0, 32, stream));
+		KD_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, lists + (size_t)k * N, N, 0, 32, stream));
 	}
 	if (levels > 0) {
 		int *lo = seg, *hi = seg + N, *lo2 = seg + 2 * N, *hi2 = seg + 3 * N;
 		hipLaunchKernelGGL(so_root_kernel, grd, blk, 0, stream, lo, hi, n);
-		SO_TRY(hipGetLastError());
+		KD_TRY(hipGetLastError());
 		const dim3 grd3((unsigned)((3 * N + 255) / 256));
 		for (int l = 0; l < levels; l++) {
 			hipLaunchKernelGGL(so_flag_kernel, grd, blk, 0, stream, d_xyz, lists, n, lo, hi, lo2, hi2, flag);
-			SO_TRY(hipGetLastError());
+			KD_TRY(hipGetLastError());
 			size_t bytes = scan_bytes;
-			SO_TRY(rocprim::exclusive_scan(tmp, bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
+			KD_TRY(rocprim::exclusive_scan(tmp, bytes, flags_of(lists), scan, 0, 3 * N, rocprim::plus<int>(), stream));
 			hipLaunchKernelGGL(so_partition_kernel, grd3, blk, 0, stream, lists, lists2, n, lo, hi, flag, scan);
-			SO_TRY(hipGetLastError());
+			KD_TRY(hipGetLastError());
 			std::swap(lists, lists2);
 			std::swap(lo, lo2);
 			std::swap(hi, hi2);
 		}
 	}
-	SO_TRY(hipMemcpyAsync(d_perm, lists, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
-#undef SO_TRY
+	KD_TRY(hipMemcpyAsync(d_perm, lists, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
 	return hipStreamSynchronize(stream);             // the temporaries are in use until here
 }
 
@@ -352,11 +389,62 @@ struct VxHeadOf {
 	__device__ int operator()(int i) const { return (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0; }
 };
 
-__device__ __forceinline__ long long vx_shfl_up(long long v, int off)
+// The sorted cell grid of a VoxelFrame, which every grid operator starts from: the key of every point (vx_key_kernel), rocPRIM's radix sort
+// of (key, id) over the frame's used key bits -- stable, and the ids start ascending, so the ids of a cell ascend -- and, for the operators
+// that walk tiles, the gather into sorted 16-byte records
+struct __align__(16) RorPt { float x, y, z; int id; };
+
+__global__ void ror_gather_kernel(const float* __restrict__ xyz, const int* __restrict__ ids, int n, RorPt* __restrict__ pts)
 {
-	const int lo = __shfl_up((int)(unsigned)((unsigned long long)v & 0xffffffffull), off, 64);
-	const int hi = __shfl_up((int)(unsigned)((unsigned long long)v >> 32), off, 64);
-	return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
+	const int s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= n) return;
+	const int id = ids[s];
+	pts[s] = RorPt{xyz[3 * (size_t)id], xyz[3 * (size_t)id + 1], xyz[3 * (size_t)id + 2], id};
+}
+
+struct CellGrid {
+	unsigned long long *keys = nullptr, *sorted_keys = nullptr;  // by input index; ascending
+	int *ids = nullptr, *order = nullptr;                        // 0..n-1; the input index of every sorted position
+	RorPt* pts = nullptr;                                        // the records in sorted order (not allocated for the voxel operator)
+	hipError_t alloc(Temps& t, size_t N, bool records)
+	{
+		KD_TRY(t.get(keys, N));
+		KD_TRY(t.get(sorted_keys, N));
+		KD_TRY(t.get(ids, N));
+		KD_TRY(t.get(order, N));
+		if (records) KD_TRY(t.get(pts, N));
+		return hipSuccess;
+	}
+};
+
+static unsigned grid_end_bit(const VoxelFrame& f) { return (unsigned)std::min(std::max(f.key_bits, 1), 63); }
+
+// bytes = the sort's temporary storage for the largest of `count` frames
+static hipError_t grid_sort_bytes(const CellGrid& g, size_t N, const VoxelFrame* frames, int count, size_t& bytes, hipStream_t stream)
+{
+	bytes = 0;
+	for (int L = 0; L < count; L++) {
+		size_t b = 0;
+		KD_TRY(rocprim::radix_sort_pairs(nullptr, b, g.keys, g.sorted_keys, g.ids, g.order, N, 0, grid_end_bit(frames[L]), stream));
+		bytes = std::max(bytes, b);
+	}
+	return hipSuccess;
+}
+
+// keys and order of frame f; tmp holds sort_bytes as grid_sort_bytes reported them
+static hipError_t grid_sort(const float* d_xyz, int n, const VoxelFrame& f, const CellGrid& g, void* tmp, size_t sort_bytes, hipStream_t stream)
+{
+	hipLaunchKernelGGL(vx_key_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, g.keys, g.ids);
+	KD_TRY(hipGetLastError());
+	return rocprim::radix_sort_pairs(tmp, sort_bytes, g.keys, g.sorted_keys, g.ids, g.order, (size_t)n, 0, grid_end_bit(f), stream);
+}
+
+// grid_sort and the records
+static hipError_t grid_build(const float* d_xyz, int n, const VoxelFrame& f, const CellGrid& g, void* tmp, size_t sort_bytes, hipStream_t stream)
+{
+	KD_TRY(grid_sort(d_xyz, n, f, g, tmp, sort_bytes, stream));
+	hipLaunchKernelGGL(ror_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_xyz, g.order, n, g.pts);
+	return hipGetLastError();
 }
 
 // One thread per SORTED position i (blocks of 256 = 4 waves of 64 consecutive positions).  cell1[i] = 1 + the cell index of position i (the
@@ -389,7 +477,8 @@ __global__ void __launch_bounds__(256) vx_segsum_kernel(const float* __restrict_
 	const int start = below ? 63 - __clzll(below) : 0;          // first lane of this lane's piece
 	const int reach = lane - start;
 	for (int off = 1; off < 64; off <<= 1) {
-		const long long u0 = vx_shfl_up(t0, off), u1 = vx_shfl_up(t1, off), u2 = vx_shfl_up(t2, off);
+		const long long u0 = (long long)shfl_up64((unsigned long long)t0, off), u1 = (long long)shfl_up64((unsigned long long)t1, off),
+		                u2 = (long long)shfl_up64((unsigned long long)t2, off);
 		const int uc = __shfl_up(cnt, off, 64);
 		if (off <= reach) { t0 += u0; t1 += u1; t2 += u2; cnt += uc; }
 	}
@@ -433,54 +522,37 @@ hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& 
 {
 	if (n <= 0 || !m_out) return hipErrorInvalidValue;
 	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define VX_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-	unsigned long long *keys = nullptr, *keys2 = nullptr, *acc = nullptr;
-	int *ids = nullptr, *ids2 = nullptr, *cell1 = nullptr, *first_id = nullptr;
+	unsigned long long* acc = nullptr;
+	int *cell1 = nullptr, *first_id = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		unsigned long long*& a; unsigned long long*& b; unsigned long long*& c; int*& d; int*& f; int*& g; int*& h; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(t); }
-	} cleanup{keys, keys2, acc, ids, ids2, cell1, first_id, tmp};
+	Temps t;
+	CellGrid g;
 	const size_t N = (size_t)n;
-	VX_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
-	VX_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
-	VX_TRY(hipMalloc(&ids, sizeof(int) * N));
-	VX_TRY(hipMalloc(&ids2, sizeof(int) * N));
-	VX_TRY(hipMalloc(&cell1, sizeof(int) * N));
-	// the used key bits only; the sort is stable and the ids start ascending, so the ids of a cell ascend
-	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
-	auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), VxHeadOf{keys2});
+	KD_TRY(g.alloc(t, N, false));
+	KD_TRY(t.get(cell1, N));
+	auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), VxHeadOf{g.sorted_keys});
 	size_t sort_bytes = 0, scan_bytes = 0;
-	VX_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	VX_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, heads, cell1, N, rocprim::plus<int>(), stream));
-	const size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
-	VX_TRY(hipMalloc(&tmp, tmp_bytes));
+	KD_TRY(grid_sort_bytes(g, N, &f, 1, sort_bytes, stream));
+	KD_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, heads, cell1, N, rocprim::plus<int>(), stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
 	// ev_begin .. ev_end: the kernels, the 4-byte read-back of m and the two m-sized allocations; the n-sized allocations above and the
 	// frees at the end are outside
-	if (ev_begin) VX_TRY(hipEventRecord(ev_begin, stream));
-	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
-	VX_TRY(hipGetLastError());
-	size_t bytes = sort_bytes;
-	VX_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	bytes = scan_bytes;
-	VX_TRY(rocprim::inclusive_scan(tmp, bytes, heads, cell1, N, rocprim::plus<int>(), stream));
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(grid_sort(d_xyz, n, f, g, tmp, sort_bytes, stream));
+	KD_TRY(rocprim::inclusive_scan(tmp, scan_bytes, heads, cell1, N, rocprim::plus<int>(), stream));
 	int m = 0;                                                  // the last index + 1
-	VX_TRY(hipMemcpyAsync(&m, cell1 + (N - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
-	VX_TRY(hipStreamSynchronize(stream));
+	KD_TRY(hipMemcpyAsync(&m, cell1 + (N - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
+	KD_TRY(hipStreamSynchronize(stream));
 	if (m < 1 || m > n) return hipErrorUnknown;
-	VX_TRY(hipMalloc(&acc, sizeof(unsigned long long) * 4 * (size_t)m));
-	VX_TRY(hipMalloc(&first_id, sizeof(int) * (size_t)m));
-	VX_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4 * (size_t)m, stream));
-	hipLaunchKernelGGL(vx_segsum_kernel, grd, blk, 0, stream, d_xyz, ids2, cell1, n, f.mn[0], f.mn[1], f.mn[2], f.s, acc, first_id);
-	VX_TRY(hipGetLastError());
+	KD_TRY(t.get(acc, 4 * (size_t)m));
+	KD_TRY(t.get(first_id, (size_t)m));
+	KD_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4 * (size_t)m, stream));
+	hipLaunchKernelGGL(vx_segsum_kernel, grd, blk, 0, stream, d_xyz, g.order, cell1, n, f.mn[0], f.mn[1], f.mn[2], f.s, acc, first_id);
+	KD_TRY(hipGetLastError());
 	hipLaunchKernelGGL(vx_finish_kernel, dim3((m + 255) / 256), blk, 0, stream, d_xyz, acc, first_id, m, f.mn[0], f.mn[1], f.mn[2], f.s, d_out, d_count);
-	VX_TRY(hipGetLastError());
-	if (ev_end) VX_TRY(hipEventRecord(ev_end, stream));
+	KD_TRY(hipGetLastError());
 	*m_out = m;
-#undef VX_TRY
-	return hipStreamSynchronize(stream);                       // the temporaries are in use until here
+	return end_and_drain(ev_end, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -490,16 +562,7 @@ hipError_t launch_voxel_downsample(const float* d_xyz, int n, const VoxelFrame& 
 // of the keep flags; ours are the key kernel (the voxel operator's), the gather into sorted 16-byte records, the count kernel and the
 // compaction.
 // ------------------------------------------------------------------------------------------------
-struct __align__(16) RorPt { float x, y, z; int id; };
 constexpr int kRorBlock = 256;                                 // the span of sorted points a workgroup owns, and the LDS tile (4 KB)
-
-__global__ void ror_gather_kernel(const float* __restrict__ xyz, const int* __restrict__ ids, int n, RorPt* __restrict__ pts)
-{
-	const int s = blockIdx.x * blockDim.x + threadIdx.x;
-	if (s >= n) return;
-	const int id = ids[s];
-	pts[s] = RorPt{xyz[3 * (size_t)id], xyz[3 * (size_t)id + 1], xyz[3 * (size_t)id + 2], id};
-}
 
 // the first sorted position whose key is >= k (upper = false) or > k (upper = true); a negative k is below every key
 __device__ __forceinline__ int ror_bound(const unsigned long long* __restrict__ keys, int n, long long k, bool upper)
@@ -514,23 +577,15 @@ __device__ __forceinline__ int ror_bound(const unsigned long long* __restrict__ 
 	return lo;
 }
 
-// A workgroup owns kRorBlock consecutive SORTED points, keys Ka..Kb.  The cells around a point with key K are the 9 runs
-// [K + D - 1, K + D + 1], D = dy 2^21 + dz 2^42, so all runs of the span lie in the 9 intervals [Ka + D - 1, Kb + D + 1].  Lanes 0..8 find
-// them by binary search, lane 0 makes them disjoint (D ascends, so both ends ascend: each interval starts no earlier than the one before
-// it ends).  A key of the intervals that is no neighbour cell -- a field that wrapped below zero, the cells between two rows -- is only a
-// candidate that fails the distance test or the cull.  The intervals pass through LDS in tiles of kRorBlock records; each lane tests its
-// own point against every record of a tile, skips its own id and stops counting at min_neighbors.  A wave skips a tile none of whose
-// unsaturated lanes has a run that meets the tile's key range, and the workgroup leaves once every lane is saturated: a dense cell costs a
-// lane min_neighbors hits, not the cell.  No workgroup waits on another.
-__global__ void __launch_bounds__(kRorBlock) ror_count_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, float r2,
-                                                              int min_neighbors, int32_t* __restrict__ count, int* __restrict__ flag)
+// What the tile kernels of every grid operator share.  A workgroup owns a span of consecutive SORTED points first..last, keys Ka..Kb.  The
+// cells around a point with key K are the 9 runs [K + D - 1, K + D + 1], D = dy 2^21 + dz 2^42, so all runs of the span lie in the 9
+// intervals [Ka + D - 1, Kb + D + 1].  Lanes 0..8 find them by binary search, lane 0 makes them disjoint (D ascends, so both ends ascend:
+// each interval starts no earlier than the one before it ends), so no candidate is offered twice.  A key of the intervals that is no
+// neighbour cell -- a field that wrapped below zero, the cells between two rows -- is only a candidate that fails the distance test or the
+// cull.  iv_lo / iv_hi: 9 words of LDS each; every lane of the workgroup calls, and the intervals are visible on return
+__device__ __forceinline__ void grid_intervals(const unsigned long long* __restrict__ keys, int n, int first, int last, int* iv_lo, int* iv_hi)
 {
-	__shared__ RorPt tile[kRorBlock];
-	__shared__ int iv_lo[9], iv_hi[9];
 	const int tid = threadIdx.x;
-	const int first = blockIdx.x * kRorBlock, last = min(first + kRorBlock, n) - 1;
-	const int s = first + tid;
-	const bool valid = s < n;
 	if (tid < 9) {
 		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
 		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
@@ -543,6 +598,33 @@ __global__ void __launch_bounds__(kRorBlock) ror_count_kernel(const RorPt* __res
 			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
 		}
 	__syncthreads();
+}
+
+// does one of the 9 runs of a point with key K meet a tile whose keys are ta..tb
+__device__ __forceinline__ bool grid_tile_meets(long long K, long long ta, long long tb)
+{
+	bool need = false;
+	for (int q = 0; q < 9; q++) {
+		const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
+		need = need || (c - 1 <= tb && c + 1 >= ta);
+	}
+	return need;
+}
+
+// A workgroup owns kRorBlock consecutive SORTED points and passes their candidate intervals (grid_intervals) through LDS in tiles of
+// kRorBlock records; each lane tests its own point against every record of a tile, skips its own id and stops counting at min_neighbors.
+// A wave skips a tile none of whose unsaturated lanes has a run that meets the tile's key range, and the workgroup leaves once every lane
+// is saturated: a dense cell costs a lane min_neighbors hits, not the cell.  No workgroup waits on another.
+__global__ void __launch_bounds__(kRorBlock) ror_count_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, float r2,
+                                                              int min_neighbors, int32_t* __restrict__ count, int* __restrict__ flag)
+{
+	__shared__ RorPt tile[kRorBlock];
+	__shared__ int iv_lo[9], iv_hi[9];
+	const int tid = threadIdx.x;
+	const int first = blockIdx.x * kRorBlock, last = min(first + kRorBlock, n) - 1;
+	const int s = first + tid;
+	const bool valid = s < n;
+	grid_intervals(keys, n, first, last, iv_lo, iv_hi);
 	RorPt P{0.f, 0.f, 0.f, -1};
 	long long K = 0;
 	if (valid) { P = pts[s]; K = (long long)keys[s]; }
@@ -554,13 +636,7 @@ __global__ void __launch_bounds__(kRorBlock) ror_count_kernel(const RorPt* __res
 			const int len = min(kRorBlock, hi - t0);
 			if (tid < len) tile[tid] = pts[t0 + tid];
 			__syncthreads();
-			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
-			bool need = false;
-			if (cnt < min_neighbors)
-				for (int q = 0; q < 9; q++) {
-					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
-					need = need || (c - 1 <= tb && c + 1 >= ta);
-				}
+			const bool need = cnt < min_neighbors && grid_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
 			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
 			for (int j = 0; j < len; j++) {
 				const RorPt Q = tile[j];
@@ -588,57 +664,66 @@ __global__ void ror_compact_kernel(const float* __restrict__ xyz, const int* __r
 	if (index) index[d] = i;
 }
 
+// the same with the label column of the clustering
+__global__ void cl_compact_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ label, const int* __restrict__ flag, const int* __restrict__ scan,
+                                  int n, float* __restrict__ out, int32_t* __restrict__ index, int32_t* __restrict__ out_label)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || !flag[i]) return;
+	const size_t d = (size_t)scan[i];
+	out[3 * d] = xyz[3 * (size_t)i]; out[3 * d + 1] = xyz[3 * (size_t)i + 1]; out[3 * d + 2] = xyz[3 * (size_t)i + 2];
+	if (index) index[d] = i;
+	if (out_label) out_label[d] = label[i];
+}
+
+// bytes = the temporary storage of compact_tail's scan
+static hipError_t compact_scan_bytes(int* flag, int* scan, size_t N, size_t& bytes, hipStream_t stream)
+{
+	return rocprim::exclusive_scan(nullptr, bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream);
+}
+
+// The tail of every filter.  flag: n + 1 ints whose first n a kernel on the stream has set (1 = keep, input order); scan: n + 1 ints; tmp
+// holds scan_bytes.  Scans the flags, writes the kept points (with their labels when d_label is given) and enqueues the 4-byte read-back
+// of scan[n] into *m, which holds the number kept, in 0..n, once the stream has drained (end_and_drain)
+static hipError_t compact_tail(const float* d_xyz, int n, int* flag, int* scan, void* tmp, size_t scan_bytes, const int32_t* d_label, float* d_out,
+                               int32_t* d_index, int32_t* d_out_label, int* m, hipStream_t stream)
+{
+	const dim3 blk(256), grd((n + 255) / 256);
+	const size_t N = (size_t)n;
+	KD_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
+	KD_TRY(rocprim::exclusive_scan(tmp, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	if (d_label) hipLaunchKernelGGL(cl_compact_kernel, grd, blk, 0, stream, d_xyz, d_label, flag, scan, n, d_out, d_index, d_out_label);
+	else hipLaunchKernelGGL(ror_compact_kernel, grd, blk, 0, stream, d_xyz, flag, scan, n, d_out, d_index);
+	KD_TRY(hipGetLastError());
+	return hipMemcpyAsync(m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream);
+}
+
 hipError_t launch_radius_outlier_removal(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, float* d_out, int32_t* d_index,
                                          int32_t* d_count, int* m_out, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
 	if (n <= 0 || !m_out || min_neighbors < 1) return hipErrorInvalidValue;
-	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define ROR_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-	unsigned long long *keys = nullptr, *keys2 = nullptr;
-	int *ids = nullptr, *ids2 = nullptr, *flag = nullptr, *scan = nullptr, *cnt = nullptr;
-	RorPt* pts = nullptr;
+	int *flag = nullptr, *scan = nullptr, *cnt = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		unsigned long long*& a; unsigned long long*& b; int*& c; int*& d; int*& f; int*& g; int*& h; RorPt*& p; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(p); hipFree(t); }
-	} cleanup{keys, keys2, ids, ids2, flag, scan, cnt, pts, tmp};
+	Temps t;
+	CellGrid g;
 	const size_t N = (size_t)n;
-	ROR_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
-	ROR_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
-	ROR_TRY(hipMalloc(&ids, sizeof(int) * N));
-	ROR_TRY(hipMalloc(&ids2, sizeof(int) * N));
-	ROR_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
-	ROR_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
-	ROR_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
-	if (!d_count) ROR_TRY(hipMalloc(&cnt, sizeof(int) * N));
-	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+	KD_TRY(g.alloc(t, N, true));
+	KD_TRY(t.get(flag, N + 1));
+	KD_TRY(t.get(scan, N + 1));
+	if (!d_count) KD_TRY(t.get(cnt, N));
 	size_t sort_bytes = 0, scan_bytes = 0;
-	ROR_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	ROR_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	ROR_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	KD_TRY(grid_sort_bytes(g, N, &f, 1, sort_bytes, stream));
+	KD_TRY(compact_scan_bytes(flag, scan, N, scan_bytes, stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
 	// ev_begin .. ev_end: the kernels and the 4-byte read-back of m; the allocations above and the frees at the end are outside
-	if (ev_begin) ROR_TRY(hipEventRecord(ev_begin, stream));
-	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
-	ROR_TRY(hipGetLastError());
-	size_t bytes = sort_bytes;
-	ROR_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-	ROR_TRY(hipGetLastError());
-	ROR_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
-	hipLaunchKernelGGL(ror_count_kernel, dim3((n + kRorBlock - 1) / kRorBlock), dim3(kRorBlock), 0, stream, pts, keys2, n, r2, min_neighbors,
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(grid_build(d_xyz, n, f, g, tmp, sort_bytes, stream));
+	hipLaunchKernelGGL(ror_count_kernel, dim3((n + kRorBlock - 1) / kRorBlock), dim3(kRorBlock), 0, stream, g.pts, g.sorted_keys, n, r2, min_neighbors,
 	                   d_count ? d_count : cnt, flag);
-	ROR_TRY(hipGetLastError());
-	bytes = scan_bytes;
-	ROR_TRY(rocprim::exclusive_scan(tmp, bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	hipLaunchKernelGGL(ror_compact_kernel, grd, blk, 0, stream, d_xyz, flag, scan, n, d_out, d_index);
-	ROR_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	int m = -1;
-	ROR_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
-	if (ev_end) ROR_TRY(hipEventRecord(ev_end, stream));
-	ROR_TRY(hipStreamSynchronize(stream));                     // the temporaries are in use until here
-#undef ROR_TRY
+	KD_TRY(compact_tail(d_xyz, n, flag, scan, tmp, scan_bytes, nullptr, d_out, d_index, nullptr, &m, stream));
+	KD_TRY(end_and_drain(ev_end, stream));
 	if (m < 0 || m > n) return hipErrorUnknown;
 	*m_out = m;
 	return hipSuccess;
@@ -696,34 +781,6 @@ __device__ __forceinline__ void cl_unite(int* parent, int a, int b)
 	}
 }
 
-// what the component and the border kernel share with ror_count_kernel: the 9 disjoint candidate intervals of the workgroup's span
-__device__ __forceinline__ void cl_intervals(const unsigned long long* __restrict__ keys, int n, int first, int last, int* iv_lo, int* iv_hi)
-{
-	const int tid = threadIdx.x;
-	if (tid < 9) {
-		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
-		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
-		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
-	}
-	__syncthreads();
-	if (tid == 0)
-		for (int o = 1; o < 9; o++) {
-			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
-			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
-		}
-	__syncthreads();
-}
-
-__device__ __forceinline__ bool cl_tile_meets(long long K, long long ta, long long tb)
-{
-	bool need = false;
-	for (int q = 0; q < 9; q++) {
-		const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
-		need = need || (c - 1 <= tb && c + 1 >= ta);
-	}
-	return need;
-}
-
 // The count kernel's shape: a workgroup owns kClBlock consecutive SORTED points and passes their candidate intervals through LDS in
 // tiles, each record with its core flag.  A core lane unites its point with every core candidate within r that has a smaller index (each
 // pair once).  The tile loops run over the intervals' lengths; the loops inside cl_unite are bounded as written there.  No workgroup waits
@@ -742,7 +799,7 @@ __global__ void __launch_bounds__(kClBlock) cl_union_kernel(const RorPt* __restr
 	bool mine = false;
 	if (s < n) { P = pts[s]; K = (long long)keys[s]; mine = core[P.id] != 0; }
 	if (!__syncthreads_or(mine)) return;                         // no core point in the span
-	cl_intervals(keys, n, first, last, iv_lo, iv_hi);
+	grid_intervals(keys, n, first, last, iv_lo, iv_hi);
 	for (int o = 0; o < 9; o++) {
 		const int lo = iv_lo[o], hi = iv_hi[o];
 		for (int t0 = lo; t0 < hi; t0 += kClBlock) {
@@ -754,7 +811,7 @@ __global__ void __launch_bounds__(kClBlock) cl_union_kernel(const RorPt* __restr
 				tile_core[tid] = core[Q.id];
 			}
 			__syncthreads();
-			const bool need = mine && cl_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
+			const bool need = mine && grid_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
 			if (!need) continue;                                 // the next barrier is at the loop's head, which every lane reaches
 			for (int j = 0; j < len; j++) {
 				const RorPt Q = tile[j];
@@ -797,7 +854,7 @@ __global__ void __launch_bounds__(kClBlock) cl_border_kernel(const RorPt* __rest
 	bool mine = false;
 	if (s < n) { P = pts[s]; K = (long long)keys[s]; mine = core[P.id] == 0; }
 	if (!__syncthreads_or(mine)) return;                         // every point of the span is core
-	cl_intervals(keys, n, first, last, iv_lo, iv_hi);
+	grid_intervals(keys, n, first, last, iv_lo, iv_hi);
 	unsigned long long best = ~0ull;
 	for (int o = 0; o < 9; o++) {
 		const int lo = iv_lo[o], hi = iv_hi[o];
@@ -810,7 +867,7 @@ __global__ void __launch_bounds__(kClBlock) cl_border_kernel(const RorPt* __rest
 				tile_core[tid] = core[Q.id];
 			}
 			__syncthreads();
-			const bool need = mine && cl_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
+			const bool need = mine && grid_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
 			if (!need) continue;                                 // the next barrier is at the loop's head, which every lane reaches
 			for (int j = 0; j < len; j++) {
 				const RorPt Q = tile[j];
@@ -850,85 +907,54 @@ __global__ void cl_keepflag_kernel(const int32_t* __restrict__ label, const int3
 	flag[i] = (l >= 0 && keep[l]) ? 1 : 0;
 }
 
-__global__ void cl_compact_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ label, const int* __restrict__ flag, const int* __restrict__ scan,
-                                  int n, float* __restrict__ out, int32_t* __restrict__ index, int32_t* __restrict__ out_label)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n || !flag[i]) return;
-	const size_t d = (size_t)scan[i];
-	out[3 * d] = xyz[3 * (size_t)i]; out[3 * d + 1] = xyz[3 * (size_t)i + 1]; out[3 * d + 2] = xyz[3 * (size_t)i + 2];
-	if (index) index[d] = i;
-	if (out_label) out_label[d] = label[i];
-}
-
 hipError_t launch_cluster(const float* d_xyz, int n, const VoxelFrame& f, float r2, int min_neighbors, int32_t* d_label, int32_t* d_sizes, int* c_out,
                           hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
 	if (n <= 0 || !c_out || !d_label || !d_sizes || min_neighbors < 0) return hipErrorInvalidValue;
 	const dim3 blk(256), grd((n + 255) / 256), tgrd((n + kClBlock - 1) / kClBlock), tblk(kClBlock);
-	hipError_t e;
-#define CL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-	unsigned long long *keys = nullptr, *keys2 = nullptr;
-	int *ids = nullptr, *ids2 = nullptr, *core = nullptr, *parent = nullptr, *root = nullptr, *isroot = nullptr, *scan = nullptr;
-	RorPt* pts = nullptr;
+	int *core = nullptr, *parent = nullptr, *root = nullptr, *isroot = nullptr, *scan = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		unsigned long long*& a; unsigned long long*& b; int*& c; int*& d; int*& f; int*& g; int*& h; int*& i; int*& j; RorPt*& p; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(f); hipFree(g); hipFree(h); hipFree(i); hipFree(j); hipFree(p); hipFree(t); }
-	} cleanup{keys, keys2, ids, ids2, core, parent, root, isroot, scan, pts, tmp};
+	Temps t;
+	CellGrid g;
 	const size_t N = (size_t)n;
-	CL_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
-	CL_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
-	CL_TRY(hipMalloc(&ids, sizeof(int) * N));
-	CL_TRY(hipMalloc(&ids2, sizeof(int) * N));
-	CL_TRY(hipMalloc(&core, sizeof(int) * N));
-	CL_TRY(hipMalloc(&parent, sizeof(int) * N));
-	CL_TRY(hipMalloc(&root, sizeof(int) * N));
-	CL_TRY(hipMalloc(&isroot, sizeof(int) * (N + 1)));
-	CL_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
-	CL_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
-	const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
+	KD_TRY(g.alloc(t, N, true));
+	KD_TRY(t.get(core, N));
+	KD_TRY(t.get(parent, N));
+	KD_TRY(t.get(root, N));
+	KD_TRY(t.get(isroot, N + 1));
+	KD_TRY(t.get(scan, N + 1));
 	size_t sort_bytes = 0, scan_bytes = 0;
-	CL_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	CL_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	CL_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	KD_TRY(grid_sort_bytes(g, N, &f, 1, sort_bytes, stream));
+	KD_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
 	// ev_begin .. ev_end: the kernels and the 4-byte read-back of c; the allocations above and the frees at the end are outside
-	if (ev_begin) CL_TRY(hipEventRecord(ev_begin, stream));
-	hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
-	CL_TRY(hipGetLastError());
-	size_t bytes = sort_bytes;
-	CL_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-	hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-	CL_TRY(hipGetLastError());
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(grid_build(d_xyz, n, f, g, tmp, sort_bytes, stream));
 	hipLaunchKernelGGL(cl_init_kernel, grd, blk, 0, stream, parent, core, n, min_neighbors == 0 ? 1 : 0);
-	CL_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	if (min_neighbors > 0) {
 		// the radius filter's saturating count: core[i] = (count_i == min_neighbors); the counts themselves go to root, which is rewritten below
-		hipLaunchKernelGGL(ror_count_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, min_neighbors, root, core);
-		CL_TRY(hipGetLastError());
+		hipLaunchKernelGGL(ror_count_kernel, tgrd, tblk, 0, stream, g.pts, g.sorted_keys, n, r2, min_neighbors, root, core);
+		KD_TRY(hipGetLastError());
 	}
-	hipLaunchKernelGGL(cl_union_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, core, parent);
-	CL_TRY(hipGetLastError());
+	hipLaunchKernelGGL(cl_union_kernel, tgrd, tblk, 0, stream, g.pts, g.sorted_keys, n, r2, core, parent);
+	KD_TRY(hipGetLastError());
 	hipLaunchKernelGGL(cl_flatten_kernel, grd, blk, 0, stream, parent, core, n, root);
-	CL_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	if (min_neighbors > 0) {
-		hipLaunchKernelGGL(cl_border_kernel, tgrd, tblk, 0, stream, pts, keys2, n, r2, core, root);
-		CL_TRY(hipGetLastError());
+		hipLaunchKernelGGL(cl_border_kernel, tgrd, tblk, 0, stream, g.pts, g.sorted_keys, n, r2, core, root);
+		KD_TRY(hipGetLastError());
 	}
 	hipLaunchKernelGGL(cl_rootflag_kernel, grd, blk, 0, stream, root, n, isroot);
-	CL_TRY(hipGetLastError());
-	CL_TRY(hipMemsetAsync(isroot + N, 0, sizeof(int), stream));
-	bytes = scan_bytes;
-	CL_TRY(rocprim::exclusive_scan(tmp, bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	CL_TRY(hipMemsetAsync(d_sizes, 0, sizeof(int32_t) * N, stream));
+	KD_TRY(hipGetLastError());
+	KD_TRY(hipMemsetAsync(isroot + N, 0, sizeof(int), stream));
+	KD_TRY(rocprim::exclusive_scan(tmp, scan_bytes, isroot, scan, 0, N + 1, rocprim::plus<int>(), stream));
+	KD_TRY(hipMemsetAsync(d_sizes, 0, sizeof(int32_t) * N, stream));
 	hipLaunchKernelGGL(cl_label_kernel, grd, blk, 0, stream, root, scan, n, d_label, d_sizes);
-	CL_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	int c = -1;
-	CL_TRY(hipMemcpyAsync(&c, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
-	if (ev_end) CL_TRY(hipEventRecord(ev_end, stream));
-	CL_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
-#undef CL_TRY
+	KD_TRY(hipMemcpyAsync(&c, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
+	KD_TRY(end_and_drain(ev_end, stream));
 	if (c < 0 || c > n) return hipErrorUnknown;
 	*c_out = c;
 	return hipSuccess;
@@ -938,34 +964,21 @@ hipError_t launch_cluster_compact(const float* d_xyz, int n, const int32_t* d_la
                                   int32_t* d_out_label, int* m_out, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
 	if (n <= 0 || !m_out || !d_label || !d_keep || !d_out) return hipErrorInvalidValue;
-	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define CL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
 	int *flag = nullptr, *scan = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		int*& a; int*& b; void*& t;
-		~Cleanup() { hipFree(a); hipFree(b); hipFree(t); }
-	} cleanup{flag, scan, tmp};
+	Temps t;
 	const size_t N = (size_t)n;
-	CL_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
-	CL_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
+	KD_TRY(t.get(flag, N + 1));
+	KD_TRY(t.get(scan, N + 1));
 	size_t scan_bytes = 0;
-	CL_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	CL_TRY(hipMalloc(&tmp, std::max<size_t>(scan_bytes, 16)));
-	if (ev_begin) CL_TRY(hipEventRecord(ev_begin, stream));
-	hipLaunchKernelGGL(cl_keepflag_kernel, grd, blk, 0, stream, d_label, d_keep, n, flag);
-	CL_TRY(hipGetLastError());
-	CL_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
-	CL_TRY(rocprim::exclusive_scan(tmp, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	hipLaunchKernelGGL(cl_compact_kernel, grd, blk, 0, stream, d_xyz, d_label, flag, scan, n, d_out, d_index, d_out_label);
-	CL_TRY(hipGetLastError());
+	KD_TRY(compact_scan_bytes(flag, scan, N, scan_bytes, stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(scan_bytes, 16)));
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	hipLaunchKernelGGL(cl_keepflag_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_label, d_keep, n, flag);
+	KD_TRY(hipGetLastError());
 	int m = -1;
-	CL_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
-	if (ev_end) CL_TRY(hipEventRecord(ev_end, stream));
-	CL_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
-#undef CL_TRY
+	KD_TRY(compact_tail(d_xyz, n, flag, scan, tmp, scan_bytes, d_label, d_out, d_index, d_out_label, &m, stream));
+	KD_TRY(end_and_drain(ev_end, stream));
 	if (m < 0 || m > n) return hipErrorUnknown;
 	*m_out = m;
 	return hipSuccess;
@@ -976,7 +989,7 @@ hipError_t launch_cluster_compact(const float* d_xyz, int n, const int32_t* d_la
 // point are found on grids of doubling radius r_L = r0 2^L (pitch 1.03125 r_L, the radius filter's grid and its proof): a point whose k-th
 // smallest d2 over its 27 cells is <= r_L * r_L has seen every point that close, so those k are its k smallest of the whole
 // cloud; the others go to a compacted list for the next level, and what the last level leaves scans all points.  Level 0 serves every point
-// (stat_knn_block_kernel, the count kernel's shape), the later levels few scattered ones (stat_knn_wave_kernel, a wave per point).  The
+// (grid_knn_block_kernel, the count kernel's shape), the later levels few scattered ones (grid_knn_wave_kernel, a wave per point).  The
 // number of levels is fixed by the host; the length of the list comes back between levels (4 bytes) so that an empty one ends the chain.
 // The statistics stay on the device: the maximum over float bits, exact 64-bit integer sums, one thread that finishes in fp64.
 // ------------------------------------------------------------------------------------------------
@@ -992,40 +1005,65 @@ __device__ __forceinline__ float stat_d2(float px, float py, float pz, const Ror
 // on the same).  __fsqrt_rn is the hardware's approximate instruction in this toolchain and differs from the host in the last bit
 __device__ __forceinline__ float stat_sqrt(float v) { return sqrtf(v); }
 
-// The count kernel's shape: a workgroup owns kStatBlock consecutive SORTED points, finds the 9 candidate intervals of its span once, makes
-// them disjoint (no candidate is offered twice) and passes them through LDS in tiles; a wave skips a tile that meets none of its lanes'
-// runs, and a lane takes only tiles that meet its own.  Each lane keeps its k smallest d2 ascending in LDS at stride kStatBlock (lane t owns
-// column t: no two lanes of a wave share a bank column), KT >= k rows of 1 KB.  A candidate is inserted only when strictly below the lane's
-// k-th value, so ties and a cell of identical points cost nothing.  A lane whose k-th value is <= r2 writes u; any other appends its id to
-// the open list.  No workgroup waits on another
-template <int KT>
-__global__ void __launch_bounds__(kStatBlock) stat_knn_block_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, int k,
-                                                                    float r2, float* __restrict__ u, int* __restrict__ open_list, int* __restrict__ open_count)
+// The search kernels serve this filter and the self k-NN (below), which differ in the entry of the k-best lists and in what a resolved
+// point writes.  An entry policy E: the type T, none() (above every candidate), make(d2, id), d2(e) -- of none() a value that is <= no
+// radius, so a list with fewer than k entries is never resolved -- and the wave's shuffles.  A sink names its entry policy; lane() is
+// called by a resolved lane of the block kernel with its column of the lists (entry j at col[j * kStatBlock]), wave() by every lane of a
+// resolved wave (lane j holds entry j)
+struct KnnDist {                                               // d2 alone; none = INFINITY
+	using T = float;
+	static __device__ __forceinline__ T none() { return INFINITY; }
+	static __device__ __forceinline__ T make(float d2, int) { return d2; }
+	static __device__ __forceinline__ float d2(T e) { return e; }
+	static __device__ __forceinline__ T shfl(T e, int src) { return __shfl(e, src, 64); }
+	static __device__ __forceinline__ T shfl_up(T e) { return __shfl_up(e, 1, 64); }
+};
+
+// u = the mean of the k distances, summed ascending in fp64
+struct MeanSink {
+	using Entry = KnnDist;
+	float* __restrict__ u;
+	__device__ __forceinline__ void lane(int id, int k, const float* col) const
+	{
+		double sum = 0.0;
+		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(col[j * kStatBlock]));
+		u[id] = (float)__ddiv_rn(sum, (double)k);
+	}
+	__device__ __forceinline__ void wave(int id, int k, int lane, float mine) const
+	{
+		double sum = 0.0;
+		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(__shfl(mine, j, 64)));
+		if (lane == 0) u[id] = (float)__ddiv_rn(sum, (double)k);
+	}
+};
+
+// The count kernel's shape: a workgroup owns kStatBlock consecutive SORTED points and passes the candidate intervals of its span
+// (grid_intervals) through LDS in tiles; a wave skips a tile that meets none of its lanes' runs, and a lane takes only tiles that meet its
+// own.  Each lane keeps its k smallest entries ascending in LDS at stride kStatBlock (lane t owns column t: no two lanes of a wave share a
+// bank column; of 8-byte entries the 32 lanes of a half wave read 64 consecutive dwords, one bank each), KT >= k rows of 1 or 2 KB.  A
+// candidate is inserted only when strictly below the lane's k-th entry, held in registers, so ties of d2 and a cell of identical points
+// cost nothing; keys are unique, so there a cell of identical points costs one comparison per candidate once the column holds the k
+// smallest indices.  A lane whose k-th d2 is <= r2 hands its column to the sink; any other appends its id to the open list.  No workgroup
+// waits on another
+template <int KT, class Sink>
+__global__ void __launch_bounds__(kStatBlock) grid_knn_block_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, int k,
+                                                                    float r2, Sink sink, int* __restrict__ open_list, int* __restrict__ open_count)
 {
+	using E = typename Sink::Entry;
+	using T = typename E::T;
 	__shared__ RorPt tile[kStatBlock];
-	__shared__ float best[KT * kStatBlock];
+	__shared__ T best[KT * kStatBlock];
 	__shared__ int iv_lo[9], iv_hi[9];
 	const int tid = threadIdx.x;
 	const int first = blockIdx.x * kStatBlock, last = min(first + kStatBlock, n) - 1;
 	const int s = first + tid;
 	const bool valid = s < n;
-	if (tid < 9) {
-		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
-		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
-		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
-	}
-	for (int j = 0; j < k; j++) best[j * kStatBlock + tid] = INFINITY;
-	__syncthreads();
-	if (tid == 0)
-		for (int o = 1; o < 9; o++) {
-			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
-			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
-		}
-	__syncthreads();
+	for (int j = 0; j < k; j++) best[j * kStatBlock + tid] = E::none();
+	grid_intervals(keys, n, first, last, iv_lo, iv_hi);
 	RorPt P{0.f, 0.f, 0.f, -1};
 	long long K = 0;
 	if (valid) { P = pts[s]; K = (long long)keys[s]; }
-	float kth = INFINITY;
+	T kth = E::none();
 	for (int o = 0; o < 9; o++) {
 		const int lo = iv_lo[o], hi = iv_hi[o];
 		for (int t0 = lo; t0 < hi; t0 += kStatBlock) {
@@ -1033,52 +1071,44 @@ __global__ void __launch_bounds__(kStatBlock) stat_knn_block_kernel(const RorPt*
 			const int len = min(kStatBlock, hi - t0);
 			if (tid < len) tile[tid] = pts[t0 + tid];
 			__syncthreads();
-			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
-			bool need = false;
-			if (valid)
-				for (int q = 0; q < 9; q++) {
-					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
-					need = need || (c - 1 <= tb && c + 1 >= ta);
-				}
+			const bool need = valid && grid_tile_meets(K, (long long)keys[t0], (long long)keys[t0 + len - 1]);
 			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
 			if (!need) continue;
 			for (int j = 0; j < len; j++) {
 				const RorPt Q = tile[j];
-				const float d2 = stat_d2(P.x, P.y, P.z, Q);
-				if (d2 < kth && Q.id != P.id) {
+				const T c = E::make(stat_d2(P.x, P.y, P.z, Q), Q.id);
+				if (c < kth && Q.id != P.id) {
 					int p = k - 1;
 					while (p > 0) {
-						const float b = best[(p - 1) * kStatBlock + tid];
-						if (!(b > d2)) break;
+						const T b = best[(p - 1) * kStatBlock + tid];
+						if (!(b > c)) break;
 						best[p * kStatBlock + tid] = b;
 						p--;
 					}
-					best[p * kStatBlock + tid] = d2;
+					best[p * kStatBlock + tid] = c;
 					kth = best[(k - 1) * kStatBlock + tid];
 				}
 			}
 		}
 	}
 	if (!valid) return;
-	if (kth <= r2) {
-		double sum = 0.0;
-		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(best[j * kStatBlock + tid]));
-		u[P.id] = (float)__ddiv_rn(sum, (double)k);
-	} else {
-		open_list[atomicAdd(open_count, 1)] = P.id;
-	}
+	if (E::d2(kth) <= r2) sink.lane(P.id, k, best + tid);
+	else open_list[atomicAdd(open_count, 1)] = P.id;
 }
 
 // A wave per listed point.  Lanes 0..8 find the point's own 9 runs [K + D - 1, K + D + 1] (disjoint key ranges: no candidate is offered
-// twice); all = 1 is the top level, the one run [0, n).  The lanes read 64 candidates at a time; lane j holds the j-th smallest d2 seen so
-// far in a register, and a candidate strictly below the k-th value is inserted by one shuffle: a lane keeps its value if it is <= v, takes
-// v if its lower neighbour's value is <= v, and its lower neighbour's value otherwise.  The loops run over the runs' lengths, which the
+// twice); all = 1 is the top level, the one run [0, n).  The lanes read 64 candidates at a time; lane j holds the j-th smallest entry seen
+// so far in registers, and a candidate v strictly below the k-th entry is inserted by one shuffle up: a lane keeps its entry if it is
+// <= v, takes v if its lower neighbour's entry is <= v, and its lower neighbour's entry otherwise.  (Keys are unique, every candidate is
+// offered once and v is never none(), so of keys no entry equals v and <= reads as <.)  The loops run over the runs' lengths, which the
 // host's number of levels bounds; no wave waits on another
-__global__ void __launch_bounds__(256) stat_knn_wave_kernel(const float* __restrict__ xyz, const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys,
+template <class Sink>
+__global__ void __launch_bounds__(256) grid_knn_wave_kernel(const float* __restrict__ xyz, const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys,
                                                             int n, const int* __restrict__ list, int count, int k, float r2, int all, float mnx, float mny,
-                                                            float mnz, float pitch, float* __restrict__ u, int* __restrict__ open_list,
-                                                            int* __restrict__ open_count)
+                                                            float mnz, float pitch, Sink sink, int* __restrict__ open_list, int* __restrict__ open_count)
 {
+	using E = typename Sink::Entry;
+	using T = typename E::T;
 	const int w = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
 	if (w >= count) return;                                      // wave-uniform
 	const int id = list[w];
@@ -1092,48 +1122,36 @@ __global__ void __launch_bounds__(256) stat_knn_wave_kernel(const float* __restr
 		my_lo = ror_bound(keys, n, c - 1, false);
 		my_hi = max(my_lo, ror_bound(keys, n, c + 1, true));
 	}
-	float mine = INFINITY, kth = INFINITY;
+	T mine = E::none(), kth = E::none();
 	const int runs = all ? 1 : 9;
 	for (int o = 0; o < runs; o++) {
 		const int lo = __shfl(my_lo, o, 64), hi = __shfl(my_hi, o, 64);
 		for (int base = lo; base < hi; base += 64) {
 			const int j = base + lane;
-			float d2 = INFINITY;
+			T c = E::none();
 			if (j < hi) {
 				const RorPt Q = pts[j];
-				if (Q.id != id) d2 = stat_d2(px, py, pz, Q);
+				if (Q.id != id) c = E::make(stat_d2(px, py, pz, Q), Q.id);
 			}
-			unsigned long long hot = __ballot(d2 < kth);
+			unsigned long long hot = __ballot(c < kth);
 			while (hot) {
 				const int src = __ffsll((long long)hot) - 1;
 				hot &= hot - 1;
-				const float v = __shfl(d2, src, 64);
+				const T v = E::shfl(c, src);
 				if (v < kth) {                                       // wave-uniform
-					const float below = __shfl_up(mine, 1, 64);
+					const T below = E::shfl_up(mine);
 					mine = (mine <= v) ? mine : ((lane == 0 || below <= v) ? v : below);
-					kth = __shfl(mine, k - 1, 64);
+					kth = E::shfl(mine, k - 1);
 				}
 			}
 		}
 	}
-	if (all || kth <= r2) {
-		double sum = 0.0;
-		for (int j = 0; j < k; j++) sum = __dadd_rn(sum, (double)stat_sqrt(__shfl(mine, j, 64)));
-		if (lane == 0) u[id] = (float)__ddiv_rn(sum, (double)k);
-	} else if (lane == 0) {
-		open_list[atomicAdd(open_count, 1)] = id;
-	}
+	if (all || E::d2(kth) <= r2) sink.wave(id, k, lane, mine);
+	else if (lane == 0) open_list[atomicAdd(open_count, 1)] = id;
 }
 
 // what the finishing thread leaves for the flags and the host
 struct StatFinish { double Tq, threshold; int e, all; };
-
-__device__ __forceinline__ unsigned long long stat_xor64(unsigned long long v, int off)
-{
-	const int lo = __shfl_xor((int)(unsigned)(v & 0xffffffffull), off, 64);
-	const int hi = __shfl_xor((int)(unsigned)(v >> 32), off, 64);
-	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
-}
 
 // U over the bits of u: non-negative floats order as unsigned integers
 __global__ void __launch_bounds__(256) stat_max_kernel(const float* __restrict__ u, int n, unsigned* __restrict__ umax)
@@ -1156,7 +1174,7 @@ __global__ void __launch_bounds__(256) stat_sums_kernel(const float* __restrict_
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	const unsigned long long q = i < n ? stat_q(u[i], e) : 0ull;
 	unsigned long long s1 = q, a = (q * q) >> 32, b = (q * q) & 0xffffffffull;
-	for (int off = 32; off; off >>= 1) { s1 += stat_xor64(s1, off); a += stat_xor64(a, off); b += stat_xor64(b, off); }
+	for (int off = 32; off; off >>= 1) { s1 += shfl_xor64(s1, off); a += shfl_xor64(a, off); b += shfl_xor64(b, off); }
 	if ((threadIdx.x & 63) == 0) { atomicAdd(sums, s1); atomicAdd(sums + 1, a); atomicAdd(sums + 2, b); }
 }
 
@@ -1188,79 +1206,42 @@ __global__ void stat_flag_kernel(const float* __restrict__ u, int n, const StatF
 	flag[i] = (fin->all || (double)(long long)stat_q(u[i], fin->e) <= fin->Tq) ? 1 : 0;
 }
 
-hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, float std_ratio,
-                                       float* d_out, int32_t* d_index, float* d_mean, double* threshold, int* m_out, StatReport* report, hipStream_t stream,
-                                       hipEvent_t ev_begin, hipEvent_t ev_end)
+// The levels of a search, for both of its users.  Level 0 serves every point -- block(r2, open_list, open_count) launches the caller's
+// block kernel -- and every later level the listed ones: wave(list, count, r2, all, frame, open_list, open_count) launches its wave
+// kernel.  After each level the length of the open list comes back (4 bytes), so that an empty one ends the chain, and the lists swap;
+// what the last level leaves goes to the top level, where every point is a candidate, in any order (all = 1: the frame is not read).
+// g.order and g.pts start as level 0's or, with no level, as the input order, which the top level's records and list then need; that
+// first order is what d_order (may be null) receives.  n >= 2 points are open before level 0, so a search with levels runs level 0.
+// cur / nxt: n ints each; counts: kStatMaxLevels + 1 zeroed ints, one per level and the top level's
+template <class Block, class Wave>
+static hipError_t grid_knn_levels(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, const CellGrid& g, void* tmp,
+                                  size_t sort_bytes, int* cur, int* nxt, int* counts, int* d_order, StatReport& rep, hipStream_t stream, Block block,
+                                  Wave wave)
 {
-	if (n < 2 || !m_out || k < 1 || k > 64 || k > n - 1 || levels < 0 || levels > kStatMaxLevels || (levels > 0 && (!frames || !r2))) return hipErrorInvalidValue;
 	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define ST_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-	unsigned long long *keys = nullptr, *keys2 = nullptr, *sums = nullptr;
-	int *ids = nullptr, *ids2 = nullptr, *flag = nullptr, *scan = nullptr, *listA = nullptr, *listB = nullptr, *counts = nullptr;
-	float* mean = nullptr;
-	RorPt* pts = nullptr;
-	StatFinish* fin = nullptr;
-	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		void* const* p[14];
-		~Cleanup() { for (void* const* q : p) hipFree(*q); }
-	} cleanup{{(void**)&keys, (void**)&keys2, (void**)&sums, (void**)&ids, (void**)&ids2, (void**)&flag, (void**)&scan, (void**)&listA, (void**)&listB,
-	           (void**)&counts, (void**)&mean, (void**)&pts, (void**)&fin, &tmp}};
-	const size_t N = (size_t)n;
-	ST_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
-	ST_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
-	ST_TRY(hipMalloc(&sums, sizeof(unsigned long long) * 4));        // S1, A, B and the bits of U
-	ST_TRY(hipMalloc(&ids, sizeof(int) * N));
-	ST_TRY(hipMalloc(&ids2, sizeof(int) * N));
-	ST_TRY(hipMalloc(&flag, sizeof(int) * (N + 1)));
-	ST_TRY(hipMalloc(&scan, sizeof(int) * (N + 1)));
-	ST_TRY(hipMalloc(&listA, sizeof(int) * N));
-	ST_TRY(hipMalloc(&listB, sizeof(int) * N));
-	ST_TRY(hipMalloc(&counts, sizeof(int) * (kStatMaxLevels + 1)));
-	ST_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
-	ST_TRY(hipMalloc(&fin, sizeof(StatFinish)));
-	if (!d_mean) ST_TRY(hipMalloc(&mean, sizeof(float) * N));
-	float* u = d_mean ? d_mean : mean;
-	unsigned* umax = (unsigned*)(sums + 3);
-	size_t sort_bytes = 0, scan_bytes = 0;
-	for (int L = 0; L < levels; L++) {
-		size_t bytes = 0;
-		ST_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys2, ids, ids2, N, 0, (unsigned)std::min(std::max(frames[L].key_bits, 1), 63), stream));
-		sort_bytes = std::max(sort_bytes, bytes);
+	if (levels > 0) {
+		KD_TRY(grid_build(d_xyz, n, frames[0], g, tmp, sort_bytes, stream));
+	} else {
+		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, g.order, n);
+		KD_TRY(hipGetLastError());
+		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, cur, n);
+		KD_TRY(hipGetLastError());
+		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, g.order, n, g.pts);
+		KD_TRY(hipGetLastError());
 	}
-	ST_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	ST_TRY(hipMalloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
-	StatReport rep;
-	// ev_begin .. ev_end: the kernels and the read-backs; the allocations above and the frees at the end are outside
-	if (ev_begin) ST_TRY(hipEventRecord(ev_begin, stream));
-	ST_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
-	ST_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 4, stream));
+	if (d_order) KD_TRY(hipMemcpyAsync(d_order, g.order, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, stream));
 	int open = n;                                              // the points no level has resolved yet
-	int *cur = listA, *nxt = listB;
 	for (int L = 0; L < levels && open > 0; L++) {
-		const VoxelFrame& f = frames[L];
-		const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
-		hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
-		ST_TRY(hipGetLastError());
-		size_t bytes = sort_bytes;
-		ST_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-		ST_TRY(hipGetLastError());
 		if (L == 0) {
-			const dim3 g0((n + kStatBlock - 1) / kStatBlock), b0(kStatBlock);
-			if (k <= 16) hipLaunchKernelGGL(stat_knn_block_kernel<16>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
-			else if (k <= 32) hipLaunchKernelGGL(stat_knn_block_kernel<32>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
-			else hipLaunchKernelGGL(stat_knn_block_kernel<64>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], u, nxt, counts);
+			block(r2[0], nxt, counts);
 		} else {
-			hipLaunchKernelGGL(stat_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, r2[L], 0,
-			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, u, nxt, counts + L);
+			KD_TRY(grid_build(d_xyz, n, frames[L], g, tmp, sort_bytes, stream));
+			wave(cur, open, r2[L], 0, frames[L], nxt, counts + L);
 		}
-		ST_TRY(hipGetLastError());
+		KD_TRY(hipGetLastError());
 		int left = -1;
-		ST_TRY(hipMemcpyAsync(&left, counts + L, sizeof(int), hipMemcpyDeviceToHost, stream));
-		ST_TRY(hipStreamSynchronize(stream));
+		KD_TRY(hipMemcpyAsync(&left, counts + L, sizeof(int), hipMemcpyDeviceToHost, stream));
+		KD_TRY(hipStreamSynchronize(stream));
 		if (left < 0 || left > open) return hipErrorUnknown;
 		rep.resolved[L] = open - left;
 		rep.levels_run = L + 1;
@@ -1268,40 +1249,76 @@ hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFra
 		std::swap(cur, nxt);
 	}
 	if (open > 0) {
-		// the top level: every point is a candidate, in any order
-		if (rep.levels_run == 0) {
-			hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, ids2, n);
-			ST_TRY(hipGetLastError());
-			hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, cur, n);
-			ST_TRY(hipGetLastError());
-			hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-			ST_TRY(hipGetLastError());
-		}
-		hipLaunchKernelGGL(stat_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, 0.f, 1, 0.f, 0.f,
-		                   0.f, 1.f, u, nxt, counts + kStatMaxLevels);
-		ST_TRY(hipGetLastError());
+		const VoxelFrame unread{{0.f, 0.f, 0.f}, 0.f, 1.f, 0, 0};
+		wave(cur, open, 0.f, 1, unread, nxt, counts + kStatMaxLevels);
+		KD_TRY(hipGetLastError());
 		rep.top = open;
 	}
+	return hipSuccess;
+}
+
+static dim3 knn_wave_grid(int count) { return dim3((unsigned)(((size_t)count * 64 + 255) / 256)); }
+
+hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFrame* frames, const float* r2, int levels, int k, float std_ratio,
+                                       float* d_out, int32_t* d_index, float* d_mean, double* threshold, int* m_out, StatReport* report, hipStream_t stream,
+                                       hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n < 2 || !m_out || k < 1 || k > 64 || k > n - 1 || levels < 0 || levels > kStatMaxLevels || (levels > 0 && (!frames || !r2))) return hipErrorInvalidValue;
+	const dim3 blk(256), grd((n + 255) / 256);
+	unsigned long long* sums = nullptr;
+	int *flag = nullptr, *scan = nullptr, *listA = nullptr, *listB = nullptr, *counts = nullptr;
+	float* mean = nullptr;
+	StatFinish* fin = nullptr;
+	void* tmp = nullptr;
+	Temps t;
+	CellGrid g;
+	const size_t N = (size_t)n;
+	KD_TRY(g.alloc(t, N, true));
+	KD_TRY(t.get(sums, 4));                                      // S1, A, B and the bits of U
+	KD_TRY(t.get(flag, N + 1));
+	KD_TRY(t.get(scan, N + 1));
+	KD_TRY(t.get(listA, N));
+	KD_TRY(t.get(listB, N));
+	KD_TRY(t.get(counts, kStatMaxLevels + 1));
+	KD_TRY(t.get(fin, 1));
+	if (!d_mean) KD_TRY(t.get(mean, N));
+	float* u = d_mean ? d_mean : mean;
+	unsigned* umax = (unsigned*)(sums + 3);
+	size_t sort_bytes = 0, scan_bytes = 0;
+	KD_TRY(grid_sort_bytes(g, N, frames, levels, sort_bytes, stream));
+	KD_TRY(compact_scan_bytes(flag, scan, N, scan_bytes, stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16)));
+	StatReport rep;
+	// ev_begin .. ev_end: the kernels and the read-backs; the allocations above and the frees at the end are outside
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
+	KD_TRY(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 4, stream));
+	const MeanSink sink{u};
+	KD_TRY(grid_knn_levels(
+		d_xyz, n, frames, r2, levels, g, tmp, sort_bytes, listA, listB, counts, nullptr, rep, stream,
+		[&](float r2_0, int* open_list, int* open_count) {
+			const dim3 g0((n + kStatBlock - 1) / kStatBlock), b0(kStatBlock);
+			if (k <= 16) hipLaunchKernelGGL((grid_knn_block_kernel<16, MeanSink>), g0, b0, 0, stream, g.pts, g.sorted_keys, n, k, r2_0, sink, open_list, open_count);
+			else if (k <= 32) hipLaunchKernelGGL((grid_knn_block_kernel<32, MeanSink>), g0, b0, 0, stream, g.pts, g.sorted_keys, n, k, r2_0, sink, open_list, open_count);
+			else hipLaunchKernelGGL((grid_knn_block_kernel<64, MeanSink>), g0, b0, 0, stream, g.pts, g.sorted_keys, n, k, r2_0, sink, open_list, open_count);
+		},
+		[&](const int* list, int count, float r2_L, int all, const VoxelFrame& f, int* open_list, int* open_count) {
+			hipLaunchKernelGGL(grid_knn_wave_kernel<MeanSink>, knn_wave_grid(count), blk, 0, stream, d_xyz, g.pts, g.sorted_keys, n, list, count, k, r2_L, all,
+			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, sink, open_list, open_count);
+		}));
 	hipLaunchKernelGGL(stat_max_kernel, grd, blk, 0, stream, u, n, umax);
-	ST_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	hipLaunchKernelGGL(stat_sums_kernel, grd, blk, 0, stream, u, n, umax, sums);
-	ST_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	hipLaunchKernelGGL(stat_finish_kernel, dim3(1), dim3(64), 0, stream, umax, sums, n, std_ratio, fin);
-	ST_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	hipLaunchKernelGGL(stat_flag_kernel, grd, blk, 0, stream, u, n, fin, flag);
-	ST_TRY(hipGetLastError());
-	ST_TRY(hipMemsetAsync(flag + N, 0, sizeof(int), stream));
-	size_t bytes = scan_bytes;
-	ST_TRY(rocprim::exclusive_scan(tmp, bytes, flag, scan, 0, N + 1, rocprim::plus<int>(), stream));
-	hipLaunchKernelGGL(ror_compact_kernel, grd, blk, 0, stream, d_xyz, flag, scan, n, d_out, d_index);
-	ST_TRY(hipGetLastError());
+	KD_TRY(hipGetLastError());
 	int m = -1;
 	StatFinish h_fin{0.0, 0.0, 0, 0};
-	ST_TRY(hipMemcpyAsync(&m, scan + N, sizeof(int), hipMemcpyDeviceToHost, stream));
-	ST_TRY(hipMemcpyAsync(&h_fin, fin, sizeof(StatFinish), hipMemcpyDeviceToHost, stream));
-	if (ev_end) ST_TRY(hipEventRecord(ev_end, stream));
-	ST_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
-#undef ST_TRY
+	KD_TRY(compact_tail(d_xyz, n, flag, scan, tmp, scan_bytes, nullptr, d_out, d_index, nullptr, &m, stream));
+	KD_TRY(hipMemcpyAsync(&h_fin, fin, sizeof(StatFinish), hipMemcpyDeviceToHost, stream));
+	KD_TRY(end_and_drain(ev_end, stream));
 	if (m < 1 || m > n) return hipErrorUnknown;
 	*m_out = m;
 	if (threshold) *threshold = h_fin.threshold;
@@ -1314,165 +1331,41 @@ hipError_t launch_stat_outlier_removal(const float* d_xyz, int n, const VoxelFra
 // statistical filter's search with the neighbours kept, not only their distances: every candidate is the 64-bit key
 // (bits of d2) << 32 | index, a total order, so the k smallest keys are the rows the header defines, ties at the k-th place included.  A
 // point is resolved at level L when the d2 of its k-th key is <= r_L * r_L: every point that close lies in its 27 cells, so
-// no unseen point has a smaller key.  Level 0 serves every point (self_knn_block_kernel), the later levels and the top level the listed
-// ones (self_knn_wave_kernel); normal_pca_kernel turns the rows into normals, one thread per point.
+// no unseen point has a smaller key.  Level 0 serves every point (grid_knn_block_kernel with keys), the later levels and the top level the
+// listed ones (grid_knn_wave_kernel with keys); normal_pca_kernel turns the rows into normals, one thread per point.
 // ------------------------------------------------------------------------------------------------
 constexpr unsigned long long kKnnNoKey = ~0ull;                // above every key: the d2 of a key is finite
 
-__device__ __forceinline__ unsigned long long knn_key(float d2, int id) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(unsigned)id; }
-// the d2 of a key; of kKnnNoKey a NaN, which is <= no radius
-__device__ __forceinline__ float knn_key_d2(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+struct KnnKey {                                                // (bits of d2) << 32 | index; none = kKnnNoKey
+	using T = unsigned long long;
+	static __device__ __forceinline__ T none() { return kKnnNoKey; }
+	static __device__ __forceinline__ T make(float d2, int id) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(unsigned)id; }
+	// the d2 of a key; of kKnnNoKey a NaN, which is <= no radius
+	static __device__ __forceinline__ float d2(T key) { return __uint_as_float((unsigned)(key >> 32)); }
+	static __device__ __forceinline__ T shfl(T key, int src) { return shfl64(key, src); }
+	static __device__ __forceinline__ T shfl_up(T key) { return shfl_up64(key, 1); }
+};
 
-// stat_knn_block_kernel's shape with keys in the columns: lane t owns column t of `best` (8-byte words at stride kStatBlock: the 32 lanes
-// of a half wave read 64 consecutive dwords, one bank each), KT >= k rows of 2 KB.  A candidate is inserted only when its key is strictly
-// below the lane's k-th key, held in registers; keys are unique, so a cell of identical points costs one comparison per candidate once the
-// column holds the k smallest indices.  A lane whose k-th d2 is <= r2 writes row P.id; any other appends its id to the open list.  No
-// workgroup waits on another
-template <int KT>
-__global__ void __launch_bounds__(kStatBlock) self_knn_block_kernel(const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys, int n, int k,
-                                                                    float r2, int32_t* __restrict__ out_index, float* __restrict__ out_d2,
-                                                                    int* __restrict__ open_list, int* __restrict__ open_count)
-{
-	__shared__ RorPt tile[kStatBlock];
-	__shared__ unsigned long long best[KT * kStatBlock];
-	__shared__ int iv_lo[9], iv_hi[9];
-	const int tid = threadIdx.x;
-	const int first = blockIdx.x * kStatBlock, last = min(first + kStatBlock, n) - 1;
-	const int s = first + tid;
-	const bool valid = s < n;
-	if (tid < 9) {
-		const long long D = (long long)(tid % 3 - 1) * (1ll << 21) + (long long)(tid / 3 - 1) * (1ll << 42);
-		iv_lo[tid] = ror_bound(keys, n, (long long)keys[first] + D - 1, false);
-		iv_hi[tid] = ror_bound(keys, n, (long long)keys[last] + D + 1, true);
+// row id of the index matrix and, when asked for, of the d2 matrix
+struct RowSink {
+	using Entry = KnnKey;
+	int32_t* __restrict__ index;
+	float* __restrict__ d2;
+	__device__ __forceinline__ void put(size_t at, unsigned long long key) const
+	{
+		index[at] = (int32_t)(unsigned)(key & 0xffffffffull);
+		if (d2) d2[at] = KnnKey::d2(key);
 	}
-	for (int j = 0; j < k; j++) best[j * kStatBlock + tid] = kKnnNoKey;
-	__syncthreads();
-	if (tid == 0)
-		for (int o = 1; o < 9; o++) {
-			iv_lo[o] = max(iv_lo[o], iv_hi[o - 1]);
-			iv_hi[o] = max(iv_hi[o], iv_lo[o]);
-		}
-	__syncthreads();
-	RorPt P{0.f, 0.f, 0.f, -1};
-	long long K = 0;
-	if (valid) { P = pts[s]; K = (long long)keys[s]; }
-	unsigned long long kth = kKnnNoKey;
-	for (int o = 0; o < 9; o++) {
-		const int lo = iv_lo[o], hi = iv_hi[o];
-		for (int t0 = lo; t0 < hi; t0 += kStatBlock) {
-			__syncthreads();                                     // the previous tile has been read by everybody
-			const int len = min(kStatBlock, hi - t0);
-			if (tid < len) tile[tid] = pts[t0 + tid];
-			__syncthreads();
-			const long long ta = (long long)keys[t0], tb = (long long)keys[t0 + len - 1];
-			bool need = false;
-			if (valid)
-				for (int q = 0; q < 9; q++) {
-					const long long c = K + (long long)(q % 3 - 1) * (1ll << 21) + (long long)(q / 3 - 1) * (1ll << 42);
-					need = need || (c - 1 <= tb && c + 1 >= ta);
-				}
-			if (!__any(need)) continue;                          // wave-uniform; the next barrier is at the loop's head
-			if (!need) continue;
-			for (int j = 0; j < len; j++) {
-				const RorPt Q = tile[j];
-				const unsigned long long ck = knn_key(stat_d2(P.x, P.y, P.z, Q), Q.id);
-				if (ck < kth && Q.id != P.id) {
-					int p = k - 1;
-					while (p > 0) {
-						const unsigned long long b = best[(p - 1) * kStatBlock + tid];
-						if (!(b > ck)) break;
-						best[p * kStatBlock + tid] = b;
-						p--;
-					}
-					best[p * kStatBlock + tid] = ck;
-					kth = best[(k - 1) * kStatBlock + tid];
-				}
-			}
-		}
+	__device__ __forceinline__ void lane(int id, int k, const unsigned long long* col) const
+	{
+		const size_t row = (size_t)id * (size_t)k;
+		for (int j = 0; j < k; j++) put(row + j, col[j * kStatBlock]);
 	}
-	if (!valid) return;
-	if (knn_key_d2(kth) <= r2) {
-		const size_t row = (size_t)P.id * (size_t)k;
-		for (int j = 0; j < k; j++) {
-			const unsigned long long key = best[j * kStatBlock + tid];
-			out_index[row + j] = (int32_t)(unsigned)(key & 0xffffffffull);
-			if (out_d2) out_d2[row + j] = knn_key_d2(key);
-		}
-	} else {
-		open_list[atomicAdd(open_count, 1)] = P.id;
+	__device__ __forceinline__ void wave(int id, int k, int lane, unsigned long long mine) const
+	{
+		if (lane < k) put((size_t)id * (size_t)k + (size_t)lane, mine);
 	}
-}
-
-__device__ __forceinline__ unsigned long long knn_shfl64(unsigned long long v, int src)
-{
-	const int lo = __shfl((int)(unsigned)(v & 0xffffffffull), src, 64);
-	const int hi = __shfl((int)(unsigned)(v >> 32), src, 64);
-	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
-}
-
-__device__ __forceinline__ unsigned long long knn_shfl_up64(unsigned long long v)
-{
-	const int lo = __shfl_up((int)(unsigned)(v & 0xffffffffull), 1, 64);
-	const int hi = __shfl_up((int)(unsigned)(v >> 32), 1, 64);
-	return ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
-}
-
-// stat_knn_wave_kernel with keys: a wave per listed point, lane j holds the j-th smallest key seen so far (a 64-bit shuffle is two 32-bit
-// ones), a candidate strictly below the k-th key is inserted by one shuffle up -- a lane keeps its key if it is below the candidate, takes
-// the candidate if its lower neighbour's key is below it, and its lower neighbour's key otherwise.  Lanes 0..k-1 write the row.  all = 1 is
-// the top level, the one run [0, n).  The loops run over the runs' lengths; no wave waits on another
-__global__ void __launch_bounds__(256) self_knn_wave_kernel(const float* __restrict__ xyz, const RorPt* __restrict__ pts, const unsigned long long* __restrict__ keys,
-                                                            int n, const int* __restrict__ list, int count, int k, float r2, int all, float mnx, float mny,
-                                                            float mnz, float pitch, int32_t* __restrict__ out_index, float* __restrict__ out_d2,
-                                                            int* __restrict__ open_list, int* __restrict__ open_count)
-{
-	const int w = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-	if (w >= count) return;                                      // wave-uniform
-	const int id = list[w];
-	const float px = xyz[3 * (size_t)id], py = xyz[3 * (size_t)id + 1], pz = xyz[3 * (size_t)id + 2];
-	int my_lo = 0, my_hi = 0;
-	if (all) {
-		if (lane == 0) my_hi = n;
-	} else if (lane < 9) {
-		const long long K = (long long)(vx_cell(px - mnx, pitch) | (vx_cell(py - mny, pitch) << 21) | (vx_cell(pz - mnz, pitch) << 42));
-		const long long c = K + (long long)(lane % 3 - 1) * (1ll << 21) + (long long)(lane / 3 - 1) * (1ll << 42);
-		my_lo = ror_bound(keys, n, c - 1, false);
-		my_hi = max(my_lo, ror_bound(keys, n, c + 1, true));
-	}
-	unsigned long long mine = kKnnNoKey, kth = kKnnNoKey;
-	const int runs = all ? 1 : 9;
-	for (int o = 0; o < runs; o++) {
-		const int lo = __shfl(my_lo, o, 64), hi = __shfl(my_hi, o, 64);
-		for (int base = lo; base < hi; base += 64) {
-			const int j = base + lane;
-			unsigned long long ck = kKnnNoKey;
-			if (j < hi) {
-				const RorPt Q = pts[j];
-				if (Q.id != id) ck = knn_key(stat_d2(px, py, pz, Q), Q.id);
-			}
-			unsigned long long hot = __ballot(ck < kth);
-			while (hot) {
-				const int src = __ffsll((long long)hot) - 1;
-				hot &= hot - 1;
-				const unsigned long long v = knn_shfl64(ck, src);
-				if (v < kth) {                                       // wave-uniform
-					const unsigned long long below = knn_shfl_up64(mine);
-					mine = (mine < v) ? mine : ((lane == 0 || below < v) ? v : below);
-					kth = knn_shfl64(mine, k - 1);
-				}
-			}
-		}
-	}
-	if (all || knn_key_d2(kth) <= r2) {
-		if (lane < k) {
-			const size_t at = (size_t)id * (size_t)k + (size_t)lane;
-			out_index[at] = (int32_t)(unsigned)(mine & 0xffffffffull);
-			if (out_d2) out_d2[at] = knn_key_d2(mine);
-		}
-	} else if (lane == 0) {
-		open_list[atomicAdd(open_count, 1)] = id;
-	}
-}
+};
 
 // One thread per point, taken in the order of the first grid level so that the threads of a wave gather from neighbouring memory.  The
 // arithmetic is normal_pca_point's (device.hpp), the host's text
@@ -1493,88 +1386,35 @@ hipError_t launch_self_knn(const float* d_xyz, int n, const VoxelFrame* frames, 
                            int* d_order, StatReport* report, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
 	if (n < 2 || !d_index || k < 1 || k > kKnnSelfMax || k > n - 1 || levels < 0 || levels > kStatMaxLevels || (levels > 0 && (!frames || !r2))) return hipErrorInvalidValue;
-	const dim3 blk(256), grd((n + 255) / 256);
-	hipError_t e;
-#define KS_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-	unsigned long long *keys = nullptr, *keys2 = nullptr;
-	int *ids = nullptr, *ids2 = nullptr, *listA = nullptr, *listB = nullptr, *counts = nullptr;
-	RorPt* pts = nullptr;
+	int *listA = nullptr, *listB = nullptr, *counts = nullptr;
 	void* tmp = nullptr;
-	// every exit path frees the temporaries
-	struct Cleanup {
-		void* const* p[9];
-		~Cleanup() { for (void* const* q : p) hipFree(*q); }
-	} cleanup{{(void**)&keys, (void**)&keys2, (void**)&ids, (void**)&ids2, (void**)&listA, (void**)&listB, (void**)&counts, (void**)&pts, &tmp}};
+	Temps t;
+	CellGrid g;
 	const size_t N = (size_t)n;
-	KS_TRY(hipMalloc(&keys, sizeof(unsigned long long) * N));
-	KS_TRY(hipMalloc(&keys2, sizeof(unsigned long long) * N));
-	KS_TRY(hipMalloc(&ids, sizeof(int) * N));
-	KS_TRY(hipMalloc(&ids2, sizeof(int) * N));
-	KS_TRY(hipMalloc(&listA, sizeof(int) * N));
-	KS_TRY(hipMalloc(&listB, sizeof(int) * N));
-	KS_TRY(hipMalloc(&counts, sizeof(int) * (kStatMaxLevels + 1)));
-	KS_TRY(hipMalloc(&pts, sizeof(RorPt) * N));
+	KD_TRY(g.alloc(t, N, true));
+	KD_TRY(t.get(listA, N));
+	KD_TRY(t.get(listB, N));
+	KD_TRY(t.get(counts, kStatMaxLevels + 1));
 	size_t sort_bytes = 0;
-	for (int L = 0; L < levels; L++) {
-		size_t bytes = 0;
-		KS_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys2, ids, ids2, N, 0, (unsigned)std::min(std::max(frames[L].key_bits, 1), 63), stream));
-		sort_bytes = std::max(sort_bytes, bytes);
-	}
-	KS_TRY(hipMalloc(&tmp, std::max<size_t>(sort_bytes, 16)));
+	KD_TRY(grid_sort_bytes(g, N, frames, levels, sort_bytes, stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(sort_bytes, 16)));
 	StatReport rep;
 	// ev_begin .. ev_end: the kernels and the read-backs; the allocations above and the frees at the end are outside
-	if (ev_begin) KS_TRY(hipEventRecord(ev_begin, stream));
-	KS_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
-	int open = n;                                              // the points no level has resolved yet
-	int *cur = listA, *nxt = listB;
-	for (int L = 0; L < levels && open > 0; L++) {
-		const VoxelFrame& f = frames[L];
-		const unsigned end_bit = (unsigned)std::min(std::max(f.key_bits, 1), 63);
-		hipLaunchKernelGGL(vx_key_kernel, grd, blk, 0, stream, d_xyz, n, f.mn[0], f.mn[1], f.mn[2], f.voxel, keys, ids);
-		KS_TRY(hipGetLastError());
-		size_t bytes = sort_bytes;
-		KS_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, ids, ids2, N, 0, end_bit, stream));
-		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-		KS_TRY(hipGetLastError());
-		if (L == 0) {
-			if (d_order) KS_TRY(hipMemcpyAsync(d_order, ids2, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (kStatMaxLevels + 1), stream));
+	const RowSink sink{d_index, d_dist_sq};
+	KD_TRY(grid_knn_levels(
+		d_xyz, n, frames, r2, levels, g, tmp, sort_bytes, listA, listB, counts, d_order, rep, stream,
+		[&](float r2_0, int* open_list, int* open_count) {
 			const dim3 g0((n + kStatBlock - 1) / kStatBlock), b0(kStatBlock);
-			if (k <= 16) hipLaunchKernelGGL(self_knn_block_kernel<16>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], d_index, d_dist_sq, nxt, counts);
-			else hipLaunchKernelGGL(self_knn_block_kernel<32>, g0, b0, 0, stream, pts, keys2, n, k, r2[0], d_index, d_dist_sq, nxt, counts);
-		} else {
-			hipLaunchKernelGGL(self_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, r2[L], 0,
-			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, d_index, d_dist_sq, nxt, counts + L);
-		}
-		KS_TRY(hipGetLastError());
-		int left = -1;
-		KS_TRY(hipMemcpyAsync(&left, counts + L, sizeof(int), hipMemcpyDeviceToHost, stream));
-		KS_TRY(hipStreamSynchronize(stream));
-		if (left < 0 || left > open) return hipErrorUnknown;
-		rep.resolved[L] = open - left;
-		rep.levels_run = L + 1;
-		open = left;
-		std::swap(cur, nxt);
-	}
-	if (rep.levels_run == 0) {
-		// no grid level: input order, for the top level's records and list and for the caller
-		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, ids2, n);
-		KS_TRY(hipGetLastError());
-		hipLaunchKernelGGL(so_iota_kernel, grd, blk, 0, stream, cur, n);
-		KS_TRY(hipGetLastError());
-		hipLaunchKernelGGL(ror_gather_kernel, grd, blk, 0, stream, d_xyz, ids2, n, pts);
-		KS_TRY(hipGetLastError());
-		if (d_order) KS_TRY(hipMemcpyAsync(d_order, ids2, sizeof(int) * N, hipMemcpyDeviceToDevice, stream));
-	}
-	if (open > 0) {
-		// the top level: every point is a candidate, in any order
-		hipLaunchKernelGGL(self_knn_wave_kernel, dim3((unsigned)(((size_t)open * 64 + 255) / 256)), blk, 0, stream, d_xyz, pts, keys2, n, cur, open, k, 0.f, 1, 0.f, 0.f,
-		                   0.f, 1.f, d_index, d_dist_sq, nxt, counts + kStatMaxLevels);
-		KS_TRY(hipGetLastError());
-		rep.top = open;
-	}
-	if (ev_end) KS_TRY(hipEventRecord(ev_end, stream));
-	KS_TRY(hipStreamSynchronize(stream));                      // the temporaries are in use until here
-#undef KS_TRY
+			if (k <= 16) hipLaunchKernelGGL((grid_knn_block_kernel<16, RowSink>), g0, b0, 0, stream, g.pts, g.sorted_keys, n, k, r2_0, sink, open_list, open_count);
+			else hipLaunchKernelGGL((grid_knn_block_kernel<32, RowSink>), g0, b0, 0, stream, g.pts, g.sorted_keys, n, k, r2_0, sink, open_list, open_count);
+		},
+		[&](const int* list, int count, float r2_L, int all, const VoxelFrame& f, int* open_list, int* open_count) {
+			hipLaunchKernelGGL(grid_knn_wave_kernel<RowSink>, knn_wave_grid(count), dim3(256), 0, stream, d_xyz, g.pts, g.sorted_keys, n, list, count, k, r2_L, all,
+			                   f.mn[0], f.mn[1], f.mn[2], f.voxel, sink, open_list, open_count);
+		}));
+	KD_TRY(end_and_drain(ev_end, stream));
 	if (report) *report = rep;
 	return hipSuccess;
 }
@@ -1585,19 +1425,14 @@ hipError_t launch_estimate_normals(const float* d_xyz, int n, const VoxelFrame* 
 {
 	if (n < 3 || !d_normals || !d_index || k < 3 || k > kKnnSelfMax || k - 1 > n - 1) return hipErrorInvalidValue;
 	int* order = nullptr;
-	struct Cleanup {
-		int*& p;
-		~Cleanup() { hipFree(p); }
-	} cleanup{order};
-	hipError_t e;
-	if ((e = hipMalloc(&order, sizeof(int) * (size_t)n)) != hipSuccess) return e;
+	Temps t;
+	KD_TRY(t.get(order, (size_t)n));
 	// ev_begin is recorded by the search, ev_end after the PCA
-	if ((e = launch_self_knn(d_xyz, n, frames, r2, levels, k - 1, d_index, nullptr, order, report, stream, ev_begin, nullptr)) != hipSuccess) return e;
+	KD_TRY(launch_self_knn(d_xyz, n, frames, r2, levels, k - 1, d_index, nullptr, order, report, stream, ev_begin, nullptr));
 	hipLaunchKernelGGL(normal_pca_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_xyz, d_index, order, n, k - 1, vp ? 1 : 0, vp ? vp[0] : 0.f,
 	                   vp ? vp[1] : 0.f, vp ? vp[2] : 0.f, d_normals, d_variation);
-	if ((e = hipGetLastError()) != hipSuccess) return e;
-	if (ev_end && (e = hipEventRecord(ev_end, stream)) != hipSuccess) return e;
-	return hipStreamSynchronize(stream);                       // `order` is in use until here
+	KD_TRY(hipGetLastError());
+	return end_and_drain(ev_end, stream);                      // `order` is in use until here
 }
 
 // the per-axis minimum and maximum of a cloud on the device: what voxel_frame derives on the host, for a cloud that never leaves the device
@@ -1622,20 +1457,19 @@ struct MinMaxJoin {
 hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream)
 {
 	if (n <= 0) return hipErrorInvalidValue;
-	hipError_t e;
 	MinMax3* d_res = nullptr;
 	void* tmp = nullptr;
-	struct Cleanup { MinMax3*& r; void*& t; ~Cleanup() { hipFree(r); hipFree(t); } } cleanup{d_res, tmp};
+	Temps t;
 	auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), MinMaxOf{d_xyz});
 	const MinMax3 init{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}};
 	size_t bytes = 0;
-	if ((e = rocprim::reduce(nullptr, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream)) != hipSuccess) return e;
-	if ((e = hipMalloc(&tmp, std::max<size_t>(bytes, 16))) != hipSuccess) return e;
-	if ((e = hipMalloc(&d_res, sizeof(MinMax3))) != hipSuccess) return e;
-	if ((e = rocprim::reduce(tmp, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream)) != hipSuccess) return e;
+	KD_TRY(rocprim::reduce(nullptr, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(bytes, 16)));
+	KD_TRY(t.get(d_res, 1));
+	KD_TRY(rocprim::reduce(tmp, bytes, in, d_res, init, (size_t)n, MinMaxJoin(), stream));
 	MinMax3 res;
-	if ((e = hipMemcpyAsync(&res, d_res, sizeof(MinMax3), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-	if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+	KD_TRY(hipMemcpyAsync(&res, d_res, sizeof(MinMax3), hipMemcpyDeviceToHost, stream));
+	KD_TRY(hipStreamSynchronize(stream));
 	for (int k = 0; k < 3; k++) { mn[k] = res.mn[k]; mx[k] = res.mx[k]; }
 	return hipSuccess;
 }

@@ -1,7 +1,7 @@
 """goicp_knn_self and goicp_estimate_normals on the device.
 
 The device path (kdbuild.hip: per level the voxel operator's key kernel, rocPRIM radix sort and the gather into sorted records; level 0
-self_knn_block_kernel, later levels and the top level self_knn_wave_kernel; normal_pca_kernel) against the host functions, element for
+grid_knn_block_kernel, later levels and the top level grid_knn_wave_kernel, both with keys; normal_pca_kernel) against the host functions, element for
 element, over the grid of tests/test_normals_host.py, and on clouds placed to cut the kernels' edges: sorted cells of exactly 1, 63, 64, 65,
 255, 256, 257, 1, 1 and 511 points at the tier edges of k, 20 001 identical points (every candidate ties at 0: the rows are the smallest
 other indices), a 12 x 12 x 12 unit lattice (every shell is a tie), a cluster with isolated points up to 10^4 cluster diameters away

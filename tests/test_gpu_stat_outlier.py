@@ -1,7 +1,7 @@
 """goicp_statistical_outlier_removal and goicp_set_source_pipeline on the device.
 
 The device filter (kdbuild.hip: per level the voxel operator's key kernel, rocPRIM radix sort and the gather into sorted records; level 0
-stat_knn_block_kernel, later levels and the top level stat_knn_wave_kernel; then the maximum, the exact sums, the finishing thread, the
+grid_knn_block_kernel, later levels and the top level grid_knn_wave_kernel, both with distances; then the maximum, the exact sums, the finishing thread, the
 flags, rocPRIM scan and the compaction) against the host function, element for element, over the grid of
 tests/test_stat_outlier_host.py, and on clouds placed to cut the kernels' edges: sorted cells of exactly 1, 63, 64, 65, 255, 256, 257, 1, 1
 and 511 points at the tier edges of k, 20 001 identical points, a cluster with isolated points up to 10^4 cluster diameters away (several
