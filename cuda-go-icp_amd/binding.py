@@ -104,6 +104,20 @@ class CClusterSelect(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbors", C.c_int32), ("min_size", C.c_int32), ("max_clusters", C.c_int32)]
 
 
+class CPlaneSelect(C.Structure):
+    _fields_ = [("distance", C.c_float), ("iterations", C.c_int32), ("refine", C.c_int32), ("max_planes", C.c_int32), ("min_inliers", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class CPlane(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("point", C.c_float * 3), ("d", C.c_float), ("inliers", C.c_int32), ("hypothesis", C.c_int32),
+                ("refined", C.c_int32)]
+
+
+PLANE_MAX_ITERATIONS = 65536
+PLANE_MAX_PLANES = 8
+
+
 class CPoseInfoOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
 
@@ -227,6 +241,15 @@ SYMBOLS = {
     "goicp_cluster_filter": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CClusterSelect), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_size_t)]),
     "goicp_set_source_clustered": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(CClusterSelect), C.POINTER(C.c_size_t)]),
+    "goicp_plane_select_default": (None, [C.POINTER(CPlaneSelect)]),
+    "goicp_segment_plane_host": (C.c_int, [_fp, C.c_size_t, C.POINTER(CPlaneSelect), C.POINTER(C.c_int32), C.POINTER(CPlane), C.POINTER(C.c_size_t)]),
+    "goicp_segment_plane": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CPlaneSelect), C.POINTER(C.c_int32), C.POINTER(CPlane), C.POINTER(C.c_size_t)]),
+    "goicp_plane_filter_host": (C.c_int, [_fp, C.c_size_t, C.POINTER(CPlaneSelect), _fp, C.POINTER(C.c_int32), C.POINTER(CPlane), C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_size_t)]),
+    "goicp_plane_filter": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CPlaneSelect), _fp, C.POINTER(C.c_int32), C.POINTER(CPlane), C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_size_t)]),
+    "goicp_set_source_segmented": (C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(CSourcePipeline), C.POINTER(CPlaneSelect), C.POINTER(CClusterSelect),
+                                            C.POINTER(C.c_size_t)]),
     "goicp_knn_self_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_knn_self": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_estimate_normals_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),

@@ -4,6 +4,7 @@
 //                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
 //                                [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]
 //                                [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]
+//                                [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]]
 //   --ranks N   (modes 3/4) shard the rotation-cube search over N GPUs of this node: N engines (device r for rank r),
 //               N host threads, RCCL all-reduce / broadcast over xGMI (goicp_register_multi_gpu)
 //   --reference-root   search the reference CPU path's roots ([-pi,pi]^3 x [-0.5,0.5]^3, src/goicp/jly_goicp.cpp:44-53) and
@@ -63,6 +64,15 @@
 //               (goicp_set_source_clustered: the same bits); each prints "kept m of n".  The --target-cluster-* forms filter the target the
 //               same way, on the host, before the engine is created.  R must be finite, > 0 and R * R a normal float, K, S and C integers
 //               >= 0, and the three need --cluster-radius -- refused before any device is touched
+//   --plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]   RANSAC plane removal,
+//               after the neighbourhood filters and before --cluster-*: the points of the source -- and of every cloud of --source-list --
+//               within D (cloud units after `resize`) of the dominant plane are dropped: the best of T three-point hypotheses (default 1000),
+//               refit once by least squares over its inliers unless --plane-no-refine, for up to P planes in turn (default 1), each with at
+//               least S inliers (default 0); X seeds the draws (default 0).  The config's own source is filtered on the host
+//               (goicp_plane_filter_host), every listed cloud on the device as part of its swap (goicp_set_source_segmented: the same bits);
+//               each prints "kept m of n".  The --target-plane-* forms filter the target the same way, on the host, before the engine is
+//               created.  D must be a finite number > 0, T an integer in 0..65536, P in 0..8, S an integer >= 0, and the others need
+//               --plane-distance -- refused before any device is touched
 //   --estimate-normals IN OUT.ply [--normal-k K] [--viewpoint X,Y,Z]   a mode of its own that takes no config and registers nothing: per-point
 //               normals and surface variation of the cloud IN from its K-point neighbourhoods (K counts the point itself, 3..32, default 16;
 //               goicp_estimate_normals on the device when there is one, goicp_estimate_normals_host otherwise: the same bits), flipped
@@ -199,7 +209,7 @@ int main(int argc, char** argv)
 {
 	for (int i = 1; i < argc; i++)
 		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16;
 	const char* snk_arg = nullptr;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
@@ -227,6 +237,10 @@ int main(int argc, char** argv)
 	const char* cl_arg[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // radius, min-neighbors, min-size, keep
 	goicp_cluster_select cluster[2];                                                                        // [0] the source's, [1] the target's
 	for (int k = 0; k < 2; k++) goicp_cluster_select_default(&cluster[k]);
+	const char* pl_arg[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};   // distance, iterations, max, min-inliers, seed
+	int pl_no_refine[2] = {0, 0};
+	goicp_plane_select plane_sel[2];                                                                        // [0] the source's, [1] the target's
+	for (int k = 0; k < 2; k++) goicp_plane_select_default(&plane_sel[k]);
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -255,11 +269,19 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--stat-std-ratio")) sa_arg[0] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-neighbors")) sk_arg[1] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-std-ratio")) sa_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--plane-no-refine")) pl_no_refine[0] = 1;
+		else if (!std::strcmp(argv[i], "--target-plane-no-refine")) pl_no_refine[1] = 1;
 		else {
 			static const char* const cl_names[2][4] = {{"--cluster-radius", "--cluster-min-neighbors", "--cluster-min-size", "--cluster-keep"},
 			                                           {"--target-cluster-radius", "--target-cluster-min-neighbors", "--target-cluster-min-size", "--target-cluster-keep"}};
+			const char* const name = argv[i];                       // a match below consumes the value after it
 			for (int q = 0; q < 8; q++)
-				if (!std::strcmp(argv[i], cl_names[q / 4][q % 4])) { cl_arg[q / 4][q % 4] = i + 1 < argc ? argv[++i] : ""; break; }
+				if (!std::strcmp(name, cl_names[q / 4][q % 4])) { cl_arg[q / 4][q % 4] = i + 1 < argc ? argv[++i] : ""; break; }
+			static const char* const pl_names[2][5] = {{"--plane-distance", "--plane-iterations", "--plane-max", "--plane-min-inliers", "--plane-seed"},
+			                                           {"--target-plane-distance", "--target-plane-iterations", "--target-plane-max", "--target-plane-min-inliers",
+			                                            "--target-plane-seed"}};
+			for (int q = 0; q < 10; q++)
+				if (!std::strcmp(name, pl_names[q / 5][q % 5])) { pl_arg[q / 5][q % 5] = i + 1 < argc ? argv[++i] : ""; break; }
 		}
 	}
 	for (int k = 0; k < 2; k++) {
@@ -346,6 +368,44 @@ int main(int argc, char** argv)
 		}
 		cluster[k].radius = r;
 		cluster[k].min_neighbors = (int32_t)v[1]; cluster[k].min_size = (int32_t)v[2]; cluster[k].max_clusters = (int32_t)v[3];
+	}
+	for (int k = 0; k < 2; k++) {
+		// a bad plane selection is refused before any device is touched
+		const char* pre = k ? "--target-plane" : "--plane";
+		if (!pl_arg[k][0] && !pl_arg[k][1] && !pl_arg[k][2] && !pl_arg[k][3] && !pl_arg[k][4] && !pl_no_refine[k]) continue;
+		if (!pl_arg[k][0]) {
+			std::fprintf(stderr, "error: %s-iterations, %s-max, %s-min-inliers, %s-seed and %s-no-refine need %s-distance\n", pre, pre, pre, pre, pre, pre);
+			return 2;
+		}
+		char* end = nullptr;
+		const float d = std::strtof(pl_arg[k][0], &end);
+		if (end == pl_arg[k][0] || *end != '\0' || !(d > 0.f) || !(d <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: %s-distance needs a finite distance > 0, got '%s'\n", pre, pl_arg[k][0]);
+			return 2;
+		}
+		static const char* const what[4] = {"distance", "iterations", "max", "min-inliers"};
+		const long top[4] = {0, GOICP_PLANE_MAX_ITERATIONS, GOICP_PLANE_MAX_PLANES, 2147483647L};
+		long v[4] = {0, 0, 0, 0};                                   // the defaults: 1000 hypotheses, one plane, any count
+		for (int a = 1; a < 4; a++) {
+			if (!pl_arg[k][a]) continue;
+			v[a] = std::strtol(pl_arg[k][a], &end, 10);
+			if (end == pl_arg[k][a] || *end != '\0' || v[a] < 0 || v[a] > top[a]) {
+				std::fprintf(stderr, "error: %s-%s needs an integer in 0..%ld, got '%s'\n", pre, what[a], top[a], pl_arg[k][a]);
+				return 2;
+			}
+		}
+		unsigned long long sd = 0;
+		if (pl_arg[k][4]) {
+			sd = std::strtoull(pl_arg[k][4], &end, 10);
+			if (end == pl_arg[k][4] || *end != '\0' || pl_arg[k][4][0] == '-') {
+				std::fprintf(stderr, "error: %s-seed needs an unsigned integer, got '%s'\n", pre, pl_arg[k][4]);
+				return 2;
+			}
+		}
+		plane_sel[k].distance = d;
+		plane_sel[k].iterations = (int32_t)v[1]; plane_sel[k].max_planes = (int32_t)v[2]; plane_sel[k].min_inliers = (int32_t)v[3];
+		plane_sel[k].refine = pl_no_refine[k] ? 0 : 1;
+		plane_sel[k].seed = (uint64_t)sd;
 	}
 	if (list_arg) {
 		// refused before any device is touched
@@ -502,6 +562,24 @@ int main(int argc, char** argv)
 			cloud.swap(kept);
 		}
 		for (int k = 0; k < 2; k++) {
+			// after the neighbourhood filters, before the cluster selection; the host function again
+			std::vector<P3>& cloud = k ? target : source;
+			if (!(plane_sel[k].distance > 0.f) || cloud.empty()) continue;
+			std::vector<P3> kept(cloud.size());
+			goicp_plane found[GOICP_PLANE_MAX_PLANES];
+			size_t m = 0, np = 0;
+			check(goicp_plane_filter_host(&cloud[0].x, cloud.size(), &plane_sel[k], &kept[0].x, nullptr, found, &np, &m));
+			kept.resize(m);
+			std::printf("%s plane distance %g iterations %d max %d min inliers %d refine %d: %zu planes, kept %zu of %zu points\n", k ? "target" : "source",
+			            plane_sel[k].distance, (int)plane_sel[k].iterations, (int)plane_sel[k].max_planes, (int)plane_sel[k].min_inliers, (int)plane_sel[k].refine, np, m,
+			            cloud.size());
+			for (size_t q = 0; q < np; q++)
+				std::printf("%s plane %zu: %.9g x + %.9g y + %.9g z + %.9g = 0, %d inliers\n", k ? "target" : "source", q, found[q].normal[0], found[q].normal[1],
+				            found[q].normal[2], found[q].d, (int)found[q].inliers);
+			if (m == 0) throw std::runtime_error(std::string(k ? "target" : "source") + ": the plane removal keeps no point");
+			cloud.swap(kept);
+		}
+		for (int k = 0; k < 2; k++) {
 			// after every other filter; the host function again
 			std::vector<P3>& cloud = k ? target : source;
 			if (!(cluster[k].radius > 0.f) || cloud.empty()) continue;
@@ -633,7 +711,15 @@ int main(int argc, char** argv)
 			load_cloud(source_list[k], config.subsample, config.resize, next, seed);
 			const auto t0 = std::chrono::steady_clock::now();
 			size_t kept = next.size();
-			if (cluster[0].radius > 0.f) {
+			if (plane_sel[0].distance > 0.f) {
+				goicp_source_pipeline sp;
+				goicp_source_pipeline_default(&sp);
+				sp.voxel = voxel; sp.stat_neighbors = stat_k[0]; sp.stat_std_ratio = stat_ratio[0];
+				sp.radius = outlier_radius[0]; sp.min_neighbors = outlier_min[0];
+				kept = engine.set_source(next, &sp, plane_sel[0], cluster[0].radius > 0.f ? &cluster[0] : nullptr);
+				std::printf("source %zu plane distance %g iterations %d max %d min inliers %d refine %d: kept %zu of %zu points\n", k + 1, plane_sel[0].distance,
+				            (int)plane_sel[0].iterations, (int)plane_sel[0].max_planes, (int)plane_sel[0].min_inliers, (int)plane_sel[0].refine, kept, next.size());
+			} else if (cluster[0].radius > 0.f) {
 				goicp_source_pipeline sp;
 				goicp_source_pipeline_default(&sp);
 				sp.voxel = voxel; sp.stat_neighbors = stat_k[0]; sp.stat_std_ratio = stat_ratio[0];

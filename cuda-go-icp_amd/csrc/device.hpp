@@ -603,6 +603,93 @@ GOICP_HD inline void normal_pca_point(const float* xyz, int i, const int32_t* ro
 	out_n[2] = n2 == 0.f ? 0.f : (flip ? -n2 : n2);
 }
 
+// ---- RANSAC plane segmentation (kdbuild.hip; goicp_segment_plane_host / goicp_plane_filter_host are the host twins) ----
+// What include/goicp_mi355.h defines per hypothesis and per pair, one text for the host path (kdtree.cpp) and the kernels: the counter-based
+// draw (integers only), the plane of a triple (fp64, every operation rounded once, pca's + - * / sqrt), the sign rule and the float pair.
+constexpr int kPlaneMaxIterations = 65536, kPlaneMaxPlanes = 8, kPlaneDefaultIterations = 1000;
+constexpr int kPlaneWords = 16;   // the refit's integer moments: m, S_0..2, the high words of P_00 P_01 P_02 P_11 P_12 P_22, their low words
+// goicp_plane_select with the defaults filled in (iterations and max_planes >= 1)
+struct PlaneSelect {
+	float distance = 0.f;
+	int32_t iterations = 0, refine = 0, max_planes = 0, min_inliers = 0;
+	uint64_t seed = 0;
+};
+struct PlaneRecord {                                           // goicp_plane, field for field
+	float normal[3], point[3], d;
+	int32_t inliers, hypothesis, refined;
+};
+namespace plane {
+// h(c): the splitmix64 finaliser of seed + (c + 1) * 0x9E3779B97F4A7C15
+GOICP_HD inline uint64_t hash(uint64_t seed, uint64_t c)
+{
+	uint64_t z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+// three distinct positions of a cloud of n >= 3 points for hypothesis number g = p * T + t
+GOICP_HD inline void draw(uint64_t seed, uint64_t g, uint32_t n, uint32_t* a_out, uint32_t* b_out, uint32_t* c_out)
+{
+	const uint32_t a = (uint32_t)(hash(seed, 3ull * g) % (uint64_t)n);
+	uint32_t b = (uint32_t)(hash(seed, 3ull * g + 1ull) % (uint64_t)(n - 1u));
+	if (b >= a) b++;
+	uint32_t c = (uint32_t)(hash(seed, 3ull * g + 2ull) % (uint64_t)(n - 2u));
+	const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+	if (c >= lo) c++;
+	if (c >= hi) c++;
+	*a_out = a; *b_out = b; *c_out = c;
+}
+GOICP_HD inline bool finite3(const float v[3])
+{
+	// x - x is 0 for a finite x and NaN for an infinity or a NaN
+	return v[0] - v[0] == 0.f && v[1] - v[1] == 0.f && v[2] - v[2] == 0.f;
+}
+// the normals operator's sign rule without a viewpoint: the first non-zero component positive, a zero written as +0
+GOICP_HD inline void sign(float n[3])
+{
+	const float lead = n[0] != 0.f ? n[0] : (n[1] != 0.f ? n[1] : n[2]);
+	const bool flip = lead < 0.f;
+	for (int k = 0; k < 3; k++) n[k] = n[k] == 0.f ? 0.f : (flip ? -n[k] : n[k]);
+}
+// the float normal of the plane through pa, pb, pc; false: the hypothesis is degenerate (nrm is then not to be used)
+GOICP_HD inline bool of_triple(const float* pa, const float* pb, const float* pc, float nrm[3])
+{
+	using namespace pca;
+	const double u0 = sub((double)pb[0], (double)pa[0]), u1 = sub((double)pb[1], (double)pa[1]), u2 = sub((double)pb[2], (double)pa[2]);
+	const double v0 = sub((double)pc[0], (double)pa[0]), v1 = sub((double)pc[1], (double)pa[1]), v2 = sub((double)pc[2], (double)pa[2]);
+	const double n0 = sub(mul(u1, v2), mul(u2, v1)), n1 = sub(mul(u2, v0), mul(u0, v2)), n2 = sub(mul(u0, v1), mul(u1, v0));
+	const double l2 = add(add(mul(n0, n0), mul(n1, n1)), mul(n2, n2));
+	if (!(l2 > 0.0)) return false;
+	const double len = root(l2);
+	nrm[0] = (float)div(n0, len); nrm[1] = (float)div(n1, len); nrm[2] = (float)div(n2, len);
+	if (!finite3(nrm)) return false;
+	sign(nrm);
+	return true;
+}
+// the pair: is the point within `distance` of the plane through a with normal n?  Float, left to right; a NaN compares false
+GOICP_HD inline bool inlier(float x, float y, float z, float a0, float a1, float a2, float n0, float n1, float n2, float distance)
+{
+	const float e = ((x - a0) * n0 + (y - a1) * n1) + (z - a2) * n2;
+	return (e < 0.f ? -e : e) <= distance;
+}
+// ax + by + cz + d = 0
+GOICP_HD inline float offset(const float n[3], const float p[3])
+{
+	using namespace pca;
+	return (float)-add(add(mul((double)n[0], (double)p[0]), mul((double)n[1], (double)p[1])), mul((double)n[2], (double)p[2]));
+}
+}  // namespace plane
+// The refit's host finish, which both paths call on the 16 integer words (kdtree.cpp): the covariance from exact 128-bit integers, the
+// normals operator's Jacobi, the smallest eigenvalue's column as the float normal, the centroid as the anchor.  mn / e: the frame of the
+// round's cloud (E < 2^e).  false: no usable normal (the refit then does not stand)
+bool plane_refit(const unsigned long long words[kPlaneWords], const float mn[3], int e, float normal[3], float point[3]);
+// d_xyz: the n points on the device; s: the resolved selection.  d_label (may be null): n ints, -1 or the plane that took the point;
+// d_out (may be null): room for 3 n floats, the first 3 * *m are the points no plane took, input order, own bits; d_index (may be null, only
+// with d_out): their original indices.  planes: room for s.max_planes records on the host; *n_planes of them are written.  Between the rounds
+// 8 bytes (the best key), the best hypothesis' 32 and the refit's 128 + 4 come back.  Returns after the stream has drained
+hipError_t launch_segment_plane(const float* d_xyz, int n, const PlaneSelect& s, int32_t* d_label, float* d_out, int32_t* d_index, PlaneRecord* planes,
+                                int* n_planes, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+
 // per-axis minimum and maximum of n points on the device (one rocPRIM reduction, 24 bytes come back): the frame of a cloud that a device
 // stage produced and the host has not seen.  Returns after the stream has drained
 hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream);

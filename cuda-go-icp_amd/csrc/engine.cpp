@@ -896,6 +896,53 @@ void Engine::cluster_filter(const float* xyz, size_t n, float radius, int32_t mi
 	if (p_.verbose) std::fprintf(stderr, "[goicp] cluster_filter: %zu -> %d points of %d clusters, device %.3f ms\n", n, m, c, ms);
 }
 
+void Engine::segment_plane(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, PlaneRecord* out_planes, size_t* n_planes)
+{
+	if (!out_label || !out_planes || !n_planes) throw std::invalid_argument("goicp_segment_plane: out_label, out_planes and n_planes must be non-null");
+	plane_check_cloud(xyz, n);
+	if (registering_.load()) throw std::invalid_argument("goicp_segment_plane: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_);
+	Buf<int32_t> d_label(n);
+	PlaneRecord planes[kPlaneMaxPlanes];
+	int c = 0, m = 0;
+	HIPCHK(launch_segment_plane(d_xyz, (int)n, s, d_label, nullptr, nullptr, planes, &c, &m, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_label, d_label, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	for (int p = 0; p < c; p++) out_planes[p] = planes[p];
+	*n_planes = (size_t)c;
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		std::fprintf(stderr, "[goicp] segment_plane: %zu points, %d planes, device %.3f ms\n", n, c, ms);
+	}
+}
+
+void Engine::plane_filter(const float* xyz, size_t n, const PlaneSelect& s, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes, size_t* n_planes,
+                          size_t* m_out)
+{
+	if (!out_xyz || !m_out) throw std::invalid_argument("goicp_plane_filter: out_xyz and m must be non-null");
+	plane_check_cloud(xyz, n);
+	if (registering_.load()) throw std::invalid_argument("goicp_plane_filter: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_out(3 * n);
+	Buf<int32_t> d_idx(out_index ? n : 0);
+	PlaneRecord planes[kPlaneMaxPlanes];
+	int c = 0, m = 0;
+	HIPCHK(launch_segment_plane(d_xyz, (int)n, s, nullptr, d_out, out_index ? d_idx.get() : nullptr, planes, &c, &m, stream_, ev0_, ev1_));
+	if (m > 0) HIPCHK(hipMemcpyAsync(out_xyz, d_out, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	if (out_index && m > 0) HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (out_planes) for (int p = 0; p < c; p++) out_planes[p] = planes[p];
+	if (n_planes) *n_planes = (size_t)c;
+	*m_out = (size_t)m;
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		std::fprintf(stderr, "[goicp] plane_filter: %zu -> %d points behind %d planes, device %.3f ms\n", n, m, c, ms);
+	}
+}
+
 void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const SourceStages& st, size_t* n_kept)
 {
 	const std::string who(fn);
@@ -906,8 +953,12 @@ void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const
 	// the counts of the cluster stage are refused with that stage off too; every other parameter of a stage that is off is not looked at
 	if (st.cluster_min_neighbors < 0) throw std::invalid_argument("goicp cluster: min_neighbors must not be negative");
 	cluster_check_select(st.cluster_min_size, st.cluster_max_clusters);
+	if (std::isnan(st.plane_distance) || st.plane_distance < 0.f) throw std::invalid_argument(who + ": the plane distance must be 0 (no stage) or a distance > 0");
 	const bool has_voxel = st.voxel > 0.f, has_stat = st.stat_neighbors > 0, has_radius = st.radius > 0.f, has_cluster = st.cluster_radius > 0.f;
-	if (!has_voxel && !has_stat && !has_radius && !has_cluster) {
+	const bool has_plane = st.plane_distance > 0.f;
+	PlaneSelect plane_sel;
+	if (has_plane) plane_sel = plane_check_select(st.plane_distance, st.plane_iterations, st.plane_refine, st.plane_max, st.plane_min_inliers, st.plane_seed);
+	if (!has_voxel && !has_stat && !has_radius && !has_plane && !has_cluster) {
 		set_source(xyz, n, fn);
 		if (n_kept) *n_kept = n;
 		return;
@@ -920,6 +971,7 @@ void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const
 	if (has_voxel) voxel_frame(xyz, n, st.voxel, &f);
 	else if (has_stat) stat_check_cloud(xyz, n, mn, mx);
 	else if (has_radius) radius_frame(xyz, n, st.radius, st.min_neighbors, &f);
+	else if (has_plane) plane_check_cloud(xyz, n);
 	else cluster_frame(xyz, n, st.cluster_radius, st.cluster_min_neighbors, &f);
 	if (has_stat) stat_check_params(has_voxel ? 65 : n, st.stat_neighbors, st.stat_std_ratio);   // behind the grid: the range of k and the ratio alone
 	if (has_radius) radius_check_params(st.radius, st.min_neighbors);
@@ -931,9 +983,9 @@ void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const
 	sync_lane_streams();
 	// the raw cloud goes up once; each stage reads the one before it on the device; the final cloud comes back for the host mirror
 	const Buf<float> d_raw = upload_cloud(xyz, n, stream_);
-	Buf<float> d_voxel, d_stat, d_radius, d_cluster;
+	Buf<float> d_voxel, d_stat, d_radius, d_plane, d_cluster;
 	const float* d_in = d_raw;
-	int n_in = (int)n, m = 0, n_clusters = 0;
+	int n_in = (int)n, m = 0, n_clusters = 0, n_planes = 0;
 	bool first = true;                                          // d_in is still the raw cloud, which the host has seen
 	float ms = 0.f;
 	std::string counts = std::to_string(n), times;              // of the verbose line
@@ -989,6 +1041,13 @@ void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const
 		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
 		ran("outlier", d_radius);
 	}
+	if (has_plane) {
+		PlaneRecord planes[kPlaneMaxPlanes];
+		d_plane.alloc(3 * (size_t)n_in);
+		HIPCHK(launch_segment_plane(d_in, n_in, plane_sel, nullptr, d_plane, nullptr, planes, &n_planes, &m, stream_, ev0_, ev1_));
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		ran("plane", d_plane);
+	}
 	if (has_cluster) {
 		if (!first) {
 			bounds();
@@ -1007,6 +1066,7 @@ void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const
 	finish_source_swap();
 	if (n_kept) *n_kept = N_;
 	if (p_.verbose) {
+		if (has_plane) counts += " (" + std::to_string(n_planes) + " planes removed)";
 		if (has_cluster) counts += " points of " + std::to_string(n_clusters) + " clusters";
 		else counts += " points";
 		std::fprintf(stderr, "[goicp] %s: %s, %.2f ms (%sdevice order %.3f ms)\n", fn + 6, counts.c_str(), now_ms() - t0, times.c_str(),

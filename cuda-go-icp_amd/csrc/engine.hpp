@@ -301,7 +301,7 @@ public:
 	// entry point the caller used, which the refusals, the trace range and the verbose line name
 	void set_source(const float* source_xyz, size_t N, const char* fn = "goicp_set_source");
 	// goicp_set_source_voxel / _filtered / _pipeline / _clustered: one chain, of which each entry point can switch on its share of the stages
-	// voxel grid -> statistical filter -> radius filter -> cluster selection (a stage whose size is 0 is off; with none on it is
+	// voxel grid -> statistical filter -> radius filter -> plane removal -> cluster selection (a stage whose size is 0 is off; with none on it is
 	// set_source).  The raw cloud goes up once, each stage reads the one before it on the device, only the final cloud and the permutation
 	// come back; afterwards the engine is the one set_source(the composition of the host functions) leaves.  What the arguments and the raw
 	// cloud show is refused before any device work (the first stage that runs checks the raw cloud on the host and takes its frame from
@@ -315,6 +315,10 @@ public:
 		int32_t min_neighbors = 0;
 		float cluster_radius = 0.f;
 		int32_t cluster_min_neighbors = 0, cluster_min_size = 0, cluster_max_clusters = 0;
+		// plane removal (between the radius and the cluster stage): plane_distance == 0 is no stage; the fields of goicp_plane_select
+		float plane_distance = 0.f;
+		int32_t plane_iterations = 0, plane_refine = 0, plane_max = 0, plane_min_inliers = 0;
+		uint64_t plane_seed = 0;
 	};
 	void set_source_staged(const char* fn, const float* xyz, size_t n, const SourceStages& st, size_t* n_kept);
 	// goicp_debug_source_order (test): the device ordering alone, of any cloud
@@ -340,6 +344,10 @@ public:
 	void cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
 	void cluster_filter(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t min_size, int32_t max_clusters, float* out_xyz,
 	                    int32_t* out_index, int32_t* out_label, size_t* m);
+	// goicp_segment_plane / goicp_plane_filter: RANSAC plane segmentation on the device (kdbuild.hip launch_segment_plane; the refit's finish
+	// runs on the host over 16 integer words); the engine lends its device and stream and nothing else.  s: the checked selection
+	void segment_plane(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, PlaneRecord* out_planes, size_t* n_planes);
+	void plane_filter(const float* xyz, size_t n, const PlaneSelect& s, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes, size_t* n_planes, size_t* m);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -627,6 +635,13 @@ void radius_outlier_removal_host(const float* xyz, size_t n, float radius, int32
 // min_neighbors == 0 legal and a negative one refused; cluster_check_select refuses a negative min_size or max_clusters; cluster_select is
 // the selection over the c sizes that both paths share (keep[l] = 1 or 0).  cluster_host / cluster_filter_host are goicp_cluster_host /
 // goicp_cluster_filter_host
+// RANSAC plane segmentation (kdtree.cpp).  plane_check_cloud refuses an empty, too large or non-finite cloud; plane_check_select
+// what goicp_segment_plane refuses of the parameters, and returns them with the defaults filled in.  segment_plane_host is
+// goicp_segment_plane_host and goicp_plane_filter_host in one: every output may be null
+void plane_check_cloud(const float* xyz, size_t n);
+PlaneSelect plane_check_select(float distance, int32_t iterations, int32_t refine, int32_t max_planes, int32_t min_inliers, uint64_t seed);
+void segment_plane_host(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes,
+                        size_t* n_planes, size_t* m);
 void cluster_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void cluster_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void cluster_check_select(int32_t min_size, int32_t max_clusters);

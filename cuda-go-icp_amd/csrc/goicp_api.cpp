@@ -337,6 +337,83 @@ int goicp_set_source_clustered(goicp_handle h, const float* xyz, size_t n, const
 	return guarded([&] { h->e->set_source_staged("goicp_set_source_clustered", xyz, n, st, n_kept); });
 }
 
+void goicp_plane_select_default(goicp_plane_select* out)
+{
+	if (!out) return;
+	out->distance = 0.f;
+	out->iterations = 0;
+	out->refine = 0;
+	out->max_planes = 0;
+	out->min_inliers = 0;
+	out->seed = 0;
+}
+
+static_assert(sizeof(goicp_plane) == sizeof(goicp::PlaneRecord) && sizeof(goicp_plane) == 40, "goicp_plane is PlaneRecord, field for field");
+static goicp::PlaneRecord* records(goicp_plane* p) { return reinterpret_cast<goicp::PlaneRecord*>(p); }
+static goicp::PlaneSelect checked(const goicp_plane_select& s)
+{
+	return goicp::plane_check_select(s.distance, s.iterations, s.refine, s.max_planes, s.min_inliers, s.seed);
+}
+
+int goicp_segment_plane_host(const float* xyz, size_t n, const goicp_plane_select* sel, int32_t* out_label, goicp_plane* out_planes, size_t* n_planes)
+{
+	REQUIRE(xyz && sel && out_label && out_planes && n_planes && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] {
+		const goicp::PlaneSelect s = checked(*sel);
+		goicp::plane_check_cloud(xyz, n);
+		goicp::segment_plane_host(xyz, n, s, out_label, nullptr, nullptr, records(out_planes), n_planes, nullptr);
+	});
+}
+
+int goicp_segment_plane(goicp_handle h, const float* xyz, size_t n, const goicp_plane_select* sel, int32_t* out_label, goicp_plane* out_planes, size_t* n_planes)
+{
+	REQUIRE(h && xyz && sel && out_label && out_planes && n_planes && n > 0);
+	return guarded([&] { h->e->segment_plane(xyz, n, checked(*sel), out_label, records(out_planes), n_planes); });
+}
+
+int goicp_plane_filter_host(const float* xyz, size_t n, const goicp_plane_select* sel, float* out_xyz, int32_t* out_index, goicp_plane* out_planes,
+                            size_t* n_planes, size_t* m)
+{
+	REQUIRE(xyz && sel && out_xyz && m && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] {
+		const goicp::PlaneSelect s = checked(*sel);
+		goicp::plane_check_cloud(xyz, n);
+		goicp::segment_plane_host(xyz, n, s, nullptr, out_xyz, out_index, records(out_planes), n_planes, m);
+	});
+}
+
+int goicp_plane_filter(goicp_handle h, const float* xyz, size_t n, const goicp_plane_select* sel, float* out_xyz, int32_t* out_index, goicp_plane* out_planes,
+                       size_t* n_planes, size_t* m)
+{
+	REQUIRE(h && xyz && sel && out_xyz && m && n > 0);
+	return guarded([&] { h->e->plane_filter(xyz, n, checked(*sel), out_xyz, out_index, records(out_planes), n_planes, m); });
+}
+
+int goicp_set_source_segmented(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_plane_select* pl,
+                               const goicp_cluster_select* s, size_t* n_kept)
+{
+	REQUIRE(h && xyz && n > 0);
+	goicp::Engine::SourceStages st;
+	if (p) st = stages_of(*p);
+	if (pl) {
+		st.plane_distance = pl->distance;
+		st.plane_iterations = pl->iterations;
+		st.plane_refine = pl->refine;
+		st.plane_max = pl->max_planes;
+		st.plane_min_inliers = pl->min_inliers;
+		st.plane_seed = pl->seed;
+	}
+	if (s) {
+		st.cluster_radius = s->radius;
+		st.cluster_min_neighbors = s->min_neighbors;
+		st.cluster_min_size = s->min_size;
+		st.cluster_max_clusters = s->max_clusters;
+	}
+	return guarded([&] { h->e->set_source_staged("goicp_set_source_segmented", xyz, n, st, n_kept); });
+}
+
 int goicp_knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq)
 {
 	REQUIRE(xyz && out_index && n > 0);

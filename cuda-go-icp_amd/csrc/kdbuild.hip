@@ -1474,4 +1474,259 @@ hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[
 	return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------------------
+// RANSAC plane segmentation on the device (host twin: segment_plane_host, kdtree.cpp).  A round is: the hypothesis kernel (one
+// thread per hypothesis: the draw and the fp64 plane, device.hpp's text), the score kernel (all points x all hypotheses, integer counts),
+// the argmax over (count << 32) | ~t, 8 + 32 bytes to the host; with refine the integer-moment kernel, 128 bytes to the host, plane_refit
+// there, the score kernel once more on the one refit plane; then the label kernel and the filters' scan and compaction (compact_tail),
+// which form the next round's cloud and carry the index map.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPlBlock = 256;                                  // threads of a score workgroup: 4 waves
+constexpr int kPlPts = 4;                                      // points a lane keeps in registers: 1 024 per workgroup
+constexpr int kPlTile = 256;                                   // hypotheses of a workgroup's LDS tile (8 KB of planes + 1 KB of counts)
+static_assert(kPlTile == kPlBlock && kPlTile % 64 == 0, "one thread loads one hypothesis of the tile; a wave keeps 64 counts at a time");
+
+// hyp[2 t] = (anchor, 0), hyp[2 t + 1] = (normal, 0) of hypothesis t of the round that starts at number `first`; a degenerate hypothesis gets a
+// NaN normal, against which no point is an inlier: it scores 0
+__global__ void pl_hyp_kernel(const float* __restrict__ xyz, int n, unsigned long long seed, unsigned long long first, int T, float4* __restrict__ hyp)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= T) return;
+	uint32_t a, b, c;
+	plane::draw(seed, first + (unsigned long long)t, (uint32_t)n, &a, &b, &c);
+	const float pa[3] = {xyz[3 * (size_t)a], xyz[3 * (size_t)a + 1], xyz[3 * (size_t)a + 2]};
+	const float pb[3] = {xyz[3 * (size_t)b], xyz[3 * (size_t)b + 1], xyz[3 * (size_t)b + 2]};
+	const float pc[3] = {xyz[3 * (size_t)c], xyz[3 * (size_t)c + 1], xyz[3 * (size_t)c + 2]};
+	float nr[3];
+	const float nan = __int_as_float(0x7fc00000);
+	if (!plane::of_triple(pa, pb, pc, nr)) nr[0] = nr[1] = nr[2] = nan;
+	hyp[2 * (size_t)t] = make_float4(pa[0], pa[1], pa[2], 0.f);
+	hyp[2 * (size_t)t + 1] = make_float4(nr[0], nr[1], nr[2], 0.f);
+}
+
+// Workgroup (bx, by): the 1 024 points from bx * 1 024 against the hypotheses by * kPlTile ...  A lane keeps kPlPts points in registers (a
+// point past the end is NaN: never an inlier); the tile's planes sit in LDS and are read wave-uniformly; per hypothesis and point the nine
+// float operations of the pair, a ballot and a popcount of its 64-bit mask.  The wave's count of hypothesis j0 + jj stays with lane jj, so
+// LDS sees one atomic per lane per 64 hypotheses, and global memory one atomic per hypothesis per workgroup
+__global__ void __launch_bounds__(kPlBlock) pl_score_kernel(const float* __restrict__ xyz, int n, const float4* __restrict__ hyp, int T, float dist,
+                                                            unsigned* __restrict__ counts)
+{
+	__shared__ float4 s_a[kPlTile], s_n[kPlTile];
+	__shared__ unsigned s_cnt[kPlTile];
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int t0 = blockIdx.y * kPlTile;
+	const float nan = __int_as_float(0x7fc00000);
+	{
+		const int t = t0 + tid;
+		s_a[tid] = t < T ? hyp[2 * (size_t)t] : make_float4(0.f, 0.f, 0.f, 0.f);
+		s_n[tid] = t < T ? hyp[2 * (size_t)t + 1] : make_float4(nan, nan, nan, 0.f);
+		s_cnt[tid] = 0u;
+	}
+	float px[kPlPts], py[kPlPts], pz[kPlPts];
+	const size_t base = (size_t)blockIdx.x * (size_t)(kPlBlock * kPlPts);
+#pragma unroll
+	for (int k = 0; k < kPlPts; k++) {
+		const size_t i = base + (size_t)(k * kPlBlock + tid);
+		const bool valid = i < (size_t)n;
+		px[k] = valid ? xyz[3 * i] : nan; py[k] = valid ? xyz[3 * i + 1] : nan; pz[k] = valid ? xyz[3 * i + 2] : nan;
+	}
+	__syncthreads();
+	const int live = min(kPlTile, T - t0);                      // the tile's hypotheses that exist; the others have NaN normals
+	for (int j0 = 0; j0 < live; j0 += 64) {
+		unsigned mine = 0u;
+		const int jn = min(64, live - j0);                      // wave-uniform; a lane past it keeps 0 (the refit's re-score has one plane)
+		for (int jj = 0; jj < jn; jj++) {
+			const float4 a = s_a[j0 + jj], nr = s_n[j0 + jj];
+			unsigned c = 0u;
+#pragma unroll
+			for (int k = 0; k < kPlPts; k++)
+				c += (unsigned)__popcll(__ballot(plane::inlier(px[k], py[k], pz[k], a.x, a.y, a.z, nr.x, nr.y, nr.z, dist)));
+			mine = lane == jj ? c : mine;
+		}
+		if (mine) atomicAdd(&s_cnt[j0 + lane], mine);
+	}
+	__syncthreads();
+	if (t0 + tid < T && s_cnt[tid]) atomicAdd(&counts[t0 + tid], s_cnt[tid]);
+}
+
+// one workgroup: the largest key (count << 32) | ~t, so the largest count and among equals the smallest t
+__global__ void __launch_bounds__(256) pl_argmax_kernel(const unsigned* __restrict__ counts, int T, unsigned long long* __restrict__ best)
+{
+	__shared__ unsigned long long s_best[4];
+	unsigned long long k = 0ull;
+	for (int t = threadIdx.x; t < T; t += 256) {
+		const unsigned long long key = ((unsigned long long)counts[t] << 32) | (unsigned long long)(~(unsigned)t);
+		k = key > k ? key : k;
+	}
+	for (int off = 32; off; off >>= 1) {
+		const unsigned long long o = shfl_xor64(k, off);
+		k = o > k ? o : k;
+	}
+	if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = k;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (int w = 1; w < 4; w++) k = s_best[w] > k ? s_best[w] : k;
+		*best = k;
+	}
+}
+
+// the refit's 16 integer words over the inliers of the plane (a, nr): one thread per point, wave-level sums, then 64-bit atomics (the voxel
+// operator's style).  q = llrint(ldexp(x - mn, sh)) < 2^31, so a product has 62 bits and every word of fewer than 2^28 points stays below 2^60
+__global__ void __launch_bounds__(256) pl_moment_kernel(const float* __restrict__ xyz, int n, float4 a, float4 nr, float dist, float mnx, float mny, float mnz,
+                                                        int sh, unsigned long long* __restrict__ words)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	unsigned long long w[kPlaneWords];
+#pragma unroll
+	for (int k = 0; k < kPlaneWords; k++) w[k] = 0ull;
+	if (i < n) {
+		const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+		if (plane::inlier(x, y, z, a.x, a.y, a.z, nr.x, nr.y, nr.z, dist)) {
+			const unsigned long long q0 = (unsigned long long)llrint(ldexp((double)(x - mnx), sh)), q1 = (unsigned long long)llrint(ldexp((double)(y - mny), sh)),
+			                         q2 = (unsigned long long)llrint(ldexp((double)(z - mnz), sh));
+			const unsigned long long p[6] = {q0 * q0, q0 * q1, q0 * q2, q1 * q1, q1 * q2, q2 * q2};
+			w[0] = 1ull; w[1] = q0; w[2] = q1; w[3] = q2;
+#pragma unroll
+			for (int k = 0; k < 6; k++) { w[4 + k] = p[k] >> 32; w[10 + k] = p[k] & 0xffffffffull; }
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < kPlaneWords; k++)
+		for (int off = 32; off; off >>= 1) w[k] += shfl_xor64(w[k], off);
+	if ((threadIdx.x & 63) == 0 && w[0]) {
+#pragma unroll
+		for (int k = 0; k < kPlaneWords; k++) atomicAdd(words + k, w[k]);
+	}
+}
+
+// the inliers of the final plane of round `p` get its label (through the index map; null = identity), the others the keep flag
+__global__ void pl_label_kernel(const float* __restrict__ xyz, int n, float4 a, float4 nr, float dist, const int* __restrict__ map, int p,
+                                int32_t* __restrict__ label, int* __restrict__ flag)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const bool in = plane::inlier(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], a.x, a.y, a.z, nr.x, nr.y, nr.z, dist);
+	if (in && label) label[map ? map[i] : i] = p;
+	flag[i] = in ? 0 : 1;
+}
+
+hipError_t launch_segment_plane(const float* d_xyz, int n, const PlaneSelect& s, int32_t* d_label, float* d_out, int32_t* d_index, PlaneRecord* planes,
+                                int* n_planes, int* m_out, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n <= 0 || !planes || !n_planes || !m_out || (d_index && !d_out)) return hipErrorInvalidValue;
+	if (s.iterations < 1 || s.iterations > kPlaneMaxIterations || s.max_planes < 1 || s.max_planes > kPlaneMaxPlanes) return hipErrorInvalidValue;
+	const int T = s.iterations;
+	const size_t N = (size_t)n;
+	float *buf[2] = {nullptr, nullptr};
+	int *mapbuf[2] = {nullptr, nullptr}, *flag = nullptr, *scan = nullptr;
+	float4* hyp = nullptr;
+	unsigned* counts = nullptr;
+	unsigned long long* small = nullptr;                         // [0] the best key, [1..16] the moment words
+	void* tmp = nullptr;
+	Temps t;
+	KD_TRY(t.get(flag, N + 1));
+	KD_TRY(t.get(hyp, 2 * (size_t)T));
+	KD_TRY(t.get(counts, (size_t)T));
+	KD_TRY(t.get(small, 1 + kPlaneWords));
+	size_t scan_bytes = 0;
+	if (d_out || s.max_planes > 1) {
+		// a next cloud is formed; a labels-only call of one round never compacts and needs none of this
+		KD_TRY(t.get(buf[0], 3 * N)); KD_TRY(t.get(buf[1], 3 * N));
+		KD_TRY(t.get(mapbuf[0], N)); KD_TRY(t.get(mapbuf[1], N));
+		KD_TRY(t.get(scan, N + 1));
+		KD_TRY(compact_scan_bytes(flag, scan, N, scan_bytes, stream));
+		KD_TRY(t.get_bytes(tmp, std::max<size_t>(scan_bytes, 16)));
+	}
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	if (d_label) KD_TRY(hipMemsetAsync(d_label, 0xff, sizeof(int32_t) * N, stream));
+	const float* cur = d_xyz;
+	const int* map = nullptr;                                    // the original index of every point of cur; null: the identity
+	int np = n, found = 0, side = 0;
+	const dim3 blk(256);
+	auto score = [&](const float4* h, int count, unsigned* out) {
+		hipLaunchKernelGGL(pl_score_kernel, dim3((unsigned)((np + kPlBlock * kPlPts - 1) / (kPlBlock * kPlPts)), (unsigned)((count + kPlTile - 1) / kPlTile)),
+		                   dim3(kPlBlock), 0, stream, cur, np, h, count, s.distance, out);
+		return hipGetLastError();
+	};
+	for (int p = 0; p < s.max_planes && np >= 3; p++) {
+		KD_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned) * (size_t)T, stream));
+		hipLaunchKernelGGL(pl_hyp_kernel, dim3((T + 255) / 256), blk, 0, stream, cur, np, (unsigned long long)s.seed,
+		                   (unsigned long long)p * (unsigned long long)T, T, hyp);
+		KD_TRY(hipGetLastError());
+		KD_TRY(score(hyp, T, counts));
+		hipLaunchKernelGGL(pl_argmax_kernel, dim3(1), blk, 0, stream, counts, T, small);
+		KD_TRY(hipGetLastError());
+		unsigned long long key = 0ull;
+		KD_TRY(hipMemcpyAsync(&key, small, sizeof(key), hipMemcpyDeviceToHost, stream));
+		KD_TRY(hipStreamSynchronize(stream));
+		const int best_count = (int)(key >> 32), best = (int)(~(unsigned)(key & 0xffffffffull));
+		if (best < 0 || best >= T || best_count > np) return hipErrorUnknown;
+		if (best_count < std::max(s.min_inliers, 3)) break;
+		float4 h[2];
+		KD_TRY(hipMemcpyAsync(h, hyp + 2 * (size_t)best, sizeof(h), hipMemcpyDeviceToHost, stream));
+		KD_TRY(hipStreamSynchronize(stream));
+		PlaneRecord rec;
+		rec.normal[0] = h[1].x; rec.normal[1] = h[1].y; rec.normal[2] = h[1].z;
+		rec.point[0] = h[0].x; rec.point[1] = h[0].y; rec.point[2] = h[0].z;
+		rec.inliers = best_count;
+		rec.hypothesis = best;
+		rec.refined = 0;
+		if (s.refine) {
+			float mn[3], mx[3], E = 0.f;
+			KD_TRY(launch_cloud_minmax(cur, np, mn, mx, stream));
+			for (int k = 0; k < 3; k++) E = std::max(E, mx[k] - mn[k]);
+			int e = 0;
+			std::frexp(E, &e);
+			KD_TRY(hipMemsetAsync(small + 1, 0, sizeof(unsigned long long) * kPlaneWords, stream));
+			hipLaunchKernelGGL(pl_moment_kernel, dim3((np + 255) / 256), blk, 0, stream, cur, np, h[0], h[1], s.distance, mn[0], mn[1], mn[2], 31 - e, small + 1);
+			KD_TRY(hipGetLastError());
+			unsigned long long w[kPlaneWords];
+			KD_TRY(hipMemcpyAsync(w, small + 1, sizeof(w), hipMemcpyDeviceToHost, stream));
+			KD_TRY(hipStreamSynchronize(stream));
+			float rn[3], rp[3];
+			if (plane_refit(w, mn, e, rn, rp)) {
+				// the refit plane takes the place of hypothesis 0 (the round's hypotheses are done with) and is scored by the same kernel
+				const float4 r[2] = {make_float4(rp[0], rp[1], rp[2], 0.f), make_float4(rn[0], rn[1], rn[2], 0.f)};
+				unsigned cnt = 0u;
+				KD_TRY(hipMemcpyAsync(hyp, r, sizeof(r), hipMemcpyHostToDevice, stream));
+				KD_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned), stream));
+				KD_TRY(score(hyp, 1, counts));
+				KD_TRY(hipMemcpyAsync(&cnt, counts, sizeof(cnt), hipMemcpyDeviceToHost, stream));
+				KD_TRY(hipStreamSynchronize(stream));
+				if (cnt > (unsigned)np) return hipErrorUnknown;
+				if ((int)cnt >= rec.inliers) {
+					for (int k = 0; k < 3; k++) { rec.normal[k] = rn[k]; rec.point[k] = rp[k]; }
+					rec.inliers = (int)cnt;
+					rec.refined = 1;
+					h[0] = r[0]; h[1] = r[1];
+				}
+			}
+		}
+		rec.d = plane::offset(rec.normal, rec.point);
+		planes[found] = rec;
+		hipLaunchKernelGGL(pl_label_kernel, dim3((np + 255) / 256), blk, 0, stream, cur, np, h[0], h[1], s.distance, map, found, d_label, flag);
+		KD_TRY(hipGetLastError());
+		found++;
+		if (!d_out && p + 1 == s.max_planes) { np -= rec.inliers; break; }      // only labels are wanted and no round follows: no next cloud
+		// the next round's cloud and its index map: round 0 writes the positions themselves, the later rounds carry the map as the label column
+		int m = -1;
+		KD_TRY(compact_tail(cur, np, flag, scan, tmp, scan_bytes, map, buf[side], map ? nullptr : mapbuf[side], map ? mapbuf[side] : nullptr, &m, stream));
+		KD_TRY(hipStreamSynchronize(stream));
+		if (m != np - rec.inliers) return hipErrorUnknown;
+		cur = buf[side]; map = mapbuf[side]; np = m;
+		side ^= 1;
+	}
+	if (d_out && np > 0) {
+		KD_TRY(hipMemcpyAsync(d_out, cur, sizeof(float) * 3 * (size_t)np, hipMemcpyDeviceToDevice, stream));
+		if (d_index) {
+			if (map) KD_TRY(hipMemcpyAsync(d_index, map, sizeof(int) * (size_t)np, hipMemcpyDeviceToDevice, stream));
+			else hipLaunchKernelGGL(so_iota_kernel, dim3((np + 255) / 256), blk, 0, stream, d_index, np);
+			KD_TRY(hipGetLastError());
+		}
+	}
+	*n_planes = found;
+	*m_out = np;
+	return end_and_drain(ev_end, stream);
+}
+
 }  // namespace goicp

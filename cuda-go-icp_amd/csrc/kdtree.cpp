@@ -941,4 +941,169 @@ void estimate_normals_host(const float* xyz, size_t n, int32_t k, const float* v
 	});
 }
 
+// ---- RANSAC plane segmentation: what both paths share, and the host path ----
+void plane_check_cloud(const float* xyz, size_t n)
+{
+	if (!xyz || n == 0) throw std::invalid_argument("goicp plane: empty cloud");
+	if (n > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp plane: cloud too large");
+	for (size_t i = 0; i < 3 * n; i++)
+		if (!std::isfinite(xyz[i])) throw std::invalid_argument("goicp plane: non-finite coordinate in the cloud");
+}
+
+PlaneSelect plane_check_select(float distance, int32_t iterations, int32_t refine, int32_t max_planes, int32_t min_inliers, uint64_t seed)
+{
+	if (!(distance > 0.f) || !std::isfinite(distance)) throw std::invalid_argument("goicp plane: the distance must be positive and finite");
+	if (iterations < 0 || iterations > kPlaneMaxIterations) throw std::invalid_argument("goicp plane: iterations must be in 0..65536 (0 = 1000)");
+	if (refine < 0 || refine > 1) throw std::invalid_argument("goicp plane: refine must be 0 or 1");
+	if (max_planes < 0 || max_planes > kPlaneMaxPlanes) throw std::invalid_argument("goicp plane: max_planes must be in 0..8 (0 = 1)");
+	if (min_inliers < 0) throw std::invalid_argument("goicp plane: min_inliers must not be negative");
+	PlaneSelect s;
+	s.distance = distance;
+	s.iterations = iterations ? iterations : kPlaneDefaultIterations;
+	s.refine = refine;
+	s.max_planes = max_planes ? max_planes : 1;
+	s.min_inliers = min_inliers;
+	s.seed = seed;
+	return s;
+}
+
+bool plane_refit(const unsigned long long words[kPlaneWords], const float mn[3], int e, float normal[3], float point[3])
+{
+	using namespace pca;
+	const int sh = 31 - e;
+	const unsigned long long m = words[0];
+	if (m == 0) return false;
+	const double md = (double)m, mm = md * md;
+	// C_ab = (m P_ab - S_a S_b) 2^(-2 sh) / m^2, the integer formed exactly and rounded once
+	static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {0, 1, 2, 1, 2, 2};
+	double c[6];
+	for (int k = 0; k < 6; k++) {
+		const __int128 P = (__int128)(((unsigned __int128)words[4 + k] << 32) + (unsigned __int128)words[10 + k]);
+		const __int128 v = (__int128)m * P - (__int128)words[1 + pa[k]] * (__int128)words[1 + pb[k]];
+		c[k] = std::ldexp((double)v, -2 * sh) / mm;
+	}
+	double A[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}};
+	double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+	for (int sweep = 0; sweep < kMaxSweeps; sweep++) {
+		const bool r01 = rotate<0, 1>(A, V), r02 = rotate<0, 2>(A, V), r12 = rotate<1, 2>(A, V);
+		if (!(r01 || r02 || r12)) break;
+	}
+	const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+	const int s1 = l1 < l0 ? 1 : 0;
+	const int col = l2 < (s1 ? l1 : l0) ? 2 : s1;              // the smallest l, the lowest index on equal values
+	const double v0 = V[0][col], v1 = V[1][col], v2 = V[2][col];
+	const double len = root(add(add(mul(v0, v0), mul(v1, v1)), mul(v2, v2)));
+	normal[0] = (float)div(v0, len); normal[1] = (float)div(v1, len); normal[2] = (float)div(v2, len);
+	if (!plane::finite3(normal) || (normal[0] == 0.f && normal[1] == 0.f && normal[2] == 0.f)) return false;
+	plane::sign(normal);
+	for (int k = 0; k < 3; k++) point[k] = (float)((double)mn[k] + std::ldexp((double)words[1 + k] / md, -sh));
+	return true;
+}
+
+namespace {
+
+struct PlaneHyp { float a[3], n[3]; bool ok; };
+
+// the count of one plane over a cloud
+int32_t plane_count(const float* xyz, size_t n, const float a[3], const float nr[3], float distance)
+{
+	int32_t cnt = 0;
+	for (size_t i = 0; i < n; i++) cnt += plane::inlier(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], a[0], a[1], a[2], nr[0], nr[1], nr[2], distance) ? 1 : 0;
+	return cnt;
+}
+
+}  // namespace
+
+// the rounds of the header, on the remaining cloud `cur` (input order) with its index map; threads over blocks of hypotheses (integer counts)
+void segment_plane_host(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes,
+                        size_t* n_planes, size_t* m_out)
+{
+	std::vector<float> cur(xyz, xyz + 3 * n), nxt;
+	std::vector<int32_t> map(n), nmap, label(n, -1);
+	std::iota(map.begin(), map.end(), 0);
+	const int T = s.iterations;
+	std::vector<int32_t> counts((size_t)T);
+	size_t found = 0;
+	for (int p = 0; p < s.max_planes; p++) {
+		const size_t np = cur.size() / 3;
+		if (np < 3) break;
+		const int chunk = 16, chunks = (T + chunk - 1) / chunk;
+		parallel_tasks((uint64_t)np * (uint64_t)T >= (1ull << 20) ? 8 : 1, chunks, [&](int ch) {
+			for (int t = ch * chunk; t < std::min(T, (ch + 1) * chunk); t++) {
+				uint32_t a, b, c;
+				float nr[3];
+				plane::draw(s.seed, (uint64_t)p * (uint64_t)T + (uint64_t)t, (uint32_t)np, &a, &b, &c);
+				const bool ok = plane::of_triple(&cur[3 * (size_t)a], &cur[3 * (size_t)b], &cur[3 * (size_t)c], nr);
+				counts[(size_t)t] = ok ? plane_count(cur.data(), np, &cur[3 * (size_t)a], nr, s.distance) : 0;
+			}
+		});
+		int best = 0;
+		for (int t = 1; t < T; t++) if (counts[(size_t)t] > counts[(size_t)best]) best = t;   // ties: the smallest t
+		if (counts[(size_t)best] < std::max(s.min_inliers, 3)) break;
+		PlaneRecord rec;
+		{
+			uint32_t a, b, c;
+			plane::draw(s.seed, (uint64_t)p * (uint64_t)T + (uint64_t)best, (uint32_t)np, &a, &b, &c);
+			plane::of_triple(&cur[3 * (size_t)a], &cur[3 * (size_t)b], &cur[3 * (size_t)c], rec.normal);
+			for (int k = 0; k < 3; k++) rec.point[k] = cur[3 * (size_t)a + k];
+		}
+		rec.inliers = counts[(size_t)best];
+		rec.hypothesis = best;
+		rec.refined = 0;
+		if (s.refine) {
+			float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY}, E = 0.f;
+			for (size_t i = 0; i < np; i++)
+				for (int k = 0; k < 3; k++) { mn[k] = std::min(mn[k], cur[3 * i + k]); mx[k] = std::max(mx[k], cur[3 * i + k]); }
+			for (int k = 0; k < 3; k++) E = std::max(E, mx[k] - mn[k]);   // rounding is monotone: the largest offset is an axis' maximum's
+			int e = 0;
+			std::frexp(E, &e);
+			unsigned long long w[kPlaneWords] = {};
+			for (size_t i = 0; i < np; i++) {
+				const float* x = &cur[3 * i];
+				if (!plane::inlier(x[0], x[1], x[2], rec.point[0], rec.point[1], rec.point[2], rec.normal[0], rec.normal[1], rec.normal[2], s.distance)) continue;
+				unsigned long long q[3];
+				for (int k = 0; k < 3; k++) q[k] = (unsigned long long)std::llrint(std::ldexp((double)(x[k] - mn[k]), 31 - e));
+				w[0]++;
+				int j = 0;
+				for (int ka = 0; ka < 3; ka++) {
+					w[1 + ka] += q[ka];
+					for (int kb = ka; kb < 3; kb++, j++) {
+						const unsigned long long prod = q[ka] * q[kb];
+						w[4 + j] += prod >> 32;
+						w[10 + j] += prod & 0xffffffffull;
+					}
+				}
+			}
+			float rn[3], rp[3];
+			if (plane_refit(w, mn, e, rn, rp)) {
+				const int32_t cnt = plane_count(cur.data(), np, rp, rn, s.distance);
+				if (cnt >= rec.inliers) {
+					for (int k = 0; k < 3; k++) { rec.normal[k] = rn[k]; rec.point[k] = rp[k]; }
+					rec.inliers = cnt;
+					rec.refined = 1;
+				}
+			}
+		}
+		rec.d = plane::offset(rec.normal, rec.point);
+		if (out_planes) out_planes[found] = rec;
+		nxt.clear(); nmap.clear();
+		for (size_t i = 0; i < np; i++) {
+			const float* x = &cur[3 * i];
+			if (plane::inlier(x[0], x[1], x[2], rec.point[0], rec.point[1], rec.point[2], rec.normal[0], rec.normal[1], rec.normal[2], s.distance)) {
+				label[(size_t)map[i]] = (int32_t)found;
+			} else {
+				nxt.insert(nxt.end(), x, x + 3);
+				nmap.push_back(map[i]);
+			}
+		}
+		cur.swap(nxt); map.swap(nmap);
+		found++;
+	}
+	if (out_label) std::memcpy(out_label, label.data(), sizeof(int32_t) * n);
+	if (out_xyz && !cur.empty()) std::memcpy(out_xyz, cur.data(), sizeof(float) * cur.size());
+	if (out_index && !map.empty()) std::memcpy(out_index, map.data(), sizeof(int32_t) * map.size());
+	if (n_planes) *n_planes = found;
+	if (m_out) *m_out = map.size();
+}
+
 }  // namespace goicp

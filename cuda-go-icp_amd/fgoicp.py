@@ -175,14 +175,56 @@ def cluster_filter(xyz, radius, min_neighbors=0, min_size=0, keep=0):
     return _cluster_filter_call(B.load_library().goicp_cluster_filter_host, xyz, radius, min_neighbors, min_size, keep)
 
 
-def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None, cluster=None):
-    """the composition of the host functions that goicp_set_source_filtered, goicp_set_source_pipeline and goicp_set_source_clustered equal"""
+# goicp_plane, field for field: the planes come back as a structured array
+PLANE_DTYPE = np.dtype([("normal", "<f4", (3,)), ("point", "<f4", (3,)), ("d", "<f4"), ("inliers", "<i4"), ("hypothesis", "<i4"), ("refined", "<i4")])
+
+
+def _plane_select(distance, iterations, refine, max_planes, min_inliers, seed):
+    return B.CPlaneSelect(float(distance), int(iterations), int(refine), int(max_planes), int(min_inliers), int(seed) & (2 ** 64 - 1))
+
+
+def _segment_plane_call(fn, xyz, sel):
+    xyz = _f32(xyz, (-1, 3))
+    n = len(xyz)
+    label, planes, c = np.empty(n, np.int32), np.zeros(B.PLANE_MAX_PLANES, PLANE_DTYPE), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), n, C.byref(sel), label.ctypes.data_as(C.POINTER(C.c_int32)), planes.ctypes.data_as(C.POINTER(B.CPlane)), C.byref(c)))
+    return label, planes[:c.value].copy()
+
+
+def segment_plane(xyz, distance, iterations=1000, refine=1, max_planes=1, min_inliers=0, seed=0):
+    """goicp_segment_plane_host (host only): RANSAC over `iterations` three-point hypotheses per round, up to `max_planes` rounds, each on
+    the points no earlier plane took; a point within `distance` of a plane is its inlier; refine = 1 refits the best hypothesis by least
+    squares over its inliers -> (labels (n,) int32, -1 = no plane, planes (c,) PLANE_DTYPE: normal, point, d of normal . x + d = 0, inliers,
+    hypothesis, refined).  Registration.segment_plane gives the same bits on the device."""
+    return _segment_plane_call(B.load_library().goicp_segment_plane_host, xyz, _plane_select(distance, iterations, refine, max_planes, min_inliers, seed))
+
+
+def _plane_filter_call(fn, xyz, sel):
+    xyz = _f32(xyz, (-1, 3))
+    n = len(xyz)
+    out, idx, planes, c, m = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.zeros(B.PLANE_MAX_PLANES, PLANE_DTYPE), C.c_size_t(0), C.c_size_t(0)
+    B.check(fn(_fptr(xyz), n, C.byref(sel), _fptr(out), idx.ctypes.data_as(C.POINTER(C.c_int32)), planes.ctypes.data_as(C.POINTER(B.CPlane)), C.byref(c),
+               C.byref(m)))
+    return out[:m.value].copy(), idx[:m.value].copy(), planes[:c.value].copy()
+
+
+def plane_filter(xyz, distance, iterations=1000, refine=1, max_planes=1, min_inliers=0, seed=0):
+    """goicp_plane_filter_host (host only): the points no plane of segment_plane took, in input order -> (cloud (m, 3) float32, their indices
+    (m,) int32, planes (c,) PLANE_DTYPE).  Registration.plane_filter and set_source(plane_distance=, ...) give the same bits on the device."""
+    return _plane_filter_call(B.load_library().goicp_plane_filter_host, xyz, _plane_select(distance, iterations, refine, max_planes, min_inliers, seed))
+
+
+def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None, cluster=None, plane=None):
+    """the composition of the host functions that goicp_set_source_filtered, goicp_set_source_pipeline, goicp_set_source_clustered and
+    goicp_set_source_segmented equal"""
     if voxel:
         pcs = voxel_downsample(pcs, voxel)[0]
     if stat_neighbors:
         pcs = statistical_outlier_removal(pcs, stat_neighbors, std_ratio)[0]
     if radius:
         pcs = radius_outlier_removal(pcs, radius, min_neighbors)[0]
+    if plane:
+        pcs = plane_filter(pcs, *plane)[0]
     if cluster:
         pcs = cluster_filter(pcs, *cluster)[0]
     return pcs
@@ -364,7 +406,8 @@ class Registration:
         self._pcs, self._pcs_raw = value, None
 
     def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None, cluster_radius=None,
-                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0):
+                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0, plane_distance=None, plane_iterations=0, plane_refine=1, plane_max=1,
+                   plane_min_inliers=0, plane_seed=0):
         """goicp_set_source: a new source cloud under the same target.  Everything built from the target, the params and the per-handle
         options stay; afterwards the handle answers as a fresh Registration(pct, pcs, ...) with the same options would, bit for bit.
         voxel: goicp_set_source_voxel -- the cloud is reduced to one centroid per voxel on the device first, and the handle answers as after
@@ -377,13 +420,31 @@ class Registration:
         deviations, and the handle answers as after set_source of the composed host functions' output.
         cluster_radius (with cluster_min_neighbors, cluster_min_size, cluster_keep): goicp_set_source_clustered -- after the other stages, if
         any, only the points of the cluster_keep largest clusters (0 = all) with at least cluster_min_size members stay, and the handle
-        answers as after set_source of cluster_filter(..., cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_keep)[0]."""
+        answers as after set_source of cluster_filter(..., cluster_radius, cluster_min_neighbors, cluster_min_size, cluster_keep)[0].
+        plane_distance (with plane_iterations, plane_refine, plane_max, plane_min_inliers, plane_seed): goicp_set_source_segmented -- between
+        the radius filter and the cluster selection, if any, the points of up to plane_max RANSAC planes are dropped, and the handle answers
+        as after set_source of plane_filter(..., plane_distance, plane_iterations, ...)[0] followed by the cluster selection."""
         pcs = _f32(pcs, (-1, 3))
         if (radius is None) != (min_neighbors is None):
             raise ValueError("set_source: radius and min_neighbors go together")
         if (stat_neighbors is None) != (std_ratio is None):
             raise ValueError("set_source: stat_neighbors and std_ratio go together")
-        if cluster_radius is not None:
+        if plane_distance is not None:
+            if not float(plane_distance) > 0 or (cluster_radius is not None and not float(cluster_radius) > 0) or (voxel is not None and not float(voxel) > 0) \
+                    or (radius is not None and not float(radius) > 0) or (stat_neighbors is not None and not int(stat_neighbors) > 0):
+                raise ValueError("set_source: a stage that is named needs a size > 0")
+            kept = C.c_size_t(0)
+            p = B.CSourcePipeline(float(voxel or 0.0), int(stat_neighbors or 0), float(std_ratio or 0.0), float(radius or 0.0), int(min_neighbors or 0))
+            plane = (float(plane_distance), int(plane_iterations), int(plane_refine), int(plane_max), int(plane_min_inliers), int(plane_seed))
+            cluster = None if cluster_radius is None else (float(cluster_radius), int(cluster_min_neighbors), int(cluster_min_size), int(cluster_keep))
+            pl = _plane_select(*plane)
+            cs = B.CClusterSelect(*cluster) if cluster else None
+            B.check(self._lib.goicp_set_source_segmented(self.handle, _fptr(pcs), len(pcs), C.byref(p), C.byref(pl), C.byref(cs) if cs else None, C.byref(kept)))
+            self._pcs, self.ns = None, kept.value
+            self._pcs_raw = (pcs, None if voxel is None else float(voxel), None if radius is None else float(radius),
+                             None if min_neighbors is None else int(min_neighbors), None if stat_neighbors is None else int(stat_neighbors),
+                             None if std_ratio is None else float(std_ratio), cluster, plane)
+        elif cluster_radius is not None:
             if not float(cluster_radius) > 0 or (voxel is not None and not float(voxel) > 0) or (radius is not None and not float(radius) > 0) \
                     or (stat_neighbors is not None and not int(stat_neighbors) > 0):
                 raise ValueError("set_source: a stage that is named needs a size > 0")
@@ -447,6 +508,18 @@ class Registration:
         """goicp_cluster_filter: the module-level cluster_filter on the device (the handle lends its device and stream, its state is
         untouched) -> (cloud (m, 3) float32, indices (m,) int32, labels (m,) int32), the same bits"""
         return _cluster_filter_call(lambda *a: self._lib.goicp_cluster_filter(self.handle, *a), xyz, radius, min_neighbors, min_size, keep)
+
+    def segment_plane(self, xyz, distance, iterations=1000, refine=1, max_planes=1, min_inliers=0, seed=0):
+        """goicp_segment_plane: the module-level segment_plane on the device (the handle lends its device and stream, its state is
+        untouched) -> (labels (n,) int32, planes (c,) PLANE_DTYPE), the same bits"""
+        return _segment_plane_call(lambda *a: self._lib.goicp_segment_plane(self.handle, *a), xyz,
+                                   _plane_select(distance, iterations, refine, max_planes, min_inliers, seed))
+
+    def plane_filter(self, xyz, distance, iterations=1000, refine=1, max_planes=1, min_inliers=0, seed=0):
+        """goicp_plane_filter: the module-level plane_filter on the device (the handle lends its device and stream, its state is
+        untouched) -> (cloud (m, 3) float32, indices (m,) int32, planes (c,) PLANE_DTYPE), the same bits"""
+        return _plane_filter_call(lambda *a: self._lib.goicp_plane_filter(self.handle, *a), xyz,
+                                  _plane_select(distance, iterations, refine, max_planes, min_inliers, seed))
 
     def knn_self(self, xyz, k):
         """goicp_knn_self: the module-level knn_self on the device (the handle lends its device and stream, its state is untouched)"""
@@ -743,10 +816,12 @@ class FastGoICP:
         self.sse_threshold = self.registration.sse_threshold      # mse_threshold * inlierNum (jly_goicp.cpp:198-208), from the engine
 
     def set_source(self, pcs, voxel=None, radius=None, min_neighbors=None, stat_neighbors=None, std_ratio=None, cluster_radius=None,
-                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0):
+                   cluster_min_neighbors=0, cluster_min_size=0, cluster_keep=0, plane_distance=None, plane_iterations=0, plane_refine=1, plane_max=1,
+                   plane_min_inliers=0, plane_seed=0):
         """Registration.set_source, then the fields this object mirrors are read again (the polled snapshot is the fresh handle's)"""
         self.registration.set_source(pcs, voxel, radius, min_neighbors, stat_neighbors, std_ratio, cluster_radius, cluster_min_neighbors,
-                                     cluster_min_size, cluster_keep)
+                                     cluster_min_size, cluster_keep, plane_distance, plane_iterations, plane_refine, plane_max, plane_min_inliers,
+                                     plane_seed)
         self.sse_threshold = self.registration.sse_threshold
 
     def run(self):

@@ -433,6 +433,81 @@ void goicp_cluster_select_default(goicp_cluster_select* out);   /* all 0 = no st
 int goicp_cluster_filter_host(const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label, size_t* m);
 int goicp_cluster_filter(goicp_handle h, const float* xyz, size_t n, const goicp_cluster_select* s, float* out_xyz, int32_t* out_index, int32_t* out_label, size_t* m);
 int goicp_set_source_clustered(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_cluster_select* s, size_t* n_kept);
+/*
+ * RANSAC plane segmentation (PCL's SACSegmentation with SACMODEL_PLANE / SAC_RANSAC plus ExtractIndices(negative), Open3D's segment_plane
+ * plus select_by_index(invert=True)): the dominant planes of a cloud -- the floor, table or wall an object stands on -- and the filter
+ * "drop their points" built on it.  The host functions, the device functions and the segmented swap produce the same bits.  Arithmetic is
+ * IEEE, nothing fused.  With T = iterations (0 means 1000) and P = max_planes (0 means 1):
+ *   rounds  round p = 0, 1, ... < P works on the points no earlier round labelled, in input order: n_p of them.  A round with n_p < 3 finds
+ *           nothing and ends the search, and so does a round whose best count is below max(min_inliers, 3);
+ *   draw    hypothesis t < T of round p takes three distinct positions a, b, c of the remaining cloud from a counter-based generator:
+ *           h(c) = the splitmix64 finaliser of z = seed + (c + 1) * 0x9E3779B97F4A7C15 (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *           z *= 0x94D049BB133111EB, z ^= z >> 31; all mod 2^64) at the counters 3 (p T + t) + {0, 1, 2}: a = h_0 mod n_p; b = h_1 mod
+ *           (n_p - 1), incremented when >= a; c = h_2 mod (n_p - 2), incremented when >= min(a, b), then again when >= max(a, b).  Integers
+ *           only, no state: any hypothesis can be computed alone;
+ *   plane   in fp64, each operation rounded once: u = p_b - p_a, v = p_c - p_a on the widened floats, n = u x v (each component x*y - z*w
+ *           with both products rounded), l2 = (n_0 n_0 + n_1 n_1) + n_2 n_2.  The hypothesis is degenerate when !(l2 > 0) or a component of
+ *           the float normal n_c = (float)(n_c / sqrt(l2)) is not finite: it scores 0 and can never be the best.  The sign is the normals
+ *           operator's on the float normal (the first non-zero component positive, a zero written as +0); the anchor is point a's own bits;
+ *   pair    in float, left to right: e = ((x_0 - a_0) * n_0 + (x_1 - a_1) * n_1) + (x_2 - a_2) * n_2; the point is an inlier iff
+ *           fabsf(e) <= distance (a NaN compares false).  Offsets from the anchor keep the error relative to the cloud's extent, not to |x|;
+ *   score   the exact integer count over all n_p points; the best is the largest count, ties to the smallest t;
+ *   refit   (refine = 1) one least-squares refit over the best hypothesis' inliers, with exact integer moments.  The frame is the voxel
+ *           operator's over the round's cloud: mn_k, d = x - mn_k in float, E = max d, E < 2^e by frexp;
+ *           q_k = llrint(ldexp((double)d_k, 31 - e)) in [0, 2^31); the sums m (the count), S_a = sum q_a and P_ab = sum q_a q_b for the
+ *           six pairs a <= b, the P_ab as sum (prod >> 32) and sum (prod & 0xffffffff): 16 words, each below 2^60, so the order of addition
+ *           cannot matter.  From those words, on the host in both paths: C_ab = ldexp((double)(m P_ab - S_a S_b), -2 (31 - e)) /
+ *           ((double)m * (double)m), the integer formed exactly in 128 bits and converted to double correctly rounded; the normals
+ *           operator's Jacobi on C; the column of the smallest eigenvalue (the lowest index on equal values) normalised, cast and signed as
+ *           above; the anchor (float)((double)mn_k + ldexp((double)S_k / (double)m, -(31 - e))), the voxel operator's centroid.  The pair
+ *           re-selects against the refit plane, which is adopted iff its count is >= the hypothesis' count (a refit without a finite
+ *           non-zero normal is not adopted); `refined` reports which stands;
+ *   output  per point a label: -1, or the index of the plane that took it; per plane a goicp_plane with `inliers` the count of the plane
+ *           that stands, `hypothesis` the best t, and d = (float)(-((n_0 p_0 + n_1 p_1) + n_2 p_2)) in fp64 on the widened floats: the
+ *           ax + by + cz + d = 0 form PCL and Open3D return.  The filter returns the points labelled -1 in input order with their own bits
+ *           and their original indices (ascending).
+ * goicp_segment_plane: out_label holds n ints (all written), out_planes room for max_planes records (GOICP_PLANE_MAX_PLANES always
+ * suffices; the first *n_planes are written).  goicp_plane_filter: out_xyz holds n x 3 floats (the first m x 3 are written), out_index (may
+ * be NULL) n ints (the first m), out_planes and n_planes (each may be NULL) as above.  Zero planes, m == n and m == 0 are valid results.
+ * The _host forms run on the host alone (no handle, no GPU).  The handle forms run on the device: the handle lends its device and stream,
+ * its state is untouched; only the best key and plane of a round, the refit's 16 words and the final cloud come back.
+ * goicp_set_source_segmented is the full chain behind one upload: voxel -> statistical -> radius (p; NULL = none of them) -> plane removal
+ * (pl; NULL or pl->distance == 0 = no stage) -> cluster selection (s; NULL or s->radius == 0 = no stage) -> swap.  Afterwards the handle
+ * answers every entry point bit for bit as after goicp_set_source(h, D, m) with D the composition of the host functions.  With the plane
+ * stage off it is goicp_set_source_clustered.  *n_kept (may be NULL) = m.
+ * GOICP_ERR_INVALID, nothing written or the handle untouched: NULL arguments, n == 0 or above goicp_create's limit, a non-finite
+ * coordinate, a distance that is <= 0, NaN or infinite (for the swap: negative or NaN; 0 is "no stage"), iterations outside
+ * 0..GOICP_PLANE_MAX_ITERATIONS, max_planes outside 0..GOICP_PLANE_MAX_PLANES, a negative min_inliers (a min_inliers above n is legal and
+ * finds no plane), refine outside 0..1, for the swap everything goicp_set_source_clustered refuses and a chain that keeps no point, and
+ * for the handle forms any call while a registration runs.
+ */
+#define GOICP_PLANE_MAX_ITERATIONS 65536
+#define GOICP_PLANE_MAX_PLANES 8
+typedef struct goicp_plane_select {
+    float    distance;      /* inlier threshold; 0 = no stage (the swap) */
+    int32_t  iterations;    /* hypotheses per round; 0 = 1000 */
+    int32_t  refine;        /* 1 = least-squares refit over the best hypothesis' inliers */
+    int32_t  max_planes;    /* rounds at most; 0 = 1 */
+    int32_t  min_inliers;   /* a best count below max(min_inliers, 3) ends the search */
+    uint64_t seed;
+} goicp_plane_select;
+typedef struct goicp_plane {
+    float   normal[3];
+    float   point[3];       /* the anchor: a point of the plane */
+    float   d;              /* normal . x + d = 0 */
+    int32_t inliers;
+    int32_t hypothesis;     /* the best t of the round */
+    int32_t refined;        /* 1: the refit stands */
+} goicp_plane;
+void goicp_plane_select_default(goicp_plane_select* out);   /* all 0 = no stage */
+int goicp_segment_plane_host(const float* xyz, size_t n, const goicp_plane_select* sel, int32_t* out_label, goicp_plane* out_planes, size_t* n_planes);
+int goicp_segment_plane(goicp_handle h, const float* xyz, size_t n, const goicp_plane_select* sel, int32_t* out_label, goicp_plane* out_planes, size_t* n_planes);
+int goicp_plane_filter_host(const float* xyz, size_t n, const goicp_plane_select* sel, float* out_xyz, int32_t* out_index, goicp_plane* out_planes,
+                            size_t* n_planes, size_t* m);
+int goicp_plane_filter(goicp_handle h, const float* xyz, size_t n, const goicp_plane_select* sel, float* out_xyz, int32_t* out_index, goicp_plane* out_planes,
+                       size_t* n_planes, size_t* m);
+int goicp_set_source_segmented(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_plane_select* pl,
+                               const goicp_cluster_select* s, size_t* n_kept);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

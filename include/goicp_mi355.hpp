@@ -289,6 +289,48 @@ public:
 		if (label) label->resize(m);
 		return m;
 	}
+	// the full chain (goicp_set_source_segmented): after p's stages (p may be null) the points of the planes `pl` finds are dropped, then the
+	// cluster selection s (may be null) runs; returns the points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, size_t ns, const goicp_source_pipeline* p, const goicp_plane_select& pl, const goicp_cluster_select* s)
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		size_t kept = 0;
+		check(goicp_set_source_segmented(h_, reinterpret_cast<const float*>(pcs.data()), ns, p, &pl, s, &kept));
+		ns_ = kept;
+		return kept;
+	}
+	// RANSAC plane segmentation of any cloud, on the device (goicp_segment_plane): label gets n entries (-1 = no plane), planes the planes
+	// found; returns their number.  The registration lends its device, its state is untouched
+	template <class Point3>
+	size_t segment_plane(const std::vector<Point3>& cloud, size_t n, const goicp_plane_select& sel, std::vector<int32_t>& label, std::vector<goicp_plane>& planes) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		label.resize(n);
+		planes.resize(GOICP_PLANE_MAX_PLANES);
+		size_t c = 0;
+		check(goicp_segment_plane(h_, reinterpret_cast<const float*>(cloud.data()), n, &sel, label.data(), planes.data(), &c));
+		planes.resize(c);
+		return c;
+	}
+	// the points no plane took, on the device (goicp_plane_filter), in input order: kept gets the m points, index and planes (each may be
+	// null) their original indices and the planes found; returns m
+	template <class Point3>
+	size_t plane_filter(const std::vector<Point3>& cloud, size_t n, const goicp_plane_select& sel, std::vector<Point3>& kept, std::vector<int32_t>* index = nullptr,
+	                    std::vector<goicp_plane>* planes = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		kept.resize(n);
+		if (index) index->resize(n);
+		if (planes) planes->resize(GOICP_PLANE_MAX_PLANES);
+		size_t m = 0, c = 0;
+		check(goicp_plane_filter(h_, reinterpret_cast<const float*>(cloud.data()), n, &sel, reinterpret_cast<float*>(kept.data()), index ? index->data() : nullptr,
+		                         planes ? planes->data() : nullptr, &c, &m));
+		kept.resize(m);
+		if (index) index->resize(m);
+		if (planes) planes->resize(c);
+		return m;
+	}
 	// the exact k nearest other points of every point of any cloud, on the device (goicp_knn_self): index gets n x k entries, row i ascending
 	// by (squared distance, index); dist_sq (may be null) their squared distances.  The registration lends its device, its state is untouched
 	template <class Point3>
@@ -507,6 +549,14 @@ public:
 	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_pipeline* p, const goicp_cluster_select& s)
 	{
 		const size_t kept = registration.set_source(pcs, pcs.size(), p, s);
+		sync();
+		return kept;
+	}
+	// ... behind the chain `p` (may be null), the plane removal `pl` and the cluster selection `s` (may be null); returns the number of points kept
+	template <class Point3>
+	size_t set_source(const std::vector<Point3>& pcs, const goicp_source_pipeline* p, const goicp_plane_select& pl, const goicp_cluster_select* s)
+	{
+		const size_t kept = registration.set_source(pcs, pcs.size(), p, pl, s);
 		sync();
 		return kept;
 	}
