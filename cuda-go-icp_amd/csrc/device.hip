@@ -2688,9 +2688,15 @@ __global__ __launch_bounds__(kIcpThreads) void icp_accum_kernel(const float4* __
 // Sum the per-block partials in double (fixed order -> deterministic), then -- one lane -- the body of
 // the ICP loop after the correspondence pass (jly_icp3d.hpp:253-292): convergence test, means, H,
 // SVD, R_ / t_, compose.  The pose lives in device memory, so the host can queue several iterations
-// back-to-back without a round trip.  Written for one workgroup of kFinThreads threads; used by the last
-// workgroup of the fused iteration kernel and by the stand-alone finalize launch (trimmed ICP, A/B tests):
-// the same code and the same summation order, so both forms give bit-identical states.
+// back-to-back without a round trip.  Written for one workgroup of T threads; used by the last workgroup of
+// the fused iteration kernel (T = kIcpThreads), by the stand-alone finalize launch (T = kFinThreads; trimmed
+// ICP, A/B tests) and by icp_partials_reduce (T = kPreThreads): the same code, but NOT the same summation
+// order -- a thread adds the rows r, r + T/4, r + 2 T/4, ..., and T / 64 wavefront totals follow.  A double sum
+// of n floats is exact, hence order-free, while the terms' exponents span at most 29 - log2(n) bits, and
+// finalize_rows rounds the sums and H to float again, so the fused and the stand-alone form on the same
+// rows have given the same states bit for bit in every run compared (tests/test_gpu_icp_forms.py: 17, 65, 257
+// and 4 096 rows, whole runs); nothing in the code makes them.  Above 4 096 rows icp_partials_reduce also
+// rounds subtotals to float, and the states do differ (seen at 4 097 rows: R by 1.5e-8 after one iteration).
 
 // every thread of the workgroup (T threads); returns with sh.sums[] valid for all threads
 template <int T>
@@ -3277,7 +3283,11 @@ hipError_t launch_icp_finalize_from_sums(const long long* sums16, IcpState* st, 
 	return hipGetLastError();
 }
 
-// ticket != nullptr: one fused launch per iteration; nullptr: pass + stand-alone finalize (same arithmetic, bit-identical)
+// Three forms of one iteration (guard: tests/test_gpu_icp_forms.py).  ticket != nullptr: one fused launch, float rows summed by its last
+// workgroup (finalize_reduce<kIcpThreads>); nullptr on the bricked DT with `acc`: the fixed-point pass + icp_finalize_update_acc (the default);
+// nullptr otherwise: the float-row pass + stand-alone finalize (finalize_reduce<kFinThreads>, above 4 * kPreRows workgroups behind
+// icp_partials_reduce).  The same per-point arithmetic and the same 16-query float row sums in all three; the rows are then added in an order
+// of the form's own (see finalize_reduce), so the states of two forms agree within float rounding, not to the bit by construction.
 hipError_t launch_icp_iteration(const float4* src, int N, IcpState* st, const KdDesc& kd, const DtDesc& dt, float* partials,
                                 int* ticket, float4* nn_cache, int* hits, hipStream_t stream, unsigned long long* acc)
 {

@@ -91,7 +91,7 @@ struct Params {
 	                              // streams (own lists, own control block): one lane's dependent launches drain beside the others' (run_inner_device)
 	int lane_min_searches = 64;
 	int stream_priority = 0;      // 1: the engine's stream gets the highest priority of the device (an ICP engine beside a bounds engine on one GPU: tools/overlap_probe.py)
-	int icp_fused = 0;            // 1: one launch per ICP iteration (last workgroup finalizes); 0: pass + finalize launches (A/B, bit-identical)
+	int icp_fused = 0;            // 1: one launch per ICP iteration (last workgroup finalizes); 0: pass + finalize launches (A/B).  Same per-point arithmetic; the sums are added in another order: states within float rounding of each other, equal to the bit only as observed, on the linear DT at 17 to 4 096 workgroups, and not above (tests/test_gpu_icp_forms.py)
 	float trim_fraction = 0.f;    // GoICP::trimFraction (jly_goicp.h:116; the reference hard-wires 0, jly_goicp.cpp:55)
 	// Search domain ([params.rotation] / [params.translation] of the reference's configs, test/skull_goicp.toml:22-41;
 	// declared in src/common.h:157-169, never parsed there).  Unset = the CPU path's fixed domain

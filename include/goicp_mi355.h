@@ -119,7 +119,8 @@ typedef struct goicp_params {
 	float trans_min[3], trans_max[3];   /* in cloud units after `resize` */
 	int32_t rot_search_depth, trans_search_depth;
 	int32_t icp_fused;       /* 1: one launch per ICP iteration, the last workgroup to arrive runs the update;
-	                          * 0: correspondence pass + update as two launches (same arithmetic, bit-identical states) */
+	                          * 0: correspondence pass + update as two launches (same per-point arithmetic; the sums are added in
+	                          * another order, so the states agree within float rounding -- not to the bit by construction) */
 	int32_t bounds_fp16;     /* 1: the BnB cube bounds read a half-precision copy of the bricked DT (one 128-byte line per 4x4x4 brick
 	                          * instead of two), rounded toward zero so that lower bounds stay valid.  Each LOOKED-UP VALUE comes out
 	                          * low by < 2^-10 relative where its half is normal (2^-14 .. 65504 in cloud units; below that by
