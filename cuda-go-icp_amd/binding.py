@@ -200,6 +200,8 @@ SYMBOLS = {
     "goicp_target_normals": (C.c_int, [_vp, _fp]),
     "goicp_set_icp_symmetric": (C.c_int, [_vp, C.c_int32, C.c_int32]),
     "goicp_get_icp_symmetric": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "goicp_set_icp_generalized": (C.c_int, [_vp, C.c_int32, C.c_float, C.c_int32]),
+    "goicp_get_icp_generalized": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "goicp_source_normals": (C.c_int, [_vp, _fp]),
     "goicp_set_source_normals": (C.c_int, [_vp, _fp, C.c_size_t]),
     "goicp_icp_gate_default": (None, [C.POINTER(CIcpGate)]),

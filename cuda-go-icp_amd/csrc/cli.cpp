@@ -1,6 +1,6 @@
 // goicp_cli: headless replacement for the reference's viewer main (src/main.cpp:14-187).  Takes the
 // reference's .toml unchanged:  goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root]
-//                                [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
+//                                [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--generalized [--gicp-epsilon E]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C]
 //                                [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V]
 //                                [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K]
 //                                [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A]
@@ -17,6 +17,10 @@
 //   --symmetric   implies --point-to-plane; every ICP of the run takes the symmetric point-to-plane form over the normals of both clouds
 //               (goicp_set_icp_symmetric; --source-normal-k K neighbours per source normal, 3..32, default 16).  Refused together with
 //               --ranks N > 1 and --trim-fraction F > 0, and with K out of range -- before any device is touched
+//   --generalized   implies --point-to-plane; every ICP of the run takes the generalized (plane-to-plane) form, each correspondence weighted by the
+//               combined covariance of both clouds' normals (goicp_set_icp_generalized; --gicp-epsilon E in [1e-4, 1], default 1e-3;
+//               --source-normal-k K as under --symmetric).  Refused together with --symmetric, --ranks N > 1 and --trim-fraction F > 0, and with
+//               E out of range -- before any device is touched
 //   --max-corr-dist D   every ICP of the run uses only correspondences within distance D (goicp_set_icp_gate; cloud units after
 //               `resize`); output.toml then gets an [icp_gate] table with D and the inlier count of the final pose.  D must be a finite
 //               number > 0, and the flag is refused together with --ranks N > 1 and --trim-fraction F > 0 -- before any device is touched
@@ -209,9 +213,11 @@ int main(int argc, char** argv)
 {
 	for (int i = 1; i < argc; i++)
 		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...]\n"); return 2; }
-	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16;
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--generalized [--gicp-epsilon E]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...]\n"); return 2; }
+	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16, generalized = 0;
+	float gicp_epsilon = 1e-3f;
 	const char* snk_arg = nullptr;
+	const char* geps_arg = nullptr;
 	float trim_fraction = 0.f;   // the TOML's `trim = true` carries no fraction (the reference ignores it): given here
 	unsigned long long seed = 0;
 	const char* gate_arg = nullptr;
@@ -251,6 +257,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--point-to-plane")) plane = 1;
 		else if (!std::strcmp(argv[i], "--normal-k") && i + 1 < argc) normal_k = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--symmetric")) symmetric = plane = 1;
+		else if (!std::strcmp(argv[i], "--generalized")) generalized = plane = 1;
+		else if (!std::strcmp(argv[i], "--gicp-epsilon")) geps_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--source-normal-k")) snk_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--max-corr-dist")) gate_arg = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--robust-kernel")) rk_arg = i + 1 < argc ? argv[++i] : "";
@@ -505,14 +513,31 @@ int main(int argc, char** argv)
 			std::fprintf(stderr, "error: --source-normal-k needs an integer in 3..%d, got '%s'\n", GOICP_KNN_SELF_MAX, snk_arg);
 			return 2;
 		}
-		if (!symmetric) {
-			std::fprintf(stderr, "error: --source-normal-k goes with --symmetric\n");
+		if (!symmetric && !generalized) {
+			std::fprintf(stderr, "error: --source-normal-k goes with --symmetric or --generalized\n");
 			return 2;
 		}
 		source_normal_k = (int)k;
 	}
 	if (symmetric && (ranks > 1 || trim_fraction > 0.f)) {
 		std::fprintf(stderr, "error: --symmetric cannot be combined with --ranks N > 1 (the multi-GPU registration runs point-to-point ICP) or --trim-fraction F > 0\n");
+		return 2;
+	}
+	if (geps_arg) {
+		char* end = nullptr;
+		const float e = std::strtof(geps_arg, &end);
+		if (end == geps_arg || *end != '\0' || !(e >= 1e-4f && e <= 1.f)) {
+			std::fprintf(stderr, "error: --gicp-epsilon needs a number in [1e-4, 1], got '%s'\n", geps_arg);
+			return 2;
+		}
+		if (!generalized) {
+			std::fprintf(stderr, "error: --gicp-epsilon goes with --generalized\n");
+			return 2;
+		}
+		gicp_epsilon = e;
+	}
+	if (generalized && (symmetric || ranks > 1 || trim_fraction > 0.f)) {
+		std::fprintf(stderr, "error: --generalized cannot be combined with --symmetric, --ranks N > 1 (the multi-GPU registration runs point-to-point ICP) or --trim-fraction F > 0\n");
 		return 2;
 	}
 	if (plane && ranks > 1) {
@@ -627,6 +652,7 @@ int main(int argc, char** argv)
 		goicp_handle h = engine.registration.handle();
 		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
 		if (symmetric) engine.registration.set_icp_symmetric(true, source_normal_k);
+		if (generalized) engine.registration.set_icp_generalized(true, gicp_epsilon, source_normal_k);
 		if (gate > 0.f) engine.registration.set_icp_gate(gate);
 		if (robust_kernel) engine.registration.set_icp_robust(robust_kernel, robust_scale);
 		if (trunc > 0.f) engine.registration.set_search_truncation(trunc);
@@ -660,6 +686,15 @@ int main(int argc, char** argv)
 				std::fclose(f);
 			}
 		}
+		if (generalized) {
+			std::printf("ICP metric: generalized plane-to-plane (epsilon %.7g, normal_k %d, source_normal_k %d)\n", gicp_epsilon, normal_k, source_normal_k);
+			if (!config.io.output.empty()) {
+				FILE* f = std::fopen(config.io.output.c_str(), "a");
+				if (!f) throw std::runtime_error("cannot append to " + config.io.output);
+				std::fprintf(f, "\n[icp_generalized]\nenabled = true\nepsilon = %.9g\nsource_normal_k = %d\n", gicp_epsilon, source_normal_k);
+				std::fclose(f);
+			}
+		}
 		if (gate > 0.f) {
 			int32_t n_in = 0;
 			check(goicp_eval_correspondences(h, R, t, gate, nullptr, nullptr, &n_in, nullptr));
@@ -683,7 +718,7 @@ int main(int argc, char** argv)
 			if (rank_tol >= 0.0) io.rank_tol = rank_tol;
 			const goicp_pose_info I = engine.registration.pose_information(R, t, &io);
 			std::printf("Information: rank %d of 6, sigma %.7g (metric %d%s, %lld inliers)\n", (int)I.rank, std::sqrt(I.sigma2), (int)I.metric,
-			            symmetric && I.metric == 1 ? " symmetric" : "", (long long)I.inliers);
+			            symmetric && I.metric == 1 ? " symmetric" : generalized && I.metric == 1 ? " generalized" : "", (long long)I.inliers);
 			if (!config.io.output.empty()) {
 				FILE* f = std::fopen(config.io.output.c_str(), "a");
 				if (!f) throw std::runtime_error("cannot append to " + config.io.output);

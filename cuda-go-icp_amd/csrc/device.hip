@@ -3728,9 +3728,64 @@ __device__ __forceinline__ float4 symmetric_normal(const float* R, const float4&
 	return make_float4(0.5f * (sx + nm.x), 0.5f * (sy + nm.y), 0.5f * (sz + nm.z), 0.5f);
 }
 
-template <int K, int LAYOUT, bool STRIDED, bool GATE = false, bool ROBUST = false, bool SYM = false>
+// GENERALIZED (goicp_set_icp_generalized; include/goicp_mi355.h "generalized (plane-to-plane) ICP"): the correspondence's 3 x 3 weight
+// W = 2 eps Sigma^-1, Sigma = 2 I - (1 - eps) (u u^T + s s^T) with u the target normal and s = R ns, from six cofactors and one determinant, in
+// float, operation by operation in the header's order; then the 27 words of the system linearised about the pivot, e' = e + omega x a + tau:
+// H_ww = [a]x W [a]x^T (6), H_wt = [a]x W (9), H_tt = W (6) in the upper-triangle order of the plane pass's J J^T, b = (a x g, g), g = W e.
+// The words go to the row's LDS line as they are formed: W (6 values) and one row of [a]x W (3) are all that stays live.  W's eigenvalues
+// lie in [eps, 1], so every word keeps the plane pass's bound (|n| <= 1 there).  -> e . g, the correspondence's weighted squared residual
+__device__ __forceinline__ float generalized_terms(float* dst, const float* R, const float4& ns, const float4& u, float eps, float ax, float ay, float az,
+                                                   float ex, float ey, float ez)
+{
+	const float sx = R[0] * ns.x + R[1] * ns.y + R[2] * ns.z;        // symmetric_normal's row expression
+	const float sy = R[3] * ns.x + R[4] * ns.y + R[5] * ns.z;
+	const float sz = R[6] * ns.x + R[7] * ns.y + R[8] * ns.z;
+	const float k = 1.f - eps, h = 2.f * eps;
+	// Sigma: a product of a normal with itself does not see the normal's sign; a zero normal subtracts nothing
+	const float Sxx = 2.f - k * (u.x * u.x + sx * sx), Syy = 2.f - k * (u.y * u.y + sy * sy), Szz = 2.f - k * (u.z * u.z + sz * sz);
+	const float Sxy = -(k * (u.x * u.y + sx * sy)), Sxz = -(k * (u.x * u.z + sx * sz)), Syz = -(k * (u.y * u.z + sy * sz));
+	const float C00 = Syy * Szz - Syz * Syz, C01 = Sxz * Syz - Sxy * Szz, C02 = Sxy * Syz - Sxz * Syy;
+	const float C11 = Sxx * Szz - Sxz * Sxz, C12 = Sxy * Sxz - Sxx * Syz, C22 = Sxx * Syy - Sxy * Sxy;
+	float det = Sxx * C00;
+	det += Sxy * C01;
+	det += Sxz * C02;
+	const float W00 = (h * C00) / det, W01 = (h * C01) / det, W02 = (h * C02) / det;
+	const float W11 = (h * C11) / det, W12 = (h * C12) / det, W22 = (h * C22) / det;
+	dst[15] = W00; dst[16] = W01; dst[17] = W02; dst[18] = W11; dst[19] = W12; dst[20] = W22;
+	float gx = W00 * ex, gy = W01 * ex, gz = W02 * ex;
+	gx += W01 * ey; gy += W11 * ey; gz += W12 * ey;
+	gx += W02 * ez; gy += W12 * ez; gz += W22 * ez;
+	dst[21] = ay * gz - az * gy;
+	dst[22] = az * gx - ax * gz;
+	dst[23] = ax * gy - ay * gx;
+	dst[24] = gx; dst[25] = gy; dst[26] = gz;
+	float eg = ex * gx;
+	eg += ey * gy;
+	eg += ez * gz;
+	// [a]x W row by row (row i = the i-th component of a x column j of W), and that row times [a]x^T
+	{
+		const float m0 = ay * W02 - az * W01, m1 = ay * W12 - az * W11, m2 = ay * W22 - az * W12;
+		dst[0] = m2 * ay - m1 * az; dst[1] = m0 * az - m2 * ax; dst[2] = m1 * ax - m0 * ay;
+		dst[3] = m0; dst[4] = m1; dst[5] = m2;
+	}
+	{
+		const float m0 = az * W00 - ax * W02, m1 = az * W01 - ax * W12, m2 = az * W02 - ax * W22;
+		dst[6] = m0 * az - m2 * ax; dst[7] = m1 * ax - m0 * ay;
+		dst[8] = m0; dst[9] = m1; dst[10] = m2;
+	}
+	{
+		const float m0 = ax * W01 - ay * W00, m1 = ax * W11 - ay * W01, m2 = ax * W12 - ay * W02;
+		dst[11] = m1 * ax - m0 * ay;
+		dst[12] = m0; dst[13] = m1; dst[14] = m2;
+	}
+	return eg;
+}
+
+// FORM: the plane pass's own (kIcpFormPlane), SYM (kIcpFormSymmetric) or GENERALIZED (kIcpFormGeneralized; gicp_eps is read by it alone)
+enum : int { kIcpFormPlane = 0, kIcpFormSymmetric = 1, kIcpFormGeneralized = 2 };
+template <int K, int LAYOUT, bool STRIDED, bool GATE = false, bool ROBUST = false, int FORM = kIcpFormPlane>
 __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, const IcpState* st, const KdDesc& kd, const DtDesc& dt, const float4* normals,
-                                                    unsigned long long* acc, int capped = 0, const float4* src_normals = nullptr)
+                                                    unsigned long long* acc, int capped = 0, const float4* src_normals = nullptr, float gicp_eps = 0.f)
 {
 	static_assert(!ROBUST || !GATE, "a robust kernel and a gate exclude each other");
 	__shared__ float red[kIcpThreads / 16][kIcpPlaneStride];
@@ -3766,12 +3821,20 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 			float4 nm = normals[r.idx];                               // one gather per correspondence (by original index: the walk's slot is dead)
 			float ax = qx - st->cq[0], ay = qy - st->cq[1], az = qz - st->cq[2];
 			const float ex = qx - r.mx, ey = qy - r.my, ez = qz - r.mz;
-			if constexpr (SYM) {
+			if constexpr (FORM == kIcpFormSymmetric) {
 				const float4 ns = src_normals[ic];                    // the query's own normal: one coalesced load (an inlier's ic is its i)
 				const float4 n = symmetric_normal(st->R, ns, nm);
 				nm.x = n.x; nm.y = n.y; nm.z = n.z;
 				ax -= n.w * ex; ay -= n.w * ey; az -= n.w * ez;           // c: the midpoint of the correspondence relative to the pivot
 			}
+			if constexpr (FORM == kIcpFormGeneralized) {
+				// the query's index again (an inlier's is its i), from the lane and wave numbers as the hardware gives them: held across the walk it
+				// costs the K = 3 walk, which is at the 64-VGPR bound, a spill
+				const int wave2 = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6, row2 = (int)__lane_id() >> 4;
+				const int wv2 = gb * (kIcpThreads / 64) + wave2;
+				const float4 ns = src_normals[STRIDED ? wv2 + row2 * nw : wv2 * 4 + row2];
+				generalized_terms(dst, st->R, ns, nm, gicp_eps, ax, ay, az, ex, ey, ez);   // words 0 .. 26, as they are formed
+			} else {
 			res = ex * nm.x;
 			res += ey * nm.y;
 			res += ez * nm.z;
@@ -3779,8 +3842,15 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 			J[1] = az * nm.x - ax * nm.z;
 			J[2] = ax * nm.y - ay * nm.x;
 			J[3] = nm.x; J[4] = nm.y; J[5] = nm.z;
+			}
 			d2 = r.best;
 		}
+		if constexpr (FORM == kIcpFormGeneralized) {
+			if (!inlier) {
+#pragma unroll
+				for (int k = 0; k < kIcpPlaneTerms - 1; k++) dst[k] = 0.f;
+			}
+		} else {
 		int k = 0;
 #pragma unroll
 		for (int a = 0; a < 6; a++)
@@ -3788,13 +3858,19 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 			for (int b = a; b < 6; b++) dst[k++] = J[a] * J[b];
 #pragma unroll
 		for (int a = 0; a < 6; a++) dst[21 + a] = J[a] * res;
+		}
 		dst[27] = d2;
 		if constexpr (GATE) dst[kIcpPlaneTerms] = inlier ? 1.f : 0.f;
 		if constexpr (ROBUST) {
 			// the 27 terms go to LDS unweighted and the row's weight beside them: the column sums below multiply (J and the walk's registers are
 			// dead by now, so the weight costs no register of the walk's budget)
 			RobustTerms rob{0.f, 0.f};                                // a row without a query adds no weight and no cost
+			if constexpr (FORM == kIcpFormGeneralized) {
+				// the weight of the Euclidean distance, point-to-point's argument: the residual here is a vector
+				if (inlier) { const float d = __fsqrt_rn(d2); rob = robust_terms(st->rk, st->rc, d, d, d2); }
+			} else {
 			if (inlier) rob = robust_terms(st->rk, st->rc, fabsf(res), __fsqrt_rn(d2), d2);
+			}
 			dst[kIcpPlaneTerms] = rob.w; dst[kIcpPlaneTerms + 1] = rob.rho;
 		}
 	}
@@ -3818,13 +3894,14 @@ __device__ __forceinline__ void icp_plane_pass_body(const float4* src, int N, co
 // and the accumulator block acc + s * kIcpBatchAccWords.  Every workgroup runs the single-pose body on that slot: the same 16 queries, the same float
 // row sums, the same acc_scale, the same replica -- and integer addition is associative, so the slot's totals are the single-pose totals bit for bit,
 // whatever else the grid holds.  `normals` is read by METRIC 1 and 2 only, `active` by BATCH only, `capped` by the gated mode only.
-// METRIC 2 is internal: metric 1 on a handle with goicp_set_icp_symmetric on; `src_normals` (parallel to src) is read by it alone.
+// METRIC 2 is internal: metric 1 on a handle with goicp_set_icp_symmetric on; `src_normals` (parallel to src) is read by it and METRIC 3.
+// METRIC 3 is internal: metric 1 on a handle with goicp_set_icp_generalized on; `gicp_eps` is read by it alone.
 template <int K, int LAYOUT, bool STRIDED, int METRIC, int MODE, bool BATCH>
 __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_kernel(const float4* __restrict__ src, int N,
                                                                       IcpState* __restrict__ states, KdDesc kd, DtDesc dt,
                                                                       const float4* __restrict__ normals, unsigned long long* __restrict__ acc,
                                                                       const int* __restrict__ active, int capped,
-                                                                      const float4* __restrict__ src_normals)
+                                                                      const float4* __restrict__ src_normals, float gicp_eps)
 {
 	constexpr bool GATE = MODE == kIcpModeGate, ROBUST = MODE == kIcpModeRobust;
 	IcpState* st = states;
@@ -3837,7 +3914,8 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_
 	if constexpr (METRIC == 0)
 		icp_pass_body<K, 1, false, false, 4, STRIDED, true, false, GATE, ROBUST>(src, N, st, kd, dt, reinterpret_cast<float*>(a), nullptr, nullptr, nullptr, 0, capped);
 	else
-		icp_plane_pass_body<K, LAYOUT, STRIDED, GATE, ROBUST, METRIC == 2>(src, N, st, kd, dt, normals, a, capped, src_normals);
+		icp_plane_pass_body<K, LAYOUT, STRIDED, GATE, ROBUST, METRIC == 3 ? kIcpFormGeneralized : METRIC == 2 ? kIcpFormSymmetric : kIcpFormPlane>(
+			src, N, st, kd, dt, normals, a, capped, src_normals, gicp_eps);
 }
 
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
@@ -4015,9 +4093,10 @@ __global__ __launch_bounds__(kFinAccThreads) void icp_opt_finalize_kernel(unsign
 hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream)
 {
 	const bool batch = a.active != nullptr;
-	if (!a.states || !a.acc || a.metric < 0 || a.metric > 2 || (a.metric != 0 && !a.normals) || (a.metric == 2 && !a.src_normals) || a.mode < kIcpModePlain ||
+	if (!a.states || !a.acc || a.metric < 0 || a.metric > 3 || (a.metric != 0 && !a.normals) || (a.metric >= 2 && !a.src_normals) || a.mode < kIcpModePlain ||
 	    a.mode > kIcpModeRobust)
 		return hipErrorInvalidValue;
+	if (a.metric == 3 && !(a.gicp_eps >= kGicpEpsMin && a.gicp_eps <= 1.f)) return hipErrorInvalidValue;
 	if (!dt.layout && (a.metric == 0 || a.mode != kIcpModePlain)) return hipErrorInvalidValue;   // the linear DT: the plain plane pass only
 	if (a.n_active < 1 || a.n_active > kIcpBatchMax || (!batch && a.n_active != 1)) return hipErrorInvalidValue;
 	if (!batch && a.metric == 0 && a.mode == kIcpModePlain) return hipErrorInvalidValue;         // launch_icp_iteration's
@@ -4026,19 +4105,22 @@ hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const
 		with_flag(a.N <= kIcpStridedMaxN, [&](auto S) {       // the default pass's choice: strangers per wavefront for small clouds
 			auto go = [&](auto L, auto M, auto MODE, auto B) {
 				hipLaunchKernelGGL((icp_opt_pass_kernel<K(), L(), S(), M(), MODE(), B()>), pass_grid, dim3(kIcpThreads), 0, stream, a.src, a.N, a.states, kd, dt,
-				                   a.normals, a.acc, a.active, a.capped, a.src_normals);
+				                   a.normals, a.acc, a.active, a.capped, a.src_normals, a.gicp_eps);
 				hipLaunchKernelGGL((icp_opt_finalize_kernel<M(), MODE(), B()>), fin_grid, dim3(kFinAccThreads), 0, stream, a.acc, a.states, a.active);
 			};
 			constexpr std::integral_constant<int, 0> c0{};
 			constexpr std::integral_constant<int, 1> c1{};
 			constexpr std::integral_constant<int, 2> c2{};
+			constexpr std::integral_constant<int, 3> c3{};
 			// the instantiations: the linear DT with the plain plane pass only; plain point-to-point in a batch only
 			if (a.mode != kIcpModePlain)
-				with_value<2, 1, 0>(a.metric, [&](auto M) { with_value<kIcpModeGate, kIcpModeRobust>(a.mode, [&](auto MODE) { with_flag(batch, [&](auto B) { go(c1, M, MODE, B); }); }); });
+				with_value<3, 2, 1, 0>(a.metric, [&](auto M) { with_value<kIcpModeGate, kIcpModeRobust>(a.mode, [&](auto MODE) { with_flag(batch, [&](auto B) { go(c1, M, MODE, B); }); }); });
 			else if (a.metric == 1)
 				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c1, c0, B); }); });
 			else if (a.metric == 2)
 				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c2, c0, B); }); });
+			else if (a.metric == 3)
+				with_flag(dt.layout, [&](auto L) { with_flag(batch, [&](auto B) { go(L, c3, c0, B); }); });
 			else
 				go(c1, c0, c0, c1);
 		});
@@ -4126,6 +4208,22 @@ __device__ __forceinline__ void pose_info_symmetric_row(float* dst, const PoseIn
 	dst[29] = w;
 	dst[30] = w > 0.f ? 1.f : 0.f;
 }
+//   METRIC 3 (internal; the generalized form of metric 1): H (21) | b (6) | sum w e^T W e | sum d^2 | W | n_in from generalized_terms, in METRIC 2's
+//            two phases; the weight under a kernel is that of the distance d, as in METRIC 0
+__device__ __forceinline__ void pose_info_generalized_row(float* dst, const PoseInfoArgs& pa, const float4* src_normals)
+{
+	if (dst[kIcpPlaneStride - 1] == 0.f) return;
+	const float ax = dst[0], ay = dst[1], az = dst[2];
+	const float ex = dst[3], ey = dst[4], ez = dst[5], d2 = dst[9];
+	const float4 nm = make_float4(dst[6], dst[7], dst[8], 0.f);
+	const float4 ns = src_normals[__float_as_int(dst[10])];
+	dst[27] = generalized_terms(dst, pa.R, ns, nm, pa.eps, ax, ay, az, ex, ey, ez);   // every input is in a register before the first word is stored
+	dst[28] = d2;
+	float w = d2 <= pa.g2 ? 1.f : 0.f;
+	if (pa.rk) { const float d = __fsqrt_rn(d2); w = robust_terms(pa.rk, pa.rc, d, d, d2).w; }
+	dst[29] = w;
+	dst[30] = w > 0.f ? 1.f : 0.f;
+}
 template <int K, int METRIC>
 __device__ __forceinline__ void pose_info_body(const float4* src, int N, const PoseInfoArgs& pa, int strided, const KdDesc& kd, const DtDesc& dt,
                                                const float4* normals, unsigned long long* acc, const float4* src_normals = nullptr)
@@ -4152,7 +4250,7 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 		if (!valid) {
 #pragma unroll
 			for (int k = 0; k < kWords; k++) dst[k] = 0.f;       // a row without a query: no terms, no weight, no count
-			if constexpr (METRIC == 2) dst[kIcpPlaneStride - 1] = 0.f;
+			if constexpr (METRIC >= 2) dst[kIcpPlaneStride - 1] = 0.f;
 		} else {
 			const float d2 = r.best;
 			const float ax = qx - pa.c[0], ay = qy - pa.c[1], az = qz - pa.c[2];
@@ -4173,8 +4271,8 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 				dst[17] = d2;
 				dst[kWordN] = w > 0.f ? 1.f : 0.f;
 			} else {
-				if constexpr (METRIC == 2) {
-					// the row's raw inputs go to LDS; sixteen lanes form the symmetric terms from them after the barrier below, so the walk keeps
+				if constexpr (METRIC >= 2) {
+					// the row's raw inputs go to LDS; sixteen lanes form the symmetric (METRIC 3: the generalized) terms from them after the barrier below, so the walk keeps
 					// metric 1's registers (its K = 3 form is at the 64-VGPR bound).  The query's index again (a valid row's i is below N), from
 					// the lane and wave numbers as the hardware gives them
 					const float4 nm = normals[r.idx];
@@ -4217,6 +4315,10 @@ __device__ __forceinline__ void pose_info_body(const float4* src, int N, const P
 		if (threadIdx.x < kIcpThreads / 16) pose_info_symmetric_row(red[threadIdx.x], pa, src_normals);
 		__syncthreads();
 	}
+	if constexpr (METRIC == 3) {
+		if (threadIdx.x < kIcpThreads / 16) pose_info_generalized_row(red[threadIdx.x], pa, src_normals);
+		__syncthreads();
+	}
 	if (threadIdx.x < kWords) {
 		const bool weighted = METRIC != 0 && threadIdx.x < 28;
 		float sum = weighted ? red[0][threadIdx.x] * red[0][kWordW] : red[0][threadIdx.x];
@@ -4255,7 +4357,7 @@ static void launch_pose_info_k(const float4* src, int N, const PoseInfoArgs* h_a
 {
 	const dim3 block(kIcpThreads);
 	const int strided = N <= kIcpStridedMaxN ? 1 : 0;        // the ICP passes' choice
-	with_value<2, 1, 0>(metric, [&](auto M) {
+	with_value<3, 2, 1, 0>(metric, [&](auto M) {
 		if (h_args)
 			hipLaunchKernelGGL((pose_info_kernel<K, M()>), dim3(icp_blocks(N)), block, 0, stream, src, N, *h_args, strided, kd, dt, normals, acc, src_normals);
 		else
@@ -4268,7 +4370,7 @@ static hipError_t launch_pose_info_any(const float4* src, int N, const PoseInfoA
                                        const KdDesc& kd, const DtDesc& dt, const float4* normals, unsigned long long* acc, const float4* src_normals,
                                        hipStream_t stream)
 {
-	if (N <= 0 || !acc || !dt.layout || metric < 0 || metric > 2 || (metric != 0 && !normals) || (metric == 2 && !src_normals) || n_poses < 1 ||
+	if (N <= 0 || !acc || !dt.layout || metric < 0 || metric > 3 || (metric != 0 && !normals) || (metric >= 2 && !src_normals) || n_poses < 1 ||
 	    n_poses > kIcpBatchMax)
 		return hipErrorInvalidValue;
 	with_k(kd.K, [&](auto K) { launch_pose_info_k<K()>(src, N, h_args, d_args, n_poses, metric, kd, dt, normals, acc, src_normals, stream); });

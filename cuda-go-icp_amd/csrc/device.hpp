@@ -363,7 +363,9 @@ constexpr double kIcpRobustWScale = 68719476736.0;   // 2^36
 //   kIcpModeRobust  W (scaled by kIcpRobustWScale) in word kIcpGateCountWord[metric] = 16 / 28, C (scaled by the pass's acc_scale) in the word
 //                   after it, 17 / 29
 // metric 2 is internal: metric 1 in its symmetric form (goicp_set_icp_symmetric), metric 1's words and modes, src_normals beside normals.
-// Anything else -- a null states or acc, a metric outside 0..2, metric 1 / 2 without normals, metric 2 without src_normals, metric 0 or a mode on the linear DT, n_active outside
+// metric 3 is internal: metric 1 in its generalized form (goicp_set_icp_generalized), likewise, with gicp_eps; an eps outside [kGicpEpsMin, 1] is refused.
+constexpr float kGicpEpsMin = 1e-4f;
+// Anything else -- a null states or acc, a metric outside 0..3, metric 1 / 2 / 3 without normals, metric 2 / 3 without src_normals, metric 0 or a mode on the linear DT, n_active outside
 // [1, kIcpBatchMax] or != 1 without a list, the default cell -- is hipErrorInvalidValue without a launch.
 enum IcpMode : int { kIcpModePlain = 0, kIcpModeGate = 1, kIcpModeRobust = 2 };
 constexpr int kIcpBatchMax = 1024;
@@ -373,12 +375,13 @@ struct IcpOptArgs {
 	IcpState* states;             // the loop state; batch: kIcpBatchMax slots at most
 	const int* active;            // nullptr: single pose
 	int n_active;                 // 1 for a single pose
-	int metric;                   // 0 point-to-point, 1 point-to-plane, 2 symmetric point-to-plane
+	int metric;                   // 0 point-to-point, 1 point-to-plane, 2 symmetric point-to-plane, 3 generalized (plane-to-plane)
 	int mode;                     // IcpMode
 	const float4* normals;        // metric 1: one per target point (launch_normal_build)
 	unsigned long long* acc;
 	int capped;                   // kIcpModeGate: the walk's pruning bound starts at min(seed distance, g2) -- exact for every inlier, no neighbour for an outlier
-	const float4* src_normals = nullptr;   // metric 2: one per source point, parallel to src (launch_source_normals_gather)
+	const float4* src_normals = nullptr;   // metric 2 / 3: one per source point, parallel to src (launch_source_normals_gather)
+	float gicp_eps = 0.f;                  // metric 3: epsilon, in [kGicpEpsMin, 1]
 };
 hipError_t launch_icp_iteration_opt(const IcpOptArgs& a, const KdDesc& kd, const DtDesc& dt, hipStream_t stream);
 
@@ -394,10 +397,10 @@ struct PoseInfoArgs {
 	int32_t rk;         // robust kernel, 0 = none
 	float rc;           // its scale
 	float scale;        // fixed-point scale of the sums
-	int32_t pad;
+	float eps;          // metric 3: the generalized form's epsilon (0 elsewhere)
 };
 static_assert(sizeof(PoseInfoArgs) == 80, "PoseInfoArgs layout");
-constexpr int kPoseInfoWords[3] = {19, 31, 31};   // [2]: the symmetric form of metric 1 (src_normals beside normals), metric 1's layout
+constexpr int kPoseInfoWords[4] = {19, 31, 31, 31};   // [2], [3]: the symmetric and the generalized form of metric 1 (src_normals beside normals), metric 1's layout
 hipError_t launch_pose_info(const float4* src, int N, const PoseInfoArgs& args, int metric, const KdDesc& kd, const DtDesc& dt, const float4* normals,
                             unsigned long long* acc, hipStream_t stream, const float4* src_normals = nullptr);
 // n_poses <= kIcpBatchMax argument blocks in device memory, slot s adding into acc + s * kIcpBatchAccWords: each slot the single call bit for bit

@@ -489,13 +489,13 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 	// part of the source stage (the first ICP after a swap is not charged for them), otherwise they are built on first use
 	src_normals_k_ = 0;
 	src_normals_user_ = false;
-	if (symmetric_active()) build_source_normals(source, d_xyz, on_device ? d_perm.get() : nullptr);
+	if (source_normals_active()) build_source_normals(source, d_xyz, on_device ? d_perm.get() : nullptr);
 }
 
 void Engine::check_swap_size(size_t n, const char* fn) const
 {
-	if (icp_symmetric_ && n < (size_t)source_normal_k_)
-		throw std::invalid_argument(std::string(fn) + ": the cloud has fewer points than the handle's source_normal_k (goicp_set_icp_symmetric)");
+	if (reads_source_normals() && n < (size_t)source_normal_k_)
+		throw std::invalid_argument(std::string(fn) + ": the cloud has fewer points than the handle's source_normal_k (goicp_set_icp_symmetric / goicp_set_icp_generalized)");
 }
 
 void Engine::sync_lane_streams()
@@ -759,20 +759,38 @@ void Engine::check_symmetric_query(const char* fn) const
 void Engine::set_icp_symmetric(int enabled, int source_normal_k)
 {
 	if (enabled != 0 && enabled != 1) throw std::invalid_argument("goicp_set_icp_symmetric: enabled must be 0 or 1");
-	if (source_normal_k < 3 || source_normal_k > kKnnMax) throw std::invalid_argument("goicp_set_icp_symmetric: source_normal_k must be in [3, 32]");
-	if ((size_t)source_normal_k > N_) throw std::invalid_argument("goicp_set_icp_symmetric: source_normal_k exceeds the number of source points");
-	if (enabled && p_.trim_fraction > 0.f) throw std::invalid_argument("goicp_set_icp_symmetric: symmetric ICP with trim_fraction > 0 is not supported");
-	check_symmetric_query("goicp_set_icp_symmetric");
+	if (enabled && icp_generalized_) throw std::invalid_argument("goicp_set_icp_symmetric: the handle's generalized flag is on (goicp_set_icp_generalized)");
+	set_normal_form("goicp_set_icp_symmetric", enabled != 0, enabled != 0, icp_generalized_, gicp_eps_, source_normal_k);
+}
+
+void Engine::set_icp_generalized(int enabled, float epsilon, int source_normal_k)
+{
+	if (enabled != 0 && enabled != 1) throw std::invalid_argument("goicp_set_icp_generalized: enabled must be 0 or 1");
+	if (!(epsilon >= kGicpEpsMin && epsilon <= 1.f)) throw std::invalid_argument("goicp_set_icp_generalized: epsilon must be in [1e-4, 1]");
+	if (enabled && icp_symmetric_) throw std::invalid_argument("goicp_set_icp_generalized: the handle's symmetric flag is on (goicp_set_icp_symmetric)");
+	set_normal_form("goicp_set_icp_generalized", enabled != 0, icp_symmetric_, enabled != 0, epsilon, source_normal_k);
+}
+
+// enabled: the value the calling setter gives its own flag; symmetric / generalized: both flags after the call
+void Engine::set_normal_form(const char* fn, bool enabled, bool symmetric, bool generalized, float epsilon, int source_normal_k)
+{
+	const std::string f(fn);
+	if (source_normal_k < 3 || source_normal_k > kKnnMax) throw std::invalid_argument(f + ": source_normal_k must be in [3, 32]");
+	if ((size_t)source_normal_k > N_) throw std::invalid_argument(f + ": source_normal_k exceeds the number of source points");
+	if (enabled && p_.trim_fraction > 0.f) throw std::invalid_argument(f + ": this form of ICP with trim_fraction > 0 is not supported");
+	check_symmetric_query(fn);
 	if (enabled && icp_gated() && gate_min_inliers_ != 0 && gate_min_inliers_ < 6)
-		throw std::invalid_argument("goicp_set_icp_symmetric: the handle's gate has min_inliers below point-to-plane's floor of 6");
-	const bool was = symmetric_active();
-	icp_symmetric_ = enabled != 0;
+		throw std::invalid_argument(f + ": the handle's gate has min_inliers below point-to-plane's floor of 6");
+	const int was = source_normals_active() ? icp_kernel_metric() : 0;
+	icp_symmetric_ = symmetric;
+	icp_generalized_ = generalized;
+	gicp_eps_ = epsilon;
 	source_normal_k_ = source_normal_k;
-	if (symmetric_active()) {
+	if (source_normals_active()) {
 		DeviceGuard guard(dev_);
 		ensure_source_normals();
-		if (!was) {
-			// the first launch of the symmetric kernels (code object load) belongs here, not to the first refinement: one frozen pass
+		if (was != icp_kernel_metric()) {
+			// the first launch of the form's kernels (code object load) belongs here, not to the first refinement: one frozen pass
 			const float I0[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z0[3] = {0, 0, 0};
 			icp_state_init(I0, Z0, 0.f, 0, 1);
 			icp_launch_one();
@@ -1628,8 +1646,8 @@ void Engine::pose_information(size_t K, const float* R, const float* t, const go
 	const int metric = o.metric < 0 ? icp_metric_ : o.metric;
 	DeviceGuard guard(dev_);
 	if (metric == 1) ensure_normals(normal_k_);
-	const int kmetric = metric == 1 && icp_symmetric_ ? 2 : metric;     // the symmetric form wherever metric 1 is evaluated on a flagged handle
-	if (kmetric == 2) ensure_source_normals();
+	const int kmetric = kernel_metric(metric);     // the symmetric or generalized form wherever metric 1 is evaluated on a flagged handle
+	if (kmetric >= 2) ensure_source_normals();
 	if (src_crad_ < 0.0) {
 		// largest distance of a source point from the source centroid: with the default pivot |a| <= |R| * this
 		double m = 0.0;
@@ -1660,7 +1678,7 @@ void Engine::pose_information(size_t K, const float* R, const float* t, const go
 		a.g2 = icp_gated() ? gate_dist_ * gate_dist_ : INFINITY;   // icp_state_fill's float product
 		a.rk = robust_kernel_;
 		a.rc = robust_scale_;
-		a.pad = 0;
+		a.eps = kmetric == 3 ? gicp_eps_ : 0.f;
 		// fixed-point scale: |a| <= Ba, |e| <= E, |n| <= 1, so every term is below T^2 with T = 2 (max(Ba, E) + 1), and N of them must fit 2^62
 		const double Ba = rho * src_crad_ + std::sqrt(off);
 		const double E = rho * (double)src_radius_ + std::sqrt(tl) + std::sqrt(3.0) * (double)target_abs_max_;
@@ -1744,7 +1762,7 @@ void Engine::result_information(const goicp_pose_info_options* opt, goicp_pose_i
 void Engine::icp_state_init(const float R[9], const float t[3], float err_diff, int carry_means, int frozen)
 {
 	icp_cache_active_ = false;          // icp_nn_cache = 2: every run starts with plain walks
-	if (symmetric_active()) ensure_source_normals();   // built with the flag, the metric or the swap: a no-op but after set_icp_options(1) on a flagged handle
+	if (source_normals_active()) ensure_source_normals();   // built with the flag, the metric or the swap: a no-op but after set_icp_options(1) on a flagged handle
 	icp_state_fill(*h_icp_state_, R, t, err_diff, carry_means, frozen);
 	HIPCHK(hipMemcpyAsync(d_icp_state_, h_icp_state_, sizeof(IcpState), hipMemcpyHostToDevice, stream_));
 }
@@ -1793,7 +1811,7 @@ void Engine::icp_launch_one()
 	// a kernel or a gate, either metric (set_icp_robust / set_icp_gate refuse each other, trimming, the linear DT and the fused iteration), or
 	// point-to-plane (set_icp_options refuses it together with trimming)
 	if (icp_mode() != kIcpModePlain || icp_metric_ == 1)
-		HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_icp_state_, nullptr, 1, icp_kernel_metric(), icp_mode(), d_normals_, d_icp_acc_opt_, gate_capped_, d_src_normals_}, kd_, dt_, stream_));
+		HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_icp_state_, nullptr, 1, icp_kernel_metric(), icp_mode(), d_normals_, d_icp_acc_opt_, gate_capped_, d_src_normals_, gicp_eps_}, kd_, dt_, stream_));
 	else if (inliers_ < (int)N_)
 		HIPCHK(launch_icp_iteration_trim(d_src_, (int)N_, inliers_, d_icp_state_, kd_, dt_, d_nn_d2_, d_nn_slot_, d_include_, d_icp_partials_, stream_));
 	else
@@ -1900,7 +1918,7 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 	if (registering_.load()) throw std::invalid_argument("goicp_icp_run_batch: not while a registration runs");
 	DeviceGuard guard(dev_);
 	if (icp_metric_ == 1) ensure_normals(normal_k_);
-	if (symmetric_active()) ensure_source_normals();
+	if (source_normals_active()) ensure_source_normals();
 	ensure_icp_batch(K);
 	IcpState* up = h_batch_states_;
 	for (size_t k = 0; k < K; k++) icp_state_fill(up[k], R + 9 * k, t + 3 * k, err_diff, 1, 0);
@@ -1920,7 +1938,7 @@ void Engine::icp_run_batch(size_t K, float* R, float* t, int max_iter, float err
 		std::memcpy(h_act, act.data(), sizeof(int) * n_active);
 		HIPCHK(hipMemcpyAsync(d_act, h_act, sizeof(int) * n_active, hipMemcpyHostToDevice, stream_));
 		for (int i = 0; i < k; i++)
-			HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_batch_states_, d_act, n_active, icp_kernel_metric(), icp_mode(), d_normals_, d_batch_acc_, gate_capped_, d_src_normals_}, kd_, dt_, stream_));
+			HIPCHK(launch_icp_iteration_opt({d_src_, (int)N_, d_batch_states_, d_act, n_active, icp_kernel_metric(), icp_mode(), d_normals_, d_batch_acc_, gate_capped_, d_src_normals_, gicp_eps_}, kd_, dt_, stream_));
 		queued += k;
 		HIPCHK(hipMemcpyAsync(slots[slot], d_batch_states_, sizeof(IcpState) * K, hipMemcpyDeviceToHost, stream_));
 		HIPCHK(hipEventRecord(evs[slot], stream_));
@@ -2038,12 +2056,17 @@ int Engine::icp_run_collective(const goicp_comm_ops* comm, float R[9], float t[3
 			const int32_t si[2] = {1, source_normal_k_};
 			h = fnv1a(h, si, sizeof(si));
 		}
+		if (icp_generalized_) {                        // and the generalized flag with epsilon's bits and its source_normal_k
+			int32_t gi[3] = {2, 0, source_normal_k_};
+			std::memcpy(&gi[1], &gicp_eps_, sizeof(float));
+			h = fnv1a(h, gi, sizeof(gi));
+		}
 		uint64_t w[3] = {h, ~h, health()};
 		const int rc = comm->allreduce_min_u64(comm->ctx, w, 3);
 		if (rc != GOICP_OK) return rc;
 		ss.collectives++;
 		if (w[2] != kHealthyWord) return leave(w[2]);
-		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric, symmetric flag, gate, robust kernel or scale) or clouds");
+		if (w[0] != ~w[1]) throw StatusError(GOICP_ERR_INVALID, "goicp_icp_run_collective: the ranks were called with different arguments (pose, max_iter, err_diff, ICP metric, symmetric or generalized flag, gate, robust kernel or scale) or clouds");
 	}
 
 	const long long passes0 = cnt_.icp_iters;

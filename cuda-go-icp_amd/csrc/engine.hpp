@@ -187,6 +187,12 @@ public:
 	int source_normal_k() const { return source_normal_k_; }
 	bool user_source_normals() const { return src_normals_user_; }
 	void check_symmetric_query(const char* fn) const;            // what every entry point of the feature refuses: a running registration
+	// goicp_set_icp_generalized: the other modifier of metric 1 -- generalized (plane-to-plane) ICP, a 3 x 3 weight per correspondence from the
+	// normals of both clouds (include/goicp_mi355.h).  Stored and inert under metric 0; it shares source_normal_k and the source normals with
+	// the symmetric flag, and the two refuse each other.  Refused beyond that: epsilon outside [1e-4, 1], and what set_icp_symmetric refuses
+	void set_icp_generalized(int enabled, float epsilon, int source_normal_k);
+	bool icp_generalized() const { return icp_generalized_; }
+	float gicp_epsilon() const { return gicp_eps_; }
 	void source_normals(float* normals_xyz);                     // N x 3, original source order (built on first use)
 	// the caller's own normals (original source order; each exactly zero or of length within 1e-3 of 1), in the place of the estimated ones
 	// until the next source swap
@@ -569,13 +575,21 @@ private:
 	int source_normal_k_ = 16, src_normals_k_ = 0;        // src_normals_k_: the k the estimated normals were built with (0: none yet)
 	Buf<float4> d_src_normals_;                           // N, the source's order; grow-only
 	double source_normal_build_ms_ = 0;
-	bool symmetric_active() const { return icp_symmetric_ && icp_metric_ == 1; }
-	int icp_kernel_metric() const { return symmetric_active() ? 2 : icp_metric_; }   // launch_icp_iteration_opt's
+	// generalized ICP (opt-in): the flag and its epsilon; the source normals are the symmetric form's
+	bool icp_generalized_ = false;
+	float gicp_eps_ = 1e-3f;
+	bool reads_source_normals() const { return icp_symmetric_ || icp_generalized_; }                 // a flag that reads them is set
+	bool source_normals_active() const { return reads_source_normals() && icp_metric_ == 1; }        // and its form is the one every ICP runs
+	// launch_icp_iteration_opt's and launch_pose_info's metric where the public one is `metric`
+	int kernel_metric(int metric) const { return metric != 1 ? metric : icp_generalized_ ? 3 : icp_symmetric_ ? 2 : 1; }
+	int icp_kernel_metric() const { return kernel_metric(icp_metric_); }
+	// what the two flags' setters share: the refusals, the flags' new values, the source normals and the form's first launch
+	void set_normal_form(const char* fn, bool enabled, bool symmetric, bool generalized, float epsilon, int source_normal_k);
 	void ensure_source_normals();
 	// launch_estimate_normals on the source in the caller's point order, then the gather into the source's order.  d_xyz / d_perm: the cloud and
 	// the permutation where they are on the device already (a swap), else both are uploaded
 	void build_source_normals(const float* h_xyz, const float* d_xyz, const int32_t* d_perm);
-	void check_swap_size(size_t n, const char* fn) const;   // a swap to fewer than source_normal_k points is refused while the flag is on
+	void check_swap_size(size_t n, const char* fn) const;   // a swap to fewer than source_normal_k points is refused while either flag is on
 	// pose information (allocated on first use, grown on demand): one accumulator block (kIcpBatchAccWords) and one argument block per pose
 	Buf<unsigned long long> d_info_acc_; Buf<PoseInfoArgs> d_info_args_;
 	double src_crad_ = -1.0;           // largest distance of a source point from the source centroid (first use)

@@ -816,6 +816,24 @@ int goicp_get_icp_symmetric(goicp_handle h, int32_t* enabled, int32_t* source_no
 	});
 }
 
+int goicp_set_icp_generalized(goicp_handle h, int32_t enabled, float epsilon, int32_t source_normal_k)
+{
+	REQUIRE(h);
+	return guarded([&] { h->e->set_icp_generalized(enabled, epsilon, source_normal_k); });
+}
+
+int goicp_get_icp_generalized(goicp_handle h, int32_t* enabled, float* epsilon, int32_t* source_normal_k, int32_t* user_normals)
+{
+	REQUIRE(h && enabled && epsilon && source_normal_k && user_normals);
+	return guarded([&] {
+		h->e->check_symmetric_query("goicp_get_icp_generalized");
+		*enabled = h->e->icp_generalized() ? 1 : 0;
+		*epsilon = h->e->gicp_epsilon();
+		*source_normal_k = h->e->source_normal_k();
+		*user_normals = h->e->user_source_normals() ? 1 : 0;
+	});
+}
+
 int goicp_source_normals(goicp_handle h, float* normals_xyz)
 {
 	REQUIRE(h && normals_xyz);

@@ -328,7 +328,7 @@ class Registration:
     """icp::Registration(pct, nt, pcs, ns): owns the device-resident clouds, DT and k-d tree."""
 
     def __init__(self, pct, pcs, mse_threshold=1e-3, icp_metric=None, normal_k=None, max_corr_dist=None, robust_kernel=0, robust_scale=0.0, trunc_dist=None,
-                 icp_symmetric=False, source_normal_k=16, **params):
+                 icp_symmetric=False, source_normal_k=16, icp_generalized=False, gicp_epsilon=1e-3, **params):
         """icp_metric / normal_k (not goicp_params fields): goicp_set_icp_options after creation -- 1 makes every ICP of this
         engine point-to-plane (target normals from normal_k neighbours, default 16); None keeps the defaults untouched.
         max_corr_dist: goicp_set_icp_gate after creation -- every ICP of this engine uses only correspondences within that distance.
@@ -337,7 +337,10 @@ class Registration:
         trunc_dist: goicp_set_search_truncation after creation -- the search (bounds, pose scores, best_sse) minimises
         sum min(DT(R p + t), trunc_dist)^2 instead of the plain sum of squares; None or 0 keeps the plain objective.
         icp_symmetric / source_normal_k: goicp_set_icp_symmetric after creation -- wherever this engine evaluates metric 1 it takes the
-        symmetric point-to-plane form over the normals of both clouds (source normals from source_normal_k neighbours); inert under metric 0."""
+        symmetric point-to-plane form over the normals of both clouds (source normals from source_normal_k neighbours); inert under metric 0.
+        icp_generalized / gicp_epsilon: goicp_set_icp_generalized after creation -- wherever this engine evaluates metric 1 it takes the
+        generalized (plane-to-plane) form, every correspondence weighted by the combined covariance of both normals; it shares source_normal_k
+        with the symmetric flag, the two refuse each other; inert under metric 0."""
         self._lib = B.load_library()
         self.pct, self.pcs = _f32(pct, (-1, 3)), _f32(pcs, (-1, 3))
         p = B.CParams()
@@ -387,6 +390,13 @@ class Registration:
         if icp_symmetric:
             try:
                 self.set_icp_symmetric(True, source_normal_k)
+            except Exception:
+                self.close()
+                raise
+
+        if icp_generalized:
+            try:
+                self.set_icp_generalized(True, gicp_epsilon, source_normal_k)
             except Exception:
                 self.close()
                 raise
@@ -655,6 +665,18 @@ class Registration:
         B.check(self._lib.goicp_get_icp_symmetric(self.handle, C.byref(e), C.byref(k), C.byref(u)))
         return bool(e.value), k.value, bool(u.value)
 
+    # ---- generalized (plane-to-plane) ICP (goicp_set_icp_generalized) ----
+    def set_icp_generalized(self, enabled=True, epsilon=1e-3, source_normal_k=16):
+        """goicp_set_icp_generalized: metric 1 in its generalized form, W = 2 eps (C_m + R C_p R^T)^-1 from the normals of both clouds; stored
+        and inert under metric 0."""
+        B.check(self._lib.goicp_set_icp_generalized(self.handle, int(bool(enabled)), float(epsilon), int(source_normal_k)))
+
+    def get_icp_generalized(self):
+        """goicp_get_icp_generalized -> (enabled, epsilon, source_normal_k, user_normals)"""
+        e, eps, k, u = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32()
+        B.check(self._lib.goicp_get_icp_generalized(self.handle, C.byref(e), C.byref(eps), C.byref(k), C.byref(u)))
+        return bool(e.value), eps.value, k.value, bool(u.value)
+
     def source_normals(self):
         """(N, 3) float32 source normals in the source's original order: the estimated ones (built on first use) or the caller's"""
         n = np.empty((self.ns, 3), np.float32)
@@ -809,6 +831,7 @@ class FastGoICP:
     fields are a consistent snapshot (the reference published them unlocked)."""
 
     def __init__(self, pct, pcs, mse_threshold, mtx=None, icp_metric=None, normal_k=None, max_corr_dist=None, trunc_dist=None, **params):
+        # icp_symmetric / icp_generalized / gicp_epsilon / source_normal_k and the goicp_params fields travel in **params
         self.registration = Registration(pct, pcs, mse_threshold, icp_metric=icp_metric, normal_k=normal_k, max_corr_dist=max_corr_dist,
                                          trunc_dist=trunc_dist, **params)
         self.mtx = mtx or threading.Lock()

@@ -662,6 +662,53 @@ int goicp_source_normals(goicp_handle h, float* normals_xyz);
  * stored as given */
 int goicp_set_source_normals(goicp_handle h, const float* normals_xyz, size_t n);
 
+/* ---- generalized (plane-to-plane) ICP (opt-in; the other per-handle modifier of metric 1, not a metric value of its own) -----------
+ * Generalized-ICP (Segal, Haehnel, Thrun, RSS 2009) in its plane-to-plane version -- PCL's GeneralizedIterativeClosestPoint, Open3D's
+ * registration_generalized_icp -- in the incremental form of the point-to-plane iteration above.  Each cloud's local surface covariance
+ * has the eigenvalues (1, 1, epsilon) about the point's normal n, C = I - (1 - epsilon) n n^T, a function of the normal alone, and a
+ * correspondence is weighted by the inverse of the two covariances' sum.  goicp_set_icp_options(2, ..), (3, ..) and
+ * goicp_pose_information(metric = 2) stay refused; no struct changes size; goicp_abi_version() stays 4.  The flag takes effect wherever
+ * metric 1 is evaluated on the handle -- goicp_icp_run, _step, _run_batch, goicp_time_icp_pass, the refinements of goicp_register (every
+ * driver) and of goicp_register_sharded*, goicp_pose_information[_batch] and goicp_result_information with metric -1 or 1 -- and is
+ * stored and inert under metric 0; a handle that never sets it runs none of this.  For a correspondence with q = R p + t (the engine's
+ * float expression), m the nearest target point (the unchanged walk: same index, same d^2 bits), u = the target normal of m and
+ * ns = the source normal of p, e = q - m and a = q - cq (cq the pivot) -- in float, every sum left to right as written, without
+ * contraction, `/` the correctly rounded division:
+ *   s   = R ns                       by the row expression of q without t (the symmetric form's);
+ *   k   = 1 - epsilon,  h = 2 * epsilon;
+ *   Sigma = 2 I - k (u u^T + s s^T), its six unique entries:
+ *     Sxx = 2 - k * (u.x * u.x + s.x * s.x)      Syy, Szz likewise;
+ *     Sxy = -(k * (u.x * u.y + s.x * s.y))       Sxz, Syz likewise.
+ *     A normal that is exactly zero adds exact zeros, so that point's covariance is I; no product sees a normal's sign;
+ *   the cofactors  C00 = Syy * Szz - Syz * Syz   C01 = Sxz * Syz - Sxy * Szz   C02 = Sxy * Syz - Sxz * Syy
+ *                  C11 = Sxx * Szz - Sxz * Sxz   C12 = Sxy * Sxz - Sxx * Syz   C22 = Sxx * Syy - Sxy * Sxy
+ *   det = Sxx * C00 + Sxy * C01 + Sxz * C02;
+ *   W   = 2 epsilon Sigma^-1:  Wij = (h * Cij) / det.   Sigma's eigenvalues lie in [2 epsilon, 2], so W's lie in [epsilon, 1]: the
+ *         minimiser is that of sum e^T Sigma^-1 e, and every summed term keeps point-to-plane's bound (|n| <= 1 there).
+ *         epsilon = 1: W = I exactly (point-to-point Gauss-Newton about the pivot); both normals zero: W = epsilon I exactly;
+ *   g   = W e:   g.x = W00 * e.x + W01 * e.y + W02 * e.z   (rows of the symmetric W likewise);
+ *   the system linearised with e' = e + omega x a + tau:
+ *     right-hand side  b = (a x g, g),   a x g = (a.y * g.z - a.z * g.y, a.z * g.x - a.x * g.z, a.x * g.y - a.y * g.x);
+ *     M = [a]x W, row i the i-th component of a x (column j of W):  M0j = a.y * W2j - a.z * W1j,  M1j = a.z * W0j - a.x * W2j,
+ *                                                                    M2j = a.x * W1j - a.y * W0j;
+ *     H_tt = W,  H_wt = M,  H_ww = M [a]x^T:  Hi0 = Mi2 * a.y - Mi1 * a.z,  Hi1 = Mi0 * a.z - Mi2 * a.x,  Hi2 = Mi1 * a.x - Mi0 * a.y;
+ *     the 21 words are the upper triangle of [[H_ww, H_wt], [., H_tt]] in point-to-plane's J J^T order, the 28th word is d^2.
+ * Everything after these 28 words is point-to-plane's: the 64-bit fixed-point replicas, the damped fp64 Cholesky step, the pose and pivot
+ * update, ICP3D::Run's stop rule on sum d^2 (err keeps its meaning), the gate's inlier word.  Under a robust kernel
+ * (goicp_set_icp_robust) the weight is taken of the Euclidean distance d = sqrt(d^2) -- metric 0's argument: the residual here is a
+ * vector -- it multiplies the 27 terms in the column sums, and rho of d goes to the cost.  goicp_pose_information reports sum w e^T W e
+ * where point-to-plane reports sum w r^2.
+ * epsilon must lie in [1e-4, 1]; the default is 1e-3, PCL's gicp_epsilon and Open3D's.  source_normal_k (3..32, at most N) and the
+ * source normals are the symmetric flag's: goicp_source_normals and goicp_set_source_normals serve both flags -- built on first use,
+ * rebuilt inside every source swap (goicp_set_source, _voxel, _filtered, _pipeline, _clustered, _segmented) while a flag is on and
+ * metric 1 is active, dropped at every swap otherwise; a swap to fewer than source_normal_k points is refused before anything changes.
+ * Refused with GOICP_ERR_INVALID, changing nothing: a NULL argument, epsilon or source_normal_k out of range, enabled together with
+ * trim_fraction > 0 or with a gate whose min_inliers is below 6, any call while a registration runs, enabled while the symmetric flag
+ * is on -- and goicp_set_icp_symmetric(1, ..) while this flag is on.  goicp_icp_run_collective runs the form replicated on every rank
+ * (the flag, epsilon's bits and source_normal_k join its check word); goicp_register_multi_gpu stays point-to-point. */
+int goicp_set_icp_generalized(goicp_handle h, int32_t enabled, float epsilon, int32_t source_normal_k);
+int goicp_get_icp_generalized(goicp_handle h, int32_t* enabled, float* epsilon, int32_t* source_normal_k, int32_t* user_normals);
+
 /* ---- distance-gated ICP (opt-in; new: a maximum correspondence distance, the outlier rule of PCL / Open3D) ----------------------
  * The gate applies to every ICP the handle runs, both metrics: goicp_icp_run, goicp_icp_run_batch, goicp_icp_step, goicp_time_icp_pass, the
  * ICP inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded* (the DT re-score of a refined pose still scores

@@ -368,7 +368,21 @@ public:
 		check(goicp_get_icp_symmetric(h_, &e, &k, &u));
 		return IcpSymmetric{e != 0, (int)k, u != 0};
 	}
-	// the source normals the symmetric form reads (original source order): the estimated ones, built on first use, or the caller's
+	// metric 1 in its generalized (plane-to-plane) form, each correspondence weighted by the combined covariance of both clouds' normals
+	// (goicp_set_icp_generalized); stored and inert under metric 0; the symmetric flag and this one refuse each other
+	void set_icp_generalized(bool enabled, float epsilon = 1e-3f, int source_normal_k = 16)
+	{
+		check(goicp_set_icp_generalized(h_, enabled ? 1 : 0, epsilon, (int32_t)source_normal_k));
+	}
+	struct IcpGeneralized { bool enabled; float epsilon; int source_normal_k; bool user_normals; };
+	IcpGeneralized get_icp_generalized() const
+	{
+		int32_t e = 0, k = 0, u = 0;
+		float eps = 0.f;
+		check(goicp_get_icp_generalized(h_, &e, &eps, &k, &u));
+		return IcpGeneralized{e != 0, eps, (int)k, u != 0};
+	}
+	// the source normals the symmetric and the generalized form read (original source order): the estimated ones, built on first use, or the caller's
 	template <class Point3>
 	void source_normals(std::vector<Point3>& normals) const
 	{
