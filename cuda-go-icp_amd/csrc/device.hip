@@ -1177,7 +1177,21 @@ __device__ __forceinline__ unsigned order_key(const float (&c)[3], const float (
 // thread keeps the centres and keys of its first kOrderHeld groups of the run in registers from the extent to the scatter (a longer run
 // loads the rest again in each phase), and the scatter writes order[] and the pair list straight from the slot the counting sort hands out.
 constexpr int kOrderHeld = 4;                        // runs of up to 4 096 groups; eight spill at the 128 VGPRs of a 1 024-thread workgroup
-__global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __restrict__ cubes, int B, int G, DtDesc dt, BoundsOrder bo)
+// The first wavefront of block 0 leaves the cuts of the pair launch's 8-chunk shape behind ctl[0..3] on both exits: lane x forms cut[x] from the
+// plan the source cloud left (bounds_cut_of: one division, all nine side by side), the bound of a piece is enforced along the lanes
+// (bounds_cut_cap's two passes), lanes 0 .. 8 store.  balanced = 0: the equal split.  Called by all 64 lanes of the wavefront.
+__device__ __forceinline__ void bounds_cuts_store(const BoundsOrder& bo, int balanced, int items, int lane)
+{
+	const int x = min(lane, 8);
+	int cut = balanced ? bounds_cut_of(bo.cost + kBoundsCost, x, items) : x * items;
+	if (balanced) {
+		const int cap = (int)(((long long)items * 5 + 3) / 4);
+		for (int k = 1; k < 8; k++) { const int prev = __shfl(cut, k - 1, 64); if (lane == k) cut = min(cut, prev + cap); }
+		for (int k = 7; k >= 1; k--) { const int next = __shfl(cut, k + 1, 64); if (lane == k) cut = max(cut, next - cap); }
+	}
+	if (lane <= 8) bo.ctl[kBoundsCut + lane] = cut;
+}
+__global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __restrict__ cubes, int B, int G, DtDesc dt, BoundsOrder bo, int balanced)
 {
 	constexpr int per = kSortBins / 1024;            // 32 consecutive bins per thread, padded against the bank conflict (task_scan_kernel)
 	constexpr int words = kSortBins + kSortBins / per;
@@ -1211,7 +1225,10 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	__syncthreads();
 	const int nb = nbound, runs = nb + 1;
 	if (runs > bo.max_runs) {
-		if (blockIdx.x == 0 && tid == 0) { bo.ctl[0] = 0; bo.ctl[1] = 0; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1; }
+		if (blockIdx.x == 0 && tid == 0) {
+			bo.ctl[0] = 0; bo.ctl[1] = 0; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1;
+		}
+		if (blockIdx.x == 0 && tid < 64) bounds_cuts_store(bo, balanced, (G + 1) >> 1, tid);
 		return;
 	}
 	if (tid == 0) { run_start[0] = 0; run_start[runs] = G; }
@@ -1228,6 +1245,7 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	int item0 = 0, items = 0;
 	for (int q = 0; q < runs; q++) { if (q == run) item0 = items; items += (run_start[q + 1] - run_start[q] + 1) >> 1; }
 	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = (long long)G << 1; }
+	if (run == 0 && tid < 64) bounds_cuts_store(bo, balanced, items, tid);
 	// the extent of the run's centres (a thread without a k-th group holds the run's last one again: it changes neither the extent nor, below, a counter)
 	float held[kOrderHeld][3];
 	float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -1356,8 +1374,19 @@ __device__ __forceinline__ bool same_box(const PairMember& a, const PairMember& 
 // Thread 0 of the item's chunk-0 workgroup counts the form in ctl[2] / ctl[3] (goicp_debug_bounds_twins).
 // A batch the pre-pass left alone (ctl[1] = 0) is evaluated here too, two groups per item in arrival order on the plain path: the grid of
 // bounds_order_items(groups, max_runs) >= (groups + 1) / 2 items covers it, and no second launch is needed.
+// The 8-chunk shape (chunks == 8) takes its units from the cuts the pre-pass left behind ctl[0..3] (bounds_cuts): block label x = work & 7
+// evaluates the units cut[x] .. cut[x + 1] - 1 of the chunk-major list u = chunk * items + item, so a label whose chunk gathers more lines per
+// wavefront hands the tail of its chunk to its neighbour.  The map is a bijection of the blocks below cut[x + 1] - cut[x] per label onto the
+// units whatever XCD a label lands on; the grid is 8 * bounds_pair_slots(max_items) and the surplus leaves at once.  Equal cuts
+// (cut[x] = x * items: bounds_balance = 0, a batch the pre-pass left alone included) are the static map chunk = x.
+#ifdef GOICP_BOUNDS_XCD_STAMPS
+// diagnostic build only (make stamps): the kernel below becomes the body of a kernel that stamps its entry and exit per XCC
+#define GOICP_BOUNDS_PAIR_HEAD __device__ __forceinline__ void bounds_pair_body
+#else
+#define GOICP_BOUNDS_PAIR_HEAD __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel
+#endif
 template <bool TRUNC>
-__global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
+GOICP_BOUNDS_PAIR_HEAD(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
     float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl)
@@ -1365,7 +1394,13 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
 	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
 	const int work = blockIdx.x, total = gridDim.x;
 	int chunk, item;
-	if ((chunks & 7) == 0) {
+	if (chunks == 8) {
+		const int xcd = work & 7, u = ctl[kBoundsCut + xcd] + (work >> 3);
+		if (u >= ctl[kBoundsCut + xcd + 1]) return;
+		const int items = ctl[kBoundsCut + 8] >> 3;          // cut[8] = 8 * items
+		chunk = u / items;
+		item = u - chunk * items;
+	} else if ((chunks & 7) == 0) {
 		const int cpx = chunks >> 3, xcd = work & 7, slot = work >> 3;
 		item = slot / cpx;
 		chunk = xcd * cpx + (slot - item * cpx);
@@ -1469,6 +1504,35 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
 		bounds_work<1, true, TRUNC>(bounds_work_of(g, chunk, groups, chunks), groups * chunks, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub_out, lb_out, red);
 	}
 }
+#undef GOICP_BOUNDS_PAIR_HEAD
+#ifdef GOICP_BOUNDS_XCD_STAMPS
+// Per XCC (HW_REG_XCC_ID, the physical XCD) and per block label (work & 7): the first entry and the last exit of a workgroup on the 100 MHz
+// clock, the workgroups, the sum of their times, and for the XCC rows a mask of the labels seen there.  Thread 0 stamps; the barrier makes its
+// exit stamp the workgroup's (every return of the body is taken by the whole workgroup).
+constexpr int kXcdStampStride = 16;                  // a row per 128-B line: the rows do not contend with each other
+__device__ unsigned long long g_xcd_stamps[kXcdStampRows * kXcdStampStride];
+template <bool TRUNC>
+__global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
+    const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
+    const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl)
+{
+	const unsigned long long t0 = wall_clock64();
+	bounds_pair_body<TRUNC>(src, N, dt, rots, cubes, parents, B, groups, max_items, chunks, chunk_pts, scratch, ub_out, lb_out, pairs, ctl);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		const unsigned long long t1 = wall_clock64();
+		const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u;      // hwreg(HW_REG_XCC_ID, 0, 4)
+		const unsigned rows[2] = {xcc, 8u + (blockIdx.x & 7u)};
+		for (int k = 0; k < 2; k++) {
+			unsigned long long* s = g_xcd_stamps + rows[k] * kXcdStampStride;
+			if (t1 - t0 < 100ull) { atomicAdd(s + 5, 1ull); continue; }           // under 1 us: a surplus workgroup that left at once
+			atomicMin(s + 0, t0); atomicMax(s + 1, t1); atomicAdd(s + 2, 1ull); atomicAdd(s + 3, t1 - t0);
+		}
+		atomicOr(g_xcd_stamps + xcc * kXcdStampStride + 4, 1ull << (blockIdx.x & 7u));
+	}
+}
+#endif
 
 // The same evaluation for a batch whose size only the DEVICE knows (the device-resident BnB queues, bnbqueue.hip):
 // *d_groups expansions of 8 children each; a fixed grid walks the (group, chunk) work items, the split of the cloud
@@ -1851,6 +1915,74 @@ hipError_t launch_queue_sort(const ParentRec* parents, const Rot9* rots, const i
 	return hipGetLastError();
 }
 
+// the four poses the chunk cost is counted at: the identity and three fixed rotations (Rodrigues vectors (0.9, -0.5, 0.3), (-0.4, 1.1, 0.8),
+// (0.6, 0.7, -1.3)).  The share of a chunk in the lines is a property of the patch, not of the pose (EXPERIMENTS R9.1): four poses average it.
+__constant__ float kCostRots[4][9] = {
+	{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f},
+	{0.84567982f, -0.449964464f, -0.286980212f, 0.0414698496f, 0.591505408f, -0.805233896f, 0.532076955f, 0.669069052f, 0.518884122f},
+	{0.219921082f, -0.74321264f, 0.631877899f, 0.372148067f, 0.662668586f, 0.649904728f, -0.901743054f, 0.0922243893f, 0.422319949f},
+	{0.122044131f, 0.98462534f, 0.124972485f, -0.646330416f, 0.174399301f, -0.742860556f, -0.753234506f, 0.00988825131f, 0.65767777f}};
+// one thread per point, a wavefront = 64 consecutive points (chunk_pts is a multiple of 256: a wavefront lies in one chunk).  The index is the
+// float fast path's without its exactness test, in separate multiply and add: a cost model, restated operation for operation by the test.
+__global__ __launch_bounds__(256) void bounds_chunk_cost_kernel(const float4* __restrict__ src, int N, int chunk_pts, DtDesc dt, int* __restrict__ cost)
+{
+	const int i = blockIdx.x * 256 + (int)threadIdx.x, lane = (int)threadIdx.x & 63, first_pt = i - lane;
+	if (first_pt >= N) return;
+	const bool have = i < N;
+	const float4 p = src[have ? i : N - 1];
+	const unsigned V = (unsigned)dt.V;
+	int lines = 0;
+	for (int r = 0; r < 4; r++) {
+		const float* R = kCostRots[r];
+		const float rx = R[0] * p.x + R[1] * p.y + R[2] * p.z, ry = R[3] * p.x + R[4] * p.y + R[5] * p.z, rz = R[6] * p.x + R[7] * p.y + R[8] * p.z;
+		const int ix = (int)((rx - dt.xmin_f) * dt.scale_f + 0.5f), iy = (int)((ry - dt.ymin_f) * dt.scale_f + 0.5f), iz = (int)((rz - dt.zmin_f) * dt.scale_f + 0.5f);
+		const bool in = have && (unsigned)ix < V && (unsigned)iy < V && (unsigned)iz < V;
+		// a 256-B brick is two lines: z & 2 picks the half (brick_z)
+		const int line = in ? (int)((((((unsigned)iz >> 2) * (unsigned)dt.VB + ((unsigned)iy >> 2)) * (unsigned)dt.VB + ((unsigned)ix >> 2)) << 1) | (((unsigned)iz >> 1) & 1u)) : -1;
+		bool first = in;
+		for (int j = 0; j < 63; j++) {
+			const int o = __shfl(line, j, 64);
+			if (j < lane && o == line) first = false;
+		}
+		lines += __popcll(__ballot(first));
+	}
+	if (lane == 0) { const int chunk = first_pt / chunk_pts; atomicAdd(cost + chunk, lines); atomicAdd(cost + 8 + chunk, 4); }
+}
+// the plan of the cuts from the totals (bounds_cut_plan): what depends on the cloud and the weight only is worked out here, once
+__global__ void bounds_cut_plan_kernel(int* __restrict__ cost, int a_q8)
+{
+	if (blockIdx.x == 0 && threadIdx.x == 0) bounds_cut_plan(cost, a_q8, cost + kBoundsCost);
+}
+hipError_t launch_bounds_chunk_cost(const float4* src, int N, const DtDesc& dt, int a_q8, int* cost, hipStream_t stream)
+{
+	hipError_t e = hipMemsetAsync(cost, 0, kBoundsCost * sizeof(int), stream);
+	if (e != hipSuccess) return e;
+	if ((N + kBoundsThreads - 1) / kBoundsThreads >= 32 && dt.layout == 1 && bounds_lean(dt)) {   // else no 8-chunk shape (bounds_shape), or no pair launch: no cost, equal cuts
+		int chunk_pts = (N + 7) / 8;
+		chunk_pts = (chunk_pts + kBoundsThreads - 1) / kBoundsThreads * kBoundsThreads;
+		hipLaunchKernelGGL(bounds_chunk_cost_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, src, N, chunk_pts, dt, cost);
+	}
+	hipLaunchKernelGGL(bounds_cut_plan_kernel, dim3(1), dim3(64), 0, stream, cost, a_q8);
+	return hipGetLastError();
+}
+
+hipError_t bounds_xcd_stamps_take(unsigned long long* out, hipStream_t stream)
+{
+#ifdef GOICP_BOUNDS_XCD_STAMPS
+	unsigned long long clear[kXcdStampRows * kXcdStampStride] = {}, got[kXcdStampRows * kXcdStampStride];
+	for (int r = 0; r < kXcdStampRows; r++) clear[r * kXcdStampStride] = ~0ull;
+	hipError_t e = hipStreamSynchronize(stream);
+	if (e == hipSuccess) e = hipMemcpyFromSymbol(got, HIP_SYMBOL(g_xcd_stamps), sizeof(got));
+	if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_stamps), clear, sizeof(clear));
+	for (int r = 0; r < kXcdStampRows; r++)
+		for (int c = 0; c < kXcdStampCols; c++) out[r * kXcdStampCols + c] = got[r * kXcdStampStride + c];
+	return e;
+#else
+	(void)out; (void)stream;
+	return hipErrorNotSupported;
+#endif
+}
+
 hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const CubeRec* cubes, const ParentRec* parents,
                          int B, float* scratch, float* ub, float* lb, hipStream_t stream, const BoundsOrder* bo)
 {
@@ -1859,13 +1991,15 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 	bounds_shape(B, N, &groups, &chunks, &chunk_pts);
 	dim3 grid(groups * chunks), block(kBoundsThreads);
 	if (bo && bo->mode > 0 && cubes && !parents && dt.layout == 1 && bounds_lean(dt) && groups >= bo->min_groups && bo->max_runs >= 1 && bo->max_runs <= kBoundsOrderMaxRuns) {
-		hipLaunchKernelGGL(bounds_order_kernel, dim3(bo->max_runs), dim3(1024), 0, stream, cubes, B, groups, dt, *bo);
+		const bool balanced = bo->mode == 2 && chunks == 8 && bo->balance && bo->cost;
+		hipLaunchKernelGGL(bounds_order_kernel, dim3(bo->max_runs), dim3(1024), 0, stream, cubes, B, groups, dt, *bo, balanced ? 1 : 0);
 		if (bo->mode == 1) {
 			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_ordered_kernel<true> : bounds_ordered_kernel<false>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups,
 			                   chunks, chunk_pts, scratch, ub, lb, bo->order, bo->ctl, 1);
 		} else {
 			const int max_items = (int)bounds_order_items(groups, bo->max_runs);
-			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_pair_kernel<true> : bounds_pair_kernel<false>), dim3(max_items * chunks), block, 0, stream, src, N, dt, rots, cubes, parents,
+			const int nblocks = chunks == 8 ? 8 * bounds_pair_slots(max_items, balanced) : max_items * chunks;
+			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_pair_kernel<true> : bounds_pair_kernel<false>), dim3(nblocks), block, 0, stream, src, N, dt, rots, cubes, parents,
 			                   B, groups, max_items, chunks, chunk_pts, scratch, ub, lb, bo->pairs, bo->ctl);
 		}
 	} else

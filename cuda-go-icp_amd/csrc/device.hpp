@@ -130,12 +130,92 @@ struct BoundsOrder {
 	int* pairs;                  // [2 * bounds_order_items(groups, max_runs)]: the two groups of an item, -1 = none
 	int* ctl;                    // [0] items of the pair list, [1] 1 = order and pairs are valid (0: too many runs); [2], [3] items the pair launch
 	                             // evaluated in twin form / in identical form (coincident members, bounds_pair_kernel): zeroed by the pre-pass
+	                             // [kBoundsCut .. kBoundsCut + 8] the cuts of the pair launch's 8-chunk shape (bounds_cuts), in ctl[0]'s 128-B line
 	long long* host_note;        // pinned host memory: the pre-pass leaves (groups << 1 | left alone) there, a hint for the caller's next launch
+	const int* cost;             // [kBoundsCost + kBoundsPlan] lines[8], waves[8] of the source's eight chunks and the plan of the cuts made from
+	                             // them (launch_bounds_chunk_cost, bounds_cut_plan); null or balance = 0: equal cuts
+	int balance;                 // 1: the cuts follow the chunks' cost
 };
 constexpr int kBoundsOrderMaxRuns = 64;
+constexpr int kBoundsCut = 4, kBoundsCtlInts = 32;     // ctl[] is one 128-B line
+constexpr float kBoundsBalanceA = 18.f;                // default weight of a wavefront, in lines: the fit of the spans, EXPERIMENTS R9.1
 inline size_t bounds_order_items(int groups, int max_runs) { return (size_t)(groups + 1) / 2 + (size_t)max_runs; }
+// slots per block label of the pair launch's grid: no piece of the cuts is longer than 1.25 items (bounds_cuts clamps the weights)
+inline int bounds_pair_slots(int max_items, bool balanced) { return balanced ? (int)(((long long)max_items * 5 + 3) / 4) : max_items; }
+// Integer cuts of the U = 8 items units (u = chunk * items + item) into eight pieces of equal weight.  A unit of chunk k weighs
+// W_k = a_q8 * waves_k + 256 * lines_k, clamped to [0.8, 1.25] x the mean weight; cut[x] is the first unit at which the weighted prefix reaches
+// x / 8 of the total.  Everything is 64-bit integer arithmetic on weights scaled to a mean of 2^20: items = 2^20 gives products below 2^47.
+// The work is split by what it depends on.  bounds_cut_plan, once per source cloud and weight (launch_bounds_chunk_cost): the clamped weights
+// w[8] and their total, and from them, for x = 1 .. 7, the chunk k_x the cut falls into -- 8 (w_0 + .. + w_k) <= x total is free of `items` --
+// and n_x = x total - 8 (w_0 + .. + w_{k - 1}), d_x = 8 w_k: plan[x] = k_x, plan[8 + x] = n_x, plan[16 + x] = d_x (entry 0 unused).
+// bounds_cut_of, per batch: cut[x] = k_x items + min(ceil(items n_x / d_x), items), one division.  bounds_cut_cap then enforces the bound of a
+// piece.  No cost (a cloud without the 8-chunk shape): k_x = x, n_x = 0, the equal split.
+constexpr int kBoundsCost = 16, kBoundsPlan = 24;      // BoundsOrder::cost: lines[8], waves[8], then the plan
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void bounds_cut_plan(const int* cost, int a_q8, int plan[kBoundsPlan])
+{
+	long long w[8], sum = 0;
+	for (int k = 0; k < 8; k++) { w[k] = (long long)a_q8 * cost[8 + k] + 256ll * cost[k]; sum += w[k]; }
+	for (int x = 0; x < 8; x++) { plan[x] = x; plan[8 + x] = 0; plan[16 + x] = 1; }
+	if (sum <= 0) return;
+	while (sum >= (1ll << 39)) { sum = 0; for (int k = 0; k < 8; k++) { w[k] >>= 1; sum += w[k]; } }   // keeps w << 23 inside 63 bits
+	long long total = 0;
+	for (int k = 0; k < 8; k++) {
+		long long s = (w[k] << 23) / sum;                  // 2^20 x the weight over the mean weight
+		s = s < 838861 ? 838861 : (s > 1310720 ? 1310720 : s);   // [0.8, 1.25] x 2^20
+		w[k] = s; total += s;
+	}
+	int k = 0;
+	long long before = 0;                                   // weight of the whole chunks before k, per item
+	for (int x = 1; x < 8; x++) {
+		while (k < 7 && 8 * (before + w[k]) <= x * total) { before += w[k]; k++; }
+		plan[x] = k; plan[8 + x] = (int)(x * total - 8 * before); plan[16 + x] = (int)(8 * w[k]);     // both below 2^27
+	}
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int bounds_cut_of(const int* plan, int x, int items)
+{
+	if (x <= 0) return 0;
+	if (x >= 8) return 8 * items;
+	const long long d = plan[16 + x];
+	long long j = ((long long)items * plan[8 + x] + d - 1) / d;
+	if (j > items) j = items;
+	return (int)((long long)plan[x] * items + j);
+}
+// the clamp bounds a piece by 1.25 items but for a corner (an empty chunk raised to 0.8 lifts the mean of the clamped weights: 1.26 items);
+// the grid has ceil(1.25 items) slots per label, so the bound is enforced: forward, then back from the fixed end
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void bounds_cut_cap(int cut[9], int items)
+{
+	const int cap = (int)(((long long)items * 5 + 3) / 4);
+	for (int x = 1; x < 8; x++) if (cut[x] > cut[x - 1] + cap) cut[x] = cut[x - 1] + cap;
+	for (int x = 7; x >= 1; x--) if (cut[x] < cut[x + 1] - cap) cut[x] = cut[x + 1] - cap;
+}
+// the whole formula in one piece (the host's restatement of what the two device steps leave in ctl[])
+inline void bounds_cuts(const int* cost, int a_q8, int items, int cut[9])
+{
+	int plan[kBoundsPlan];
+	bounds_cut_plan(cost, a_q8, plan);
+	for (int x = 0; x < 9; x++) cut[x] = bounds_cut_of(plan, x, items);
+	bounds_cut_cap(cut, items);
+}
 hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const CubeRec* cubes, const ParentRec* parents,
                          int B, float* scratch, float* ub, float* lb, hipStream_t stream, const BoundsOrder* bo = nullptr);
+// What a chunk of the ordered source costs the pair launch (BoundsOrder::cost), once per source cloud: over the eight chunks of the 8-chunk
+// shape (chunk_pts = roundup256(ceil(N / 8)); fewer than 32 x 256 points: all zero, equal cuts) and the four rotations of kCostRots at
+// translation 0, per wavefront of 64 consecutive points the distinct 128-B lines of the bricked fp32 grid under its in-grid lanes.
+// cost[0..7] lines, cost[8..15] wavefronts counted (one per wavefront and rotation); integer sums, hence the same whatever the order.
+// a_q8: the weight of a wavefront in lines, in 1/256; a one-thread kernel behind the count leaves the plan of the cuts in cost[16 ..]
+hipError_t launch_bounds_chunk_cost(const float4* src, int N, const DtDesc& dt, int a_q8, int* cost, hipStream_t stream);
+constexpr int kXcdStampRows = 16, kXcdStampCols = 6;   // diagnostic build (GOICP_BOUNDS_XCD_STAMPS): rows 0-7 per XCC, 8-15 per block label
+// copies the stamps out and clears them; hipErrorNotSupported in the shipped library
+hipError_t bounds_xcd_stamps_take(unsigned long long* out, hipStream_t stream);
 
 // an UNRELATED cube batch, evaluated grouped by (rotation, pass, translation cell) and written back in the caller's order (same bits)
 size_t bounds_grouped_scratch_bytes(int B, int nrots);

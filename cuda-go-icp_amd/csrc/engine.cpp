@@ -245,6 +245,7 @@ void Engine::init(const float* target, size_t M, const float* source, size_t N)
 		dt_.c1 = (float)(1.05 * std::ldexp(1.0, -24) * (s0 + 8.0));
 		dt_.c2 = (float)(1.05 * std::ldexp(1.0, -24) * 4.0);
 	}
+	update_bounds_cost();                     // reads the geometry only: it runs beside the DT build
 	// ---- DT build on the GPU ----
 	{
 		double t0 = now_ms();
@@ -490,6 +491,16 @@ void Engine::load_source(const float* source, size_t N, bool device_order, const
 	src_normals_k_ = 0;
 	src_normals_user_ = false;
 	if (source_normals_active()) build_source_normals(source, d_xyz, on_device ? d_perm.get() : nullptr);
+	if (dt_.V > 0) update_bounds_cost();      // a swap; init counts once the grid's geometry is known
+}
+
+// what each of the source's eight chunks costs the pair launch (BoundsOrder::cost): one small launch behind the ordered source on the engine's
+// stream, no wait of its own (init and every swap wait for the stream before they return)
+void Engine::update_bounds_cost()
+{
+	if (!d_bcost_) d_bcost_.alloc(kBoundsCost + kBoundsPlan);
+	const float a = p_.bounds_balance_a > 0.f ? p_.bounds_balance_a : kBoundsBalanceA;
+	HIPCHK(launch_bounds_chunk_cost(d_src_, (int)N_, dt_, (int)std::min(a * 256.f + 0.5f, 16777216.f), d_bcost_, stream_));
 }
 
 void Engine::check_swap_size(size_t n, const char* fn) const
@@ -1185,7 +1196,9 @@ const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
 		border_skipped_ = 0;
 	}
 	const int max_runs = std::min(std::max(p_.bounds_order_max_runs, 1), kBoundsOrderMaxRuns);
-	const size_t items = bounds_order_items(groups, max_runs), need = 2 * (size_t)groups + 2 * items + 4;
+	// keys, order, pairs, then ctl[] on a 128-B line of its own (the buffer's base is aligned far beyond that)
+	const size_t items = bounds_order_items(groups, max_runs), ctl_at = (2 * (size_t)groups + 2 * items + kBoundsCtlInts - 1) / kBoundsCtlInts * kBoundsCtlInts;
+	const size_t need = ctl_at + kBoundsCtlInts;
 	if (need > d_border_.size()) {
 		HIPCHK(hipStreamSynchronize(stream_));
 		if (s && s != stream_) HIPCHK(hipStreamSynchronize(s));
@@ -1195,8 +1208,9 @@ const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
 	border_.mode = p_.bounds_order >= 2 ? 2 : 1;
 	border_.min_groups = p_.bounds_order_min_groups; border_.max_runs = max_runs; border_.cell_vox = p_.bounds_order_cell;
 	border_.keys = d_border_.get(); border_.order = border_.keys + groups;
-	border_.pairs = reinterpret_cast<int*>(border_.order + groups); border_.ctl = border_.pairs + 2 * items;
+	border_.pairs = reinterpret_cast<int*>(border_.order + groups); border_.ctl = reinterpret_cast<int*>(border_.keys + ctl_at);
 	border_.host_note = h_border_note_.get();
+	border_.cost = d_bcost_.get(); border_.balance = p_.bounds_balance != 0;
 	return &border_;
 }
 
@@ -1211,6 +1225,9 @@ void Engine::eval_bounds_dev(const Rot9* d_rots, const CubeRec* d_cubes, int B, 
 		const BoundsOrder* bo = d_cubes && !d_parents ? ensure_bounds_order(B, s) : nullptr;     // cube batches only: the search's own rounds come ordered (launch_queue_sort)
 		HIPCHK(launch_bounds(d_src_, (int)N_, bounds_dt(), d_rots, d_cubes, d_parents, B, d_scratch_, d_ub, d_lb, s ? s : stream_, bo));
 		border_form_ = bo ? bo->mode : 0; border_stream_ = s ? s : stream_;
+		int groups = 0;
+		bounds_scratch_floats(B, (int)N_, &groups, &border_chunks_);
+		border_items_ = (groups + 1) / 2;
 	}
 	cnt_.bounds_launches++;
 }
@@ -1233,6 +1250,38 @@ void Engine::debug_bounds_twins(int info[2])
 	if (border_form_ != 2) return;
 	HIPCHK(hipStreamSynchronize(border_stream_));
 	HIPCHK(hipMemcpy(info, border_.ctl + 2, 2 * sizeof(int), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_bounds_balance(int info[26])
+{
+	DeviceGuard guard(dev_);
+	for (int x = 0; x < 26; x++) info[x] = 0;
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (d_bcost_) HIPCHK(hipMemcpy(info + 9, d_bcost_, 16 * sizeof(int), hipMemcpyDeviceToHost));
+	if (border_form_ == 2 && border_chunks_ == 8) {
+		HIPCHK(hipStreamSynchronize(border_stream_));
+		HIPCHK(hipMemcpy(info, border_.ctl + kBoundsCut, 9 * sizeof(int), hipMemcpyDeviceToHost));
+		info[25] = border_.balance && border_.cost ? 1 : 0;
+	} else {
+		// no pair launch over eight chunks: its mapping was not in use
+		int items = border_items_;
+		if (border_form_) {
+			int ctl[2] = {0, 0};
+			HIPCHK(hipStreamSynchronize(border_stream_));
+			HIPCHK(hipMemcpy(ctl, border_.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+			if (ctl[1]) items = ctl[0];
+		}
+		for (int x = 0; x < 9; x++) info[x] = x * items;
+	}
+}
+
+bool Engine::debug_bounds_xcd_spans(unsigned long long* out)
+{
+	DeviceGuard guard(dev_);
+	const hipError_t e = bounds_xcd_stamps_take(out, border_stream_ ? border_stream_ : stream_);
+	if (e == hipErrorNotSupported) return false;
+	HIPCHK(e);
+	return true;
 }
 
 void Engine::reduce_min_dev(const float* d_v, int n, float* d_min, int* d_idx, hipStream_t s)

@@ -76,7 +76,10 @@ struct Params {
 	float bounds_order_cell = 4.f;        // tuning only: smallest Morton cell of the order, in DT voxels
 	int bounds_order_reprobe = 64;        // tuning only: after the pre-pass left a batch alone, batches of the same size skip the pre-pass (the parent's launch) and every
 	                                      // this-many-th of them runs it again; 0: every batch runs it
-	int twin_fusion = 1;          // the same translation node listed by both searches of a rotation child in a round is gathered once (device.hip lean_points<.., 2>)
+	int bounds_balance = 1;               // the pair launch's 8-chunk shape: 1 a block label takes an equal share of the chunks' COST (distinct DT lines per wavefront,
+	                                      // counted once per source cloud; device.hpp bounds_cuts), 0 one chunk each.  Same bits either way
+	float bounds_balance_a = 0.f;         // tuning only: the weight of a wavefront against one DT line in that cost; <= 0: kBoundsBalanceA
+	int twin_fusion = 1;         // the same translation node listed by both searches of a rotation child in a round is gathered once (device.hip lean_points<.., 2>)
 	int lds_tiles = 2;            // LDS-staged DT tiles for inner searches whose selected nodes lie within a few voxels of each other (deep rounds): 0 off, 1 the
 	                              // tile evaluation is launched every round, 2 only while the previous rounds had searches that qualify (default)
 	float tile_spread_vox = 10.f; // ... "a few": largest extent of a search's selected translations, in DT voxels (measured: the tile kernel is 1.7x the gathering one at 3 voxels, 1.3x at 5, even at 10)
@@ -251,6 +254,12 @@ public:
 	// twin lists were in use.
 	void debug_bounds_order(int info[3]);   // test: form of the last eval_bounds_dev launch, and what its pre-pass decided (device.hip BoundsOrder::ctl)
 	void debug_bounds_twins(int info[2]);   // test: items of that launch evaluated in twin form and in identical form (BoundsOrder::ctl[2], [3])
+	// test: the cuts of that launch and the source's chunk cost: info[0..8] cut, [9..16] lines, [17..24] waves, [25] 1 = the cuts followed the cost
+	// (pair form, 8 chunks, bounds_balance); a launch without the 8-chunk pair form reports the equal split of its items
+	void debug_bounds_balance(int info[26]);
+	// diagnostic build (GOICP_BOUNDS_XCD_STAMPS) only: the stamps of the pair launches since the last call, which clears them
+	// (device.hpp kXcdStampRows x kXcdStampCols); false in the shipped library
+	bool debug_bounds_xcd_spans(unsigned long long* out);
 	void debug_queue_expand(const float R[9], int level, const float* parents4, int n, float* ub0, float* lb0, float* ub1, float* lb1, int info[2]);
 	// test: the same round with the TILE list on (tile_min 1, no spread limit): both searches list their nodes there and nothing in the direct
 	// list; the upper-bound search queues only the first n_ub nodes (out arrays: 8 n_ub and 8 n floats).  info = {tile chunks the device chose,
@@ -376,6 +385,9 @@ private:
 	int border_form_ = 0;                // the form of the last eval_bounds_dev launch, and the stream it went to (debug_bounds_order)
 	hipStream_t border_stream_ = nullptr;
 	BoundsOrder border_{};
+	Buf<int> d_bcost_;                   // lines[8], waves[8] of the source's chunks and the plan of the cuts (BoundsOrder::cost); update_bounds_cost, on the engine's stream
+	int border_chunks_ = 0, border_items_ = 0;   // chunks and groups-derived equal-split items of the last launch (debug_bounds_balance)
+	void update_bounds_cost();
 	void ensure_bounds_scratch(int B, hipStream_t s);   // d_scratch_ holds a launch of B cube bounds; growing waits for stream_ and s only
 	void upload_rots(const std::vector<Rot9>& rots);    // the batch's rotation table -> d_rots_, on stream_
 	void run_inner(std::vector<InnerSearch*>& searches, const std::vector<Rot9>& rots);

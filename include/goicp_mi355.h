@@ -201,6 +201,10 @@ typedef struct goicp_params {
 	float bounds_order_cell;         /* tuning only: smallest Morton cell of the order, in distance-transform voxels (<= 0: the default) */
 	int32_t bounds_order_reprobe;    /* tuning only (default 64): once the pre-pass has left a batch alone, batches of the same size take the plain launch without a
 	                                  * pre-pass, and every this-many-th of them runs it again; 0: every batch runs the pre-pass */
+	int32_t bounds_balance;          /* default 1.  Form 2 over a cloud cut into eight point chunks: the eight block labels of the launch (blocks b and b + 8 share an
+	                                  * XCD) take equal shares of the chunks' COST -- the distinct distance-transform lines a wavefront of the chunk gathers, counted on
+	                                  * the device once per source cloud -- instead of one chunk each; 0: one chunk each.  Scheduling only: same bits either way */
+	float bounds_balance_a;          /* tuning only: the weight of a wavefront against one line in that cost (<= 0: the default) */
 } goicp_params;
 
 void goicp_params_default(goicp_params* p);
@@ -1073,6 +1077,17 @@ int goicp_debug_bounds_order(goicp_handle h, int32_t info[3]);
  * per point, a sum per coefficient), info[1] = items whose coefficients were equal as well (evaluated once, stored to both).  Both 0 for the
  * other forms and for a batch the pre-pass left alone. */
 int goicp_debug_bounds_twins(goicp_handle h, int32_t info[2]);
+/* goicp_debug_bounds_balance (test): the mapping of the same last call.  info[0..8] = the cuts: block label x evaluated the units
+ * cut[x] .. cut[x + 1] - 1 of the list u = chunk * items + item (cut[8] = 8 items); info[9..16] = lines and info[17..24] = waves of the
+ * source's eight chunks (all 0 for a cloud of fewer than 7 937 points, whose cuts are the equal split); info[25] = 1 when the launch was
+ * the pair form over eight chunks with bounds_balance on.  A call that was no pair launch over eight chunks reports info[25] = 0 and the
+ * equal split x * items of its items. */
+int goicp_debug_bounds_balance(goicp_handle h, int32_t info[26]);
+/* goicp_debug_bounds_xcd_spans (diagnostic build, make -C csrc stamps): per XCC (rows 0-7) and per block label (rows 8-15) of the pair
+ * launches since the last call, six 64-bit words: first workgroup entry and last exit on the 100 MHz clock, workgroups that worked, the sum of
+ * their times, (XCC rows) the mask of the labels seen there, workgroups that left at once.  The call clears the stamps.
+ * GOICP_ERR_INVALID in the shipped library, which stamps nothing. */
+int goicp_debug_bounds_xcd_spans(goicp_handle h, uint64_t out[96]);
 /* diagnostics of the ICP pass's neighbour cache: two scoring passes at (R, t); *hits = queries of the second pass that
  * skipped the tree walk (-1 when the cache is off) */
 int goicp_debug_cache_hits(goicp_handle h, const float R[9], const float t[3], int64_t* hits);

@@ -35,6 +35,12 @@ rotation child (search_shaped_batch): items any order could give at most (floor(
 items --trials random tie orders capture (mean, min, max), and how many two-member families share their cell with anything else.
 
   python3 tools/dt_sector_model.py --twins [--trials 200] [--json profiles/r08_twin_tie_order_model.json]
+
+--chunks: what each of the pair launch's eight point chunks costs: distinct 128-B lines per 64-lane gather and the chunk's share of the lines,
+over random rotations x 12 sibling expansions; the spread of that share over the rotations; the same at the identity pose; and the device's
+own per-chunk cost (bounds_chunk_cost_kernel), as goicp_debug_bounds_balance and tools/xcd_balance_probe.py report it.
+
+  python3 tools/dt_sector_model.py --chunks [--rotations 8] [--seed 0] [--json profiles/r09_chunk_cost_model.json]
 """
 import argparse
 import json
@@ -293,8 +299,81 @@ def lines_mode(a, rots, recs, src, mn, scale, V):
     return out
 
 
+COST_ROTS = ((0.9, -0.5, 0.3), (-0.4, 1.1, 0.8), (0.6, 0.7, -1.3))     # Rodrigues vectors of device.hip kCostRots[1..3]
+
+
+def wave_lines(line, N):
+    """distinct line ids (>= 0) per wavefront of 64 consecutive points -> (waves,)"""
+    pad = (-N) % 64
+    s = np.sort(np.pad(line, (0, pad), constant_values=-1).reshape(-1, 64), 1)
+    return ((s[:, 1:] != s[:, :-1]) & (s[:, 1:] >= 0)).sum(1) + (s[:, 0] >= 0)
+
+
+def chunks_mode(a, pkg, src, mn, scale, V):
+    """What each of the pair launch's eight point chunks costs (EXPERIMENTS R9.1): distinct 128-B lines per 64-lane gather, per chunk, over
+    --rotations random rotations x 12 sibling expansions at depths 0 - 5 (two per depth; corners as bench.make_batch draws them), the eight
+    dword gathers of a point each; the same count at the identity pose without translation; and the device's own cost
+    (bounds_chunk_cost_kernel: the identity and COST_ROTS at translation 0, one gather per pose), which goicp_debug_bounds_balance reports."""
+    N = len(src)
+    chunk_pts = -(-(-(-N // 8)) // 256) * 256
+    wave_chunk = (np.arange(-(-N // 64)) * 64) // chunk_pts
+    rng = np.random.default_rng(a.seed)
+
+    def gather_lines(R, t):
+        """t: three (lo, hi) translation pairs -> per child gather the lines per wavefront, lanes with an index outside the grid left out"""
+        rp = (src[:, 0:1] * R[:, 0] + src[:, 1:2] * R[:, 1]) + src[:, 2:3] * R[:, 2]
+        idx = [[((rp[:, k] + np.float32(t[k][j]) - mn[k]) * scale + np.float32(0.5)).astype(np.int32) for j in range(len(t[k]))] for k in range(3)]
+        ok = np.ones(N, bool)
+        for k in range(3):
+            for v in idx[k]:
+                ok &= (v >= 0) & (v < V)
+        out = []
+        for c in range(8 if len(t[0]) == 2 else 1):
+            x, y, z = (np.clip(idx[k][(c >> k) & 1 if len(t[k]) == 2 else 0], 0, V - 1) for k in range(3))
+            out.append(wave_lines(np.where(ok, element_index(x, y, z, V, a.chunk_layout) >> 5, -1), N))
+        return out
+
+    def per_chunk(ws):
+        """sum over the gathers of lines per chunk, and the gathers (wavefront instructions) per chunk"""
+        lines = np.zeros(8)
+        for w in ws:
+            lines += np.bincount(wave_chunk, weights=w, minlength=8)
+        return lines, np.bincount(wave_chunk, minlength=8) * len(ws)
+
+    tot_l, tot_g, ratios = np.zeros(8), np.zeros(8), []
+    for _ in range(a.rotations):
+        R = np.asarray(pkg.fgoicp.rodrigues(rng.uniform(-2.0, 2.0, 3)), np.float32).reshape(3, 3)
+        rl, rg = np.zeros(8), np.zeros(8)
+        for lev in list(range(6)) * 2:
+            pw = np.float32(1.0 / (1 << lev))
+            corner = (rng.uniform(-0.5, 0.5, 3) * (1 - pw) - pw / 2).astype(np.float32)
+            w = pw / np.float32(2)
+            t = [(corner[k] + w / np.float32(2), corner[k] + w + w / np.float32(2)) for k in range(3)]
+            l, g = per_chunk(gather_lines(R, t))
+            rl += l; rg += g
+        tot_l += rl; tot_g += rg
+        ratios.append(rl / rl.mean())
+    ratios = np.array(ratios)
+    ident, _ = per_chunk(gather_lines(np.eye(3, dtype=np.float32), [(0.0,), (0.0,), (0.0,)]))
+    dev = np.zeros(8)
+    for v in (None,) + COST_ROTS:
+        R = np.eye(3, dtype=np.float32) if v is None else np.asarray(pkg.fgoicp.rodrigues(np.asarray(v, np.float64)), np.float32).reshape(3, 3)
+        dev += per_chunk(gather_lines(R, [(0.0,), (0.0,), (0.0,)]))[0]
+    pts = [int(min((k + 1) * chunk_pts, N) - min(k * chunk_pts, N)) for k in range(8)]
+    return {"N": N, "V": V, "layout": a.chunk_layout, "chunk_pts": chunk_pts, "rotations": a.rotations, "expansions_per_rotation": 12, "seed": a.seed,
+            "points": pts, "lines_per_gather": np.round(tot_l / tot_g, 2).tolist(), "lines_per_chunk_over_mean": np.round(tot_l / tot_l.mean(), 3).tolist(),
+            "ratio_min_over_rotations": np.round(ratios.min(0), 3).tolist(), "ratio_max_over_rotations": np.round(ratios.max(0), 3).tolist(),
+            "identity_no_translation_over_mean": np.round(ident / ident.mean(), 3).tolist(),
+            "device_cost_lines": [int(x) for x in dev], "device_cost_waves": [int(4 * x) for x in np.bincount(wave_chunk, minlength=8)],
+            "device_cost_lines_over_mean": np.round(dev / dev.mean(), 3).tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chunks", action="store_true", help="model the cost of the pair launch's eight point chunks: distinct 128-B lines per 64-lane gather (see chunks_mode)")
+    ap.add_argument("--rotations", type=int, default=8, help="--chunks: random rotations")
+    ap.add_argument("--seed", type=int, default=0, help="--chunks: seed of the rotations and corners")
+    ap.add_argument("--chunk-layout", default="4x4x1", help="--chunks: sector shape inside the brick (4x4x1: the engine's brick_index)")
     ap.add_argument("--layouts", default="4x4x1,4x2x2,2x2x4,2x4x2,linear")
     ap.add_argument("--lanes", type=int, default=4, help="lanes that share one tag lookup (4: a quad)")
     ap.add_argument("--every", type=int, default=16, help="model every k-th expansion of the batch")
@@ -330,6 +409,13 @@ def main():
     pad = (-N) % 64
     V = 300
     mn, scale = dt_geometry(model, V)
+    if a.chunks:
+        out = chunks_mode(a, pkg, src, mn, scale, V)
+        print(json.dumps(out, indent=1))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.twins:
         out = {"cell_vox": a.cell, "voxels_per_unit": round(float(scale), 2),
                "bench_batch": dict(batch="bench.make_batch(8192 expansions, 8 rotations, seed 1234)", **twins_mode(recs, scale, a.cell, a.trials, 0)),
