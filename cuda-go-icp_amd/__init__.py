@@ -10,7 +10,8 @@ missing.
 from . import binding  # noqa: F401
 from .binding import GoicpError, build_library, library_path, load_library  # noqa: F401
 from .fgoicp import (Config, FastGoICP, IterativeClosestPoint3D, Registration, RotNode, TransNode,  # noqa: F401
-                     cluster, cluster_filter, estimate_normals, knn_self, load_cloud, plane_filter, radius_outlier_removal, segment_plane, source_order,
+                     cluster, cluster_filter, estimate_normals, fpfh, knn_self, load_cloud, match_features, plane_filter, radius_outlier_removal,
+                     segment_plane, source_order,
                      statistical_outlier_removal, voxel_downsample)
 
 

@@ -259,6 +259,11 @@ SYMBOLS = {
     "goicp_knn_self": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32), _fp]),
     "goicp_estimate_normals_host": (C.c_int, [_fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
     "goicp_estimate_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
+    "goicp_fpfh_host": (C.c_int, [_fp, _fp, C.c_size_t, C.c_int32, _fp, C.POINTER(C.c_uint8)]),
+    "goicp_fpfh": (C.c_int, [_vp, _fp, _fp, C.c_size_t, C.c_int32, _fp, C.POINTER(C.c_uint8)]),
+    "goicp_match_features_host": (C.c_int, [_fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint8)]),
+    "goicp_match_features": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint8)]),
+    "goicp_match_features_tile": (C.c_int, []),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

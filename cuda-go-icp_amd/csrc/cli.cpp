@@ -82,6 +82,12 @@
 //               goicp_estimate_normals on the device when there is one, goicp_estimate_normals_host otherwise: the same bits), flipped
 //               towards the viewpoint when one is given.  OUT.ply is an ASCII PLY with x y z nx ny nz curvature.  Refused together with
 //               --ranks -- before any device is touched
+//   --fpfh-match SRC TGT OUT.txt [--fpfh-k K] [--normal-k K] [--voxel V]   a mode of its own that takes no config and registers nothing: both
+//               clouds, reduced by a voxel grid of pitch V on the host when --voxel is given, get normals from their K-point neighbourhoods
+//               (--normal-k, 3..32, default 16, no viewpoint) and 33-bin FPFH descriptors over their K nearest other points (--fpfh-k, 1..32,
+//               default 16); every descriptor of SRC is matched to its nearest of TGT (goicp_estimate_normals, goicp_fpfh and
+//               goicp_match_features on the device when there is one, the _host forms otherwise: the same bits).  OUT.txt gets one line
+//               `i j d2 d2_second` per mutual match.  Refused together with --ranks -- before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -209,10 +215,127 @@ static int estimate_normals_mode(int argc, char** argv, int at)
 	}
 }
 
+// goicp_cli --fpfh-match SRC TGT OUT.txt [--fpfh-k K] [--normal-k K] [--voxel V] [--verbose]: no config, no registration.  `at` is the
+// position of --fpfh-match in argv
+static int fpfh_match_mode(int argc, char** argv, int at)
+{
+	const char* path[3] = {at + 1 < argc ? argv[at + 1] : nullptr, at + 2 < argc ? argv[at + 2] : nullptr, at + 3 < argc ? argv[at + 3] : nullptr};
+	const char *k_arg = nullptr, *nk_arg = nullptr, *voxel_arg = nullptr;
+	int verbose = 0;
+	// refused before any device is touched
+	for (int i = 1; i < argc; i++) {
+		if (i >= at && i <= at + 3) continue;
+		if (!std::strcmp(argv[i], "--ranks")) {
+			std::fprintf(stderr, "error: --fpfh-match cannot be combined with --ranks (it runs on one device and registers nothing)\n");
+			return 2;
+		}
+		if (!std::strcmp(argv[i], "--fpfh-k")) k_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--normal-k")) nk_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--voxel")) voxel_arg = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--verbose")) verbose = 1;
+		else {
+			std::fprintf(stderr, "error: --fpfh-match takes --fpfh-k K, --normal-k K, --voxel V and --verbose, got '%s'\n", argv[i]);
+			return 2;
+		}
+	}
+	for (int a = 0; a < 3; a++)
+		if (!path[a] || !*path[a] || !std::strncmp(path[a], "--", 2)) {
+			std::fprintf(stderr, "error: --fpfh-match needs SRC, TGT and OUT.txt\n");
+			return 2;
+		}
+	long k = 16, nk = 16;
+	for (int a = 0; a < 2; a++) {
+		const char* arg = a ? nk_arg : k_arg;
+		if (!arg) continue;
+		char* end = nullptr;
+		const long v = std::strtol(arg, &end, 10);
+		if (end == arg || *end != '\0' || v < (a ? 3 : 1) || v > GOICP_KNN_SELF_MAX) {
+			std::fprintf(stderr, "error: --fpfh-match needs %s in %d..%d, got '%s'\n", a ? "--normal-k" : "--fpfh-k", a ? 3 : 1, GOICP_KNN_SELF_MAX, arg);
+			return 2;
+		}
+		(a ? nk : k) = v;
+	}
+	float voxel = 0.f;
+	if (voxel_arg) {
+		char* end = nullptr;
+		voxel = std::strtof(voxel_arg, &end);
+		if (end == voxel_arg || *end != '\0' || !(voxel > 0.f) || !(voxel <= 3.402823466e+38f)) {
+			std::fprintf(stderr, "error: --voxel needs a finite voxel size > 0, got '%s'\n", voxel_arg);
+			return 2;
+		}
+	}
+	try {
+		std::vector<P3> cloud[2];
+		for (int c = 0; c < 2; c++) {
+			load_cloud(path[c], 1.f, 1.f, cloud[c], 0);
+			if (voxel_arg && !cloud[c].empty()) {
+				std::vector<P3> cells(cloud[c].size());
+				size_t m = 0;
+				check(goicp_voxel_downsample_host(&cloud[c][0].x, cloud[c].size(), voxel, &cells[0].x, nullptr, &m));
+				cells.resize(m);
+				cloud[c].swap(cells);
+			}
+		}
+		// a handle only lends its device: eight corners of a cube are its clouds
+		std::vector<P3> corners;
+		for (int c = 0; c < 8; c++) corners.push_back(P3{c & 1 ? 0.5f : -0.5f, c & 2 ? 0.5f : -0.5f, c & 4 ? 0.5f : -0.5f});
+		goicp_params params;
+		goicp_params_default(&params);
+		params.dt_size = 32;
+		params.verbose = verbose;
+		goicp_handle h = nullptr;
+		const int rc = goicp_create(&params, &corners[0].x, 8, &corners[0].x, 8, &h);
+		if (rc != GOICP_OK && rc != GOICP_ERR_NO_DEVICE) check(rc);
+		const bool on_device = h != nullptr;
+		const auto t0 = std::chrono::steady_clock::now();
+		std::vector<float> feature[2];
+		int st = GOICP_OK;
+		for (int c = 0; c < 2 && st == GOICP_OK; c++) {
+			const size_t n = cloud[c].size();
+			const float* xyz = n ? &cloud[c][0].x : nullptr;
+			std::vector<float> normals(3 * n);
+			feature[c].resize(n * (size_t)GOICP_FPFH_DIM);
+			st = h ? goicp_estimate_normals(h, xyz, n, (int32_t)nk, nullptr, normals.data(), nullptr, nullptr)
+			       : goicp_estimate_normals_host(xyz, n, (int32_t)nk, nullptr, normals.data(), nullptr, nullptr);
+			if (st == GOICP_OK)
+				st = h ? goicp_fpfh(h, xyz, normals.data(), n, (int32_t)k, feature[c].data(), nullptr)
+				       : goicp_fpfh_host(xyz, normals.data(), n, (int32_t)k, feature[c].data(), nullptr);
+		}
+		const size_t nq = cloud[0].size(), nt = cloud[1].size();
+		std::vector<int32_t> index(nq);
+		std::vector<float> d2(nq), second(nq);
+		std::vector<uint8_t> mutual(nq);
+		if (st == GOICP_OK)
+			st = h ? goicp_match_features(h, feature[0].data(), nq, feature[1].data(), nt, index.data(), d2.data(), second.data(), mutual.data())
+			       : goicp_match_features_host(feature[0].data(), nq, feature[1].data(), nt, index.data(), d2.data(), second.data(), mutual.data());
+		const auto t1 = std::chrono::steady_clock::now();
+		const std::string why = st != GOICP_OK ? goicp_last_error() : "";
+		if (h) goicp_destroy(h);
+		if (st != GOICP_OK) throw std::runtime_error(why);
+		FILE* f = std::fopen(path[2], "w");
+		if (!f) throw std::runtime_error(std::string("cannot write ") + path[2]);
+		size_t matches = 0;
+		for (size_t i = 0; i < nq; i++)
+			if (mutual[i]) {
+				std::fprintf(f, "%zu %d %.9g %.9g\n", i, index[i], d2[i], second[i]);
+				matches++;
+			}
+		if (std::fclose(f) != 0) throw std::runtime_error(std::string("cannot write ") + path[2]);
+		std::printf("fpfh match: %zu x %zu points, k %ld, normal k %ld, %zu mutual matches, %s, %.2f ms -> %s\n", nq, nt, k, nk, matches,
+		            on_device ? "on the device" : "on the host (no device)", std::chrono::duration<double, std::milli>(t1 - t0).count(), path[2]);
+		return 0;
+	} catch (const std::exception& e) {
+		std::fprintf(stderr, "error: %s\n", e.what());
+		return 1;
+	}
+}
+
 int main(int argc, char** argv)
 {
 	for (int i = 1; i < argc; i++)
 		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
+	for (int i = 1; i < argc; i++)
+		if (!std::strcmp(argv[i], "--fpfh-match")) return fpfh_match_mode(argc, argv, i);
 	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--generalized [--gicp-epsilon E]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16, generalized = 0;
 	float gicp_epsilon = 1e-3f;

@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/goicp_mi355.h"   // GOICP_FPFH_COS / GOICP_FPFH_SIN: the one table of the host path and the kernel
+
 namespace goicp {
 
 // Search-range cull shared by the host queues (engine.hpp) and the device queues (bnbqueue.hip): the half-open cube
@@ -685,6 +687,77 @@ GOICP_HD inline void normal_pca_point(const float* xyz, int i, const int32_t* ro
 	out_n[1] = n1 == 0.f ? 0.f : (flip ? -n1 : n1);
 	out_n[2] = n2 == 0.f ? 0.f : (flip ? -n2 : n2);
 }
+
+// ---- FPFH descriptors and descriptor matching (kdbuild.hip; goicp_fpfh_host / goicp_match_features_host are the host twins) ----
+constexpr int kFpfhDim = 33, kFpfhBins = 11;
+// the matcher's LDS tile: kMatchTile target descriptors, each in a row of kMatchRow words (33 padded to a multiple of four, so that a row
+// starts on 16 bytes and is read as eight 128-bit words and one 32-bit word)
+constexpr int kMatchTile = 128, kMatchRow = 36;
+// frames / r2 / levels as launch_self_knn takes them, k in 1..kKnnSelfMax, k <= n - 1.  d_normals: n x 3 floats; d_index / d_dist_sq: n x k,
+// the self k-NN rows (left on the device); d_counts: n x 33 bytes, the SPFH counts; d_fpfh: n x 33 floats.  Returns after the stream has
+// drained; ev_begin / ev_end (may be null) are recorded around the search and the two kernels
+hipError_t launch_fpfh(const float* d_xyz, const float* d_normals, int n, const VoxelFrame* frames, const float* r2, int levels, int k, int32_t* d_index,
+                       float* d_dist_sq, unsigned char* d_counts, float* d_fpfh, StatReport* report, hipStream_t stream, hipEvent_t ev_begin = nullptr,
+                       hipEvent_t ev_end = nullptr);
+// d_q: nq x 33 floats, d_t: nt x 33 floats; d_index (nq ints), d_d2, d_second (nq floats): the smallest key of every query and the d2 of
+// the second smallest (+inf when nt == 1); d_mutual (may be null): nq bytes.  Returns after the stream has drained
+hipError_t launch_match_features(const float* d_q, int nq, const float* d_t, int nt, int32_t* d_index, float* d_d2, float* d_second,
+                                 unsigned char* d_mutual, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+
+// The pair feature and its three bins as include/goicp_mi355.h defines them, one text for the host path (kdtree.cpp) and spfh_kernel: fp64,
+// every operation rounded once (pca's + - * / sqrt), comparisons, |.| and floor.
+namespace fpfh {
+using pca::add; using pca::sub; using pca::mul; using pca::div; using pca::root; using pca::mag;
+GOICP_HD inline double dot3(double ax, double ay, double az, double bx, double by, double bz) { return add(add(mul(ax, bx), mul(ay, by)), mul(az, bz)); }
+// clamp(floor(11 * ((f + 1) * 0.5)), 0, 10), clamped as a double: f is finite but need not lie in [-1, 1] (the normals need not be unit)
+GOICP_HD inline int bin11(double f)
+{
+	const double t = floor(mul(11.0, mul(add(f, 1.0), 0.5)));
+	return t < 0.0 ? 0 : (t > 10.0 ? 10 : (int)t);
+}
+// the bin of atan2(y, x) among 11 equal bins of [-pi, pi): the number of k in 1..10 with angle(-x, -y) >= 2 pi k / 11
+GOICP_HD inline int theta_bin(double x, double y)
+{
+	if (x == 0.0 && y == 0.0) return 5;
+	const double C[10] = GOICP_FPFH_COS, S[10] = GOICP_FPFH_SIN;
+	const double a = -x, b = -y;
+	int count = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+	for (int k = 1; k <= 10; k++) {
+		const bool turn = sub(mul(C[k - 1], b), mul(S[k - 1], a)) >= 0.0;
+		count += k <= 5 ? (b < 0.0 || turn) : (b < 0.0 && turn);
+	}
+	return count;
+}
+// p_i, n_i, p_j, n_j: three floats each -> false: the pair is skipped; true: its bins b[0] (theta), b[1] (f2), b[2] (f3), each in 0..10
+GOICP_HD inline bool pair_bins(const float* p_i, const float* n_i, const float* p_j, const float* n_j, int b[3])
+{
+	double d0 = sub((double)p_j[0], (double)p_i[0]), d1 = sub((double)p_j[1], (double)p_i[1]), d2 = sub((double)p_j[2], (double)p_i[2]);
+	const double l2 = dot3(d0, d1, d2, d0, d1, d2);
+	const bool zero_i = n_i[0] == 0.f && n_i[1] == 0.f && n_i[2] == 0.f, zero_j = n_j[0] == 0.f && n_j[1] == 0.f && n_j[2] == 0.f;
+	if (!(l2 > 0.0) || zero_i || zero_j) return false;
+	const double l = root(l2);
+	const double i0 = (double)n_i[0], i1 = (double)n_i[1], i2 = (double)n_i[2], j0 = (double)n_j[0], j1 = (double)n_j[1], j2 = (double)n_j[2];
+	const double a1 = div(dot3(i0, i1, i2, d0, d1, d2), l), a2 = div(dot3(j0, j1, j2, d0, d1, d2), l);
+	const bool swap = mag(a1) < mag(a2);
+	const double s0 = swap ? j0 : i0, s1 = swap ? j1 : i1, s2 = swap ? j2 : i2, t0 = swap ? i0 : j0, t1 = swap ? i1 : j1, t2 = swap ? i2 : j2;
+	const double f3 = swap ? -a2 : a1;
+	if (swap) { d0 = -d0; d1 = -d1; d2 = -d2; }
+	double v0 = sub(mul(d1, s2), mul(d2, s1)), v1 = sub(mul(d2, s0), mul(d0, s2)), v2 = sub(mul(d0, s1), mul(d1, s0));
+	const double vl2 = dot3(v0, v1, v2, v0, v1, v2);
+	if (!(vl2 > 0.0)) return false;
+	const double vl = root(vl2);
+	v0 = div(v0, vl); v1 = div(v1, vl); v2 = div(v2, vl);
+	const double w0 = sub(mul(s1, v2), mul(s2, v1)), w1 = sub(mul(s2, v0), mul(s0, v2)), w2 = sub(mul(s0, v1), mul(s1, v0));
+	const double f2 = dot3(v0, v1, v2, t0, t1, t2), x = dot3(s0, s1, s2, t0, t1, t2), y = dot3(w0, w1, w2, t0, t1, t2);
+	b[0] = theta_bin(x, y);
+	b[1] = bin11(f2);
+	b[2] = bin11(f3);
+	return true;
+}
+}  // namespace fpfh
 
 // ---- RANSAC plane segmentation (kdbuild.hip; goicp_segment_plane_host / goicp_plane_filter_host are the host twins) ----
 // What include/goicp_mi355.h defines per hypothesis and per pair, one text for the host path (kdtree.cpp) and the kernels: the counter-based

@@ -724,6 +724,56 @@ void Engine::estimate_normals(const float* xyz, size_t n, int32_t k, const float
 	}
 }
 
+// ---- FPFH descriptors and descriptor matching ----
+void Engine::fpfh(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts)
+{
+	if (!out_fpfh) throw std::invalid_argument("goicp_fpfh: out_fpfh must be non-null");
+	knn_self_check_params(n, k);
+	const StatPlan plan = StatPlan::of_host_cloud(xyz, n, k);
+	fpfh_check_normals(normals, n);
+	if (registering_.load()) throw std::invalid_argument("goicp_fpfh: not while a registration runs");
+	DeviceGuard guard(dev_);
+	const size_t rows = n * (size_t)k, words = n * (size_t)kFpfhDim;
+	Buf<float> d_xyz = upload_cloud(xyz, n, stream_), d_nrm = upload_cloud(normals, n, stream_), d_d2(rows), d_out(words);
+	Buf<int32_t> d_idx(rows);
+	Buf<unsigned char> d_cnt(words);
+	StatReport rep;
+	HIPCHK(launch_fpfh(d_xyz, d_nrm, (int)n, plan.frames.data(), plan.r2.data(), (int)plan.frames.size(), k, d_idx, d_d2, d_cnt, d_out, &rep, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_fpfh, d_out, sizeof(float) * words, hipMemcpyDeviceToHost, stream_));
+	if (out_spfh_counts) HIPCHK(hipMemcpyAsync(out_spfh_counts, d_cnt, words, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		stat_report_line("fpfh", n, (int)n, rep);
+		std::fprintf(stderr, "[goicp] fpfh: k %d, device %.3f ms\n", k, ms);
+	}
+}
+
+void Engine::match_features(const float* q, size_t nq, const float* t, size_t nt, int32_t* out_index, float* out_d2, float* out_d2_second, uint8_t* out_mutual)
+{
+	if (!out_index || !out_d2 || !out_d2_second) throw std::invalid_argument("goicp_match_features: out_index, out_d2 and out_d2_second must be non-null");
+	match_check_descriptors(q, nq, t, nt);
+	if (registering_.load()) throw std::invalid_argument("goicp_match_features: not while a registration runs");
+	DeviceGuard guard(dev_);
+	Buf<float> d_q((size_t)kFpfhDim * nq), d_t((size_t)kFpfhDim * nt), d_d2(nq), d_second(nq);
+	Buf<int32_t> d_idx(nq);
+	Buf<unsigned char> d_mut(out_mutual ? nq : 0);
+	HIPCHK(hipMemcpyAsync(d_q, q, sizeof(float) * kFpfhDim * nq, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(d_t, t, sizeof(float) * kFpfhDim * nt, hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_match_features(d_q, (int)nq, d_t, (int)nt, d_idx, d_d2, d_second, out_mutual ? d_mut.get() : nullptr, stream_, ev0_, ev1_));
+	HIPCHK(hipMemcpyAsync(out_index, d_idx, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * nq, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(out_d2_second, d_second, sizeof(float) * nq, hipMemcpyDeviceToHost, stream_));
+	if (out_mutual) HIPCHK(hipMemcpyAsync(out_mutual, d_mut, nq, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		std::fprintf(stderr, "[goicp] match_features: %zu x %zu, device %.3f ms\n", nq, nt, ms);
+	}
+}
+
 // ---- symmetric point-to-plane ICP: the source normals ----
 void Engine::build_source_normals(const float* h_xyz, const float* d_xyz, const int32_t* d_perm)
 {

@@ -354,6 +354,10 @@ public:
 	// launch_estimate_normals); as statistical_outlier_removal, the engine lends its device and stream and nothing else
 	void knn_self(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
 	void estimate_normals(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index);
+	// goicp_fpfh / goicp_match_features: the descriptors of any cloud and the nearest-descriptor search on the device (kdbuild.hip launch_fpfh /
+	// launch_match_features); the engine lends its device and stream and nothing else
+	void fpfh(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts);
+	void match_features(const float* q, size_t nq, const float* t, size_t nt, int32_t* out_index, float* out_d2, float* out_d2_second, uint8_t* out_mutual);
 	// goicp_cluster / goicp_cluster_filter: Euclidean / DBSCAN clustering and the cluster selection on the device (kdbuild.hip launch_cluster /
 	// launch_cluster_compact; the selection itself runs on the host over the c sizes); the engine lends its device and stream and nothing else
 	void cluster(const float* xyz, size_t n, float radius, int32_t min_neighbors, int32_t* out_label, int32_t* out_sizes, size_t* n_clusters);
@@ -693,6 +697,13 @@ void knn_self_check_params(size_t n, int32_t k);
 void normals_check_params(size_t n, int32_t k, const float* vp);
 void knn_self_host(const float* xyz, size_t n, int32_t k, int32_t* out_index, float* out_dist_sq);
 void estimate_normals_host(const float* xyz, size_t n, int32_t k, const float* vp, float* out_normals, float* out_variation, int32_t* out_index);
+// FPFH descriptors and descriptor matching (kdtree.cpp).  fpfh_check_normals refuses null and non-finite normals,
+// match_check_descriptors empty, oversized and non-finite descriptor sets; the cloud and k are checked as the self k-NN checks them.
+// fpfh_host / match_features_host are goicp_fpfh_host / goicp_match_features_host
+void fpfh_check_normals(const float* normals, size_t n);
+void match_check_descriptors(const float* q, size_t nq, const float* t, size_t nt);
+void fpfh_host(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts);
+void match_features_host(const float* q, size_t nq, const float* t, size_t nt, int32_t* out_index, float* out_d2, float* out_d2_second, uint8_t* out_mutual);
 // goicp_information_decompose: cyclic Jacobi of the symmetrised 6x6, rank and pseudo-inverse over the eigenvalues > rank_tol * lambda_max (engine.cpp)
 void information_decompose(const double info[36], double rank_tol, double eig[6], double vec[36], double pinv[36], int32_t* rank);
 void debug_kabsch(const float H[9], float R[9]);            // the device SVD routine on the current device (tests)

@@ -443,6 +443,38 @@ int goicp_estimate_normals(goicp_handle h, const float* xyz, size_t n, int32_t k
 	return guarded([&] { h->e->estimate_normals(xyz, n, k, vp, out_normals, out_variation, out_index); });
 }
 
+int goicp_fpfh_host(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts)
+{
+	REQUIRE(xyz && normals && out_fpfh && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::fpfh_host(xyz, normals, n, k, out_fpfh, out_spfh_counts); });
+}
+
+int goicp_fpfh(goicp_handle h, const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts)
+{
+	REQUIRE(h && xyz && normals && out_fpfh && n > 0);
+	REQUIRE(n <= (size_t)INT32_MAX / 8);
+	return guarded([&] { h->e->fpfh(xyz, normals, n, k, out_fpfh, out_spfh_counts); });
+}
+
+int goicp_match_features_host(const float* query, size_t n_q, const float* target, size_t n_t, int32_t* out_index, float* out_d2, float* out_d2_second,
+                              uint8_t* out_mutual)
+{
+	REQUIRE(query && target && out_index && out_d2 && out_d2_second && n_q > 0 && n_t > 0);
+	REQUIRE(n_q <= (size_t)INT32_MAX / 8 && n_t <= (size_t)INT32_MAX / 8);
+	return guarded([&] { goicp::match_features_host(query, n_q, target, n_t, out_index, out_d2, out_d2_second, out_mutual); });
+}
+
+int goicp_match_features(goicp_handle h, const float* query, size_t n_q, const float* target, size_t n_t, int32_t* out_index, float* out_d2,
+                         float* out_d2_second, uint8_t* out_mutual)
+{
+	REQUIRE(h && query && target && out_index && out_d2 && out_d2_second && n_q > 0 && n_t > 0);
+	REQUIRE(n_q <= (size_t)INT32_MAX / 8 && n_t <= (size_t)INT32_MAX / 8);
+	return guarded([&] { h->e->match_features(query, n_q, target, n_t, out_index, out_d2, out_d2_second, out_mutual); });
+}
+
+int goicp_match_features_tile(void) { return goicp::kMatchTile; }
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

@@ -1435,6 +1435,231 @@ hipError_t launch_estimate_normals(const float* d_xyz, int n, const VoxelFrame* 
 	return end_and_drain(ev_end, stream);                      // `order` is in use until here
 }
 
+// ------------------------------------------------------------------------------------------------
+// FPFH descriptors and descriptor matching on the device (host twins: fpfh_host, match_features_host, kdtree.cpp).  The self
+// k-NN's rows stay on the device; spfh_kernel counts the pair features of every point with its row, fpfh_kernel adds the neighbours'
+// counts in row order.  Neither kernel parallelises over the neighbours: the order of addition is part of the definition.
+// ------------------------------------------------------------------------------------------------
+constexpr int kSpfhBlock = 256;
+constexpr int kFpfhPoints = 15, kFpfhBlock = 512;              // 15 points x 33 bins = 495 of a workgroup's 512 lanes
+static_assert(kFpfhPoints * kFpfhDim <= kFpfhBlock && kKnnSelfMax <= kFpfhDim, "fpfh_kernel: one lane per (point, bin), and per (point, neighbour)");
+
+// One thread per point, in the order of the first grid level as normal_pca_kernel takes them.  The 33 counters of a lane are a byte column
+// of LDS (a count is at most k <= 32): indexed by a computed bin they would otherwise live in scratch.  The arithmetic is
+// fpfh::pair_bins' (device.hpp), the host's text
+__global__ void __launch_bounds__(kSpfhBlock) spfh_kernel(const float* __restrict__ xyz, const float* __restrict__ nrm, const int32_t* __restrict__ rows,
+                                                          const int* __restrict__ order, int n, int k, unsigned char* __restrict__ counts)
+{
+	__shared__ unsigned char cnt[kFpfhDim * kSpfhBlock];
+	const int tid = threadIdx.x, s = blockIdx.x * kSpfhBlock + tid;
+	if (s >= n) return;                                          // no barrier below: a lane touches its own column alone
+	for (int b = 0; b < kFpfhDim; b++) cnt[b * kSpfhBlock + tid] = 0;
+	const int i = order[s];
+	const float p[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+	const float m[3] = {nrm[3 * (size_t)i], nrm[3 * (size_t)i + 1], nrm[3 * (size_t)i + 2]};
+	const int32_t* row = rows + (size_t)i * (size_t)k;
+	for (int j = 0; j < k; j++) {
+		const size_t q = (size_t)row[j];
+		const float pq[3] = {xyz[3 * q], xyz[3 * q + 1], xyz[3 * q + 2]};
+		const float mq[3] = {nrm[3 * q], nrm[3 * q + 1], nrm[3 * q + 2]};
+		int b[3];
+		if (!fpfh::pair_bins(p, m, pq, mq, b)) continue;
+		cnt[b[0] * kSpfhBlock + tid]++;
+		cnt[(kFpfhBins + b[1]) * kSpfhBlock + tid]++;
+		cnt[(2 * kFpfhBins + b[2]) * kSpfhBlock + tid]++;
+	}
+	unsigned char* out = counts + (size_t)i * kFpfhDim;
+	for (int b = 0; b < kFpfhDim; b++) out[b] = cnt[b * kSpfhBlock + tid];
+}
+
+// One lane per (point, bin), 15 points per workgroup: every lane walks its point's row in key order and adds its bin of the neighbours'
+// counts; the weights 1 / d2 and the neighbours' ids are formed once per (point, neighbour) in LDS.  A neighbour at d2 == 0 has weight 0
+// here and is skipped as the definition says (no 1 / d2 of a float is 0).  The group sums add the 11 LDS values in bin order in every lane
+__global__ void __launch_bounds__(kFpfhBlock) fpfh_kernel(const int32_t* __restrict__ rows, const float* __restrict__ d2, const unsigned char* __restrict__ counts,
+                                                          const int* __restrict__ order, int n, int k, float* __restrict__ out)
+{
+	__shared__ double acc[kFpfhPoints * kFpfhDim];
+	__shared__ double weight[kFpfhPoints * kKnnSelfMax];
+	__shared__ int32_t nb[kFpfhPoints * kKnnSelfMax];
+	const int tid = threadIdx.x, p = tid / kFpfhDim, b = tid - p * kFpfhDim;
+	const int s = blockIdx.x * kFpfhPoints + p;
+	const bool live = p < kFpfhPoints && s < n;
+	const int i = live ? order[s] : 0;
+	if (live && b < k) {
+		const size_t at = (size_t)i * (size_t)k + (size_t)b;
+		const float w2 = d2[at];
+		weight[p * kKnnSelfMax + b] = w2 == 0.f ? 0.0 : __ddiv_rn(1.0, (double)w2);
+		nb[p * kKnnSelfMax + b] = rows[at];
+	}
+	__syncthreads();
+	const double inc = __ddiv_rn(100.0, (double)k);
+	double a = 0.0;
+	if (live) {
+		for (int j = 0; j < k; j++) {
+			const double w = weight[p * kKnnSelfMax + j];
+			if (!(w > 0.0)) continue;
+			const double c = (double)counts[(size_t)nb[p * kKnnSelfMax + j] * kFpfhDim + b];
+			a = __dadd_rn(a, __dmul_rn(__dmul_rn(c, inc), w));
+		}
+		acc[tid] = a;
+	}
+	__syncthreads();
+	if (!live) return;
+	const int g = b / kFpfhBins;
+	double sum = 0.0;
+	for (int c = 0; c < kFpfhBins; c++) sum = __dadd_rn(sum, acc[p * kFpfhDim + g * kFpfhBins + c]);
+	if (sum > 0.0) a = __dmul_rn(a, __ddiv_rn(100.0, sum));
+	const double own = (double)counts[(size_t)i * kFpfhDim + b];
+	out[(size_t)i * kFpfhDim + b] = (float)__dadd_rn(a, __dmul_rn(own, inc));
+}
+
+hipError_t launch_fpfh(const float* d_xyz, const float* d_normals, int n, const VoxelFrame* frames, const float* r2, int levels, int k, int32_t* d_index,
+                       float* d_dist_sq, unsigned char* d_counts, float* d_fpfh, StatReport* report, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (n < 2 || !d_normals || !d_index || !d_dist_sq || !d_counts || !d_fpfh || k < 1 || k > kKnnSelfMax || k > n - 1) return hipErrorInvalidValue;
+	int* order = nullptr;
+	Temps t;
+	KD_TRY(t.get(order, (size_t)n));
+	// ev_begin is recorded by the search, ev_end after the two kernels
+	KD_TRY(launch_self_knn(d_xyz, n, frames, r2, levels, k, d_index, d_dist_sq, order, report, stream, ev_begin, nullptr));
+	hipLaunchKernelGGL(spfh_kernel, dim3((n + kSpfhBlock - 1) / kSpfhBlock), dim3(kSpfhBlock), 0, stream, d_xyz, d_normals, d_index, order, n, k, d_counts);
+	KD_TRY(hipGetLastError());
+	hipLaunchKernelGGL(fpfh_kernel, dim3((n + kFpfhPoints - 1) / kFpfhPoints), dim3(kFpfhBlock), 0, stream, d_index, d_dist_sq, d_counts, order, n, k, d_fpfh);
+	KD_TRY(hipGetLastError());
+	return end_and_drain(ev_end, stream);                      // `order` is in use until here
+}
+
+// Brute-force nearest descriptor.  A workgroup of 256 lanes keeps one query per lane in registers and walks a chunk of the targets in
+// tiles of kMatchTile descriptors staged in LDS; every lane of a wave reads the same target word at a time (an LDS broadcast), and a row of
+// kMatchRow = 36 words keeps the 128-bit reads aligned.  The sum is the definition's: left to right, nothing fused, no matrix instruction.
+// blockIdx.y splits the targets into chunks so that few queries still fill the device; partial: [chunk][query][2] keys
+constexpr int kMatchBlock = 256;
+static_assert(kMatchRow % 4 == 0 && kMatchRow >= kFpfhDim && kFpfhDim == 33, "match_tile_kernel reads a row as eight float4 and one float");
+
+// the two smallest keys seen, by value: x = the smallest, y = the second
+__device__ __forceinline__ ulonglong2 match_offer(unsigned long long key, ulonglong2 two)
+{
+	const bool first = key < two.x, second = key < two.y;
+	return make_ulonglong2(first ? key : two.x, first ? two.x : (second ? key : two.y));
+}
+
+__global__ void __launch_bounds__(kMatchBlock) match_tile_kernel(const float* __restrict__ q, int nq, const float* __restrict__ t, int nt, int chunk_targets,
+                                                                 unsigned long long* __restrict__ partial)
+{
+	__shared__ float4 tile4[kMatchTile * kMatchRow / 4];
+	float* tile = reinterpret_cast<float*>(tile4);
+	const int tid = threadIdx.x, qi = blockIdx.x * kMatchBlock + tid;
+	const bool live = qi < nq;
+	float v[kFpfhDim];
+#pragma unroll
+	for (int c = 0; c < kFpfhDim; c++) v[c] = live ? q[(size_t)qi * kFpfhDim + c] : 0.f;
+	ulonglong2 two = make_ulonglong2(kKnnNoKey, kKnnNoKey);
+	const int t0 = blockIdx.y * chunk_targets, t1 = min(nt, t0 + chunk_targets);
+	for (int base = t0; base < t1; base += kMatchTile) {
+		const int rows = min(kMatchTile, t1 - base);
+		__syncthreads();                                         // the previous tile has been read
+		for (int e = tid; e < rows * kFpfhDim; e += kMatchBlock) {
+			const int r = e / kFpfhDim;
+			tile[r * kMatchRow + (e - r * kFpfhDim)] = t[(size_t)base * kFpfhDim + (size_t)e];
+		}
+		__syncthreads();
+		for (int r = 0; r < rows; r++) {
+			const float4* row = tile4 + r * (kMatchRow / 4);
+			float d2 = 0.f;
+#pragma unroll
+			for (int w = 0; w < 8; w++) {
+				const float4 u = row[w];
+				float d = __fsub_rn(v[4 * w], u.x);
+				d2 = __fadd_rn(d2, __fmul_rn(d, d));
+				d = __fsub_rn(v[4 * w + 1], u.y);
+				d2 = __fadd_rn(d2, __fmul_rn(d, d));
+				d = __fsub_rn(v[4 * w + 2], u.z);
+				d2 = __fadd_rn(d2, __fmul_rn(d, d));
+				d = __fsub_rn(v[4 * w + 3], u.w);
+				d2 = __fadd_rn(d2, __fmul_rn(d, d));
+			}
+			const float d = __fsub_rn(v[32], tile[r * kMatchRow + 32]);
+			d2 = __fadd_rn(d2, __fmul_rn(d, d));
+			two = match_offer(KnnKey::make(d2, base + r), two);
+		}
+	}
+	if (live) {
+		const size_t at = ((size_t)blockIdx.y * (size_t)nq + (size_t)qi) * 2;
+		partial[at] = two.x;
+		partial[at + 1] = two.y;
+	}
+}
+
+// the two smallest keys of every query over its chunks' pairs (the key order is total, so the merge is exact); d2 / second may be null
+__global__ void __launch_bounds__(256) match_merge_kernel(const unsigned long long* __restrict__ partial, int nq, int chunks, int32_t* __restrict__ index,
+                                                          float* __restrict__ d2, float* __restrict__ second_d2)
+{
+	const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+	if (qi >= nq) return;
+	ulonglong2 two = make_ulonglong2(kKnnNoKey, kKnnNoKey);
+	for (int c = 0; c < chunks; c++) {
+		const size_t at = ((size_t)c * (size_t)nq + (size_t)qi) * 2;
+		two = match_offer(partial[at], two);
+		two = match_offer(partial[at + 1], two);             // the "none" key is below no key: it changes nothing
+	}
+	index[qi] = (int32_t)(unsigned)(two.x & 0xffffffffull);
+	if (d2) d2[qi] = KnnKey::d2(two.x);
+	if (second_d2) second_d2[qi] = two.y == kKnnNoKey ? __uint_as_float(0x7f800000u) : KnnKey::d2(two.y);
+}
+
+// mutual[q] = 1 iff the nearest query of q's nearest target is q
+__global__ void __launch_bounds__(256) match_mutual_kernel(const int32_t* __restrict__ index, const int32_t* __restrict__ back, int nq, unsigned char* __restrict__ mutual)
+{
+	const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+	if (qi >= nq) return;
+	mutual[qi] = back[index[qi]] == qi ? 1 : 0;
+}
+
+// one direction: the smallest key of every one of the nq descriptors of d_q among the nt of d_t, and the d2 of the second smallest
+static hipError_t match_direction(const float* d_q, int nq, const float* d_t, int nt, unsigned long long* partial, int chunks, int chunk_targets,
+                                  int32_t* d_index, float* d_d2, float* d_second, hipStream_t stream)
+{
+	hipLaunchKernelGGL(match_tile_kernel, dim3((nq + kMatchBlock - 1) / kMatchBlock, chunks), dim3(kMatchBlock), 0, stream, d_q, nq, d_t, nt, chunk_targets, partial);
+	KD_TRY(hipGetLastError());
+	hipLaunchKernelGGL(match_merge_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, partial, nq, chunks, d_index, d_d2, d_second);
+	return hipGetLastError();
+}
+
+// the chunks of nt targets for nq queries: whole tiles, as many chunks as bring the launch to about 2 048 workgroups
+static void match_chunks(int nq, int nt, int* chunks, int* chunk_targets)
+{
+	const int tiles = (nt + kMatchTile - 1) / kMatchTile, qblocks = (nq + kMatchBlock - 1) / kMatchBlock;
+	const int want = std::min(tiles, std::max(1, 2048 / qblocks));
+	const int per = (tiles + want - 1) / want;
+	*chunks = (tiles + per - 1) / per;
+	*chunk_targets = per * kMatchTile;
+}
+
+hipError_t launch_match_features(const float* d_q, int nq, const float* d_t, int nt, int32_t* d_index, float* d_d2, float* d_second, unsigned char* d_mutual,
+                                 hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (nq < 1 || nt < 1 || !d_q || !d_t || !d_index || !d_d2 || !d_second) return hipErrorInvalidValue;
+	int chunks = 0, chunk_targets = 0, back_chunks = 0, back_chunk_targets = 0;
+	match_chunks(nq, nt, &chunks, &chunk_targets);
+	match_chunks(nt, nq, &back_chunks, &back_chunk_targets);
+	unsigned long long* partial = nullptr;
+	int32_t* back = nullptr;
+	Temps tmp;
+	size_t words = 2 * (size_t)chunks * (size_t)nq;
+	if (d_mutual) words = std::max(words, 2 * (size_t)back_chunks * (size_t)nt);
+	KD_TRY(tmp.get(partial, words));
+	if (d_mutual) KD_TRY(tmp.get(back, (size_t)nt));
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	KD_TRY(match_direction(d_q, nq, d_t, nt, partial, chunks, chunk_targets, d_index, d_d2, d_second, stream));
+	if (d_mutual) {
+		// the same stream: the merge above has read `partial` before the transposed call writes it
+		KD_TRY(match_direction(d_t, nt, d_q, nq, partial, back_chunks, back_chunk_targets, back, nullptr, nullptr, stream));
+		hipLaunchKernelGGL(match_mutual_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, d_index, back, nq, d_mutual);
+		KD_TRY(hipGetLastError());
+	}
+	return end_and_drain(ev_end, stream);                      // the temporaries are in use until here
+}
+
 // the per-axis minimum and maximum of a cloud on the device: what voxel_frame derives on the host, for a cloud that never leaves the device
 struct MinMax3 { float mn[3], mx[3]; };
 struct MinMaxOf {

@@ -941,6 +941,136 @@ void estimate_normals_host(const float* xyz, size_t n, int32_t k, const float* v
 	});
 }
 
+// ---- FPFH descriptors and descriptor matching: what both paths share, and the host path ----
+void fpfh_check_normals(const float* normals, size_t n)
+{
+	if (!normals) throw std::invalid_argument("goicp fpfh: the normals must be non-null");
+	for (size_t i = 0; i < 3 * n; i++)
+		if (!std::isfinite(normals[i])) throw std::invalid_argument("goicp fpfh: non-finite normal");
+}
+
+void match_check_descriptors(const float* q, size_t nq, const float* t, size_t nt)
+{
+	if (!q || !t || nq == 0 || nt == 0) throw std::invalid_argument("goicp match features: empty descriptor set");
+	if (nq > (size_t)INT32_MAX / 8 || nt > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp match features: descriptor set too large");
+	for (size_t i = 0; i < (size_t)kFpfhDim * nq; i++)
+		if (!std::isfinite(q[i])) throw std::invalid_argument("goicp match features: non-finite query descriptor");
+	for (size_t i = 0; i < (size_t)kFpfhDim * nt; i++)
+		if (!std::isfinite(t[i])) throw std::invalid_argument("goicp match features: non-finite target descriptor");
+}
+
+void fpfh_host(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts)
+{
+	if (!out_fpfh) throw std::invalid_argument("goicp_fpfh_host: out_fpfh must be non-null");
+	float mn[3], mx[3];
+	stat_check_cloud(xyz, n, mn, mx);
+	knn_self_check_params(n, k);
+	fpfh_check_normals(normals, n);
+	std::vector<int32_t> rows(n * (size_t)k);
+	std::vector<float> d2(n * (size_t)k);
+	knn_self_rows(xyz, n, k, mn, mx, rows.data(), d2.data());
+	std::vector<uint8_t> counts(n * (size_t)kFpfhDim, 0);
+	const size_t chunk = 4096;
+	const int threads = n >= 65536 ? 8 : 1, tasks = (int)((n + chunk - 1) / chunk);
+	// the SPFH: the pair features of every point with its row, counted
+	parallel_tasks(threads, tasks, [&](int t) {
+		for (size_t i = (size_t)t * chunk; i < std::min(n, ((size_t)t + 1) * chunk); i++) {
+			uint8_t* c = counts.data() + i * kFpfhDim;
+			for (int j = 0; j < k; j++) {
+				const size_t q = (size_t)rows[i * (size_t)k + j];
+				int b[3];
+				if (!fpfh::pair_bins(xyz + 3 * i, normals + 3 * i, xyz + 3 * q, normals + 3 * q, b)) continue;
+				c[b[0]]++; c[kFpfhBins + b[1]]++; c[2 * kFpfhBins + b[2]]++;
+			}
+		}
+	});
+	// the FPFH: the neighbours' counts weighted by 1 / d2 in row order, each group of 11 scaled to 100, plus the point's own
+	const double inc = 100.0 / (double)k;
+	parallel_tasks(threads, tasks, [&](int t) {
+		for (size_t i = (size_t)t * chunk; i < std::min(n, ((size_t)t + 1) * chunk); i++) {
+			double a[kFpfhDim] = {};
+			for (int j = 0; j < k; j++) {
+				const float w2 = d2[i * (size_t)k + j];
+				if (w2 == 0.f) continue;
+				const double w = 1.0 / (double)w2;
+				const uint8_t* c = counts.data() + (size_t)rows[i * (size_t)k + j] * kFpfhDim;
+				for (int b = 0; b < kFpfhDim; b++) a[b] = a[b] + ((double)c[b] * inc) * w;
+			}
+			for (int g = 0; g < 3; g++) {
+				double s = 0.0;
+				for (int b = 0; b < kFpfhBins; b++) s = s + a[g * kFpfhBins + b];
+				if (s > 0.0) {
+					const double scale = 100.0 / s;
+					for (int b = 0; b < kFpfhBins; b++) a[g * kFpfhBins + b] = a[g * kFpfhBins + b] * scale;
+				}
+			}
+			for (int b = 0; b < kFpfhDim; b++) out_fpfh[i * kFpfhDim + b] = (float)(a[b] + (double)counts[i * kFpfhDim + b] * inc);
+		}
+	});
+	if (out_spfh_counts) std::memcpy(out_spfh_counts, counts.data(), counts.size());
+}
+
+namespace {
+
+// the two smallest keys (bits of d2) << 32 | t of every query of [a, b) over all targets
+void match_rows(const float* q, size_t a, size_t b, const float* t, size_t nt, uint64_t* best, uint64_t* second)
+{
+	for (size_t i = a; i < b; i++) {
+		const float* qi = q + i * kFpfhDim;
+		uint64_t k1 = ~0ull, k2 = ~0ull;
+		for (size_t j = 0; j < nt; j++) {
+			const float* tj = t + j * kFpfhDim;
+			float d2 = 0.f;
+			for (int c = 0; c < kFpfhDim; c++) {
+				const float d = qi[c] - tj[c];
+				d2 = d2 + d * d;
+			}
+			uint32_t bits;
+			std::memcpy(&bits, &d2, sizeof bits);
+			const uint64_t key = ((uint64_t)bits << 32) | (uint32_t)j;
+			if (key < k1) { k2 = k1; k1 = key; }
+			else if (key < k2) k2 = key;
+		}
+		best[i] = k1;
+		if (second) second[i] = k2;
+	}
+}
+
+void match_all(const float* q, size_t nq, const float* t, size_t nt, std::vector<uint64_t>& best, std::vector<uint64_t>* second)
+{
+	best.resize(nq);
+	if (second) second->resize(nq);
+	const size_t chunk = std::max<size_t>(1, std::min<size_t>(256, (1u << 22) / (nt * kFpfhDim) + 1));
+	const int threads = nq * nt >= ((size_t)1 << 22) ? 8 : 1;
+	parallel_tasks(threads, (int)((nq + chunk - 1) / chunk), [&](int task) {
+		match_rows(q, (size_t)task * chunk, std::min(nq, ((size_t)task + 1) * chunk), t, nt, best.data(), second ? second->data() : nullptr);
+	});
+}
+
+}  // namespace
+
+void match_features_host(const float* q, size_t nq, const float* t, size_t nt, int32_t* out_index, float* out_d2, float* out_d2_second, uint8_t* out_mutual)
+{
+	if (!out_index || !out_d2 || !out_d2_second) throw std::invalid_argument("goicp_match_features_host: out_index, out_d2 and out_d2_second must be non-null");
+	match_check_descriptors(q, nq, t, nt);
+	std::vector<uint64_t> best, second, back;
+	match_all(q, nq, t, nt, best, &second);
+	if (out_mutual) match_all(t, nt, q, nq, back, nullptr);
+	auto d2_of = [](uint64_t key) {
+		const uint32_t bits = (uint32_t)(key >> 32);
+		float d2;
+		std::memcpy(&d2, &bits, sizeof d2);
+		return d2;
+	};
+	for (size_t i = 0; i < nq; i++) {
+		const uint32_t j = (uint32_t)(best[i] & 0xffffffffull);
+		out_index[i] = (int32_t)j;
+		out_d2[i] = d2_of(best[i]);
+		out_d2_second[i] = second[i] == ~0ull ? INFINITY : d2_of(second[i]);
+		if (out_mutual) out_mutual[i] = (uint32_t)(back[j] & 0xffffffffull) == (uint32_t)i ? 1 : 0;
+	}
+}
+
 // ---- RANSAC plane segmentation: what both paths share, and the host path ----
 void plane_check_cloud(const float* xyz, size_t n)
 {

@@ -144,6 +144,46 @@ def estimate_normals(xyz, k, viewpoint=None):
     return _normals_call(B.load_library().goicp_estimate_normals_host, xyz, k, viewpoint)
 
 
+FPFH_DIM = 33
+
+
+def _fpfh_call(fn, xyz, normals, k):
+    xyz, normals = _f32(xyz, (-1, 3)), _f32(normals, (-1, 3))
+    if len(normals) != len(xyz):
+        raise ValueError("fpfh: one normal per point")
+    n = len(xyz)
+    out, cnt = np.empty((n, FPFH_DIM), np.float32), np.empty((n, FPFH_DIM), np.uint8)
+    B.check(fn(_fptr(xyz), _fptr(normals), n, int(k), _fptr(out), cnt.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out, cnt
+
+
+def fpfh(xyz, k, normals=None, normal_k=16, viewpoint=None):
+    """goicp_fpfh_host (host only): the 33-bin FPFH descriptor of every point from its k nearest other points and the normals (the
+    caller's, or estimate_normals(xyz, normal_k, viewpoint) when none are given) -> (descriptors (n, 33) float32, SPFH counts (n, 33)
+    uint8).  Registration.fpfh gives the same bits on the device."""
+    if normals is None:
+        normals = estimate_normals(xyz, normal_k, viewpoint)[0]
+    return _fpfh_call(B.load_library().goicp_fpfh_host, xyz, normals, k)
+
+
+def _match_call(fn, fq, ft, mutual):
+    fq, ft = _f32(fq, (-1, FPFH_DIM)), _f32(ft, (-1, FPFH_DIM))
+    nq = len(fq)
+    idx, d2, second = np.empty(nq, np.int32), np.empty(nq, np.float32), np.empty(nq, np.float32)
+    mut = np.empty(nq, np.uint8) if mutual else None
+    B.check(fn(_fptr(fq), nq, _fptr(ft), len(ft), idx.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2), _fptr(second),
+               mut.ctypes.data_as(C.POINTER(C.c_uint8)) if mutual else None))
+    return idx, d2, second, mut
+
+
+def match_features(fq, ft, mutual=True):
+    """goicp_match_features_host (host only): for every query descriptor the nearest target descriptor in the 33-dimensional space, ties
+    to the smaller index -> (indices (n_q,) int32, squared distances (n_q,) float32, the second-nearest squared distances (n_q,) float32,
+    mutual flags (n_q,) uint8 or None).  The cost is n_q * n_t: meant for downsampled clouds.  Registration.match_features gives the same
+    bits on the device."""
+    return _match_call(B.load_library().goicp_match_features_host, fq, ft, mutual)
+
+
 def _cluster_call(fn, xyz, radius, min_neighbors):
     xyz = _f32(xyz, (-1, 3))
     n, ip = len(xyz), C.POINTER(C.c_int32)
@@ -539,6 +579,18 @@ class Registration:
         """goicp_estimate_normals: the module-level estimate_normals on the device (the handle lends its device and stream, its state is
         untouched)"""
         return _normals_call(lambda *a: self._lib.goicp_estimate_normals(self.handle, *a), xyz, k, viewpoint)
+
+    def fpfh(self, xyz, k, normals=None, normal_k=16, viewpoint=None):
+        """goicp_fpfh: the module-level fpfh on the device, the normals too when none are given (the handle lends its device and stream,
+        its state is untouched)"""
+        if normals is None:
+            normals = self.estimate_normals(xyz, normal_k, viewpoint)[0]
+        return _fpfh_call(lambda *a: self._lib.goicp_fpfh(self.handle, *a), xyz, normals, k)
+
+    def match_features(self, fq, ft, mutual=True):
+        """goicp_match_features: the module-level match_features on the device (the handle lends its device and stream, its state is
+        untouched)"""
+        return _match_call(lambda *a: self._lib.goicp_match_features(self.handle, *a), fq, ft, mutual)
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""

@@ -399,6 +399,60 @@ int goicp_knn_self(goicp_handle h, const float* xyz, size_t n, int32_t k, int32_
 int goicp_estimate_normals_host(const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
 int goicp_estimate_normals(goicp_handle h, const float* xyz, size_t n, int32_t k, const float vp[3], float* out_normals, float* out_variation, int32_t* out_index);
 /*
+ * FPFH descriptors and descriptor matching (Rusu, Blodow and Beetz 2009: the Fast Point Feature Histogram, 33 bins; PCL's FPFHEstimation
+ * with setKSearch, Open3D's compute_fpfh_feature with KDTreeSearchParamKNN, and the nearest-descriptor search both libraries' feature
+ * matching starts from).  Each operator has a host function, a device function and a numpy twin that produce the same bits.  Arithmetic
+ * is IEEE, nothing fused.
+ *
+ * FPFH: n points, n float normals (the caller's own, or goicp_estimate_normals' output), k in 1..GOICP_KNN_SELF_MAX, k <= n - 1, counts
+ * the nearest OTHER points.  The neighbourhood of i is row i of the self k-NN at k: key order, with that operator's float d2.  Everything
+ * below is fp64 (every float widened first), each operation rounded once, and uses only + - * / sqrt, comparisons, |.| and floor:
+ *   pair    (i, j): d = p_j - p_i per component, l2 = (d0*d0 + d1*d1) + d2*d2.  The pair is SKIPPED when !(l2 > 0) or when either normal is
+ *           all zeros.  l = sqrt(l2), a1 = (n_i . d) / l, a2 = (n_j . d) / l; every dot is (x*x' + y*y') + z*z'.
+ *           If |a1| < |a2| the frame's source is j: ns = n_j, nt = n_i, d = -d, f3 = -a2.  Otherwise ns = n_i, nt = n_j, f3 = a1 (PCL's
+ *           computePairFeatures).  v = d x ns, every component x*y - z*w with both products rounded; vl2 formed as l2 was; the pair is
+ *           skipped when !(vl2 > 0).  v_c = v_c / sqrt(vl2), w = ns x v, f2 = v . nt, x = ns . nt, y = w . nt;
+ *   bins    b3 = clamp(floor(11.0 * ((f3 + 1.0) * 0.5)), 0, 10), clamped before the conversion to an integer; b2 the same over f2.
+ *           b1 is the bin of atan2(y, x) among 11 equal bins of [-pi, pi), decided without atan2: with (a, b) = (-x, -y), whose angle is
+ *           atan2(y, x) + pi in [0, 2 pi), and (C_k, S_k) = GOICP_FPFH_COS[k - 1], GOICP_FPFH_SIN[k - 1], the doubles nearest the cosine
+ *           and sine of 2 pi k / 11, cross_k = C_k*b - S_k*a with both products rounded; the test of k holds when b < 0 || cross_k >= 0
+ *           for k <= 5 and when b < 0 && cross_k >= 0 for k >= 6; b1 = the number of k in 1..10 whose test holds.  x == 0 && y == 0
+ *           gives bin 5 (atan2(0, 0) = 0);
+ *   SPFH    exact integer counts c_i[33] over the k neighbours of i in PCL's layout: c[b1], c[11 + b2], c[22 + b3] each go up by one per
+ *           pair; skipped pairs count nowhere;
+ *   FPFH    inc = 100.0 / (double)k.  For every bin, a_b = sum over the row of (((double)c_jb * inc) * w_j), added in key order from 0,
+ *           w_j = 1.0 / (double)d2_j (the squared-distance weight of PCL and Open3D); neighbours with d2_j == 0 are skipped.  For each of
+ *           the three groups of 11 bins, s_g = sum of a_b ascending in b from 0; when s_g > 0, a_b = a_b * (100.0 / s_g).
+ *           out_b = (float)(a_b + (double)c_ib * inc);
+ *   output  out_fpfh: n x GOICP_FPFH_DIM floats in input order; out_spfh_counts (may be NULL): n x GOICP_FPFH_DIM uint8, the counts c_i.
+ * GOICP_ERR_INVALID, nothing written: what goicp_knn_self refuses, a NULL or non-finite normal, and for the handle form any call while a
+ * registration runs.
+ *
+ * Matching: for every one of n_q query descriptors (GOICP_FPFH_DIM floats each) the nearest of n_t target descriptors.  Float:
+ *   pair    d2(q, t) = sum over b = 0..32 of (q_b - t_b) * (q_b - t_b), added left to right from 0;
+ *   order   by the key ((uint64)bits of d2 << 32) | t, ascending: ties go to the smaller index;
+ *   output  out_index (n_q int32), out_d2 (n_q floats): the smallest key; out_d2_second (n_q floats): the d2 of the second-smallest key,
+ *           +inf when n_t == 1 (for the caller's ratio test); out_mutual (may be NULL; n_q uint8): 1 iff the query is in turn the
+ *           smallest-key match of its target, the same rule with the two sets exchanged, else 0.
+ * The cost is n_q * n_t * 33 subtractions, products and additions in the order above (no matrix instruction can keep that order): it
+ * is meant for downsampled clouds of some 10^4 descriptors, not for raw scans.
+ * GOICP_ERR_INVALID, nothing written: NULL arguments (out_mutual aside), n_q == 0, n_t == 0, a size above goicp_create's limit, a
+ * non-finite descriptor, and for the handle form any call while a registration runs.
+ * goicp_match_features_tile(): the number of target descriptors the device kernel stages per tile (tests cut their sizes around it).
+ */
+#define GOICP_FPFH_DIM 33
+#define GOICP_FPFH_COS { 0x1.aeb8c8764f0bap-1, 0x1.a9628d9c712b6p-2, -0x1.2375f640f44dbp-3, -0x1.4f49e7f775887p-1, -0x1.eb42a9bcd5057p-1, \
+                         -0x1.eb42a9bcd5057p-1, -0x1.4f49e7f775887p-1, -0x1.2375f640f44dbp-3, 0x1.a9628d9c712b6p-2, 0x1.aeb8c8764f0bap-1 }
+#define GOICP_FPFH_SIN { 0x1.14cedf8bb580bp-1, 0x1.d1bb48eee2c13p-1, 0x1.fac9e043842efp-1, 0x1.82f19bb3a28a1p-1, 0x1.207e7fd768dbfp-2, \
+                         -0x1.207e7fd768dbfp-2, -0x1.82f19bb3a28a1p-1, -0x1.fac9e043842efp-1, -0x1.d1bb48eee2c13p-1, -0x1.14cedf8bb580bp-1 }
+int goicp_fpfh_host(const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts);
+int goicp_fpfh(goicp_handle h, const float* xyz, const float* normals, size_t n, int32_t k, float* out_fpfh, uint8_t* out_spfh_counts);
+int goicp_match_features_host(const float* query, size_t n_q, const float* target, size_t n_t, int32_t* out_index, float* out_d2, float* out_d2_second,
+                              uint8_t* out_mutual);
+int goicp_match_features(goicp_handle h, const float* query, size_t n_q, const float* target, size_t n_t, int32_t* out_index, float* out_d2,
+                         float* out_d2_second, uint8_t* out_mutual);
+int goicp_match_features_tile(void);
+/*
  * Euclidean / DBSCAN clustering (PCL's EuclideanClusterExtraction, Open3D's cluster_dbscan): connected components under a distance, and
  * the filter "keep the largest clusters" built on it.  The host functions, the device functions and the clustered swap produce the same
  * bits.  The only float expression is the radius filter's pair; everything else is integers:

@@ -353,6 +353,29 @@ public:
 		check(goicp_estimate_normals(h_, reinterpret_cast<const float*>(cloud.data()), n, (int32_t)k, viewpoint, reinterpret_cast<float*>(normals.data()),
 		                             variation ? variation->data() : nullptr, nullptr));
 	}
+	// the 33-bin FPFH descriptor of every point of any cloud with its normals, on the device (goicp_fpfh): descriptors gets n x GOICP_FPFH_DIM
+	// floats; k counts the nearest other points; spfh_counts (may be null) gets the n x GOICP_FPFH_DIM counts of the simplified histograms
+	template <class Point3>
+	void fpfh(const std::vector<Point3>& cloud, const std::vector<Point3>& normals, size_t n, int k, std::vector<float>& descriptors,
+	          std::vector<uint8_t>* spfh_counts = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		if (normals.size() < n || cloud.size() < n) throw std::runtime_error("fpfh: one point and one normal per descriptor");
+		descriptors.resize(n * (size_t)GOICP_FPFH_DIM);
+		if (spfh_counts) spfh_counts->resize(descriptors.size());
+		check(goicp_fpfh(h_, reinterpret_cast<const float*>(cloud.data()), reinterpret_cast<const float*>(normals.data()), n, (int32_t)k, descriptors.data(),
+		                 spfh_counts ? spfh_counts->data() : nullptr));
+	}
+	// the nearest target descriptor of every query descriptor, on the device (goicp_match_features; n_q * n_t pairs: for downsampled clouds).
+	// index, d2 and d2_second get one entry per query; mutual (may be null) 1 where the match holds in both directions
+	void match_features(const std::vector<float>& query, const std::vector<float>& target, std::vector<int32_t>& index, std::vector<float>& d2,
+	                    std::vector<float>& d2_second, std::vector<uint8_t>* mutual = nullptr) const
+	{
+		const size_t nq = query.size() / GOICP_FPFH_DIM, nt = target.size() / GOICP_FPFH_DIM;
+		index.resize(nq); d2.resize(nq); d2_second.resize(nq);
+		if (mutual) mutual->resize(nq);
+		check(goicp_match_features(h_, query.data(), nq, target.data(), nt, index.data(), d2.data(), d2_second.data(), mutual ? mutual->data() : nullptr));
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
