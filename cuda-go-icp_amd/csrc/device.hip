@@ -2258,6 +2258,9 @@ __device__ __forceinline__ RowNn rows_nearest(const KdDesc& kd, const DtDesc& dt
 			if (!acted && d == L) {
 				int c;
 				const unsigned m = row_take(key[L], l, row, c);
+				// bbits / b2bits are the bits of a distance, finite or +inf (<= 0x7f800000), in every template form and from the first step
+				// on, so the all-taken key 0xffffffff always lies above them: an emptied group is left here without a test of its own
+				// (rows_knn's bound is 0xffffffff while its list is short, and it has one)
 				if ((m & ~3u) > (TWO ? b2bits : bbits)) {            // nothing left within the best (TWO: second-best) distance
 					if (L == 0) { done = true; acted = true; }
 					else d = L - 1;
@@ -3657,7 +3660,12 @@ __device__ __forceinline__ void rows_knn(const KdDesc& kd, const DtDesc& dt, con
 			if (!acted && d == L) {
 				int c;
 				const unsigned m = row_take(key[L], l, row, c);
-				if ((m & ~3u) > bound) {
+				// A group with nothing left to take is exhausted whatever the bound: while the list is short the bound is 0xffffffff, which
+				// no key lies above, and the all-taken key (no real key: box distances are finite or +inf) would otherwise send the row back
+				// into child 3 of the group, for ever if that leaf is empty, inserting its points again if not.  Reached by hierarchies whose
+				// bottom groups hold fewer than k points (the device build at M / 64^(K-1) < k); k <= M lets every walk fill its list.
+				// rows_nearest needs no such test: its bound is a distance from the first step on, finite or +inf, below the all-taken key
+				if (m == 0xffffffffu || (m & ~3u) > bound) {
 					if (L == 0) { done = true; acted = true; }
 					else d = L - 1;
 				} else if (L == K - 1) {

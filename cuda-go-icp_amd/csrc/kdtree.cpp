@@ -41,8 +41,10 @@ void parallel_tasks(int threads, int ntasks, const std::function<void(int)>& fn)
 // Balanced binary k-d tree by median splits along the widest extent, of the smallest depth D whose
 // 2^D leaves hold <= leaf_max points each, flattened into K = ceil(D/6) levels of 64-ary box groups.
 // The ROOT group is the sparse one: it has F = 2^(D - 6(K-1)) real children (the binary nodes at that
-// depth; the other child slots are empty boxes, which no query ever enters), every group below has
-// 64.  A level-l group (l >= 1) is the binary node at depth d_l = log2(F) + 6(l-1) with index g, its
+// depth; the other child slots are empty boxes at distance +inf, which a walk enters only while its
+// bound is not yet a finite distance -- the k-NN walk while its list is short.  Never here: the real
+// children are taken first and hold all M >= k points.  The device build's empty leaves are entered
+// that way, kdbuild.hip), every group below has 64.  A level-l group (l >= 1) is the binary node at depth d_l = log2(F) + 6(l-1) with index g, its
 // children are the nodes 6 binary levels below (g*64 + c): the walker's node arithmetic needs no
 // child pointers and no per-level fan-out.  Sizing the depth to the cloud keeps leaves full (100 k
 // points: 8 192 leaves of 12 instead of 262 144 leaves of 0.4; 1 M: 65 536 of 15 instead of 262 144 of 4).
