@@ -2938,6 +2938,28 @@ __device__ __forceinline__ void kabsch_rows(double b0, double b1, double b2, int
 		if (!(W1 > 1e-200) && W2 > 1e-200 && W0 > 1e-200) u1 = a2 * c0 - c2 * a0;       // columns a = 2, b = 0
 		if (!(W2 > 1e-200) && W0 > 1e-200 && W1 > 1e-200) u2 = a0 * c1 - c0 * a1;       // columns a = 0, b = 1
 	}
+	// rank-1 input (every matched target point on one line; exactly so when the line is parallel to an axis): one left vector u, and any
+	// orthonormal pair across it completes the basis -- the objective tr(R H) = W_k does not see the choice.  a = e x u, e the axis u has
+	// the least of, normalised; b = u x a.  Uniform: the norms and the three components of u are the same in every lane.
+	{
+		const bool p0 = W0 > 1e-200, p1 = W1 > 1e-200, p2 = W2 > 1e-200;
+		const double uk = p0 ? u0 : p1 ? u1 : u2;
+		const double x = lane_get(uk, 0), y = lane_get(uk, 1), z = lane_get(uk, 2);
+		if ((int)p0 + (int)p1 + (int)p2 == 1) {
+			const double fx = fabs(x), fy = fabs(y), fz = fabs(z);
+			double ax, ay, az;
+			if (fx <= fy && fx <= fz) { ax = 0.0; ay = -z; az = y; }                     // e_x x u
+			else if (fy <= fz) { ax = z; ay = 0.0; az = -x; }                            // e_y x u
+			else { ax = -y; ay = x; az = 0.0; }                                          // e_z x u
+			const double rn = rsqrt(ax * ax + ay * ay + az * az);                        // |e x u|^2 >= 2/3 for a unit u
+			ax *= rn; ay *= rn; az *= rn;
+			const double bx = y * az - z * ay, by = z * ax - x * az, bz = x * ay - y * ax;
+			const double ar = row == 0 ? ax : row == 1 ? ay : az, br = row == 0 ? bx : row == 1 ? by : bz;
+			if (p0) { u1 = ar; u2 = br; }
+			else if (p1) { u2 = ar; u0 = br; }
+			else { u0 = ar; u1 = br; }
+		}
+	}
 	// VUt[row][j] = sum_k V[row][k] U[j][k]
 	double vut[3];
 #pragma unroll
@@ -2969,8 +2991,7 @@ __device__ __forceinline__ void kabsch_rows(double b0, double b1, double b2, int
 	// H = 0 has no singular direction at all, and U above is the zero matrix: the rotation of the reference's SVD there is the identity
 	// (U = V = I), the step a pure translation.  It is what a single correspondence gives, exactly: the pass centres on the pivot cq =
 	// R * centroid + t, which for one point is the moved point itself (the same float expression), so every term of H is an exact 0.
-	// Uniform: the norms are wave-wide sums.  An H with two vanishing singular values (collinear correspondences) still leaves two columns
-	// of U zero and the result singular: degenerate geometry beyond this case is not handled here.
+	// Uniform: the norms are wave-wide sums.  (One or two vanishing columns were completed above: the result is a rotation for every finite H.)
 	if (n0 == 0.0 && n1 == 0.0 && n2 == 0.0) {                              // exact zeros only: a NaN in H still propagates
 #pragma unroll
 		for (int j = 0; j < 3; j++) r[j] = row == j ? 1.f : 0.f;
@@ -3052,6 +3073,18 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ sums, I
 	for (int j = 0; j < 3; j++) {
 		const double hj = sums[6 + 3 * a + j] - alpha * sums[3 + j] - sums[a] * lane_get(beta, j) + nn * alpha * lane_get(beta, j);
 		h[j] = (double)(float)hj;                                            // the reference holds H in float
+	}
+	// An H that is nothing but the rounding of its own terms (every correspondence the same target point: the centred target terms are one
+	// constant, H is exactly 0 in exact arithmetic and about 2^-24 of a product as summed) has no direction to give: it is taken as the 0 it
+	// stands for -- kabsch_rows' identity, a pure translation.  The scale: T = sum |q - cq|^2 + sum |m - cm|^2, from the pass's own sums
+	// (sum d^2 = T + n |c|^2 - 2 tr S + 2 c . (sum (q - cq) - sum (m - cm)), c = cq - cm); each of the four terms of an entry of H is at most T / 2
+	// (Cauchy-Schwarz) and carries the float rounding of a product and of a row sum of 16, together under 2^-20 T.  A covariance a
+	// registration can use is of the order of T.  The robust pass weights the 15 terms and not d^2: no T there, H stays as it is.
+	if constexpr (!ROBUST) {
+		const double c = (double)cq - (double)cm;
+		const double T = sums[15] + 2.0 * sum3(sums[6 + 4 * a]) - nn * sum3(c * c) - 2.0 * sum3(c * (sums[a] - sums[3 + a]));
+		const double hm = fmax(fabs(h[0]), fmax(fabs(h[1]), fabs(h[2])));
+		if (fmax(lane_const<0>(hm), fmax(lane_const<1>(hm), lane_const<2>(hm))) <= kIcpCovNoise * T) h[0] = h[1] = h[2] = 0.0;
 	}
 	float Rrow[3];
 	kabsch_rows(h[0], h[1], h[2], a, Rrow);
@@ -4060,10 +4093,52 @@ __global__ __launch_bounds__(kIcpThreads, 2048 / kIcpThreads) void icp_opt_pass_
 			src, N, st, kd, dt, normals, a, capped, src_normals, gicp_eps);
 }
 
+// fp64 6x6 symmetric eigenproblem by cyclic Jacobi rotations, sym3_smallest's rotation on both sides: S -> diagonal (the eigenvalues), E (the
+// identity on entry) -> the eigenvectors in its columns.  A pair whose off-diagonal entry is within `off` is left alone.  Every index is a
+// constant once the pair loops are unrolled: both matrices live in registers.
+__device__ __forceinline__ void sym6_jacobi(double (&S)[6][6], double (&E)[6][6], double off)
+{
+#pragma unroll 1
+	for (int sweep = 0; sweep < 32; sweep++) {
+		bool rotated = false;
+#pragma unroll
+		for (int p = 0; p < 5; p++) {
+#pragma unroll
+			for (int q = p + 1; q < 6; q++) {
+				const double app = S[p][p], aqq = S[q][q], apq = S[p][q];
+				if (!(apq == 0.0 || fabs(apq) <= off)) {
+					rotated = true;
+					const double da = aqq - app, db = 2 * apq;
+					const double tn = (da >= 0 ? db : -db) / (fabs(da) + sqrt(da * da + db * db));
+					const double cs = rsqrt(1 + tn * tn), sn = cs * tn;
+#pragma unroll
+					for (int k = 0; k < 6; k++) {                           // S <- S G (columns p, q)
+						const double akp = S[k][p], akq = S[k][q];
+						S[k][p] = cs * akp - sn * akq; S[k][q] = sn * akp + cs * akq;
+					}
+#pragma unroll
+					for (int k = 0; k < 6; k++) {                           // S <- G^T S (rows p, q)
+						const double apk = S[p][k], aqk = S[q][k];
+						S[p][k] = cs * apk - sn * aqk; S[q][k] = sn * apk + cs * aqk;
+					}
+					S[p][q] = 0.0; S[q][p] = 0.0;
+#pragma unroll
+					for (int k = 0; k < 6; k++) {
+						const double ekp = E[k][p], ekq = E[k][q];
+						E[k][p] = cs * ekp - sn * ekq; E[k][q] = sn * ekp + cs * ekq;
+					}
+				}
+			}
+		}
+		if (!rotated) break;
+	}
+}
+
 // One wavefront: the replicas -> 28 integer totals (replicas zeroed) -> double; the stop test of finalize_rows; else the damped
 // Gauss-Newton step (A + mu I) x = -b by fp64 Cholesky, mu = 1e-12 trace(A); omega = x[0:3], tau = x[3:6]; dR = Rodrigues(omega);
-// R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is not positive definite (no usable normal) leaves
-// the pose unchanged: the next pass then scores the same error and the loop stops.
+// R <- dR R, t <- dR (t - cq) + cq + tau, cq <- R src_centroid + t.  A system that is rank deficient under kIcpRankTol (a planar target: rank
+// 3) takes the minimum-norm step over its retained eigenvalues instead; one with no positive eigenvalue (no usable normal) leaves the pose
+// unchanged: the next pass then scores the same error and the loop stops.
 // GATE: word 28 is the inlier count (unscaled); the stop rule is gate_step's, the Cholesky system is the one over the inliers as it stands.
 // PLANE = false: the same wavefront as the gated POINT-TO-POINT finalize -- the gated pass of either metric adds to kIcpPlaneStride-word
 // replicas -- 16 scaled totals and the count in word 16, then finalize_rows<GATE>
@@ -4169,8 +4244,74 @@ __device__ __forceinline__ void icp_plane_finalize_body(unsigned long long* acc,
 		for (int k = i2 + 1; k < 6; k++) s2 -= A[k][i2] * xs[k];
 		xs[i2] = s2 / A[i2][i2];
 	}
+	// Is the system rank deficient under the rule?  tr(A) tr(A^-1) lies between the condition number and 36 times it (lambda_max <= tr(A) <=
+	// 6 lambda_max, the same for A^-1), and tr(A^-1) is the squared Frobenius norm of L^-1: 6 reciprocals and 35 products.  Below the bar the
+	// smallest eigenvalue is certainly above the rule and the Cholesky step stands as it is; a failed factorisation or an estimate at the bar
+	// (a condition number of at least 1.4e4) sends the system to the eigenvalues, which decide.
+	bool trouble = !ok;
+	if (ok) {
+		double rl[6], tinv = 0.0;
 #pragma unroll
-	for (int a = 0; a < 6; a++) xs[a] = ok ? xs[a] : 0.0;
+		for (int j = 0; j < 6; j++) rl[j] = 1.0 / A[j][j];
+#pragma unroll
+		for (int c = 0; c < 6; c++) {
+			double z[6];                                                 // column c of L^-1
+			z[c] = rl[c];
+			tinv += z[c] * z[c];
+#pragma unroll
+			for (int i2 = c + 1; i2 < 6; i2++) {
+				double s2 = 0.0;
+#pragma unroll
+				for (int k = c; k < i2; k++) s2 -= A[i2][k] * z[k];
+				z[i2] = s2 * rl[i2];
+				tinv += z[i2] * z[i2];
+			}
+		}
+		trouble = !(tr * tinv < 0.5 / kIcpRankTol);
+	}
+	if (trouble) {
+		// the sums again, without the shift; then the eigenvalues: kept are those above kIcpRankTol times the largest.  Full rank: the Cholesky
+		// step, untouched.  Else the minimum-norm step x = -sum over the kept (v . b) / lambda v -- no motion along a direction the
+		// correspondences do not constrain (a planar target: the turn about its normal and the slide along it)
+		double S[6][6], E[6][6];
+		{
+			int k = 0;
+#pragma unroll
+			for (int a = 0; a < 6; a++)
+#pragma unroll
+				for (int c = a; c < 6; c++) { S[a][c] = sums[k]; S[c][a] = sums[k]; k++; }
+#pragma unroll
+			for (int a = 0; a < 6; a++)
+#pragma unroll
+				for (int c = 0; c < 6; c++) E[a][c] = a == c ? 1.0 : 0.0;
+		}
+		int rank = 0;
+		double lmax = 0.0;
+		if (tr > 0.0) {
+			sym6_jacobi(S, E, 1e-16 * tr);
+#pragma unroll
+			for (int a = 0; a < 6; a++) lmax = fmax(lmax, S[a][a]);
+#pragma unroll
+			for (int a = 0; a < 6; a++) rank += S[a][a] > kIcpRankTol * lmax ? 1 : 0;
+		}
+		if (!(ok && rank == 6)) {
+			double g[6];
+#pragma unroll
+			for (int a = 0; a < 6; a++) {
+				double s2 = 0.0;
+#pragma unroll
+				for (int k = 0; k < 6; k++) s2 += E[k][a] * b[k];
+				g[a] = lmax > 0.0 && S[a][a] > kIcpRankTol * lmax ? -s2 / S[a][a] : 0.0;
+			}
+#pragma unroll
+			for (int a = 0; a < 6; a++) {
+				double s2 = 0.0;
+#pragma unroll
+				for (int k = 0; k < 6; k++) s2 += E[a][k] * g[k];
+				xs[a] = s2;
+			}
+		}
+	}
 	// dR = Rodrigues(omega) = I + sin(th)/th W + (1 - cos(th))/th^2 W^2, W = [omega]x
 	const double wx = xs[0], wy = xs[1], wz = xs[2];
 	const double th = sqrt(wx * wx + wy * wy + wz * wz);

@@ -116,6 +116,12 @@ struct Pose { float R[9]; float t[3]; };
 constexpr int kGroup = 8;          // cubes per workgroup pass (the 8 siblings of one BnB expansion)
 constexpr int kBoundsThreads = 256;
 constexpr int kIcpAcc = 16;        // sum(q-cq)[3] sum(m-cm)[3] sum((q-cq)(m-cm)^T)[9] sum(d^2)
+// the rank rule of every 6x6 pose matrix: an eigenvalue counts iff it exceeds kIcpRankTol times the largest (the Gauss-Newton solve of
+// the opt-in ICP iterations, pose_information's default)
+constexpr double kIcpRankTol = 1e-6;
+// a point-to-point covariance H whose largest entry is within kIcpCovNoise of sum |q - cq|^2 + sum |m - cm|^2 is the rounding of its own terms
+// and is taken as 0 (finalize_rows)
+constexpr double kIcpCovNoise = 0x1p-20;
 
 // ---- bounds ---------------------------------------------------------------------------------
 // scratch must hold groups*chunks*2*kGroup floats.  ub/lb: [B].

@@ -234,7 +234,7 @@ public:
 	// fixed-point sums, rank_tol outside [0, 1), K outside 1..1024, while a registration runs
 	void pose_information(size_t K, const float* R, const float* t, const goicp_pose_info_options* opt, goicp_pose_info* out, bool batch);
 	void result_information(const goicp_pose_info_options* opt, goicp_pose_info* out);   // at optR | optT of the last finished registration
-	static constexpr double kPoseInfoRankTol = 1e-6;
+	static constexpr double kPoseInfoRankTol = kIcpRankTol;
 	void knn_query(const float* q_xyz, size_t n, int k, int32_t* idx, float* d2);
 	double normal_build_ms() const { return normal_build_ms_; }   // exact, ascending (d2, index), n x k
 	double source_normal_build_ms() const { return source_normal_build_ms_; }

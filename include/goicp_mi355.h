@@ -667,7 +667,9 @@ int goicp_nn_query(goicp_handle h, const float* query_xyz, size_t n, int32_t* in
  * metric), the ICP inside goicp_register (every driver) and the per-rank ICP of goicp_register_sharded*.  With metric 1 every iteration
  * is one damped Gauss-Newton step on sum_i ((q_i - m_i) . n_i)^2, linearised about the transformed source centroid: m_i = the exact
  * nearest target point of q_i (the same neighbour search as point-to-point), n_i = its normal.  err keeps its meaning: the sum of
- * squared NN distances of the last pass; the stop rule is ICP3D::Run's.  Refused (GOICP_ERR_INVALID): metric 1 with trim_fraction > 0,
+ * squared NN distances of the last pass; the stop rule is ICP3D::Run's.  Where the 6x6 matrix of an iteration is rank deficient under
+ * goicp_pose_information's default rule (eigenvalues <= 1e-6 of the largest; a planar target: rank 3), the step is the minimum-norm one
+ * over the retained eigenvalues: no motion along a direction the correspondences leave free.  Refused (GOICP_ERR_INVALID): metric 1 with trim_fraction > 0,
  * metric outside {0, 1}, normal_k outside [3, 32], any change while a registration runs.  goicp_icp_run_collective runs metric 1
  * replicated on every rank (the metric joins its check word); goicp_register_multi_gpu stays point-to-point. */
 typedef struct goicp_icp_options {
