@@ -11,7 +11,7 @@ from . import binding  # noqa: F401
 from .binding import GoicpError, build_library, library_path, load_library  # noqa: F401
 from .fgoicp import (Config, FastGoICP, IterativeClosestPoint3D, Registration, RotNode, TransNode,  # noqa: F401
                      cluster, cluster_filter, estimate_normals, fpfh, knn_self, load_cloud, match_features, plane_filter, radius_outlier_removal,
-                     segment_plane, source_order,
+                     feature_poses, ransac_pose, segment_plane, select_matches, source_order,
                      statistical_outlier_removal, voxel_downsample)
 
 

@@ -119,6 +119,19 @@ PLANE_MAX_ITERATIONS = 65536
 PLANE_MAX_PLANES = 8
 
 
+class CRansacPoseSelect(C.Structure):
+    _fields_ = [("distance", C.c_float), ("iterations", C.c_int32), ("refine", C.c_int32), ("max_poses", C.c_int32), ("min_inliers", C.c_int32),
+                ("edge_similarity", C.c_float), ("seed", C.c_uint64)]
+
+
+class CRansacPose(C.Structure):
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("inliers", C.c_int32), ("hypothesis", C.c_int32), ("refined", C.c_int32)]
+
+
+RANSAC_POSE_MAX_ITERATIONS = 1 << 20
+RANSAC_POSE_MAX_POSES = 64
+
+
 class CPoseInfoOptions(C.Structure):
     _fields_ = [("metric", C.c_int32), ("use_pivot", C.c_int32), ("pivot", C.c_double * 3), ("rank_tol", C.c_double)]
 
@@ -264,6 +277,15 @@ SYMBOLS = {
     "goicp_match_features_host": (C.c_int, [_fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint8)]),
     "goicp_match_features": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint8)]),
     "goicp_match_features_tile": (C.c_int, []),
+    "goicp_ransac_pose_select_default": (None, [C.POINTER(CRansacPoseSelect)]),
+    "goicp_ransac_pose_host": (C.c_int, [_fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(CRansacPoseSelect),
+                                        C.POINTER(CRansacPose), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8)]),
+    "goicp_ransac_pose": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(CRansacPoseSelect),
+                                   C.POINTER(CRansacPose), C.POINTER(C.c_size_t), C.POINTER(C.c_uint8)]),
+    "goicp_select_matches": (C.c_int, [C.POINTER(C.c_int32), _fp, _fp, C.POINTER(C.c_uint8), C.c_size_t, C.c_float, C.c_int32, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_size_t)]),
+    "goicp_ransac_pose_tile": (C.c_int, []),
+    "goicp_ransac_pose_block": (C.c_int, []),
     "goicp_search_truncation": (C.c_int, [_vp, _fp]),
     "goicp_register": (C.c_int, [_vp]),
     "goicp_cancel": (C.c_int, [_vp]),

@@ -88,6 +88,15 @@
 //               default 16); every descriptor of SRC is matched to its nearest of TGT (goicp_estimate_normals, goicp_fpfh and
 //               goicp_match_features on the device when there is one, the _host forms otherwise: the same bits).  OUT.txt gets one line
 //               `i j d2 d2_second` per mutual match.  Refused together with --ranks -- before any device is touched
+//   --feature-init [--feature-voxel V] [--fpfh-k K] [--normal-k K] [--match-ratio R] [--ransac-distance D] [--ransac-iterations T]
+//               [--ransac-poses K] [--ransac-seed X]   modes 0..2: the ICP starts from the best feature pose, not from the identity.  Both
+//               clouds (reduced by a voxel grid of pitch V when given) get normals (--normal-k, 3..32, default 16) and FPFH descriptors
+//               (--fpfh-k, 1..32, default 16) on the device; the mutual matches that pass the ratio test (--match-ratio, default 0 = none) go to
+//               goicp_ransac_pose (inlier distance D, default 1.5 V; T hypotheses, default 100 000; K poses, default 1; seed X) and
+//               goicp_icp_run refines the best-supported pose for --iters iterations.  With this flag alone --normal-k is the features' k; it
+//               reaches the ICP options only together with --point-to-plane, --symmetric or --generalized.  Refused together with --ranks,
+//               --source-list, modes 3/4 and a config with [io] output or visualization (those files report the engine's own state) --
+//               before any device is touched
 //   modes 0/1/2 (plain ICP, src/main.cpp:99-110): N ICP iterations (the reference iterates forever; default 50)
 //   modes 3/4   (Go-ICP,   src/main.cpp:111-141): full registration
 // Prints the result the way the reference logs it and writes io.output (output.toml) when set.
@@ -336,7 +345,7 @@ int main(int argc, char** argv)
 		if (!std::strcmp(argv[i], "--estimate-normals")) return estimate_normals_mode(argc, argv, i);
 	for (int i = 1; i < argc; i++)
 		if (!std::strcmp(argv[i], "--fpfh-match")) return fpfh_match_mode(argc, argv, i);
-	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--generalized [--gicp-epsilon E]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: goicp_cli <config.toml> [--iters N] [--trim-fraction F] [--verbose] [--seed S] [--ranks N] [--reference-root] [--point-to-plane] [--normal-k K] [--symmetric [--source-normal-k K]] [--generalized [--gicp-epsilon E]] [--max-corr-dist D] [--robust-kernel {huber,cauchy,gm,tukey} --robust-scale C] [--trunc-dist D] [--information [--information-rank-tol X]] [--source-list FILE] [--voxel V] [--target-voxel V] [--outlier-radius R --outlier-min-neighbors K] [--target-outlier-radius R --target-outlier-min-neighbors K] [--stat-neighbors K --stat-std-ratio A] [--target-stat-neighbors K --target-stat-std-ratio A] [--plane-distance D [--plane-iterations T] [--plane-max P] [--plane-min-inliers S] [--plane-seed X] [--plane-no-refine]] [--target-plane-distance D ...] [--feature-init [--feature-voxel V] [--fpfh-k K] [--match-ratio R] [--ransac-distance D] [--ransac-iterations T] [--ransac-poses K] [--ransac-seed X]]\n"); return 2; }
 	int iters = 50, verbose = 0, ranks = 1, reference_root = 0, plane = 0, normal_k = 16, symmetric = 0, source_normal_k = 16, generalized = 0;
 	float gicp_epsilon = 1e-3f;
 	const char* snk_arg = nullptr;
@@ -370,6 +379,13 @@ int main(int argc, char** argv)
 	int pl_no_refine[2] = {0, 0};
 	goicp_plane_select plane_sel[2];                                                                        // [0] the source's, [1] the target's
 	for (int k = 0; k < 2; k++) goicp_plane_select_default(&plane_sel[k]);
+	// --feature-init: the ICP of modes 0..2 starts from the best RANSAC pose over FPFH matches, not from the identity
+	int feature_init = 0;
+	const char* ft_arg[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // voxel, fpfh-k, match-ratio, ransac-distance, -iterations, -poses, -seed
+	float feature_voxel = 0.f, match_ratio = 0.f;
+	long fpfh_k = 16;
+	goicp_ransac_pose_select ransac_sel;
+	goicp_ransac_pose_select_default(&ransac_sel);
 	for (int i = 2; i < argc; i++) {
 		if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) iters = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -400,6 +416,14 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--stat-std-ratio")) sa_arg[0] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-neighbors")) sk_arg[1] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--target-stat-std-ratio")) sa_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--feature-init")) feature_init = 1;
+		else if (!std::strcmp(argv[i], "--feature-voxel")) ft_arg[0] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--fpfh-k")) ft_arg[1] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--match-ratio")) ft_arg[2] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--ransac-distance")) ft_arg[3] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--ransac-iterations")) ft_arg[4] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--ransac-poses")) ft_arg[5] = i + 1 < argc ? argv[++i] : "";
+		else if (!std::strcmp(argv[i], "--ransac-seed")) ft_arg[6] = i + 1 < argc ? argv[++i] : "";
 		else if (!std::strcmp(argv[i], "--plane-no-refine")) pl_no_refine[0] = 1;
 		else if (!std::strcmp(argv[i], "--target-plane-no-refine")) pl_no_refine[1] = 1;
 		else {
@@ -413,6 +437,53 @@ int main(int argc, char** argv)
 			                                            "--target-plane-seed"}};
 			for (int q = 0; q < 10; q++)
 				if (!std::strcmp(name, pl_names[q / 5][q % 5])) { pl_arg[q / 5][q % 5] = i + 1 < argc ? argv[++i] : ""; break; }
+		}
+	}
+	{
+		// bad feature options are refused before any device is touched
+		static const char* const ft_names[7] = {"--feature-voxel", "--fpfh-k", "--match-ratio", "--ransac-distance", "--ransac-iterations", "--ransac-poses",
+		                                        "--ransac-seed"};
+		for (int q = 0; q < 7; q++) {
+			if (!ft_arg[q]) continue;
+			if (!feature_init) {
+				std::fprintf(stderr, "error: %s needs --feature-init\n", ft_names[q]);
+				return 2;
+			}
+			char* end = nullptr;
+			bool ok = true;
+			if (q == 0 || q == 2 || q == 3) {
+				const float v = std::strtof(ft_arg[q], &end);
+				ok = end != ft_arg[q] && *end == '\0' && v <= 3.402823466e+38f && (q == 2 ? v >= 0.f : v > 0.f);
+				(q == 0 ? feature_voxel : (q == 2 ? match_ratio : ransac_sel.distance)) = v;
+			} else if (q == 6) {
+				ransac_sel.seed = std::strtoull(ft_arg[q], &end, 10);
+				ok = end != ft_arg[q] && *end == '\0';
+			} else {
+				const long v = std::strtol(ft_arg[q], &end, 10);
+				const long hi = q == 1 ? GOICP_KNN_SELF_MAX : (q == 4 ? GOICP_RANSAC_POSE_MAX_ITERATIONS : GOICP_RANSAC_POSE_MAX_POSES);
+				ok = end != ft_arg[q] && *end == '\0' && v >= 1 && v <= hi;
+				if (q == 1) fpfh_k = v;
+				else (q == 4 ? ransac_sel.iterations : ransac_sel.max_poses) = (int32_t)v;
+			}
+			if (!ok) {
+				std::fprintf(stderr, "error: %s got a value out of range: '%s'\n", ft_names[q], ft_arg[q]);
+				return 2;
+			}
+		}
+		if (feature_init && !ft_arg[3]) {
+			if (!ft_arg[0]) {
+				std::fprintf(stderr, "error: --feature-init needs --ransac-distance D or --feature-voxel V (D = 1.5 V)\n");
+				return 2;
+			}
+			ransac_sel.distance = 1.5f * feature_voxel;
+		}
+		if (feature_init && (normal_k < 3 || normal_k > GOICP_KNN_SELF_MAX)) {
+			std::fprintf(stderr, "error: --feature-init needs --normal-k in 3..%d\n", GOICP_KNN_SELF_MAX);
+			return 2;
+		}
+		if (feature_init && (ranks > 1 || list_arg)) {
+			std::fprintf(stderr, "error: --feature-init cannot be combined with --ranks or --source-list\n");
+			return 2;
 		}
 	}
 	for (int k = 0; k < 2; k++) {
@@ -670,6 +741,11 @@ int main(int argc, char** argv)
 	}
 	try {
 		Config config(argv[1]);
+		// refused before any device is touched: the result files report the engine's own search and ICP state, which a run from a feature pose
+		// does not set, and modes 3/4 search globally and take no start pose
+		if (feature_init && config.mode > 2) throw std::runtime_error("--feature-init starts the ICP of modes 0..2; modes 3/4 search globally and take no start pose");
+		if (feature_init && (!config.io.output.empty() || !config.io.visualization.empty()))
+			throw std::runtime_error("--feature-init cannot be combined with [io] output or visualization: the pose is printed, not written");
 		std::vector<P3> source, target;
 		load_cloud(resolve(config.io.source, argv[1]), config.subsample, config.resize, source, seed);
 		load_cloud(resolve(config.io.target, argv[1]), config.subsample, config.resize, target, seed);
@@ -773,14 +849,53 @@ int main(int argc, char** argv)
 		std::mutex mtx;
 		icp::FastGoICP engine(target, source, config.mse_threshold, mtx, &p);
 		goicp_handle h = engine.registration.handle();
-		if (plane || normal_k != 16) engine.registration.set_icp_options(plane, normal_k);
+		if (plane || (normal_k != 16 && !feature_init)) engine.registration.set_icp_options(plane, normal_k);   // with --feature-init alone --normal-k is the features' k
 		if (symmetric) engine.registration.set_icp_symmetric(true, source_normal_k);
 		if (generalized) engine.registration.set_icp_generalized(true, gicp_epsilon, source_normal_k);
 		if (gate > 0.f) engine.registration.set_icp_gate(gate);
 		if (robust_kernel) engine.registration.set_icp_robust(robust_kernel, robust_scale);
 		if (trunc > 0.f) engine.registration.set_search_truncation(trunc);
 		goicp_result r;
-		if (config.mode <= 2) {
+		if (feature_init) {
+			// voxel grid -> normals -> FPFH -> matches -> correspondences -> RANSAC poses, on the device through the engine's handle
+			std::vector<P3> cloud[2] = {source, target};
+			std::vector<float> feature[2];
+			for (int c = 0; c < 2; c++) {
+				if (feature_voxel > 0.f) {
+					std::vector<P3> cells(cloud[c].size());
+					size_t m = 0;
+					check(goicp_voxel_downsample(h, &cloud[c][0].x, cloud[c].size(), feature_voxel, &cells[0].x, nullptr, &m));
+					cells.resize(m);
+					cloud[c].swap(cells);
+				}
+				const size_t n = cloud[c].size();
+				std::vector<float> normals(3 * n);
+				feature[c].resize(n * (size_t)GOICP_FPFH_DIM);
+				check(goicp_estimate_normals(h, &cloud[c][0].x, n, (int32_t)normal_k, nullptr, normals.data(), nullptr, nullptr));
+				check(goicp_fpfh(h, &cloud[c][0].x, normals.data(), n, (int32_t)fpfh_k, feature[c].data(), nullptr));
+			}
+			const size_t nq = cloud[0].size(), nt = cloud[1].size();
+			std::vector<int32_t> index(nq), corr(2 * nq);
+			std::vector<float> d2(nq), second(nq);
+			std::vector<uint8_t> mutual(nq);
+			check(goicp_match_features(h, feature[0].data(), nq, feature[1].data(), nt, index.data(), d2.data(), second.data(), mutual.data()));
+			size_t M = 0, found = 0;
+			check(goicp_select_matches(index.data(), d2.data(), second.data(), mutual.data(), nq, match_ratio, 1, corr.data(), &M));
+			std::vector<goicp_ransac_pose_result> poses(GOICP_RANSAC_POSE_MAX_POSES);
+			if (M >= 3) check(goicp_ransac_pose(h, &cloud[0][0].x, nq, &cloud[1][0].x, nt, corr.data(), M, &ransac_sel, poses.data(), &found, nullptr));
+			std::printf("feature init: %zu x %zu points, fpfh k %ld, normal k %d, ratio %g: %zu correspondences; ransac distance %g iterations %d: %zu poses", nq, nt,
+			            fpfh_k, normal_k, match_ratio, M, ransac_sel.distance, (int)(ransac_sel.iterations ? ransac_sel.iterations : 100000), found);
+			if (found) std::printf(", the best with %d inliers%s\n", (int)poses[0].inliers, poses[0].refined ? " (refit)" : "");
+			else std::printf("\n");
+			if (!found) throw std::runtime_error("--feature-init: the feature matches support no pose");
+			float err = 0.f;
+			int32_t done = 0;
+			check(goicp_icp_run(h, poses[0].R, poses[0].t, iters, 0.f, &err, &done));
+			check(goicp_poll(h, &r));
+			std::memcpy(r.curR, poses[0].R, sizeof(r.curR)); std::memcpy(r.curT, poses[0].t, sizeof(r.curT));
+			r.best_sse = err;
+			std::printf("ICP from the feature pose after %d iterations: SSE %.7g\n", (int)done, err);
+		} else if (config.mode <= 2) {
 			for (int i = 0; i < iters; i++) check(goicp_icp_step(h));
 			check(goicp_poll(h, &r));
 			std::printf("ICP after %d iterations: SSE %.7g\n", iters, r.best_sse);

@@ -852,6 +852,133 @@ bool plane_refit(const unsigned long long words[kPlaneWords], const float mn[3],
 hipError_t launch_segment_plane(const float* d_xyz, int n, const PlaneSelect& s, int32_t* d_label, float* d_out, int32_t* d_index, PlaneRecord* planes,
                                 int* n_planes, int* m, hipStream_t stream, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 
+// ---- RANSAC pose estimation from correspondences (kdbuild.hip; goicp_ransac_pose_host is the host twin) ----
+// What include/goicp_mi355.h defines per hypothesis and per pair, one text for the host path (kdtree.cpp), the kernels and the refit's host
+// finish: plane's draw, the edge-length pre-rejection and the rotation of a cross-covariance (fp64, every operation rounded once, pca's
+// + - * / sqrt and its Jacobi), and the float pair.
+constexpr int kRansacPoseMaxIterations = 1 << 20, kRansacPoseMaxPoses = 64, kRansacPoseDefaultIterations = 100000;
+constexpr int kRansacPoseWords = 25;   // the refit's integer moments: m, Ss_0..2, St_0..2, the high words of the nine P_ab (3 a + b), their low words
+constexpr int kRpBlock = 256;          // threads of a score workgroup: 4 waves
+constexpr int kRpPts = 4;              // correspondences a lane keeps in registers: 1 024 per workgroup
+constexpr int kRpTile = 256;           // hypotheses of a workgroup's LDS tile (12 KB of poses + 1 KB of counts)
+// goicp_ransac_pose_select with the defaults filled in (iterations and max_poses >= 1)
+struct RansacPoseSelect {
+	float distance = 0.f;
+	int32_t iterations = 0, refine = 0, max_poses = 0, min_inliers = 0;
+	float edge_similarity = 0.f;
+	uint64_t seed = 0;
+};
+struct RansacPoseRecord {                                      // goicp_ransac_pose, field for field
+	float R[9], t[3];
+	int32_t inliers, hypothesis, refined;
+};
+// the frame of one side of the correspondences (the voxel operator's: mn_k, E = max (x_k - mn_k) in float, E < 2^e by frexp)
+struct RansacPoseFrame {
+	float mn[3];
+	int e;
+};
+namespace pose {
+using pca::add; using pca::sub; using pca::mul; using pca::div; using pca::root;
+using fpfh::dot3;
+GOICP_HD inline double len2_of_edge(const float* p, const float* q)
+{
+	const double d0 = sub((double)q[0], (double)p[0]), d1 = sub((double)q[1], (double)p[1]), d2 = sub((double)q[2], (double)p[2]);
+	return dot3(d0, d1, d2, d0, d1, d2);
+}
+// the pre-rejection of one edge: min(ls2, lt2) >= ss * max(ls2, lt2), ss = sigma * sigma in fp64
+GOICP_HD inline bool edge_ok(const float* sp, const float* sq, const float* tp, const float* tq, double ss)
+{
+	const double ls2 = len2_of_edge(sp, sq), lt2 = len2_of_edge(tp, tq);
+	const double lo = ls2 < lt2 ? ls2 : lt2, hi = ls2 < lt2 ? lt2 : ls2;
+	return lo >= mul(ss, hi);
+}
+GOICP_HD inline bool triple_ok(const float* sa, const float* sb, const float* sc, const float* ta, const float* tb, const float* tc, float sigma)
+{
+	const double ss = mul((double)sigma, (double)sigma);
+	return edge_ok(sa, sb, ta, tb, ss) && edge_ok(sb, sc, tb, tc, ss) && edge_ok(sc, sa, tc, ta, ss);
+}
+// swap the pair (l, column) i, j of the eigen-decomposition when l_j > l_i (selects on values: an index into V would put it into scratch)
+#define GOICP_POSE_ORDER(li, lj, xi, yi, zi, xj, yj, zj) \
+	do { \
+		const bool sw = lj > li; \
+		const double tl = sw ? lj : li, tx = sw ? xj : xi, ty = sw ? yj : yi, tz = sw ? zj : zi; \
+		lj = sw ? li : lj; xj = sw ? xi : xj; yj = sw ? yi : yj; zj = sw ? zi : zj; \
+		li = tl; xi = tx; yi = ty; zi = tz; \
+	} while (0)
+// The rotation and translation that take the source onto the target in the least-squares sense from the cross-covariance
+// H_ab = sum (m_a - ct_a)(s_b - cs_b) (target rows, source columns; any positive scale) and the centroids cs, ct.  false: degenerate (R, t
+// are then not to be used)
+GOICP_HD inline bool from_cross_covariance(const double H[3][3], const double cs[3], const double ct[3], float R[9], float t[3])
+{
+	double A[3][3], V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+	for (int a = 0; a < 3; a++)
+		for (int b = 0; b < 3; b++) A[a][b] = dot3(H[0][a], H[1][a], H[2][a], H[0][b], H[1][b], H[2][b]);
+	for (int sweep = 0; sweep < pca::kMaxSweeps; sweep++) {
+		const bool r01 = pca::rotate<0, 1>(A, V), r02 = pca::rotate<0, 2>(A, V), r12 = pca::rotate<1, 2>(A, V);
+		if (!(r01 || r02 || r12)) break;
+	}
+	// descending l, the lower index first on equal values: the three adjacent exchanges of a stable sort
+	double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+	double x0 = V[0][0], y0 = V[1][0], z0 = V[2][0], x1 = V[0][1], y1 = V[1][1], z1 = V[2][1], x2 = V[0][2], y2 = V[1][2], z2 = V[2][2];
+	GOICP_POSE_ORDER(l0, l1, x0, y0, z0, x1, y1, z1);
+	GOICP_POSE_ORDER(l1, l2, x1, y1, z1, x2, y2, z2);
+	GOICP_POSE_ORDER(l0, l1, x0, y0, z0, x1, y1, z1);
+	if (!(l1 > 0.0)) return false;                               // rank below 2: collinear or coincident points
+	double u0[3], u1[3];
+	for (int a = 0; a < 3; a++) { u0[a] = dot3(H[a][0], H[a][1], H[a][2], x0, y0, z0); u1[a] = dot3(H[a][0], H[a][1], H[a][2], x1, y1, z1); }
+	const double n0 = root(dot3(u0[0], u0[1], u0[2], u0[0], u0[1], u0[2])), n1 = root(dot3(u1[0], u1[1], u1[2], u1[0], u1[1], u1[2]));
+	for (int a = 0; a < 3; a++) { u0[a] = div(u0[a], n0); u1[a] = div(u1[a], n1); }
+	const double d = dot3(u0[0], u0[1], u0[2], u1[0], u1[1], u1[2]);
+	for (int a = 0; a < 3; a++) u1[a] = sub(u1[a], mul(d, u0[a]));
+	const double n2 = root(dot3(u1[0], u1[1], u1[2], u1[0], u1[1], u1[2]));
+	for (int a = 0; a < 3; a++) u1[a] = div(u1[a], n2);
+	const double u2[3] = {sub(mul(u0[1], u1[2]), mul(u0[2], u1[1])), sub(mul(u0[2], u1[0]), mul(u0[0], u1[2])), sub(mul(u0[0], u1[1]), mul(u0[1], u1[0]))};
+	const double v0[3] = {x0, y0, z0}, v1[3] = {x1, y1, z1};
+	const double v2[3] = {sub(mul(y0, z1), mul(z0, y1)), sub(mul(z0, x1), mul(x0, z1)), sub(mul(x0, y1), mul(y0, x1))};
+	bool ok = true;
+	for (int a = 0; a < 3; a++) {
+		for (int b = 0; b < 3; b++) R[3 * a + b] = (float)add(add(mul(u0[a], v0[b]), mul(u1[a], v1[b])), mul(u2[a], v2[b]));
+		t[a] = (float)sub(ct[a], dot3((double)R[3 * a], (double)R[3 * a + 1], (double)R[3 * a + 2], cs[0], cs[1], cs[2]));
+		ok = ok && plane::finite3(R + 3 * a) && t[a] - t[a] == 0.f;
+	}
+	return ok;
+}
+#undef GOICP_POSE_ORDER
+// the pose of three correspondences (source points sa, sb, sc onto target points ta, tb, tc); false: degenerate
+GOICP_HD inline bool of_triple(const float* sa, const float* sb, const float* sc, const float* ta, const float* tb, const float* tc, float R[9], float t[3])
+{
+	double cs[3], ct[3], H[3][3];
+	for (int k = 0; k < 3; k++) {
+		cs[k] = div(add(add((double)sa[k], (double)sb[k]), (double)sc[k]), 3.0);
+		ct[k] = div(add(add((double)ta[k], (double)tb[k]), (double)tc[k]), 3.0);
+	}
+	for (int a = 0; a < 3; a++)
+		for (int b = 0; b < 3; b++)
+			H[a][b] = add(add(mul(sub((double)ta[a], ct[a]), sub((double)sa[b], cs[b])), mul(sub((double)tb[a], ct[a]), sub((double)sb[b], cs[b]))),
+			              mul(sub((double)tc[a], ct[a]), sub((double)sc[b], cs[b])));
+	return from_cross_covariance(H, cs, ct, R, t);
+}
+// the pair: does the pose take the source point within sqrt(d2max) of the target point?  Float, left to right; a NaN compares false
+// one axis of it: row (r0, r1, r2 | t) of the pose
+GOICP_HD inline float residual(float r0, float r1, float r2, float t, float x0, float x1, float x2, float m) { return (((r0 * x0 + r1 * x1) + r2 * x2) + t) - m; }
+GOICP_HD inline bool within(float e0, float e1, float e2, float d2max) { return (e0 * e0 + e1 * e1) + e2 * e2 <= d2max; }
+GOICP_HD inline bool inlier(const float R[9], const float t[3], float x0, float x1, float x2, float m0, float m1, float m2, float d2max)
+{
+	return within(residual(R[0], R[1], R[2], t[0], x0, x1, x2, m0), residual(R[3], R[4], R[5], t[1], x0, x1, x2, m1),
+	              residual(R[6], R[7], R[8], t[2], x0, x1, x2, m2), d2max);
+}
+}  // namespace pose
+// The refit's host finish, which both paths call on the 25 integer words (kdtree.cpp): the cross-covariance from exact 128-bit integers, the
+// centroids as the voxel operator forms them (kept in fp64), pose::from_cross_covariance.  false: no usable pose (the refit then does not stand)
+bool ransac_pose_refit(const unsigned long long words[kRansacPoseWords], const RansacPoseFrame& fs, const RansacPoseFrame& ft, float R[9], float t[3]);
+// d_src / d_tgt: the two clouds on the device, d_corr: M x 2 ints (source, target), every index in range; s: the resolved selection; fs / ft:
+// the frames of the two sides (ransac_pose_frames, kdtree.cpp; read only with s.refine).  poses: room for s.max_poses records on the host,
+// *n_poses of them are written; d_inlier (may be null): M bytes, the pair's verdict under pose 0, zeros without one.  8 + 48 bytes per
+// returned pose and, with refine, 200 more come back.  Returns after the stream has drained
+hipError_t launch_ransac_pose(const float* d_src, const float* d_tgt, const int32_t* d_corr, int M, const RansacPoseSelect& s, const RansacPoseFrame& fs,
+                              const RansacPoseFrame& ft, RansacPoseRecord* poses, int* n_poses, unsigned char* d_inlier, hipStream_t stream,
+                              hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+
 // per-axis minimum and maximum of n points on the device (one rocPRIM reduction, 24 bytes come back): the frame of a cloud that a device
 // stage produced and the host has not seen.  Returns after the stream has drained
 hipError_t launch_cloud_minmax(const float* d_xyz, int n, float mn[3], float mx[3], hipStream_t stream);

@@ -1022,6 +1022,36 @@ void Engine::plane_filter(const float* xyz, size_t n, const PlaneSelect& s, floa
 	}
 }
 
+void Engine::ransac_pose(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M, const RansacPoseSelect& s,
+                         RansacPoseRecord* out_poses, size_t* n_poses, uint8_t* out_inlier)
+{
+	if (!out_poses || !n_poses) throw std::invalid_argument("goicp_ransac_pose: out_poses and n_poses must be non-null");
+	ransac_pose_check_input(src, n_s, tgt, n_t, corr, M);
+	if (registering_.load()) throw std::invalid_argument("goicp_ransac_pose: not while a registration runs");
+	RansacPoseFrame fs = {}, ft = {};
+	if (s.refine) {
+		ransac_pose_frame(src, corr, M, 0, &fs);
+		ransac_pose_frame(tgt, corr, M, 1, &ft);
+	}
+	DeviceGuard guard(dev_);
+	Buf<float> d_src = upload_cloud(src, n_s, stream_), d_tgt = upload_cloud(tgt, n_t, stream_);
+	Buf<int32_t> d_corr(2 * M);
+	Buf<unsigned char> d_inlier(out_inlier ? M : 0);
+	HIPCHK(hipMemcpyAsync(d_corr, corr, sizeof(int32_t) * 2 * M, hipMemcpyHostToDevice, stream_));
+	RansacPoseRecord poses[kRansacPoseMaxPoses];
+	int c = 0;
+	HIPCHK(launch_ransac_pose(d_src, d_tgt, d_corr, (int)M, s, fs, ft, poses, &c, out_inlier ? d_inlier.get() : nullptr, stream_, ev0_, ev1_));
+	if (out_inlier) HIPCHK(hipMemcpyAsync(out_inlier, d_inlier, M, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	for (int p = 0; p < c; p++) out_poses[p] = poses[p];
+	*n_poses = (size_t)c;
+	if (p_.verbose) {
+		float ms = 0.f;
+		HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+		std::fprintf(stderr, "[goicp] ransac_pose: %zu correspondences, %d hypotheses, %d poses, device %.3f ms\n", M, s.iterations, c, ms);
+	}
+}
+
 void Engine::set_source_staged(const char* fn, const float* xyz, size_t n, const SourceStages& st, size_t* n_kept)
 {
 	const std::string who(fn);

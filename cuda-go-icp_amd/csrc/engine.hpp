@@ -367,6 +367,10 @@ public:
 	// runs on the host over 16 integer words); the engine lends its device and stream and nothing else.  s: the checked selection
 	void segment_plane(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, PlaneRecord* out_planes, size_t* n_planes);
 	void plane_filter(const float* xyz, size_t n, const PlaneSelect& s, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes, size_t* n_planes, size_t* m);
+	// goicp_ransac_pose: RANSAC pose estimation from correspondences on the device (kdbuild.hip launch_ransac_pose; the refit's finish runs on
+	// the host over 25 integer words per pose); the engine lends its device and stream and nothing else.  s: the checked selection
+	void ransac_pose(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M, const RansacPoseSelect& s,
+	                 RansacPoseRecord* out_poses, size_t* n_poses, uint8_t* out_inlier);
 
 private:
 	Engine(const Params& p, size_t M, size_t N);     // the members' defaults; the public constructor delegates to it and runs init
@@ -672,6 +676,18 @@ void plane_check_cloud(const float* xyz, size_t n);
 PlaneSelect plane_check_select(float distance, int32_t iterations, int32_t refine, int32_t max_planes, int32_t min_inliers, uint64_t seed);
 void segment_plane_host(const float* xyz, size_t n, const PlaneSelect& s, int32_t* out_label, float* out_xyz, int32_t* out_index, PlaneRecord* out_planes,
                         size_t* n_planes, size_t* m);
+// RANSAC pose estimation from correspondences (kdtree.cpp).  ransac_pose_check_select / ransac_pose_check_input refuse what
+// goicp_ransac_pose refuses of the parameters (and return them with the defaults filled in) and of the clouds and correspondences;
+// ransac_pose_frame is the refit's frame of one side (0 source, 1 target); ransac_pose_host is goicp_ransac_pose_host (out_inlier may be
+// null) and select_matches_host goicp_select_matches
+RansacPoseSelect ransac_pose_check_select(float distance, int32_t iterations, int32_t refine, int32_t max_poses, int32_t min_inliers, float edge_similarity,
+                                          uint64_t seed);
+void ransac_pose_check_input(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M);
+void ransac_pose_frame(const float* xyz, const int32_t* corr, size_t M, int side, RansacPoseFrame* f);
+void ransac_pose_host(const float* src, const float* tgt, const int32_t* corr, size_t M, const RansacPoseSelect& s, RansacPoseRecord* out_poses, size_t* n_poses,
+                      uint8_t* out_inlier);
+void select_matches_host(const int32_t* index, const float* d2, const float* d2_second, const uint8_t* mutual, size_t n_q, float ratio, int32_t require_mutual,
+                         int32_t* out_corr, size_t* M);
 void cluster_frame(const float* xyz, size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void cluster_frame_of_box(const float mn[3], const float mx[3], size_t n, float radius, int32_t min_neighbors, VoxelFrame* f);
 void cluster_check_select(int32_t min_size, int32_t max_clusters);

@@ -475,6 +475,53 @@ int goicp_match_features(goicp_handle h, const float* query, size_t n_q, const f
 
 int goicp_match_features_tile(void) { return goicp::kMatchTile; }
 
+void goicp_ransac_pose_select_default(goicp_ransac_pose_select* out)
+{
+	if (!out) return;
+	out->distance = 0.f;
+	out->iterations = 0;
+	out->refine = 1;
+	out->max_poses = 0;
+	out->min_inliers = 0;
+	out->edge_similarity = 0.9f;
+	out->seed = 0;
+}
+
+static_assert(sizeof(goicp_ransac_pose_result) == sizeof(goicp::RansacPoseRecord) && sizeof(goicp_ransac_pose_result) == 60, "goicp_ransac_pose_result is RansacPoseRecord, field for field");
+static goicp::RansacPoseRecord* records(goicp_ransac_pose_result* p) { return reinterpret_cast<goicp::RansacPoseRecord*>(p); }
+static goicp::RansacPoseSelect checked(const goicp_ransac_pose_select& s)
+{
+	return goicp::ransac_pose_check_select(s.distance, s.iterations, s.refine, s.max_poses, s.min_inliers, s.edge_similarity, s.seed);
+}
+
+int goicp_ransac_pose_host(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M, const goicp_ransac_pose_select* sel,
+                           goicp_ransac_pose_result* out_poses, size_t* n_poses, uint8_t* out_inlier)
+{
+	REQUIRE(src && tgt && corr && sel && out_poses && n_poses);
+	return guarded([&] {
+		const goicp::RansacPoseSelect s = checked(*sel);
+		goicp::ransac_pose_check_input(src, n_s, tgt, n_t, corr, M);
+		goicp::ransac_pose_host(src, tgt, corr, M, s, records(out_poses), n_poses, out_inlier);
+	});
+}
+
+int goicp_ransac_pose(goicp_handle h, const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M,
+                      const goicp_ransac_pose_select* sel, goicp_ransac_pose_result* out_poses, size_t* n_poses, uint8_t* out_inlier)
+{
+	REQUIRE(h && src && tgt && corr && sel && out_poses && n_poses);
+	return guarded([&] { h->e->ransac_pose(src, n_s, tgt, n_t, corr, M, checked(*sel), records(out_poses), n_poses, out_inlier); });
+}
+
+int goicp_select_matches(const int32_t* index, const float* d2, const float* d2_second, const uint8_t* mutual, size_t n_q, float ratio, int32_t require_mutual,
+                         int32_t* out_corr, size_t* M)
+{
+	REQUIRE(index && d2 && d2_second && out_corr && M);
+	return guarded([&] { goicp::select_matches_host(index, d2, d2_second, mutual, n_q, ratio, require_mutual, out_corr, M); });
+}
+
+int goicp_ransac_pose_tile(void) { return goicp::kRpTile; }
+int goicp_ransac_pose_block(void) { return goicp::kRpBlock * goicp::kRpPts; }
+
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers)
 {
 	REQUIRE(h);

@@ -1954,4 +1954,281 @@ hipError_t launch_segment_plane(const float* d_xyz, int n, const PlaneSelect& s,
 	return end_and_drain(ev_end, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// RANSAC pose estimation from correspondences on the device (host twin: ransac_pose_host, kdtree.cpp).  The gather kernel packs
+// the correspondences once; the hypothesis kernel (one thread per hypothesis: the draw, the pre-rejection and the fp64 pose, device.hpp's
+// text); the score kernel (all correspondences x all hypotheses, integer counts); the keys (count << 32) | ~t sorted descending by rocPRIM;
+// the first max_poses keys and their poses to the host; with refine the integer-moment kernel over (pose, correspondence), 200 bytes per
+// pose to the host, ransac_pose_refit there, the score kernel once more on the refit poses; the mask kernel for pose 0.
+// ------------------------------------------------------------------------------------------------
+static_assert(kRpTile == kRpBlock && kRpTile % 64 == 0, "one thread loads one hypothesis of the tile; a wave keeps 64 counts at a time");
+constexpr int kRpSpan = kRpBlock * kRpPts;                     // correspondences of a score workgroup
+
+// ps[j] = (source point of correspondence j, 0), pt[j] = (its target point, 0); a slot j >= M (the arrays are padded to whole spans) holds
+// NaN: never an inlier
+__global__ void rp_gather_kernel(const float* __restrict__ src, const float* __restrict__ tgt, const int32_t* __restrict__ corr, int M, int slots,
+                                 float4* __restrict__ ps, float4* __restrict__ pt)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= slots) return;
+	const float nan = __int_as_float(0x7fc00000);
+	float4 s = make_float4(nan, nan, nan, 0.f), m = s;
+	if (j < M) {
+		const size_t a = (size_t)corr[2 * (size_t)j], b = (size_t)corr[2 * (size_t)j + 1];
+		s = make_float4(src[3 * a], src[3 * a + 1], src[3 * a + 2], 0.f);
+		m = make_float4(tgt[3 * b], tgt[3 * b + 1], tgt[3 * b + 2], 0.f);
+	}
+	ps[j] = s;
+	pt[j] = m;
+}
+
+// hyp[3 t + a] = (R_a0, R_a1, R_a2, t_a) of hypothesis t; a rejected or degenerate hypothesis is NaN throughout, against which no pair is an
+// inlier: it scores 0
+__global__ void __launch_bounds__(256) rp_hyp_kernel(const float4* __restrict__ ps, const float4* __restrict__ pt, int M, unsigned long long seed, int T,
+                                                     float sigma, float4* __restrict__ hyp)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= T) return;
+	uint32_t a, b, c;
+	plane::draw(seed, (unsigned long long)t, (uint32_t)M, &a, &b, &c);
+	const float4 qa = ps[a], qb = ps[b], qc = ps[c], ma = pt[a], mb = pt[b], mc = pt[c];
+	const float sa[3] = {qa.x, qa.y, qa.z}, sb[3] = {qb.x, qb.y, qb.z}, sc[3] = {qc.x, qc.y, qc.z};
+	const float ta[3] = {ma.x, ma.y, ma.z}, tb[3] = {mb.x, mb.y, mb.z}, tc[3] = {mc.x, mc.y, mc.z};
+	float R[9], tr[3];
+	bool ok = sigma > 0.f ? pose::triple_ok(sa, sb, sc, ta, tb, tc, sigma) : true;
+	ok = ok && pose::of_triple(sa, sb, sc, ta, tb, tc, R, tr);
+	const float nan = __int_as_float(0x7fc00000);
+#pragma unroll
+	for (int r = 0; r < 3; r++)
+		hyp[3 * (size_t)t + r] = ok ? make_float4(R[3 * r], R[3 * r + 1], R[3 * r + 2], tr[r]) : make_float4(nan, nan, nan, nan);
+}
+
+// Workgroup (bx, by): the kRpSpan correspondences from bx * kRpSpan against the hypotheses by * kRpTile ...  A lane keeps kRpPts
+// correspondences in registers; the tile's poses sit in LDS and are read wave-uniformly as three 128-bit words; per hypothesis and
+// correspondence the float pair, a ballot and a popcount of its 64-bit mask.  The wave's count of hypothesis j0 + jj stays with lane jj, so
+// LDS sees one atomic per lane per 64 hypotheses, and global memory one atomic per hypothesis per workgroup (pl_score_kernel's shape)
+__global__ void __launch_bounds__(kRpBlock) rp_score_kernel(const float4* __restrict__ ps, const float4* __restrict__ pt, const float4* __restrict__ hyp, int T,
+                                                            float d2max, unsigned* __restrict__ counts)
+{
+	__shared__ float4 s_r0[kRpTile], s_r1[kRpTile], s_r2[kRpTile];
+	__shared__ unsigned s_cnt[kRpTile];
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int t0 = blockIdx.y * kRpTile;
+	const float nan = __int_as_float(0x7fc00000);
+	{
+		const int t = t0 + tid;
+		float4 r0 = make_float4(nan, nan, nan, nan), r1 = r0, r2 = r0;
+		if (t < T) { r0 = hyp[3 * (size_t)t]; r1 = hyp[3 * (size_t)t + 1]; r2 = hyp[3 * (size_t)t + 2]; }
+		s_r0[tid] = r0; s_r1[tid] = r1; s_r2[tid] = r2;
+		s_cnt[tid] = 0u;
+	}
+	float sx[kRpPts], sy[kRpPts], sz[kRpPts], mx[kRpPts], my[kRpPts], mz[kRpPts];
+	const size_t base = (size_t)blockIdx.x * (size_t)kRpSpan;    // the packed arrays hold whole spans: no slot is past their end
+#pragma unroll
+	for (int k = 0; k < kRpPts; k++) {
+		const float4 s = ps[base + (size_t)(k * kRpBlock + tid)], m = pt[base + (size_t)(k * kRpBlock + tid)];
+		sx[k] = s.x; sy[k] = s.y; sz[k] = s.z; mx[k] = m.x; my[k] = m.y; mz[k] = m.z;
+	}
+	__syncthreads();
+	const int live = min(kRpTile, T - t0);                      // the tile's hypotheses that exist
+	for (int j0 = 0; j0 < live; j0 += 64) {
+		unsigned mine = 0u;
+		const int jn = min(64, live - j0);                      // wave-uniform; a lane past it keeps 0 (the refit's re-score has few poses)
+		for (int jj = 0; jj < jn; jj++) {
+			const float4 r0 = s_r0[j0 + jj], r1 = s_r1[j0 + jj], r2 = s_r2[j0 + jj];
+			unsigned c = 0u;
+#pragma unroll
+			for (int k = 0; k < kRpPts; k++) {
+				const float e0 = pose::residual(r0.x, r0.y, r0.z, r0.w, sx[k], sy[k], sz[k], mx[k]);
+				const float e1 = pose::residual(r1.x, r1.y, r1.z, r1.w, sx[k], sy[k], sz[k], my[k]);
+				const float e2 = pose::residual(r2.x, r2.y, r2.z, r2.w, sx[k], sy[k], sz[k], mz[k]);
+				c += (unsigned)__popcll(__ballot(pose::within(e0, e1, e2, d2max)));
+			}
+			mine = lane == jj ? c : mine;
+		}
+		if (mine) atomicAdd(&s_cnt[j0 + lane], mine);
+	}
+	__syncthreads();
+	if (t0 + tid < T && s_cnt[tid]) atomicAdd(&counts[t0 + tid], s_cnt[tid]);
+}
+
+__global__ void rp_key_kernel(const unsigned* __restrict__ counts, int T, unsigned long long* __restrict__ keys)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t < T) keys[t] = ((unsigned long long)counts[t] << 32) | (unsigned long long)(~(unsigned)t);
+}
+
+// the poses of the K largest keys, in their order: out[3 i + r] = hyp[3 t_i + r]
+__global__ void rp_take_kernel(const unsigned long long* __restrict__ sorted, int K, int T, const float4* __restrict__ hyp, float4* __restrict__ out)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= 3 * K) return;
+	const unsigned t = ~(unsigned)(sorted[i / 3] & 0xffffffffull);
+	const float nan = __int_as_float(0x7fc00000);
+	out[i] = t < (unsigned)T ? hyp[3 * (size_t)t + (size_t)(i % 3)] : make_float4(nan, nan, nan, nan);
+}
+
+// the refit's 25 integer words of pose blockIdx.y over its inliers: one thread per correspondence, wave-level sums, then 64-bit atomics
+// (pl_moment_kernel's style).  q < 2^31 on both sides, so a product has 62 bits and every word of at most 2^28 correspondences stays below 2^60
+__global__ void __launch_bounds__(256) rp_moment_kernel(const float4* __restrict__ ps, const float4* __restrict__ pt, int M, const float4* __restrict__ poses,
+                                                        float d2max, float4 mns, float4 mnt, int shs, int sht, unsigned long long* __restrict__ words)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	const float4 r0 = poses[3 * blockIdx.y], r1 = poses[3 * blockIdx.y + 1], r2 = poses[3 * blockIdx.y + 2];
+	unsigned long long w[kRansacPoseWords];
+#pragma unroll
+	for (int k = 0; k < kRansacPoseWords; k++) w[k] = 0ull;
+	if (j < M) {
+		const float4 s = ps[j], m = pt[j];
+		const float e0 = pose::residual(r0.x, r0.y, r0.z, r0.w, s.x, s.y, s.z, m.x), e1 = pose::residual(r1.x, r1.y, r1.z, r1.w, s.x, s.y, s.z, m.y),
+		            e2 = pose::residual(r2.x, r2.y, r2.z, r2.w, s.x, s.y, s.z, m.z);
+		if (pose::within(e0, e1, e2, d2max)) {
+			const unsigned long long qs[3] = {(unsigned long long)llrint(ldexp((double)(s.x - mns.x), shs)), (unsigned long long)llrint(ldexp((double)(s.y - mns.y), shs)),
+			                                  (unsigned long long)llrint(ldexp((double)(s.z - mns.z), shs))};
+			const unsigned long long qt[3] = {(unsigned long long)llrint(ldexp((double)(m.x - mnt.x), sht)), (unsigned long long)llrint(ldexp((double)(m.y - mnt.y), sht)),
+			                                  (unsigned long long)llrint(ldexp((double)(m.z - mnt.z), sht))};
+			w[0] = 1ull;
+#pragma unroll
+			for (int a = 0; a < 3; a++) {
+				w[1 + a] = qs[a]; w[4 + a] = qt[a];
+#pragma unroll
+				for (int b = 0; b < 3; b++) {
+					const unsigned long long p = qt[a] * qs[b];
+					w[7 + 3 * a + b] = p >> 32; w[16 + 3 * a + b] = p & 0xffffffffull;
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < kRansacPoseWords; k++)
+		for (int off = 32; off; off >>= 1) w[k] += shfl_xor64(w[k], off);
+	if ((threadIdx.x & 63) == 0 && w[0]) {
+#pragma unroll
+		for (int k = 0; k < kRansacPoseWords; k++) atomicAdd(words + (size_t)blockIdx.y * kRansacPoseWords + k, w[k]);
+	}
+}
+
+// the pair's verdict of every correspondence under one pose
+__global__ void rp_mask_kernel(const float4* __restrict__ ps, const float4* __restrict__ pt, int M, float4 r0, float4 r1, float4 r2, float d2max,
+                               unsigned char* __restrict__ inlier)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= M) return;
+	const float4 s = ps[j], m = pt[j];
+	inlier[j] = pose::within(pose::residual(r0.x, r0.y, r0.z, r0.w, s.x, s.y, s.z, m.x), pose::residual(r1.x, r1.y, r1.z, r1.w, s.x, s.y, s.z, m.y),
+	                         pose::residual(r2.x, r2.y, r2.z, r2.w, s.x, s.y, s.z, m.z), d2max) ? 1 : 0;
+}
+
+hipError_t launch_ransac_pose(const float* d_src, const float* d_tgt, const int32_t* d_corr, int M, const RansacPoseSelect& s, const RansacPoseFrame& fs,
+                              const RansacPoseFrame& ft, RansacPoseRecord* poses, int* n_poses, unsigned char* d_inlier, hipStream_t stream,
+                              hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+	if (M < 3 || !d_src || !d_tgt || !d_corr || !poses || !n_poses) return hipErrorInvalidValue;
+	if (s.iterations < 1 || s.iterations > kRansacPoseMaxIterations || s.max_poses < 1 || s.max_poses > kRansacPoseMaxPoses) return hipErrorInvalidValue;
+	const int T = s.iterations, K = std::min(s.max_poses, T);
+	const int spans = (M + kRpSpan - 1) / kRpSpan, slots = spans * kRpSpan;
+	const float d2max = s.distance * s.distance;
+	float4 *ps = nullptr, *pt = nullptr, *hyp = nullptr, *top = nullptr;   // top: the K returned poses, then the K refit poses
+	unsigned* counts = nullptr;
+	unsigned long long *keys = nullptr, *sorted = nullptr, *words = nullptr;
+	void* tmp = nullptr;
+	size_t sort_bytes = 0;
+	Temps t;
+	KD_TRY(t.get(ps, (size_t)slots)); KD_TRY(t.get(pt, (size_t)slots));
+	KD_TRY(t.get(hyp, 3 * (size_t)T));
+	KD_TRY(t.get(top, 6 * (size_t)kRansacPoseMaxPoses));
+	KD_TRY(t.get(counts, (size_t)T));
+	KD_TRY(t.get(keys, (size_t)T)); KD_TRY(t.get(sorted, (size_t)T));
+	KD_TRY(t.get(words, (size_t)kRansacPoseMaxPoses * kRansacPoseWords));
+	KD_TRY(rocprim::radix_sort_keys_desc(nullptr, sort_bytes, keys, sorted, (size_t)T, 0, 64, stream));
+	KD_TRY(t.get_bytes(tmp, std::max<size_t>(sort_bytes, 16)));
+	if (ev_begin) KD_TRY(hipEventRecord(ev_begin, stream));
+	const dim3 blk(256);
+	auto score = [&](const float4* h, int count, unsigned* out) {
+		hipLaunchKernelGGL(rp_score_kernel, dim3((unsigned)spans, (unsigned)((count + kRpTile - 1) / kRpTile)), dim3(kRpBlock), 0, stream, ps, pt, h, count, d2max,
+		                   out);
+		return hipGetLastError();
+	};
+	hipLaunchKernelGGL(rp_gather_kernel, dim3((slots + 255) / 256), blk, 0, stream, d_src, d_tgt, d_corr, M, slots, ps, pt);
+	KD_TRY(hipGetLastError());
+	KD_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned) * (size_t)T, stream));
+	hipLaunchKernelGGL(rp_hyp_kernel, dim3((T + 255) / 256), blk, 0, stream, ps, pt, M, (unsigned long long)s.seed, T, s.edge_similarity, hyp);
+	KD_TRY(hipGetLastError());
+	KD_TRY(score(hyp, T, counts));
+	hipLaunchKernelGGL(rp_key_kernel, dim3((T + 255) / 256), blk, 0, stream, counts, T, keys);
+	KD_TRY(hipGetLastError());
+	KD_TRY(rocprim::radix_sort_keys_desc(tmp, sort_bytes, keys, sorted, (size_t)T, 0, 64, stream));
+	hipLaunchKernelGGL(rp_take_kernel, dim3((3 * K + 255) / 256), blk, 0, stream, sorted, K, T, hyp, top);
+	KD_TRY(hipGetLastError());
+	unsigned long long key[kRansacPoseMaxPoses];
+	float4 h[3 * kRansacPoseMaxPoses];
+	KD_TRY(hipMemcpyAsync(key, sorted, sizeof(unsigned long long) * (size_t)K, hipMemcpyDeviceToHost, stream));
+	KD_TRY(hipMemcpyAsync(h, top, sizeof(float4) * 3 * (size_t)K, hipMemcpyDeviceToHost, stream));
+	KD_TRY(hipStreamSynchronize(stream));
+	int found = 0;
+	const int floor_count = std::max(s.min_inliers, 3);
+	for (; found < K; found++) {
+		const long long cnt = (long long)(key[found] >> 32);
+		const unsigned best = ~(unsigned)(key[found] & 0xffffffffull);
+		if (best >= (unsigned)T || cnt > (long long)M) return hipErrorUnknown;
+		if (cnt < (long long)floor_count) break;
+		RansacPoseRecord& rec = poses[found];
+		for (int r = 0; r < 3; r++) {
+			const float4 row = h[3 * found + r];
+			rec.R[3 * r] = row.x; rec.R[3 * r + 1] = row.y; rec.R[3 * r + 2] = row.z; rec.t[r] = row.w;
+		}
+		rec.inliers = (int32_t)cnt;
+		rec.hypothesis = (int32_t)best;
+		rec.refined = 0;
+	}
+	if (s.refine && found > 0) {
+		KD_TRY(hipMemsetAsync(words, 0, sizeof(unsigned long long) * (size_t)found * kRansacPoseWords, stream));
+		hipLaunchKernelGGL(rp_moment_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)found), blk, 0, stream, ps, pt, M, top, d2max,
+		                   make_float4(fs.mn[0], fs.mn[1], fs.mn[2], 0.f), make_float4(ft.mn[0], ft.mn[1], ft.mn[2], 0.f), 31 - fs.e, 31 - ft.e, words);
+		KD_TRY(hipGetLastError());
+		unsigned long long w[kRansacPoseMaxPoses * kRansacPoseWords];
+		KD_TRY(hipMemcpyAsync(w, words, sizeof(unsigned long long) * (size_t)found * kRansacPoseWords, hipMemcpyDeviceToHost, stream));
+		KD_TRY(hipStreamSynchronize(stream));
+		const float nan = std::nanf("");
+		float4 r[3 * kRansacPoseMaxPoses];
+		for (int i = 0; i < found; i++) {
+			float R[9], tr[3];
+			const bool ok = ransac_pose_refit(w + (size_t)i * kRansacPoseWords, fs, ft, R, tr);
+			for (int a = 0; a < 3; a++) r[3 * i + a] = ok ? make_float4(R[3 * a], R[3 * a + 1], R[3 * a + 2], tr[a]) : make_float4(nan, nan, nan, nan);
+		}
+		// the refit poses are scored by the same kernel as `found` hypotheses; a refit that does not exist is NaN and counts 0
+		unsigned cnt[kRansacPoseMaxPoses];
+		float4* refit = top + 3 * (size_t)kRansacPoseMaxPoses;
+		KD_TRY(hipMemcpyAsync(refit, r, sizeof(float4) * 3 * (size_t)found, hipMemcpyHostToDevice, stream));
+		KD_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned) * (size_t)found, stream));
+		KD_TRY(score(refit, found, counts));
+		KD_TRY(hipMemcpyAsync(cnt, counts, sizeof(unsigned) * (size_t)found, hipMemcpyDeviceToHost, stream));
+		KD_TRY(hipStreamSynchronize(stream));
+		for (int i = 0; i < found; i++) {
+			if (cnt[i] > (unsigned)M) return hipErrorUnknown;
+			RansacPoseRecord& rec = poses[i];
+			if (r[3 * i].x == r[3 * i].x && (int32_t)cnt[i] >= rec.inliers) {
+				for (int a = 0; a < 3; a++) {
+					const float4 row = r[3 * i + a];
+					rec.R[3 * a] = row.x; rec.R[3 * a + 1] = row.y; rec.R[3 * a + 2] = row.z; rec.t[a] = row.w;
+				}
+				rec.inliers = (int32_t)cnt[i];
+				rec.refined = 1;
+			}
+		}
+	}
+	if (d_inlier) {
+		if (found > 0) {
+			const RansacPoseRecord& p = poses[0];
+			hipLaunchKernelGGL(rp_mask_kernel, dim3((M + 255) / 256), blk, 0, stream, ps, pt, M, make_float4(p.R[0], p.R[1], p.R[2], p.t[0]),
+			                   make_float4(p.R[3], p.R[4], p.R[5], p.t[1]), make_float4(p.R[6], p.R[7], p.R[8], p.t[2]), d2max, d_inlier);
+			KD_TRY(hipGetLastError());
+		} else {
+			KD_TRY(hipMemsetAsync(d_inlier, 0, (size_t)M, stream));
+		}
+	}
+	*n_poses = found;
+	return end_and_drain(ev_end, stream);
+}
+
 }  // namespace goicp

@@ -1238,4 +1238,193 @@ void segment_plane_host(const float* xyz, size_t n, const PlaneSelect& s, int32_
 	if (m_out) *m_out = map.size();
 }
 
+// ---- RANSAC pose estimation from correspondences: what both paths share, and the host path ----
+RansacPoseSelect ransac_pose_check_select(float distance, int32_t iterations, int32_t refine, int32_t max_poses, int32_t min_inliers, float edge_similarity,
+                                          uint64_t seed)
+{
+	if (!(distance > 0.f) || !std::isfinite(distance)) throw std::invalid_argument("goicp ransac_pose: the distance must be positive and finite");
+	if (iterations < 0 || iterations > kRansacPoseMaxIterations) throw std::invalid_argument("goicp ransac_pose: iterations must be in 0..1048576 (0 = 100000)");
+	if (refine < 0 || refine > 1) throw std::invalid_argument("goicp ransac_pose: refine must be 0 or 1");
+	if (max_poses < 0 || max_poses > kRansacPoseMaxPoses) throw std::invalid_argument("goicp ransac_pose: max_poses must be in 0..64 (0 = 1)");
+	if (min_inliers < 0) throw std::invalid_argument("goicp ransac_pose: min_inliers must not be negative");
+	if (!(edge_similarity >= 0.f && edge_similarity <= 1.f)) throw std::invalid_argument("goicp ransac_pose: edge_similarity must be 0 (off) or in (0, 1]");
+	RansacPoseSelect s;
+	s.distance = distance;
+	s.iterations = iterations ? iterations : kRansacPoseDefaultIterations;
+	s.refine = refine;
+	s.max_poses = max_poses ? max_poses : 1;
+	s.min_inliers = min_inliers;
+	s.edge_similarity = edge_similarity;
+	s.seed = seed;
+	return s;
+}
+
+void ransac_pose_check_input(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M)
+{
+	const size_t limit = (size_t)INT32_MAX / 8;
+	if (!src || !tgt || !corr) throw std::invalid_argument("goicp ransac_pose: src, tgt and corr must be non-null");
+	if (M < 3) throw std::invalid_argument("goicp ransac_pose: at least three correspondences are needed");
+	if (n_s == 0 || n_t == 0 || M > limit || n_s > limit || n_t > limit) throw std::invalid_argument("goicp ransac_pose: a cloud is empty, or a size is too large");
+	for (size_t j = 0; j < M; j++)
+		if (corr[2 * j] < 0 || (size_t)corr[2 * j] >= n_s || corr[2 * j + 1] < 0 || (size_t)corr[2 * j + 1] >= n_t)
+			throw std::invalid_argument("goicp ransac_pose: an index of corr is out of range");
+	for (size_t i = 0; i < 3 * n_s; i++)
+		if (!std::isfinite(src[i])) throw std::invalid_argument("goicp ransac_pose: non-finite coordinate in the source cloud");
+	for (size_t i = 0; i < 3 * n_t; i++)
+		if (!std::isfinite(tgt[i])) throw std::invalid_argument("goicp ransac_pose: non-finite coordinate in the target cloud");
+}
+
+// the voxel operator's frame over the points of one side that the correspondences name (side 0 source, 1 target)
+void ransac_pose_frame(const float* xyz, const int32_t* corr, size_t M, int side, RansacPoseFrame* f)
+{
+	float mn[3] = {INFINITY, INFINITY, INFINITY}, E = 0.f;
+	for (size_t j = 0; j < M; j++)
+		for (int k = 0; k < 3; k++) mn[k] = std::min(mn[k], xyz[3 * (size_t)corr[2 * j + side] + k]);
+	for (size_t j = 0; j < M; j++)
+		for (int k = 0; k < 3; k++) E = std::max(E, xyz[3 * (size_t)corr[2 * j + side] + k] - mn[k]);
+	for (int k = 0; k < 3; k++) f->mn[k] = mn[k];
+	f->e = 0;
+	std::frexp(E, &f->e);                                        // E < 2^e
+}
+
+bool ransac_pose_refit(const unsigned long long words[kRansacPoseWords], const RansacPoseFrame& fs, const RansacPoseFrame& ft, float R[9], float t[3])
+{
+	const int shs = 31 - fs.e, sht = 31 - ft.e;
+	const unsigned long long m = words[0];
+	if (m == 0) return false;
+	const double md = (double)m, mm = md * md;
+	// H_ab = (m P_ab - St_a Ss_b) 2^(-shs - sht) / m^2, the integer formed exactly and rounded once
+	double H[3][3], cs[3], ct[3];
+	for (int a = 0; a < 3; a++)
+		for (int b = 0; b < 3; b++) {
+			const __int128 P = (__int128)(((unsigned __int128)words[7 + 3 * a + b] << 32) + (unsigned __int128)words[16 + 3 * a + b]);
+			const __int128 v = (__int128)m * P - (__int128)words[4 + a] * (__int128)words[1 + b];
+			H[a][b] = std::ldexp((double)v, -shs - sht) / mm;
+		}
+	for (int k = 0; k < 3; k++) {
+		cs[k] = (double)fs.mn[k] + std::ldexp((double)words[1 + k] / md, -shs);
+		ct[k] = (double)ft.mn[k] + std::ldexp((double)words[4 + k] / md, -sht);
+	}
+	return pose::from_cross_covariance(H, cs, ct, R, t);
+}
+
+namespace {
+
+struct PosePair { float s[3], m[3]; };
+
+int32_t pose_count(const std::vector<PosePair>& pk, const float R[9], const float t[3], float d2max, uint8_t* mask)
+{
+	int32_t cnt = 0;
+	for (size_t j = 0; j < pk.size(); j++) {
+		const PosePair& p = pk[j];
+		const bool in = pose::inlier(R, t, p.s[0], p.s[1], p.s[2], p.m[0], p.m[1], p.m[2], d2max);
+		cnt += in ? 1 : 0;
+		if (mask) mask[j] = in ? 1 : 0;
+	}
+	return cnt;
+}
+
+bool pose_of_hypothesis(const std::vector<PosePair>& pk, const RansacPoseSelect& s, int t, float R[9], float tr[3])
+{
+	uint32_t a, b, c;
+	plane::draw(s.seed, (uint64_t)t, (uint32_t)pk.size(), &a, &b, &c);
+	const PosePair &pa = pk[a], &pb = pk[b], &pc = pk[c];
+	if (s.edge_similarity > 0.f && !pose::triple_ok(pa.s, pb.s, pc.s, pa.m, pb.m, pc.m, s.edge_similarity)) return false;
+	return pose::of_triple(pa.s, pb.s, pc.s, pa.m, pb.m, pc.m, R, tr);
+}
+
+}  // namespace
+
+// the header's definition on the host; threads over blocks of hypotheses (integer counts)
+void ransac_pose_host(const float* src, const float* tgt, const int32_t* corr, size_t M, const RansacPoseSelect& s, RansacPoseRecord* out_poses, size_t* n_poses,
+                      uint8_t* out_inlier)
+{
+	std::vector<PosePair> pk(M);
+	for (size_t j = 0; j < M; j++)
+		for (int k = 0; k < 3; k++) { pk[j].s[k] = src[3 * (size_t)corr[2 * j] + k]; pk[j].m[k] = tgt[3 * (size_t)corr[2 * j + 1] + k]; }
+	const int T = s.iterations;
+	const float d2max = s.distance * s.distance;
+	std::vector<uint64_t> keys((size_t)T);
+	const int chunk = 16, chunks = (T + chunk - 1) / chunk;
+	parallel_tasks((uint64_t)M * (uint64_t)T >= (1ull << 20) ? 8 : 1, chunks, [&](int ch) {
+		for (int t = ch * chunk; t < std::min(T, (ch + 1) * chunk); t++) {
+			float R[9], tr[3];
+			const int32_t cnt = pose_of_hypothesis(pk, s, t, R, tr) ? pose_count(pk, R, tr, d2max, nullptr) : 0;
+			keys[(size_t)t] = ((uint64_t)(uint32_t)cnt << 32) | (uint64_t)(~(uint32_t)t);
+		}
+	});
+	const size_t K = std::min<size_t>((size_t)s.max_poses, (size_t)T);
+	std::partial_sort(keys.begin(), keys.begin() + (std::ptrdiff_t)K, keys.end(), std::greater<uint64_t>());
+	size_t found = 0;
+	for (; found < K; found++) {
+		const int32_t cnt = (int32_t)(keys[found] >> 32);
+		if (cnt < std::max(s.min_inliers, 3)) break;
+		RansacPoseRecord& rec = out_poses[found];
+		rec.hypothesis = (int32_t)(~(uint32_t)(keys[found] & 0xffffffffull));
+		pose_of_hypothesis(pk, s, rec.hypothesis, rec.R, rec.t);
+		rec.inliers = cnt;
+		rec.refined = 0;
+	}
+	if (s.refine && found > 0) {
+		RansacPoseFrame fs, ft;
+		ransac_pose_frame(src, corr, M, 0, &fs);
+		ransac_pose_frame(tgt, corr, M, 1, &ft);
+		for (size_t i = 0; i < found; i++) {
+			RansacPoseRecord& rec = out_poses[i];
+			unsigned long long w[kRansacPoseWords] = {};
+			for (size_t j = 0; j < M; j++) {
+				const PosePair& p = pk[j];
+				if (!pose::inlier(rec.R, rec.t, p.s[0], p.s[1], p.s[2], p.m[0], p.m[1], p.m[2], d2max)) continue;
+				unsigned long long qs[3], qt[3];
+				for (int k = 0; k < 3; k++) {
+					qs[k] = (unsigned long long)std::llrint(std::ldexp((double)(p.s[k] - fs.mn[k]), 31 - fs.e));
+					qt[k] = (unsigned long long)std::llrint(std::ldexp((double)(p.m[k] - ft.mn[k]), 31 - ft.e));
+				}
+				w[0]++;
+				for (int a = 0; a < 3; a++) {
+					w[1 + a] += qs[a]; w[4 + a] += qt[a];
+					for (int b = 0; b < 3; b++) {
+						const unsigned long long prod = qt[a] * qs[b];
+						w[7 + 3 * a + b] += prod >> 32;
+						w[16 + 3 * a + b] += prod & 0xffffffffull;
+					}
+				}
+			}
+			float R[9], tr[3];
+			if (ransac_pose_refit(w, fs, ft, R, tr)) {
+				const int32_t cnt = pose_count(pk, R, tr, d2max, nullptr);
+				if (cnt >= rec.inliers) {
+					std::memcpy(rec.R, R, sizeof(R)); std::memcpy(rec.t, tr, sizeof(tr));
+					rec.inliers = cnt;
+					rec.refined = 1;
+				}
+			}
+		}
+	}
+	if (out_inlier) {
+		if (found > 0) pose_count(pk, out_poses[0].R, out_poses[0].t, d2max, out_inlier);
+		else std::memset(out_inlier, 0, M);
+	}
+	*n_poses = found;
+}
+
+void select_matches_host(const int32_t* index, const float* d2, const float* d2_second, const uint8_t* mutual, size_t n_q, float ratio, int32_t require_mutual,
+                         int32_t* out_corr, size_t* M)
+{
+	if (!index || !d2 || !d2_second || !out_corr || !M) throw std::invalid_argument("goicp_select_matches: index, d2, d2_second, out_corr and M must be non-null");
+	if (n_q == 0 || n_q > (size_t)INT32_MAX / 8) throw std::invalid_argument("goicp_select_matches: n_q must be in 1..goicp_create's limit");
+	if (!(ratio >= 0.f) || !std::isfinite(ratio)) throw std::invalid_argument("goicp_select_matches: the ratio must be 0 (no test) or positive and finite");
+	if (require_mutual < 0 || require_mutual > 1) throw std::invalid_argument("goicp_select_matches: require_mutual must be 0 or 1");
+	if (require_mutual && !mutual) throw std::invalid_argument("goicp_select_matches: require_mutual needs the mutual flags");
+	const float rr = ratio * ratio;
+	size_t m = 0;
+	for (size_t q = 0; q < n_q; q++) {
+		if (require_mutual && !mutual[q]) continue;
+		if (ratio != 0.f && !(d2[q] <= rr * d2_second[q])) continue;
+		out_corr[2 * m] = (int32_t)q; out_corr[2 * m + 1] = index[q];
+		m++;
+	}
+	*M = m;
+}
+
 }  // namespace goicp

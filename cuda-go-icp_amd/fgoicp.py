@@ -254,6 +254,75 @@ def plane_filter(xyz, distance, iterations=1000, refine=1, max_planes=1, min_inl
     return _plane_filter_call(B.load_library().goicp_plane_filter_host, xyz, _plane_select(distance, iterations, refine, max_planes, min_inliers, seed))
 
 
+# goicp_ransac_pose_result, field for field: the poses come back as a structured array
+RANSAC_POSE_DTYPE = np.dtype([("R", "<f4", (3, 3)), ("t", "<f4", (3,)), ("inliers", "<i4"), ("hypothesis", "<i4"), ("refined", "<i4")])
+
+
+def _select_matches_call(index, d2, d2_second, mutual, ratio, require_mutual):
+    index, d2, d2_second = np.ascontiguousarray(index, np.int32).reshape(-1), _f32(d2, (-1,)), _f32(d2_second, (-1,))
+    nq = len(index)
+    if len(d2) != nq or len(d2_second) != nq:
+        raise ValueError("select_matches: index, d2 and d2_second must have one entry per query")
+    mut = None if mutual is None else np.ascontiguousarray(mutual, np.uint8).reshape(-1)
+    if mut is not None and len(mut) != nq:
+        raise ValueError("select_matches: one mutual flag per query")
+    corr, m = np.empty((nq, 2), np.int32), C.c_size_t(0)
+    ip = C.POINTER(C.c_int32)
+    B.check(B.load_library().goicp_select_matches(index.ctypes.data_as(ip), _fptr(d2), _fptr(d2_second),
+                                                  None if mut is None else mut.ctypes.data_as(C.POINTER(C.c_uint8)), nq, float(ratio),
+                                                  int(bool(require_mutual) and mut is not None), corr.ctypes.data_as(ip), C.byref(m)))
+    return corr[:m.value].copy()
+
+
+def select_matches(index, d2, d2_second, mutual=None, ratio=0.0, require_mutual=True):
+    """goicp_select_matches (host only): match_features' output -> correspondences (M, 2) int32 (query, target), ascending in the query:
+    the queries whose match is mutual (require_mutual; mutual=None: no mutual test) and passes the ratio test d2 <= ratio^2 * d2_second
+    (ratio = 0: no ratio test)."""
+    return _select_matches_call(index, d2, d2_second, mutual, ratio, require_mutual)
+
+
+def _ransac_pose_select(distance, iterations, refine, max_poses, min_inliers, edge_similarity, seed):
+    return B.CRansacPoseSelect(float(distance), int(iterations), int(refine), int(max_poses), int(min_inliers), float(edge_similarity),
+                               int(seed) & (2 ** 64 - 1))
+
+
+def _ransac_pose_call(fn, src, tgt, corr, sel):
+    src, tgt = _f32(src, (-1, 3)), _f32(tgt, (-1, 3))
+    corr = np.ascontiguousarray(corr, np.int32).reshape(-1, 2)
+    M = len(corr)
+    poses, c, mask = np.zeros(B.RANSAC_POSE_MAX_POSES, RANSAC_POSE_DTYPE), C.c_size_t(0), np.zeros(M, np.uint8)
+    B.check(fn(_fptr(src), len(src), _fptr(tgt), len(tgt), corr.ctypes.data_as(C.POINTER(C.c_int32)), M, C.byref(sel),
+               poses.ctypes.data_as(C.POINTER(B.CRansacPose)), C.byref(c), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return poses[:c.value].copy(), mask
+
+
+def ransac_pose(src, tgt, corr, distance, iterations=100000, refine=1, max_poses=1, min_inliers=0, edge_similarity=0.9, seed=0):
+    """goicp_ransac_pose_host (host only): RANSAC over `iterations` three-correspondence hypotheses; a correspondence (source index, target
+    index) is an inlier of a pose when |R s + t - m| <= distance; the max_poses best-supported poses with at least max(min_inliers, 3)
+    inliers, each refit by least squares over its inliers with refine = 1 -> (poses (c,) RANSAC_POSE_DTYPE: R, t, inliers, hypothesis,
+    refined; the inlier mask (M,) uint8 of pose 0).  Registration.ransac_pose gives the same bits on the device."""
+    return _ransac_pose_call(B.load_library().goicp_ransac_pose_host, src, tgt, corr,
+                             _ransac_pose_select(distance, iterations, refine, max_poses, min_inliers, edge_similarity, seed))
+
+
+def feature_poses(src, tgt, voxel, k, distance, normal_k=16, viewpoint_src=None, viewpoint_tgt=None, ratio=0.0, require_mutual=True, ops=None, **ransac):
+    """voxel_downsample -> estimate_normals -> fpfh -> match_features -> select_matches -> ransac_pose on the host functions (ops: an object
+    with the same six methods, a Registration for the device) -> (poses, a dict of the intermediate results: the two downsampled clouds
+    'src' / 'tgt', 'corr' and the inlier mask 'inlier').  The poses take the downsampled source onto the downsampled target.  voxel = 0 or
+    None: no voxel stage, the clouds as they are."""
+    import sys
+    o = ops if ops is not None else sys.modules[__name__]
+    ds, dt = (o.voxel_downsample(src, voxel)[0], o.voxel_downsample(tgt, voxel)[0]) if voxel else (_f32(src, (-1, 3)), _f32(tgt, (-1, 3)))
+    ns, nt = o.estimate_normals(ds, normal_k, viewpoint_src)[0], o.estimate_normals(dt, normal_k, viewpoint_tgt)[0]
+    fs, ft = o.fpfh(ds, k, normals=ns)[0], o.fpfh(dt, k, normals=nt)[0]
+    idx, d2, second, mut = o.match_features(fs, ft, mutual=True)
+    corr = select_matches(idx, d2, second, mut, ratio, require_mutual)
+    if len(corr) < 3:
+        return np.zeros(0, RANSAC_POSE_DTYPE), {"src": ds, "tgt": dt, "corr": corr, "inlier": np.zeros(len(corr), np.uint8)}
+    poses, mask = o.ransac_pose(ds, dt, corr, distance, **ransac)
+    return poses, {"src": ds, "tgt": dt, "corr": corr, "inlier": mask}
+
+
 def _filter_host(pcs, voxel, radius, min_neighbors, stat_neighbors=None, std_ratio=None, cluster=None, plane=None):
     """the composition of the host functions that goicp_set_source_filtered, goicp_set_source_pipeline, goicp_set_source_clustered and
     goicp_set_source_segmented equal"""
@@ -591,6 +660,30 @@ class Registration:
         """goicp_match_features: the module-level match_features on the device (the handle lends its device and stream, its state is
         untouched)"""
         return _match_call(lambda *a: self._lib.goicp_match_features(self.handle, *a), fq, ft, mutual)
+
+    def ransac_pose(self, src, tgt, corr, distance, iterations=100000, refine=1, max_poses=1, min_inliers=0, edge_similarity=0.9, seed=0):
+        """goicp_ransac_pose: the module-level ransac_pose on the device (the handle lends its device and stream, its state is untouched)
+        -> (poses (c,) RANSAC_POSE_DTYPE, inlier mask (M,) uint8), the same bits"""
+        return _ransac_pose_call(lambda *a: self._lib.goicp_ransac_pose(self.handle, *a), src, tgt, corr,
+                                 _ransac_pose_select(distance, iterations, refine, max_poses, min_inliers, edge_similarity, seed))
+
+    def feature_poses(self, src, tgt, voxel, k, distance, normal_k=16, viewpoint_src=None, viewpoint_tgt=None, ratio=0.0, require_mutual=True, **ransac):
+        """the module-level feature_poses with every stage on the device through this handle (select_matches, linear in the number of
+        points, stays on the host) -> (poses, intermediates), the same bits"""
+        return feature_poses(src, tgt, voxel, k, distance, normal_k, viewpoint_src, viewpoint_tgt, ratio, require_mutual, ops=self, **ransac)
+
+    def register_features(self, voxel, k, distance, max_iter=10000, err_diff=1e-7, **kw):
+        """feature_poses of this handle's own clouds (source onto target; max_poses defaults to 8) as the start poses of icp_run_batch ->
+        (R (3, 3), t (3,), err of the candidate with the smallest final error -- the first of equals -- and a dict: 'poses' the start poses,
+        'inliers' their counts, 'R' / 't' / 'err' / 'iters' of every candidate after ICP, 'best' the winner's index).  Without a feature
+        pose it raises a GoicpError."""
+        kw.setdefault("max_poses", 8)
+        poses, _ = self.feature_poses(self.pcs, self.pct, voxel, k, distance, **kw)
+        if len(poses) == 0:
+            raise B.GoicpError(-1, "register_features: the feature matches support no pose")
+        R, t, err, it = self.icp_run_batch(poses["R"], poses["t"], max_iter, err_diff)
+        best = int(np.argmin(err))
+        return R[best], t[best], err[best], {"poses": poses, "inliers": poses["inliers"].copy(), "R": R, "t": t, "err": err, "iters": it, "best": best}
 
     def debug_source_order(self, xyz, mode=2):
         """goicp_debug_source_order (test): the device ordering alone; equals source_order(xyz, mode)"""

@@ -567,6 +567,91 @@ int goicp_plane_filter(goicp_handle h, const float* xyz, size_t n, const goicp_p
                        size_t* n_planes, size_t* m);
 int goicp_set_source_segmented(goicp_handle h, const float* xyz, size_t n, const goicp_source_pipeline* p, const goicp_plane_select* pl,
                                const goicp_cluster_select* s, size_t* n_kept);
+/*
+ * RANSAC pose estimation from correspondences (PCL's SampleConsensusPrerejective, Open3D's registration_ransac_based_on_correspondence):
+ * the rigid poses that the most of M putative correspondences (source index, target index) agree with -- the step from
+ * goicp_match_features to start poses for goicp_icp_run_batch.  The host function and the device function produce the same bits, and two
+ * device runs the same bytes.  Arithmetic is IEEE, nothing fused; fp64 operations are rounded once each and are + - * / sqrt and
+ * comparisons only.  With T = iterations (0 means 100000), K = max_poses (0 means 1), s_j / m_j the source / target point of
+ * correspondence j, and dot3(a, b) = (a_0 b_0 + a_1 b_1) + a_2 b_2:
+ *   draw    hypothesis t < T takes three distinct correspondences a, b, c: the plane operator's draw at the counters 3 t + {0, 1, 2}
+ *           (its round p = 0) over M positions;
+ *   reject  (edge_similarity = sigma > 0) in fp64 on the widened floats, for each of the edges (a, b), (b, c), (c, a): d = p_second -
+ *           p_first, ls2 = dot3(d, d) on the source points and lt2 on the target points; the hypothesis is rejected unless every edge has
+ *           min(ls2, lt2) >= (sigma sigma) max(ls2, lt2), the product sigma sigma formed once in fp64 from the widened float.  Open3D's
+ *           CorrespondenceCheckerBasedOnEdgeLength and PCL's polygon pre-rejector, without the square roots.  A rejected hypothesis scores 0;
+ *   pose    in fp64 from a cross-covariance H (target rows, source columns) and the centroids cs, ct -- one text for the hypothesis and
+ *           the refit.  For a triple: cs_k = ((sa_k + sb_k) + sc_k) / 3.0, ct likewise, H_ab = ((ma_a - ct_a)(sa_b - cs_b) +
+ *           (mb_a - ct_a)(sb_b - cs_b)) + (mc_a - ct_a)(sc_b - cs_b).  Then K = H^T H, K_ab = dot3(column a of H, column b of H); the
+ *           normals operator's cyclic Jacobi on K (rotations (0,1), (0,2), (1,2), at most 32 sweeps, the same skip and stop tests) gives
+ *           l_c = the diagonal and the columns of V; they are put in descending order of l by the exchanges (0,1), (1,2), (0,1), each made
+ *           only when the later l is strictly larger (equal values keep the lower index first).  Degenerate when !(l_1 > 0): collinear
+ *           or coincident points.  u_k = H v_k (u_ka = dot3(row a of H, v_k)), u_k /= sqrt(dot3(u_k, u_k)) for k = 0, 1;
+ *           u_1 -= dot3(u_0, u_1) u_0 and u_1 /= sqrt(dot3(u_1, u_1)) again; u_2 = u_0 x u_1 and v_2 = v_0 x v_1 (each component
+ *           x*y - z*w with both products rounded); R_ab = (float)((u0_a v0_b + u1_a v1_b) + u2_a v2_b), a proper rotation by
+ *           construction; t_a = (float)(ct_a - dot3(widened float row a of R, cs)).  A pose with a non-finite entry is degenerate.  A
+ *           degenerate hypothesis scores 0 and can never be returned;
+ *   pair    in float, left to right: y_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a, e_a = y_a - m_a, d2 = (e_0 e_0 + e_1 e_1) + e_2 e_2;
+ *           correspondence j is an inlier iff d2 <= distance * distance, the product formed once in float (a NaN compares false);
+ *   score   the exact integer count over all M correspondences; key = (count << 32) | ~t as 64 unsigned bits;
+ *   poses   the K largest keys (the largest count first, ties to the smallest t) whose count is at least max(min_inliers, 3), in
+ *           descending key order.  *n_poses may be 0, a valid result;
+ *   refit   (refine = 1, for each returned pose on its own) one least-squares refit over the pose's inliers, with exact integer moments.
+ *           Each side has the voxel operator's frame over the M points that the correspondences name on it (a point named twice counts
+ *           once for the frame): mn_k, d = x - mn_k in float, E = max d, E < 2^e by frexp; q_k = llrint(ldexp((double)d_k, 31 - e)) in
+ *           [0, 2^31).  The sums over the inliers: m (the count), Ss_b = sum qs_b, St_a = sum qt_a and P_ab = sum qt_a qs_b for the nine
+ *           pairs, the P_ab as sum (prod >> 32) and sum (prod & 0xffffffff): 25 words, each below 2^60, so the order of addition cannot
+ *           matter.  From those words, on the host in both paths: H_ab = ldexp((double)(m P_ab - St_a Ss_b), -(31 - e_s) - (31 - e_t)) /
+ *           ((double)m * (double)m), the integer formed exactly in 128 bits and converted to double correctly rounded; cs_k =
+ *           (double)mn_k + ldexp((double)Ss_k / (double)m, -(31 - e_s)), the voxel operator's centroid kept in fp64, ct likewise; then
+ *           `pose` above.  The pair re-selects against the refit pose, which is adopted iff it is not degenerate and its count is >= the
+ *           hypothesis' count; `refined` reports which stands;
+ *   output  out_poses[i]: R (row-major) and t of the pose that stands, `inliers` its count, `hypothesis` its t, `refined`;
+ *           out_inlier[j] (may be NULL; M bytes): the pair's verdict on correspondence j under out_poses[0], all 0 when there is no pose.
+ * out_poses has room for max_poses records (GOICP_RANSAC_POSE_MAX_POSES always suffices; the first *n_poses are written).  A source or
+ * target index may occur in several correspondences.  The _host form runs on the host alone (no handle, no GPU).  The handle form runs on
+ * the device: the handle lends its device and stream, its state is untouched; 56 bytes per returned pose, the refit's 200 per pose and the
+ * M verdicts come back.
+ * goicp_select_matches (host only, linear in n_q) turns goicp_match_features' output into correspondences: query q is kept iff
+ * (!require_mutual || mutual[q]) and, with ratio != 0, d2[q] <= (ratio * ratio) * d2_second[q] in float with ratio * ratio formed once
+ * (Lowe's ratio test on squared distances; a d2_second of +inf passes).  out_corr holds n_q x 2 ints; the *M kept pairs (q, index[q]) are
+ * written in ascending q.  mutual may be NULL when require_mutual == 0.
+ * goicp_ransac_pose_tile() / goicp_ransac_pose_block(): the hypotheses the device score kernel stages per LDS tile and the correspondences
+ * of one of its workgroups (tests cut their sizes around them).
+ * GOICP_ERR_INVALID, nothing written and the handle untouched: NULL arguments, M < 3, M, n_s or n_t above goicp_create's limit or a cloud
+ * of no points, an index of corr out of range, a non-finite coordinate, a distance that is <= 0, NaN or infinite, iterations outside
+ * 0..GOICP_RANSAC_POSE_MAX_ITERATIONS, max_poses outside 0..GOICP_RANSAC_POSE_MAX_POSES, refine outside 0..1, an edge_similarity outside
+ * [0, 1] or NaN, a negative min_inliers (one above M is legal and finds no pose), for the handle form any call while a registration runs;
+ * for goicp_select_matches NULL arguments (mutual only with require_mutual != 0), n_q == 0 or above the limit, a negative, NaN or infinite
+ * ratio, require_mutual outside 0..1.
+ */
+#define GOICP_RANSAC_POSE_MAX_ITERATIONS (1 << 20)
+#define GOICP_RANSAC_POSE_MAX_POSES 64
+typedef struct goicp_ransac_pose_select {
+    float    distance;         /* inlier threshold on |R s + t - m|; > 0, finite */
+    int32_t  iterations;       /* hypotheses; 0 = 100000 */
+    int32_t  refine;           /* 1 = least-squares refit over each returned pose's inliers */
+    int32_t  max_poses;        /* poses returned at most; 0 = 1 */
+    int32_t  min_inliers;      /* poses with a count below max(min_inliers, 3) are not returned */
+    float    edge_similarity;  /* 0 = no pre-rejection; else in (0, 1] (Open3D's default is 0.9) */
+    uint64_t seed;
+} goicp_ransac_pose_select;
+typedef struct goicp_ransac_pose_result {
+    float   R[9];              /* row-major: y = R x + t takes the source onto the target */
+    float   t[3];
+    int32_t inliers;
+    int32_t hypothesis;        /* the t of the hypothesis */
+    int32_t refined;           /* 1: the refit stands */
+} goicp_ransac_pose_result;
+void goicp_ransac_pose_select_default(goicp_ransac_pose_select* out);   /* refine 1, edge_similarity 0.9, the rest 0 (distance is to be set) */
+int goicp_ransac_pose_host(const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M, const goicp_ransac_pose_select* sel,
+                           goicp_ransac_pose_result* out_poses, size_t* n_poses, uint8_t* out_inlier);
+int goicp_ransac_pose(goicp_handle h, const float* src, size_t n_s, const float* tgt, size_t n_t, const int32_t* corr, size_t M,
+                      const goicp_ransac_pose_select* sel, goicp_ransac_pose_result* out_poses, size_t* n_poses, uint8_t* out_inlier);
+int goicp_select_matches(const int32_t* index, const float* d2, const float* d2_second, const uint8_t* mutual, size_t n_q, float ratio, int32_t require_mutual,
+                         int32_t* out_corr, size_t* M);
+int goicp_ransac_pose_tile(void);
+int goicp_ransac_pose_block(void);
 /* SSEThresh = mse_threshold * inlierNum and inlierNum = (int)(N * (1 - trim_fraction))
  * (src/goicp/jly_goicp.cpp:198-208; FastGoICP::sse_threshold, src/fgoicp/fgoicp.hpp:23) as the engine uses them */
 int goicp_thresholds(goicp_handle h, float* sse_threshold, int32_t* inliers);

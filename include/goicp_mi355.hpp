@@ -376,6 +376,35 @@ public:
 		if (mutual) mutual->resize(nq);
 		check(goicp_match_features(h_, query.data(), nq, target.data(), nt, index.data(), d2.data(), d2_second.data(), mutual ? mutual->data() : nullptr));
 	}
+	// match_features' output as correspondences (goicp_select_matches, host only): corr gets the M kept pairs (query, target) flat, 2 M ints;
+	// mutual may be null when require_mutual is false; ratio 0 = no ratio test; returns M
+	static size_t select_matches(const std::vector<int32_t>& index, const std::vector<float>& d2, const std::vector<float>& d2_second,
+	                             const std::vector<uint8_t>* mutual, float ratio, bool require_mutual, std::vector<int32_t>& corr)
+	{
+		const size_t nq = index.size();
+		if (d2.size() != nq || d2_second.size() != nq || (mutual && mutual->size() != nq)) throw std::invalid_argument("select_matches: one entry per query");
+		corr.resize(2 * nq);
+		size_t m = 0;
+		check(goicp_select_matches(index.data(), d2.data(), d2_second.data(), mutual ? mutual->data() : nullptr, nq, ratio, require_mutual ? 1 : 0, corr.data(), &m));
+		corr.resize(2 * m);
+		return m;
+	}
+	// RANSAC pose estimation from correspondences, on the device (goicp_ransac_pose): corr holds M pairs (source index, target index) flat;
+	// poses gets the poses found (at most sel.max_poses), inlier (may be null) the M verdicts under poses[0]; returns the number of poses
+	template <class Point3>
+	size_t ransac_pose(const std::vector<Point3>& src, const std::vector<Point3>& tgt, const std::vector<int32_t>& corr, const goicp_ransac_pose_select& sel,
+	                   std::vector<goicp_ransac_pose_result>& poses, std::vector<uint8_t>* inlier = nullptr) const
+	{
+		static_assert(sizeof(Point3) == 3 * sizeof(float), "Point3 must be three packed floats");
+		const size_t M = corr.size() / 2;
+		poses.resize(GOICP_RANSAC_POSE_MAX_POSES);
+		if (inlier) inlier->resize(M);
+		size_t c = 0;
+		check(goicp_ransac_pose(h_, reinterpret_cast<const float*>(src.data()), src.size(), reinterpret_cast<const float*>(tgt.data()), tgt.size(), corr.data(), M, &sel,
+		                        poses.data(), &c, inlier ? inlier->data() : nullptr));
+		poses.resize(c);
+		return c;
+	}
 	// the metric of every ICP this registration runs (goicp_set_icp_options): 0 point-to-point (default), 1 point-to-plane
 	void set_icp_options(int metric, int normal_k = 16)
 	{
