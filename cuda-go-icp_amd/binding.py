@@ -38,7 +38,7 @@ class CParams(C.Structure):
                 ("icp_fused", C.c_int32), ("bounds_fp16", C.c_int32), ("icp_nn_cache", C.c_int32), ("flow", C.c_int32), ("adaptive_k", C.c_int32), ("queue_cap", C.c_int32), ("device_queues", C.c_int32),
                 ("lds_tiles", C.c_int32), ("tile_spread_vox", C.c_float), ("tile_min", C.c_int32), ("stale_widen", C.c_int32), ("ub_tiebreak", C.c_int32), ("icp_point_seed", C.c_int32), ("ub_share", C.c_float), ("twin_fusion", C.c_int32), ("sort_items", C.c_int32), ("stale_compact", C.c_int32), ("stream_priority", C.c_int32), ("lanes", C.c_int32), ("lane_min_searches", C.c_int32),
                 ("bounds_order", C.c_int32), ("bounds_order_min_groups", C.c_int32), ("bounds_order_max_runs", C.c_int32), ("bounds_order_cell", C.c_float), ("bounds_order_reprobe", C.c_int32),
-                ("bounds_balance", C.c_int32), ("bounds_balance_a", C.c_float)]
+                ("bounds_balance", C.c_int32), ("bounds_balance_a", C.c_float), ("bounds_dedup", C.c_int32)]
 
 
 class CCube(C.Structure):
@@ -185,6 +185,7 @@ SYMBOLS = {
     "goicp_debug_cache_hits": (C.c_int, [_vp, _fp, _fp, C.POINTER(C.c_int64)]),
     "goicp_debug_bounds_order": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "goicp_debug_bounds_twins": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "goicp_debug_bounds_copies": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "goicp_debug_bounds_balance": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "goicp_debug_bounds_xcd_spans": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "goicp_debug_select": (C.c_int, [_vp, _fp, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),

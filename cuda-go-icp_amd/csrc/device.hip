@@ -982,7 +982,8 @@ __global__ __launch_bounds__(256) void bounds_tile_kernel(const float4* __restri
 	}
 }
 
-__global__ void bounds_finalize(const float* __restrict__ scratch, int B, int groups, int chunks, float* __restrict__ ub_out, float* __restrict__ lb_out);
+__global__ void bounds_finalize(const float* __restrict__ scratch, int B, int groups, int chunks, float* __restrict__ ub_out, float* __restrict__ lb_out,
+                                const int* __restrict__ alias, const int* __restrict__ ctl);
 // test / measurement entry: nseg searches of n <= 64 expansions each (segment i = parents[i*n .. i*n+n), rotation i)
 hipError_t launch_bounds_tile(const float4* src, int N, const DtDesc& dt, const Rot9* rots, const ParentRec* parents, const void* segs, int nseg, int n,
                               int chunks, float* scratch, float* ub, float* lb, unsigned* stats, hipStream_t stream)
@@ -994,7 +995,7 @@ hipError_t launch_bounds_tile(const float4* src, int N, const DtDesc& dt, const 
 	                   static_cast<const TileSeg*>(segs), nseg, chunks, cp, static_cast<const int*>(nullptr), static_cast<int*>(nullptr), scratch, ub, lb, stats);
 	if (chunks > 1) {
 		const int groups = nseg * n, t = groups * 2 * kGroup;
-		hipLaunchKernelGGL(bounds_finalize, dim3((t + 255) / 256), dim3(256), 0, stream, scratch, groups * kGroup, groups, chunks, ub, lb);
+		hipLaunchKernelGGL(bounds_finalize, dim3((t + 255) / 256), dim3(256), 0, stream, scratch, groups * kGroup, groups, chunks, ub, lb, (const int*)nullptr, (const int*)nullptr);
 	}
 	return hipGetLastError();
 }
@@ -1172,6 +1173,27 @@ __device__ __forceinline__ unsigned order_key(const float (&c)[3], const float (
 	}
 	return key;
 }
+// the table key of a full group: its children 0 and 7 (what group_centre reads) as raw words, rotation and coefficient included
+__device__ __forceinline__ unsigned alias_hash(const CubeRec& a, const CubeRec& b)
+{
+	const unsigned w[12] = {__float_as_uint(a.tx), __float_as_uint(a.ty), __float_as_uint(a.tz), __float_as_uint(a.delta), __float_as_uint(a.coeff), (unsigned)a.rot,
+	                        __float_as_uint(b.tx), __float_as_uint(b.ty), __float_as_uint(b.tz), __float_as_uint(b.delta), __float_as_uint(b.coeff), (unsigned)b.rot};
+	unsigned h = 0x9e3779b9u;
+#pragma unroll
+	for (int k = 0; k < 12; k++) { h = (h ^ w[k]) * 0x85ebca6bu; h ^= h >> 15; }
+	return h;
+}
+// are the eight records of two full groups the same 48 words?  raw bits: -0 against +0, or one ulp anywhere, is another expansion
+__device__ __forceinline__ bool same_records(const CubeRec* __restrict__ cubes, int ga, int gb)
+{
+	constexpr int nw = kGroup * (int)(sizeof(CubeRec) / sizeof(unsigned));
+	const unsigned* a = reinterpret_cast<const unsigned*>(cubes + (size_t)ga * kGroup);
+	const unsigned* b = reinterpret_cast<const unsigned*>(cubes + (size_t)gb * kGroup);
+	unsigned d = 0u;
+#pragma unroll
+	for (int k = 0; k < nw; k++) d |= a[k] ^ b[k];
+	return d == 0u;
+}
 // No step of the pre-pass waits on a chain of loads.  Run starts: thread t compares the rotation of groups t, t + 1024, ... with their
 // predecessors' (independent loads, all in flight together); the at most 63 boundaries take a slot of an LDS list and are ranked there.  A
 // thread keeps the centres and keys of its first kOrderHeld groups of the run in registers from the extent to the scatter (a longer run
@@ -1226,7 +1248,7 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	const int nb = nbound, runs = nb + 1;
 	if (runs > bo.max_runs) {
 		if (blockIdx.x == 0 && tid == 0) {
-			bo.ctl[0] = 0; bo.ctl[1] = 0; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1;
+			bo.ctl[0] = 0; bo.ctl[1] = 0; bo.ctl[2] = 0; bo.ctl[3] = 0; bo.ctl[kBoundsCopies] = 0; if (bo.host_note) *bo.host_note = ((long long)G << 1) | 1;
 		}
 		if (blockIdx.x == 0 && tid < 64) bounds_cuts_store(bo, balanced, (G + 1) >> 1, tid);
 		return;
@@ -1244,7 +1266,7 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 	const int s0 = run_start[run], n = run_start[run + 1] - s0;
 	int item0 = 0, items = 0;
 	for (int q = 0; q < runs; q++) { if (q == run) item0 = items; items += (run_start[q + 1] - run_start[q] + 1) >> 1; }
-	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; bo.ctl[2] = 0; bo.ctl[3] = 0; if (bo.host_note) *bo.host_note = (long long)G << 1; }
+	if (run == 0 && tid == 0) { bo.ctl[0] = items; bo.ctl[1] = 1; bo.ctl[2] = 0; bo.ctl[3] = 0; bo.ctl[kBoundsCopies] = 0; if (bo.host_note) *bo.host_note = (long long)G << 1; }
 	if (run == 0 && tid < 64) bounds_cuts_store(bo, balanced, items, tid);
 	// the extent of the run's centres (a thread without a k-th group holds the run's last one again: it changes neither the extent nor, below, a counter)
 	float held[kOrderHeld][3];
@@ -1321,6 +1343,36 @@ __global__ __launch_bounds__(1024) void bounds_order_kernel(const CubeRec* __res
 		group_centre(cubes, s0 + j, B, c);
 		place(order_key(c, lo, to_cell), j);
 	}
+	// Copies (BoundsOrder::alias): the counters are dead now and serve as an open-addressing table over the run's full groups, two 64-bit
+	// slots per group up to the 16 384 that fit.  A group hashes its children 0 and 7, claims the first empty slot of its probe sequence with a
+	// compare-and-swap of (hash, index), and on the way compares all eight of its records with those of every occupant of its hash, word for
+	// word: equal, and the occupant is its owner.  An occupant has claimed a slot, hence is its own owner; a partial last group neither claims nor compares; a group
+	// that saw kBoundsAliasProbes slots taken by others stays its own owner unlisted.  Which listing of a family owns it follows the atomics:
+	// no bound depends on it, a copy takes the sums of an evaluation of the very records it holds.
+	if (!bo.alias) return;
+	__syncthreads();
+	// an entry is (hash << 32 | index in the run): an occupant of another hash is passed without a look at its records
+	unsigned long long* table = reinterpret_cast<unsigned long long*>(lds);
+	int slots = 64;
+	while (slots < 2 * n && slots < kSortBins / 2) slots <<= 1;
+	for (int i = tid; i < slots / 2; i += 1024) reinterpret_cast<uint4*>(lds)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+	__syncthreads();
+	for (int j = tid; j < n; j += 1024) {
+		const int g = s0 + j;
+		int owner = g;
+		if (g * kGroup + kGroup <= B) {
+			const unsigned h = alias_hash(cubes[(size_t)g * kGroup], cubes[(size_t)g * kGroup + kGroup - 1]);
+			const unsigned long long mine = ((unsigned long long)h << 32) | (unsigned)j;     // never all ones: j < 2^31
+			unsigned slot = h & (unsigned)(slots - 1);
+			for (int probe = 0; probe < kBoundsAliasProbes; probe++) {
+				const unsigned long long old = atomicCAS(&table[slot], ~0ull, mine);
+				if (old == ~0ull) break;
+				if ((unsigned)(old >> 32) == h && same_records(cubes, g, s0 + (int)(unsigned)old)) { owner = s0 + (int)(unsigned)old; break; }
+				slot = (slot + 1) & (unsigned)(slots - 1);
+			}
+		}
+		bo.alias[g] = owner;
+	}
 }
 
 // the plain launch walking order[] when the pre-pass built one (bounds_order = 1): bounds_kernel<1, true> with the slot -> group table.
@@ -1372,6 +1424,9 @@ __device__ __forceinline__ bool same_box(const PairMember& a, const PairMember& 
 // rotation child list; the pre-pass puts them in one cell, hence next to each other -- have the same addresses: such an item runs
 // lean_points<1, 2, ..> once (the loop of the queue twins), or, with equal coefficients too, lean_points<1, 1, ..> once for both groups' rows.
 // Thread 0 of the item's chunk-0 workgroup counts the form in ctl[2] / ctl[3] (goicp_debug_bounds_twins).
+// COPIES -- a family listed more than twice is more than one item: over several chunks a member the pre-pass found to repeat another group
+// of its run record for record (alias[g] != g) is not evaluated at all, the other member goes alone on the plain path, and bounds_finalize
+// takes the copy's bounds from its owner's rows; the forms are tallied first, from the records, and ctl[kBoundsCopies] counts the copies.
 // A batch the pre-pass left alone (ctl[1] = 0) is evaluated here too, two groups per item in arrival order on the plain path: the grid of
 // bounds_order_items(groups, max_runs) >= (groups + 1) / 2 items covers it, and no second launch is needed.
 // The 8-chunk shape (chunks == 8) takes its units from the cuts the pre-pass left behind ctl[0..3] (bounds_cuts): block label x = work & 7
@@ -1389,7 +1444,8 @@ template <bool TRUNC>
 GOICP_BOUNDS_PAIR_HEAD(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
-    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl)
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl,
+    const int* __restrict__ alias)
 {
 	__shared__ float red[kBoundsThreads / 64][2 * kGroup];
 	const int work = blockIdx.x, total = gridDim.x;
@@ -1418,11 +1474,22 @@ GOICP_BOUNDS_PAIR_HEAD(
 		if (ga >= groups) return;
 		gb = ga + 1 < groups ? ga + 1 : -1;
 	}
+	// members the pre-pass found to be copies of another group of their run (BoundsOrder::alias; several chunks only, where bounds_finalize
+	// sums a copy's bounds from its owner's rows): bit 0 the first, bit 1 the second.  Counted like the forms, by the item's chunk-0 workgroup
+	int copy = 0;
+	if (listed && alias && chunks > 1) {
+		copy = (alias[ga] != ga ? 1 : 0) | (gb >= 0 && alias[gb] != gb ? 2 : 0);
+		if (copy && chunk == 0 && threadIdx.x == 0) atomicAdd(ctl + kBoundsCopies, (copy & 1) + (copy >> 1));
+	}
 	if (listed && gb >= 0) {
 		PairMember A, Bm;
 		int ra, rb;
 		const bool sa = pair_member(cubes, parents, ga, B, A, ra), sb = pair_member(cubes, parents, gb, B, Bm, rb);
-		if (sa && sb && ra == rb) {
+		const bool both = sa && sb && ra == rb;
+		// the forms are tallied from the records, whatever is evaluated below
+		if (both && chunk == 0 && threadIdx.x == 0 && same_box(A, Bm))
+			atomicAdd(ctl + (__float_as_uint(A.coeff) == __float_as_uint(Bm.coeff) || (A.coeff == 0.f && Bm.coeff == 0.f) ? 3 : 2), 1);
+		if (both && !copy) {
 			const Rot9 R0 = rots[ra];
 			const int p0 = chunk * chunk_pts;
 			const int p1 = p0 + chunk_pts < N ? p0 + chunk_pts : N;
@@ -1430,7 +1497,6 @@ GOICP_BOUNDS_PAIR_HEAD(
 				// coincident members: one index set, one exactness test and one set of gathers per point serve both (lean_points, which has
 				// its own checked branch: nothing is given up here); a pass of the NP = 2 loop is a separate evaluation operation for operation
 				const bool same = __float_as_uint(A.coeff) == __float_as_uint(Bm.coeff) || (A.coeff == 0.f && Bm.coeff == 0.f);
-				if (chunk == 0 && threadIdx.x == 0) atomicAdd(ctl + (same ? 3 : 2), 1);
 				float ub[kGroup], lb[kGroup];
 				if (same) {                                       // the same expansion twice: evaluated once, stored to both groups' rows
 					f2 ub2[1][4], lb2[1][4];
@@ -1496,6 +1562,8 @@ GOICP_BOUNDS_PAIR_HEAD(
 			if (bad != 3) gb = -1;
 		}
 	}
+	if (copy & 2) gb = -1;                                // a copy is not evaluated: the other member goes alone, or the workgroup leaves
+	if (copy & 1) { ga = gb; gb = -1; }
 #pragma unroll 1
 	for (int m = 0; m < 2; m++) {
 		const int g = m ? gb : ga;
@@ -1515,10 +1583,11 @@ template <bool TRUNC>
 __global__ __launch_bounds__(kBoundsThreads) void bounds_pair_kernel(
     const float4* __restrict__ src, int N, DtDesc dt, const Rot9* __restrict__ rots,
     const CubeRec* __restrict__ cubes, const ParentRec* __restrict__ parents, int B, int groups, int max_items, int chunks, int chunk_pts,
-    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl)
+    float* __restrict__ scratch, float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ pairs, int* __restrict__ ctl,
+    const int* __restrict__ alias)
 {
 	const unsigned long long t0 = wall_clock64();
-	bounds_pair_body<TRUNC>(src, N, dt, rots, cubes, parents, B, groups, max_items, chunks, chunk_pts, scratch, ub_out, lb_out, pairs, ctl);
+	bounds_pair_body<TRUNC>(src, N, dt, rots, cubes, parents, B, groups, max_items, chunks, chunk_pts, scratch, ub_out, lb_out, pairs, ctl, alias);
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		const unsigned long long t1 = wall_clock64();
@@ -1580,15 +1649,18 @@ __global__ __launch_bounds__(kBoundsThreads) void bounds_queue_kernel(
 	}
 }
 
+// alias, ctl: null, or the pair launch's (BoundsOrder::alias, ::ctl): with an order in force (ctl[1]) the rows of group g are those of alias[g],
+// the group evaluated in its place -- the same fixed chunk order over the sums of the same eight records
 __global__ void bounds_finalize(const float* __restrict__ scratch, int B, int groups, int chunks,
-                                float* __restrict__ ub_out, float* __restrict__ lb_out)
+                                float* __restrict__ ub_out, float* __restrict__ lb_out, const int* __restrict__ alias, const int* __restrict__ ctl)
 {
 	int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= groups * 2 * kGroup) return;
 	int group = t / (2 * kGroup), k = t - group * 2 * kGroup;
 	int c = group * kGroup + (k & (kGroup - 1));
 	if (c >= B) return;
-	const float* s = scratch + (size_t)group * chunks * (2 * kGroup) + k;
+	const int rows = alias && ctl[1] ? alias[group] : group;
+	const float* s = scratch + (size_t)rows * chunks * (2 * kGroup) + k;
 	float acc = 0.f;
 	for (int j = 0; j < chunks; j++) acc += s[(size_t)j * 2 * kGroup];
 	(k < kGroup ? ub_out : lb_out)[c] = acc;
@@ -1990,9 +2062,14 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 	int groups, chunks, chunk_pts;
 	bounds_shape(B, N, &groups, &chunks, &chunk_pts);
 	dim3 grid(groups * chunks), block(kBoundsThreads);
+	const int* alias = nullptr;                          // what this launch's finalize reads: set only behind a pre-pass that wrote it
+	const int* alias_ctl = nullptr;
 	if (bo && bo->mode > 0 && cubes && !parents && dt.layout == 1 && bounds_lean(dt) && groups >= bo->min_groups && bo->max_runs >= 1 && bo->max_runs <= kBoundsOrderMaxRuns) {
 		const bool balanced = bo->mode == 2 && chunks == 8 && bo->balance && bo->cost;
-		hipLaunchKernelGGL(bounds_order_kernel, dim3(bo->max_runs), dim3(1024), 0, stream, cubes, B, groups, dt, *bo, balanced ? 1 : 0);
+		BoundsOrder pre = *bo;
+		if (bo->mode != 2 || chunks == 1) pre.alias = nullptr;   // copies are skipped by the pair launch over several chunks only: elsewhere the table is not built
+		alias = pre.alias; alias_ctl = pre.alias ? bo->ctl : nullptr;
+		hipLaunchKernelGGL(bounds_order_kernel, dim3(bo->max_runs), dim3(1024), 0, stream, cubes, B, groups, dt, pre, balanced ? 1 : 0);
 		if (bo->mode == 1) {
 			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_ordered_kernel<true> : bounds_ordered_kernel<false>), grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups,
 			                   chunks, chunk_pts, scratch, ub, lb, bo->order, bo->ctl, 1);
@@ -2000,7 +2077,7 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 			const int max_items = (int)bounds_order_items(groups, bo->max_runs);
 			const int nblocks = chunks == 8 ? 8 * bounds_pair_slots(max_items, balanced) : max_items * chunks;
 			hipLaunchKernelGGL((dt.trunc > 0.f ? bounds_pair_kernel<true> : bounds_pair_kernel<false>), dim3(nblocks), block, 0, stream, src, N, dt, rots, cubes, parents,
-			                   B, groups, max_items, chunks, chunk_pts, scratch, ub, lb, bo->pairs, bo->ctl);
+			                   B, groups, max_items, chunks, chunk_pts, scratch, ub, lb, bo->pairs, bo->ctl, alias);
 		}
 	} else
 	if (dt.trunc > 0.f) {                                                // the truncated objective (DtDesc::trunc): the same four choices
@@ -2023,7 +2100,7 @@ hipError_t launch_bounds(const float4* src, int N, const DtDesc& dt, const Rot9*
 		hipLaunchKernelGGL(bounds_kernel<2>, grid, block, 0, stream, src, N, dt, rots, cubes, parents, B, groups, chunks, chunk_pts, scratch, ub, lb);
 	if (chunks > 1) {
 		int t = groups * 2 * kGroup;
-		hipLaunchKernelGGL(bounds_finalize, dim3((t + 255) / 256), dim3(256), 0, stream, scratch, B, groups, chunks, ub, lb);
+		hipLaunchKernelGGL(bounds_finalize, dim3((t + 255) / 256), dim3(256), 0, stream, scratch, B, groups, chunks, ub, lb, alias, alias_ctl);
 	}
 	return hipGetLastError();
 }

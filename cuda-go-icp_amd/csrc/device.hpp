@@ -133,19 +133,23 @@ struct BoundsOrder {
 	int mode;                    // 1 order, 2 order + pairs
 	int min_groups, max_runs;    // fewer groups, or more runs of equal rotation: the launch is the unordered one
 	float cell_vox;              // smallest Morton cell of the order, in DT voxels
-	unsigned* keys;              // [groups]
+	int* alias;                  // [groups], or null (bounds_dedup = 0).  alias[g] = the group of g's run whose eight records equal g's as raw bits and
+	                             // that the pre-pass met first (the OWNER; alias[owner] = owner): the pair launch over several chunks evaluates owners
+	                             // only and bounds_finalize sums a copy's bounds from its owner's rows.  Valid where ctl[1] = 1
 	unsigned* order;             // [groups]
 	int* pairs;                  // [2 * bounds_order_items(groups, max_runs)]: the two groups of an item, -1 = none
 	int* ctl;                    // [0] items of the pair list, [1] 1 = order and pairs are valid (0: too many runs); [2], [3] items the pair launch
 	                             // evaluated in twin form / in identical form (coincident members, bounds_pair_kernel): zeroed by the pre-pass
 	                             // [kBoundsCut .. kBoundsCut + 8] the cuts of the pair launch's 8-chunk shape (bounds_cuts), in ctl[0]'s 128-B line
+	                             // [kBoundsCopies] groups the pair launch did not evaluate, being copies (alias[g] != g): zeroed by the pre-pass
 	long long* host_note;        // pinned host memory: the pre-pass leaves (groups << 1 | left alone) there, a hint for the caller's next launch
 	const int* cost;             // [kBoundsCost + kBoundsPlan] lines[8], waves[8] of the source's eight chunks and the plan of the cuts made from
 	                             // them (launch_bounds_chunk_cost, bounds_cut_plan); null or balance = 0: equal cuts
 	int balance;                 // 1: the cuts follow the chunks' cost
 };
 constexpr int kBoundsOrderMaxRuns = 64;
-constexpr int kBoundsCut = 4, kBoundsCtlInts = 32;     // ctl[] is one 128-B line
+constexpr int kBoundsCut = 4, kBoundsCopies = 13, kBoundsCtlInts = 32;     // ctl[] is one 128-B line
+constexpr int kBoundsAliasProbes = 32;                 // slots of the pre-pass's table a group looks at before it gives up and stays its own owner
 constexpr float kBoundsBalanceA = 18.f;                // default weight of a wavefront, in lines: the fit of the spans, EXPERIMENTS R9.1
 inline size_t bounds_order_items(int groups, int max_runs) { return (size_t)(groups + 1) / 2 + (size_t)max_runs; }
 // slots per block label of the pair launch's grid: no piece of the cuts is longer than 1.25 items (bounds_cuts clamps the weights)

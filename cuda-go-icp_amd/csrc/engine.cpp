@@ -1276,7 +1276,7 @@ const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
 		border_skipped_ = 0;
 	}
 	const int max_runs = std::min(std::max(p_.bounds_order_max_runs, 1), kBoundsOrderMaxRuns);
-	// keys, order, pairs, then ctl[] on a 128-B line of its own (the buffer's base is aligned far beyond that)
+	// alias, order, pairs, then ctl[] on a 128-B line of its own (the buffer's base is aligned far beyond that)
 	const size_t items = bounds_order_items(groups, max_runs), ctl_at = (2 * (size_t)groups + 2 * items + kBoundsCtlInts - 1) / kBoundsCtlInts * kBoundsCtlInts;
 	const size_t need = ctl_at + kBoundsCtlInts;
 	if (need > d_border_.size()) {
@@ -1287,8 +1287,8 @@ const BoundsOrder* Engine::ensure_bounds_order(int B, hipStream_t s)
 	// carved for this launch: a stream runs its launches in order, and the buffer only ever grows after the streams were waited for
 	border_.mode = p_.bounds_order >= 2 ? 2 : 1;
 	border_.min_groups = p_.bounds_order_min_groups; border_.max_runs = max_runs; border_.cell_vox = p_.bounds_order_cell;
-	border_.keys = d_border_.get(); border_.order = border_.keys + groups;
-	border_.pairs = reinterpret_cast<int*>(border_.order + groups); border_.ctl = reinterpret_cast<int*>(border_.keys + ctl_at);
+	border_.alias = p_.bounds_dedup != 0 ? reinterpret_cast<int*>(d_border_.get()) : nullptr; border_.order = d_border_.get() + groups;
+	border_.pairs = reinterpret_cast<int*>(border_.order + groups); border_.ctl = reinterpret_cast<int*>(d_border_.get() + ctl_at);
 	border_.host_note = h_border_note_.get();
 	border_.cost = d_bcost_.get(); border_.balance = p_.bounds_balance != 0;
 	return &border_;
@@ -1330,6 +1330,15 @@ void Engine::debug_bounds_twins(int info[2])
 	if (border_form_ != 2) return;
 	HIPCHK(hipStreamSynchronize(border_stream_));
 	HIPCHK(hipMemcpy(info, border_.ctl + 2, 2 * sizeof(int), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_bounds_copies(int info[1])
+{
+	DeviceGuard guard(dev_);
+	info[0] = 0;
+	if (border_form_ != 2) return;
+	HIPCHK(hipStreamSynchronize(border_stream_));
+	HIPCHK(hipMemcpy(info, border_.ctl + kBoundsCopies, sizeof(int), hipMemcpyDeviceToHost));
 }
 
 void Engine::debug_bounds_balance(int info[26])

@@ -79,6 +79,9 @@ struct Params {
 	int bounds_balance = 1;               // the pair launch's 8-chunk shape: 1 a block label takes an equal share of the chunks' COST (distinct DT lines per wavefront,
 	                                      // counted once per source cloud; device.hpp bounds_cuts), 0 one chunk each.  Same bits either way
 	float bounds_balance_a = 0.f;         // tuning only: the weight of a wavefront against one DT line in that cost; <= 0: kBoundsBalanceA
+	int bounds_dedup = 1;                 // the pair launch over several point chunks: 1 an expansion a run lists more than once (all eight records equal as raw bits) is
+	                                      // evaluated once and its copies take the owner's sums (device.hip bounds_order_kernel, BoundsOrder::alias); 0 every listing is
+	                                      // evaluated.  Same bits either way
 	int twin_fusion = 1;         // the same translation node listed by both searches of a rotation child in a round is gathered once (device.hip lean_points<.., 2>)
 	int lds_tiles = 2;            // LDS-staged DT tiles for inner searches whose selected nodes lie within a few voxels of each other (deep rounds): 0 off, 1 the
 	                              // tile evaluation is launched every round, 2 only while the previous rounds had searches that qualify (default)
@@ -254,6 +257,7 @@ public:
 	// twin lists were in use.
 	void debug_bounds_order(int info[3]);   // test: form of the last eval_bounds_dev launch, and what its pre-pass decided (device.hip BoundsOrder::ctl)
 	void debug_bounds_twins(int info[2]);   // test: items of that launch evaluated in twin form and in identical form (BoundsOrder::ctl[2], [3])
+	void debug_bounds_copies(int info[1]);  // test: groups of that launch not evaluated, being copies of another group of their run (BoundsOrder::ctl[kBoundsCopies])
 	// test: the cuts of that launch and the source's chunk cost: info[0..8] cut, [9..16] lines, [17..24] waves, [25] 1 = the cuts followed the cost
 	// (pair form, 8 chunks, bounds_balance); a launch without the 8-chunk pair form reports the equal split of its items
 	void debug_bounds_balance(int info[26]);

@@ -111,7 +111,7 @@ void goicp_params_default(goicp_params* p)
 	p->icp_fused = d.icp_fused; p->bounds_fp16 = d.bounds_fp16; p->icp_nn_cache = d.icp_nn_cache; p->flow = d.flow; p->adaptive_k = d.adaptive_k; p->queue_cap = d.queue_cap; p->device_queues = d.device_queues;
 	p->lds_tiles = d.lds_tiles; p->tile_spread_vox = d.tile_spread_vox; p->tile_min = d.tile_min; p->stale_widen = d.stale_widen; p->ub_tiebreak = d.ub_tiebreak; p->icp_point_seed = d.icp_point_seed; p->ub_share = d.ub_share; p->twin_fusion = d.twin_fusion; p->sort_items = d.sort_items; p->stale_compact = d.stale_compact; p->stream_priority = d.stream_priority; p->lanes = d.lanes; p->lane_min_searches = d.lane_min_searches;
 	p->bounds_order = d.bounds_order; p->bounds_order_min_groups = d.bounds_order_min_groups; p->bounds_order_max_runs = d.bounds_order_max_runs; p->bounds_order_cell = d.bounds_order_cell; p->bounds_order_reprobe = d.bounds_order_reprobe;
-	p->bounds_balance = d.bounds_balance; p->bounds_balance_a = d.bounds_balance_a;
+	p->bounds_balance = d.bounds_balance; p->bounds_balance_a = d.bounds_balance_a; p->bounds_dedup = d.bounds_dedup;
 }
 
 void goicp_params_from_config(const goicp_config* c, goicp_params* p)
@@ -157,7 +157,7 @@ int goicp_create(const goicp_params* params, const float* target_xyz, size_t n_t
 			p.icp_fused = params->icp_fused; p.bounds_fp16 = params->bounds_fp16; p.icp_nn_cache = params->icp_nn_cache; p.flow = params->flow; p.adaptive_k = params->adaptive_k; p.queue_cap = params->queue_cap; p.device_queues = params->device_queues;
 			p.lds_tiles = params->lds_tiles; p.stale_widen = params->stale_widen; p.ub_tiebreak = params->ub_tiebreak; p.icp_point_seed = params->icp_point_seed; p.ub_share = params->ub_share; p.twin_fusion = params->twin_fusion; p.sort_items = params->sort_items; p.stale_compact = params->stale_compact; p.stream_priority = params->stream_priority; p.lanes = params->lanes; p.lane_min_searches = params->lane_min_searches;
 			p.bounds_order = params->bounds_order; p.bounds_order_min_groups = params->bounds_order_min_groups; p.bounds_order_max_runs = params->bounds_order_max_runs; p.bounds_order_reprobe = params->bounds_order_reprobe;
-			p.bounds_balance = params->bounds_balance; p.bounds_balance_a = params->bounds_balance_a;
+			p.bounds_balance = params->bounds_balance; p.bounds_balance_a = params->bounds_balance_a; p.bounds_dedup = params->bounds_dedup;
 			if (params->bounds_order_cell > 0.f) p.bounds_order_cell = params->bounds_order_cell;
 			if (params->tile_spread_vox > 0.f) p.tile_spread_vox = params->tile_spread_vox;
 			if (params->tile_min > 0) p.tile_min = params->tile_min;
@@ -611,6 +611,16 @@ int goicp_debug_bounds_twins(goicp_handle h, int32_t info[2])
 		int inf[2] = {0, 0};
 		h->e->debug_bounds_twins(inf);
 		info[0] = inf[0]; info[1] = inf[1];
+	});
+}
+
+int goicp_debug_bounds_copies(goicp_handle h, int32_t info[1])
+{
+	REQUIRE(h && info);
+	return guarded([&] {
+		int inf[1] = {0};
+		h->e->debug_bounds_copies(inf);
+		info[0] = inf[0];
 	});
 }
 

@@ -205,6 +205,9 @@ typedef struct goicp_params {
 	                                  * XCD) take equal shares of the chunks' COST -- the distinct distance-transform lines a wavefront of the chunk gathers, counted on
 	                                  * the device once per source cloud -- instead of one chunk each; 0: one chunk each.  Scheduling only: same bits either way */
 	float bounds_balance_a;          /* tuning only: the weight of a wavefront against one line in that cost (<= 0: the default) */
+	int32_t bounds_dedup;            /* default 1.  Form 2 over a cloud cut into several point chunks: an expansion that a run of equal rotation lists more than once --
+	                                  * all eight cube records equal as raw bits, as the root expansion listed by every inner search of a rotation -- is evaluated
+	                                  * once, and the other listings take its sums; 0: every listing is evaluated.  Same bits either way */
 } goicp_params;
 
 void goicp_params_default(goicp_params* p);
@@ -1218,6 +1221,10 @@ int goicp_debug_bounds_order(goicp_handle h, int32_t info[3]);
  * per point, a sum per coefficient), info[1] = items whose coefficients were equal as well (evaluated once, stored to both).  Both 0 for the
  * other forms and for a batch the pre-pass left alone. */
 int goicp_debug_bounds_twins(goicp_handle h, int32_t info[2]);
+/* goicp_debug_bounds_copies (test): info[0] = the groups of the same last call that the pair launch (form 2, several point chunks,
+ * bounds_dedup on) did not evaluate because their eight records repeat, bit for bit, those of another group of their run, whose sums they
+ * took.  0 for the other forms, for one point chunk, for a batch the pre-pass left alone and with bounds_dedup = 0. */
+int goicp_debug_bounds_copies(goicp_handle h, int32_t info[1]);
 /* goicp_debug_bounds_balance (test): the mapping of the same last call.  info[0..8] = the cuts: block label x evaluated the units
  * cut[x] .. cut[x + 1] - 1 of the list u = chunk * items + item (cut[8] = 8 items); info[9..16] = lines and info[17..24] = waves of the
  * source's eight chunks (all 0 for a cloud of fewer than 7 937 points, whose cuts are the equal split); info[25] = 1 when the launch was

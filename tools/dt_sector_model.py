@@ -32,9 +32,11 @@ whose members have the same depth.
 --twins: the COINCIDENT items of the pair launch (bounds_pair_kernel: both members of an item with the same six translations and delta,
 bit for bit) when the order inside a Morton cell is random, for the bench batch and for a batch shaped like the two inner searches of a
 rotation child (search_shaped_batch): items any order could give at most (floor(family / 2) per family of equal expansions in a run), the
-items --trials random tie orders capture (mean, min, max), and how many two-member families share their cell with anything else.
+items --trials random tie orders capture (mean, min, max), and how many two-member families share their cell with anything else.  Beside
+them ("dedup", dedup_mode) the COPIES the pre-pass finds (bounds_order_kernel's alias table: a full group whose eight records repeat another
+group's of its run as raw bytes): groups, distinct groups per run, and the sets of eight gathers per point chunk before and after.
 
-  python3 tools/dt_sector_model.py --twins [--trials 200] [--json profiles/r08_twin_tie_order_model.json]
+  python3 tools/dt_sector_model.py --twins [--trials 200] [--json profiles/r08_twin_tie_order_model.json | profiles/r12_dedup_model.json]
 
 --chunks: what each of the pair launch's eight point chunks costs: distinct 128-B lines per 64-lane gather and the chunk's share of the lines,
 over random rotations x 12 sibling expansions; the spread of that share over the rotations; the same at the identity pose; and the device's
@@ -224,6 +226,27 @@ def twins_mode(recs, scale, cell, trials, seed):
             "two_member_families": two_member, "two_member_families_sharing_their_cell": shared, "trials": trials,
             "captured_mean": round(float(caught.mean()), 1), "captured_min": int(caught.min()), "captured_max": int(caught.max()),
             "captured_share_mean": round(float(caught.mean()) / max(eligible, 1), 4), "captured_share_min": round(float(caught.min()) / max(eligible, 1), 4)}
+
+
+def dedup_mode(recs, twins):
+    """bounds_order_kernel's copies (BoundsOrder::alias): per run of equal rotation the full groups whose eight records repeat an earlier group's,
+    all 192 bytes.  Gather sets per point chunk: today a coincident item (twins["captured_mean"], the same for every tie order on these batches)
+    gathers once for its two groups and every other group once for itself; after, no expansion is gathered for more than once -- at most
+    the distinct ones, and never more than today (owners that still meet as twins share a set as before)"""
+    g = len(recs) // 8
+    raw = np.ascontiguousarray(recs[:8 * g]).view(np.uint8).reshape(g, 192)
+    rot = recs["rot"][0:8 * g:8]
+    starts = np.flatnonzero(np.concatenate([[True], rot[1:] != rot[:-1]]))
+    bounds = np.concatenate([starts, [g]])
+    distinct = [len({row.tobytes() for row in raw[s:e]}) for s, e in zip(bounds[:-1], bounds[1:])]
+    roots = np.flatnonzero(recs["delta"][0:8 * g:8] == recs["delta"].max())            # width 1 has one position: the root expansion
+    root_distinct = len({raw[i].tobytes() for i in roots})
+    outside = g - sum(distinct) - (len(roots) - root_distinct)
+    before = g - int(round(twins["captured_mean"]))          # a coincident item saves one of its two sets
+    return {"groups": int(g), "runs": int(len(starts)), "distinct_groups_per_run": distinct, "distinct_groups": int(sum(distinct)),
+            "copies": int(g - sum(distinct)), "root_listings": int(len(roots)), "distinct_root_expansions": int(root_distinct),
+            "copies_outside_the_roots": int(outside), "gather_sets_before": int(before), "gather_sets_after": int(min(before, sum(distinct))),
+            "ratio": round(min(before, sum(distinct)) / max(before, 1), 4)}
 
 
 def lines_mode(a, rots, recs, src, mn, scale, V):
@@ -420,6 +443,19 @@ def main():
         out = {"cell_vox": a.cell, "voxels_per_unit": round(float(scale), 2),
                "bench_batch": dict(batch="bench.make_batch(8192 expansions, 8 rotations, seed 1234)", **twins_mode(recs, scale, a.cell, a.trials, 0)),
                "search_shaped_batch": dict(batch="search_shaped_batch(64 runs, seed 1): 7 + 16 expansions per run", **twins_mode(search_shaped_batch(64, 1), scale, a.cell, a.trials, 0))}
+
+        class _RegLevels(_Reg):                              # the copies are told apart by the coefficient too: one value per rotation level, as the engine's table has
+            @staticmethod
+            def rot_coeff(level):
+                return np.float32(2.0 * np.sin(min(np.sqrt(3.0) * np.pi / (1 << level), np.pi) / 2.0))
+
+        levelled = bench.make_batch(pkg, _RegLevels(), 8192, 8, seed=1234)[1]
+        out["bench_batch"]["dedup"] = dedup_mode(levelled, out["bench_batch"])
+        out["search_shaped_batch"]["dedup"] = dedup_mode(search_shaped_batch(64, 1), out["search_shaped_batch"])
+        for name in ("bench_batch", "search_shaped_batch"):
+            d = out[name]["dedup"]
+            print("%s: groups / distinct %d / %d, gather sets per point chunk %d -> %d (%.3f)" % (name, d["groups"], d["distinct_groups"], d["gather_sets_before"],
+                                                                                                d["gather_sets_after"], d["ratio"]), file=sys.stderr)
         print(json.dumps(out, indent=1))
         if a.json:
             with open(a.json, "w") as f:
