@@ -142,6 +142,23 @@ class CPoseInfo(C.Structure):
                 ("sigma2", C.c_double), ("inliers", C.c_int64), ("rank", C.c_int32), ("metric", C.c_int32), ("dof_nonpositive", C.c_int32)]
 
 
+class CQueueSearch(C.Structure):      # goicp_queue_search (test hook goicp_debug_queue_round)
+    _fields_ = [("best", C.c_float), ("coeff", C.c_float), ("rot", C.c_int32), ("count", C.c_int32), ("done", C.c_int32), ("improved", C.c_int32),
+                ("n_parents", C.c_int32), ("parent_off", C.c_int32), ("pops", C.c_int32), ("cubes", C.c_int32), ("bx", C.c_float), ("by", C.c_float),
+                ("bz", C.c_float), ("bw", C.c_float), ("tile", C.c_int32), ("min_ub", C.c_float), ("deep", C.c_int32), ("stale", C.c_int32),
+                ("twin", C.c_int32)]
+
+
+class CQueueRound(C.Structure):       # goicp_queue_round
+    _fields_ = [("nsearch", C.c_int32), ("parity", C.c_int32), ("deep", C.c_int32), ("chunks", C.c_int32), ("n_prev_list", C.c_int32),
+                ("thr", C.c_float), ("K", C.c_int32), ("kmax", C.c_int32), ("cap", C.c_int32), ("list_cap", C.c_int32), ("soft_overflow", C.c_int32),
+                ("root", C.c_float * 4), ("boxed", C.c_int32), ("depth", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("stale_widen", C.c_int32), ("stale_compact", C.c_int32), ("tile_spread", C.c_float), ("tile_min", C.c_int32)]
+
+
+QUEUE_SLAB = 8192
+
+
 class CShardOptions(C.Structure):
     _fields_ = [("rot_pops_per_step", C.c_int32), ("rebalance", C.c_int32), ("stale_exchange", C.c_int32), ("ramp_to", C.c_int32)]
 
@@ -181,6 +198,8 @@ SYMBOLS = {
     "goicp_debug_queue_expand": (C.c_int, [C.c_void_p, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
     "goicp_debug_queue_expand_tiles": (C.c_int, [C.c_void_p, _fp, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), C.c_int32, _fp,
                                                  C.POINTER(C.c_int32), _fp, _fp]),
+    "goicp_debug_queue_round": (C.c_int, [C.c_void_p, C.POINTER(CQueueRound), C.POINTER(CQueueSearch), _fp, C.c_void_p, _fp, _fp, _fp, C.POINTER(C.c_int32),
+                                          C.c_void_p, C.POINTER(C.c_int32)]),
     "goicp_debug_bounds_tile": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     "goicp_debug_cache_hits": (C.c_int, [_vp, _fp, _fp, C.POINTER(C.c_int64)]),
     "goicp_debug_bounds_order": (C.c_int, [_vp, C.POINTER(C.c_int32)]),

@@ -20,6 +20,10 @@
 // position, so a run is bit-reproducible.  Pruning uses the incumbent after ALL children of the round are known
 // (the reference updates it child by child): never prunes a node the reference would keep alive for a valid reason,
 // only more of them -- any expansion order of a best-first BnB keeps the bounds valid.
+// A search that stops stores its incumbent and its count, but not stale, deep or parent_off (they go with a listing); one that leaves by an
+// overflow exit stores none of them, and its queue is not defined afterwards: the host re-runs it from its original incumbent.
+// One round is held to an independent model, byte for byte: goicp_debug_queue_round (engine.cpp) launches this kernel alone on given state,
+// tests/queue_round_twin.py states the round as data operations, tests/test_gpu_queue_round.py compares the two.
 #include <hip/hip_runtime.h>
 
 #include "device.hpp"
@@ -86,7 +90,7 @@ __device__ __forceinline__ void queue_round(QShared& sh, QSearch* __restrict__ S
 	int stale = S->stale;
 	const int n_prev = S->n_parents;
 	// ------------------------------------------------------------------------------------------------------------
-	// digest: the bounds of the children evaluated in the previous round (8 per expansion, <= 256 children)
+	// digest: the bounds of the children evaluated in the previous round (8 per expansion, up to 512 expansions: 1 024 children per pass)
 	// ------------------------------------------------------------------------------------------------------------
 	if (n_prev > 0) {
 		const int Ctot = 8 * n_prev, off = S->parent_off;
@@ -267,7 +271,11 @@ __device__ __forceinline__ void queue_round(QShared& sh, QSearch* __restrict__ S
 				key[j] = node_key(nd.lb, node_depth(qp.root_w, nd.w));
 		} else { lbv[j] = INFINITY; key[j] = 0xffffffffu; }
 	}
-	// smallest key and the stop rule on it (jly_goicp.cpp:257): nothing left that could close the gap -> done
+	// smallest key and the stop rule on it (jly_goicp.cpp:257): nothing left that could close the gap -> done.  Of several nodes that share the
+	// smallest (truncated) key, the one asked is whichever the ties below leave in place (strict <: the lowest slot of a thread, then a butterfly
+	// over the lanes, then the lowest wavefront) -- a fixed choice, but NOT the first in queue order, at any queue length.  It matters only when
+	// those nodes disagree on the rule, i.e. the gap is closed to within the key's truncation (2^-19 relative): a search may then stop although
+	// the first of them in queue order would have passed (tests/test_gpu_queue_round.py::test_select_stop_rule)
 	unsigned kmin = 0xffffffffu;
 	float lbmin = INFINITY;
 #pragma unroll
@@ -415,8 +423,8 @@ __device__ __forceinline__ void queue_round(QShared& sh, QSearch* __restrict__ S
 	__syncthreads();
 	const int n_sel = sh.n_sel;
 	if (n_sel == 0) {
-		// only possible when nodes share the smallest (truncated) key and the first of them in queue order misses the
-		// stop rule by a rounding: the gap is closed to within 2^-19 relative -> done
+		// only possible when nodes share the smallest (truncated) key, the one asked above passed the stop rule and the ones selected -- the
+		// first of them in queue order -- miss it by a rounding: the gap is closed to within 2^-19 relative -> done
 		if (tid == 0) { S->best = best; S->count = n; S->n_parents = 0; S->done = 1; S->pops += 1; }
 		return;
 	}

@@ -2565,6 +2565,84 @@ void Engine::debug_queue_expand_tiles(const float R[9], int level, const float* 
 	}
 }
 
+void Engine::debug_queue_round(const goicp_queue_round& rp, goicp_queue_search* searches, float* nodes, const void* prev_parents, const float* prev_ub,
+                               const float* prev_lb, const float* prev_scratch, int32_t ctl[6], void* listed, int32_t* parent_search)
+{
+	static_assert(sizeof(goicp_queue_search) == sizeof(QSearch) && offsetof(goicp_queue_search, twin) == offsetof(QSearch, twin) &&
+	              offsetof(goicp_queue_search, min_ub) == offsetof(QSearch, min_ub), "goicp_queue_search is QSearch");
+	static_assert(GOICP_QUEUE_SLAB == kQueueCap && sizeof(QNode) == 6 * sizeof(float), "a slab of six-float nodes");
+	// everything the kernel turns into an address is checked here: it trusts its host
+	const auto bad = [](const char* what) { throw std::invalid_argument(std::string("goicp: debug_queue_round: ") + what); };
+	const int ns = rp.nsearch, npl = rp.n_prev_list;
+	if (ns < 1 || ns > 8 || (rp.parity != 0 && rp.parity != 1) || (rp.deep != 0 && rp.deep != 1)) bad("nsearch 1..8, parity and deep 0 / 1");
+	if (rp.K < 1 || rp.K > kQueueMaxPop || rp.kmax < 1) bad("K 1..512, kmax >= 1");
+	if (rp.cap < 1 || rp.cap > kQueueCap) bad("cap 1..8192");
+	if (rp.list_cap < 1 || rp.list_cap > 65536 || npl < 0 || npl > rp.list_cap) bad("list_cap 1..65536, n_prev_list 0..list_cap");
+	if (rp.chunks < 1 || rp.chunks > 1024) bad("chunks 1..1024");
+	if (rp.stale_widen < 0 || rp.stale_widen > 3 || rp.stale_compact < 0 || rp.depth < 0 || rp.tile_min < 0) bad("stale_widen 0..3; stale_compact, depth, tile_min >= 0");
+	if (!(rp.root[3] > 0.f) || !std::isfinite(rp.root[3]) || !std::isfinite(rp.thr)) bad("a finite threshold and a positive finite root width");
+	if (npl > 0 && (!prev_parents || (rp.chunks == 1 ? !(prev_ub && prev_lb) : !prev_scratch))) bad("the previous list or its bounds are missing");
+	if (ctl[rp.parity] < 0 || ctl[rp.parity] > rp.list_cap) bad("n_groups of this parity outside the list");
+	for (int s = 0; s < ns; s++) {
+		const goicp_queue_search& q = searches[s];
+		if (q.count < 0 || q.count > rp.cap) bad("a queue longer than cap");
+		if (q.done < 0 || q.done > 2 || q.tile != 0 || q.stale < 0 || q.stale > (1 << 20)) bad("done 0..2, tile 0, stale 0..2^20");
+		if (q.n_parents < 0 || q.n_parents > kQueueMaxPop || (q.n_parents > 0 && (q.parent_off < 0 || q.parent_off > npl - q.n_parents)))
+			bad("previous expansions outside the previous list");
+	}
+	DeviceGuard guard(dev_);
+	const size_t nprev = (size_t)std::max(npl, 1), ncap = (size_t)rp.list_cap;
+	Buf<QSearch> d_search((size_t)ns);
+	Buf<QNode> d_nodes((size_t)ns * kQueueCap);
+	Buf<ParentRec> d_prev(nprev), d_list(ncap);
+	Buf<float> d_ub(nprev * kGroup), d_lb(nprev * kGroup), d_scratch(nprev * (size_t)rp.chunks * 2 * kGroup);
+	Buf<int> d_psearch(ncap);
+	Buf<QCtl> d_ctl(1);
+	QParams qp{};
+	qp.thr = rp.thr; qp.K = rp.K; qp.kmax = rp.kmax; qp.list_cap = rp.list_cap; qp.seg_cap = 0;
+	qp.root_x = rp.root[0]; qp.root_y = rp.root[1]; qp.root_z = rp.root[2]; qp.root_w = rp.root[3];
+	qp.boxed = rp.boxed; qp.depth = rp.depth; qp.cap = rp.cap; qp.soft_overflow = rp.soft_overflow;
+	for (int k = 0; k < 3; k++) { qp.lo[k] = rp.lo[k]; qp.hi[k] = rp.hi[k]; }
+	qp.tile_on = 0; qp.tile_min = rp.tile_min; qp.tile_spread = rp.tile_spread;
+	qp.stale_widen = rp.stale_widen; qp.stale_compact = rp.stale_compact;
+	QCtl c{};
+	c.n_groups[0] = ctl[0]; c.n_groups[1] = ctl[1]; c.n_active[0] = ctl[2]; c.n_active[1] = ctl[3]; c.overflow = ctl[4]; c.tile_hint = ctl[5];
+	c.chunks = rp.chunks; c.tile_chunks = 1;
+	// what the kernel does not write reads back as all-ones bits (NaN, -1); so do the bounds the caller did not give
+	HIPCHK(hipMemsetAsync(d_list.get(), 0xff, sizeof(ParentRec) * ncap, stream_));
+	HIPCHK(hipMemsetAsync(d_psearch.get(), 0xff, sizeof(int) * ncap, stream_));
+	HIPCHK(hipMemsetAsync(d_ub.get(), 0xff, sizeof(float) * nprev * kGroup, stream_));
+	HIPCHK(hipMemsetAsync(d_lb.get(), 0xff, sizeof(float) * nprev * kGroup, stream_));
+	HIPCHK(hipMemsetAsync(d_scratch.get(), 0xff, sizeof(float) * nprev * (size_t)rp.chunks * 2 * kGroup, stream_));
+	HIPCHK(hipMemsetAsync(d_prev.get(), 0xff, sizeof(ParentRec) * nprev, stream_));
+	if (npl > 0) {
+		HIPCHK(hipMemcpyAsync(d_prev.get(), prev_parents, sizeof(ParentRec) * (size_t)npl, hipMemcpyHostToDevice, stream_));
+		if (rp.chunks == 1) {
+			HIPCHK(hipMemcpyAsync(d_ub.get(), prev_ub, sizeof(float) * (size_t)npl * kGroup, hipMemcpyHostToDevice, stream_));
+			HIPCHK(hipMemcpyAsync(d_lb.get(), prev_lb, sizeof(float) * (size_t)npl * kGroup, hipMemcpyHostToDevice, stream_));
+		} else
+			HIPCHK(hipMemcpyAsync(d_scratch.get(), prev_scratch, sizeof(float) * (size_t)npl * rp.chunks * 2 * kGroup, hipMemcpyHostToDevice, stream_));
+	}
+	HIPCHK(hipMemcpyAsync(d_search.get(), searches, sizeof(QSearch) * (size_t)ns, hipMemcpyHostToDevice, stream_));
+	for (int s = 0; s < ns; s++)
+		if (searches[s].count > 0)
+			HIPCHK(hipMemcpyAsync(d_nodes.get() + (size_t)s * kQueueCap, nodes + (size_t)s * kQueueCap * 6, sizeof(QNode) * (size_t)searches[s].count, hipMemcpyHostToDevice, stream_));
+	HIPCHK(hipMemcpyAsync(d_ctl.get(), &c, sizeof(QCtl), hipMemcpyHostToDevice, stream_));
+	HIPCHK(launch_bnb_queue(d_search.get(), d_nodes.get(), ns, qp, d_prev.get(), d_list.get(), d_ub.get(), d_lb.get(), d_scratch.get(), d_ctl.get(), rp.parity, stream_,
+	                        nullptr, parent_search ? d_psearch.get() : nullptr, rp.deep != 0));
+	HIPCHK(hipMemcpyAsync(searches, d_search.get(), sizeof(QSearch) * (size_t)ns, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(&c, d_ctl.get(), sizeof(QCtl), hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipMemcpyAsync(listed, d_list.get(), sizeof(ParentRec) * ncap, hipMemcpyDeviceToHost, stream_));
+	if (parent_search) HIPCHK(hipMemcpyAsync(parent_search, d_psearch.get(), sizeof(int) * ncap, hipMemcpyDeviceToHost, stream_));
+	HIPCHK(hipStreamSynchronize(stream_));
+	for (int s = 0; s < ns; s++) {
+		const int cnt = searches[s].count;
+		if (cnt < 0 || cnt > rp.cap) throw std::logic_error("goicp: debug_queue_round: the kernel left a queue longer than cap");
+		if (cnt > 0) HIPCHK(hipMemcpy(nodes + (size_t)s * kQueueCap * 6, d_nodes.get() + (size_t)s * kQueueCap, sizeof(QNode) * (size_t)cnt, hipMemcpyDeviceToHost));
+	}
+	ctl[0] = c.n_groups[0]; ctl[1] = c.n_groups[1]; ctl[2] = c.n_active[0]; ctl[3] = c.n_active[1]; ctl[4] = c.overflow; ctl[5] = c.tile_hint;
+}
+
 void Engine::debug_select(const float* d2, size_t n, int num, int kernel, unsigned char* include)
 {
 	if (n < 1 || n > 0x7fffffffu || num < 1 || (size_t)num > n || kernel < 0 || kernel > 2 || (kernel == 1 && n > 32768))

@@ -278,6 +278,11 @@ public:
 	};
 	void debug_queue_expand_tiles(const float R[9], int level, const float* parents4, int n, int n_ub, float* ub0, float* lb0, float* ub1, float* lb1, int info[4],
 	                              const QueueDigest* dg);
+	// test: launch_bnb_queue once on caller-given searches, queues, previous list and children's bounds (goicp_debug_queue_round, goicp_mi355.h),
+	// in device buffers of the call's own: no bound evaluation, no cloud, no distance transform; the engine's lanes, lists and counters are not
+	// touched.  std::invalid_argument before any launch for arguments outside the documented ranges
+	void debug_queue_round(const goicp_queue_round& rp, goicp_queue_search* searches, float* nodes, const void* prev_parents, const float* prev_ub,
+	                       const float* prev_lb, const float* prev_scratch, int32_t ctl[6], void* listed, int32_t* parent_search);
 	// measurement / test: the 8 children of nseg x n expansions (segment i: rotation i, parents4[(i*n + e)*4 ..] = corner xyz + width) through
 	// the LDS-tile kernel and through the direct kernel; out arrays hold 8*nseg*n floats each; ms[0] tile, ms[1] direct (per launch)
 	void debug_bounds_tile(const float* rots9, const float* parents4, int nseg, int n, int level, int chunks, float* ub_tile, float* lb_tile,

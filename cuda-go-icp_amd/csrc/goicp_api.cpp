@@ -594,6 +594,14 @@ int goicp_debug_queue_expand_tiles(goicp_handle h, const float R[9], int32_t lev
 	});
 }
 
+int goicp_debug_queue_round(goicp_handle h, const goicp_queue_round* round, goicp_queue_search* searches, float* nodes, const void* prev_parents,
+                            const float* prev_ub, const float* prev_lb, const float* prev_scratch, int32_t ctl[6], void* listed,
+                            int32_t* parent_search)
+{
+	REQUIRE(h && round && searches && nodes && ctl && listed);
+	return guarded([&] { h->e->debug_queue_round(*round, searches, nodes, prev_parents, prev_ub, prev_lb, prev_scratch, ctl, listed, parent_search); });
+}
+
 int goicp_debug_bounds_order(goicp_handle h, int32_t info[3])
 {
 	REQUIRE(h && info);

@@ -1210,6 +1210,52 @@ int goicp_debug_queue_expand(goicp_handle h, const float R[9], int32_t level, co
 int goicp_debug_queue_expand_tiles(goicp_handle h, const float R[9], int32_t level, const float* parents4, int32_t n, int32_t n_ub, float* ub_ubpass,
                                    float* lb_ubpass, float* ub_lbpass, float* lb_lbpass, int32_t info[4], int32_t digest, float* queue_nodes,
                                    int32_t* queue_counts, float* listed4, float* search8);
+/*
+ * goicp_debug_queue_round (test): ONE launch of the queue kernel (bnb_queue_kernel, csrc/bnbqueue.hip) on caller-given state and nothing
+ * else -- no bound evaluation: the caller supplies the bounds of the previous round's children.  The call works on device buffers of its
+ * own; of the handle it uses the device and the stream, and leaves its lanes, lists and counters alone.
+ *   goicp_queue_search   the device's record of one inner search, field for field (csrc/device.hpp QSearch); in: the search before the
+ *                        round (count <= cap queued nodes, n_parents <= 512 expansions of the previous round at parent_off of the previous
+ *                        list, tile 0), out: the record after it.
+ *   goicp_queue_round    the round: nsearch (1..8) searches = workgroups; parity (0 / 1) of the list the round writes; deep 0 / 1 = the 128- /
+ *                        64-VGPR build; chunks = point chunks of the previous evaluation (1: prev_ub / prev_lb hold the children's bounds,
+ *                        8 per record of the previous list; > 1: prev_scratch holds chunk partials [record][chunk][ub 8 | lb 8] and the
+ *                        digest adds them); n_prev_list (<= list_cap) = records of the previous list; the other fields are QParams' of the
+ *                        same names (K 1..512, cap 1..8 192, list_cap 1..65 536; root = corner xyz + width).  No tile buffers: nothing is
+ *                        listed in the tile list, QSearch::deep and ctl's tile_hint still report the spread decision.
+ *   nodes                [nsearch][8 192][6] floats (corner xyz, width, ub, lb); in: the first `count` nodes of every queue, out: the first
+ *                        `count` nodes afterwards (the rest of a slab is not touched on the host)
+ *   prev_parents         n_prev_list records {float x, y, z, w, coeff; int32 rot} (may be null when n_prev_list = 0, as prev_ub / prev_lb /
+ *                        prev_scratch, of which only the one `chunks` selects is read)
+ *   ctl                  in / out: {n_groups[0], n_groups[1], n_active[0], n_active[1], overflow, tile_hint} of the control block
+ *   listed               out, list_cap records of the same form: the list of this round; a record the kernel did not write is all-ones bits
+ *                        (NaN floats, rot -1)
+ *   parent_search        out, list_cap words (-1 where not written), or null: the kernel is launched without that array
+ * GOICP_ERR_INVALID, before any launch, on arguments outside these ranges.
+ */
+#define GOICP_QUEUE_SLAB 8192
+typedef struct goicp_queue_search {
+	float best, coeff;
+	int32_t rot, count, done, improved, n_parents, parent_off, pops, cubes;
+	float bx, by, bz, bw;
+	int32_t tile;
+	float min_ub;
+	int32_t deep, stale, twin;
+} goicp_queue_search;
+typedef struct goicp_queue_round {
+	int32_t nsearch, parity, deep, chunks, n_prev_list;
+	float thr;
+	int32_t K, kmax, cap, list_cap, soft_overflow;
+	float root[4];
+	int32_t boxed, depth;
+	float lo[3], hi[3];
+	int32_t stale_widen, stale_compact;
+	float tile_spread;
+	int32_t tile_min;
+} goicp_queue_round;
+int goicp_debug_queue_round(goicp_handle h, const goicp_queue_round* round, goicp_queue_search* searches, float* nodes, const void* prev_parents,
+                            const float* prev_ub, const float* prev_lb, const float* prev_scratch, int32_t ctl[6], void* listed,
+                            int32_t* parent_search);
 /* goicp_debug_bounds_order (test): how the last goicp_eval_bounds_device / goicp_time_bounds_device launch of this handle walked its batch.
  * info[0] = the form launched (goicp_params::bounds_order: 0 the plain launch -- switch off, fewer groups than bounds_order_min_groups, not
  * a bricked fp32 grid in the Infinity Cache --, 1 ordered, 2 ordered + pairs); for forms 1 and 2, read back after the launch has finished:
